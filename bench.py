@@ -381,20 +381,38 @@ def run_single(args, cfg, path):
     prompt[0] = 1
     logits = m.eval(prompt, 0, args.threads)
     first, n_past = int(np.argmax(logits)), len(prompt)
-    steps = min(args.steps, args.n_ctx - n_past - args.warmup)
+    steps = args.steps
+    window = args.n_ctx - n_past - args.warmup          # context positions left after the warm-up
+    if window < 1:
+        raise SystemExit(f"--warmup {args.warmup} leaves no room in n_ctx {args.n_ctx} after the {n_past}-token prompt")
     tok, warm = first, np.zeros(0, np.int32)
     if args.warmup > 0:
         warm = m.decode_greedy(tok, n_past, args.warmup, args.threads)
         tok, n_past = int(warm[-1]), n_past + args.warmup
+    # --steps is the number of timed steps: more steps than the context holds decode the same window again from the same token and
+    # position (the KV rows are rewritten with the same values), so every call repeats the work of the first
+    dump = args.dump_outputs is not None
+    calls, last_logits = [], None
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    out = m.decode_greedy(tok, n_past, steps, args.threads)       # synchronises before returning
+    for c0 in range(0, steps, window):
+        got = m.decode_greedy(tok, n_past, min(window, steps - c0), args.threads, want_logits=dump)       # synchronises before returning
+        if dump:
+            got, last_logits = got
+        calls.append(got)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    out = calls[0]
+    if dump:
+        # what a caller of the timed path received from its last call: the greedy tokens and the logits of the last step
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), calls[-1].astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits.astype(np.float32))
+        log(f"[bench] wrote tokens.npy ({len(calls[-1])}) and logits.npy ({len(last_logits)}) to {args.dump_outputs}")
     gpu_trace = [int(x) for x in warm] + [int(x) for x in out]     # every token generated after the prompt's pick `first` (extended by the full-context run below)
     # PCIe-inclusive variant: the reference boundary (llama_eval returning host logits every token); its tokens must
     # be those of the device-resident loop
-    n_pcie = min(64, steps)
+    n_pcie = min(64, len(out))
     t1 = time.perf_counter()
     tk, pcie_toks = tok, []
     for i in range(n_pcie):
@@ -453,7 +471,7 @@ def run_single(args, cfg, path):
         t_ = int(np.argmax(lg0))
         _, last = m.decode_greedy(t_, len(prompt), n_tokens, args.threads, want_logits=True)
         return last
-    res = dict(steps=steps, dt=dt, t_load=t_load, value_pcie=n_pcie / dt_pcie, pcie_same=pcie_same, shapes=shapes,
+    res = dict(steps=steps, window=len(out), dt=dt, t_load=t_load, value_pcie=n_pcie / dt_pcie, pcie_same=pcie_same, shapes=shapes,
                gemv_bytes_per_token=tot_bytes, gemv_us_per_token=tot_us, prefill=prefill, first=first, gpu_trace=gpu_trace,
                n_past0=n_past, gpu_logits_at=gpu_logits_at, model=m, full=full)
     return res
@@ -1000,7 +1018,7 @@ def prefill_2048(args, cfg, path):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=496)
+    ap.add_argument("--steps", type=int, default=496, help="timed decode steps (one token each); more than the context holds repeat its window")
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--model", default=os.environ.get("LLAMAHIP_BENCH_MODEL", "7B"), choices=sorted(MODELS))
     ap.add_argument("--n_ctx", type=int, default=512)
@@ -1013,11 +1031,15 @@ def main():
     ap.add_argument("--no-prefill-2048", action="store_true")
     ap.add_argument("--no-concurrent", action="store_true", help="skip the concurrent-sequences leg (2 and 4 independent sequences on the one GPU)")
     ap.add_argument("--save-profile", default="", help="write the in-situ kernel table (rocprofv3 summary) to this file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed call returned to DIR: tokens.npy (float64) and the last step's logits.npy (float32)")
     ap.add_argument("--insitu-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--insitu-stage-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--stage-layers", type=int, default=0, help=argparse.SUPPRESS)
     ap.add_argument("--stage-set", type=int, default=1, help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1029,9 +1051,8 @@ def main():
         return insitu_stage_child(args, cfg, model_path(args.model, cfg, args.seed))
 
     if world > 1 or args.gpus > 1 or os.environ.get("LLAMAHIP_FORCE_PIPELINE"):      # FORCE: exercise the N > 1 code path on one GPU
-        # every stream of a rank (compute, one per RCCL communicator) gets its own hardware queue, so
-        # a point-to-point kernel waiting for its peer can never sit in front of unrelated work
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+        if args.dump_outputs is not None:
+            raise SystemExit("--dump-outputs is implemented for the single-GPU run (--gpus 1)")
         return pipeline_bench_main(args, cfg, model_path, log, MODELS)
 
     import torch
@@ -1050,7 +1071,7 @@ def main():
         try:
             # the timed run's tokens, and configs[0]'s 128 greedy tokens whenever the budget allows (~7 s of the reference's 8-thread path;
             # the driver's --steps 20 would otherwise stop the CPU side at 25 tokens)
-            want = args.warmup + r["steps"]
+            want = args.warmup + r["window"]
             if args.cpu_seconds >= 10:
                 want = min(max(want, 128), len(r["gpu_trace"]))
             c = cpu_decode(path, 8, args.cpu_seconds, args.n_ctx, want)
@@ -1060,7 +1081,7 @@ def main():
             if n > 0 and not bad and c["first"] == r["first"]:
                 dl = float(np.abs(r["gpu_logits_at"](n) - c["last_logits"]).max())
             parity = {"checked": True, "against": c["kind"] + " CPU path, 8 threads", "tokens_compared": n, "tokens_in_timed_run_covered": max(0, n - args.warmup),
-                      "timed_run_fully_covered": n >= args.warmup + r["steps"], "configs0_128_tokens_covered": n >= 128, "identical": not bad and c["first"] == r["first"], "first_divergence": bad[0] if bad else None,
+                      "timed_run_fully_covered": n >= args.warmup + r["window"], "configs0_128_tokens_covered": n >= 128, "identical": not bad and c["first"] == r["first"], "first_divergence": bad[0] if bad else None,
                       "max_abs_dlogit_at_last_compared_step": dl, "tolerance": 1e-3,
                       "pcie_loop_tokens_equal_device_loop": r["pcie_same"]}
             cpu_base = {"value": len(c["toks"]) / c["dt"], "unit": "tokens/s", "cores": 8, "kind": c["kind"], "tokens": len(c["toks"]),
@@ -1085,7 +1106,7 @@ def main():
     probe = {"note": "stand-alone k_gemv<PRE_QA, EPI_STORE> launched back to back over all layers (HIP events); never runs in the decode step",
              "per_shape": [{k: s[k] for k in ("name", "M", "K", "us_per_launch", "GBps")} for s in r["shapes"]],
              "all_gemv_launches_of_a_token": {"GBps": r["gemv_bytes_per_token"] / (r["gemv_us_per_token"] * 1e-6) / 1e9}}
-    t_mid = r["n_past0"] + r["steps"] // 2
+    t_mid = r["n_past0"] + r["window"] // 2
     e2e_bytes = token_bytes(cfg, t_mid)
     roof = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
             "end_to_end": {"bytes_per_token": e2e_bytes, "at_position": t_mid, "GBps": e2e_bytes / (ms_step * 1e-3) / 1e9,
@@ -1171,7 +1192,7 @@ def main():
         "vs_baseline": None, "dtype": "q4_0 x q4_0 -> int32 block sums, fp32 scales/accumulate",
         "data": "synthetic (random-init 7B-architecture weights in the reference file format, synthetic token ids)",
         "config": {"workload": f"LLaMA-{args.model} Q4_0 single-token decode, greedy, n_ctx {args.n_ctx}: `value` = {r['steps']} timed tokens at context positions "
-                               f"{r['n_past0']} .. {r['n_past0'] + r['steps'] - 1} (after 8 prompt + {args.warmup} warm-up tokens); BASELINE.json configs[1] proper -- the generation "
+                               f"{r['n_past0']} .. {r['n_past0'] + r['window'] - 1}{' (repeated)' if r['steps'] > r['window'] else ''} (after 8 prompt + {args.warmup} warm-up tokens); BASELINE.json configs[1] proper -- the generation "
                                f"to the end of the {args.n_ctx}-token context -- is config.full_context_tokens_per_s / roofline.full_context_*",
                    "n_threads_semantics": args.threads, "parallelism": "1 GPU"},
         "value_pcie": r["value_pcie"],

@@ -104,10 +104,9 @@ def oracle(built):
 
 @pytest.fixture(scope="session")
 def ref(built):
+    """the reference build (oracle/_ref), or None where it could not be built: tests then use its stored outputs (tests/refgolden.py)"""
     import reflib
-    if not reflib.have_ref():
-        pytest.skip("oracle/_ref/libggml_ref.so not present (needs /root/reference at build time)")
-    return reflib.RefLib()
+    return reflib.RefLib() if reflib.have_ref() else None
 
 
 @pytest.fixture(scope="session")

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import refgolden
 import synth
 from conftest import synth_tool
 
@@ -564,17 +565,31 @@ def test_q4_1_model_file_golden(L, tmp_path):
             assert same(k, g[f"nth{nth}_k1"]) and same(vv, g[f"nth{nth}_v1"])
 
 
-def test_dense_multipart_files_vs_reference(L, ref, tmp_path):
-    """An f16 model in two part files (column / row shards merged at load, .mm:358-388, 467-487) against
-    the reference library on the same files; refusals: per-layer dumps, the fused stage step."""
+def _dense_multipart_model(tmp):
     hp = synth.HParams(n_vocab=64, n_embd=256, n_mult=128, n_head=2, n_layer=1)
-    path = str(tmp_path / "m.bin")
+    path = str(tmp) + "/m.bin"
     t = synth.random_tensors(hp, seed=77)
     synth.write_model_unquantized(path, hp, t, 1, n_parts=2)
-    prompt = synth.synth_prompt(35, hp.n_vocab, seed=2)
+    return path, t, synth.synth_prompt(35, hp.n_vocab, seed=2)
+
+
+@refgolden.computed_by("gpu_parity.dense_multipart")
+def _ref_dense_multipart(ref, tmp):
+    path, _, prompt = _dense_multipart_model(tmp)
     rm = ref.load(path, 48, 2)
+    out = {"logits_all": rm.eval(prompt, 0, 8, all_logits=True)["logits_all"]}
+    rm.close()
+    return out
+
+
+def test_dense_multipart_files_vs_reference(L, ref, tmp_path):
+    """An f16 model in two part files (column / row shards merged at load, .mm:358-388, 467-487) against
+    the reference library on the same files (its logits stored in tests/golden/ref_outputs.npz); refusals: per-layer dumps, the fused
+    stage step."""
+    want = refgolden.outputs("gpu_parity.dense_multipart", ref, tmp_path)
+    path, t, prompt = _dense_multipart_model(tmp_path)
     with L.Model(path, n_ctx=48, n_parts=2) as m:
-        assert same(m.eval_debug(prompt, 0, 8, all_logits=True)["logits_all"], rm.eval(prompt, 0, 8, all_logits=True)["logits_all"])
+        assert same(m.eval_debug(prompt, 0, 8, all_logits=True)["logits_all"], want["logits_all"])
         for name in ("layers.0.attention.wo.weight", "layers.0.feed_forward.w1.weight", "tok_embeddings.weight"):
             assert m.tensor_bytes(name).tobytes() == np.ascontiguousarray(t[name], np.float16).tobytes(), name
         with pytest.raises(L.LlamaHipError, match="Q4_0 models only"):
@@ -764,13 +779,39 @@ def test_7b_width_2048_token_prefill_vs_oracle(L, oracle, tmp_path):
         om.close()
 
 
+def _topk_model(tmp):
+    hp = synth.HParams(n_vocab=1200, n_embd=256, n_mult=64, n_head=2, n_layer=2)
+    path = str(tmp) + "/m.bin"
+    synth.write_model(path, hp, synth.random_tensors(hp, seed=21))
+    return path, synth.synth_prompt(9, hp.n_vocab, seed=4)
+
+
+@refgolden.computed_by("gpu_parity.topk_sampled")
+def _ref_topk_sampled(ref, tmp):
+    """60 steps of the reference's own llama_sample_top_p_top_k, fed with the reference's logits of every step"""
+    path, toks = _topk_model(tmp)
+    rm = ref.load(path, 128)
+    rs = ref.L.refllama_sampler_new(-1, 64)
+    n_past, ids = 0, []
+    for _ in range(60):
+        full = rm.eval(toks, n_past, 8)["logits"]
+        ids.append(int(ref.L.refllama_sampler_sample(rm.h, rs, full, 1.3, 40, float(np.float32(0.95)), float(np.float32(0.8)))))
+        ref.L.refllama_sampler_accept(rs, ids[-1])
+        n_past += len(toks)
+        toks = np.array([ids[-1]], np.int32)
+    ref.L.refllama_sampler_free(rs)
+    rm.close()
+    return {"ids": np.array(ids)}
+
+
 def test_device_topk_candidates_vs_the_reference_sampler(L, ref, tmp_path):
     """The sampler's front half on the device (scores + top-k, utils.cpp:345-395).  (1) On logits without ties the k
     (score, id) pairs are the host formula's, sorted -- checked against float64 numpy.  (2) On tie-heavy logits the kernel
     must flag every case where an equality could matter (exact = 0), and where it claims exactness the pairs must again
     be the unique answer.  (3) End to end: a sampled generation through llamahip_eval_topk + sample_from_candidates
     (fallback to the host path when flagged) draws the same ids, with the same mt19937 state, as the reference's own
-    llama_sample_top_p_top_k fed with the host logits of every step."""
+    llama_sample_top_p_top_k fed with the logits of every step (the reference's logits, bit for bit the library's; stored in
+    tests/golden/ref_outputs.npz)."""
     rng = np.random.default_rng(77)
     V = 32000
 
@@ -801,28 +842,20 @@ def test_device_topk_candidates_vs_the_reference_sampler(L, ref, tmp_path):
             assert np.array_equal(sc, want[order[:k]]), trial
     assert n_exact >= 20
     # end to end on a model
-    hp = synth.HParams(n_vocab=1200, n_embd=256, n_mult=64, n_head=2, n_layer=2)
-    path = str(tmp_path / "m.bin")
-    synth.write_model(path, hp, synth.random_tensors(hp, seed=21))
-    rm = ref.load(path, 128)
-    rs = ref.L.refllama_sampler_new(-1, 64)
+    want_ids = refgolden.outputs("gpu_parity.topk_sampled", ref, tmp_path)["ids"].tolist()
+    path, prompt = _topk_model(tmp_path)
     s = L.Sampler(seed=-1, repeat_last_n=64)
-    try:
-        with L.Model(path, n_ctx=128) as m:
-            toks, n_past, hits = synth.synth_prompt(9, hp.n_vocab, seed=4), 0, 0
-            for step in range(60):
-                exact, sc, ids, lg = m.eval_topk(toks, n_past, s)
-                full = m.eval(toks, n_past, 8)                               # the row the reference sampler sees
-                want = int(ref.L.refllama_sampler_sample(rm.h, rs, full, 1.3, 40, float(np.float32(0.95)), float(np.float32(0.8))))
-                got = s.sample_from_candidates(sc, ids) if exact else s.sample(m, lg)
-                hits += exact
-                assert got == want, (step, exact, got, want)
-                s.accept(got); ref.L.refllama_sampler_accept(rs, want)
-                n_past += len(toks)
-                toks = np.array([got], np.int32)
-            assert hits >= 50
-    finally:
-        ref.L.refllama_sampler_free(rs)
+    with L.Model(path, n_ctx=128) as m:
+        toks, n_past, hits = prompt, 0, 0
+        for step, want in enumerate(want_ids):
+            exact, sc, ids, lg = m.eval_topk(toks, n_past, s)
+            got = s.sample_from_candidates(sc, ids) if exact else s.sample(m, lg)
+            hits += exact
+            assert got == want, (step, exact, got, want)
+            s.accept(got)
+            n_past += len(toks)
+            toks = np.array([got], np.int32)
+        assert hits >= 50
 
 
 def test_fast_prefill_is_opt_in_and_close(L, tmp_path):

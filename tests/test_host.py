@@ -3,11 +3,13 @@ error strings (file parsing happens before any device work); host-only handles: 
 tokenizer and sampler against the golden vectors; the runner's event order on failure.
 No compute call is made (there is no GPU here)."""
 import os
+import pathlib
 import struct
 
 import numpy as np
 import pytest
 
+import refgolden
 import synth
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -85,17 +87,33 @@ def test_unknown_and_misshapen_tensors_are_rejected(L, tmp_path):
     assert "has wrong size in model file" in e.value.message                        # .mm:394-395
 
 
+MERGE_TENSORS = ("tok_embeddings.weight", "output.weight", "norm.weight", "layers.0.attention.wq.weight",
+                 "layers.1.attention.wo.weight", "layers.0.feed_forward.w1.weight", "layers.1.feed_forward.w2.weight",
+                 "layers.1.feed_forward.w3.weight", "layers.0.ffn_norm.weight")
+
+
+def _merge_model(tmp, parts):
+    hp = synth.HParams(n_vocab=64, n_embd=256, n_mult=256, n_head=2, n_layer=2)      # n_ff 768: shards stay multiples of 64
+    return _write(tmp, hp, parts=parts, seed=11)[0]
+
+
+@refgolden.computed_by("host.multipart_merge", [(1,), (2,), (4,)])
+def _ref_multipart_merge(ref, tmp, parts):
+    r = ref.load(_merge_model(pathlib.Path(tmp), parts), 32, parts)
+    out = {"hparams": np.array([r.n_vocab, r.n_embd, r.n_head, r.n_layer, r.n_ff])}
+    out.update({f"tensor/{name}": refgolden.digest(r.tensor_bytes(name)) for name in MERGE_TENSORS})
+    r.close()
+    return out
+
+
 @pytest.mark.parametrize("parts", [1, 2, 4])
 def test_multipart_merge_matches_the_reference_loader(L, ref, tmp_path, parts):
-    hp = synth.HParams(n_vocab=64, n_embd=256, n_mult=256, n_head=2, n_layer=2)      # n_ff 768: shards stay multiples of 64
-    path, _ = _write(tmp_path, hp, parts=parts, seed=11)
+    want = refgolden.outputs("host.multipart_merge", ref, tmp_path, parts)
+    path = _merge_model(tmp_path, parts)
     m = L.Model(path, n_ctx=32, n_parts=parts, flags=HOST_ONLY)
-    r = ref.load(path, 32, parts)
-    assert (m.n_vocab, m.n_embd, m.n_head, m.n_layer, m.n_ff, m.n_parts) == (r.n_vocab, r.n_embd, r.n_head, r.n_layer, r.n_ff, parts)
-    for name in ("tok_embeddings.weight", "output.weight", "norm.weight", "layers.0.attention.wq.weight",
-                 "layers.1.attention.wo.weight", "layers.0.feed_forward.w1.weight", "layers.1.feed_forward.w2.weight",
-                 "layers.1.feed_forward.w3.weight", "layers.0.ffn_norm.weight"):
-        assert np.array_equal(m.tensor_bytes(name), r.tensor_bytes(name)), name
+    assert (m.n_vocab, m.n_embd, m.n_head, m.n_layer, m.n_ff, m.n_parts) == tuple(want["hparams"].tolist()) + (parts,)
+    for name in MERGE_TENSORS:
+        assert np.array_equal(refgolden.digest(m.tensor_bytes(name)), want[f"tensor/{name}"]), name
     with pytest.raises(L.LlamaHipError) as e:          # no device state behind a host-only handle
         m.eval([1], 0)
     assert e.value.code == -1001
@@ -191,66 +209,117 @@ def test_sampler_matches_reference_sequence(L, tmp_path):
     assert got == t["sampler_ids"].tolist()
 
 
-def test_tokenizer_and_sampler_against_the_reference_build(L, ref, tmp_path):
-    """The host utilities next to the reference's OWN utils.cpp (oracle/_ref): random texts over the model's
-    vocabulary, and 400 sampling steps on logits with many exact ties (so that std::partial_sort's handling of
-    equal scores at the top_k boundary matters) and repeated tokens in the penalty window -- same ids, same
-    mt19937 draws.  (The sampler's window lookup is a byte map here, std::find per logit there.)"""
-    import synth
-    m, g = _golden_model(L, tmp_path)
-    rm = ref.load(str(tmp_path / "tiny.bin"), 64)
+def _tokenizer_sampler_inputs(m):
+    """random texts over the golden model's vocabulary, then 400 (logits, top_k) sampling steps with many exact ties"""
     rng = np.random.default_rng(2024)
     pieces = [m.token_text(i) for i in range(m.n_vocab)]
     pieces = [p for p in pieces if p and b"\x00" not in p]
+    texts = []
     for _ in range(60):
         text = b"".join(pieces[int(i)] for i in rng.integers(0, len(pieces), int(rng.integers(1, 40))))
         try:
-            t = text.decode()
+            text.decode()
         except UnicodeDecodeError:
             continue
-        for bos in (True, False):
-            assert np.array_equal(m.tokenize(text, bos), rm.tokenize(t, bos)), text
-    V = m.n_vocab
-    rl = ref.L
-    rs = rl.refllama_sampler_new(-1, 64)
+        texts.append(text)
+    steps = []
+    for step in range(400):
+        lg = (rng.integers(-6, 7, m.n_vocab) * 0.5).astype(np.float32)           # 13 distinct values: ties everywhere
+        if step % 3 == 0:
+            lg += rng.standard_normal(m.n_vocab).astype(np.float32) * np.float32(0.01)
+        steps.append((lg, int(min(m.n_vocab, rng.integers(1, 41)))))
+    return texts, steps
+
+
+SAMPLE_KW = dict(repeat_penalty=1.3, top_p=float(np.float32(0.95)), temp=float(np.float32(0.8)))
+
+
+@refgolden.computed_by("host.tokenizer_and_sampler")
+def _ref_tokenizer_and_sampler(ref, tmp):
+    import llama_swift_amd as L
+    tmp = pathlib.Path(tmp)
+    m, _ = _golden_model(L, tmp)
+    texts, steps = _tokenizer_sampler_inputs(m)
+    rm = ref.load(str(tmp / "tiny.bin"), 64)
+    out = {}
+    for bos in (True, False):
+        toks = [rm.tokenize(t.decode(), bos) for t in texts]
+        out[f"tokens_bos{int(bos)}"] = np.concatenate(toks)
+        out[f"lengths_bos{int(bos)}"] = np.array([len(t) for t in toks])
+    rs = ref.L.refllama_sampler_new(-1, 64)
+    ids = []
+    for lg, top_k in steps:
+        ids.append(int(ref.L.refllama_sampler_sample(rm.h, rs, lg, SAMPLE_KW["repeat_penalty"], top_k, SAMPLE_KW["top_p"], SAMPLE_KW["temp"])))
+        ref.L.refllama_sampler_accept(rs, ids[-1])
+    ref.L.refllama_sampler_free(rs)
+    rm.close()
+    out["sampled_ids"] = np.array(ids)
+    return out
+
+
+def test_tokenizer_and_sampler_against_the_reference_build(L, ref, tmp_path):
+    """The host utilities next to the reference's OWN utils.cpp (oracle/_ref; its results stored in tests/golden/ref_outputs.npz): random
+    texts over the model's vocabulary, and 400 sampling steps on logits with many exact ties (so that std::partial_sort's handling of
+    equal scores at the top_k boundary matters) and repeated tokens in the penalty window -- same ids, same
+    mt19937 draws.  (The sampler's window lookup is a byte map here, std::find per logit there.)"""
+    want = refgolden.outputs("host.tokenizer_and_sampler", ref, tmp_path)
+    m, g = _golden_model(L, tmp_path)
+    texts, steps = _tokenizer_sampler_inputs(m)
+    assert len(texts) > 40
+    for bos in (True, False):
+        ends = np.cumsum(want[f"lengths_bos{int(bos)}"])
+        assert len(ends) == len(texts)
+        for text, e, n in zip(texts, ends, want[f"lengths_bos{int(bos)}"]):
+            assert np.array_equal(m.tokenize(text, bos), want[f"tokens_bos{int(bos)}"][e - n:e]), text
     s = L.Sampler(seed=-1, repeat_last_n=64)
-    try:
-        for step in range(400):
-            lg = (rng.integers(-6, 7, V) * 0.5).astype(np.float32)           # 13 distinct values: ties everywhere
-            if step % 3 == 0:
-                lg += rng.standard_normal(V).astype(np.float32) * np.float32(0.01)
-            kw = dict(repeat_penalty=1.3, top_k=int(min(V, rng.integers(1, 41))), top_p=float(np.float32(0.95)), temp=float(np.float32(0.8)))
-            a = s.sample(m, lg, **kw)
-            b = int(rl.refllama_sampler_sample(rm.h, rs, lg, kw["repeat_penalty"], kw["top_k"], kw["top_p"], kw["temp"]))
-            assert a == b, (step, a, b)
-            s.accept(a)
-            rl.refllama_sampler_accept(rs, b)
-    finally:
-        rl.refllama_sampler_free(rs)
+    for step, ((lg, top_k), b) in enumerate(zip(steps, want["sampled_ids"].tolist())):
+        a = s.sample(m, lg, top_k=top_k, **SAMPLE_KW)
+        assert a == b, (step, a, b)
+        s.accept(a)
+
+
+EMPTY_PROMPT_SEEDS = (-1, 0, 1, 7, 12345)
+
+
+def _empty_prompt_logits(n_vocab):
+    rng = np.random.default_rng(5)
+    return [[rng.standard_normal(n_vocab).astype(np.float32) for _ in range(8)] for _ in EMPTY_PROMPT_SEEDS]
+
+
+@refgolden.computed_by("host.empty_prompt")
+def _ref_empty_prompt(ref, tmp):
+    import ctypes as C
+    path = os.path.join(tmp, "tiny.bin")
+    np.load(os.path.join(G, "tiny_model.npz"))["model_file"].tofile(path)
+    rm = ref.load(path, 64)
+    out = {}
+    for seed, lgs in zip(EMPTY_PROMPT_SEEDS, _empty_prompt_logits(rm.n_vocab)):
+        rs = ref.L.refllama_sampler_new(seed, 64)
+        buf = C.create_string_buffer(64)
+        ref.L.refllama_sampler_random_prompt(rs, buf, 64)
+        out[f"prompt_{seed}"] = np.frombuffer(buf.value, np.uint8)
+        ids = []
+        for lg in lgs:
+            ids.append(int(ref.L.refllama_sampler_sample(rm.h, rs, lg, 1.3, 40, float(np.float32(0.95)), float(np.float32(0.8)))))
+            ref.L.refllama_sampler_accept(rs, ids[-1])
+        ref.L.refllama_sampler_free(rs)
+        out[f"ids_{seed}"] = np.array(ids)
+    rm.close()
+    return out
 
 
 def test_empty_prompt_draws_the_reference_random_prompt(L, ref, tmp_path):
     """-[LlamaPredictOperation main] replaces an empty prompt by gpt_random_prompt(rng) (.mm:774-776), which
     consumes one draw of the rng the sampler uses afterwards: same prompt, same sampled ids after it."""
-    import ctypes as C
+    want = refgolden.outputs("host.empty_prompt", ref, tmp_path)
     m, _ = _golden_model(L, tmp_path)
-    rm = ref.load(str(tmp_path / "tiny.bin"), 64)
-    rng = np.random.default_rng(5)
-    for seed in (-1, 0, 1, 7, 12345):
+    for seed, lgs in zip(EMPTY_PROMPT_SEEDS, _empty_prompt_logits(m.n_vocab)):
         s = L.Sampler(seed=seed, repeat_last_n=64)
-        rs = ref.L.refllama_sampler_new(seed, 64)
-        try:
-            buf = C.create_string_buffer(64)
-            ref.L.refllama_sampler_random_prompt(rs, buf, 64)
-            assert s.random_prompt() == buf.value.decode()
-            for _ in range(8):
-                lg = rng.standard_normal(m.n_vocab).astype(np.float32)
-                a = s.sample(m, lg)
-                b = int(ref.L.refllama_sampler_sample(rm.h, rs, lg, 1.3, 40, float(np.float32(0.95)), float(np.float32(0.8))))
-                assert a == b
-                s.accept(a); ref.L.refllama_sampler_accept(rs, b)
-        finally:
-            ref.L.refllama_sampler_free(rs)
+        assert s.random_prompt() == want[f"prompt_{seed}"].tobytes().decode()
+        for lg, b in zip(lgs, want[f"ids_{seed}"].tolist()):
+            a = s.sample(m, lg)
+            assert a == b
+            s.accept(a)
 
 
 def test_sampler_clamps_top_k_to_the_vocabulary(L, tmp_path):

@@ -1,61 +1,127 @@
 """CPU: the standalone restatement against the reference's own ggml.c compiled in place
-(oracle/_ref, present in the build container and shipped prebuilt to the GPU box).  Randomised,
-larger shapes than the committed fixtures.  Bit-exact."""
+(oracle/_ref where the reference sources are present; its outputs for these inputs are stored in
+tests/golden/ref_outputs.npz, tests/refgolden.py).  Randomised, larger shapes than the committed fixtures.  Bit-exact."""
 import numpy as np
 import pytest
 
+import refgolden
 import synth
 
 
-def test_quantizers(oracle, ref):
+def _quantizer_input():
     rng = np.random.default_rng(1)
     x = (rng.standard_normal((64, 4096)) * rng.uniform(0.01, 5, (64, 1))).astype(np.float32)
     x[3, 64:96] = 0
-    for r in x[:16]:
-        assert np.array_equal(oracle.quantize_row(r), ref.quantize_row(r))
-    assert np.array_equal(oracle.quantize_offline(x), ref.quantize_offline(x))
-    assert np.array_equal(synth.quantize_q4_0_offline(x), ref.quantize_offline(x))      # the numpy writer too
+    return x
 
 
-@pytest.mark.parametrize("M,K,N", [(64, 4096, 1), (32, 11008, 3), (40, 5120, 9), (16, 8192, 2), (128, 64, 4)])
-def test_mul_mat(oracle, ref, M, K, N):
+@refgolden.computed_by("oracle_vs_ref.quantizers")
+def _ref_quantizers(ref, tmp):
+    x = _quantizer_input()
+    return {"rows": np.stack([ref.quantize_row(r) for r in x[:16]]), "offline": ref.quantize_offline(x)}
+
+
+def test_quantizers(oracle, ref, tmp_path):
+    x = _quantizer_input()
+    want = refgolden.outputs("oracle_vs_ref.quantizers", ref, tmp_path)
+    for r, w in zip(x[:16], want["rows"]):
+        assert np.array_equal(oracle.quantize_row(r), w)
+    assert np.array_equal(oracle.quantize_offline(x), want["offline"])
+    assert np.array_equal(synth.quantize_q4_0_offline(x), want["offline"])      # the numpy writer too
+
+
+MUL_MAT_CASES = [(64, 4096, 1), (32, 11008, 3), (40, 5120, 9), (16, 8192, 2), (128, 64, 4)]
+
+
+def _mul_mat_inputs(M, K, N):
     rng = np.random.default_rng(M * 7 + K + N)
     w = synth.quantize_q4_0_offline((0.02 * rng.standard_normal((M, K))).astype(np.float32))
     x = rng.standard_normal((N, K)).astype(np.float32)
-    assert np.array_equal(oracle.mul_mat_q4_0(w, x, 4), ref.mul_mat_q4_0(w, x, 8))
+    return w, x
 
 
-def test_row_ops(oracle, ref):
+@refgolden.computed_by("oracle_vs_ref.mul_mat", MUL_MAT_CASES)
+def _ref_mul_mat(ref, tmp, M, K, N):
+    w, x = _mul_mat_inputs(M, K, N)
+    return {"y": ref.mul_mat_q4_0(w, x, 8)}
+
+
+@pytest.mark.parametrize("M,K,N", MUL_MAT_CASES)
+def test_mul_mat(oracle, ref, tmp_path, M, K, N):
+    w, x = _mul_mat_inputs(M, K, N)
+    assert np.array_equal(oracle.mul_mat_q4_0(w, x, 4), refgolden.outputs("oracle_vs_ref.mul_mat", ref, tmp_path, M, K, N)["y"])
+
+
+def _row_ops_inputs():
     rng = np.random.default_rng(2)
     x = (rng.standard_normal((9, 5120)) * 2).astype(np.float32)
-    assert np.array_equal(oracle.unary_rows("norm", x), ref.unary_rows("norm", x, 4))
-    assert np.array_equal(oracle.unary_rows("silu", x), ref.unary_rows("silu", x, 4))
     s = (rng.standard_normal((40, 513)) * 4).astype(np.float32)
     s[::3, 200:] = -np.inf
-    assert np.array_equal(oracle.unary_rows("soft_max", s), ref.unary_rows("soft_max", s, 4))
     r = rng.standard_normal((12, 4, 128)).astype(np.float32)
-    assert np.array_equal(oracle.rope(r, 37, 0), ref.rope(r, 37, 0))
-    assert np.array_equal(oracle.rope(r, 5, 1), ref.rope(r, 5, 1))
+    return x, s, r
 
 
-@pytest.mark.parametrize("nth,parts", [(8, 1), (5, 2)])
-def test_model_eval_and_multipart_merge(oracle, ref, tmp_path, nth, parts):
+@refgolden.computed_by("oracle_vs_ref.row_ops")
+def _ref_row_ops(ref, tmp):
+    x, s, r = _row_ops_inputs()
+    return {"norm": ref.unary_rows("norm", x, 4), "silu": ref.unary_rows("silu", x, 4), "soft_max": ref.unary_rows("soft_max", s, 4),
+            "rope_37_0": ref.rope(r, 37, 0), "rope_5_1": ref.rope(r, 5, 1)}
+
+
+def test_row_ops(oracle, ref, tmp_path):
+    x, s, r = _row_ops_inputs()
+    want = refgolden.outputs("oracle_vs_ref.row_ops", ref, tmp_path)
+    assert np.array_equal(oracle.unary_rows("norm", x), want["norm"])
+    assert np.array_equal(oracle.unary_rows("silu", x), want["silu"])
+    assert np.array_equal(oracle.unary_rows("soft_max", s), want["soft_max"])
+    assert np.array_equal(oracle.rope(r, 37, 0), want["rope_37_0"])
+    assert np.array_equal(oracle.rope(r, 5, 1), want["rope_5_1"])
+
+
+MODEL_CASES = [(8, 1), (5, 2)]
+MODEL_TENSORS = ("tok_embeddings.weight", "layers.1.attention.wo.weight", "layers.2.feed_forward.w2.weight",
+                 "layers.0.feed_forward.w1.weight", "output.weight", "norm.weight")
+
+
+def _model(tmp, parts):
     hp = synth.HParams(n_vocab=128, n_embd=256, n_mult=256, n_head=2, n_layer=3)
-    path = str(tmp_path / "m.bin")
+    path = str(tmp) + "/m.bin"
     synth.write_model(path, hp, synth.random_tensors(hp, seed=77), n_parts=parts)
-    mo, mr = oracle.load(path, 48, parts), ref.load(path, 48, parts)
-    for name in ("tok_embeddings.weight", "layers.1.attention.wo.weight", "layers.2.feed_forward.w2.weight",
-                 "layers.0.feed_forward.w1.weight", "output.weight", "norm.weight"):
-        assert np.array_equal(mo.tensor_bytes(name), mr.tensor_bytes(name)), name
-    toks = synth.synth_prompt(11, hp.n_vocab, seed=5)
-    a, b = mo.eval(toks[:9], 0, nth, all_logits=True, dump_layer=2), mr.eval(toks[:9], 0, nth, all_logits=True, dump_layer=2)
+    return path, synth.synth_prompt(11, hp.n_vocab, seed=5)
+
+
+@refgolden.computed_by("oracle_vs_ref.model", MODEL_CASES)
+def _ref_model(ref, tmp, nth, parts):
+    path, toks = _model(tmp, parts)
+    mr = ref.load(path, 48, parts)
+    out = {f"tensor/{name}": refgolden.digest(mr.tensor_bytes(name)) for name in MODEL_TENSORS}
+    out.update({f"eval9/{k}": v for k, v in mr.eval(toks[:9], 0, nth, all_logits=True, dump_layer=2).items()})
+    out["eval2_logits_all"] = mr.eval(toks[9:], 9, nth, all_logits=True)["logits_all"]
+    tok, n_past, steps = int(np.argmax(out["eval2_logits_all"][-1])), 11, []
+    for _ in range(10):
+        steps.append(mr.eval(np.array([tok], np.int32), n_past, nth)["logits"])
+        tok = int(np.argmax(steps[-1])); n_past += 1
+    out["decode_logits"] = np.stack(steps)
+    mr.close()
+    return out
+
+
+@pytest.mark.parametrize("nth,parts", MODEL_CASES)
+def test_model_eval_and_multipart_merge(oracle, ref, tmp_path, nth, parts):
+    want = refgolden.outputs("oracle_vs_ref.model", ref, tmp_path, nth, parts)
+    path, toks = _model(tmp_path, parts)
+    mo = oracle.load(path, 48, parts)
+    for name in MODEL_TENSORS:
+        assert np.array_equal(refgolden.digest(mo.tensor_bytes(name)), want[f"tensor/{name}"]), name
+    a = mo.eval(toks[:9], 0, nth, all_logits=True, dump_layer=2)
+    b = {k[len("eval9/"):]: v for k, v in want.items() if k.startswith("eval9/")}
+    assert b
     for k in b:
         assert np.array_equal(a[k], b[k]), k
-    a, b = mo.eval(toks[9:], 9, nth, all_logits=True), mr.eval(toks[9:], 9, nth, all_logits=True)
-    assert np.array_equal(a["logits_all"], b["logits_all"])
-    tok, n_past = int(np.argmax(b["logits"])), 11
-    for _ in range(10):
+    a = mo.eval(toks[9:], 9, nth, all_logits=True)
+    assert np.array_equal(a["logits_all"], want["eval2_logits_all"])
+    tok, n_past = int(np.argmax(want["eval2_logits_all"][-1])), 11
+    for lb in want["decode_logits"]:
         la = mo.eval(np.array([tok], np.int32), n_past, nth)["logits"]
-        lb = mr.eval(np.array([tok], np.int32), n_past, nth)["logits"]
         assert np.array_equal(la, lb)
         tok = int(np.argmax(lb)); n_past += 1

@@ -636,7 +636,7 @@ def test_device_side_mailboxes_two_stages_two_streams(L, tmp_path, shape):
 def test_device_side_mailboxes_three_stages_with_a_one_layer_middle_stage(L, tmp_path, shape):
     """What a pipeline of more than two GPUs adds: a MIDDLE stage, whose step takes its row from one mailbox and leaves it in another --
     here with a single layer, so the mailbox prologue (first layer) and the mailbox epilogue (last layer's w2) belong to the same
-    layer.  Three stage handles, three streams, the consumers' steps enqueued before their producers'; tokens = the whole model's."""
+    layer.  Three stage handles, three streams, no ordering between them but the mailboxes; tokens = the whole model's."""
     import torch
     path, n_vocab, n_embd, n_layer = _mailbox_model(tmp_path, shape)
     a = L.Model(path, n_ctx=64, layer_begin=0, layer_end=1, n_seq=2)
@@ -670,18 +670,16 @@ def test_device_side_mailboxes_three_stages_with_a_one_layer_middle_stage(L, tmp
         c.stage_bind(s, len(prompts[s]))
     sa, sm, sc = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
     n_steps = 6
+    # Producer first: a process may get fewer hardware queues than these three streams, and a consumer's waiting launch enqueued on a
+    # queue it shares with its own producer would sit in front of it -- a co-location artefact, every stage has its own GPU in the pipeline.
+    # Small stages: nothing in between, so the consumers' launches on the other queues are in flight at once and really wait.
+    # 7B-wide stages: the waiting first launches of TWO stages (576 polling workgroups each) fill the ONE GPU of this test and the
+    # producer's launch would never become resident: one stage at a time, the rows still travel through the mailboxes.
     for _ in range(n_steps):
         for s in (1, 0):
-            if shape == "small":
-                c.stage_step(s, 8, sc.cuda_stream)               # consumers first: their kernels really wait
-                mid.stage_step(s, 8, sm.cuda_stream)
-                a.stage_step(s, 8, sa.cuda_stream)
-            else:
-                # 7B-wide stages: the waiting first launches of TWO stages (576 polling workgroups each) fill the ONE GPU of this test and the
-                # producer's launch would never become resident -- a co-location artefact, every stage has its own GPU in the pipeline.
-                # Producer first, one stage at a time: the rows still travel through the mailboxes.
-                for m, st in ((a, sa), (mid, sm), (c, sc)):
-                    m.stage_step(s, 8, st.cuda_stream)
+            for m, st in ((a, sa), (mid, sm), (c, sc)):
+                m.stage_step(s, 8, st.cuda_stream)
+                if shape != "small":
                     torch.cuda.synchronize()
     for s in range(2):
         n, pos, got = c.stage_trace(s, n_steps)
