@@ -72,7 +72,8 @@ typedef struct llamahip_opts {
  * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_decode_greedy / llamahip_kv_read / llamahip_get_stats and the
  * llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690) crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
- * Results are bit for bit the single-device handle's.  The stage-level entry points (llamahip_eval_stage, llamahip_stage_*) and
+ * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
+ * LLAMAHIP_FLAG_UNFUSED decode one pipeline eval per token, the pick by the same argmax kernel).  The stage-level entry points (llamahip_eval_stage, llamahip_stage_*) and
  * llamahip_eval_debug's dumps refuse such a handle.  LLAMAHIP_DEVICES never applies to a handle loaded with an explicit device, layer range
  * or LLAMAHIP_FLAG_HOST_ONLY. */
 
@@ -184,7 +185,8 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
  * gets out_tokens[i * n_steps + t], t < n_steps: bit for bit the tokens of llamahip_decode_greedy on that sequence alone.  The slots are stepped in
  * groups of up to 16 as sets (llamahip_stage_step_set: the weights are streamed once per step for a whole group); on a pipeline handle
  * (n_devices > 1) the groups -- at least one per stage -- are additionally pipelined over the stages: in steady state every stage (GPU) works on a
- * different group, rows and picks move between stages as stream-ordered copies.  The native form of the schedule bench.py --gpus N runs over RCCL. */
+ * different group, rows and picks move between stages as stream-ordered copies.  The native form of the schedule bench.py --gpus N runs over RCCL.
+ * f16 / f32 / Q4_1 files and LLAMAHIP_FLAG_UNFUSED handles have no set step: their sequences run one after the other, llamahip_decode_greedy each. */
 int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
                                  int32_t n_steps, int32_t *out_tokens, char *err, size_t err_cap);
 

@@ -1197,7 +1197,10 @@ int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past, c
                          int32_t chunk_tokens, float *logits_out, char *err, size_t err_cap) {
     if (chunk_tokens < 1) { set_err(err, err_cap, "llamahip_eval_chunks: chunk_tokens must be >= 1"); return LLAMAHIP_ERR_PREDICT; }
     if (!m || n_tokens <= chunk_tokens) return llamahip_eval(m, n_threads, n_past, tokens, n_tokens, logits_out, err, err_cap);
-    if ((m->host_only && m->stages.empty()) || m->dense) {          // f16 / f32 model files: the evals themselves, one after the other
+    // f16 / f32 / Q4_1 model files: the evals themselves, one after the other (a pipeline handle's front is loaded HOST_ONLY and never
+    // learns the file type: its stages know it)
+    const bool dense = m->stages.empty() ? m->dense : m->stages[0]->dense;
+    if ((m->host_only && m->stages.empty()) || dense) {
         for (int32_t c0 = 0; c0 < n_tokens; c0 += chunk_tokens) {
             const int32_t n = std::min(chunk_tokens, n_tokens - c0);
             const int rc = llamahip_eval(m, n_threads, n_past + c0, tokens + c0, n, c0 + n == n_tokens ? logits_out : nullptr, err, err_cap);
@@ -1978,6 +1981,21 @@ static int pipe_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_pa
     if (rc) return rc;
     if (n_steps < 1 || n_past + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past, n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     if (!out_tokens) { set_err(err, err_cap, "null out_tokens"); return LLAMAHIP_ERR_PREDICT; }
+    if (first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+        // un-fused stages (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED) have no captured stage step: one pipeline eval per token, the pick by
+        // k_argmax itself on the last stage's logits row -- the plain handle's rule (lowest index on ties, NaN never picked) -- read back for the
+        // next step's token
+        int32_t tok = first_token;
+        for (int i = 0; i < n_steps; i++) {
+            if ((rc = pipe_eval(m, n_threads, n_past + i, &tok, 1, 0, i + 1 == n_steps ? logits_last : nullptr, err, err_cap)) != 0) return rc;
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_argmax(last->logits, m->hp.n_vocab, last->pipe_tok, 0, nullptr, nullptr, last->stream), LLAMAHIP_ERR_PREDICT);
+            if ((rc = pipe_wait_stage(last, S - 1, err, err_cap)) != 0) return rc;
+            HIP_TRY(hipMemcpy(&tok, last->pipe_tok, 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            out_tokens[i] = tok;
+        }
+        return LLAMAHIP_OK;                                                // (pipe_eval counted the evals and their time)
+    }
     const double t0 = now_ms();
     const size_t d = m->hp.n_embd;
     const int seq = m->cur_seq;
@@ -2050,6 +2068,17 @@ static int decode_greedy_multi_impl(llamahip_model *m, int32_t n_threads, int32_
         int rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap);
         if (rc) return rc;
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    }
+    if (first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+        // no stage step to batch (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED): llamahip_decode_greedy on each slot in turn
+        const int save_seq = m->cur_seq;
+        int rc = 0;
+        for (int i = 0; i < n_seqs && rc == 0; i++) {
+            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
+                rc = llamahip_decode_greedy(m, n_threads, n_past[i], first_tokens[i], n_steps, out_tokens + (size_t) i * n_steps, nullptr, err, err_cap);
+        }
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
     }
     const double t0 = now_ms();
     const size_t d = m->hp.n_embd;

@@ -2,7 +2,8 @@
 
 oracle/_ref (the reference's own ggml.c / utils.cpp) can only be built where the reference sources are present.  A test that compares
 against it registers the reference side as a function of (RefLib, scratch directory, *case) -> {key: array} with @computed_by and reads
-the arrays with outputs(); tests/golden/make_ref_golden.py runs every registered function and writes tests/golden/ref_outputs.npz.
+the arrays with outputs(); tests/golden/make_ref_golden.py runs every registered function and writes the store each one names
+(tests/golden/ref_outputs.npz unless computed_by is given another file, which keeps every store a small file of its own).
 Where oracle/_ref is present, outputs() runs the function again and the stored arrays must be its result bit for bit."""
 import hashlib
 import os
@@ -10,18 +11,18 @@ import os
 import numpy as np
 
 STORE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_outputs.npz")
-FUNCS = {}
-_stored = None
+FUNCS = {}                                    # key -> (function, case, store file)
+_stored = {}                                  # store file -> {array name: array}
 
 
 def key(name, case=()):
     return name + "".join(f":{c}" for c in case)
 
 
-def computed_by(name, cases=((),)):
+def computed_by(name, cases=((),), store=STORE):
     def register(fn):
         for case in cases:
-            FUNCS[key(name, case)] = (fn, tuple(case))
+            FUNCS[key(name, case)] = (fn, tuple(case), store)
         return fn
     return register
 
@@ -35,7 +36,7 @@ def digest(a) -> np.ndarray:
 
 
 def compute(ref, tmp_dir, k) -> dict:
-    fn, case = FUNCS[k]
+    fn, case, _ = FUNCS[k]
     return {n: np.asarray(v) for n, v in fn(ref, str(tmp_dir), *case).items()}
 
 
@@ -44,15 +45,15 @@ def _same(a, b):
 
 
 def outputs(name, ref, tmp_dir, *case) -> dict:
-    global _stored
-    if _stored is None:
-        with np.load(STORE) as z:
-            _stored = {n: z[n] for n in z.files}
     k = key(name, case)
-    want = {n[len(k) + 1:]: v for n, v in _stored.items() if n.startswith(k + "/")}
-    assert want, f"{STORE} has no reference outputs for {k}: run tests/golden/make_ref_golden.py where oracle/_ref is built"
+    store = FUNCS[k][2] if k in FUNCS else STORE
+    if store not in _stored:
+        with np.load(store) as z:
+            _stored[store] = {n: z[n] for n in z.files}
+    want = {n[len(k) + 1:]: v for n, v in _stored[store].items() if n.startswith(k + "/")}
+    assert want, f"{store} has no reference outputs for {k}: run tests/golden/make_ref_golden.py where oracle/_ref is built"
     if ref is not None:
         live = compute(ref, tmp_dir, k)
         bad = sorted(n for n in live.keys() | want.keys() if n not in live or n not in want or not _same(live[n], want[n]))
-        assert not bad, f"{STORE} does not hold what oracle/_ref computes for {k} ({bad}): run tests/golden/make_ref_golden.py"
+        assert not bad, f"{store} does not hold what oracle/_ref computes for {k} ({bad}): run tests/golden/make_ref_golden.py"
     return want

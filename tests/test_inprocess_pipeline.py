@@ -10,8 +10,10 @@ import sys
 import numpy as np
 import pytest
 
+import refgolden
 import synth
 from conftest import synth_tool
+from test_gpu_dense import STORE as DENSE_STORE, file_sha256, ref_quantize, write_model
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -162,6 +164,14 @@ def test_runner_event_stream_through_the_pipeline_with_no_change_to_the_caller(t
     hp = synth.HParams(n_vocab=96, n_embd=256, n_mult=64, n_head=2, n_layer=4)
     path = str(tmp_path / "m.bin")
     synth.write_model(path, hp, synth.random_tensors(hp, seed=21))
+    res = _runner_streams(path, ("plain", "pipe", "pipe_count"))
+    assert res["plain"]["True"]["states"] == ["notStarted", "initializing", "generatingOutput", "completed"]
+    assert res["pipe"] == res["plain"] and res["pipe_count"] == res["plain"]
+    assert len(res["plain"]["False"]["toks"]) == len(res["plain"]["True"]["toks"])
+
+
+def _runner_streams(path, tags):
+    """the llama_runner_* event stream of one greedy and one sampled run on `path`, in a fresh process per device setting"""
     code = ("import sys, json, llama_swift_amd as L\n"
             "out = {}\n"
             "for greedy in (True, False):\n"
@@ -172,15 +182,115 @@ def test_runner_event_stream_through_the_pipeline_with_no_change_to_the_caller(t
             "print('JSON' + json.dumps(out))\n")
     res = {}
     for tag, env in (("plain", {}), ("pipe", {"LLAMAHIP_DEVICES": "0,0"}), ("pipe_count", {"LLAMAHIP_DEVICES": "1"})):
+        if tag not in tags:
+            continue
         e = dict(os.environ, PYTHONPATH=ROOT, **env)
         e.pop("LLAMAHIP_DEVICES", None) if not env else None
         r = subprocess.run([sys.executable, "-c", code, path], env=e, capture_output=True, text=True, cwd=ROOT, timeout=600)
         assert "JSON" in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
         import json
         res[tag] = json.loads(r.stdout.split("JSON", 1)[1])
+    return res
+
+
+# f16 / Q4_1 files and LLAMAHIP_FLAG_UNFUSED handles: no fused stage step, so the pipeline handle walks its stages with one eval per token
+_DENSE_PIPES = {
+    "f16_2_stages": ("odd_widths", "f16", [0, 0], 0),        # 2 + 1 layers; V 250, d 1344, H 21
+    "q4_1_3_stages": ("q41_odd", "q41", [0, 0, 0], 0),       # 1 + 1 + 1 layers; V 200, d 320, H 10
+    "q4_0_unfused_2_stages": (None, "q4_0", [0, 0], 2),      # LLAMAHIP_FLAG_UNFUSED, against the oracle
+}
+_DP_CTX, _DP_PROMPT, _DP_GREEDY = 96, 40, 12
+
+
+def _chunked_flow(rm, prompt, nth=8):
+    """what the bridge's flow leaves behind on a CPU model, one eval call at a time: the prompt in 9-token evals (last logits, every layer's
+    KV rows), 12 greedy steps (tokens, last logits), one more single-token eval (its logits)"""
+    for c0 in range(0, len(prompt), 9):
+        lo = rm.eval(prompt[c0:c0 + 9], c0, nth)["logits"]
+    out = {"prompt_last": lo}
+    for il in range(rm.n_layer):
+        k, v = rm.kv(il, len(prompt))
+        out[f"k{il}"], out[f"v{il}"] = refgolden.digest(k), refgolden.digest(v)
+    toks, n_past = [int(np.argmax(lo))], len(prompt)
+    for i in range(_DP_GREEDY):
+        lo = rm.eval(np.array([toks[-1]], np.int32), n_past, nth)["logits"]
+        toks.append(int(np.argmax(lo))); n_past += 1
+    out["greedy_tokens"], out["greedy_last"] = np.array(toks[1:], np.int32), lo
+    out["next"] = rm.eval(np.array([toks[-1]], np.int32), n_past, nth)["logits"]
+    return out
+
+
+@refgolden.computed_by("inprocess_pipeline.dense", [("odd_widths", "f16"), ("q41_odd", "q41")], store=DENSE_STORE)
+def _ref_dense_pipe(ref, tmp, shape, ftype):
+    path = write_model(tmp, shape, ftype, ref_quantize, n_layer=3)
+    rm = ref.load(path, _DP_CTX)
+    out = _chunked_flow(rm, synth.synth_prompt(_DP_PROMPT, rm.n_vocab, seed=64))
+    out["file_sha256"] = file_sha256(path)
+    rm.close()
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", sorted(_DENSE_PIPES))
+def test_dense_and_unfused_pipeline_handles_equal_the_plain_handle_and_the_reference(L, oracle, ref, tmp_path, case):
+    """f16 / Q4_1 files (against the reference build's stored outputs) and a Q4_0 LLAMAHIP_FLAG_UNFUSED handle (against the oracle), 3 layers
+    over 2 or 3 stages, next to a plain handle on the same file: eval_chunks = the reference's 9-token evals (logits, every layer's KV rows);
+    decode_greedy (tokens, last logits); eval_topk falls back to the logits row (exact = 0); decode_greedy_multi over 3 slots with their own
+    prompt lengths = decode_greedy on each slot alone, on both handles."""
+    shape, ftype, devices, flags = _DENSE_PIPES[case]
+    if ftype == "q4_0":
+        kw = dict(n_vocab=160, n_embd=512, n_mult=256, n_head=4, n_layer=3)
+        path = synth_tool(tmp_path / "m.bin", seed=53, **kw)
+        om = oracle.load(path, _DP_CTX)
+        want = _chunked_flow(om, synth.synth_prompt(_DP_PROMPT, kw["n_vocab"], seed=64))
+        om.close()
+    else:
+        want = refgolden.outputs("inprocess_pipeline.dense", ref, tmp_path, shape, ftype)
+        path = write_model(tmp_path, shape, ftype, lambda s, t: L.quantize_file(s, t, 3), n_layer=3)
+        assert same(file_sha256(path), want["file_sha256"])
+    with L.Model(path, n_ctx=_DP_CTX, flags=flags, n_seq=3) as one, L.Model(path, n_ctx=_DP_CTX, flags=flags, n_seq=3, devices=devices) as pm:
+        V = one.n_vocab
+        prompt = synth.synth_prompt(_DP_PROMPT, V, seed=64)
+        for tag, h in (("plain", one), ("pipeline", pm)):
+            lo = h.eval_chunks(prompt, 0, 9, 8)
+            assert same(lo, want["prompt_last"]), f"{tag}: eval_chunks logits"
+            for il in range(3):
+                k, v = h.kv(il, _DP_PROMPT)
+                assert same(refgolden.digest(k), want[f"k{il}"]) and same(refgolden.digest(v), want[f"v{il}"]), f"{tag}: KV rows of layer {il}"
+            toks, last = h.decode_greedy(int(np.argmax(lo)), _DP_PROMPT, _DP_GREEDY, 8, want_logits=True)
+            assert toks.tolist() == want["greedy_tokens"].tolist() and same(last, want["greedy_last"]), f"{tag}: decode_greedy"
+            n_past = _DP_PROMPT + _DP_GREEDY
+            if h is pm:
+                exact, _, _, lg = pm.eval_topk(np.array([toks[-1]], np.int32), n_past, L.Sampler(seed=-1, repeat_last_n=64))
+                assert not exact
+            else:
+                lg = one.eval(np.array([toks[-1]], np.int32), n_past, 8)
+            assert same(lg, want["next"]), f"{tag}: eval_topk / eval logits"
+        # three slots, three prompt lengths: slot 0 continues behind the eval above
+        firsts, n_pasts = [int(np.argmax(lg))], [n_past + 1]
+        for i, n in ((1, 13), (2, 22)):
+            q = synth.synth_prompt(n, V, seed=65 + n)
+            one.set_seq(i), pm.set_seq(i)
+            lo = one.eval_chunks(q, 0, 9, 8)
+            assert same(pm.eval_chunks(q, 0, 9, 8), lo), f"slot {i}: eval_chunks"
+            firsts.append(int(np.argmax(lo))); n_pasts.append(n)
+        alone = []
+        for i in range(3):
+            one.set_seq(i)
+            alone.append(one.decode_greedy(firsts[i], n_pasts[i], 10, 8).tolist())
+        for tag, h in (("pipeline", pm), ("plain", one)):
+            h.set_seq(0)
+            assert h.decode_greedy_multi(firsts, n_pasts, 10, 8).tolist() == alone, f"{tag}: decode_greedy_multi"
+
+
+@pytest.mark.gpu
+def test_runner_event_stream_through_a_dense_pipeline(L, tmp_path):
+    """the llama_runner_* event stream of an f16 file through LLAMAHIP_DEVICES=0,0 (eval_chunks and decode_greedy of a dense pipeline
+    handle) equals the plain handle's, greedy and sampled"""
+    path = write_model(tmp_path, "odd_widths", "f16", n_layer=3)
+    res = _runner_streams(path, ("plain", "pipe"))
     assert res["plain"]["True"]["states"] == ["notStarted", "initializing", "generatingOutput", "completed"]
-    assert res["pipe"] == res["plain"] and res["pipe_count"] == res["plain"]
-    assert len(res["plain"]["False"]["toks"]) == len(res["plain"]["True"]["toks"])
+    assert res["pipe"] == res["plain"]
 
 
 _MULTI = {
