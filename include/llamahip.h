@@ -69,8 +69,9 @@ typedef struct llamahip_opts {
 /* In-process layer pipeline (SURVEY.md section 8e behind the reference's own surface): the bridge makes ONE llama_model_load call from ONE
  * process (.mm:790; LlamaRunnerBridge.mm:18-26).  A handle loaded with n_devices > 1 -- or, for a caller that passes no options such as the
  * replacement bridge, with the environment variable LLAMAHIP_DEVICES="0,1,...,7" (or a count: "8" = devices 0 .. 7) -- holds one stage per
- * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_decode_greedy / llamahip_kv_read / llamahip_get_stats and the
- * llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690) crosses devices as stream-ordered peer copies.
+ * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_eval_logprobs / llamahip_perplexity / llamahip_decode_greedy /
+ * llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
+ * crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
  * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
  * LLAMAHIP_FLAG_UNFUSED decode one pipeline eval per token, the pick by the same argmax kernel).  The stage-level entry points (llamahip_eval_stage, llamahip_stage_*) and
@@ -122,6 +123,28 @@ int llamahip_eval(llamahip_model *m, int32_t n_threads, int32_t n_past,
 int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past,
                          const int32_t *tokens, int32_t n_tokens, int32_t chunk_tokens, float *logits_out,
                          char *err, size_t err_cap);
+
+/* ---- scoring a text (perplexity) ------------------------------------------------------------- */
+/* llamahip_eval / llamahip_eval_chunks (chunk_tokens 0 = one eval) + each row's next-token score, reduced on the device:
+ * only n_tokens * 16 bytes come back.  KV cache and logits_last (may be NULL) are bit for bit what
+ * llamahip_eval / llamahip_eval_chunks of the same arguments leave.  targets: n_tokens ids, -1 = not scored;
+ * NULL = tokens[i + 1] for i < n_tokens - 1, last row not scored.  Any of the three outputs may be NULL.
+ * Per row i: logprob_out[i] = log softmax(logits_i)[targets[i]] in double (0.0 for an unscored row), argmax_out[i] = the
+ * largest logit's index (the lowest on ties: the greedy pick), rank_out[i] = the number of logits strictly greater than the
+ * target's (0: the target was the greedy pick; -1 for an unscored row).  A row holding a NaN or a +inf gives NaN / -1 / -1.
+ * The log-probability is deterministic: a pure function of the row's logits (DESIGN.md "Scoring"). */
+int llamahip_eval_logprobs(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                           int32_t chunk_tokens, const int32_t *targets, double *logprob_out, int32_t *argmax_out,
+                           int32_t *rank_out, float *logits_last, char *err, size_t err_cap);
+
+/* Perplexity of a token stream: windows of `window` tokens (0 = n_ctx), floor(n_tokens / window) of them, the rest unused.
+ * Window k's first window - 1 tokens are evaluated at n_past 0 (chunk_tokens as above).  Row j predicts token k*window + j + 1
+ * and is scored if j >= score_from (-1 = window / 2, the usual tool's choice; 0 = every row).
+ * nll_sum = -sum(logprob) in double, in window order then row order; ppl = exp(nll_sum / n_scored).
+ * running_ppl (may be NULL): n_windows doubles, the ppl after each window.  Overwrites the current sequence slot's KV cache. */
+int llamahip_perplexity(llamahip_model *m, int32_t n_threads, const int32_t *tokens, int32_t n_tokens, int32_t window,
+                        int32_t score_from, int32_t chunk_tokens, double *nll_sum, int64_t *n_scored, double *running_ppl,
+                        char *err, size_t err_cap);
 
 /* Replaces ggml_free(model.ctx)  (.mm:900). */
 void llamahip_model_free(llamahip_model *m);
@@ -300,6 +323,10 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);
+/* the device half of llamahip_eval_logprobs on caller-supplied rows: logits[n_rows][n_vocab], targets n_rows ids (-1 = not scored,
+ * NULL = none scored); any of the three outputs may be NULL */
+int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
+                        double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap);
 /* runtime activation quantizer (ggml.c:456-523): x[k] -> k/32 blocks of 20 bytes */
 int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap);
 

@@ -23,6 +23,7 @@ from .binding import (  # noqa: F401
     declared_symbols,
     gemm_paths,
     lib,
+    op_logprob,
     op_mul_mat_q4_0,
     op_quantize_row_q4_0,
     op_topk,

@@ -2,6 +2,7 @@
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -85,6 +86,8 @@ def lib() -> C.CDLL:
     L.llamahip_model_load.argtypes = [cp, i32, C.POINTER(_Opts), C.POINTER(vp), cp, sz]
     L.llamahip_eval.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_eval_chunks.argtypes = [vp, i32, i32, vp, i32, i32, vp, cp, sz]
+    L.llamahip_eval_logprobs.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_perplexity.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp, vp, vp, cp, sz]
     L.llamahip_model_free.argtypes = [vp]
     for fn in ("n_vocab", "n_ctx", "n_embd", "n_head", "n_layer", "n_ff", "n_parts"):
         getattr(L, "llamahip_" + fn).argtypes = [vp]
@@ -127,6 +130,7 @@ def lib() -> C.CDLL:
     L.llamahip_op_mul_mat_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_op_quantize_row_q4_0.argtypes = [vp, i32, vp, cp, sz]
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
+    L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
     L.llamahip_get_stats.argtypes = [vp, C.POINTER(_Stats)]
     L.llamahip_debug_lut_math.restype = i32
@@ -249,6 +253,37 @@ class Model:
         rc = lib().llamahip_eval_chunks(self._h, n_threads, n_past, _ptr(tokens), tokens.size, chunk_tokens, _ptr(logits), err, len(err))
         _check(rc, err)
         return logits
+
+    def eval_logprobs(self, tokens, n_past: int, n_threads: int = 8, targets=None, chunk_tokens: int = 0) -> dict:
+        """eval / eval_chunks (chunk_tokens 0 = one eval) + every row's next-token score, reduced on the device: logprob (float64; 0.0 for
+        an unscored row), argmax, rank (logits strictly greater than the target's; -1 unscored), logits (the last row's).  targets: one id
+        per row, -1 = not scored; None = the next token of every row but the last."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        N = tokens.size
+        if targets is not None:
+            targets = np.ascontiguousarray(targets, np.int32)
+            if targets.size != N:
+                raise ValueError(f"targets: {targets.size} ids for {N} rows")
+        lp, am, rk = np.empty(N, np.float64), np.empty(N, np.int32), np.empty(N, np.int32)
+        last = np.empty(self.n_vocab, np.float32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_eval_logprobs(self._h, n_threads, n_past, _ptr(tokens), N, chunk_tokens, _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk),
+                                          _ptr(last), err, len(err))
+        _check(rc, err)
+        return {"logprob": lp, "argmax": am, "rank": rk, "logits": last}
+
+    def perplexity(self, tokens, window: int = 0, score_from: int = -1, n_threads: int = 8, chunk_tokens: int = 0) -> dict:
+        """Perplexity of a token stream over windows of `window` tokens (0 = n_ctx; the partial tail is unused), rows from score_from
+        (-1 = window / 2) scored: ppl, nll_sum, n_scored, running (the ppl after each window).  Overwrites the KV cache."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        w = window or self.n_ctx
+        running = np.zeros(max(tokens.size // w, 1) if w > 0 else 1, np.float64)
+        nll, n = C.c_double(0.0), C.c_int64(0)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_perplexity(self._h, n_threads, _ptr(tokens), tokens.size, window, score_from, chunk_tokens, C.byref(nll), C.byref(n),
+                                       _ptr(running), err, len(err))
+        _check(rc, err)
+        return {"ppl": math.exp(nll.value / n.value), "nll_sum": nll.value, "n_scored": n.value, "running": running[: tokens.size // w]}
 
     def eval_debug(self, tokens, n_past: int, n_threads: int = 8, all_logits: bool = True, dump_layer: int = -1) -> dict:
         tokens = np.ascontiguousarray(tokens, np.int32)
@@ -470,6 +505,23 @@ def op_topk(logits, window, repeat_penalty: float = 1.3, top_k: int = 40, temp: 
     rc = lib().llamahip_op_topk(_ptr(logits), logits.size, _ptr(window), window.size, repeat_penalty, top_k, temp, _ptr(sc), _ptr(ids), C.byref(exact), err, len(err))
     _check(rc, err)
     return bool(exact.value), sc[:top_k], ids[:top_k]
+
+
+def op_logprob(logits2d, targets=None):
+    """k_row_logprob on host rows f32 [n_rows, n_vocab]: returns (logprob float64, argmax int32, rank int32) per row; targets -1 = not scored."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    if targets is not None:
+        targets = np.ascontiguousarray(targets, np.int32)
+        if targets.size != R:
+            raise ValueError(f"targets: {targets.size} ids for {R} rows")
+    lp, am, rk = np.empty(R, np.float64), np.empty(R, np.int32), np.empty(R, np.int32)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_logprob(_ptr(logits2d), R, V, _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk), err, len(err))
+    _check(rc, err)
+    return lp, am, rk
 
 
 def op_mul_mat_q4_0(wq: np.ndarray, x: np.ndarray) -> np.ndarray:

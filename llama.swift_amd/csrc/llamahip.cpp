@@ -171,6 +171,10 @@ struct llamahip_model {
     float *qa1_d = nullptr, *qa2_d = nullptr;
     bool w13_interleaved = false;
     bool prompt_copies = false;          // the row-lane / matrix-core copies of the layer matrices exist (ensure_prompt_copies)
+    bool output_copies_tried = false;    // ... and of `output`, for the scoring entry points' all-rows lm head (ensure_output_copies)
+    bool score_rows = false;             // set around forward() by the scoring entry points: the all-rows lm head takes those copies
+    void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
+    int score_cap = 0;
     uint32_t *d_attn_sync = nullptr;     // per-head hand-off counters of k_dec_attn_x ([H][32] dwords); null: two-launch attention
     uint64_t *d_qkv2 = nullptr, *d_sc2 = nullptr;   // tagged hand-off buffers of k_qkv_attn: [3 d] and [H][n_ctx] {fp32 bits, tag} granules
     uint32_t *d_epoch = nullptr;         // ... and the epoch word their tags are made from (bumped once per decode forward pass)
@@ -265,7 +269,8 @@ llamahip_model::~llamahip_model() {
     free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
     free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
     free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk);
+    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score);
+    free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
     free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
     free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
     if (h_fault) { (void) hipHostFree(h_fault); h_fault = nullptr; }
@@ -403,6 +408,15 @@ int ensure_prompt_copies(llamahip_model *m, int N, char *err, size_t err_cap) {
             }
     m->prompt_copies = true;
     return 0;
+}
+// The lm head over EVERY row (llamahip_eval_logprobs / llamahip_perplexity) is a long-prompt GEMM of its own (7B: 32 000 x 4 096): from
+// 64 rows it gets `output`'s copies too, built once, by the same code, so that it can take k_gemm_mfma4.  Out of device memory: it keeps
+// the decode-tile kernels (bit-identical).  llamahip_eval / _chunks / _debug never build or read them (forward: score_rows).
+constexpr int OUTPUT_COPY_MIN_ROWS = 64;
+void ensure_output_copies(llamahip_model *m, int N) {
+    if (N < OUTPUT_COPY_MIN_ROWS || m->dense || m->output_copies_tried || (m->flags & LLAMAHIP_FLAG_NO_PREFILL_COPY)) return;
+    m->output_copies_tried = true;
+    (void) make_rows(m->output, m);
 }
 
 int upload_f32(llamahip_model *m, const std::string &name, float **dst, char *err, size_t err_cap) {
@@ -800,7 +814,10 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
             HIP_TRY(launch_gemv(m->output, PREP_NORM, EPI_STORE, nullptr, nullptr, m->x, m->norm_w, m->logits, nullptr, m->T_silu, nullptr, nullptr, st, &np_out), LLAMAHIP_ERR_PREDICT);
         } else if (want_all) {
             HIP_TRY(launch_prep(PREP_NORM, m->x, m->norm_w, d, 0, d, N, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
+            // (the scoring entry points: with `output`'s prompt copies and the operand workspace; llamahip_eval_debug: the decode tiles only)
+            QMat out = m->output;
+            if (!m->score_rows) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }
+            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st, m->score_rows ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_prep(PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
             HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
@@ -1257,8 +1274,9 @@ int llamahip_eval_topk(llamahip_model *m, int32_t n_threads, int32_t n_past, con
 }
 
 // the launches of a stage eval, enqueued on m->stream without waiting (llamahip_eval_stage; the in-process pipeline walks its stages with it)
+// (want_all: the last stage computes the logits of every row, for k_row_logprob -- the scoring entry points)
 static int eval_stage_enqueue(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, const void *hidden_in,
-                              int chunk, char *err, size_t err_cap) {
+                              int chunk, bool want_all, char *err, size_t err_cap) {
     int rc = check_eval_args(m, n_past, tokens, N, m && m->first_stage, err, err_cap);
     if (rc) return rc;
     if (!m->first_stage && !hidden_in) { set_err(err, err_cap, "stage [%d,%d) needs hidden_in", m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
@@ -1269,9 +1287,13 @@ static int eval_stage_enqueue(llamahip_model *m, int32_t n_threads, int32_t n_pa
     if (rc) return rc;
     rc = ensure_prompt_copies(m, N, err, err_cap);
     if (rc) return rc;
+    const bool all = want_all && m->last_stage;
+    if (all) ensure_output_copies(m, N);
     if (m->first_stage) HIP_TRY(hipMemcpyAsync(m->d_tokens, tokens, (size_t) N * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
     m->attn_sched = N == 1 ? attn_sched_at(m, n_past) : 0;
-    rc = forward(m, n_threads, n_past, N, (const float *) hidden_in, false, false, -1, nullptr, err, err_cap, nullptr, chunk);
+    m->score_rows = all;
+    rc = forward(m, n_threads, n_past, N, (const float *) hidden_in, false, all, -1, nullptr, err, err_cap, nullptr, chunk);
+    m->score_rows = false;
     m->last_rows.clear();                                                 // (m->logits rewritten: llamahip_stage_logits rows are this eval's rows again)
     return rc;
 }
@@ -1281,7 +1303,7 @@ int llamahip_eval_stage(llamahip_model *m, int32_t n_threads, int32_t n_past,
                         float *logits_out, char *err, size_t err_cap) {
     PIPE_REFUSE(m, "llamahip_eval_stage");
     const double t0 = now_ms();
-    int rc = eval_stage_enqueue(m, n_threads, n_past, tokens, N, hidden_in, 0, err, err_cap);
+    int rc = eval_stage_enqueue(m, n_threads, n_past, tokens, N, hidden_in, 0, false, err, err_cap);
     if (rc) return rc;
     const size_t d = m->hp.n_embd, V = m->hp.n_vocab;
     if (hidden_out) HIP_TRY(hipMemcpyAsync(hidden_out, m->x, (size_t) N * d * 4, hipMemcpyDeviceToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
@@ -1951,7 +1973,7 @@ static int pipe_eval(llamahip_model *m, int32_t n_threads, int32_t n_past, const
     for (int s = 0; s < S; s++) {
         llamahip_model *st = m->stages[s];
         st->cur_seq = m->cur_seq;
-        if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, st->dense ? 0 : chunk, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, st->dense ? 0 : chunk, false, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
     }
     // (the bounded wait first, the copy of the logits row behind it: a device-to-host copy into the caller's pageable buffer blocks inside the
@@ -1962,6 +1984,150 @@ static int pipe_eval(llamahip_model *m, int32_t n_threads, int32_t n_past, const
     if (logits_out) HIP_TRY(hipMemcpy(logits_out, last->logits + (size_t) (N - 1) * V, V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
     m->n_evals++;
     m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scoring a text: llamahip_eval_logprobs / llamahip_perplexity.  The eval is llamahip_eval's (llamahip_eval_chunks' with chunk_tokens)
+// except that the last stage's lm head runs over every row; k_row_logprob (logprob.hip) then reduces each row on that stage's stream, and
+// only the N x 16 bytes of results cross to the host.
+// ------------------------------------------------------------------------------------------------
+struct ScoreIo { double *lp; int32_t *am, *rk, *tgt; };
+static ScoreIo score_io(llamahip_model *m, int N) {
+    char *b = (char *) m->d_score;
+    return { (double *) b, (int32_t *) (b + 8L * N), (int32_t *) (b + 12L * N), (int32_t *) (b + 16L * N) };
+}
+// targets up, k_row_logprob over the N rows of m->logits, ordered behind the eval on m->stream
+static int score_enqueue(llamahip_model *m, int N, const int32_t *targets, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    if (N > m->score_cap) {
+        free_dev(m->d_score); m->d_score = nullptr; m->score_cap = 0;
+        HIP_TRY(hipMalloc(&m->d_score, (size_t) N * 20), LLAMAHIP_ERR_PREDICT);
+        m->score_cap = N;
+    }
+    const ScoreIo io = score_io(m, N);
+    HIP_TRY(hipMemcpyAsync(io.tgt, targets, (size_t) N * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_row_logprob(m->logits, N, m->hp.n_vocab, io.tgt, io.lp, io.am, io.rk, m->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// after the wait: the results of the N rows to the host in one copy
+static int score_fetch(llamahip_model *m, int N, double *lp, int32_t *am, int32_t *rk, char *err, size_t err_cap) {
+    std::vector<char> h((size_t) N * 16);
+    HIP_TRY(hipMemcpy(h.data(), m->d_score, h.size(), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    if (lp) memcpy(lp, h.data(), (size_t) N * 8);
+    if (am) memcpy(am, h.data() + (size_t) N * 8, (size_t) N * 4);
+    if (rk) memcpy(rk, h.data() + (size_t) N * 12, (size_t) N * 4);
+    return 0;
+}
+
+// one eval of N rows at n_past (chunk: the key split of llamahip_eval_chunks, 0 = none) + the scores of its rows, on a plain or a pipeline handle
+static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int chunk, const int32_t *targets,
+                      double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap) {
+    const double t0 = now_ms();
+    llamahip_model *last = m;
+    int rc;
+    if (m->stages.empty()) {
+        if ((rc = eval_stage_enqueue(m, n_threads, n_past, tokens, N, nullptr, chunk, true, err, err_cap)) != 0) return rc;
+        if ((rc = score_enqueue(m, N, targets, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+        if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
+    } else {
+        // pipe_eval's walk, the last stage with every row of logits and k_row_logprob behind it; the bounded wait before any copy to the host
+        const int S = (int) m->stages.size();
+        const size_t d = m->hp.n_embd;
+        for (int s = 1; s < S; s++) if ((rc = pipe_ensure_in(m->stages[s], N, err, err_cap)) != 0) return rc;
+        for (int s = 0; s < S; s++) {
+            llamahip_model *st = m->stages[s];
+            st->cur_seq = m->cur_seq;
+            if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, st->dense ? 0 : chunk, s == S - 1, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+            if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        }
+        last = m->stages[S - 1];
+        if ((rc = score_enqueue(last, N, targets, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = pipe_sync(m, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    }
+    if ((rc = score_fetch(last, N, lp, am, rk, err, err_cap)) != 0) return rc;
+    const size_t V = m->hp.n_vocab;
+    if (logits_last) HIP_TRY(hipMemcpy(logits_last, last->logits + (size_t) (N - 1) * V, V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+// llamahip_eval_chunks' split: f16 / f32 / Q4_1 files evaluate chunk by chunk (each chunk's rows scored), Q4_0 files in one pass
+static int logprobs_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int32_t chunk_tokens,
+                         const int32_t *targets, double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap) {
+    const bool chunked = chunk_tokens > 0 && N > chunk_tokens;
+    const bool dense = m->stages.empty() ? m->dense : m->stages[0]->dense;
+    if (!chunked || !dense) return eval_score(m, n_threads, n_past, tokens, N, chunked ? chunk_tokens : 0, targets, lp, am, rk, logits_last, err, err_cap);
+    for (int32_t c0 = 0; c0 < N; c0 += chunk_tokens) {
+        const int32_t n = std::min(chunk_tokens, N - c0);
+        const int rc = eval_score(m, n_threads, n_past + c0, tokens + c0, n, 0, targets + c0, lp ? lp + c0 : nullptr, am ? am + c0 : nullptr,
+                                  rk ? rk + c0 : nullptr, c0 + n == N ? logits_last : nullptr, err, err_cap);
+        if (rc) return rc;
+    }
+    return LLAMAHIP_OK;
+}
+
+// the arguments first (a HOST_ONLY handle knows n_vocab / n_ctx: the checks are the same without a device), then the handle
+static int check_score_args(llamahip_model *m, int32_t n_past, const int32_t *tokens, int32_t N, int32_t chunk_tokens, const int32_t *targets,
+                            const char *fn, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int V = m->hp.n_vocab, C = m->hp.n_ctx;
+    if (N < 1) { set_err(err, err_cap, "%s: n_tokens must be >= 1 (got %d)", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    if (n_past < 0 || n_past + N > C) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_tokens (%d) > n_ctx (%d)", fn, n_past, N, C); return LLAMAHIP_ERR_PREDICT; }
+    if (chunk_tokens < 0) { set_err(err, err_cap, "%s: chunk_tokens must be >= 0 (0 = one eval; got %d)", fn, chunk_tokens); return LLAMAHIP_ERR_PREDICT; }
+    if (!tokens) { set_err(err, err_cap, "%s: null tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < N; i++)
+        if (tokens[i] < 0 || tokens[i] >= V) { set_err(err, err_cap, "%s: token id %d at %d out of range [0, %d)", fn, tokens[i], i, V); return LLAMAHIP_ERR_PREDICT; }
+    if (targets)
+        for (int i = 0; i < N; i++)
+            if (targets[i] < -1 || targets[i] >= V) { set_err(err, err_cap, "%s: target %d of row %d out of range [-1, %d)", fn, targets[i], i, V); return LLAMAHIP_ERR_PREDICT; }
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, tokens, N, true, err, err_cap);      // (HOST_ONLY: refused here)
+}
+
+int llamahip_eval_logprobs(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                           int32_t chunk_tokens, const int32_t *targets, double *logprob_out, int32_t *argmax_out,
+                           int32_t *rank_out, float *logits_last, char *err, size_t err_cap) {
+    int rc = check_score_args(m, n_past, tokens, n_tokens, chunk_tokens, targets, "llamahip_eval_logprobs", err, err_cap);
+    if (rc) return rc;
+    std::vector<int32_t> tgt(n_tokens, -1);
+    if (targets) std::copy(targets, targets + n_tokens, tgt.begin());
+    else for (int i = 0; i + 1 < n_tokens; i++) tgt[i] = tokens[i + 1];
+    return logprobs_impl(m, n_threads, n_past, tokens, n_tokens, chunk_tokens, tgt.data(), logprob_out, argmax_out, rank_out, logits_last, err, err_cap);
+}
+
+int llamahip_perplexity(llamahip_model *m, int32_t n_threads, const int32_t *tokens, int32_t n_tokens, int32_t window,
+                        int32_t score_from, int32_t chunk_tokens, double *nll_sum, int64_t *n_scored, double *running_ppl,
+                        char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "llamahip_perplexity: null model"); return LLAMAHIP_ERR_PREDICT; }
+    const int C = m->hp.n_ctx;
+    const int W = window == 0 ? C : window;
+    if (window < 0 || W < 2) { set_err(err, err_cap, "llamahip_perplexity: window must be >= 2 tokens (0 = n_ctx; got %d)", window); return LLAMAHIP_ERR_PREDICT; }
+    if (W - 1 > C) { set_err(err, err_cap, "llamahip_perplexity: window %d: its %d evaluated tokens exceed n_ctx (%d)", W, W - 1, C); return LLAMAHIP_ERR_PREDICT; }
+    if (!tokens || n_tokens < W) { set_err(err, err_cap, "llamahip_perplexity: a stream of %d tokens is shorter than one window of %d", n_tokens, W); return LLAMAHIP_ERR_PREDICT; }
+    const int sf = score_from == -1 ? W / 2 : score_from;
+    if (score_from < -1 || sf > W - 2) { set_err(err, err_cap, "llamahip_perplexity: score_from %d: rows 0 .. %d of a window of %d predict a token (-1 = window / 2)", score_from, W - 2, W); return LLAMAHIP_ERR_PREDICT; }
+    const int n_win = n_tokens / W;
+    for (int i = 0; i < n_win * W; i++)
+        if (tokens[i] < 0 || tokens[i] >= m->hp.n_vocab) { set_err(err, err_cap, "llamahip_perplexity: token id %d at %d out of range [0, %d)", tokens[i], i, m->hp.n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    int rc = check_score_args(m, 0, tokens, W - 1, chunk_tokens, nullptr, "llamahip_perplexity", err, err_cap);
+    if (rc) return rc;
+    std::vector<int32_t> tgt(W - 1);
+    std::vector<double> lp(W - 1);
+    double nll = 0.0;
+    int64_t cnt = 0;
+    for (int k = 0; k < n_win; k++) {
+        const int32_t *win = tokens + (size_t) k * W;
+        for (int j = 0; j < W - 1; j++) tgt[j] = j >= sf ? win[j + 1] : -1;
+        if ((rc = logprobs_impl(m, n_threads, 0, win, W - 1, chunk_tokens, tgt.data(), lp.data(), nullptr, nullptr, nullptr, err, err_cap)) != 0) return rc;
+        for (int j = sf; j < W - 1; j++) { nll -= lp[j]; cnt++; }
+        if (running_ppl) running_ppl[k] = exp(nll / (double) cnt);
+    }
+    if (nll_sum) *nll_sum = nll;
+    if (n_scored) *n_scored = cnt;
     return LLAMAHIP_OK;
 }
 
@@ -2314,6 +2480,33 @@ int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n
     HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
     *exact = h.fl[0];
     for (int i = 0; i < top_k; i++) { cand_scores[i] = h.sc[i]; cand_ids[i] = h.id[i]; }
+    return LLAMAHIP_OK;
+}
+
+// k_row_logprob on caller-supplied rows (parity tests): see llamahip_eval_logprobs
+int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
+                        double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap) {
+    if (!logits || n_rows < 1 || n_vocab < 1) { set_err(err, err_cap, "llamahip_op_logprob: bad arguments (n_rows %d, n_vocab %d)", n_rows, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (targets)
+        for (int i = 0; i < n_rows; i++)
+            if (targets[i] < -1 || targets[i] >= n_vocab) { set_err(err, err_cap, "llamahip_op_logprob: target %d of row %d out of range [-1, %d)", targets[i], i, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    int rc = need_device(err, err_cap);
+    if (rc) return rc;
+    const size_t N = (size_t) n_rows, row_bytes = (size_t) n_vocab * 4;
+    float *d_l = nullptr; char *d_s = nullptr;
+    std::vector<char> h(N * 16);
+    hipError_t e = hipMalloc((void **) &d_l, N * row_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **) &d_s, N * 20);
+    int32_t *d_t = d_s ? (int32_t *) (d_s + 16 * N) : nullptr;
+    if (e == hipSuccess) e = hipMemcpy(d_l, logits, N * row_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = targets ? hipMemcpy(d_t, targets, N * 4, hipMemcpyHostToDevice) : hipMemset(d_t, 0xFF, N * 4);      // (0xFFFFFFFF = -1)
+    if (e == hipSuccess) e = launch_row_logprob(d_l, n_rows, n_vocab, d_t, (double *) d_s, (int32_t *) (d_s + 8 * N), (int32_t *) (d_s + 12 * N), nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d_s, N * 16, hipMemcpyDeviceToHost);
+    free_dev(d_l); free_dev(d_s);
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
+    if (logprob_out) memcpy(logprob_out, h.data(), N * 8);
+    if (argmax_out) memcpy(argmax_out, h.data() + N * 8, N * 4);
+    if (rank_out) memcpy(rank_out, h.data() + N * 12, N * 4);
     return LLAMAHIP_OK;
 }
 

@@ -214,6 +214,10 @@ hipError_t launch_advance(int32_t *state, hipStream_t st);
 hipError_t launch_topk_candidates(const float *logits, int V, const int32_t *window, int n_window, double scale, double repeat_penalty, int k,
                                   double *out_score, int32_t *out_id, int32_t *flags, hipStream_t st, void *ws = nullptr);      // ws: TOPK_WS_BYTES zeroed once -> the two-launch variant
 constexpr size_t TOPK_WS_BYTES = 32768 * 8 + 64 * 8 + 64;
+// next-token scoring of n_rows rows of logits (logprob.hip): per row the log-probability of targets[r] in double, the argmax (lowest index
+// on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
+hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,
+                              hipStream_t st);
 hipError_t launch_argmax(const float *logits, int V, int32_t *out, int out_idx, int32_t *next_token, int32_t *state, hipStream_t st, uint64_t *token_mb = nullptr);
 
 }  // namespace lh
