@@ -10,9 +10,14 @@ the 7B architecture written in the reference's exact file format by csrc/tools/m
 the prompt is synthetic token ids.  One *step* = one decoded token = one pass of the hot path
 (llama_eval with one token at a growing context offset) including the greedy argmax that feeds the
 next step on the device.  `value` = tokens/s with everything resident in HBM (logits are not copied
-back per token inside the timed region; the PCIe-inclusive rate is reported as `value_pcie`).
+back per token inside the timed region; --full reports the PCIe-inclusive rate as `value_pcie`).
 
-Objects next to the contract's fields (N = 1):
+A plain run sets up (synthetic model file, load, prompt), warms up, times the steps, writes --dump-outputs and
+prints the line: the contract's fields, `load_s`, `roofline.end_to_end_frac` (from `ms_per_step`, no run of its
+own) and `full_context` when the timed run fills the context.  `--full` adds everything below after the timed
+steps, each leg in runs of its own; the headline fields are the same either way.
+
+Objects next to the contract's fields (N = 1, --full):
   roofline      the dominant kernel of the decode step AS IT RUNS IN THE STEP: the w1|w3 mat-vec with its norm
                 prologue and SiLU*up -> Q4_0 epilogue.  Its average duration (and that of every other launch of
                 the captured step) comes from a rocprofv3 --kernel-trace run of the same decode loop in a child
@@ -32,7 +37,8 @@ Objects next to the contract's fields (N = 1):
 
 N > 1: the model is layer-sharded into N pipeline stages (one process per GPU); independent greedy sequences are
 kept in flight round-robin so every stage is busy, and the residual stream crosses stages with point-to-point RCCL
-send/recv.  value = all sequences' tokens / time, scaling = "weak".
+send/recv.  value = all sequences' tokens / time, scaling = "weak".  --full adds rank 0's in-situ stage
+roofline, the single-stream latency leg, the parity gate against the CPU path and the 65B leg.
 """
 import argparse
 import csv
@@ -409,7 +415,18 @@ def run_single(args, cfg, path):
         np.save(os.path.join(args.dump_outputs, "tokens.npy"), calls[-1].astype(np.float64))
         np.save(os.path.join(args.dump_outputs, "logits.npy"), last_logits.astype(np.float32))
         log(f"[bench] wrote tokens.npy ({len(calls[-1])}) and logits.npy ({len(last_logits)}) to {args.dump_outputs}")
-    gpu_trace = [int(x) for x in warm] + [int(x) for x in out]     # every token generated after the prompt's pick `first` (extended by the full-context run below)
+    gpu_trace = [int(x) for x in warm] + [int(x) for x in out]     # every token generated after the prompt's pick `first` (extended by the full-context run of --full)
+    res = dict(steps=steps, window=len(out), dt=dt, t_load=t_load, first=first, gpu_trace=gpu_trace, n_past0=n_past, model=m)
+    if args.full:
+        res.update(single_extras(args, cfg, m, prompt, tok, n_past, warm, out))
+    return res
+
+
+def single_extras(args, cfg, m, prompt, tok, n_past, warm, out):
+    """(--full) what the single-GPU line reports next to the timed steps, on the same handle after them: the PCIe-inclusive loop, the
+    full-context run, the stand-alone mat-vec probe and the prompt evaluations."""
+    steps = args.steps
+    gpu_trace = [int(x) for x in warm] + [int(x) for x in out]
     # PCIe-inclusive variant: the reference boundary (llama_eval returning host logits every token); its tokens must
     # be those of the device-resident loop
     n_pcie = min(64, len(out))
@@ -471,10 +488,8 @@ def run_single(args, cfg, path):
         t_ = int(np.argmax(lg0))
         _, last = m.decode_greedy(t_, len(prompt), n_tokens, args.threads, want_logits=True)
         return last
-    res = dict(steps=steps, window=len(out), dt=dt, t_load=t_load, value_pcie=n_pcie / dt_pcie, pcie_same=pcie_same, shapes=shapes,
-               gemv_bytes_per_token=tot_bytes, gemv_us_per_token=tot_us, prefill=prefill, first=first, gpu_trace=gpu_trace,
-               n_past0=n_past, gpu_logits_at=gpu_logits_at, model=m, full=full)
-    return res
+    return dict(value_pcie=n_pcie / dt_pcie, pcie_same=pcie_same, shapes=shapes, gemv_bytes_per_token=tot_bytes, gemv_us_per_token=tot_us,
+                prefill=prefill, gpu_trace=gpu_trace, gpu_logits_at=gpu_logits_at, full=full)
 
 
 def inprocess_pipeline(args, cfg, path, n_stages, single_trace):
@@ -698,6 +713,9 @@ def pipeline_bench_main(args, cfg, model_path_fn, log, models=None, env=None, em
         raise SystemExit(f"bench.py --gpus {args.gpus} must be launched with {args.gpus} ranks (WORLD_SIZE={world}); "
                          f"use: python -m torch.distributed.run --nnodes=1 --nproc-per-node {args.gpus} bench.py --gpus {args.gpus}")
     in_test = env is not None
+    # --full: the extra legs after the timed loop.  A caller that builds its own `args` without the option gets all of them, as this
+    # function ran before the option existed
+    full = getattr(args, "full", True)
     # RCCL prints a version banner on STDOUT when it creates a communicator; the bench contract is ONE
     # JSON line on stdout, so everything before that line goes to stderr at the file-descriptor level
     saved_stdout = None
@@ -855,7 +873,7 @@ def pipeline_bench_main(args, cfg, model_path_fn, log, models=None, env=None, em
             dt_loc = time.perf_counter() - t0
             # single-stream latency, measured: sequence 0 alone through all stages
             single = None
-            if world > 1:
+            if world > 1 and full:
                 dist.barrier(); env.sync()
                 t1 = time.perf_counter()
                 guard(lambda: decode(n_single, [0]), "decode (single stream)")
@@ -864,14 +882,15 @@ def pipeline_bench_main(args, cfg, model_path_fn, log, models=None, env=None, em
                 dist.all_reduce(ds, op=dist.ReduceOp.MAX)
                 single = {"tokens": n_single, "ms_per_token": float(ds.item()) * 1e3 / n_single, "tokens_per_s": n_single / float(ds.item()),
                           "note": "sequence 0 alone: one token at a time through every stage (the latency a single user sees)"}
-            traces, _pos = guard(lambda: gather_traces(stage, rank, world, dist, torch, S, handshake_tokens + warmup + steps + (n_single if world > 1 else 0)), "gather_traces")
+            if full:                # (the parity gate's input)
+                traces, _pos = guard(lambda: gather_traces(stage, rank, world, dist, torch, S, handshake_tokens + warmup + steps + (n_single if world > 1 else 0)), "gather_traces")
         dt = torch.tensor([dt_loc], dtype=torch.float64, device=dev)
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)
         dt = float(dt.item())
         # parity gate: sequence 0's prompt pick and first generated tokens against the CPU path (rank 0 computes it, bounded);
         # in set mode also the last sequence of the last set (another row of a batched step, another position)
         parity = {"checked": False}
-        if rank == 0 and parity_tokens > 0:
+        if rank == 0 and parity_tokens > 0 and full:
             try:
                 budget = float(os.environ.get("LLAMAHIP_PIPE_PARITY_S", "30"))
                 checked = []
@@ -889,7 +908,7 @@ def pipeline_bench_main(args, cfg, model_path_fn, log, models=None, env=None, em
             except Exception as e:                              # the checker must never take the measurement down
                 parity = {"checked": False, "error": repr(e)}
         lo_, hi_ = layer_range(mcfg["n_layer"], 0, world)
-        roof = env.stage_roofline(stage, args, mcfg, model_name, hi_ - lo_, per_stage if set_mode else 1, rank)
+        roof = env.stage_roofline(stage, args, mcfg, model_name, hi_ - lo_, per_stage if set_mode else 1, rank) if full else None
         env.close_stage(stage)
         return dict(S=S, steps=steps, dt=dt, parity=parity, roof=roof, single=single, hand_off=hand_off, n_layer=mcfg["n_layer"], set_mode=set_mode)
 
@@ -914,13 +933,13 @@ def pipeline_bench_main(args, cfg, model_path_fn, log, models=None, env=None, em
             "roofline": r["roof"],
             "parity": r["parity"],
             "cpu_baseline": None,
-            "cpu_baseline_note": "timed at N = 1 only (bench.py --gpus 1)",
+            "cpu_baseline_note": "timed at N = 1 only (bench.py --gpus 1 --full)",
             "single_stream": r["single"],
             "schedule": "host-synchronous" if sync_schedule else "stream-ordered (hipGraph stage steps, device-side greedy pick)",
         })
-    # BASELINE.json configs[4]: the 65B model is what the 8-GPU pipeline is for.  A bounded extra leg (32 timed steps) with its OWN
+    # BASELINE.json configs[4]: the 65B model is what the 8-GPU pipeline is for.  A bounded extra leg of --full (32 timed steps) with its OWN
     # timer, reported next to the headline; whatever happens to it -- on any rank -- the headline above is printed and every rank exits 0.
-    if models and args.model != "65B" and os.environ.get("LLAMAHIP_BENCH_65B", "1") != "0" and "65B" in models:
+    if full and models and args.model != "65B" and os.environ.get("LLAMAHIP_BENCH_65B", "1") != "0" and "65B" in models:
         leg_limit = float(os.environ.get("LLAMAHIP_PIPE_65B_S", "420"))
         leg_timer = threading.Timer(leg_limit, lambda: (os.write(2, f"[bench] rank {rank}: the 65B leg did not finish in {leg_limit:.0f} s; the headline stands\n".encode()), _emit_and_exit(0)))
         leg_timer.daemon = True
@@ -1015,6 +1034,51 @@ def prefill_2048(args, cfg, path):
                                   "included) is divided by the peaks here"}}
 
 
+def headline(args, cfg, r, tps, ms_step):
+    """The single-GPU line as far as the timed steps give it: all a plain run prints, and what --full adds its legs to."""
+    t_mid = r["n_past0"] + r["window"] // 2
+    e2e_bytes = token_bytes(cfg, t_mid)
+    roof = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+            "end_to_end": {"bytes_per_token": e2e_bytes, "at_position": t_mid, "GBps": e2e_bytes / (ms_step * 1e-3) / 1e9,
+                           "frac": e2e_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                           "note": "W + KV(t) + small of SURVEY.md 8d at the middle position of the timed run / ms_per_step / 8 TB/s"},
+            "end_to_end_frac": e2e_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS}
+    if not args.full:
+        roof["note"] = "end to end only: the in-situ per-launch figures of the decode step are measured by bench.py --full"
+    fills = r["steps"] >= args.n_ctx - len(PROMPT) - args.warmup
+    result = {
+        "metric": "decode tokens/sec LLaMA-7B Q4_0 @1 GPU; % HBM-roofline on Q4_0 GEMV",
+        "value": tps, "unit": "tokens/s", "n_gpus": 1, "steps": r["steps"], "warmup": args.warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "q4_0 x q4_0 -> int32 block sums, fp32 scales/accumulate",
+        "data": "synthetic (random-init 7B-architecture weights in the reference file format, synthetic token ids)",
+        "config": {"workload": f"LLaMA-{args.model} Q4_0 single-token decode, greedy, n_ctx {args.n_ctx}: `value` = {r['steps']} timed tokens at context positions "
+                               f"{r['n_past0']} .. {r['n_past0'] + r['window'] - 1}{' (repeated)' if r['steps'] > r['window'] else ''} (after 8 prompt + {args.warmup} warm-up tokens); BASELINE.json configs[1] proper -- the generation "
+                               f"to the end of the {args.n_ctx}-token context -- is config.full_context_tokens_per_s / roofline.full_context_*"
+                               f"{'' if args.full or fills else ' of bench.py --full'}",
+                   "n_threads_semantics": args.threads, "parallelism": "1 GPU"},
+        "load_s": r["t_load"],
+        "roofline": roof,
+        "parity": {"checked": False, "note": "bench.py --full checks the timed run's tokens against the CPU path"},
+    }
+    if r.get("full"):
+        fc = r["full"]
+        fb = token_bytes(cfg, len(PROMPT) + args.warmup + fc["steps"] // 2)
+        fms = fc["seconds"] * 1e3 / fc["steps"]
+        result["full_context"] = {"workload": f"configs[1]: {fc['steps']} generated tokens to context {args.n_ctx} (8 prompt + {args.warmup} warm-up before them)",
+                                  "steps": fc["steps"], "tokens_per_s": fc["steps"] / fc["seconds"], "ms_per_step": fms,
+                                  "end_to_end_frac": fb / (fms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "tokens_continue_the_timed_run": fc["same_prefix"]}
+    elif fills:
+        result["full_context"] = {"workload": "the timed run IS configs[1]: it fills the context", "steps": r["steps"], "tokens_per_s": tps, "ms_per_step": ms_step,
+                                  "end_to_end_frac": roof["end_to_end_frac"]}
+    # figures that must survive a reader that keeps only metric / value / config / roofline of this line
+    if "full_context" in result:
+        result["roofline"]["full_context_tokens_per_s"] = result["full_context"]["tokens_per_s"]
+        result["roofline"]["full_context_end_to_end_frac"] = result["full_context"]["end_to_end_frac"]
+        result["config"]["full_context_tokens_per_s"] = result["full_context"]["tokens_per_s"]
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1024,13 +1088,18 @@ def main():
     ap.add_argument("--n_ctx", type=int, default=512)
     ap.add_argument("--threads", type=int, default=8, help="reference n_threads (selects its V*P summation split)")
     ap.add_argument("--seed", type=int, default=20230312)
-    ap.add_argument("--gemv-iters", type=int, default=20)
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-insitu", action="store_true", help="skip the rocprofv3 child that times the launches of the decode step")
-    ap.add_argument("--no-prefill-2048", action="store_true")
-    ap.add_argument("--no-concurrent", action="store_true", help="skip the concurrent-sequences leg (2 and 4 independent sequences on the one GPU)")
-    ap.add_argument("--save-profile", default="", help="write the in-situ kernel table (rocprofv3 summary) to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run everything else the bench measures and checks: the CPU parity gate and baselines, the in-situ "
+                         "roofline children, prompt evaluation, the other sequence / pipeline configurations (N > 1: the parity gate, the stage "
+                         "roofline, the single-stream and 65B legs).  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--gemv-iters", type=int, default=20, help="(--full) launches per shape of the stand-alone mat-vec probe")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="(--full) budget of the CPU decode behind the parity gate")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU parity gate and baselines")
+    ap.add_argument("--no-insitu", action="store_true", help="(--full) skip the rocprofv3 child that times the launches of the decode step")
+    ap.add_argument("--no-prefill-2048", action="store_true", help="(--full) skip configs[2]'s 2048-token prompt")
+    ap.add_argument("--no-concurrent", action="store_true", help="(--full) skip the concurrent-sequences leg (2 and 4 independent sequences on the one GPU) "
+                                                                 "and the batched and in-process pipeline legs")
+    ap.add_argument("--save-profile", default="", help="(--full) write the in-situ kernel table (rocprofv3 summary) to this file")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the last timed call returned to DIR: tokens.npy (float64) and the last step's logits.npy (float32)")
     ap.add_argument("--insitu-child", action="store_true", help=argparse.SUPPRESS)
@@ -1063,6 +1132,11 @@ def main():
     m = r.pop("model")
     tps = r["steps"] / r["dt"]
     ms_step = r["dt"] * 1e3 / r["steps"]
+    if not args.full:
+        m.close()
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, r, tps, ms_step)), flush=True)
+        return
 
     # ---- parity gate + CPU baselines (the CPU path decodes the same prompt: its tokens check the timed run)
     parity = {"checked": False}
@@ -1106,14 +1180,9 @@ def main():
     probe = {"note": "stand-alone k_gemv<PRE_QA, EPI_STORE> launched back to back over all layers (HIP events); never runs in the decode step",
              "per_shape": [{k: s[k] for k in ("name", "M", "K", "us_per_launch", "GBps")} for s in r["shapes"]],
              "all_gemv_launches_of_a_token": {"GBps": r["gemv_bytes_per_token"] / (r["gemv_us_per_token"] * 1e-6) / 1e9}}
-    t_mid = r["n_past0"] + r["window"] // 2
-    e2e_bytes = token_bytes(cfg, t_mid)
-    roof = {"bound": "hbm", "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-            "end_to_end": {"bytes_per_token": e2e_bytes, "at_position": t_mid, "GBps": e2e_bytes / (ms_step * 1e-3) / 1e9,
-                           "frac": e2e_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                           "note": "W + KV(t) + small of SURVEY.md 8d at the middle position of the timed run / ms_per_step / 8 TB/s"},
-            "end_to_end_frac": e2e_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-            "probe_back_to_back": probe}
+    result = headline(args, cfg, r, tps, ms_step)
+    roof = result["roofline"]
+    roof["probe_back_to_back"] = probe
     traffic = None
     traffic_src = None
     pmc, pmc_err = (None, "skipped") if args.no_insitu else insitu_traffic(args, cfg)
@@ -1185,31 +1254,8 @@ def main():
                      "achieved": dom["GBps"], "frac": dom["GBps"] / HBM_PEAK_GBPS, "algorithmic_bytes_per_launch": dom["algo_bytes"],
                      "us_per_launch": dom["us_per_launch"], "traffic": None, "traffic_committed": traffic_committed, "method": "HIP events over back-to-back launches (probe variant, not in situ)"})
 
-    result = {
-        "metric": "decode tokens/sec LLaMA-7B Q4_0 @1 GPU; % HBM-roofline on Q4_0 GEMV",
-        "value": tps, "unit": "tokens/s", "n_gpus": 1, "steps": r["steps"], "warmup": args.warmup,
-        "ms_per_step": ms_step, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "q4_0 x q4_0 -> int32 block sums, fp32 scales/accumulate",
-        "data": "synthetic (random-init 7B-architecture weights in the reference file format, synthetic token ids)",
-        "config": {"workload": f"LLaMA-{args.model} Q4_0 single-token decode, greedy, n_ctx {args.n_ctx}: `value` = {r['steps']} timed tokens at context positions "
-                               f"{r['n_past0']} .. {r['n_past0'] + r['window'] - 1}{' (repeated)' if r['steps'] > r['window'] else ''} (after 8 prompt + {args.warmup} warm-up tokens); BASELINE.json configs[1] proper -- the generation "
-                               f"to the end of the {args.n_ctx}-token context -- is config.full_context_tokens_per_s / roofline.full_context_*",
-                   "n_threads_semantics": args.threads, "parallelism": "1 GPU"},
-        "value_pcie": r["value_pcie"],
-        "load_s": r["t_load"],
-        "roofline": roof,
-        "parity": parity,
-    }
-    if r.get("full"):
-        fc = r["full"]
-        fb = token_bytes(cfg, len(PROMPT) + args.warmup + fc["steps"] // 2)
-        fms = fc["seconds"] * 1e3 / fc["steps"]
-        result["full_context"] = {"workload": f"configs[1]: {fc['steps']} generated tokens to context {args.n_ctx} (8 prompt + {args.warmup} warm-up before them)",
-                                  "steps": fc["steps"], "tokens_per_s": fc["steps"] / fc["seconds"], "ms_per_step": fms,
-                                  "end_to_end_frac": fb / (fms * 1e-3) / 1e9 / HBM_PEAK_GBPS, "tokens_continue_the_timed_run": fc["same_prefix"]}
-    elif r["steps"] >= args.n_ctx - len(PROMPT) - args.warmup:
-        result["full_context"] = {"workload": "the timed run IS configs[1]: it fills the context", "steps": r["steps"], "tokens_per_s": tps, "ms_per_step": ms_step,
-                                  "end_to_end_frac": roof["end_to_end_frac"]}
+    result["value_pcie"] = r["value_pcie"]
+    result["parity"] = parity
     if cpu_base is not None:
         result["cpu_baseline"] = cpu_base
     result["prefill"] = r["prefill"]
@@ -1240,10 +1286,6 @@ def main():
         except Exception as e:
             result["inprocess_pipeline_multi"] = {"error": repr(e)}
     # figures that must survive a reader that keeps only metric / value / config / roofline of this line
-    if "full_context" in result:
-        result["roofline"]["full_context_tokens_per_s"] = result["full_context"]["tokens_per_s"]
-        result["roofline"]["full_context_end_to_end_frac"] = result["full_context"]["end_to_end_frac"]
-        result["config"]["full_context_tokens_per_s"] = result["full_context"]["tokens_per_s"]
     # (scalars only: nested objects of config / roofline do not survive such a reader)
     if isinstance(result.get("inprocess_pipeline"), list):
         for b in result["inprocess_pipeline"]:

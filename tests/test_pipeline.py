@@ -275,7 +275,7 @@ class _CpuEnv:
         pass
 
 
-def _bench_main_worker(rank, world, init_file, out_dir, env_extra):
+def _bench_main_worker(rank, world, init_file, out_dir, env_extra, full=True):
     sys.path.insert(0, ROOT); sys.path.insert(0, HERE)
     import argparse
     import json
@@ -294,7 +294,7 @@ def _bench_main_worker(rank, world, init_file, out_dir, env_extra):
             synth.write_model(path + ".tmp", hp, synth.random_tensors(hp, seed=seed % 1000))
             os.replace(path + ".tmp", path)
         return path
-    args = argparse.Namespace(gpus=world, steps=3, warmup=1, model="tiny8", n_ctx=64, threads=8, seed=20230312)
+    args = argparse.Namespace(gpus=world, steps=3, warmup=1, model="tiny8", n_ctx=64, threads=8, seed=20230312, full=full)
     def emit(line):                                 # (written at once: a failing extra leg ends the process right after emitting)
         json.dump([line], open(os.path.join(out_dir, "line.json"), "w"))
     bench.pipeline_bench_main(args, cfgs["tiny8"], model_path, lambda *a: None, cfgs, env=_CpuEnv(), emit=emit)
@@ -371,6 +371,21 @@ def test_bench_pipeline_control_flow_at_world_8_gloo(built, tmp_path, mode):
     assert "error" not in leg, leg
     assert "80 layers over 8 stages" in leg["workload"] and leg["parity"]["checked"] and leg["parity"]["identical"], leg
     assert line["single_stream"]["tokens"] == 16
+
+
+def test_bench_pipeline_plain_run_skips_the_extra_legs_gloo(built, tmp_path):
+    """`bench.py --gpus 2` without --full: prompt rounds, warm-up and the timed loop give the line; the single-stream leg, the trace gather,
+    the parity gate, the stage roofline and the 65B leg do not run."""
+    import json
+
+    import torch.multiprocessing as mp
+    world = 2
+    env_extra = {"LLAMAHIP_PIPE_SEQS_PER_STAGE": "2", "LLAMAHIP_PIPE_SET": "1", "LLAMAHIP_PIPE_65B_STEPS": "2", "ORC_OMP_THREADS": "1"}
+    mp.spawn(_bench_main_worker, args=(world, str(tmp_path / "rdv"), str(tmp_path), env_extra, False), nprocs=world, join=True)
+    line, = json.load(open(tmp_path / "line.json"))
+    assert line["n_gpus"] == 2 and line["config"]["sequences"] == 4 and line["steps"] == 3 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["parity"] == {"checked": False} and line["roofline"] is None and line["single_stream"] is None
+    assert "config4_65B" not in line and not os.path.exists(os.path.join(str(tmp_path), "65B.bin"))
 
 @pytest.mark.gpu
 def test_hip_stage_in_the_pipeline_schedule_single_rank(L, tmp_path):

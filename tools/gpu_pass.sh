@@ -9,10 +9,10 @@
 #   x      soft_max ablation of k_dec_pv_dma at 2 048 keys (libllamahip_pvabl.so)
 #   pf     long-prompt A/B of library / switch variants (VARIANTS) + the prompt parity tests
 #   w13    whole- vs half-block w1|w3 workgroups of the few-row kernel + 9-row plans (fresh processes), the variant parity test
-#   verify the last check of a tree: full GPU suite, smoke(), bench.py with defaults, chunk / prefill probes
+#   verify the last check of a tree: full GPU suite, smoke(), bench.py --full, chunk / prefill probes
 #   nccl   the RCCL branch of the pipeline bench at world 1 (communicators, self-check, forced one-rank schedule) with its log
 #   65b    BASELINE configs[4]'s model on one GPU: the forced one-rank pipeline in set mode (in-situ roofline of the stage step, parity gate)
-#   final  everything profiles/<tag>_* is made from: full GPU test suite, bench.py (7B, 13B), config[3] mixed run with HBM counters,
+#   final  everything profiles/<tag>_* is made from: full GPU test suite, bench.py --full (7B, 13B), config[3] mixed run with HBM counters,
 #          prefill kernel table, prompt / chunk / runner probes, set-step tables + PMC, fresh-process set / eval rates
 pass=${1:-quick}; tag=${2:-r06_$pass}
 O=gpurun_out; mkdir -p $O; R=$PWD
@@ -51,7 +51,7 @@ mid)
   set_tables
   ;;
 nccl)
-  LLAMAHIP_FORCE_PIPELINE=1 LLAMAHIP_BENCH_65B=0 timeout 900 python bench.py --steps 64 --warmup 8 > $O/${tag}_nccl_world1.json 2> $O/${tag}_nccl_world1.log
+  LLAMAHIP_FORCE_PIPELINE=1 LLAMAHIP_BENCH_65B=0 timeout 900 python bench.py --full --steps 64 --warmup 8 > $O/${tag}_nccl_world1.json 2> $O/${tag}_nccl_world1.log
   grep -v "^$" $O/${tag}_nccl_world1.log | tail -25; head -c 2500 $O/${tag}_nccl_world1.json; echo
   ;;
 x)    # round 5's last bounded experiment still in the tree: the soft_max of k_dec_pv_dma reduced to a workgroup's own keys (upper bound of a split;
@@ -67,10 +67,10 @@ w13)  # whole-block vs half-block w1|w3 workgroups and the 9-row plans, fresh pr
   timeout 900 python -m pytest tests/test_gpu_parity.py -x -q -m gpu -k "few_row_kernel_selectable or few_row_handoff or mul_mat" > $O/${tag}_parity.txt 2>&1; tail -3 $O/${tag}_parity.txt
   SEQS="${SEQS:-4 8}" EVALS="${EVALS:-9 16}" timeout 900 bash tools/fresh_ab.sh ${VARIANTS:-tools/variants.txt} > $O/${tag}_fresh_ab.txt 2>&1; cat $O/${tag}_fresh_ab.txt
   ;;
-verify)   # the last check of a tree: full GPU suite, smoke(), bench.py with defaults, the chunk / prefill probes
+verify)   # the last check of a tree: full GPU suite, smoke(), bench.py --full, the chunk / prefill probes
   python -m pytest tests -x -q -m gpu --durations=8 > $O/${tag}_pytest.txt 2>&1; tail -12 $O/${tag}_pytest.txt
   python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2
-  timeout 1200 python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.log; tail -2 $O/${tag}_bench.log; python - <<PY
+  timeout 1200 python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.log; tail -2 $O/${tag}_bench.log; python - <<PY
 import json
 d = json.load(open("$O/${tag}_bench.json"))
 print({k: d[k] for k in ("metric", "value", "unit", "ms_per_step")}, d["roofline"].get("frac"), d["roofline"].get("end_to_end_frac"), d["roofline"].get("traffic"))
@@ -81,14 +81,14 @@ PY
   timeout 300 python tools/prefill_probe.py > $O/${tag}_prefill_probe.txt 2>&1; tail -6 $O/${tag}_prefill_probe.txt
   ;;
 65b)
-  LLAMAHIP_FORCE_PIPELINE=1 LLAMAHIP_PIPE_PARITY_S=${PARITY_S:-60} timeout 2400 python bench.py --model 65B --steps 32 --warmup 4 > $O/${tag}_bench_65B_1gpu.json 2> $O/${tag}_bench_65B_1gpu.log
+  LLAMAHIP_FORCE_PIPELINE=1 LLAMAHIP_PIPE_PARITY_S=${PARITY_S:-60} timeout 2400 python bench.py --full --model 65B --steps 32 --warmup 4 > $O/${tag}_bench_65B_1gpu.json 2> $O/${tag}_bench_65B_1gpu.log
   tail -12 $O/${tag}_bench_65B_1gpu.log; head -c 3000 $O/${tag}_bench_65B_1gpu.json; echo
   ;;
 final)
   # (LLAMAHIP_HEAD: the commit the snapshot was taken from -- there is no .git on the GPU box; the caller passes `git rev-parse HEAD`)
   { echo "# tree: ${LLAMAHIP_HEAD:-unknown} -- python -m pytest tests -x -q -m gpu --durations=12 on $(date -u +%Y-%m-%dT%H:%MZ)"; python -m pytest tests -x -q -m gpu --durations=12; } > $O/${tag}_pytest.txt 2>&1; tail -16 $O/${tag}_pytest.txt
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-  timeout 1200 python bench.py --save-profile $O/${tag}_decode_kernel_stats.txt > $O/${tag}_bench.json 2> $O/${tag}_bench.log; tail -3 $O/${tag}_bench.log; python - <<PY
+  timeout 1200 python bench.py --full --save-profile $O/${tag}_decode_kernel_stats.txt > $O/${tag}_bench.json 2> $O/${tag}_bench.log; tail -3 $O/${tag}_bench.log; python - <<PY
 import json
 d = json.load(open("$O/${tag}_bench.json"))
 print({k: d[k] for k in ("metric", "value", "unit", "ms_per_step")}, d["roofline"].get("frac"), d["roofline"].get("end_to_end_frac"), d["roofline"].get("traffic"))
@@ -101,7 +101,7 @@ print("batched", [(c.get("sequences"), c.get("aggregate_tokens_per_s"), c.get("t
 print("parity", d.get("parity"), "cpu", d.get("cpu_baseline", {}).get("value"))
 PY
   # configs[3]: 13B bench line (parity gate + cpu_baseline) and the mixed prefill + decode run under rocprofv3 (decode crosses position 544)
-  timeout 1200 python bench.py --model 13B --no-prefill-2048 --no-concurrent > $O/${tag}_bench_13B.json 2> $O/${tag}_bench_13B.log; python - <<PY
+  timeout 1200 python bench.py --full --model 13B --no-prefill-2048 --no-concurrent > $O/${tag}_bench_13B.json 2> $O/${tag}_bench_13B.log; python - <<PY
 import json
 d = json.load(open("$O/${tag}_bench_13B.json"))
 print("13B", {k: d[k] for k in ("value", "ms_per_step")}, d["roofline"].get("frac"), d["roofline"].get("end_to_end_frac"), d.get("parity"), d.get("cpu_baseline", {}).get("value"), d["config"])
