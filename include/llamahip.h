@@ -213,6 +213,20 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
 int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
                                  int32_t n_steps, int32_t *out_tokens, char *err, size_t err_cap);
 
+/* Sampled decode of n_seqs independent sequences at once: llamahip_decode_greedy_multi's schedule (KV slot i continues at n_past[i] with
+ * first_tokens[i]; groups of up to 16 slots stepped as sets, pipelined over the stages of a pipeline handle) with the reference's sampler
+ * (llama_sample_top_p_top_k, .mm:851-870) in place of the argmax.  Sequence i draws with samplers[i] -- its own mt19937 and last_n_tokens
+ * window, each sequence a different sampler -- and every pick is accepted into it (.mm:865-868).  Bit for bit, per sequence, the loop
+ *   llamahip_eval_topk(token, n_past[i] + t) -> llamahip_sample_from_candidates (exact) / llamahip_sample_top_p_top_k (not exact) -> accept
+ * on that slot alone: out_tokens[i * n_steps + t]; the samplers' windows and rng states end where that loop leaves them.  The candidate
+ * selection runs on the device behind each group's step; the draw stays on the host, one group at a time while the groups behind it run.
+ * out_exact (may be NULL), the same shape: 1 = drawn from the device's candidates, 0 = from the full logits row on the host (a tie only
+ * libstdc++'s partial_sort orders, a NaN, a window longer than 1024 ids, top_k > 64 or n_vocab > 32768).  f16 / f32 / Q4_1 files and
+ * LLAMAHIP_FLAG_UNFUSED handles run the single-sequence loop above on each slot in turn. */
+int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                 int32_t n_steps, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p,
+                                 double temp, int32_t *out_tokens, int32_t *out_exact, char *err, size_t err_cap);
+
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
 int llamahip_eval_debug(llamahip_model *m, int32_t n_threads, int32_t n_past,
@@ -323,6 +337,12 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);
+/* the batched device half of llamahip_decode_sample_multi on caller-supplied rows: logits[n_rows][n_vocab], windows[n_rows][1024] with n_last[r]
+ * ids in row r (n_last[r] > 1024: the row is reported inexact); out_scores / out_ids [n_rows][64], out_exact [n_rows] -- row r bit for bit
+ * llamahip_op_topk on that row alone.  out_spill (may be NULL) [n_rows][n_vocab]: the rows reported inexact are copied there, the others keep
+ * the caller's contents. */
+int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *windows, const int32_t *n_last, double repeat_penalty,
+                          int32_t top_k, double temp, double *out_scores, int32_t *out_ids, int32_t *out_exact, float *out_spill, char *err, size_t err_cap);
 /* the device half of llamahip_eval_logprobs on caller-supplied rows: logits[n_rows][n_vocab], targets n_rows ids (-1 = not scored,
  * NULL = none scored); any of the three outputs may be NULL */
 int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,

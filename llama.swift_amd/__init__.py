@@ -27,6 +27,7 @@ from .binding import (  # noqa: F401
     op_mul_mat_q4_0,
     op_quantize_row_q4_0,
     op_topk,
+    op_topk_rows,
     quantize_file,
     set_plan,
     version,

@@ -111,6 +111,7 @@ def lib() -> C.CDLL:
     L.llamahip_sample_top_p_top_k.restype = i32
     L.llamahip_decode_greedy.argtypes = [vp, i32, i32, i32, i32, vp, vp, cp, sz]
     L.llamahip_decode_greedy_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, cp, sz]
+    L.llamahip_decode_sample_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, cp, sz]
     L.llamahip_eval_debug.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, C.c_int64, vp, cp, sz]
     L.llamahip_eval_stage.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, cp, sz]
     L.llamahip_stage_bind.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
@@ -130,6 +131,7 @@ def lib() -> C.CDLL:
     L.llamahip_op_mul_mat_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_op_quantize_row_q4_0.argtypes = [vp, i32, vp, cp, sz]
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
+    L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
     L.llamahip_get_stats.argtypes = [vp, C.POINTER(_Stats)]
@@ -417,6 +419,25 @@ class Model:
         _check(rc, err)
         return out
 
+    def decode_sample_multi(self, first_tokens, n_past, n_steps: int, samplers, repeat_penalty: float = 1.3, top_k: int = 40,
+                            top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), n_threads: int = 8,
+                            want_exact: bool = False):
+        """llamahip_decode_sample_multi: sequence i (KV slot i) continues at n_past[i] with first_tokens[i] and draws with samplers[i] (one
+        Sampler per sequence; every pick is accepted into it).  Returns [n_seqs][n_steps] int32, and with want_exact the [n_seqs][n_steps]
+        flags too (1 = drawn from the device's candidates, 0 = from the full logits row on the host)."""
+        ft = np.ascontiguousarray(first_tokens, np.int32)
+        npast = np.ascontiguousarray(n_past, np.int32)
+        if npast.size != ft.size or len(samplers) != ft.size:
+            raise ValueError(f"{ft.size} first tokens, {npast.size} positions, {len(samplers)} samplers")
+        sp = (C.c_void_p * max(ft.size, 1))(*[s._s.value if s is not None else None for s in samplers])
+        out = np.empty((ft.size, n_steps), np.int32)
+        exact = np.empty((ft.size, n_steps), np.int32) if want_exact else None
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_sample_multi(self._h, n_threads, ft.size, _ptr(npast), _ptr(ft), n_steps, sp, repeat_penalty, top_k, top_p, temp,
+                                                _ptr(out), _ptr(exact), err, len(err))
+        _check(rc, err)
+        return (out, exact) if want_exact else out
+
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
         v = np.empty((n_pos, self.n_embd), np.float32)
@@ -478,6 +499,13 @@ class Sampler:
         scores, ids = np.ascontiguousarray(scores, np.float64), np.ascontiguousarray(ids, np.int32)
         return int(lib().llamahip_sample_from_candidates(self._s, _ptr(scores), _ptr(ids), len(ids), top_p))
 
+    def window(self) -> np.ndarray:
+        """the last_n_tokens window, oldest first (llamahip_sampler_window)"""
+        n = lib().llamahip_sampler_window(self._s, None, 0)
+        out = np.zeros(max(n, 1), np.int32)
+        lib().llamahip_sampler_window(self._s, _ptr(out), n)
+        return out[:n]
+
     def random_prompt(self) -> str:
         """gpt_random_prompt on this sampler's rng (utils.cpp:102-119; .mm:774-776)."""
         return lib().llamahip_sampler_random_prompt(self._s).decode()
@@ -505,6 +533,32 @@ def op_topk(logits, window, repeat_penalty: float = 1.3, top_k: int = 40, temp: 
     rc = lib().llamahip_op_topk(_ptr(logits), logits.size, _ptr(window), window.size, repeat_penalty, top_k, temp, _ptr(sc), _ptr(ids), C.byref(exact), err, len(err))
     _check(rc, err)
     return bool(exact.value), sc[:top_k], ids[:top_k]
+
+
+def op_topk_rows(logits2d, windows, repeat_penalty: float = 1.3, top_k: int = 40, temp: float = float(np.float32(0.8)), want_spill: bool = False):
+    """The batched device half of the sampler on host rows f32 [R, n_vocab]; windows: R id lists (up to 1024 ids each; longer: the row is
+    reported inexact).  Returns (exact bool[R], scores float64[R][top_k], ids int32[R][top_k]), and with want_spill the [R, n_vocab] rows the
+    kernel copied out (the rows reported inexact; NaN elsewhere)."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    if len(windows) != R:
+        raise ValueError(f"{len(windows)} windows for {R} rows")
+    win = np.zeros((R, 1024), np.int32)
+    n_last = np.zeros(R, np.int32)
+    for r, w in enumerate(windows):
+        w = np.asarray(w, np.int32).ravel()
+        n_last[r] = w.size
+        win[r, :min(w.size, 1024)] = w[:1024]
+    sc, ids, exact = np.zeros((R, 64), np.float64), np.zeros((R, 64), np.int32), np.zeros(R, np.int32)
+    spill = np.full((R, V), np.nan, np.float32) if want_spill else None
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_topk_rows(_ptr(logits2d), R, V, _ptr(win), _ptr(n_last), repeat_penalty, top_k, temp, _ptr(sc), _ptr(ids), _ptr(exact),
+                                     _ptr(spill), err, len(err))
+    _check(rc, err)
+    res = (exact.astype(bool), sc[:, :top_k].copy(), ids[:, :top_k].copy())
+    return res + (spill,) if want_spill else res
 
 
 def op_logprob(logits2d, targets=None):

@@ -29,9 +29,10 @@
 //                               epilogues (store | +residual | SiLU*up -> Q4_0 | tagged rows), register ring of weight chunks
 //   k_dec_scores, k_decn_scores, k_dec_pv_blk   attention of one row (decode fallback) / of a short eval (2..60 rows)
 //   attn_x_body, k_dec_attn_x, k_qkv_attn       attention in one launch; wq|wk|wv mat-vec + attention in one launch (XCD-local tagged hand-offs)
-//   k_xcd_selftest, k_argmax, k_advance, k_bump_epoch, k_topk_keys, k_topk_select
+//   k_xcd_selftest, k_argmax, k_advance, k_bump_epoch, k_topk_keys, k_topk_select,
+//              k_topk_keys_rows, k_topk_select_rows, k_topk_spill
 //   launchers: set_phase_probe, launch_gemv (+ kernel selection rules), launch_attn_short, xcd_selftest, launch_dec_attn,
-//              launch_qkv_attn, launch_bump_epoch, launch_topk_candidates, launch_argmax, launch_advance, init_kernel_attrs
+//              launch_qkv_attn, launch_bump_epoch, launch_topk_candidates, launch_topk_rows, launch_argmax, launch_advance, init_kernel_attrs
 #define LH_DEFINE_PHASE_PROBE 1
 #include <cmath>
 
@@ -2309,9 +2310,10 @@ hipError_t launch_bump_epoch(uint32_t *epoch, hipStream_t st) {
 // key, the 64 group maxima) over V / 1024 workgroups; k_topk_select (one workgroup) only compares the finished keys with the
 // threshold and ranks the survivors.  Same groups (element i belongs to group (i % 1024) / 16), same threshold, same flags.
 //   ws: keys[32768] u64 | gmax[64] u64 (zero between calls: k_topk_select clears it) | bad u32
-__global__ void __launch_bounds__(1024)
-k_topk_keys(const float *__restrict__ logits, int V, const int32_t *__restrict__ window, int n_window, double scale, double repeat_penalty,
-            unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw) {
+// (the bodies are shared with the batched variants k_topk_keys_rows / k_topk_select_rows below: one row each, same bits)
+__device__ __forceinline__ void
+topk_keys_row(const float *__restrict__ logits, int V, const int32_t *__restrict__ window, int n_window, double scale, double repeat_penalty,
+              unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw) {
     __shared__ uint32_t seen[1024];
     const int tid = threadIdx.x, i = blockIdx.x * 1024 + tid;
     seen[tid] = 0u;
@@ -2339,8 +2341,16 @@ k_topk_keys(const float *__restrict__ logits, int V, const int32_t *__restrict__
 }
 
 __global__ void __launch_bounds__(1024)
-k_topk_select(int V, int k, unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw,
-              double *__restrict__ out_score, int32_t *__restrict__ out_id, int32_t *__restrict__ flags) {
+k_topk_keys(const float *__restrict__ logits, int V, const int32_t *__restrict__ window, int n_window, double scale, double repeat_penalty,
+            unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw) {
+    topk_keys_row(logits, V, window, n_window, scale, repeat_penalty, keys, gmax, badw);
+}
+
+// force_host: the row is reported inexact whatever its values (k_topk_select_rows: a window longer than the device takes); the workspace
+// is cleared all the same
+__device__ __forceinline__ void
+topk_select_row(int V, int k, unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw,
+                double *__restrict__ out_score, int32_t *__restrict__ out_id, int32_t *__restrict__ flags, bool force_host) {
     constexpr int NPT = 32, LCAP = 768;
     __shared__ unsigned long long list_key[LCAP];
     __shared__ int32_t list_id[LCAP];
@@ -2367,7 +2377,7 @@ k_topk_select(int V, int k, unsigned long long *__restrict__ keys, unsigned long
     const unsigned long long T = s_T;
     if (tid < 64) gmax[tid] = 0ull;
     if (tid == 0) badw[0] = 0u;
-    if (T == 0ull) {                                   // a group without a real value (tiny vocabularies) -- host path
+    if (T == 0ull || force_host) {                     // a group without a real value (tiny vocabularies) -- host path
         if (tid == 0) { flags[0] = 0; flags[1] = 0; }
         return;
     }
@@ -2424,6 +2434,61 @@ k_topk_select(int V, int k, unsigned long long *__restrict__ keys, unsigned long
     }
     __syncthreads();
     if (tid == 0) { flags[0] = (bad == 0u && n >= k) ? 1 : 0; flags[1] = n; }
+}
+
+__global__ void __launch_bounds__(1024)
+k_topk_select(int V, int k, unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw,
+              double *__restrict__ out_score, int32_t *__restrict__ out_id, int32_t *__restrict__ flags) {
+    topk_select_row(V, k, keys, gmax, badw, out_score, out_id, flags, false);
+}
+
+// The same selection over R rows of logits (rows [R][V], contiguous) in one launch pair: row r = blockIdx.y of k_topk_keys_rows and
+// blockIdx.x of k_topk_select_rows, with its own window (windows + r * 1024, n_last[r] ids), its own TOPK_WS_BYTES of workspace and its
+// own TopkOut -- so every row's (scores, ids, order, exact) is bit for bit launch_topk_candidates on that row alone.  A row whose window
+// is longer than 1024 ids is flagged inexact.  k_topk_spill then copies the rows flagged inexact (only those) to spill + r * V, for the
+// host sampler.
+__global__ void __launch_bounds__(1024)
+k_topk_keys_rows(const float *__restrict__ logits, int V, const int32_t *__restrict__ windows, const int32_t *__restrict__ n_last, double scale,
+                 double repeat_penalty, char *__restrict__ ws) {
+    const int r = blockIdx.y;
+    unsigned long long *keys = (unsigned long long *) (ws + (size_t) r * TOPK_WS_BYTES), *gmax = keys + 32768;
+    const int nw = n_last[r];
+    topk_keys_row(logits + (size_t) r * V, V, windows + (size_t) r * 1024, nw < 0 ? 0 : (nw > 1024 ? 1024 : nw), scale, repeat_penalty,
+                  keys, gmax, (uint32_t *) (gmax + 64));
+}
+
+__global__ void __launch_bounds__(1024)
+k_topk_select_rows(int V, int k, const int32_t *__restrict__ n_last, char *__restrict__ ws, TopkOut *__restrict__ out) {
+    const int r = blockIdx.x;
+    unsigned long long *keys = (unsigned long long *) (ws + (size_t) r * TOPK_WS_BYTES), *gmax = keys + 32768;
+    const int nw = n_last[r];
+    topk_select_row(V, k, keys, gmax, (uint32_t *) (gmax + 64), out[r].sc, out[r].id, out[r].fl, nw < 0 || nw > 1024);
+}
+
+// grid (ceil(V / 4096), R): 1024 threads x 4 floats; whole rows of inexact results only
+__global__ void __launch_bounds__(1024)
+k_topk_spill(const float *__restrict__ logits, int V, const TopkOut *__restrict__ out, float *__restrict__ spill) {
+    const int r = blockIdx.y;
+    if (out[r].fl[0] != 0) return;
+    const float *src = logits + (size_t) r * V;
+    float *dst = spill + (size_t) r * V;
+    const int i0 = blockIdx.x * 4096 + threadIdx.x;
+#pragma unroll
+    for (int u = 0; u < 4; u++) { const int i = i0 + u * 1024; if (i < V) dst[i] = src[i]; }
+}
+
+hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *windows, const int32_t *n_last, double scale, double repeat_penalty,
+                            int k, TopkOut *out, float *spill, hipStream_t st, void *ws) {
+    if (R < 1 || V < 1 || V > 32768 || k < 1 || k > 64 || !ws || !out) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_topk_keys_rows, dim3((V + 1023) / 1024, R), dim3(1024), 0, st, logits, V, windows, n_last, scale, repeat_penalty, (char *) ws);
+    LH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_topk_select_rows, dim3(R), dim3(1024), 0, st, V, k, n_last, (char *) ws, out);
+    LH_LAUNCH_CHECK();
+    if (spill) {
+        hipLaunchKernelGGL(k_topk_spill, dim3((V + 4095) / 4096, R), dim3(1024), 0, st, logits, V, out, spill);
+        LH_LAUNCH_CHECK();
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_topk_candidates(const float *logits, int V, const int32_t *window, int n_window, double scale, double repeat_penalty, int k,

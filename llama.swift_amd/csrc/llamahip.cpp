@@ -230,6 +230,12 @@ struct llamahip_model {
     float *mq_in = nullptr, *mq_out = nullptr;     // [n_seq][n_embd]
     int32_t *mq_tok = nullptr;                     // [n_seq]
     std::vector<hipEvent_t> mq_ev;
+    // llamahip_decode_sample_multi: one pinned, device-mapped block per stage -- the first stage's token words, the last stage's sampler windows,
+    // candidates and spilled rows -- and (last stage) the selection workspace of SET_MAX rows
+    struct SampleIo { int32_t *tok = nullptr, *n_last = nullptr, *win = nullptr; TopkOut *out = nullptr; float *spill = nullptr; };
+    char *smp_blk = nullptr;
+    SampleIo smp_h, smp_d;                         // host view / device view: tok [n_seq], n_last [n_seq], win [n_seq][1024], out [n_seq], spill [n_seq][V]
+    void *smp_ws = nullptr;                        // SET_MAX * TOPK_WS_BYTES, zeroed once (the selection leaves it zeroed)
     int pipe_hand_off = 0;               // (front) llamahip_stats.hand_off
 
     ~llamahip_model();
@@ -290,6 +296,8 @@ llamahip_model::~llamahip_model() {
     free_dev(pipe_in); free_dev(pipe_hout); free_dev(pipe_tok);
     free_dev(mq_in); free_dev(mq_out); free_dev(mq_tok);
     for (hipEvent_t e : mq_ev) (void) hipEventDestroy(e);
+    if (smp_blk) { (void) hipHostFree(smp_blk); smp_blk = nullptr; }
+    free_dev(smp_ws);
     if (pipe_ev) (void) hipEventDestroy(pipe_ev);
     if (stream) (void) hipStreamDestroy(stream);
 }
@@ -1933,12 +1941,13 @@ static int pipe_hand_off(llamahip_model *a, llamahip_model *b, void *dst, const 
 // making progress -- a hung device, a lost xGMI link under a peer copy -- turns into LLAMAHIP_ERR_PREDICT after LLAMAHIP_PIPE_WATCHDOG_S seconds
 // (default 600; the longest legitimate wait is a 2 048-token eval of a 65B stage, well under a second) instead of blocking the caller's thread for
 // ever.  Spins on hipStreamQuery for the first milliseconds (token steps), then yields 100 us per look.
-static int pipe_wait_stage(llamahip_model *st, int s, char *err, size_t err_cap) {
+// (ev: wait for that event of the stage's stream instead of the whole stream -- llamahip_decode_sample_multi waits for one group at a time)
+static int pipe_wait_stage(llamahip_model *st, int s, char *err, size_t err_cap, hipEvent_t ev = nullptr) {
     static const double limit_ms = (getenv("LLAMAHIP_PIPE_WATCHDOG_S") ? atof(getenv("LLAMAHIP_PIPE_WATCHDOG_S")) : 600.0) * 1e3;
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     const double t0 = now_ms();
     for (;;) {
-        const hipError_t e = hipStreamQuery(st->stream);
+        const hipError_t e = ev ? hipEventQuery(ev) : hipStreamQuery(st->stream);
         if (e == hipSuccess) return 0;
         (void) hipGetLastError();
         if (e != hipErrorNotReady) { set_err(err, err_cap, "HIP error: %s while waiting for pipeline stage %d (device %d)", hipGetErrorString(e), s, st->device); return LLAMAHIP_ERR_PREDICT; }
@@ -2310,6 +2319,188 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
     return decode_greedy_multi_impl(m, n_threads, n_seqs, n_past, first_tokens, n_steps, out_tokens, err, err_cap);
 }
 
+// ------------------------------------------------------------------------------------------------
+// llamahip_decode_sample_multi: the schedule of llamahip_decode_greedy_multi (same groups, set steps, per-slot fall-back, stage hand-offs)
+// with the reference's sampler in place of the argmax.  Behind the launch that produced a group's rows of logits, the last stage's stream
+// runs the sampler's device half over those rows (launch_topk_rows: one launch pair for the group, then k_topk_spill copies the rows
+// flagged inexact to the slots' spill rows) and records the group's event.  The host waits for that event only, finishes each slot's draw
+// with the slot's own sampler (llamahip_sample_from_candidates, or llamahip_sample_top_p_top_k on the spilled row), accepts it, writes the
+// token and the new window into the pinned block and enqueues the group's next step -- while the groups enqueued behind it keep the device
+// (and the other stages) busy.  The draw itself stays on the host: it is libstdc++'s std::discrete_distribution on the sampler's mt19937.
+// ------------------------------------------------------------------------------------------------
+static int sample_prepare(llamahip_model *st, bool last, char *err, size_t err_cap) {
+    if (st->smp_blk) return 0;
+    HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+    const size_t n = st->n_seq, V = last ? st->hp.n_vocab : 0;
+    const size_t o_last = (n * 4 + 63) / 64 * 64, o_win = o_last + (n * 4 + 63) / 64 * 64, o_out = o_win + n * 1024 * 4;
+    const size_t o_spill = o_out + (last ? n * sizeof(TopkOut) : 0), bytes = o_spill + n * V * 4;
+    HIP_TRY(hipHostMalloc((void **) &st->smp_blk, bytes, hipHostMallocMapped), LLAMAHIP_ERR_PREDICT);
+    memset(st->smp_blk, 0, bytes);
+    char *d = nullptr;
+    HIP_TRY(hipHostGetDevicePointer((void **) &d, st->smp_blk, 0), LLAMAHIP_ERR_PREDICT);
+    for (int v = 0; v < 2; v++) {
+        char *b = v ? d : st->smp_blk;
+        llamahip_model::SampleIo &io = v ? st->smp_d : st->smp_h;
+        io.tok = (int32_t *) b; io.n_last = (int32_t *) (b + o_last); io.win = (int32_t *) (b + o_win);
+        io.out = last ? (TopkOut *) (b + o_out) : nullptr; io.spill = last ? (float *) (b + o_spill) : nullptr;
+    }
+    if (last) {
+        HIP_TRY(hipMalloc(&st->smp_ws, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemset(st->smp_ws, 0, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+
+int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                 int32_t n_steps, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p,
+                                 double temp, int32_t *out_tokens, int32_t *out_exact, char *err, size_t err_cap) {
+    static const char *F = "llamahip_decode_sample_multi";
+    if (!m) { set_err(err, err_cap, "null model"); return LLAMAHIP_ERR_PREDICT; }
+    if (!n_past || !first_tokens || !samplers || !out_tokens) {
+        set_err(err, err_cap, "%s: %s is NULL", F, !n_past ? "n_past" : !first_tokens ? "first_tokens" : !samplers ? "samplers" : "out_tokens"); return LLAMAHIP_ERR_PREDICT; }
+    if (n_seqs < 1) { set_err(err, err_cap, "%s: n_seqs must be >= 1 (got %d)", F, n_seqs); return LLAMAHIP_ERR_PREDICT; }
+    if (n_steps < 1) { set_err(err, err_cap, "%s: n_steps must be >= 1 (got %d)", F, n_steps); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_seqs; i++) {
+        if (!samplers[i]) { set_err(err, err_cap, "%s: samplers[%d] is NULL", F, i); return LLAMAHIP_ERR_PREDICT; }
+        for (int j = 0; j < i; j++)
+            if (samplers[j] == samplers[i]) { set_err(err, err_cap, "%s: samplers[%d] and samplers[%d] are the same sampler: every sequence draws with its own", F, j, i); return LLAMAHIP_ERR_PREDICT; }
+    }
+    std::vector<llamahip_model *> stages = m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages;
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    if (n_seqs > first->n_seq) { set_err(err, err_cap, "%s: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", F, n_seqs, first->n_seq); return LLAMAHIP_ERR_PREDICT; }
+    if (first->host_only) { set_err(err, err_cap, "model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate"); return LLAMAHIP_ERR_PREDICT; }
+    if (!first->first_stage || !last->last_stage) { set_err(err, err_cap, "%s needs a whole-model or a pipeline handle", F); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_seqs; i++) {
+        int rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap);
+        if (rc) return rc;
+        if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    }
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    if (first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+        // no stage step to batch (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED): the single-sequence loop on each slot in turn
+        const int save_seq = m->cur_seq;
+        std::vector<float> logits(V);
+        std::vector<int32_t> win;
+        double sc[64];
+        int32_t ids[64];
+        int rc = 0;
+        for (int i = 0; i < n_seqs && rc == 0; i++) {
+            if ((rc = llamahip_set_seq(m, i, err, err_cap)) != 0) break;
+            int32_t tok = first_tokens[i];
+            for (int t = 0; t < n_steps && rc == 0; t++) {
+                win.resize((size_t) std::max(llamahip_sampler_window(samplers[i], nullptr, 0), 1));
+                const int32_t nw = std::min(llamahip_sampler_window(samplers[i], win.data(), (int32_t) win.size()), (int32_t) win.size());
+                int32_t exact = 0;
+                if ((rc = llamahip_eval_topk(m, n_threads, n_past[i] + t, &tok, 1, win.data(), nw, repeat_penalty, top_k, temp, sc, ids, &exact, logits.data(), err, err_cap)) != 0) break;
+                tok = exact == 1 ? llamahip_sample_from_candidates(samplers[i], sc, ids, k, top_p)
+                                 : llamahip_sample_top_p_top_k(m, samplers[i], logits.data(), repeat_penalty, top_k, top_p, temp);
+                llamahip_sampler_accept(samplers[i], tok);
+                out_tokens[(size_t) i * n_steps + t] = tok;
+                if (out_exact) out_exact[(size_t) i * n_steps + t] = exact == 1;
+            }
+        }
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
+    }
+    const double t0 = now_ms();
+    const size_t d = m->hp.n_embd;
+    // the device half runs unless top_k > 64 or n_vocab > 32768 (then every row is spilled); a window of more than 1024 ids spills its row only
+    const bool dev_sel = V <= 32768 && k <= 64;
+    const double scale = 1.0 / temp;
+    const int G = std::min(n_seqs, std::max(S, (n_seqs + SET_MAX - 1) / SET_MAX));
+    std::vector<int> g0(G + 1, 0);
+    for (int g = 0; g < G; g++) g0[g + 1] = g0[g] + n_seqs / G + (g < n_seqs % G ? 1 : 0);
+    int rc = 0;
+    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, G, err, err_cap)) != 0) return rc;
+    if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
+    if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
+    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h, &dl = last->smp_d;
+    // (the stream of every stage is idle here: every entry point synchronises before it returns)
+    auto publish = [&](int i, int32_t tok) {
+        hf.tok[i] = tok;
+        hl.n_last[i] = llamahip_sampler_window(samplers[i], hl.win + (size_t) i * 1024, 1024);
+    };
+    for (int i = 0; i < n_seqs; i++) publish(i, first_tokens[i]);
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        for (int i = 0; i < n_seqs; i++) {
+            // (token_out NULL: the argmax of the stage step still advances the slot's position; the next token is the host's draw)
+            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->smp_d.tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
+                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, nullptr, err, err_cap)) != 0) return rc;
+        }
+    }
+    std::vector<int32_t> slots(n_seqs);
+    for (int i = 0; i < n_seqs; i++) slots[i] = i;
+    // the selection of rows [0, R) of the last stage's logits = slots [i0, i0 + R)
+    auto select = [&](int i0, int R) -> int {
+        if (dev_sel)
+            HIP_TRY(launch_topk_rows(last->logits, R, V, dl.win + (size_t) i0 * 1024, dl.n_last + i0, scale, repeat_penalty, k, dl.out + i0,
+                                     dl.spill + (size_t) i0 * V, last->stream, last->smp_ws), LLAMAHIP_ERR_PREDICT);
+        else HIP_TRY(hipMemcpyAsync(hl.spill + (size_t) i0 * V, last->logits, (size_t) R * V * 4, hipMemcpyDeviceToHost, last->stream), LLAMAHIP_ERR_PREDICT);
+        return 0;
+    };
+    // one step of group g through every stage, its selection, and the group's event on the last stage
+    auto enqueue = [&](int g) -> int {
+        const int gn = g0[g + 1] - g0[g];
+        int r = 0;
+        for (int s = 0; s < S && r == 0; s++) {
+            llamahip_model *st = stages[s];
+            HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+            if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[g], 0), LLAMAHIP_ERR_PREDICT);
+            if (gn >= 2 && llamahip_stage_set_applies(st, gn, n_threads)) {
+                r = llamahip_stage_step_set(st, slots.data() + g0[g], gn, n_threads, st->stream, err, err_cap);
+                if (r == 0 && s + 1 == S) r = select(g0[g], gn);                  // (a set orders its rows by slot id: row i = slot g0[g] + i)
+            } else {
+                for (int i = g0[g]; i < g0[g + 1] && r == 0; i++) {
+                    r = llamahip_stage_step(st, i, n_threads, st->stream, err, err_cap);
+                    if (r == 0 && s + 1 == S) r = select(i, 1);                   // (row 0, before the next slot's step rewrites it)
+                }
+            }
+            if (r) break;
+            if (s + 1 < S) {
+                llamahip_model *to = stages[s + 1];
+                void *dst = to->mq_in + (size_t) g0[g] * d;
+                const void *src = st->mq_out + (size_t) g0[g] * d;
+                if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, (size_t) gn * d * 4, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
+                else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, (size_t) gn * d * 4, st->stream), LLAMAHIP_ERR_PREDICT);
+            }
+            HIP_TRY(hipEventRecord(st->mq_ev[g], st->stream), LLAMAHIP_ERR_PREDICT);
+        }
+        return r;
+    };
+    for (int g = 0; g < G && rc == 0; g++) rc = enqueue(g);
+    for (int t = 0; t < n_steps && rc == 0; t++) {
+        for (int g = 0; g < G && rc == 0; g++) {
+            if ((rc = pipe_wait_stage(last, S - 1, err, err_cap, last->mq_ev[g])) != 0) break;
+            for (int i = g0[g]; i < g0[g + 1]; i++) {
+                const TopkOut &c = hl.out[i];
+                const bool exact = dev_sel && c.fl[0] == 1;
+                const int32_t tok = exact ? llamahip_sample_from_candidates(samplers[i], c.sc, c.id, k, top_p)
+                                          : llamahip_sample_top_p_top_k(m, samplers[i], hl.spill + (size_t) i * V, repeat_penalty, top_k, top_p, temp);
+                llamahip_sampler_accept(samplers[i], tok);
+                out_tokens[(size_t) i * n_steps + t] = tok;
+                if (out_exact) out_exact[(size_t) i * n_steps + t] = exact ? 1 : 0;
+                if (t + 1 < n_steps) publish(i, tok);
+            }
+            if (t + 1 < n_steps) rc = enqueue(g);
+        }
+    }
+    // wait for every stage (bounded), collect their fault words -- on the error paths too, before anything of this call is left behind
+    const int rc_sync = pipe_sync_stages(stages, rc ? nullptr : err, rc ? 0 : err_cap);
+    if (rc) return rc;
+    if (rc_sync) return rc_sync;
+    std::vector<int32_t> state((size_t) 2 * n_seqs);
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(state.data(), last->d_slot_state, state.size() * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    for (int i = 0; i < n_seqs; i++)
+        if (state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d, not %d", F, i, state[2 * i], n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
+    m->n_evals += (int64_t) n_seqs * n_steps;
+    m->t_eval_ms += now_ms() - t0;
+    if (!m->stages.empty()) m->pipe_hand_off = 1;
+    return LLAMAHIP_OK;
+}
+
 int llamahip_set_seq(llamahip_model *m, int32_t seq, char *err, size_t err_cap) {
     if (!m || seq < 0 || seq >= m->n_seq) { set_err(err, err_cap, "sequence slot %d out of range [0, %d)", seq, m ? m->n_seq : 0); return LLAMAHIP_ERR_PREDICT; }
     m->cur_seq = seq;
@@ -2480,6 +2671,41 @@ int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n
     HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
     *exact = h.fl[0];
     for (int i = 0; i < top_k; i++) { cand_scores[i] = h.sc[i]; cand_ids[i] = h.id[i]; }
+    return LLAMAHIP_OK;
+}
+
+// the batched device half of the sampler on caller-supplied rows (parity tests): see llamahip_decode_sample_multi
+int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *windows, const int32_t *n_last, double repeat_penalty,
+                          int32_t top_k, double temp, double *out_scores, int32_t *out_ids, int32_t *out_exact, float *out_spill, char *err, size_t err_cap) {
+    if (!logits || !windows || !n_last || !out_scores || !out_ids || !out_exact || n_rows < 1 || n_vocab < 1 || n_vocab > 32768 || top_k < 1 || top_k > 64 || top_k > n_vocab) {
+        set_err(err, err_cap, "llamahip_op_topk_rows: bad arguments (n_rows %d, n_vocab %d <= 32768, top_k %d in [1, min(64, n_vocab)])", n_rows, n_vocab, top_k); return LLAMAHIP_ERR_PREDICT;
+    }
+    for (int r = 0; r < n_rows; r++)
+        if (n_last[r] < 0) { set_err(err, err_cap, "llamahip_op_topk_rows: n_last[%d] = %d", r, n_last[r]); return LLAMAHIP_ERR_PREDICT; }
+    int rc = need_device(err, err_cap);
+    if (rc) return rc;
+    const size_t R = n_rows, V = n_vocab;
+    float *d_l = nullptr, *d_sp = nullptr; int32_t *d_win = nullptr; void *d_ws = nullptr; TopkOut *d_out = nullptr;
+    std::vector<TopkOut> h(R);
+    hipError_t e = hipMalloc((void **) &d_l, R * V * 4);
+    if (e == hipSuccess) e = hipMalloc((void **) &d_win, R * 1024 * 4 + R * 4);
+    if (e == hipSuccess) e = hipMalloc(&d_ws, R * TOPK_WS_BYTES);
+    if (e == hipSuccess) e = hipMalloc((void **) &d_out, R * sizeof(TopkOut));
+    if (e == hipSuccess && out_spill) e = hipMalloc((void **) &d_sp, R * V * 4);
+    if (e == hipSuccess) e = hipMemset(d_ws, 0, R * TOPK_WS_BYTES);
+    if (e == hipSuccess) e = hipMemcpy(d_l, logits, R * V * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_win, windows, R * 1024 * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_win + R * 1024, n_last, R * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && out_spill) e = hipMemcpy(d_sp, out_spill, R * V * 4, hipMemcpyHostToDevice);      // (rows that are not spilled keep the caller's bits)
+    if (e == hipSuccess) e = launch_topk_rows(d_l, n_rows, n_vocab, d_win, d_win + R * 1024, 1.0 / temp, repeat_penalty, top_k, d_out, d_sp, nullptr, d_ws);
+    if (e == hipSuccess) e = hipMemcpy(h.data(), d_out, R * sizeof(TopkOut), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && out_spill) e = hipMemcpy(out_spill, d_sp, R * V * 4, hipMemcpyDeviceToHost);
+    free_dev(d_l); free_dev(d_win); free_dev(d_ws); free_dev(d_out); free_dev(d_sp);
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
+    for (size_t r = 0; r < R; r++) {
+        out_exact[r] = h[r].fl[0];
+        for (int i = 0; i < top_k; i++) { out_scores[r * 64 + i] = h[r].sc[i]; out_ids[r * 64 + i] = h[r].id[i]; }
+    }
     return LLAMAHIP_OK;
 }
 

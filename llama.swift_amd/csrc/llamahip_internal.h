@@ -214,6 +214,11 @@ hipError_t launch_advance(int32_t *state, hipStream_t st);
 hipError_t launch_topk_candidates(const float *logits, int V, const int32_t *window, int n_window, double scale, double repeat_penalty, int k,
                                   double *out_score, int32_t *out_id, int32_t *flags, hipStream_t st, void *ws = nullptr);      // ws: TOPK_WS_BYTES zeroed once -> the two-launch variant
 constexpr size_t TOPK_WS_BYTES = 32768 * 8 + 64 * 8 + 64;
+// the same selection over R rows [R][V] in one launch pair (llamahip_decode_sample_multi, llamahip_op_topk_rows): windows [R][1024], n_last [R]
+// (> 1024: the row is flagged inexact), ws R * TOPK_WS_BYTES zeroed once, out [R]; spill (may be null) [R][V] receives the rows flagged inexact
+struct TopkOut { double sc[64]; int32_t id[64]; int32_t fl[2]; };          // fl[0] = exact, fl[1] = values collected
+hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *windows, const int32_t *n_last, double scale, double repeat_penalty,
+                            int k, TopkOut *out, float *spill, hipStream_t st, void *ws);
 // next-token scoring of n_rows rows of logits (logprob.hip): per row the log-probability of targets[r] in double, the argmax (lowest index
 // on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,
