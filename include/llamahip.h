@@ -334,6 +334,25 @@ int llamahip_quantize_file(const char *fname_inp, const char *fname_out, int32_t
  * (replaces ggml_compute_forward_mul_mat_q4_0_f32, ggml.c:5987-6285). */
 int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N,
                              float *y, char *err, size_t err_cap);
+/* The multi-row (prompt) mat-mul with its kernel chosen by the caller: y[n][m] = W . quantize_q4_0(x[n]) (+ resid[n][m]) through the
+ * model's activation quantizer and ONE of its prompt GEMM kernels.  W: M rows of K/32 Q4_0 blocks in file layout, K a positive multiple
+ * of 64; x [N][K]; resid [N][M] or NULL (no residual epilogue); y [N][y_stride], y_stride >= M: the WHOLE buffer is copied to the device
+ * before the launch and back after it, so columns M .. y_stride - 1 keep what the caller put there unless a kernel writes out of place.
+ * path: LLAMAHIP_GEMM_AUTO -- what a model handle with its prompt copies picks (exact kernels only); _MFMA4 k_gemm_mfma4 (exact); _MFMA_I8
+ * the int8 matrix-core kernel (exact); _FAST the int8 kernel of LLAMAHIP_FLAG_FAST_PREFILL (NOT exact: one fp32 chain per output);
+ * _ROWS k_gemm_rows; _SET k_gemv_set (2 .. 60 rows); _LDS k_gemm_lds (one row: the decode mat-vec).  A kernel that cannot take the shape
+ * is refused with a message naming the limit, before anything is launched.  *path_taken (may be NULL): the path that ran --
+ * LLAMAHIP_GEMM_GEMV for one row on the decode mat-vec. */
+#define LLAMAHIP_GEMM_AUTO    0
+#define LLAMAHIP_GEMM_MFMA4   1
+#define LLAMAHIP_GEMM_MFMA_I8 2
+#define LLAMAHIP_GEMM_FAST    3
+#define LLAMAHIP_GEMM_ROWS    4
+#define LLAMAHIP_GEMM_SET     5
+#define LLAMAHIP_GEMM_LDS     6
+#define LLAMAHIP_GEMM_GEMV    7   /* reported only */
+int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);
@@ -370,7 +389,8 @@ int64_t llamahip_debug_decode_phases(llamahip_model *m, int32_t n_past, int32_t 
                                      uint64_t *records, int64_t cap, char *err, size_t err_cap);
 
 /* Launch counts of the multi-row mat-mul kernel families since process start, in the order
- * {matrix-core (k_gemm_mfma4), row-per-lane (k_gemm_rows), LDS-staged (k_gemm_lds), mat-vec (k_gemv), few rows (k_gemv_set)}:
+ * {matrix-core (k_gemm_mfma4 and k_gemm_mfma, every launch), row-per-lane (k_gemm_rows), LDS-staged (k_gemm_lds), mat-vec (k_gemv),
+ *  few rows (k_gemv_set), the fast kernel of LLAMAHIP_FLAG_FAST_PREFILL (k_gemm_mfma<*, true>: also counted as matrix-core)}:
  * lets a test assert that a shape took the path it is meant to.  Returns the number of families. */
 int32_t llamahip_debug_gemm_paths(int64_t *out, int32_t cap);
 /* Host-only (no device needed): how the few-row mat-mul would take n_rows activation rows against an m x k Q4_0 matrix (interleaved:

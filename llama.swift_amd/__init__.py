@@ -25,6 +25,7 @@ from .binding import (  # noqa: F401
     lib,
     op_logprob,
     op_mul_mat_q4_0,
+    op_prompt_gemm_q4_0,
     op_quantize_row_q4_0,
     op_topk,
     op_topk_rows,

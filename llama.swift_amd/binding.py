@@ -130,6 +130,7 @@ def lib() -> C.CDLL:
     L.llamahip_tensor_bytes.restype = C.c_int64
     L.llamahip_op_mul_mat_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_op_quantize_row_q4_0.argtypes = [vp, i32, vp, cp, sz]
+    L.llamahip_op_prompt_gemm_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
@@ -155,7 +156,7 @@ def gemm_paths() -> dict:
     """Launch counts of the multi-row mat-mul kernel families since process start (llamahip_debug_gemm_paths)."""
     a = np.zeros(8, np.int64)
     n = lib().llamahip_debug_gemm_paths(a.ctypes.data_as(C.c_void_p), 8)
-    return dict(zip(("mfma", "rows", "lds", "gemv", "set"), a[:n].tolist()))
+    return dict(zip(("mfma", "rows", "lds", "gemv", "set", "fast"), a[:n].tolist()))
 
 
 def version() -> str:
@@ -590,6 +591,30 @@ def op_mul_mat_q4_0(wq: np.ndarray, x: np.ndarray) -> np.ndarray:
     rc = lib().llamahip_op_mul_mat_q4_0(_ptr(wq), M, K, _ptr(x), N, _ptr(y), err, len(err))
     _check(rc, err)
     return y
+
+
+GEMM_PATHS = ("auto", "mfma4", "mfma_i8", "fast", "rows", "set", "lds", "gemv")      # LLAMAHIP_GEMM_* of llamahip.h, in order
+
+
+def op_prompt_gemm_q4_0(wq: np.ndarray, x: np.ndarray, resid=None, path: str = "auto", y_stride: int | None = None, y_init=None):
+    """One prompt GEMM kernel (llamahip_op_prompt_gemm_q4_0): wq uint8 [M, K/32, 20] (file layout), x f32 [N, K], resid f32 [N, M] or None.
+    path: one of GEMM_PATHS[:7].  Returns (y f32 [N, y_stride], the path taken): the whole buffer as the device left it -- y_init
+    (default: NaN everywhere) is what columns M .. y_stride - 1 and any output a kernel skips keep."""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    M, nb, _ = wq.shape
+    K = nb * 32
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, ys), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    code = GEMM_PATHS.index(path) if path in GEMM_PATHS else int(path)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_prompt_gemm_q4_0(_ptr(wq), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
+    _check(rc, err)
+    return y, GEMM_PATHS[taken.value]
 
 
 def op_quantize_row_q4_0(x: np.ndarray) -> np.ndarray:

@@ -2649,6 +2649,74 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
     return rc;
 }
 
+// one prompt GEMM kernel on caller-supplied operands (per-op tests of every kernel launch_gemm can pick): see llamahip.h
+int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {
+    if (!w_q4_0 || !x || !y || M < 1 || N < 1 || K < 64 || K % 64 != 0) {
+        set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: bad arguments (M %d, N %d >= 1; K %d must be a positive multiple of 64)", M, N, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (y_stride < M) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: y_stride %d < M %d", y_stride, M); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_GEMM_AUTO || path > LLAMAHIP_GEMM_LDS) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: unknown path %d", path); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    QMat q;
+    q.M = M; q.K = K; q.ngroups = (M + 7) / 8; q.nchunks = (K + 255) / 256;
+    q.nrb = (M + 63) / 64; q.nrb32 = (M + 31) / 32;
+    const size_t wbytes = (size_t) M * (K / 32) * 20, Kp = (size_t) q.nchunks * 256, ybytes = (size_t) N * y_stride * 4;
+    const bool auto_ = path == LLAMAHIP_GEMM_AUTO;
+    const bool want_rows = auto_ || path == LLAMAHIP_GEMM_ROWS, want_mt4 = auto_ || path == LLAMAHIP_GEMM_MFMA4;
+    const bool want_mt = path == LLAMAHIP_GEMM_MFMA_I8 || path == LLAMAHIP_GEMM_FAST;
+    uint8_t *d_w = nullptr, *d_qb = nullptr; float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr, *d_qd = nullptr; uint32_t *d_qA = nullptr;
+    hipStream_t st = nullptr;
+    const char *why = nullptr;
+    long before[GEMM_PATH_COUNT];
+    int rc = LLAMAHIP_ERR_PREDICT;
+    do {
+        if (hipMalloc((void **) &d_w, wbytes) != hipSuccess) break;
+        if (hipMalloc((void **) &q.tiles, q.bytes()) != hipSuccess) break;
+        if (want_rows && hipMalloc((void **) &q.rows, q.rows_bytes()) != hipSuccess) break;
+        if (want_mt4 && hipMalloc((void **) &q.mt4, q.mt4_bytes()) != hipSuccess) break;
+        if (want_mt && hipMalloc((void **) &q.mt, q.mt_bytes()) != hipSuccess) break;
+        if (hipMalloc((void **) &d_x, (size_t) N * K * 4) != hipSuccess) break;
+        if (hipMalloc((void **) &d_y, ybytes) != hipSuccess) break;
+        if (resid && hipMalloc((void **) &d_r, (size_t) N * M * 4) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qA, (size_t) N * Kp) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qd, (size_t) N * (Kp / 32) * 4) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qb, (size_t) N * Kp * 2) != hipSuccess) break;      // as the model's workspace: the fp16 (or int8) operand
+        if (hipStreamCreate(&st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_w, w_q4_0, wbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_x, x, (size_t) N * K * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_y, y, ybytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (resid && hipMemcpyAsync(d_r, resid, (size_t) N * M * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (launch_repack(d_w, q.tiles, M, K, 0, 0, st) != hipSuccess) break;
+        if (want_rows && launch_tiles_to_rows(q, st) != hipSuccess) break;
+        if (want_mt4 && launch_tiles_to_mt4(q, st) != hipSuccess) break;
+        if (want_mt && launch_tiles_to_mtiles(q, st) != hipSuccess) break;
+        if (launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st) != hipSuccess) break;
+        const int epi = resid ? EPI_RESID : EPI_STORE;
+        for (int i = 0; i < GEMM_PATH_COUNT; i++) before[i] = g_gemm_path_counts[i];
+        const hipError_t e = auto_ ? launch_gemm(q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, false)
+                                   : launch_gemm_forced(path, q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, &why);
+        if (e != hipSuccess) break;
+        if (hipMemcpyAsync(y, d_y, ybytes, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+        if (hipStreamSynchronize(st) != hipSuccess) break;
+        rc = LLAMAHIP_OK;
+    } while (0);
+    if (why) set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: path %d refused for M %d, K %d, N %d: %s", path, M, K, N, why);
+    else if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in llamahip_op_prompt_gemm_q4_0: %s", hipGetErrorString(hipGetLastError()));
+    if (st) (void) hipStreamDestroy(st);
+    free_dev(d_w); free_dev(q.tiles); free_dev(q.rows); free_dev(q.mt4); free_dev(q.mt); free_dev(d_x); free_dev(d_y); free_dev(d_r);
+    free_dev(d_qA); free_dev(d_qd); free_dev(d_qb);
+    if (rc == LLAMAHIP_OK && path_taken) {
+        // the kernel family whose count moved (the matrix-core count moves with the fast one; this handle has ONE matrix-core copy)
+        auto moved = [&](int i) { return g_gemm_path_counts[i] != before[i]; };
+        *path_taken = moved(GEMM_PATH_FAST) ? LLAMAHIP_GEMM_FAST : moved(GEMM_PATH_MFMA) ? (want_mt4 ? LLAMAHIP_GEMM_MFMA4 : LLAMAHIP_GEMM_MFMA_I8)
+                    : moved(GEMM_PATH_ROWS) ? LLAMAHIP_GEMM_ROWS : moved(GEMM_PATH_SET) ? LLAMAHIP_GEMM_SET
+                    : moved(GEMM_PATH_LDS) ? LLAMAHIP_GEMM_LDS : LLAMAHIP_GEMM_GEMV;
+    }
+    return rc;
+}
+
 // the device half of the sampler on caller-supplied logits (parity tests): see llamahip_eval_topk
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap) {

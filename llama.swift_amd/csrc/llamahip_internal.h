@@ -140,12 +140,21 @@ hipError_t launch_gemv(const QMat &w, int pre, int epi, const uint32_t *qa_A, co
 // embedding row of ONE token (decode) + its {sum x, sum x^2} pair for the first norm (part_out[0])
 hipError_t launch_embed_part(const int32_t *token, const uint8_t *emb, float *x, int d, double *part_out, hipStream_t st, uint32_t *epoch = nullptr, uint64_t *xt = nullptr,
                              const uint64_t *token_mb = nullptr, const int32_t *state = nullptr, uint32_t *fault = nullptr, int n_vocab = 0);      // token_mb: the token arrives as a mailbox granule
-enum { GEMM_PATH_MFMA = 0, GEMM_PATH_ROWS = 1, GEMM_PATH_LDS = 2, GEMM_PATH_GEMV = 3, GEMM_PATH_SET = 4, GEMM_PATH_COUNT = 5 };
+// (GEMM_PATH_MFMA counts every matrix-core launch, the fast kernel's too; GEMM_PATH_FAST counts the fast kernel's alone)
+enum { GEMM_PATH_MFMA = 0, GEMM_PATH_ROWS = 1, GEMM_PATH_LDS = 2, GEMM_PATH_GEMV = 3, GEMM_PATH_SET = 4, GEMM_PATH_FAST = 5, GEMM_PATH_COUNT = 6 };
 extern long g_gemm_path_counts[GEMM_PATH_COUNT];     // launches per kernel family of launch_gemm (process-wide; tests)
 // qb_ws: scratch for the int8 operand of the matrix-core path (N * nchunks * 256 B), or nullptr
 hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
                        float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st,
                        uint8_t *qb_ws = nullptr, bool fast = false);
+// ONE kernel family of launch_gemm, forced whatever its selection rule would pick (llamahip_op_prompt_gemm_q4_0: per-op tests of every
+// prompt GEMM).  The path values are LLAMAHIP_GEMM_* of llamahip.h; EPI_STORE / EPI_RESID only.  A family that cannot take the matrix
+// (its copy is missing) or the shape is refused with hipErrorInvalidValue and the limit in *why; nothing is launched then.  Counts as
+// launch_gemm does.
+enum { GEMM_FORCE_MFMA4 = 1, GEMM_FORCE_MFMA_I8 = 2, GEMM_FORCE_FAST = 3, GEMM_FORCE_ROWS = 4, GEMM_FORCE_SET = 5, GEMM_FORCE_LDS = 6 };
+hipError_t launch_gemm_forced(int path, const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                              float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st,
+                              uint8_t *qb_ws, const char **why);
 hipError_t launch_rope_kv(const float *qkv, long qkv_stride, int d, int dh, const double *tab,
                           float *qr, float *Kc, float *Vc, int n_past, int N, hipStream_t st);
 // workspace of the many-row prompt attention (k_attnq_*): scores [H][T_cap][NB] fp32 + per-query max / 1/sum

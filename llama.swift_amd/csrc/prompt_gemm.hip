@@ -884,53 +884,42 @@ hipError_t launch_tiles_to_rows(const QMat &w, hipStream_t st) {
 //   else: LDS-staged column tiles of 16 (the last one clamped), small remainders as 8 / 4 columns
 //   a single row always goes through the decode GEMV
 // which kernel family served a mat-mul (tests assert that the full-size shapes take the path they are meant to)
-long g_gemm_path_counts[GEMM_PATH_COUNT] = { 0, 0, 0, 0, 0 };
+long g_gemm_path_counts[GEMM_PATH_COUNT] = { 0, 0, 0, 0, 0, 0 };
 
-hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
-                       float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast) {
-    // Matrix-core path when its 64 x 64-output workgroups fill the chip twice over, or from 128 rows when the last 64-column tile is
-    // not mostly padding (measured against the row-per-lane kernel, 7B, every matrix on one kernel, profiles/r04_y_midN_ab.txt: 64 rows
-    // -3 %, 96 -7 %, 128 +19 %, 192 +10 %, 240 +32 %; 1.5x at 1 024).
-    static const int mfma_min = getenv("LLAMAHIP_MFMA_MIN") ? atoi(getenv("LLAMAHIP_MFMA_MIN")) : 0;     // tests: the small models through this kernel
-    const long mfma_wgs = (long) ((w.nrb32 + 1) / 2) * ((N + 63) / 64);
-    const bool mfma_rows = N >= 128 && N * 10 >= (N + 63) / 64 * 64 * 7;
+// (the kernel families of launch_gemm below, each as it launches them; launch_gemm_forced runs one of them on its own)
+static bool mfma4_fits(const QMat &w, int N) {
     // (k_gemm_mfma4 addresses its operands as base + 32-bit byte offset)
-    const bool mfma_fits = w.mt4_bytes() < ((size_t) 1 << 32) && (size_t) N * w.nchunks * 8 * 64 < ((size_t) 1 << 32);
-    if (w.mt4 && !fast && qb_ws && mfma_fits && (mfma_min ? N >= mfma_min : (mfma_rows || (N >= 64 && mfma_wgs >= 512)))) {
-        // matrix-core path, exact: fp16 operands (QB4: 2 bytes per element of these N activation rows), four chains per MFMA
-        g_gemm_path_counts[GEMM_PATH_MFMA]++;
-        return launch_gemm_mfma4(w, epi, qa_A, qb_ws, qa_d, N, y, y_stride, resid, resid_stride, st);
-    }
-    if (w.mt && qb_ws && (mfma_min ? N >= mfma_min : (N >= 64 && mfma_wgs >= 512))) {
-        // matrix-core path on the int8 tiles (the opt-in fast path; LLAMAHIP_MFMA_I8: the round-1 exact kernel): needs the int8 operand (QB)
-        g_gemm_path_counts[GEMM_PATH_MFMA]++;
-        hipError_t e = launch_qa_to_qb(qa_A, qb_ws, w.nchunks, N, st);
-        if (e != hipSuccess) return e;
-        return launch_gemm_mfma(w, epi, qb_ws, qa_d, N, y, y_stride, resid, resid_stride, st, fast);
-    }
-    const long strideA = (long) w.nchunks * 64, strideD = (long) w.nchunks * 8;
-    // 2 .. 60 rows (a batched decode step, the reference's 9-token evals, short prompt chunks): k_gemv_set
-    if ((epi == EPI_STORE || epi == EPI_RESID) && gemv_set_applies(w, N, epi)) {
-        g_gemm_path_counts[GEMM_PATH_SET]++;
-        return launch_gemv_set(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
-    }
-    if (w.rows && N >= 2) {
-        // widest column group that still gives the chip >= 2 waves per SIMD.  Wider groups (8, 16
-        // columns: 191 / 249 VGPRs, 2 waves per SIMD) measured 10-16 % slower than 4 columns at 3 waves
-        // per SIMD on a 512-token prompt: the kernel runs at ~85 % of its VALU issue limit and the third
-        // wave is what hides the scalar-load latency of the operand.
-        int nc = 1;
-        for (int cand : { 4, 2 })
-            if ((long) w.nrb * ((N + cand - 1) / cand) >= 2048) { nc = cand; break; }
-        g_gemm_path_counts[GEMM_PATH_ROWS]++;
+    return w.mt4_bytes() < ((size_t) 1 << 32) && (size_t) N * w.nchunks * 8 * 64 < ((size_t) 1 << 32);
+}
+static hipError_t launch_mfma_i8(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                                 float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast) {
+    g_gemm_path_counts[GEMM_PATH_MFMA]++;
+    if (fast) g_gemm_path_counts[GEMM_PATH_FAST]++;
+    hipError_t e = launch_qa_to_qb(qa_A, qb_ws, w.nchunks, N, st);
+    if (e != hipSuccess) return e;
+    return launch_gemm_mfma(w, epi, qb_ws, qa_d, N, y, y_stride, resid, resid_stride, st, fast);
+}
+static hipError_t launch_rows(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                              float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st) {
+    // widest column group that still gives the chip >= 2 waves per SIMD.  Wider groups (8, 16
+    // columns: 191 / 249 VGPRs, 2 waves per SIMD) measured 10-16 % slower than 4 columns at 3 waves
+    // per SIMD on a 512-token prompt: the kernel runs at ~85 % of its VALU issue limit and the third
+    // wave is what hides the scalar-load latency of the operand.
+    int nc = 1;
+    for (int cand : { 4, 2 })
+        if ((long) w.nrb * ((N + cand - 1) / cand) >= 2048) { nc = cand; break; }
+    g_gemm_path_counts[GEMM_PATH_ROWS]++;
 #define LH_ROWS_ARGS w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st
-        switch (nc) {
-        case 4:  return launch_gemm_rows_t<4, true, 3>(LH_ROWS_ARGS);
-        case 2:  return launch_gemm_rows_t<2, true, 3>(LH_ROWS_ARGS);
-        default: return launch_gemm_rows_t<1, true, 2>(LH_ROWS_ARGS);
-        }
-#undef LH_ROWS_ARGS
+    switch (nc) {
+    case 4:  return launch_gemm_rows_t<4, true, 3>(LH_ROWS_ARGS);
+    case 2:  return launch_gemm_rows_t<2, true, 3>(LH_ROWS_ARGS);
+    default: return launch_gemm_rows_t<1, true, 2>(LH_ROWS_ARGS);
     }
+#undef LH_ROWS_ARGS
+}
+static hipError_t launch_lds(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                             float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st) {
+    const long strideA = (long) w.nchunks * 64, strideD = (long) w.nchunks * 8;
     g_gemm_path_counts[N == 1 ? GEMM_PATH_GEMV : GEMM_PATH_LDS]++;
     int n0 = 0;
     while (n0 < N) {
@@ -951,5 +940,64 @@ hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float
     return hipSuccess;
 }
 
+hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                       float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast) {
+    // Matrix-core path when its 64 x 64-output workgroups fill the chip twice over, or from 128 rows when the last 64-column tile is
+    // not mostly padding (measured against the row-per-lane kernel, 7B, every matrix on one kernel, profiles/r04_y_midN_ab.txt: 64 rows
+    // -3 %, 96 -7 %, 128 +19 %, 192 +10 %, 240 +32 %; 1.5x at 1 024).
+    static const int mfma_min = getenv("LLAMAHIP_MFMA_MIN") ? atoi(getenv("LLAMAHIP_MFMA_MIN")) : 0;     // tests: the small models through this kernel
+    const long mfma_wgs = (long) ((w.nrb32 + 1) / 2) * ((N + 63) / 64);
+    const bool mfma_rows = N >= 128 && N * 10 >= (N + 63) / 64 * 64 * 7;
+    const bool mfma_fits = mfma4_fits(w, N);
+    if (w.mt4 && !fast && qb_ws && mfma_fits && (mfma_min ? N >= mfma_min : (mfma_rows || (N >= 64 && mfma_wgs >= 512)))) {
+        // matrix-core path, exact: fp16 operands (QB4: 2 bytes per element of these N activation rows), four chains per MFMA
+        g_gemm_path_counts[GEMM_PATH_MFMA]++;
+        return launch_gemm_mfma4(w, epi, qa_A, qb_ws, qa_d, N, y, y_stride, resid, resid_stride, st);
+    }
+    if (w.mt && qb_ws && (mfma_min ? N >= mfma_min : (N >= 64 && mfma_wgs >= 512))) {
+        // matrix-core path on the int8 tiles (the opt-in fast path; LLAMAHIP_MFMA_I8: the round-1 exact kernel): needs the int8 operand (QB)
+        return launch_mfma_i8(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st, qb_ws, fast);
+    }
+    // 2 .. 60 rows (a batched decode step, the reference's 9-token evals, short prompt chunks): k_gemv_set
+    if ((epi == EPI_STORE || epi == EPI_RESID) && gemv_set_applies(w, N, epi)) {
+        g_gemm_path_counts[GEMM_PATH_SET]++;
+        return launch_gemv_set(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
+    }
+    if (w.rows && N >= 2) return launch_rows(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
+    return launch_lds(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
+}
+
+hipError_t launch_gemm_forced(int path, const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                              float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st,
+                              uint8_t *qb_ws, const char **why) {
+    const char *r = nullptr;
+    if (N < 1 || (epi != EPI_STORE && epi != EPI_RESID)) r = "N >= 1 rows and a store or residual epilogue";
+    else switch (path) {
+    case GEMM_FORCE_MFMA4:
+        if (!w.mt4 || !qb_ws) r = "k_gemm_mfma4 needs the matrix's mt4 copy and the operand workspace";
+        else if (!mfma4_fits(w, N)) r = "k_gemm_mfma4 addresses its operands with 32-bit byte offsets: mt4 bytes and N * Kp * 2 must stay below 2^32";
+        else { g_gemm_path_counts[GEMM_PATH_MFMA]++; return launch_gemm_mfma4(w, epi, qa_A, qb_ws, qa_d, N, y, y_stride, resid, resid_stride, st); }
+        break;
+    case GEMM_FORCE_MFMA_I8:
+    case GEMM_FORCE_FAST:
+        if (!w.mt || !qb_ws) r = "k_gemm_mfma needs the matrix's int8 copy and the operand workspace";
+        else return launch_mfma_i8(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st, qb_ws, path == GEMM_FORCE_FAST);
+        break;
+    case GEMM_FORCE_ROWS:
+        if (!w.rows) r = "k_gemm_rows needs the matrix's row-lane copy";
+        else return launch_rows(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
+        break;
+    case GEMM_FORCE_SET:
+        if (!gemv_set_applies(w, N, epi)) r = "k_gemv_set does not take this shape (2 .. 60 rows, and a plan that fits its LDS: llamahip_debug_set_plan)";
+        else { g_gemm_path_counts[GEMM_PATH_SET]++; return launch_gemv_set(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st); }
+        break;
+    case GEMM_FORCE_LDS:
+        return launch_lds(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
+    default:
+        r = "unknown path";
+    }
+    if (why) *why = r;
+    return hipErrorInvalidValue;
+}
 
 }  // namespace lh

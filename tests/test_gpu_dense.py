@@ -122,7 +122,8 @@ def test_dense_kernel_branches_vs_reference(L, ref, tmp_path, model_files, shape
     path = model_files(shape, ftype)
     assert same(file_sha256(path), want["file_sha256"]), "model file differs from the reference's (Q4_1: the quantize tool's bytes)"
     p, c = prompts(hp)
-    for flags in ((0, 1) if (shape, ftype, nth) == ("odd_widths", "f16", 8) else (0,)):      # 1: the greedy loop launched eagerly (NO_GRAPH)
+    # 1: the greedy loop launched eagerly (NO_GRAPH); 16: FAST_PREFILL, which dense files never reach (it re-associates the Q4_0 prompt GEMMs only)
+    for flags in ((0, 1) if (shape, ftype, nth) == ("odd_widths", "f16", 8) else (0,)) + ((16,) if nth == 8 else ()):
         with L.Model(path, n_ctx=N_CTX, flags=flags) as m:
             r = m.eval_debug(p, 0, nth, all_logits=True)
             assert same(r["logits"], want["prompt_last"]), f"flags {flags}: {N_PROMPT}-row prompt eval, last row"

@@ -85,6 +85,24 @@ def test_big_vocabulary_rows_take_the_matrix_core_lm_head(L, oracle, tmp_path):
         nc = m.eval_logprobs(toks, 0, n_threads=8)
     for k in ("logprob", "argmax", "rank", "logits"):
         assert same(nc[k], got[k]), k
+    # a FAST_PREFILL handle has the int8 matrix-core copies instead of mt4: its all-rows lm head takes the int8 EXACT kernel (fast is for the
+    # layers only), and no layer matrix of this width reaches the fast kernel's 512 workgroups -- so every field and KV row is the exact one
+    with L.Model(path, n_ctx=512, flags=FAST_PREFILL) as m:
+        p0 = L.gemm_paths()
+        fa = m.eval_logprobs(toks, 0, n_threads=8)
+        p1 = L.gemm_paths()
+        fkv = [m.kv(il, 511) for il in range(hp.n_layer)]
+        flast = m.eval(toks, 0, n_threads=8)
+        p2 = L.gemm_paths()
+        fkv_eval = [m.kv(il, 511) for il in range(hp.n_layer)]
+    assert p1["mfma"] - p0["mfma"] == 1 and p2["mfma"] == p1["mfma"], (p0, p1, p2)       # the lm head alone, on k_gemm_mfma<*, false>
+    assert p2["fast"] == p0["fast"], (p0, p2)
+    for k in ("logprob", "argmax", "rank", "logits"):
+        assert same(fa[k], got[k]), k
+    assert same(flast, last)
+    for il in range(hp.n_layer):
+        for a, b in ((fkv[il], kv[il]), (fkv_eval[il], kv_eval[il])):
+            assert same(a[0], b[0]) and same(a[1], b[1]), f"FAST handle: KV rows of layer {il}"
 
 
 RAGGED = synth.HParams(n_vocab=250, n_embd=128, n_mult=64, n_head=2, n_layer=3)
@@ -287,3 +305,7 @@ def test_tool_fast_prefill_gives_a_finite_perplexity(L, ragged, tmp_path):
     f.write_text(tool_text(700, 141))
     ppl, n, k, _ = run_tool([ragged, "--file", str(f), "--ctx", "128", "--fast-prefill"])
     assert math.isfinite(ppl) and ppl > 0 and n > 0 and k >= 2
+    # ... and it is the library's FAST handle over the same windows, bit for bit (%.17g prints every bit of a double)
+    with L.Model(ragged, n_ctx=128, flags=FAST_PREFILL) as m:
+        want = m.perplexity(m.tokenize(f.read_text(), bos=True), n_threads=8)
+    assert ppl == want["ppl"] and n == want["n_scored"], (ppl, want["ppl"], n, want["n_scored"])

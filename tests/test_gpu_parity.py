@@ -884,6 +884,23 @@ def test_fast_prefill_is_opt_in_and_close(L, tmp_path):
         assert same(ex2, fa2), "a 9-token eval must not take the fast kernel"
         t = int(np.argmax(ex2))
         assert ex.decode_greedy(t, 9, 8, 8).tolist() == fa.decode_greedy(t, 9, 8, 8).tolist()
+        # ragged prompt lengths: the fast kernel takes exactly the matrices whose 64 x 64 workgroups reach 512 (launch_gemm:
+        # ceil(M / 64) row pairs x ceil(N / 64) column tiles) -- at 65 and 100 rows w1|w3 alone, at 129 also wq|wk|wv, from 449 all four
+        de, F = kw["n_embd"], synth.n_ff_of(kw["n_embd"], kw["n_mult"])
+        for n in (65, 100, 129, 449, 512):
+            p = synth.synth_prompt(n, kw["n_vocab"], seed=20 + n)
+            want_fast = kw["n_layer"] * sum(1 for rows in (3 * de, de, 2 * F, de) if (rows + 63) // 64 * ((n + 63) // 64) >= 512)
+            p0 = L.gemm_paths()
+            b = fa.eval(p, 0, 8)
+            p1 = L.gemm_paths()
+            assert p1["fast"] - p0["fast"] == want_fast, (n, p0, p1)
+            assert p1["mfma"] - p0["mfma"] >= want_fast, (n, p0, p1)
+            a = ex.eval(p, 0, 8)
+            d_, cos = float(np.abs(a - b).max()), float(np.dot(a, b) / (np.linalg.norm(a) * np.linalg.norm(b)))
+            print(f"fast prefill vs exact, {n} tokens: max |delta logit| = {d_:.3e}, cosine {cos:.5f}")
+            assert np.all(np.isfinite(b)) and d_ <= 2.0 and cos > 0.97, (n, d_, cos)
+            p2 = L.gemm_paths()
+            assert p2["fast"] == p1["fast"], "the exact handle took the fast kernel"
 
 
 def test_7b_full_context_properties(L, model7b):

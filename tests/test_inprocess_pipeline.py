@@ -157,6 +157,34 @@ def test_pipeline_handle_equals_the_single_device_handle_on_a_long_prompt(L, tmp
 
 
 @pytest.mark.gpu
+def test_fast_prefill_pipeline_handle_equals_the_fast_plain_handle(L, tmp_path):
+    """LLAMAHIP_FLAG_FAST_PREFILL is not the reference's arithmetic, but it is deterministic and a stage runs its layers as the plain handle
+    does: a FAST pipeline handle gives the FAST plain handle's bits -- a 129-token prompt (wq|wk|wv and w1|w3 on the fast kernel), every
+    layer's KV rows, the greedy decode that follows."""
+    kw = dict(n_vocab=512, n_embd=4096, n_mult=256, n_head=32, n_layer=2)
+    path = synth_tool(tmp_path / "m.bin", seed=47, **kw)
+    prompt = synth.synth_prompt(129, kw["n_vocab"], seed=10)
+    with L.Model(path, n_ctx=256, flags=16) as one, L.Model(path, n_ctx=256, flags=16, devices=[0, 0]) as pm:
+        p0 = L.gemm_paths()
+        a = one.eval(prompt, 0, 8)
+        p1 = L.gemm_paths()
+        b = pm.eval(prompt, 0, 8)
+        p2 = L.gemm_paths()
+        assert p1["fast"] - p0["fast"] == 2 * kw["n_layer"] and p2["fast"] - p1["fast"] == 2 * kw["n_layer"], (p0, p1, p2)
+        assert same(a, b)
+        for il in range(kw["n_layer"]):
+            (k1, v1), (k2, v2) = one.kv(il, 129), pm.kv(il, 129)
+            assert same(k1, k2) and same(v1, v2), f"KV rows of layer {il}"
+        t = int(np.argmax(a))
+        ta, la = one.decode_greedy(t, 129, 12, 8, want_logits=True)
+        tb, lb = pm.decode_greedy(t, 129, 12, 8, want_logits=True)
+        assert ta.tolist() == tb.tolist() and same(la, lb)
+        for il in range(kw["n_layer"]):
+            (k1, v1), (k2, v2) = one.kv(il, 141), pm.kv(il, 141)
+            assert same(k1, k2) and same(v1, v2), f"KV rows of layer {il} after the decode"
+
+
+@pytest.mark.gpu
 def test_runner_event_stream_through_the_pipeline_with_no_change_to_the_caller(tmp_path):
     """LLAMAHIP_DEVICES is all a caller that passes no options needs: the llama_runner_* driver (the C mirror of -[LlamaPredictOperation
     main], .mm:768-901) produces the same event stream -- prompt echo, tokens, completion -- through a 2-stage pipeline as through the
