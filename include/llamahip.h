@@ -353,6 +353,30 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
 #define LLAMAHIP_GEMM_GEMV    7   /* reported only */
 int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
+/* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
+ * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
+ * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
+ * (T = n_past + N <= n_ctx) with the model's RoPE table, then runs the path.  n_threads (1 .. 64) selects the reference's V*P key split,
+ * chunk > 0 splits row n's keys as the eval of `chunk` rows it belongs to (llamahip_eval_chunks).  ws_rows: query rows per batch of the
+ * matrix-core chain's workspace (a positive multiple of 64; 0: the model's 512), which the op allocates itself with every byte NaN.
+ * merged [N][merged_stride] (merged_stride >= d) or NULL: copied whole both ways, rows merged_stride apart; wo_operand (SHORT, DEC,
+ * DEC_STREAM; NULL: not returned): the Q4_0 operand of wo those paths write, as [N][d/32] blocks in file layout.
+ * path: LLAMAHIP_ATTN_AUTO -- what a model's multi-row eval picks for the shape once its workspace exists (N >= 2); _MFMA k_rope_kv, then
+ * k_attnq_scores_lds -> k_attnq_softmax -> k_attnq_pv_mfma -> k_attnq_merge (N >= 2, head size 128, n_threads <= 8); _ROW k_rope_kv, k_attn;
+ * _SHORT k_rope_kv, k_decn_scores + k_dec_pv_blk<true> (2 .. 60 rows); _DEC k_dec_scores (RoPE and append inside, position from a device
+ * state word) + k_dec_pv_blk<false> (N = 1); _DEC_STREAM k_dec_scores + k_dec_pv_stream with one workgroup per column block (N = 1).
+ * A path that cannot take the shape is refused with a message naming the limit, before anything is launched.  *path_taken (may be NULL):
+ * the path that ran.  Not covered (model-level tests only): the kernels with cross-workgroup hand-offs (k_dec_attn_x, k_qkv_attn,
+ * k_dec_pv_dma, k_dec_pv_stream split over workgroups) and the batched decode step's form of the short path. */
+#define LLAMAHIP_ATTN_AUTO       0
+#define LLAMAHIP_ATTN_MFMA       1
+#define LLAMAHIP_ATTN_ROW        2
+#define LLAMAHIP_ATTN_SHORT      3
+#define LLAMAHIP_ATTN_DEC        4
+#define LLAMAHIP_ATTN_DEC_STREAM 5
+int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
+                          int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
+                          void *wo_operand, int32_t *path_taken, char *err, size_t err_cap);
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);
@@ -393,6 +417,9 @@ int64_t llamahip_debug_decode_phases(llamahip_model *m, int32_t n_past, int32_t 
  *  few rows (k_gemv_set), the fast kernel of LLAMAHIP_FLAG_FAST_PREFILL (k_gemm_mfma<*, true>: also counted as matrix-core)}:
  * lets a test assert that a shape took the path it is meant to.  Returns the number of families. */
 int32_t llamahip_debug_gemm_paths(int64_t *out, int32_t cap);
+/* Host-only (no device needed): the attention path (LLAMAHIP_ATTN_SHORT / _MFMA / _ROW) a model's multi-row eval of N rows after n_past
+ * takes once its workspace exists (allocated with the first multi-row eval), or -1 for N < 2 -- the rule llamahip_op_attention's AUTO runs. */
+int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx);
 /* Host-only (no device needed): how the few-row mat-mul would take n_rows activation rows against an m x k Q4_0 matrix (interleaved:
  * the w1|w3 layout; epi: 0 store, 1 +residual, 2 / 7 SiLU*up -> Q4_0 in whole- / half-block workgroups, 3 RoPE + KV append) --
  * out = {columns per wave, column-waves per row-group, column groups, row-groups per workgroup, LDS bytes}; 0 = the kernel does not

@@ -20,9 +20,11 @@ from .binding import (  # noqa: F401
     Sampler,
     bench_gemv_names,
     build,
+    debug_attn_path,
     declared_symbols,
     gemm_paths,
     lib,
+    op_attention,
     op_logprob,
     op_mul_mat_q4_0,
     op_prompt_gemm_q4_0,

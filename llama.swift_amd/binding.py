@@ -131,6 +131,9 @@ def lib() -> C.CDLL:
     L.llamahip_op_mul_mat_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_op_quantize_row_q4_0.argtypes = [vp, i32, vp, cp, sz]
     L.llamahip_op_prompt_gemm_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
+    L.llamahip_op_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, cp, sz]
+    L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
+    L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
@@ -615,6 +618,39 @@ def op_prompt_gemm_q4_0(wq: np.ndarray, x: np.ndarray, resid=None, path: str = "
     rc = lib().llamahip_op_prompt_gemm_q4_0(_ptr(wq), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
     _check(rc, err)
     return y, GEMM_PATHS[taken.value]
+
+
+ATTN_PATHS = ("auto", "mfma", "row", "short", "dec", "dec_stream")      # LLAMAHIP_ATTN_* of llamahip.h, in order
+
+
+def op_attention(qkv: np.ndarray, H: int, n_past: int, Kc: np.ndarray, Vc: np.ndarray, n_threads: int = 8, chunk: int = 0,
+                 path: str = "auto", ws_rows: int = 0, merged_stride: int | None = None, merged_init=None, want_wo: bool = True):
+    """One layer's attention (llamahip_op_attention): qkv f32 [N, 3d] un-rotated, Kc / Vc f32 [n_ctx, d] (updated in place: the device's
+    whole copy comes back).  Returns (merged f32 [N, merged_stride] -- merged_init, default NaN, where nothing was written --, the wo
+    operand uint8 [N, d/32, 20] or None, the path taken)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    N, d3 = qkv.shape
+    d = d3 // 3
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 2 or a.shape[1] != d or a.shape[0] != Kc.shape[0]:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_ctx, d]")
+    ms = d if merged_stride is None else int(merged_stride)
+    merged = np.full((N, ms), np.nan, np.float32) if merged_init is None else np.array(merged_init, np.float32, order="C").reshape(N, ms)
+    wo = np.full((N, max(d // 32, 1), 20), 0xEE, np.uint8) if want_wo else None
+    code = ATTN_PATHS.index(path) if path in ATTN_PATHS else int(path)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_attention(_ptr(qkv), N, d, int(H), int(n_past), Kc.shape[0], _ptr(Kc), _ptr(Vc), int(n_threads), int(chunk),
+                                     code, int(ws_rows), _ptr(merged), ms, _ptr(wo), C.byref(taken), err, len(err))
+    _check(rc, err)
+    name = ATTN_PATHS[taken.value]
+    return merged, (wo if name in ("short", "dec", "dec_stream") else None), name
+
+
+def debug_attn_path(N: int, head_size: int, n_past: int, n_threads: int, n_ctx: int) -> str | None:
+    """Host-only: the attention path a model's multi-row eval takes for the shape (llamahip_debug_attn_path); None for one row."""
+    r = lib().llamahip_debug_attn_path(N, head_size, n_past, n_threads, n_ctx)
+    return None if r < 0 else ATTN_PATHS[r]
 
 
 def op_quantize_row_q4_0(x: np.ndarray) -> np.ndarray:

@@ -912,7 +912,7 @@ __global__ void __launch_bounds__(1024)
 k_dec_pv_blk(const float *__restrict__ sc, const float *__restrict__ Vc, int d, int dh, int n_ctx, int nth,
              float *__restrict__ merged, uint32_t *__restrict__ qa_A, float *__restrict__ qa_d,
              const uint16_t *__restrict__ T_exp, const int32_t *__restrict__ st,
-             int n_past0, long qa_strideA, long qa_strideD, int lut_math, int chunk, const SeqSet *__restrict__ set) {
+             int n_past0, long qa_strideA, long qa_strideD, int lut_math, int chunk, const SeqSet *__restrict__ set, long m_stride) {
     extern __shared__ double smem_d[];
     double *red = smem_d;
     float *p = (float *) (smem_d + 32);
@@ -926,7 +926,7 @@ k_dec_pv_blk(const float *__restrict__ sc, const float *__restrict__ Vc, int d, 
     if (MULTI) {
         const int n = blockIdx.z;
         row = sc + ((size_t) n * gridDim.x + h) * n_ctx;
-        if (merged) merged += (size_t) n * d;
+        if (merged) merged += (size_t) n * m_stride;
         qa_A += (size_t) n * qa_strideA;
         qa_d += (size_t) n * qa_strideD;
         if (h == (int) gridDim.x - 1 && cb == (int) gridDim.y - 1)
@@ -2108,7 +2108,7 @@ bool gemv_pick_applies(const QMat &w) {
 //   sc : scratch of N * H * n_ctx floats
 hipError_t launch_attn_short(const float *qr, const float *Kc, const float *Vc, float *sc, float *merged,
                              uint32_t *qa_A, float *qa_d, int n_past, int N, int d, int H, int n_ctx, int nth,
-                             const uint16_t *T_exp, hipStream_t st, int chunk, const SeqSet *set, int set_keys) {
+                             const uint16_t *T_exp, hipStream_t st, int chunk, const SeqSet *set, int set_keys, long merged_stride) {
     // (set: positions live on the device -- the key slices up to `set_keys`, the host's bound on every row's position + 1 over the life of the
     //  captured step (0: n_ctx), are launched; those beyond a row's position return at once)
     const int dh = d / H, T = set ? (set_keys > 0 && set_keys < n_ctx ? set_keys : n_ctx) : n_past + N;
@@ -2119,7 +2119,7 @@ hipError_t launch_attn_short(const float *qr, const float *Kc, const float *Vc, 
     const int nt = (32 * (nth < 32 ? nth : 32) + 63) / 64 * 64;
     const size_t lds = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
     hipLaunchKernelGGL(k_dec_pv_blk<true>, dim3(H, dh / 32, N), dim3(nt), lds, st, sc, Vc, d, dh, n_ctx, nth, merged, qa_A, qa_d, T_exp,
-                       (const int32_t *) nullptr, n_past, (long) Kp / 4, (long) Kp / 32, g_lut_math, chunk, set);
+                       (const int32_t *) nullptr, n_past, (long) Kp / 4, (long) Kp / 32, g_lut_math, chunk, set, merged_stride > 0 ? merged_stride : (long) d);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -2235,7 +2235,7 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
     LH_LAUNCH_CHECK();
     const int nt = (32 * (nth < 32 ? nth : 32) + 63) / 64 * 64;      // whole waves: the DPP reductions need every lane live
     const size_t lds = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
-    hipLaunchKernelGGL(k_dec_pv_blk<false>, dim3(H, dh / 32), dim3(nt), lds, st, sc, Vc, d, dh, n_ctx, nth, merged, qa_A, qa_d, T_exp, state, 0, 0L, 0L, g_lut_math, 0, (const SeqSet *) nullptr);
+    hipLaunchKernelGGL(k_dec_pv_blk<false>, dim3(H, dh / 32), dim3(nt), lds, st, sc, Vc, d, dh, n_ctx, nth, merged, qa_A, qa_d, T_exp, state, 0, 0L, 0L, g_lut_math, 0, (const SeqSet *) nullptr, 0L);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -187,7 +187,7 @@ struct llamahip_model {
     double *npart_a = nullptr, *npart_b = nullptr;   // norm statistics handed between decode launches: [NORM_PART_MAX]{sum, sum2}
                                                      // a: of the row in x (attention / final norm), b: of the row in x1 (ffn norm)
     int n_seq = 1, cur_seq = 0;          // KV caches: [seq][layer][n_ctx][d]
-    AttnWs attn_ws;                      // many-row prompt attention workspace (allocated with the first eval of >= 32 tokens)
+    AttnWs attn_ws;                      // many-row prompt attention workspace (allocated with the first eval of >= 2 tokens: ensure_attn_ws)
     std::map<int, hipGraphExec_t> decode_graphs;   // keyed by nth * 4096 + seq + (attention schedule << 24)
     int attn_sched = 0;                            // decode attention schedule of the single-row pass being launched / captured (attn_sched_at): 0 fused, 1 two launches, 2 long-context
     // asynchronous pipeline-stage steps (llamahip_stage_bind / llamahip_stage_step)
@@ -489,6 +489,28 @@ int ensure_workspace(llamahip_model *m, int N, char *err, size_t err_cap) {
     return 0;
 }
 
+// the silu and exp tables of ggml_init (ggml.c:2376-2389) and the RoPE angle table [n_ctx][dh/2][cos, sin] (ggml.c:7113-7116), host libm
+static void lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te) {
+    for (int i = 0; i < (1 << 16); i++) {
+        const float f = f16_to_f32((uint16_t) i);
+        ts[i] = f32_to_f16_rne((float) ((double) f / (1.0 + exp((double) -f))));
+        te[i] = f32_to_f16_rne((float) exp((double) f));
+    }
+}
+static std::vector<double> rope_table(int n_ctx, int dh) {
+    std::vector<double> sc((size_t) n_ctx * dh);
+    for (int p = 0; p < n_ctx; p++) {
+        for (int i0 = 0; i0 < dh; i0 += 2) {
+            const double theta = pow(10000.0, ((double) -i0) / dh);
+            double sn, cs;
+            sincos(p * theta, &sn, &cs);                  // the reference's -O3 build calls sincos()
+            sc[(size_t) p * dh + i0] = cs;
+            sc[(size_t) p * dh + i0 + 1] = sn;
+        }
+    }
+    return sc;
+}
+
 // the score workspace of the multi-row prompt attention: [n_head][n_ctx][NB] fp32, NB = 512 query rows
 // (a 2 048-token 7B eval with NB = 256 / 512 / 1 024 / 2 048: 225.9 / 201.8 / 200.3 / 212.4 ms on one box in round 3, 183.3 / 161.6 / 162.6 / 175.9 in
 // round 4 (profiles/r04_v_attn_shapes_ab.txt) -- 512 keeps the workspace at a quarter and inside the Infinity Cache)
@@ -643,8 +665,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
 
     // short prompt chunks (the reference evaluates prompts 8 tokens at a time, .mm / LlamaRunner n_batch) take
     // the decode-shaped attention
-    constexpr int short_max = 60;
-    const bool short_chunk = N >= 2 && N <= short_max && m->attn_ws.S && N <= m->attn_ws.NB && dh % 32 == 0 && dh <= 256;
+    const bool short_chunk = attn_path_pick(&m->attn_ws, N, dh, n_past + N, nth) == ATTN_PATH_SHORT;
     // short evals (2 .. 16 rows): the w1|w3 launch of k_gemv_set runs half-block workgroups whose halves exchange their amax as tagged
     // granules -- needs the XCD placement the load-time self-test confirmed and one epoch per pass
     SiluHalfIO set_hx;
@@ -933,27 +954,13 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
     // ---- lookup tables (ggml.c:2376-2389) and the RoPE angle table (ggml.c:7113-7116), host libm
     {
         std::vector<uint16_t> ts(1 << 16), te(1 << 16);
-        for (int i = 0; i < (1 << 16); i++) {
-            const float f = f16_to_f32((uint16_t) i);
-            ts[i] = f32_to_f16_rne((float) ((double) f / (1.0 + exp((double) -f))));
-            te[i] = f32_to_f16_rne((float) exp((double) f));
-        }
+        lut_tables(ts, te);
         HIP_TRY(hipMalloc((void **) &m->T_silu, ts.size() * 2), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMalloc((void **) &m->T_exp, te.size() * 2), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->T_silu, ts.data(), ts.size() * 2, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->T_exp, te.data(), te.size() * 2, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         HIP_TRY(launch_check_lut_math(m->T_silu, m->T_exp, m->stream), LLAMAHIP_ERR_LOAD);
-        const int dh = d / H;
-        std::vector<double> sc((size_t) n_ctx * dh);
-        for (int p = 0; p < n_ctx; p++) {
-            for (int i0 = 0; i0 < dh; i0 += 2) {
-                const double theta = pow(10000.0, ((double) -i0) / dh);
-                double sn, cs;
-                sincos(p * theta, &sn, &cs);                  // the reference's -O3 build calls sincos()
-                sc[(size_t) p * dh + i0] = cs;
-                sc[(size_t) p * dh + i0 + 1] = sn;
-            }
-        }
+        const std::vector<double> sc = rope_table(n_ctx, d / H);
         HIP_TRY(hipMalloc((void **) &m->sincos, sc.size() * 8), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->sincos, sc.data(), sc.size() * 8, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
     }
@@ -2715,6 +2722,143 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
                     : moved(GEMM_PATH_LDS) ? LLAMAHIP_GEMM_LDS : LLAMAHIP_GEMM_GEMV;
     }
     return rc;
+}
+
+// one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
+int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
+                          int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
+                          void *wo_operand, int32_t *path_taken, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_attention";
+    if (!qkv || !Kc || !Vc || N < 1 || d < 1 || H < 1 || d % H != 0 || n_past < 0 || chunk < 0) {
+        set_err(err, err_cap, "%s: bad arguments (N %d >= 1, d %d a multiple of H %d, n_past %d >= 0, chunk %d >= 0)", fn, N, d, H, n_past, chunk);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const int dh = d / H, T = n_past + N, nth = n_threads;
+    if (T > n_ctx) { set_err(err, err_cap, "%s: T = n_past + N = %d > n_ctx %d", fn, T, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (merged && merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (ws_rows < 0 || ws_rows % 64 != 0) { set_err(err, err_cap, "%s: ws_rows %d must be a positive multiple of 64 (0: 512)", fn, ws_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (nth < 1 || nth > 64) { set_err(err, err_cap, "%s: n_threads %d outside 1 .. 64 (the model's clamp)", fn, nth); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_ATTN_AUTO || path > LLAMAHIP_ATTN_DEC_STREAM) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
+    if (d % 32 != 0) { set_err(err, err_cap, "%s: d %d must be a multiple of 32 (Q4_0 blocks of the wo operand)", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    AttnWs ws;                                       // as ensure_attn_ws, NB = ws_rows
+    ws.NB = ws_rows ? ws_rows : 512; ws.T_cap = n_ctx; ws.KS_cap = 32; ws.nth_cap = 8;
+    int run = path;
+    if (path == LLAMAHIP_ATTN_AUTO) run = N >= 2 ? attn_path_pick(&ws, N, dh, T, nth) : -1;
+    const char *why = nullptr;
+    const bool dh_ok = dh % 32 == 0 && dh <= 256;
+    switch (run) {
+    case -1: why = "AUTO takes N >= 2 (one row is the decode step: paths DEC / DEC_STREAM)"; break;
+    case LLAMAHIP_ATTN_MFMA: if (!attn_mfma_applies(&ws, N, dh, T, nth)) why = "MFMA takes N >= 2, head size 128 and n_threads <= 8"; break;
+    case LLAMAHIP_ATTN_ROW: if (!dh_ok) why = "ROW takes head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_SHORT: if (!attn_short_applies(&ws, N, dh)) why = "SHORT takes 2 <= N <= 60 and head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_DEC: if (N != 1 || !dh_ok) why = "DEC takes N = 1 and head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_DEC_STREAM:
+        if (N != 1 || !dh_ok || !pv_stream_applies(dh, n_ctx, nth)) why = "DEC_STREAM takes N = 1, head sizes that are multiples of 32 up to 256, n_threads <= 32 and n_ctx <= 4096";
+        break;
+    }
+    if (why) { set_err(err, err_cap, "%s: path %d refused for N %d, head size %d, n_threads %d: %s", fn, path, N, dh, nth, why); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const bool dec = run == LLAMAHIP_ATTN_DEC || run == LLAMAHIP_ATTN_DEC_STREAM, quant = dec || run == LLAMAHIP_ATTN_SHORT;
+    const int Kp = (d + 255) / 256 * 256;
+    const size_t cache_b = (size_t) n_ctx * d * 4, ms = merged ? (size_t) merged_stride : (size_t) d, mbytes = (size_t) N * ms * 4;
+    const size_t qaA_b = (size_t) N * Kp, qad_b = (size_t) N * (Kp / 32) * 4;
+    const size_t S_b = (size_t) H * n_ctx * ws.NB * 4, pmax_b = (size_t) H * ws.KS_cap * ws.NB * 4, inv_b = (size_t) H * ws.NB * 4;
+    const size_t part_b = (size_t) ws.nth_cap * H * ws.NB * 128 * 4;
+    float *d_qkv = nullptr, *d_K = nullptr, *d_V = nullptr, *d_qr = nullptr, *d_m = nullptr, *d_qad = nullptr;
+    uint32_t *d_qaA = nullptr; uint16_t *d_ts = nullptr, *d_te = nullptr; double *d_tab = nullptr; int32_t *d_state = nullptr;
+    hipStream_t st = nullptr;
+    int rc = LLAMAHIP_ERR_PREDICT;
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    const int32_t hs[2] = { n_past, 0 };
+    do {
+        if (hipStreamCreate(&st) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qkv, (size_t) N * 3 * d * 4) != hipSuccess) break;
+        if (hipMalloc((void **) &d_K, cache_b) != hipSuccess || hipMalloc((void **) &d_V, cache_b) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qr, (size_t) N * d * 4) != hipSuccess) break;
+        if (hipMalloc((void **) &d_m, mbytes) != hipSuccess) break;
+        if (hipMalloc((void **) &d_qaA, qaA_b) != hipSuccess || hipMalloc((void **) &d_qad, qad_b) != hipSuccess) break;
+        if (hipMalloc((void **) &d_ts, 1 << 17) != hipSuccess || hipMalloc((void **) &d_te, 1 << 17) != hipSuccess) break;
+        if (hipMalloc((void **) &d_tab, tab.size() * 8) != hipSuccess || hipMalloc((void **) &d_state, 8) != hipSuccess) break;
+        // the op's own workspace, every byte NaN (0xFF): a read of something the launch did not write shows in the result
+        if (hipMalloc((void **) &ws.S, S_b) != hipSuccess || hipMalloc((void **) &ws.pmax, pmax_b) != hipSuccess) break;
+        if (hipMalloc((void **) &ws.inv, inv_b) != hipSuccess || hipMalloc((void **) &ws.part, part_b) != hipSuccess) break;
+        if (hipMemsetAsync(ws.S, 0xFF, S_b, st) != hipSuccess || hipMemsetAsync(ws.pmax, 0xFF, pmax_b, st) != hipSuccess) break;
+        if (hipMemsetAsync(ws.inv, 0xFF, inv_b, st) != hipSuccess || hipMemsetAsync(ws.part, 0xFF, part_b, st) != hipSuccess) break;
+        if (hipMemsetAsync(d_qr, 0xFF, (size_t) N * d * 4, st) != hipSuccess) break;
+        if (hipMemsetAsync(d_qaA, 0xFF, qaA_b, st) != hipSuccess || hipMemsetAsync(d_qad, 0xFF, qad_b, st) != hipSuccess) break;
+        if (!merged && hipMemsetAsync(d_m, 0xFF, mbytes, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_qkv, qkv, (size_t) N * 3 * d * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_K, Kc, cache_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_V, Vc, cache_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (merged && hipMemcpyAsync(d_m, merged, mbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_ts, ts.data(), 1 << 17, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_te, te.data(), 1 << 17, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (hipMemcpyAsync(d_state, hs, 8, hipMemcpyHostToDevice, st) != hipSuccess) break;
+        if (launch_check_lut_math(d_ts, d_te, st) != hipSuccess) break;          // g_lut_math, as a model load leaves it
+        float *mo = merged ? d_m : nullptr;
+        hipError_t e = hipSuccess;
+        if (dec) {
+            e = launch_dec_attn(d_qkv, d, H, n_ctx, nth, d_tab, d_K, d_V, ws.S, nullptr, mo, d_qaA, d_qad, d_te, d_state, st,
+                                nullptr, nullptr, run == LLAMAHIP_ATTN_DEC_STREAM);
+        } else {
+            e = launch_rope_kv(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, n_past, N, st);
+            if (e == hipSuccess) {
+                if (run == LLAMAHIP_ATTN_SHORT)
+                    e = launch_attn_short(d_qr, d_K, d_V, ws.S, mo, d_qaA, d_qad, n_past, N, d, H, n_ctx, nth, d_te, st, chunk, nullptr, 0, (long) ms);
+                else
+                    e = launch_attn(d_qr, d_K, d_V, d_m, nullptr, nullptr, n_past, N, d, H, nth, d_te, run == LLAMAHIP_ATTN_MFMA ? &ws : nullptr, st, chunk, (long) ms);
+            }
+        }
+        if (e != hipSuccess) break;
+        if (hipMemcpyAsync(Kc, d_K, cache_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+        if (hipMemcpyAsync(Vc, d_V, cache_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+        if (merged && hipMemcpyAsync(merged, d_m, mbytes, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+        std::vector<uint32_t> qa(qaA_b / 4);
+        std::vector<float> qd(qad_b / 4);
+        if (quant && wo_operand) {
+            if (hipMemcpyAsync(qa.data(), d_qaA, qaA_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+            if (hipMemcpyAsync(qd.data(), d_qad, qad_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
+        }
+        if (hipStreamSynchronize(st) != hipSuccess) break;
+        if (quant && wo_operand) {
+            // QA layout (kcommon.hip.h quantize_y) -> Q4_0 blocks in file layout: {d, qs[16]}, qs[k] = (q[2k] + 8) | (q[2k+1] + 8) << 4
+            // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
+            uint8_t *o = (uint8_t *) wo_operand;
+            for (int n = 0; n < N; n++)
+                for (int b = 0; b < d / 32; b++) {
+                    const uint32_t *A = qa.data() + (size_t) n * (Kp / 4);
+                    uint8_t *blk = o + ((size_t) n * (d / 32) + b) * 20;
+                    memcpy(blk, &qd[(size_t) n * (Kp / 32) + b], 4);
+                    const int c = b >> 3, j = b & 7;
+                    for (int k = 0; k < 8; k++) {
+                        const uint32_t w = A[(c * 8 + k) * 8 + j] >> (4 * (j & 1));
+                        const uint32_t q0 = (w & 0xF) ^ 8, q1 = ((w >> 8) & 0xF) ^ 8, q2 = ((w >> 16) & 0xF) ^ 8, q3 = ((w >> 24) & 0xF) ^ 8;
+                        blk[4 + k] = (uint8_t) (q0 | (q1 << 4));
+                        blk[12 + k] = (uint8_t) (q2 | (q3 << 4));
+                    }
+                }
+        }
+        rc = LLAMAHIP_OK;
+    } while (0);
+    if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in %s: %s", fn, hipGetErrorString(hipGetLastError()));
+    if (st) (void) hipStreamDestroy(st);
+    free_dev(d_qkv); free_dev(d_K); free_dev(d_V); free_dev(d_qr); free_dev(d_m); free_dev(d_qaA); free_dev(d_qad);
+    free_dev(d_ts); free_dev(d_te); free_dev(d_tab); free_dev(d_state);
+    free_dev(ws.S); free_dev(ws.pmax); free_dev(ws.inv); free_dev(ws.part);
+    if (rc == LLAMAHIP_OK && path_taken) *path_taken = run;
+    return rc;
+}
+
+// host-only: the attention path a model's multi-row eval of N rows after n_past takes once its workspace exists (ensure_attn_ws)
+int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx) {
+    AttnWs ws;
+    ws.NB = 512; ws.T_cap = n_ctx; ws.KS_cap = 32; ws.nth_cap = 8;
+    if (N < 2) return -1;
+    return attn_path_pick(&ws, N, head_size, n_past + N, std::max(1, std::min((int) n_threads, 64)));
 }
 
 // the device half of the sampler on caller-supplied logits (parity tests): see llamahip_eval_topk

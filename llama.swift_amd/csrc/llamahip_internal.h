@@ -167,7 +167,16 @@ struct AttnWs {
 };
 hipError_t launch_attn(const float *qr, const float *Kc, const float *Vc, float *merged, float *dbg_p, float *dbg_kqv,
                        int n_past, int N, int d, int H, int nth, const uint16_t *T_exp, const AttnWs *ws, hipStream_t st,
-                       int chunk = 0);       // chunk > 0: the pass stands for successive evals of `chunk` rows (prompt_attn.hip split_keys)
+                       int chunk = 0,        // chunk > 0: the pass stands for successive evals of `chunk` rows (prompt_attn.hip split_keys)
+                       long merged_stride = 0);      // floats between merged rows (0: d)
+// The model's one rule for a multi-row eval's attention (forward and llamahip_op_attention's AUTO share it): ATTN_PATH_SHORT -- rope_kv,
+// then launch_attn_short (k_decn_scores + k_dec_pv_blk<true>, N <= ATTN_SHORT_MAX) -- else launch_attn, which takes the matrix-core
+// chain (k_attnq_*) where attn_mfma_applies and k_attn otherwise.  ws: the eval's workspace, NB == 0 before the first multi-row eval.
+constexpr int ATTN_SHORT_MAX = 60;
+enum { ATTN_PATH_MFMA = 1, ATTN_PATH_ROW = 2, ATTN_PATH_SHORT = 3 };      // = LLAMAHIP_ATTN_* of llamahip.h
+bool attn_mfma_applies(const AttnWs *ws, int N, int dh, int T, int nth);
+bool attn_short_applies(const AttnWs *ws, int N, int dh);
+int attn_path_pick(const AttnWs *ws, int N, int dh, int T, int nth);
 bool gemm_rope_kv_applies(const QMat &wqkv, int N, int d);
 hipError_t launch_gemm_rope_kv(const QMat &wqkv, const uint32_t *qa_A, const float *qa_d, int N, const RopeKvArgs &ra, hipStream_t st);
 bool gemm_silu_qa_applies(const QMat &w13, int N);
@@ -193,7 +202,8 @@ long set_probe_dump(unsigned long long *out, long cap_records, bool reset);     
 hipError_t launch_attn_short(const float *qr, const float *Kc, const float *Vc, float *sc, float *merged,
                              uint32_t *qa_A, float *qa_d, int n_past, int N, int d, int H, int n_ctx, int nth,
                              const uint16_t *T_exp, hipStream_t st, int chunk = 0, const SeqSet *set = nullptr,      // set: N independent single-row evals (batched decode step)
-                             int set_keys = 0);                                                                   // ... whose positions are all < set_keys (0: n_ctx): bounds the score grid
+                             int set_keys = 0,                                                                    // ... whose positions are all < set_keys (0: n_ctx): bounds the score grid
+                             long merged_stride = 0);                                                             // floats between merged rows (0: d)
 // batched decode step: embedding rows / residual rows in and out / greedy picks of the set's rows
 // (the step's FIRST launch -- embed, or rows with gather -- also writes set->pos and, given the epoch word, opens the step's epoch)
 hipError_t launch_embed_set(SeqSet *set, int n, const uint8_t *emb, float *x, int d, hipStream_t st, uint32_t *epoch = nullptr);

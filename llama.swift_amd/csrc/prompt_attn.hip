@@ -59,7 +59,7 @@ __device__ __host__ __forceinline__ int split_keys(int n_past, int N, int n, int
 __global__ void __launch_bounds__(256)
 k_attn(const float *__restrict__ qr, const float *__restrict__ Kc, const float *__restrict__ Vc,
        float *__restrict__ merged, float *__restrict__ dbg_p, float *__restrict__ dbg_kqv,
-       int n_past, int N, int d, int dh, int nth, float kq_scale, const uint16_t *__restrict__ T_exp, int chunk) {
+       int n_past, int N, int d, int dh, int nth, float kq_scale, const uint16_t *__restrict__ T_exp, int chunk, long m_stride) {
     extern __shared__ double smem_d[];
     const int h = blockIdx.x, n = blockIdx.y;
     const int T = n_past + N;
@@ -111,11 +111,14 @@ k_attn(const float *__restrict__ qr, const float *__restrict__ Kc, const float *
         const int Ts = split_keys(n_past, N, n, chunk);      // the key count the reference splits for this row (chunk_keys.h rule below)
         const int dc = (Ts + nth - 1) / nth;
         for (int th = sub; th < nth; th += nsub) {
-            const int t0 = dc * th;
-            int t1 = t0 + dc < Ts ? t0 + dc : Ts;
-            if (t1 > tmax + 1) t1 = tmax + 1;         // P = 0 beyond tmax: fma(v, 0, acc) == acc
+            const int t0 = dc * th, t1 = t0 + dc < Ts ? t0 + dc : Ts;
+            const int tv = t1 < tmax + 1 ? t1 : tmax + 1;         // the visible keys of the chunk
             float acc = 0.0f;
-            for (int t = t0; t < t1; t++) acc = fmaf(Vc[(size_t) t * d + h * dh + c], sc[t], acc);
+            for (int t = t0; t < tv; t++) acc = fmaf(Vc[(size_t) t * d + h * dh + c], sc[t], acc);
+            // P = +0 beyond tmax: fma(v, +0, acc) == acc except that a -0 sum becomes +0 at the first v >= +0 -- walked, as the reference
+            // does, only for the zero sums that can change (a chunk without a visible key stays +0)
+            if (acc == 0.0f && t0 <= tmax)
+                for (int t = tv > t0 ? tv : t0; t < t1; t++) acc = fmaf(Vc[(size_t) t * d + h * dh + c], 0.0f, acc);
             part[th * dh + c] = acc;
         }
     }
@@ -123,7 +126,7 @@ k_attn(const float *__restrict__ qr, const float *__restrict__ Kc, const float *
     if (tid < dh) {
         float s = part[tid];
         for (int th = 1; th < nth; th++) s += part[th * dh + tid];
-        merged[(size_t) n * d + h * dh + tid] = s;
+        merged[(size_t) n * m_stride + h * dh + tid] = s;
         if (dbg_kqv) dbg_kqv[((size_t) h * N + n) * dh + tid] = s;
     }
 }
@@ -407,6 +410,7 @@ k_attnq_pv_mfma(const float *__restrict__ S, const float *__restrict__ inv, cons
     }
 #undef LH_PVLOAD
     // part[th][h][nl][128]; D register r of tile (a, b): query q0 + 32 a + (r & 3) + 8 (r >> 2) + 4 kk, column 32 b + i
+    uint64_t zero = 0;                                        // bit 16 (NCB a + b) + r: that sum is +-0
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -414,21 +418,59 @@ k_attnq_pv_mfma(const float *__restrict__ S, const float *__restrict__ inv, cons
             const int nl = q0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * kk;
             float *o = part + (((size_t) th * gridDim.y + h) * NB + nl) * 128 + c0 + i;
 #pragma unroll
-            for (int b = 0; b < NCB; b++) o[32 * b] = D[a][b][r];
+            for (int b = 0; b < NCB; b++) {
+                o[32 * b] = D[a][b][r];
+                if (D[a][b][r] == 0.0f) zero |= 1ull << (16 * (NCB * a + b) + r);
+            }
         }
+    // Zero sums: keys of weight +0 still decide the sign of a zero sum (fma(v, +0, -0) = +0 for v >= +0), so a chain must END where the
+    // reference's does.  The wave walked [t0, t1): keys >= Tb of a block are left out, and under PERROW a query's lanes also walk the
+    // block's keys past their own range.  A +-0 sum whose query's chain ends elsewhere is recomputed as the reference's own chain: keys
+    // lo .. hi of its query and chunk, p = S * inv up to the query's position and +0 after it.  Rare (every term of the chain must vanish);
+    // one ballot otherwise.  A chain without a visible key (lo > the query's position) is +0 either way: the chunks past a block's last
+    // query (t0 >= Tb) are not looked at.
+    if (t0 < Tb && __builtin_amdgcn_ballot_w64(zero != 0)) {
+        while (zero) {
+            const int bit = __builtin_ctzll(zero);
+            zero &= zero - 1;
+            const int ab = bit >> 4, r = bit & 15, a = ab / NCB, b = ab % NCB;
+            const int nl = q0 + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * kk, n = nb0 + nl;
+            if (n >= N) continue;
+            const int Ts = split_keys(n_past, N, n, chunk), dcq = (Ts + nth - 1) / nth, lo = dcq * th, hi = min(lo + dcq, Ts), tq = n_past + n;
+            if (hi == t1 || lo > tq) continue;                // the walk ended where the query's chain does, or the chain has no visible key
+            const float ivq = inv[(size_t) h * NB + nl];
+            const float *vp = Vc + h * 128 + c0 + 32 * b + i;
+            float acc = 0.0f;
+            for (int t = lo; t < hi; t++) acc = fmaf(vp[(size_t) t * d], t <= tq ? S[((size_t) h * T + t) * NB + nl] * ivq : 0.0f, acc);
+            part[(((size_t) th * gridDim.y + h) * NB + nl) * 128 + c0 + 32 * b + i] = acc;
+        }
+    }
 }
 
 // merged[n][h*128 + c] = part[0] + part[1] + ... in thread order (ggml.c:5553-5577).  grid (NB/2, H), 256 threads = 2 queries x 128 columns
 __global__ void __launch_bounds__(256)
-k_attnq_merge(const float *__restrict__ part, float *__restrict__ merged, int N, int nb0, int NB, int d, int nth) {
+k_attnq_merge(const float *__restrict__ part, float *__restrict__ merged, int N, int nb0, int NB, long m_stride, int nth) {
     const int c = threadIdx.x & 127, nl = blockIdx.x * 2 + (threadIdx.x >> 7), h = blockIdx.y, H = gridDim.y;
     const int n = nb0 + nl;
     if (n >= N) return;
     float s = part[(((size_t) 0 * H + h) * NB + nl) * 128 + c];
     for (int th = 1; th < nth; th++) s += part[(((size_t) th * H + h) * NB + nl) * 128 + c];
-    merged[(size_t) n * d + h * 128 + c] = s;
+    merged[(size_t) n * m_stride + h * 128 + c] = s;
 }
 
+
+// the model's choice of prompt attention kernels (forward, llamahip_op_attention's AUTO, llamahip_debug_attn_path): the decode-shaped
+// per-row kernels for short chunks, else the matrix-core chain where the workspace takes the shape, else k_attn.  ws->NB > 0: the
+// workspace exists (ensure_attn_ws, the first multi-row eval)
+bool attn_mfma_applies(const AttnWs *ws, int N, int dh, int T, int nth) {
+    return ws && ws->NB > 0 && dh == 128 && N >= 2 && T <= ws->T_cap && nth <= ws->nth_cap;
+}
+bool attn_short_applies(const AttnWs *ws, int N, int dh) {
+    return N >= 2 && N <= ATTN_SHORT_MAX && ws && ws->NB > 0 && N <= ws->NB && dh % 32 == 0 && dh <= 256;
+}
+int attn_path_pick(const AttnWs *ws, int N, int dh, int T, int nth) {
+    return attn_short_applies(ws, N, dh) ? ATTN_PATH_SHORT : attn_mfma_applies(ws, N, dh, T, nth) ? ATTN_PATH_MFMA : ATTN_PATH_ROW;
+}
 
 hipError_t launch_rope_kv(const float *qkv, long qkv_stride, int d, int dh, const double *tab,
                           float *qr, float *Kc, float *Vc, int n_past, int N, hipStream_t st) {
@@ -438,10 +480,12 @@ hipError_t launch_rope_kv(const float *qkv, long qkv_stride, int d, int dh, cons
 }
 
 hipError_t launch_attn(const float *qr, const float *Kc, const float *Vc, float *merged, float *dbg_p, float *dbg_kqv,
-                       int n_past, int N, int d, int H, int nth, const uint16_t *T_exp, const AttnWs *ws, hipStream_t st, int chunk) {
+                       int n_past, int N, int d, int H, int nth, const uint16_t *T_exp, const AttnWs *ws, hipStream_t st, int chunk,
+                       long merged_stride) {
     const int dh = d / H, T = n_past + N;
+    const long ms = merged_stride > 0 ? merged_stride : d;
     const float kq_scale = 1.0f / sqrtf((float) d / (float) H);          // .mm:620
-    if (ws && ws->S && dh == 128 && N >= 2 && !dbg_p && !dbg_kqv && T <= ws->T_cap && nth <= ws->nth_cap) {
+    if (attn_mfma_applies(ws, N, dh, T, nth) && !dbg_p && !dbg_kqv) {
         for (int nb0 = 0; nb0 < N; nb0 += ws->NB) {
             const int nb = min(ws->NB, N - nb0), qb = (nb + 63) / 64;
             // scores: 16 queries per wave, ~4 waves per SIMD over key slices
@@ -459,13 +503,13 @@ hipError_t launch_attn(const float *qr, const float *Kc, const float *Vc, float 
             if (chunk > 0) hipLaunchKernelGGL((k_attnq_pv_mfma<true, 2>), dim3(qb, H, nth * 2), dim3(64), 0, st, ws->S, ws->inv, Vc, ws->part, n_past, N, nb0, ws->NB, d, T, nth, chunk);
             else hipLaunchKernelGGL((k_attnq_pv_mfma<false, 2>), dim3(qb, H, nth * 2), dim3(64), 0, st, ws->S, ws->inv, Vc, ws->part, n_past, N, nb0, ws->NB, d, T, nth, 0);
             LH_LAUNCH_CHECK();
-            hipLaunchKernelGGL(k_attnq_merge, dim3((nb + 1) / 2, H), dim3(256), 0, st, ws->part, merged, N, nb0, ws->NB, d, nth);
+            hipLaunchKernelGGL(k_attnq_merge, dim3((nb + 1) / 2, H), dim3(256), 0, st, ws->part, merged, N, nb0, ws->NB, ms, nth);
             LH_LAUNCH_CHECK();
         }
         return hipSuccess;
     }
     const size_t lds = 32 * sizeof(double) + ((size_t) T + (size_t) nth * dh + dh + 16) * sizeof(float);
-    hipLaunchKernelGGL(k_attn, dim3(H, N), dim3(256), lds, st, qr, Kc, Vc, merged, dbg_p, dbg_kqv, n_past, N, d, dh, nth, kq_scale, T_exp, chunk);
+    hipLaunchKernelGGL(k_attn, dim3(H, N), dim3(256), lds, st, qr, Kc, Vc, merged, dbg_p, dbg_kqv, n_past, N, d, dh, nth, kq_scale, T_exp, chunk, ms);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

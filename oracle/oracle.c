@@ -512,6 +512,72 @@ static void norm_mul(const float *x, const float *w, float *y, int d, int N) {
 static int g_split_chunk = 0;
 void orc_set_split_chunk(int chunk) { g_split_chunk = chunk > 0 ? chunk : 0; }
 
+/* One layer's attention (.mm:614-646) on rotated q [N][d] and the cache rows 0 .. n_past + N - 1 of Kc / Vc ([T][d], K rotated):
+ * kq [H][N][T] receives soft_max(scale * K.Q + mask), kqv [H][N][dh] the V*P product, merged [N][d] its permuted copy. */
+static void attention(const float *q, const float *Kc, const float *Vc, int d, int H, int n_past, int N, int nth, int chunk,
+                      float *kq, float *kqv, float *merged) {
+    const int dh = d / H, T = n_past + N;
+    const float kq_scale = 1.0f / sqrtf((float) d / H);         /* .mm:620 */
+    /* KQ[h][n][t] = K[t,h,:] . Q[n,h,:]  (.mm:614; ggml.c:5579-5618) then scale, mask, softmax */
+#pragma omp parallel for num_threads(omp_workers(nth)) collapse(2) schedule(static)
+    for (int h = 0; h < H; h++)
+        for (int n = 0; n < N; n++) {
+            float *row = kq + ((size_t) h * N + n) * T;
+            for (int t = 0; t < T; t++) {
+                float s = orc_vec_dot_f32(dh, Kc + (size_t) t * d + h * dh, q + (size_t) n * d + h * dh);
+                s *= kq_scale;                                                /* .mm:617-621 */
+                if (t > n_past + n) s = -INFINITY;                            /* ggml.c:6946-6953 */
+                row[t] = s;
+            }
+            orc_softmax_rows(row, row, T, 1);                                 /* .mm:627 */
+        }
+
+    /* KQV[h][n][c] = sum_t V[t,h,c] * P[h][n][t]  (.mm:638).  src0 is "transposed", so the
+     * reference splits t into n_threads contiguous ranges, each accumulated with FMA into a
+     * private zeroed buffer (ggml.c:5619-5665), then adds the buffers in thread order
+     * (ggml.c:5553-5577).  The split therefore is part of the numerics.                     */
+    const int nwk = omp_workers(nth);
+    float *part_all = (float *) malloc((size_t) nwk * nth * dh * 4);      /* one set of n_threads buffers per OpenMP worker */
+#pragma omp parallel for num_threads(nwk) collapse(2) schedule(static)
+    for (int h = 0; h < H; h++)
+        for (int n = 0; n < N; n++) {
+            const float *P = kq + ((size_t) h * N + n) * T;
+            float *part = part_all + (size_t) omp_get_thread_num() * nth * dh;
+            memset(part, 0, (size_t) nth * dh * 4);
+            /* keys the reference splits for this row: n_past + N of the llama_eval call the row belongs to.  chunk > 0 evaluates the
+             * rows as if they had arrived in successive calls of that many rows -- the claim behind llamahip_eval_chunks, checked
+             * against real successive calls by tests/test_oracle_chunks.py and tests/test_oracle_vs_ref.py */
+            const int Ts = chunk > 0 ? n_past + ((n / chunk + 1) * chunk < N ? (n / chunk + 1) * chunk : N) : T;
+            const int dc = (Ts + nth - 1) / nth;
+            for (int th = 0; th < nth; th++) {
+                const int t0 = dc * th, t1 = (t0 + dc < Ts) ? t0 + dc : Ts;
+                float *acc = part + (size_t) th * dh;
+                for (int t = t0; t < t1; t++) {
+                    const float *vr = Vc + (size_t) t * d + h * dh;
+                    for (int c = 0; c < dh; c++) acc[c] = fmaf(vr[c], P[t], acc[c]);
+                }
+            }
+            float *out = kqv + ((size_t) h * N + n) * dh;
+            for (int c = 0; c < dh; c++) {
+                float s = part[c];
+                for (int th = 1; th < nth; th++) s += part[(size_t) th * dh + c];
+                out[c] = s;
+            }
+        }
+    free(part_all);
+    for (int n = 0; n < N; n++)                                               /* .mm:641-646 */
+        for (int h = 0; h < H; h++)
+            memcpy(merged + (size_t) n * d + h * dh, kqv + ((size_t) h * N + n) * dh, (size_t) dh * 4);
+}
+
+void orc_attention(const float *q, const float *Kc, const float *Vc, int d, int H, int n_past, int N, int n_threads, int chunk,
+                   float *merged) {
+    const int nth = n_threads < 1 ? 1 : n_threads, T = n_past + N;
+    float *kq = (float *) malloc((size_t) H * N * T * 4), *kqv = (float *) malloc((size_t) N * d * 4);
+    attention(q, Kc, Vc, d, H, n_past, N, nth, chunk > 0 ? chunk : 0, kq, kqv, merged);
+    free(kq); free(kqv);
+}
+
 /* layers [l0, l1): a pipeline stage.  The first stage embeds `tokens`, later stages start from
  * hidden_in (the fp32 residual stream, .mm:563-564, 687-690); the last stage applies the final norm
  * and lm head, earlier stages return the residual stream in hidden_out. */
@@ -531,9 +597,7 @@ static int eval_range(orc_model *m, int n_threads, int n_past, const int32_t *to
     float *k = (float *) malloc(Nd * 4), *v = (float *) malloc(Nd * 4), *ffin = (float *) malloc(Nd * 4);
     float *merged = (float *) malloc(Nd * 4), *up = (float *) malloc(NF * 4), *gate = (float *) malloc(NF * 4);
     float *kq = (float *) malloc((size_t) H * N * T * 4), *kqv = (float *) malloc(Nd * 4);
-    float *part = (float *) malloc((size_t) nth * dh * 4);
     uint8_t *qa = (uint8_t *) malloc((size_t) N * ((F > d ? F : d) / QK) * BLK);
-    const float kq_scale = 1.0f / sqrtf((float) d / H);         /* .mm:620 */
 
     if (l0 == 0) {
         /* ggml_get_rows on a Q4_0 matrix (ggml.c:6760-6785) */
@@ -561,60 +625,9 @@ static int eval_range(orc_model *m, int n_threads, int n_past, const int32_t *to
         orc_rope(Kc, dh, H, T, n_past, 1);                                        /* .mm:604-611, in cache */
         DUMP(5, q, Nd);
 
-        /* KQ[h][n][t] = K[t,h,:] . Q[n,h,:]  (.mm:614; ggml.c:5579-5618) then scale, mask, softmax */
-#pragma omp parallel for num_threads(omp_workers(nth)) collapse(2) schedule(static)
-        for (int h = 0; h < H; h++)
-            for (int n = 0; n < N; n++) {
-                float *row = kq + ((size_t) h * N + n) * T;
-                for (int t = 0; t < T; t++) {
-                    float s = orc_vec_dot_f32(dh, Kc + (size_t) t * d + h * dh, q + (size_t) n * d + h * dh);
-                    s *= kq_scale;                                                /* .mm:617-621 */
-                    if (t > n_past + n) s = -INFINITY;                            /* ggml.c:6946-6953 */
-                    row[t] = s;
-                }
-                orc_softmax_rows(row, row, T, 1);                                 /* .mm:627 */
-            }
+        attention(q, Kc, Vc, d, H, n_past, N, nth, g_split_chunk, kq, kqv, merged);   /* .mm:614-646 */
         DUMP(6, kq, (size_t) H * N * T);
-
-        /* KQV[h][n][c] = sum_t V[t,h,c] * P[h][n][t]  (.mm:638).  src0 is "transposed", so the
-         * reference splits t into n_threads contiguous ranges, each accumulated with FMA into a
-         * private zeroed buffer (ggml.c:5619-5665), then adds the buffers in thread order
-         * (ggml.c:5553-5577).  The split therefore is part of the numerics.                     */
-        {
-            const int nwk = omp_workers(nth);
-            float *part_all = (float *) malloc((size_t) nwk * nth * dh * 4);      /* one set of n_threads buffers per OpenMP worker */
-#pragma omp parallel for num_threads(nwk) collapse(2) schedule(static)
-            for (int h = 0; h < H; h++)
-                for (int n = 0; n < N; n++) {
-                    const float *P = kq + ((size_t) h * N + n) * T;
-                    float *part = part_all + (size_t) omp_get_thread_num() * nth * dh;
-                    memset(part, 0, (size_t) nth * dh * 4);
-                    /* keys the reference splits for this row: n_past + N of the llama_eval call the row belongs to.  g_split_chunk > 0
-                     * (orc_set_split_chunk, tests only) evaluates the rows as if they had arrived in successive calls of that many
-                     * rows -- the claim behind llamahip_eval_chunks, checked against real successive calls by tests/test_oracle_chunks.py */
-                    const int Ts = g_split_chunk > 0 ? n_past + ((n / g_split_chunk + 1) * g_split_chunk < N ? (n / g_split_chunk + 1) * g_split_chunk : N) : T;
-                    const int dc = (Ts + nth - 1) / nth;
-                    for (int th = 0; th < nth; th++) {
-                        const int t0 = dc * th, t1 = (t0 + dc < Ts) ? t0 + dc : Ts;
-                        float *acc = part + (size_t) th * dh;
-                        for (int t = t0; t < t1; t++) {
-                            const float *vr = Vc + (size_t) t * d + h * dh;
-                            for (int c = 0; c < dh; c++) acc[c] = fmaf(vr[c], P[t], acc[c]);
-                        }
-                    }
-                    float *out = kqv + ((size_t) h * N + n) * dh;
-                    for (int c = 0; c < dh; c++) {
-                        float s = part[c];
-                        for (int th = 1; th < nth; th++) s += part[(size_t) th * dh + c];
-                        out[c] = s;
-                    }
-                }
-            free(part_all);
-        }
         DUMP(7, kqv, Nd);
-        for (int n = 0; n < N; n++)                                               /* .mm:641-646 */
-            for (int h = 0; h < H; h++)
-                memcpy(merged + (size_t) n * d + h * dh, kqv + ((size_t) h * N + n) * dh, (size_t) dh * 4);
         DUMP(8, merged, Nd);
         quantize_rows(merged, qa, d, N);
         matmul_q4(l->wo, qa, cur, N, nth);                                        /* .mm:649-651 */
@@ -651,7 +664,7 @@ static int eval_range(orc_model *m, int n_threads, int n_past, const int32_t *to
     }
 
     free(logits); free(x); free(cur); free(q); free(k); free(v); free(ffin); free(merged);
-    free(up); free(gate); free(kq); free(kqv); free(part); free(qa);
+    free(up); free(gate); free(kq); free(kqv); free(qa);
     return 0;
 }
 

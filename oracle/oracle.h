@@ -33,6 +33,10 @@ void     orc_norm_rows(const float *x, float *y, int ncols, int nrows);         
 void     orc_silu_rows(const float *x, float *y, int ncols, int nrows);          /* ggml.c:1956-1963 */
 void     orc_softmax_rows(const float *x, float *y, int ncols, int nrows);       /* ggml.c:6982-7050 */
 void     orc_rope(float *x, int dh, int H, int n, int n_past, int mode);         /* ggml.c:7076-7131 */
+/* one layer's attention (.mm:614-646): q [N][d] rotated, Kc / Vc rows 0 .. n_past + N - 1 ([T][d], K rotated) -> merged [N][d];
+ * n_threads selects the reference's V*P key split, chunk > 0 splits row n's keys as the eval of `chunk` rows it would belong to */
+void     orc_attention(const float *q, const float *Kc, const float *Vc, int d, int H, int n_past, int N, int n_threads, int chunk,
+                       float *merged);
 
 /* --- model --------------------------------------------------------------------------------- */
 orc_model *orc_load(const char *path, int n_ctx, int force_parts, char *err, size_t err_cap); /* .mm:98-498 */

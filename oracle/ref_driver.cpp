@@ -13,7 +13,7 @@
 //                                    : LlamaPredictOperation.mm:33-38
 // Also exported: thin wrappers over the reference's non-static kernels (quantize_row_q4_0,
 // dequantize_row_q4_0, ggml_quantize_q4_0, llama_tokenize, llama_sample_top_p_top_k) and single-op
-// graphs (mul_mat, norm, soft_max, silu, rope) so tests can pin the standalone restatement
+// graphs (mul_mat, norm, soft_max, silu, rope, attention) so tests can pin the standalone restatement
 // (oracle/oracle.c) op by op.
 //
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
@@ -482,6 +482,37 @@ void ref_rope(float * x, int dh, int H, int n, int n_past, int mode) {
     ggml_build_forward_expand(&gf, ty);
     ggml_graph_compute(c, &gf);
     memcpy(x, ty->data, sizeof(float)*(size_t) dh*H*n);
+    ggml_free(c);
+}
+
+// one layer's attention as the reference's graph builds it (LlamaPredictOperation.mm:614-646): q [N][d] already rotated, Kc / Vc
+// [T][d] (T = n_past + N; K rotated as the cache holds it) -> merged [N][d].  n_threads gives the reference's V*P key split.
+void ref_attention(const float * q, const float * Kc, const float * Vc, int d, int H, int n_past, int N, int n_threads, float * merged) {
+    const int dh = d/H, T = n_past + N;
+    const size_t qkv = (size_t) (N + 2*T)*d, kq = (size_t) H*N*T;
+    auto & buf = op_arena(4*(2*qkv + 3*kq + (size_t) n_threads*((size_t) N*d + 64)) + (1u << 20));
+    ggml_init_params ip = { buf.size(), buf.data() };
+    ggml_context * c = ggml_init(ip);
+    ggml_tensor * tq = ggml_new_tensor_3d(c, GGML_TYPE_F32, dh, H, N);
+    ggml_tensor * tk = ggml_new_tensor_3d(c, GGML_TYPE_F32, dh, H, T);
+    ggml_tensor * tv = ggml_new_tensor_1d(c, GGML_TYPE_F32, (int64_t) T*d);
+    memcpy(tq->data, q, sizeof(float)*(size_t) N*d);
+    memcpy(tk->data, Kc, sizeof(float)*(size_t) T*d);
+    memcpy(tv->data, Vc, sizeof(float)*(size_t) T*d);
+    ggml_tensor * Q = ggml_permute(c, tq, 0, 2, 1, 3);
+    ggml_tensor * K = ggml_permute(c, tk, 0, 2, 1, 3);
+    ggml_tensor * KQ = ggml_mul_mat(c, K, Q);                                // .mm:614
+    KQ = ggml_scale(c, KQ, ggml_new_f32(c, 1.0f/sqrt(float(d)/H)));          // .mm:617-621
+    KQ = ggml_diag_mask_inf(c, KQ, n_past);                                  // .mm:624
+    KQ = ggml_soft_max(c, KQ);                                               // .mm:627
+    ggml_tensor * Vt = ggml_permute(c, ggml_reshape_3d(c, tv, dh, H, T), 1, 2, 0, 3);   // .mm:630-635
+    ggml_tensor * KQV = ggml_mul_mat(c, Vt, KQ);                             // .mm:638
+    ggml_tensor * out = ggml_cpy(c, ggml_permute(c, KQV, 0, 2, 1, 3), ggml_new_tensor_2d(c, GGML_TYPE_F32, d, N));   // .mm:641-646
+    ggml_cgraph gf = {};
+    gf.n_threads = n_threads;
+    ggml_build_forward_expand(&gf, out);
+    ggml_graph_compute(c, &gf);
+    memcpy(merged, out->data, sizeof(float)*(size_t) N*d);
     ggml_free(c);
 }
 

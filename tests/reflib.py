@@ -59,6 +59,11 @@ class RefLib:
         L.ref_mul_mat_q4_0.argtypes = [u8p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.ref_unary_rows.argtypes = [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int]
         L.ref_rope.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        # (a reference build kept from before ref_attention joined the driver -- oracle/_ref is only rebuilt where the reference sources
+        # are present -- has no attention op: the tests that compare against it then read its stored outputs, tests/refgolden.py)
+        self.has_attention = hasattr(L, "ref_attention")
+        if self.has_attention:
+            L.ref_attention.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]
         L.refllama_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.c_int, i32p, C.c_int]
         L.refllama_sampler_new.restype = C.c_void_p
         L.refllama_sampler_new.argtypes = [C.c_int32, C.c_int]
@@ -116,6 +121,17 @@ class RefLib:
         n, H, dh = x.shape
         self.L.ref_rope(x, dh, H, n, n_past, mode)
         return x
+
+    def attention(self, q, Kc, Vc, H: int, n_past: int, n_threads: int) -> np.ndarray:
+        """ref_attention: one layer's attention graph (.mm:614-646) on rotated q [N, d] and cache rows [n_past + N, d] -> merged [N, d]"""
+        q = np.ascontiguousarray(q, np.float32)
+        N, d = q.shape
+        T = n_past + N
+        Kc = np.ascontiguousarray(np.asarray(Kc, np.float32).reshape(-1, d)[:T])
+        Vc = np.ascontiguousarray(np.asarray(Vc, np.float32).reshape(-1, d)[:T])
+        out = np.empty((N, d), np.float32)
+        self.L.ref_attention(q, Kc, Vc, d, H, n_past, N, n_threads, out)
+        return out
 
     def f2h(self, v: float) -> int:
         return int(self.L.ref_fp32_to_fp16(C.c_float(v)))
@@ -226,6 +242,7 @@ class OracleLib:
         for fn in (L.orc_norm_rows, L.orc_silu_rows, L.orc_softmax_rows):
             fn.argtypes = [f32p, f32p, C.c_int, C.c_int]
         L.orc_rope.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.orc_attention.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]
         L.orc_load.restype = C.c_void_p
         L.orc_load.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
         L.orc_free.argtypes = [C.c_void_p]
@@ -298,6 +315,17 @@ class OracleLib:
         n, H, dh = x.shape
         self.L.orc_rope(x, dh, H, n, n_past, mode)
         return x
+
+    def attention(self, q, Kc, Vc, H, n_past, n_threads, chunk=0):
+        """orc_attention: q [N, d] rotated, cache rows [n_past + N, d] (K rotated) -> merged [N, d]"""
+        q = np.ascontiguousarray(q, np.float32)
+        N, d = q.shape
+        T = n_past + N
+        Kc = np.ascontiguousarray(np.asarray(Kc, np.float32).reshape(-1, d)[:T])
+        Vc = np.ascontiguousarray(np.asarray(Vc, np.float32).reshape(-1, d)[:T])
+        out = np.empty((N, d), np.float32)
+        self.L.orc_attention(q, Kc, Vc, d, H, n_past, N, n_threads, chunk, out)
+        return out
 
     def load(self, path, n_ctx=512, force_parts=0):
         err = C.create_string_buffer(512)

@@ -125,3 +125,60 @@ def test_model_eval_and_multipart_merge(oracle, ref, tmp_path, nth, parts):
         la = mo.eval(np.array([tok], np.int32), n_past, nth)["logits"]
         assert np.array_equal(la, lb)
         tok = int(np.argmax(lb)); n_past += 1
+
+
+# one layer's attention (.mm:614-646): (regime, dh, H, N, n_past, n_threads) -- head sizes 32 .. 256, one / nine / seventy rows with and
+# without earlier keys, n_threads 1, 3, 8, 12 and more than the keys (16 > 9), key counts the split does not divide
+ATTN_CASES = [("plain", 32, 4, 1, 0, 1), ("plain", 64, 2, 9, 0, 3), ("plain", 128, 2, 70, 5, 8), ("plain", 256, 1, 9, 20, 12),
+              ("plain", 64, 2, 9, 0, 16), ("plain", 128, 2, 1, 40, 8), ("wide", 128, 2, 70, 0, 3), ("ties", 64, 2, 9, 7, 8),
+              ("leak", 128, 2, 70, 3, 12), ("negzero", 64, 2, 70, 0, 1), ("negzero", 128, 1, 9, 4, 3), ("negzero", 32, 2, 70, 6, 8),
+              ("zeroq", 32, 4, 70, 11, 8)]
+# a chunked pass (chunk > 0) against successive reference calls of `chunk` rows: (regime, dh, H, N, n_past, n_threads, chunk)
+ATTN_CHUNK_CASES = [("plain", 64, 2, 70, 5, 8, 9), ("negzero", 64, 2, 30, 0, 3, 7), ("plain", 128, 1, 20, 3, 12, 1)]
+ATTN_STORE = refgolden.os.path.join(refgolden.os.path.dirname(refgolden.STORE), "ref_attention.npz")
+
+
+def _attn_ref(ref):
+    """the reference build where it has the attention op, else None (its stored outputs)"""
+    return ref if ref is not None and ref.has_attention else None
+
+
+def _attn_inputs(oracle, regime, dh, H, N, n_past):
+    import attn_cases
+    qkv, Kc, Vc = attn_cases.make(regime, N, H * dh, H, n_past, n_past + N + 3, seed=5)
+    _, Kr, Vr, qr = attn_cases.oracle_side(oracle, qkv, Kc, Vc, H, n_past, 1)
+    return qr, Kr, Vr
+
+
+@refgolden.computed_by("oracle_vs_ref.attention", ATTN_CASES, store=ATTN_STORE)
+def _ref_attention(ref, tmp, regime, dh, H, N, n_past, nth):
+    import reflib
+    qr, Kr, Vr = _attn_inputs(reflib.OracleLib(), regime, dh, H, N, n_past)
+    return {"merged": refgolden.digest(ref.attention(qr, Kr, Vr, H, n_past, nth))}
+
+
+@pytest.mark.parametrize("regime,dh,H,N,n_past,nth", ATTN_CASES)
+def test_attention(oracle, ref, tmp_path, regime, dh, H, N, n_past, nth):
+    qr, Kr, Vr = _attn_inputs(oracle, regime, dh, H, N, n_past)
+    got = oracle.attention(qr, Kr, Vr, H, n_past, nth)
+    want = refgolden.outputs("oracle_vs_ref.attention", _attn_ref(ref), tmp_path, regime, dh, H, N, n_past, nth)
+    assert np.array_equal(refgolden.digest(got), want["merged"])
+    if regime == "negzero":              # the regime reaches -0 sums (else it would not test their sign)
+        assert np.any(got.view(np.uint32) == 0x80000000)
+
+
+@refgolden.computed_by("oracle_vs_ref.attention_chunks", ATTN_CHUNK_CASES, store=ATTN_STORE)
+def _ref_attention_chunks(ref, tmp, regime, dh, H, N, n_past, nth, chunk):
+    import reflib
+    qr, Kr, Vr = _attn_inputs(reflib.OracleLib(), regime, dh, H, N, n_past)
+    rows = [ref.attention(qr[c0:c0 + chunk], Kr, Vr, H, n_past + c0, nth) for c0 in range(0, N, chunk)]
+    return {"merged": refgolden.digest(np.concatenate(rows))}
+
+
+@pytest.mark.parametrize("regime,dh,H,N,n_past,nth,chunk", ATTN_CHUNK_CASES)
+def test_attention_chunks_are_successive_calls(oracle, ref, tmp_path, regime, dh, H, N, n_past, nth, chunk):
+    qr, Kr, Vr = _attn_inputs(oracle, regime, dh, H, N, n_past)
+    want = refgolden.outputs("oracle_vs_ref.attention_chunks", _attn_ref(ref), tmp_path, regime, dh, H, N, n_past, nth, chunk)
+    assert np.array_equal(refgolden.digest(oracle.attention(qr, Kr, Vr, H, n_past, nth, chunk)), want["merged"])
+    # ... and the one-call pass differs (else the case would not test the split)
+    assert not np.array_equal(refgolden.digest(oracle.attention(qr, Kr, Vr, H, n_past, nth)), want["merged"])
