@@ -70,7 +70,7 @@ typedef struct llamahip_opts {
  * process (.mm:790; LlamaRunnerBridge.mm:18-26).  A handle loaded with n_devices > 1 -- or, for a caller that passes no options such as the
  * replacement bridge, with the environment variable LLAMAHIP_DEVICES="0,1,...,7" (or a count: "8" = devices 0 .. 7) -- holds one stage per
  * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_eval_logprobs / llamahip_perplexity / llamahip_decode_greedy /
- * llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
+ * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
  * crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
  * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
@@ -226,6 +226,65 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
 int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
                                  int32_t n_steps, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p,
                                  double temp, int32_t *out_tokens, int32_t *out_exact, char *err, size_t err_cap);
+
+/* ---- greedy decode with drafted tokens (prompt-lookup / speculative decoding, exact) --------------------------------------------
+ * A decode step streams every weight once to produce ONE token; an eval of 2 .. 16 rows streams them once for all its rows.  So: guess the
+ * next tokens cheaply (a DRAFT), evaluate [last token, draft ...] as one eval, take every row's greedy pick and keep the longest prefix of
+ * the draft the model itself would have produced, plus the one token behind it that comes for free.  The token stream is
+ * llamahip_decode_greedy's; only the number of weight passes changes.
+ * Why it is exact: with every row on the V*P key split of its OWN single-token eval (llamahip_eval_chunks with chunk_tokens = 1) row j of an
+ * eval at n_past holds, bit for bit, the logits of a single-token eval at n_past + j -- every other operator of llama_eval's graph works row
+ * by row -- and the pick is k_argmax's rule (the largest value, the lowest index on ties, a NaN never).
+ * (Norm statistics, as for llamahip_stage_step_set: the fused single step takes the norm's second moment in one pass, a multi-row eval in
+ * two; both narrow to the same fp32 bits except with probability ~2^-29 per value.  The equality of a verify step and single steps is
+ * therefore BY TEST (tests/test_gpu_lookup.py), not structural.)
+ *
+ * llamahip_verify_greedy -- one verify step: rows = [token, draft[0 .. n_draft)] at n_past, n_draft 0 .. 15 (0: one plain step).
+ *   picks[j], j <= *n_accept: the token llamahip_decode_greedy produces at position n_past + j; *n_accept = the number of leading draft
+ *   tokens that are those picks (draft[j] == picks[j] for j < *n_accept).  picks[j] beyond that: the pick of a row that was fed a token the
+ *   model would not have produced (of no use), or -1 where the row was not evaluated.  The caller's new context is n_past + *n_accept + 1
+ *   and its next token picks[*n_accept]; logits_next (may be NULL): the n_vocab logits that token was picked from.
+ *   KV cache: rows [n_past, n_past + *n_accept + 1) are bit for bit what single steps leave; rows AT AND ABOVE the returned context are
+ *   unspecified (rejected draft positions were written) -- they are never read before they are overwritten, because every eval writes
+ *   its own positions first.  n_past + n_draft + 1 > n_ctx is refused.
+ * llamahip_decode_greedy_lookup -- the loop: llamahip_decode_greedy's arguments and results (out_tokens[0 .. n_steps), logits_last, KV
+ *   rows [0, n_past + n_steps): bit for bit), drafts by llamahip_lookup_draft from the tokens seen so far -- context (the n_context = n_past
+ *   tokens at positions [0, n_past)), first_token, everything produced -- and then from `corpus` (optional: any token stream worth
+ *   looking continuations up in; NULL / 0).  A draft that would pass position n_past + n_steps - 1 is cut; where the drafter finds
+ *   nothing the step is the fused single-token step.  draft_len 1 .. 15, 0 = LLAMAHIP_LOOKUP_DRAFT_LEN; ngram_min / ngram_max > 0,
+ *   0 = LLAMAHIP_LOOKUP_NGRAM_MIN / _MAX.  stats (may be NULL; struct_size set by the caller): steps of either kind, tokens drafted and
+ *   accepted -- n_steps = n_verify_steps + n_single_steps + n_accepted.
+ * Handles: plain and in-process pipeline handles.  f16 / f32 / Q4_1 files have no per-row key split in one pass: llamahip_verify_greedy
+ *   evaluates its rows one single-token step at a time and stops behind the first mismatch, llamahip_decode_greedy_lookup is
+ *   llamahip_decode_greedy and reports zero drafts.  Stage handles (layer_begin / layer_end) and HOST_ONLY handles are refused; the
+ *   arguments are checked first, without a device.
+ * llamahip_lookup_draft -- host only, no handle, deterministic: for n = ngram_max down to ngram_min take the last n tokens of `history`,
+ *   find their most recent EARLIER occurrence in history, else their last occurrence in corpus (an occurrence counts if at least one token
+ *   follows it), and on the first hit copy the tokens that followed it to draft_out, up to draft_len, stopping at the end of that stream.
+ *   Returns the draft's length, 0 = no hit, -1 = bad arguments (0 = the defaults here too).  A linear scan from the end of each stream.
+ * llamahip_op_verify_rows -- the device half on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16, tokens[n_rows]
+ *   = [last token, draft ...]; picks[n_rows], *n_accept.
+ * Defaults.  n-grams of 3 down to 1 tokens: the longest match first, a single token as the last resort (a wrong draft costs a verify step
+ * that still yields one token).  LLAMAHIP_LOOKUP_DRAFT_LEN: the draft length whose break-even acceptance rate is lowest in
+ * profiles/lookup_probe_7b.json (tools/lookup_probe.py; DESIGN.md "Drafted greedy decoding"). */
+#define LLAMAHIP_LOOKUP_DRAFT_LEN 15
+#define LLAMAHIP_LOOKUP_NGRAM_MIN 1
+#define LLAMAHIP_LOOKUP_NGRAM_MAX 3
+typedef struct llamahip_lookup_stats {
+    int32_t struct_size;               /* sizeof(llamahip_lookup_stats) */
+    int32_t n_verify_steps, n_single_steps;
+    int64_t n_drafted, n_accepted;     /* draft tokens evaluated / of those, reproduced by the model */
+} llamahip_lookup_stats;
+int llamahip_verify_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft,
+                           int32_t *n_accept, int32_t *picks /* n_draft + 1 */, float *logits_next, char *err, size_t err_cap);
+int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
+                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                  int32_t *out_tokens, float *logits_last, llamahip_lookup_stats *stats, char *err, size_t err_cap);
+int32_t llamahip_lookup_draft(const int32_t *history, int32_t n_history, const int32_t *corpus, int32_t n_corpus,
+                              int32_t draft_len, int32_t ngram_min, int32_t ngram_max, int32_t *draft_out);
+int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
+                            int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */

@@ -24,6 +24,7 @@ from .binding import (  # noqa: F401
     declared_symbols,
     gemm_paths,
     lib,
+    lookup_draft,
     op_attention,
     op_logprob,
     op_mul_mat_q4_0,
@@ -31,6 +32,7 @@ from .binding import (  # noqa: F401
     op_quantize_row_q4_0,
     op_topk,
     op_topk_rows,
+    op_verify_rows,
     quantize_file,
     set_plan,
     version,

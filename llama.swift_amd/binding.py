@@ -56,6 +56,10 @@ class _GemvBench(C.Structure):
                 ("algo_bytes", C.c_double)]
 
 
+class _LookupStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_verify_steps", C.c_int32), ("n_single_steps", C.c_int32), ("n_drafted", C.c_int64), ("n_accepted", C.c_int64)]
+
+
 class _Stats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("weight_bytes_device", C.c_int64), ("kv_bytes_device", C.c_int64),
                 ("n_evals", C.c_int64), ("t_load_ms", C.c_double), ("t_eval_ms_total", C.c_double), ("n_stages", C.c_int32), ("hand_off", C.c_int32)]
@@ -110,6 +114,11 @@ def lib() -> C.CDLL:
     L.llamahip_sample_top_p_top_k.argtypes = [vp, vp, vp, C.c_double, i32, C.c_double, C.c_double]
     L.llamahip_sample_top_p_top_k.restype = i32
     L.llamahip_decode_greedy.argtypes = [vp, i32, i32, i32, i32, vp, vp, cp, sz]
+    L.llamahip_verify_greedy.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, cp, sz]
+    L.llamahip_decode_greedy_lookup.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(_LookupStats), cp, sz]
+    L.llamahip_lookup_draft.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
+    L.llamahip_lookup_draft.restype = i32
+    L.llamahip_op_verify_rows.argtypes = [vp, i32, i32, vp, vp, vp, cp, sz]
     L.llamahip_decode_greedy_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, cp, sz]
     L.llamahip_decode_sample_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, cp, sz]
     L.llamahip_eval_debug.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, C.c_int64, vp, cp, sz]
@@ -413,6 +422,35 @@ class Model:
         _check(rc, err)
         return (out, logits) if want_logits else out
 
+    def verify_greedy(self, token: int, draft, n_past: int, n_threads: int = 8, want_logits: bool = False):
+        """llamahip_verify_greedy: the rows [token, draft ...] at n_past as one eval.  Returns (n_accept, picks[len(draft) + 1]) -- the new
+        context is n_past + n_accept + 1, the next token picks[n_accept] -- and with want_logits the logits that token was picked from."""
+        draft = np.ascontiguousarray(draft, np.int32).ravel()
+        picks = np.full(draft.size + 1, -1, np.int32)
+        n_acc = C.c_int32(-1)
+        logits = np.empty(self.n_vocab, np.float32) if want_logits else None
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_verify_greedy(self._h, n_threads, n_past, int(token), _ptr(draft), draft.size, C.byref(n_acc), _ptr(picks), _ptr(logits), err, len(err))
+        _check(rc, err)
+        return (n_acc.value, picks, logits) if want_logits else (n_acc.value, picks)
+
+    def decode_greedy_lookup(self, first_token: int, n_steps: int, n_past: int, context, corpus=None, draft_len: int = 0, ngram_min: int = 0,
+                             ngram_max: int = 0, n_threads: int = 8, want_logits: bool = False):
+        """llamahip_decode_greedy_lookup: decode_greedy's tokens, drafted from context (the n_past tokens already evaluated) + what is produced,
+        then from corpus.  Returns (tokens[n_steps], stats dict) and with want_logits the last step's logits too."""
+        context = np.ascontiguousarray(context, np.int32).ravel()
+        corpus = None if corpus is None else np.ascontiguousarray(corpus, np.int32).ravel()
+        out = np.empty(max(n_steps, 0), np.int32)
+        logits = np.empty(self.n_vocab, np.float32) if want_logits else None
+        st = _LookupStats(C.sizeof(_LookupStats))
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_greedy_lookup(self._h, n_threads, n_past, int(first_token), n_steps, _ptr(context), context.size, _ptr(corpus),
+                                                 0 if corpus is None else corpus.size, draft_len, ngram_min, ngram_max, _ptr(out), _ptr(logits),
+                                                 C.byref(st), err, len(err))
+        _check(rc, err)
+        stats = {k: getattr(st, k) for k, _ in _LookupStats._fields_ if k != "struct_size"}
+        return (out, stats, logits) if want_logits else (out, stats)
+
     def decode_greedy_multi(self, first_tokens, n_past, n_steps: int, n_threads: int = 8) -> np.ndarray:
         """llamahip_decode_greedy_multi: sequences in KV slots 0 .. len(first_tokens) - 1 decoded together; returns [n_seqs][n_steps]."""
         ft = np.ascontiguousarray(first_tokens, np.int32)
@@ -580,6 +618,35 @@ def op_logprob(logits2d, targets=None):
     rc = lib().llamahip_op_logprob(_ptr(logits2d), R, V, _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk), err, len(err))
     _check(rc, err)
     return lp, am, rk
+
+
+def lookup_draft(history, corpus=None, draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0) -> np.ndarray:
+    """llamahip_lookup_draft (host only): the tokens that followed the most recent earlier occurrence of history's last n tokens -- in history,
+    else in corpus -- for the longest n of ngram_max .. ngram_min that occurs; empty = no hit.  0 = the header's defaults."""
+    history = np.ascontiguousarray(history, np.int32).ravel()
+    corpus = None if corpus is None else np.ascontiguousarray(corpus, np.int32).ravel()
+    out = np.empty(max(draft_len, 16), np.int32)
+    n = lib().llamahip_lookup_draft(_ptr(history), history.size, _ptr(corpus), 0 if corpus is None else corpus.size, draft_len, ngram_min, ngram_max, _ptr(out))
+    if n < 0:
+        raise ValueError(f"lookup_draft: bad arguments (draft_len {draft_len}, ngram_min {ngram_min}, ngram_max {ngram_max})")
+    return out[:n].copy()
+
+
+def op_verify_rows(logits2d, tokens):
+    """k_verify_rows + k_accept_drafts on host rows f32 [n_rows, n_vocab] (1 .. 16 rows); tokens = [last token, draft ...], one per row.
+    Returns (n_accept, picks int32[n_rows])."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+    if tokens.size != R:
+        raise ValueError(f"tokens: {tokens.size} ids for {R} rows")
+    picks, n_acc = np.full(R, -1, np.int32), C.c_int32(-1)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_verify_rows(_ptr(logits2d), R, V, _ptr(tokens), C.byref(n_acc), _ptr(picks), err, len(err))
+    _check(rc, err)
+    return n_acc.value, picks
 
 
 def op_mul_mat_q4_0(wq: np.ndarray, x: np.ndarray) -> np.ndarray:

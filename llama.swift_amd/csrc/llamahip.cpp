@@ -175,6 +175,7 @@ struct llamahip_model {
     bool score_rows = false;             // set around forward() by the scoring entry points: the all-rows lm head takes those copies
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
+    int32_t *d_verify = nullptr;         // drafted greedy decoding (last stage): {position, cursor} | 16 row tokens | 16 picks | {n_accept, 16 picks} | from [64]: the token log, n_ctx entries (verify_io)
     uint32_t *d_attn_sync = nullptr;     // per-head hand-off counters of k_dec_attn_x ([H][32] dwords); null: two-launch attention
     uint64_t *d_qkv2 = nullptr, *d_sc2 = nullptr;   // tagged hand-off buffers of k_qkv_attn: [3 d] and [H][n_ctx] {fp32 bits, tag} granules
     uint32_t *d_epoch = nullptr;         // ... and the epoch word their tags are made from (bumped once per decode forward pass)
@@ -275,7 +276,7 @@ llamahip_model::~llamahip_model() {
     free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
     free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
     free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score);
+    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify);
     free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
     free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
     free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
@@ -2211,6 +2212,227 @@ static int pipe_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_pa
 }
 
 // ------------------------------------------------------------------------------------------------
+// Drafted greedy decoding: llamahip_verify_greedy / llamahip_decode_greedy_lookup.  A verify step is ONE eval of the rows
+// [last accepted token, draft ...] at n_past in which every row takes the V*P key split of its own single-token eval (chunk = 1, as
+// llamahip_eval_chunks) and the last stage's lm head runs over every row (as the scoring entry points); row j then holds the logits of
+// a single-token eval at n_past + j.  k_verify_rows picks each row's token and k_accept_drafts counts how much of the draft the picks
+// reproduce (verify.hip), on the last stage's stream: {n_accept, picks} come back through the pinned block, 4 (N + 1) bytes.
+// ------------------------------------------------------------------------------------------------
+struct VerifyIo { int32_t *state, *tok, *pick, *res, *log; };
+static VerifyIo verify_io(llamahip_model *m) { return { m->d_verify, m->d_verify + 2, m->d_verify + 18, m->d_verify + 34, m->d_verify + 64 }; }
+static int verify_ensure(llamahip_model *last, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    if (last->d_verify) return 0;
+    const size_t bytes = (64 + (size_t) last->hp.n_ctx) * 4;
+    HIP_TRY(hipMalloc((void **) &last->d_verify, bytes), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemset(last->d_verify, 0, bytes), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// the two kernels over the N rows of last->logits, ordered behind the eval on last->stream (restart_pos >= 0: the log starts over there)
+static int verify_enqueue(llamahip_model *last, const int32_t *rows, int N, int restart_pos, char *err, size_t err_cap) {
+    int rc = verify_ensure(last, err, err_cap);
+    if (rc) return rc;
+    const VerifyIo io = verify_io(last);
+    const int32_t *tok = io.tok;
+    int32_t *res = io.res;
+    if (last->h_io) {                       // (the stream is idle: every entry point synchronises before it returns)
+        memcpy(last->h_io->tok, rows, (size_t) N * 4);
+        tok = last->d_io->tok; res = last->d_io->id;
+    } else HIP_TRY(hipMemcpyAsync(io.tok, rows, (size_t) N * 4, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_verify_rows(last->logits, N, last->hp.n_vocab, io.pick, last->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_accept_drafts(tok, io.pick, 0, N, restart_pos, io.log, last->hp.n_ctx, io.state, res, last->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// a single-token step of the lookup loop took `pick` by the fused decode step: the same log and position word, one more entry (not waited for)
+static int verify_append(llamahip_model *last, int32_t pick, int restart_pos, char *err, size_t err_cap) {
+    int rc = verify_ensure(last, err, err_cap);
+    if (rc) return rc;
+    const VerifyIo io = verify_io(last);
+    HIP_TRY(launch_accept_drafts(nullptr, nullptr, pick, 1, restart_pos, io.log, last->hp.n_ctx, io.state, io.res, last->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
+// one verify step of N = 2 .. 16 rows on a Q4_0 handle, plain or pipeline (eval_score's walk); res: {n_accept, picks[N]}
+static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *rows, int N, int restart_pos, int32_t *res,
+                       float *logits_next, char *err, size_t err_cap) {
+    const double t0 = now_ms();
+    llamahip_model *last = m;
+    int rc;
+    if (m->stages.empty()) {
+        if ((rc = eval_stage_enqueue(m, n_threads, n_past, rows, N, nullptr, 1, true, err, err_cap)) != 0) return rc;
+        if ((rc = verify_enqueue(m, rows, N, restart_pos, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+        if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
+    } else {
+        const int S = (int) m->stages.size();
+        const size_t d = m->hp.n_embd;
+        for (int s = 1; s < S; s++) if ((rc = pipe_ensure_in(m->stages[s], N, err, err_cap)) != 0) return rc;
+        for (int s = 0; s < S; s++) {
+            llamahip_model *st = m->stages[s];
+            st->cur_seq = m->cur_seq;
+            if ((rc = eval_stage_enqueue(st, n_threads, n_past, rows, N, s ? st->pipe_in : nullptr, 1, s == S - 1, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+            if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        }
+        last = m->stages[S - 1];
+        if ((rc = verify_enqueue(last, rows, N, restart_pos, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = pipe_sync(m, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    }
+    if (last->h_io) memcpy(res, last->h_io->id, (size_t) (N + 1) * 4);
+    else HIP_TRY(hipMemcpy(res, verify_io(last).res, (size_t) (N + 1) * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    if (res[0] < 0 || res[0] > N - 1) { set_err(err, err_cap, "verify step: the device reported %d accepted of %d drafted tokens", res[0], N - 1); return LLAMAHIP_ERR_PREDICT; }
+    const size_t V = m->hp.n_vocab;
+    if (logits_next) HIP_TRY(hipMemcpy(logits_next, last->logits + (size_t) res[0] * V, V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+static bool lookup_dense(const llamahip_model *m) { return m->stages.empty() ? m->dense : m->stages[0]->dense; }
+
+// the arguments first (a HOST_ONLY handle knows n_vocab / n_ctx: the checks are the same without a device), then the handle
+static int check_verify_args(llamahip_model *m, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, const char *fn, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int V = m->hp.n_vocab, C = m->hp.n_ctx;
+    if (n_draft < 0 || n_draft > VERIFY_ROWS_MAX - 1) { set_err(err, err_cap, "%s: n_draft must be 0 .. %d (got %d): a verify step has at most %d rows", fn, VERIFY_ROWS_MAX - 1, n_draft, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_past < 0 || n_past > C - n_draft - 1) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_draft (%d) + 1 > n_ctx (%d)", fn, n_past, n_draft, C); return LLAMAHIP_ERR_PREDICT; }
+    if (token < 0 || token >= V) { set_err(err, err_cap, "%s: token id %d out of range [0, %d)", fn, token, V); return LLAMAHIP_ERR_PREDICT; }
+    if (n_draft > 0 && !draft) { set_err(err, err_cap, "%s: null draft", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_draft; i++)
+        if (draft[i] < 0 || draft[i] >= V) { set_err(err, err_cap, "%s: draft token id %d at %d out of range [0, %d)", fn, draft[i], i, V); return LLAMAHIP_ERR_PREDICT; }
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+}
+
+static int verify_greedy_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, int restart_pos,
+                              int32_t *n_accept, int32_t *picks, float *logits_next, char *err, size_t err_cap) {
+    const int N = n_draft + 1;
+    if (N == 1 || lookup_dense(m)) {
+        // one plain step -- and f16 / f32 / Q4_1 files, which have no per-row key split in one pass: the rows one single-token step at a
+        // time, stopping behind the first pick the draft does not continue with
+        int a = 0;
+        int32_t tok = token;
+        for (;; a++) {
+            int rc = llamahip_decode_greedy(m, n_threads, n_past + a, tok, 1, &picks[a], nullptr, err, err_cap);
+            if (rc) return rc;
+            if (a == n_draft || picks[a] != draft[a]) break;
+            tok = draft[a];
+        }
+        for (int j = a + 1; j < N; j++) picks[j] = -1;
+        *n_accept = a;
+        llamahip_model *last = m->stages.empty() ? m : m->stages.back();
+        if (logits_next) {
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(logits_next, last->logits, (size_t) m->hp.n_vocab * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        }
+        return LLAMAHIP_OK;
+    }
+    int32_t rows[VERIFY_ROWS_MAX], res[VERIFY_ROWS_MAX + 1];
+    rows[0] = token;
+    for (int i = 0; i < n_draft; i++) rows[1 + i] = draft[i];
+    int rc = verify_step(m, n_threads, n_past, rows, N, restart_pos, res, logits_next, err, err_cap);
+    if (rc) return rc;
+    *n_accept = res[0];
+    memcpy(picks, res + 1, (size_t) N * 4);
+    return LLAMAHIP_OK;
+}
+
+int llamahip_verify_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft,
+                           int32_t *n_accept, int32_t *picks, float *logits_next, char *err, size_t err_cap) {
+    int rc = check_verify_args(m, n_past, token, draft, n_draft, "llamahip_verify_greedy", err, err_cap);
+    if (rc) return rc;
+    if (!n_accept || !picks) { set_err(err, err_cap, "llamahip_verify_greedy: null output"); return LLAMAHIP_ERR_PREDICT; }
+    return verify_greedy_impl(m, n_threads, n_past, token, draft, n_draft, n_past, n_accept, picks, logits_next, err, err_cap);
+}
+
+int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
+                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                  int32_t *out_tokens, float *logits_last, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_greedy_lookup";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int V = m->hp.n_vocab, C = m->hp.n_ctx;
+    if (n_steps < 1 || n_past < 0 || n_past > C - n_steps) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past, n_steps, C); return LLAMAHIP_ERR_PREDICT; }
+    if (first_token < 0 || first_token >= V) { set_err(err, err_cap, "%s: token id %d out of range [0, %d)", fn, first_token, V); return LLAMAHIP_ERR_PREDICT; }
+    if (n_context != n_past) { set_err(err, err_cap, "%s: n_context (%d) must equal n_past (%d): the drafter's history is the tokens at positions [0, n_past)", fn, n_context, n_past); return LLAMAHIP_ERR_PREDICT; }
+    if (n_context > 0 && !context) { set_err(err, err_cap, "%s: null context", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_context; i++)
+        if (context[i] < 0 || context[i] >= V) { set_err(err, err_cap, "%s: context token id %d at %d out of range [0, %d)", fn, context[i], i, V); return LLAMAHIP_ERR_PREDICT; }
+    if (n_corpus < 0 || (n_corpus > 0 && !corpus)) { set_err(err, err_cap, "%s: a corpus of %d tokens at a null pointer", fn, n_corpus); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_corpus; i++)
+        if (corpus[i] < 0 || corpus[i] >= V) { set_err(err, err_cap, "%s: corpus token id %d at %d out of range [0, %d)", fn, corpus[i], i, V); return LLAMAHIP_ERR_PREDICT; }
+    if (draft_len < 0 || draft_len > VERIFY_ROWS_MAX - 1) { set_err(err, err_cap, "%s: draft_len must be 1 .. %d (0 = the default, %d; got %d)", fn, VERIFY_ROWS_MAX - 1, LLAMAHIP_LOOKUP_DRAFT_LEN, draft_len); return LLAMAHIP_ERR_PREDICT; }
+    if (ngram_min < 0 || ngram_max < 0 || ((ngram_min ? ngram_min : LLAMAHIP_LOOKUP_NGRAM_MIN) > (ngram_max ? ngram_max : LLAMAHIP_LOOKUP_NGRAM_MAX))) {
+        set_err(err, err_cap, "%s: ngram_min (%d) / ngram_max (%d) must be positive with ngram_min <= ngram_max (0 = the defaults, %d and %d)", fn, ngram_min, ngram_max,
+                LLAMAHIP_LOOKUP_NGRAM_MIN, LLAMAHIP_LOOKUP_NGRAM_MAX);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (stats && stats->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) { set_err(err, err_cap, "%s: stats->struct_size (%d) is not sizeof(llamahip_lookup_stats) (%d)", fn, stats->struct_size, (int) sizeof(llamahip_lookup_stats)); return LLAMAHIP_ERR_PREDICT; }
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+    if (rc) return rc;
+    llamahip_lookup_stats ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
+    if (lookup_dense(m)) {
+        // f16 / f32 / Q4_1 files: no multi-row eval with every row's own key split -- nothing is drafted
+        if ((rc = llamahip_decode_greedy(m, n_threads, n_past, first_token, n_steps, out_tokens, logits_last, err, err_cap)) != 0) return rc;
+        ls.n_single_steps = n_steps;
+        if (stats) *stats = ls;
+        return LLAMAHIP_OK;
+    }
+    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+    llamahip_model *last = m->stages.empty() ? m : m->stages.back();
+    std::vector<int32_t> hist((size_t) n_past + n_steps + 1);
+    if (n_past > 0) memcpy(hist.data(), context, (size_t) n_past * 4);
+    hist[n_past] = first_token;                     // hist[0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
+    int done = 0;
+    while (done < n_steps) {
+        const int pos = n_past + done, restart = done == 0 ? n_past : -1;
+        int32_t draft[VERIFY_ROWS_MAX], res_n = 0, picks[VERIFY_ROWS_MAX];
+        // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
+        const int room = std::min(K, n_steps - done - 1);
+        const int nd = room > 0 ? llamahip_lookup_draft(hist.data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft) : 0;
+        if (nd < 0 || nd > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, nd, room); return LLAMAHIP_ERR_PREDICT; }
+        const bool fin_single = nd == 0 && done + 1 == n_steps;
+        if (nd == 0) {
+            // nothing to verify: the fused single-token step, its pick appended to the device log behind it
+            if ((rc = llamahip_decode_greedy(m, n_threads, pos, hist[pos], 1, picks, fin_single ? logits_last : nullptr, err, err_cap)) != 0) return rc;
+            if ((rc = verify_append(last, picks[0], restart, err, err_cap)) != 0) return rc;
+            ls.n_single_steps++;
+        } else {
+            int32_t rows[VERIFY_ROWS_MAX], res[VERIFY_ROWS_MAX + 1];
+            rows[0] = hist[pos];
+            memcpy(rows + 1, draft, (size_t) nd * 4);
+            const bool may_end = done + nd + 1 == n_steps;      // (all accepted: row nd is the call's last position)
+            if ((rc = verify_step(m, n_threads, pos, rows, nd + 1, restart, res, nullptr, err, err_cap)) != 0) return rc;
+            res_n = res[0];
+            memcpy(picks, res + 1, (size_t) (nd + 1) * 4);
+            if (may_end && res_n == nd && logits_last) {
+                HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+                HIP_TRY(hipMemcpy(logits_last, last->logits + (size_t) nd * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            }
+            ls.n_verify_steps++;
+            ls.n_drafted += nd;
+            ls.n_accepted += res_n;
+        }
+        for (int j = 0; j <= res_n; j++) hist[pos + 1 + j] = picks[j];
+        done += res_n + 1;
+    }
+    // the result is the device's log, checked against what the host saw step by step
+    std::vector<int32_t> h(64 + (size_t) n_steps);
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipStreamSynchronize(last->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(h.data(), last->d_verify, h.size() * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    if (done != n_steps || h[0] != n_past + n_steps || h[1] != n_steps || memcmp(h.data() + 64, hist.data() + n_past + 1, (size_t) n_steps * 4) != 0) {
+        set_err(err, err_cap, "%s: the device log holds %d tokens up to position %d, the host counted %d of %d up to %d", fn, h[1], h[0], done, n_steps, n_past + n_steps);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    memcpy(out_tokens, h.data() + 64, (size_t) n_steps * 4);
+    if (stats) *stats = ls;
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
 // llamahip_decode_greedy_multi: n_seqs independent greedy streams at once -- the micro-batched schedule of the layer pipeline (SURVEY.md 8e:
 // "throughput scales only with independent sequences in flight"), native, behind the C ABI.  The slots are cut into G >= n_stages groups of
 // consecutive slots; a stage steps a group as ONE set (llamahip_stage_step_set: its weights streamed once for the group) and hands the group's
@@ -2945,6 +3167,33 @@ int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, co
     if (logprob_out) memcpy(logprob_out, h.data(), N * 8);
     if (argmax_out) memcpy(argmax_out, h.data() + N * 8, N * 4);
     if (rank_out) memcpy(rank_out, h.data() + N * 12, N * 4);
+    return LLAMAHIP_OK;
+}
+
+// k_verify_rows + k_accept_drafts on caller-supplied rows (parity tests): see llamahip_verify_greedy
+int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
+                            int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    if (!logits || !tokens || n_rows < 1 || n_rows > VERIFY_ROWS_MAX || n_vocab < 1) {
+        set_err(err, err_cap, "llamahip_op_verify_rows: bad arguments (n_rows %d of 1 .. %d, n_vocab %d)", n_rows, VERIFY_ROWS_MAX, n_vocab);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    int rc = need_device(err, err_cap);
+    if (rc) return rc;
+    const size_t N = (size_t) n_rows, row_bytes = (size_t) n_vocab * 4;
+    float *d_l = nullptr; int32_t *d_v = nullptr;      // d_v: {position, cursor} | tokens | picks | result | from [64]: a log of 16 entries
+    int32_t h[VERIFY_ROWS_MAX + 1] = { 0 };
+    hipError_t e = hipMalloc((void **) &d_l, N * row_bytes);
+    if (e == hipSuccess) e = hipMalloc((void **) &d_v, 80 * 4);
+    if (e == hipSuccess) e = hipMemset(d_v, 0, 80 * 4);
+    if (e == hipSuccess) e = hipMemcpy(d_l, logits, N * row_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_v + 2, tokens, N * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = launch_verify_rows(d_l, n_rows, n_vocab, d_v + 18, nullptr);
+    if (e == hipSuccess) e = launch_accept_drafts(d_v + 2, d_v + 18, 0, n_rows, 0, d_v + 64, VERIFY_ROWS_MAX, d_v, d_v + 34, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(h, d_v + 34, (N + 1) * 4, hipMemcpyDeviceToHost);
+    free_dev(d_l); free_dev(d_v);
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
+    if (n_accept) *n_accept = h[0];
+    if (picks) memcpy(picks, h + 1, N * 4);
     return LLAMAHIP_OK;
 }
 

@@ -243,5 +243,13 @@ hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *wi
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,
                               hipStream_t st);
 hipError_t launch_argmax(const float *logits, int V, int32_t *out, int out_idx, int32_t *next_token, int32_t *state, hipStream_t st, uint64_t *token_mb = nullptr);
+// drafted greedy decoding (verify.hip): pick[r] = the greedy pick of row r (k_argmax's rule), 1 .. VERIFY_ROWS_MAX rows; then, for
+// tokens = [last accepted token, draft ...] of those rows: n_accept = the number of leading draft tokens the picks reproduce,
+// log[state[1] ..] (log_cap entries) receives pick[0 .. n_accept], state = {position, cursor} advances by n_accept + 1 and
+// res = {n_accept, pick[0 .. n_rows)}.  pick == null: one row whose pick is pick_imm; restart_pos >= 0: state = {restart_pos, 0} first.
+constexpr int VERIFY_ROWS_MAX = 16;
+hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st);
+hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int pick_imm, int n_rows, int restart_pos, int32_t *log, int log_cap,
+                                int32_t *state, int32_t *res, hipStream_t st);
 
 }  // namespace lh

@@ -1,0 +1,112 @@
+// verify.hip -- the device half of drafted greedy decoding (llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_op_verify_rows).
+// A verify step evaluates the rows [last accepted token, draft ...] as ONE multi-row eval whose row j holds the logits of a single-token
+// eval at n_past + j; the two kernels here turn those N rows into "how much of the draft the model itself would have produced", so that
+// 4 (N + 1) bytes cross to the host instead of N x n_vocab x 4.
+//
+// k_verify_rows: one workgroup of 1024 threads per row, the row's greedy pick by k_argmax's rule (decode.hip argmax_take): the largest
+//   value, the LOWEST index on ties; a NaN is never taken (both comparisons are false); a row of nothing but NaN picks 0.  The scan is
+//   k_argmax's, thread for thread (each thread visits its indices in ascending order, the pairs are folded by the same DPP / readlane /
+//   LDS tree) -- not that it matters: "largest value, then lowest index" is a total order on the non-NaN entries, so every reduction
+//   tree gives the same pick.  The lm head's pick epilogue of the fused greedy step (decode.hip EPI_STORE_PICK, launch_gemv_pick) follows
+//   the same rule through an order-preserving 64-bit key {value bits with -0 folded onto +0, ~index} under an unsigned max, key 0 for a
+//   NaN and index 0 when no key is set: -0 == +0 ties go to the lower index and a row of -inf picks index 0 there as here.  So
+//   llamahip_decode_greedy and a verify step never disagree on a row.
+// k_accept_drafts: one wave, behind it on the stream.  tokens[0] is the last accepted token, tokens[1 .. N) the draft:
+//   n_accept = the largest a <= N - 1 with pick[j] == tokens[j + 1] for all j < a
+//   log[cursor .. cursor + n_accept] = pick[0 .. n_accept]; state = {position, cursor}, both advanced by n_accept + 1
+//   res = {n_accept, pick[0 .. N)}      (res: the pinned, device-mapped host block where the handle has one)
+// Plain loads and stores, no hand-offs between workgroups: the launch boundary orders the two kernels.
+#include <cmath>
+
+#include "kcommon.hip.h"
+
+namespace lh {
+
+__device__ __forceinline__ void vr_take(float &v, int &i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+template <int CTRL>
+__device__ __forceinline__ void vr_take_dpp(float &v, int &i) {
+    const float ov = dpp_f<CTRL>(v);
+    const int oi = __builtin_amdgcn_mov_dpp(i, CTRL, 0xF, 0xF, true);
+    vr_take(v, i, ov, oi);
+}
+
+__global__ void __launch_bounds__(1024)
+k_verify_rows(const float *__restrict__ logits, int V, int32_t *__restrict__ pick) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int r = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    const float *__restrict__ row = logits + (size_t) r * V;
+    float best = -INFINITY;
+    int idx = 0x7fffffff;
+    for (int i0 = tid; i0 < V; i0 += 32 * nt) {
+        float v[32];
+#pragma unroll
+        for (int u = 0; u < 32; u++) v[u] = row[min(i0 + u * nt, V - 1)];
+#pragma unroll
+        for (int u = 0; u < 32; u++) {
+            const int i = i0 + u * nt;
+            if (i < V) vr_take(best, idx, v[u], i);           // ascending i: a tie keeps the lower index
+        }
+    }
+    vr_take_dpp<DPP_QUAD_XOR1>(best, idx);
+    vr_take_dpp<DPP_QUAD_XOR2>(best, idx);
+    vr_take_dpp<DPP_ROW_HALF_MIRROR>(best, idx);
+    vr_take_dpp<DPP_ROW_MIRROR>(best, idx);                   // every lane of a 16-lane row holds the row's pick
+    {
+        const int vb = __builtin_bit_cast(int, best);
+        float wv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 0));
+        int wi = __builtin_amdgcn_readlane(idx, 0);
+        vr_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 16)), __builtin_amdgcn_readlane(idx, 16));
+        vr_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 32)), __builtin_amdgcn_readlane(idx, 32));
+        vr_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 48)), __builtin_amdgcn_readlane(idx, 48));
+        if ((tid & 63) == 0) { bv[tid >> 6] = wv; bi[tid >> 6] = wi; }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float v = bv[0];
+        int i = bi[0];
+        for (int w = 1; w < (nt >> 6); w++) vr_take(v, i, bv[w], bi[w]);
+        pick[r] = i == 0x7fffffff ? 0 : i;                    // (nothing taken: every entry a NaN)
+    }
+}
+
+// pick == null: one row whose pick is pick_imm (a single-token step of the caller's loop, appended to the same log).
+// restart_pos >= 0: the log starts over -- position restart_pos, cursor 0 -- before this step is appended.
+// log_cap: entries the log holds; an append that would pass it is dropped (the host refuses such a call before it is launched).
+__global__ void __launch_bounds__(64)
+k_accept_drafts(const int32_t *__restrict__ tokens, const int32_t *__restrict__ pick, int pick_imm, int N, int restart_pos,
+                int32_t *__restrict__ log, int log_cap, int32_t *__restrict__ state, int32_t *__restrict__ res) {
+    const int lane = threadIdx.x;
+    const int p = !pick ? pick_imm : lane < N ? pick[lane] : 0;
+    // lane j < N - 1: row j's pick is the draft's next token; the first lane where that fails (or N - 1) is n_accept
+    const bool agree = lane < N - 1 && p == tokens[lane + 1];
+    const unsigned long long miss = ~__ballot(agree);
+    const int n_accept = min((int) __builtin_ctzll(miss), N - 1);
+    const int pos = restart_pos >= 0 ? restart_pos : state[0], cur = restart_pos >= 0 ? 0 : state[1];
+    if (lane <= n_accept && cur >= 0 && cur + lane < log_cap) log[cur + lane] = p;
+    if (lane < N) res[1 + lane] = p;
+    if (lane == 0) {
+        res[0] = n_accept;
+        state[0] = pos + n_accept + 1;
+        state[1] = cur + n_accept + 1;
+    }
+}
+
+hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st) {
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || V < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_verify_rows, dim3((unsigned) n_rows), dim3(1024), 0, st, logits, V, pick);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int pick_imm, int n_rows, int restart_pos, int32_t *log, int log_cap,
+                                int32_t *state, int32_t *res, hipStream_t st) {
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || !log || !state || !res || (!pick && n_rows != 1) || (n_rows > 1 && !tokens)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_accept_drafts, dim3(1), dim3(64), 0, st, tokens, pick, pick_imm, n_rows, restart_pos, log, log_cap, state, res);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+}  // namespace lh
