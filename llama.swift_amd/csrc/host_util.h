@@ -1,0 +1,82 @@
+// host_util.h -- what the host translation units (llamahip.cpp, ops.cpp, quantize.cpp) share: the error text, HIP error handling, the
+// host-built tables, and the owning scratch of a single-op call.  Host .cpp files only: no .hip kernel file includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/llamahip.h"
+
+namespace lh {
+
+void set_err(char *err, size_t cap, const char *fmt, ...) __attribute__((format(printf, 3, 4)));      // llamahip.cpp
+
+#define HIP_TRY(expr, code)                                                                          \
+    do {                                                                                             \
+        hipError_t e_ = (expr);                                                                      \
+        if (e_ != hipSuccess) {                                                                      \
+            lh::set_err(err, err_cap, "HIP error: %s (%s) at %s:%d", hipGetErrorString(e_), #expr, __FILE__, __LINE__); \
+            return (code);                                                                           \
+        }                                                                                            \
+    } while (0)
+
+inline void free_dev(void *p) { if (p) (void) hipFree(p); }
+
+// there is no CPU fallback: 0 with a device, else LLAMAHIP_ERR_PREDICT and the message
+inline int need_device(char *err, size_t err_cap) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) == hipSuccess && ndev >= 1) return 0;
+    set_err(err, err_cap, "no HIP device available: libllamahip has no CPU fallback");
+    return LLAMAHIP_ERR_PREDICT;
+}
+
+// the silu and exp tables of ggml_init (ggml.c:2376-2389) and the RoPE angle table [n_ctx][dh/2][cos, sin] (ggml.c:7113-7116), host libm
+// (llamahip.cpp: a model load and llamahip_op_attention upload the same ones)
+void lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te);
+std::vector<double> rope_table(int n_ctx, int dh);
+
+// Device memory, a stream and events that live for ONE call.  The first HIP error sticks: after it alloc returns null and upload /
+// download / fill / sync do nothing, so a body reads top to bottom, guards its launches with `if (s.ok()) s.check(launch_...)` and
+// asks once at the end.  The destructor releases everything on every return path.
+struct Scratch {
+    std::vector<void *> bufs;
+    std::vector<hipEvent_t> events;
+    hipStream_t st = nullptr;
+    hipError_t e = hipSuccess;
+    Scratch() = default;
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch() {
+        for (void *p : bufs) (void) hipFree(p);
+        for (hipEvent_t ev : events) (void) hipEventDestroy(ev);
+        if (st) (void) hipStreamDestroy(st);
+    }
+    bool ok() const { return e == hipSuccess; }
+    hipError_t error() const { return e; }
+    void check(hipError_t r) { if (ok()) e = r; }
+    template <class T> T *alloc(size_t count, const T *init = nullptr) {      // init: uploaded at once
+        void *p = nullptr;
+        if (ok()) check(hipMalloc(&p, count * sizeof(T)));
+        if (!ok()) return nullptr;
+        bufs.push_back(p);
+        if (init) upload(p, init, count * sizeof(T));
+        return (T *) p;
+    }
+    // without a stream the copies and fills below are the synchronous ones on the null stream
+    hipStream_t stream() { if (ok() && !st) check(hipStreamCreate(&st)); return st; }
+    hipEvent_t event() { hipEvent_t ev = nullptr; if (ok()) check(hipEventCreate(&ev)); if (ev) events.push_back(ev); return ev; }
+    void upload(void *dst, const void *src, size_t bytes) { if (ok()) check(st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); }
+    void download(void *dst, const void *src, size_t bytes) { if (ok()) check(st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); }
+    void fill(void *dst, int byte, size_t bytes) { if (ok()) check(st ? hipMemsetAsync(dst, byte, bytes, st) : hipMemset(dst, byte, bytes)); }
+    void sync() { if (ok() && st) check(hipStreamSynchronize(st)); }
+    // the one exit of a body that failed: the message names the entry point; the runtime's sticky last error is cleared with it
+    int fail(const char *fn, char *err, size_t err_cap) const {
+        (void) hipGetLastError();
+        set_err(err, err_cap, "HIP error in %s: %s", fn, hipGetErrorString(e));
+        return LLAMAHIP_ERR_PREDICT;
+    }
+};
+
+}  // namespace lh

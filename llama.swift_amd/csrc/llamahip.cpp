@@ -20,6 +20,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_util.h"
 #include "llamahip_internal.h"
 #include "model_file.h"
 
@@ -28,10 +29,7 @@ using namespace lh;
 // ------------------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------------------
-namespace {
-
-void set_err(char *err, size_t cap, const char *fmt, ...) __attribute__((format(printf, 3, 4)));
-void set_err(char *err, size_t cap, const char *fmt, ...) {
+void lh::set_err(char *err, size_t cap, const char *fmt, ...) {
     if (!err || !cap) return;
     va_list ap;
     va_start(ap, fmt);
@@ -39,18 +37,11 @@ void set_err(char *err, size_t cap, const char *fmt, ...) {
     va_end(ap);
 }
 
+namespace {
+
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
-
-#define HIP_TRY(expr, code)                                                                          \
-    do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
-        if (e_ != hipSuccess) {                                                                      \
-            set_err(err, err_cap, "HIP error: %s (%s) at %s:%d", hipGetErrorString(e_), #expr, __FILE__, __LINE__); \
-            return (code);                                                                           \
-        }                                                                                            \
-    } while (0)
 
 struct Layer {
     float *attention_norm = nullptr, *ffn_norm = nullptr;   // fp32 [d]
@@ -113,6 +104,28 @@ float f16_to_f32(uint16_t h) {
 }
 
 }  // namespace
+
+// the silu and exp tables of ggml_init (ggml.c:2376-2389) and the RoPE angle table [n_ctx][dh/2][cos, sin] (ggml.c:7113-7116), host libm
+void lh::lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te) {
+    for (int i = 0; i < (1 << 16); i++) {
+        const float f = f16_to_f32((uint16_t) i);
+        ts[i] = f32_to_f16_rne((float) ((double) f / (1.0 + exp((double) -f))));
+        te[i] = f32_to_f16_rne((float) exp((double) f));
+    }
+}
+std::vector<double> lh::rope_table(int n_ctx, int dh) {
+    std::vector<double> sc((size_t) n_ctx * dh);
+    for (int p = 0; p < n_ctx; p++) {
+        for (int i0 = 0; i0 < dh; i0 += 2) {
+            const double theta = pow(10000.0, ((double) -i0) / dh);
+            double sn, cs;
+            sincos(p * theta, &sn, &cs);                  // the reference's -O3 build calls sincos()
+            sc[(size_t) p * dh + i0] = cs;
+            sc[(size_t) p * dh + i0 + 1] = sn;
+        }
+    }
+    return sc;
+}
 
 // ------------------------------------------------------------------------------------------------
 // the model handle
@@ -242,7 +255,6 @@ struct llamahip_model {
     ~llamahip_model();
 };
 
-static void free_dev(void *p) { if (p) (void) hipFree(p); }
 // A pipeline mailbox is polled by this GPU's kernels while ANOTHER GPU's kernel stores into it over xGMI.  Ordinary hipMalloc
 // memory is coarse-grained: the local L2 may keep serving a line it cached on an earlier look, and coherence with other agents is
 // only promised at kernel boundaries.  Uncached (else fine-grained) device memory is what in-kernel flags between GPUs need;
@@ -362,9 +374,7 @@ int alloc_dmat(DMat &q, int M, int K, llamahip_model *m, char *err, size_t err_c
 }
 
 int alloc_qmat(QMat &q, int M, int K, llamahip_model *m, char *err, size_t err_cap) {
-    q.M = M; q.K = K;
-    q.ngroups = (M + 7) / 8;
-    q.nchunks = (K + 255) / 256;
+    q.set_shape(M, K);
     HIP_TRY(hipMalloc((void **) &q.tiles, q.bytes()), LLAMAHIP_ERR_LOAD);
     m->weight_bytes += (int64_t) q.bytes();
     return 0;
@@ -391,12 +401,10 @@ int make_rows(QMat &q, llamahip_model *m) {
         m->weight_bytes += (int64_t) bytes;
         return true;
     };
-    q.nrb = (q.M + 63) / 64;
     if (!build(&q.rows, q.rows_bytes(), [&]() { return launch_tiles_to_rows(q, m->stream); })) return 1;
     // matrix-core tiles: one byte per weight in four-chain operand order for the exact path (k_gemm_mfma4); the int8 order only for a
     // handle opened with LLAMAHIP_FLAG_FAST_PREFILL (or LLAMAHIP_MFMA_I8=1: the round-1 exact kernel, for A/B) -- one of the two
     static const bool want_i8 = getenv("LLAMAHIP_MFMA_I8") != nullptr;
-    q.nrb32 = (q.M + 31) / 32;
     if ((m->flags & LLAMAHIP_FLAG_FAST_PREFILL) || want_i8) {
         if (!build(&q.mt, q.mt_bytes(), [&]() { return launch_tiles_to_mtiles(q, m->stream); })) return 1;
     } else if (!build(&q.mt4, q.mt4_bytes(), [&]() { return launch_tiles_to_mt4(q, m->stream); })) return 1;
@@ -490,41 +498,19 @@ int ensure_workspace(llamahip_model *m, int N, char *err, size_t err_cap) {
     return 0;
 }
 
-// the silu and exp tables of ggml_init (ggml.c:2376-2389) and the RoPE angle table [n_ctx][dh/2][cos, sin] (ggml.c:7113-7116), host libm
-static void lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te) {
-    for (int i = 0; i < (1 << 16); i++) {
-        const float f = f16_to_f32((uint16_t) i);
-        ts[i] = f32_to_f16_rne((float) ((double) f / (1.0 + exp((double) -f))));
-        te[i] = f32_to_f16_rne((float) exp((double) f));
-    }
-}
-static std::vector<double> rope_table(int n_ctx, int dh) {
-    std::vector<double> sc((size_t) n_ctx * dh);
-    for (int p = 0; p < n_ctx; p++) {
-        for (int i0 = 0; i0 < dh; i0 += 2) {
-            const double theta = pow(10000.0, ((double) -i0) / dh);
-            double sn, cs;
-            sincos(p * theta, &sn, &cs);                  // the reference's -O3 build calls sincos()
-            sc[(size_t) p * dh + i0] = cs;
-            sc[(size_t) p * dh + i0 + 1] = sn;
-        }
-    }
-    return sc;
-}
-
 // the score workspace of the multi-row prompt attention: [n_head][n_ctx][NB] fp32, NB = 512 query rows
 // (a 2 048-token 7B eval with NB = 256 / 512 / 1 024 / 2 048: 225.9 / 201.8 / 200.3 / 212.4 ms on one box in round 3, 183.3 / 161.6 / 162.6 / 175.9 in
 // round 4 (profiles/r04_v_attn_shapes_ab.txt) -- 512 keeps the workspace at a quarter and inside the Infinity Cache)
 // per batch (7B, n_ctx 2560: 168 MB), allocated with the first multi-token eval
 int ensure_attn_ws(llamahip_model *m, int N, char *err, size_t err_cap) {
     if (N < 2 || m->attn_ws.S) return 0;
-    const size_t H = m->hp.n_head, C = m->hp.n_ctx;
     AttnWs &w = m->attn_ws;
-    w.NB = 512; w.T_cap = (int) C; w.KS_cap = 32; w.nth_cap = 8;
-    HIP_TRY(hipMalloc((void **) &w.S, H * C * w.NB * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.pmax, H * w.KS_cap * w.NB * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.inv, H * w.NB * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.part, (size_t) w.nth_cap * H * w.NB * 128 * 4), LLAMAHIP_ERR_PREDICT);
+    attn_ws_shape(w, m->hp.n_ctx);
+    const AttnWsBytes b = attn_ws_bytes(w, m->hp.n_head);
+    HIP_TRY(hipMalloc((void **) &w.S, b.S), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMalloc((void **) &w.pmax, b.pmax), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMalloc((void **) &w.inv, b.inv), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMalloc((void **) &w.part, b.part), LLAMAHIP_ERR_PREDICT);
     return 0;
 }
 
@@ -2828,397 +2814,8 @@ int llamahip_get_stats(const llamahip_model *m, llamahip_stats *out) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// single-op entry points
+// the decode mat-vec on its own, timed (the single-op entry points llamahip_op_* are ops.cpp)
 // ------------------------------------------------------------------------------------------------
-static int need_device(char *err, size_t err_cap) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        set_err(err, err_cap, "no HIP device available: libllamahip has no CPU fallback");
-        return LLAMAHIP_ERR_PREDICT;
-    }
-    return 0;
-}
-
-int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N,
-                             float *y, char *err, size_t err_cap) {
-    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
-    if (!w_q4_0 || !x || !y || M < 1 || N < 1 || K < 64 || K % 64 != 0) { set_err(err, err_cap, "bad mul_mat arguments (K must be a positive multiple of 64)"); return LLAMAHIP_ERR_PREDICT; }
-    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
-    QMat q;
-    q.M = M; q.K = K; q.ngroups = (M + 7) / 8; q.nchunks = (K + 255) / 256;
-    const size_t wbytes = (size_t) M * (K / 32) * 20, Kp = (size_t) q.nchunks * 256;
-    uint8_t *d_w = nullptr; float *d_x = nullptr, *d_y = nullptr, *d_qd = nullptr; uint32_t *d_qA = nullptr;
-    hipStream_t st = nullptr;
-    int rc = LLAMAHIP_ERR_PREDICT;
-    do {
-        if (hipMalloc((void **) &d_w, wbytes) != hipSuccess) break;
-        if (hipMalloc((void **) &q.tiles, q.bytes()) != hipSuccess) break;
-        if (hipMalloc((void **) &d_x, (size_t) N * K * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_y, (size_t) N * M * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qA, (size_t) N * Kp) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qd, (size_t) N * (Kp / 32) * 4) != hipSuccess) break;
-        if (hipStreamCreate(&st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_w, w_q4_0, wbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_x, x, (size_t) N * K * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (launch_repack(d_w, q.tiles, M, K, 0, 0, st) != hipSuccess) break;
-        if (N >= 2) {          // the model path's prompt GEMM: row-lane copy
-            q.nrb = (M + 63) / 64;
-            if (hipMalloc((void **) &q.rows, q.rows_bytes()) != hipSuccess) break;
-            if (launch_tiles_to_rows(q, st) != hipSuccess) break;
-        }
-        if (launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st) != hipSuccess) break;
-        if (launch_gemm(q, EPI_STORE, d_qA, d_qd, N, d_y, M, nullptr, 0, st) != hipSuccess) break;
-        if (hipMemcpyAsync(y, d_y, (size_t) N * M * 4, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = LLAMAHIP_OK;
-    } while (0);
-    if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in llamahip_op_mul_mat_q4_0: %s", hipGetErrorString(hipGetLastError()));
-    if (st) (void) hipStreamDestroy(st);
-    free_dev(d_w); free_dev(q.tiles); free_dev(q.rows); free_dev(d_x); free_dev(d_y); free_dev(d_qA); free_dev(d_qd);
-    return rc;
-}
-
-// one prompt GEMM kernel on caller-supplied operands (per-op tests of every kernel launch_gemm can pick): see llamahip.h
-int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
-                                 float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {
-    if (!w_q4_0 || !x || !y || M < 1 || N < 1 || K < 64 || K % 64 != 0) {
-        set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: bad arguments (M %d, N %d >= 1; K %d must be a positive multiple of 64)", M, N, K); return LLAMAHIP_ERR_PREDICT;
-    }
-    if (y_stride < M) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: y_stride %d < M %d", y_stride, M); return LLAMAHIP_ERR_PREDICT; }
-    if (path < LLAMAHIP_GEMM_AUTO || path > LLAMAHIP_GEMM_LDS) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: unknown path %d", path); return LLAMAHIP_ERR_PREDICT; }
-    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
-    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
-    QMat q;
-    q.M = M; q.K = K; q.ngroups = (M + 7) / 8; q.nchunks = (K + 255) / 256;
-    q.nrb = (M + 63) / 64; q.nrb32 = (M + 31) / 32;
-    const size_t wbytes = (size_t) M * (K / 32) * 20, Kp = (size_t) q.nchunks * 256, ybytes = (size_t) N * y_stride * 4;
-    const bool auto_ = path == LLAMAHIP_GEMM_AUTO;
-    const bool want_rows = auto_ || path == LLAMAHIP_GEMM_ROWS, want_mt4 = auto_ || path == LLAMAHIP_GEMM_MFMA4;
-    const bool want_mt = path == LLAMAHIP_GEMM_MFMA_I8 || path == LLAMAHIP_GEMM_FAST;
-    uint8_t *d_w = nullptr, *d_qb = nullptr; float *d_x = nullptr, *d_y = nullptr, *d_r = nullptr, *d_qd = nullptr; uint32_t *d_qA = nullptr;
-    hipStream_t st = nullptr;
-    const char *why = nullptr;
-    long before[GEMM_PATH_COUNT];
-    int rc = LLAMAHIP_ERR_PREDICT;
-    do {
-        if (hipMalloc((void **) &d_w, wbytes) != hipSuccess) break;
-        if (hipMalloc((void **) &q.tiles, q.bytes()) != hipSuccess) break;
-        if (want_rows && hipMalloc((void **) &q.rows, q.rows_bytes()) != hipSuccess) break;
-        if (want_mt4 && hipMalloc((void **) &q.mt4, q.mt4_bytes()) != hipSuccess) break;
-        if (want_mt && hipMalloc((void **) &q.mt, q.mt_bytes()) != hipSuccess) break;
-        if (hipMalloc((void **) &d_x, (size_t) N * K * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_y, ybytes) != hipSuccess) break;
-        if (resid && hipMalloc((void **) &d_r, (size_t) N * M * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qA, (size_t) N * Kp) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qd, (size_t) N * (Kp / 32) * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qb, (size_t) N * Kp * 2) != hipSuccess) break;      // as the model's workspace: the fp16 (or int8) operand
-        if (hipStreamCreate(&st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_w, w_q4_0, wbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_x, x, (size_t) N * K * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_y, y, ybytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (resid && hipMemcpyAsync(d_r, resid, (size_t) N * M * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (launch_repack(d_w, q.tiles, M, K, 0, 0, st) != hipSuccess) break;
-        if (want_rows && launch_tiles_to_rows(q, st) != hipSuccess) break;
-        if (want_mt4 && launch_tiles_to_mt4(q, st) != hipSuccess) break;
-        if (want_mt && launch_tiles_to_mtiles(q, st) != hipSuccess) break;
-        if (launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st) != hipSuccess) break;
-        const int epi = resid ? EPI_RESID : EPI_STORE;
-        for (int i = 0; i < GEMM_PATH_COUNT; i++) before[i] = g_gemm_path_counts[i];
-        const hipError_t e = auto_ ? launch_gemm(q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, false)
-                                   : launch_gemm_forced(path, q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, &why);
-        if (e != hipSuccess) break;
-        if (hipMemcpyAsync(y, d_y, ybytes, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        rc = LLAMAHIP_OK;
-    } while (0);
-    if (why) set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: path %d refused for M %d, K %d, N %d: %s", path, M, K, N, why);
-    else if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in llamahip_op_prompt_gemm_q4_0: %s", hipGetErrorString(hipGetLastError()));
-    if (st) (void) hipStreamDestroy(st);
-    free_dev(d_w); free_dev(q.tiles); free_dev(q.rows); free_dev(q.mt4); free_dev(q.mt); free_dev(d_x); free_dev(d_y); free_dev(d_r);
-    free_dev(d_qA); free_dev(d_qd); free_dev(d_qb);
-    if (rc == LLAMAHIP_OK && path_taken) {
-        // the kernel family whose count moved (the matrix-core count moves with the fast one; this handle has ONE matrix-core copy)
-        auto moved = [&](int i) { return g_gemm_path_counts[i] != before[i]; };
-        *path_taken = moved(GEMM_PATH_FAST) ? LLAMAHIP_GEMM_FAST : moved(GEMM_PATH_MFMA) ? (want_mt4 ? LLAMAHIP_GEMM_MFMA4 : LLAMAHIP_GEMM_MFMA_I8)
-                    : moved(GEMM_PATH_ROWS) ? LLAMAHIP_GEMM_ROWS : moved(GEMM_PATH_SET) ? LLAMAHIP_GEMM_SET
-                    : moved(GEMM_PATH_LDS) ? LLAMAHIP_GEMM_LDS : LLAMAHIP_GEMM_GEMV;
-    }
-    return rc;
-}
-
-// one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
-int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
-                          int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
-                          void *wo_operand, int32_t *path_taken, char *err, size_t err_cap) {
-    const char *fn = "llamahip_op_attention";
-    if (!qkv || !Kc || !Vc || N < 1 || d < 1 || H < 1 || d % H != 0 || n_past < 0 || chunk < 0) {
-        set_err(err, err_cap, "%s: bad arguments (N %d >= 1, d %d a multiple of H %d, n_past %d >= 0, chunk %d >= 0)", fn, N, d, H, n_past, chunk);
-        return LLAMAHIP_ERR_PREDICT;
-    }
-    const int dh = d / H, T = n_past + N, nth = n_threads;
-    if (T > n_ctx) { set_err(err, err_cap, "%s: T = n_past + N = %d > n_ctx %d", fn, T, n_ctx); return LLAMAHIP_ERR_PREDICT; }
-    if (merged && merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
-    if (ws_rows < 0 || ws_rows % 64 != 0) { set_err(err, err_cap, "%s: ws_rows %d must be a positive multiple of 64 (0: 512)", fn, ws_rows); return LLAMAHIP_ERR_PREDICT; }
-    if (nth < 1 || nth > 64) { set_err(err, err_cap, "%s: n_threads %d outside 1 .. 64 (the model's clamp)", fn, nth); return LLAMAHIP_ERR_PREDICT; }
-    if (path < LLAMAHIP_ATTN_AUTO || path > LLAMAHIP_ATTN_DEC_STREAM) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
-    if (d % 32 != 0) { set_err(err, err_cap, "%s: d %d must be a multiple of 32 (Q4_0 blocks of the wo operand)", fn, d); return LLAMAHIP_ERR_PREDICT; }
-    AttnWs ws;                                       // as ensure_attn_ws, NB = ws_rows
-    ws.NB = ws_rows ? ws_rows : 512; ws.T_cap = n_ctx; ws.KS_cap = 32; ws.nth_cap = 8;
-    int run = path;
-    if (path == LLAMAHIP_ATTN_AUTO) run = N >= 2 ? attn_path_pick(&ws, N, dh, T, nth) : -1;
-    const char *why = nullptr;
-    const bool dh_ok = dh % 32 == 0 && dh <= 256;
-    switch (run) {
-    case -1: why = "AUTO takes N >= 2 (one row is the decode step: paths DEC / DEC_STREAM)"; break;
-    case LLAMAHIP_ATTN_MFMA: if (!attn_mfma_applies(&ws, N, dh, T, nth)) why = "MFMA takes N >= 2, head size 128 and n_threads <= 8"; break;
-    case LLAMAHIP_ATTN_ROW: if (!dh_ok) why = "ROW takes head sizes that are multiples of 32 up to 256"; break;
-    case LLAMAHIP_ATTN_SHORT: if (!attn_short_applies(&ws, N, dh)) why = "SHORT takes 2 <= N <= 60 and head sizes that are multiples of 32 up to 256"; break;
-    case LLAMAHIP_ATTN_DEC: if (N != 1 || !dh_ok) why = "DEC takes N = 1 and head sizes that are multiples of 32 up to 256"; break;
-    case LLAMAHIP_ATTN_DEC_STREAM:
-        if (N != 1 || !dh_ok || !pv_stream_applies(dh, n_ctx, nth)) why = "DEC_STREAM takes N = 1, head sizes that are multiples of 32 up to 256, n_threads <= 32 and n_ctx <= 4096";
-        break;
-    }
-    if (why) { set_err(err, err_cap, "%s: path %d refused for N %d, head size %d, n_threads %d: %s", fn, path, N, dh, nth, why); return LLAMAHIP_ERR_PREDICT; }
-    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
-    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
-    const bool dec = run == LLAMAHIP_ATTN_DEC || run == LLAMAHIP_ATTN_DEC_STREAM, quant = dec || run == LLAMAHIP_ATTN_SHORT;
-    const int Kp = (d + 255) / 256 * 256;
-    const size_t cache_b = (size_t) n_ctx * d * 4, ms = merged ? (size_t) merged_stride : (size_t) d, mbytes = (size_t) N * ms * 4;
-    const size_t qaA_b = (size_t) N * Kp, qad_b = (size_t) N * (Kp / 32) * 4;
-    const size_t S_b = (size_t) H * n_ctx * ws.NB * 4, pmax_b = (size_t) H * ws.KS_cap * ws.NB * 4, inv_b = (size_t) H * ws.NB * 4;
-    const size_t part_b = (size_t) ws.nth_cap * H * ws.NB * 128 * 4;
-    float *d_qkv = nullptr, *d_K = nullptr, *d_V = nullptr, *d_qr = nullptr, *d_m = nullptr, *d_qad = nullptr;
-    uint32_t *d_qaA = nullptr; uint16_t *d_ts = nullptr, *d_te = nullptr; double *d_tab = nullptr; int32_t *d_state = nullptr;
-    hipStream_t st = nullptr;
-    int rc = LLAMAHIP_ERR_PREDICT;
-    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
-    lut_tables(ts, te);
-    const std::vector<double> tab = rope_table(n_ctx, dh);
-    const int32_t hs[2] = { n_past, 0 };
-    do {
-        if (hipStreamCreate(&st) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qkv, (size_t) N * 3 * d * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_K, cache_b) != hipSuccess || hipMalloc((void **) &d_V, cache_b) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qr, (size_t) N * d * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_m, mbytes) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qaA, qaA_b) != hipSuccess || hipMalloc((void **) &d_qad, qad_b) != hipSuccess) break;
-        if (hipMalloc((void **) &d_ts, 1 << 17) != hipSuccess || hipMalloc((void **) &d_te, 1 << 17) != hipSuccess) break;
-        if (hipMalloc((void **) &d_tab, tab.size() * 8) != hipSuccess || hipMalloc((void **) &d_state, 8) != hipSuccess) break;
-        // the op's own workspace, every byte NaN (0xFF): a read of something the launch did not write shows in the result
-        if (hipMalloc((void **) &ws.S, S_b) != hipSuccess || hipMalloc((void **) &ws.pmax, pmax_b) != hipSuccess) break;
-        if (hipMalloc((void **) &ws.inv, inv_b) != hipSuccess || hipMalloc((void **) &ws.part, part_b) != hipSuccess) break;
-        if (hipMemsetAsync(ws.S, 0xFF, S_b, st) != hipSuccess || hipMemsetAsync(ws.pmax, 0xFF, pmax_b, st) != hipSuccess) break;
-        if (hipMemsetAsync(ws.inv, 0xFF, inv_b, st) != hipSuccess || hipMemsetAsync(ws.part, 0xFF, part_b, st) != hipSuccess) break;
-        if (hipMemsetAsync(d_qr, 0xFF, (size_t) N * d * 4, st) != hipSuccess) break;
-        if (hipMemsetAsync(d_qaA, 0xFF, qaA_b, st) != hipSuccess || hipMemsetAsync(d_qad, 0xFF, qad_b, st) != hipSuccess) break;
-        if (!merged && hipMemsetAsync(d_m, 0xFF, mbytes, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_qkv, qkv, (size_t) N * 3 * d * 4, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_K, Kc, cache_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_V, Vc, cache_b, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (merged && hipMemcpyAsync(d_m, merged, mbytes, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_ts, ts.data(), 1 << 17, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_te, te.data(), 1 << 17, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_tab, tab.data(), tab.size() * 8, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (hipMemcpyAsync(d_state, hs, 8, hipMemcpyHostToDevice, st) != hipSuccess) break;
-        if (launch_check_lut_math(d_ts, d_te, st) != hipSuccess) break;          // g_lut_math, as a model load leaves it
-        float *mo = merged ? d_m : nullptr;
-        hipError_t e = hipSuccess;
-        if (dec) {
-            e = launch_dec_attn(d_qkv, d, H, n_ctx, nth, d_tab, d_K, d_V, ws.S, nullptr, mo, d_qaA, d_qad, d_te, d_state, st,
-                                nullptr, nullptr, run == LLAMAHIP_ATTN_DEC_STREAM);
-        } else {
-            e = launch_rope_kv(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, n_past, N, st);
-            if (e == hipSuccess) {
-                if (run == LLAMAHIP_ATTN_SHORT)
-                    e = launch_attn_short(d_qr, d_K, d_V, ws.S, mo, d_qaA, d_qad, n_past, N, d, H, n_ctx, nth, d_te, st, chunk, nullptr, 0, (long) ms);
-                else
-                    e = launch_attn(d_qr, d_K, d_V, d_m, nullptr, nullptr, n_past, N, d, H, nth, d_te, run == LLAMAHIP_ATTN_MFMA ? &ws : nullptr, st, chunk, (long) ms);
-            }
-        }
-        if (e != hipSuccess) break;
-        if (hipMemcpyAsync(Kc, d_K, cache_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (hipMemcpyAsync(Vc, d_V, cache_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        if (merged && hipMemcpyAsync(merged, d_m, mbytes, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        std::vector<uint32_t> qa(qaA_b / 4);
-        std::vector<float> qd(qad_b / 4);
-        if (quant && wo_operand) {
-            if (hipMemcpyAsync(qa.data(), d_qaA, qaA_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-            if (hipMemcpyAsync(qd.data(), d_qad, qad_b, hipMemcpyDeviceToHost, st) != hipSuccess) break;
-        }
-        if (hipStreamSynchronize(st) != hipSuccess) break;
-        if (quant && wo_operand) {
-            // QA layout (kcommon.hip.h quantize_y) -> Q4_0 blocks in file layout: {d, qs[16]}, qs[k] = (q[2k] + 8) | (q[2k+1] + 8) << 4
-            // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
-            uint8_t *o = (uint8_t *) wo_operand;
-            for (int n = 0; n < N; n++)
-                for (int b = 0; b < d / 32; b++) {
-                    const uint32_t *A = qa.data() + (size_t) n * (Kp / 4);
-                    uint8_t *blk = o + ((size_t) n * (d / 32) + b) * 20;
-                    memcpy(blk, &qd[(size_t) n * (Kp / 32) + b], 4);
-                    const int c = b >> 3, j = b & 7;
-                    for (int k = 0; k < 8; k++) {
-                        const uint32_t w = A[(c * 8 + k) * 8 + j] >> (4 * (j & 1));
-                        const uint32_t q0 = (w & 0xF) ^ 8, q1 = ((w >> 8) & 0xF) ^ 8, q2 = ((w >> 16) & 0xF) ^ 8, q3 = ((w >> 24) & 0xF) ^ 8;
-                        blk[4 + k] = (uint8_t) (q0 | (q1 << 4));
-                        blk[12 + k] = (uint8_t) (q2 | (q3 << 4));
-                    }
-                }
-        }
-        rc = LLAMAHIP_OK;
-    } while (0);
-    if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in %s: %s", fn, hipGetErrorString(hipGetLastError()));
-    if (st) (void) hipStreamDestroy(st);
-    free_dev(d_qkv); free_dev(d_K); free_dev(d_V); free_dev(d_qr); free_dev(d_m); free_dev(d_qaA); free_dev(d_qad);
-    free_dev(d_ts); free_dev(d_te); free_dev(d_tab); free_dev(d_state);
-    free_dev(ws.S); free_dev(ws.pmax); free_dev(ws.inv); free_dev(ws.part);
-    if (rc == LLAMAHIP_OK && path_taken) *path_taken = run;
-    return rc;
-}
-
-// host-only: the attention path a model's multi-row eval of N rows after n_past takes once its workspace exists (ensure_attn_ws)
-int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx) {
-    AttnWs ws;
-    ws.NB = 512; ws.T_cap = n_ctx; ws.KS_cap = 32; ws.nth_cap = 8;
-    if (N < 2) return -1;
-    return attn_path_pick(&ws, N, head_size, n_past + N, std::max(1, std::min((int) n_threads, 64)));
-}
-
-// the device half of the sampler on caller-supplied logits (parity tests): see llamahip_eval_topk
-int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
-                     int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap) {
-    int rc = need_device(err, err_cap);
-    if (rc) return rc;
-    if (!logits || !cand_scores || !cand_ids || !exact || n_vocab < 1 || n_vocab > 32768 || top_k < 1 || top_k > 64 || top_k > n_vocab || n_last < 0 || n_last > 1024) {
-        set_err(err, err_cap, "llamahip_op_topk: bad arguments"); return LLAMAHIP_ERR_PREDICT;
-    }
-    float *d_l = nullptr; void *d_w = nullptr;
-    HIP_TRY(hipMalloc((void **) &d_l, (size_t) n_vocab * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc(&d_w, 8192 + TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-    if (hipMemset(d_w, 0, 8192 + TOPK_WS_BYTES) != hipSuccess) { (void) hipFree(d_l); (void) hipFree(d_w); set_err(err, err_cap, "llamahip_op_topk: memset failed"); return LLAMAHIP_ERR_PREDICT; }
-    int32_t *d_win = (int32_t *) d_w; double *d_sc = (double *) ((char *) d_w + 4096); int32_t *d_id = (int32_t *) ((char *) d_w + 4096 + 512), *d_fl = d_id + 64;
-    struct { double sc[64]; int32_t id[64]; int32_t fl[2]; } h;
-    hipError_t e = hipMemcpy(d_l, logits, (size_t) n_vocab * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && n_last > 0) e = hipMemcpy(d_win, last_n_tokens, (size_t) n_last * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_topk_candidates(d_l, n_vocab, d_win, n_last, 1.0 / temp, repeat_penalty, top_k, d_sc, d_id, d_fl, nullptr, (char *) d_w + 8192);
-    if (e == hipSuccess) e = hipMemcpy(&h, d_sc, sizeof(h), hipMemcpyDeviceToHost);
-    (void) hipFree(d_l); (void) hipFree(d_w);
-    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
-    *exact = h.fl[0];
-    for (int i = 0; i < top_k; i++) { cand_scores[i] = h.sc[i]; cand_ids[i] = h.id[i]; }
-    return LLAMAHIP_OK;
-}
-
-// the batched device half of the sampler on caller-supplied rows (parity tests): see llamahip_decode_sample_multi
-int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *windows, const int32_t *n_last, double repeat_penalty,
-                          int32_t top_k, double temp, double *out_scores, int32_t *out_ids, int32_t *out_exact, float *out_spill, char *err, size_t err_cap) {
-    if (!logits || !windows || !n_last || !out_scores || !out_ids || !out_exact || n_rows < 1 || n_vocab < 1 || n_vocab > 32768 || top_k < 1 || top_k > 64 || top_k > n_vocab) {
-        set_err(err, err_cap, "llamahip_op_topk_rows: bad arguments (n_rows %d, n_vocab %d <= 32768, top_k %d in [1, min(64, n_vocab)])", n_rows, n_vocab, top_k); return LLAMAHIP_ERR_PREDICT;
-    }
-    for (int r = 0; r < n_rows; r++)
-        if (n_last[r] < 0) { set_err(err, err_cap, "llamahip_op_topk_rows: n_last[%d] = %d", r, n_last[r]); return LLAMAHIP_ERR_PREDICT; }
-    int rc = need_device(err, err_cap);
-    if (rc) return rc;
-    const size_t R = n_rows, V = n_vocab;
-    float *d_l = nullptr, *d_sp = nullptr; int32_t *d_win = nullptr; void *d_ws = nullptr; TopkOut *d_out = nullptr;
-    std::vector<TopkOut> h(R);
-    hipError_t e = hipMalloc((void **) &d_l, R * V * 4);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_win, R * 1024 * 4 + R * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_ws, R * TOPK_WS_BYTES);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_out, R * sizeof(TopkOut));
-    if (e == hipSuccess && out_spill) e = hipMalloc((void **) &d_sp, R * V * 4);
-    if (e == hipSuccess) e = hipMemset(d_ws, 0, R * TOPK_WS_BYTES);
-    if (e == hipSuccess) e = hipMemcpy(d_l, logits, R * V * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_win, windows, R * 1024 * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_win + R * 1024, n_last, R * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess && out_spill) e = hipMemcpy(d_sp, out_spill, R * V * 4, hipMemcpyHostToDevice);      // (rows that are not spilled keep the caller's bits)
-    if (e == hipSuccess) e = launch_topk_rows(d_l, n_rows, n_vocab, d_win, d_win + R * 1024, 1.0 / temp, repeat_penalty, top_k, d_out, d_sp, nullptr, d_ws);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_out, R * sizeof(TopkOut), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && out_spill) e = hipMemcpy(out_spill, d_sp, R * V * 4, hipMemcpyDeviceToHost);
-    free_dev(d_l); free_dev(d_win); free_dev(d_ws); free_dev(d_out); free_dev(d_sp);
-    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
-    for (size_t r = 0; r < R; r++) {
-        out_exact[r] = h[r].fl[0];
-        for (int i = 0; i < top_k; i++) { out_scores[r * 64 + i] = h[r].sc[i]; out_ids[r * 64 + i] = h[r].id[i]; }
-    }
-    return LLAMAHIP_OK;
-}
-
-// k_row_logprob on caller-supplied rows (parity tests): see llamahip_eval_logprobs
-int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
-                        double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap) {
-    if (!logits || n_rows < 1 || n_vocab < 1) { set_err(err, err_cap, "llamahip_op_logprob: bad arguments (n_rows %d, n_vocab %d)", n_rows, n_vocab); return LLAMAHIP_ERR_PREDICT; }
-    if (targets)
-        for (int i = 0; i < n_rows; i++)
-            if (targets[i] < -1 || targets[i] >= n_vocab) { set_err(err, err_cap, "llamahip_op_logprob: target %d of row %d out of range [-1, %d)", targets[i], i, n_vocab); return LLAMAHIP_ERR_PREDICT; }
-    int rc = need_device(err, err_cap);
-    if (rc) return rc;
-    const size_t N = (size_t) n_rows, row_bytes = (size_t) n_vocab * 4;
-    float *d_l = nullptr; char *d_s = nullptr;
-    std::vector<char> h(N * 16);
-    hipError_t e = hipMalloc((void **) &d_l, N * row_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_s, N * 20);
-    int32_t *d_t = d_s ? (int32_t *) (d_s + 16 * N) : nullptr;
-    if (e == hipSuccess) e = hipMemcpy(d_l, logits, N * row_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = targets ? hipMemcpy(d_t, targets, N * 4, hipMemcpyHostToDevice) : hipMemset(d_t, 0xFF, N * 4);      // (0xFFFFFFFF = -1)
-    if (e == hipSuccess) e = launch_row_logprob(d_l, n_rows, n_vocab, d_t, (double *) d_s, (int32_t *) (d_s + 8 * N), (int32_t *) (d_s + 12 * N), nullptr);
-    if (e == hipSuccess) e = hipMemcpy(h.data(), d_s, N * 16, hipMemcpyDeviceToHost);
-    free_dev(d_l); free_dev(d_s);
-    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
-    if (logprob_out) memcpy(logprob_out, h.data(), N * 8);
-    if (argmax_out) memcpy(argmax_out, h.data() + N * 8, N * 4);
-    if (rank_out) memcpy(rank_out, h.data() + N * 12, N * 4);
-    return LLAMAHIP_OK;
-}
-
-// k_verify_rows + k_accept_drafts on caller-supplied rows (parity tests): see llamahip_verify_greedy
-int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
-                            int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
-    if (!logits || !tokens || n_rows < 1 || n_rows > VERIFY_ROWS_MAX || n_vocab < 1) {
-        set_err(err, err_cap, "llamahip_op_verify_rows: bad arguments (n_rows %d of 1 .. %d, n_vocab %d)", n_rows, VERIFY_ROWS_MAX, n_vocab);
-        return LLAMAHIP_ERR_PREDICT;
-    }
-    int rc = need_device(err, err_cap);
-    if (rc) return rc;
-    const size_t N = (size_t) n_rows, row_bytes = (size_t) n_vocab * 4;
-    float *d_l = nullptr; int32_t *d_v = nullptr;      // d_v: {position, cursor} | tokens | picks | result | from [64]: a log of 16 entries
-    int32_t h[VERIFY_ROWS_MAX + 1] = { 0 };
-    hipError_t e = hipMalloc((void **) &d_l, N * row_bytes);
-    if (e == hipSuccess) e = hipMalloc((void **) &d_v, 80 * 4);
-    if (e == hipSuccess) e = hipMemset(d_v, 0, 80 * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_l, logits, N * row_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_v + 2, tokens, N * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = launch_verify_rows(d_l, n_rows, n_vocab, d_v + 18, nullptr);
-    if (e == hipSuccess) e = launch_accept_drafts(d_v + 2, d_v + 18, 0, n_rows, 0, d_v + 64, VERIFY_ROWS_MAX, d_v, d_v + 34, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(h, d_v + 34, (N + 1) * 4, hipMemcpyDeviceToHost);
-    free_dev(d_l); free_dev(d_v);
-    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
-    if (n_accept) *n_accept = h[0];
-    if (picks) memcpy(picks, h + 1, N * 4);
-    return LLAMAHIP_OK;
-}
-
-int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap) {
-    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
-    if (!x || !y || k < 32 || k % 32 != 0) { set_err(err, err_cap, "bad quantize arguments"); return LLAMAHIP_ERR_PREDICT; }
-    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
-    const size_t Kp = ((size_t) k + 255) / 256 * 256;
-    float *d_x = nullptr, *d_qd = nullptr; uint32_t *d_qA = nullptr; uint8_t *d_raw = nullptr;
-    int rc = LLAMAHIP_ERR_PREDICT;
-    do {
-        if (hipMalloc((void **) &d_x, (size_t) k * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qA, Kp) != hipSuccess) break;
-        if (hipMalloc((void **) &d_qd, (Kp / 32) * 4) != hipSuccess) break;
-        if (hipMalloc((void **) &d_raw, (size_t) (k / 32) * 20) != hipSuccess) break;
-        if (hipMemcpy(d_x, x, (size_t) k * 4, hipMemcpyHostToDevice) != hipSuccess) break;
-        if (launch_prep(PREP_PLAIN, d_x, nullptr, k, 0, k, 1, d_qA, d_qd, nullptr, d_raw, nullptr, nullptr) != hipSuccess) break;
-        if (hipMemcpy(y, d_raw, (size_t) (k / 32) * 20, hipMemcpyDeviceToHost) != hipSuccess) break;
-        rc = LLAMAHIP_OK;
-    } while (0);
-    if (rc != LLAMAHIP_OK) set_err(err, err_cap, "HIP error in llamahip_op_quantize_row_q4_0: %s", hipGetErrorString(hipGetLastError()));
-    free_dev(d_x); free_dev(d_qA); free_dev(d_qd); free_dev(d_raw);
-    return rc;
-}
-
 int llamahip_bench_gemv(llamahip_model *m, int32_t which, int32_t layer, int32_t warmup, int32_t iters,
                         llamahip_gemv_bench *out, char *err, size_t err_cap) {
     if (!m || m->host_only || !out || iters < 1) { set_err(err, err_cap, "bad bench arguments"); return LLAMAHIP_ERR_PREDICT; }
@@ -3260,9 +2857,9 @@ int llamahip_bench_gemv(llamahip_model *m, int32_t which, int32_t layer, int32_t
         default: return launch_gemv(*w, PRE_QA, EPI_STORE, m->qa_A, m->qa_d, nullptr, nullptr, yout, nullptr, m->T_silu, nullptr, nullptr, m->stream);
         }
     };
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipEventCreate(&e1), LLAMAHIP_ERR_PREDICT);
+    Scratch ev;              // destroys the events on every return
+    const hipEvent_t e0 = ev.event(), e1 = ev.event();
+    if (!ev.ok()) return ev.fail("llamahip_bench_gemv", err, err_cap);
     float ms_total = 0;
     int launches = 0;
     if (which == 4 && !m->layers.empty()) {
@@ -3292,7 +2889,6 @@ int llamahip_bench_gemv(llamahip_model *m, int32_t which, int32_t layer, int32_t
         HIP_TRY(hipEventElapsedTime(&ms_total, e0, e1), LLAMAHIP_ERR_PREDICT);
         launches = iters * (int) mats.size();
     }
-    (void) hipEventDestroy(e0); (void) hipEventDestroy(e1);
     out->M = q->M; out->K = q->K; out->iters = launches; out->ms_total = ms_total;
     out->algo_bytes = (double) q->M * (q->K / 32) * 20 + (double) (q->K / 32) * 20 + 4.0 * q->M;
     return LLAMAHIP_OK;

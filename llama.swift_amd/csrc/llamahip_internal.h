@@ -52,6 +52,8 @@ struct QMat {
     uint8_t *mt = nullptr;      // int8 operand order (the opt-in fast path and LLAMAHIP_MFMA_I8)
     uint8_t *mt4 = nullptr;     // one byte per weight, four-chain operand order (k_gemm_mfma4: the exact path): nrb32 * (2 * nchunks) * 4608 B
     int nrb32 = 0;              // ceil(M / 32)
+    // the tile geometry of an M x K matrix, every copy's (the one place that derives it)
+    void set_shape(int m, int k) { M = m; K = k; ngroups = (M + 7) / 8; nchunks = (K + 255) / 256; nrb = (M + 63) / 64; nrb32 = (M + 31) / 32; }
     size_t mt_bytes() const { return (size_t) nrb32 * nchunks * 2 * 2560; }
     size_t mt4_bytes() const { return (size_t) nrb32 * nchunks * 2 * MT4_TILE_BYTES; }
     size_t rows_bytes() const { return (size_t) nrb * (nchunks + 1) * 10240; }
@@ -162,9 +164,17 @@ struct AttnWs {
     float *S = nullptr, *pmax = nullptr, *inv = nullptr, *part = nullptr;   // part: [nth_cap][H][NB][128]
     int NB = 0;        // query rows per batch (multiple of 64)
     int T_cap = 0;     // keys the workspace can hold
-    int KS_cap = 32;   // key slices of the score pass
-    int nth_cap = 8;   // chunks of the V*P key split the workspace can hold (larger n_threads: per-row kernel)
+    int KS_cap = 0;    // key slices of the score pass
+    int nth_cap = 0;   // chunks of the V*P key split the workspace can hold (larger n_threads: per-row kernel)
 };
+// the one shape of that workspace, the model's and llamahip_op_attention's: n_ctx keys, NB query rows per batch (0: the model's 512) ...
+inline void attn_ws_shape(AttnWs &w, int n_ctx, int NB = 0) { w.NB = NB ? NB : 512; w.T_cap = n_ctx; w.KS_cap = 32; w.nth_cap = 8; }
+// ... and the bytes of its four buffers for H heads
+struct AttnWsBytes { size_t S, pmax, inv, part; };
+inline AttnWsBytes attn_ws_bytes(const AttnWs &w, int H) {
+    const size_t h = (size_t) H;
+    return { h * w.T_cap * w.NB * 4, h * w.KS_cap * w.NB * 4, h * w.NB * 4, (size_t) w.nth_cap * h * w.NB * 128 * 4 };
+}
 hipError_t launch_attn(const float *qr, const float *Kc, const float *Vc, float *merged, float *dbg_p, float *dbg_kqv,
                        int n_past, int N, int d, int H, int nth, const uint16_t *T_exp, const AttnWs *ws, hipStream_t st,
                        int chunk = 0,        // chunk > 0: the pass stands for successive evals of `chunk` rows (prompt_attn.hip split_keys)

@@ -1,0 +1,326 @@
+// ops.cpp -- the single-op entry points of include/llamahip.h (llamahip_op_*, llamahip_debug_attn_path): one or two kernel families on
+// caller-supplied operands, for the per-op tests.  None of them touches a model handle: each uploads its operands into a Scratch
+// (host_util.h), launches, copies back; the Scratch frees the device memory and the stream on every return.  No CPU fallback.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "host_util.h"
+#include "llamahip_internal.h"
+
+using namespace lh;
+
+extern "C" {
+
+int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N,
+                             float *y, char *err, size_t err_cap) {
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!w_q4_0 || !x || !y || M < 1 || N < 1 || K < 64 || K % 64 != 0) { set_err(err, err_cap, "bad mul_mat arguments (K must be a positive multiple of 64)"); return LLAMAHIP_ERR_PREDICT; }
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    QMat q;
+    q.set_shape(M, K);
+    const size_t wbytes = (size_t) M * (K / 32) * 20, Kp = (size_t) q.Kp();
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_w = s.alloc(wbytes, (const uint8_t *) w_q4_0);
+    float *d_x = s.alloc((size_t) N * K, x), *d_y = s.alloc<float>((size_t) N * M);
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    uint32_t *d_qA = s.alloc<uint32_t>((size_t) N * Kp / 4);
+    float *d_qd = s.alloc<float>((size_t) N * (Kp / 32));
+    if (s.ok()) s.check(launch_repack(d_w, q.tiles, M, K, 0, 0, st));
+    if (N >= 2) {          // the model path's prompt GEMM: row-lane copy
+        q.rows = s.alloc<uint8_t>(q.rows_bytes());
+        if (s.ok()) s.check(launch_tiles_to_rows(q, st));
+    }
+    if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+    if (s.ok()) s.check(launch_gemm(q, EPI_STORE, d_qA, d_qd, N, d_y, M, nullptr, 0, st));
+    s.download(y, d_y, (size_t) N * M * 4);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail("llamahip_op_mul_mat_q4_0", err, err_cap);
+}
+
+// one prompt GEMM kernel on caller-supplied operands (per-op tests of every kernel launch_gemm can pick): see llamahip.h
+int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {
+    if (!w_q4_0 || !x || !y || M < 1 || N < 1 || K < 64 || K % 64 != 0) {
+        set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: bad arguments (M %d, N %d >= 1; K %d must be a positive multiple of 64)", M, N, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (y_stride < M) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: y_stride %d < M %d", y_stride, M); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_GEMM_AUTO || path > LLAMAHIP_GEMM_LDS) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: unknown path %d", path); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    QMat q;
+    q.set_shape(M, K);
+    const size_t wbytes = (size_t) M * (K / 32) * 20, Kp = (size_t) q.Kp(), ybytes = (size_t) N * y_stride * 4;
+    const bool auto_ = path == LLAMAHIP_GEMM_AUTO;
+    const bool want_rows = auto_ || path == LLAMAHIP_GEMM_ROWS, want_mt4 = auto_ || path == LLAMAHIP_GEMM_MFMA4;
+    const bool want_mt = path == LLAMAHIP_GEMM_MFMA_I8 || path == LLAMAHIP_GEMM_FAST;
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_w = s.alloc(wbytes, (const uint8_t *) w_q4_0);
+    float *d_x = s.alloc((size_t) N * K, x);
+    float *d_y = s.alloc((size_t) N * y_stride, y);      // (the floats between M and y_stride keep the caller's bits)
+    float *d_r = resid ? s.alloc((size_t) N * M, resid) : nullptr;
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    if (want_rows) q.rows = s.alloc<uint8_t>(q.rows_bytes());
+    if (want_mt4) q.mt4 = s.alloc<uint8_t>(q.mt4_bytes());
+    if (want_mt) q.mt = s.alloc<uint8_t>(q.mt_bytes());
+    uint32_t *d_qA = s.alloc<uint32_t>((size_t) N * Kp / 4);
+    float *d_qd = s.alloc<float>((size_t) N * (Kp / 32));
+    uint8_t *d_qb = s.alloc<uint8_t>((size_t) N * Kp * 2);      // as the model's workspace: the fp16 (or int8) operand
+    if (s.ok()) s.check(launch_repack(d_w, q.tiles, M, K, 0, 0, st));
+    if (s.ok() && want_rows) s.check(launch_tiles_to_rows(q, st));
+    if (s.ok() && want_mt4) s.check(launch_tiles_to_mt4(q, st));
+    if (s.ok() && want_mt) s.check(launch_tiles_to_mtiles(q, st));
+    if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+    const int epi = resid ? EPI_RESID : EPI_STORE;
+    const char *why = nullptr;
+    long before[GEMM_PATH_COUNT];
+    for (int i = 0; i < GEMM_PATH_COUNT; i++) before[i] = g_gemm_path_counts[i];
+    if (s.ok()) s.check(auto_ ? launch_gemm(q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, false)
+                              : launch_gemm_forced(path, q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, d_qb, &why));
+    s.download(y, d_y, ybytes);
+    s.sync();
+    if (why) { set_err(err, err_cap, "llamahip_op_prompt_gemm_q4_0: path %d refused for M %d, K %d, N %d: %s", path, M, K, N, why); return LLAMAHIP_ERR_PREDICT; }
+    if (!s.ok()) return s.fail("llamahip_op_prompt_gemm_q4_0", err, err_cap);
+    if (path_taken) {
+        // the kernel family whose count moved (the matrix-core count moves with the fast one; this handle has ONE matrix-core copy)
+        auto moved = [&](int i) { return g_gemm_path_counts[i] != before[i]; };
+        *path_taken = moved(GEMM_PATH_FAST) ? LLAMAHIP_GEMM_FAST : moved(GEMM_PATH_MFMA) ? (want_mt4 ? LLAMAHIP_GEMM_MFMA4 : LLAMAHIP_GEMM_MFMA_I8)
+                    : moved(GEMM_PATH_ROWS) ? LLAMAHIP_GEMM_ROWS : moved(GEMM_PATH_SET) ? LLAMAHIP_GEMM_SET
+                    : moved(GEMM_PATH_LDS) ? LLAMAHIP_GEMM_LDS : LLAMAHIP_GEMM_GEMV;
+    }
+    return LLAMAHIP_OK;
+}
+
+// one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
+int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
+                          int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
+                          void *wo_operand, int32_t *path_taken, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_attention";
+    if (!qkv || !Kc || !Vc || N < 1 || d < 1 || H < 1 || d % H != 0 || n_past < 0 || chunk < 0) {
+        set_err(err, err_cap, "%s: bad arguments (N %d >= 1, d %d a multiple of H %d, n_past %d >= 0, chunk %d >= 0)", fn, N, d, H, n_past, chunk);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const int dh = d / H, T = n_past + N, nth = n_threads;
+    if (T > n_ctx) { set_err(err, err_cap, "%s: T = n_past + N = %d > n_ctx %d", fn, T, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (merged && merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (ws_rows < 0 || ws_rows % 64 != 0) { set_err(err, err_cap, "%s: ws_rows %d must be a positive multiple of 64 (0: 512)", fn, ws_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (nth < 1 || nth > 64) { set_err(err, err_cap, "%s: n_threads %d outside 1 .. 64 (the model's clamp)", fn, nth); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_ATTN_AUTO || path > LLAMAHIP_ATTN_DEC_STREAM) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
+    if (d % 32 != 0) { set_err(err, err_cap, "%s: d %d must be a multiple of 32 (Q4_0 blocks of the wo operand)", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    AttnWs ws;                                       // the model's workspace, for ws_rows query rows per batch
+    attn_ws_shape(ws, n_ctx, ws_rows);
+    int run = path;
+    if (path == LLAMAHIP_ATTN_AUTO) run = N >= 2 ? attn_path_pick(&ws, N, dh, T, nth) : -1;
+    const char *why = nullptr;
+    const bool dh_ok = dh % 32 == 0 && dh <= 256;
+    switch (run) {
+    case -1: why = "AUTO takes N >= 2 (one row is the decode step: paths DEC / DEC_STREAM)"; break;
+    case LLAMAHIP_ATTN_MFMA: if (!attn_mfma_applies(&ws, N, dh, T, nth)) why = "MFMA takes N >= 2, head size 128 and n_threads <= 8"; break;
+    case LLAMAHIP_ATTN_ROW: if (!dh_ok) why = "ROW takes head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_SHORT: if (!attn_short_applies(&ws, N, dh)) why = "SHORT takes 2 <= N <= 60 and head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_DEC: if (N != 1 || !dh_ok) why = "DEC takes N = 1 and head sizes that are multiples of 32 up to 256"; break;
+    case LLAMAHIP_ATTN_DEC_STREAM:
+        if (N != 1 || !dh_ok || !pv_stream_applies(dh, n_ctx, nth)) why = "DEC_STREAM takes N = 1, head sizes that are multiples of 32 up to 256, n_threads <= 32 and n_ctx <= 4096";
+        break;
+    }
+    if (why) { set_err(err, err_cap, "%s: path %d refused for N %d, head size %d, n_threads %d: %s", fn, path, N, dh, nth, why); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const bool dec = run == LLAMAHIP_ATTN_DEC || run == LLAMAHIP_ATTN_DEC_STREAM, quant = dec || run == LLAMAHIP_ATTN_SHORT;
+    const int Kp = (d + 255) / 256 * 256;
+    const size_t cache_b = (size_t) n_ctx * d * 4, qr_b = (size_t) N * d * 4;
+    const size_t ms = merged ? (size_t) merged_stride : (size_t) d, mbytes = (size_t) N * ms * 4;
+    const size_t qaA_b = (size_t) N * Kp, qad_b = (size_t) N * (Kp / 32) * 4;
+    const AttnWsBytes wb = attn_ws_bytes(ws, H);
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    const int32_t hs[2] = { n_past, 0 };
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_qr = s.alloc<float>(qr_b / 4), *d_m = s.alloc<float>(mbytes / 4), *d_qad = s.alloc<float>(qad_b / 4);
+    uint32_t *d_qaA = s.alloc<uint32_t>(qaA_b / 4);
+    ws.S = s.alloc<float>(wb.S / 4); ws.pmax = s.alloc<float>(wb.pmax / 4); ws.inv = s.alloc<float>(wb.inv / 4); ws.part = s.alloc<float>(wb.part / 4);
+    // the op's own workspace, every byte NaN (0xFF): a read of something the launch did not write shows in the result
+    s.fill(ws.S, 0xFF, wb.S); s.fill(ws.pmax, 0xFF, wb.pmax); s.fill(ws.inv, 0xFF, wb.inv); s.fill(ws.part, 0xFF, wb.part);
+    s.fill(d_qr, 0xFF, qr_b);
+    s.fill(d_qaA, 0xFF, qaA_b); s.fill(d_qad, 0xFF, qad_b);
+    if (!merged) s.fill(d_m, 0xFF, mbytes);
+    float *d_qkv = s.alloc((size_t) N * 3 * d, qkv), *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    if (merged) s.upload(d_m, merged, mbytes);
+    uint16_t *d_ts = s.alloc(ts.size(), ts.data()), *d_te = s.alloc(te.size(), te.data());
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    int32_t *d_state = s.alloc(2, hs);
+    if (s.ok()) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    float *mo = merged ? d_m : nullptr;
+    if (s.ok() && dec) {
+        s.check(launch_dec_attn(d_qkv, d, H, n_ctx, nth, d_tab, d_K, d_V, ws.S, nullptr, mo, d_qaA, d_qad, d_te, d_state, st,
+                                nullptr, nullptr, run == LLAMAHIP_ATTN_DEC_STREAM));
+    } else if (s.ok()) {
+        s.check(launch_rope_kv(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, n_past, N, st));
+        if (s.ok() && run == LLAMAHIP_ATTN_SHORT)
+            s.check(launch_attn_short(d_qr, d_K, d_V, ws.S, mo, d_qaA, d_qad, n_past, N, d, H, n_ctx, nth, d_te, st, chunk, nullptr, 0, (long) ms));
+        else if (s.ok())
+            s.check(launch_attn(d_qr, d_K, d_V, d_m, nullptr, nullptr, n_past, N, d, H, nth, d_te, run == LLAMAHIP_ATTN_MFMA ? &ws : nullptr, st, chunk, (long) ms));
+    }
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    if (merged) s.download(merged, d_m, mbytes);
+    std::vector<uint32_t> qa(qaA_b / 4);
+    std::vector<float> qd(qad_b / 4);
+    if (quant && wo_operand) {
+        s.download(qa.data(), d_qaA, qaA_b);
+        s.download(qd.data(), d_qad, qad_b);
+    }
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (quant && wo_operand) {
+        // QA layout (kcommon.hip.h quantize_y) -> Q4_0 blocks in file layout: {d, qs[16]}, qs[k] = (q[2k] + 8) | (q[2k+1] + 8) << 4
+        // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
+        uint8_t *o = (uint8_t *) wo_operand;
+        for (int n = 0; n < N; n++)
+            for (int b = 0; b < d / 32; b++) {
+                const uint32_t *A = qa.data() + (size_t) n * (Kp / 4);
+                uint8_t *blk = o + ((size_t) n * (d / 32) + b) * 20;
+                memcpy(blk, &qd[(size_t) n * (Kp / 32) + b], 4);
+                const int c = b >> 3, j = b & 7;
+                for (int k = 0; k < 8; k++) {
+                    const uint32_t w = A[(c * 8 + k) * 8 + j] >> (4 * (j & 1));
+                    const uint32_t q0 = (w & 0xF) ^ 8, q1 = ((w >> 8) & 0xF) ^ 8, q2 = ((w >> 16) & 0xF) ^ 8, q3 = ((w >> 24) & 0xF) ^ 8;
+                    blk[4 + k] = (uint8_t) (q0 | (q1 << 4));
+                    blk[12 + k] = (uint8_t) (q2 | (q3 << 4));
+                }
+            }
+    }
+    if (path_taken) *path_taken = run;
+    return LLAMAHIP_OK;
+}
+
+// host-only: the attention path a model's multi-row eval of N rows after n_past takes once its workspace exists (ensure_attn_ws)
+int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx) {
+    AttnWs ws;
+    attn_ws_shape(ws, n_ctx);
+    if (N < 2) return -1;
+    return attn_path_pick(&ws, N, head_size, n_past + N, std::max(1, std::min((int) n_threads, 64)));
+}
+
+// the device half of the sampler on caller-supplied logits (parity tests): see llamahip_eval_topk
+int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
+                     int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap) {
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!logits || !cand_scores || !cand_ids || !exact || n_vocab < 1 || n_vocab > 32768 || top_k < 1 || top_k > 64 || top_k > n_vocab || n_last < 0 || n_last > 1024) {
+        set_err(err, err_cap, "llamahip_op_topk: bad arguments"); return LLAMAHIP_ERR_PREDICT;
+    }
+    Scratch s;
+    char *d_w = s.alloc<char>(8192 + TOPK_WS_BYTES);      // window [1024] | TopkOut at 4096 | from 8192: the selection's workspace
+    s.fill(d_w, 0, 8192 + TOPK_WS_BYTES);
+    float *d_l = s.alloc((size_t) n_vocab, logits);
+    int32_t *d_win = (int32_t *) d_w;
+    TopkOut *d_out = d_w ? (TopkOut *) (d_w + 4096) : nullptr;
+    TopkOut h;
+    if (n_last > 0) s.upload(d_win, last_n_tokens, (size_t) n_last * 4);
+    if (s.ok()) s.check(launch_topk_candidates(d_l, n_vocab, d_win, n_last, 1.0 / temp, repeat_penalty, top_k, d_out->sc, d_out->id, d_out->fl, nullptr, d_w + 8192));
+    s.download(&h, d_out, sizeof(h));
+    if (!s.ok()) return s.fail("llamahip_op_topk", err, err_cap);
+    *exact = h.fl[0];
+    for (int i = 0; i < top_k; i++) { cand_scores[i] = h.sc[i]; cand_ids[i] = h.id[i]; }
+    return LLAMAHIP_OK;
+}
+
+// the batched device half of the sampler on caller-supplied rows (parity tests): see llamahip_decode_sample_multi
+int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *windows, const int32_t *n_last, double repeat_penalty,
+                          int32_t top_k, double temp, double *out_scores, int32_t *out_ids, int32_t *out_exact, float *out_spill, char *err, size_t err_cap) {
+    if (!logits || !windows || !n_last || !out_scores || !out_ids || !out_exact || n_rows < 1 || n_vocab < 1 || n_vocab > 32768 || top_k < 1 || top_k > 64 || top_k > n_vocab) {
+        set_err(err, err_cap, "llamahip_op_topk_rows: bad arguments (n_rows %d, n_vocab %d <= 32768, top_k %d in [1, min(64, n_vocab)])", n_rows, n_vocab, top_k); return LLAMAHIP_ERR_PREDICT;
+    }
+    for (int r = 0; r < n_rows; r++)
+        if (n_last[r] < 0) { set_err(err, err_cap, "llamahip_op_topk_rows: n_last[%d] = %d", r, n_last[r]); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t R = n_rows, V = n_vocab;
+    std::vector<TopkOut> h(R);
+    Scratch s;
+    char *d_ws = s.alloc<char>(R * TOPK_WS_BYTES);
+    s.fill(d_ws, 0, R * TOPK_WS_BYTES);
+    float *d_l = s.alloc(R * V, logits);
+    int32_t *d_win = s.alloc<int32_t>(R * 1024 + R);      // the windows, then n_last
+    s.upload(d_win, windows, R * 1024 * 4);
+    if (s.ok()) s.upload(d_win + R * 1024, n_last, R * 4);
+    float *d_sp = out_spill ? s.alloc(R * V, out_spill) : nullptr;      // (rows that are not spilled keep the caller's bits)
+    TopkOut *d_out = s.alloc<TopkOut>(R);
+    if (s.ok()) s.check(launch_topk_rows(d_l, n_rows, n_vocab, d_win, d_win + R * 1024, 1.0 / temp, repeat_penalty, top_k, d_out, d_sp, nullptr, d_ws));
+    s.download(h.data(), d_out, R * sizeof(TopkOut));
+    if (out_spill) s.download(out_spill, d_sp, R * V * 4);
+    if (!s.ok()) return s.fail("llamahip_op_topk_rows", err, err_cap);
+    for (size_t r = 0; r < R; r++) {
+        out_exact[r] = h[r].fl[0];
+        for (int i = 0; i < top_k; i++) { out_scores[r * 64 + i] = h[r].sc[i]; out_ids[r * 64 + i] = h[r].id[i]; }
+    }
+    return LLAMAHIP_OK;
+}
+
+// k_row_logprob on caller-supplied rows (parity tests): see llamahip_eval_logprobs
+int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
+                        double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap) {
+    if (!logits || n_rows < 1 || n_vocab < 1) { set_err(err, err_cap, "llamahip_op_logprob: bad arguments (n_rows %d, n_vocab %d)", n_rows, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (targets)
+        for (int i = 0; i < n_rows; i++)
+            if (targets[i] < -1 || targets[i] >= n_vocab) { set_err(err, err_cap, "llamahip_op_logprob: target %d of row %d out of range [-1, %d)", targets[i], i, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows;
+    std::vector<char> h(N * 16);
+    Scratch s;
+    float *d_l = s.alloc(N * (size_t) n_vocab, logits);
+    char *d_s = s.alloc<char>(N * 20);      // logprob [N] doubles | argmax [N] | rank [N] | targets [N]
+    int32_t *d_t = d_s ? (int32_t *) (d_s + 16 * N) : nullptr;
+    if (targets) s.upload(d_t, targets, N * 4);
+    else s.fill(d_t, 0xFF, N * 4);      // (0xFFFFFFFF = -1)
+    if (s.ok()) s.check(launch_row_logprob(d_l, n_rows, n_vocab, d_t, (double *) d_s, (int32_t *) (d_s + 8 * N), (int32_t *) (d_s + 12 * N), nullptr));
+    s.download(h.data(), d_s, N * 16);
+    if (!s.ok()) return s.fail("llamahip_op_logprob", err, err_cap);
+    if (logprob_out) memcpy(logprob_out, h.data(), N * 8);
+    if (argmax_out) memcpy(argmax_out, h.data() + N * 8, N * 4);
+    if (rank_out) memcpy(rank_out, h.data() + N * 12, N * 4);
+    return LLAMAHIP_OK;
+}
+
+// k_verify_rows + k_accept_drafts on caller-supplied rows (parity tests): see llamahip_verify_greedy
+int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
+                            int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    if (!logits || !tokens || n_rows < 1 || n_rows > VERIFY_ROWS_MAX || n_vocab < 1) {
+        set_err(err, err_cap, "llamahip_op_verify_rows: bad arguments (n_rows %d of 1 .. %d, n_vocab %d)", n_rows, VERIFY_ROWS_MAX, n_vocab);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows;
+    int32_t h[VERIFY_ROWS_MAX + 1] = { 0 };
+    Scratch s;
+    int32_t *d_v = s.alloc<int32_t>(80);      // {position, cursor} | tokens | picks | result | from [64]: a log of 16 entries
+    s.fill(d_v, 0, 80 * 4);
+    float *d_l = s.alloc(N * (size_t) n_vocab, logits);
+    if (s.ok()) s.upload(d_v + 2, tokens, N * 4);
+    if (s.ok()) s.check(launch_verify_rows(d_l, n_rows, n_vocab, d_v + 18, nullptr));
+    if (s.ok()) s.check(launch_accept_drafts(d_v + 2, d_v + 18, 0, n_rows, 0, d_v + 64, VERIFY_ROWS_MAX, d_v, d_v + 34, nullptr));
+    if (s.ok()) s.download(h, d_v + 34, (N + 1) * 4);
+    if (!s.ok()) return s.fail("llamahip_op_verify_rows", err, err_cap);
+    if (n_accept) *n_accept = h[0];
+    if (picks) memcpy(picks, h + 1, N * 4);
+    return LLAMAHIP_OK;
+}
+
+int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap) {
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!x || !y || k < 32 || k % 32 != 0) { set_err(err, err_cap, "bad quantize arguments"); return LLAMAHIP_ERR_PREDICT; }
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t Kp = ((size_t) k + 255) / 256 * 256, raw_b = (size_t) (k / 32) * 20;
+    Scratch s;
+    float *d_x = s.alloc((size_t) k, x), *d_qd = s.alloc<float>(Kp / 32);
+    uint32_t *d_qA = s.alloc<uint32_t>(Kp / 4);
+    uint8_t *d_raw = s.alloc<uint8_t>(raw_b);
+    if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_x, nullptr, k, 0, k, 1, d_qA, d_qd, nullptr, d_raw, nullptr, nullptr));
+    s.download(y, d_raw, raw_b);
+    return s.ok() ? LLAMAHIP_OK : s.fail("llamahip_op_quantize_row_q4_0", err, err_cap);
+}
+
+}  // extern "C"

@@ -6,7 +6,6 @@
 // (k_quantize_offline); the host only moves bytes.  No CPU fallback.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -14,18 +13,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/llamahip.h"
+#include "host_util.h"
 #include "llamahip_internal.h"
 
 namespace {
-
-void set_err(char *err, size_t cap, const char *fmt, ...) {
-    if (!err || cap == 0) return;
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err, cap, fmt, ap);
-    va_end(ap);
-}
 
 struct File {
     FILE *f = nullptr;
@@ -42,6 +33,7 @@ static int quantize_file_impl(const char *fname_inp, const char *fname_out, int3
 
 // No C++ exception may cross the C ABI.
 extern "C" int llamahip_quantize_file(const char *fname_inp, const char *fname_out, int32_t itype, char *err, size_t err_cap) {
+    using lh::set_err;
     try {
         return quantize_file_impl(fname_inp, fname_out, itype, err, err_cap);
     } catch (const std::exception &ex) {
@@ -59,11 +51,7 @@ static int quantize_file_impl(const char *fname_inp, const char *fname_out, int3
         set_err(err, err_cap, "invalid quantization type %d", itype);
         return LLAMAHIP_ERR_LOAD;
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-        set_err(err, err_cap, "no HIP device available: libllamahip has no CPU fallback");
-        return LLAMAHIP_ERR_LOAD;
-    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_LOAD;
     File in, out;
     in.f = fopen(fname_inp, "rb");
     if (!in.f) { set_err(err, err_cap, "failed to open '%s' for reading", fname_inp); return LLAMAHIP_ERR_LOAD; }      // quantize.cpp:49-53
