@@ -449,6 +449,33 @@ int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, 
  * NULL = none scored); any of the three outputs may be NULL */
 int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
                         double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap);
+/* One activation-preparation launch (the producers of every mat-mul's Q4_0 operand) on caller-supplied rows, kernel family chosen by the
+ * caller.  buf [buf_floats]: ONE buffer uploaded as the caller laid it out; row n of in0 starts at float in0_offset + n * in_stride; in1
+ * is the K norm weights at in1_offset (NORM), rows at in1_offset + n * in1_stride (SILU_MUL: the model's layout is in1_offset = in0_offset
+ * + F with both strides 2F), unused for PLAIN.  K: a multiple of 32 up to 32768; offsets and strides multiples of 4 floats, strides >= K.
+ * mode: _PLAIN y = in0; _NORM y = w * ((float) (x - mean) * scale) (ggml_norm + ggml_mul); _SILU_MUL y = silu_table(in0) * in1.
+ * kernel: _AUTO the rule of the model's launches (k_prep_fast unless y is wanted or a NORM row has K / 16 > 1024), _FAST k_prep_fast
+ * (register resident; no y; NORM rows up to K / 16 = 1024), _LDS k_prep_qa.  Refusals happen before any device is touched.
+ * qa_A [qa_rows][Kp / 4] dwords and qa_d [qa_rows][Kp / 32] scales, Kp = K rounded up to 256, qa_rows >= N: the raw operand, copied to the
+ * device before the launch and back after it, so whatever the launch does not write keeps the caller's bits.  y [N][K] (may be NULL):
+ * the fp32 rows before quantization, likewise copied both ways.  *kernel_taken (may be NULL): _FAST or _LDS. */
+#define LLAMAHIP_PREP_PLAIN    1
+#define LLAMAHIP_PREP_NORM     2
+#define LLAMAHIP_PREP_SILU_MUL 3
+#define LLAMAHIP_PREP_KERNEL_AUTO 0
+#define LLAMAHIP_PREP_KERNEL_FAST 1
+#define LLAMAHIP_PREP_KERNEL_LDS  2
+int llamahip_op_prep(int32_t mode, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
+                     int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, uint32_t *qa_A, float *qa_d, int32_t qa_rows,
+                     float *y, int32_t *kernel_taken, char *err, size_t err_cap);
+/* Host-only: N rows of the raw operand above -> [N][K / 32] Q4_0 blocks in file layout (what llamahip_op_attention's wo_operand holds). */
+int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t N, int32_t K, void *blocks);
+/* The embedding gather (ggml_get_rows on a Q4_0 matrix): tokens [N] in [0, V) (checked on the host), emb [V][d / 32] blocks in file layout,
+ * x [N][x_stride] (x_stride >= d) copied whole both ways: the kernels write dense [N][d] rows on the device (followed by a guard the op checks), which
+ * the op places x_stride apart.  stats == NULL: k_embed as a multi-row eval launches it.  stats != NULL (N = 1):
+ * the decode step's k_embed_part, which also leaves {sum x, sum x^2} of the row in stats[0 .. 1]. */
+int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, int32_t V, int32_t d, float *x, int32_t x_stride,
+                      double *stats, char *err, size_t err_cap);
 /* runtime activation quantizer (ggml.c:456-523): x[k] -> k/32 blocks of 20 bytes */
 int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap);
 

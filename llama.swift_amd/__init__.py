@@ -26,13 +26,16 @@ from .binding import (  # noqa: F401
     lib,
     lookup_draft,
     op_attention,
+    op_embed,
     op_logprob,
     op_mul_mat_q4_0,
+    op_prep,
     op_prompt_gemm_q4_0,
     op_quantize_row_q4_0,
     op_topk,
     op_topk_rows,
     op_verify_rows,
+    qa_to_blocks,
     quantize_file,
     set_plan,
     version,

@@ -146,6 +146,9 @@ def lib() -> C.CDLL:
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_op_prep.argtypes = [i32, i32, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, i32, vp, vp, i32, vp, vp, cp, sz]
+    L.llamahip_debug_qa_to_blocks.argtypes = [vp, vp, i32, i32, vp]
+    L.llamahip_op_embed.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
     L.llamahip_get_stats.argtypes = [vp, C.POINTER(_Stats)]
     L.llamahip_debug_lut_math.restype = i32
@@ -718,6 +721,60 @@ def debug_attn_path(N: int, head_size: int, n_past: int, n_threads: int, n_ctx: 
     """Host-only: the attention path a model's multi-row eval takes for the shape (llamahip_debug_attn_path); None for one row."""
     r = lib().llamahip_debug_attn_path(N, head_size, n_past, n_threads, n_ctx)
     return None if r < 0 else ATTN_PATHS[r]
+
+
+PREP_MODES = {"plain": 1, "norm": 2, "silu_mul": 3}      # LLAMAHIP_PREP_* of llamahip.h
+PREP_KERNELS = ("auto", "fast", "lds")                    # LLAMAHIP_PREP_KERNEL_*, in order
+
+
+def op_prep(mode: str, buf: np.ndarray, K: int, N: int, in_stride: int | None = None, in0_offset: int = 0, in1_offset: int = 0,
+            in1_stride: int = 0, kernel: str = "auto", want_y: bool = False, qa_rows: int | None = None, fill: int = 0xFF):
+    """One activation-preparation launch (llamahip_op_prep).  buf: ONE float32 buffer holding every operand as the caller laid it out: in0
+    rows at in0_offset + n * in_stride (default stride K); in1 = the K norm weights at in1_offset ("norm") or rows at in1_offset + n *
+    in1_stride ("silu_mul").  Returns (qa_A uint32 [qa_rows, Kp/4], qa_d float32 [qa_rows, Kp/32], y float32 [N, K] or None, the kernel
+    taken): the raw operand buffers as the device left them, every byte `fill` where the launch wrote nothing (y: likewise)."""
+    buf = np.ascontiguousarray(buf, np.float32).ravel()
+    Kp = (int(K) + 255) // 256 * 256
+    rows = int(N) if qa_rows is None else int(qa_rows)
+    qa_A = np.full((max(rows, 0), Kp // 4), fill * 0x01010101, np.uint32)
+    qa_d = np.full((max(rows, 0), Kp // 32), fill * 0x01010101, np.uint32).view(np.float32)
+    y = np.full((max(int(N), 0), max(int(K), 0)), fill * 0x01010101, np.uint32).view(np.float32) if want_y else None
+    mcode = PREP_MODES[mode] if mode in PREP_MODES else int(mode)
+    kcode = PREP_KERNELS.index(kernel) if kernel in PREP_KERNELS else int(kernel)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_prep(mcode, kcode, _ptr(buf), buf.size, int(in0_offset), int(K if in_stride is None else in_stride), int(in1_offset),
+                                int(in1_stride), int(K), int(N), _ptr(qa_A), _ptr(qa_d), rows, _ptr(y), C.byref(taken), err, len(err))
+    _check(rc, err)
+    return qa_A, qa_d, y, PREP_KERNELS[taken.value]
+
+
+def qa_to_blocks(qa_A: np.ndarray, qa_d: np.ndarray, N: int, K: int) -> np.ndarray:
+    """Host-only: rows 0 .. N-1 of a raw QA operand (op_prep) -> uint8 [N, K/32, 20] Q4_0 blocks in file layout (llamahip_debug_qa_to_blocks)."""
+    qa_A, qa_d = np.ascontiguousarray(qa_A, np.uint32), np.ascontiguousarray(qa_d, np.float32)
+    Kp = (K + 255) // 256 * 256
+    if qa_A.size < N * Kp // 4 or qa_d.size < N * Kp // 32:
+        raise ValueError(f"qa_to_blocks: {qa_A.size} dwords / {qa_d.size} scales for {N} rows of K {K}")
+    out = np.empty((N, K // 32, 20), np.uint8)
+    if lib().llamahip_debug_qa_to_blocks(_ptr(qa_A), _ptr(qa_d), N, K, _ptr(out)) != 0:
+        raise ValueError(f"qa_to_blocks: bad arguments (N {N}, K {K})")
+    return out
+
+
+def op_embed(tokens, emb: np.ndarray, x_stride: int | None = None, x_init=None, want_stats: bool = False):
+    """The embedding gather (llamahip_op_embed): tokens int32 [N], emb uint8 [V, d/32, 20] -> x float32 [N, x_stride] as the device left it
+    (x_init, default NaN, where nothing was written).  want_stats (N = 1): k_embed_part instead of k_embed; returns (x, float64 [2])."""
+    tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+    emb = np.ascontiguousarray(emb, np.uint8)
+    V, nb, _ = emb.shape
+    d, N = nb * 32, tokens.size
+    xs = d if x_stride is None else int(x_stride)
+    x = np.full((N, max(xs, 0)), np.nan, np.float32) if x_init is None else np.array(x_init, np.float32, order="C").reshape(N, xs)
+    stats = np.full(2, np.nan, np.float64) if want_stats else None
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_embed(_ptr(tokens), N, _ptr(emb), V, d, _ptr(x), xs, _ptr(stats), err, len(err))
+    _check(rc, err)
+    return (x, stats) if want_stats else x
 
 
 def op_quantize_row_q4_0(x: np.ndarray) -> np.ndarray:

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 
 #include "../../include/llamahip.h"
@@ -36,6 +37,26 @@ inline int need_device(char *err, size_t err_cap) {
 // (llamahip.cpp: a model load and llamahip_op_attention upload the same ones)
 void lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te);
 std::vector<double> rope_table(int n_ctx, int dh);
+
+// QA operand (kcommon.hip.h quantize_y: rows Kp / 4 dwords and Kp / 32 scales apart, Kp = K rounded up to 256; dword (c * 8 + k) * 8 + j
+// of a row holds chain k of block c * 8 + j as signed nibbles, shifted 4 bits in odd blocks) -> N rows of K / 32 Q4_0 blocks in file
+// layout: {d, qs[16]}, qs[k] = (q[2k] + 8) | (q[2k+1] + 8) << 4
+inline void qa_to_q4_0_blocks(const uint32_t *qa_A, const float *qa_d, int N, int K, uint8_t *out) {
+    const int Kp = (K + 255) / 256 * 256;
+    for (int n = 0; n < N; n++)
+        for (int b = 0; b < K / 32; b++) {
+            const uint32_t *A = qa_A + (size_t) n * (Kp / 4);
+            uint8_t *blk = out + ((size_t) n * (K / 32) + b) * 20;
+            memcpy(blk, &qa_d[(size_t) n * (Kp / 32) + b], 4);
+            const int c = b >> 3, j = b & 7;
+            for (int k = 0; k < 8; k++) {
+                const uint32_t w = A[(c * 8 + k) * 8 + j] >> (4 * (j & 1));
+                const uint32_t q0 = (w & 0xF) ^ 8, q1 = ((w >> 8) & 0xF) ^ 8, q2 = ((w >> 16) & 0xF) ^ 8, q3 = ((w >> 24) & 0xF) ^ 8;
+                blk[4 + k] = (uint8_t) (q0 | (q1 << 4));
+                blk[12 + k] = (uint8_t) (q2 | (q3 << 4));
+            }
+        }
+}
 
 // Device memory, a stream and events that live for ONE call.  The first HIP error sticks: after it alloc returns null and upload /
 // download / fill / sync do nothing, so a body reads top to bottom, guards its launches with `if (s.ok()) s.check(launch_...)` and

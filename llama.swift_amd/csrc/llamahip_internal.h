@@ -95,9 +95,15 @@ hipError_t launch_tiles_to_rows(const QMat &w, hipStream_t st);   // w.rows / w.
 hipError_t launch_tiles_to_mtiles(const QMat &w, hipStream_t st); // w.mt / w.nrb32 set by the caller
 hipError_t launch_tiles_to_mt4(const QMat &w, hipStream_t st);    // w.mt4 / w.nrb32 set by the caller
 hipError_t launch_embed(const int32_t *tokens, const uint8_t *emb, float *x, int d, int N, hipStream_t st);
+// The rule of launch_prep: the register-resident k_prep_fast unless a side output (y_out / raw_out) is wanted or a NORM row is wider than
+// one workgroup's 1024 half-blocks; else the LDS-staged k_prep_qa.  force (llamahip_op_prep: per-op tests of both kernels on one shape):
+// PREP_FORCE_FAST is refused with hipErrorInvalidValue where the rule's conditions for k_prep_fast do not hold; nothing is launched then.
+// *launched (may be null): PREP_FORCE_FAST or PREP_FORCE_LDS, set on the branch that launches.
+enum { PREP_FORCE_AUTO = 0, PREP_FORCE_FAST = 1, PREP_FORCE_LDS = 2 };      // = LLAMAHIP_PREP_KERNEL_* of llamahip.h
+bool prep_fast_applies(int mode, int K, bool side_output);
 hipError_t launch_prep(int mode, const float *in0, const float *in1, long in_stride, long in1_stride, int K, int N,
                        uint32_t *qa_A, float *qa_d, float *y_out, uint8_t *raw_out, const uint16_t *T_silu,
-                       hipStream_t st);
+                       hipStream_t st, int force = PREP_FORCE_AUTO, int *launched = nullptr);
 // Norm statistics handed from the producer of a residual-stream row to the norm-fused mat-vec that reads it
 // (decode only): an EPI_RESID launch with `out` set writes one {sum y, sum y^2} pair of doubles per workgroup
 // (gemv_resid_parts(w) of them); a PREP_NORM launch with `in` / `n_in` set folds them instead of reducing the

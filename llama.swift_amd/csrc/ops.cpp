@@ -10,6 +10,9 @@
 
 using namespace lh;
 
+static_assert(LLAMAHIP_PREP_PLAIN == PREP_PLAIN && LLAMAHIP_PREP_NORM == PREP_NORM && LLAMAHIP_PREP_SILU_MUL == PREP_SILU_MUL, "llamahip.h mirrors the prep modes");
+static_assert(LLAMAHIP_PREP_KERNEL_AUTO == PREP_FORCE_AUTO && LLAMAHIP_PREP_KERNEL_FAST == PREP_FORCE_FAST && LLAMAHIP_PREP_KERNEL_LDS == PREP_FORCE_LDS, "... and launch_prep's force values");
+
 extern "C" {
 
 int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N,
@@ -176,24 +179,8 @@ int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int
     }
     s.sync();
     if (!s.ok()) return s.fail(fn, err, err_cap);
-    if (quant && wo_operand) {
-        // QA layout (kcommon.hip.h quantize_y) -> Q4_0 blocks in file layout: {d, qs[16]}, qs[k] = (q[2k] + 8) | (q[2k+1] + 8) << 4
-        // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
-        uint8_t *o = (uint8_t *) wo_operand;
-        for (int n = 0; n < N; n++)
-            for (int b = 0; b < d / 32; b++) {
-                const uint32_t *A = qa.data() + (size_t) n * (Kp / 4);
-                uint8_t *blk = o + ((size_t) n * (d / 32) + b) * 20;
-                memcpy(blk, &qd[(size_t) n * (Kp / 32) + b], 4);
-                const int c = b >> 3, j = b & 7;
-                for (int k = 0; k < 8; k++) {
-                    const uint32_t w = A[(c * 8 + k) * 8 + j] >> (4 * (j & 1));
-                    const uint32_t q0 = (w & 0xF) ^ 8, q1 = ((w >> 8) & 0xF) ^ 8, q2 = ((w >> 16) & 0xF) ^ 8, q3 = ((w >> 24) & 0xF) ^ 8;
-                    blk[4 + k] = (uint8_t) (q0 | (q1 << 4));
-                    blk[12 + k] = (uint8_t) (q2 | (q3 << 4));
-                }
-            }
-    }
+    // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
+    if (quant && wo_operand) qa_to_q4_0_blocks(qa.data(), qd.data(), N, d, (uint8_t *) wo_operand);
     if (path_taken) *path_taken = run;
     return LLAMAHIP_OK;
 }
@@ -306,6 +293,92 @@ int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab
     if (!s.ok()) return s.fail("llamahip_op_verify_rows", err, err_cap);
     if (n_accept) *n_accept = h[0];
     if (picks) memcpy(picks, h + 1, N * 4);
+    return LLAMAHIP_OK;
+}
+
+// one launch_prep on caller-supplied rows, the kernel family chosen by the caller (per-op tests of the activation producers): see llamahip.h
+int llamahip_op_prep(int32_t mode, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
+                     int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, uint32_t *qa_A, float *qa_d, int32_t qa_rows,
+                     float *y, int32_t *kernel_taken, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_prep";
+    if (mode != LLAMAHIP_PREP_PLAIN && mode != LLAMAHIP_PREP_NORM && mode != LLAMAHIP_PREP_SILU_MUL) { set_err(err, err_cap, "%s: unknown mode %d", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    if (kernel < LLAMAHIP_PREP_KERNEL_AUTO || kernel > LLAMAHIP_PREP_KERNEL_LDS) { set_err(err, err_cap, "%s: unknown kernel %d", fn, kernel); return LLAMAHIP_ERR_PREDICT; }
+    if (!buf || !qa_A || !qa_d || N < 1 || qa_rows < N) { set_err(err, err_cap, "%s: bad arguments (N %d >= 1, qa_rows %d >= N)", fn, N, qa_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (K < 32 || K % 32 != 0 || K > 32768) { set_err(err, err_cap, "%s: K %d must be a multiple of 32 in 32 .. 32768", fn, K); return LLAMAHIP_ERR_PREDICT; }
+    const bool rows1 = mode == LLAMAHIP_PREP_SILU_MUL, has1 = mode != LLAMAHIP_PREP_PLAIN;
+    if (in_stride < K || (rows1 && in1_stride < K)) {
+        set_err(err, err_cap, "%s: row stride %lld / %lld < K %d", fn, (long long) in_stride, (long long) in1_stride, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (in_stride % 4 != 0 || in0_offset % 4 != 0 || (has1 && in1_offset % 4 != 0) || (rows1 && in1_stride % 4 != 0)) {
+        set_err(err, err_cap, "%s: strides and offsets must be multiples of 4 floats (the kernels load 16 bytes at a time)", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    const int64_t end0 = in0_offset + (int64_t) (N - 1) * in_stride + K, end1 = !has1 ? 0 : in1_offset + (rows1 ? (int64_t) (N - 1) * in1_stride : 0) + K;
+    if (in0_offset < 0 || (has1 && in1_offset < 0) || end0 > buf_floats || end1 > buf_floats) {
+        set_err(err, err_cap, "%s: the operands end at float %lld / %lld of a buffer of %lld", fn, (long long) end0, (long long) end1, (long long) buf_floats); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (kernel == LLAMAHIP_PREP_KERNEL_FAST && y) { set_err(err, err_cap, "%s: kernel FAST (k_prep_fast) has no fp32 output: y is the LDS kernel's", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (kernel == LLAMAHIP_PREP_KERNEL_FAST && !prep_fast_applies(mode, K, false)) {
+        set_err(err, err_cap, "%s: kernel FAST refused for NORM with K %d: a row is one workgroup of K / 16 <= 1024 threads", fn, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t Kp = ((size_t) K + 255) / 256 * 256, A_b = (size_t) qa_rows * Kp, d_b = (size_t) qa_rows * (Kp / 32) * 4;
+    int launched = -1;      // the family launch_prep's own branch reports
+    std::vector<uint16_t> ts, te;
+    if (rows1) { ts.resize(1 << 16); te.resize(1 << 16); lut_tables(ts, te); }
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_buf = s.alloc((size_t) buf_floats, buf), *d_qd = s.alloc(d_b / 4, qa_d);      // (the QA buffers keep the caller's bits wherever the launch does not write)
+    uint32_t *d_qA = s.alloc(A_b / 4, qa_A);
+    float *d_y = y ? s.alloc((size_t) N * K, y) : nullptr;
+    uint16_t *d_ts = rows1 ? s.alloc(ts.size(), ts.data()) : nullptr;
+    if (s.ok()) s.check(launch_prep(mode, d_buf + in0_offset, has1 ? d_buf + in1_offset : nullptr, (long) in_stride, (long) in1_stride, K, N, d_qA, d_qd, d_y, nullptr,
+                                    d_ts, st, kernel, &launched));
+    s.download(qa_A, d_qA, A_b);
+    s.download(qa_d, d_qd, d_b);
+    if (y) s.download(y, d_y, (size_t) N * K * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (kernel_taken) *kernel_taken = launched;
+    return LLAMAHIP_OK;
+}
+
+// host-only: the QA operand llamahip_op_prep returns -> Q4_0 blocks in file layout (host_util.h qa_to_q4_0_blocks)
+int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t N, int32_t K, void *blocks) {
+    if (!qa_A || !qa_d || !blocks || N < 1 || K < 32 || K % 32 != 0) return LLAMAHIP_ERR_PREDICT;
+    qa_to_q4_0_blocks(qa_A, qa_d, N, K, (uint8_t *) blocks);
+    return LLAMAHIP_OK;
+}
+
+// the embedding gather on a caller-supplied Q4_0 matrix: k_embed, or with stats k_embed_part (one token): see llamahip.h
+int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, int32_t V, int32_t d, float *x, int32_t x_stride,
+                      double *stats, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_embed";
+    if (!tokens || !emb_q4_0 || !x || N < 1 || V < 1 || d < 32 || d % 32 != 0) { set_err(err, err_cap, "%s: bad arguments (N %d, V %d >= 1; d %d a multiple of 32)", fn, N, V, d); return LLAMAHIP_ERR_PREDICT; }
+    if (x_stride < d) { set_err(err, err_cap, "%s: x_stride %d < d %d", fn, x_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (stats && N != 1) { set_err(err, err_cap, "%s: stats are k_embed_part's, which takes one token (N %d)", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    for (int n = 0; n < N; n++)
+        if (tokens[n] < 0 || tokens[n] >= V) { set_err(err, err_cap, "%s: token %d of row %d outside [0, %d)", fn, tokens[n], n, V); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t xfloats = (size_t) N * x_stride;
+    Scratch s;
+    hipStream_t st = s.stream();
+    int32_t *d_tok = s.alloc((size_t) N, tokens);
+    uint8_t *d_emb = s.alloc((size_t) V * (d / 32) * 20, (const uint8_t *) emb_q4_0);
+    float *d_x = s.alloc(xfloats, x);      // (the floats between d and x_stride keep the caller's bits)
+    float *d_rows = s.alloc<float>((size_t) N * d + 64);      // the kernels' dense [N][d] output, then 64 floats that must stay NaN
+    s.fill(d_rows, 0xFF, ((size_t) N * d + 64) * 4);
+    double *d_part = stats ? s.alloc<double>(2) : nullptr;
+    if (s.ok()) s.check(stats ? launch_embed_part(d_tok, d_emb, d_rows, d, d_part, st) : launch_embed(d_tok, d_emb, d_rows, d, N, st));
+    if (s.ok()) s.check(hipMemcpy2DAsync(d_x, (size_t) x_stride * 4, d_rows, (size_t) d * 4, (size_t) d * 4, N, hipMemcpyDeviceToDevice, st));
+    uint32_t tail[64];
+    s.download(tail, d_rows + (size_t) N * d, sizeof(tail));
+    s.download(x, d_x, xfloats * 4);
+    if (stats) s.download(stats, d_part, 16);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (uint32_t t : tail)
+        if (t != 0xFFFFFFFFu) { set_err(err, err_cap, "%s: the kernel wrote past row N - 1 of its [N][d] output", fn); return LLAMAHIP_ERR_PREDICT; }
     return LLAMAHIP_OK;
 }
 

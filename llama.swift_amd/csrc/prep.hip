@@ -388,6 +388,7 @@ hipError_t launch_rows_set(SeqSet *set, int n, float *x, int d, bool gather, hip
     return hipSuccess;
 }
 
+bool prep_fast_applies(int mode, int K, bool side_output) { return !side_output && (mode != PREP_NORM || K / 16 <= 1024); }
 size_t prep_lds_bytes(int K) { return 32 * sizeof(double) + ((size_t) K + K / 32 + 64) * sizeof(float); }
 
 hipError_t launch_embed_part(const int32_t *token, const uint8_t *emb, float *x, int d, double *part_out, hipStream_t st, uint32_t *epoch, uint64_t *xt,
@@ -398,10 +399,13 @@ hipError_t launch_embed_part(const int32_t *token, const uint8_t *emb, float *x,
 }
 hipError_t launch_prep(int mode, const float *in0, const float *in1, long in_stride, long in1_stride, int K, int N,
                        uint32_t *qa_A, float *qa_d, float *y_out, uint8_t *raw_out, const uint16_t *T_silu,
-                       hipStream_t st) {
+                       hipStream_t st, int force, int *launched) {
     const int Kp = (K + 255) / 256 * 256;
     const int nh = K / 16;
-    if (!y_out && !raw_out && (mode != PREP_NORM || nh <= 1024)) {
+    const bool fast_ok = prep_fast_applies(mode, K, y_out || raw_out);
+    if (force == PREP_FORCE_FAST && !fast_ok) return hipErrorInvalidValue;
+    if (force == PREP_FORCE_FAST || (force != PREP_FORCE_LDS && fast_ok)) {
+        if (launched) *launched = PREP_FORCE_FAST;
         // register-resident kernel: NORM = one workgroup per row, the others sliced 256 half-blocks per workgroup
         const int nt = mode == PREP_NORM ? (nh + 63) / 64 * 64 : 256;
         const dim3 grid(N, mode == PREP_NORM ? 1 : (nh + nt - 1) / nt);
@@ -417,6 +421,7 @@ hipError_t launch_prep(int mode, const float *in0, const float *in1, long in_str
         return hipSuccess;
     }
     const size_t lds = prep_lds_bytes(K);
+    if (launched) *launched = PREP_FORCE_LDS;
 #define LH_PREP(MODE) hipLaunchKernelGGL(k_prep_qa<MODE>, dim3(N), dim3(256), lds, st, in0, in1, in_stride, in1_stride, K, Kp, qa_A, qa_d, y_out, raw_out, T_silu)
     switch (mode) {
         case PREP_PLAIN:    LH_PREP(PREP_PLAIN); break;

@@ -3,7 +3,8 @@ produced by the reference build, (b) the oracle on seeded inputs, (c) size-indep
 the full LLaMA-7B size.  Everything is compared BIT FOR BIT (fp32 logits included): the kernels
 reproduce the arithmetic order of the reference's AVX2 build, so the tolerance the north star allows
 (1e-3 on logits) is not needed; the only documented exception is the double-precision sum order in
-the norm statistics, which has never produced a differing float in any test."""
+the norm statistics: tests/test_gpu_prep.py shows for its rows that no summation order can
+change a float (and requires bit-equality there), and bounds a row where it can."""
 import os
 
 import numpy as np
