@@ -511,6 +511,12 @@ int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, i
  * out = {columns per wave, column-waves per row-group, column groups, row-groups per workgroup, LDS bytes}; 0 = the kernel does not
  * take that shape (the caller's generic path runs).  Lets a CPU test walk every LLaMA shape and row count. */
 int32_t llamahip_debug_set_plan(int32_t m, int32_t k, int32_t interleaved, int32_t n_rows, int32_t epi, int64_t out[5]);
+/* Host-only (no device needed): the launch plan of the single-row decode mat-vec for an m x k Q4_0 matrix (interleaved: the w1|w3 layout)
+ * under prologue `pre` (0 staged Q4_0 operand, 1 plain, 2 norm, 3 SiLU*up, 4 norm with the producer's statistics, 6 norm of a tagged row)
+ * and epilogue `epi` (0 store, 1 +residual, 2 / 7 SiLU*up -> Q4_0 in whole- / half-block workgroups, 5 +residual with tagged rows, 6 store
+ * + greedy pick) -- out = {waves per workgroup, operand granules per thread, ring depth, 1 ring / 0 whole row in flight, grid, LDS bytes}.
+ * Returns 1; 0 = the kernel does not take that (matrix, pre, epi); -1 = the plan names an instance that was never compiled (a defect). */
+int32_t llamahip_debug_gemv_plan(int32_t m, int32_t k, int32_t interleaved, int32_t pre, int32_t epi, int64_t out[6]);
 /* in-kernel phase records of the few-row mat-mul (measurement builds only; 0 records in the product build) */
 int64_t llamahip_debug_set_probe(uint64_t *records, int64_t cap, int32_t reset);
 

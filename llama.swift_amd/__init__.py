@@ -37,6 +37,7 @@ from .binding import (  # noqa: F401
     op_verify_rows,
     qa_to_blocks,
     quantize_file,
+    gemv_plan,
     set_plan,
     version,
 )

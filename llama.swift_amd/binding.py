@@ -167,6 +167,20 @@ def set_plan(m: int, k: int, n_rows: int, epi: int, interleaved: bool = False):
     return tuple(int(x) for x in a) if f(m, k, int(interleaved), n_rows, epi, a.ctypes.data_as(C.c_void_p)) else None
 
 
+def gemv_plan(m: int, k: int, pre: int, epi: int, interleaved: bool = False):
+    """Host-only: the single-row decode mat-vec's launch plan (nw, pg, depth, ring, grid, lds_bytes) for an m x k matrix under a
+    (prologue, epilogue) pair, or None where the kernel does not take it (llamahip_debug_gemv_plan); a plan that names an instance
+    that does not exist is an error."""
+    a = np.zeros(6, np.int64)
+    f = lib().llamahip_debug_gemv_plan
+    f.restype = C.c_int32
+    f.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+    rc = f(m, k, int(interleaved), pre, epi, a.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise LlamaHipError(rc, f"gemv_plan({m}, {k}, pre={pre}, epi={epi}): the plan {a.tolist()} names a kernel instance that does not exist")
+    return tuple(int(x) for x in a) if rc else None
+
+
 def gemm_paths() -> dict:
     """Launch counts of the multi-row mat-mul kernel families since process start (llamahip_debug_gemm_paths)."""
     a = np.zeros(8, np.int64)

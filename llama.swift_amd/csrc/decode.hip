@@ -1891,167 +1891,163 @@ static int pick_depth(int nchunks, int ngroups) {
     return best;
 }
 
-template <int PRE, int EPI, int PG>
-static hipError_t launch_gemv_pg(const QMat &w, int nw, const uint32_t *qa_A, const float *qa_d,
-                                 const float *in0, const float *in1, float *y, const float *resid,
-                                 const uint16_t *T_silu,
-                                 uint32_t *out_A, float *out_d, const NormPart &np, hipStream_t st, const MailboxIO *mb = nullptr) {
-    const int grid = (w.ngroups + nw - 1) / nw;
-    size_t lds = (size_t) w.nchunks * 64 * 4 + (size_t) w.nchunks * 8 * 4 + 32 * sizeof(double);
-    if (PRE == PREP_SILU_MUL) lds += prep_lds_bytes(w.K);      // only the LDS-staged prologues need y scratch
-    lds = (lds + 15) & ~(size_t) 15;
-    GemvArgs ga = { w.tiles, w.ngroups, w.nchunks, w.M, w.gmapF8, qa_A, qa_d, in0, in1, w.K, y, resid, T_silu, out_A, out_d,
-                    (const f64x2 *) np.in, np.n_in, (f64x2 *) np.out, nullptr, 0, 0, g_lut_math };
-    if (mb) {       // a row of a pipeline mailbox on one side of this launch
-        ga.in_t = mb->in_t; ga.resid_t = mb->resid_t; ga.out_t = mb->out_t; ga.slot_in = ga.slot_resid = ga.slot_out = 0;
-        ga.pos_w = mb->pos_w; ga.patience = 3; ga.fault = mb->fault; ga.sync = mb->epoch; ga.lut_math |= mb->test_bits;
+// THE launch rule of the single-row decode mat-vec: which instance of k_gemv an (M x K matrix, prologue, epilogue) gets.  Every launcher,
+// every *_applies predicate, gemv_resid_parts and the attribute set-up below derive from it (and from gemv_kernel, the instances that exist).
+// Workgroup size and prologue register budget PG: fp32 prologues (norm / plain) keep K/4 float4 granules in registers, PRE_QA keeps the
+// nchunks*16 granules of the A array: small budgets (PG 4) keep the kernel near 128 VGPRs so 4 waves per SIMD stay resident; the large
+// budget covers wide rows.
+GemvPlan gemv_plan(const QMat &w, int pre, int epi) {
+    GemvPlan p = { 0, 0, 0, true, 0, 0 };
+    const int need = pre == PRE_QA ? w.nchunks * 16 : w.K / 16;       // operand granules of the row (fp32 prologues: half-block granules, 32 VGPRs each with the norm weight)
+    int nw = 0, pg = 0;
+    if (epi == EPI_SILU_QA || epi == EPI_SILU_QAH) {
+        if (!w.gmapF8 || w.ngroups % 8 != 0 || w.K / 16 > 512) return p;        // the interleaved w1|w3 layout, rows of one register pass
+        if (epi == EPI_SILU_QA) {
+            // 8 waves = 4 gate row-groups + the 4 matching up row-groups
+            if (pre == PRE_QA && need > 512) return p;      // (measurement variant only)
+            nw = 8; pg = 1;
+        } else {
+            // half-block workgroups (see gemv_silu_half_applies): 4 waves, only where the launch takes the 4-deep ring and the row outlasts it
+            if (w.nchunks <= 4 || w.ngroups < 2048) return p;
+            nw = 4; pg = need <= 256 ? 1 : 2;
+        }
+    } else if (pre == PRE_QA) {
+        // Workgroups of ngroups / 256 waves (1, 2 or 4): ONE workgroup per CU where the matrix has fewer than 1024
+        // row-groups.  Measured on the 7B decode step: w2 (512 row-groups) as 256 x 2 waves with the 12-granule operand
+        // budget 7.60 us, as 128 x 4 waves with the 4-granule budget 8.52 us, as 512 x 1 wave 7.99 us; wo as 256 x 2 waves
+        // 5.15 us against 5.41 us as 512 x 1 (profiles/r02_d_small_matvec_ab.txt).  The operand budget (4 or 12 granules
+        // of 16 B per thread) follows from the workgroup size, not the other way round.
+        nw = w.ngroups >= 1024 ? 4 : w.ngroups >= 512 ? 2 : 1;
+        while (!(pg = need <= 4 * nw * 64 ? 4 : need <= 12 * nw * 64 ? 12 : 0) && nw < 4) nw *= 2;
+        if (!pg) return p;
+    } else if (pre == PREP_SILU_MUL) {
+        nw = pick_waves(w.ngroups); pg = 1;     // (LDS-staged prologue: no register budget to fit)
+    } else {
+        nw = pick_waves(w.ngroups);
+        while (nw < 4 && need > nw * 64) nw *= 2;
+        pg = need <= nw * 64 ? 1 : need <= 2 * nw * 64 ? 2 : 0;
+        if (!pg) return p;          // caller falls back to the unfused path
     }
-#define LH_GO(D, RING) hipLaunchKernelGGL((k_gemv<PRE, EPI, D, RING, PG>), dim3(grid), dim3(nw * 64), lds + ((LH_GEMV_PAD && (RING)) ? (D) * 288 : 0), st, ga)
-    if (np.out && grid > NORM_PART_MAX) return hipErrorInvalidValue;
     // rows that fit 16 slots: whole row in flight (latency-bound small matrices) unless the launch
     // already has >= 4 waves per CU, where an 8-deep ring saves 48 VGPRs and keeps 4 waves/SIMD resident
-    if (w.nchunks <= 16 && !(w.nchunks == 16 && w.ngroups >= 1024)) {
-        LH_GO(16, false);
-    } else {
-        switch (pick_depth(w.nchunks, w.ngroups)) {
-            case 4:  LH_GO(4, true); break;
-            case 8:  LH_GO(8, true); break;
-            case 10: LH_GO(10, true); break;
-            case 14: LH_GO(14, true); break;
-            case 18: LH_GO(18, true); break;
-            case 22: LH_GO(22, true); break;
-            default: LH_GO(16, true); break;
+    p.ring = epi == EPI_SILU_QAH || w.nchunks > 16 || (w.nchunks == 16 && w.ngroups >= 1024);
+    p.depth = p.ring ? pick_depth(w.nchunks, w.ngroups) : 16;
+    // the lm head's pick epilogue is written for 256 threads and instantiated for the shallow rings (every LLaMA lm head)
+    if (epi == EPI_STORE_PICK && (nw != 4 || !p.ring || (p.depth != 4 && p.depth != 8 && p.depth != 10))) return p;
+    p.grid = epi == EPI_SILU_QAH ? (w.ngroups / 8 + 7) / 8 * 16        // two halves per block, blocks of one XCD 16 apart
+                                 : (w.ngroups + nw - 1) / nw;
+    p.lds = (size_t) w.nchunks * 64 * 4 + (size_t) w.nchunks * 8 * 4 + 32 * sizeof(double);
+    if (pre == PREP_SILU_MUL) p.lds += prep_lds_bytes(w.K);      // only the LDS-staged prologues need y scratch
+    p.lds = ((p.lds + 15) & ~(size_t) 15) + ((LH_GEMV_PAD && p.ring) ? (size_t) p.depth * 288 : 0);
+    p.nw = nw; p.pg = pg;
+    return p;
+}
+
+// The instances of k_gemv<PRE, EPI, ., ., PG>: run-time (ring depth, ring or whole row in flight) -> the kernel, null where there is none
+using GemvKernel = void (*)(const GemvArgs);
+template <int PRE, int EPI, int PG>
+static GemvKernel gemv_kernel_at(int depth, bool ring) {
+    constexpr bool ALL = EPI != EPI_STORE_PICK && EPI != EPI_SILU_QAH;      // (those two: rings only, the shallow ones)
+    if (!ring) {
+        if constexpr (ALL) if (depth == 16) return k_gemv<PRE, EPI, 16, false, PG>;
+        return nullptr;
+    }
+    if (depth == 4) return k_gemv<PRE, EPI, 4, true, PG>;
+    if constexpr (EPI != EPI_SILU_QAH) {
+        if (depth == 8) return k_gemv<PRE, EPI, 8, true, PG>;
+        if (depth == 10) return k_gemv<PRE, EPI, 10, true, PG>;
+        if constexpr (ALL) {
+            if (depth == 14) return k_gemv<PRE, EPI, 14, true, PG>;
+            if (depth == 16) return k_gemv<PRE, EPI, 16, true, PG>;
+            if (depth == 18) return k_gemv<PRE, EPI, 18, true, PG>;
+            if (depth == 22) return k_gemv<PRE, EPI, 22, true, PG>;
         }
     }
-#undef LH_GO
+    return nullptr;
+}
+template <int PRE, int EPI, int PG0, int PG1 = 0>
+static GemvKernel gemv_kernel_pg(const GemvPlan &p) {
+    if (p.pg == PG0) return gemv_kernel_at<PRE, EPI, PG0>(p.depth, p.ring);
+    if constexpr (PG1 != 0) if (p.pg == PG1) return gemv_kernel_at<PRE, EPI, PG1>(p.depth, p.ring);
+    return nullptr;
+}
+// ... and the (prologue, epilogue, budget) combinations that exist: only the pairs the forward pass uses are instantiated
+static GemvKernel gemv_kernel(int pre, int epi, const GemvPlan &p) {
+    if (pre == PRE_QA && epi == EPI_STORE)             return gemv_kernel_pg<PRE_QA, EPI_STORE, 4, 12>(p);
+    if (pre == PRE_QA && epi == EPI_RESID)             return gemv_kernel_pg<PRE_QA, EPI_RESID, 4, 12>(p);
+    if (pre == PRE_QA && epi == EPI_RESID_TAG)         return gemv_kernel_pg<PRE_QA, EPI_RESID_TAG, 4, 12>(p);
+    if (pre == PRE_QA && epi == EPI_SILU_QA)           return gemv_kernel_pg<PRE_QA, EPI_SILU_QA, 1>(p);          // llamahip_bench_gemv variant
+    if (pre == PREP_NORM && epi == EPI_STORE)          return gemv_kernel_pg<PREP_NORM, EPI_STORE, 1, 2>(p);
+    if (pre == PREP_NORM && epi == EPI_SILU_QA)        return gemv_kernel_pg<PREP_NORM, EPI_SILU_QA, 1>(p);
+    if (pre == PREP_NORM && epi == EPI_SILU_QAH)       return gemv_kernel_pg<PREP_NORM, EPI_SILU_QAH, 1, 2>(p);
+    if (pre == PREP_NORM && epi == EPI_STORE_PICK)     return gemv_kernel_pg<PREP_NORM, EPI_STORE_PICK, 1, 2>(p);
+    if (pre == PREP_NORMP && epi == EPI_STORE)         return gemv_kernel_pg<PREP_NORMP, EPI_STORE, 1, 2>(p);
+    if (pre == PREP_NORMP && epi == EPI_SILU_QA)       return gemv_kernel_pg<PREP_NORMP, EPI_SILU_QA, 1>(p);
+    if (pre == PREP_NORMP && epi == EPI_SILU_QAH)      return gemv_kernel_pg<PREP_NORMP, EPI_SILU_QAH, 1, 2>(p);
+    if (pre == PREP_NORMP && epi == EPI_STORE_PICK)    return gemv_kernel_pg<PREP_NORMP, EPI_STORE_PICK, 1, 2>(p);
+    if (pre == PREP_NORM_TAG && epi == EPI_STORE)      return gemv_kernel_pg<PREP_NORM_TAG, EPI_STORE, 1, 2>(p);
+    if (pre == PREP_PLAIN && epi == EPI_RESID)         return gemv_kernel_pg<PREP_PLAIN, EPI_RESID, 1, 2>(p);
+    if (pre == PREP_SILU_MUL && epi == EPI_RESID)      return gemv_kernel_pg<PREP_SILU_MUL, EPI_RESID, 1>(p);
+    return nullptr;
+}
+bool gemv_plan_has_kernel(int pre, int epi, const GemvPlan &p) { return p.nw && gemv_kernel(pre, epi, p); }
+int gemv_resid_parts(const QMat &w) { return gemv_plan(w, PRE_QA, EPI_RESID).grid; }      // 0: the kernel does not take w
+
+// LLAMAHIP_NORM_MODE (measurement only), read here and nowhere else: 0 = the reference's two-pass statistics in the prologue, 1 = one-pass
+// statistics in the prologue, 2 (default) = statistics handed over by the producer where the caller offers them.  Resolves a launch's
+// (prologue, NormPart) to the prologue to launch -- PREP_NORM with usable partial sums becomes PREP_NORMP -- and to the kernel's
+// part_in / npart (np->in / np->n_in; n_in -1: two-pass).  Returns whether the mode is the default; pre == null asks that alone.
+bool norm_mode_resolve(int *pre, NormPart *np) {
+    static const int norm_mode = [] { const char *e = getenv("LLAMAHIP_NORM_MODE"); return e ? atoi(e) : 2; }();
+    if (pre) {
+        if (norm_mode < 2) *np = NormPart();
+        if (*pre == PREP_NORM && np->in && np->n_in > 0 && np->n_in <= NORM_PART_MAX) *pre = PREP_NORMP;
+        else { np->in = nullptr; np->n_in = norm_mode == 0 ? -1 : 0; }
+    }
+    return norm_mode >= 2;
+}
+
+// Every launcher of k_gemv: `ga` arrives with the operands; the statistics, the mailbox, the matrix and the plan are filled in here
+static hipError_t launch_gemv_plan(const QMat &w, int pre, int epi, const NormPart *npp, const MailboxIO *mb, GemvArgs ga, hipStream_t st) {
+    NormPart np = npp ? *npp : NormPart();
+    norm_mode_resolve(&pre, &np);
+    if (mb) {
+        // pipeline mailbox on one side of the launch: the row arrives tagged (first layer's wq|wk|wv; its wo takes the residual from
+        // the same granules) or leaves tagged (last layer's w2)
+        if (mb->in_t && (pre == PREP_NORM || pre == PREP_NORMP) && epi == EPI_STORE) pre = PREP_NORM_TAG;
+        else if ((mb->resid_t || mb->out_t) && pre == PRE_QA && epi == EPI_RESID) epi = EPI_RESID_TAG;
+        else return hipErrorInvalidValue;
+        ga.in_t = mb->in_t; ga.resid_t = mb->resid_t; ga.out_t = mb->out_t;
+        ga.pos_w = mb->pos_w; ga.patience = 3; ga.fault = mb->fault; ga.sync = mb->epoch; ga.lut_math = mb->test_bits;
+    }
+    const GemvPlan p = gemv_plan(w, pre, epi);
+    const GemvKernel k = gemv_kernel(pre, epi, p);
+    if (!p.nw || !k || (np.out && p.grid > NORM_PART_MAX)) return hipErrorInvalidValue;
+    ga.wt = w.tiles; ga.ngroups = w.ngroups; ga.nchunks = w.nchunks; ga.M = w.M; ga.gmapF8 = w.gmapF8; ga.K = w.K;
+    ga.part_in = (const f64x2 *) np.in; ga.npart = np.n_in; ga.part_out = (f64x2 *) np.out;
+    ga.lut_math |= g_lut_math;
+    hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.nw * 64), p.lds, st, ga);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
 
-// Workgroup size and prologue register budget.  fp32 prologues (norm / plain) keep K/4 float4
-// granules in registers, PRE_QA keeps the nchunks*16 granules of the A array: small budgets (PG 4)
-// keep the kernel near 128 VGPRs so 4 waves per SIMD stay resident; the large budget covers wide rows.
-// workgroup size of the decode mat-vec for a (prologue, matrix) pair -- also what sizes the partial-sum
-// array an EPI_RESID launch writes (gemv_resid_parts)
-static int gemv_pick_nw_qa(const QMat &w, int *pg) {
-    // Workgroups of ngroups / 256 waves (1, 2 or 4): ONE workgroup per CU where the matrix has fewer than 1024
-    // row-groups.  Measured on the 7B decode step: w2 (512 row-groups) as 256 x 2 waves with the 12-granule operand
-    // budget 7.60 us, as 128 x 4 waves with the 4-granule budget 8.52 us, as 512 x 1 wave 7.99 us; wo as 256 x 2 waves
-    // 5.15 us against 5.41 us as 512 x 1 (profiles/r02_d_small_matvec_ab.txt).  The operand budget (4 or 12 granules
-    // of 16 B per thread) follows from the workgroup size, not the other way round.
-    int nw = w.ngroups >= 1024 ? 4 : w.ngroups >= 512 ? 2 : 1;
-    const int need = w.nchunks * 16;
-    for (; nw <= 4; nw *= 2) {
-        if (need <= 4 * nw * 64) { *pg = 4; return nw; }
-        if (need <= 12 * nw * 64) { *pg = 12; return nw; }
-    }
-    *pg = 0;
-    return 0;
-}
-int gemv_resid_parts(const QMat &w) {
-    int pg = 0;
-    const int nw = gemv_pick_nw_qa(w, &pg);
-    return nw ? (w.ngroups + nw - 1) / nw : 0;
-}
-
-template <int PRE, int EPI>
-static hipError_t launch_gemv_t(const QMat &w, const uint32_t *qa_A, const float *qa_d,
-                                const float *in0, const float *in1, float *y, const float *resid,
-                                const uint16_t *T_silu,
-                                uint32_t *out_A, float *out_d, const NormPart &np, hipStream_t st, const MailboxIO *mb = nullptr) {
-#define LH_PGARGS w, nw, qa_A, qa_d, in0, in1, y, resid, T_silu, out_A, out_d, np, st, mb
-    if constexpr (EPI == EPI_SILU_QA) {
-        // 8 waves = 4 gate row-groups + the 4 matching up row-groups (interleaved layout)
-        const int nw = 8;
-        if (!w.gmapF8 || w.ngroups % 8 != 0 || w.K / 16 > 1 * 512) return hipErrorInvalidValue;
-        if (PRE == PRE_QA && w.nchunks * 16 > 512) return hipErrorInvalidValue;      // (measurement variant only)
-        return launch_gemv_pg<PRE, EPI, 1>(LH_PGARGS);
-    } else if constexpr (PRE == PREP_SILU_MUL) {
-        const int nw = pick_waves(w.ngroups);
-        return launch_gemv_pg<PRE, EPI, 1>(LH_PGARGS);
-    } else {
-        int nw = pick_waves(w.ngroups);
-        if constexpr (PRE == PRE_QA) {
-            int pg = 0;
-            nw = gemv_pick_nw_qa(w, &pg);
-            if (np.out && (w.ngroups + std::max(nw, 1) - 1) / std::max(nw, 1) > NORM_PART_MAX) return hipErrorInvalidValue;
-            if (pg == 4) return launch_gemv_pg<PRE, EPI, 4>(LH_PGARGS);
-            if (pg == 12) return launch_gemv_pg<PRE, EPI, 12>(LH_PGARGS);
-        } else {
-            const int need = w.K / 16;            // half-block granules (32 VGPRs each with the norm weight)
-            while (nw < 4 && need > 1 * nw * 64) nw *= 2;
-            if (need <= 1 * nw * 64) return launch_gemv_pg<PRE, EPI, 1>(LH_PGARGS);
-            if (need <= 2 * nw * 64) return launch_gemv_pg<PRE, EPI, 2>(LH_PGARGS);
-        }
-        return hipErrorInvalidValue;          // caller falls back to the unfused path
-    }
-#undef LH_PGARGS
-}
-
-static size_t gemv_lds_bytes(const QMat &w, int depth_pad) {
-    size_t lds = (size_t) w.nchunks * 64 * 4 + (size_t) w.nchunks * 8 * 4 + 32 * sizeof(double);
-    lds = (lds + 15) & ~(size_t) 15;
-    return lds + (LH_GEMV_PAD ? (size_t) depth_pad * 288 : 0);
-}
 hipError_t launch_gemv(const QMat &w, int pre, int epi, const uint32_t *qa_A, const float *qa_d,
                        const float *in0, const float *in1, float *y, const float *resid,
                        const uint16_t *T_silu,
-                       uint32_t *out_A, float *out_d, hipStream_t st, const NormPart *npp, const MailboxIO *mb) {
-    // LLAMAHIP_NORM_MODE (measurement only): 0 = the reference's two-pass statistics in the prologue, 1 = one-pass
-    // statistics in the prologue, 2 (default) = statistics handed over by the producer where the caller offers them
-    static const int norm_mode = getenv("LLAMAHIP_NORM_MODE") ? atoi(getenv("LLAMAHIP_NORM_MODE")) : 2;
-    NormPart np = npp ? *npp : NormPart();
-    if (norm_mode < 2) np = NormPart();
-    if (pre == PREP_NORM && np.in && np.n_in > 0 && np.n_in <= NORM_PART_MAX) pre = PREP_NORMP;
-    else { np.in = nullptr; np.n_in = norm_mode == 0 ? -1 : 0; }
-    // pipeline mailbox on one side of the launch: the row arrives tagged (first layer's wq|wk|wv; its wo takes the residual from
-    // the same granules) or leaves tagged (last layer's w2)
-    if (mb && mb->in_t && (pre == PREP_NORM || pre == PREP_NORMP) && epi == EPI_STORE) return launch_gemv_t<PREP_NORM_TAG, EPI_STORE>(w, qa_A, qa_d, in0, in1, y, resid, T_silu, out_A, out_d, np, st, mb);
-    if (mb && (mb->resid_t || mb->out_t) && pre == PRE_QA && epi == EPI_RESID) return launch_gemv_t<PRE_QA, EPI_RESID_TAG>(w, qa_A, qa_d, in0, in1, y, resid, T_silu, out_A, out_d, np, st, mb);
-    if (mb) return hipErrorInvalidValue;
-#define LH_ARGS w, qa_A, qa_d, in0, in1, y, resid, T_silu, out_A, out_d, np, st
-    // only the (prologue, epilogue) pairs the forward pass uses are instantiated
-    if (pre == PRE_QA && epi == EPI_STORE)        return launch_gemv_t<PRE_QA, EPI_STORE>(LH_ARGS);
-    if (pre == PRE_QA && epi == EPI_RESID)        return launch_gemv_t<PRE_QA, EPI_RESID>(LH_ARGS);
-    if (pre == PREP_NORM && epi == EPI_STORE)     return launch_gemv_t<PREP_NORM, EPI_STORE>(LH_ARGS);
-    if (pre == PREP_NORM && epi == EPI_SILU_QA)   return launch_gemv_t<PREP_NORM, EPI_SILU_QA>(LH_ARGS);
-    if (pre == PREP_NORMP && epi == EPI_STORE)    return launch_gemv_t<PREP_NORMP, EPI_STORE>(LH_ARGS);
-    if (pre == PREP_NORMP && epi == EPI_SILU_QA)  return launch_gemv_t<PREP_NORMP, EPI_SILU_QA>(LH_ARGS);
-    if (pre == PRE_QA && epi == EPI_SILU_QA)      return launch_gemv_t<PRE_QA, EPI_SILU_QA>(LH_ARGS);        // llamahip_bench_gemv variant
-    if (pre == PREP_PLAIN && epi == EPI_RESID)    return launch_gemv_t<PREP_PLAIN, EPI_RESID>(LH_ARGS);
-    if (pre == PREP_SILU_MUL && epi == EPI_RESID) return launch_gemv_t<PREP_SILU_MUL, EPI_RESID>(LH_ARGS);
-#undef LH_ARGS
-    return hipErrorInvalidValue;
+                       uint32_t *out_A, float *out_d, hipStream_t st, const NormPart *np, const MailboxIO *mb) {
+    if (pre == PREP_NORM_TAG || epi >= EPI_STORE_TAG) return hipErrorInvalidValue;      // (selected by a mailbox / launchers of their own)
+    GemvArgs ga = {};
+    ga.qa_A = qa_A; ga.qa_d = qa_d; ga.in0 = in0; ga.in1 = in1; ga.y = y; ga.resid = resid; ga.T_silu = T_silu; ga.out_A = out_A; ga.out_d = out_d;
+    return launch_gemv_plan(w, pre, epi, np, mb, ga, st);
 }
 
-
+// the lm head with the pick epilogue (EPI_STORE_PICK, llamahip_internal.h)
+bool gemv_pick_applies(const QMat &w) { return gemv_plan(w, PREP_NORM, EPI_STORE_PICK).nw != 0; }
 hipError_t launch_gemv_pick(const QMat &w, const float *in0, const float *in1, float *y, const uint16_t *T_silu, hipStream_t st,
-                            const NormPart *npp, const PickIO &pick) {
-    static const int norm_mode = getenv("LLAMAHIP_NORM_MODE") ? atoi(getenv("LLAMAHIP_NORM_MODE")) : 2;
-    NormPart np = npp ? *npp : NormPart();
-    const bool normp = norm_mode >= 2 && np.in && np.n_in > 0 && np.n_in <= NORM_PART_MAX;
-    if (!normp) { np.in = nullptr; np.n_in = norm_mode == 0 ? -1 : 0; }
-    // the workgroup shape of launch_gemv_t's fp32 prologues; the embedding in the epilogue is written for 256 threads
-    int nw = pick_waves(w.ngroups);
-    const int need = w.K / 16;
-    while (nw < 4 && need > nw * 64) nw *= 2;
-    const int pg = need <= nw * 64 ? 1 : need <= 2 * nw * 64 ? 2 : 0;
-    if (nw != 4 || !pg || (w.nchunks <= 16 && !(w.nchunks == 16 && w.ngroups >= 1024))) return hipErrorInvalidValue;      // (the caller checks gemv_pick_applies)
-    const int D = pick_depth(w.nchunks, w.ngroups);
-    const int grid = (w.ngroups + nw - 1) / nw;
-    size_t lds = (size_t) w.nchunks * 64 * 4 + (size_t) w.nchunks * 8 * 4 + 32 * sizeof(double);
-    lds = ((lds + 15) & ~(size_t) 15) + (size_t) D * 288;
-    GemvArgs ga = { w.tiles, w.ngroups, w.nchunks, w.M, w.gmapF8, nullptr, nullptr, in0, in1, w.K, y, nullptr, T_silu, nullptr, nullptr,
-                    (const f64x2 *) np.in, np.n_in, nullptr, nullptr, 0, 0, g_lut_math };
-    ga.pick = pick;
-#define LH_GOP(PRE, DD, PG) hipLaunchKernelGGL((k_gemv<PRE, EPI_STORE_PICK, DD, true, PG>), dim3(grid), dim3(nw * 64), lds, st, ga)
-#define LH_GOPD(PRE, PG) { if (D == 4) LH_GOP(PRE, 4, PG); else if (D == 8) LH_GOP(PRE, 8, PG); else if (D == 10) LH_GOP(PRE, 10, PG); else return hipErrorInvalidValue; }
-    if (normp) { if (pg == 1) LH_GOPD(PREP_NORMP, 1) else LH_GOPD(PREP_NORMP, 2) }
-    else { if (pg == 1) LH_GOPD(PREP_NORM, 1) else LH_GOPD(PREP_NORM, 2) }
-#undef LH_GOPD
-#undef LH_GOP
-    LH_LAUNCH_CHECK();
-    return hipSuccess;
+                            const NormPart *np, const PickIO &pick) {
+    GemvArgs ga = {};
+    ga.in0 = in0; ga.in1 = in1; ga.y = y; ga.T_silu = T_silu; ga.pick = pick;
+    return launch_gemv_plan(w, PREP_NORM, EPI_STORE_PICK, np, nullptr, ga, st);      // (the caller checks gemv_pick_applies)
 }
 // w1|w3 in half-block workgroups (EPI_SILU_QAH, llamahip_internal.h)
 // (QUARTER-block workgroups of two waves -- VERDICT r04 item 4c: 13B's 432 blocks would go from max / mean 1.19 to 1.04 workgroups per CU --
@@ -2062,7 +2058,7 @@ bool gemv_silu_half_applies(const QMat &w) {
     static const bool off = getenv("LLAMAHIP_NO_W13_HALF") != nullptr;
     static const bool force = getenv("LLAMAHIP_W13_HALF") && atoi(getenv("LLAMAHIP_W13_HALF")) == 1;      // tests: shapes the balance rule leaves with block workgroups
     static const int ncu = [] { int dev = 0; hipDeviceProp_t p; return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256; }();
-    if (off || !w.gmapF8 || w.ngroups % 8 != 0 || w.K / 16 > 512 || w.nchunks <= 4 || pick_depth(w.nchunks, w.ngroups) != 4 || w.ngroups < 2048) return false;
+    if (off || !gemv_plan(w, PREP_NORM, EPI_SILU_QAH).nw) return false;
     if (force) return true;
     // halves only where they leave the busiest CU relatively less to stream than whole blocks do: max / mean workgroups per CU
     // (7B: 344 blocks 2 / 1.34 = 1.49 against 688 halves 3 / 2.69 = 1.12; 13B 432 / 864 and 65B 688 / 1 376: equal, blocks stay)
@@ -2071,36 +2067,12 @@ bool gemv_silu_half_applies(const QMat &w) {
     return r_halves < r_blocks - 0.02;
 }
 hipError_t launch_gemv_silu_half(const QMat &w, const float *in0, const float *in1, const uint16_t *T_silu, uint32_t *out_A, float *out_d, hipStream_t st,
-                                 const NormPart *npp, uint64_t *amax_t, uint32_t *epoch, int layer, uint32_t *fault) {
-    static const int norm_mode = getenv("LLAMAHIP_NORM_MODE") ? atoi(getenv("LLAMAHIP_NORM_MODE")) : 2;
+                                 const NormPart *np, uint64_t *amax_t, uint32_t *epoch, int layer, uint32_t *fault) {
     static const int fault_test = (getenv("LLAMAHIP_HANDOFF_FAULT_TEST") && atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) == 6) ? 0x1000 : 0;
-    NormPart np = npp ? *npp : NormPart();
-    const bool normp = norm_mode >= 2 && np.in && np.n_in > 0 && np.n_in <= NORM_PART_MAX;
-    if (!normp) { np.in = nullptr; np.n_in = norm_mode == 0 ? -1 : 0; }
-    const int nblocks = w.ngroups / 8, grid = (nblocks + 7) / 8 * 16;       // two halves per block, blocks of one XCD 16 apart
-    const int need = w.K / 16, pg = need <= 256 ? 1 : 2;
-    size_t lds = (size_t) w.nchunks * 64 * 4 + (size_t) w.nchunks * 8 * 4 + 32 * sizeof(double);
-    lds = ((lds + 15) & ~(size_t) 15) + (size_t) 4 * 288;
-    GemvArgs ga = { w.tiles, w.ngroups, w.nchunks, w.M, w.gmapF8, nullptr, nullptr, in0, in1, w.K, nullptr, nullptr, T_silu, out_A, out_d,
-                    (const f64x2 *) np.in, np.n_in, nullptr, epoch, 0, layer, g_lut_math | fault_test, fault };
-    ga.out_t = amax_t;
-#define LH_GOH(PRE, PG) hipLaunchKernelGGL((k_gemv<PRE, EPI_SILU_QAH, 4, true, PG>), dim3(grid), dim3(256), lds, st, ga)
-    if (normp) { if (pg == 1) LH_GOH(PREP_NORMP, 1); else LH_GOH(PREP_NORMP, 2); }
-    else { if (pg == 1) LH_GOH(PREP_NORM, 1); else LH_GOH(PREP_NORM, 2); }
-#undef LH_GOH
-    LH_LAUNCH_CHECK();
-    return hipSuccess;
-}
-
-// the shapes launch_gemv_pick is instantiated for (ring kernels with 4-wave workgroups: every LLaMA lm head)
-bool gemv_pick_applies(const QMat &w) {
-    int nw = pick_waves(w.ngroups);
-    const int need = w.K / 16;
-    while (nw < 4 && need > nw * 64) nw *= 2;
-    const int pg = need <= nw * 64 ? 1 : need <= 2 * nw * 64 ? 2 : 0;
-    if (nw != 4 || !pg || (w.nchunks <= 16 && !(w.nchunks == 16 && w.ngroups >= 1024))) return false;
-    const int D = pick_depth(w.nchunks, w.ngroups);
-    return D == 4 || D == 8 || D == 10;
+    GemvArgs ga = {};
+    ga.in0 = in0; ga.in1 = in1; ga.T_silu = T_silu; ga.out_A = out_A; ga.out_d = out_d;
+    ga.sync = epoch; ga.sync_epoch = layer; ga.lut_math = fault_test; ga.fault = fault; ga.out_t = amax_t;
+    return launch_gemv_plan(w, PREP_NORM, EPI_SILU_QAH, np, nullptr, ga, st);      // (the caller checks gemv_silu_half_applies)
 }
 
 // Short prompt chunk (see k_decn_scores): scores -> soft_max + V*P + ordered combine + Q4_0 quantization of the
@@ -2240,59 +2212,59 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
     return hipSuccess;
 }
 
-// wq|wk|wv mat-vec + decode attention in ONE launch (k_qkv_attn).  Applies to the shapes its mat-vec role is instantiated
-// for (the 8-deep ring, 4-wave, one-granule variant: K = 4096) and head layouts whose workgroups line up with heads.
-// the mat-vec role of k_qkv_attn is instantiated for (ring depth, granules per thread) = (8, 1) [7B], (10, 2) [13B], (4, 2) [65B]:
-// what launch_gemv_t / launch_gemv_pg pick for wq|wk|wv of those models; returns 0 when the shape takes another variant
-static int qkv_attn_variant(const QMat &w) {
-    int nw = pick_waves(w.ngroups);
-    const int need = w.K / 16;                  // as launch_gemv_t
-    while (nw < 4 && need > nw * 64) nw *= 2;
-    if (nw != 4) return 0;
-    const int pg = need <= 256 ? 1 : need <= 512 ? 2 : 0;
-    if (!pg || (w.nchunks <= 16 && !(w.nchunks == 16 && w.ngroups >= 1024))) return 0;          // (whole-row-in-flight variant: small models)
-    const int D = pick_depth(w.nchunks, w.ngroups);
-    if (D == 8 && pg == 1) return 1;
-    if (D == 10 && pg == 2) return 2;
-    if (D == 4 && pg == 2) return 3;
-    return 0;
+// wq|wk|wv mat-vec + decode attention in ONE launch (k_qkv_attn).  Its mat-vec role is gemv_plan's answer for (PREP_NORM, EPI_STORE) where
+// that is a 4-wave ring of (ring depth, granules per thread) = (8, 1) [7B], (10, 2) [13B], (4, 2) [30B, 65B] -- the instances below; other
+// shapes (the whole-row-in-flight variant of small models among them) keep the separate launches.
+using QkvAttnKernel = void (*)(const GemvArgs, const AttnXArgs, const int, const int);
+template <int PRE>
+static QkvAttnKernel qkv_attn_kernel_at(int depth, int pg) {
+    if (depth == 8 && pg == 1) return k_qkv_attn<PRE, 8, 1>;
+    if (depth == 10 && pg == 2) return k_qkv_attn<PRE, 10, 2>;
+    if (depth == 4 && pg == 2) return k_qkv_attn<PRE, 4, 2>;
+    return nullptr;
+}
+static QkvAttnKernel qkv_attn_kernel(int pre, int depth, int pg) {
+    return pre == PREP_NORM ? qkv_attn_kernel_at<PREP_NORM>(depth, pg) : pre == PREP_NORMP ? qkv_attn_kernel_at<PREP_NORMP>(depth, pg)
+         : pre == PREP_NORM_TAG ? qkv_attn_kernel_at<PREP_NORM_TAG>(depth, pg) : nullptr;
+}
+static GemvPlan qkv_attn_plan(const QMat &w) {
+    GemvPlan p = gemv_plan(w, PREP_NORM, EPI_STORE);
+    if (p.nw != 4 || !p.ring || !qkv_attn_kernel(PREP_NORM, p.depth, p.pg)) p.nw = 0;
+    return p;
 }
 bool qkv_attn_applies(const QMat &w, int d, int H, int nth) {
     static const bool off = getenv("LLAMAHIP_NO_QKV_ATTN") != nullptr;
     if (off || H % 8 != 0 || d % H != 0) return false;
     const int dh = d / H;
-    if (dh % 32 != 0 || dh > 256 || nth > 8 || w.gmapF8 || w.M != 3 * d || w.K != d || w.ngroups != 3 * d / 8) return false;
-    return qkv_attn_variant(w) != 0;
+    if (dh % 32 != 0 || dh > 256 || nth > 8 || w.gmapF8 || w.M != 3 * d || w.K != d || w.ngroups != 3 * d / 8) return false;        // head layouts whose workgroups line up with heads
+    return qkv_attn_plan(w).nw != 0;
 }
-hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, const NormPart &np, uint64_t *qkv2, uint64_t *sc2, uint32_t *epoch, int layer,
+hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, const NormPart &npp, uint64_t *qkv2, uint64_t *sc2, uint32_t *epoch, int layer,
                            int d, int H, int n_ctx, int nth, const double *tab, float *Kc, float *Vc, float *merged, uint32_t *qa_A, float *qa_d,
                            const uint16_t *T_silu, const uint16_t *T_exp, const int32_t *state, uint32_t *fault, hipStream_t st,
                            const MailboxIO *mb) {
     const uint64_t *x_t = mb ? mb->in_t : nullptr;
     // x_t (first layer of a pipeline stage fed through a device-side mailbox): the input row arrives as tagged granules, slot 0
-    const int dh = d / H, nsl = (n_ctx + DEC_TS - 1) / DEC_TS, gridA = w.ngroups / 4;
+    const GemvPlan p = qkv_attn_plan(w);
+    NormPart np = npp;
+    int pre = x_t ? PREP_NORM_TAG : PREP_NORM;
+    norm_mode_resolve(&pre, &np);
+    const QkvAttnKernel k = qkv_attn_kernel(pre, p.depth, p.pg);
+    if (!p.nw || !k) return hipErrorInvalidValue;
+    const int dh = d / H, nsl = (n_ctx + DEC_TS - 1) / DEC_TS, gridA = p.grid;
     const float kq_scale = 1.0f / sqrtf((float) d / (float) H);          // .mm:620
-    static const int norm_mode = getenv("LLAMAHIP_NORM_MODE") ? atoi(getenv("LLAMAHIP_NORM_MODE")) : 2;      // as launch_gemv
-    const bool normp = norm_mode >= 2 && np.in && np.n_in > 0 && np.n_in <= NORM_PART_MAX;
-    const int variant = qkv_attn_variant(w);
-    const size_t lds_mv = gemv_lds_bytes(w, variant == 1 ? 8 : variant == 2 ? 10 : 4);
     const size_t lds_pv = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
-    const size_t lds = std::max(std::max(lds_mv, lds_pv), (size_t) 2 * dh * sizeof(float));
+    const size_t lds = std::max(std::max(p.lds, lds_pv), (size_t) 2 * dh * sizeof(float));
     // the mat-vec role writes tagged granules: y -> qkv2, sync -> the epoch word, sync_epoch = layer
     // test only (tests/test_gpu_parity.py): the mat-vec role publishes a wrong tag and every poll gives up after 256 looks -> the
     // sticky fault word must come back as an error
     static const int fault_test = (getenv("LLAMAHIP_HANDOFF_FAULT_TEST") && atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) < 2) ? 0x1000 : 0;     // (2: the wo launch of the overlapped schedule misbehaves instead)
     GemvArgs ga = { w.tiles, w.ngroups, w.nchunks, w.M, w.gmapF8, nullptr, nullptr, x, norm_w, w.K, (float *) qkv2, nullptr, T_silu, nullptr, nullptr,
-                    (const f64x2 *) (normp ? np.in : nullptr), normp ? np.n_in : (norm_mode == 0 ? -1 : 0), nullptr, epoch, 0, layer, g_lut_math | fault_test, fault };
-    if (x_t) { ga.in_t = x_t; ga.slot_in = 0; ga.part_in = nullptr; ga.npart = norm_mode == 0 ? -1 : 0; ga.pos_w = mb->pos_w; ga.patience = 3; ga.lut_math |= mb->test_bits; }
+                    (const f64x2 *) np.in, np.n_in, nullptr, epoch, 0, layer, g_lut_math | fault_test, fault };
+    if (x_t) { ga.in_t = x_t; ga.slot_in = 0; ga.pos_w = mb->pos_w; ga.patience = 3; ga.lut_math |= mb->test_bits; }
     const AttnXArgs aa = { nullptr, d, dh, tab, Kc, Vc, nullptr, n_ctx, nth, kq_scale, merged, qa_A, qa_d, T_exp, state, nullptr, fault, g_lut_math | fault_test,
                            qkv2, sc2, epoch, layer };
-    const int grid = gridA + H * (nsl + dh / 32);
-#define LH_GOX(D, PG) { if (x_t) hipLaunchKernelGGL((k_qkv_attn<PREP_NORM_TAG, D, PG>), dim3(grid), dim3(256), lds, st, ga, aa, gridA, H); \
-                        else if (normp) hipLaunchKernelGGL((k_qkv_attn<PREP_NORMP, D, PG>), dim3(grid), dim3(256), lds, st, ga, aa, gridA, H); \
-                        else hipLaunchKernelGGL((k_qkv_attn<PREP_NORM, D, PG>), dim3(grid), dim3(256), lds, st, ga, aa, gridA, H); }
-    if (variant == 1) LH_GOX(8, 1) else if (variant == 2) LH_GOX(10, 2) else if (variant == 3) LH_GOX(4, 2) else return hipErrorInvalidValue;
-#undef LH_GOX
+    hipLaunchKernelGGL(k, dim3(gridA + H * (nsl + dh / 32)), dim3(256), lds, st, ga, aa, gridA, H);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -2541,24 +2513,19 @@ hipError_t init_kernel_attrs() {
 
 hipError_t init_attrs_decode() {
     const int cap = 160 * 1024;          // fused prologues / wide rows need more than the default 64 KB of dynamic LDS
-#define LH_ATTR(KERNEL) do { hipError_t e_ = hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, cap); if (e_ != hipSuccess) return e_; } while (0)
-#define LH_ATTR_G1(PRE, EPI, PG) LH_ATTR((k_gemv<PRE, EPI, 16, false, PG>)); LH_ATTR((k_gemv<PRE, EPI, 16, true, PG>)); LH_ATTR((k_gemv<PRE, EPI, 22, true, PG>)); \
-    LH_ATTR((k_gemv<PRE, EPI, 18, true, PG>)); LH_ATTR((k_gemv<PRE, EPI, 14, true, PG>)); LH_ATTR((k_gemv<PRE, EPI, 10, true, PG>)); LH_ATTR((k_gemv<PRE, EPI, 8, true, PG>)); LH_ATTR((k_gemv<PRE, EPI, 4, true, PG>))
-    LH_ATTR_G1(PRE_QA, EPI_STORE, 4); LH_ATTR_G1(PRE_QA, EPI_STORE, 12); LH_ATTR_G1(PRE_QA, EPI_RESID, 4); LH_ATTR_G1(PRE_QA, EPI_RESID, 12);
-    LH_ATTR_G1(PREP_NORM, EPI_STORE, 1); LH_ATTR_G1(PREP_NORM, EPI_STORE, 2); LH_ATTR_G1(PREP_PLAIN, EPI_RESID, 1); LH_ATTR_G1(PREP_PLAIN, EPI_RESID, 2);
-    LH_ATTR_G1(PREP_SILU_MUL, EPI_RESID, 1); LH_ATTR_G1(PREP_NORM, EPI_SILU_QA, 1);
-    LH_ATTR_G1(PREP_NORMP, EPI_STORE, 1); LH_ATTR_G1(PREP_NORMP, EPI_STORE, 2); LH_ATTR_G1(PREP_NORMP, EPI_SILU_QA, 1);
-    LH_ATTR_G1(PRE_QA, EPI_SILU_QA, 1);
-    LH_ATTR((k_gemv<PREP_NORMP, EPI_SILU_QAH, 4, true, 1>)); LH_ATTR((k_gemv<PREP_NORMP, EPI_SILU_QAH, 4, true, 2>)); LH_ATTR((k_gemv<PREP_NORM, EPI_SILU_QAH, 4, true, 1>)); LH_ATTR((k_gemv<PREP_NORM, EPI_SILU_QAH, 4, true, 2>));
-    LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 4, true, 1>)); LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 8, true, 1>)); LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 10, true, 1>));
-    LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 4, true, 2>)); LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 8, true, 2>)); LH_ATTR((k_gemv<PREP_NORMP, EPI_STORE_PICK, 10, true, 2>));
-    LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 4, true, 1>)); LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 8, true, 1>)); LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 10, true, 1>));
-    LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 4, true, 2>)); LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 8, true, 2>)); LH_ATTR((k_gemv<PREP_NORM, EPI_STORE_PICK, 10, true, 2>));
-    LH_ATTR_G1(PREP_NORM_TAG, EPI_STORE, 1); LH_ATTR_G1(PREP_NORM_TAG, EPI_STORE, 2); LH_ATTR_G1(PRE_QA, EPI_RESID_TAG, 4); LH_ATTR_G1(PRE_QA, EPI_RESID_TAG, 12);
-#undef LH_ATTR_G1
-    LH_ATTR(k_dec_pv_blk<false>); LH_ATTR(k_dec_pv_blk<true>); LH_ATTR(k_dec_pv_stream<4>); LH_ATTR(k_dec_pv_dma); LH_ATTR(k_dec_attn_x); LH_ATTR((k_qkv_attn<PREP_NORMP, 8, 1>)); LH_ATTR((k_qkv_attn<PREP_NORM, 8, 1>)); LH_ATTR((k_qkv_attn<PREP_NORMP, 10, 2>)); LH_ATTR((k_qkv_attn<PREP_NORM, 10, 2>)); LH_ATTR((k_qkv_attn<PREP_NORMP, 4, 2>)); LH_ATTR((k_qkv_attn<PREP_NORM, 4, 2>));
-    LH_ATTR((k_qkv_attn<PREP_NORM_TAG, 8, 1>)); LH_ATTR((k_qkv_attn<PREP_NORM_TAG, 10, 2>)); LH_ATTR((k_qkv_attn<PREP_NORM_TAG, 4, 2>));
-#undef LH_ATTR
+    auto raise = [](const void *kernel) { return kernel ? hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cap) : hipSuccess; };
+    hipError_t e;
+    // every instance the launchers' own lookups can return, and no other: nothing launches without its attribute
+    for (int pre = PRE_QA; pre <= PREP_NORM_TAG; pre++)
+        for (int depth = 4; depth <= 22; depth += 2)
+            for (int pg : { 1, 2, 4, 12 }) {
+                for (int epi = EPI_STORE; epi <= EPI_SILU_QAH; epi++)
+                    for (int ring = 0; ring < 2; ring++)
+                        if ((e = raise((const void *) gemv_kernel(pre, epi, GemvPlan{ 4, pg, depth, ring != 0, 0, 0 }))) != hipSuccess) return e;
+                if ((e = raise((const void *) qkv_attn_kernel(pre, depth, pg))) != hipSuccess) return e;
+            }
+    for (const void *kernel : { (const void *) k_dec_pv_blk<false>, (const void *) k_dec_pv_blk<true>, (const void *) k_dec_pv_stream<4>, (const void *) k_dec_pv_dma, (const void *) k_dec_attn_x })
+        if ((e = raise(kernel)) != hipSuccess) return e;
     return hipSuccess;
 }
 

@@ -666,7 +666,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
     // decode: the producer of every residual-stream row (embedding, wo and w2 mat-vecs) hands {sum, sum of
     // squares} of the row to the norm-fused mat-vec that consumes it, which then needs no reduction of its own
     // (k_gemv PREP_NORMP).  LLAMAHIP_NORM_MODE=0 / 1 restore the self-contained prologues (measurement only).
-    static const bool no_norm_part = getenv("LLAMAHIP_NORM_MODE") && atoi(getenv("LLAMAHIP_NORM_MODE")) < 2;
+    const bool no_norm_part = !norm_mode_resolve();
     const bool use_part = fused && m->w13_interleaved && !no_norm_part;
     int n_part_x = 0;                                       // pairs in npart_a valid for the row currently in x (0: none)
     // decode: wq|wk|wv + attention as one launch with tagged hand-offs (k_qkv_attn); one forward pass = one epoch
@@ -1351,7 +1351,7 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
         // Where the lm head's pick epilogue applies (EPI_STORE_PICK) the step is layers -> lm head alone: that launch picks the token,
         // advances the position and embeds the pick for the next step; only the FIRST token of the call is embedded by a launch of its own.
         static const bool no_fold = getenv("LLAMAHIP_NO_PICK_FOLD") != nullptr;
-        static const bool norm_default = !(getenv("LLAMAHIP_NORM_MODE") && atoi(getenv("LLAMAHIP_NORM_MODE")) < 2);
+        const bool norm_default = norm_mode_resolve();
         const bool fold = !no_fold && norm_default && !m->dense && !(m->flags & LLAMAHIP_FLAG_UNFUSED) && m->w13_interleaved && m->l1 > m->l0 && gemv_pick_applies(m->output);
         StepIO pio;
         pio.fold_pick = true; pio.pick_out = m->d_out_tokens; pio.pick_next = m->d_tokens;
@@ -2792,6 +2792,18 @@ int32_t llamahip_debug_set_plan(int32_t m, int32_t k, int32_t interleaved, int32
     if (m < 1 || k < 1 || !out || !gemv_set_plan_query(m, k, interleaved != 0, n_rows, epi, o)) return 0;
     for (int i = 0; i < 5; i++) out[i] = o[i];
     return 1;
+}
+
+int32_t llamahip_debug_gemv_plan(int32_t m, int32_t k, int32_t interleaved, int32_t pre, int32_t epi, int64_t out[6]) {
+    if (m < 1 || k < 1 || !out) return 0;
+    QMat w;
+    w.set_shape(m, k);
+    if (interleaved) w.gmapF8 = m / 16;
+    const GemvPlan p = gemv_plan(w, pre, epi);
+    if (!p.nw) return 0;
+    const int64_t o[6] = { p.nw, p.pg, p.depth, p.ring, p.grid, (int64_t) p.lds };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return gemv_plan_has_kernel(pre, epi, p) ? 1 : -1;
 }
 
 int32_t llamahip_debug_gemm_paths(int64_t *out, int32_t cap) {

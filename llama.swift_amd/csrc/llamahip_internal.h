@@ -130,6 +130,14 @@ struct PickIO {
     const uint8_t *emb; float *x_next; double *part_next; uint32_t *epoch; int n_vocab;      // the next step's embedding row
 };
 int gemv_resid_parts(const QMat &w);
+// The launch plan of the single-row decode mat-vec (decode.hip gemv_plan, the one rule every launcher and predicate below derives from):
+// waves per workgroup, operand granules per thread, ring depth, ring or whole row in flight, grid, dynamic LDS bytes.
+struct GemvPlan { int nw, pg, depth; bool ring; int grid; size_t lds; };   // nw == 0: the kernel does not take this (matrix, pre, epi)
+GemvPlan gemv_plan(const QMat &w, int pre, int epi);
+bool gemv_plan_has_kernel(int pre, int epi, const GemvPlan &p);      // the plan names an instance of k_gemv that exists
+// LLAMAHIP_NORM_MODE, read in one place: resolves (*pre, *np) to the prologue to launch (PREP_NORM / PREP_NORMP) and the kernel's
+// part_in / npart; returns whether the mode is the default (pre == null: that question alone)
+bool norm_mode_resolve(int *pre = nullptr, NormPart *np = nullptr);
 // EPI_SILU_QAH: the w1|w3 decode mat-vec in HALF-block workgroups (4 waves: 16 gate rows + the same 16 up rows).  The 8-wave workgroups of
 // EPI_SILU_QA are F / 32 = 344 on 256 CUs at 7B: 88 CUs stream two workgroups' weights, the others one, and a CU's load path bounds what
 // it can pull -- the launch ends with a third of the chip streaming alone.  688 half-block workgroups spread 3 / 2 per CU.  The two halves

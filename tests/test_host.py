@@ -468,3 +468,59 @@ def test_few_row_kernel_forced_plans_take_every_shape_too(built, env):
     import variants
     r = subprocess.run([sys.executable, os.path.join(variants.HERE, "variants.py"), "walk"], env=dict(os.environ, **env), capture_output=True, text=True, cwd=variants.ROOT)
     assert r.returncode == 0 and "plans walked: 1416" in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
+def _gemv_plan_table():
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gemv_plans.json")) as f:
+        return json.load(f)
+
+
+def test_decode_matvec_plan_table_does_not_move(L):
+    """The launch plan of the single-row decode mat-vec (csrc/decode.hip gemv_plan: waves, operand budget, ring depth, ring or whole row
+    in flight, grid, LDS bytes -- host only) equals, entry for entry, the table recorded from the launchers before they shared one plan
+    function (tests/golden/gemv_plans.json; the sweep is tests/variants.py gemv_plan_sweep): every decode matrix of the four LLaMA widths
+    and of the synthetic models' widths, the edges of every rule, under every (prologue, epilogue) pair a launcher dispatches.
+    Refusals are part of the table."""
+    import variants
+    table = _gemv_plan_table()
+    assert [tuple(r[:5]) for r in table] == [(M, K, int(inter), pre, epi) for M, K, inter, pre, epi in variants.gemv_plan_sweep()]
+    assert len(table) > 2000 and sum(r[5] is None for r in table) > 100
+    for M, K, inter, pre, epi, want in table:
+        got = L.gemv_plan(M, K, pre, epi, bool(inter))
+        assert got == (tuple(want) if want else None), (M, K, inter, pre, epi, want, got)
+
+
+def test_decode_matvec_plans_of_the_llama_sizes(L):
+    """The same plans against rows worked out by hand from the launch rules (they agree with the instances
+    profiles/r06_kernel_scratch_report.txt recorded on the hardware): nw / pg / depth / ring / grid of every decode mat-vec."""
+    import variants as v
+    R, W = True, False          # ring | whole row in flight
+    want = {
+        "7B":  {"wq|wk|wv": (4, 1, 8, R, 384), "wo": (2, 4, 16, W, 256), "w1|w3": (8, 1, 4, R, 344), "w2": (2, 12, 10, R, 256), "output": (4, 1, 4, R, 1000)},
+        "13B": {"wq|wk|wv": (4, 2, 10, R, 480), "wo": (2, 4, 10, R, 320), "w1|w3": (8, 1, 4, R, 432), "w2": (2, 12, 10, R, 320), "output": (4, 2, 4, R, 1000)},
+        "30B": {"wq|wk|wv": (4, 2, 4, R, 624), "wo": (2, 4, 10, R, 416), "w1|w3": (8, 1, 4, R, 560), "w2": (2, 12, 10, R, 416), "output": (4, 2, 4, R, 1000)},
+        "65B": {"wq|wk|wv": (4, 2, 4, R, 768), "wo": (4, 4, 8, R, 256), "w1|w3": (8, 1, 4, R, 688), "w2": (4, 12, 10, R, 256), "output": (4, 2, 4, R, 1000)},
+    }
+    pairs = {"wq|wk|wv": (v.PREP_NORM, v.EPI_STORE), "wo": (v.PRE_QA, v.EPI_RESID), "w1|w3": (v.PREP_NORM, v.EPI_SILU_QA), "w2": (v.PRE_QA, v.EPI_RESID),
+             "output": (v.PREP_NORM, v.EPI_STORE)}
+    for size, d in v.LLAMA_WIDTHS.items():
+        for name, (M, K, inter) in v.llama_matrices(d).items():
+            pre, epi = pairs[name]
+            p = L.gemv_plan(M, K, pre, epi, inter)
+            assert p is not None and p[:5] == tuple(int(x) for x in want[size][name]), (size, name, p, want[size][name])
+
+
+def test_decode_matvec_plans_name_kernels_that_exist(L):
+    """Every plan of the table names an instance of k_gemv that was compiled: the launchers look their kernel up by the plan, so a plan
+    without one would be refused at launch (llamahip_debug_gemv_plan returns -1 for it) -- the single-row counterpart of the few-row walk."""
+    import ctypes as C
+    f = L.lib().llamahip_debug_gemv_plan
+    f.restype, f.argtypes = C.c_int32, [C.c_int32] * 5 + [C.c_void_p]
+    out = np.zeros(6, np.int64)
+    n = 0
+    for M, K, inter, pre, epi, want in _gemv_plan_table():
+        rc = f(M, K, inter, pre, epi, out.ctypes.data_as(C.c_void_p))
+        assert rc == (1 if want else 0), (M, K, inter, pre, epi, want, rc, out.tolist())
+        n += rc
+    assert n > 1000

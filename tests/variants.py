@@ -61,7 +61,7 @@ def walk_set_plans(L):
     empty group), operand rows + weight ring inside the CU's 160 KB of LDS.  Returns the number of plans walked."""
     n = 0
     for d, mult in ((4096, 256), (5120, 256), (6656, 256), (8192, 256)):
-        F = ((2 * (4 * d) // 3 + mult - 1) // mult) * mult                  # .mm:118-120
+        F = ffn_width(d, mult)
         mats = [("wq|wk|wv", 3 * d, d, EPI_ROPE_KV, False), ("wo", d, d, EPI_RESID, False), ("w1|w3 halves", 2 * F, d, EPI_SILU_QAH, True),
                 ("w1|w3 blocks", 2 * F, d, EPI_SILU_QA, True), ("w2", d, F, EPI_RESID, False), ("output", 32000, d, EPI_STORE, False)]
         for name, M, K, epi, inter in mats:
@@ -83,6 +83,40 @@ def walk_set_plans(L):
                     nc, cw, ncg, rgw, lds = p
                     assert (nc, cw) in SET_PAIRS and nc * cw * ncg >= N > nc * cw * (ncg - 1) and lds <= 160 * 1024, (M, K, N, epi, p)
     return n
+
+
+# the single-row decode mat-vec (k_gemv): prologues / epilogues of llamahip_internal.h, and every pair a launcher dispatches
+PRE_QA, PREP_PLAIN, PREP_NORM, PREP_SILU_MUL, PREP_NORMP, PREP_NORM_TAG = 0, 1, 2, 3, 4, 6
+EPI_RESID_TAG, EPI_STORE_PICK = 5, 6
+GEMV_PAIRS = [(PRE_QA, EPI_STORE), (PRE_QA, EPI_RESID), (PREP_NORM, EPI_STORE), (PREP_NORM, EPI_SILU_QA), (PREP_NORMP, EPI_STORE), (PREP_NORMP, EPI_SILU_QA),
+              (PRE_QA, EPI_SILU_QA), (PREP_PLAIN, EPI_RESID), (PREP_SILU_MUL, EPI_RESID), (PREP_NORM_TAG, EPI_STORE), (PRE_QA, EPI_RESID_TAG),
+              (PREP_NORM, EPI_STORE_PICK), (PREP_NORMP, EPI_STORE_PICK), (PREP_NORM, EPI_SILU_QAH), (PREP_NORMP, EPI_SILU_QAH)]
+LLAMA_WIDTHS = {"7B": 4096, "13B": 5120, "30B": 6656, "65B": 8192}
+SYNTH_WIDTHS = [(64, 32), (128, 64), (256, 64), (256, 128), (256, 256), (320, 64), (512, 256), (1344, 64)]      # (n_embd, n_mult) of the synthetic test models
+
+
+def ffn_width(d, mult):
+    return ((2 * (4 * d) // 3 + mult - 1) // mult) * mult                  # .mm:118-120
+
+
+def llama_matrices(d, mult=256, V=32000):
+    """name -> (M, K, interleaved) of a model's decode mat-vecs"""
+    F = ffn_width(d, mult)
+    return {"wq|wk|wv": (3 * d, d, False), "wo": (d, d, False), "w1|w3": (2 * F, d, True), "w2": (d, F, False), "output": (V, d, False)}
+
+
+def gemv_plan_sweep():
+    """The (M, K, interleaved, pre, epi) keys of tests/golden/gemv_plans.json: every decode matrix of the four LLaMA widths and of the
+    synthetic test models' widths (w1|w3 in both layouts), and the edges of every launch rule (row-groups around 512 / 1024 / 2048, rows
+    of 4 .. 43 chunks, K / 16 around the one- and two-granule budgets), each under every (prologue, epilogue) pair a launcher dispatches."""
+    shapes = []
+    for d, mult, V in [(d, 256, 32000) for d in LLAMA_WIDTHS.values()] + [(d, mult, V) for d, mult in SYNTH_WIDTHS for V in (64, 96, 32000)]:
+        mats = llama_matrices(d, mult, V)
+        shapes += list(mats.values()) + [mats["w1|w3"][:2] + (False,)]
+    for ngroups in (511, 512, 1023, 1024, 2047, 2048):
+        for K in [256 * c for c in (4, 5, 15, 16, 17, 43)] + [16 * g for g in (256, 257, 512, 513)]:
+            shapes += [(8 * ngroups, K, False), (8 * ngroups, K, True)]
+    return [(M, K, inter, pre, epi) for M, K, inter in dict.fromkeys(shapes) for pre, epi in GEMV_PAIRS]
 
 
 def run_nested(env, select, files, tag, timeout=1500):
