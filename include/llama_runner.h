@@ -71,6 +71,21 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt, cons
 
 void llama_runner_config_default(llama_runner_config *c);                       /* Config.default */
 
+/* Extension: drafted sampled decoding in the generation loop (llamahip_verify_sample; llamahip.h "sampled decode with drafted tokens").
+ * draft_len 0 = off (the default), 1 .. 15 = on with drafts of up to that many tokens (values outside are clamped).  A bridge that never
+ * calls the setter -- the unchanged replacement bridge -- takes LLAMAHIP_RUNNER_LOOKUP=<1..15> from the environment at each run.
+ * llama_runner_config keeps its layout (it has no size field and callers pass it by pointer).
+ * When on, and the run is not `greedy`, LLAMAHIP_HOST_SAMPLER is not set, the prompt is used up and one token is pending: the loop drafts
+ * from the prompt tokens plus everything generated so far (llamahip_lookup_draft, its default n-grams), cut to remaining - 1, runs one
+ * llamahip_verify_sample and posts picks[0 .. n_accept] as token events in order; where nothing is drafted the step is the usual one.
+ * The event stream is byte for byte the one the same seed produces with lookup off; runs with lookup off, `greedy` runs and the prompt
+ * phase run the code they ran before.
+ * llama_runner_bridge_lookup_stats: the counts of the bridge's last run (all zero before the first run and for runs without lookup steps);
+ * out->struct_size is set by the caller; returns 0, or -1 for a null argument or a wrong struct_size. */
+struct llamahip_lookup_stats;
+void llama_runner_bridge_set_lookup(llama_runner_bridge *b, int32_t draft_len);
+int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, struct llamahip_lookup_stats *out);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -70,7 +70,7 @@ typedef struct llamahip_opts {
  * process (.mm:790; LlamaRunnerBridge.mm:18-26).  A handle loaded with n_devices > 1 -- or, for a caller that passes no options such as the
  * replacement bridge, with the environment variable LLAMAHIP_DEVICES="0,1,...,7" (or a count: "8" = devices 0 .. 7) -- holds one stage per
  * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_eval_logprobs / llamahip_perplexity / llamahip_decode_greedy /
- * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
+ * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_verify_sample / llamahip_decode_sample_lookup / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
  * crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
  * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
@@ -285,6 +285,51 @@ int32_t llamahip_lookup_draft(const int32_t *history, int32_t n_history, const i
                               int32_t draft_len, int32_t ngram_min, int32_t ngram_max, int32_t *draft_out);
 int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
                             int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
+
+/* ---- sampled decode with drafted tokens (exact) -----------------------------------------------------------------------------------
+ * The same trade for the reference's sampler (llama_sample_top_p_top_k, .mm:851-870), which is what the bridge runs.  The sampler is a
+ * deterministic function of the row's logits, the last_n_tokens window and the std::mt19937 state.  Row j of a verify step holds the logits
+ * of the single-token eval at n_past + j (above); if draft tokens 0 .. j - 1 were accepted, the window at row j is the current window
+ * shifted by j with those tokens pushed -- known before the eval.  The device selects every row's candidates under that window
+ * (k_topk_keys_slide + k_topk_select_rows behind the eval, in place of the greedy pick), the host draws row 0 with the real sampler and
+ * accepts the draw, draws row 1 only if that draw was draft[0], and so on: it stops at the first draw the draft does not continue with.
+ * The walk consumes exactly the rng draws of the token-by-token loop
+ *   llamahip_eval_topk -> llamahip_sample_from_candidates (exact) / llamahip_sample_top_p_top_k (not exact) -> llamahip_sampler_accept
+ * and leaves the window where that loop leaves it: the token stream is that loop's, bit for bit.
+ * (Norm statistics as above: the equality of a verify row and a single step is BY TEST -- tests/test_gpu_sample_lookup.py -- not structural.)
+ *
+ * llamahip_verify_sample -- one step.  `sampler` has already accepted `token` (the loop above: eval_topk -> draw -> accept); rows =
+ *   [token, draft[0 .. n_draft)] at n_past, n_draft 0 .. 15.  For every row j the walk reaches: picks[j] = the sampler's draw at position
+ *   n_past + j, accepted into the sampler; exact[j] (may be NULL) = 1 drawn from the device's candidates, 0 drawn from the row's logits (a
+ *   tie only libstdc++'s partial_sort orders, a NaN: that row alone is copied to the host).  Rows not reached: picks[j] = exact[j] = -1.
+ *   *n_accept = the row the walk stopped at = the number of leading draft tokens that are the draws.  New context n_past + *n_accept + 1,
+ *   next token picks[*n_accept].  KV rows: llamahip_verify_greedy's contract.  Arguments (llamahip_verify_greedy's, a null sampler, top_k
+ *   < 1, temp / repeat_penalty <= 0) are checked before any device work.
+ *   Where the device cannot make candidates (top_k > 64, n_vocab > 32768, a window longer than 1024 ids) the walk takes every row it
+ *   reaches from its logits.  f16 / f32 / Q4_1 files and LLAMAHIP_FLAG_UNFUSED handles evaluate their rows one llamahip_eval_topk step at a
+ *   time and stop behind the first mismatch; so does n_draft = 0.
+ * llamahip_decode_sample_lookup -- the loop: llamahip_decode_greedy_lookup's arguments, refusals, drafter, draft cut and stats identity
+ *   (n_steps = n_verify_steps + n_single_steps + n_accepted); where nothing is drafted the step is one llamahip_eval_topk step.
+ *   out_tokens [n_steps], out_exact [n_steps] (may be NULL), the sampler's window and rng state and KV rows [0, n_past + n_steps) are bit
+ *   for bit what the single-sequence loop above leaves on that slot.  In all the cases of the previous paragraph nothing is drafted: the
+ *   single-token loop runs and zero drafts are reported.  (On a pipeline handle llamahip_eval_topk returns the logits row, so single steps
+ *   report exact = 0 there while verify rows report the last stage's selection; the tokens are the same either way.)
+ * llamahip_op_topk_slide -- the device half on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16; ids: ONE stream
+ *   of n_last + n_rows - 1 ids, row r's window = ids[r .. r + n_last), n_last <= 1024 (ids outside [0, n_vocab) are ignored, as by the
+ *   sampler); out_scores / out_ids [n_rows][64], out_exact [n_rows] -- row r bit for bit llamahip_op_topk on that row with that window. */
+int llamahip_verify_sample(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft,
+                           llamahip_sampler *sampler, double repeat_penalty, int32_t top_k, double top_p, double temp,
+                           int32_t *n_accept, int32_t *picks /* n_draft + 1 */, int32_t *exact /* n_draft + 1, may be NULL */,
+                           char *err, size_t err_cap);
+int llamahip_decode_sample_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
+                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max, llamahip_sampler *sampler,
+                                  double repeat_penalty, int32_t top_k, double top_p, double temp,
+                                  int32_t *out_tokens, int32_t *out_exact /* may be NULL */, llamahip_lookup_stats *stats,
+                                  char *err, size_t err_cap);
+int llamahip_op_topk_slide(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *ids, int32_t n_last,
+                           double repeat_penalty, int32_t top_k, double temp,
+                           double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */

@@ -34,6 +34,7 @@ from .binding import (  # noqa: F401
     op_quantize_row_q4_0,
     op_topk,
     op_topk_rows,
+    op_topk_slide,
     op_verify_rows,
     qa_to_blocks,
     quantize_file,

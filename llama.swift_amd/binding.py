@@ -116,6 +116,10 @@ def lib() -> C.CDLL:
     L.llamahip_decode_greedy.argtypes = [vp, i32, i32, i32, i32, vp, vp, cp, sz]
     L.llamahip_verify_greedy.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, vp, cp, sz]
     L.llamahip_decode_greedy_lookup.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(_LookupStats), cp, sz]
+    L.llamahip_verify_sample.argtypes = [vp, i32, i32, i32, vp, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, cp, sz]
+    L.llamahip_decode_sample_lookup.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, i32, i32, i32, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp,
+                                                C.POINTER(_LookupStats), cp, sz]
+    L.llamahip_op_topk_slide.argtypes = [vp, i32, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_lookup_draft.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
     L.llamahip_lookup_draft.restype = i32
     L.llamahip_op_verify_rows.argtypes = [vp, i32, i32, vp, vp, vp, cp, sz]
@@ -468,6 +472,36 @@ class Model:
         stats = {k: getattr(st, k) for k, _ in _LookupStats._fields_ if k != "struct_size"}
         return (out, stats, logits) if want_logits else (out, stats)
 
+    def verify_sample(self, token: int, draft, n_past: int, sampler: "Sampler", repeat_penalty: float = 1.3, top_k: int = 40,
+                      top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), n_threads: int = 8):
+        """llamahip_verify_sample: the rows [token, draft ...] at n_past as one eval, walked by `sampler` (which has accepted `token`).  Returns
+        (n_accept, picks[len(draft) + 1], exact[len(draft) + 1]); -1 in both for the rows the walk did not reach."""
+        draft = np.ascontiguousarray(draft, np.int32).ravel()
+        picks, exact = np.full(draft.size + 1, -2, np.int32), np.full(draft.size + 1, -2, np.int32)
+        n_acc = C.c_int32(-1)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_verify_sample(self._h, n_threads, n_past, int(token), _ptr(draft), draft.size, None if sampler is None else sampler._s,
+                                          repeat_penalty, top_k, top_p, temp, C.byref(n_acc), _ptr(picks), _ptr(exact), err, len(err))
+        _check(rc, err)
+        return n_acc.value, picks, exact
+
+    def decode_sample_lookup(self, first_token: int, n_steps: int, n_past: int, context, sampler: "Sampler", corpus=None, draft_len: int = 0,
+                             ngram_min: int = 0, ngram_max: int = 0, repeat_penalty: float = 1.3, top_k: int = 40,
+                             top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), n_threads: int = 8, stats_size: int | None = None):
+        """llamahip_decode_sample_lookup: the eval_topk -> draw -> accept loop's tokens, drafted from context (the n_past tokens already
+        evaluated) + what is produced, then from corpus.  Returns (tokens[n_steps], exact[n_steps], stats dict)."""
+        context = np.ascontiguousarray(context, np.int32).ravel()
+        corpus = None if corpus is None else np.ascontiguousarray(corpus, np.int32).ravel()
+        out, exact = np.empty(max(n_steps, 0), np.int32), np.empty(max(n_steps, 0), np.int32)
+        st = _LookupStats(C.sizeof(_LookupStats) if stats_size is None else stats_size)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_sample_lookup(self._h, n_threads, n_past, int(first_token), n_steps, _ptr(context), context.size, _ptr(corpus),
+                                                 0 if corpus is None else corpus.size, draft_len, ngram_min, ngram_max,
+                                                 None if sampler is None else sampler._s, repeat_penalty, top_k, top_p, temp, _ptr(out), _ptr(exact),
+                                                 C.byref(st), err, len(err))
+        _check(rc, err)
+        return out, exact, {k: getattr(st, k) for k, _ in _LookupStats._fields_ if k != "struct_size"}
+
     def decode_greedy_multi(self, first_tokens, n_past, n_steps: int, n_threads: int = 8) -> np.ndarray:
         """llamahip_decode_greedy_multi: sequences in KV slots 0 .. len(first_tokens) - 1 decoded together; returns [n_seqs][n_steps]."""
         ft = np.ascontiguousarray(first_tokens, np.int32)
@@ -618,6 +652,23 @@ def op_topk_rows(logits2d, windows, repeat_penalty: float = 1.3, top_k: int = 40
     _check(rc, err)
     res = (exact.astype(bool), sc[:, :top_k].copy(), ids[:, :top_k].copy())
     return res + (spill,) if want_spill else res
+
+
+def op_topk_slide(logits2d, ids, n_last: int, repeat_penalty: float = 1.3, top_k: int = 40, temp: float = float(np.float32(0.8))):
+    """k_topk_keys_slide + k_topk_select_rows on host rows f32 [R, n_vocab] (1 .. 16 rows): ids is ONE stream of n_last + R - 1 ids, row r's
+    window = ids[r : r + n_last].  Returns (exact bool[R], scores float64[R][top_k], ids int32[R][top_k])."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    ids = np.ascontiguousarray(ids, np.int32).ravel()
+    if ids.size != max(n_last + R - 1, 0):
+        raise ValueError(f"ids: {ids.size} ids for {R} rows with windows of {n_last} (want {n_last + R - 1})")
+    sc, out_ids, exact = np.zeros((max(R, 1), 64), np.float64), np.zeros((max(R, 1), 64), np.int32), np.zeros(max(R, 1), np.int32)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_topk_slide(_ptr(logits2d), R, V, _ptr(ids), n_last, repeat_penalty, top_k, temp, _ptr(sc), _ptr(out_ids), _ptr(exact), err, len(err))
+    _check(rc, err)
+    return exact[:R].astype(bool), sc[:R, :top_k].copy(), out_ids[:R, :top_k].copy()
 
 
 def op_logprob(logits2d, targets=None):

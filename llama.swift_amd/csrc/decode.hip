@@ -30,9 +30,9 @@
 //   k_dec_scores, k_decn_scores, k_dec_pv_blk   attention of one row (decode fallback) / of a short eval (2..60 rows)
 //   attn_x_body, k_dec_attn_x, k_qkv_attn       attention in one launch; wq|wk|wv mat-vec + attention in one launch (XCD-local tagged hand-offs)
 //   k_xcd_selftest, k_argmax, k_advance, k_bump_epoch, k_topk_keys, k_topk_select,
-//              k_topk_keys_rows, k_topk_select_rows, k_topk_spill
+//              k_topk_keys_rows, k_topk_keys_slide, k_topk_select_rows, k_topk_spill
 //   launchers: set_phase_probe, launch_gemv (+ kernel selection rules), launch_attn_short, xcd_selftest, launch_dec_attn,
-//              launch_qkv_attn, launch_bump_epoch, launch_topk_candidates, launch_topk_rows, launch_argmax, launch_advance, init_kernel_attrs
+//              launch_qkv_attn, launch_bump_epoch, launch_topk_candidates, launch_topk_rows, launch_topk_slide, launch_argmax, launch_advance, init_kernel_attrs
 #define LH_DEFINE_PHASE_PROBE 1
 #include <cmath>
 
@@ -2429,11 +2429,23 @@ k_topk_keys_rows(const float *__restrict__ logits, int V, const int32_t *__restr
                   keys, gmax, (uint32_t *) (gmax + 64));
 }
 
+// The rows of a verify step (llamahip_verify_sample): row r's window is ids[r .. r + n_last) of ONE id stream -- the sampler's window followed
+// by the draft, n_last + R - 1 ids -- i.e. the window after draft tokens 0 .. r - 1 were accepted.  Same body, same workspace layout; the
+// selection behind it is k_topk_select_rows with no per-row lengths (n_last <= 1024 is the launcher's refusal).
+__global__ void __launch_bounds__(1024)
+k_topk_keys_slide(const float *__restrict__ logits, int V, const int32_t *__restrict__ ids, int n_last, double scale, double repeat_penalty,
+                  char *__restrict__ ws) {
+    const int r = blockIdx.y;
+    unsigned long long *keys = (unsigned long long *) (ws + (size_t) r * TOPK_WS_BYTES), *gmax = keys + 32768;
+    topk_keys_row(logits + (size_t) r * V, V, ids + r, n_last, scale, repeat_penalty, keys, gmax, (uint32_t *) (gmax + 64));
+}
+
+// (n_last == nullptr: every row's window is one the device took -- launch_topk_slide)
 __global__ void __launch_bounds__(1024)
 k_topk_select_rows(int V, int k, const int32_t *__restrict__ n_last, char *__restrict__ ws, TopkOut *__restrict__ out) {
     const int r = blockIdx.x;
     unsigned long long *keys = (unsigned long long *) (ws + (size_t) r * TOPK_WS_BYTES), *gmax = keys + 32768;
-    const int nw = n_last[r];
+    const int nw = n_last ? n_last[r] : 0;
     topk_select_row(V, k, keys, gmax, (uint32_t *) (gmax + 64), out[r].sc, out[r].id, out[r].fl, nw < 0 || nw > 1024);
 }
 
@@ -2460,6 +2472,16 @@ hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *wi
         hipLaunchKernelGGL(k_topk_spill, dim3((V + 4095) / 4096, R), dim3(1024), 0, st, logits, V, out, spill);
         LH_LAUNCH_CHECK();
     }
+    return hipSuccess;
+}
+
+hipError_t launch_topk_slide(const float *logits, int R, int V, const int32_t *ids, int n_last, double scale, double repeat_penalty, int k,
+                             TopkOut *out, hipStream_t st, void *ws) {
+    if (R < 1 || V < 1 || V > 32768 || k < 1 || k > 64 || n_last < 0 || n_last > 1024 || !ws || !out || !logits || (!ids && n_last > 0)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_topk_keys_slide, dim3((V + 1023) / 1024, R), dim3(1024), 0, st, logits, V, ids, n_last, scale, repeat_penalty, (char *) ws);
+    LH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_topk_select_rows, dim3(R), dim3(1024), 0, st, V, k, (const int32_t *) nullptr, (char *) ws, out);
+    LH_LAUNCH_CHECK();
     return hipSuccess;
 }
 

@@ -160,7 +160,8 @@ struct llamahip_model {
     int32_t *d_tokens = nullptr;
     // single-token evals through the C ABI: token, sampler window and candidate results live in ONE pinned, device-mapped host
     // block that the kernels read / write directly (three ~4 us blit copies per sampled token otherwise)
-    struct HostIo { int32_t tok[16]; int32_t window[1024]; double sc[64]; int32_t id[64]; int32_t fl[2]; };
+    struct HostIo { int32_t tok[16]; int32_t window[1024]; double sc[64]; int32_t id[64]; int32_t fl[2];
+                    int32_t slide[1024 + VERIFY_ROWS_MAX]; TopkOut rows[VERIFY_ROWS_MAX]; };      // (a sampled verify step: its id stream in, its rows' candidates out)
     HostIo *h_io = nullptr, *d_io = nullptr;       // host pointer / its device alias
     const int32_t *tok_src = nullptr;              // set by eval_impl around forward(): where the embedding kernel finds the token
     float *x = nullptr, *x1 = nullptr, *qkv = nullptr, *qr = nullptr, *merged = nullptr, *gu = nullptr;
@@ -188,6 +189,7 @@ struct llamahip_model {
     bool score_rows = false;             // set around forward() by the scoring entry points: the all-rows lm head takes those copies
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
+    char *d_slide = nullptr;             // sampled verify step (last stage): 16 x TOPK_WS_BYTES of selection workspace | the id stream (SLIDE_IDS_BYTES) | 16 TopkOut (slide_ensure)
     int32_t *d_verify = nullptr;         // drafted greedy decoding (last stage): {position, cursor} | 16 row tokens | 16 picks | {n_accept, 16 picks} | from [64]: the token log, n_ctx entries (verify_io)
     uint32_t *d_attn_sync = nullptr;     // per-head hand-off counters of k_dec_attn_x ([H][32] dwords); null: two-launch attention
     uint64_t *d_qkv2 = nullptr, *d_sc2 = nullptr;   // tagged hand-off buffers of k_qkv_attn: [3 d] and [H][n_ctx] {fp32 bits, tag} granules
@@ -288,7 +290,7 @@ llamahip_model::~llamahip_model() {
     free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
     free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
     free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify);
+    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_slide);
     free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
     free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
     free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
@@ -2238,15 +2240,45 @@ static int verify_append(llamahip_model *last, int32_t pick, int restart_pos, ch
     return 0;
 }
 
+// The sampled verify step's device half (llamahip_verify_sample): behind the eval, in place of the two kernels above, the sampler's candidate
+// selection over the N rows with row r's window = ids[r .. r + n_last) (launch_topk_slide).  ids: the sampler's window followed by the draft,
+// n_last + N - 1 ids; k == 0: the device cannot make candidates (top_k > 64, n_vocab > 32768, a window longer than 1024 ids) -- nothing is
+// launched and the walk takes every row it reaches from its logits.  out: N rows, valid after the step.
+struct SlideReq { const int32_t *ids; int n_last; double scale, repeat_penalty; int k; TopkOut *out; };
+constexpr size_t SLIDE_WS_BYTES = (size_t) VERIFY_ROWS_MAX * TOPK_WS_BYTES, SLIDE_IDS_BYTES = (1024 + VERIFY_ROWS_MAX) * 4;
+static int slide_ensure(llamahip_model *last, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    if (last->d_slide) return 0;
+    const size_t bytes = SLIDE_WS_BYTES + SLIDE_IDS_BYTES + VERIFY_ROWS_MAX * sizeof(TopkOut);
+    HIP_TRY(hipMalloc((void **) &last->d_slide, bytes), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemset(last->d_slide, 0, bytes), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+static int slide_enqueue(llamahip_model *last, const SlideReq &sl, int N, char *err, size_t err_cap) {
+    if (sl.k == 0) return 0;
+    int rc = slide_ensure(last, err, err_cap);
+    if (rc) return rc;
+    const size_t n_ids = (size_t) sl.n_last + N - 1;
+    int32_t *ids = (int32_t *) (last->d_slide + SLIDE_WS_BYTES);
+    TopkOut *out = (TopkOut *) (last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES);
+    if (last->h_io) {                       // (the stream is idle: every entry point synchronises before it returns)
+        memcpy(last->h_io->slide, sl.ids, n_ids * 4);
+        ids = last->d_io->slide; out = last->d_io->rows;
+    } else HIP_TRY(hipMemcpyAsync(ids, sl.ids, n_ids * 4, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_topk_slide(last->logits, N, last->hp.n_vocab, ids, sl.n_last, sl.scale, sl.repeat_penalty, sl.k, out, last->stream, last->d_slide), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
 // one verify step of N = 2 .. 16 rows on a Q4_0 handle, plain or pipeline (eval_score's walk); res: {n_accept, picks[N]}
+// (sl != nullptr: the sampled step -- res and logits_next unused, sl->out receives the rows' candidates)
 static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *rows, int N, int restart_pos, int32_t *res,
-                       float *logits_next, char *err, size_t err_cap) {
+                       float *logits_next, char *err, size_t err_cap, const SlideReq *sl = nullptr) {
     const double t0 = now_ms();
     llamahip_model *last = m;
     int rc;
     if (m->stages.empty()) {
         if ((rc = eval_stage_enqueue(m, n_threads, n_past, rows, N, nullptr, 1, true, err, err_cap)) != 0) return rc;
-        if ((rc = verify_enqueue(m, rows, N, restart_pos, err, err_cap)) != 0) return rc;
+        if ((rc = sl ? slide_enqueue(m, *sl, N, err, err_cap) : verify_enqueue(m, rows, N, restart_pos, err, err_cap)) != 0) return rc;
         HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
         if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
     } else {
@@ -2260,9 +2292,18 @@ static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, con
             if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         }
         last = m->stages[S - 1];
-        if ((rc = verify_enqueue(last, rows, N, restart_pos, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = sl ? slide_enqueue(last, *sl, N, err, err_cap) : verify_enqueue(last, rows, N, restart_pos, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         if ((rc = pipe_sync(m, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    }
+    if (sl) {
+        if (sl->k > 0) {
+            if (last->h_io) memcpy(sl->out, last->h_io->rows, (size_t) N * sizeof(TopkOut));
+            else HIP_TRY(hipMemcpy(sl->out, last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES, (size_t) N * sizeof(TopkOut), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        }
+        m->n_evals++;
+        m->t_eval_ms += now_ms() - t0;
+        return LLAMAHIP_OK;
     }
     if (last->h_io) memcpy(res, last->h_io->id, (size_t) (N + 1) * 4);
     else HIP_TRY(hipMemcpy(res, verify_io(last).res, (size_t) (N + 1) * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
@@ -2331,11 +2372,10 @@ int llamahip_verify_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
     return verify_greedy_impl(m, n_threads, n_past, token, draft, n_draft, n_past, n_accept, picks, logits_next, err, err_cap);
 }
 
-int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
-                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
-                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
-                                  int32_t *out_tokens, float *logits_last, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
-    static const char *fn = "llamahip_decode_greedy_lookup";
+// the arguments of the two lookup loops (greedy and sampled), checked without a device; the handle last
+static int check_lookup_args(llamahip_model *m, const char *fn, int32_t n_past, int32_t first_token, int32_t n_steps, const int32_t *context, int32_t n_context,
+                             const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max, const int32_t *out_tokens,
+                             const llamahip_lookup_stats *stats, char *err, size_t err_cap) {
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     const int V = m->hp.n_vocab, C = m->hp.n_ctx;
     if (n_steps < 1 || n_past < 0 || n_past > C - n_steps) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past, n_steps, C); return LLAMAHIP_ERR_PREDICT; }
@@ -2356,8 +2396,17 @@ int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t 
     if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
     if (stats && stats->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) { set_err(err, err_cap, "%s: stats->struct_size (%d) is not sizeof(llamahip_lookup_stats) (%d)", fn, stats->struct_size, (int) sizeof(llamahip_lookup_stats)); return LLAMAHIP_ERR_PREDICT; }
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    int rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+}
+
+int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
+                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                  int32_t *out_tokens, float *logits_last, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_greedy_lookup";
+    int rc = check_lookup_args(m, fn, n_past, first_token, n_steps, context, n_context, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap);
     if (rc) return rc;
+    const int V = m->hp.n_vocab;
     llamahip_lookup_stats ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
     if (lookup_dense(m)) {
         // f16 / f32 / Q4_1 files: no multi-row eval with every row's own key split -- nothing is drafted
@@ -2414,6 +2463,156 @@ int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t 
         return LLAMAHIP_ERR_PREDICT;
     }
     memcpy(out_tokens, h.data() + 64, (size_t) n_steps * 4);
+    if (stats) *stats = ls;
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Drafted SAMPLED decoding: llamahip_verify_sample / llamahip_decode_sample_lookup.  The reference's sampler is a deterministic function of
+// the row's logits, the last_n_tokens window and the mt19937 state; row j of a verify step holds the logits of the single-token eval at
+// n_past + j, and IF draft tokens 0 .. j - 1 were accepted the window at row j is the current one shifted by j with those tokens pushed --
+// known before the eval.  So the device selects every row's candidates under that window (launch_topk_slide on the last stage's stream,
+// in place of k_verify_rows / k_accept_drafts) and the host walks the rows with the real sampler: row 0, then row j + 1 only if row j's
+// draw was draft[j].  Exactly the rng draws and accepts of the token-by-token loop; only the number of weight passes changes.
+// ------------------------------------------------------------------------------------------------
+static int check_sampler_params(const char *fn, const llamahip_sampler *sampler, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
+    if (!sampler) { set_err(err, err_cap, "%s: null sampler", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (top_k < 1) { set_err(err, err_cap, "%s: top_k must be >= 1 (got %d)", fn, top_k); return LLAMAHIP_ERR_PREDICT; }
+    if (!(temp > 0.0)) { set_err(err, err_cap, "%s: temp must be > 0 (got %g)", fn, temp); return LLAMAHIP_ERR_PREDICT; }
+    if (!(repeat_penalty > 0.0)) { set_err(err, err_cap, "%s: repeat_penalty must be > 0 (got %g)", fn, repeat_penalty); return LLAMAHIP_ERR_PREDICT; }
+    if (top_p != top_p) { set_err(err, err_cap, "%s: top_p is NaN", fn); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+// handles whose verify step is a loop of single steps: f16 / f32 / Q4_1 files (no per-row key split in one pass) and LLAMAHIP_FLAG_UNFUSED
+static bool sample_lookup_by_rows(const llamahip_model *m) {
+    const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
+    return first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED) != 0;
+}
+// the documented single step: llamahip_eval_topk -> draw -> accept; *exact as llamahip_eval_topk reports it
+static int sample_single_step(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, llamahip_sampler *sampler, double repeat_penalty, int32_t top_k,
+                              double top_p, double temp, std::vector<int32_t> &win, std::vector<float> &logits, int32_t *pick, int32_t *exact, char *err, size_t err_cap) {
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    win.resize((size_t) std::max(llamahip_sampler_window(sampler, nullptr, 0), 1));
+    const int32_t nw = std::min(llamahip_sampler_window(sampler, win.data(), (int32_t) win.size()), (int32_t) win.size());
+    logits.resize((size_t) V);
+    double sc[64];
+    int32_t ids[64], ex = 0;
+    int rc = llamahip_eval_topk(m, n_threads, n_past, &token, 1, win.data(), nw, repeat_penalty, top_k, temp, sc, ids, &ex, logits.data(), err, err_cap);
+    if (rc) return rc;
+    *pick = ex == 1 ? llamahip_sample_from_candidates(sampler, sc, ids, k, top_p) : llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
+    llamahip_sampler_accept(sampler, *pick);
+    *exact = ex == 1 ? 1 : 0;
+    return 0;
+}
+
+static int verify_sample_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, llamahip_sampler *sampler,
+                              double repeat_penalty, int32_t top_k, double top_p, double temp, int32_t *n_accept, int32_t *picks, int32_t *exact,
+                              std::vector<int32_t> &win, std::vector<float> &logits, char *err, size_t err_cap) {
+    const int N = n_draft + 1, V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    for (int j = 0; j < N; j++) { picks[j] = -1; if (exact) exact[j] = -1; }
+    int rc;
+    if (N == 1 || sample_lookup_by_rows(m)) {
+        // one plain step -- and the handles without a one-pass verify eval: the rows one llamahip_eval_topk step at a time, stopping behind
+        // the first draw the draft does not continue with
+        int a = 0;
+        int32_t tok = token, ex = 0;
+        for (;; a++) {
+            if ((rc = sample_single_step(m, n_threads, n_past + a, tok, sampler, repeat_penalty, top_k, top_p, temp, win, logits, &picks[a], &ex, err, err_cap)) != 0) return rc;
+            if (exact) exact[a] = ex;
+            if (a == n_draft || picks[a] != draft[a]) break;
+            tok = draft[a];
+        }
+        *n_accept = a;
+        return LLAMAHIP_OK;
+    }
+    // the id stream: the sampler's window, then the draft (the last draft token is in no row's window)
+    const int32_t nw = llamahip_sampler_window(sampler, nullptr, 0);
+    const bool dev_sel = V <= 32768 && k <= 64 && nw <= 1024;
+    int32_t ids[1024 + VERIFY_ROWS_MAX], rows[VERIFY_ROWS_MAX];
+    TopkOut out[VERIFY_ROWS_MAX];
+    if (dev_sel) {
+        (void) llamahip_sampler_window(sampler, ids, nw);
+        for (int i = 0; i + 1 < N; i++) ids[nw + i] = draft[i];
+    }
+    rows[0] = token;
+    for (int i = 0; i < n_draft; i++) rows[1 + i] = draft[i];
+    const SlideReq sl = { ids, nw, 1.0 / temp, repeat_penalty, dev_sel ? k : 0, out };
+    if ((rc = verify_step(m, n_threads, n_past, rows, N, -1, nullptr, nullptr, err, err_cap, &sl)) != 0) return rc;
+    llamahip_model *last = m->stages.empty() ? m : m->stages.back();
+    int a = 0;
+    for (;; a++) {
+        const bool ex = dev_sel && out[a].fl[0] == 1;
+        if (ex) picks[a] = llamahip_sample_from_candidates(sampler, out[a].sc, out[a].id, k, top_p);
+        else {
+            // (the rows stay on the device until the next eval: a row the walk reaches and finds inexact is fetched now, that row only)
+            logits.resize((size_t) V);
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(logits.data(), last->logits + (size_t) a * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            picks[a] = llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
+        }
+        llamahip_sampler_accept(sampler, picks[a]);
+        if (exact) exact[a] = ex ? 1 : 0;
+        if (a == n_draft || picks[a] != draft[a]) break;
+    }
+    *n_accept = a;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_verify_sample(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft,
+                           llamahip_sampler *sampler, double repeat_penalty, int32_t top_k, double top_p, double temp,
+                           int32_t *n_accept, int32_t *picks, int32_t *exact, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_verify_sample";
+    int rc = check_sampler_params(fn, sampler, repeat_penalty, top_k, top_p, temp, err, err_cap);
+    if (rc) return rc;
+    if (!n_accept || !picks) { set_err(err, err_cap, "%s: null output", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_verify_args(m, n_past, token, draft, n_draft, fn, err, err_cap)) != 0) return rc;
+    std::vector<int32_t> win;
+    std::vector<float> logits;
+    return verify_sample_impl(m, n_threads, n_past, token, draft, n_draft, sampler, repeat_penalty, top_k, top_p, temp, n_accept, picks, exact, win, logits, err, err_cap);
+}
+
+int llamahip_decode_sample_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
+                                  int32_t draft_len, int32_t ngram_min, int32_t ngram_max, llamahip_sampler *sampler,
+                                  double repeat_penalty, int32_t top_k, double top_p, double temp,
+                                  int32_t *out_tokens, int32_t *out_exact, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_sample_lookup";
+    int rc = check_sampler_params(fn, sampler, repeat_penalty, top_k, top_p, temp, err, err_cap);
+    if (rc) return rc;
+    if ((rc = check_lookup_args(m, fn, n_past, first_token, n_steps, context, n_context, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap)) != 0) return rc;
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    llamahip_lookup_stats ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
+    // nothing is drafted where a verify step would stream the weights once per row anyway, or where every row would come back whole
+    const bool drafts = !sample_lookup_by_rows(m) && V <= 32768 && k <= 64 && llamahip_sampler_window(sampler, nullptr, 0) <= 1024;
+    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+    std::vector<int32_t> hist((size_t) n_past + n_steps + 1), win;
+    std::vector<float> logits;
+    if (n_past > 0) memcpy(hist.data(), context, (size_t) n_past * 4);
+    hist[n_past] = first_token;                     // hist[0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
+    int done = 0;
+    while (done < n_steps) {
+        const int pos = n_past + done;
+        int32_t draft[VERIFY_ROWS_MAX], n_acc = 0, picks[VERIFY_ROWS_MAX], exact[VERIFY_ROWS_MAX];
+        // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
+        const int room = drafts ? std::min(K, n_steps - done - 1) : 0;
+        const int nd = room > 0 ? llamahip_lookup_draft(hist.data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft) : 0;
+        if (nd < 0 || nd > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, nd, room); return LLAMAHIP_ERR_PREDICT; }
+        if (nd == 0) {
+            if ((rc = sample_single_step(m, n_threads, pos, hist[pos], sampler, repeat_penalty, top_k, top_p, temp, win, logits, &picks[0], &exact[0], err, err_cap)) != 0) return rc;
+            ls.n_single_steps++;
+        } else {
+            if ((rc = verify_sample_impl(m, n_threads, pos, hist[pos], draft, nd, sampler, repeat_penalty, top_k, top_p, temp, &n_acc, picks, exact, win, logits, err, err_cap)) != 0) return rc;
+            ls.n_verify_steps++;
+            ls.n_drafted += nd;
+            ls.n_accepted += n_acc;
+        }
+        for (int j = 0; j <= n_acc; j++) {
+            hist[pos + 1 + j] = picks[j];
+            out_tokens[done + j] = picks[j];
+            if (out_exact) out_exact[done + j] = exact[j];
+        }
+        done += n_acc + 1;
+    }
     if (stats) *stats = ls;
     return LLAMAHIP_OK;
 }

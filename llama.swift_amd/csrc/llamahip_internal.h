@@ -262,6 +262,10 @@ constexpr size_t TOPK_WS_BYTES = 32768 * 8 + 64 * 8 + 64;
 struct TopkOut { double sc[64]; int32_t id[64]; int32_t fl[2]; };          // fl[0] = exact, fl[1] = values collected
 hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *windows, const int32_t *n_last, double scale, double repeat_penalty,
                             int k, TopkOut *out, float *spill, hipStream_t st, void *ws);
+// ... with row r's window = ids[r .. r + n_last) of one id stream of n_last + R - 1 ids (llamahip_verify_sample, llamahip_op_topk_slide): refuses
+// n_last > 1024, V > 32768, k > 64; ws and out as above, no spill (the rows stay on the device until the next eval)
+hipError_t launch_topk_slide(const float *logits, int R, int V, const int32_t *ids, int n_last, double scale, double repeat_penalty, int k,
+                             TopkOut *out, hipStream_t st, void *ws);
 // next-token scoring of n_rows rows of logits (logprob.hip): per row the log-probability of targets[r] in double, the argmax (lowest index
 // on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,

@@ -247,6 +247,36 @@ int llamahip_op_topk_rows(const float *logits, int32_t n_rows, int32_t n_vocab, 
     return LLAMAHIP_OK;
 }
 
+// k_topk_keys_slide + k_topk_select_rows on caller-supplied rows (parity tests): see llamahip_verify_sample
+int llamahip_op_topk_slide(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *ids, int32_t n_last, double repeat_penalty,
+                           int32_t top_k, double temp, double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_topk_slide";
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: n_rows must be 1 .. %d (got %d): a verify step has at most %d rows", fn, VERIFY_ROWS_MAX, n_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_vocab < 1 || n_vocab > 32768) { set_err(err, err_cap, "%s: n_vocab must be 1 .. 32768 (got %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (top_k < 1 || top_k > 64 || top_k > n_vocab) { set_err(err, err_cap, "%s: top_k must be 1 .. min(64, n_vocab) (got %d, n_vocab %d)", fn, top_k, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_last < 0 || n_last > 1024) { set_err(err, err_cap, "%s: n_last must be 0 .. 1024 (got %d): the device takes windows of up to 1024 ids", fn, n_last); return LLAMAHIP_ERR_PREDICT; }
+    const size_t R = n_rows, V = n_vocab, n_ids = (size_t) n_last + R - 1;
+    if (!logits || !out_scores || !out_ids || !out_exact || (n_ids > 0 && !ids)) { set_err(err, err_cap, "%s: null argument", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!(temp > 0.0) || !(repeat_penalty > 0.0)) { set_err(err, err_cap, "%s: temp (%g) and repeat_penalty (%g) must be positive", fn, temp, repeat_penalty); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    std::vector<TopkOut> h(R);
+    Scratch s;
+    char *d_ws = s.alloc<char>(R * TOPK_WS_BYTES);
+    s.fill(d_ws, 0, R * TOPK_WS_BYTES);
+    float *d_l = s.alloc(R * V, logits);
+    int32_t *d_ids = s.alloc<int32_t>(n_ids + 1);
+    if (n_ids > 0) s.upload(d_ids, ids, n_ids * 4);
+    TopkOut *d_out = s.alloc<TopkOut>(R);
+    if (s.ok()) s.check(launch_topk_slide(d_l, n_rows, n_vocab, d_ids, n_last, 1.0 / temp, repeat_penalty, top_k, d_out, nullptr, d_ws));
+    s.download(h.data(), d_out, R * sizeof(TopkOut));
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (size_t r = 0; r < R; r++) {
+        out_exact[r] = h[r].fl[0];
+        for (int i = 0; i < top_k; i++) { out_scores[r * 64 + i] = h[r].sc[i]; out_ids[r * 64 + i] = h[r].id[i]; }
+    }
+    return LLAMAHIP_OK;
+}
+
 // k_row_logprob on caller-supplied rows (parity tests): see llamahip_eval_logprobs
 int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
                         double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap) {

@@ -38,6 +38,8 @@ struct llama_runner_bridge {
     llamahip_model *kept = nullptr;      // config.keepModel: the model of the previous run ...
     int32_t kept_n_ctx = 0;              // ... and the context size it was loaded with
     int64_t loads = 0;                   // model loads performed by this bridge (tests)
+    int32_t lookup = -1;                 // drafted sampled decoding: -1 never set (LLAMAHIP_RUNNER_LOOKUP decides), 0 off, 1 .. 15 the draft length
+    llamahip_lookup_stats lookup_stats = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };   // of the last run
 };
 
 // llama_sample_top_p_top_k from the soft-max on (utils.cpp:397-428): `cand` = the top_k candidates, best first
@@ -212,6 +214,14 @@ void llama_runner_bridge_free(llama_runner_bridge *b) {
 }
 int64_t llama_runner_bridge_loads(const llama_runner_bridge *b) { return b ? b->loads : 0; }
 const char *llama_runner_bridge_model_path(const llama_runner_bridge *b) { return b ? b->model_path.c_str() : nullptr; }
+void llama_runner_bridge_set_lookup(llama_runner_bridge *b, int32_t draft_len) {
+    if (b) b->lookup = std::min(std::max(draft_len, 0), 15);
+}
+int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, llamahip_lookup_stats *out) {
+    if (!b || !out || out->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) return -1;
+    *out = b->lookup_stats;
+    return 0;
+}
 
 int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, const llama_runner_config *config,
                                 llama_event_handler handler, void *user) {
@@ -229,6 +239,15 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
     const int32_t n_ctx = cfg.n_ctx > 0 ? cfg.n_ctx : 512;                          // .mm:790
     const int32_t n_threads = (int32_t) cfg.numberOfThreads;
     std::string prompt = prompt_c ? prompt_c : "";
+
+    // drafted sampled decoding: the setter's value, else LLAMAHIP_RUNNER_LOOKUP (the unchanged replacement bridge never calls the setter)
+    int32_t lookup = b->lookup;
+    if (lookup < 0) {
+        const char *e = getenv("LLAMAHIP_RUNNER_LOOKUP");
+        lookup = e ? std::min(std::max(atoi(e), 0), 15) : 0;
+    }
+    llamahip_lookup_stats &ls = b->lookup_stats;
+    ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
 
     char err[512] = { 0 };
     post(LLAMA_EVENT_STARTED_LOADING_MODEL, nullptr, 0, 0);                         // .mm:785
@@ -283,8 +302,36 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
     std::vector<int32_t> embd;
     int32_t n_past = 0, remaining = n_predict;
     size_t consumed = 0;
+    const bool lookup_on = lookup > 0 && !cfg.greedy && !host_sampler;
+    std::vector<int32_t> hist;                                                      // lookup: the prompt tokens + everything generated so far
+    if (lookup_on) hist = embd_inp;
     while (remaining > 0) {                                                         // .mm:834
         bool have_cand = false;
+        if (lookup_on && embd_inp.size() <= consumed && embd.size() == 1) {
+            // a lookup step: the pending token (drawn, accepted and posted) with a draft behind it as ONE eval; the sampler walks the rows
+            // exactly as the iterations below would have (llamahip_verify_sample) -- same draws, same window, same events
+            int32_t draft[15], picks[16], n_acc = 0;
+            const int32_t room = std::min(lookup, remaining - 1);
+            const int32_t nd = room > 0 ? llamahip_lookup_draft(hist.data(), (int32_t) hist.size(), nullptr, 0, room, 0, 0, draft) : 0;
+            if (nd > 0) {
+                if (llamahip_verify_sample(model, n_threads, n_past, embd[0], draft, nd, sampler, repeat_penalty, top_k, top_p, temp,
+                                           &n_acc, picks, nullptr, err, sizeof(err)) != 0) return fail();
+                n_past += n_acc + 1;
+                remaining -= n_acc + 1;
+                ls.n_verify_steps++;
+                ls.n_drafted += nd;
+                ls.n_accepted += n_acc;
+                for (int32_t j = 0; j <= n_acc; j++) {
+                    hist.push_back(picks[j]);
+                    uint32_t len = 0;
+                    const char *tok = llamahip_token_text(model, picks[j], &len);
+                    post(LLAMA_EVENT_OUTPUT_TOKEN, tok, len, 0);
+                }
+                embd[0] = picks[n_acc];
+                continue;
+            }
+            ls.n_single_steps++;
+        }
         if ((int32_t) embd.size() > n_batch + 1) {
             // a run of prompt chunks (gathered below): everything but the last chunk in ONE pass that leaves the KV cache exactly as the
             // reference's chunk-by-chunk evals do (llamahip_eval_chunks); the last chunk takes the usual route, its logits may be sampled
@@ -323,6 +370,7 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
             }
             llamahip_sampler_accept(sampler, id);
             embd.push_back(id);
+            if (lookup_on) hist.push_back(id);
             --remaining;
         } else {
             // .mm:880-888 hands the prompt over in chunks of n_batch + 1 tokens, one llama_eval each; here the whole rest of the prompt is

@@ -53,6 +53,9 @@ int llamahip_eval(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int3
 int llamahip_eval_chunks(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int32_t n, int32_t chunk, float *lg, char *err, size_t err_cap) { return fake_eval(m, 1, np, t, n, chunk, lg, err, err_cap); }
 int llamahip_eval_topk(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int32_t n, const int32_t *, int32_t, double, int32_t, double,
                        double *, int32_t *, int32_t *exact, float *lg, char *err, size_t err_cap) { *exact = 0; return fake_eval(m, 2, np, t, n, 0, lg, err, err_cap); }
+// (the driver's lookup steps are off here -- no setter call, no LLAMAHIP_RUNNER_LOOKUP -- so this is never reached)
+int llamahip_verify_sample(llamahip_model *, int32_t, int32_t, int32_t, const int32_t *, int32_t, llamahip_sampler *, double, int32_t, double, double,
+                           int32_t *, int32_t *, int32_t *, char *err, size_t err_cap) { snprintf(err, err_cap, "no HIP device available: libllamahip has no CPU fallback"); return LLAMAHIP_ERR_PREDICT; }
 }
 
 static int failures = 0;

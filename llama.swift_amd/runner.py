@@ -63,6 +63,23 @@ class LlamaRunner:
             self._bridge = C.c_void_p(L.llama_runner_bridge_new(self.modelURL.encode()))
         return L, self._bridge
 
+    def set_lookup(self, draft_len: int) -> None:
+        """Drafted sampled decoding in the generation loop (llama_runner_bridge_set_lookup): 0 = off, 1 .. 15 = drafts of up to that many tokens."""
+        L, bridge = self._get_bridge()
+        L.llama_runner_bridge_set_lookup.argtypes = [C.c_void_p, C.c_int32]
+        L.llama_runner_bridge_set_lookup.restype = None
+        L.llama_runner_bridge_set_lookup(bridge, int(draft_len))
+
+    def lookup_stats(self) -> dict:
+        """The lookup step counts of the last run (llama_runner_bridge_lookup_stats): all zero before the first run and with lookup off."""
+        L, bridge = self._get_bridge()
+        L.llama_runner_bridge_lookup_stats.argtypes = [C.c_void_p, C.POINTER(binding._LookupStats)]
+        L.llama_runner_bridge_lookup_stats.restype = C.c_int32
+        st = binding._LookupStats(C.sizeof(binding._LookupStats))
+        if L.llama_runner_bridge_lookup_stats(bridge, C.byref(st)) != 0:
+            raise RuntimeError("llama_runner_bridge_lookup_stats refused its arguments")
+        return {k: getattr(st, k) for k, _ in binding._LookupStats._fields_ if k != "struct_size"}
+
     @property
     def loads(self) -> int:
         """Model loads performed so far by this runner's bridge."""

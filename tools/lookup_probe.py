@@ -10,7 +10,13 @@
   ceiling  tokens/s of llamahip_decode_greedy_lookup with the true stream as corpus (everything it drafts is accepted)
   floor    ... with a drafter that never hits (n-grams longer than the context: all single steps, one host round trip per token)
 
+  sampled  (--sampled: the drafted SAMPLED loop, llamahip_verify_sample / llamahip_decode_sample_lookup, one process) ms per verify_sample call
+           of 2 / 4 / 8 / 16 rows at the three positions next to verify_greedy calls of the same rows in the same run, ms per single
+           llamahip_eval_topk step + draw (the loop with a drafter that never hits), breakeven against that step, and the loop's tokens/s
+           with the true stream as corpus and with no corpus (drafts from the tokens seen so far only)
+
     python tools/lookup_probe.py [--out profiles/lookup_probe_7b.json] [--parent-lib libllamahip_parent.so] [--reps 20]
+    python tools/lookup_probe.py --sampled [--out profiles/sample_lookup_probe_7b.json]
     python tools/lookup_probe.py --leg ceiling      (one leg in this process: for rocprofv3 --kernel-trace --stats)
 """
 import argparse
@@ -63,6 +69,8 @@ def leg(name, reps):
 
     import bench
     path = bench.model_path("7B", bench.MODELS["7B"], 20230312)
+    if name == "sampled":
+        return sampled_leg(reps)
     if name == "step":
         return step_leg(path, os.environ.get("LLAMAHIP_LIB", "libllamahip.so"))
     import llama_swift_amd as L
@@ -100,6 +108,68 @@ def leg(name, reps):
         return {"tok_s": STEPS / t, "ms_per_token": 1e3 * t / STEPS, "spread_ms_per_token": 1e3 * (max(ts) - min(ts)) / STEPS, "stats": st}
 
 
+def sampled_leg(reps):
+    import numpy as np
+
+    import bench
+    import llama_swift_amd as L
+    import synth
+    path = bench.model_path("7B", bench.MODELS["7B"], 20230312)
+    seed = 20230312
+
+    def start(m, prompt, plg):
+        s = L.Sampler(seed=seed, repeat_last_n=64)
+        for t in prompt:
+            s.accept(int(t))
+        first = s.sample(m, plg)
+        s.accept(first)
+        return s, first
+
+    def timed_loop(m, prompt, plg, G, **kw):
+        ts, st = [], None
+        for r in range(4):                              # (the first run is the warm-up)
+            s, first = start(m, prompt, plg)
+            t0 = time.perf_counter()
+            out, _, st = m.decode_sample_lookup(first, STEPS, P, prompt, s, n_threads=NTH, **kw)
+            if r:
+                ts.append(time.perf_counter() - t0)
+            assert G is None or out.tolist() == G
+        t = statistics.median(ts)
+        return out.tolist(), {"tok_s": STEPS / t, "ms_per_token": 1e3 * t / STEPS, "spread_ms_per_token": 1e3 * (max(ts) - min(ts)) / STEPS, "stats": st}
+
+    with L.Model(path, n_ctx=N_CTX) as m:
+        prompt = synth.synth_prompt(P, m.n_vocab, seed=4)
+        plg = m.eval(prompt, 0, NTH)
+        G, single = timed_loop(m, prompt, plg, None, ngram_min=4 * N_CTX, ngram_max=4 * N_CTX)      # never drafts: the eval_topk loop itself
+        res = {"single": single}
+        _, res["ceiling"] = timed_loop(m, prompt, plg, G, corpus=np.array(G, np.int32))
+        _, res["no_corpus"] = timed_loop(m, prompt, plg, G)
+        # verify steps, sampled next to greedy: wrong from the first draft token, so rows [pos, ..) stay re-usable
+        first = start(m, prompt, plg)[1]
+        S = [first] + G
+        tv = {"sample": {}, "greedy": {}}
+        s = L.Sampler(seed=seed, repeat_last_n=64)
+        for pos in (64, 256, 448):
+            i = pos - P
+            for N in (2, 4, 8, 16):
+                d = (np.array(S[i + 1:i + N], np.int32) + 1) % m.n_vocab
+                for kind, call in (("sample", lambda: m.verify_sample(S[i], d, pos, s, n_threads=NTH)), ("greedy", lambda: m.verify_greedy(S[i], d, pos, NTH))):
+                    call()
+                    ts = []
+                    for _ in range(reps):
+                        t0 = time.perf_counter()
+                        call()
+                        ts.append(1e3 * (time.perf_counter() - t0))
+                    tv[kind].setdefault(str(N), {})[str(pos)] = round(statistics.median(ts), 4)
+        res["t_verify_sample_ms"], res["t_verify_greedy_ms"] = tv["sample"], tv["greedy"]
+    t_step = res["single"]["ms_per_token"]
+    res["selection_ms"] = {N: round(statistics.mean(tv["sample"][N].values()) - statistics.mean(tv["greedy"][N].values()), 4) for N in tv["sample"]}
+    res["breakeven"] = {N: round((statistics.mean(tv["sample"][N].values()) / t_step - 1.0) / (int(N) - 1), 4) for N in tv["sample"]}
+    for name in ("ceiling", "no_corpus"):
+        res[name]["vs_single"] = round(res[name]["ms_per_token"] / t_step, 4)
+    return res
+
+
 def child(name, reps, lib=None):
     env = dict(os.environ)
     if lib:
@@ -116,9 +186,19 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--parent-lib", default="")
+    ap.add_argument("--sampled", action="store_true", help="the drafted sampled loop's leg alone (default --out profiles/sample_lookup_probe_7b.json)")
     a = ap.parse_args()
     if a.leg:
         print(json.dumps(leg(a.leg, a.reps)))
+        return
+    if a.sampled:
+        res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH,
+               "sampler": "repeat_penalty 1.3, top_k 40, top_p 0.95, temp 0.8, repeat_last_n 64"}
+        res.update(child("sampled", a.reps))
+        text = json.dumps(res, indent=1)
+        print(text)
+        with open(a.out or os.path.join(ROOT, "profiles", "sample_lookup_probe_7b.json"), "w") as f:
+            f.write(text + "\n")
         return
     res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH}
     res["step"] = child("step", a.reps)
