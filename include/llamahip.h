@@ -286,6 +286,56 @@ int32_t llamahip_lookup_draft(const int32_t *history, int32_t n_history, const i
 int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens,
                             int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
 
+/* ---- greedy decode with drafted tokens for several sequences at once (exact) ------------------------------------------------------
+ * llamahip_decode_greedy_multi steps up to 16 sequences as one set, one row each; llamahip_decode_greedy_lookup steps one sequence with up
+ * to 15 drafted rows.  The price of a step is set by the weight stream, not by its row count, so a server that holds 2 .. 8 conversations
+ * leaves 8 .. 14 rows of every set step unused: here they carry the sequences' drafts.  The rows of a step are cut into SEGMENTS, one per
+ * sequence -- [the slot's last token, its draft ...] at the slot's position and the ones behind it.  The kernels of a set step read a
+ * position, a KV-cache offset and a token per row and nothing in them requires the rows' slots to be distinct, so the step is the set
+ * step's launches on a descriptor built on the host, then k_verify_rows over all rows and k_accept_drafts_set (one wave per segment,
+ * llamahip_verify_greedy's rule): 4 (rows + segments) bytes come back, no logits row does.  Eager, as every verify step.
+ * (Norm statistics, as for set steps and verify steps: one pass in the fused single step, two in a multi-row step.  The equality of a
+ * segment's rows and single steps is therefore BY TEST (tests/test_gpu_lookup_multi.py), not by construction.)
+ *
+ * llamahip_verify_greedy_multi -- one step: for each i < n_seqs the rows [tokens[i], drafts of sequence i ...] of KV slot slots[i] at
+ *   n_past[i]; the drafts concatenated in sequence order, n_draft[i] of them (0 allowed); sum(n_draft[i] + 1) <= 16, slots distinct.
+ *   n_accept[i] and picks (concatenated, n_draft[i] + 1 each): llamahip_verify_greedy's, per sequence, and its KV contract per slot.
+ * llamahip_decode_greedy_lookup_multi -- the loop: llamahip_decode_greedy_multi's arguments and results (sequence i in KV slot i;
+ *   out_tokens[i * n_steps ..) and KV rows [0, n_past[i] + n_steps) of slot i: bit for bit llamahip_decode_greedy's on that slot alone; rows
+ *   at and above a slot's final context unspecified) with llamahip_decode_greedy_lookup's drafter: each sequence drafts from its own
+ *   history (contexts: concatenated, n_past[i] tokens each; its first token; everything it has produced), then from the shared corpus.  A
+ *   draft that would pass position n_past[i] + n_steps - 1 is cut; a sequence that has produced n_steps tokens leaves the step and its rows
+ *   become spare.  The spare rows of a step are dealt by llamahip_lookup_deal_rows.  A step in which nothing is drafted is the captured set
+ *   step (llamahip_stage_step_set; one active sequence: llamahip_stage_step) plus one host wait for the picks.  stats (may be NULL):
+ *   [n_seqs], struct_size set by the caller in each; per sequence n_steps = n_verify_steps + n_single_steps + n_accepted, a step in which
+ *   the sequence carried no draft counting as one of its single steps.  The handle's current slot (llamahip_set_seq) is left alone.
+ *   n_seqs = 1 is llamahip_decode_greedy_lookup on slot 0.
+ * Handles: plain and in-process pipeline handles; n_seqs 1 .. 16 and <= llamahip_opts.n_seq (more than 16: llamahip_decode_greedy_multi
+ *   -- a 16-row step has nothing to spare).  f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED handles and handles without a set step
+ *   (llamahip_stage_set_applies) run llamahip_decode_greedy_lookup / llamahip_verify_greedy on each slot in turn.  Stage handles and
+ *   HOST_ONLY handles are refused; the arguments are checked first, without a device.
+ * llamahip_lookup_deal_rows -- host only, no handle, a pure function: want[i] = the draft tokens sequence i could use (0 .. 15), budget =
+ *   the rows of the step (n_seqs .. 16).  Every sequence has its base row; the budget - n_seqs spare rows go one draft token at a time,
+ *   round-robin in ascending sequence order, to the sequences that still want more, until the spares are used up or nobody wants more.
+ *   give[i] <= want[i]; returns sum(give), -1 = bad arguments.  The token stream does not depend on the dealing, only the step counts do.
+ * llamahip_op_verify_rows_set -- the device half on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16,
+ *   tokens[n_rows], seg_begin[n_segs + 1] ascending from 0 to n_rows, n_segs 1 .. n_rows; n_accept[n_segs], picks[n_rows].
+ * Measured on the 7B, 2 / 4 / 8 sequences (profiles/lookup_multi_probe_7b.json, tools/lookup_probe.py --multi): a set step
+ *   takes 1.93 / 2.30 / 3.07 ms, a verify step over the set filled to 16 rows 4.1 .. 4.8 ms; the loop runs at 3652 / 3645 / 3573 tokens/s
+ *   aggregate when every draft is accepted, against 1037 / 1741 / 2603 for llamahip_decode_greedy_multi in the same run, and at
+ *   1025 / 1724 / 2583 when nothing is ever drafted -- about 1 % slower than llamahip_decode_greedy_multi: one host wait per step. */
+int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                                 const int32_t *tokens, const int32_t *drafts, const int32_t *n_draft, int32_t *n_accept /* [n_seqs] */,
+                                 int32_t *picks /* concatenated, n_draft[i] + 1 each */, char *err, size_t err_cap);
+int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                        int32_t n_steps, const int32_t *contexts /* concatenated, n_past[i] tokens each */,
+                                        const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                        int32_t *out_tokens /* [n_seqs][n_steps] */, llamahip_lookup_stats *stats /* [n_seqs], may be NULL */,
+                                        char *err, size_t err_cap);
+int32_t llamahip_lookup_deal_rows(const int32_t *want, int32_t n_seqs, int32_t budget, int32_t *give);
+int llamahip_op_verify_rows_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens, const int32_t *seg_begin,
+                                int32_t n_segs, int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
+
 /* ---- sampled decode with drafted tokens (exact) -----------------------------------------------------------------------------------
  * The same trade for the reference's sampler (llama_sample_top_p_top_k, .mm:851-870), which is what the bridge runs.  The sampler is a
  * deterministic function of the row's logits, the last_n_tokens window and the std::mt19937 state.  Row j of a verify step holds the logits

@@ -24,6 +24,7 @@ from .binding import (  # noqa: F401
     declared_symbols,
     gemm_paths,
     lib,
+    lookup_deal_rows,
     lookup_draft,
     op_attention,
     op_embed,
@@ -36,6 +37,7 @@ from .binding import (  # noqa: F401
     op_topk_rows,
     op_topk_slide,
     op_verify_rows,
+    op_verify_rows_set,
     qa_to_blocks,
     quantize_file,
     gemv_plan,

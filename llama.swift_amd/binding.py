@@ -123,6 +123,11 @@ def lib() -> C.CDLL:
     L.llamahip_lookup_draft.argtypes = [vp, i32, vp, i32, i32, i32, i32, vp]
     L.llamahip_lookup_draft.restype = i32
     L.llamahip_op_verify_rows.argtypes = [vp, i32, i32, vp, vp, vp, cp, sz]
+    L.llamahip_op_verify_rows_set.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, cp, sz]
+    L.llamahip_verify_greedy_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_decode_greedy_lookup_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, cp, sz]
+    L.llamahip_lookup_deal_rows.argtypes = [vp, i32, i32, vp]
+    L.llamahip_lookup_deal_rows.restype = i32
     L.llamahip_decode_greedy_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, cp, sz]
     L.llamahip_decode_sample_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, cp, sz]
     L.llamahip_eval_debug.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, vp, C.c_int64, vp, cp, sz]
@@ -512,6 +517,46 @@ class Model:
         _check(rc, err)
         return out
 
+    def verify_greedy_multi(self, slots, tokens, drafts, n_past, n_threads: int = 8):
+        """llamahip_verify_greedy_multi: one step whose rows are, per sequence i, [tokens[i], *drafts[i]] of KV slot slots[i] at n_past[i]
+        (drafts: one sequence of ids per slot, empty allowed).  Returns (n_accept int32[n_seqs], picks: one int32 array per sequence)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        drafts = [np.ascontiguousarray(d, np.int32).ravel() for d in drafts]
+        if not (slots.size == tokens.size == npast.size == len(drafts)):
+            raise ValueError(f"verify_greedy_multi: {slots.size} slots, {tokens.size} tokens, {npast.size} n_past, {len(drafts)} drafts")
+        nd = np.array([d.size for d in drafts], np.int32)
+        flat = np.concatenate(drafts).astype(np.int32) if int(nd.sum()) else np.zeros(1, np.int32)
+        n_acc = np.full(slots.size, -1, np.int32)
+        picks = np.full(int(nd.sum()) + slots.size, -1, np.int32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_verify_greedy_multi(self._h, n_threads, slots.size, _ptr(slots), _ptr(npast), _ptr(tokens), _ptr(flat), _ptr(nd), _ptr(n_acc),
+                                                _ptr(picks), err, len(err))
+        _check(rc, err)
+        cut = np.cumsum(nd + 1)[:-1]
+        return n_acc, np.split(picks, cut)
+
+    def decode_greedy_lookup_multi(self, first_tokens, n_past, n_steps: int, contexts, corpus=None, draft_len: int = 0, ngram_min: int = 0,
+                                   ngram_max: int = 0, n_threads: int = 8, stats_size: int | None = None):
+        """llamahip_decode_greedy_lookup_multi: sequences in KV slots 0 .. len(first_tokens) - 1 decoded together, the spare rows of every step
+        carrying drafts (contexts: one sequence of n_past[i] ids per sequence).  Returns (tokens [n_seqs][n_steps], one stats dict per sequence)."""
+        ft = np.ascontiguousarray(first_tokens, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        ctx = [np.ascontiguousarray(c, np.int32).ravel() for c in contexts]
+        flat = np.concatenate(ctx).astype(np.int32) if sum(c.size for c in ctx) else None
+        corpus = None if corpus is None else np.ascontiguousarray(corpus, np.int32).ravel()
+        out = np.empty((ft.size, max(n_steps, 0)), np.int32)
+        st = (_LookupStats * max(ft.size, 1))()
+        for x in st:
+            x.struct_size = C.sizeof(_LookupStats) if stats_size is None else stats_size
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_greedy_lookup_multi(self._h, n_threads, ft.size, _ptr(npast), _ptr(ft), n_steps, _ptr(flat), _ptr(corpus),
+                                                       0 if corpus is None else corpus.size, draft_len, ngram_min, ngram_max, _ptr(out),
+                                                       C.cast(st, C.c_void_p), err, len(err))
+        _check(rc, err)
+        return out, [{k: getattr(x, k) for k, _ in _LookupStats._fields_ if k != "struct_size"} for x in st[:ft.size]]
+
     def decode_sample_multi(self, first_tokens, n_past, n_steps: int, samplers, repeat_penalty: float = 1.3, top_k: int = 40,
                             top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), n_threads: int = 8,
                             want_exact: bool = False):
@@ -698,6 +743,38 @@ def lookup_draft(history, corpus=None, draft_len: int = 0, ngram_min: int = 0, n
     if n < 0:
         raise ValueError(f"lookup_draft: bad arguments (draft_len {draft_len}, ngram_min {ngram_min}, ngram_max {ngram_max})")
     return out[:n].copy()
+
+
+def lookup_deal_rows(want, budget: int = 16) -> np.ndarray:
+    """llamahip_lookup_deal_rows (host only): the draft tokens each sequence of a step gets -- every sequence has its base row, the
+    budget - n_seqs spare rows go one at a time, round-robin in ascending order, to the sequences that still want more."""
+    want = np.ascontiguousarray(want, np.int32).ravel()
+    give = np.zeros(max(want.size, 1), np.int32)
+    n = lib().llamahip_lookup_deal_rows(_ptr(want), want.size, budget, _ptr(give))
+    if n < 0:
+        raise ValueError(f"lookup_deal_rows: bad arguments ({want.size} sequences, budget {budget}, want {want.tolist()})")
+    return give[:want.size].copy()
+
+
+def op_verify_rows_set(logits2d, tokens, seg_begin):
+    """k_verify_rows + k_accept_drafts_set on host rows f32 [n_rows, n_vocab] (1 .. 16 rows) cut into the segments [seg_begin[s], seg_begin[s + 1]):
+    a segment's first token its last token, the rest its draft.  Returns (n_accept int32[n_segs], picks int32[n_rows])."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+    seg_begin = np.ascontiguousarray(seg_begin, np.int32).ravel()
+    if tokens.size != R:
+        raise ValueError(f"tokens: {tokens.size} ids for {R} rows")
+    if seg_begin.size < 2:
+        raise ValueError("seg_begin: at least one segment")
+    n_segs = seg_begin.size - 1
+    picks, n_acc = np.full(R, -1, np.int32), np.full(n_segs, -1, np.int32)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_verify_rows_set(_ptr(logits2d), R, V, _ptr(tokens), _ptr(seg_begin), n_segs, _ptr(n_acc), _ptr(picks), err, len(err))
+    _check(rc, err)
+    return n_acc, picks
 
 
 def op_verify_rows(logits2d, tokens):

@@ -127,6 +127,19 @@ std::vector<double> lh::rope_table(int n_ctx, int dh) {
     return sc;
 }
 
+// The step descriptor of a verify step over a set (llamahip_verify_greedy_multi): a SeqSet whose rows take their position and token from the
+// per-row words behind it instead of a bound slot's -- set.state[r] points at state[r], set.tok_in[r] at tok[r] -- so the launches of a set step
+// (forward_set) run it unchanged; the segments, the rows' picks and the result follow.  Built on the host up to `pick`, lives in device memory.
+struct VsetBlock {
+    SeqSet set;
+    int32_t state[SET_MAX][2];          // row r: {position, unused}
+    int32_t tok[SET_MAX];               // row r's token: a segment's first row the slot's last token, the rest its draft
+    int32_t seg_begin[SET_MAX + 1];     // segment s = rows [seg_begin[s], seg_begin[s + 1])
+    int32_t seg_slot[SET_MAX];
+    int32_t pick[SET_MAX];              // (device) k_verify_rows
+    int32_t res[2 * SET_MAX];           // (device) k_accept_drafts_set: {n_accept[n_segs], pick[n_rows]}
+};
+
 // ------------------------------------------------------------------------------------------------
 // the model handle
 // ------------------------------------------------------------------------------------------------
@@ -161,7 +174,8 @@ struct llamahip_model {
     // single-token evals through the C ABI: token, sampler window and candidate results live in ONE pinned, device-mapped host
     // block that the kernels read / write directly (three ~4 us blit copies per sampled token otherwise)
     struct HostIo { int32_t tok[16]; int32_t window[1024]; double sc[64]; int32_t id[64]; int32_t fl[2];
-                    int32_t slide[1024 + VERIFY_ROWS_MAX]; TopkOut rows[VERIFY_ROWS_MAX]; };      // (a sampled verify step: its id stream in, its rows' candidates out)
+                    int32_t slide[1024 + VERIFY_ROWS_MAX]; TopkOut rows[VERIFY_ROWS_MAX];      // (a sampled verify step: its id stream in, its rows' candidates out)
+                    VsetBlock vset; };             // (a verify step over a set: its descriptor out, vset.res back)
     HostIo *h_io = nullptr, *d_io = nullptr;       // host pointer / its device alias
     const int32_t *tok_src = nullptr;              // set by eval_impl around forward(): where the embedding kernel finds the token
     float *x = nullptr, *x1 = nullptr, *qkv = nullptr, *qr = nullptr, *merged = nullptr, *gu = nullptr;
@@ -190,6 +204,7 @@ struct llamahip_model {
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
     char *d_slide = nullptr;             // sampled verify step (last stage): 16 x TOPK_WS_BYTES of selection workspace | the id stream (SLIDE_IDS_BYTES) | 16 TopkOut (slide_ensure)
+    VsetBlock *d_vset = nullptr;         // a verify step over a set: the step's descriptor (vset_step)
     int32_t *d_verify = nullptr;         // drafted greedy decoding (last stage): {position, cursor} | 16 row tokens | 16 picks | {n_accept, 16 picks} | from [64]: the token log, n_ctx entries (verify_io)
     uint32_t *d_attn_sync = nullptr;     // per-head hand-off counters of k_dec_attn_x ([H][32] dwords); null: two-launch attention
     uint64_t *d_qkv2 = nullptr, *d_sc2 = nullptr;   // tagged hand-off buffers of k_qkv_attn: [3 d] and [H][n_ctx] {fp32 bits, tag} granules
@@ -290,7 +305,7 @@ llamahip_model::~llamahip_model() {
     free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
     free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
     free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_slide);
+    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_vset); free_dev(d_slide);
     free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
     free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
     free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
@@ -1622,7 +1637,8 @@ namespace {
 // llama_eval's graph works row by row (.mm:563-705), so row b is bit for bit a single-token llama_eval of its sequence: its own
 // position in RoPE / the KV append / the causal range, its own cache, and the V*P key split of ITS eval, n_past_b + 1 keys over
 // n_threads (ggml.c:5459-5480).  The weights are streamed once per step for all rows.
-static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys = 0) {
+// (tail = false, a verify step over a set: the rows stay where they are -- logits on the last stage, m->x on the others -- and no slot advances)
+static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys = 0, bool tail = true) {
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
     hipStream_t st = m->stream;
@@ -1654,8 +1670,8 @@ static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *e
     if (m->last_stage) {
         HIP_TRY(launch_prep(PREP_NORM, m->x, m->norm_w, d, 0, d, B, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);          // .mm:695-705
         HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, B, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_argmax_set(m->logits, V, d_set, B, st), LLAMAHIP_ERR_PREDICT);
-    } else {
+        if (tail) HIP_TRY(launch_argmax_set(m->logits, V, d_set, B, st), LLAMAHIP_ERR_PREDICT);
+    } else if (tail) {
         HIP_TRY(launch_rows_set(d_set, B, m->x, d, false, st), LLAMAHIP_ERR_PREDICT);
         HIP_TRY(launch_advance_set(d_set, B, st), LLAMAHIP_ERR_PREDICT);
     }
@@ -2375,7 +2391,7 @@ int llamahip_verify_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
 // the arguments of the two lookup loops (greedy and sampled), checked without a device; the handle last
 static int check_lookup_args(llamahip_model *m, const char *fn, int32_t n_past, int32_t first_token, int32_t n_steps, const int32_t *context, int32_t n_context,
                              const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max, const int32_t *out_tokens,
-                             const llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+                             const llamahip_lookup_stats *stats, char *err, size_t err_cap, bool handle = true) {      // handle = false: the arguments alone
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     const int V = m->hp.n_vocab, C = m->hp.n_ctx;
     if (n_steps < 1 || n_past < 0 || n_past > C - n_steps) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past, n_steps, C); return LLAMAHIP_ERR_PREDICT; }
@@ -2395,6 +2411,7 @@ static int check_lookup_args(llamahip_model *m, const char *fn, int32_t n_past, 
     }
     if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
     if (stats && stats->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) { set_err(err, err_cap, "%s: stats->struct_size (%d) is not sizeof(llamahip_lookup_stats) (%d)", fn, stats->struct_size, (int) sizeof(llamahip_lookup_stats)); return LLAMAHIP_ERR_PREDICT; }
+    if (!handle) return 0;
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
     return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
 }
@@ -2731,6 +2748,327 @@ static int decode_greedy_multi_impl(llamahip_model *m, int32_t n_threads, int32_
 int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
                                  int32_t *out_tokens, char *err, size_t err_cap) {
     return decode_greedy_multi_impl(m, n_threads, n_seqs, n_past, first_tokens, n_steps, out_tokens, err, err_cap);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Drafted greedy decoding for SEVERAL sequences at once: llamahip_verify_greedy_multi / llamahip_decode_greedy_lookup_multi.  A set step has 16
+// rows and costs what its weight stream costs; with 2 .. 8 sequences most rows are unused, and here they carry the sequences' drafts.  The rows
+// of such a step are cut into SEGMENTS, one per sequence: segment i = [last token of slot i, its draft ...] at positions p_i, p_i + 1, ...  The
+// kernels of the set path read three things per row -- position, KV offset, token -- and nothing in them requires the rows' slots to be
+// distinct: rows r .. r + j that share one kv_off and hold positions p .. p + j make row r + j the single-token eval of that slot at p + j (its
+// K / V rows are appended by the launch before the score launch, as in a multi-row eval; every row runs the V*P key split of its own
+// single-token eval).  So the step is forward_set on a descriptor built on the host (VsetBlock), then k_verify_rows over all rows and
+// k_accept_drafts_set, one wave per segment: 4 (rows + segments) bytes come back.  Eager, like every verify step.
+// (Equality with single steps is BY TEST -- tests/test_gpu_lookup_multi.py -- not structural: the norm's one-pass against two-pass statistics,
+//  as for set steps and verify steps.)
+// ------------------------------------------------------------------------------------------------
+struct VsetReq {
+    int n_segs = 0, n_rows = 0;
+    int32_t slot[SET_MAX], pos[SET_MAX];        // per segment: KV slot, position of its first row
+    int32_t seg_begin[SET_MAX + 1];
+    int32_t rows[SET_MAX];                      // the rows' tokens
+    bool bound = false;                         // the slots are bound (the loop): logs, {position, cursor} and next-token words are kept on the device
+};
+
+static std::vector<llamahip_model *> stages_of(llamahip_model *m) { return m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages; }
+
+// every stage takes set steps of 2 .. 16 rows with this n_threads (else: the callers' per-slot fall-back)
+static bool vset_applies(const std::vector<llamahip_model *> &stages, int n_threads) {
+    for (const llamahip_model *st : stages)
+        for (int n = 2; n <= SET_MAX; n++) if (!llamahip_stage_set_applies(st, n, n_threads)) return false;
+    return true;
+}
+
+static int vset_ensure(llamahip_model *st, bool first, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+    int rc = ensure_workspace(st, SET_MAX, err, err_cap);
+    if (rc) return rc;
+    const size_t H = st->hp.n_head, C = st->hp.n_ctx;
+    if (!st->set_sc) HIP_TRY(hipMalloc((void **) &st->set_sc, (size_t) SET_MAX * H * C * 4), LLAMAHIP_ERR_PREDICT);
+    if (!st->d_vset) {
+        HIP_TRY(hipMalloc((void **) &st->d_vset, sizeof(VsetBlock)), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemset(st->d_vset, 0, sizeof(VsetBlock)), LLAMAHIP_ERR_PREDICT);
+    }
+    if (!first && (rc = pipe_ensure_in(st, SET_MAX, err, err_cap)) != 0) return rc;
+    return 0;
+}
+
+// one verify step over a set on a Q4_0 handle, plain or pipeline; res: {n_accept[n_segs], picks[n_rows]}
+static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &stages, int32_t n_threads, const VsetReq &rq, int32_t *res, char *err, size_t err_cap) {
+    const double t0 = now_ms();
+    const int S = (int) stages.size(), R = rq.n_rows, G = rq.n_segs;
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const int C = m->hp.n_ctx, V = m->hp.n_vocab;
+    const size_t d = m->hp.n_embd;
+    const int nth = std::max(1, std::min(n_threads, 64));
+    int rc, max_pos = 0;
+    for (int g = 0; g < G; g++) max_pos = std::max(max_pos, rq.pos[g] + rq.seg_begin[g + 1] - rq.seg_begin[g] - 1);
+    if (R < 2 || R > SET_MAX || G < 1 || G > R || max_pos >= C) { set_err(err, err_cap, "verify step over a set: %d rows in %d segments up to position %d", R, G, max_pos); return LLAMAHIP_ERR_PREDICT; }
+    const int set_keys = std::min(C, (max_pos / 128 + 1) * 128);            // (llamahip_stage_step_set's key bucket, exact for this step)
+    for (int s = 0; s < S; s++) if ((rc = vset_ensure(stages[s], s == 0, err, err_cap)) != 0) return rc;
+    auto bail = [&](int r) { (void) pipe_sync_stages(stages, nullptr, 0); return r; };
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        VsetBlock *dv = st->d_vset;
+        std::vector<char> pageable;
+        VsetBlock *hb = st->h_io ? &st->h_io->vset : nullptr;      // (the stream is idle: every entry point synchronises before it returns)
+        if (!hb) { pageable.resize(sizeof(VsetBlock)); hb = (VsetBlock *) pageable.data(); }
+        memset(hb, 0, offsetof(VsetBlock, pick));
+        hb->set.n = R;
+        for (int g = 0; g < G; g++) {
+            hb->seg_begin[g] = rq.seg_begin[g];
+            hb->seg_slot[g] = rq.slot[g];
+            for (int r = rq.seg_begin[g]; r < rq.seg_begin[g + 1]; r++) {
+                hb->set.state[r] = dv->state[r];
+                hb->set.tok_in[r] = &dv->tok[r];
+                hb->set.hid_in[r] = s ? st->pipe_in + (size_t) r * d : nullptr;
+                hb->set.kv_off[r] = (long) ((size_t) rq.slot[g] * (st->l1 - st->l0) * C * d);
+                hb->state[r][0] = rq.pos[g] + (r - rq.seg_begin[g]);
+                hb->tok[r] = rq.rows[r];
+            }
+        }
+        hb->seg_begin[G] = R;
+        // (pinned: stream-ordered; else the synchronous copy, done before the launches below are enqueued)
+        if ((st->h_io ? hipMemcpyAsync(dv, hb, offsetof(VsetBlock, pick), hipMemcpyHostToDevice, st->stream)
+                      : hipMemcpy(dv, hb, offsetof(VsetBlock, pick), hipMemcpyHostToDevice)) != hipSuccess) { set_err(err, err_cap, "HIP error copying the step descriptor"); return bail(LLAMAHIP_ERR_PREDICT); }
+        if ((rc = forward_set(st, nth, &dv->set, R, err, err_cap, set_keys, false)) != 0) return bail(rc);
+        if (s + 1 < S && (rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) R * d * 4, err, err_cap)) != 0) return bail(rc);
+    }
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    VsetBlock *dv = last->d_vset;
+    int32_t *d_res = last->h_io ? last->d_io->vset.res : dv->res;
+    int32_t *next_tok = S == 1 ? first->mq_tok : last->mq_tok;
+    if (rq.bound && (!last->d_slot_state || !last->d_slot_trace || !next_tok)) { set_err(err, err_cap, "verify step over a set: the slots are not bound"); return bail(LLAMAHIP_ERR_PREDICT); }
+    if (launch_verify_rows(last->logits, R, V, dv->pick, last->stream) != hipSuccess ||
+        launch_accept_drafts_set(dv->tok, dv->pick, dv->seg_begin, dv->seg_slot, G, R, rq.bound ? last->d_slot_state : nullptr, rq.bound ? last->d_slot_trace : nullptr,
+                                 C, rq.bound ? next_tok : nullptr, d_res, last->stream) != hipSuccess) {
+        set_err(err, err_cap, "HIP error launching the verify kernels of a set step");
+        return bail(LLAMAHIP_ERR_PREDICT);
+    }
+    if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    if (last->h_io) memcpy(res, last->h_io->vset.res, (size_t) (R + G) * 4);
+    else HIP_TRY(hipMemcpy(res, dv->res, (size_t) (R + G) * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    for (int g = 0; g < G; g++) {
+        const int nd = rq.seg_begin[g + 1] - rq.seg_begin[g] - 1;
+        if (res[g] < 0 || res[g] > nd) { set_err(err, err_cap, "verify step over a set: the device reported %d accepted of %d drafted tokens for slot %d", res[g], nd, rq.slot[g]); return LLAMAHIP_ERR_PREDICT; }
+    }
+    last->last_rows.clear();
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+static int check_multi_handle(llamahip_model *m, const char *fn, int32_t n_seqs, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (n_seqs > SET_MAX) { set_err(err, err_cap, "%s: n_seqs must be 1 .. %d (got %d): a step of %d rows has none to spare for drafts, use llamahip_decode_greedy_multi", fn, SET_MAX, n_seqs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_seqs < 1) { set_err(err, err_cap, "%s: n_seqs must be 1 .. %d (got %d)", fn, SET_MAX, n_seqs); return LLAMAHIP_ERR_PREDICT; }
+    const int have = (m->stages.empty() ? m : m->stages[0])->n_seq;
+    if (n_seqs > have) { set_err(err, err_cap, "%s: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", fn, n_seqs, have); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+
+int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                                 const int32_t *drafts, const int32_t *n_draft, int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_verify_greedy_multi";
+    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
+    if (rc) return rc;
+    if (!slots || !n_past || !tokens || !n_draft) { set_err(err, err_cap, "%s: null slots / n_past / tokens / n_draft", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!n_accept || !picks) { set_err(err, err_cap, "%s: null output", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int V = m->hp.n_vocab, C = m->hp.n_ctx, have = (m->stages.empty() ? m : m->stages[0])->n_seq;
+    VsetReq rq;
+    int n_rows = 0, n_dr = 0;
+    for (int i = 0; i < n_seqs; i++) {
+        if (slots[i] < 0 || slots[i] >= have) { set_err(err, err_cap, "%s: sequence slot %d out of range [0, %d)", fn, slots[i], have); return LLAMAHIP_ERR_PREDICT; }
+        for (int j = 0; j < i; j++) if (slots[j] == slots[i]) { set_err(err, err_cap, "%s: sequence slot %d appears twice in the step", fn, slots[i]); return LLAMAHIP_ERR_PREDICT; }
+        if (n_draft[i] < 0 || n_draft[i] > VERIFY_ROWS_MAX - 1) { set_err(err, err_cap, "%s: n_draft must be 0 .. %d (got %d for slot %d): a verify step has at most %d rows", fn, VERIFY_ROWS_MAX - 1, n_draft[i], slots[i], VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+        if (n_past[i] < 0 || n_past[i] > C - n_draft[i] - 1) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_draft (%d) + 1 > n_ctx (%d)", fn, n_past[i], n_draft[i], C); return LLAMAHIP_ERR_PREDICT; }
+        if (tokens[i] < 0 || tokens[i] >= V) { set_err(err, err_cap, "%s: token id %d out of range [0, %d)", fn, tokens[i], V); return LLAMAHIP_ERR_PREDICT; }
+        n_rows += n_draft[i] + 1;
+        if (n_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: a verify step has at most %d rows (%d sequences with their drafts make more)", fn, VERIFY_ROWS_MAX, i + 1); return LLAMAHIP_ERR_PREDICT; }
+        if (n_draft[i] > 0 && !drafts) { set_err(err, err_cap, "%s: null drafts", fn); return LLAMAHIP_ERR_PREDICT; }
+        for (int j = 0; j < n_draft[i]; j++)
+            if (drafts[n_dr + j] < 0 || drafts[n_dr + j] >= V) { set_err(err, err_cap, "%s: draft token id %d at %d out of range [0, %d)", fn, drafts[n_dr + j], n_dr + j, V); return LLAMAHIP_ERR_PREDICT; }
+        rq.slot[i] = slots[i]; rq.pos[i] = n_past[i]; rq.seg_begin[i] = n_rows - n_draft[i] - 1;
+        rq.rows[rq.seg_begin[i]] = tokens[i];
+        for (int j = 0; j < n_draft[i]; j++) rq.rows[rq.seg_begin[i] + 1 + j] = drafts[n_dr + j];
+        n_dr += n_draft[i];
+    }
+    rq.seg_begin[n_seqs] = n_rows; rq.n_segs = n_seqs; rq.n_rows = n_rows;
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    if (n_rows == 1 || lookup_dense(m) || (stages[0]->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads)) {
+        // no set step on this handle (or one row): llamahip_verify_greedy on each slot in turn
+        const int save_seq = m->cur_seq;
+        for (int i = 0, od = 0, op = 0; i < n_seqs && rc == 0; od += n_draft[i], op += n_draft[i] + 1, i++)
+            if ((rc = llamahip_set_seq(m, slots[i], err, err_cap)) == 0)
+                rc = verify_greedy_impl(m, n_threads, n_past[i], tokens[i], drafts + od, n_draft[i], n_past[i], &n_accept[i], picks + op, nullptr, err, err_cap);
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
+    }
+    int32_t res[2 * SET_MAX];
+    if ((rc = vset_step(m, stages, n_threads, rq, res, err, err_cap)) != 0) return rc;
+    memcpy(n_accept, res, (size_t) n_seqs * 4);
+    memcpy(picks, res + n_seqs, (size_t) n_rows * 4);
+    return LLAMAHIP_OK;
+}
+
+// one step of the loop in which nothing is drafted: the captured set step (one active slot: the single step) on the bound slots, stage by stage
+static int multi_plain_step(const std::vector<llamahip_model *> &stages, const std::vector<int32_t> &act, int32_t n_seqs, int32_t n_threads, char *err, size_t err_cap) {
+    const int S = (int) stages.size(), gn = (int) act.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const size_t d = first->hp.n_embd;
+    int rc = 0;
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[0], 0), LLAMAHIP_ERR_PREDICT);
+        if (gn >= 2) rc = llamahip_stage_step_set(st, act.data(), gn, n_threads, st->stream, err, err_cap);
+        else rc = llamahip_stage_step(st, act[0], n_threads, st->stream, err, err_cap);
+        if (rc) return rc;
+        if (S == 1) break;
+        // (every slot's row / token word travels: the words of the slots that sat the step out are not read before they are written again)
+        llamahip_model *to = s + 1 < S ? stages[s + 1] : first;
+        void *dst = s + 1 < S ? (void *) to->mq_in : (void *) first->mq_tok;
+        const void *src = s + 1 < S ? (const void *) st->mq_out : (const void *) last->mq_tok;
+        const size_t bytes = s + 1 < S ? (size_t) n_seqs * d * 4 : (size_t) n_seqs * 4;
+        if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
+        else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, bytes, st->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipEventRecord(st->mq_ev[0], st->stream), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+
+int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
+                                        const int32_t *contexts, const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                        int32_t *out_tokens, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_greedy_lookup_multi";
+    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
+    if (rc) return rc;
+    if (!n_past || !first_tokens) { set_err(err, err_cap, "%s: null n_past / first_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    std::vector<size_t> coff(n_seqs + 1, 0);
+    for (int i = 0; i < n_seqs; i++) {
+        if (n_past[i] < 0) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        coff[i + 1] = coff[i] + (size_t) n_past[i];
+    }
+    for (int i = 0; i < n_seqs; i++)
+        if ((rc = check_lookup_args(m, fn, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, i == 0 ? n_corpus : 0, draft_len, ngram_min,
+                                    ngram_max, out_tokens, stats ? stats + i : nullptr, err, err_cap, false)) != 0) return rc;
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], first_tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const int save_seq = m->cur_seq;
+    if (n_seqs == 1 || lookup_dense(m) || (first->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads)) {
+        // one sequence, or no set step on this handle: llamahip_decode_greedy_lookup on each slot in turn
+        for (int i = 0; i < n_seqs && rc == 0; i++)
+            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
+                rc = llamahip_decode_greedy_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, n_corpus,
+                                                   draft_len, ngram_min, ngram_max, out_tokens + (size_t) i * n_steps, nullptr, stats ? stats + i : nullptr, err, err_cap);
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
+    }
+    const double t0 = now_ms();
+    const size_t d = m->hp.n_embd;
+    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, 1, err, err_cap)) != 0) return rc;
+    HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(first->mq_tok, first_tokens, (size_t) n_seqs * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        for (int i = 0; i < n_seqs; i++)        // (llamahip_decode_greedy_multi's binding: sequence i in slot i, its token word fed by the last stage's pick)
+            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->mq_tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
+                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, s + 1 == S ? (S == 1 ? first->mq_tok + i : last->mq_tok + i) : nullptr, err, err_cap)) != 0) return rc;
+    }
+    std::vector<std::vector<int32_t>> hist(n_seqs);      // hist[i][0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
+    std::vector<int> done(n_seqs, 0);
+    std::vector<llamahip_lookup_stats> ls(n_seqs, llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 });
+    for (int i = 0; i < n_seqs; i++) {
+        hist[i].resize((size_t) n_past[i] + n_steps + 1);
+        if (n_past[i] > 0) memcpy(hist[i].data(), contexts + coff[i], (size_t) n_past[i] * 4);
+        hist[i][n_past[i]] = first_tokens[i];
+    }
+    std::vector<int32_t> act, words(n_seqs), st2((size_t) 2 * n_seqs);
+    for (;;) {
+        act.clear();
+        for (int i = 0; i < n_seqs; i++) if (done[i] < n_steps) act.push_back(i);
+        if (act.empty()) break;
+        const int A = (int) act.size();
+        int32_t want[SET_MAX], give[SET_MAX], draft[SET_MAX][VERIFY_ROWS_MAX];
+        for (int a = 0; a < A; a++) {
+            const int i = act[a], pos = n_past[i] + done[i];
+            // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
+            const int room = std::min(K, n_steps - done[i] - 1);
+            want[a] = room > 0 ? llamahip_lookup_draft(hist[i].data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft[a]) : 0;
+            if (want[a] < 0 || want[a] > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, want[a], room); return LLAMAHIP_ERR_PREDICT; }
+        }
+        const int dealt = llamahip_lookup_deal_rows(want, A, SET_MAX, give);
+        if (dealt < 0) { set_err(err, err_cap, "%s: dealing the rows of a step failed", fn); return LLAMAHIP_ERR_PREDICT; }
+        if (dealt == 0) {
+            if ((rc = multi_plain_step(stages, act, n_seqs, n_threads, err, err_cap)) != 0) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
+            if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+            llamahip_model *src = S == 1 ? first : last;
+            HIP_TRY(hipSetDevice(src->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(words.data(), src->mq_tok, (size_t) n_seqs * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            for (int a = 0; a < A; a++) {
+                const int i = act[a];
+                hist[i][n_past[i] + done[i] + 1] = words[i];
+                done[i]++;
+                ls[i].n_single_steps++;
+            }
+            continue;
+        }
+        VsetReq rq;
+        rq.bound = true; rq.n_segs = A;
+        int R = 0;
+        for (int a = 0; a < A; a++) {
+            const int i = act[a];
+            rq.slot[a] = i; rq.pos[a] = n_past[i] + done[i]; rq.seg_begin[a] = R;
+            rq.rows[R++] = hist[i][rq.pos[a]];
+            for (int j = 0; j < give[a]; j++) rq.rows[R++] = draft[a][j];
+        }
+        rq.seg_begin[A] = R; rq.n_rows = R;
+        int32_t res[2 * SET_MAX];
+        if ((rc = vset_step(m, stages, n_threads, rq, res, err, err_cap)) != 0) return rc;
+        for (int a = 0; a < A; a++) {
+            const int i = act[a], na = res[a];
+            for (int j = 0; j <= na; j++) hist[i][rq.pos[a] + 1 + j] = res[A + rq.seg_begin[a] + j];
+            done[i] += na + 1;
+            if (give[a] > 0) { ls[i].n_verify_steps++; ls[i].n_drafted += give[a]; ls[i].n_accepted += na; }
+            else ls[i].n_single_steps++;
+            for (llamahip_model *st : stages) st->slots[i].next_pos += na + 1;      // (the host's mirror of the position the accept kernel advanced)
+        }
+        if (S > 1) {
+            // the last stage's accept kernel advanced ITS slot words; the other stages' positions and the first stage's token words follow from the host
+            for (int i = 0; i < n_seqs; i++) { st2[2 * i] = n_past[i] + done[i]; st2[2 * i + 1] = done[i]; words[i] = hist[i][n_past[i] + done[i]]; }
+            for (int s = 0; s + 1 < S; s++) {
+                HIP_TRY(hipSetDevice(stages[s]->device), LLAMAHIP_ERR_PREDICT);
+                HIP_TRY(hipMemcpy(stages[s]->d_slot_state, st2.data(), st2.size() * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+            }
+            HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(first->mq_tok, words.data(), (size_t) n_seqs * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+        }
+    }
+    // the result is each slot's device log, checked against what the host saw step by step
+    std::vector<int32_t> log(n_steps);
+    for (int i = 0; i < n_seqs; i++) {
+        int32_t pos = 0;
+        const int n = llamahip_stage_trace(last, i, &pos, log.data(), n_steps, err, err_cap);
+        if (n < 0) return n;
+        if (done[i] != n_steps || n != n_steps || pos != n_past[i] + n_steps || memcmp(log.data(), hist[i].data() + n_past[i] + 1, (size_t) n_steps * 4) != 0) {
+            set_err(err, err_cap, "%s: the device log of sequence %d holds %d tokens up to position %d, the host counted %d of %d up to %d", fn, i, n, pos, done[i], n_steps, n_past[i] + n_steps);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        memcpy(out_tokens + (size_t) i * n_steps, log.data(), (size_t) n_steps * 4);
+        if (stats) stats[i] = ls[i];
+    }
+    m->t_eval_ms += now_ms() - t0;
+    if (!m->stages.empty()) m->pipe_hand_off = 1;
+    return LLAMAHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

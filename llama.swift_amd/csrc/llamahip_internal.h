@@ -279,5 +279,10 @@ constexpr int VERIFY_ROWS_MAX = 16;
 hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st);
 hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int pick_imm, int n_rows, int restart_pos, int32_t *log, int log_cap,
                                 int32_t *state, int32_t *res, hipStream_t st);
+// ... for the rows of several sequences in one step: segment s = rows [seg_begin[s], seg_begin[s + 1]) of slot seg_slot[s] (seg_begin ascending from 0
+// to n_rows: checked by the caller), res = {n_accept[n_segs], pick[n_rows]}.  state / log / next_tok (all or none): the bound slots' {position,
+// cursor} [slot][2], token logs [slot][log_cap] and next-token words [slot], advanced / appended / set per segment.
+hipError_t launch_accept_drafts_set(const int32_t *tokens, const int32_t *pick, const int32_t *seg_begin, const int32_t *seg_slot, int n_segs, int n_rows,
+                                    int32_t *state, int32_t *log, int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st);
 
 }  // namespace lh

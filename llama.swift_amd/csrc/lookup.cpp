@@ -1,4 +1,5 @@
-// lookup.cpp -- the drafter of llamahip_decode_greedy_lookup (include/llamahip.h): prompt-lookup drafting, pure host code, no handle.
+// lookup.cpp -- the drafter of llamahip_decode_greedy_lookup (include/llamahip.h): prompt-lookup drafting, pure host code, no handle;
+// and the dealing of a multi-sequence verify step's spare rows (llamahip_lookup_deal_rows).
 // The guess for "what comes next" is "what came next the last time the text ended like this": the last n tokens are looked up in the
 // tokens seen so far, then in a caller-supplied corpus, longest n first.  Deterministic; a wrong guess costs speed, never a token.
 #include <stdint.h>
@@ -39,4 +40,19 @@ extern "C" int32_t llamahip_lookup_draft(const int32_t *history, int32_t n_histo
         return k;
     }
     return 0;
+}
+
+// Every sequence has its base row; the budget - n_seqs spare rows go one draft token at a time, round-robin in ascending sequence order, to
+// the sequences that still want more, until the spares are used up or nobody wants more.
+extern "C" int32_t llamahip_lookup_deal_rows(const int32_t *want, int32_t n_seqs, int32_t budget, int32_t *give) {
+    if (!want || !give || n_seqs < 1 || n_seqs > 16 || budget < n_seqs || budget > 16) return -1;
+    for (int i = 0; i < n_seqs; i++) if (want[i] < 0 || want[i] > 15) return -1;
+    for (int i = 0; i < n_seqs; i++) give[i] = 0;
+    int spare = budget - n_seqs, dealt = 0;
+    for (bool any = true; spare > 0 && any;) {
+        any = false;
+        for (int i = 0; i < n_seqs && spare > 0; i++)
+            if (give[i] < want[i]) { give[i]++; spare--; dealt++; any = true; }
+    }
+    return dealt;
 }

@@ -326,6 +326,34 @@ int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab
     return LLAMAHIP_OK;
 }
 
+// k_verify_rows + k_accept_drafts_set on caller-supplied rows cut into segments (parity tests): see llamahip_verify_greedy_multi
+int llamahip_op_verify_rows_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens, const int32_t *seg_begin, int32_t n_segs,
+                                int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_verify_rows_set";
+    if (!logits || !tokens || !seg_begin || n_vocab < 1) { set_err(err, err_cap, "%s: bad arguments (null pointer or n_vocab %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: n_rows must be 1 .. %d (got %d): a verify step has at most %d rows", fn, VERIFY_ROWS_MAX, n_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_segs < 1 || n_segs > n_rows) { set_err(err, err_cap, "%s: n_segs must be 1 .. n_rows (%d; got %d)", fn, n_rows, n_segs); return LLAMAHIP_ERR_PREDICT; }
+    if (seg_begin[0] != 0 || seg_begin[n_segs] != n_rows) { set_err(err, err_cap, "%s: seg_begin must run from 0 to n_rows (%d; got %d .. %d)", fn, n_rows, seg_begin[0], seg_begin[n_segs]); return LLAMAHIP_ERR_PREDICT; }
+    for (int s = 0; s < n_segs; s++)
+        if (seg_begin[s + 1] <= seg_begin[s]) { set_err(err, err_cap, "%s: seg_begin must ascend strictly (segment %d: %d .. %d)", fn, s, seg_begin[s], seg_begin[s + 1]); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, S = (size_t) n_segs;
+    int32_t h[2 * VERIFY_ROWS_MAX] = { 0 };
+    Scratch s;
+    int32_t *d_v = s.alloc<int32_t>(96);      // tokens | picks | seg_begin (17) at [32] | result at [64]
+    s.fill(d_v, 0, 96 * 4);
+    float *d_l = s.alloc(N * (size_t) n_vocab, logits);
+    if (s.ok()) s.upload(d_v, tokens, N * 4);
+    if (s.ok()) s.upload(d_v + 32, seg_begin, (S + 1) * 4);
+    if (s.ok()) s.check(launch_verify_rows(d_l, n_rows, n_vocab, d_v + 16, nullptr));
+    if (s.ok()) s.check(launch_accept_drafts_set(d_v, d_v + 16, d_v + 32, nullptr, n_segs, n_rows, nullptr, nullptr, 0, nullptr, d_v + 64, nullptr));
+    if (s.ok()) s.download(h, d_v + 64, (N + S) * 4);
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (n_accept) memcpy(n_accept, h, S * 4);
+    if (picks) memcpy(picks, h + S, N * 4);
+    return LLAMAHIP_OK;
+}
+
 // one launch_prep on caller-supplied rows, the kernel family chosen by the caller (per-op tests of the activation producers): see llamahip.h
 int llamahip_op_prep(int32_t mode, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
                      int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, uint32_t *qa_A, float *qa_d, int32_t qa_rows,

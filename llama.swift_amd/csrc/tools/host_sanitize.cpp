@@ -188,6 +188,23 @@ int main(int argc, char **argv) {
         if (mv) llamahip_model_free(mv);
         g_drive = false;
     }
+    // the dealing of a multi-sequence verify step's rows: exactly sized arrays, every n_seqs and budget, and the refusals
+    for (int n = 1; n <= 16; n++)
+        for (int budget = n; budget <= 16; budget++)
+            for (int it = 0; it < 8; it++) {
+                std::vector<int32_t> want((size_t) n), give((size_t) n, -7);
+                int sum_want = 0;
+                for (int i = 0; i < n; i++) { want[i] = (int32_t) (rng() % (it % 2 ? 16 : 3)); sum_want += want[i]; }
+                const int32_t dealt = llamahip_lookup_deal_rows(want.data(), n, budget, give.data());
+                int sum = 0;
+                for (int i = 0; i < n; i++) { EXPECT(give[i] >= 0 && give[i] <= want[i]); sum += give[i]; }
+                EXPECT(dealt == sum && sum == std::min(budget - n, sum_want));
+            }
+    {
+        int32_t w[2] = { 1, 16 }, g[2] = { 0, 0 };
+        EXPECT(llamahip_lookup_deal_rows(w, 2, 16, g) == -1 && llamahip_lookup_deal_rows(w, 1, 0, g) == -1 && llamahip_lookup_deal_rows(w, 17, 16, g) == -1);
+        EXPECT(llamahip_lookup_deal_rows(nullptr, 1, 16, g) == -1 && llamahip_lookup_deal_rows(w, 1, 16, nullptr) == -1 && llamahip_lookup_deal_rows(w, 1, 17, g) == -1);
+    }
     printf("host_sanitize: %zu tensor bytes merged, tokenizer + sampler + bridge failure path exercised: %s\n", total, failures ? "FAILED" : "clean");
     return failures ? 1 : 0;
 }

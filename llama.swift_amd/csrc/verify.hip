@@ -16,6 +16,13 @@
 //   log[cursor .. cursor + n_accept] = pick[0 .. n_accept]; state = {position, cursor}, both advanced by n_accept + 1
 //   res = {n_accept, pick[0 .. N)}      (res: the pinned, device-mapped host block where the handle has one)
 // Plain loads and stores, no hand-offs between workgroups: the launch boundary orders the two kernels.
+// k_accept_drafts_set: the same rule for the rows of SEVERAL sequences in one step (llamahip_verify_greedy_multi /
+//   llamahip_decode_greedy_lookup_multi / llamahip_op_verify_rows_set), one wave per segment.  Segment s is the rows
+//   [seg_begin[s], seg_begin[s + 1]) of KV slot seg_slot[s]: its first row the slot's last token, the rest its draft.  Per segment
+//   n_accept as above; with slot words (state != null: the slots are bound, llamahip_stage_bind) the slot's token log receives
+//   pick[0 .. n_accept] at the slot's cursor, the slot's {position, cursor} advance by n_accept + 1 and the slot's next-token word
+//   receives pick[n_accept] -- an ordinary set step or single step continues the slot from there.
+//   res = {n_accept[0 .. n_segs), pick[0 .. n_rows)}: 4 (n_rows + n_segs) bytes for the host.
 #include <cmath>
 
 #include "kcommon.hip.h"
@@ -94,6 +101,32 @@ k_accept_drafts(const int32_t *__restrict__ tokens, const int32_t *__restrict__ 
     }
 }
 
+// one wave per segment (blockIdx.x); slot words: state [slot][2], log [slot][log_cap], next_tok [slot] -- all three or none
+__global__ void __launch_bounds__(64)
+k_accept_drafts_set(const int32_t *__restrict__ tokens, const int32_t *__restrict__ pick, const int32_t *__restrict__ seg_begin,
+                    const int32_t *__restrict__ seg_slot, int n_segs, int n_rows, int32_t *__restrict__ state, int32_t *__restrict__ log,
+                    int log_cap, int32_t *__restrict__ next_tok, int32_t *__restrict__ res) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int b = seg_begin[s], N = seg_begin[s + 1] - b;
+    if (b < 0 || N < 1 || b + N > n_rows) return;                 // (the host refuses such segments before the launch)
+    const int p = lane < N ? pick[b + lane] : 0;
+    const bool agree = lane < N - 1 && p == tokens[b + lane + 1];
+    const unsigned long long miss = ~__ballot(agree);
+    const int n_accept = min((int) __builtin_ctzll(miss), N - 1);
+    if (lane < N) res[n_segs + b + lane] = p;
+    if (lane == 0) res[s] = n_accept;
+    if (!state) return;
+    const int slot = seg_slot[s];
+    int32_t *st = state + 2 * (size_t) slot;
+    const int pos = st[0], cur = st[1];                           // (every lane reads before lane 0 writes: one wave, program order)
+    if (lane <= n_accept && cur >= 0 && cur + lane < log_cap) log[(size_t) slot * log_cap + cur + lane] = p;
+    if (lane == n_accept) next_tok[slot] = p;
+    if (lane == 0) {
+        st[0] = pos + n_accept + 1;
+        st[1] = cur + n_accept + 1;
+    }
+}
+
 hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st) {
     if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || V < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_verify_rows, dim3((unsigned) n_rows), dim3(1024), 0, st, logits, V, pick);
@@ -105,6 +138,16 @@ hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int 
                                 int32_t *state, int32_t *res, hipStream_t st) {
     if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || !log || !state || !res || (!pick && n_rows != 1) || (n_rows > 1 && !tokens)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_accept_drafts, dim3(1), dim3(64), 0, st, tokens, pick, pick_imm, n_rows, restart_pos, log, log_cap, state, res);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_accept_drafts_set(const int32_t *tokens, const int32_t *pick, const int32_t *seg_begin, const int32_t *seg_slot, int n_segs, int n_rows,
+                                    int32_t *state, int32_t *log, int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st) {
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || n_segs < 1 || n_segs > n_rows || !tokens || !pick || !seg_begin || !res) return hipErrorInvalidValue;
+    if (state && (!log || !next_tok || !seg_slot || log_cap < 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_accept_drafts_set, dim3((unsigned) n_segs), dim3(64), 0, st, tokens, pick, seg_begin, seg_slot, n_segs, n_rows, state, log, log_cap,
+                       next_tok, res);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -15,8 +15,16 @@
            llamahip_eval_topk step + draw (the loop with a drafter that never hits), breakeven against that step, and the loop's tokens/s
            with the true stream as corpus and with no corpus (drafts from the tokens seen so far only)
 
+  multi    (--multi: drafted greedy decoding for several sequences at once, llamahip_verify_greedy_multi / llamahip_decode_greedy_lookup_multi,
+           one process) for 2 / 4 / 8 sequences: ms per step of llamahip_decode_greedy_multi (a captured set step, one row per sequence)
+           against ms per llamahip_verify_greedy_multi call filled to 16 rows at the three positions (wrong drafts), and the loop's aggregate
+           tokens/s with the true streams as corpus (every draft accepted) and with a drafter that never hits (set steps + one host wait
+           each), next to llamahip_decode_greedy_multi of the same run for the same sequences.  --parent-lib NAME measures
+           llamahip_decode_greedy_multi of a second library file in csrc/ (a build of the parent commit) the same way, in its own process
+
     python tools/lookup_probe.py [--out profiles/lookup_probe_7b.json] [--parent-lib libllamahip_parent.so] [--reps 20]
     python tools/lookup_probe.py --sampled [--out profiles/sample_lookup_probe_7b.json]
+    python tools/lookup_probe.py --multi [--out profiles/lookup_multi_probe_7b.json] [--parent-lib libllamahip_parent.so]
     python tools/lookup_probe.py --leg ceiling      (one leg in this process: for rocprofv3 --kernel-trace --stats)
 """
 import argparse
@@ -71,6 +79,8 @@ def leg(name, reps):
     path = bench.model_path("7B", bench.MODELS["7B"], 20230312)
     if name == "sampled":
         return sampled_leg(reps)
+    if name == "multi":
+        return multi_leg(reps)
     if name == "step":
         return step_leg(path, os.environ.get("LLAMAHIP_LIB", "libllamahip.so"))
     import llama_swift_amd as L
@@ -170,6 +180,122 @@ def sampled_leg(reps):
     return res
 
 
+MULTI_SEQS, MULTI_SLOTS = (2, 4, 8), 8
+
+
+def multi_parent_leg(path, lib_name):
+    """llamahip_decode_greedy_multi for 2 / 4 / 8 sequences through bare ctypes calls, so that a library file without the new entry points
+    (the parent commit's) runs the same code"""
+    import ctypes as C
+
+    import numpy as np
+
+    import synth
+    lib = C.CDLL(os.path.join(ROOT, "llama.swift_amd", "csrc", lib_name))
+    vp, i32, cp, sz = C.c_void_p, C.c_int32, C.c_char_p, C.c_size_t
+
+    class Opts(C.Structure):          # the head of llamahip_opts: struct_size says how much of it is there
+        _fields_ = [("struct_size", i32), ("device", i32), ("layer_begin", i32), ("layer_end", i32), ("n_parts", i32), ("flags", i32), ("n_seq", i32)]
+    lib.llamahip_model_load.argtypes = [cp, i32, vp, C.POINTER(vp), cp, sz]
+    lib.llamahip_eval.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
+    lib.llamahip_set_seq.argtypes = [vp, i32, cp, sz]
+    lib.llamahip_decode_greedy_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, cp, sz]
+    lib.llamahip_model_free.argtypes = [vp]
+    err, h = C.create_string_buffer(1024), vp()
+    o = Opts(C.sizeof(Opts), -1, 0, -1, 0, 0, MULTI_SLOTS)
+    if lib.llamahip_model_load(path.encode(), N_CTX, C.byref(o), C.byref(h), err, len(err)) != 0:
+        raise RuntimeError(err.value.decode())
+    logits, firsts = np.empty(32000, np.float32), []
+    for i in range(MULTI_SLOTS):
+        prompt = synth.synth_prompt(P, 32000, seed=4 + i)
+        if lib.llamahip_set_seq(h, i, err, len(err)) != 0 or lib.llamahip_eval(h, NTH, 0, prompt.ctypes.data_as(vp), P, logits.ctypes.data_as(vp), err, len(err)) != 0:
+            raise RuntimeError(err.value.decode())
+        firsts.append(int(np.argmax(logits)))
+    res = {"lib": lib_name}
+    for n in MULTI_SEQS:
+        ft, npast, out, ts = np.array(firsts[:n], np.int32), np.full(n, P, np.int32), np.empty((n, STEPS), np.int32), []
+        for r in range(4):                              # (the first run is the warm-up: graph capture)
+            t0 = time.perf_counter()
+            if lib.llamahip_decode_greedy_multi(h, NTH, n, npast.ctypes.data_as(vp), ft.ctypes.data_as(vp), STEPS, out.ctypes.data_as(vp), err, len(err)) != 0:
+                raise RuntimeError(err.value.decode())
+            if r:
+                ts.append(time.perf_counter() - t0)
+        t = statistics.median(ts)
+        res[str(n)] = {"tok_s": round(n * STEPS / t, 1), "ms_per_step": round(1e3 * t / STEPS, 4), "spread_ms_per_step": round(1e3 * (max(ts) - min(ts)) / STEPS, 4)}
+    lib.llamahip_model_free(h)
+    return res
+
+
+def multi_leg(reps):
+    import numpy as np
+
+    import bench
+    import llama_swift_amd as L
+    import synth
+    path = bench.model_path("7B", bench.MODELS["7B"], 20230312)
+    if os.environ.get("LLAMAHIP_LIB"):
+        return multi_parent_leg(path, os.environ["LLAMAHIP_LIB"])
+
+    def timed(call, n):
+        ts = []
+        for r in range(4):                              # (the first run is the warm-up)
+            t0 = time.perf_counter()
+            ret = call()
+            if r:
+                ts.append(time.perf_counter() - t0)
+        t = statistics.median(ts)
+        return ret, {"tok_s": round(n * STEPS / t, 1), "ms_per_token": round(1e3 * t / (n * STEPS), 4), "spread_ms_per_token": round(1e3 * (max(ts) - min(ts)) / (n * STEPS), 4)}
+
+    res = {}
+    with L.Model(path, n_ctx=N_CTX, n_seq=MULTI_SLOTS) as m:
+        prompts = [synth.synth_prompt(P, m.n_vocab, seed=4 + i) for i in range(MULTI_SLOTS)]
+        firsts, S = [], []
+        for i in range(MULTI_SLOTS):
+            m.set_seq(i)
+            firsts.append(int(np.argmax(m.eval(prompts[i], 0, NTH))))
+            S.append([firsts[i]] + m.decode_greedy(firsts[i], P, STEPS, NTH).tolist())          # (the slot keeps the true rows)
+        m.set_seq(0)
+        for n in MULTI_SEQS:
+            G = [s[1:] for s in S[:n]]
+            npast, r = [P] * n, {}
+            out, r["decode_greedy_multi"] = timed(lambda: m.decode_greedy_multi(firsts[:n], npast, STEPS, NTH), n)
+            assert out.tolist() == G
+            r["set_step_ms"] = round(r["decode_greedy_multi"]["ms_per_token"] * n, 4)
+            # a verify step over the set filled to 16 rows: wrong from the first draft token, so rows [pos, ..) stay re-usable
+            rows = [16 // n + (1 if i < 16 % n else 0) for i in range(n)]
+            tv = {}
+            for pos in (64, 256, 448):
+                i0 = pos - P
+                drafts = [(np.array(S[i][i0 + 1:i0 + rows[i]], np.int32) + 1) % m.n_vocab for i in range(n)]
+                call = lambda: m.verify_greedy_multi(range(n), [S[i][i0] for i in range(n)], drafts, [pos] * n, NTH)
+                call()
+                ts = []
+                for _ in range(reps):
+                    t0 = time.perf_counter()
+                    call()
+                    ts.append(1e3 * (time.perf_counter() - t0))
+                tv[str(pos)] = round(statistics.median(ts), 4)
+                for i in range(n):                                                            # the true rows back
+                    m.set_seq(i)
+                    m.decode_greedy(S[i][i0], pos, STEPS - i0, NTH)
+            m.set_seq(0)
+            r["rows_per_sequence"], r["verify_set_step_16_rows_ms"] = rows, tv
+            r["verify_set_over_set_step"] = round(statistics.mean(tv.values()) / r["set_step_ms"], 4)
+            (out, st), r["loop_all_accepted"] = timed(lambda: m.decode_greedy_lookup_multi(firsts[:n], npast, STEPS, prompts[:n], corpus=np.concatenate([np.array(g, np.int32) for g in G]),
+                                                                                           n_threads=NTH), n)
+            assert out.tolist() == G
+            r["loop_all_accepted"]["stats"] = st
+            (out, st), r["loop_nothing_drafted"] = timed(lambda: m.decode_greedy_lookup_multi(firsts[:n], npast, STEPS, prompts[:n], ngram_min=4 * N_CTX, ngram_max=4 * N_CTX,
+                                                                                              n_threads=NTH), n)
+            assert out.tolist() == G and all(x["n_verify_steps"] == 0 for x in st)
+            base = r["decode_greedy_multi"]["tok_s"]
+            r["loop_all_accepted"]["vs_decode_greedy_multi"] = round(r["loop_all_accepted"]["tok_s"] / base, 4)
+            r["loop_nothing_drafted"]["vs_decode_greedy_multi"] = round(r["loop_nothing_drafted"]["tok_s"] / base, 4)
+            r["loop_nothing_drafted"]["slower_than_decode_greedy_multi"] = r["loop_nothing_drafted"]["tok_s"] < base      # (it pays one host wait per step)
+            res[str(n)] = r
+    return {"sequences": res}
+
+
 def child(name, reps, lib=None):
     env = dict(os.environ)
     if lib:
@@ -187,9 +313,20 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--parent-lib", default="")
     ap.add_argument("--sampled", action="store_true", help="the drafted sampled loop's leg alone (default --out profiles/sample_lookup_probe_7b.json)")
+    ap.add_argument("--multi", action="store_true", help="the multi-sequence drafted loop's leg alone (default --out profiles/lookup_multi_probe_7b.json)")
     a = ap.parse_args()
     if a.leg:
         print(json.dumps(leg(a.leg, a.reps)))
+        return
+    if a.multi:
+        res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH, "kv_slots": MULTI_SLOTS}
+        res.update(child("multi", a.reps))
+        if a.parent_lib:
+            res["parent_decode_greedy_multi"] = child("multi", a.reps, a.parent_lib)
+        text = json.dumps(res, indent=1)
+        print(text)
+        with open(a.out or os.path.join(ROOT, "profiles", "lookup_multi_probe_7b.json"), "w") as f:
+            f.write(text + "\n")
         return
     if a.sampled:
         res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH,
