@@ -70,7 +70,8 @@ typedef struct llamahip_opts {
  * process (.mm:790; LlamaRunnerBridge.mm:18-26).  A handle loaded with n_devices > 1 -- or, for a caller that passes no options such as the
  * replacement bridge, with the environment variable LLAMAHIP_DEVICES="0,1,...,7" (or a count: "8" = devices 0 .. 7) -- holds one stage per
  * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_eval_logprobs / llamahip_perplexity / llamahip_decode_greedy /
- * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_verify_sample / llamahip_decode_sample_lookup / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
+ * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_verify_sample / llamahip_decode_sample_lookup /
+ * llamahip_verify_sample_multi / llamahip_decode_sample_lookup_multi / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
  * crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
  * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
@@ -380,6 +381,66 @@ int llamahip_decode_sample_lookup(llamahip_model *m, int32_t n_threads, int32_t 
 int llamahip_op_topk_slide(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *ids, int32_t n_last,
                            double repeat_penalty, int32_t top_k, double temp,
                            double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap);
+
+/* ---- sampled decode with drafted tokens for several sequences at once ---------------------------------------------------------------
+ * The eighth cell of {greedy, sampled} x {one sequence, several} x {plain, drafted}, and the one a server uses: the bridge never decodes
+ * greedily (.mm:851-870).  Two halves that exist above meet here.  ROWS: a verify step over a set evaluates rows cut into per-slot segments,
+ * every row the single-token eval of its slot at its own position (llamahip_verify_greedy_multi).  SAMPLER: the sampler is a deterministic
+ * function of (row logits, last_n_tokens window, mt19937 state) and the window at row j of a segment is known before the eval
+ * (llamahip_verify_sample).  So behind the set step's launches the device selects every row's candidates -- k_topk_keys_slide_set +
+ * k_topk_select_rows on the last stage's stream, in place of k_verify_rows + k_accept_drafts_set: every segment slides inside its own id
+ * stream (that sequence's window, then its draft) of one id pool, addressed through a per-row table of at most 16 entries that the host
+ * builds -- and the host walks every segment with that sequence's own sampler exactly as llamahip_verify_sample walks its rows.  The accept
+ * step is the host's: what a segment accepts depends on draws of a host-side mt19937, so no device kernel can count it, and the loop keeps
+ * the slots' device words in step from the host.  Eager, as every verify step.
+ * (Norm statistics, as for set steps and verify steps: one pass in the fused single step, two in a multi-row step.  The equality of a
+ * segment's rows and single steps is therefore BY TEST (tests/test_gpu_sample_lookup_multi.py), not by construction.)
+ *
+ * llamahip_verify_sample_multi -- one step: llamahip_verify_greedy_multi's arguments (slots distinct, sum(n_draft[i] + 1) <= 16, context
+ *   overflow per slot) plus one sampler per sequence (distinct, none NULL; llamahip_verify_sample's parameter checks), all checked first,
+ *   without a device.  samplers[i] has already accepted tokens[i].  Per sequence llamahip_verify_sample's contract holds: n_accept[i]; picks
+ *   and exact (concatenated, n_draft[i] + 1 each; exact may be NULL; -1 in both behind the walk); the sampler's window and rng state; KV
+ *   rows [n_past[i], n_past[i] + n_accept[i] + 1) of slot slots[i] -- bit for bit.  A reached row flagged inexact is fetched alone from the
+ *   device and drawn by llamahip_sample_top_p_top_k; where the device cannot make candidates for a sequence (a window longer than 1024
+ *   ids) or for any (top_k > 64, n_vocab > 32768) those rows are drawn from their logits.
+ * llamahip_decode_sample_lookup_multi -- the loop: llamahip_decode_greedy_lookup_multi's arguments, refusals, drafter, draft cut, dealing
+ *   (llamahip_lookup_deal_rows) and stats identity (per sequence n_steps = n_verify_steps + n_single_steps + n_accepted), with one sampler
+ *   per sequence as above.  A sequence whose sampler window exceeds 1024 ids wants no draft; with top_k > 64 or n_vocab > 32768 nobody
+ *   drafts.  A step in which nothing is dealt is llamahip_decode_sample_multi's step: the captured set step (one active sequence: the
+ *   single step), the candidate selection over the active rows and the host draw.  After a verify step the host writes the slots'
+ *   {position, cursor} words on every stage before the next captured step continues them.  Per sequence, bit for bit the loop
+ *   llamahip_eval_topk -> draw -> accept on that slot alone: out_tokens[i * n_steps ..), the sampler's window and rng state, KV rows
+ *   [0, n_past[i] + n_steps) of slot i.  out_exact [n_seqs][n_steps] (may be NULL): that loop's flags on a PLAIN handle -- every row here,
+ *   of plain and of verify steps, is selected on the last stage's device, on pipeline handles too (unlike llamahip_decode_sample_lookup,
+ *   whose single steps report 0 there).  The handle's current slot (llamahip_set_seq) is left alone.  n_seqs = 1 is
+ *   llamahip_decode_sample_lookup on slot 0.
+ * Handles: plain and in-process pipeline handles; n_seqs 1 .. 16 and <= llamahip_opts.n_seq (more than 16: llamahip_decode_sample_multi).
+ *   f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED handles, handles without a set step (llamahip_stage_set_applies) and a one-row step run
+ *   llamahip_decode_sample_lookup / llamahip_verify_sample on each slot in turn.  Stage handles and HOST_ONLY handles are refused.
+ * llamahip_op_topk_slide_set -- the device half on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16, top_k
+ *   1 .. 64; seg_begin[n_segs + 1] ascending from 0 to n_rows; segment s slides inside ids[seg_ids_off[s] ..): its row j's window is
+ *   ids[seg_ids_off[s] + j .. + seg_n_last[s]), and seg_ids_off[s] + seg_n_last[s] + rows_s - 1 <= n_ids.  seg_n_last[s] > 1024 reports that
+ *   segment's rows inexact and leaves the others alone.  out_scores / out_ids [n_rows][64], out_exact [n_rows] -- row r bit for bit
+ *   llamahip_op_topk on that row with that window.  Refusals name their limit, before any launch.
+ * Measured on the 7B, 2 / 4 / 8 sequences (profiles/sample_lookup_multi_probe_7b.json, tools/lookup_probe.py --multi --sampled; DESIGN.md
+ *   12.14): a sampled verify step over the set filled to 16 rows takes 4.1 .. 4.8 ms, 0.01 .. 0.08 ms more than the greedy one of the same
+ *   rows in the same run; the loop runs at 3699 / 3701 / 3606 tokens/s aggregate when every draft is accepted, against 1015 / 1750 / 2580
+ *   for llamahip_decode_sample_multi in the same run, and at 1016 / 1751 / 2588 when nothing is ever drafted -- level with it. */
+int llamahip_verify_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                                 const int32_t *tokens, const int32_t *drafts, const int32_t *n_draft, llamahip_sampler *const *samplers,
+                                 double repeat_penalty, int32_t top_k, double top_p, double temp, int32_t *n_accept /* [n_seqs] */,
+                                 int32_t *picks /* concatenated, n_draft[i] + 1 each */, int32_t *exact /* same shape, may be NULL */,
+                                 char *err, size_t err_cap);
+int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                        int32_t n_steps, const int32_t *contexts /* concatenated, n_past[i] tokens each */,
+                                        const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                        llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p, double temp,
+                                        int32_t *out_tokens /* [n_seqs][n_steps] */, int32_t *out_exact /* same, may be NULL */,
+                                        llamahip_lookup_stats *stats /* [n_seqs], may be NULL */, char *err, size_t err_cap);
+int llamahip_op_topk_slide_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *ids, int32_t n_ids,
+                               const int32_t *seg_begin, int32_t n_segs, const int32_t *seg_ids_off, const int32_t *seg_n_last,
+                               double repeat_penalty, int32_t top_k, double temp,
+                               double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */

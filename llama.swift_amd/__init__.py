@@ -36,6 +36,7 @@ from .binding import (  # noqa: F401
     op_topk,
     op_topk_rows,
     op_topk_slide,
+    op_topk_slide_set,
     op_verify_rows,
     op_verify_rows_set,
     qa_to_blocks,

@@ -126,6 +126,9 @@ def lib() -> C.CDLL:
     L.llamahip_op_verify_rows_set.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, cp, sz]
     L.llamahip_verify_greedy_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, cp, sz]
     L.llamahip_decode_greedy_lookup_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, cp, sz]
+    L.llamahip_verify_sample_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, cp, sz]
+    L.llamahip_decode_sample_lookup_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, i32, i32, vp, C.c_double, i32, C.c_double, C.c_double, vp, vp, vp, cp, sz]
+    L.llamahip_op_topk_slide_set.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_lookup_deal_rows.argtypes = [vp, i32, i32, vp]
     L.llamahip_lookup_deal_rows.restype = i32
     L.llamahip_decode_greedy_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, cp, sz]
@@ -576,6 +579,56 @@ class Model:
         _check(rc, err)
         return (out, exact) if want_exact else out
 
+    def verify_sample_multi(self, slots, tokens, drafts, n_past, samplers, repeat_penalty: float = 1.3, top_k: int = 40,
+                            top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), n_threads: int = 8):
+        """llamahip_verify_sample_multi: one step whose rows are, per sequence i, [tokens[i], *drafts[i]] of KV slot slots[i] at n_past[i], walked
+        by samplers[i] (which has accepted tokens[i]).  Returns (n_accept int32[n_seqs], picks, exact: one int32 array per sequence each; -1 in
+        both for the rows a walk did not reach)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        drafts = [np.ascontiguousarray(d, np.int32).ravel() for d in drafts]
+        if not (slots.size == tokens.size == npast.size == len(drafts) == len(samplers)):
+            raise ValueError(f"verify_sample_multi: {slots.size} slots, {tokens.size} tokens, {npast.size} n_past, {len(drafts)} drafts, {len(samplers)} samplers")
+        nd = np.array([d.size for d in drafts], np.int32)
+        flat = np.concatenate(drafts).astype(np.int32) if int(nd.sum()) else np.zeros(1, np.int32)
+        sp = (C.c_void_p * max(slots.size, 1))(*[s._s.value if s is not None else None for s in samplers])
+        n_acc = np.full(slots.size, -1, np.int32)
+        picks, exact = np.full(int(nd.sum()) + slots.size, -2, np.int32), np.full(int(nd.sum()) + slots.size, -2, np.int32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_verify_sample_multi(self._h, n_threads, slots.size, _ptr(slots), _ptr(npast), _ptr(tokens), _ptr(flat), _ptr(nd), sp,
+                                                repeat_penalty, top_k, top_p, temp, _ptr(n_acc), _ptr(picks), _ptr(exact), err, len(err))
+        _check(rc, err)
+        cut = np.cumsum(nd + 1)[:-1]
+        return n_acc, np.split(picks, cut), np.split(exact, cut)
+
+    def decode_sample_lookup_multi(self, first_tokens, n_past, n_steps: int, contexts, samplers, corpus=None, draft_len: int = 0, ngram_min: int = 0,
+                                   ngram_max: int = 0, repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)),
+                                   temp: float = float(np.float32(0.8)), n_threads: int = 8, want_exact: bool = False, stats_size: int | None = None):
+        """llamahip_decode_sample_lookup_multi: sequence i (KV slot i) continues at n_past[i] with first_tokens[i] and draws with samplers[i], the
+        spare rows of every step carrying drafts (contexts: one sequence of n_past[i] ids per sequence).  Returns (tokens [n_seqs][n_steps],
+        one stats dict per sequence), and with want_exact (tokens, exact [n_seqs][n_steps], stats)."""
+        ft = np.ascontiguousarray(first_tokens, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        if len(samplers) != ft.size:
+            raise ValueError(f"{ft.size} first tokens, {len(samplers)} samplers")
+        ctx = [np.ascontiguousarray(c, np.int32).ravel() for c in contexts]
+        flat = np.concatenate(ctx).astype(np.int32) if sum(c.size for c in ctx) else None
+        corpus = None if corpus is None else np.ascontiguousarray(corpus, np.int32).ravel()
+        sp = (C.c_void_p * max(ft.size, 1))(*[s._s.value if s is not None else None for s in samplers])
+        out = np.empty((ft.size, max(n_steps, 0)), np.int32)
+        exact = np.empty((ft.size, max(n_steps, 0)), np.int32) if want_exact else None
+        st = (_LookupStats * max(ft.size, 1))()
+        for x in st:
+            x.struct_size = C.sizeof(_LookupStats) if stats_size is None else stats_size
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_sample_lookup_multi(self._h, n_threads, ft.size, _ptr(npast), _ptr(ft), n_steps, _ptr(flat), _ptr(corpus),
+                                                       0 if corpus is None else corpus.size, draft_len, ngram_min, ngram_max, sp, repeat_penalty, top_k,
+                                                       top_p, temp, _ptr(out), _ptr(exact), C.cast(st, C.c_void_p), err, len(err))
+        _check(rc, err)
+        stats = [{k: getattr(x, k) for k, _ in _LookupStats._fields_ if k != "struct_size"} for x in st[:ft.size]]
+        return (out, exact, stats) if want_exact else (out, stats)
+
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
         v = np.empty((n_pos, self.n_embd), np.float32)
@@ -712,6 +765,27 @@ def op_topk_slide(logits2d, ids, n_last: int, repeat_penalty: float = 1.3, top_k
     sc, out_ids, exact = np.zeros((max(R, 1), 64), np.float64), np.zeros((max(R, 1), 64), np.int32), np.zeros(max(R, 1), np.int32)
     err = C.create_string_buffer(512)
     rc = lib().llamahip_op_topk_slide(_ptr(logits2d), R, V, _ptr(ids), n_last, repeat_penalty, top_k, temp, _ptr(sc), _ptr(out_ids), _ptr(exact), err, len(err))
+    _check(rc, err)
+    return exact[:R].astype(bool), sc[:R, :top_k].copy(), out_ids[:R, :top_k].copy()
+
+
+def op_topk_slide_set(logits2d, ids, seg_begin, seg_ids_off, seg_n_last, repeat_penalty: float = 1.3, top_k: int = 40, temp: float = float(np.float32(0.8))):
+    """k_topk_keys_slide_set + k_topk_select_rows on host rows f32 [R, n_vocab] (1 .. 16 rows) cut into the segments [seg_begin[s], seg_begin[s + 1]):
+    row j of segment s has the window ids[seg_ids_off[s] + j : + seg_n_last[s]] of the id pool `ids` (seg_n_last[s] > 1024: its rows are
+    reported inexact).  Returns (exact bool[R], scores float64[R][top_k], ids int32[R][top_k])."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    ids = np.ascontiguousarray(ids, np.int32).ravel()
+    seg_begin = np.ascontiguousarray(seg_begin, np.int32).ravel()
+    off, nl = np.ascontiguousarray(seg_ids_off, np.int32).ravel(), np.ascontiguousarray(seg_n_last, np.int32).ravel()
+    if seg_begin.size < 2 or off.size != seg_begin.size - 1 or nl.size != off.size:
+        raise ValueError(f"op_topk_slide_set: {seg_begin.size} segment bounds, {off.size} offsets, {nl.size} window lengths")
+    sc, out_ids, exact = np.zeros((max(R, 1), 64), np.float64), np.zeros((max(R, 1), 64), np.int32), np.zeros(max(R, 1), np.int32)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_topk_slide_set(_ptr(logits2d), R, V, _ptr(ids) if ids.size else None, ids.size, _ptr(seg_begin), seg_begin.size - 1, _ptr(off), _ptr(nl),
+                                          repeat_penalty, top_k, temp, _ptr(sc), _ptr(out_ids), _ptr(exact), err, len(err))
     _check(rc, err)
     return exact[:R].astype(bool), sc[:R, :top_k].copy(), out_ids[:R, :top_k].copy()
 

@@ -2440,6 +2440,21 @@ k_topk_keys_slide(const float *__restrict__ logits, int V, const int32_t *__rest
     topk_keys_row(logits + (size_t) r * V, V, ids + r, n_last, scale, repeat_penalty, keys, gmax, (uint32_t *) (gmax + 64));
 }
 
+// The rows of a verify step over a SET (llamahip_verify_sample_multi): the rows are cut into segments, one per sequence, and every segment
+// slides inside its own id stream -- that sequence's sampler window followed by its draft -- of one id pool.  The host resolves the
+// segments into two per-row words (at most 16 rows): row r's window is ids[row_off[r] .. + row_n_last[r]), i.e. row_off[r] = the segment's
+// offset + the row's index in its segment.  Same body, same workspace layout; the selection behind it is k_topk_select_rows with
+// row_n_last, which flags the rows of a window longer than 1024 ids inexact (and still clears their workspace).  Such a row reads no ids.
+__global__ void __launch_bounds__(1024)
+k_topk_keys_slide_set(const float *__restrict__ logits, int V, const int32_t *__restrict__ ids, const int32_t *__restrict__ row_off,
+                      const int32_t *__restrict__ row_n_last, double scale, double repeat_penalty, char *__restrict__ ws) {
+    const int r = blockIdx.y;
+    unsigned long long *keys = (unsigned long long *) (ws + (size_t) r * TOPK_WS_BYTES), *gmax = keys + 32768;
+    const int nw = row_n_last[r];
+    topk_keys_row(logits + (size_t) r * V, V, ids + row_off[r], nw < 0 || nw > 1024 ? 0 : nw, scale, repeat_penalty, keys, gmax,
+                  (uint32_t *) (gmax + 64));
+}
+
 // (n_last == nullptr: every row's window is one the device took -- launch_topk_slide)
 __global__ void __launch_bounds__(1024)
 k_topk_select_rows(int V, int k, const int32_t *__restrict__ n_last, char *__restrict__ ws, TopkOut *__restrict__ out) {
@@ -2481,6 +2496,16 @@ hipError_t launch_topk_slide(const float *logits, int R, int V, const int32_t *i
     hipLaunchKernelGGL(k_topk_keys_slide, dim3((V + 1023) / 1024, R), dim3(1024), 0, st, logits, V, ids, n_last, scale, repeat_penalty, (char *) ws);
     LH_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_topk_select_rows, dim3(R), dim3(1024), 0, st, V, k, (const int32_t *) nullptr, (char *) ws, out);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_topk_slide_set(const float *logits, int R, int V, const int32_t *ids, const int32_t *row_off, const int32_t *row_n_last, double scale,
+                                 double repeat_penalty, int k, TopkOut *out, hipStream_t st, void *ws) {
+    if (R < 1 || R > 16 || V < 1 || V > 32768 || k < 1 || k > 64 || !ws || !out || !logits || !row_off || !row_n_last) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_topk_keys_slide_set, dim3((V + 1023) / 1024, R), dim3(1024), 0, st, logits, V, ids, row_off, row_n_last, scale, repeat_penalty, (char *) ws);
+    LH_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_topk_select_rows, dim3(R), dim3(1024), 0, st, V, k, row_n_last, (char *) ws, out);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

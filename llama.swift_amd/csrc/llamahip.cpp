@@ -175,7 +175,9 @@ struct llamahip_model {
     // block that the kernels read / write directly (three ~4 us blit copies per sampled token otherwise)
     struct HostIo { int32_t tok[16]; int32_t window[1024]; double sc[64]; int32_t id[64]; int32_t fl[2];
                     int32_t slide[1024 + VERIFY_ROWS_MAX]; TopkOut rows[VERIFY_ROWS_MAX];      // (a sampled verify step: its id stream in, its rows' candidates out)
-                    VsetBlock vset; };             // (a verify step over a set: its descriptor out, vset.res back)
+                    VsetBlock vset;                // (a verify step over a set: its descriptor out, vset.res back)
+                    int32_t pool[SLIDE_SET_IDS]; int32_t row_tab[2 * VERIFY_ROWS_MAX];          // (a sampled verify step over a set: its id pool and {row_off, row_n_last} in; `rows` back)
+                    int32_t slot_words[2 * SET_MAX]; };                                         // (the drafted sampled loop: the slots' {position, cursor} on their way to d_slot_state)
     HostIo *h_io = nullptr, *d_io = nullptr;       // host pointer / its device alias
     const int32_t *tok_src = nullptr;              // set by eval_impl around forward(): where the embedding kernel finds the token
     float *x = nullptr, *x1 = nullptr, *qkv = nullptr, *qr = nullptr, *merged = nullptr, *gu = nullptr;
@@ -205,6 +207,7 @@ struct llamahip_model {
     int score_cap = 0;
     char *d_slide = nullptr;             // sampled verify step (last stage): 16 x TOPK_WS_BYTES of selection workspace | the id stream (SLIDE_IDS_BYTES) | 16 TopkOut (slide_ensure)
     VsetBlock *d_vset = nullptr;         // a verify step over a set: the step's descriptor (vset_step)
+    int32_t *d_slide_set = nullptr;      // sampled verify step over a set (last stage, no pinned block): the id pool (SLIDE_SET_IDS) | row_off[16] | row_n_last[16]
     int32_t *d_verify = nullptr;         // drafted greedy decoding (last stage): {position, cursor} | 16 row tokens | 16 picks | {n_accept, 16 picks} | from [64]: the token log, n_ctx entries (verify_io)
     uint32_t *d_attn_sync = nullptr;     // per-head hand-off counters of k_dec_attn_x ([H][32] dwords); null: two-launch attention
     uint64_t *d_qkv2 = nullptr, *d_sc2 = nullptr;   // tagged hand-off buffers of k_qkv_attn: [3 d] and [H][n_ctx] {fp32 bits, tag} granules
@@ -305,7 +308,7 @@ llamahip_model::~llamahip_model() {
     free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
     free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
     free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_vset); free_dev(d_slide);
+    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_vset); free_dev(d_slide); free_dev(d_slide_set);
     free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
     free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
     free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
@@ -2793,8 +2796,44 @@ static int vset_ensure(llamahip_model *st, bool first, char *err, size_t err_cap
     return 0;
 }
 
+// The sampled step's device half (llamahip_verify_sample_multi): behind forward_set, in place of k_verify_rows / k_accept_drafts_set, the
+// sampler's candidate selection over the R rows, row r's window = ids[row_off[r] .. + row_n_last[r]) of the id pool (launch_topk_slide_set).
+// k == 0: the device cannot make candidates for any row (top_k > 64, n_vocab > 32768) -- nothing is launched.  out: R rows, valid after the step.
+struct SlideSetReq { const int32_t *ids; int n_ids; int32_t row_off[VERIFY_ROWS_MAX], row_n_last[VERIFY_ROWS_MAX]; double scale, repeat_penalty; int k; TopkOut *out; };
+static int slide_set_enqueue(llamahip_model *last, const SlideSetReq &ss, int R, char *err, size_t err_cap) {
+    if (ss.k == 0) return 0;
+    if (ss.n_ids < 0 || (size_t) ss.n_ids > SLIDE_SET_IDS) { set_err(err, err_cap, "sampled verify step over a set: an id pool of %d ids", ss.n_ids); return LLAMAHIP_ERR_PREDICT; }
+    for (int r = 0; r < R; r++)      // (every window the kernel reads lies inside the pool)
+        if (ss.row_n_last[r] < 0 || ss.row_off[r] < 0 || (ss.row_n_last[r] <= 1024 && ss.row_off[r] + ss.row_n_last[r] > ss.n_ids)) {
+            set_err(err, err_cap, "sampled verify step over a set: row %d's window [%d, + %d) leaves the pool of %d ids", r, ss.row_off[r], ss.row_n_last[r], ss.n_ids);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    int rc = slide_ensure(last, err, err_cap);
+    if (rc) return rc;
+    const int32_t *ids, *tab;
+    TopkOut *out;
+    if (last->h_io) {                       // (the stream is idle: every entry point synchronises before it returns)
+        memcpy(last->h_io->pool, ss.ids, (size_t) ss.n_ids * 4);
+        memcpy(last->h_io->row_tab, ss.row_off, sizeof(ss.row_off));
+        memcpy(last->h_io->row_tab + VERIFY_ROWS_MAX, ss.row_n_last, sizeof(ss.row_n_last));
+        ids = last->d_io->pool; tab = last->d_io->row_tab; out = last->d_io->rows;
+    } else {
+        if (!last->d_slide_set) HIP_TRY(hipMalloc((void **) &last->d_slide_set, (SLIDE_SET_IDS + 2 * VERIFY_ROWS_MAX) * 4), LLAMAHIP_ERR_PREDICT);
+        int32_t *d_tab = last->d_slide_set + SLIDE_SET_IDS;
+        // (pageable sources: each copy has left the host buffer when the call returns)
+        if (ss.n_ids > 0) HIP_TRY(hipMemcpyAsync(last->d_slide_set, ss.ids, (size_t) ss.n_ids * 4, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(d_tab, ss.row_off, sizeof(ss.row_off), hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(d_tab + VERIFY_ROWS_MAX, ss.row_n_last, sizeof(ss.row_n_last), hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+        ids = last->d_slide_set; tab = d_tab; out = (TopkOut *) (last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES);
+    }
+    HIP_TRY(launch_topk_slide_set(last->logits, R, last->hp.n_vocab, ids, tab, tab + VERIFY_ROWS_MAX, ss.scale, ss.repeat_penalty, ss.k, out, last->stream, last->d_slide), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
 // one verify step over a set on a Q4_0 handle, plain or pipeline; res: {n_accept[n_segs], picks[n_rows]}
-static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &stages, int32_t n_threads, const VsetReq &rq, int32_t *res, char *err, size_t err_cap) {
+// (ss != nullptr: the sampled step -- res unused, ss->out receives the rows' candidates, no slot word is touched)
+static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &stages, int32_t n_threads, const VsetReq &rq, int32_t *res, char *err, size_t err_cap,
+                     const SlideSetReq *ss = nullptr) {
     const double t0 = now_ms();
     const int S = (int) stages.size(), R = rq.n_rows, G = rq.n_segs;
     llamahip_model *first = stages[0], *last = stages[S - 1];
@@ -2840,6 +2879,19 @@ static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &sta
     int32_t *d_res = last->h_io ? last->d_io->vset.res : dv->res;
     int32_t *next_tok = S == 1 ? first->mq_tok : last->mq_tok;
     if (rq.bound && (!last->d_slot_state || !last->d_slot_trace || !next_tok)) { set_err(err, err_cap, "verify step over a set: the slots are not bound"); return bail(LLAMAHIP_ERR_PREDICT); }
+    if (ss) {
+        if ((rc = slide_set_enqueue(last, *ss, R, err, err_cap)) != 0) return bail(rc);
+        if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        if (ss->k > 0) {
+            if (last->h_io) memcpy(ss->out, last->h_io->rows, (size_t) R * sizeof(TopkOut));
+            else HIP_TRY(hipMemcpy(ss->out, last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES, (size_t) R * sizeof(TopkOut), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        }
+        last->last_rows.clear();
+        m->n_evals++;
+        m->t_eval_ms += now_ms() - t0;
+        return LLAMAHIP_OK;
+    }
     if (launch_verify_rows(last->logits, R, V, dv->pick, last->stream) != hipSuccess ||
         launch_accept_drafts_set(dv->tok, dv->pick, dv->seg_begin, dv->seg_slot, G, R, rq.bound ? last->d_slot_state : nullptr, rq.bound ? last->d_slot_trace : nullptr,
                                  C, rq.bound ? next_tok : nullptr, d_res, last->stream) != hipSuccess) {
@@ -2869,15 +2921,10 @@ static int check_multi_handle(llamahip_model *m, const char *fn, int32_t n_seqs,
     return 0;
 }
 
-int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
-                                 const int32_t *drafts, const int32_t *n_draft, int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
-    static const char *fn = "llamahip_verify_greedy_multi";
-    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
-    if (rc) return rc;
-    if (!slots || !n_past || !tokens || !n_draft) { set_err(err, err_cap, "%s: null slots / n_past / tokens / n_draft", fn); return LLAMAHIP_ERR_PREDICT; }
-    if (!n_accept || !picks) { set_err(err, err_cap, "%s: null output", fn); return LLAMAHIP_ERR_PREDICT; }
+// the arguments of a verify step over a set (greedy and sampled), checked without a device, and the step they describe; the handle last
+static int check_vset_args(llamahip_model *m, const char *fn, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                           const int32_t *drafts, const int32_t *n_draft, VsetReq &rq, char *err, size_t err_cap) {
     const int V = m->hp.n_vocab, C = m->hp.n_ctx, have = (m->stages.empty() ? m : m->stages[0])->n_seq;
-    VsetReq rq;
     int n_rows = 0, n_dr = 0;
     for (int i = 0; i < n_seqs; i++) {
         if (slots[i] < 0 || slots[i] >= have) { set_err(err, err_cap, "%s: sequence slot %d out of range [0, %d)", fn, slots[i], have); return LLAMAHIP_ERR_PREDICT; }
@@ -2897,7 +2944,19 @@ int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
     }
     rq.seg_begin[n_seqs] = n_rows; rq.n_segs = n_seqs; rq.n_rows = n_rows;
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], tokens, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+}
+
+int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                                 const int32_t *drafts, const int32_t *n_draft, int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_verify_greedy_multi";
+    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
+    if (rc) return rc;
+    if (!slots || !n_past || !tokens || !n_draft) { set_err(err, err_cap, "%s: null slots / n_past / tokens / n_draft", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!n_accept || !picks) { set_err(err, err_cap, "%s: null output", fn); return LLAMAHIP_ERR_PREDICT; }
+    VsetReq rq;
+    if ((rc = check_vset_args(m, fn, n_seqs, slots, n_past, tokens, drafts, n_draft, rq, err, err_cap)) != 0) return rc;
+    const int n_rows = rq.n_rows;
     const std::vector<llamahip_model *> stages = stages_of(m);
     if (n_rows == 1 || lookup_dense(m) || (stages[0]->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads)) {
         // no set step on this handle (or one row): llamahip_verify_greedy on each slot in turn
@@ -3248,6 +3307,302 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
     for (int i = 0; i < n_seqs; i++)
         if (state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d, not %d", F, i, state[2 * i], n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
     m->n_evals += (int64_t) n_seqs * n_steps;
+    m->t_eval_ms += now_ms() - t0;
+    if (!m->stages.empty()) m->pipe_hand_off = 1;
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Drafted SAMPLED decoding for SEVERAL sequences at once: llamahip_verify_sample_multi / llamahip_decode_sample_lookup_multi -- the two halves
+// above put together.  ROWS: a verify step over a set (vset_step) evaluates rows cut into per-slot segments, every row the single-token eval
+// of its slot at its own position.  SAMPLER: the reference's sampler is a deterministic function of (row logits, last_n_tokens window,
+// mt19937 state), and the window at row j of a segment -- IF that sequence's draft tokens 0 .. j - 1 were accepted -- is known before the eval.
+// So the device selects every row's candidates under that window (launch_topk_slide_set behind forward_set on the last stage's stream: the
+// segments slide inside their own id streams of one pool) and the host walks every segment with that sequence's OWN sampler, as
+// verify_sample_impl walks its rows: row 0, then row j + 1 only if row j's draw was draft[j].  The accept step therefore lives on the host:
+// what a segment accepts depends on draws of a host-side mt19937 (std::discrete_distribution), so there is nothing for k_accept_drafts_set
+// to compare; the loop keeps the slots' device words {position, cursor} in step from the host instead.
+// (Equality with single steps is BY TEST -- tests/test_gpu_sample_lookup_multi.py -- not structural: the norm's one-pass against two-pass
+//  statistics, as for set steps and verify steps.)
+// ------------------------------------------------------------------------------------------------
+// the id pool and the per-row table of a sampled step: segment g's stream = samplers[g]'s window, then its draft (rq.rows behind its first row)
+static void slide_set_build(const VsetReq &rq, llamahip_sampler *const *samplers, bool dev_sel, int32_t *pool, SlideSetReq &ss, bool *seg_sel) {
+    ss.ids = pool; ss.n_ids = 0;
+    memset(ss.row_off, 0, sizeof(ss.row_off));
+    memset(ss.row_n_last, 0, sizeof(ss.row_n_last));
+    for (int g = 0; g < rq.n_segs; g++) {
+        const int rows = rq.seg_begin[g + 1] - rq.seg_begin[g];
+        const int32_t nw = llamahip_sampler_window(samplers[g], nullptr, 0);
+        seg_sel[g] = dev_sel && nw <= 1024;
+        if (!dev_sel) continue;
+        if (nw > 1024) {        // (no ids travel: the rows are flagged inexact by their length)
+            for (int j = 0; j < rows; j++) ss.row_n_last[rq.seg_begin[g] + j] = 1025;
+            continue;
+        }
+        int32_t *st = pool + ss.n_ids;
+        (void) llamahip_sampler_window(samplers[g], st, nw);
+        for (int j = 0; j + 1 < rows; j++) st[nw + j] = rq.rows[rq.seg_begin[g] + 1 + j];
+        for (int j = 0; j < rows; j++) { ss.row_off[rq.seg_begin[g] + j] = ss.n_ids + j; ss.row_n_last[rq.seg_begin[g] + j] = nw; }
+        ss.n_ids += nw + rows - 1;
+    }
+}
+// the walk of segment g behind the step: draws and accepts with the sequence's sampler; picks / exact: the segment's rows (-1 behind the walk)
+static int slide_set_walk(llamahip_model *m, llamahip_model *last, const VsetReq &rq, int g, llamahip_sampler *sampler, bool seg_sel, const TopkOut *out,
+                          double repeat_penalty, int32_t top_k, double top_p, double temp, int32_t *n_accept, int32_t *picks, int32_t *exact,
+                          std::vector<float> &logits, char *err, size_t err_cap) {
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V), r0 = rq.seg_begin[g], n_draft = rq.seg_begin[g + 1] - r0 - 1;
+    const int32_t *draft = rq.rows + r0 + 1;
+    for (int j = 0; j <= n_draft; j++) { picks[j] = -1; if (exact) exact[j] = -1; }
+    int a = 0;
+    for (;; a++) {
+        const bool ex = seg_sel && out[r0 + a].fl[0] == 1;
+        if (ex) picks[a] = llamahip_sample_from_candidates(sampler, out[r0 + a].sc, out[r0 + a].id, k, top_p);
+        else {
+            // (the rows stay on the device until the next eval: a row the walk reaches and finds inexact is fetched now, that row only)
+            logits.resize((size_t) V);
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(logits.data(), last->logits + (size_t) (r0 + a) * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            picks[a] = llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
+        }
+        llamahip_sampler_accept(sampler, picks[a]);
+        if (exact) exact[a] = ex ? 1 : 0;
+        if (a == n_draft || picks[a] != draft[a]) break;
+    }
+    *n_accept = a;
+    return 0;
+}
+
+static int check_samplers(const char *fn, int32_t n_seqs, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
+    if (!samplers) { set_err(err, err_cap, "%s: null samplers", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int i = 0; i < n_seqs; i++) {
+        if (!samplers[i]) { set_err(err, err_cap, "%s: null sampler (samplers[%d])", fn, i); return LLAMAHIP_ERR_PREDICT; }
+        int rc = check_sampler_params(fn, samplers[i], repeat_penalty, top_k, top_p, temp, err, err_cap);
+        if (rc) return rc;
+        for (int j = 0; j < i; j++)
+            if (samplers[j] == samplers[i]) { set_err(err, err_cap, "%s: samplers[%d] and samplers[%d] are the same sampler: every sequence draws with its own", fn, j, i); return LLAMAHIP_ERR_PREDICT; }
+    }
+    return 0;
+}
+
+int llamahip_verify_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                                 const int32_t *drafts, const int32_t *n_draft, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k,
+                                 double top_p, double temp, int32_t *n_accept, int32_t *picks, int32_t *exact, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_verify_sample_multi";
+    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
+    if (rc) return rc;
+    if (!slots || !n_past || !tokens || !n_draft) { set_err(err, err_cap, "%s: null slots / n_past / tokens / n_draft", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!n_accept || !picks) { set_err(err, err_cap, "%s: null output", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_samplers(fn, n_seqs, samplers, repeat_penalty, top_k, top_p, temp, err, err_cap)) != 0) return rc;
+    VsetReq rq;
+    if ((rc = check_vset_args(m, fn, n_seqs, slots, n_past, tokens, drafts, n_draft, rq, err, err_cap)) != 0) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    std::vector<int32_t> win;
+    std::vector<float> logits;
+    if (rq.n_rows == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads)) {
+        // no set step on this handle (or one row): llamahip_verify_sample on each slot in turn
+        const int save_seq = m->cur_seq;
+        for (int i = 0, od = 0, op = 0; i < n_seqs && rc == 0; od += n_draft[i], op += n_draft[i] + 1, i++)
+            if ((rc = llamahip_set_seq(m, slots[i], err, err_cap)) == 0)
+                rc = verify_sample_impl(m, n_threads, n_past[i], tokens[i], drafts + od, n_draft[i], samplers[i], repeat_penalty, top_k, top_p, temp, &n_accept[i],
+                                        picks + op, exact ? exact + op : nullptr, win, logits, err, err_cap);
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
+    }
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    const bool dev_sel = V <= 32768 && k <= 64;
+    std::vector<int32_t> pool(SLIDE_SET_IDS);
+    TopkOut out[VERIFY_ROWS_MAX];
+    bool seg_sel[SET_MAX];
+    SlideSetReq ss;
+    slide_set_build(rq, samplers, dev_sel, pool.data(), ss, seg_sel);
+    ss.scale = 1.0 / temp; ss.repeat_penalty = repeat_penalty; ss.k = dev_sel ? k : 0; ss.out = out;
+    if ((rc = vset_step(m, stages, n_threads, rq, nullptr, err, err_cap, &ss)) != 0) return rc;
+    for (int g = 0; g < n_seqs; g++)
+        if ((rc = slide_set_walk(m, stages.back(), rq, g, samplers[g], seg_sel[g], out, repeat_penalty, top_k, top_p, temp, &n_accept[g], picks + rq.seg_begin[g],
+                                 exact ? exact + rq.seg_begin[g] : nullptr, logits, err, err_cap)) != 0) return rc;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
+                                        const int32_t *contexts, const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                        llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p, double temp,
+                                        int32_t *out_tokens, int32_t *out_exact, llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_sample_lookup_multi";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (n_seqs > SET_MAX) { set_err(err, err_cap, "%s: n_seqs must be 1 .. %d (got %d): a step of %d rows has none to spare for drafts, use llamahip_decode_sample_multi", fn, SET_MAX, n_seqs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    int rc = check_multi_handle(m, fn, n_seqs, err, err_cap);
+    if (rc) return rc;
+    if (!n_past || !first_tokens) { set_err(err, err_cap, "%s: null n_past / first_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_samplers(fn, n_seqs, samplers, repeat_penalty, top_k, top_p, temp, err, err_cap)) != 0) return rc;
+    std::vector<size_t> coff(n_seqs + 1, 0);
+    for (int i = 0; i < n_seqs; i++) {
+        if (n_past[i] < 0) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        coff[i + 1] = coff[i] + (size_t) n_past[i];
+    }
+    for (int i = 0; i < n_seqs; i++)
+        if ((rc = check_lookup_args(m, fn, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, i == 0 ? n_corpus : 0, draft_len, ngram_min,
+                                    ngram_max, out_tokens, stats ? stats + i : nullptr, err, err_cap, false)) != 0) return rc;
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], first_tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    if (n_seqs == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads)) {
+        // one sequence, or no set step on this handle: llamahip_decode_sample_lookup on each slot in turn
+        const int save_seq = m->cur_seq;
+        for (int i = 0; i < n_seqs && rc == 0; i++)
+            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
+                rc = llamahip_decode_sample_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, n_corpus,
+                                                   draft_len, ngram_min, ngram_max, samplers[i], repeat_penalty, top_k, top_p, temp, out_tokens + (size_t) i * n_steps,
+                                                   out_exact ? out_exact + (size_t) i * n_steps : nullptr, stats ? stats + i : nullptr, err, err_cap);
+        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+        return rc;
+    }
+    const double t0 = now_ms();
+    const size_t d = m->hp.n_embd;
+    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+    // the device half runs unless top_k > 64 or n_vocab > 32768: then every row is spilled and nobody drafts; a window of more than 1024 ids spills
+    // its own rows only, and that sequence wants no draft
+    const bool dev_sel = V <= 32768 && k <= 64;
+    const double scale = 1.0 / temp;
+    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, 1, err, err_cap)) != 0) return rc;
+    if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
+    if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
+    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h, &dl = last->smp_d;
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        for (int i = 0; i < n_seqs; i++)        // (llamahip_decode_sample_multi's binding: sequence i in slot i, its token word in the pinned block, written by the host)
+            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->smp_d.tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
+                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, nullptr, err, err_cap)) != 0) return rc;
+    }
+    std::vector<std::vector<int32_t>> hist(n_seqs);      // hist[i][0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
+    std::vector<int> done(n_seqs, 0);
+    std::vector<llamahip_lookup_stats> ls(n_seqs, llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 });
+    for (int i = 0; i < n_seqs; i++) {
+        hist[i].resize((size_t) n_past[i] + n_steps + 1);
+        if (n_past[i] > 0) memcpy(hist[i].data(), contexts + coff[i], (size_t) n_past[i] * 4);
+        hist[i][n_past[i]] = first_tokens[i];
+    }
+    auto emit = [&](int i, int32_t tok, int32_t ex) {
+        hist[i][n_past[i] + done[i] + 1] = tok;
+        out_tokens[(size_t) i * n_steps + done[i]] = tok;
+        if (out_exact) out_exact[(size_t) i * n_steps + done[i]] = ex;
+        done[i]++;
+    };
+    // a verify step advances no slot word on any device (what it accepts is known on the host only): before the next captured step the host writes
+    // every slot's {position, cursor} on every stage -- through the pinned block where the stage has one; the first stage's token words are
+    // written before every plain step anyway
+    bool words_stale = false;
+    auto push_words = [&]() -> int {
+        int32_t w[2 * SET_MAX];
+        for (int i = 0; i < n_seqs; i++) { w[2 * i] = n_past[i] + done[i]; w[2 * i + 1] = done[i]; }
+        for (llamahip_model *st : stages) {
+            HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+            if (st->h_io) {                 // (the stream is idle: the step before was waited for)
+                memcpy(st->h_io->slot_words, w, (size_t) n_seqs * 8);
+                HIP_TRY(hipMemcpyAsync(st->d_slot_state, st->h_io->slot_words, (size_t) n_seqs * 8, hipMemcpyHostToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
+            } else HIP_TRY(hipMemcpy(st->d_slot_state, w, (size_t) n_seqs * 8, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+        }
+        words_stale = false;
+        return 0;
+    };
+    std::vector<int32_t> act, pool(SLIDE_SET_IDS);
+    std::vector<float> logits;
+    for (;;) {
+        act.clear();
+        for (int i = 0; i < n_seqs; i++) if (done[i] < n_steps) act.push_back(i);
+        if (act.empty()) break;
+        const int A = (int) act.size();
+        int32_t want[SET_MAX], give[SET_MAX], draft[SET_MAX][VERIFY_ROWS_MAX];
+        for (int a = 0; a < A; a++) {
+            const int i = act[a], pos = n_past[i] + done[i];
+            // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
+            const int room = dev_sel && llamahip_sampler_window(samplers[i], nullptr, 0) <= 1024 ? std::min(K, n_steps - done[i] - 1) : 0;
+            want[a] = room > 0 ? llamahip_lookup_draft(hist[i].data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft[a]) : 0;
+            if (want[a] < 0 || want[a] > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, want[a], room); return LLAMAHIP_ERR_PREDICT; }
+        }
+        const int dealt = llamahip_lookup_deal_rows(want, A, SET_MAX, give);
+        if (dealt < 0) { set_err(err, err_cap, "%s: dealing the rows of a step failed", fn); return LLAMAHIP_ERR_PREDICT; }
+        if (dealt == 0) {
+            // llamahip_decode_sample_multi's step over the active slots: row a of the step = slot act[a] (a set orders its rows by slot id)
+            if (words_stale && (rc = push_words()) != 0) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
+            for (int a = 0; a < A; a++) {
+                const int i = act[a];
+                hf.tok[i] = hist[i][n_past[i] + done[i]];
+                hl.n_last[a] = llamahip_sampler_window(samplers[i], hl.win + (size_t) a * 1024, 1024);
+            }
+            for (int s = 0; s < S && rc == 0; s++) {
+                llamahip_model *st = stages[s];
+                if (hipSetDevice(st->device) != hipSuccess || (s > 0 && hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[0], 0) != hipSuccess)) { set_err(err, err_cap, "%s: HIP error ordering the stages of a step", fn); rc = LLAMAHIP_ERR_PREDICT; break; }
+                if (A >= 2) rc = llamahip_stage_step_set(st, act.data(), A, n_threads, st->stream, err, err_cap);
+                else rc = llamahip_stage_step(st, act[0], n_threads, st->stream, err, err_cap);
+                if (rc || s + 1 == S) break;
+                // (every slot's row travels: the rows of the slots that sat the step out are not read before they are written again)
+                llamahip_model *to = stages[s + 1];
+                const hipError_t e = st->device == to->device ? hipMemcpyAsync(to->mq_in, st->mq_out, (size_t) n_seqs * d * 4, hipMemcpyDeviceToDevice, st->stream)
+                                                              : hipMemcpyPeerAsync(to->mq_in, to->device, st->mq_out, st->device, (size_t) n_seqs * d * 4, st->stream);
+                if (e != hipSuccess || hipEventRecord(st->mq_ev[0], st->stream) != hipSuccess) { set_err(err, err_cap, "%s: HIP error handing a step's rows on", fn); rc = LLAMAHIP_ERR_PREDICT; }
+            }
+            if (rc == 0) {
+                const hipError_t e = dev_sel ? launch_topk_rows(last->logits, A, V, dl.win, dl.n_last, scale, repeat_penalty, k, dl.out, dl.spill, last->stream, last->smp_ws)
+                                             : hipMemcpyAsync(hl.spill, last->logits, (size_t) A * V * 4, hipMemcpyDeviceToHost, last->stream);
+                if (e != hipSuccess) { set_err(err, err_cap, "%s: HIP error enqueuing the selection of a step", fn); rc = LLAMAHIP_ERR_PREDICT; }
+            }
+            if (rc) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
+            if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+            for (int a = 0; a < A; a++) {
+                const int i = act[a];
+                const TopkOut &c = hl.out[a];
+                const bool ex = dev_sel && c.fl[0] == 1;
+                const int32_t tok = ex ? llamahip_sample_from_candidates(samplers[i], c.sc, c.id, k, top_p)
+                                       : llamahip_sample_top_p_top_k(m, samplers[i], hl.spill + (size_t) a * V, repeat_penalty, top_k, top_p, temp);
+                llamahip_sampler_accept(samplers[i], tok);
+                emit(i, tok, ex ? 1 : 0);
+                ls[i].n_single_steps++;
+            }
+            m->n_evals += A;
+            continue;
+        }
+        VsetReq rq;
+        rq.n_segs = A;
+        int R = 0;
+        llamahip_sampler *seg_smp[SET_MAX];
+        for (int a = 0; a < A; a++) {
+            const int i = act[a];
+            rq.slot[a] = i; rq.pos[a] = n_past[i] + done[i]; rq.seg_begin[a] = R; seg_smp[a] = samplers[i];
+            rq.rows[R++] = hist[i][rq.pos[a]];
+            for (int j = 0; j < give[a]; j++) rq.rows[R++] = draft[a][j];
+        }
+        rq.seg_begin[A] = R; rq.n_rows = R;
+        TopkOut out[VERIFY_ROWS_MAX];
+        bool seg_sel[SET_MAX];
+        SlideSetReq ss;
+        slide_set_build(rq, seg_smp, dev_sel, pool.data(), ss, seg_sel);
+        ss.scale = scale; ss.repeat_penalty = repeat_penalty; ss.k = k; ss.out = out;
+        if ((rc = vset_step(m, stages, n_threads, rq, nullptr, err, err_cap, &ss)) != 0) return rc;
+        for (int a = 0; a < A; a++) {
+            const int i = act[a];
+            int32_t na = 0, picks[VERIFY_ROWS_MAX], exact[VERIFY_ROWS_MAX];
+            if ((rc = slide_set_walk(m, last, rq, a, samplers[i], seg_sel[a], out, repeat_penalty, top_k, top_p, temp, &na, picks, exact, logits, err, err_cap)) != 0) return rc;
+            for (int j = 0; j <= na; j++) emit(i, picks[j], exact[j]);
+            if (give[a] > 0) { ls[i].n_verify_steps++; ls[i].n_drafted += give[a]; ls[i].n_accepted += na; }
+            else ls[i].n_single_steps++;
+            for (llamahip_model *st : stages) st->slots[i].next_pos += na + 1;      // (the host's mirror of the slot's position)
+        }
+        words_stale = true;
+    }
+    // the slots end where a caller of the stage API expects them; the last stage's words are read back against the host's count
+    if (words_stale && (rc = push_words()) != 0) return rc;
+    if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+    std::vector<int32_t> state((size_t) 2 * n_seqs);
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(state.data(), last->d_slot_state, state.size() * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    for (int i = 0; i < n_seqs; i++) {
+        if (done[i] != n_steps || state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d after %d of %d steps, not at %d", fn, i, state[2 * i], done[i], n_steps, n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
+        if (stats) stats[i] = ls[i];
+    }
     m->t_eval_ms += now_ms() - t0;
     if (!m->stages.empty()) m->pipe_hand_off = 1;
     return LLAMAHIP_OK;

@@ -266,6 +266,13 @@ hipError_t launch_topk_rows(const float *logits, int R, int V, const int32_t *wi
 // n_last > 1024, V > 32768, k > 64; ws and out as above, no spill (the rows stay on the device until the next eval)
 hipError_t launch_topk_slide(const float *logits, int R, int V, const int32_t *ids, int n_last, double scale, double repeat_penalty, int k,
                              TopkOut *out, hipStream_t st, void *ws);
+// ... with the R <= 16 rows cut into segments that slide inside their own id streams of one id pool (llamahip_verify_sample_multi,
+// llamahip_op_topk_slide_set): row r's window = ids[row_off[r] .. + row_n_last[r]) -- two device words per row, resolved from the segments by the
+// host, which also checks that every window lies inside the pool.  row_n_last[r] > 1024: the row reads no ids and is flagged inexact.
+hipError_t launch_topk_slide_set(const float *logits, int R, int V, const int32_t *ids, const int32_t *row_off, const int32_t *row_n_last, double scale,
+                                 double repeat_penalty, int k, TopkOut *out, hipStream_t st, void *ws);
+// the id pool of such a step: per segment at most 1024 window ids + its rows - 1 draft ids; and its per-row table {row_off[16], row_n_last[16]}
+constexpr size_t SLIDE_SET_IDS = 16 * 1024 + 16;
 // next-token scoring of n_rows rows of logits (logprob.hip): per row the log-probability of targets[r] in double, the argmax (lowest index
 // on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,

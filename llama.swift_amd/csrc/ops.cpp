@@ -277,6 +277,50 @@ int llamahip_op_topk_slide(const float *logits, int32_t n_rows, int32_t n_vocab,
     return LLAMAHIP_OK;
 }
 
+// k_topk_keys_slide_set + k_topk_select_rows on caller-supplied rows cut into segments (parity tests): see llamahip_verify_sample_multi
+int llamahip_op_topk_slide_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *ids, int32_t n_ids, const int32_t *seg_begin, int32_t n_segs,
+                               const int32_t *seg_ids_off, const int32_t *seg_n_last, double repeat_penalty, int32_t top_k, double temp,
+                               double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_topk_slide_set";
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: n_rows must be 1 .. %d (got %d): a verify step has at most %d rows", fn, VERIFY_ROWS_MAX, n_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_vocab < 1 || n_vocab > 32768) { set_err(err, err_cap, "%s: n_vocab must be 1 .. 32768 (got %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (top_k < 1 || top_k > 64 || top_k > n_vocab) { set_err(err, err_cap, "%s: top_k must be 1 .. min(64, n_vocab) (got %d, n_vocab %d)", fn, top_k, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (!logits || !out_scores || !out_ids || !out_exact || !seg_begin || !seg_ids_off || !seg_n_last || n_ids < 0 || (n_ids > 0 && !ids)) { set_err(err, err_cap, "%s: null argument (or n_ids %d < 0)", fn, n_ids); return LLAMAHIP_ERR_PREDICT; }
+    if (!(temp > 0.0) || !(repeat_penalty > 0.0)) { set_err(err, err_cap, "%s: temp (%g) and repeat_penalty (%g) must be positive", fn, temp, repeat_penalty); return LLAMAHIP_ERR_PREDICT; }
+    if (n_segs < 1 || n_segs > n_rows) { set_err(err, err_cap, "%s: n_segs must be 1 .. n_rows (%d; got %d)", fn, n_rows, n_segs); return LLAMAHIP_ERR_PREDICT; }
+    if (seg_begin[0] != 0 || seg_begin[n_segs] != n_rows) { set_err(err, err_cap, "%s: seg_begin must run from 0 to n_rows (%d; got %d .. %d)", fn, n_rows, seg_begin[0], seg_begin[n_segs]); return LLAMAHIP_ERR_PREDICT; }
+    int32_t tab[2 * VERIFY_ROWS_MAX] = { 0 };          // row_off[16] | row_n_last[16]
+    for (int s = 0; s < n_segs; s++) {
+        if (seg_begin[s + 1] <= seg_begin[s]) { set_err(err, err_cap, "%s: seg_begin must ascend strictly (segment %d: %d .. %d)", fn, s, seg_begin[s], seg_begin[s + 1]); return LLAMAHIP_ERR_PREDICT; }
+        const int rows = seg_begin[s + 1] - seg_begin[s];
+        if (seg_ids_off[s] < 0 || seg_n_last[s] < 0) { set_err(err, err_cap, "%s: segment %d: seg_ids_off (%d) and seg_n_last (%d) must be >= 0", fn, s, seg_ids_off[s], seg_n_last[s]); return LLAMAHIP_ERR_PREDICT; }
+        if ((int64_t) seg_ids_off[s] + seg_n_last[s] + rows - 1 > (int64_t) n_ids) {
+            set_err(err, err_cap, "%s: segment %d's id stream does not fit: seg_ids_off (%d) + seg_n_last (%d) + rows (%d) - 1 > n_ids (%d)", fn, s, seg_ids_off[s], seg_n_last[s], rows, n_ids);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        for (int r = seg_begin[s]; r < seg_begin[s + 1]; r++) { tab[r] = seg_ids_off[s] + (r - seg_begin[s]); tab[VERIFY_ROWS_MAX + r] = seg_n_last[s]; }
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t R = n_rows, V = n_vocab;
+    std::vector<TopkOut> h(R);
+    Scratch s;
+    char *d_ws = s.alloc<char>(R * TOPK_WS_BYTES);
+    s.fill(d_ws, 0, R * TOPK_WS_BYTES);
+    float *d_l = s.alloc(R * V, logits);
+    int32_t *d_ids = s.alloc<int32_t>((size_t) n_ids + 1);
+    if (n_ids > 0) s.upload(d_ids, ids, (size_t) n_ids * 4);
+    int32_t *d_tab = s.alloc((size_t) 2 * VERIFY_ROWS_MAX, tab);
+    TopkOut *d_out = s.alloc<TopkOut>(R);
+    if (s.ok()) s.check(launch_topk_slide_set(d_l, n_rows, n_vocab, d_ids, d_tab, d_tab + VERIFY_ROWS_MAX, 1.0 / temp, repeat_penalty, top_k, d_out, nullptr, d_ws));
+    s.download(h.data(), d_out, R * sizeof(TopkOut));
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (size_t r = 0; r < R; r++) {
+        out_exact[r] = h[r].fl[0];
+        for (int i = 0; i < top_k; i++) { out_scores[r * 64 + i] = h[r].sc[i]; out_ids[r * 64 + i] = h[r].id[i]; }
+    }
+    return LLAMAHIP_OK;
+}
+
 // k_row_logprob on caller-supplied rows (parity tests): see llamahip_eval_logprobs
 int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *targets,
                         double *logprob_out, int32_t *argmax_out, int32_t *rank_out, char *err, size_t err_cap) {

@@ -22,9 +22,16 @@
            each), next to llamahip_decode_greedy_multi of the same run for the same sequences.  --parent-lib NAME measures
            llamahip_decode_greedy_multi of a second library file in csrc/ (a build of the parent commit) the same way, in its own process
 
+  multi sampled  (--multi --sampled: the drafted SAMPLED loop for several sequences, llamahip_verify_sample_multi /
+           llamahip_decode_sample_lookup_multi, one process) for 2 / 4 / 8 sequences: llamahip_decode_sample_multi's aggregate tokens/s and ms per
+           step, ms per llamahip_verify_sample_multi call filled to 16 rows at the three positions next to llamahip_verify_greedy_multi calls of
+           the same rows (wrong drafts), and the loop's aggregate tokens/s with the true streams as corpus (every draft accepted) and with a
+           drafter that never hits, all next to llamahip_decode_sample_multi of the same run for the same sequences and samplers
+
     python tools/lookup_probe.py [--out profiles/lookup_probe_7b.json] [--parent-lib libllamahip_parent.so] [--reps 20]
     python tools/lookup_probe.py --sampled [--out profiles/sample_lookup_probe_7b.json]
     python tools/lookup_probe.py --multi [--out profiles/lookup_multi_probe_7b.json] [--parent-lib libllamahip_parent.so]
+    python tools/lookup_probe.py --multi --sampled [--out profiles/sample_lookup_multi_probe_7b.json]
     python tools/lookup_probe.py --leg ceiling      (one leg in this process: for rocprofv3 --kernel-trace --stats)
 """
 import argparse
@@ -81,6 +88,8 @@ def leg(name, reps):
         return sampled_leg(reps)
     if name == "multi":
         return multi_leg(reps)
+    if name == "multi_sampled":
+        return multi_sampled_leg(reps)
     if name == "step":
         return step_leg(path, os.environ.get("LLAMAHIP_LIB", "libllamahip.so"))
     import llama_swift_amd as L
@@ -296,6 +305,91 @@ def multi_leg(reps):
     return {"sequences": res}
 
 
+def multi_sampled_leg(reps):
+    import numpy as np
+
+    import bench
+    import llama_swift_amd as L
+    import synth
+    path = bench.model_path("7B", bench.MODELS["7B"], 20230312)
+    seed = 20230312
+
+    def timed(prep, call, n):
+        """4 runs (the first is the warm-up), each on what prep() returns: fresh samplers are made outside the timed region"""
+        ts = []
+        for r in range(4):
+            arg = prep()
+            t0 = time.perf_counter()
+            ret = call(arg)
+            if r:
+                ts.append(time.perf_counter() - t0)
+        t = statistics.median(ts)
+        return ret, {"tok_s": round(n * STEPS / t, 1), "ms_per_token": round(1e3 * t / (n * STEPS), 4), "spread_ms_per_token": round(1e3 * (max(ts) - min(ts)) / (n * STEPS), 4)}
+
+    res = {}
+    with L.Model(path, n_ctx=N_CTX, n_seq=MULTI_SLOTS) as m:
+        prompts = [synth.synth_prompt(P, m.n_vocab, seed=4 + i) for i in range(MULTI_SLOTS)]
+        plg = []
+        for i in range(MULTI_SLOTS):
+            m.set_seq(i)
+            plg.append(m.eval(prompts[i], 0, NTH))
+        m.set_seq(0)
+
+        def fresh(n):
+            """sampler i: seed + i, the prompt and the first token (drawn from the prompt's logits) accepted"""
+            smp, firsts = [], []
+            for i in range(n):
+                s = L.Sampler(seed=seed + i, repeat_last_n=64)
+                for t in prompts[i]:
+                    s.accept(int(t))
+                firsts.append(s.sample(m, plg[i]))
+                s.accept(firsts[-1])
+                smp.append(s)
+            return smp, firsts
+
+        for n in MULTI_SEQS:
+            npast, r = [P] * n, {}
+            firsts = fresh(n)[1]
+            plain = lambda smp: m.decode_sample_multi(firsts, npast, STEPS, smp[0], n_threads=NTH)
+            out, r["decode_sample_multi"] = timed(lambda: fresh(n), plain, n)
+            G = out.tolist()
+            S = [[firsts[i]] + G[i] for i in range(n)]
+            r["set_step_ms"] = round(r["decode_sample_multi"]["ms_per_token"] * n, 4)
+            # a verify step over the set filled to 16 rows, sampled next to greedy: wrong from the first draft token
+            rows = [16 // n + (1 if i < 16 % n else 0) for i in range(n)]
+            tv = {"sample": {}, "greedy": {}}
+            smp = [L.Sampler(seed=seed + i, repeat_last_n=64) for i in range(n)]
+            for pos in (64, 256, 448):
+                i0 = pos - P
+                drafts = [(np.array(S[i][i0 + 1:i0 + rows[i]], np.int32) + 1) % m.n_vocab for i in range(n)]
+                toks = [S[i][i0] for i in range(n)]
+                for kind, call in (("sample", lambda: m.verify_sample_multi(range(n), toks, drafts, [pos] * n, smp, n_threads=NTH)),
+                                   ("greedy", lambda: m.verify_greedy_multi(range(n), toks, drafts, [pos] * n, NTH))):
+                    call()
+                    ts = []
+                    for _ in range(reps):
+                        t0 = time.perf_counter()
+                        call()
+                        ts.append(1e3 * (time.perf_counter() - t0))
+                    tv[kind][str(pos)] = round(statistics.median(ts), 4)
+                plain(fresh(n))                                                                # the true rows back
+            r["rows_per_sequence"] = rows
+            r["verify_sample_set_step_16_rows_ms"], r["verify_greedy_set_step_16_rows_ms"] = tv["sample"], tv["greedy"]
+            r["verify_sample_set_over_set_step"] = round(statistics.mean(tv["sample"].values()) / r["set_step_ms"], 4)
+            corpus = np.concatenate([np.array(g, np.int32) for g in G])
+            (out, st), r["loop_all_accepted"] = timed(lambda: fresh(n), lambda a: m.decode_sample_lookup_multi(firsts, npast, STEPS, prompts[:n], a[0], corpus=corpus, n_threads=NTH), n)
+            assert out.tolist() == G
+            r["loop_all_accepted"]["stats"] = st
+            (out, st), r["loop_nothing_drafted"] = timed(lambda: fresh(n), lambda a: m.decode_sample_lookup_multi(firsts, npast, STEPS, prompts[:n], a[0], ngram_min=4 * N_CTX,
+                                                                                                                  ngram_max=4 * N_CTX, n_threads=NTH), n)
+            assert out.tolist() == G and all(x["n_verify_steps"] == 0 for x in st)
+            base = r["decode_sample_multi"]["tok_s"]
+            r["loop_all_accepted"]["vs_decode_sample_multi"] = round(r["loop_all_accepted"]["tok_s"] / base, 4)
+            r["loop_nothing_drafted"]["vs_decode_sample_multi"] = round(r["loop_nothing_drafted"]["tok_s"] / base, 4)
+            res[str(n)] = r
+    return {"sequences": res}
+
+
 def child(name, reps, lib=None):
     env = dict(os.environ)
     if lib:
@@ -317,6 +411,15 @@ def main():
     a = ap.parse_args()
     if a.leg:
         print(json.dumps(leg(a.leg, a.reps)))
+        return
+    if a.multi and a.sampled:
+        res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH, "kv_slots": MULTI_SLOTS,
+               "sampler": "repeat_penalty 1.3, top_k 40, top_p 0.95, temp 0.8, repeat_last_n 64, seed 20230312 + sequence"}
+        res.update(child("multi_sampled", a.reps))
+        text = json.dumps(res, indent=1)
+        print(text)
+        with open(a.out or os.path.join(ROOT, "profiles", "sample_lookup_multi_probe_7b.json"), "w") as f:
+            f.write(text + "\n")
         return
     if a.multi:
         res = {"model": "synthetic LLaMA-7B Q4_0, 32 layers", "n_ctx": N_CTX, "positions": [P, P + STEPS], "n_threads": NTH, "kv_slots": MULTI_SLOTS}
