@@ -86,6 +86,20 @@ struct llamahip_lookup_stats;
 void llama_runner_bridge_set_lookup(llama_runner_bridge *b, int32_t draft_len);
 int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, struct llamahip_lookup_stats *out);
 
+/* Extension: generating past the context window (llamahip.h "generating past the context window").
+ * mode 0 = stop at the wall (the default and the reference's behaviour: n_predict = min(numberOfTokens, n_ctx - n_inp), .mm:812),
+ * 1 = re-evaluate (LLAMAHIP_CTX_REEVAL: exact); other values are 0.
+ * n_keep: the tokens at the start of the context that are never dropped; -1 = the prompt's length; either way at most n_ctx / 2.
+ * A bridge that never calls the setter -- a caller that cannot be changed -- takes LLAMAHIP_RUNNER_OVERFLOW=reeval from the
+ * environment at each run (n_keep -1).  llama_runner_config keeps its layout.
+ * With a mode set and a prompt that fits (n_inp <= n_ctx), n_predict is numberOfTokens, uncapped.  When the prompt is used up and the
+ * pending token has no room (n_past == n_ctx) the loop applies llamahip_ctx_overflow_plan and feeds
+ * the surviving tail's tokens again at n_past = n_keep the way the prompt is fed (llamahip_eval_chunks in chunks of n_batch + 1 = 9
+ * tokens); then the loop goes on as before.  Lookup steps cut their draft to the room left in the cache.  With mode 0 the loop runs the
+ * code it ran before and the event stream is unchanged; a prompt that does not fit is handled as before in every mode, and so
+ * is a context so small that the plan could never discard a token (n_ctx - n_keep < 2): the run stops at the wall as with mode 0. */
+void llama_runner_bridge_set_overflow(llama_runner_bridge *b, int32_t mode, int32_t n_keep);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -71,7 +71,7 @@ typedef struct llamahip_opts {
  * replacement bridge, with the environment variable LLAMAHIP_DEVICES="0,1,...,7" (or a count: "8" = devices 0 .. 7) -- holds one stage per
  * device; llamahip_eval / llamahip_eval_chunks / llamahip_eval_topk / llamahip_eval_logprobs / llamahip_perplexity / llamahip_decode_greedy /
  * llamahip_verify_greedy / llamahip_decode_greedy_lookup / llamahip_verify_sample / llamahip_decode_sample_lookup /
- * llamahip_verify_sample_multi / llamahip_decode_sample_lookup_multi / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
+ * llamahip_verify_sample_multi / llamahip_decode_sample_lookup_multi / llamahip_decode_greedy_window / llamahip_kv_read / llamahip_get_stats and the llama_runner_* driver work on it unchanged, the residual stream (.mm:563-564, 687-690)
  * crosses devices as stream-ordered peer copies.
  * Waiting for a stage is bounded: LLAMAHIP_PIPE_WATCHDOG_S seconds (default 600) without the stage's stream completing is LLAMAHIP_ERR_PREDICT, not a hang.
  * Results are bit for bit the single-device handle's, for every file type and flag the plain handle takes (f16 / f32 / Q4_1 files and
@@ -441,6 +441,33 @@ int llamahip_op_topk_slide_set(const float *logits, int32_t n_rows, int32_t n_vo
                                const int32_t *seg_begin, int32_t n_segs, const int32_t *seg_ids_off, const int32_t *seg_n_last,
                                double repeat_penalty, int32_t top_k, double temp,
                                double *out_scores, int32_t *out_ids, int32_t *out_exact, char *err, size_t err_cap);
+
+/* ---- generating past the context window ----------------------------------------------------------------------------------------------
+ * The reference stops when the KV cache is full (n_predict = min(n_predict, n_ctx - n_inp), .mm:812) and every entry point above refuses
+ * to pass n_ctx.  What every LLaMA runtime offers instead: keep the first n_keep tokens, drop the older half of the rest, go on.
+ * Here by RE-EVALUATION:
+ *   LLAMAHIP_CTX_REEVAL  rows [0, n_keep) stay; the surviving tail is evaluated again at its new positions (llamahip_eval /
+ *                        llamahip_eval_chunks at n_past = n_keep).  Defined purely by llama_eval calls, so it is EXACT: the reference making
+ *                        the same calls leaves the same bits.  Costs one eval of the tail.
+ *
+ * llamahip_ctx_overflow_plan -- host only, pure, the one rule every loop shares: *n_discard = (n_past - n_keep) / 2; returns the new
+ *   context n_past - *n_discard, or -1 (and *n_discard = 0) where that leaves n_discard < 1 or the arguments are out of range
+ *   (0 <= n_keep <= n_past <= n_ctx).
+ * llamahip_decode_greedy_window -- llamahip_decode_greedy in legs.  context: the n_context = n_past tokens at positions [0, n_past), as
+ *   llamahip_decode_greedy_lookup takes them.  Whenever the pending token has no room (position == n_ctx) the plan is applied -- the
+ *   tail's tokens go through llamahip_eval_chunks(n_past = n_keep, chunk_tokens), chunk_tokens 0 = one
+ *   llamahip_eval -- the loop's own token list drops the discarded tokens, and the pending token is evaluated as an ordinary single step.
+ *   n_steps may exceed n_ctx many times over; n_past == n_ctx on entry is allowed.  out_tokens [n_steps]; logits_last (may be NULL): the
+ *   last step's logits; *n_past_out (may be NULL): the context the cache holds afterwards.  Refused before any device work: what
+ *   llamahip_decode_greedy refuses (HOST_ONLY and stage handles, token ids out of range), a mode other than LLAMAHIP_CTX_REEVAL, n_context != n_past,
+ *   n_past > n_ctx, chunk_tokens < 0, and n_keep outside [0, n_ctx - 2] (nothing could be discarded at the wall).
+ * An in-place shift of the cache (move the surviving K / V rows down, re-rotate the keys) is a second way to carry out the same plan; it is
+ * not the reference's arithmetic and is not part of this library. */
+#define LLAMAHIP_CTX_REEVAL 1
+int32_t llamahip_ctx_overflow_plan(int32_t n_ctx, int32_t n_past, int32_t n_keep, int32_t *n_discard);
+int llamahip_decode_greedy_window(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
+                                  const int32_t *context, int32_t n_context, int32_t n_keep, int32_t mode, int32_t chunk_tokens,
+                                  int32_t *out_tokens, float *logits_last, int32_t *n_past_out, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */

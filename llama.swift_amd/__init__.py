@@ -14,12 +14,14 @@ The directory is literally named ``llama.swift_amd``; import it as ``llama_swift
 shim module at the repository root.
 """
 from .binding import (  # noqa: F401
+    CTX_REEVAL,
     LIB_PATH,
     LlamaHipError,
     Model,
     Sampler,
     bench_gemv_names,
     build,
+    ctx_overflow_plan,
     debug_attn_path,
     declared_symbols,
     gemm_paths,

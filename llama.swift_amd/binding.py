@@ -16,6 +16,7 @@ LIB_PATH = os.path.join(CSRC, os.environ.get("LLAMAHIP_LIB", "libllamahip.so")) 
 INCLUDE = os.path.join(ROOT, "include")
 
 ERR_LOAD, ERR_PREDICT = -1000, -1001
+CTX_REEVAL = 1          # LLAMAHIP_CTX_REEVAL: what to do when the KV cache is full
 DUMP_NAMES = [
     "layer_in", "attn_normed", "q", "k", "v", "q_roped", "kq_softmax", "kqv", "kqv_merged",
     "wo_out", "ffn_in", "ffn_normed", "w3_out", "w1_out", "silu_mul", "w2_out", "layer_out",
@@ -147,6 +148,9 @@ def lib() -> C.CDLL:
     L.llamahip_quantize_file.argtypes = [cp, cp, i32, cp, sz]
     L.llamahip_kv_read.argtypes = [vp, i32, i32, vp, vp, cp, sz]
     L.llamahip_set_seq.argtypes = [vp, i32, cp, sz]
+    L.llamahip_ctx_overflow_plan.argtypes = [i32, i32, i32, C.POINTER(i32)]
+    L.llamahip_ctx_overflow_plan.restype = i32
+    L.llamahip_decode_greedy_window.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, i32, i32, vp, vp, C.POINTER(i32), cp, sz]
     L.llamahip_tensor_bytes.argtypes = [vp, cp, vp, C.c_int64]
     L.llamahip_tensor_bytes.restype = C.c_int64
     L.llamahip_op_mul_mat_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, cp, sz]
@@ -629,6 +633,22 @@ class Model:
         stats = [{k: getattr(x, k) for k, _ in _LookupStats._fields_ if k != "struct_size"} for x in st[:ft.size]]
         return (out, exact, stats) if want_exact else (out, stats)
 
+    def decode_greedy_window(self, first_token: int, n_steps: int, n_past: int, context, n_keep: int = 0, mode: int = CTX_REEVAL,
+                             chunk_tokens: int = 0, n_threads: int = 8, want_logits: bool = False):
+        """llamahip_decode_greedy_window: decode_greedy in legs that never stop at n_ctx -- at the wall the first n_keep tokens stay, the older
+        half of the rest is dropped (ctx_overflow_plan) and the tail is re-evaluated (CTX_REEVAL, exact; chunk_tokens 0 = one eval).
+        context: the n_past tokens already evaluated.  Returns (tokens[n_steps], n_past afterwards) and with
+        want_logits the last step's logits too."""
+        context = np.ascontiguousarray(context, np.int32).ravel()
+        out = np.empty(max(n_steps, 0), np.int32)
+        logits = np.empty(self.n_vocab, np.float32) if want_logits else None
+        np_out = C.c_int32(-1)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_greedy_window(self._h, n_threads, n_past, int(first_token), n_steps, _ptr(context), context.size, n_keep, mode,
+                                                 chunk_tokens, _ptr(out), _ptr(logits), C.byref(np_out), err, len(err))
+        _check(rc, err)
+        return (out, np_out.value, logits) if want_logits else (out, np_out.value)
+
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
         v = np.empty((n_pos, self.n_embd), np.float32)
@@ -713,6 +733,13 @@ class Sampler:
                 self._s = None
         except Exception:
             pass
+
+
+def ctx_overflow_plan(n_ctx: int, n_past: int, n_keep: int):
+    """llamahip_ctx_overflow_plan (host only): (new context, n_discard) with n_discard = (n_past - n_keep) // 2, or (-1, 0) where nothing can be dropped."""
+    nd = C.c_int32(-1)
+    new = lib().llamahip_ctx_overflow_plan(n_ctx, n_past, n_keep, C.byref(nd))
+    return int(new), int(nd.value)
 
 
 def op_topk(logits, window, repeat_penalty: float = 1.3, top_k: int = 40, temp: float = float(np.float32(0.8))):

@@ -900,6 +900,17 @@ int check_eval_args(llamahip_model *m, int n_past, const int32_t *tokens, int N,
 
 }  // namespace
 
+// what llamahip_decode_greedy refuses of a HANDLE, for the loops above the C ABI (ctx_overflow.cpp): no device is touched
+namespace lh {
+int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!m->stages.empty()) return 0;
+    if (m->host_only) { set_err(err, err_cap, "%s: model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!m->first_stage || !m->last_stage) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+}  // namespace lh
+
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------

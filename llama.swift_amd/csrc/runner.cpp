@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <random>
@@ -40,6 +41,8 @@ struct llama_runner_bridge {
     int64_t loads = 0;                   // model loads performed by this bridge (tests)
     int32_t lookup = -1;                 // drafted sampled decoding: -1 never set (LLAMAHIP_RUNNER_LOOKUP decides), 0 off, 1 .. 15 the draft length
     llamahip_lookup_stats lookup_stats = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };   // of the last run
+    int32_t overflow = -1;               // past the context window: -1 never set (LLAMAHIP_RUNNER_OVERFLOW decides), 0 stop at the wall, 1 re-evaluate
+    int32_t overflow_keep = -1;          // ... tokens never dropped; -1 = the prompt's length
 };
 
 // llama_sample_top_p_top_k from the soft-max on (utils.cpp:397-428): `cand` = the top_k candidates, best first
@@ -217,6 +220,11 @@ const char *llama_runner_bridge_model_path(const llama_runner_bridge *b) { retur
 void llama_runner_bridge_set_lookup(llama_runner_bridge *b, int32_t draft_len) {
     if (b) b->lookup = std::min(std::max(draft_len, 0), 15);
 }
+void llama_runner_bridge_set_overflow(llama_runner_bridge *b, int32_t mode, int32_t n_keep) {
+    if (!b) return;
+    b->overflow = mode == LLAMAHIP_CTX_REEVAL ? mode : 0;
+    b->overflow_keep = n_keep < 0 ? -1 : n_keep;
+}
 int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, llamahip_lookup_stats *out) {
     if (!b || !out || out->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) return -1;
     *out = b->lookup_stats;
@@ -245,6 +253,13 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
     if (lookup < 0) {
         const char *e = getenv("LLAMAHIP_RUNNER_LOOKUP");
         lookup = e ? std::min(std::max(atoi(e), 0), 15) : 0;
+    }
+    // past the context window: the setter's values, else LLAMAHIP_RUNNER_OVERFLOW=reeval (0: the reference's stop at the wall)
+    int32_t overflow = b->overflow, keep_req = b->overflow_keep;
+    if (overflow < 0) {
+        const char *e = getenv("LLAMAHIP_RUNNER_OVERFLOW");
+        overflow = e && !strcmp(e, "reeval") ? LLAMAHIP_CTX_REEVAL : 0;
+        keep_req = -1;
     }
     llamahip_lookup_stats &ls = b->lookup_stats;
     ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
@@ -278,6 +293,9 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
     const int32_t n_inp = llamahip_tokenize(model, prompt.c_str(), 1, embd_inp.data(), (int32_t) embd_inp.size());   // .mm:810
     embd_inp.resize(n_inp);
     int32_t n_predict = std::min((int32_t) cfg.numberOfTokens, n_ctx - n_inp);     // .mm:812
+    const int32_t n_keep = std::min(keep_req < 0 ? n_inp : keep_req, n_ctx / 2);
+    if (overflow && llamahip_ctx_overflow_plan(n_ctx, n_ctx, n_keep, nullptr) < 0) overflow = 0;      // nothing could ever be discarded -- stop at the wall
+    if (overflow && n_inp <= n_ctx) n_predict = (int32_t) std::min<uint32_t>(cfg.numberOfTokens, 0x7fffffffu);      // a prompt that fits: no wall
     if (cfg.reversePrompt) {                                                        // .mm:815 (result unused there too)
         std::vector<int32_t> anti(strlen(cfg.reversePrompt) + 2);
         (void) llamahip_tokenize(model, cfg.reversePrompt, 0, anti.data(), (int32_t) anti.size());
@@ -305,17 +323,31 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
     const bool lookup_on = lookup > 0 && !cfg.greedy && !host_sampler;
     std::vector<int32_t> hist;                                                      // lookup: the prompt tokens + everything generated so far
     if (lookup_on) hist = embd_inp;
+    std::vector<int32_t> ctx_toks;                                                  // overflow: the tokens at positions [0, n_past)
     while (remaining > 0) {                                                         // .mm:834
         bool have_cand = false;
+        if (overflow && embd_inp.size() <= consumed && embd.size() == 1 && n_past == n_ctx) {
+            // the pending token has no room: keep [0, n_keep), drop the older half of the rest, go on (llamahip.h "generating past the
+            // context window") -- re-evaluation feeds the surviving tail the way the prompt is fed, in chunks of n_batch + 1 tokens
+            int32_t n_discard = 0;
+            const int32_t n_new = llamahip_ctx_overflow_plan(n_ctx, n_past, n_keep, &n_discard);
+            if (n_new < 0) { snprintf(err, sizeof(err), "context overflow: nothing to discard at n_ctx %d with n_keep %d", n_ctx, n_keep); return fail(); }
+            if (llamahip_eval_chunks(model, n_threads, n_keep, ctx_toks.data() + n_keep + n_discard, n_past - n_keep - n_discard, n_batch + 1,
+                                     nullptr, err, sizeof(err)) != 0) return fail();
+            ctx_toks.erase(ctx_toks.begin() + n_keep, ctx_toks.begin() + n_keep + n_discard);
+            n_past = n_new;
+        }
         if (lookup_on && embd_inp.size() <= consumed && embd.size() == 1) {
             // a lookup step: the pending token (drawn, accepted and posted) with a draft behind it as ONE eval; the sampler walks the rows
             // exactly as the iterations below would have (llamahip_verify_sample) -- same draws, same window, same events
             int32_t draft[15], picks[16], n_acc = 0;
-            const int32_t room = std::min(lookup, remaining - 1);
+            int32_t room = std::min(lookup, remaining - 1);
+            if (overflow) room = std::min(room, n_ctx - n_past - 1);               // the rows of a verify step must fit the cache
             const int32_t nd = room > 0 ? llamahip_lookup_draft(hist.data(), (int32_t) hist.size(), nullptr, 0, room, 0, 0, draft) : 0;
             if (nd > 0) {
                 if (llamahip_verify_sample(model, n_threads, n_past, embd[0], draft, nd, sampler, repeat_penalty, top_k, top_p, temp,
                                            &n_acc, picks, nullptr, err, sizeof(err)) != 0) return fail();
+                if (overflow) { ctx_toks.push_back(embd[0]); ctx_toks.insert(ctx_toks.end(), picks, picks + n_acc); }
                 n_past += n_acc + 1;
                 remaining -= n_acc + 1;
                 ls.n_verify_steps++;
@@ -337,6 +369,7 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
             // reference's chunk-by-chunk evals do (llamahip_eval_chunks); the last chunk takes the usual route, its logits may be sampled
             const int32_t chunk = n_batch + 1, n_full = (((int32_t) embd.size() - 1) / chunk) * chunk;
             if (llamahip_eval_chunks(model, n_threads, n_past, embd.data(), n_full, chunk, nullptr, err, sizeof(err)) != 0) return fail();
+            if (overflow) ctx_toks.insert(ctx_toks.end(), embd.begin(), embd.begin() + n_full);
             n_past += n_full;
             embd.erase(embd.begin(), embd.begin() + n_full);
         }
@@ -357,6 +390,7 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
                 have_cand = exact == 1;
             } else if (llamahip_eval(model, n_threads, n_past, embd.data(), (int32_t) embd.size(), logits.data(), err, sizeof(err)) != 0) return fail();
         }
+        if (overflow) ctx_toks.insert(ctx_toks.end(), embd.begin(), embd.end());
         n_past += (int32_t) embd.size();
         embd.clear();
         if (embd_inp.size() <= consumed) {                                          // .mm:851

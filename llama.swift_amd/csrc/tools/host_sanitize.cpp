@@ -38,7 +38,7 @@ const char *llamahip_token_text(const llamahip_model *m, int32_t id, uint32_t *l
 // Two modes.  Default: every eval fails like a box without a GPU.  g_drive: evals SUCCEED with deterministic made-up logits and are
 // logged, so that the generation driver's control flow (warm-up, the prompt taken at once and evaluated chunk-exactly, the last
 // chunk's sampled logits, one eval per generated token, the event sequence) runs end to end on the host, under the sanitizers.
-struct EvalCall { int kind /* 0 eval, 1 eval_chunks, 2 eval_topk */, n_past, n, chunk; };
+struct EvalCall { int kind /* 0 eval, 1 eval_chunks, 2 eval_topk, 3 decode_greedy (n steps), 4 verify_sample (n rows) */, n_past, n, chunk; };
 static bool g_drive = false;
 static std::vector<EvalCall> g_calls;
 static int fake_eval(llamahip_model *m, int kind, int32_t np, const int32_t *t, int32_t n, int32_t chunk, float *lg, char *err, size_t err_cap) {
@@ -53,9 +53,38 @@ int llamahip_eval(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int3
 int llamahip_eval_chunks(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int32_t n, int32_t chunk, float *lg, char *err, size_t err_cap) { return fake_eval(m, 1, np, t, n, chunk, lg, err, err_cap); }
 int llamahip_eval_topk(llamahip_model *m, int32_t, int32_t np, const int32_t *t, int32_t n, const int32_t *, int32_t, double, int32_t, double,
                        double *, int32_t *, int32_t *exact, float *lg, char *err, size_t err_cap) { *exact = 0; return fake_eval(m, 2, np, t, n, 0, lg, err, err_cap); }
-// (the driver's lookup steps are off here -- no setter call, no LLAMAHIP_RUNNER_LOOKUP -- so this is never reached)
-int llamahip_verify_sample(llamahip_model *, int32_t, int32_t, int32_t, const int32_t *, int32_t, llamahip_sampler *, double, int32_t, double, double,
-                           int32_t *, int32_t *, int32_t *, char *err, size_t err_cap) { snprintf(err, err_cap, "no HIP device available: libllamahip has no CPU fallback"); return LLAMAHIP_ERR_PREDICT; }
+// the driver's lookup steps: off in the runs above (no setter call, no LLAMAHIP_RUNNER_LOOKUP); in the overflow runs with lookup on the
+// step succeeds on made-up draws -- every draft token accepted at odd positions, none at even ones -- refuses rows past the cache and is logged
+int llamahip_verify_sample(llamahip_model *m, int32_t, int32_t np, int32_t token, const int32_t *draft, int32_t nd, llamahip_sampler *s, double, int32_t, double, double,
+                           int32_t *n_accept, int32_t *picks, int32_t *, char *err, size_t err_cap) {
+    if (!g_drive) { snprintf(err, err_cap, "no HIP device available: libllamahip has no CPU fallback"); return LLAMAHIP_ERR_PREDICT; }
+    if (!m || !draft || nd < 1 || nd > 15 || np < 0 || np + nd + 1 > m->file.hp.n_ctx) { snprintf(err, err_cap, "context overflow: n_past (%d) + n_draft (%d) + 1 > n_ctx (%d)", np, nd, m ? m->file.hp.n_ctx : 0); return LLAMAHIP_ERR_PREDICT; }
+    g_calls.push_back({ 4, np, nd + 1, 0 });
+    const int V = m->file.hp.n_vocab, acc = np % 2 ? nd : 0;
+    for (int j = 0; j < acc; j++) picks[j] = draft[j];
+    picks[acc] = (int32_t) (((uint32_t) token * 31u + (uint32_t) np * 7u + 5u) % (uint32_t) V);
+    for (int j = acc + 1; j <= nd; j++) picks[j] = -1;
+    for (int j = 0; j <= acc; j++) llamahip_sampler_accept(s, picks[j]);
+    *n_accept = acc;
+    return 0;
+}
+// past the context window (ctx_overflow.cpp, the driver's overflow modes): the greedy leg makes up its picks
+int32_t llamahip_n_ctx(const llamahip_model *m) { return m ? m->file.hp.n_ctx : 0; }
+int llamahip_decode_greedy(llamahip_model *m, int32_t, int32_t np, int32_t first, int32_t n, int32_t *out, float *lg, char *err, size_t err_cap) {
+    if (!g_drive) { snprintf(err, err_cap, "no HIP device available: libllamahip has no CPU fallback"); return LLAMAHIP_ERR_PREDICT; }
+    if (!m || n < 1 || np < 0 || np + n > m->file.hp.n_ctx) { snprintf(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", np, n, m ? m->file.hp.n_ctx : 0); return LLAMAHIP_ERR_PREDICT; }
+    g_calls.push_back({ 3, np, n, 0 });
+    const int V = m->file.hp.n_vocab;
+    for (int i = 0; i < n; i++) out[i] = (int32_t) (((uint32_t) (i ? out[i - 1] : first) * 31u + (uint32_t) (np + i) * 7u + 3u) % (uint32_t) V);
+    for (int i = 0; lg && i < V; i++) lg[i] = (float) i;
+    return 0;
+}
+}
+namespace lh {
+int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
+    if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
 }
 
 static int failures = 0;
@@ -186,6 +215,86 @@ int main(int argc, char **argv) {
                    P, g_calls.size(), n_full, P - n_full, e2.tokens);
         }
         if (mv) llamahip_model_free(mv);
+        g_drive = false;
+    }
+    // past the context window: the plan over a grid; the greedy loop in legs (exactly sized arrays, every n_keep that leaves
+    // something to discard, a start at the wall) and its refusals; the driver with and without the overflow mode, with and without lookup steps
+    for (int C = 1; C <= 12; C++)
+        for (int np = -1; np <= C + 1; np++)
+            for (int keep = -1; keep <= C + 1; keep++) {
+                int32_t nd = -7;
+                const int32_t got = llamahip_ctx_overflow_plan(C, np, keep, &nd);
+                const bool bad = np < 0 || np > C || keep < 0 || keep > np || (np - keep) / 2 < 1;
+                EXPECT(bad ? (got == -1 && nd == 0) : (nd == (np - keep) / 2 && got == np - nd));
+                EXPECT(llamahip_ctx_overflow_plan(C, np, keep, nullptr) == got);
+            }
+    if (parts <= 1) {
+        g_drive = true;
+        llamahip_model *mw = nullptr;
+        EXPECT(llamahip_model_load(path.c_str(), 16, &o, &mw, err, sizeof(err)) == 0);
+        if (mw)
+            for (int keep = 0; keep <= 14; keep++)
+                for (int np0 : { 0, 5, 16 })
+                    for (int chunk : { 0, 3 }) {
+                        const int n_steps = 70;
+                        std::vector<int32_t> ctx((size_t) np0), out((size_t) n_steps, -1);
+                        for (int i = 0; i < np0; i++) ctx[i] = (int32_t) (rng() % (uint32_t) V);
+                        int32_t np_out = -1;
+                        g_calls.clear();
+                        const int rcw = llamahip_decode_greedy_window(mw, 1, np0, 1, n_steps, ctx.data(), np0, keep, LLAMAHIP_CTX_REEVAL, chunk, out.data(), nullptr, &np_out, err, sizeof(err));
+                        EXPECT(rcw == 0);
+                        // replay: the calls against the plan, the steps they add up to, the final context
+                        int pos = np0, steps = 0;
+                        for (const EvalCall &c : g_calls) {
+                            if (c.kind == 3) { EXPECT(c.n_past == pos && pos + c.n <= 16); pos += c.n; steps += c.n; continue; }
+                            int32_t nd = 0;
+                            const int32_t nn = llamahip_ctx_overflow_plan(16, pos, keep, &nd);
+                            EXPECT(pos == 16 && nn > 0);
+                            EXPECT(c.kind == (chunk ? 1 : 0) && c.chunk == chunk && c.n_past == keep && c.n == pos - keep - nd);
+                            pos = nn;
+                        }
+                        EXPECT(steps == n_steps && np_out == pos);
+                        for (int32_t t : out) EXPECT(t >= 0 && t < V);
+                    }
+        if (mw) {
+            int32_t out1[4], one = 1, npo = 0;
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 4, &one, 1, 0, 0, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // mode
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 4, &one, 1, 15, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);     // n_keep
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 4, &one, 1, -1, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 4, &one, 0, 0, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // n_context
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 17, 1, 4, &one, 17, 0, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);    // n_past
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 0, &one, 1, 0, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // n_steps
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, 1, 4, &one, 1, 0, 1, -1, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);     // chunk_tokens
+            EXPECT(llamahip_decode_greedy_window(mw, 1, 1, V, 4, &one, 1, 0, 1, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // token id
+            EXPECT(llamahip_decode_greedy_window(nullptr, 1, 1, 1, 4, &one, 1, 0, 1, 0, out1, nullptr, &npo, nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+            llamahip_model_free(mw);
+        }
+        // the driver: 60 tokens at n_ctx 24, without and with the overflow mode, greedy and sampled (made-up logits: eval_topk reports inexact, the host sampler draws)
+        for (int mode = 0; mode <= 1; mode++)
+            for (int greedy = 0; greedy <= 2; greedy++)          // (2: sampled with lookup steps of up to 4 draft tokens)
+                for (int keep : { -1, 0, 3, 100 }) {
+                    struct Ev3 { int tokens = 0, failed = 0, completed = 0; } e3;
+                    g_calls.clear();
+                    llama_runner_bridge *b3 = llama_runner_bridge_new(path.c_str());
+                    llama_runner_bridge_set_overflow(b3, mode, keep);
+                    if (greedy == 2) llama_runner_bridge_set_lookup(b3, 4);
+                    llama_runner_config c3; llama_runner_config_default(&c3); c3.numberOfTokens = 60; c3.n_ctx = 24; c3.greedy = greedy == 1; c3.seed = 7;
+                    const int32_t rc3 = llama_runner_bridge_run(b3, "", &c3, [](void *u, llama_event_type t, const char *, uint32_t, int32_t) {
+                        Ev3 *e = (Ev3 *) u; if (t == LLAMA_EVENT_OUTPUT_TOKEN) e->tokens++; if (t == LLAMA_EVENT_FAILED) e->failed++; if (t == LLAMA_EVENT_COMPLETED) e->completed++; }, &e3);
+                    llama_runner_bridge_free(b3);
+                    EXPECT(rc3 == 0 && e3.failed == 0 && e3.completed == 1);
+                    int reevals = 0, over = 0, verifies = 0;
+                    for (size_t k = 1; k < g_calls.size(); k++) {          // (k = 0: the warm-up)
+                        const EvalCall &c = g_calls[k];
+                        if (c.kind == 4) verifies++;
+                        else if (k > 1 && c.n > 1) reevals++;
+                        if (c.n_past + c.n > 24) over++;
+                    }
+                    EXPECT(over == 0);
+                    EXPECT(greedy == 2 ? verifies > 0 : verifies == 0);          // (a verify step whose rows pass the cache fails the run: counted in `failed`)
+                    if (mode == 0) EXPECT(reevals == 0 && e3.tokens <= 24);
+                    if (mode == 1) EXPECT(reevals >= 2 && e3.tokens > 60);
+                }
         g_drive = false;
     }
     // the dealing of a multi-sequence verify step's rows: exactly sized arrays, every n_seqs and budget, and the refusals

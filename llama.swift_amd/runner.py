@@ -70,6 +70,14 @@ class LlamaRunner:
         L.llama_runner_bridge_set_lookup.restype = None
         L.llama_runner_bridge_set_lookup(bridge, int(draft_len))
 
+    def set_overflow(self, mode: int, n_keep: int = -1) -> None:
+        """Generating past the context window (llama_runner_bridge_set_overflow): mode 0 = stop at the wall (the reference), 1 = re-evaluate
+        the surviving tail (exact); n_keep -1 = the prompt's length."""
+        L, bridge = self._get_bridge()
+        L.llama_runner_bridge_set_overflow.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        L.llama_runner_bridge_set_overflow.restype = None
+        L.llama_runner_bridge_set_overflow(bridge, int(mode), int(n_keep))
+
     def lookup_stats(self) -> dict:
         """The lookup step counts of the last run (llama_runner_bridge_lookup_stats): all zero before the first run and with lookup off."""
         L, bridge = self._get_bridge()
