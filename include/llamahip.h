@@ -210,7 +210,9 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
  * groups of up to 16 as sets (llamahip_stage_step_set: the weights are streamed once per step for a whole group); on a pipeline handle
  * (n_devices > 1) the groups -- at least one per stage -- are additionally pipelined over the stages: in steady state every stage (GPU) works on a
  * different group, rows and picks move between stages as stream-ordered copies.  The native form of the schedule bench.py --gpus N runs over RCCL.
- * f16 / f32 / Q4_1 files and LLAMAHIP_FLAG_UNFUSED handles have no set step: their sequences run one after the other, llamahip_decode_greedy each. */
+ * f16 / f32 files take the same set steps on plain handles (the few-row dense mat-mul k_dense_set streams the weights once per step: DESIGN.md
+ * 12.16); Q4_1 files, LLAMAHIP_FLAG_UNFUSED handles and pipeline handles over f16 / f32 stages have no set step: their sequences run one after
+ * the other, llamahip_decode_greedy each. */
 int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
                                  int32_t n_steps, int32_t *out_tokens, char *err, size_t err_cap);
 
@@ -222,8 +224,9 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
  * on that slot alone: out_tokens[i * n_steps + t]; the samplers' windows and rng states end where that loop leaves them.  The candidate
  * selection runs on the device behind each group's step; the draw stays on the host, one group at a time while the groups behind it run.
  * out_exact (may be NULL), the same shape: 1 = drawn from the device's candidates, 0 = from the full logits row on the host (a tie only
- * libstdc++'s partial_sort orders, a NaN, a window longer than 1024 ids, top_k > 64 or n_vocab > 32768).  f16 / f32 / Q4_1 files and
- * LLAMAHIP_FLAG_UNFUSED handles run the single-sequence loop above on each slot in turn. */
+ * libstdc++'s partial_sort orders, a NaN, a window longer than 1024 ids, top_k > 64 or n_vocab > 32768).  f16 / f32 files on plain handles
+ * take the set steps too; Q4_1 files, LLAMAHIP_FLAG_UNFUSED handles and pipeline handles over f16 / f32 stages run the single-sequence loop
+ * above on each slot in turn. */
 int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
                                  int32_t n_steps, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p,
                                  double temp, int32_t *out_tokens, int32_t *out_exact, char *err, size_t err_cap);
@@ -495,6 +498,9 @@ int llamahip_eval_stage(llamahip_model *m, int32_t n_threads, int32_t n_past,
  *   hidden_out fp32[n_embd]    residual stream for the next stage      (NULL on the last stage)
  *   token_out  int32[1]        greedy pick (argmax, lowest index on ties) of the last stage; may be
  *                              NULL, and may alias token_in on a whole-model handle
+ * token_in is checked at bind: an address that is not device-accessible memory is refused there (the step's first kernel reads it; with
+ * tokens on the host use llamahip_eval_stage).  Handles: every Q4_0 handle shape; f16 / f32 whole-model handles (the un-fused dense step,
+ * captured the same way); not Q4_1 files, LLAMAHIP_FLAG_UNFUSED handles or layer-range f16 / f32 handles.
  * llamahip_stage_step enqueues one token step for that slot on `stream` (a hipStream_t; NULL = the
  * null stream) and returns without waiting: the caller orders its receives before and its
  * sends after the step on the same stream.  The position advances on the device after every step
@@ -523,8 +529,9 @@ int llamahip_stage_trace(llamahip_model *m, int32_t seq, int32_t *n_past, int32_
  * a captured step is keyed by that bucket too and re-captured when a row crosses into the next one). */
 int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_seqs, int32_t n_threads, void *stream,
                             char *err, size_t err_cap);
-/* 1 if llamahip_stage_step_set can step n_seqs slots of this handle with this n_threads as ONE set (Q4_0 handle with layers, head size a
- * multiple of 32, n_threads <= 32); 0: step the slots one by one with llamahip_stage_step (up to 64 threads, every handle shape). */
+/* 1 if llamahip_stage_step_set can step n_seqs slots of this handle with this n_threads as ONE set (Q4_0 handle with layers or f16 / f32
+ * whole-model handle, head size a multiple of 32, n_threads <= 32); 0: step the slots one by one with llamahip_stage_step (up to 64 threads;
+ * every Q4_0 handle shape, f16 / f32 whole-model handles). */
 int32_t llamahip_stage_set_applies(const llamahip_model *m, int32_t n_seqs, int32_t n_threads);
 
 /* Device-side mailboxes between pipeline stages: instead of the caller moving hidden_out -> hidden_in (and token_out -> token_in)
@@ -595,6 +602,20 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
 #define LLAMAHIP_GEMM_GEMV    7   /* reported only */
 int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
+/* The f16 / f32 mat-mul with its kernel chosen by the caller: y[n][m] = dot(W[m], act(x[n])) (+ resid[n][m]), bit for bit ggml_vec_dot_f16
+ * (wtype 1: act rounds x to fp16, as the reference's mat-mul does once per row) or ggml_vec_dot_f32 (wtype 0).  w: M rows of K fp16 / fp32
+ * values in file layout, K a positive multiple of 32; x [N][K]; resid [N][M] or NULL; y [N][y_stride], y_stride >= M: the WHOLE buffer is
+ * copied to the device before the launch and back after it, so columns M .. y_stride - 1 keep what the caller put there unless a kernel
+ * writes out of place.  path: LLAMAHIP_DENSE_AUTO -- what a model handle picks (one row _MV, 2 .. 16 rows _SET or _MM by the measured rule of
+ * DESIGN.md 12.16, more _MM); _MV k_dense_mv, the decode mat-vec, one launch per row; _MM k_dense_mm (any N: the weights are streamed once
+ * per 8 rows); _SET k_dense_set (N 1 .. 16: the weights streamed once).  Refusals name their limit and happen before any device is touched.
+ * *path_taken (may be NULL): the path that ran. */
+#define LLAMAHIP_DENSE_AUTO 0
+#define LLAMAHIP_DENSE_MV   1
+#define LLAMAHIP_DENSE_MM   2
+#define LLAMAHIP_DENSE_SET  3
+int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                              float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -686,6 +707,14 @@ int64_t llamahip_debug_decode_phases(llamahip_model *m, int32_t n_past, int32_t 
  *  few rows (k_gemv_set), the fast kernel of LLAMAHIP_FLAG_FAST_PREFILL (k_gemm_mfma<*, true>: also counted as matrix-core)}:
  * lets a test assert that a shape took the path it is meant to.  Returns the number of families. */
 int32_t llamahip_debug_gemm_paths(int64_t *out, int32_t cap);
+/* Launch counts of the f16 / f32 mat-mul kernels since process start: out[0 .. 2] = { k_dense_mv, k_dense_mm, k_dense_set } (at most `cap`
+ * entries are written); returns 3.  Tests and measurement tooling. */
+int32_t llamahip_debug_dense_paths(int64_t *out, int32_t cap);
+/* Host only: the launch plan of k_dense_set for an M x K matrix of wtype (0 fp32, 1 fp16) and n_rows activation rows --
+ * out = { grid, threads per workgroup, weight rows per half-wave, activation rows of the compiled instance, groups of 256 elements per
+ * row and LDS slab, static LDS bytes }.  Returns 1, 0 where the kernel does not take the shape (K not a multiple of 32, n_rows outside
+ * 1 .. 16, another wtype), -1 where the plan names an instance that was never compiled. */
+int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]);
 /* Host-only (no device needed): the attention path (LLAMAHIP_ATTN_SHORT / _MFMA / _ROW) a model's multi-row eval of N rows after n_past
  * takes once its workspace exists (allocated with the first multi-row eval), or -1 for N < 2 -- the rule llamahip_op_attention's AUTO runs. */
 int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx);

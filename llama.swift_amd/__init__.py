@@ -24,6 +24,8 @@ from .binding import (  # noqa: F401
     ctx_overflow_plan,
     debug_attn_path,
     declared_symbols,
+    dense_paths,
+    dense_set_plan,
     gemm_paths,
     lib,
     lookup_deal_rows,
@@ -31,6 +33,7 @@ from .binding import (  # noqa: F401
     op_attention,
     op_embed,
     op_logprob,
+    op_mul_mat_dense,
     op_mul_mat_q4_0,
     op_prep,
     op_prompt_gemm_q4_0,

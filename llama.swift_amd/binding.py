@@ -170,6 +170,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_lut_math.restype = i32
     L.llamahip_debug_gemm_paths.argtypes = [vp, i32]
     L.llamahip_debug_gemm_paths.restype = i32
+    L.llamahip_op_mul_mat_dense.argtypes = [vp, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
+    L.llamahip_debug_dense_paths.argtypes = [vp, i32]
+    L.llamahip_debug_dense_paths.restype = i32
+    L.llamahip_debug_dense_set_plan.argtypes = [i32, i32, i32, i32, vp]
+    L.llamahip_debug_dense_set_plan.restype = i32
     _lib = L
     return L
 
@@ -202,6 +207,24 @@ def gemm_paths() -> dict:
     a = np.zeros(8, np.int64)
     n = lib().llamahip_debug_gemm_paths(a.ctypes.data_as(C.c_void_p), 8)
     return dict(zip(("mfma", "rows", "lds", "gemv", "set", "fast"), a[:n].tolist()))
+
+
+def dense_paths() -> dict:
+    """Launch counts of the f16 / f32 mat-mul kernels since process start (llamahip_debug_dense_paths)."""
+    a = np.zeros(4, np.int64)
+    n = lib().llamahip_debug_dense_paths(a.ctypes.data_as(C.c_void_p), 4)
+    return dict(zip(("mv", "mm", "set"), a[:n].tolist()))
+
+
+def dense_set_plan(m: int, k: int, wtype: int, n_rows: int):
+    """Host-only: the launch plan of the few-row f16 / f32 mat-mul k_dense_set (llamahip_debug_dense_set_plan) for n_rows rows against an
+    m x k matrix of wtype (0 fp32, 1 fp16): a dict, or None where the kernel does not take the shape; a plan that names an instance that
+    does not exist is an error."""
+    a = np.zeros(6, np.int64)
+    rc = lib().llamahip_debug_dense_set_plan(m, k, wtype, n_rows, a.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise LlamaHipError(rc, f"dense_set_plan({m}, {k}, wtype={wtype}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
+    return dict(zip(("grid", "threads", "rows_per_half_wave", "rows", "slab_groups", "lds_bytes"), (int(x) for x in a))) if rc else None
 
 
 def version() -> str:
@@ -931,6 +954,32 @@ def op_prompt_gemm_q4_0(wq: np.ndarray, x: np.ndarray, resid=None, path: str = "
     rc = lib().llamahip_op_prompt_gemm_q4_0(_ptr(wq), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
     _check(rc, err)
     return y, GEMM_PATHS[taken.value]
+
+
+DENSE_PATHS = ("auto", "mv", "mm", "set")      # LLAMAHIP_DENSE_* of llamahip.h, in order
+
+
+def op_mul_mat_dense(w: np.ndarray, x: np.ndarray, resid=None, path: str = "auto", y_stride: int | None = None, y_init=None, wtype: int | None = None):
+    """One f16 / f32 mat-mul kernel (llamahip_op_mul_mat_dense): w float16 or float32 [M, K] (file layout; wtype overrides the dtype's 1 / 0),
+    x f32 [N, K], resid f32 [N, M] or None.  path: one of DENSE_PATHS.  Returns (y f32 [N, y_stride], the path taken): the whole buffer as the
+    device left it -- y_init (default: NaN everywhere) is what columns M .. y_stride - 1 keep."""
+    w = np.ascontiguousarray(w)
+    if w.dtype not in (np.float16, np.float32):
+        w = w.astype(np.float32)
+    wt = (1 if w.dtype == np.float16 else 0) if wtype is None else int(wtype)
+    M, K = w.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    code = DENSE_PATHS.index(path) if path in DENSE_PATHS else int(path)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_mul_mat_dense(_ptr(w), wt, M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
+    _check(rc, err)
+    return y, DENSE_PATHS[taken.value]
 
 
 ATTN_PATHS = ("auto", "mfma", "row", "short", "dec", "dec_stream")      # LLAMAHIP_ATTN_* of llamahip.h, in order

@@ -12,10 +12,14 @@
 // One half-wave (32 lanes = the 32 chains) owns RG weight rows x NC activation rows; the fold is the
 // xor butterfly 8, 16, 4, 1, 2 (the reference's tree; float add commutes).  Weights and activations are kept
 // in a chain-major order (perm_index) so that a lane's loads are 16 / 32 bytes wide.
+// Three mat-mul kernels share that arithmetic: k_dense_mv (one row, software-pipelined), k_dense_set (2 .. 16 rows -- a set step's rows, the
+// 9-token prompt evals -- the weights streamed once, the rows shared through LDS) and k_dense_mm (any row count, 8 rows per pass over the
+// weights); launch_dense_mm picks.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <stdlib.h>
+#include <algorithm>
 
 #include "llamahip_internal.h"
 
@@ -353,6 +357,144 @@ k_dense_mv(const void *__restrict__ wv, int M, int K, const float *__restrict__ 
     }
 }
 
+// 2 .. 16 activation rows, the weights streamed ONCE: k_dense_mv's chains and its software-pipelined weight loads, with
+// NR accumulators per weight row.  A half-wave owns RGS weight rows x NR activation rows (RGS = RG, or 2 for the narrow matrices: twice
+// the waves on the same bytes, see dense_set_plan); the activation rows reach the 8
+// half-waves of a workgroup through LDS in slabs of UG groups (256 elements) per row -- 16 fp32 rows of K = 11 008 do not
+// fit -- staged global -> registers -> LDS one slab ahead, into the buffer the previous slab was read from a barrier ago
+// (two buffers, one barrier per slab).  Per slab and half-iteration, in issue order:
+//   activation loads of slab b + 1 (registers) | weight loads of batch b + 1 (the other register buffer) |
+//   consume batch b against LDS buffer b & 1 | write slab b + 1 into LDS buffer (b + 1) & 1 | barrier
+// so the weight loads of the next batch are in flight while this one is consumed, and the wait of the LDS write is for
+// the older activation loads only.  No branch surrounds a load: groups past the end are clamped re-reads that are never
+// consumed, rows past N are clamped re-reads of row N - 1 whose sums are never stored.  The LDS image of a group keeps a
+// lane's operands 0 .. 3 at [l] and 4 .. 7 at [32 + l] (16 bytes each): both reads are conflict-free and the two
+// half-waves of a wave read the same addresses (broadcast).  The tail group (K % 256) is un-pipelined, its few activation
+// operands read from global memory as k_dense_mv reads them.  Launch plan: dense_set_plan.
+// 7B matrices in an 8-layer f16 file's set step, us per launch against k_dense_mm<WT, 8> (profiles/dense_set_probe.json): 2 rows
+// 19.0 / 9.5 / 38.8 / 20.7 / 55.1 against 48.0 / 29.9 / 61.4 / 68.2 / 95.5 (wq|wk|wv, wo, w1|w3, w2, lm head; k_dense_mv: 18.0 / 8.3 /
+// 37.6 / 20.2 / 52.2), 16 rows 43.0 / 31.6 / 71.8 / 63.3 / 93.0 against 57.9 / 40.0 / 105.2 / 85.0 / 144.1; a step of 16 sequences
+// 2.30 ms against 15.34 ms one sequence after the other.
+//   grid ceil(M / (8 * RGS)), block 256 threads
+template <int WT, int NR> struct DenseSetShape { static constexpr int UG = (WT == 1 && NR <= 4) ? 2 : 1; };
+template <int WT, int NR, int RGS>
+__global__ void __launch_bounds__(256)
+k_dense_set(const void *__restrict__ wv, int M, int K, const float *__restrict__ xp, int N,
+            float *__restrict__ y, long y_stride, const float *__restrict__ resid, long resid_stride) {
+    typedef typename WElem<WT>::T T;
+    constexpr int UG = DenseSetShape<WT, NR>::UG, HW = 8, NT = HW * 32;
+    constexpr int SLAB4 = UG * NR * 64;                    // 16-byte granules of one slab
+    constexpr int ST = (SLAB4 + NT - 1) / NT;              // ... staged per thread
+    __shared__ df4 xs[2][SLAB4];
+    const T *w = (const T *) wv;
+    const int tid = threadIdx.x, l = tid & 31, hw = tid >> 5;
+    const int m0 = (blockIdx.x * HW + hw) * RGS;
+    const T *wr[RGS];
+#pragma unroll
+    for (int r = 0; r < RGS; r++) wr[r] = w + (size_t) min(m0 + r, M - 1) * K;
+    float acc[RGS][NR];
+#pragma unroll
+    for (int r = 0; r < RGS; r++)
+#pragma unroll
+        for (int n = 0; n < NR; n++) acc[r][n] = 0.0f;
+    const int ng = K >> 8;
+    WVec8<WT> wq[2][UG][RGS];
+    df4 xst[ST];
+    // granule j of this thread: slab index i = tid + j * NT = (v * NR + n) * 64 + q -- group v of the slab, row n, granule q of the
+    // group's 64 (elements 4 q .. 4 q + 3: operands 4 (q & 1) .. of lane q >> 1)
+    const float *xsrc[ST];
+    int xv[ST], xdst[ST];
+#pragma unroll
+    for (int j = 0; j < ST; j++) {
+        const int i = min(tid + j * NT, SLAB4 - 1);
+        const int q = i & 63, vn = i >> 6, v = vn / NR, n = vn - v * NR;
+        xsrc[j] = xp + (size_t) min(n, N - 1) * K + q * 4;
+        xv[j] = v;
+        xdst[j] = vn * 64 + (q & 1) * 32 + (q >> 1);
+    }
+#define LD_LOADX(G0)                                                                               \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < ST; j++) xst[j] = *(const df4 *) (xsrc[j] + (size_t) min((G0) + xv[j], ng - 1) * 256);
+#define LD_STOREX(LB)                                                                              \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < ST; j++) if (tid + j * NT < SLAB4) xs[LB][xdst[j]] = xst[j];
+#define LD_LOADB(B, G0)                                                                            \
+    _Pragma("unroll")                                                                              \
+    for (int v = 0; v < UG; v++) {                                                                 \
+        const size_t at = (size_t) min((G0) + v, ng - 1) * 256 + l * 8;                            \
+        _Pragma("unroll")                                                                          \
+        for (int r = 0; r < RGS; r++) wq[B][v][r].load(wr[r] + at);                                 \
+    }
+#define LD_CONSUMEB(B, LB, G0)                                                                     \
+    _Pragma("unroll")                                                                              \
+    for (int v = 0; v < UG; v++) {                                                                 \
+        if ((G0) + v < ng) {                                                                       \
+            _Pragma("unroll")                                                                      \
+            for (int n = 0; n < NR; n++) {                                                         \
+                const df4 xa = xs[LB][(v * NR + n) * 64 + l], xb = xs[LB][(v * NR + n) * 64 + 32 + l]; \
+                _Pragma("unroll")                                                                  \
+                for (int u = 0; u < 8; u++)                                                        \
+                    _Pragma("unroll")                                                              \
+                    for (int r = 0; r < RGS; r++) wq[B][v][r].fma_into(acc[r][n], u, u < 4 ? xa[u & 3] : xb[u & 3]); \
+            }                                                                                      \
+        }                                                                                          \
+    }
+    if (ng) {
+        LD_LOADX(0)
+        LD_LOADB(0, 0)
+        LD_STOREX(0)
+        __syncthreads();
+        for (int g0 = 0; g0 < ng; g0 += 2 * UG) {
+            LD_LOADX(g0 + UG)
+            LD_LOADB(1, g0 + UG)
+            __builtin_amdgcn_sched_barrier(0);             // the next batch goes out BEFORE the wait for this one
+            LD_CONSUMEB(0, 0, g0)
+            __builtin_amdgcn_sched_barrier(0);
+            LD_STOREX(1)
+            __syncthreads();
+            LD_LOADX(g0 + 2 * UG)
+            LD_LOADB(0, g0 + 2 * UG)
+            __builtin_amdgcn_sched_barrier(0);
+            LD_CONSUMEB(1, 1, g0 + UG)
+            __builtin_amdgcn_sched_barrier(0);
+            LD_STOREX(0)
+            __syncthreads();
+        }
+    }
+#undef LD_LOADX
+#undef LD_STOREX
+#undef LD_LOADB
+#undef LD_CONSUMEB
+    const int st = (K & 255) >> 5;                         // tail group: st < 8 steps
+    for (int u = 0; u < st; u++) {
+        const size_t at = (size_t) ng * 256 + l * st + u;
+        float wt[RGS];
+#pragma unroll
+        for (int r = 0; r < RGS; r++) wt[r] = WElem<WT>::widen(wr[r][at]);
+#pragma unroll
+        for (int n = 0; n < NR; n++) {
+            const float xa = xp[(size_t) min(n, N - 1) * K + at];
+#pragma unroll
+            for (int r = 0; r < RGS; r++) acc[r][n] = fmaf(wt[r], xa, acc[r][n]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < RGS; r++)
+#pragma unroll
+        for (int n = 0; n < NR; n++) {
+            float s = acc[r][n];
+            s += __shfl_xor(s, 8);
+            s += __shfl_xor(s, 16);
+            s += __shfl_xor(s, 4);
+            s += __shfl_xor(s, 1);
+            s += __shfl_xor(s, 2);
+            if (l == 0 && m0 + r < M && n < N) {
+                if (resid) s = s + resid[(size_t) n * resid_stride + m0 + r];
+                y[(size_t) n * y_stride + m0 + r] = s;
+            }
+        }
+}
+
 template <int WT>
 __global__ void k_embed_dense(const int32_t *__restrict__ tokens, const void *__restrict__ emb, float *__restrict__ x, int d) {
     typedef typename WElem<WT>::T T;
@@ -361,20 +503,91 @@ __global__ void k_embed_dense(const int32_t *__restrict__ tokens, const void *__
     for (int i = threadIdx.x; i < d; i += blockDim.x) x[(size_t) n * d + i] = WElem<WT>::widen(row[i]);
 }
 
+// a batched decode step's rows (SeqSet): row n = the token at *set->tok_in[n]; the step's first launch also gathers the rows'
+// positions into the descriptor (SeqSet::pos), as k_embed_set does
+template <int WT>
+__global__ void k_embed_dense_set(SeqSet *set, const void *__restrict__ emb, float *__restrict__ x, int d) {
+    typedef typename WElem<WT>::T T;
+    const int n = blockIdx.x;
+    if (threadIdx.x == 0) set->pos[n] = set->state[n][0];
+    const T *row = (const T *) emb + (size_t) *set->tok_in[n] * d;
+    for (int i = threadIdx.x; i < d; i += blockDim.x) x[(size_t) n * d + i] = WElem<WT>::widen(row[i]);
+}
+
+// k_rope_kv (prompt_attn.hip) for the rows of a set: row n is at position set->pos[n] of the cache at + set->kv_off[n]
+__global__ void k_rope_kv_set(const float *__restrict__ qkv, long qkv_stride, int d, int dh, const double *__restrict__ sincos_tab,
+                              float *__restrict__ qr, float *__restrict__ Kc, float *__restrict__ Vc, const SeqSet *__restrict__ set) {
+    const int n = blockIdx.x;
+    const int pos = set->pos[n];
+    float *Kn = Kc + set->kv_off[n], *Vn = Vc + set->kv_off[n];
+    const float *q = qkv + (size_t) n * qkv_stride, *k = q + d, *v = q + 2 * d;
+    const double *tab = sincos_tab + (size_t) pos * dh;
+    for (int i = threadIdx.x; i < d / 2; i += blockDim.x) {
+        const int e = 2 * i;
+        const int pr = (e % dh) >> 1;
+        const double cs = tab[2 * pr], sn = tab[2 * pr + 1];
+        {
+            const double x0 = (double) q[e], x1 = (double) q[e + 1];
+            qr[(size_t) n * d + e] = (float) (x0 * cs - x1 * sn);
+            qr[(size_t) n * d + e + 1] = (float) (x0 * sn + x1 * cs);
+        }
+        {
+            const double x0 = (double) k[e], x1 = (double) k[e + 1];
+            Kn[(size_t) pos * d + e] = (float) (x0 * cs - x1 * sn);
+            Kn[(size_t) pos * d + e + 1] = (float) (x0 * sn + x1 * cs);
+        }
+        Vn[(size_t) pos * d + e] = v[e];
+        Vn[(size_t) pos * d + e + 1] = v[e + 1];
+    }
+}
+
+template <int WT, int NR>
+hipError_t go_set(const DenseSetPlan &p, const DMat &w, int N, float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, float *scratch) {
+    if (p.rg == RG) hipLaunchKernelGGL((k_dense_set<WT, NR, RG>), dim3(p.grid), dim3(256), 0, st, w.w, w.M, w.K, scratch, N, y, y_stride, resid, resid_stride);
+    else            hipLaunchKernelGGL((k_dense_set<WT, NR, 2>), dim3(p.grid), dim3(256), 0, st, w.w, w.M, w.K, scratch, N, y, y_stride, resid, resid_stride);
+    return hipGetLastError();
+}
+template <int WT>
+hipError_t go_set_rows(const DenseSetPlan &p, const DMat &w, int N, float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, float *scratch) {
+    switch (p.nr) {
+    case 2:  return go_set<WT, 2>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 4:  return go_set<WT, 4>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 6:  return go_set<WT, 6>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 8:  return go_set<WT, 8>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 10: return go_set<WT, 10>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 12: return go_set<WT, 12>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 14: return go_set<WT, 14>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    case 16: return go_set<WT, 16>(p, w, N, y, y_stride, resid, resid_stride, st, scratch);
+    }
+    return hipErrorInvalidValue;
+}
+
 template <int WT, int NC>
 hipError_t go(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
-              const float *resid, long resid_stride, hipStream_t st, float *scratch) {
+              const float *resid, long resid_stride, hipStream_t st, float *scratch, int path) {
     if (x) hipLaunchKernelGGL(k_dense_perm_act<WT>, dim3(N), dim3(256), 0, st, x, x_stride, w.K, scratch);     // x == nullptr: scratch already holds the prepared rows
-    if (N == 1) {
+    if (path == DENSE_PATH_MV) {
         // small matrices: 4 half-waves per workgroup so that every CU gets one (a 4096-row matrix is 256 workgroups)
         const int nhw = (w.M + 8 * RG - 1) / (8 * RG) >= 512 ? 8 : 4;
         const dim3 g1((w.M + nhw * RG - 1) / (nhw * RG));
-        if (epi == EPI_RESID)
-            hipLaunchKernelGGL((k_dense_mv<WT, EPI_RESID>), g1, dim3(nhw * 32), 0, st, w.w, w.M, w.K, scratch, y, resid);
-        else
-            hipLaunchKernelGGL((k_dense_mv<WT, EPI_STORE>), g1, dim3(nhw * 32), 0, st, w.w, w.M, w.K, scratch, y, resid);
+        for (int n = 0; n < N; n++) {                      // (more than one row: forced, llamahip_op_mul_mat_dense -- one launch per row)
+            const float *xn = scratch + (size_t) n * w.K, *rn = resid ? resid + (size_t) n * resid_stride : nullptr;
+            float *yn = y + (size_t) n * y_stride;
+            if (epi == EPI_RESID)
+                hipLaunchKernelGGL((k_dense_mv<WT, EPI_RESID>), g1, dim3(nhw * 32), 0, st, w.w, w.M, w.K, xn, yn, rn);
+            else
+                hipLaunchKernelGGL((k_dense_mv<WT, EPI_STORE>), g1, dim3(nhw * 32), 0, st, w.w, w.M, w.K, xn, yn, rn);
+            g_dense_path_counts[DENSE_COUNT_MV]++;
+        }
         return hipGetLastError();
     }
+    if (path == DENSE_PATH_SET) {
+        const DenseSetPlan p = dense_set_plan(w.M, w.K, WT, N);
+        if (!p.nr || !dense_set_plan_has_kernel(p)) return hipErrorInvalidValue;
+        g_dense_path_counts[DENSE_COUNT_SET]++;
+        return go_set_rows<WT>(p, w, N, y, y_stride, epi == EPI_RESID ? resid : nullptr, resid_stride, st, scratch);
+    }
+    g_dense_path_counts[DENSE_COUNT_MM]++;
     const dim3 grid((w.M + 8 * RG - 1) / (8 * RG), (N + NC - 1) / NC);
     if (epi == EPI_RESID)
         hipLaunchKernelGGL((k_dense_mm<WT, NC, EPI_RESID>), grid, dim3(256), 0, st, w.w, w.M, w.K, scratch, N, y, y_stride, resid, resid_stride);
@@ -536,8 +749,39 @@ hipError_t launch_quantize_q41_offline(const void *src, int f16, uint8_t *dst, l
     return hipGetLastError();
 }
 
+long g_dense_path_counts[DENSE_COUNT_N] = { 0, 0, 0 };
+
+// The launch plan of k_dense_set, the one place that derives it: NR = the row count rounded up to the next compiled instance (even);
+// workgroups of 8 half-waves; RG = 4 weight rows per half-wave where that still gives every CU two workgroups, and 2 rows for the narrower
+// matrices -- at 7B wq|wk|wv, wo and w2: with 4 rows a 4096-row matrix is 512 waves on 1024 SIMDs, and from ~8 activation rows on the
+// launch is bound by FMA issue, not by the stream; a slab of UG groups per activation row, two LDS buffers of it.
+DenseSetPlan dense_set_plan(int M, int K, int wtype, int N) {
+    DenseSetPlan p = { 0, 0, 0, 0, 0, 0 };
+    if (M < 1 || K < 32 || K % 32 != 0 || (wtype != 0 && wtype != 1) || N < 1 || N > DENSE_SET_MAX_ROWS) return p;
+    p.nr = std::max(2, (N + 1) & ~1);
+    p.hw = 8;
+    p.rg = (M + 8 * RG - 1) / (8 * RG) >= 512 ? RG : 2;
+    p.grid = (M + p.hw * p.rg - 1) / (p.hw * p.rg);
+    p.slab = (wtype == 1 && p.nr <= 4) ? 2 : 1;
+    p.lds = 2 * p.slab * p.nr * 256 * 4;
+    return p;
+}
+bool dense_set_plan_has_kernel(const DenseSetPlan &p) {
+    return p.nr >= 2 && p.nr <= 16 && p.nr % 2 == 0 && p.hw == 8 && (p.rg == RG || p.rg == 2);      // go_set_rows / go_set
+}
+
+// AUTO for 2 .. 16 rows: k_dense_set for the row counts at which it was not slower than k_dense_mm<WT, 8> on any of the five 7B
+// matrices; LLAMAHIP_DENSE_MM=set / mm sends every such row count to one kernel (measurement, tests)
+static int dense_auto_path(int N) {
+    static const int env = [] { const char *e = getenv("LLAMAHIP_DENSE_MM"); return !e ? 0 : !strcmp(e, "set") ? DENSE_PATH_SET : !strcmp(e, "mm") ? DENSE_PATH_MM : 0; }();
+    if (N == 1) return DENSE_PATH_MV;
+    if (N > DENSE_SET_MAX_ROWS) return DENSE_PATH_MM;
+    if (env) return env;
+    return DENSE_PATH_SET;
+}
+
 hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
-                           const float *resid, long resid_stride, hipStream_t st, float *scratch) {
+                           const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken) {
     if (w.wtype == 3) {
         if (w.K % 32 != 0 || !scratch) return hipErrorInvalidValue;
         hipLaunchKernelGGL(k_q41_act, dim3(N), dim3(64), 0, st, x, x_stride, w.K, scratch);
@@ -549,10 +793,24 @@ hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride
         return hipGetLastError();
     }
     if (w.K % 32 != 0 || (w.wtype != 0 && w.wtype != 1) || !scratch) return hipErrorInvalidValue;
-    if (w.wtype == 1) return N == 1 ? go<1, 1>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch)
-                                    : go<1, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch);
-    return N == 1 ? go<0, 1>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch)
-                  : go<0, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch);
+    if (N < 1 || path < DENSE_PATH_AUTO || path > DENSE_PATH_SET || (path == DENSE_PATH_SET && N > DENSE_SET_MAX_ROWS)) return hipErrorInvalidValue;
+    const int run = path == DENSE_PATH_AUTO ? dense_auto_path(N) : path;
+    if (path_taken) *path_taken = run;
+    if (w.wtype == 1) return go<1, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch, run);
+    return go<0, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch, run);
+}
+
+hipError_t launch_embed_dense_set(SeqSet *set, int n, const void *emb, int wtype, float *x, int d, hipStream_t st) {
+    if (wtype == 1) hipLaunchKernelGGL(k_embed_dense_set<1>, dim3(n), dim3(256), 0, st, set, emb, x, d);
+    else if (wtype == 0) hipLaunchKernelGGL(k_embed_dense_set<0>, dim3(n), dim3(256), 0, st, set, emb, x, d);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+hipError_t launch_rope_kv_set(const float *qkv, long qkv_stride, int d, int dh, const double *tab, float *qr, float *Kc, float *Vc,
+                              const SeqSet *set, int N, hipStream_t st) {
+    hipLaunchKernelGGL(k_rope_kv_set, dim3(N), dim3(256), 0, st, qkv, qkv_stride, d, dh, tab, qr, Kc, Vc, set);
+    return hipGetLastError();
 }
 
 // norm / plain / SiLU*up -> rounded, permuted activation rows in `scratch` (then launch_dense_mm with x = nullptr).

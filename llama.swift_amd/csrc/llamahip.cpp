@@ -550,70 +550,6 @@ struct DumpSink {
     }
 };
 
-// f16 / f32 model files (SURVEY.md 8f N3): the same graph with dense mat-muls (dense.hip).  Un-fused:
-// norm -> fp32 activations -> dense mat-mul; RoPE, KV cache and attention are the Q4_0 path's kernels.
-int forward_dense(llamahip_model *m, int n_threads, int n_past, int N, const float *hidden_in, bool want_all,
-                  bool state_on_device, char *err, size_t err_cap) {
-    const HParams &hp = m->hp;
-    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
-    const int nth = std::max(1, std::min(n_threads, 64));
-    hipStream_t st = m->stream;
-    if (N == 1 && !state_on_device) {
-        // the decode attention kernels read the position from device memory; only st[0] is written here
-        // (st[1], the step counter of the greedy loop, belongs to k_argmax)
-        const int32_t pos = n_past;
-        HIP_TRY(hipMemcpyAsync(m->d_state, &pos, sizeof(pos), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
-    }
-    if (m->first_stage) {
-        HIP_TRY(launch_embed_dense(m->tok_src ? m->tok_src : m->d_tokens, m->tok_emb, hp.f16, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);     // .mm:558-561
-    } else {
-        HIP_TRY(hipMemcpyAsync(m->x, hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
-    }
-    float *y = m->dbg_y;                                  // fp32 activations of the next mat-mul: [N][max(d, F)]
-    // activation preparation + mat-mul.  f16 / f32 weights: one fused launch writes the rounded, permuted rows
-    // straight into the mat-mul's operand buffer; Q4_1: fp32 rows, expanded by the mat-mul itself.
-    auto prep_mm = [&](const DMat &w, int epi, int mode, const float *in0, const float *in1, long in_stride, long in1_stride,
-                       int K, int rows, float *out, long out_stride, const float *resid, long resid_stride) -> hipError_t {
-        if (dense_prep_applies(w.wtype, mode, K)) {
-            hipError_t e = launch_dense_prep(mode, w.wtype, in0, in1, in_stride, in1_stride, K, rows, m->tmp, m->T_silu, st);
-            if (e != hipSuccess) return e;
-            return launch_dense_mm(w, epi, nullptr, K, rows, out, out_stride, resid, resid_stride, st, m->tmp);
-        }
-        const float *src = in0;
-        long src_stride = in_stride;
-        if (mode != PREP_PLAIN) {
-            hipError_t e = launch_prep(mode, in0, in1, in_stride, in1_stride, K, rows, m->qa_A, m->qa_d, y, nullptr, m->T_silu, st);
-            if (e != hipSuccess) return e;
-            src = y; src_stride = K;
-        }
-        return launch_dense_mm(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
-    };
-    for (int il = m->l0; il < m->l1; il++) {
-        const Layer &L = m->layers[il - m->l0];
-        const size_t kv_at = ((size_t) m->cur_seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
-        float *Kl = m->Kc + kv_at, *Vl = m->Vc + kv_at;
-        HIP_TRY(prep_mm(L.dqkv, EPI_STORE, PREP_NORM, m->x, L.attention_norm, d, 0, d, N, m->qkv, 3L * d, nullptr, 0), LLAMAHIP_ERR_PREDICT);             // .mm:570-582
-        if (N == 1) {
-            // one row: the decode attention kernels of the Q4_0 path (position from device memory, fp32 output)
-            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, m->d_state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
-        } else {
-            HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);                             // .mm:586-611
-            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st), LLAMAHIP_ERR_PREDICT); // .mm:614-646
-        }
-        HIP_TRY(prep_mm(L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->x1, d, m->x, d), LLAMAHIP_ERR_PREDICT);                          // .mm:649-654
-        HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
-        HIP_TRY(prep_mm(L.dw2, EPI_RESID, PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, N, m->x, d, m->x1, d), LLAMAHIP_ERR_PREDICT);               // .mm:678-687
-    }
-    if (m->last_stage) {
-        if (want_all) {
-            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x, m->norm_w, d, 0, d, N, m->logits, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-        } else {
-            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-        }
-    }
-    return 0;
-}
-
 // The forward pass for N tokens at n_past on this handle's layers (.mm:510-735).
 //   hidden_in  : device fp32 [N][d] residual stream from the previous stage (nullptr on the first stage)
 //   want_all   : compute logits for every token (debug) instead of only the last (.mm:724-725)
@@ -634,6 +570,77 @@ struct StepIO {
     bool fold_pick = false;
     int32_t *pick_out = nullptr, *pick_next = nullptr;
 };
+
+// dense model files: activation preparation + mat-mul of `rows` rows.  f16 / f32 weights: one fused launch writes the rounded, permuted rows
+// straight into the mat-mul's operand buffer; Q4_1: fp32 rows, expanded by the mat-mul itself.
+static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int mode, const float *in0, const float *in1, long in_stride, long in1_stride,
+                                int K, int rows, float *out, long out_stride, const float *resid, long resid_stride, hipStream_t st) {
+    if (dense_prep_applies(w.wtype, mode, K)) {
+        hipError_t e = launch_dense_prep(mode, w.wtype, in0, in1, in_stride, in1_stride, K, rows, m->tmp, m->T_silu, st);
+        if (e != hipSuccess) return e;
+        return launch_dense_mm(w, epi, nullptr, K, rows, out, out_stride, resid, resid_stride, st, m->tmp);
+    }
+    const float *src = in0;
+    long src_stride = in_stride;
+    if (mode != PREP_PLAIN) {
+        hipError_t e = launch_prep(mode, in0, in1, in_stride, in1_stride, K, rows, m->qa_A, m->qa_d, m->dbg_y, nullptr, m->T_silu, st);      // fp32 activations of the mat-mul: [rows][max(d, F)]
+        if (e != hipSuccess) return e;
+        src = m->dbg_y; src_stride = K;
+    }
+    return launch_dense_mm(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
+}
+
+// f16 / f32 model files (SURVEY.md 8f N3): the same graph with dense mat-muls (dense.hip).  Un-fused:
+// norm -> fp32 activations -> dense mat-mul; RoPE, KV cache and attention are the Q4_0 path's kernels.
+// (io, single-row steps: the token word and the {position, step} words of a stage step -- llamahip_stage_step on a whole-model handle)
+int forward_dense(llamahip_model *m, int n_threads, int n_past, int N, const float *hidden_in, bool want_all,
+                  bool state_on_device, char *err, size_t err_cap, const StepIO *io = nullptr) {
+    const HParams &hp = m->hp;
+    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
+    const int nth = std::max(1, std::min(n_threads, 64));
+    hipStream_t st = m->stream;
+    if (N == 1 && !state_on_device) {
+        // the decode attention kernels read the position from device memory; only st[0] is written here
+        // (st[1], the step counter of the greedy loop, belongs to k_argmax)
+        const int32_t pos = n_past;
+        HIP_TRY(hipMemcpyAsync(m->d_state, &pos, sizeof(pos), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
+    }
+    if (m->first_stage) {
+        HIP_TRY(launch_embed_dense((io && io->token) ? io->token : m->tok_src ? m->tok_src : m->d_tokens, m->tok_emb, hp.f16, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);     // .mm:558-561
+    } else {
+        HIP_TRY(hipMemcpyAsync(m->x, hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
+    }
+    int32_t *state = (io && io->state) ? io->state : m->d_state;
+    auto prep_mm = [&](const DMat &w, int epi, int mode, const float *in0, const float *in1, long in_stride, long in1_stride,
+                       int K, int rows, float *out, long out_stride, const float *resid, long resid_stride) -> hipError_t {
+        return dense_prep_mm(m, w, epi, mode, in0, in1, in_stride, in1_stride, K, rows, out, out_stride, resid, resid_stride, st);
+    };
+    for (int il = m->l0; il < m->l1; il++) {
+        const Layer &L = m->layers[il - m->l0];
+        const size_t kv_at = ((size_t) m->cur_seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
+        float *Kl = m->Kc + kv_at, *Vl = m->Vc + kv_at;
+        HIP_TRY(prep_mm(L.dqkv, EPI_STORE, PREP_NORM, m->x, L.attention_norm, d, 0, d, N, m->qkv, 3L * d, nullptr, 0), LLAMAHIP_ERR_PREDICT);             // .mm:570-582
+        if (N == 1) {
+            // one row: the decode attention kernels of the Q4_0 path (position from device memory, fp32 output)
+            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
+        } else {
+            HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);                             // .mm:586-611
+            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st), LLAMAHIP_ERR_PREDICT); // .mm:614-646
+        }
+        HIP_TRY(prep_mm(L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->x1, d, m->x, d), LLAMAHIP_ERR_PREDICT);                          // .mm:649-654
+        HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
+        HIP_TRY(prep_mm(L.dw2, EPI_RESID, PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, N, m->x, d, m->x1, d), LLAMAHIP_ERR_PREDICT);               // .mm:678-687
+    }
+    if (m->last_stage) {
+        if (want_all) {
+            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x, m->norm_w, d, 0, d, N, m->logits, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
+        } else {
+            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
+        }
+    }
+    return 0;
+}
+
 // The decode attention schedule by position (a host-side fact at every entry point: n_past, or the slot's next position; graphs are
 // captured per schedule):
 //   0  wq|wk|wv + attention in one launch (k_qkv_attn)                                        short contexts
@@ -660,7 +667,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
     const bool debug = dump_layer >= 0 && sink;
     if (m->dense) {
         if (debug) { set_err(err, err_cap, "per-layer dumps are available for Q4_0 models only"); return LLAMAHIP_ERR_PREDICT; }
-        return forward_dense(m, n_threads, n_past, N, hidden_in, want_all, state_on_device && N == 1, err, err_cap);
+        return forward_dense(m, n_threads, n_past, N, hidden_in, want_all, state_on_device && N == 1, err, err_cap, N == 1 ? io : nullptr);
     }
     const bool fused = (N == 1) && !debug && !(m->flags & LLAMAHIP_FLAG_UNFUSED);
     const bool fast_prefill = (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) != 0 && !debug;      // opt-in re-associated prompt GEMM (llamahip.h)
@@ -1431,6 +1438,8 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
 }
 
 // ---- asynchronous pipeline-stage steps ---------------------------------------------------------
+// f16 / f32 files have stage steps (and set steps) on whole-model handles only; Q4_1 files have none
+static bool dense_stage_steps(const llamahip_model *m) { return m->dense && m->hp.f16 != 3 && m->first_stage && m->last_stage; }
 int llamahip_stage_bind(llamahip_model *m, int32_t seq, int32_t n_past,
                         void *token_in, const void *hidden_in, void *hidden_out, void *token_out,
                         char *err, size_t err_cap) {
@@ -1439,7 +1448,8 @@ int llamahip_stage_bind(llamahip_model *m, int32_t seq, int32_t n_past,
     if (m->host_only) { set_err(err, err_cap, "model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate"); return LLAMAHIP_ERR_PREDICT; }
     if (seq < 0 || seq >= m->n_seq) { set_err(err, err_cap, "sequence slot %d out of range [0, %d)", seq, m->n_seq); return LLAMAHIP_ERR_PREDICT; }
     if (n_past < 0 || n_past >= m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_tokens (1) > n_ctx (%d)", n_past, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
-    if ((m->flags & LLAMAHIP_FLAG_UNFUSED) || m->dense) { set_err(err, err_cap, "llamahip_stage_step needs the fused Q4_0 decode schedule (LLAMAHIP_FLAG_UNFUSED handle or f16 / f32 model): use llamahip_eval_stage"); return LLAMAHIP_ERR_PREDICT; }
+    if ((m->flags & LLAMAHIP_FLAG_UNFUSED) || m->hp.f16 == 3) { set_err(err, err_cap, "llamahip_stage_step needs a captured decode step (LLAMAHIP_FLAG_UNFUSED handle or Q4_1 model): use llamahip_eval_stage"); return LLAMAHIP_ERR_PREDICT; }
+    if (m->dense && !(m->first_stage && m->last_stage)) { set_err(err, err_cap, "llamahip_stage_step on an f16 / f32 model needs a whole-model handle (this one holds layers [%d, %d)): use llamahip_eval_stage", m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
     if (m->first_stage && !token_in) { set_err(err, err_cap, "stage [%d,%d) is the first stage: token_in is required", m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
     {   // (a slot with device-side mailboxes needs no hidden_in / hidden_out buffers: llamahip_stage_mailbox / _connect)
         const bool has_slot = seq < (int32_t) m->slots.size();
@@ -1448,6 +1458,16 @@ int llamahip_stage_bind(llamahip_model *m, int32_t seq, int32_t n_past,
         if (!m->last_stage && !hidden_out && !mb_out) { set_err(err, err_cap, "stage [%d,%d) needs hidden_out", m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
     }
     HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    if (token_in) {
+        // the step's first kernel reads the token word on the device: an address the runtime does not know (a host variable, a stray integer)
+        // would fault the GPU at the first step instead of failing here
+        hipPointerAttribute_t pa;
+        if (hipPointerGetAttributes(&pa, token_in) != hipSuccess || pa.type == hipMemoryTypeUnregistered || !pa.devicePointer) {
+            (void) hipGetLastError();
+            set_err(err, err_cap, "llamahip_stage_bind: token_in %p is not device-accessible memory (stage steps read the token on the device; with tokens on the host use llamahip_eval_stage)", token_in);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
     int rc = ensure_workspace(m, 1, err, err_cap);
     if (rc) return rc;
     if (!m->d_slot_state) {
@@ -1652,7 +1672,35 @@ namespace {
 // position in RoPE / the KV append / the causal range, its own cache, and the V*P key split of ITS eval, n_past_b + 1 keys over
 // n_threads (ggml.c:5459-5480).  The weights are streamed once per step for all rows.
 // (tail = false, a verify step over a set: the rows stay where they are -- logits on the last stage, m->x on the others -- and no slot advances)
+// f16 / f32 files: the same step on the dense schedule of forward_dense -- per mat-mul k_dense_prep + the few-row dense mat-mul (one pass over
+// the weights for all rows: launch_dense_mm), RoPE and the KV append per row of the set (k_rope_kv_set), launch_attn_short with fp32 merged rows
+static int forward_dense_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys, bool tail) {
+    const HParams &hp = m->hp;
+    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
+    hipStream_t st = m->stream;
+    if (m->first_stage) HIP_TRY(launch_embed_dense_set(d_set, B, m->tok_emb, hp.f16, m->x, d, st), LLAMAHIP_ERR_PREDICT);                          // .mm:558-561
+    else HIP_TRY(launch_rows_set(d_set, B, m->x, d, true, st), LLAMAHIP_ERR_PREDICT);
+    for (int il = m->l0; il < m->l1; il++) {
+        const Layer &L = m->layers[il - m->l0];
+        float *Kl = m->Kc + (size_t) (il - m->l0) * C * d, *Vl = m->Vc + (size_t) (il - m->l0) * C * d;      // slot 0's cache of this layer; rows add their slot's offset
+        HIP_TRY(dense_prep_mm(m, L.dqkv, EPI_STORE, PREP_NORM, m->x, L.attention_norm, d, 0, d, B, m->qkv, 3L * d, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);        // .mm:570-582
+        HIP_TRY(launch_rope_kv_set(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, d_set, B, st), LLAMAHIP_ERR_PREDICT);                           // .mm:586-611
+        HIP_TRY(launch_attn_short(m->qr, Kl, Vl, m->set_sc, m->merged, m->qa_A, m->qa_d, 0, B, d, H, C, nth, m->T_exp, st, 0, d_set, set_keys), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
+        HIP_TRY(dense_prep_mm(m, L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, B, m->x1, d, m->x, d, st), LLAMAHIP_ERR_PREDICT);                     // .mm:649-654
+        HIP_TRY(dense_prep_mm(m, L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, B, m->gu, 2L * F, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);              // .mm:660-675
+        HIP_TRY(dense_prep_mm(m, L.dw2, EPI_RESID, PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, B, m->x, d, m->x1, d, st), LLAMAHIP_ERR_PREDICT);          // .mm:678-687
+    }
+    if (m->last_stage) {
+        HIP_TRY(dense_prep_mm(m, m->doutput, EPI_STORE, PREP_NORM, m->x, m->norm_w, d, 0, d, B, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);             // .mm:695-705
+        if (tail) HIP_TRY(launch_argmax_set(m->logits, V, d_set, B, st), LLAMAHIP_ERR_PREDICT);
+    } else if (tail) {
+        HIP_TRY(launch_rows_set(d_set, B, m->x, d, false, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_advance_set(d_set, B, st), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
 static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys = 0, bool tail = true) {
+    if (m->dense) return forward_dense_set(m, nth, d_set, B, err, err_cap, set_keys, tail);
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
     hipStream_t st = m->stream;
@@ -1700,7 +1748,8 @@ int32_t llamahip_stage_set_applies(const llamahip_model *m, int32_t n_seqs, int3
     if (n_seqs == 1) return 1;
     const int d = m->hp.n_embd, H = m->hp.n_head, dh = H > 0 ? d / H : 0;
     const int nth = std::max(1, std::min(n_threads, 64));
-    if (m->dense || (m->flags & LLAMAHIP_FLAG_UNFUSED) || m->l1 <= m->l0 || dh <= 0 || dh % 32 != 0 || dh > 256 || nth > 32) return 0;
+    if ((m->flags & LLAMAHIP_FLAG_UNFUSED) || m->l1 <= m->l0 || dh <= 0 || dh % 32 != 0 || dh > 256 || nth > 32) return 0;
+    if (m->dense) return dense_stage_steps(m) ? 1 : 0;      // (f16 / f32 whole-model handles: the few-row dense mat-mul takes every width the loader takes)
     return gemm_rope_kv_applies(m->layers[0].qkv, n_seqs, d) ? 1 : 0;
 }
 
@@ -1720,8 +1769,9 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
         if (sl.next_pos >= C) { set_err(err, err_cap, "context overflow: n_past (%d) + n_tokens (1) > n_ctx (%d)", sl.next_pos, C); return LLAMAHIP_ERR_PREDICT; }
         if ((!m->first_stage && !sl.hidden_in) || (!m->last_stage && !sl.hidden_out)) { set_err(err, err_cap, "slot %d runs on its mailboxes: set steps need slots bound with hidden_in / hidden_out buffers", sq); return LLAMAHIP_ERR_PREDICT; }
     }
-    if (m->dense || (m->flags & LLAMAHIP_FLAG_UNFUSED) || m->l1 <= m->l0 || dh % 32 != 0 || dh > 256 || nth > 32 || !gemm_rope_kv_applies(m->layers[0].qkv, n_seqs, d)) {
-        set_err(err, err_cap, "llamahip_stage_step_set needs a Q4_0 handle with layers, a head size that is a multiple of 32 (<= 256) and n_threads <= 32: step the slots one by one");
+    if ((m->dense && !dense_stage_steps(m)) || (m->flags & LLAMAHIP_FLAG_UNFUSED) || m->l1 <= m->l0 || dh % 32 != 0 || dh > 256 || nth > 32 ||
+        (!m->dense && !gemm_rope_kv_applies(m->layers[0].qkv, n_seqs, d))) {
+        set_err(err, err_cap, "llamahip_stage_step_set needs a Q4_0 handle with layers or an f16 / f32 whole-model handle, a head size that is a multiple of 32 (<= 256) and n_threads <= 32: step the slots one by one");
         return LLAMAHIP_ERR_PREDICT;
     }
     HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
@@ -2689,8 +2739,8 @@ static int decode_greedy_multi_impl(llamahip_model *m, int32_t n_threads, int32_
         if (rc) return rc;
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     }
-    if (first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
-        // no stage step to batch (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED): llamahip_decode_greedy on each slot in turn
+    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+        // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): llamahip_decode_greedy on each slot in turn
         const int save_seq = m->cur_seq;
         int rc = 0;
         for (int i = 0; i < n_seqs && rc == 0; i++) {
@@ -3199,8 +3249,8 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     }
     const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
-    if (first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
-        // no stage step to batch (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED): the single-sequence loop on each slot in turn
+    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+        // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): the single-sequence loop on each slot in turn
         const int save_seq = m->cur_seq;
         std::vector<float> logits(V);
         std::vector<int32_t> win;
@@ -3712,6 +3762,20 @@ int32_t llamahip_debug_gemv_plan(int32_t m, int32_t k, int32_t interleaved, int3
 int32_t llamahip_debug_gemm_paths(int64_t *out, int32_t cap) {
     for (int i = 0; out && i < cap && i < GEMM_PATH_COUNT; i++) out[i] = g_gemm_path_counts[i];
     return GEMM_PATH_COUNT;
+}
+
+int32_t llamahip_debug_dense_paths(int64_t *out, int32_t cap) {
+    for (int i = 0; out && i < cap && i < DENSE_COUNT_N; i++) out[i] = g_dense_path_counts[i];
+    return DENSE_COUNT_N;
+}
+
+int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
+    if (!out) return 0;
+    const DenseSetPlan p = dense_set_plan(m, k, wtype, n_rows);
+    if (!p.nr) return 0;
+    const int64_t o[6] = { p.grid, p.hw * 32, p.rg, p.nr, p.slab, p.lds };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return dense_set_plan_has_kernel(p) ? 1 : -1;
 }
 
 int llamahip_get_stats(const llamahip_model *m, llamahip_stats *out) {

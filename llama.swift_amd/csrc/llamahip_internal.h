@@ -70,9 +70,22 @@ struct DMat {
     size_t bytes() const { return wtype == 3 ? (size_t) ((M + 63) / 64) * 64 * (K / 32) * 8 : (size_t) M * K * (wtype == 1 ? 2 : 4); }
     size_t bytes2() const { return wtype == 3 ? (size_t) ((M + 63) / 64) * 64 * (K / 32) * 16 : 0; }
 };
+// The f16 / f32 mat-mul kernels (dense.hip), = LLAMAHIP_DENSE_* of llamahip.h: k_dense_mv (one row; forced with more rows: one launch per row),
+// k_dense_mm (any row count, the rows on gridDim.y: the weights are streamed once per 8 rows), k_dense_set (1 .. 16 rows, the weights streamed
+// once).  AUTO: one row MV, 2 .. 16 rows by dense_auto_path (dense.hip), more MM.  Q4_1 has one kernel and ignores the path.
+enum { DENSE_PATH_AUTO = 0, DENSE_PATH_MV = 1, DENSE_PATH_MM = 2, DENSE_PATH_SET = 3 };
+enum { DENSE_COUNT_MV = 0, DENSE_COUNT_MM = 1, DENSE_COUNT_SET = 2, DENSE_COUNT_N = 3 };
+extern long g_dense_path_counts[DENSE_COUNT_N];      // launches per kernel (process-wide; tests)
+constexpr int DENSE_SET_MAX_ROWS = 16;
+// k_dense_set's launch plan: nr = the compiled row count the launch runs (0: the kernel does not take the shape), hw half-waves per workgroup
+// of rg weight rows each, grid, slab = groups of 256 elements per activation row and LDS buffer, lds = static LDS bytes
+struct DenseSetPlan { int nr, hw, rg, grid, slab, lds; };
+DenseSetPlan dense_set_plan(int M, int K, int wtype, int N);
+bool dense_set_plan_has_kernel(const DenseSetPlan &p);
 // scratch: N * K floats (the permuted / rounded activation operand; Q4_1: the expanded one)
 hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
-                           const float *resid, long resid_stride, hipStream_t st, float *scratch = nullptr);
+                           const float *resid, long resid_stride, hipStream_t st, float *scratch = nullptr,
+                           int path = DENSE_PATH_AUTO, int *path_taken = nullptr);
 hipError_t launch_q41_repack(const uint8_t *raw_rows, DMat &w, hipStream_t st);
 bool dense_prep_applies(int wtype, int mode, int K);
 hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride,
@@ -80,6 +93,10 @@ hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float 
 hipError_t launch_dense_perm_rows(const void *raw_rows, DMat &w, int row0, int rows, hipStream_t st);
 hipError_t launch_quantize_q41_offline(const void *src, int f16, uint8_t *dst, long nrows, int nb, hipStream_t st);
 hipError_t launch_embed_dense(const int32_t *tokens, const void *emb, int wtype, float *x, int d, int N, hipStream_t st);
+// a batched decode step on an f16 / f32 file: the rows' embedding (+ SeqSet::pos, the step's first launch) and k_rope_kv per row of the set
+hipError_t launch_embed_dense_set(SeqSet *set, int n, const void *emb, int wtype, float *x, int d, hipStream_t st);
+hipError_t launch_rope_kv_set(const float *qkv, long qkv_stride, int d, int dh, const double *tab, float *qr, float *Kc, float *Vc,
+                              const SeqSet *set, int N, hipStream_t st);
 
 hipError_t init_kernel_attrs();
 size_t prep_lds_bytes(int K);                                       // dynamic LDS of the LDS-staged activation preparation (prep.hip)

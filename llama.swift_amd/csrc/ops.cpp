@@ -96,6 +96,40 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
     return LLAMAHIP_OK;
 }
 
+static_assert(LLAMAHIP_DENSE_AUTO == DENSE_PATH_AUTO && LLAMAHIP_DENSE_MV == DENSE_PATH_MV && LLAMAHIP_DENSE_MM == DENSE_PATH_MM && LLAMAHIP_DENSE_SET == DENSE_PATH_SET, "llamahip.h mirrors the dense mat-mul paths");
+
+// one f16 / f32 mat-mul kernel on caller-supplied operands (per-op tests of every kernel launch_dense_mm can pick): see llamahip.h
+int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                              float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_mul_mat_dense";
+    if (wtype != 0 && wtype != 1) { set_err(err, err_cap, "%s: wtype %d: 0 (fp32) or 1 (fp16) weights", fn, wtype); return LLAMAHIP_ERR_PREDICT; }
+    if (K < 32 || K % 32 != 0) { set_err(err, err_cap, "%s: K %d must be a positive multiple of 32", fn, K); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_DENSE_AUTO || path > LLAMAHIP_DENSE_SET) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
+    if (N < 1) { set_err(err, err_cap, "%s: N %d must be >= 1", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    if (path == LLAMAHIP_DENSE_SET && N > DENSE_SET_MAX_ROWS) { set_err(err, err_cap, "%s: path SET takes N 1 .. %d rows (got %d)", fn, DENSE_SET_MAX_ROWS, N); return LLAMAHIP_ERR_PREDICT; }
+    if (y_stride < M) { set_err(err, err_cap, "%s: y_stride %d < M %d", fn, y_stride, M); return LLAMAHIP_ERR_PREDICT; }
+    if (!w || !x || !y || M < 1) { set_err(err, err_cap, "%s: bad arguments (w, x, y not NULL; M %d >= 1)", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    DMat dm;
+    dm.M = M; dm.K = K; dm.wtype = wtype;
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_raw = s.alloc(dm.bytes(), (const uint8_t *) w);
+    dm.w = s.alloc<uint8_t>(dm.bytes());
+    float *d_x = s.alloc((size_t) N * K, x);
+    float *d_y = s.alloc((size_t) N * y_stride, y);      // (the floats between M and y_stride keep the caller's bits)
+    float *d_r = resid ? s.alloc((size_t) N * M, resid) : nullptr;
+    float *d_ws = s.alloc<float>((size_t) N * K);
+    if (s.ok()) s.check(launch_dense_perm_rows(d_raw, dm, 0, M, st));
+    int taken = 0;
+    if (s.ok()) s.check(launch_dense_mm(dm, resid ? EPI_RESID : EPI_STORE, d_x, K, N, d_y, y_stride, d_r, M, st, d_ws, path, &taken));
+    s.download(y, d_y, (size_t) N * y_stride * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (path_taken) *path_taken = taken;
+    return LLAMAHIP_OK;
+}
+
 // one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
 int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
                           int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,

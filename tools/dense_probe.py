@@ -1,23 +1,70 @@
 #!/usr/bin/env python3
 """Decode / prompt rate of an f16 model file with LLaMA-7B layer shapes (4 layers, so that the numpy writer
-finishes in seconds): per-layer time extrapolates to the 32-layer model.  usage: dense_probe.py [n_layer]"""
-import os, sys, time
+finishes in seconds): per-layer time extrapolates to the 32-layer model.
+usage: dense_probe.py [n_layer]
+       dense_probe.py [n_layer] --multi [--json OUT] [--repeats R] [--seqs 1,2,4,8,16] [--only-multi]
+--multi (default 8 layers: 3.2 GB, larger than the Infinity Cache): ms per step and aggregate tokens/s of decode_greedy_multi for S sequences
+from position 256 for 64 steps, the 9-token eval, and the single-stream greedy loop; every figure is the wall time of a call that
+synchronises before it returns, after one untimed run of the same call (graph captures, first-touch allocations), R repeats each.
+LLAMAHIP_LIB / LLAMAHIP_DENSE_MM select the library / the mat-mul of 2 .. 16 rows as usual; the model file is kept for the next run."""
+import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np
 import synth
 import llama_swift_amd as L
-nl = int(sys.argv[1]) if len(sys.argv) > 1 else 4
+
+args = sys.argv[1:]
+multi = "--multi" in args
+opt = lambda k, d: args[args.index(k) + 1] if k in args else d
+nl = int(args[0]) if args and args[0].isdigit() else (8 if multi else 4)
 hp = synth.HParams(n_vocab=32000, n_embd=4096, n_mult=256, n_head=32, n_layer=nl)
-path = "/tmp/dense7b_f16.bin"
+path = f"/tmp/dense7b_f16_{nl}.bin" if multi else "/tmp/dense7b_f16.bin"
 rng = np.random.default_rng(1)
-t = {}
-for name, shape in synth.tensor_specs(hp):
-    t[name] = (1.0 + 0.1 * rng.standard_normal(shape, dtype=np.float32)) if len(shape) == 1 else (0.02 * rng.standard_normal(shape, dtype=np.float32))
-synth.write_model_unquantized(path, hp, t, 1)
-del t
+if not (multi and os.path.exists(path)):
+    t = {}
+    for name, shape in synth.tensor_specs(hp):
+        t[name] = (1.0 + 0.1 * rng.standard_normal(shape, dtype=np.float32)) if len(shape) == 1 else (0.02 * rng.standard_normal(shape, dtype=np.float32))
+    synth.write_model_unquantized(path, hp, t, 1)
+    del t
+prompt = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 255)]).astype(np.int32)
+
+if multi:
+    seqs = [int(s) for s in opt("--seqs", "1,2,4,8,16").split(",")]
+    R, STEPS, POS = int(opt("--repeats", "3")), 64, 256
+    m = L.Model(path, n_ctx=512, n_seq=max(seqs))
+    firsts = []
+    for s in range(max(seqs)):
+        m.set_seq(s)
+        firsts.append(int(np.argmax(m.eval(np.concatenate([prompt[:POS - s - 1], prompt[:s + 1]]), 0))))      # (a different context per slot)
+    m.set_seq(0)
+
+    def timed(fn):
+        fn()
+        out = []
+        for _ in range(R):
+            t0 = time.perf_counter(); fn(); out.append((time.perf_counter() - t0) * 1e3)
+        return out
+    res = {"library": os.path.basename(L.LIB_PATH), "dense_mm": os.environ.get("LLAMAHIP_DENSE_MM", ""), "n_layer": nl,
+           "file_gb": round(os.path.getsize(path) / 1e9, 2), "steps": STEPS, "from_position": POS, "multi": {}}
+    for S in seqs:
+        ms = timed(lambda: m.decode_greedy_multi(firsts[:S], [POS] * S, STEPS))
+        res["multi"][str(S)] = {"ms_per_step": [round(x / STEPS, 4) for x in ms], "tokens_per_s": [round(S * STEPS / (x / 1e3), 1) for x in ms]}
+        print(f"S {S:2d}: {min(ms) / STEPS:.3f} ms/step, {S * STEPS / (min(ms) / 1e3):.0f} tokens/s ({nl} layers)", flush=True)
+    if "--only-multi" not in args:                             # (a kernel trace of the set steps alone ends with them)
+        res["eval9_ms"] = [round(x, 4) for x in timed(lambda: m.eval(prompt[:9], 0))]
+        res["decode_greedy_ms_per_token"] = [round(x / STEPS, 4) for x in timed(lambda: m.decode_greedy(firsts[0], POS, STEPS))]
+        print(f"9-token eval {min(res['eval9_ms']):.3f} ms; single stream {min(res['decode_greedy_ms_per_token']):.3f} ms/token")
+    if hasattr(L, "dense_paths"):
+        res["dense_paths"] = L.dense_paths()
+    print(json.dumps(res))
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+    m.close()
+    sys.exit(0)
+
 t0 = time.perf_counter(); m = L.Model(path, n_ctx=512); print(f"loaded {os.path.getsize(path) / 1e9:.2f} GB in {time.perf_counter() - t0:.2f} s")
-prompt = np.concatenate([[1], rng.integers(3, 32000, 255)]).astype(np.int32)
 m.eval(prompt[:8], 0)
 t0 = time.perf_counter(); lg = m.eval(prompt, 0); dt = time.perf_counter() - t0
 print(f"prompt 256 tokens: {dt * 1e3:.1f} ms ({nl} layers) -> {256 / (dt * 32 / nl):.0f} tok/s at 32 layers")
