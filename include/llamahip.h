@@ -183,8 +183,9 @@ int32_t llamahip_sample_top_p_top_k(const llamahip_model *m, llamahip_sampler *s
  * top_k selection of utils.cpp:345-395.  With *exact == 1, cand_scores / cand_ids [0, min(top_k, n_vocab)) are the
  * reference's candidates after its partial_sort, and llamahip_sample_from_candidates finishes the draw (soft-max,
  * top-p cut, std::discrete_distribution on the sampler's mt19937: utils.cpp:397-428) -- same ids, same rng draws.
- * With *exact == 0 (two equal scores whose order only libstdc++'s partial_sort defines, a NaN, n_vocab > 32768 or
- * top_k > 64) logits_out holds the n_vocab logits and the caller uses llamahip_sample_top_p_top_k as before.
+ * With *exact == 0 (two equal scores whose order only libstdc++'s partial_sort defines, +0.0 and -0.0 being equal
+ * scores, a NaN, n_vocab > 32768 or top_k > 64) logits_out holds the n_vocab logits and the caller uses
+ * llamahip_sample_top_p_top_k as before.
  * cand_scores / cand_ids: room for 64 entries; logits_out: n_vocab floats. */
 int llamahip_eval_topk(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
                        const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty, int32_t top_k, double temp,

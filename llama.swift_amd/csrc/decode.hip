@@ -2324,6 +2324,10 @@ __device__ __forceinline__ void
 topk_select_row(int V, int k, unsigned long long *__restrict__ keys, unsigned long long *__restrict__ gmax, uint32_t *__restrict__ badw,
                 double *__restrict__ out_score, int32_t *__restrict__ out_id, int32_t *__restrict__ flags, bool force_host) {
     constexpr int NPT = 32, LCAP = 768;
+    // +0.0 and -0.0 have neighbouring keys (KEY_NZ + 1 == KEY_PZ) but the reference's `a.first > b.first` orders neither before the other:
+    // below they count as ONE value -- the threshold never separates them, the survivor list holds KEY_PZ for both (so the rank pass sees
+    // the pair as the equality it is) and a -0 among the k best gets its own bits back from keys[]
+    constexpr unsigned long long KEY_PZ = 0x8000000000000000ull, KEY_NZ = 0x7fffffffffffffffull;
     __shared__ unsigned long long list_key[LCAP];
     __shared__ int32_t list_id[LCAP];
     __shared__ uint32_t n_list, bad;
@@ -2346,7 +2350,7 @@ topk_select_row(int V, int k, unsigned long long *__restrict__ keys, unsigned lo
         if (r == k - 1) s_T = v;
     }
     __syncthreads();                                                           // everybody has read gmax / badw: clear them for the next call
-    const unsigned long long T = s_T;
+    const unsigned long long T = s_T == KEY_PZ ? KEY_NZ : s_T;
     if (tid < 64) gmax[tid] = 0ull;
     if (tid == 0) badw[0] = 0u;
     if (T == 0ull || force_host) {                     // a group without a real value (tiny vocabularies) -- host path
@@ -2368,7 +2372,7 @@ topk_select_row(int V, int k, unsigned long long *__restrict__ keys, unsigned lo
         for (int u = 0; u < NPT; u++) {
             if (key[u] >= T) {
                 const uint32_t at = base + (uint32_t) __popcll(pass[u] & lt);
-                if (at < (uint32_t) LCAP) { list_key[at] = key[u]; list_id[at] = tid + u * 1024; }
+                if (at < (uint32_t) LCAP) { list_key[at] = key[u] == KEY_NZ ? KEY_PZ : key[u]; list_id[at] = tid + u * 1024; }
             }
             base += (uint32_t) __popcll(pass[u]);
         }
@@ -2399,7 +2403,8 @@ topk_select_row(int V, int k, unsigned long long *__restrict__ keys, unsigned lo
         }
         if (rank <= k && dup) bad = 1u;                // an equality among the k best or between the k-th and its runner-up
         if (rank < k) {
-            const unsigned long long b = (mine >> 63) ? (mine & 0x7fffffffffffffffull) : ~mine;
+            const unsigned long long own = mine == KEY_PZ ? keys[my_id] : mine;       // (+0 or -0: the score's own sign)
+            const unsigned long long b = (own >> 63) ? (own & 0x7fffffffffffffffull) : ~own;
             out_score[rank] = __longlong_as_double((long long) b);
             out_id[rank] = my_id;
         }

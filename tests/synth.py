@@ -221,3 +221,29 @@ def synth_prompt(n: int, n_vocab: int, seed: int = 1) -> np.ndarray:
     ids = rng.integers(3, n_vocab, size=n, dtype=np.int32)
     ids[0] = 1
     return ids
+
+
+def tensor_offsets(path: str) -> dict[str, tuple[int, int, tuple[int, ...], int]]:
+    """Reader for the container `write_model` writes: name -> (byte offset of the data, byte length, shape as (rows, cols) or (n,), ftype).
+    Lets a test edit a tensor of a file in place (e.g. one written by tools/make_synth_model)."""
+    per32 = {0: 128, 1: 64, 2: 20, 3: 24}                  # bytes per 32 elements: f32, f16, Q4_0, Q4_1
+    out = {}
+    with open(path, "rb") as f:
+        magic, = struct.unpack("<I", f.read(4))
+        assert magic == MAGIC, hex(magic)
+        n_vocab = struct.unpack("<7i", f.read(28))[0]
+        for _ in range(n_vocab):
+            n, = struct.unpack("<I", f.read(4))
+            f.seek(n, 1)
+        while True:
+            head = f.read(12)
+            if len(head) < 12:
+                break
+            n_dims, n_name, ftype = struct.unpack("<3i", head)
+            ne = struct.unpack(f"<{n_dims}i", f.read(4 * n_dims))
+            name = f.read(n_name).decode()
+            n_el = int(np.prod(ne))
+            nbytes = n_el // 32 * per32[ftype] if n_el % 32 == 0 else n_el * per32[ftype] // 32
+            out[name] = (f.tell(), nbytes, tuple(reversed(ne)), ftype)
+            f.seek(nbytes, 1)
+    return out
