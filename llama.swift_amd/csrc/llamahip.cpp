@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <map>
 #include <memory>
 #include <random>
@@ -2280,6 +2281,39 @@ static int pipe_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_pa
 }
 
 // ------------------------------------------------------------------------------------------------
+// The drafted and the multi-sequence decoders, from here to llamahip_set_seq, are one family built on a few shared pieces, each described
+// once where it is defined:
+//   stages_of / first_of / last_of    a handle as its list of stages (a plain handle: the one stage)
+//   each_slot, drain_stages           the per-slot fall-back (a single-sequence function on each slot in turn); the wait that ends every
+//                                     stretch of enqueued stage work, on the error paths too
+//   SampleParams, sample_draw,        the sampler's parameters, one draw (candidates or logits, accept, exact flag) and the walk over
+//   sample_walk                       the rows of a verify step
+//   LookupRun                         a lookup run over n sequences: histories, drafting, segments, accounting
+//   group_cut, multi_begin,           the groups of a multi-sequence step, the slots' binding, and one group stepped through every
+//   step_group                        stage with its hand-offs
+// ------------------------------------------------------------------------------------------------
+static std::vector<llamahip_model *> stages_of(llamahip_model *m) { return m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages; }
+static llamahip_model *first_of(llamahip_model *m) { return m->stages.empty() ? m : m->stages[0]; }
+static llamahip_model *last_of(llamahip_model *m) { return m->stages.empty() ? m : m->stages.back(); }
+
+// the end of everything enqueued on the stages: every stage waited for (bounded: pipe_wait_stage), their fault words collected.  rc: what the
+// enqueuing returned -- an error reported there stays the call's error, and the stages are drained all the same
+static int drain_stages(const std::vector<llamahip_model *> &stages, int rc, char *err, size_t err_cap) {
+    const int rc_sync = pipe_sync_stages(stages, rc ? nullptr : err, rc ? 0 : err_cap);
+    return rc ? rc : rc_sync;
+}
+
+// fn(i) with slot slots[i] current (slots == nullptr: slot i), for i = 0 .. n - 1 until one fails; the handle's current slot is restored
+static int each_slot(llamahip_model *m, int32_t n, const int32_t *slots, char *err, size_t err_cap, const std::function<int(int)> &fn) {
+    const int save_seq = m->cur_seq;
+    int rc = 0;
+    for (int i = 0; i < n && rc == 0; i++)
+        if ((rc = llamahip_set_seq(m, slots ? slots[i] : i, err, err_cap)) == 0) rc = fn(i);
+    (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
 // Drafted greedy decoding: llamahip_verify_greedy / llamahip_decode_greedy_lookup.  A verify step is ONE eval of the rows
 // [last accepted token, draft ...] at n_past in which every row takes the V*P key split of its own single-token eval (chunk = 1, as
 // llamahip_eval_chunks) and the last stage's lm head runs over every row (as the scoring entry points); row j then holds the logits of
@@ -2348,13 +2382,19 @@ static int slide_enqueue(llamahip_model *last, const SlideReq &sl, int N, char *
     HIP_TRY(launch_topk_slide(last->logits, N, last->hp.n_vocab, ids, sl.n_last, sl.scale, sl.repeat_penalty, sl.k, out, last->stream, last->d_slide), LLAMAHIP_ERR_PREDICT);
     return 0;
 }
+// the N rows of candidates a sampled step (slide_enqueue, slide_set_enqueue) left, after the step was waited for; the last stage's device is current
+static int slide_fetch(llamahip_model *last, TopkOut *out, int N, char *err, size_t err_cap) {
+    if (last->h_io) memcpy(out, last->h_io->rows, (size_t) N * sizeof(TopkOut));
+    else HIP_TRY(hipMemcpy(out, last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES, (size_t) N * sizeof(TopkOut), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
 
 // one verify step of N = 2 .. 16 rows on a Q4_0 handle, plain or pipeline (eval_score's walk); res: {n_accept, picks[N]}
 // (sl != nullptr: the sampled step -- res and logits_next unused, sl->out receives the rows' candidates)
 static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *rows, int N, int restart_pos, int32_t *res,
                        float *logits_next, char *err, size_t err_cap, const SlideReq *sl = nullptr) {
     const double t0 = now_ms();
-    llamahip_model *last = m;
+    llamahip_model *last = last_of(m);
     int rc;
     if (m->stages.empty()) {
         if ((rc = eval_stage_enqueue(m, n_threads, n_past, rows, N, nullptr, 1, true, err, err_cap)) != 0) return rc;
@@ -2371,16 +2411,12 @@ static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, con
             if ((rc = eval_stage_enqueue(st, n_threads, n_past, rows, N, s ? st->pipe_in : nullptr, 1, s == S - 1, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
             if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         }
-        last = m->stages[S - 1];
         if ((rc = sl ? slide_enqueue(last, *sl, N, err, err_cap) : verify_enqueue(last, rows, N, restart_pos, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         if ((rc = pipe_sync(m, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     }
     if (sl) {
-        if (sl->k > 0) {
-            if (last->h_io) memcpy(sl->out, last->h_io->rows, (size_t) N * sizeof(TopkOut));
-            else HIP_TRY(hipMemcpy(sl->out, last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES, (size_t) N * sizeof(TopkOut), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
-        }
+        if (sl->k > 0 && (rc = slide_fetch(last, sl->out, N, err, err_cap)) != 0) return rc;
         m->n_evals++;
         m->t_eval_ms += now_ms() - t0;
         return LLAMAHIP_OK;
@@ -2395,7 +2431,7 @@ static int verify_step(llamahip_model *m, int32_t n_threads, int32_t n_past, con
     return LLAMAHIP_OK;
 }
 
-static bool lookup_dense(const llamahip_model *m) { return m->stages.empty() ? m->dense : m->stages[0]->dense; }
+static bool lookup_dense(llamahip_model *m) { return first_of(m)->dense; }
 
 // the arguments first (a HOST_ONLY handle knows n_vocab / n_ctx: the checks are the same without a device), then the handle
 static int check_verify_args(llamahip_model *m, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, const char *fn, char *err, size_t err_cap) {
@@ -2408,7 +2444,7 @@ static int check_verify_args(llamahip_model *m, int32_t n_past, int32_t token, c
     for (int i = 0; i < n_draft; i++)
         if (draft[i] < 0 || draft[i] >= V) { set_err(err, err_cap, "%s: draft token id %d at %d out of range [0, %d)", fn, draft[i], i, V); return LLAMAHIP_ERR_PREDICT; }
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+    return check_eval_args(first_of(m), n_past, &token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
 }
 
 static int verify_greedy_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, int restart_pos,
@@ -2427,7 +2463,7 @@ static int verify_greedy_impl(llamahip_model *m, int32_t n_threads, int32_t n_pa
         }
         for (int j = a + 1; j < N; j++) picks[j] = -1;
         *n_accept = a;
-        llamahip_model *last = m->stages.empty() ? m : m->stages.back();
+        llamahip_model *last = last_of(m);
         if (logits_next) {
             HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
             HIP_TRY(hipMemcpy(logits_next, last->logits, (size_t) m->hp.n_vocab * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
@@ -2477,8 +2513,98 @@ static int check_lookup_args(llamahip_model *m, const char *fn, int32_t n_past, 
     if (stats && stats->struct_size != (int32_t) sizeof(llamahip_lookup_stats)) { set_err(err, err_cap, "%s: stats->struct_size (%d) is not sizeof(llamahip_lookup_stats) (%d)", fn, stats->struct_size, (int) sizeof(llamahip_lookup_stats)); return LLAMAHIP_ERR_PREDICT; }
     if (!handle) return 0;
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+    return check_eval_args(first_of(m), n_past, &first_token, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
 }
+
+// the rows of a verify step over a set (vset_step, below), cut into segments: one per sequence, [its last token, its draft ...]
+struct VsetReq {
+    int n_segs = 0, n_rows = 0;
+    int32_t slot[SET_MAX], pos[SET_MAX];        // per segment: KV slot, position of its first row
+    int32_t seg_begin[SET_MAX + 1];
+    int32_t rows[SET_MAX];                      // the rows' tokens
+    bool bound = false;                         // the slots are bound (the loop): logs, {position, cursor} and next-token words are kept on the device
+};
+
+// A lookup run over n sequences (n = 1: the single-sequence loops): what the host knows of each sequence and what it does between two steps.
+// A round is: active() -> draft_round() -> one step of the caller's (a plain step, or a verify step over segments()) -> accept() per sequence.
+struct LookupRun {
+    const char *fn = nullptr;
+    int n = 0, n_steps = 0, K = 0, n_corpus = 0, ngram_min = 0, ngram_max = 0;
+    const int32_t *n_past = nullptr, *corpus = nullptr;
+    int32_t *out_tokens = nullptr, *out_exact = nullptr;    // the sampled loops: accept() writes sequence i's picks (and exact flags) at [i * n_steps + done[i], ..)
+    std::vector<size_t> coff;                               // sequence i's context: n_past[i] tokens at contexts + coff[i]
+    std::vector<std::vector<int32_t>> hist;                 // hist[i][0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
+    std::vector<int> done;
+    std::vector<llamahip_lookup_stats> ls;
+    int32_t want[SET_MAX], give[SET_MAX], draft[SET_MAX][VERIFY_ROWS_MAX];      // the round's drafts, by index into its active list
+
+    int pos(int i) const { return n_past[i] + done[i]; }
+    int32_t token(int i) const { return hist[i][(size_t) pos(i)]; }
+    // the context offsets (a negative n_past is refused here, in check_lookup_args' words, before that function is given a context pointer)
+    int open(const char *fn_, int n_ctx, int n_, const int32_t *n_past_, int n_steps_, char *err, size_t err_cap) {
+        fn = fn_; n = n_; n_past = n_past_; n_steps = n_steps_;
+        coff.assign((size_t) n + 1, 0);
+        for (int i = 0; i < n; i++) {
+            if (n_past[i] < 0) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+            coff[i + 1] = coff[i] + (size_t) n_past[i];
+        }
+        return 0;
+    }
+    void start(const int32_t *first_tokens, const int32_t *contexts, const int32_t *corpus_, int n_corpus_, int draft_len, int ngram_min_, int ngram_max_) {
+        corpus = corpus_; n_corpus = n_corpus_; ngram_min = ngram_min_; ngram_max = ngram_max_;
+        K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+        hist.resize(n);
+        done.assign(n, 0);
+        ls.assign(n, llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 });
+        for (int i = 0; i < n; i++) {
+            hist[i].resize((size_t) n_past[i] + n_steps + 1);
+            if (n_past[i] > 0) memcpy(hist[i].data(), contexts + coff[i], (size_t) n_past[i] * 4);
+            hist[i][n_past[i]] = first_tokens[i];
+        }
+    }
+    bool active(std::vector<int32_t> &act) const {
+        act.clear();
+        for (int i = 0; i < n; i++) if (done[i] < n_steps) act.push_back(i);
+        return !act.empty();
+    }
+    // what every active sequence that may draft wants (want, draft), then the spare rows of a 16-row step dealt among them (give); *dealt: their sum
+    int draft_round(const std::vector<int32_t> &act, const std::function<bool(int)> &may_draft, int *dealt, char *err, size_t err_cap) {
+        const int A = (int) act.size();
+        for (int a = 0; a < A; a++) {
+            const int i = act[a];
+            // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
+            const int room = may_draft(i) ? std::min(K, n_steps - done[i] - 1) : 0;
+            want[a] = room > 0 ? llamahip_lookup_draft(hist[i].data(), pos(i) + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft[a]) : 0;
+            if (want[a] < 0 || want[a] > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, want[a], room); return LLAMAHIP_ERR_PREDICT; }
+        }
+        *dealt = llamahip_lookup_deal_rows(want, A, SET_MAX, give);
+        if (*dealt < 0) { set_err(err, err_cap, "%s: dealing the rows of a step failed", fn); return LLAMAHIP_ERR_PREDICT; }
+        return 0;
+    }
+    // the verify step of the round: segment a = sequence act[a] in slot act[a], its last token and the give[a] draft tokens it was dealt
+    void segments(const std::vector<int32_t> &act, VsetReq &rq) const {
+        const int A = (int) act.size();
+        int R = 0;
+        for (int a = 0; a < A; a++) {
+            const int i = act[a];
+            rq.slot[a] = i; rq.pos[a] = pos(i); rq.seg_begin[a] = R;
+            rq.rows[R++] = token(i);
+            for (int j = 0; j < give[a]; j++) rq.rows[R++] = draft[a][j];
+        }
+        rq.seg_begin[A] = R; rq.n_segs = A; rq.n_rows = R;
+    }
+    // sequence i took n_picks tokens in a step that carried n_give draft tokens for it (0: a single step); mirror: the stages whose host-side
+    // slot position follows (a verify step over a set moves the slots' device words without the stage API)
+    void accept(int i, int n_give, const int32_t *picks, const int32_t *exact, int n_picks, const std::vector<llamahip_model *> *mirror = nullptr) {
+        memcpy(hist[i].data() + pos(i) + 1, picks, (size_t) n_picks * 4);
+        if (out_tokens) memcpy(out_tokens + (size_t) i * n_steps + done[i], picks, (size_t) n_picks * 4);
+        if (out_exact) memcpy(out_exact + (size_t) i * n_steps + done[i], exact, (size_t) n_picks * 4);
+        done[i] += n_picks;
+        if (n_give > 0) { ls[i].n_verify_steps++; ls[i].n_drafted += n_give; ls[i].n_accepted += n_picks - 1; }
+        else ls[i].n_single_steps++;
+        if (mirror) for (llamahip_model *st : *mirror) st->slots[i].next_pos += n_picks;
+    }
+};
 
 int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
                                   const int32_t *context, int32_t n_context, const int32_t *corpus, int32_t n_corpus,
@@ -2488,53 +2614,40 @@ int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t 
     int rc = check_lookup_args(m, fn, n_past, first_token, n_steps, context, n_context, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap);
     if (rc) return rc;
     const int V = m->hp.n_vocab;
-    llamahip_lookup_stats ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
     if (lookup_dense(m)) {
         // f16 / f32 / Q4_1 files: no multi-row eval with every row's own key split -- nothing is drafted
         if ((rc = llamahip_decode_greedy(m, n_threads, n_past, first_token, n_steps, out_tokens, logits_last, err, err_cap)) != 0) return rc;
-        ls.n_single_steps = n_steps;
-        if (stats) *stats = ls;
+        if (stats) *stats = llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, n_steps, 0, 0 };
         return LLAMAHIP_OK;
     }
-    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
-    llamahip_model *last = m->stages.empty() ? m : m->stages.back();
-    std::vector<int32_t> hist((size_t) n_past + n_steps + 1);
-    if (n_past > 0) memcpy(hist.data(), context, (size_t) n_past * 4);
-    hist[n_past] = first_token;                     // hist[0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
-    int done = 0;
-    while (done < n_steps) {
-        const int pos = n_past + done, restart = done == 0 ? n_past : -1;
-        int32_t draft[VERIFY_ROWS_MAX], res_n = 0, picks[VERIFY_ROWS_MAX];
-        // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
-        const int room = std::min(K, n_steps - done - 1);
-        const int nd = room > 0 ? llamahip_lookup_draft(hist.data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft) : 0;
-        if (nd < 0 || nd > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, nd, room); return LLAMAHIP_ERR_PREDICT; }
-        const bool fin_single = nd == 0 && done + 1 == n_steps;
+    llamahip_model *last = last_of(m);
+    LookupRun run;
+    if ((rc = run.open(fn, m->hp.n_ctx, 1, &n_past, n_steps, err, err_cap)) != 0) return rc;
+    run.start(&first_token, context, corpus, n_corpus, draft_len, ngram_min, ngram_max);
+    const std::vector<int32_t> act{ 0 };
+    while (run.done[0] < n_steps) {
+        const int done = run.done[0], pos = n_past + done, restart = done == 0 ? n_past : -1;
+        int nd = 0;
+        if ((rc = run.draft_round(act, [](int) { return true; }, &nd, err, err_cap)) != 0) return rc;
+        int32_t res[VERIFY_ROWS_MAX + 1] = { 0 };       // {n_accept, picks}
         if (nd == 0) {
             // nothing to verify: the fused single-token step, its pick appended to the device log behind it
-            if ((rc = llamahip_decode_greedy(m, n_threads, pos, hist[pos], 1, picks, fin_single ? logits_last : nullptr, err, err_cap)) != 0) return rc;
-            if ((rc = verify_append(last, picks[0], restart, err, err_cap)) != 0) return rc;
-            ls.n_single_steps++;
+            if ((rc = llamahip_decode_greedy(m, n_threads, pos, run.token(0), 1, res + 1, done + 1 == n_steps ? logits_last : nullptr, err, err_cap)) != 0) return rc;
+            if ((rc = verify_append(last, res[1], restart, err, err_cap)) != 0) return rc;
         } else {
-            int32_t rows[VERIFY_ROWS_MAX], res[VERIFY_ROWS_MAX + 1];
-            rows[0] = hist[pos];
-            memcpy(rows + 1, draft, (size_t) nd * 4);
-            const bool may_end = done + nd + 1 == n_steps;      // (all accepted: row nd is the call's last position)
-            if ((rc = verify_step(m, n_threads, pos, rows, nd + 1, restart, res, nullptr, err, err_cap)) != 0) return rc;
-            res_n = res[0];
-            memcpy(picks, res + 1, (size_t) (nd + 1) * 4);
-            if (may_end && res_n == nd && logits_last) {
+            VsetReq rq;                                  // (one segment: its rows are the step's)
+            run.segments(act, rq);
+            if ((rc = verify_step(m, n_threads, pos, rq.rows, nd + 1, restart, res, nullptr, err, err_cap)) != 0) return rc;
+            if (done + nd + 1 == n_steps && res[0] == nd && logits_last) {      // (all accepted: row nd is the call's last position)
                 HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
                 HIP_TRY(hipMemcpy(logits_last, last->logits + (size_t) nd * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
             }
-            ls.n_verify_steps++;
-            ls.n_drafted += nd;
-            ls.n_accepted += res_n;
         }
-        for (int j = 0; j <= res_n; j++) hist[pos + 1 + j] = picks[j];
-        done += res_n + 1;
+        run.accept(0, nd, res + 1, nullptr, res[0] + 1);
     }
     // the result is the device's log, checked against what the host saw step by step
+    const std::vector<int32_t> &hist = run.hist[0];
+    const int done = run.done[0];
     std::vector<int32_t> h(64 + (size_t) n_steps);
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     HIP_TRY(hipStreamSynchronize(last->stream), LLAMAHIP_ERR_PREDICT);
@@ -2544,7 +2657,7 @@ int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t 
         return LLAMAHIP_ERR_PREDICT;
     }
     memcpy(out_tokens, h.data() + 64, (size_t) n_steps * 4);
-    if (stats) *stats = ls;
+    if (stats) *stats = run.ls[0];
     return LLAMAHIP_OK;
 }
 
@@ -2564,32 +2677,62 @@ static int check_sampler_params(const char *fn, const llamahip_sampler *sampler,
     if (top_p != top_p) { set_err(err, err_cap, "%s: top_p is NaN", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
 }
-// handles whose verify step is a loop of single steps: f16 / f32 / Q4_1 files (no per-row key split in one pass) and LLAMAHIP_FLAG_UNFUSED
-static bool sample_lookup_by_rows(const llamahip_model *m) {
-    const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
-    return first->dense || (first->flags & LLAMAHIP_FLAG_UNFUSED) != 0;
-}
-// the documented single step: llamahip_eval_topk -> draw -> accept; *exact as llamahip_eval_topk reports it
-static int sample_single_step(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, llamahip_sampler *sampler, double repeat_penalty, int32_t top_k,
-                              double top_p, double temp, std::vector<int32_t> &win, std::vector<float> &logits, int32_t *pick, int32_t *exact, char *err, size_t err_cap) {
+// the sampling parameters of a call and what every sampled entry point derives from them.  dev_sel: the device can make a row's candidates
+// (not with top_k > 64 or n_vocab > 32768; a window of more than 1024 ids rules it out for that sampler's rows only, checked where the window is known)
+struct SampleParams { double repeat_penalty; int32_t top_k; double top_p, temp; int k; double scale; bool dev_sel; };
+static SampleParams sample_params(const llamahip_model *m, double repeat_penalty, int32_t top_k, double top_p, double temp) {
     const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    return { repeat_penalty, top_k, top_p, temp, k, 1.0 / temp, V <= 32768 && k <= 64 };
+}
+// one draw: from the row's candidates where the device made them exactly (ex), else by the whole sampler on the row's logits; accepted at once
+static int32_t sample_draw(llamahip_model *m, llamahip_sampler *sampler, const SampleParams &sp, bool ex, const double *sc, const int32_t *ids, const float *logits, int32_t *exact) {
+    const int32_t tok = ex ? llamahip_sample_from_candidates(sampler, sc, ids, sp.k, sp.top_p)
+                           : llamahip_sample_top_p_top_k(m, sampler, logits, sp.repeat_penalty, sp.top_k, sp.top_p, sp.temp);
+    llamahip_sampler_accept(sampler, tok);
+    if (exact) *exact = ex ? 1 : 0;
+    return tok;
+}
+// handles whose verify step is a loop of single steps: f16 / f32 / Q4_1 files (no per-row key split in one pass) and LLAMAHIP_FLAG_UNFUSED
+static bool sample_lookup_by_rows(llamahip_model *m) { return first_of(m)->dense || (first_of(m)->flags & LLAMAHIP_FLAG_UNFUSED) != 0; }
+// the documented single step: llamahip_eval_topk -> draw -> accept; *exact as llamahip_eval_topk reports it
+static int sample_single_step(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, llamahip_sampler *sampler, const SampleParams &sp,
+                              std::vector<int32_t> &win, std::vector<float> &logits, int32_t *pick, int32_t *exact, char *err, size_t err_cap) {
     win.resize((size_t) std::max(llamahip_sampler_window(sampler, nullptr, 0), 1));
     const int32_t nw = std::min(llamahip_sampler_window(sampler, win.data(), (int32_t) win.size()), (int32_t) win.size());
-    logits.resize((size_t) V);
+    logits.resize((size_t) m->hp.n_vocab);
     double sc[64];
     int32_t ids[64], ex = 0;
-    int rc = llamahip_eval_topk(m, n_threads, n_past, &token, 1, win.data(), nw, repeat_penalty, top_k, temp, sc, ids, &ex, logits.data(), err, err_cap);
+    int rc = llamahip_eval_topk(m, n_threads, n_past, &token, 1, win.data(), nw, sp.repeat_penalty, sp.top_k, sp.temp, sc, ids, &ex, logits.data(), err, err_cap);
     if (rc) return rc;
-    *pick = ex == 1 ? llamahip_sample_from_candidates(sampler, sc, ids, k, top_p) : llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
-    llamahip_sampler_accept(sampler, *pick);
-    *exact = ex == 1 ? 1 : 0;
+    *pick = sample_draw(m, sampler, sp, ex == 1, sc, ids, logits.data(), exact);
+    return 0;
+}
+// the walk behind a sampled verify step: the draft's rows are rows r0 .. r0 + n_draft of the step (out, last->logits); row 0, then row j + 1 only if
+// row j's draw was draft[j].  sel: the device made candidates for these rows.  picks / exact: the rows reached (the caller set the rest to -1)
+static int sample_walk(llamahip_model *m, llamahip_model *last, int r0, const int32_t *draft, int n_draft, llamahip_sampler *sampler, bool sel, const TopkOut *out,
+                       const SampleParams &sp, int32_t *n_accept, int32_t *picks, int32_t *exact, std::vector<float> &logits, char *err, size_t err_cap) {
+    const size_t V = m->hp.n_vocab;
+    int a = 0;
+    for (;; a++) {
+        const TopkOut &c = out[r0 + a];
+        const bool ex = sel && c.fl[0] == 1;
+        if (!ex) {
+            // (the rows stay on the device until the next eval: a row the walk reaches and finds inexact is fetched now, that row only)
+            logits.resize(V);
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(logits.data(), last->logits + (size_t) (r0 + a) * V, V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        }
+        picks[a] = sample_draw(m, sampler, sp, ex, c.sc, c.id, logits.data(), exact ? &exact[a] : nullptr);
+        if (a == n_draft || picks[a] != draft[a]) break;
+    }
+    *n_accept = a;
     return 0;
 }
 
 static int verify_sample_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft, llamahip_sampler *sampler,
-                              double repeat_penalty, int32_t top_k, double top_p, double temp, int32_t *n_accept, int32_t *picks, int32_t *exact,
-                              std::vector<int32_t> &win, std::vector<float> &logits, char *err, size_t err_cap) {
-    const int N = n_draft + 1, V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+                              const SampleParams &sp, int32_t *n_accept, int32_t *picks, int32_t *exact, std::vector<int32_t> &win, std::vector<float> &logits,
+                              char *err, size_t err_cap) {
+    const int N = n_draft + 1;
     for (int j = 0; j < N; j++) { picks[j] = -1; if (exact) exact[j] = -1; }
     int rc;
     if (N == 1 || sample_lookup_by_rows(m)) {
@@ -2598,7 +2741,7 @@ static int verify_sample_impl(llamahip_model *m, int32_t n_threads, int32_t n_pa
         int a = 0;
         int32_t tok = token, ex = 0;
         for (;; a++) {
-            if ((rc = sample_single_step(m, n_threads, n_past + a, tok, sampler, repeat_penalty, top_k, top_p, temp, win, logits, &picks[a], &ex, err, err_cap)) != 0) return rc;
+            if ((rc = sample_single_step(m, n_threads, n_past + a, tok, sampler, sp, win, logits, &picks[a], &ex, err, err_cap)) != 0) return rc;
             if (exact) exact[a] = ex;
             if (a == n_draft || picks[a] != draft[a]) break;
             tok = draft[a];
@@ -2608,7 +2751,7 @@ static int verify_sample_impl(llamahip_model *m, int32_t n_threads, int32_t n_pa
     }
     // the id stream: the sampler's window, then the draft (the last draft token is in no row's window)
     const int32_t nw = llamahip_sampler_window(sampler, nullptr, 0);
-    const bool dev_sel = V <= 32768 && k <= 64 && nw <= 1024;
+    const bool dev_sel = sp.dev_sel && nw <= 1024;
     int32_t ids[1024 + VERIFY_ROWS_MAX], rows[VERIFY_ROWS_MAX];
     TopkOut out[VERIFY_ROWS_MAX];
     if (dev_sel) {
@@ -2617,26 +2760,9 @@ static int verify_sample_impl(llamahip_model *m, int32_t n_threads, int32_t n_pa
     }
     rows[0] = token;
     for (int i = 0; i < n_draft; i++) rows[1 + i] = draft[i];
-    const SlideReq sl = { ids, nw, 1.0 / temp, repeat_penalty, dev_sel ? k : 0, out };
+    const SlideReq sl = { ids, nw, sp.scale, sp.repeat_penalty, dev_sel ? sp.k : 0, out };
     if ((rc = verify_step(m, n_threads, n_past, rows, N, -1, nullptr, nullptr, err, err_cap, &sl)) != 0) return rc;
-    llamahip_model *last = m->stages.empty() ? m : m->stages.back();
-    int a = 0;
-    for (;; a++) {
-        const bool ex = dev_sel && out[a].fl[0] == 1;
-        if (ex) picks[a] = llamahip_sample_from_candidates(sampler, out[a].sc, out[a].id, k, top_p);
-        else {
-            // (the rows stay on the device until the next eval: a row the walk reaches and finds inexact is fetched now, that row only)
-            logits.resize((size_t) V);
-            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(hipMemcpy(logits.data(), last->logits + (size_t) a * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
-            picks[a] = llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
-        }
-        llamahip_sampler_accept(sampler, picks[a]);
-        if (exact) exact[a] = ex ? 1 : 0;
-        if (a == n_draft || picks[a] != draft[a]) break;
-    }
-    *n_accept = a;
-    return LLAMAHIP_OK;
+    return sample_walk(m, last_of(m), 0, draft, n_draft, sampler, dev_sel, out, sp, n_accept, picks, exact, logits, err, err_cap);
 }
 
 int llamahip_verify_sample(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t token, const int32_t *draft, int32_t n_draft,
@@ -2649,7 +2775,7 @@ int llamahip_verify_sample(llamahip_model *m, int32_t n_threads, int32_t n_past,
     if ((rc = check_verify_args(m, n_past, token, draft, n_draft, fn, err, err_cap)) != 0) return rc;
     std::vector<int32_t> win;
     std::vector<float> logits;
-    return verify_sample_impl(m, n_threads, n_past, token, draft, n_draft, sampler, repeat_penalty, top_k, top_p, temp, n_accept, picks, exact, win, logits, err, err_cap);
+    return verify_sample_impl(m, n_threads, n_past, token, draft, n_draft, sampler, sample_params(m, repeat_penalty, top_k, top_p, temp), n_accept, picks, exact, win, logits, err, err_cap);
 }
 
 int llamahip_decode_sample_lookup(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
@@ -2661,52 +2787,45 @@ int llamahip_decode_sample_lookup(llamahip_model *m, int32_t n_threads, int32_t 
     int rc = check_sampler_params(fn, sampler, repeat_penalty, top_k, top_p, temp, err, err_cap);
     if (rc) return rc;
     if ((rc = check_lookup_args(m, fn, n_past, first_token, n_steps, context, n_context, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap)) != 0) return rc;
-    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
-    llamahip_lookup_stats ls = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };
+    const SampleParams sp = sample_params(m, repeat_penalty, top_k, top_p, temp);
     // nothing is drafted where a verify step would stream the weights once per row anyway, or where every row would come back whole
-    const bool drafts = !sample_lookup_by_rows(m) && V <= 32768 && k <= 64 && llamahip_sampler_window(sampler, nullptr, 0) <= 1024;
-    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
-    std::vector<int32_t> hist((size_t) n_past + n_steps + 1), win;
+    const bool drafts = !sample_lookup_by_rows(m) && sp.dev_sel && llamahip_sampler_window(sampler, nullptr, 0) <= 1024;
+    LookupRun run;
+    if ((rc = run.open(fn, m->hp.n_ctx, 1, &n_past, n_steps, err, err_cap)) != 0) return rc;
+    run.start(&first_token, context, corpus, n_corpus, draft_len, ngram_min, ngram_max);
+    run.out_tokens = out_tokens; run.out_exact = out_exact;
+    const std::vector<int32_t> act{ 0 };
+    std::vector<int32_t> win;
     std::vector<float> logits;
-    if (n_past > 0) memcpy(hist.data(), context, (size_t) n_past * 4);
-    hist[n_past] = first_token;                     // hist[0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
-    int done = 0;
-    while (done < n_steps) {
-        const int pos = n_past + done;
-        int32_t draft[VERIFY_ROWS_MAX], n_acc = 0, picks[VERIFY_ROWS_MAX], exact[VERIFY_ROWS_MAX];
-        // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
-        const int room = drafts ? std::min(K, n_steps - done - 1) : 0;
-        const int nd = room > 0 ? llamahip_lookup_draft(hist.data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft) : 0;
-        if (nd < 0 || nd > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, nd, room); return LLAMAHIP_ERR_PREDICT; }
-        if (nd == 0) {
-            if ((rc = sample_single_step(m, n_threads, pos, hist[pos], sampler, repeat_penalty, top_k, top_p, temp, win, logits, &picks[0], &exact[0], err, err_cap)) != 0) return rc;
-            ls.n_single_steps++;
-        } else {
-            if ((rc = verify_sample_impl(m, n_threads, pos, hist[pos], draft, nd, sampler, repeat_penalty, top_k, top_p, temp, &n_acc, picks, exact, win, logits, err, err_cap)) != 0) return rc;
-            ls.n_verify_steps++;
-            ls.n_drafted += nd;
-            ls.n_accepted += n_acc;
-        }
-        for (int j = 0; j <= n_acc; j++) {
-            hist[pos + 1 + j] = picks[j];
-            out_tokens[done + j] = picks[j];
-            if (out_exact) out_exact[done + j] = exact[j];
-        }
-        done += n_acc + 1;
+    while (run.done[0] < n_steps) {
+        int32_t nd = 0, n_acc = 0, picks[VERIFY_ROWS_MAX], exact[VERIFY_ROWS_MAX];
+        if ((rc = run.draft_round(act, [&](int) { return drafts; }, &nd, err, err_cap)) != 0) return rc;
+        if (nd == 0) rc = sample_single_step(m, n_threads, run.pos(0), run.token(0), sampler, sp, win, logits, &picks[0], &exact[0], err, err_cap);
+        else rc = verify_sample_impl(m, n_threads, run.pos(0), run.token(0), run.draft[0], nd, sampler, sp, &n_acc, picks, exact, win, logits, err, err_cap);
+        if (rc) return rc;
+        run.accept(0, nd, picks, exact, n_acc + 1);
     }
-    if (stats) *stats = ls;
+    if (stats) *stats = run.ls[0];
     return LLAMAHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
 // llamahip_decode_greedy_multi: n_seqs independent greedy streams at once -- the micro-batched schedule of the layer pipeline (SURVEY.md 8e:
 // "throughput scales only with independent sequences in flight"), native, behind the C ABI.  The slots are cut into G >= n_stages groups of
-// consecutive slots; a stage steps a group as ONE set (llamahip_stage_step_set: its weights streamed once for the group) and hands the group's
-// residual rows to the next stage with one stream-ordered copy + event while it goes on with the next group -- so in steady state every stage
-// (every GPU of a pipeline handle) works on a different group; the last stage's picks go back to the first stage's token words the same way.
-// Host order (step, group, stage): every wait refers to an event recorded by work enqueued before it, so nothing here blocks but the first
-// capture of a set's graph.  A plain handle is the one-stage case: its groups are stepped one after the other, no copies.
+// consecutive slots (group_cut); a stage steps a group as ONE set (llamahip_stage_step_set: its weights streamed once for the group) and hands
+// the group's residual rows to the next stage with one stream-ordered copy + event while it goes on with the next group (step_group) -- so in
+// steady state every stage (every GPU of a pipeline handle) works on a different group; the last stage's picks go back to the first stage's
+// token words the same way.  Host order (step, group, stage): every wait refers to an event recorded by work enqueued before it, so nothing
+// here blocks but the first capture of a set's graph.  A plain handle is the one-stage case: its groups are stepped one after the other, no copies.
 // ------------------------------------------------------------------------------------------------
+// g0[0 .. G]: groups of consecutive slots, at least one per stage (so that every stage has a group to work on), at most SET_MAX slots each
+static std::vector<int> group_cut(int n_seqs, int n_stages) {
+    const int G = std::min(n_seqs, std::max(n_stages, (n_seqs + SET_MAX - 1) / SET_MAX));
+    std::vector<int> g0(G + 1, 0);
+    for (int g = 0; g < G; g++) g0[g + 1] = g0[g] + n_seqs / G + (g < n_seqs % G ? 1 : 0);
+    return g0;
+}
+
 static int multi_prepare(llamahip_model *st, int n_groups, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     const size_t d = st->hp.n_embd;
@@ -2724,79 +2843,127 @@ static int multi_prepare(llamahip_model *st, int n_groups, char *err, size_t err
     return 0;
 }
 
-static int decode_greedy_multi_impl(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
-                                    int32_t *out_tokens, char *err, size_t err_cap) {
+// the pinned block of the sampled decoders: token words, windows, candidates and spill rows, mapped into the device
+static int sample_prepare(llamahip_model *st, bool last, char *err, size_t err_cap) {
+    if (st->smp_blk) return 0;
+    HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+    const size_t n = st->n_seq, V = last ? st->hp.n_vocab : 0;
+    const size_t o_last = (n * 4 + 63) / 64 * 64, o_win = o_last + (n * 4 + 63) / 64 * 64, o_out = o_win + n * 1024 * 4;
+    const size_t o_spill = o_out + (last ? n * sizeof(TopkOut) : 0), bytes = o_spill + n * V * 4;
+    HIP_TRY(hipHostMalloc((void **) &st->smp_blk, bytes, hipHostMallocMapped), LLAMAHIP_ERR_PREDICT);
+    memset(st->smp_blk, 0, bytes);
+    char *d = nullptr;
+    HIP_TRY(hipHostGetDevicePointer((void **) &d, st->smp_blk, 0), LLAMAHIP_ERR_PREDICT);
+    for (int v = 0; v < 2; v++) {
+        char *b = v ? d : st->smp_blk;
+        llamahip_model::SampleIo &io = v ? st->smp_d : st->smp_h;
+        io.tok = (int32_t *) b; io.n_last = (int32_t *) (b + o_last); io.win = (int32_t *) (b + o_win);
+        io.out = last ? (TopkOut *) (b + o_out) : nullptr; io.spill = last ? (float *) (b + o_spill) : nullptr;
+    }
+    if (last) {
+        HIP_TRY(hipMalloc(&st->smp_ws, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemset(st->smp_ws, 0, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+
+// The start of every multi-sequence loop: the stages' queues, and sequence i bound to slot i of every stage at n_past[i].
+// first_tokens != nullptr, the greedy loops: the token words are the first stage's mq_tok, fed by the last stage's pick (one stage: the pick goes
+// straight back into the slot's token word, as the whole-model stage step allows).  nullptr, the sampled loops: the token words lie in the first
+// stage's pinned block and the host writes its draws there (token_out NULL: the argmax of the stage step still advances the slot's position).
+static int multi_begin(const std::vector<llamahip_model *> &stages, int n_groups, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, char *err, size_t err_cap) {
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const size_t d = first->hp.n_embd;
+    int rc;
+    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, n_groups, err, err_cap)) != 0) return rc;
+    if (first_tokens) {
+        HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpy(first->mq_tok, first_tokens, (size_t) n_seqs * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+    } else {
+        if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
+        if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
+    }
+    int32_t *tok_in = first_tokens ? first->mq_tok : first->smp_d.tok, *tok_out = first_tokens ? last->mq_tok : nullptr;
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s];
+        for (int i = 0; i < n_seqs; i++)
+            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? tok_in + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
+                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, s + 1 == S && tok_out ? tok_out + i : nullptr, err, err_cap)) != 0) return rc;
+    }
+    return 0;
+}
+
+// One group of bound slots stepped through every stage.  Stage s waits for stage s - 1's event `ev`, steps the n slots -- as ONE set where it
+// takes sets of n, else slot by slot -- and hands the residual rows of slots [c0, c0 + cn) to stage s + 1 with one stream-ordered copy.  On the
+// last stage `hook` (if any) runs on the stream behind each step -- hook(j, R): rows [0, R) of the logits are the group's slots j .. j + R - 1 (a
+// set orders its rows by slot id; a single step leaves row 0, taken before the next slot's step rewrites it) -- and with copy_picks, on a
+// pipeline, the token words of slots [c0, c0 + cn) go back to the first stage, which with wait_picks waits for that copy of the step before.
+// A stage records its event `ev` behind whatever it enqueued after its step.  The host waits for nothing here, and an error comes back as the
+// return code with work enqueued: every caller drains the stages (drain_stages) before it returns.
+struct SlotGroup { const int32_t *slots; int n, c0, cn, ev; };
+static int step_group(const std::vector<llamahip_model *> &stages, const SlotGroup &g, int32_t n_threads, bool wait_picks, bool copy_picks,
+                      const std::function<int(int, int)> &hook, char *err, size_t err_cap) {
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const size_t d = first->hp.n_embd;
+    for (int s = 0; s < S; s++) {
+        llamahip_model *st = stages[s], *to = s + 1 < S ? stages[s + 1] : first;
+        const bool tail = s + 1 == S;
+        int rc;
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[g.ev], 0), LLAMAHIP_ERR_PREDICT);
+        else if (wait_picks) HIP_TRY(hipStreamWaitEvent(st->stream, last->mq_ev[g.ev], 0), LLAMAHIP_ERR_PREDICT);
+        if (g.n >= 2 && llamahip_stage_set_applies(st, g.n, n_threads)) {
+            if ((rc = llamahip_stage_step_set(st, g.slots, g.n, n_threads, st->stream, err, err_cap)) != 0) return rc;
+            if (tail && hook && (rc = hook(0, g.n)) != 0) return rc;
+        } else for (int j = 0; j < g.n; j++) {
+            if ((rc = llamahip_stage_step(st, g.slots[j], n_threads, st->stream, err, err_cap)) != 0) return rc;
+            if (tail && hook && (rc = hook(j, 1)) != 0) return rc;
+        }
+        const bool picks = tail && copy_picks && S > 1;
+        if (!tail || picks) {
+            void *dst = tail ? (void *) (first->mq_tok + g.c0) : (void *) (to->mq_in + (size_t) g.c0 * d);
+            const void *src = tail ? (const void *) (last->mq_tok + g.c0) : (const void *) (st->mq_out + (size_t) g.c0 * d);
+            const size_t bytes = tail ? (size_t) g.cn * 4 : (size_t) g.cn * d * 4;
+            if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
+            else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, bytes, st->stream), LLAMAHIP_ERR_PREDICT);
+        }
+        if (!tail || picks || hook) HIP_TRY(hipEventRecord(st->mq_ev[g.ev], st->stream), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+
+int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
+                                 int32_t *out_tokens, char *err, size_t err_cap) {
     if (!m) { set_err(err, err_cap, "null model"); return LLAMAHIP_ERR_PREDICT; }
-    std::vector<llamahip_model *> stages = m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages;
+    const std::vector<llamahip_model *> stages = stages_of(m);
     const int S = (int) stages.size();
     llamahip_model *first = stages[0], *last = stages[S - 1];
     if (first->host_only) { set_err(err, err_cap, "model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate"); return LLAMAHIP_ERR_PREDICT; }
     if (!first->first_stage || !last->last_stage) { set_err(err, err_cap, "llamahip_decode_greedy_multi needs a whole-model or a pipeline handle"); return LLAMAHIP_ERR_PREDICT; }
     if (!n_past || !first_tokens || !out_tokens || n_seqs < 1 || n_steps < 1) { set_err(err, err_cap, "llamahip_decode_greedy_multi: bad arguments"); return LLAMAHIP_ERR_PREDICT; }
     if (n_seqs > first->n_seq) { set_err(err, err_cap, "llamahip_decode_greedy_multi: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", n_seqs, first->n_seq); return LLAMAHIP_ERR_PREDICT; }
+    int rc = 0;
     for (int i = 0; i < n_seqs; i++) {
-        int rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap);
-        if (rc) return rc;
+        if ((rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap)) != 0) return rc;
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     }
-    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED))
         // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): llamahip_decode_greedy on each slot in turn
-        const int save_seq = m->cur_seq;
-        int rc = 0;
-        for (int i = 0; i < n_seqs && rc == 0; i++) {
-            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
-                rc = llamahip_decode_greedy(m, n_threads, n_past[i], first_tokens[i], n_steps, out_tokens + (size_t) i * n_steps, nullptr, err, err_cap);
-        }
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
-    }
+        return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
+            return llamahip_decode_greedy(m, n_threads, n_past[i], first_tokens[i], n_steps, out_tokens + (size_t) i * n_steps, nullptr, err, err_cap); });
     const double t0 = now_ms();
-    const size_t d = m->hp.n_embd;
-    // groups of consecutive slots: at least one per stage (so that every stage has a group to work on), at most SET_MAX slots each
-    const int G = std::min(n_seqs, std::max(S, (n_seqs + SET_MAX - 1) / SET_MAX));
-    std::vector<int> g0(G + 1, 0);
-    for (int g = 0; g < G; g++) g0[g + 1] = g0[g] + n_seqs / G + (g < n_seqs % G ? 1 : 0);
-    int rc = 0;
-    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, G, err, err_cap)) != 0) return rc;
-    HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMemcpy(first->mq_tok, first_tokens, (size_t) n_seqs * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
-    for (int s = 0; s < S; s++) {
-        llamahip_model *st = stages[s];
-        for (int i = 0; i < n_seqs; i++) {
-            // (one stage: the pick goes straight back into the slot's token word, as the whole-model stage step allows)
-            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->mq_tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
-                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, s + 1 == S ? (S == 1 ? first->mq_tok + i : last->mq_tok + i) : nullptr, err, err_cap)) != 0) return rc;
-        }
-    }
+    const std::vector<int> g0 = group_cut(n_seqs, S);
+    const int G = (int) g0.size() - 1;
+    if ((rc = multi_begin(stages, G, n_seqs, n_past, first_tokens, err, err_cap)) != 0) return rc;
     std::vector<int32_t> slots(n_seqs);
     for (int i = 0; i < n_seqs; i++) slots[i] = i;
-    for (int t = 0; t < n_steps && rc == 0; t++) {
-        for (int g = 0; g < G && rc == 0; g++) {
-            const int gn = g0[g + 1] - g0[g];
-            for (int s = 0; s < S && rc == 0; s++) {
-                llamahip_model *st = stages[s];
-                HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
-                if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[g], 0), LLAMAHIP_ERR_PREDICT);
-                else if (S > 1 && t > 0) HIP_TRY(hipStreamWaitEvent(st->stream, last->mq_ev[g], 0), LLAMAHIP_ERR_PREDICT);
-                if (gn >= 2 && llamahip_stage_set_applies(st, gn, n_threads)) rc = llamahip_stage_step_set(st, slots.data() + g0[g], gn, n_threads, st->stream, err, err_cap);
-                else for (int i = g0[g]; i < g0[g + 1] && rc == 0; i++) rc = llamahip_stage_step(st, i, n_threads, st->stream, err, err_cap);
-                if (rc || S == 1) continue;
-                // hand the group on: its rows to the next stage, or (last stage) its picks to the first stage's token words
-                llamahip_model *to = s + 1 < S ? stages[s + 1] : first;
-                void *dst = s + 1 < S ? (void *) (to->mq_in + (size_t) g0[g] * d) : (void *) (first->mq_tok + g0[g]);
-                const void *src = s + 1 < S ? (const void *) (st->mq_out + (size_t) g0[g] * d) : (const void *) (last->mq_tok + g0[g]);
-                const size_t bytes = s + 1 < S ? (size_t) gn * d * 4 : (size_t) gn * 4;
-                if (s + 1 == S && t + 1 == n_steps) continue;                  // (nobody waits for the last picks: the trace holds them)
-                if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
-                else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, bytes, st->stream), LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(hipEventRecord(st->mq_ev[g], st->stream), LLAMAHIP_ERR_PREDICT);
-            }
-        }
-    }
-    // wait for every stage (bounded: pipe_wait_stage), collect their fault words
-    const int rc_sync = pipe_sync_stages(stages, rc ? nullptr : err, rc ? 0 : err_cap);
-    if (rc) return rc;
-    if (rc_sync) return rc_sync;
+    // (nobody waits for the last step's picks: the trace holds them)
+    for (int t = 0; t < n_steps && rc == 0; t++)
+        for (int g = 0; g < G && rc == 0; g++)
+            rc = step_group(stages, { slots.data() + g0[g], g0[g + 1] - g0[g], g0[g], g0[g + 1] - g0[g], g }, n_threads, S > 1 && t > 0, t + 1 < n_steps, nullptr, err, err_cap);
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
     for (int i = 0; i < n_seqs; i++) {
         int32_t pos = 0;
         const int n = llamahip_stage_trace(last, i, &pos, out_tokens + (size_t) i * n_steps, n_steps, err, err_cap);
@@ -2809,16 +2976,11 @@ static int decode_greedy_multi_impl(llamahip_model *m, int32_t n_threads, int32_
     return LLAMAHIP_OK;
 }
 
-int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
-                                 int32_t *out_tokens, char *err, size_t err_cap) {
-    return decode_greedy_multi_impl(m, n_threads, n_seqs, n_past, first_tokens, n_steps, out_tokens, err, err_cap);
-}
-
 // ------------------------------------------------------------------------------------------------
 // Drafted greedy decoding for SEVERAL sequences at once: llamahip_verify_greedy_multi / llamahip_decode_greedy_lookup_multi.  A set step has 16
 // rows and costs what its weight stream costs; with 2 .. 8 sequences most rows are unused, and here they carry the sequences' drafts.  The rows
-// of such a step are cut into SEGMENTS, one per sequence: segment i = [last token of slot i, its draft ...] at positions p_i, p_i + 1, ...  The
-// kernels of the set path read three things per row -- position, KV offset, token -- and nothing in them requires the rows' slots to be
+// of such a step are cut into SEGMENTS, one per sequence (VsetReq): segment i = [last token of slot i, its draft ...] at positions p_i, p_i + 1,
+// ...  The kernels of the set path read three things per row -- position, KV offset, token -- and nothing in them requires the rows' slots to be
 // distinct: rows r .. r + j that share one kv_off and hold positions p .. p + j make row r + j the single-token eval of that slot at p + j (its
 // K / V rows are appended by the launch before the score launch, as in a multi-row eval; every row runs the V*P key split of its own
 // single-token eval).  So the step is forward_set on a descriptor built on the host (VsetBlock), then k_verify_rows over all rows and
@@ -2826,16 +2988,6 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
 // (Equality with single steps is BY TEST -- tests/test_gpu_lookup_multi.py -- not structural: the norm's one-pass against two-pass statistics,
 //  as for set steps and verify steps.)
 // ------------------------------------------------------------------------------------------------
-struct VsetReq {
-    int n_segs = 0, n_rows = 0;
-    int32_t slot[SET_MAX], pos[SET_MAX];        // per segment: KV slot, position of its first row
-    int32_t seg_begin[SET_MAX + 1];
-    int32_t rows[SET_MAX];                      // the rows' tokens
-    bool bound = false;                         // the slots are bound (the loop): logs, {position, cursor} and next-token words are kept on the device
-};
-
-static std::vector<llamahip_model *> stages_of(llamahip_model *m) { return m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages; }
-
 // every stage takes set steps of 2 .. 16 rows with this n_threads (else: the callers' per-slot fall-back)
 static bool vset_applies(const std::vector<llamahip_model *> &stages, int n_threads) {
     for (const llamahip_model *st : stages)
@@ -2944,10 +3096,7 @@ static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &sta
         if ((rc = slide_set_enqueue(last, *ss, R, err, err_cap)) != 0) return bail(rc);
         if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        if (ss->k > 0) {
-            if (last->h_io) memcpy(ss->out, last->h_io->rows, (size_t) R * sizeof(TopkOut));
-            else HIP_TRY(hipMemcpy(ss->out, last->d_slide + SLIDE_WS_BYTES + SLIDE_IDS_BYTES, (size_t) R * sizeof(TopkOut), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
-        }
+        if (ss->k > 0 && (rc = slide_fetch(last, ss->out, R, err, err_cap)) != 0) return rc;
         last->last_rows.clear();
         m->n_evals++;
         m->t_eval_ms += now_ms() - t0;
@@ -2977,7 +3126,7 @@ static int check_multi_handle(llamahip_model *m, const char *fn, int32_t n_seqs,
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     if (n_seqs > SET_MAX) { set_err(err, err_cap, "%s: n_seqs must be 1 .. %d (got %d): a step of %d rows has none to spare for drafts, use llamahip_decode_greedy_multi", fn, SET_MAX, n_seqs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
     if (n_seqs < 1) { set_err(err, err_cap, "%s: n_seqs must be 1 .. %d (got %d)", fn, SET_MAX, n_seqs); return LLAMAHIP_ERR_PREDICT; }
-    const int have = (m->stages.empty() ? m : m->stages[0])->n_seq;
+    const int have = first_of(m)->n_seq;
     if (n_seqs > have) { set_err(err, err_cap, "%s: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", fn, n_seqs, have); return LLAMAHIP_ERR_PREDICT; }
     return 0;
 }
@@ -2985,7 +3134,7 @@ static int check_multi_handle(llamahip_model *m, const char *fn, int32_t n_seqs,
 // the arguments of a verify step over a set (greedy and sampled), checked without a device, and the step they describe; the handle last
 static int check_vset_args(llamahip_model *m, const char *fn, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
                            const int32_t *drafts, const int32_t *n_draft, VsetReq &rq, char *err, size_t err_cap) {
-    const int V = m->hp.n_vocab, C = m->hp.n_ctx, have = (m->stages.empty() ? m : m->stages[0])->n_seq;
+    const int V = m->hp.n_vocab, C = m->hp.n_ctx, have = first_of(m)->n_seq;
     int n_rows = 0, n_dr = 0;
     for (int i = 0; i < n_seqs; i++) {
         if (slots[i] < 0 || slots[i] >= have) { set_err(err, err_cap, "%s: sequence slot %d out of range [0, %d)", fn, slots[i], have); return LLAMAHIP_ERR_PREDICT; }
@@ -3005,7 +3154,7 @@ static int check_vset_args(llamahip_model *m, const char *fn, int32_t n_seqs, co
     }
     rq.seg_begin[n_seqs] = n_rows; rq.n_segs = n_seqs; rq.n_rows = n_rows;
     if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    return check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], tokens, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
+    return check_eval_args(first_of(m), n_past[0], tokens, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
 }
 
 int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
@@ -3019,15 +3168,10 @@ int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
     if ((rc = check_vset_args(m, fn, n_seqs, slots, n_past, tokens, drafts, n_draft, rq, err, err_cap)) != 0) return rc;
     const int n_rows = rq.n_rows;
     const std::vector<llamahip_model *> stages = stages_of(m);
-    if (n_rows == 1 || lookup_dense(m) || (stages[0]->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads)) {
-        // no set step on this handle (or one row): llamahip_verify_greedy on each slot in turn
-        const int save_seq = m->cur_seq;
-        for (int i = 0, od = 0, op = 0; i < n_seqs && rc == 0; od += n_draft[i], op += n_draft[i] + 1, i++)
-            if ((rc = llamahip_set_seq(m, slots[i], err, err_cap)) == 0)
-                rc = verify_greedy_impl(m, n_threads, n_past[i], tokens[i], drafts + od, n_draft[i], n_past[i], &n_accept[i], picks + op, nullptr, err, err_cap);
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
-    }
+    if (n_rows == 1 || lookup_dense(m) || (stages[0]->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads))
+        // no set step on this handle (or one row): llamahip_verify_greedy on each slot in turn (segment i's draft: rq.rows behind its first row)
+        return each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
+            return verify_greedy_impl(m, n_threads, n_past[i], tokens[i], rq.rows + rq.seg_begin[i] + 1, n_draft[i], n_past[i], &n_accept[i], picks + rq.seg_begin[i], nullptr, err, err_cap); });
     int32_t res[2 * SET_MAX];
     if ((rc = vset_step(m, stages, n_threads, rq, res, err, err_cap)) != 0) return rc;
     memcpy(n_accept, res, (size_t) n_seqs * 4);
@@ -3035,30 +3179,18 @@ int llamahip_verify_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
     return LLAMAHIP_OK;
 }
 
-// one step of the loop in which nothing is drafted: the captured set step (one active slot: the single step) on the bound slots, stage by stage
-static int multi_plain_step(const std::vector<llamahip_model *> &stages, const std::vector<int32_t> &act, int32_t n_seqs, int32_t n_threads, char *err, size_t err_cap) {
-    const int S = (int) stages.size(), gn = (int) act.size();
-    llamahip_model *first = stages[0], *last = stages[S - 1];
-    const size_t d = first->hp.n_embd;
-    int rc = 0;
-    for (int s = 0; s < S; s++) {
-        llamahip_model *st = stages[s];
-        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
-        if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[0], 0), LLAMAHIP_ERR_PREDICT);
-        if (gn >= 2) rc = llamahip_stage_step_set(st, act.data(), gn, n_threads, st->stream, err, err_cap);
-        else rc = llamahip_stage_step(st, act[0], n_threads, st->stream, err, err_cap);
-        if (rc) return rc;
-        if (S == 1) break;
-        // (every slot's row / token word travels: the words of the slots that sat the step out are not read before they are written again)
-        llamahip_model *to = s + 1 < S ? stages[s + 1] : first;
-        void *dst = s + 1 < S ? (void *) to->mq_in : (void *) first->mq_tok;
-        const void *src = s + 1 < S ? (const void *) st->mq_out : (const void *) last->mq_tok;
-        const size_t bytes = s + 1 < S ? (size_t) n_seqs * d * 4 : (size_t) n_seqs * 4;
-        if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
-        else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, bytes, st->stream), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipEventRecord(st->mq_ev[0], st->stream), LLAMAHIP_ERR_PREDICT);
-    }
-    return 0;
+// the arguments of the two multi-sequence lookup loops behind their own first refusals: the context offsets (run.open), every sequence's lookup
+// arguments, the handle last
+static int check_lookup_multi_args(llamahip_model *m, const char *fn, LookupRun &run, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
+                                   const int32_t *contexts, const int32_t *corpus, int32_t n_corpus, int32_t draft_len, int32_t ngram_min, int32_t ngram_max,
+                                   const int32_t *out_tokens, const llamahip_lookup_stats *stats, char *err, size_t err_cap) {
+    int rc = run.open(fn, m->hp.n_ctx, n_seqs, n_past, n_steps, err, err_cap);
+    if (rc) return rc;
+    for (int i = 0; i < n_seqs; i++)
+        if ((rc = check_lookup_args(m, fn, n_past[i], first_tokens[i], n_steps, contexts ? contexts + run.coff[i] : nullptr, n_past[i], corpus, i == 0 ? n_corpus : 0, draft_len, ngram_min,
+                                    ngram_max, out_tokens, stats ? stats + i : nullptr, err, err_cap, false)) != 0) return rc;
+    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
+    return check_eval_args(first_of(m), n_past[0], first_tokens, 1, true, err, err_cap);      // (HOST_ONLY: refused here)
 }
 
 int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
@@ -3069,102 +3201,45 @@ int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, in
     if (rc) return rc;
     if (!n_past || !first_tokens) { set_err(err, err_cap, "%s: null n_past / first_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
     if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
-    std::vector<size_t> coff(n_seqs + 1, 0);
-    for (int i = 0; i < n_seqs; i++) {
-        if (n_past[i] < 0) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
-        coff[i + 1] = coff[i] + (size_t) n_past[i];
-    }
-    for (int i = 0; i < n_seqs; i++)
-        if ((rc = check_lookup_args(m, fn, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, i == 0 ? n_corpus : 0, draft_len, ngram_min,
-                                    ngram_max, out_tokens, stats ? stats + i : nullptr, err, err_cap, false)) != 0) return rc;
-    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], first_tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    LookupRun run;
+    if ((rc = check_lookup_multi_args(m, fn, run, n_seqs, n_past, first_tokens, n_steps, contexts, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap)) != 0) return rc;
     const std::vector<llamahip_model *> stages = stages_of(m);
     const int S = (int) stages.size();
     llamahip_model *first = stages[0], *last = stages[S - 1];
-    const int save_seq = m->cur_seq;
-    if (n_seqs == 1 || lookup_dense(m) || (first->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads)) {
+    if (n_seqs == 1 || lookup_dense(m) || (first->flags & LLAMAHIP_FLAG_UNFUSED) || !vset_applies(stages, n_threads))
         // one sequence, or no set step on this handle: llamahip_decode_greedy_lookup on each slot in turn
-        for (int i = 0; i < n_seqs && rc == 0; i++)
-            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
-                rc = llamahip_decode_greedy_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, n_corpus,
-                                                   draft_len, ngram_min, ngram_max, out_tokens + (size_t) i * n_steps, nullptr, stats ? stats + i : nullptr, err, err_cap);
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
-    }
+        return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
+            return llamahip_decode_greedy_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + run.coff[i] : nullptr, n_past[i], corpus, n_corpus,
+                                                 draft_len, ngram_min, ngram_max, out_tokens + (size_t) i * n_steps, nullptr, stats ? stats + i : nullptr, err, err_cap); });
     const double t0 = now_ms();
-    const size_t d = m->hp.n_embd;
-    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
-    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, 1, err, err_cap)) != 0) return rc;
-    HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMemcpy(first->mq_tok, first_tokens, (size_t) n_seqs * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
-    for (int s = 0; s < S; s++) {
-        llamahip_model *st = stages[s];
-        for (int i = 0; i < n_seqs; i++)        // (llamahip_decode_greedy_multi's binding: sequence i in slot i, its token word fed by the last stage's pick)
-            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->mq_tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
-                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, s + 1 == S ? (S == 1 ? first->mq_tok + i : last->mq_tok + i) : nullptr, err, err_cap)) != 0) return rc;
-    }
-    std::vector<std::vector<int32_t>> hist(n_seqs);      // hist[i][0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
-    std::vector<int> done(n_seqs, 0);
-    std::vector<llamahip_lookup_stats> ls(n_seqs, llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 });
-    for (int i = 0; i < n_seqs; i++) {
-        hist[i].resize((size_t) n_past[i] + n_steps + 1);
-        if (n_past[i] > 0) memcpy(hist[i].data(), contexts + coff[i], (size_t) n_past[i] * 4);
-        hist[i][n_past[i]] = first_tokens[i];
-    }
+    // (llamahip_decode_greedy_multi's binding: sequence i in slot i, its token word fed by the last stage's pick)
+    if ((rc = multi_begin(stages, 1, n_seqs, n_past, first_tokens, err, err_cap)) != 0) return rc;
+    run.start(first_tokens, contexts, corpus, n_corpus, draft_len, ngram_min, ngram_max);
     std::vector<int32_t> act, words(n_seqs), st2((size_t) 2 * n_seqs);
-    for (;;) {
-        act.clear();
-        for (int i = 0; i < n_seqs; i++) if (done[i] < n_steps) act.push_back(i);
-        if (act.empty()) break;
+    while (run.active(act)) {
         const int A = (int) act.size();
-        int32_t want[SET_MAX], give[SET_MAX], draft[SET_MAX][VERIFY_ROWS_MAX];
-        for (int a = 0; a < A; a++) {
-            const int i = act[a], pos = n_past[i] + done[i];
-            // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
-            const int room = std::min(K, n_steps - done[i] - 1);
-            want[a] = room > 0 ? llamahip_lookup_draft(hist[i].data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft[a]) : 0;
-            if (want[a] < 0 || want[a] > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, want[a], room); return LLAMAHIP_ERR_PREDICT; }
-        }
-        const int dealt = llamahip_lookup_deal_rows(want, A, SET_MAX, give);
-        if (dealt < 0) { set_err(err, err_cap, "%s: dealing the rows of a step failed", fn); return LLAMAHIP_ERR_PREDICT; }
+        int dealt = 0;
+        if ((rc = run.draft_round(act, [](int) { return true; }, &dealt, err, err_cap)) != 0) return rc;
         if (dealt == 0) {
-            if ((rc = multi_plain_step(stages, act, n_seqs, n_threads, err, err_cap)) != 0) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
-            if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
-            llamahip_model *src = S == 1 ? first : last;
-            HIP_TRY(hipSetDevice(src->device), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(hipMemcpy(words.data(), src->mq_tok, (size_t) n_seqs * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
-            for (int a = 0; a < A; a++) {
-                const int i = act[a];
-                hist[i][n_past[i] + done[i] + 1] = words[i];
-                done[i]++;
-                ls[i].n_single_steps++;
-            }
+            // nothing is drafted: the captured set step (one active slot: the single step) on the bound slots.  Every slot's row / token word
+            // travels: the words of the slots that sat the step out are not read before they are written again
+            rc = step_group(stages, { act.data(), A, 0, n_seqs, 0 }, n_threads, false, true, nullptr, err, err_cap);
+            if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(words.data(), last->mq_tok, (size_t) n_seqs * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            for (int i : act) run.accept(i, 0, &words[i], nullptr, 1);
             continue;
         }
         VsetReq rq;
-        rq.bound = true; rq.n_segs = A;
-        int R = 0;
-        for (int a = 0; a < A; a++) {
-            const int i = act[a];
-            rq.slot[a] = i; rq.pos[a] = n_past[i] + done[i]; rq.seg_begin[a] = R;
-            rq.rows[R++] = hist[i][rq.pos[a]];
-            for (int j = 0; j < give[a]; j++) rq.rows[R++] = draft[a][j];
-        }
-        rq.seg_begin[A] = R; rq.n_rows = R;
+        rq.bound = true;
+        run.segments(act, rq);
         int32_t res[2 * SET_MAX];
         if ((rc = vset_step(m, stages, n_threads, rq, res, err, err_cap)) != 0) return rc;
-        for (int a = 0; a < A; a++) {
-            const int i = act[a], na = res[a];
-            for (int j = 0; j <= na; j++) hist[i][rq.pos[a] + 1 + j] = res[A + rq.seg_begin[a] + j];
-            done[i] += na + 1;
-            if (give[a] > 0) { ls[i].n_verify_steps++; ls[i].n_drafted += give[a]; ls[i].n_accepted += na; }
-            else ls[i].n_single_steps++;
-            for (llamahip_model *st : stages) st->slots[i].next_pos += na + 1;      // (the host's mirror of the position the accept kernel advanced)
-        }
+        // (mirror: the host's copy of the position the accept kernel advanced)
+        for (int a = 0; a < A; a++) run.accept(act[a], run.give[a], res + A + rq.seg_begin[a], nullptr, res[a] + 1, &stages);
         if (S > 1) {
             // the last stage's accept kernel advanced ITS slot words; the other stages' positions and the first stage's token words follow from the host
-            for (int i = 0; i < n_seqs; i++) { st2[2 * i] = n_past[i] + done[i]; st2[2 * i + 1] = done[i]; words[i] = hist[i][n_past[i] + done[i]]; }
+            for (int i = 0; i < n_seqs; i++) { st2[2 * i] = run.pos(i); st2[2 * i + 1] = run.done[i]; words[i] = run.token(i); }
             for (int s = 0; s + 1 < S; s++) {
                 HIP_TRY(hipSetDevice(stages[s]->device), LLAMAHIP_ERR_PREDICT);
                 HIP_TRY(hipMemcpy(stages[s]->d_slot_state, st2.data(), st2.size() * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
@@ -3179,12 +3254,12 @@ int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, in
         int32_t pos = 0;
         const int n = llamahip_stage_trace(last, i, &pos, log.data(), n_steps, err, err_cap);
         if (n < 0) return n;
-        if (done[i] != n_steps || n != n_steps || pos != n_past[i] + n_steps || memcmp(log.data(), hist[i].data() + n_past[i] + 1, (size_t) n_steps * 4) != 0) {
-            set_err(err, err_cap, "%s: the device log of sequence %d holds %d tokens up to position %d, the host counted %d of %d up to %d", fn, i, n, pos, done[i], n_steps, n_past[i] + n_steps);
+        if (run.done[i] != n_steps || n != n_steps || pos != n_past[i] + n_steps || memcmp(log.data(), run.hist[i].data() + n_past[i] + 1, (size_t) n_steps * 4) != 0) {
+            set_err(err, err_cap, "%s: the device log of sequence %d holds %d tokens up to position %d, the host counted %d of %d up to %d", fn, i, n, pos, run.done[i], n_steps, n_past[i] + n_steps);
             return LLAMAHIP_ERR_PREDICT;
         }
         memcpy(out_tokens + (size_t) i * n_steps, log.data(), (size_t) n_steps * 4);
-        if (stats) stats[i] = ls[i];
+        if (stats) stats[i] = run.ls[i];
     }
     m->t_eval_ms += now_ms() - t0;
     if (!m->stages.empty()) m->pipe_hand_off = 1;
@@ -3194,32 +3269,21 @@ int llamahip_decode_greedy_lookup_multi(llamahip_model *m, int32_t n_threads, in
 // ------------------------------------------------------------------------------------------------
 // llamahip_decode_sample_multi: the schedule of llamahip_decode_greedy_multi (same groups, set steps, per-slot fall-back, stage hand-offs)
 // with the reference's sampler in place of the argmax.  Behind the launch that produced a group's rows of logits, the last stage's stream
-// runs the sampler's device half over those rows (launch_topk_rows: one launch pair for the group, then k_topk_spill copies the rows
-// flagged inexact to the slots' spill rows) and records the group's event.  The host waits for that event only, finishes each slot's draw
-// with the slot's own sampler (llamahip_sample_from_candidates, or llamahip_sample_top_p_top_k on the spilled row), accepts it, writes the
-// token and the new window into the pinned block and enqueues the group's next step -- while the groups enqueued behind it keep the device
-// (and the other stages) busy.  The draw itself stays on the host: it is libstdc++'s std::discrete_distribution on the sampler's mt19937.
+// runs the sampler's device half over those rows (step_group's hook -- launch_topk_rows: one launch pair for the group, then k_topk_spill
+// copies the rows flagged inexact to the slots' spill rows) and records the group's event.  The host waits for that event only, finishes each
+// slot's draw with the slot's own sampler (sample_draw: from the candidates, or on the spilled row), writes the token and the new window into
+// the pinned block and enqueues the group's next step -- while the groups enqueued behind it keep the device (and the other stages) busy.
+// The draw itself stays on the host: it is libstdc++'s std::discrete_distribution on the sampler's mt19937.
 // ------------------------------------------------------------------------------------------------
-static int sample_prepare(llamahip_model *st, bool last, char *err, size_t err_cap) {
-    if (st->smp_blk) return 0;
-    HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
-    const size_t n = st->n_seq, V = last ? st->hp.n_vocab : 0;
-    const size_t o_last = (n * 4 + 63) / 64 * 64, o_win = o_last + (n * 4 + 63) / 64 * 64, o_out = o_win + n * 1024 * 4;
-    const size_t o_spill = o_out + (last ? n * sizeof(TopkOut) : 0), bytes = o_spill + n * V * 4;
-    HIP_TRY(hipHostMalloc((void **) &st->smp_blk, bytes, hipHostMallocMapped), LLAMAHIP_ERR_PREDICT);
-    memset(st->smp_blk, 0, bytes);
-    char *d = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **) &d, st->smp_blk, 0), LLAMAHIP_ERR_PREDICT);
-    for (int v = 0; v < 2; v++) {
-        char *b = v ? d : st->smp_blk;
-        llamahip_model::SampleIo &io = v ? st->smp_d : st->smp_h;
-        io.tok = (int32_t *) b; io.n_last = (int32_t *) (b + o_last); io.win = (int32_t *) (b + o_win);
-        io.out = last ? (TopkOut *) (b + o_out) : nullptr; io.spill = last ? (float *) (b + o_spill) : nullptr;
-    }
-    if (last) {
-        HIP_TRY(hipMalloc(&st->smp_ws, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(st->smp_ws, 0, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-    }
+// the selection of rows [0, R) of the last stage's logits under the windows at index i0 .. of the pinned block, results at the same index
+// (no device half: the rows whole to the spill rows)
+static int sample_select(llamahip_model *last, const SampleParams &sp, int i0, int R, char *err, size_t err_cap) {
+    const llamahip_model::SampleIo &hl = last->smp_h, &dl = last->smp_d;
+    const size_t V = last->hp.n_vocab;
+    if (sp.dev_sel)
+        HIP_TRY(launch_topk_rows(last->logits, R, (int) V, dl.win + (size_t) i0 * 1024, dl.n_last + i0, sp.scale, sp.repeat_penalty, sp.k, dl.out + i0,
+                                 dl.spill + (size_t) i0 * V, last->stream, last->smp_ws), LLAMAHIP_ERR_PREDICT);
+    else HIP_TRY(hipMemcpyAsync(hl.spill + (size_t) i0 * V, last->logits, (size_t) R * V * 4, hipMemcpyDeviceToHost, last->stream), LLAMAHIP_ERR_PREDICT);
     return 0;
 }
 
@@ -3237,109 +3301,48 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
         for (int j = 0; j < i; j++)
             if (samplers[j] == samplers[i]) { set_err(err, err_cap, "%s: samplers[%d] and samplers[%d] are the same sampler: every sequence draws with its own", F, j, i); return LLAMAHIP_ERR_PREDICT; }
     }
-    std::vector<llamahip_model *> stages = m->stages.empty() ? std::vector<llamahip_model *>{ m } : m->stages;
+    const std::vector<llamahip_model *> stages = stages_of(m);
     const int S = (int) stages.size();
     llamahip_model *first = stages[0], *last = stages[S - 1];
     if (n_seqs > first->n_seq) { set_err(err, err_cap, "%s: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", F, n_seqs, first->n_seq); return LLAMAHIP_ERR_PREDICT; }
     if (first->host_only) { set_err(err, err_cap, "model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate"); return LLAMAHIP_ERR_PREDICT; }
     if (!first->first_stage || !last->last_stage) { set_err(err, err_cap, "%s needs a whole-model or a pipeline handle", F); return LLAMAHIP_ERR_PREDICT; }
+    int rc = 0;
     for (int i = 0; i < n_seqs; i++) {
-        int rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap);
-        if (rc) return rc;
+        if ((rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap)) != 0) return rc;
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     }
-    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
+    // (the device half runs unless top_k > 64 or n_vocab > 32768 -- then every row is spilled; a window of more than 1024 ids spills its row only)
+    const SampleParams sp = sample_params(m, repeat_penalty, top_k, top_p, temp);
     if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
         // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): the single-sequence loop on each slot in turn
-        const int save_seq = m->cur_seq;
-        std::vector<float> logits(V);
+        std::vector<float> logits;
         std::vector<int32_t> win;
-        double sc[64];
-        int32_t ids[64];
-        int rc = 0;
-        for (int i = 0; i < n_seqs && rc == 0; i++) {
-            if ((rc = llamahip_set_seq(m, i, err, err_cap)) != 0) break;
-            int32_t tok = first_tokens[i];
-            for (int t = 0; t < n_steps && rc == 0; t++) {
-                win.resize((size_t) std::max(llamahip_sampler_window(samplers[i], nullptr, 0), 1));
-                const int32_t nw = std::min(llamahip_sampler_window(samplers[i], win.data(), (int32_t) win.size()), (int32_t) win.size());
-                int32_t exact = 0;
-                if ((rc = llamahip_eval_topk(m, n_threads, n_past[i] + t, &tok, 1, win.data(), nw, repeat_penalty, top_k, temp, sc, ids, &exact, logits.data(), err, err_cap)) != 0) break;
-                tok = exact == 1 ? llamahip_sample_from_candidates(samplers[i], sc, ids, k, top_p)
-                                 : llamahip_sample_top_p_top_k(m, samplers[i], logits.data(), repeat_penalty, top_k, top_p, temp);
-                llamahip_sampler_accept(samplers[i], tok);
-                out_tokens[(size_t) i * n_steps + t] = tok;
-                if (out_exact) out_exact[(size_t) i * n_steps + t] = exact == 1;
-            }
-        }
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
+        return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
+            int32_t *out = out_tokens + (size_t) i * n_steps, ex = 0;
+            int r = 0;
+            for (int t = 0; t < n_steps && r == 0; t++)
+                r = sample_single_step(m, n_threads, n_past[i] + t, t ? out[t - 1] : first_tokens[i], samplers[i], sp, win, logits, &out[t], out_exact ? &out_exact[(size_t) i * n_steps + t] : &ex, err, err_cap);
+            return r; });
     }
     const double t0 = now_ms();
-    const size_t d = m->hp.n_embd;
-    // the device half runs unless top_k > 64 or n_vocab > 32768 (then every row is spilled); a window of more than 1024 ids spills its row only
-    const bool dev_sel = V <= 32768 && k <= 64;
-    const double scale = 1.0 / temp;
-    const int G = std::min(n_seqs, std::max(S, (n_seqs + SET_MAX - 1) / SET_MAX));
-    std::vector<int> g0(G + 1, 0);
-    for (int g = 0; g < G; g++) g0[g + 1] = g0[g] + n_seqs / G + (g < n_seqs % G ? 1 : 0);
-    int rc = 0;
-    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, G, err, err_cap)) != 0) return rc;
-    if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
-    if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
-    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h, &dl = last->smp_d;
+    const int V = m->hp.n_vocab;
+    const std::vector<int> g0 = group_cut(n_seqs, S);
+    const int G = (int) g0.size() - 1;
+    if ((rc = multi_begin(stages, G, n_seqs, n_past, nullptr, err, err_cap)) != 0) return rc;
+    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h;
     // (the stream of every stage is idle here: every entry point synchronises before it returns)
     auto publish = [&](int i, int32_t tok) {
         hf.tok[i] = tok;
         hl.n_last[i] = llamahip_sampler_window(samplers[i], hl.win + (size_t) i * 1024, 1024);
     };
     for (int i = 0; i < n_seqs; i++) publish(i, first_tokens[i]);
-    for (int s = 0; s < S; s++) {
-        llamahip_model *st = stages[s];
-        for (int i = 0; i < n_seqs; i++) {
-            // (token_out NULL: the argmax of the stage step still advances the slot's position; the next token is the host's draw)
-            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->smp_d.tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
-                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, nullptr, err, err_cap)) != 0) return rc;
-        }
-    }
     std::vector<int32_t> slots(n_seqs);
     for (int i = 0; i < n_seqs; i++) slots[i] = i;
-    // the selection of rows [0, R) of the last stage's logits = slots [i0, i0 + R)
-    auto select = [&](int i0, int R) -> int {
-        if (dev_sel)
-            HIP_TRY(launch_topk_rows(last->logits, R, V, dl.win + (size_t) i0 * 1024, dl.n_last + i0, scale, repeat_penalty, k, dl.out + i0,
-                                     dl.spill + (size_t) i0 * V, last->stream, last->smp_ws), LLAMAHIP_ERR_PREDICT);
-        else HIP_TRY(hipMemcpyAsync(hl.spill + (size_t) i0 * V, last->logits, (size_t) R * V * 4, hipMemcpyDeviceToHost, last->stream), LLAMAHIP_ERR_PREDICT);
-        return 0;
-    };
-    // one step of group g through every stage, its selection, and the group's event on the last stage
-    auto enqueue = [&](int g) -> int {
-        const int gn = g0[g + 1] - g0[g];
-        int r = 0;
-        for (int s = 0; s < S && r == 0; s++) {
-            llamahip_model *st = stages[s];
-            HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
-            if (s > 0) HIP_TRY(hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[g], 0), LLAMAHIP_ERR_PREDICT);
-            if (gn >= 2 && llamahip_stage_set_applies(st, gn, n_threads)) {
-                r = llamahip_stage_step_set(st, slots.data() + g0[g], gn, n_threads, st->stream, err, err_cap);
-                if (r == 0 && s + 1 == S) r = select(g0[g], gn);                  // (a set orders its rows by slot id: row i = slot g0[g] + i)
-            } else {
-                for (int i = g0[g]; i < g0[g + 1] && r == 0; i++) {
-                    r = llamahip_stage_step(st, i, n_threads, st->stream, err, err_cap);
-                    if (r == 0 && s + 1 == S) r = select(i, 1);                   // (row 0, before the next slot's step rewrites it)
-                }
-            }
-            if (r) break;
-            if (s + 1 < S) {
-                llamahip_model *to = stages[s + 1];
-                void *dst = to->mq_in + (size_t) g0[g] * d;
-                const void *src = st->mq_out + (size_t) g0[g] * d;
-                if (st->device == to->device) HIP_TRY(hipMemcpyAsync(dst, src, (size_t) gn * d * 4, hipMemcpyDeviceToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
-                else HIP_TRY(hipMemcpyPeerAsync(dst, to->device, src, st->device, (size_t) gn * d * 4, st->stream), LLAMAHIP_ERR_PREDICT);
-            }
-            HIP_TRY(hipEventRecord(st->mq_ev[g], st->stream), LLAMAHIP_ERR_PREDICT);
-        }
-        return r;
+    // one step of group g through every stage, its selection (slot i's window and results at index i), and the group's event on the last stage
+    auto enqueue = [&](int g) {
+        return step_group(stages, { slots.data() + g0[g], g0[g + 1] - g0[g], g0[g], g0[g + 1] - g0[g], g }, n_threads, false, false,
+                          [&, g](int j, int R) { return sample_select(last, sp, g0[g] + j, R, err, err_cap); }, err, err_cap);
     };
     for (int g = 0; g < G && rc == 0; g++) rc = enqueue(g);
     for (int t = 0; t < n_steps && rc == 0; t++) {
@@ -3347,21 +3350,14 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
             if ((rc = pipe_wait_stage(last, S - 1, err, err_cap, last->mq_ev[g])) != 0) break;
             for (int i = g0[g]; i < g0[g + 1]; i++) {
                 const TopkOut &c = hl.out[i];
-                const bool exact = dev_sel && c.fl[0] == 1;
-                const int32_t tok = exact ? llamahip_sample_from_candidates(samplers[i], c.sc, c.id, k, top_p)
-                                          : llamahip_sample_top_p_top_k(m, samplers[i], hl.spill + (size_t) i * V, repeat_penalty, top_k, top_p, temp);
-                llamahip_sampler_accept(samplers[i], tok);
+                const int32_t tok = sample_draw(m, samplers[i], sp, sp.dev_sel && c.fl[0] == 1, c.sc, c.id, hl.spill + (size_t) i * V, out_exact ? &out_exact[(size_t) i * n_steps + t] : nullptr);
                 out_tokens[(size_t) i * n_steps + t] = tok;
-                if (out_exact) out_exact[(size_t) i * n_steps + t] = exact ? 1 : 0;
                 if (t + 1 < n_steps) publish(i, tok);
             }
             if (t + 1 < n_steps) rc = enqueue(g);
         }
     }
-    // wait for every stage (bounded), collect their fault words -- on the error paths too, before anything of this call is left behind
-    const int rc_sync = pipe_sync_stages(stages, rc ? nullptr : err, rc ? 0 : err_cap);
-    if (rc) return rc;
-    if (rc_sync) return rc_sync;
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
     std::vector<int32_t> state((size_t) 2 * n_seqs);
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     HIP_TRY(hipMemcpy(state.data(), last->d_slot_state, state.size() * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
@@ -3379,23 +3375,24 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
 // of its slot at its own position.  SAMPLER: the reference's sampler is a deterministic function of (row logits, last_n_tokens window,
 // mt19937 state), and the window at row j of a segment -- IF that sequence's draft tokens 0 .. j - 1 were accepted -- is known before the eval.
 // So the device selects every row's candidates under that window (launch_topk_slide_set behind forward_set on the last stage's stream: the
-// segments slide inside their own id streams of one pool) and the host walks every segment with that sequence's OWN sampler, as
-// verify_sample_impl walks its rows: row 0, then row j + 1 only if row j's draw was draft[j].  The accept step therefore lives on the host:
-// what a segment accepts depends on draws of a host-side mt19937 (std::discrete_distribution), so there is nothing for k_accept_drafts_set
-// to compare; the loop keeps the slots' device words {position, cursor} in step from the host instead.
+// segments slide inside their own id streams of one pool) and the host walks every segment with that sequence's OWN sampler (sample_walk,
+// as verify_sample_impl walks its rows).  The accept step therefore lives on the host: what a segment accepts depends on draws of a host-side
+// mt19937 (std::discrete_distribution), so there is nothing for k_accept_drafts_set to compare; the loop keeps the slots' device words
+// {position, cursor} in step from the host instead.
 // (Equality with single steps is BY TEST -- tests/test_gpu_sample_lookup_multi.py -- not structural: the norm's one-pass against two-pass
 //  statistics, as for set steps and verify steps.)
 // ------------------------------------------------------------------------------------------------
-// the id pool and the per-row table of a sampled step: segment g's stream = samplers[g]'s window, then its draft (rq.rows behind its first row)
-static void slide_set_build(const VsetReq &rq, llamahip_sampler *const *samplers, bool dev_sel, int32_t *pool, SlideSetReq &ss, bool *seg_sel) {
-    ss.ids = pool; ss.n_ids = 0;
+// the id pool and the per-row table of a sampled step: segment g's stream = samplers[g]'s window, then its draft (rq.rows behind its first row);
+// seg_sel[g]: the device makes candidates for the segment's rows
+static void slide_set_build(const VsetReq &rq, llamahip_sampler *const *samplers, const SampleParams &sp, int32_t *pool, TopkOut *out, SlideSetReq &ss, bool *seg_sel) {
+    ss.ids = pool; ss.n_ids = 0; ss.scale = sp.scale; ss.repeat_penalty = sp.repeat_penalty; ss.k = sp.dev_sel ? sp.k : 0; ss.out = out;
     memset(ss.row_off, 0, sizeof(ss.row_off));
     memset(ss.row_n_last, 0, sizeof(ss.row_n_last));
     for (int g = 0; g < rq.n_segs; g++) {
         const int rows = rq.seg_begin[g + 1] - rq.seg_begin[g];
         const int32_t nw = llamahip_sampler_window(samplers[g], nullptr, 0);
-        seg_sel[g] = dev_sel && nw <= 1024;
-        if (!dev_sel) continue;
+        seg_sel[g] = sp.dev_sel && nw <= 1024;
+        if (!sp.dev_sel) continue;
         if (nw > 1024) {        // (no ids travel: the rows are flagged inexact by their length)
             for (int j = 0; j < rows; j++) ss.row_n_last[rq.seg_begin[g] + j] = 1025;
             continue;
@@ -3406,31 +3403,6 @@ static void slide_set_build(const VsetReq &rq, llamahip_sampler *const *samplers
         for (int j = 0; j < rows; j++) { ss.row_off[rq.seg_begin[g] + j] = ss.n_ids + j; ss.row_n_last[rq.seg_begin[g] + j] = nw; }
         ss.n_ids += nw + rows - 1;
     }
-}
-// the walk of segment g behind the step: draws and accepts with the sequence's sampler; picks / exact: the segment's rows (-1 behind the walk)
-static int slide_set_walk(llamahip_model *m, llamahip_model *last, const VsetReq &rq, int g, llamahip_sampler *sampler, bool seg_sel, const TopkOut *out,
-                          double repeat_penalty, int32_t top_k, double top_p, double temp, int32_t *n_accept, int32_t *picks, int32_t *exact,
-                          std::vector<float> &logits, char *err, size_t err_cap) {
-    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V), r0 = rq.seg_begin[g], n_draft = rq.seg_begin[g + 1] - r0 - 1;
-    const int32_t *draft = rq.rows + r0 + 1;
-    for (int j = 0; j <= n_draft; j++) { picks[j] = -1; if (exact) exact[j] = -1; }
-    int a = 0;
-    for (;; a++) {
-        const bool ex = seg_sel && out[r0 + a].fl[0] == 1;
-        if (ex) picks[a] = llamahip_sample_from_candidates(sampler, out[r0 + a].sc, out[r0 + a].id, k, top_p);
-        else {
-            // (the rows stay on the device until the next eval: a row the walk reaches and finds inexact is fetched now, that row only)
-            logits.resize((size_t) V);
-            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(hipMemcpy(logits.data(), last->logits + (size_t) (r0 + a) * V, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
-            picks[a] = llamahip_sample_top_p_top_k(m, sampler, logits.data(), repeat_penalty, top_k, top_p, temp);
-        }
-        llamahip_sampler_accept(sampler, picks[a]);
-        if (exact) exact[a] = ex ? 1 : 0;
-        if (a == n_draft || picks[a] != draft[a]) break;
-    }
-    *n_accept = a;
-    return 0;
 }
 
 static int check_samplers(const char *fn, int32_t n_seqs, llamahip_sampler *const *samplers, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
@@ -3457,31 +3429,25 @@ int llamahip_verify_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
     VsetReq rq;
     if ((rc = check_vset_args(m, fn, n_seqs, slots, n_past, tokens, drafts, n_draft, rq, err, err_cap)) != 0) return rc;
     const std::vector<llamahip_model *> stages = stages_of(m);
+    const SampleParams sp = sample_params(m, repeat_penalty, top_k, top_p, temp);
     std::vector<int32_t> win;
     std::vector<float> logits;
-    if (rq.n_rows == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads)) {
-        // no set step on this handle (or one row): llamahip_verify_sample on each slot in turn
-        const int save_seq = m->cur_seq;
-        for (int i = 0, od = 0, op = 0; i < n_seqs && rc == 0; od += n_draft[i], op += n_draft[i] + 1, i++)
-            if ((rc = llamahip_set_seq(m, slots[i], err, err_cap)) == 0)
-                rc = verify_sample_impl(m, n_threads, n_past[i], tokens[i], drafts + od, n_draft[i], samplers[i], repeat_penalty, top_k, top_p, temp, &n_accept[i],
-                                        picks + op, exact ? exact + op : nullptr, win, logits, err, err_cap);
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
-    }
-    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
-    const bool dev_sel = V <= 32768 && k <= 64;
+    if (rq.n_rows == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads))
+        // no set step on this handle (or one row): llamahip_verify_sample on each slot in turn (segment i's draft: rq.rows behind its first row)
+        return each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
+            return verify_sample_impl(m, n_threads, n_past[i], tokens[i], rq.rows + rq.seg_begin[i] + 1, n_draft[i], samplers[i], sp, &n_accept[i],
+                                      picks + rq.seg_begin[i], exact ? exact + rq.seg_begin[i] : nullptr, win, logits, err, err_cap); });
     std::vector<int32_t> pool(SLIDE_SET_IDS);
     TopkOut out[VERIFY_ROWS_MAX];
     bool seg_sel[SET_MAX];
     SlideSetReq ss;
-    slide_set_build(rq, samplers, dev_sel, pool.data(), ss, seg_sel);
-    ss.scale = 1.0 / temp; ss.repeat_penalty = repeat_penalty; ss.k = dev_sel ? k : 0; ss.out = out;
+    slide_set_build(rq, samplers, sp, pool.data(), out, ss, seg_sel);
     if ((rc = vset_step(m, stages, n_threads, rq, nullptr, err, err_cap, &ss)) != 0) return rc;
-    for (int g = 0; g < n_seqs; g++)
-        if ((rc = slide_set_walk(m, stages.back(), rq, g, samplers[g], seg_sel[g], out, repeat_penalty, top_k, top_p, temp, &n_accept[g], picks + rq.seg_begin[g],
-                                 exact ? exact + rq.seg_begin[g] : nullptr, logits, err, err_cap)) != 0) return rc;
-    return LLAMAHIP_OK;
+    for (int r = 0; r < rq.n_rows; r++) { picks[r] = -1; if (exact) exact[r] = -1; }      // (-1 behind each segment's walk)
+    for (int g = 0; g < n_seqs && rc == 0; g++)
+        rc = sample_walk(m, stages.back(), rq.seg_begin[g], rq.rows + rq.seg_begin[g] + 1, n_draft[g], samplers[g], seg_sel[g], out, sp, &n_accept[g], picks + rq.seg_begin[g],
+                         exact ? exact + rq.seg_begin[g] : nullptr, logits, err, err_cap);
+    return rc;
 }
 
 int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens, int32_t n_steps,
@@ -3496,69 +3462,33 @@ int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, in
     if (!n_past || !first_tokens) { set_err(err, err_cap, "%s: null n_past / first_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
     if (!out_tokens) { set_err(err, err_cap, "%s: null out_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
     if ((rc = check_samplers(fn, n_seqs, samplers, repeat_penalty, top_k, top_p, temp, err, err_cap)) != 0) return rc;
-    std::vector<size_t> coff(n_seqs + 1, 0);
-    for (int i = 0; i < n_seqs; i++) {
-        if (n_past[i] < 0) { set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
-        coff[i + 1] = coff[i] + (size_t) n_past[i];
-    }
-    for (int i = 0; i < n_seqs; i++)
-        if ((rc = check_lookup_args(m, fn, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, i == 0 ? n_corpus : 0, draft_len, ngram_min,
-                                    ngram_max, out_tokens, stats ? stats + i : nullptr, err, err_cap, false)) != 0) return rc;
-    if (m->stages.empty() && (!m->first_stage || !m->last_stage)) { set_err(err, err_cap, "%s on a pipeline-stage handle: load the whole model (or a device list)", fn); return LLAMAHIP_ERR_PREDICT; }
-    if ((rc = check_eval_args(m->stages.empty() ? m : m->stages[0], n_past[0], first_tokens, 1, true, err, err_cap)) != 0) return rc;      // (HOST_ONLY: refused here)
+    LookupRun run;
+    if ((rc = check_lookup_multi_args(m, fn, run, n_seqs, n_past, first_tokens, n_steps, contexts, corpus, n_corpus, draft_len, ngram_min, ngram_max, out_tokens, stats, err, err_cap)) != 0) return rc;
     const std::vector<llamahip_model *> stages = stages_of(m);
-    const int S = (int) stages.size();
-    llamahip_model *first = stages[0], *last = stages[S - 1];
-    if (n_seqs == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads)) {
+    llamahip_model *first = stages[0], *last = stages.back();
+    if (n_seqs == 1 || sample_lookup_by_rows(m) || !vset_applies(stages, n_threads))
         // one sequence, or no set step on this handle: llamahip_decode_sample_lookup on each slot in turn
-        const int save_seq = m->cur_seq;
-        for (int i = 0; i < n_seqs && rc == 0; i++)
-            if ((rc = llamahip_set_seq(m, i, err, err_cap)) == 0)
-                rc = llamahip_decode_sample_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + coff[i] : nullptr, n_past[i], corpus, n_corpus,
-                                                   draft_len, ngram_min, ngram_max, samplers[i], repeat_penalty, top_k, top_p, temp, out_tokens + (size_t) i * n_steps,
-                                                   out_exact ? out_exact + (size_t) i * n_steps : nullptr, stats ? stats + i : nullptr, err, err_cap);
-        (void) llamahip_set_seq(m, save_seq, nullptr, 0);
-        return rc;
-    }
+        return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
+            return llamahip_decode_sample_lookup(m, n_threads, n_past[i], first_tokens[i], n_steps, contexts ? contexts + run.coff[i] : nullptr, n_past[i], corpus, n_corpus,
+                                                 draft_len, ngram_min, ngram_max, samplers[i], repeat_penalty, top_k, top_p, temp, out_tokens + (size_t) i * n_steps,
+                                                 out_exact ? out_exact + (size_t) i * n_steps : nullptr, stats ? stats + i : nullptr, err, err_cap); });
     const double t0 = now_ms();
-    const size_t d = m->hp.n_embd;
-    const int V = m->hp.n_vocab, k = std::min(std::max(top_k, 1), V);
-    const int K = draft_len ? draft_len : LLAMAHIP_LOOKUP_DRAFT_LEN;
+    const int V = m->hp.n_vocab;
     // the device half runs unless top_k > 64 or n_vocab > 32768: then every row is spilled and nobody drafts; a window of more than 1024 ids spills
     // its own rows only, and that sequence wants no draft
-    const bool dev_sel = V <= 32768 && k <= 64;
-    const double scale = 1.0 / temp;
-    for (llamahip_model *st : stages) if ((rc = multi_prepare(st, 1, err, err_cap)) != 0) return rc;
-    if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
-    if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
-    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h, &dl = last->smp_d;
-    for (int s = 0; s < S; s++) {
-        llamahip_model *st = stages[s];
-        for (int i = 0; i < n_seqs; i++)        // (llamahip_decode_sample_multi's binding: sequence i in slot i, its token word in the pinned block, written by the host)
-            if ((rc = llamahip_stage_bind(st, i, n_past[i], s == 0 ? first->smp_d.tok + i : nullptr, s ? st->mq_in + (size_t) i * d : nullptr,
-                                          s + 1 < S ? st->mq_out + (size_t) i * d : nullptr, nullptr, err, err_cap)) != 0) return rc;
-    }
-    std::vector<std::vector<int32_t>> hist(n_seqs);      // hist[i][0 .. pos]: the tokens at positions [0, pos], the last one not evaluated yet
-    std::vector<int> done(n_seqs, 0);
-    std::vector<llamahip_lookup_stats> ls(n_seqs, llamahip_lookup_stats{ (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 });
-    for (int i = 0; i < n_seqs; i++) {
-        hist[i].resize((size_t) n_past[i] + n_steps + 1);
-        if (n_past[i] > 0) memcpy(hist[i].data(), contexts + coff[i], (size_t) n_past[i] * 4);
-        hist[i][n_past[i]] = first_tokens[i];
-    }
-    auto emit = [&](int i, int32_t tok, int32_t ex) {
-        hist[i][n_past[i] + done[i] + 1] = tok;
-        out_tokens[(size_t) i * n_steps + done[i]] = tok;
-        if (out_exact) out_exact[(size_t) i * n_steps + done[i]] = ex;
-        done[i]++;
-    };
+    const SampleParams sp = sample_params(m, repeat_penalty, top_k, top_p, temp);
+    // (llamahip_decode_sample_multi's binding: sequence i in slot i, its token word in the pinned block, written by the host)
+    if ((rc = multi_begin(stages, 1, n_seqs, n_past, nullptr, err, err_cap)) != 0) return rc;
+    const llamahip_model::SampleIo &hf = first->smp_h, &hl = last->smp_h;
+    run.start(first_tokens, contexts, corpus, n_corpus, draft_len, ngram_min, ngram_max);
+    run.out_tokens = out_tokens; run.out_exact = out_exact;
     // a verify step advances no slot word on any device (what it accepts is known on the host only): before the next captured step the host writes
     // every slot's {position, cursor} on every stage -- through the pinned block where the stage has one; the first stage's token words are
     // written before every plain step anyway
     bool words_stale = false;
     auto push_words = [&]() -> int {
         int32_t w[2 * SET_MAX];
-        for (int i = 0; i < n_seqs; i++) { w[2 * i] = n_past[i] + done[i]; w[2 * i + 1] = done[i]; }
+        for (int i = 0; i < n_seqs; i++) { w[2 * i] = run.pos(i); w[2 * i + 1] = run.done[i]; }
         for (llamahip_model *st : stages) {
             HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
             if (st->h_io) {                 // (the stream is idle: the step before was waited for)
@@ -3569,100 +3499,58 @@ int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, in
         words_stale = false;
         return 0;
     };
+    // (the selection of a plain step: row a's window and results at index a of the pinned block)
+    const std::function<int(int, int)> select = [&](int j, int R) { return sample_select(last, sp, j, R, err, err_cap); };
     std::vector<int32_t> act, pool(SLIDE_SET_IDS);
     std::vector<float> logits;
-    for (;;) {
-        act.clear();
-        for (int i = 0; i < n_seqs; i++) if (done[i] < n_steps) act.push_back(i);
-        if (act.empty()) break;
+    while (run.active(act)) {
         const int A = (int) act.size();
-        int32_t want[SET_MAX], give[SET_MAX], draft[SET_MAX][VERIFY_ROWS_MAX];
-        for (int a = 0; a < A; a++) {
-            const int i = act[a], pos = n_past[i] + done[i];
-            // (the last row evaluated is position n_past + n_steps - 1: a draft that would pass it is cut)
-            const int room = dev_sel && llamahip_sampler_window(samplers[i], nullptr, 0) <= 1024 ? std::min(K, n_steps - done[i] - 1) : 0;
-            want[a] = room > 0 ? llamahip_lookup_draft(hist[i].data(), pos + 1, corpus, n_corpus, room, ngram_min, ngram_max, draft[a]) : 0;
-            if (want[a] < 0 || want[a] > room) { set_err(err, err_cap, "%s: the drafter returned %d tokens for a draft of %d", fn, want[a], room); return LLAMAHIP_ERR_PREDICT; }
-        }
-        const int dealt = llamahip_lookup_deal_rows(want, A, SET_MAX, give);
-        if (dealt < 0) { set_err(err, err_cap, "%s: dealing the rows of a step failed", fn); return LLAMAHIP_ERR_PREDICT; }
+        int dealt = 0;
+        if ((rc = run.draft_round(act, [&](int i) { return sp.dev_sel && llamahip_sampler_window(samplers[i], nullptr, 0) <= 1024; }, &dealt, err, err_cap)) != 0) return rc;
         if (dealt == 0) {
-            // llamahip_decode_sample_multi's step over the active slots: row a of the step = slot act[a] (a set orders its rows by slot id)
-            if (words_stale && (rc = push_words()) != 0) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
+            // llamahip_decode_sample_multi's step over the active slots: row a of the step = slot act[a] (a set orders its rows by slot id).  Every
+            // slot's row travels: the rows of the slots that sat the step out are not read before they are written again
+            if (words_stale) rc = push_words();
+            for (int a = 0; a < A && rc == 0; a++) {
+                hf.tok[act[a]] = run.token(act[a]);
+                hl.n_last[a] = llamahip_sampler_window(samplers[act[a]], hl.win + (size_t) a * 1024, 1024);
+            }
+            if (rc == 0) rc = step_group(stages, { act.data(), A, 0, n_seqs, 0 }, n_threads, false, false, select, err, err_cap);
+            if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
             for (int a = 0; a < A; a++) {
-                const int i = act[a];
-                hf.tok[i] = hist[i][n_past[i] + done[i]];
-                hl.n_last[a] = llamahip_sampler_window(samplers[i], hl.win + (size_t) a * 1024, 1024);
-            }
-            for (int s = 0; s < S && rc == 0; s++) {
-                llamahip_model *st = stages[s];
-                if (hipSetDevice(st->device) != hipSuccess || (s > 0 && hipStreamWaitEvent(st->stream, stages[s - 1]->mq_ev[0], 0) != hipSuccess)) { set_err(err, err_cap, "%s: HIP error ordering the stages of a step", fn); rc = LLAMAHIP_ERR_PREDICT; break; }
-                if (A >= 2) rc = llamahip_stage_step_set(st, act.data(), A, n_threads, st->stream, err, err_cap);
-                else rc = llamahip_stage_step(st, act[0], n_threads, st->stream, err, err_cap);
-                if (rc || s + 1 == S) break;
-                // (every slot's row travels: the rows of the slots that sat the step out are not read before they are written again)
-                llamahip_model *to = stages[s + 1];
-                const hipError_t e = st->device == to->device ? hipMemcpyAsync(to->mq_in, st->mq_out, (size_t) n_seqs * d * 4, hipMemcpyDeviceToDevice, st->stream)
-                                                              : hipMemcpyPeerAsync(to->mq_in, to->device, st->mq_out, st->device, (size_t) n_seqs * d * 4, st->stream);
-                if (e != hipSuccess || hipEventRecord(st->mq_ev[0], st->stream) != hipSuccess) { set_err(err, err_cap, "%s: HIP error handing a step's rows on", fn); rc = LLAMAHIP_ERR_PREDICT; }
-            }
-            if (rc == 0) {
-                const hipError_t e = dev_sel ? launch_topk_rows(last->logits, A, V, dl.win, dl.n_last, scale, repeat_penalty, k, dl.out, dl.spill, last->stream, last->smp_ws)
-                                             : hipMemcpyAsync(hl.spill, last->logits, (size_t) A * V * 4, hipMemcpyDeviceToHost, last->stream);
-                if (e != hipSuccess) { set_err(err, err_cap, "%s: HIP error enqueuing the selection of a step", fn); rc = LLAMAHIP_ERR_PREDICT; }
-            }
-            if (rc) { (void) pipe_sync_stages(stages, nullptr, 0); return rc; }
-            if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
-            for (int a = 0; a < A; a++) {
-                const int i = act[a];
                 const TopkOut &c = hl.out[a];
-                const bool ex = dev_sel && c.fl[0] == 1;
-                const int32_t tok = ex ? llamahip_sample_from_candidates(samplers[i], c.sc, c.id, k, top_p)
-                                       : llamahip_sample_top_p_top_k(m, samplers[i], hl.spill + (size_t) a * V, repeat_penalty, top_k, top_p, temp);
-                llamahip_sampler_accept(samplers[i], tok);
-                emit(i, tok, ex ? 1 : 0);
-                ls[i].n_single_steps++;
+                int32_t ex = 0;
+                const int32_t tok = sample_draw(m, samplers[act[a]], sp, sp.dev_sel && c.fl[0] == 1, c.sc, c.id, hl.spill + (size_t) a * V, &ex);
+                run.accept(act[a], 0, &tok, &ex, 1);
             }
             m->n_evals += A;
             continue;
         }
         VsetReq rq;
-        rq.n_segs = A;
-        int R = 0;
+        run.segments(act, rq);
         llamahip_sampler *seg_smp[SET_MAX];
-        for (int a = 0; a < A; a++) {
-            const int i = act[a];
-            rq.slot[a] = i; rq.pos[a] = n_past[i] + done[i]; rq.seg_begin[a] = R; seg_smp[a] = samplers[i];
-            rq.rows[R++] = hist[i][rq.pos[a]];
-            for (int j = 0; j < give[a]; j++) rq.rows[R++] = draft[a][j];
-        }
-        rq.seg_begin[A] = R; rq.n_rows = R;
+        for (int a = 0; a < A; a++) seg_smp[a] = samplers[act[a]];
         TopkOut out[VERIFY_ROWS_MAX];
         bool seg_sel[SET_MAX];
         SlideSetReq ss;
-        slide_set_build(rq, seg_smp, dev_sel, pool.data(), ss, seg_sel);
-        ss.scale = scale; ss.repeat_penalty = repeat_penalty; ss.k = k; ss.out = out;
+        slide_set_build(rq, seg_smp, sp, pool.data(), out, ss, seg_sel);
         if ((rc = vset_step(m, stages, n_threads, rq, nullptr, err, err_cap, &ss)) != 0) return rc;
         for (int a = 0; a < A; a++) {
-            const int i = act[a];
             int32_t na = 0, picks[VERIFY_ROWS_MAX], exact[VERIFY_ROWS_MAX];
-            if ((rc = slide_set_walk(m, last, rq, a, samplers[i], seg_sel[a], out, repeat_penalty, top_k, top_p, temp, &na, picks, exact, logits, err, err_cap)) != 0) return rc;
-            for (int j = 0; j <= na; j++) emit(i, picks[j], exact[j]);
-            if (give[a] > 0) { ls[i].n_verify_steps++; ls[i].n_drafted += give[a]; ls[i].n_accepted += na; }
-            else ls[i].n_single_steps++;
-            for (llamahip_model *st : stages) st->slots[i].next_pos += na + 1;      // (the host's mirror of the slot's position)
+            if ((rc = sample_walk(m, last, rq.seg_begin[a], rq.rows + rq.seg_begin[a] + 1, run.give[a], seg_smp[a], seg_sel[a], out, sp, &na, picks, exact, logits, err, err_cap)) != 0) return rc;
+            run.accept(act[a], run.give[a], picks, exact, na + 1, &stages);      // (mirror: the host's copy of the slot's position)
         }
         words_stale = true;
     }
     // the slots end where a caller of the stage API expects them; the last stage's words are read back against the host's count
-    if (words_stale && (rc = push_words()) != 0) return rc;
-    if ((rc = pipe_sync_stages(stages, err, err_cap)) != 0) return rc;
+    if (words_stale) rc = push_words();
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
     std::vector<int32_t> state((size_t) 2 * n_seqs);
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     HIP_TRY(hipMemcpy(state.data(), last->d_slot_state, state.size() * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
     for (int i = 0; i < n_seqs; i++) {
-        if (done[i] != n_steps || state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d after %d of %d steps, not at %d", fn, i, state[2 * i], done[i], n_steps, n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
-        if (stats) stats[i] = ls[i];
+        if (run.done[i] != n_steps || state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d after %d of %d steps, not at %d", fn, i, state[2 * i], run.done[i], n_steps, n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
+        if (stats) stats[i] = run.ls[i];
     }
     m->t_eval_ms += now_ms() - t0;
     if (!m->stages.empty()) m->pipe_hand_off = 1;
