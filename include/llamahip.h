@@ -473,6 +473,55 @@ int llamahip_decode_greedy_window(llamahip_model *m, int32_t n_threads, int32_t 
                                   const int32_t *context, int32_t n_context, int32_t n_keep, int32_t mode, int32_t chunk_tokens,
                                   int32_t *out_tokens, float *logits_last, int32_t *n_past_out, char *err, size_t err_cap);
 
+/* ---- the prompts of several sequences in one weight pass ------------------------------------------------------------------------------
+ * The *_multi decode loops above step up to 16 conversations per weight stream, but every slot's context still had to be evaluated with
+ * llamahip_set_seq(i) + llamahip_eval / llamahip_eval_chunks: n_seqs evals, each streaming every weight matrix (a 9-token eval of the 7B is
+ * almost all weight stream).  llamahip_eval_multi evaluates R = sum n_tokens[i] rows cut into SEGMENTS, one per KV slot -- segment i the
+ * n_tokens[i] tokens of slot slots[i] at n_past[i] -- in ONE pass: every operator of llama_eval's graph works row by row except the RoPE /
+ * KV append and the attention, and those two only need each row's position, cache and V*P key split, which they read from a device-resident
+ * ROW TABLE {pos, keys, kv_off} (rows_attn.hip: one RoPE launch and one score / soft_max . V launch pair per layer for all the rows of all
+ * the short segments; a segment of more than 60 rows takes the long eval's attention launches on its own rows and cache).  The mat-muls run
+ * over all R rows with the kernel a single eval of R rows takes; the final norm and the lm head run over the n_seqs last rows only.
+ *
+ * Contract: for every i the call leaves the bits of llamahip_set_seq(slots[i]) + llamahip_eval_chunks(n_past[i], tokens_i, n_tokens[i],
+ * chunk_tokens) on that slot alone (chunk_tokens 0: llamahip_eval) -- KV rows [n_past[i], n_past[i] + n_tokens[i]) of slot slots[i] in
+ * every layer, and row i of logits_out.  No other KV row is touched, the handle's current slot is left alone, the logits row map of
+ * llamahip_stage_logits is reset.  (A one-token segment is a single-token eval, whose norm statistics are one-pass in the fused step and
+ * two-pass here: equality there is BY TEST -- tests/test_gpu_eval_multi.py -- not structural, as for set steps and verify steps.)
+ * Refused before any device work, the message naming the limit, the handle last: n_seqs < 1 or > llamahip_opts.n_seq, a slot out of range
+ * or named twice, n_tokens[i] < 1, n_past[i] < 0 or n_past[i] + n_tokens[i] > n_ctx, a token id out of range, chunk_tokens < 0,
+ * R > LLAMAHIP_EVAL_MULTI_MAX_ROWS, HOST_ONLY and stage handles.
+ * Handles: Q4_0 plain handles and in-process pipeline handles take the one pass (the R residual rows cross the stages as an eval's do, every
+ * stage builds the table on its own device); LLAMAHIP_FLAG_UNFUSED / _NO_GRAPH / _NO_PREFILL_COPY do not change a multi-row eval.  f16 / f32
+ * / Q4_1 files, LLAMAHIP_FLAG_FAST_PREFILL handles (their GEMM choice depends on the row count: no parity claim), n_seqs == 1 and the shapes of
+ * the measured rule below run the per-slot loop of the contract itself and report its eval count in stats->n_passes.
+ * Numbers (7B, one MI355X, chunks of 9, ms per call, one pass against the per-slot loop; tools/eval_multi_probe.py, profiles/eval_multi_probe_7b.json):
+ *   segments x rows    2 x 9   4 x 9   8 x 9   16 x 9   8 x 32   16 x 32   2 x 128   16 x 128   2 x 512   4 x 512
+ *   one pass            4.77    7.59   13.36    19.66    23.62     42.31     21.40     160.34     70.59    146.76
+ *   loop                6.12   12.21   24.45    49.10    53.83    107.85     29.34     234.98     72.20    144.45
+ *   The rule that follows from it: more than 1024 rows in segments of 512 rows or more each (the one shape family where the pass measured
+ *   slower than the loop by more than the loop's spread) run the per-slot loop; the bits are the same.  Long segments keep their own
+ *   attention launches because joining the table launch measured slower (16 x 128 rows: 155.9 against 175.7 ms).  DESIGN.md 12.17.
+ * llamahip_eval_multi_rows -- host only, no handle, pure: the row table of such a pass.  Row r, the j-th of segment i's N_i rows:
+ *   row_seg[r] = i, row_pos[r] = n_past[i] + j, row_keys[r] = the key count the reference splits over its threads for that row
+ *   (n_past[i] + N_i; chunk_tokens > 0: n_past[i] + min(N_i, (j / chunk_tokens + 1) * chunk_tokens)).  Any output may be NULL.
+ *   Returns R, or -1 for bad arguments (a segment outside [0, n_ctx], R > LLAMAHIP_EVAL_MULTI_MAX_ROWS). */
+#define LLAMAHIP_EVAL_MULTI_MAX_ROWS 2048
+typedef struct llamahip_eval_multi_stats {
+    int32_t struct_size;
+    int32_t n_rows;            /* sum of n_tokens */
+    int32_t n_passes;          /* weight passes taken: 1 = one pass over all rows; the per-slot loop reports its eval count */
+    int32_t n_short_segs, n_long_segs;   /* segments whose attention ran in the table launch / in launches of their own */
+    int32_t attn_groups;       /* attention launch groups per layer: 1 for all short segments together + 1 per long segment */
+} llamahip_eval_multi_stats;
+int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots,
+                        const int32_t *n_past, const int32_t *tokens /* concatenated, n_tokens[i] each */,
+                        const int32_t *n_tokens, int32_t chunk_tokens /* 0 = one eval per segment */,
+                        float *logits_out /* [n_seqs][n_vocab], may be NULL */,
+                        llamahip_eval_multi_stats *stats /* may be NULL */, char *err, size_t err_cap);
+int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n_past, const int32_t *n_tokens,
+                                 int32_t chunk_tokens, int32_t *row_seg, int32_t *row_pos, int32_t *row_keys);
+
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
 int llamahip_eval_debug(llamahip_model *m, int32_t n_threads, int32_t n_past,
@@ -641,6 +690,16 @@ int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K
 int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
                           int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
                           void *wo_operand, int32_t *path_taken, char *err, size_t err_cap);
+/* The attention of llamahip_eval_multi's pass on caller-supplied operands: R rows of several KV slots through the row-table kernels
+ * (rows_attn.hip: k_rope_kv_rows, then k_rows_scores + k_rows_pv over all R rows).  qkv [R][3d] un-rotated; Kc, Vc [n_slots][n_ctx][d],
+ * copied whole both ways; row r belongs to slot row_slot[r], sits at position row_pos[r] and splits row_keys[r] keys over n_threads
+ * (llamahip_eval_multi_rows builds such a table).  merged [R][merged_stride] or NULL, wo_operand [R][d/32] Q4_0 blocks or NULL: as
+ * llamahip_op_attention's.  The table is checked on the host first, the message naming the limit: the rows of one slot must be one run of
+ * consecutive positions in ascending row order with row_pos < row_keys <= the run's end <= n_ctx.  Each run's results are bit for bit
+ * llamahip_op_attention's (_SHORT / _ROW) on that run alone with its slot's cache. */
+int llamahip_op_attention_rows(const float *qkv, int32_t R, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
+                               const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, int32_t n_threads,
+                               float *merged, int32_t merged_stride, void *wo_operand, char *err, size_t err_cap);
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);

@@ -26,11 +26,13 @@ from .binding import (  # noqa: F401
     declared_symbols,
     dense_paths,
     dense_set_plan,
+    eval_multi_rows,
     gemm_paths,
     lib,
     lookup_deal_rows,
     lookup_draft,
     op_attention,
+    op_attention_rows,
     op_embed,
     op_logprob,
     op_mul_mat_dense,

@@ -57,6 +57,11 @@ class _GemvBench(C.Structure):
                 ("algo_bytes", C.c_double)]
 
 
+class _EvalMultiStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_rows", C.c_int32), ("n_passes", C.c_int32), ("n_short_segs", C.c_int32),
+                ("n_long_segs", C.c_int32), ("attn_groups", C.c_int32)]
+
+
 class _LookupStats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_verify_steps", C.c_int32), ("n_single_steps", C.c_int32), ("n_drafted", C.c_int64), ("n_accepted", C.c_int64)]
 
@@ -157,6 +162,10 @@ def lib() -> C.CDLL:
     L.llamahip_op_quantize_row_q4_0.argtypes = [vp, i32, vp, cp, sz]
     L.llamahip_op_prompt_gemm_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
     L.llamahip_op_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, cp, sz]
+    L.llamahip_op_attention_rows.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, cp, sz]
+    L.llamahip_eval_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
+    L.llamahip_eval_multi_rows.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
+    L.llamahip_eval_multi_rows.restype = i32
     L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
     L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
@@ -536,6 +545,25 @@ class Model:
                                                  C.byref(st), err, len(err))
         _check(rc, err)
         return out, exact, {k: getattr(st, k) for k, _ in _LookupStats._fields_ if k != "struct_size"}
+
+    def eval_multi(self, slots, n_past, token_lists, chunk_tokens: int = 0, n_threads: int = 8, want_stats: bool = False):
+        """llamahip_eval_multi: token_lists[i] evaluated at n_past[i] on KV slot slots[i], all in one weight pass.  Returns the segments' last
+        rows of logits [n_seqs][n_vocab] (with want_stats: (logits, the llamahip_eval_multi_stats fields as a dict))."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        toks = [np.ascontiguousarray(t, np.int32).ravel() for t in token_lists]
+        if not (slots.size == npast.size == len(toks)):
+            raise ValueError(f"eval_multi: {slots.size} slots, {npast.size} n_past, {len(toks)} token lists")
+        nt = np.array([t.size for t in toks], np.int32)
+        flat = np.ascontiguousarray(np.concatenate(toks), np.int32) if int(nt.sum()) else np.zeros(1, np.int32)
+        logits = np.empty((max(slots.size, 1), self.n_vocab), np.float32)
+        st = _EvalMultiStats(C.sizeof(_EvalMultiStats))
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_eval_multi(self._h, n_threads, slots.size, _ptr(slots), _ptr(npast), _ptr(flat), _ptr(nt), int(chunk_tokens),
+                                       _ptr(logits), C.byref(st), err, len(err))
+        _check(rc, err)
+        logits = logits[:slots.size]
+        return (logits, {k: getattr(st, k) for k, _ in _EvalMultiStats._fields_ if k != "struct_size"}) if want_stats else logits
 
     def decode_greedy_multi(self, first_tokens, n_past, n_steps: int, n_threads: int = 8) -> np.ndarray:
         """llamahip_decode_greedy_multi: sequences in KV slots 0 .. len(first_tokens) - 1 decoded together; returns [n_seqs][n_steps]."""
@@ -1007,6 +1035,42 @@ def op_attention(qkv: np.ndarray, H: int, n_past: int, Kc: np.ndarray, Vc: np.nd
     _check(rc, err)
     name = ATTN_PATHS[taken.value]
     return merged, (wo if name in ("short", "dec", "dec_stream") else None), name
+
+
+def eval_multi_rows(n_ctx: int, n_past, n_tokens, chunk_tokens: int = 0):
+    """llamahip_eval_multi_rows (host only): the row table of an eval_multi pass -- (row_seg, row_pos, row_keys) int32 [R] -- or None where the
+    arguments are refused."""
+    npast = np.ascontiguousarray(n_past, np.int32).ravel()
+    nt = np.ascontiguousarray(n_tokens, np.int32).ravel()
+    if npast.size != nt.size:
+        raise ValueError(f"eval_multi_rows: {npast.size} n_past, {nt.size} n_tokens")
+    cap = max(int(np.clip(nt.astype(np.int64), 0, None).sum()), 1)
+    seg, pos, keys = (np.full(cap, -1, np.int32) for _ in range(3))
+    R = lib().llamahip_eval_multi_rows(int(n_ctx), npast.size, _ptr(npast), _ptr(nt), int(chunk_tokens), _ptr(seg), _ptr(pos), _ptr(keys))
+    return None if R < 0 else (seg[:R], pos[:R], keys[:R])
+
+
+def op_attention_rows(qkv: np.ndarray, H: int, Kc: np.ndarray, Vc: np.ndarray, row_slot, row_pos, row_keys, n_threads: int = 8,
+                      merged_stride: int | None = None, merged_init=None, want_wo: bool = True):
+    """The row-table attention of eval_multi's pass (llamahip_op_attention_rows): qkv f32 [R, 3d] un-rotated, Kc / Vc f32 [n_slots, n_ctx, d]
+    (updated in place).  Returns (merged f32 [R, merged_stride], the wo operand uint8 [R, d/32, 20] or None)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    R, d3 = qkv.shape
+    d = d3 // 3
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 3 or a.shape[2] != d or a.shape != Kc.shape:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_slots, n_ctx, d]")
+    tab = [np.ascontiguousarray(a, np.int32).ravel() for a in (row_slot, row_pos, row_keys)]
+    if any(a.size != R for a in tab):
+        raise ValueError(f"op_attention_rows: the table must have R = {R} entries")
+    ms = d if merged_stride is None else int(merged_stride)
+    merged = np.full((R, ms), np.nan, np.float32) if merged_init is None else np.array(merged_init, np.float32, order="C").reshape(R, ms)
+    wo = np.full((R, max(d // 32, 1), 20), 0xEE, np.uint8) if want_wo else None
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_attention_rows(_ptr(qkv), R, d, int(H), Kc.shape[1], Kc.shape[0], _ptr(Kc), _ptr(Vc), _ptr(tab[0]), _ptr(tab[1]),
+                                          _ptr(tab[2]), int(n_threads), _ptr(merged), ms, _ptr(wo), err, len(err))
+    _check(rc, err)
+    return merged, wo
 
 
 def debug_attn_path(N: int, head_size: int, n_past: int, n_threads: int, n_ctx: int) -> str | None:

@@ -1,0 +1,101 @@
+// eval_multi.cpp -- the host half of llamahip_eval_multi (include/llamahip.h): the row table of a pass over several KV slots
+// (llamahip_eval_multi_rows), what the entry point refuses of its arguments (eval_multi_check) and what llamahip_op_attention_rows refuses of a
+// caller's table (rows_table_check).  Pure host code, no device, no handle: tools/host_sanitize runs it under ASan + UBSan.
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/llamahip.h"
+
+namespace lh {
+
+// prompt_attn.hip split_keys, restated for the host: the key count row j of an eval of N rows at n_past splits over the threads in V*P --
+// n_past + N of the eval the row belongs to (ggml.c:5459-5480), which in a chunked pass is the eval of its chunk
+static inline int32_t split_keys_host(int32_t n_past, int32_t N, int32_t j, int32_t chunk) {
+    return chunk > 0 ? n_past + std::min(N, (j / chunk + 1) * chunk) : n_past + N;
+}
+
+// what llamahip_eval_multi refuses of its ARGUMENTS (the handle is the caller's business): 0, or LLAMAHIP_ERR_PREDICT with the limit in err
+int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                     const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_multi";
+    if (!err) err_cap = 0;
+    if (n_seqs < 1 || n_seqs > n_slots) { snprintf(err, err_cap, "%s: n_seqs (%d) outside 1 .. %d, the handle's KV slots (llamahip_opts.n_seq)", fn, n_seqs, n_slots); return LLAMAHIP_ERR_PREDICT; }
+    if (!slots || !n_past || !tokens || !n_tokens) { snprintf(err, err_cap, "%s: null slots, n_past, tokens or n_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (chunk_tokens < 0) { snprintf(err, err_cap, "%s: chunk_tokens (%d) must be >= 0 (0 = one eval per segment)", fn, chunk_tokens); return LLAMAHIP_ERR_PREDICT; }
+    std::vector<char> seen((size_t) n_slots, 0);
+    int64_t R = 0;
+    for (int32_t i = 0; i < n_seqs; i++) {
+        if (slots[i] < 0 || slots[i] >= n_slots) { snprintf(err, err_cap, "%s: slots[%d] = %d out of range [0, %d)", fn, i, slots[i], n_slots); return LLAMAHIP_ERR_PREDICT; }
+        if (seen[slots[i]]) { snprintf(err, err_cap, "%s: slot %d is named twice (slots[%d]): one segment per KV slot", fn, slots[i], i); return LLAMAHIP_ERR_PREDICT; }
+        seen[slots[i]] = 1;
+        if (n_tokens[i] < 1) { snprintf(err, err_cap, "%s: n_tokens[%d] must be >= 1 (got %d)", fn, i, n_tokens[i]); return LLAMAHIP_ERR_PREDICT; }
+        if (n_past[i] < 0 || (int64_t) n_past[i] + n_tokens[i] > n_ctx) {
+            snprintf(err, err_cap, "%s: context overflow in segment %d: n_past (%d) + n_tokens (%d) > n_ctx (%d)", fn, i, n_past[i], n_tokens[i], n_ctx);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        R += n_tokens[i];
+    }
+    for (int64_t r = 0; r < R; r++)
+        if (tokens[r] < 0 || tokens[r] >= n_vocab) { snprintf(err, err_cap, "%s: token id %d at %lld out of range [0, %d)", fn, tokens[r], (long long) r, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: %lld rows in all, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+
+// what llamahip_op_attention_rows refuses of a caller's table: every entry inside its cache, and the rows of one slot one run of consecutive
+// positions in ascending row order whose key counts stay inside what the run appends (the masked tail of V*P reads those rows)
+int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys,
+                     char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_attention_rows";
+    if (!err) err_cap = 0;
+    if (R < 1 || R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: R (%d) outside 1 .. LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    if (n_ctx < 1 || n_slots < 1) { snprintf(err, err_cap, "%s: n_ctx (%d) and n_slots (%d) must be >= 1", fn, n_ctx, n_slots); return LLAMAHIP_ERR_PREDICT; }
+    if (!row_slot || !row_pos || !row_keys) { snprintf(err, err_cap, "%s: null row_slot, row_pos or row_keys", fn); return LLAMAHIP_ERR_PREDICT; }
+    std::vector<char> closed((size_t) n_slots, 0);
+    for (int32_t r = 0; r < R;) {
+        const int32_t s = row_slot[r];
+        if (s < 0 || s >= n_slots) { snprintf(err, err_cap, "%s: row_slot[%d] = %d out of range [0, %d)", fn, r, s, n_slots); return LLAMAHIP_ERR_PREDICT; }
+        if (closed[s]) { snprintf(err, err_cap, "%s: the rows of slot %d are not consecutive (row %d)", fn, s, r); return LLAMAHIP_ERR_PREDICT; }
+        closed[s] = 1;
+        int32_t e = r;
+        while (e < R && row_slot[e] == s) {
+            if (row_pos[e] < 0 || row_pos[e] >= n_ctx) { snprintf(err, err_cap, "%s: row_pos[%d] = %d out of range [0, n_ctx = %d)", fn, e, row_pos[e], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+            if (e > r && row_pos[e] != row_pos[e - 1] + 1) {
+                snprintf(err, err_cap, "%s: the rows of slot %d must be consecutive positions in ascending row order (row %d at %d follows %d)", fn, s, e, row_pos[e], row_pos[e - 1]);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+            e++;
+        }
+        const int32_t end = row_pos[e - 1] + 1;          // the run appends positions [row_pos[r], end)
+        for (int32_t q = r; q < e; q++)
+            if (row_keys[q] <= row_pos[q] || row_keys[q] > end || row_keys[q] > n_ctx) {
+                snprintf(err, err_cap, "%s: row_keys[%d] = %d outside (row_pos = %d, %d], the end of slot %d's rows (n_ctx %d)", fn, q, row_keys[q], row_pos[q], end, s, n_ctx);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+        r = e;
+    }
+    return 0;
+}
+
+}  // namespace lh
+
+extern "C" int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n_past, const int32_t *n_tokens, int32_t chunk_tokens,
+                                            int32_t *row_seg, int32_t *row_pos, int32_t *row_keys) {
+    if (n_ctx < 1 || n_seqs < 1 || !n_past || !n_tokens || chunk_tokens < 0) return -1;
+    int64_t R = 0;
+    for (int32_t i = 0; i < n_seqs; i++) {
+        if (n_tokens[i] < 1 || n_past[i] < 0 || (int64_t) n_past[i] + n_tokens[i] > n_ctx) return -1;
+        R += n_tokens[i];
+    }
+    if (R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) return -1;
+    int32_t r = 0;
+    for (int32_t i = 0; i < n_seqs; i++)
+        for (int32_t j = 0; j < n_tokens[i]; j++, r++) {
+            if (row_seg) row_seg[r] = i;
+            if (row_pos) row_pos[r] = n_past[i] + j;
+            if (row_keys) row_keys[r] = lh::split_keys_host(n_past[i], n_tokens[i], j, chunk_tokens);
+        }
+    return r;
+}

@@ -435,5 +435,47 @@ __device__ __forceinline__ float fold8(float acc) {
     return acc;
 }
 
+// ---- the soft_max . V tail shared by k_dec_pv_blk (decode.hip) and k_rows_pv (rows_attn.hip)
+// soft_max of one head's score row into LDS (p[0..T)): max, fp16-table exp, double sum, scale (ggml.c:5619-5665); every thread
+// of the workgroup calls it, the caller synchronizes before reading p
+static __device__ __forceinline__ void pv_soft_max(const float *__restrict__ row, float *p, int T, int tid, int nt, double *red,
+                                                   const uint16_t *__restrict__ T_exp, int lut_math) {
+    float mx = -INFINITY;
+    for (int t = tid; t < T; t += nt) { const float v = row[t]; p[t] = v; mx = fmaxf(mx, v); }
+    mx = block_max_f(mx, red, 0);
+    double sum = 0.0;
+    for (int t = tid; t < T; t += nt) {
+        const uint16_t xh = f2h_bits(p[t] - mx);
+        const float e = h2f_bits((lut_math & 2) ? exp_math_bits(xh) : T_exp[xh]);
+        p[t] = e;
+        sum += (double) e;
+    }
+    sum = block_sum_d(sum, red, 1);
+    const float inv = (float) (1.0 / sum);
+    for (int t = tid; t < T; t += nt) p[t] *= inv;
+}
+// the nth partial sums of 32 columns added in thread order, stored (fp32 row, if asked) and quantized to one Q4_0 activation
+// block of the QA layout; lanes 0..31 of the workgroup's first wave work
+static __device__ __forceinline__ void pv_store_block(const float *part, int nth, int tid, int col, int h, int dh, int cb,
+                                                      float *__restrict__ merged, uint32_t *__restrict__ qa_A, float *__restrict__ qa_d) {
+    if (tid < 32) {
+        float s = part[tid];
+        for (int th = 1; th < nth; th++) s += part[th * 32 + tid];          // thread order (ggml.c:5553-5577)
+        if (merged) merged[col] = s;
+        // quantize this 32-element block (ggml.c:456-523), one element per lane
+        float amax = fabsf(s);
+        amax = max_lanes_0_31(amax);
+        const float dd = amax / 7.0f;
+        const float id = (amax != 0.0f) ? 7.0f / amax : 0.0f;
+        const uint32_t nib = (uint32_t) ((int) __builtin_rintf(s * id)) & 0xF;
+        const int kk = tid & 7;
+        const uint32_t e0 = __shfl(nib, 2 * kk), e1 = __shfl(nib, 2 * kk + 1);
+        const uint32_t e2 = __shfl(nib, 16 + 2 * kk), e3 = __shfl(nib, 17 + 2 * kk);
+        const int b = h * (dh / 32) + cb, cc = b >> 3, j = b & 7;
+        if (tid < 8) qa_A[(cc * 8 + kk) * 8 + j] = (e0 | (e1 << 8) | (e2 << 16) | (e3 << 24)) << (4 * (j & 1));
+        if (tid == 0) qa_d[b] = dd;
+    }
+}
+
 
 }  // namespace lh

@@ -272,6 +272,11 @@ struct llamahip_model {
     SampleIo smp_h, smp_d;                         // host view / device view: tok [n_seq], n_last [n_seq], win [n_seq][1024], out [n_seq], spill [n_seq][V]
     void *smp_ws = nullptr;                        // SET_MAX * TOPK_WS_BYTES, zeroed once (the selection leaves it zeroed)
     int pipe_hand_off = 0;               // (front) llamahip_stats.hand_off
+    // llamahip_eval_multi (on the stages of a pipeline handle): the pass's row table, device resident -- RowTab [rows_cap] | the rows of the short
+    // segments [rows_cap] | the segments' last rows [n_seq] -- and the host copy it is uploaded from
+    char *d_rows = nullptr;
+    int rows_cap = 0;
+    std::vector<char> h_rows;
 
     ~llamahip_model();
 };
@@ -332,6 +337,7 @@ llamahip_model::~llamahip_model() {
     for (hipEvent_t e : mq_ev) (void) hipEventDestroy(e);
     if (smp_blk) { (void) hipHostFree(smp_blk); smp_blk = nullptr; }
     free_dev(smp_ws);
+    free_dev(d_rows);
     if (pipe_ev) (void) hipEventDestroy(pipe_ev);
     if (stream) (void) hipStreamDestroy(stream);
 }
@@ -910,6 +916,9 @@ int check_eval_args(llamahip_model *m, int n_past, const int32_t *tokens, int N,
 
 // what llamahip_decode_greedy refuses of a HANDLE, for the loops above the C ABI (ctx_overflow.cpp): no device is touched
 namespace lh {
+// eval_multi.cpp: what llamahip_eval_multi refuses of its arguments
+int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                     const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     if (!m->stages.empty()) return 0;
@@ -2311,6 +2320,186 @@ static int each_slot(llamahip_model *m, int32_t n, const int32_t *slots, char *e
         if ((rc = llamahip_set_seq(m, slots ? slots[i] : i, err, err_cap)) == 0) rc = fn(i);
     (void) llamahip_set_seq(m, save_seq, nullptr, 0);
     return rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The prompts of several sequences in one weight pass: llamahip_eval_multi (llamahip.h).  R rows cut into segments, one per KV
+// slot, each a multi-row eval of its own.  The mat-muls and the activation preparations run over all R rows as a single eval of R rows runs them
+// (launch_prep / launch_gemm, the kernel chosen by R: every exact kernel gives the same bits); the RoPE / KV append and the attention read each
+// row's {position, key split, cache offset} from a device-resident table (rows_attn.hip), built and validated here, uploaded once per pass and
+// stage on the stage's stream ahead of the first launch that reads it.  A segment of more than ATTN_SHORT_MAX rows keeps launch_attn on its own
+// rows and its slot's cache -- the launches its own eval takes -- and writes fp32 merged rows; the table launch then writes merged rows too and
+// one PREP_PLAIN over all R rows makes wo's operand.
+// ------------------------------------------------------------------------------------------------
+constexpr int EVAL_MULTI_LOOP_SEG_ROWS = 512, EVAL_MULTI_LOOP_ROWS = 1024;      // the measured rule of llamahip_eval_multi: see there
+struct RowsPass {
+    int n_seqs = 0, R = 0, chunk = 0, short_max = ATTN_SHORT_MAX;      // short_max: segments up to this many rows run in the table launch
+    const int32_t *slots = nullptr, *n_past = nullptr, *n_tokens = nullptr;
+    std::vector<int32_t> pos, keys, seg;          // llamahip_eval_multi_rows
+    int n_short_segs = 0, n_long_segs = 0, n_short_rows = 0, max_keys = 1;      // max_keys: the largest position + 1 among the short segments' rows
+};
+struct RowsDev { RowTab *tab; int32_t *short_idx, *last_idx; };
+static RowsDev rows_dev(llamahip_model *m) {
+    char *b = m->d_rows;
+    return { (RowTab *) b, (int32_t *) (b + (size_t) m->rows_cap * sizeof(RowTab)), (int32_t *) (b + (size_t) m->rows_cap * (sizeof(RowTab) + 4)) };
+}
+// the stage's table for this pass: built from the pass's rows with the stage's own cache stride, every entry checked against n_ctx and n_seq
+static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t err_cap) {
+    const size_t C = m->hp.n_ctx, d = m->hp.n_embd;
+    if (rp.R > m->rows_cap) {
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+        free_dev(m->d_rows); m->d_rows = nullptr; m->rows_cap = 0;
+        const int cap = std::max(rp.R, 64);
+        HIP_TRY(hipMalloc((void **) &m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4), LLAMAHIP_ERR_PREDICT);
+        m->rows_cap = cap;
+    }
+    const size_t cap = (size_t) m->rows_cap, bytes = cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4;
+    m->h_rows.assign(bytes, 0);
+    RowTab *tab = (RowTab *) m->h_rows.data();
+    int32_t *short_idx = (int32_t *) (m->h_rows.data() + cap * sizeof(RowTab)), *last_idx = short_idx + cap;
+    const long slot_stride = (long) (m->l1 - m->l0) * (long) C * (long) d;      // [seq][layer][n_ctx][d]
+    int ns = 0;
+    for (int r = 0; r < rp.R; r++) {
+        const int i = rp.seg[r], slot = rp.slots[i];
+        if (slot < 0 || slot >= m->n_seq || rp.pos[r] < 0 || rp.keys[r] <= rp.pos[r] || rp.keys[r] > (int) C || rp.keys[r] > rp.n_past[i] + rp.n_tokens[i]) {
+            set_err(err, err_cap, "llamahip_eval_multi: row %d of the table (slot %d, position %d, %d keys) is outside the cache (n_seq %d, n_ctx %d)", r, slot, rp.pos[r], rp.keys[r], m->n_seq, (int) C);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        tab[r] = { rp.pos[r], rp.keys[r], (long) slot * slot_stride };
+        if (rp.n_tokens[i] <= rp.short_max) short_idx[ns++] = r;
+        if (r + 1 == rp.R || rp.seg[r + 1] != i) last_idx[i] = r;
+    }
+    HIP_TRY(hipMemcpyAsync(m->d_rows, m->h_rows.data(), bytes, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
+// the pass on one handle's layers, enqueued on its stream (the multi-row branch of forward, with the table kernels where the rows' segments matter)
+static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, const float *hidden_in, char *err, size_t err_cap) {
+    const HParams &hp = m->hp;
+    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab, R = rp.R;
+    const int nth = std::max(1, std::min(n_threads, 64));
+    hipStream_t st = m->stream;
+    int rc = rows_upload(m, rp, err, err_cap);
+    if (rc) return rc;
+    const RowsDev rd = rows_dev(m);
+    if (m->first_stage) HIP_TRY(launch_embed(m->d_tokens, m->tok_emb, m->x, d, R, st), LLAMAHIP_ERR_PREDICT);
+    else HIP_TRY(hipMemcpyAsync(m->x, hidden_in, (size_t) R * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
+    for (int il = m->l0; il < m->l1; il++) {
+        const Layer &L = m->layers[il - m->l0];
+        float *K0 = m->Kc + (size_t) (il - m->l0) * C * d, *V0 = m->Vc + (size_t) (il - m->l0) * C * d;      // slot 0's cache of this layer: the table's offsets start here
+        HIP_TRY(launch_prep(PREP_NORM, m->x, L.attention_norm, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, R, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_rope_kv_rows(m->qkv, 3L * d, d, dh, m->sincos, m->qr, K0, V0, rd.tab, R, st), LLAMAHIP_ERR_PREDICT);
+        if (rp.n_long_segs == 0) {
+            // every segment short: one launch pair for all rows, quantizing the merged rows straight into wo's operand
+            HIP_TRY(launch_attn_rows(m->qr, K0, V0, m->attn_ws.S, m->attn_ws.NB, nullptr, 0, m->qa_A, m->qa_d, rd.tab, nullptr, R, rp.max_keys, d, H, C, nth, m->T_exp, st), LLAMAHIP_ERR_PREDICT);
+        } else {
+            if (rp.n_short_rows > 0)
+                HIP_TRY(launch_attn_rows(m->qr, K0, V0, m->attn_ws.S, m->attn_ws.NB, m->merged, d, m->qa_A, m->qa_d, rd.tab, rd.short_idx, rp.n_short_rows, rp.max_keys, d, H, C, nth, m->T_exp, st), LLAMAHIP_ERR_PREDICT);
+            for (int i = 0, r0 = 0; i < rp.n_seqs; r0 += rp.n_tokens[i], i++) {
+                if (rp.n_tokens[i] <= rp.short_max) continue;
+                const size_t off = (size_t) rp.slots[i] * (m->l1 - m->l0) * C * d;
+                HIP_TRY(launch_attn(m->qr + (size_t) r0 * d, K0 + off, V0 + off, m->merged + (size_t) r0 * d, nullptr, nullptr, rp.n_past[i], rp.n_tokens[i], d, H, nth, m->T_exp, &m->attn_ws, st, rp.chunk), LLAMAHIP_ERR_PREDICT);
+            }
+            HIP_TRY(launch_prep(PREP_PLAIN, m->merged, nullptr, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        }
+        HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, R, m->x1, d, m->x, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, R, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_prep(PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, R, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+    }
+    if (m->last_stage) {
+        // the segments' last rows side by side (x1 is free here), the final norm and the lm head over those n_seqs rows: logits rows 0 .. n_seqs - 1
+        HIP_TRY(launch_gather_rows(m->x, rd.last_idx, rp.n_seqs, d, m->x1, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, rp.n_seqs, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        QMat out = m->output;
+        out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr;          // (the decode tiles, as llamahip_eval's lm head)
+        HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, rp.n_seqs, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
+    }
+    m->last_rows.clear();          // (m->logits rewritten)
+    return 0;
+}
+
+// one stage of the pass: its workspaces, the tokens (first stage), the launches -- enqueued, not waited for
+static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass &rp, const int32_t *tokens, const float *hidden_in, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+    int rc;
+    if ((rc = ensure_workspace(st, rp.R, err, err_cap)) != 0) return rc;
+    if ((rc = ensure_attn_ws(st, 2, err, err_cap)) != 0) return rc;
+    if ((rc = ensure_prompt_copies(st, rp.R, err, err_cap)) != 0) return rc;
+    if (st->first_stage) HIP_TRY(hipMemcpyAsync(st->d_tokens, tokens, (size_t) rp.R * 4, hipMemcpyHostToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
+    return forward_rows(st, n_threads, rp, hidden_in, err, err_cap);
+}
+
+int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                        const int32_t *n_tokens, int32_t chunk_tokens, float *logits_out, llamahip_eval_multi_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_multi";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = eval_multi_check(m->hp.n_ctx, m->hp.n_vocab, m->n_seq, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, err, err_cap);
+    if (rc) return rc;
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *last = stages[S - 1];
+    const size_t d = m->hp.n_embd, V = m->hp.n_vocab;
+    const int dh = m->hp.n_embd / m->hp.n_head;
+    RowsPass rp;
+    rp.n_seqs = n_seqs; rp.chunk = chunk_tokens; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens;
+    for (int i = 0; i < n_seqs; i++) rp.R += n_tokens[i];
+    llamahip_eval_multi_stats out = {};
+    out.struct_size = (int32_t) sizeof(out);
+    out.n_rows = rp.R;
+    auto report = [&]() { if (stats) { const int32_t n = std::min((size_t) std::max(stats->struct_size, 0), sizeof(out)); if (n >= 4) { out.struct_size = n; memcpy(stats, &out, (size_t) n); } } };
+    const bool dense = stages[0]->dense;
+    // The per-slot loop of the contract itself: f16 / f32 / Q4_1 files, fast-prefill handles (their GEMM choice depends on the row count), one
+    // segment (llamahip_eval_chunks is that pass), head sizes the table kernels do not take.
+    // ... and the one shape family where the pass measured slower than the loop by more than the loop's spread (profiles/eval_multi_probe_7b.json:
+    // 4 x 512 rows 0.98 x, 2 x 512 rows 1.02 x): more than 1024 rows in segments of 512 rows or more each -- evals that long no longer wait for weights.
+    bool all_huge = rp.R > EVAL_MULTI_LOOP_ROWS;
+    for (int i = 0; i < n_seqs; i++) all_huge = all_huge && n_tokens[i] >= EVAL_MULTI_LOOP_SEG_ROWS;
+    if (dense || (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) || n_seqs == 1 || dh % 32 != 0 || dh > 256 || all_huge) {
+        for (int i = 0; i < n_seqs; i++)
+            out.n_passes += (dense && chunk_tokens > 0 && n_tokens[i] > chunk_tokens) ? (n_tokens[i] + chunk_tokens - 1) / chunk_tokens : 1;      // (llamahip_eval_chunks on such a file: one eval per chunk)
+        std::vector<size_t> at((size_t) n_seqs, 0);
+        for (int i = 1; i < n_seqs; i++) at[i] = at[i - 1] + (size_t) n_tokens[i - 1];
+        rc = each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
+            float *lo = logits_out ? logits_out + (size_t) i * V : nullptr;
+            return chunk_tokens > 0 ? llamahip_eval_chunks(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], chunk_tokens, lo, err, err_cap)
+                                    : llamahip_eval(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], lo, err, err_cap); });
+        if (rc == 0) report();
+        return rc;
+    }
+    // (measurement only, tools/eval_multi_probe.py --short-max: segments of up to that many rows join the table launch instead of taking launch_attn)
+    static const int env_short_max = getenv("LLAMAHIP_EVAL_MULTI_SHORT_MAX") ? atoi(getenv("LLAMAHIP_EVAL_MULTI_SHORT_MAX")) : 0;
+    if (env_short_max > 0) rp.short_max = env_short_max;
+    const double t0 = now_ms();
+    rp.pos.resize((size_t) rp.R); rp.keys.resize((size_t) rp.R); rp.seg.resize((size_t) rp.R);
+    if (llamahip_eval_multi_rows(m->hp.n_ctx, n_seqs, n_past, n_tokens, chunk_tokens, rp.seg.data(), rp.pos.data(), rp.keys.data()) != rp.R) {
+        set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    for (int i = 0; i < n_seqs; i++) {
+        if (n_tokens[i] > rp.short_max) { rp.n_long_segs++; continue; }
+        rp.n_short_segs++; rp.n_short_rows += n_tokens[i];
+        rp.max_keys = std::max(rp.max_keys, n_past[i] + n_tokens[i]);
+    }
+    out.n_passes = 1; out.n_short_segs = rp.n_short_segs; out.n_long_segs = rp.n_long_segs;
+    out.attn_groups = (rp.n_short_segs > 0 ? 1 : 0) + rp.n_long_segs;
+    for (int s = 1; s < S; s++) if ((rc = pipe_ensure_in(stages[s], rp.R, err, err_cap)) != 0) return rc;
+    for (int s = 0; s < S && rc == 0; s++) {
+        llamahip_model *st = stages[s];
+        rc = rows_stage_enqueue(st, n_threads, rp, tokens, s ? st->pipe_in : nullptr, err, err_cap);
+        if (rc == 0 && s + 1 < S) rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) rp.R * d * 4, err, err_cap);
+    }
+    // (the bounded wait first, the copy of the logits rows behind it: pipe_eval)
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    if (logits_out) HIP_TRY(hipMemcpy(logits_out, last->logits, (size_t) n_seqs * V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    m->last_rows.clear();
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    report();
+    return LLAMAHIP_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

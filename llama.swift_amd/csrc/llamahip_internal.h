@@ -245,6 +245,16 @@ hipError_t launch_attn_short(const float *qr, const float *Kc, const float *Vc, 
                              const uint16_t *T_exp, hipStream_t st, int chunk = 0, const SeqSet *set = nullptr,      // set: N independent single-row evals (batched decode step)
                              int set_keys = 0,                                                                    // ... whose positions are all < set_keys (0: n_ctx): bounds the score grid
                              long merged_stride = 0);                                                             // floats between merged rows (0: d)
+// The rows of a pass over SEVERAL KV slots (rows_attn.hip; llamahip_eval_multi, llamahip_op_attention_rows): row r is at position pos of the cache
+// kv_off elements behind slot 0's (SeqSet::kv_off's meaning) and splits `keys` keys over the threads in V*P (prompt_attn.hip split_keys of the
+// eval the row stands for).  Built and validated on the host (eval_multi.cpp), device resident, uploaded once per pass.
+struct RowTab { int32_t pos, keys; long kv_off; };
+hipError_t launch_rope_kv_rows(const float *qkv, long qkv_stride, int d, int dh, const double *tab, float *qr, float *Kc, float *Vc,
+                               const RowTab *rows, int R, hipStream_t st);
+hipError_t launch_attn_rows(const float *qr, const float *Kc, const float *Vc, float *sc, int sc_rows, float *merged, long merged_stride,
+                            uint32_t *qa_A, float *qa_d, const RowTab *rows, const int32_t *idx /* may be null */, int n_rows, int max_keys,
+                            int d, int H, int n_ctx, int nth, const uint16_t *T_exp, hipStream_t st);
+hipError_t launch_gather_rows(const float *x, const int32_t *idx, int n, int d, float *out, hipStream_t st);      // out row i = x row idx[i]
 // batched decode step: embedding rows / residual rows in and out / greedy picks of the set's rows
 // (the step's FIRST launch -- embed, or rows with gather -- also writes set->pos and, given the epoch word, opens the step's epoch)
 hipError_t launch_embed_set(SeqSet *set, int n, const uint8_t *emb, float *x, int d, hipStream_t st, uint32_t *epoch = nullptr);

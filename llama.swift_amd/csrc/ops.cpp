@@ -13,6 +13,10 @@ using namespace lh;
 static_assert(LLAMAHIP_PREP_PLAIN == PREP_PLAIN && LLAMAHIP_PREP_NORM == PREP_NORM && LLAMAHIP_PREP_SILU_MUL == PREP_SILU_MUL, "llamahip.h mirrors the prep modes");
 static_assert(LLAMAHIP_PREP_KERNEL_AUTO == PREP_FORCE_AUTO && LLAMAHIP_PREP_KERNEL_FAST == PREP_FORCE_FAST && LLAMAHIP_PREP_KERNEL_LDS == PREP_FORCE_LDS, "... and launch_prep's force values");
 
+namespace lh {      // eval_multi.cpp
+int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, char *err, size_t err_cap);
+}
+
 extern "C" {
 
 int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N,
@@ -216,6 +220,61 @@ int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int
     // (DEC: one row at offset 0; SHORT: rows Kp / 4 dwords and Kp / 32 scales apart)
     if (quant && wo_operand) qa_to_q4_0_blocks(qa.data(), qd.data(), N, d, (uint8_t *) wo_operand);
     if (path_taken) *path_taken = run;
+    return LLAMAHIP_OK;
+}
+
+// the attention of llamahip_eval_multi's pass on caller-supplied rows, caches and row table (per-op tests of rows_attn.hip): see llamahip.h
+int llamahip_op_attention_rows(const float *qkv, int32_t R, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
+                               const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, int32_t n_threads,
+                               float *merged, int32_t merged_stride, void *wo_operand, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_attention_rows";
+    if (!qkv || !Kc || !Vc || d < 1 || H < 1 || d % H != 0) { set_err(err, err_cap, "%s: bad arguments (qkv, Kc, Vc not NULL; d %d a multiple of H %d)", fn, d, H); return LLAMAHIP_ERR_PREDICT; }
+    const int dh = d / H, nth = n_threads;
+    if (dh % 32 != 0 || dh > 256) { set_err(err, err_cap, "%s: head size %d: multiples of 32 up to 256", fn, dh); return LLAMAHIP_ERR_PREDICT; }
+    if (nth < 1 || nth > 64) { set_err(err, err_cap, "%s: n_threads %d outside 1 .. 64 (the model's clamp)", fn, nth); return LLAMAHIP_ERR_PREDICT; }
+    if (merged && merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (rows_table_check(R, n_ctx, n_slots, row_slot, row_pos, row_keys, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    std::vector<RowTab> tab_h((size_t) R);
+    int max_keys = 1;
+    for (int r = 0; r < R; r++) {
+        tab_h[r] = { row_pos[r], row_keys[r], (long) row_slot[r] * n_ctx * d };
+        max_keys = std::max(max_keys, row_pos[r] + 1);
+    }
+    const int Kp = (d + 255) / 256 * 256, sc_rows = 16;      // (a scratch of 16 rows: 29 and 64 rows walk it in batches)
+    const size_t cache_b = (size_t) n_slots * n_ctx * d * 4, ms = merged ? (size_t) merged_stride : (size_t) d, mbytes = (size_t) R * ms * 4;
+    const size_t qaA_b = (size_t) R * Kp, qad_b = (size_t) R * (Kp / 32) * 4, sc_b = (size_t) sc_rows * H * n_ctx * 4;
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_qr = s.alloc<float>((size_t) R * d), *d_m = s.alloc<float>(mbytes / 4), *d_qad = s.alloc<float>(qad_b / 4), *d_sc = s.alloc<float>(sc_b / 4);
+    uint32_t *d_qaA = s.alloc<uint32_t>(qaA_b / 4);
+    // the op's own workspace, every byte NaN (0xFF): a read of something the launches did not write shows in the result
+    s.fill(d_sc, 0xFF, sc_b); s.fill(d_qr, 0xFF, (size_t) R * d * 4); s.fill(d_qaA, 0xFF, qaA_b); s.fill(d_qad, 0xFF, qad_b);
+    if (!merged) s.fill(d_m, 0xFF, mbytes);
+    float *d_qkv = s.alloc((size_t) R * 3 * d, qkv), *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    if (merged) s.upload(d_m, merged, mbytes);
+    uint16_t *d_ts = s.alloc(ts.size(), ts.data()), *d_te = s.alloc(te.size(), te.data());
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    RowTab *d_rows = s.alloc(tab_h.size(), tab_h.data());
+    if (s.ok()) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    if (s.ok()) s.check(launch_rope_kv_rows(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, d_rows, R, st));
+    if (s.ok()) s.check(launch_attn_rows(d_qr, d_K, d_V, d_sc, sc_rows, merged ? d_m : nullptr, (long) ms, d_qaA, d_qad, d_rows, nullptr, R, max_keys, d, H, n_ctx, nth, d_te, st));
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    if (merged) s.download(merged, d_m, mbytes);
+    std::vector<uint32_t> qa(qaA_b / 4);
+    std::vector<float> qd(qad_b / 4);
+    if (wo_operand) {
+        s.download(qa.data(), d_qaA, qaA_b);
+        s.download(qd.data(), d_qad, qad_b);
+    }
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (wo_operand) qa_to_q4_0_blocks(qa.data(), qd.data(), R, d, (uint8_t *) wo_operand);
     return LLAMAHIP_OK;
 }
 

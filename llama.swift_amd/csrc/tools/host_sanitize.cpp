@@ -6,6 +6,7 @@
 // shard merging through read_tensor, llamahip_tokenize, llamahip_sample_top_p_top_k / _from_candidates, and the
 // bridge's failure path, and -- with evals that succeed on made-up logits -- the driver's whole control flow (prompt taken at once,
 // chunk-exact pass + last chunk, one eval per generated token, event counts).  usage: host_sanitize <model file> [n_parts]   (exit code 0 = clean)
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -81,6 +82,10 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t, int32_t np, int32_t first
 }
 }
 namespace lh {
+// eval_multi.cpp (compiled in as it is): what llamahip_eval_multi refuses of its arguments / llamahip_op_attention_rows of a caller's table
+int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                     const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap);
+int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
@@ -313,6 +318,54 @@ int main(int argc, char **argv) {
         int32_t w[2] = { 1, 16 }, g[2] = { 0, 0 };
         EXPECT(llamahip_lookup_deal_rows(w, 2, 16, g) == -1 && llamahip_lookup_deal_rows(w, 1, 0, g) == -1 && llamahip_lookup_deal_rows(w, 17, 16, g) == -1);
         EXPECT(llamahip_lookup_deal_rows(nullptr, 1, 16, g) == -1 && llamahip_lookup_deal_rows(w, 1, 16, nullptr) == -1 && llamahip_lookup_deal_rows(w, 1, 17, g) == -1);
+    }
+    // the row table of llamahip_eval_multi: exactly sized arrays over a grid of segment shapes, each entry against the rule restated; the
+    // argument checks and the op's table check on exactly sized arrays, accepted and refused
+    for (int C : { 64, 128 })
+        for (int n = 1; n <= 5; n++)
+            for (int chunk : { 0, 1, 9 })
+                for (int it = 0; it < 6; it++) {
+                    static const int lens[6] = { 1, 2, 9, 10, 18, 61 }, pasts[3] = { 0, 3, 37 };
+                    std::vector<int32_t> np((size_t) n), nt((size_t) n), slots((size_t) n);
+                    int R = 0;
+                    bool fits = true;
+                    for (int i = 0; i < n; i++) { np[i] = pasts[(it + i) % 3]; nt[i] = lens[(it * 5 + i) % 6]; slots[i] = n - 1 - i; R += nt[i]; fits = fits && np[i] + nt[i] <= C; }
+                    std::vector<int32_t> seg((size_t) R), pos((size_t) R), keys((size_t) R), toks((size_t) R, 1);
+                    const int32_t got = llamahip_eval_multi_rows(C, n, np.data(), nt.data(), chunk, seg.data(), pos.data(), keys.data());
+                    EXPECT(got == (fits ? R : -1));
+                    EXPECT(llamahip_eval_multi_rows(C, n, np.data(), nt.data(), chunk, nullptr, nullptr, nullptr) == got);
+                    EXPECT((lh::eval_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), chunk, err, sizeof(err)) == 0) == fits);
+                    if (!fits) continue;
+                    int r = 0;
+                    for (int i = 0; i < n; i++)
+                        for (int j = 0; j < nt[i]; j++, r++) {
+                            const int want = chunk > 0 ? np[i] + std::min(nt[i], (j / chunk + 1) * chunk) : np[i] + nt[i];
+                            EXPECT(seg[r] == i && pos[r] == np[i] + j && keys[r] == want);
+                        }
+                    std::vector<int32_t> rslot((size_t) R);
+                    for (int q = 0; q < R; q++) rslot[q] = slots[seg[q]];
+                    EXPECT(lh::rows_table_check(R, C, n, rslot.data(), pos.data(), keys.data(), err, sizeof(err)) == 0);
+                    EXPECT(lh::rows_table_check(R, C, n, rslot.data(), pos.data(), keys.data(), nullptr, 0) == 0);
+                    keys[R - 1] += 1;                                                                                    // past the end of the slot's rows
+                    EXPECT(lh::rows_table_check(R, C, n, rslot.data(), pos.data(), keys.data(), err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                    keys[R - 1] = pos[R - 1];                                                                            // no key of its own
+                    EXPECT(lh::rows_table_check(R, C, n, rslot.data(), pos.data(), keys.data(), err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                    keys[R - 1] = pos[R - 1] + 1;
+                    rslot[R - 1] = n;                                                                                    // slot out of range
+                    EXPECT(lh::rows_table_check(R, C, n, rslot.data(), pos.data(), keys.data(), err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                    rslot[R - 1] = slots[seg[R - 1]];
+                    if (n > 1) { slots[n - 1] = slots[0]; EXPECT(lh::eval_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), chunk, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT); slots[n - 1] = 0; }
+                    toks[R - 1] = V;
+                    EXPECT(lh::eval_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), chunk, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                    toks[R - 1] = 1;
+                    EXPECT(lh::eval_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), -1, nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+                    EXPECT(lh::eval_multi_check(C, V, n - 1, n, slots.data(), np.data(), toks.data(), nt.data(), chunk, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                }
+    {
+        const int32_t np1[1] = { 0 }, big[1] = { LLAMAHIP_EVAL_MULTI_MAX_ROWS + 1 }, zero[1] = { 0 }, neg[1] = { -1 };
+        EXPECT(llamahip_eval_multi_rows(4096, 1, np1, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, zero, 0, nullptr, nullptr, nullptr) == -1);
+        EXPECT(llamahip_eval_multi_rows(64, 1, neg, np1, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 0, np1, np1, 0, nullptr, nullptr, nullptr) == -1);
+        EXPECT(llamahip_eval_multi_rows(64, 1, nullptr, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, big, -1, nullptr, nullptr, nullptr) == -1);
     }
     printf("host_sanitize: %zu tensor bytes merged, tokenizer + sampler + bridge failure path exercised: %s\n", total, failures ? "FAILED" : "clean");
     return failures ? 1 : 0;
