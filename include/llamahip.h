@@ -120,7 +120,10 @@ int llamahip_eval(llamahip_model *m, int32_t n_threads, int32_t n_past,
  * what ceil(n_tokens / chunk_tokens) successive llamahip_eval calls of chunk_tokens tokens (the last one shorter) leave behind:
  * every operator of llama_eval's graph works row by row except the V*P key split, which depends on the eval a row belongs to
  * (ggml.c:5459-5480) and is applied per row.  One pass over all rows runs the matrix-core GEMMs instead of 9-row ones
- * (about 4x the tokens/s of the chunk-by-chunk loop on a 500-token prompt).  n_tokens <= chunk_tokens: llamahip_eval. */
+ * (about 4x the tokens/s of the chunk-by-chunk loop on a 500-token prompt).  n_tokens <= chunk_tokens: llamahip_eval.
+ * f16 / f32 files take the one pass from 36 tokens (an 8-layer f16 file of 7B width, chunks of 9: 36 tokens 6.5 -> 4.9 ms, 504 tokens
+ * 97 -> 24 ms; 18 tokens are 3.3 ms in the loop and 3.6 in one pass: DESIGN.md 12.18), on plain and in-process pipeline handles;
+ * shorter calls on such files, and Q4_1 files, run the evals themselves one after the other.  The bits are the same either way. */
 int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past,
                          const int32_t *tokens, int32_t n_tokens, int32_t chunk_tokens, float *logits_out,
                          char *err, size_t err_cap);
@@ -657,13 +660,20 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
  * values in file layout, K a positive multiple of 32; x [N][K]; resid [N][M] or NULL; y [N][y_stride], y_stride >= M: the WHOLE buffer is
  * copied to the device before the launch and back after it, so columns M .. y_stride - 1 keep what the caller put there unless a kernel
  * writes out of place.  path: LLAMAHIP_DENSE_AUTO -- what a model handle picks (one row _MV, 2 .. 16 rows _SET or _MM by the measured rule of
- * DESIGN.md 12.16, more _MM); _MV k_dense_mv, the decode mat-vec, one launch per row; _MM k_dense_mm (any N: the weights are streamed once
- * per 8 rows); _SET k_dense_set (N 1 .. 16: the weights streamed once).  Refusals name their limit and happen before any device is touched.
- * *path_taken (may be NULL): the path that ran. */
+ * DESIGN.md 12.16, more _MFMA or _MM by the measured rule of DESIGN.md 12.18); _MV k_dense_mv, the decode mat-vec, one launch per row; _MM
+ * k_dense_mm (any N: the weights are streamed once per 8 rows); _SET k_dense_set (N 1 .. 16: the weights streamed once); _MFMA k_dense_mfma (N
+ * > 16, K a multiple of 128: the 32 chains of every output on the fp32 matrix cores, the weights streamed once per 64 rows, the same bits).
+ * LLaMA-7B matrices of an 8-layer f16 file, us per launch, k_dense_mm -> k_dense_mfma (wq|wk|wv, wo, w1|w3, w2, lm head;
+ * profiles/dense_mfma_probe.json): 17 rows 88 / 41 / 152 / 95 / 206 -> 108 / 36 / 161 / 89 / 215; 32 rows 103 / 46 / 185 / 103 / 266 -> 108 / 36 /
+ * 161 / 90 / 214; 64 rows 192 / 86 / 343 / 207 / 514 -> 117 / 39 / 174 / 100 / 231; 512 rows 1416 / 489 / 2499 / 1254 / 3899 -> 690 / 234 /
+ * 1256 / 604 / 1820 (74 TF of the instruction's 155): AUTO takes _MFMA from 64 rows, where it wins on all five.
+ * Refusals name their limit and happen before any device is touched (_MFMA with N <= 16 is refused as an unknown path: it is a path of
+ * longer evals only).  *path_taken (may be NULL): the path that ran. */
 #define LLAMAHIP_DENSE_AUTO 0
 #define LLAMAHIP_DENSE_MV   1
 #define LLAMAHIP_DENSE_MM   2
 #define LLAMAHIP_DENSE_SET  3
+#define LLAMAHIP_DENSE_MFMA 4
 int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                               float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
@@ -775,6 +785,18 @@ int32_t llamahip_debug_dense_paths(int64_t *out, int32_t cap);
  * row and LDS slab, static LDS bytes }.  Returns 1, 0 where the kernel does not take the shape (K not a multiple of 32, n_rows outside
  * 1 .. 16, another wtype), -1 where the plan names an instance that was never compiled. */
 int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]);
+/* Host only: the launch plan of k_dense_mfma for an M x K matrix of wtype (0 fp32, 1 fp16) and n_rows activation rows --
+ * out = { workgroups, threads per workgroup, activation rows per workgroup tile, weight rows per workgroup tile, dynamic LDS bytes,
+ * 1 where LLAMAHIP_DENSE_AUTO picks the kernel for this shape else 0 }.  Returns 1, 0 where the kernel does not take the shape (n_rows <= 16,
+ * K not a multiple of 128, another wtype, n_rows * k >= 2^31), -1 where the plan names an instance that was never compiled. */
+int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]);
+/* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
+int64_t llamahip_debug_dense_mfma_launches(void);
+/* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more
+ * than 16 rows that a model handle (or LLAMAHIP_DENSE_AUTO) launches goes to that kernel where the kernel takes the shape, and to the rule's
+ * choice where it does not.  LLAMAHIP_DENSE_MM=mm / mfma in the environment does the same.  Returns the previous value, -1 for another path
+ * (nothing changes).  Not synchronised with evals in flight on other threads. */
+int32_t llamahip_debug_dense_force(int32_t path);
 /* Host-only (no device needed): the attention path (LLAMAHIP_ATTN_SHORT / _MFMA / _ROW) a model's multi-row eval of N rows after n_past
  * takes once its workspace exists (allocated with the first multi-row eval), or -1 for N < 2 -- the rule llamahip_op_attention's AUTO runs. */
 int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx);

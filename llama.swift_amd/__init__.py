@@ -26,6 +26,9 @@ from .binding import (  # noqa: F401
     declared_symbols,
     dense_paths,
     dense_set_plan,
+    dense_mfma_plan,
+    dense_mfma_launches,
+    dense_force,
     eval_multi_rows,
     gemm_paths,
     lib,

@@ -184,6 +184,12 @@ def lib() -> C.CDLL:
     L.llamahip_debug_dense_paths.restype = i32
     L.llamahip_debug_dense_set_plan.argtypes = [i32, i32, i32, i32, vp]
     L.llamahip_debug_dense_set_plan.restype = i32
+    L.llamahip_debug_dense_mfma_plan.argtypes = [i32, i32, i32, i32, vp]
+    L.llamahip_debug_dense_mfma_plan.restype = i32
+    L.llamahip_debug_dense_mfma_launches.argtypes = []
+    L.llamahip_debug_dense_mfma_launches.restype = C.c_int64
+    L.llamahip_debug_dense_force.argtypes = [i32]
+    L.llamahip_debug_dense_force.restype = i32
     _lib = L
     return L
 
@@ -234,6 +240,32 @@ def dense_set_plan(m: int, k: int, wtype: int, n_rows: int):
     if rc < 0:
         raise LlamaHipError(rc, f"dense_set_plan({m}, {k}, wtype={wtype}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
     return dict(zip(("grid", "threads", "rows_per_half_wave", "rows", "slab_groups", "lds_bytes"), (int(x) for x in a))) if rc else None
+
+
+def dense_mfma_plan(m: int, k: int, wtype: int, n_rows: int):
+    """Host-only: the launch plan of the matrix-core f16 / f32 mat-mul k_dense_mfma (llamahip_debug_dense_mfma_plan) for n_rows rows against
+    an m x k matrix of wtype (0 fp32, 1 fp16): a dict, or None where the kernel does not take the shape; a plan that names an instance that
+    does not exist is an error."""
+    a = np.zeros(6, np.int64)
+    rc = lib().llamahip_debug_dense_mfma_plan(m, k, wtype, n_rows, a.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise LlamaHipError(rc, f"dense_mfma_plan({m}, {k}, wtype={wtype}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
+    return dict(zip(("grid", "threads", "tile_rows", "tile_cols", "lds_bytes", "auto"), (int(x) for x in a))) if rc else None
+
+
+def dense_mfma_launches() -> int:
+    """Launches of k_dense_mfma since process start (llamahip_debug_dense_mfma_launches)."""
+    return int(lib().llamahip_debug_dense_mfma_launches())
+
+
+def dense_force(path=0) -> str:
+    """Process-wide: send every f16 / f32 mat-mul of more than 16 rows of a model handle to "mm" or "mfma" (where the kernel takes the shape);
+    0 / "auto": the measured rule again (llamahip_debug_dense_force).  Returns the previous setting as a name of DENSE_PATHS."""
+    code = DENSE_PATHS.index(path) if path in DENSE_PATHS else int(path)
+    prev = lib().llamahip_debug_dense_force(code)
+    if prev < 0:
+        raise ValueError(f"dense_force({path!r}): 0 / 'auto', 'mm' or 'mfma'")
+    return DENSE_PATHS[prev]
 
 
 def version() -> str:
@@ -984,7 +1016,7 @@ def op_prompt_gemm_q4_0(wq: np.ndarray, x: np.ndarray, resid=None, path: str = "
     return y, GEMM_PATHS[taken.value]
 
 
-DENSE_PATHS = ("auto", "mv", "mm", "set")      # LLAMAHIP_DENSE_* of llamahip.h, in order
+DENSE_PATHS = ("auto", "mv", "mm", "set", "mfma")      # LLAMAHIP_DENSE_* of llamahip.h, in order
 
 
 def op_mul_mat_dense(w: np.ndarray, x: np.ndarray, resid=None, path: str = "auto", y_stride: int | None = None, y_init=None, wtype: int | None = None):

@@ -2521,6 +2521,7 @@ hipError_t init_kernel_attrs() {
     if ((e = init_attrs_decode()) != hipSuccess) return e;
     if ((e = init_attrs_gemv_set()) != hipSuccess) return e;
     if ((e = init_attrs_rows_attn()) != hipSuccess) return e;
+    if ((e = init_attrs_dense()) != hipSuccess) return e;
     return init_attrs_prompt_attn();
 }
 

@@ -12,9 +12,10 @@
 // One half-wave (32 lanes = the 32 chains) owns RG weight rows x NC activation rows; the fold is the
 // xor butterfly 8, 16, 4, 1, 2 (the reference's tree; float add commutes).  Weights and activations are kept
 // in a chain-major order (perm_index) so that a lane's loads are 16 / 32 bytes wide.
-// Three mat-mul kernels share that arithmetic: k_dense_mv (one row, software-pipelined), k_dense_set (2 .. 16 rows -- a set step's rows, the
-// 9-token prompt evals -- the weights streamed once, the rows shared through LDS) and k_dense_mm (any row count, 8 rows per pass over the
-// weights); launch_dense_mm picks.
+// Four mat-mul kernels share that arithmetic: k_dense_mv (one row, software-pipelined), k_dense_set (2 .. 16 rows -- a set step's rows, the
+// 9-token prompt evals -- the weights streamed once, the rows shared through LDS), k_dense_mm (any row count, 8 rows per pass over the
+// weights) and k_dense_mfma (more than 16 rows: the chains on the fp32 matrix cores, 64 rows per pass); launch_dense_mm picks (DESIGN.md
+// 12.16, 12.18).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -495,6 +496,166 @@ k_dense_set(const void *__restrict__ wv, int M, int K, const float *__restrict__
         }
 }
 
+// More than 16 activation rows, on the fp32 matrix cores.  v_mfma_f32_16x16x4_f32 is bit for bit the k-ordered chain
+// fma(a3, b3, fma(a2, b2, fma(a1, b1, fma(a0, b0, C)))) per output (prompt_attn.hip), so with A = four consecutive steps of chain c of 16
+// activation rows and B = the same steps of 16 weight rows, ONE accumulator tile per chain advances exactly as acc = fmaf(w, x, acc) does in
+// the kernels above: 32 tiles = 128 registers per wave, all 32 chains of an output in one lane (D register r of lane (j, q): activation
+// row 4 q + r, weight row j), the fold 31 in-lane adds in the butterfly's tree, no cross-lane traffic.  Consecutive MFMAs go to different
+// chains, so the instruction's dependent latency is covered by the wave itself.
+// A workgroup is 4 waves, one per SIMD = 64 activation rows x 16 MT weight rows (wave: its 16 activation rows against MT tiles of 16 weight
+// rows, the A operand read once for them; MT = 2: 256 accumulator registers of the wave's 512): a weight byte is fetched once per 64
+// activation rows.  Operands reach the MFMA lanes through LDS, a group of 256 elements per row at a time, in the permuted order
+// as it is in memory (chain c's 8 steps at c * 8), weights widened on the way in: lane (i, kk) reads dword row * 260 + c * 8 + 4 h + kk.  Rows
+// are 260 dwords apart: 16 rows x 4 steps fall on 64 distinct banks (256 apart they would share four).  One LDS buffer (two of 96 rows do
+// not fit 160 KB), the next group's global loads in flight in registers while this one is consumed; two barriers per group.  No branch
+// surrounds a load: the prefetch past the last group, rows past N and weight rows past M are clamped re-reads that are never stored; a
+// wave whose tile lies wholly outside skips the arithmetic, not the barriers.  K % 256 == 128 ends in a 4-step group (chain c's steps at
+// c * 4: one MFMA per chain); other K are refused (dense_mfma_plan) -- a padded step would have to leave -0.0 sums alone.
+//   grid (ceil(M / (16 MT)), ceil(N / 64)), block 256 threads, dynamic LDS (64 + 16 MT) * 260 * 4 bytes
+typedef float f32x4m __attribute__((ext_vector_type(4)));
+constexpr int MF_TN = 64, MF_LD = 260;
+template <int WT> __device__ __forceinline__ void mf_store_widened(float *dst, const WVec8<WT> &q);
+template <> __device__ __forceinline__ void mf_store_widened<1>(float *dst, const WVec8<1> &q) {
+    const uint32_t u[4] = { q.v.x, q.v.y, q.v.z, q.v.w };
+    *(df4 *) dst = df4{ h2f((uint16_t) u[0]), h2f((uint16_t) (u[0] >> 16)), h2f((uint16_t) u[1]), h2f((uint16_t) (u[1] >> 16)) };
+    *(df4 *) (dst + 4) = df4{ h2f((uint16_t) u[2]), h2f((uint16_t) (u[2] >> 16)), h2f((uint16_t) u[3]), h2f((uint16_t) (u[3] >> 16)) };
+}
+template <> __device__ __forceinline__ void mf_store_widened<0>(float *dst, const WVec8<0> &q) {
+    *(df4 *) dst = q.a;
+    *(df4 *) (dst + 4) = q.b;
+}
+template <int WT, int EPI, int MT>
+__global__ void __launch_bounds__(256)
+k_dense_mfma(const void *__restrict__ wv, int M, int K, const float *__restrict__ xp, int N,
+             float *__restrict__ y, long y_stride, const float *__restrict__ resid, long resid_stride) {
+    typedef typename WElem<WT>::T T;
+    constexpr int NT = 256, WROWS = 16 * MT;
+    constexpr int XG = MF_TN * 64 / NT;                    // 16-byte granules of the activation rows' group staged per thread
+    constexpr int WC = WROWS * 32 / NT;                    // 8-element chunks of the weight rows' group staged per thread
+    extern __shared__ __attribute__((aligned(16))) float mf_lds[];
+    float *xs = mf_lds, *ws = mf_lds + MF_TN * MF_LD;
+    const T *w = (const T *) wv;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nt = wave;
+    const int m0 = blockIdx.x * WROWS, n0 = blockIdx.y * MF_TN;
+    const int ng = K >> 8;
+    // granule j of this thread: row (tid >> 6) + j * (NT / 64), elements 4 (tid & 63) .. + 3 of the group
+    uint32_t xoff[XG];
+    int xdst[XG];
+#pragma unroll
+    for (int j = 0; j < XG; j++) {
+        const int row = (tid >> 6) + j * (NT / 64), q = tid & 63;
+        xoff[j] = (uint32_t) min(n0 + row, N - 1) * (uint32_t) K + q * 4;
+        xdst[j] = row * MF_LD + q * 4;
+    }
+    const T *wsrc[WC];
+    int wdst[WC];
+#pragma unroll
+    for (int j = 0; j < WC; j++) {
+        const int row = (tid >> 5) + j * (NT / 32), c = tid & 31;
+        wsrc[j] = w + (size_t) min(m0 + row, M - 1) * K + c * 8;
+        wdst[j] = row * MF_LD + c * 8;
+    }
+    f32x4m acc[MT][32];
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+        for (int c = 0; c < 32; c++) acc[t][c] = f32x4m{ 0.0f, 0.0f, 0.0f, 0.0f };
+    const bool live = n0 + nt * 16 < N;                    // wave-uniform
+    const float *ap = xs + (nt * 16 + (lane & 15)) * MF_LD + (lane >> 4);
+    const float *bp = ws + (lane & 15) * MF_LD + (lane >> 4);
+    df4 xst[XG];
+    WVec8<WT> wst[WC];
+#define LD_LOADG(G)                                                                                \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < XG; j++) xst[j] = *(const df4 *) (xp + xoff[j] + (size_t) (G) * 256);      \
+    _Pragma("unroll")                                                                              \
+    for (int j = 0; j < WC; j++) wst[j].load(wsrc[j] + (size_t) (G) * 256);
+    if (ng) {
+        LD_LOADG(0)
+        for (int g = 0; g < ng; g++) {
+#pragma unroll
+            for (int j = 0; j < XG; j++) *(df4 *) (xs + xdst[j]) = xst[j];
+#pragma unroll
+            for (int j = 0; j < WC; j++) mf_store_widened<WT>(ws + wdst[j], wst[j]);
+            __syncthreads();
+            LD_LOADG(min(g + 1, ng - 1))
+            __builtin_amdgcn_sched_barrier(0);             // the next group goes out BEFORE this one is consumed
+            if (live) {
+                // eight batches of 8 chains (half h = batch >> 2), the next batch's LDS reads issued before this one's MFMAs: left to itself
+                // the compiler requests a whole half first and spills
+                float af[2][8], bf[2][MT][8];
+#define LD_READB(B, Q)                                                                             \
+    _Pragma("unroll")                                                                              \
+    for (int i = 0; i < 8; i++) {                                                                  \
+        const int o = (((Q) & 3) * 8 + i) * 8 + 4 * ((Q) >> 2);                                    \
+        af[B][i] = ap[o];                                                                          \
+        _Pragma("unroll")                                                                          \
+        for (int t = 0; t < MT; t++) bf[B][t][i] = bp[t * 16 * MF_LD + o];                         \
+    }
+                LD_READB(0, 0)
+#pragma unroll
+                for (int q = 0; q < 8; q++) {
+                    if (q + 1 < 8) { LD_READB((q + 1) & 1, q + 1) }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 8; i++)
+#pragma unroll
+                        for (int t = 0; t < MT; t++)
+                            acc[t][(q & 3) * 8 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q & 1][i], bf[q & 1][t][i], acc[t][(q & 3) * 8 + i], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+#undef LD_READB
+            }
+            __syncthreads();
+        }
+    }
+#undef LD_LOADG
+    if (K & 255) {                                         // the 4-step tail group (K % 256 == 128), un-pipelined
+        const size_t at = (size_t) ng * 256;
+        for (int i = tid; i < MF_TN * 32; i += NT) {
+            const int row = i >> 5, q = i & 31;
+            *(df4 *) (xs + row * MF_LD + q * 4) = *(const df4 *) (xp + (size_t) min(n0 + row, N - 1) * K + at + q * 4);
+        }
+        for (int i = tid; i < WROWS * 32; i += NT) {
+            const int row = i >> 5, c = i & 31;
+            const T *p = w + (size_t) min(m0 + row, M - 1) * K + at + c * 4;
+            *(df4 *) (ws + row * MF_LD + c * 4) = df4{ WElem<WT>::widen(p[0]), WElem<WT>::widen(p[1]), WElem<WT>::widen(p[2]), WElem<WT>::widen(p[3]) };
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll
+            for (int c = 0; c < 32; c++) {
+                const float a = ap[c * 4];
+#pragma unroll
+                for (int t = 0; t < MT; t++) acc[t][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, bp[t * 16 * MF_LD + c * 4], acc[t][c], 0, 0, 0);
+            }
+        }
+    }
+    if (!live) return;
+#pragma unroll
+    for (int t = 0; t < MT; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int m = m0 + t * 16 + (lane & 15);
+        // k_dense_mm's butterfly as lane 0 sees it: partners ^8, ^16, ^4, ^1, ^2
+        float a[32], b[8], c4[4];
+#pragma unroll
+        for (int i = 0; i < 8; i++) { a[i] = acc[t][i][r] + acc[t][i + 8][r]; a[16 + i] = acc[t][16 + i][r] + acc[t][24 + i][r]; }
+#pragma unroll
+        for (int i = 0; i < 8; i++) b[i] = a[i] + a[16 + i];
+#pragma unroll
+        for (int i = 0; i < 4; i++) c4[i] = b[i] + b[i + 4];
+        const float d0 = c4[0] + c4[1], d2 = c4[2] + c4[3];
+        float s = d0 + d2;
+        const int n = n0 + nt * 16 + (lane >> 4) * 4 + r;
+        if (n < N && m < M) {
+            if (EPI == EPI_RESID) s = s + resid[(size_t) n * resid_stride + m];
+            y[(size_t) n * y_stride + m] = s;
+        }
+    }
+}
+
 template <int WT>
 __global__ void k_embed_dense(const int32_t *__restrict__ tokens, const void *__restrict__ emb, float *__restrict__ x, int d) {
     typedef typename WElem<WT>::T T;
@@ -586,6 +747,17 @@ hipError_t go(const DMat &w, int epi, const float *x, long x_stride, int N, floa
         if (!p.nr || !dense_set_plan_has_kernel(p)) return hipErrorInvalidValue;
         g_dense_path_counts[DENSE_COUNT_SET]++;
         return go_set_rows<WT>(p, w, N, y, y_stride, epi == EPI_RESID ? resid : nullptr, resid_stride, st, scratch);
+    }
+    if (path == DENSE_PATH_MFMA) {
+        const DenseMfmaPlan p = dense_mfma_plan(w.M, w.K, WT, N);
+        if (!p.ok || !dense_mfma_plan_has_kernel(p)) return hipErrorInvalidValue;
+        g_dense_mfma_launches++;
+        const dim3 grid(p.grid_x, p.grid_y), block(p.threads);
+#define LD_MFMA(E, MTV) hipLaunchKernelGGL((k_dense_mfma<WT, E, MTV>), grid, block, p.lds, st, w.w, w.M, w.K, scratch, N, y, y_stride, resid, resid_stride)
+        if (p.tile_cols == 32) { if (epi == EPI_RESID) LD_MFMA(EPI_RESID, 2); else LD_MFMA(EPI_STORE, 2); }
+        else                   { if (epi == EPI_RESID) LD_MFMA(EPI_RESID, 1); else LD_MFMA(EPI_STORE, 1); }
+#undef LD_MFMA
+        return hipGetLastError();
     }
     g_dense_path_counts[DENSE_COUNT_MM]++;
     const dim3 grid((w.M + 8 * RG - 1) / (8 * RG), (N + NC - 1) / NC);
@@ -770,14 +942,57 @@ bool dense_set_plan_has_kernel(const DenseSetPlan &p) {
     return p.nr >= 2 && p.nr <= 16 && p.nr % 2 == 0 && p.hw == 8 && (p.rg == RG || p.rg == 2);      // go_set_rows / go_set
 }
 
-// AUTO for 2 .. 16 rows: k_dense_set for the row counts at which it was not slower than k_dense_mm<WT, 8> on any of the five 7B
-// matrices; LLAMAHIP_DENSE_MM=set / mm sends every such row count to one kernel (measurement, tests)
-static int dense_auto_path(int N) {
-    static const int env = [] { const char *e = getenv("LLAMAHIP_DENSE_MM"); return !e ? 0 : !strcmp(e, "set") ? DENSE_PATH_SET : !strcmp(e, "mm") ? DENSE_PATH_MM : 0; }();
+// The launch plan of k_dense_mfma, the one place that derives it.  The kernel takes more than 16 rows (fewer are k_dense_mv / k_dense_set's),
+// K a multiple of 128 (whole groups of 256 plus at most one 4-step group) and operands it can index with 32 bits.  Workgroups of 64 activation
+// rows x 32 weight rows (two accumulator tiles per wave) where that still gives every CU one, else x 16 weight rows: a 4096-row matrix
+// against 64 rows would be 128 workgroups on 256 CUs.
+long g_dense_mfma_launches = 0;
+int g_dense_force = 0;
+DenseMfmaPlan dense_mfma_plan(int M, int K, int wtype, int N) {
+    DenseMfmaPlan p = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    if (M < 1 || K < DENSE_MFMA_K_UNIT || K % DENSE_MFMA_K_UNIT != 0 || (wtype != 0 && wtype != 1) || N <= DENSE_SET_MAX_ROWS) return p;
+    if ((long) N * K >= (1L << 31) || (N + MF_TN - 1) / MF_TN > 65535) return p;
+    p.ok = 1;
+    p.tile_rows = MF_TN;
+    p.grid_y = (N + MF_TN - 1) / MF_TN;
+    p.tile_cols = (long) ((M + 31) / 32) * p.grid_y >= 256 ? 32 : 16;
+    p.grid_x = (M + p.tile_cols - 1) / p.tile_cols;
+    p.threads = 256;
+    p.lds = (p.tile_rows + p.tile_cols) * MF_LD * 4;
+    p.auto_pick = N >= DENSE_MFMA_AUTO_MIN_ROWS;
+    return p;
+}
+bool dense_mfma_plan_has_kernel(const DenseMfmaPlan &p) {
+    return p.ok && p.tile_rows == MF_TN && (p.tile_cols == 16 || p.tile_cols == 32) && p.threads == 256;      // go's LD_MFMA
+}
+
+// AUTO.  2 .. 16 rows: k_dense_set for the row counts at which it was not slower than k_dense_mm<WT, 8> on any of the five 7B
+// matrices; more rows: k_dense_mfma where it takes the shape and from the row count at which it beat k_dense_mm on all
+// five, else k_dense_mm.  LLAMAHIP_DENSE_MM=set / mm / mfma, or llamahip_debug_dense_force for more than 16 rows, sends
+// every such row count to one kernel where that kernel takes the shape (measurement, tests)
+static int dense_auto_path(int M, int K, int wtype, int N) {
+    static const int env = [] {
+        const char *e = getenv("LLAMAHIP_DENSE_MM");
+        return !e ? 0 : !strcmp(e, "set") ? DENSE_PATH_SET : !strcmp(e, "mm") ? DENSE_PATH_MM : !strcmp(e, "mfma") ? DENSE_PATH_MFMA : 0;
+    }();
     if (N == 1) return DENSE_PATH_MV;
-    if (N > DENSE_SET_MAX_ROWS) return DENSE_PATH_MM;
-    if (env) return env;
+    if (N > DENSE_SET_MAX_ROWS) {
+        const int force = g_dense_force ? g_dense_force : env == DENSE_PATH_SET ? 0 : env;
+        if (force == DENSE_PATH_MM) return DENSE_PATH_MM;
+        const DenseMfmaPlan p = dense_mfma_plan(M, K, wtype, N);
+        return p.ok && (force == DENSE_PATH_MFMA || p.auto_pick) ? DENSE_PATH_MFMA : DENSE_PATH_MM;
+    }
+    if (env == DENSE_PATH_SET || env == DENSE_PATH_MM) return env;
     return DENSE_PATH_SET;
+}
+
+hipError_t init_attrs_dense() {
+    const int cap = 160 * 1024;          // k_dense_mfma's operand tile is 83 / 100 KB of dynamic LDS
+#define LH_ATTR(KERNEL) do { hipError_t e_ = hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, cap); if (e_ != hipSuccess) return e_; } while (0)
+    LH_ATTR((k_dense_mfma<0, EPI_STORE, 1>)); LH_ATTR((k_dense_mfma<0, EPI_RESID, 1>)); LH_ATTR((k_dense_mfma<0, EPI_STORE, 2>)); LH_ATTR((k_dense_mfma<0, EPI_RESID, 2>));
+    LH_ATTR((k_dense_mfma<1, EPI_STORE, 1>)); LH_ATTR((k_dense_mfma<1, EPI_RESID, 1>)); LH_ATTR((k_dense_mfma<1, EPI_STORE, 2>)); LH_ATTR((k_dense_mfma<1, EPI_RESID, 2>));
+#undef LH_ATTR
+    return hipSuccess;
 }
 
 hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
@@ -793,8 +1008,9 @@ hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride
         return hipGetLastError();
     }
     if (w.K % 32 != 0 || (w.wtype != 0 && w.wtype != 1) || !scratch) return hipErrorInvalidValue;
-    if (N < 1 || path < DENSE_PATH_AUTO || path > DENSE_PATH_SET || (path == DENSE_PATH_SET && N > DENSE_SET_MAX_ROWS)) return hipErrorInvalidValue;
-    const int run = path == DENSE_PATH_AUTO ? dense_auto_path(N) : path;
+    if (N < 1 || path < DENSE_PATH_AUTO || path > DENSE_PATH_MFMA || (path == DENSE_PATH_SET && N > DENSE_SET_MAX_ROWS)) return hipErrorInvalidValue;
+    if (path == DENSE_PATH_MFMA && !dense_mfma_plan(w.M, w.K, w.wtype, N).ok) return hipErrorInvalidValue;
+    const int run = path == DENSE_PATH_AUTO ? dense_auto_path(w.M, w.K, w.wtype, N) : path;
     if (path_taken) *path_taken = run;
     if (w.wtype == 1) return go<1, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch, run);
     return go<0, 8>(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch, run);

@@ -600,8 +600,10 @@ static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int m
 // f16 / f32 model files: the same graph with dense mat-muls (dense.hip).  Un-fused:
 // norm -> fp32 activations -> dense mat-mul; RoPE, KV cache and attention are the Q4_0 path's kernels.
 // (io, single-row steps: the token word and the {position, step} words of a stage step -- llamahip_stage_step on a whole-model handle)
+// chunk > 0: the rows are the evals of `chunk` tokens of llamahip_eval_chunks in one pass -- norm, RoPE and the mat-muls work row by row, the
+// attention splits every row's keys as its own eval would (launch_attn)
 int forward_dense(llamahip_model *m, int n_threads, int n_past, int N, const float *hidden_in, bool want_all,
-                  bool state_on_device, char *err, size_t err_cap, const StepIO *io = nullptr) {
+                  bool state_on_device, char *err, size_t err_cap, const StepIO *io = nullptr, int chunk = 0) {
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
     const int nth = std::max(1, std::min(n_threads, 64));
@@ -632,7 +634,7 @@ int forward_dense(llamahip_model *m, int n_threads, int n_past, int N, const flo
             HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);                             // .mm:586-611
-            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st), LLAMAHIP_ERR_PREDICT); // .mm:614-646
+            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, chunk), LLAMAHIP_ERR_PREDICT); // .mm:614-646
         }
         HIP_TRY(prep_mm(L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->x1, d, m->x, d), LLAMAHIP_ERR_PREDICT);                          // .mm:649-654
         HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
@@ -674,7 +676,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
     const bool debug = dump_layer >= 0 && sink;
     if (m->dense) {
         if (debug) { set_err(err, err_cap, "per-layer dumps are available for Q4_0 models only"); return LLAMAHIP_ERR_PREDICT; }
-        return forward_dense(m, n_threads, n_past, N, hidden_in, want_all, state_on_device && N == 1, err, err_cap, N == 1 ? io : nullptr);
+        return forward_dense(m, n_threads, n_past, N, hidden_in, want_all, state_on_device && N == 1, err, err_cap, N == 1 ? io : nullptr, chunk);
     }
     const bool fused = (N == 1) && !debug && !(m->flags & LLAMAHIP_FLAG_UNFUSED);
     const bool fast_prefill = (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) != 0 && !debug;      // opt-in re-associated prompt GEMM (llamahip.h)
@@ -1260,14 +1262,21 @@ int llamahip_eval(llamahip_model *m, int32_t n_threads, int32_t n_past,
 // The reference feeds a prompt to llama_eval n_batch + 1 = 9 tokens at a time (.mm:880-888).  One pass over all the rows gives the
 // same bits -- every operator of the graph works row by row except the V*P key split, which depends on the eval a row belongs to
 // (prompt_attn.hip split_keys) and is applied per row here -- at the speed of a long eval (matrix-core GEMMs) instead of 9-row ones.
-int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
-                         int32_t chunk_tokens, float *logits_out, char *err, size_t err_cap) {
+// f16 / f32 files take the one pass from DENSE_ONE_PASS_MIN_ROWS rows (below it the chunk loop on k_dense_set measured no slower: DESIGN.md
+// 12.18); Q4_1 files (one slow kernel, correct first) keep the loop.  A pipeline handle's front is loaded HOST_ONLY and never learns the file
+// type: its stages know it.
+static bool chunks_in_one_pass(const llamahip_model *m, int n_tokens) {
+    if (m->host_only && m->stages.empty()) return false;
+    const llamahip_model *s0 = m->stages.empty() ? m : m->stages[0];
+    if (!s0->dense) return true;
+    return s0->hp.f16 != 3 && n_tokens >= DENSE_ONE_PASS_MIN_ROWS;
+}
+// (one_pass = false: llamahip_eval_multi's per-slot loop on f16 / f32 files, which reports the evals it made)
+static int eval_chunks_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                            int32_t chunk_tokens, float *logits_out, bool one_pass, char *err, size_t err_cap) {
     if (chunk_tokens < 1) { set_err(err, err_cap, "llamahip_eval_chunks: chunk_tokens must be >= 1"); return LLAMAHIP_ERR_PREDICT; }
     if (!m || n_tokens <= chunk_tokens) return llamahip_eval(m, n_threads, n_past, tokens, n_tokens, logits_out, err, err_cap);
-    // f16 / f32 / Q4_1 model files: the evals themselves, one after the other (a pipeline handle's front is loaded HOST_ONLY and never
-    // learns the file type: its stages know it)
-    const bool dense = m->stages.empty() ? m->dense : m->stages[0]->dense;
-    if ((m->host_only && m->stages.empty()) || dense) {
+    if (!one_pass || !chunks_in_one_pass(m, n_tokens)) {
         for (int32_t c0 = 0; c0 < n_tokens; c0 += chunk_tokens) {
             const int32_t n = std::min(chunk_tokens, n_tokens - c0);
             const int rc = llamahip_eval(m, n_threads, n_past + c0, tokens + c0, n, c0 + n == n_tokens ? logits_out : nullptr, err, err_cap);
@@ -1276,6 +1285,10 @@ int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past, c
         return LLAMAHIP_OK;
     }
     return eval_impl(m, n_threads, n_past, tokens, n_tokens, logits_out, nullptr, -1, nullptr, 0, nullptr, true, err, err_cap, chunk_tokens);
+}
+int llamahip_eval_chunks(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                         int32_t chunk_tokens, float *logits_out, char *err, size_t err_cap) {
+    return eval_chunks_impl(m, n_threads, n_past, tokens, n_tokens, chunk_tokens, logits_out, true, err, err_cap);
 }
 
 // llamahip_eval + the candidate selection of llama_sample_top_p_top_k on the device (utils.cpp:345-395): 816 bytes come
@@ -2068,7 +2081,7 @@ static int pipe_eval(llamahip_model *m, int32_t n_threads, int32_t n_past, const
     for (int s = 0; s < S; s++) {
         llamahip_model *st = m->stages[s];
         st->cur_seq = m->cur_seq;
-        if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, st->dense ? 0 : chunk, false, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, chunk, false, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
     }
     // (the bounded wait first, the copy of the logits row behind it: a device-to-host copy into the caller's pageable buffer blocks inside the
@@ -2134,7 +2147,7 @@ static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, cons
         for (int s = 0; s < S; s++) {
             llamahip_model *st = m->stages[s];
             st->cur_seq = m->cur_seq;
-            if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, st->dense ? 0 : chunk, s == S - 1, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+            if ((rc = eval_stage_enqueue(st, n_threads, n_past, tokens, N, s ? st->pipe_in : nullptr, chunk, s == S - 1, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
             if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         }
         last = m->stages[S - 1];
@@ -2150,12 +2163,12 @@ static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, cons
     return LLAMAHIP_OK;
 }
 
-// llamahip_eval_chunks' split: f16 / f32 / Q4_1 files evaluate chunk by chunk (each chunk's rows scored), Q4_0 files in one pass
+// llamahip_eval_chunks' split: Q4_0 files in one pass, f16 / f32 files too from DENSE_ONE_PASS_MIN_ROWS rows, else (and Q4_1 files) chunk by
+// chunk, each chunk's rows scored
 static int logprobs_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int32_t chunk_tokens,
                          const int32_t *targets, double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap) {
     const bool chunked = chunk_tokens > 0 && N > chunk_tokens;
-    const bool dense = m->stages.empty() ? m->dense : m->stages[0]->dense;
-    if (!chunked || !dense) return eval_score(m, n_threads, n_past, tokens, N, chunked ? chunk_tokens : 0, targets, lp, am, rk, logits_last, err, err_cap);
+    if (!chunked || chunks_in_one_pass(m, N)) return eval_score(m, n_threads, n_past, tokens, N, chunked ? chunk_tokens : 0, targets, lp, am, rk, logits_last, err, err_cap);
     for (int32_t c0 = 0; c0 < N; c0 += chunk_tokens) {
         const int32_t n = std::min(chunk_tokens, N - c0);
         const int rc = eval_score(m, n_threads, n_past + c0, tokens + c0, n, 0, targets + c0, lp ? lp + c0 : nullptr, am ? am + c0 : nullptr,
@@ -2465,7 +2478,7 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
         for (int i = 1; i < n_seqs; i++) at[i] = at[i - 1] + (size_t) n_tokens[i - 1];
         rc = each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
             float *lo = logits_out ? logits_out + (size_t) i * V : nullptr;
-            return chunk_tokens > 0 ? llamahip_eval_chunks(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], chunk_tokens, lo, err, err_cap)
+            return chunk_tokens > 0 ? eval_chunks_impl(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], chunk_tokens, lo, !dense, err, err_cap)
                                     : llamahip_eval(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], lo, err, err_cap); });
         if (rc == 0) report();
         return rc;
@@ -3853,6 +3866,24 @@ int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32
     const int64_t o[6] = { p.grid, p.hw * 32, p.rg, p.nr, p.slab, p.lds };
     for (int i = 0; i < 6; i++) out[i] = o[i];
     return dense_set_plan_has_kernel(p) ? 1 : -1;
+}
+
+int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
+    if (!out) return 0;
+    const DenseMfmaPlan p = dense_mfma_plan(m, k, wtype, n_rows);
+    if (!p.ok) return 0;
+    const int64_t o[6] = { (int64_t) p.grid_x * p.grid_y, p.threads, p.tile_rows, p.tile_cols, p.lds, p.auto_pick };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return dense_mfma_plan_has_kernel(p) ? 1 : -1;
+}
+
+int64_t llamahip_debug_dense_mfma_launches(void) { return g_dense_mfma_launches; }
+
+int32_t llamahip_debug_dense_force(int32_t path) {
+    if (path != 0 && path != LLAMAHIP_DENSE_MM && path != LLAMAHIP_DENSE_MFMA) return -1;
+    const int32_t prev = g_dense_force;
+    g_dense_force = path;
+    return prev;
 }
 
 int llamahip_get_stats(const llamahip_model *m, llamahip_stats *out) {

@@ -72,8 +72,9 @@ struct DMat {
 };
 // The f16 / f32 mat-mul kernels (dense.hip), = LLAMAHIP_DENSE_* of llamahip.h: k_dense_mv (one row; forced with more rows: one launch per row),
 // k_dense_mm (any row count, the rows on gridDim.y: the weights are streamed once per 8 rows), k_dense_set (1 .. 16 rows, the weights streamed
-// once).  AUTO: one row MV, 2 .. 16 rows by dense_auto_path (dense.hip), more MM.  Q4_1 has one kernel and ignores the path.
-enum { DENSE_PATH_AUTO = 0, DENSE_PATH_MV = 1, DENSE_PATH_MM = 2, DENSE_PATH_SET = 3 };
+// once), k_dense_mfma (more than 16 rows, K a multiple of 128: the chains on the fp32 matrix cores, the weights streamed once per 64 rows).
+// AUTO: one row MV, more by dense_auto_path (dense.hip).  Q4_1 has one kernel and ignores the path.
+enum { DENSE_PATH_AUTO = 0, DENSE_PATH_MV = 1, DENSE_PATH_MM = 2, DENSE_PATH_SET = 3, DENSE_PATH_MFMA = 4 };
 enum { DENSE_COUNT_MV = 0, DENSE_COUNT_MM = 1, DENSE_COUNT_SET = 2, DENSE_COUNT_N = 3 };
 extern long g_dense_path_counts[DENSE_COUNT_N];      // launches per kernel (process-wide; tests)
 constexpr int DENSE_SET_MAX_ROWS = 16;
@@ -82,6 +83,17 @@ constexpr int DENSE_SET_MAX_ROWS = 16;
 struct DenseSetPlan { int nr, hw, rg, grid, slab, lds; };
 DenseSetPlan dense_set_plan(int M, int K, int wtype, int N);
 bool dense_set_plan_has_kernel(const DenseSetPlan &p);
+// k_dense_mfma's launch plan: ok = the kernel takes the shape; grid (grid_x, grid_y) workgroups of `threads`, each tile_rows activation rows x
+// tile_cols weight rows; lds = dynamic LDS bytes; auto_pick = AUTO takes the kernel at this row count (the measured rule)
+struct DenseMfmaPlan { int ok, grid_x, grid_y, threads, tile_rows, tile_cols, lds, auto_pick; };
+constexpr int DENSE_MFMA_K_UNIT = 128;               // K: whole groups of 256 elements plus at most one 4-step group
+constexpr int DENSE_MFMA_AUTO_MIN_ROWS = 64;             // AUTO: k_dense_mfma from this many rows
+constexpr int DENSE_ONE_PASS_MIN_ROWS = 36;          // llamahip_eval_chunks / _eval_logprobs on f16 / f32 files: one pass from this many rows
+DenseMfmaPlan dense_mfma_plan(int M, int K, int wtype, int N);
+bool dense_mfma_plan_has_kernel(const DenseMfmaPlan &p);
+extern long g_dense_mfma_launches;                   // launches of k_dense_mfma (process-wide; tests)
+extern int g_dense_force;                            // llamahip_debug_dense_force: 0, DENSE_PATH_MM or DENSE_PATH_MFMA for more than 16 rows
+hipError_t init_attrs_dense();
 // scratch: N * K floats (the permuted / rounded activation operand; Q4_1: the expanded one)
 hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
                            const float *resid, long resid_stride, hipStream_t st, float *scratch = nullptr,

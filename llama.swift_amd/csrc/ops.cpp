@@ -100,7 +100,7 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
     return LLAMAHIP_OK;
 }
 
-static_assert(LLAMAHIP_DENSE_AUTO == DENSE_PATH_AUTO && LLAMAHIP_DENSE_MV == DENSE_PATH_MV && LLAMAHIP_DENSE_MM == DENSE_PATH_MM && LLAMAHIP_DENSE_SET == DENSE_PATH_SET, "llamahip.h mirrors the dense mat-mul paths");
+static_assert(LLAMAHIP_DENSE_AUTO == DENSE_PATH_AUTO && LLAMAHIP_DENSE_MV == DENSE_PATH_MV && LLAMAHIP_DENSE_MM == DENSE_PATH_MM && LLAMAHIP_DENSE_SET == DENSE_PATH_SET && LLAMAHIP_DENSE_MFMA == DENSE_PATH_MFMA, "llamahip.h mirrors the dense mat-mul paths");
 
 // one f16 / f32 mat-mul kernel on caller-supplied operands (per-op tests of every kernel launch_dense_mm can pick): see llamahip.h
 int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
@@ -108,11 +108,20 @@ int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K
     static const char *fn = "llamahip_op_mul_mat_dense";
     if (wtype != 0 && wtype != 1) { set_err(err, err_cap, "%s: wtype %d: 0 (fp32) or 1 (fp16) weights", fn, wtype); return LLAMAHIP_ERR_PREDICT; }
     if (K < 32 || K % 32 != 0) { set_err(err, err_cap, "%s: K %d must be a positive multiple of 32", fn, K); return LLAMAHIP_ERR_PREDICT; }
-    if (path < LLAMAHIP_DENSE_AUTO || path > LLAMAHIP_DENSE_SET) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_DENSE_AUTO || path > LLAMAHIP_DENSE_MFMA) { set_err(err, err_cap, "%s: unknown path %d", fn, path); return LLAMAHIP_ERR_PREDICT; }
     if (N < 1) { set_err(err, err_cap, "%s: N %d must be >= 1", fn, N); return LLAMAHIP_ERR_PREDICT; }
     if (path == LLAMAHIP_DENSE_SET && N > DENSE_SET_MAX_ROWS) { set_err(err, err_cap, "%s: path SET takes N 1 .. %d rows (got %d)", fn, DENSE_SET_MAX_ROWS, N); return LLAMAHIP_ERR_PREDICT; }
     if (y_stride < M) { set_err(err, err_cap, "%s: y_stride %d < M %d", fn, y_stride, M); return LLAMAHIP_ERR_PREDICT; }
     if (!w || !x || !y || M < 1) { set_err(err, err_cap, "%s: bad arguments (w, x, y not NULL; M %d >= 1)", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    // (up to 16 rows the paths are AUTO .. SET, as before the matrix-core kernel existed: it is a path of longer evals only)
+    if (path == LLAMAHIP_DENSE_MFMA && N <= DENSE_SET_MAX_ROWS) {
+        set_err(err, err_cap, "%s: unknown path %d for N %d rows: path MFMA takes N > %d rows", fn, path, N, DENSE_SET_MAX_ROWS);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (path == LLAMAHIP_DENSE_MFMA && !dense_mfma_plan(M, K, wtype, N).ok) {
+        set_err(err, err_cap, "%s: path MFMA takes N > %d rows, K a multiple of %d and N * K < 2^31 (got N %d, K %d)", fn, DENSE_SET_MAX_ROWS, DENSE_MFMA_K_UNIT, N, K);
+        return LLAMAHIP_ERR_PREDICT;
+    }
     if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
     DMat dm;
     dm.M = M; dm.K = K; dm.wtype = wtype;

@@ -3,9 +3,15 @@
 finishes in seconds): per-layer time extrapolates to the 32-layer model.
 usage: dense_probe.py [n_layer]
        dense_probe.py [n_layer] --multi [--json OUT] [--repeats R] [--seqs 1,2,4,8,16] [--only-multi]
+       dense_probe.py [n_layer] --prompt [--json OUT] [--repeats R] [--ftype f16|f32] [--force mm|mfma] [--evals 64,128,512]
+                      [--chunks 18,36,72,144,504] [--trace-rows 17,32,64,128,512]
 --multi (default 8 layers: 3.2 GB, larger than the Infinity Cache): ms per step and aggregate tokens/s of decode_greedy_multi for S sequences
 from position 256 for 64 steps, the 9-token eval, and the single-stream greedy loop; every figure is the wall time of a call that
 synchronises before it returns, after one untimed run of the same call (graph captures, first-touch allocations), R repeats each.
+--prompt (default 8 layers): ms per call of eval of --evals rows and of eval_chunks(chunk 9) of --chunks tokens, the single-stream greedy loop and
+the 16-sequence set step, timed the same way; --force sends every mat-mul of more than 16 rows to one kernel (dense_force).  --trace-rows:
+nothing is timed -- per row count one untimed and R further eval_logprobs calls (the lm head over every row too) and exit, for a
+rocprofv3 --kernel-trace run that tools/dense_trace_summary.py reads.
 LLAMAHIP_LIB / LLAMAHIP_DENSE_MM select the library / the mat-mul of 2 .. 16 rows as usual; the model file is kept for the next run."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,18 +22,62 @@ import llama_swift_amd as L
 
 args = sys.argv[1:]
 multi = "--multi" in args
+prompt_mode = "--prompt" in args
 opt = lambda k, d: args[args.index(k) + 1] if k in args else d
-nl = int(args[0]) if args and args[0].isdigit() else (8 if multi else 4)
+nl = int(args[0]) if args and args[0].isdigit() else (8 if multi or prompt_mode else 4)
+ftype = opt("--ftype", "f16")
 hp = synth.HParams(n_vocab=32000, n_embd=4096, n_mult=256, n_head=32, n_layer=nl)
-path = f"/tmp/dense7b_f16_{nl}.bin" if multi else "/tmp/dense7b_f16.bin"
+path = f"/tmp/dense7b_{ftype}_{nl}.bin" if multi or prompt_mode else "/tmp/dense7b_f16.bin"
 rng = np.random.default_rng(1)
-if not (multi and os.path.exists(path)):
+if not ((multi or prompt_mode) and os.path.exists(path)):
     t = {}
     for name, shape in synth.tensor_specs(hp):
         t[name] = (1.0 + 0.1 * rng.standard_normal(shape, dtype=np.float32)) if len(shape) == 1 else (0.02 * rng.standard_normal(shape, dtype=np.float32))
-    synth.write_model_unquantized(path, hp, t, 1)
+    synth.write_model_unquantized(path, hp, t, 0 if ftype == "f32" else 1)
     del t
 prompt = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 255)]).astype(np.int32)
+
+if prompt_mode:
+    R = int(opt("--repeats", "3"))
+    ints = lambda k, d: [int(x) for x in opt(k, d).split(",") if x]
+    force = opt("--force", "")
+    if force:
+        L.dense_force(force)
+    stream = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 511)]).astype(np.int32)
+    m = L.Model(path, n_ctx=512, n_seq=16)
+
+    def timed(fn):
+        fn()
+        out = []
+        for _ in range(R):
+            t0 = time.perf_counter(); fn(); out.append(round((time.perf_counter() - t0) * 1e3, 4))
+        return out
+    res = {"library": os.path.basename(L.LIB_PATH), "force": force, "ftype": ftype, "n_layer": nl, "file_gb": round(os.path.getsize(path) / 1e9, 2)}
+    if "--trace-rows" in args:
+        for n in ints("--trace-rows", ""):
+            for _ in range(1 + R):
+                m.eval_logprobs(stream[:n], 0)
+        res["trace_rows"], res["repeats"] = ints("--trace-rows", ""), R
+    else:
+        res["eval_ms"] = {str(n): timed(lambda: m.eval(stream[:n], 0)) for n in ints("--evals", "64,128,512")}
+        res["eval_chunks9_ms"] = {str(n): timed(lambda: m.eval_chunks(stream[:n], 0, 9)) for n in ints("--chunks", "18,36,72,144,504")}
+        firsts = []
+        for s_ in range(16):
+            m.set_seq(s_)
+            firsts.append(int(np.argmax(m.eval(np.concatenate([prompt[:255 - s_], prompt[:s_ + 1]]), 0))))
+        m.set_seq(0)
+        res["decode_greedy_ms_per_token"] = [round(x / 64, 4) for x in timed(lambda: m.decode_greedy(firsts[0], 256, 64))]
+        res["set16_ms_per_step"] = [round(x / 64, 4) for x in timed(lambda: m.decode_greedy_multi(firsts, [256] * 16, 64))]
+    if hasattr(L, "dense_paths"):
+        res["dense_paths"] = L.dense_paths()
+    if hasattr(L, "dense_mfma_launches"):
+        res["dense_mfma_launches"] = L.dense_mfma_launches()
+    print(json.dumps(res))
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+    m.close()
+    sys.exit(0)
 
 if multi:
     seqs = [int(s) for s in opt("--seqs", "1,2,4,8,16").split(",")]
