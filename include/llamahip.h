@@ -525,6 +525,114 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
 int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n_past, const int32_t *n_tokens,
                                  int32_t chunk_tokens, int32_t *row_seg, int32_t *row_pos, int32_t *row_keys);
 
+/* ---- request scheduler: prompts admitted into a running multi-sequence decode --------------------------------------------------------
+ * The *_multi loops above take their slots' contexts as given and run every sequence for the same n_steps; llamahip_eval_multi evaluates
+ * several prompts in one pass.  The scheduler is the loop that joins them: requests wait in a queue, take a free KV slot, have their prompt
+ * evaluated in the weight pass the other conversations' decode rows pay for anyway, decode, and leave at their stop token or their length.
+ * One llamahip_sched_step makes ONE weight pass (one per stage group on a pipeline handle) and returns that step's events: a TOKEN event for
+ * every token produced, a DONE event behind a request's last token (or for a cancelled request).
+ *
+ * Slots.  KV slots [0, max_active) belong to the scheduler while it lives; slots at and above max_active stay the caller's; the handle's
+ *   current slot (llamahip_set_seq) is left alone.  At the start of a step queued requests take the free slots, lowest slot first, in
+ *   submission order.  A slot freed by a DONE in step t is reused from step t + 1; its previous occupant's KV rows are stale and never read,
+ *   because every eval writes its positions before it reads them.
+ * The step rule (llamahip_sched_plan; host only, pure, deterministic -- the one place the policy lives).  prompt_left[i]: the prompt tokens
+ *   sequence i still has to evaluate, sequences in admission order (oldest first), 0 = decoding.  Every decoding sequence gets one row.
+ *   rest = row_budget - (decode rows); the prefilling sequences are walked oldest first: with chunk_tokens = c > 0 a sequence gets
+ *   min(prompt_left, floor(max(rest, 0) / c) * c) rows, with c == 0 its whole prompt_left if that fits in rest; where that is less than one
+ *   row and no prefilling sequence has been given rows yet in this step it gets min(prompt_left, c) rows (c == 0: the whole prompt) -- the
+ *   progress guarantee, the only way a step exceeds the budget -- otherwise the walk stops.  rows_out[i]; returns the total, -1 for bad
+ *   arguments (n_active outside 0 .. 16, a negative entry, chunk_tokens < 0, row_budget < 1).  A piece therefore starts at a multiple of c
+ *   and ends at a multiple of c or at the prompt's end: its rows' key counts (llamahip_eval_multi_rows with n_past = the piece's offset) are
+ *   those of the whole prompt's llamahip_eval_chunks.
+ * What a step runs.  Some sequence prefilling: a MIXED PASS -- llamahip_eval_multi's pass over segments, a prefilling sequence's piece at its
+ *   offset, a decoding sequence's one row [its last token] at its position; the lm head over the segments' last rows; k_sched_pick (one wave
+ *   per segment, behind the lm head on the last stage's stream) takes the greedy pick of every segment that EMITS (a decode row, a piece
+ *   that ends its prompt) by k_argmax's rule, stores it in the result block -- 4 bytes per segment come back, no logits row -- publishes it
+ *   into the slot's next-token word and trace, and sets the slot's {position, step} words behind the segment's rows, so that the next
+ *   captured step continues on the device (the other stages of a pipeline handle are kept in step from the host, as
+ *   llamahip_decode_sample_lookup_multi does).  Sampled requests take the candidate selection over their emitting rows instead; the host
+ *   draws, accepts and writes the token word, as llamahip_decode_sample_multi does.  Nobody prefilling: a DECODE-ONLY step, exactly the step
+ *   llamahip_decode_greedy_multi / llamahip_decode_sample_multi take -- the captured llamahip_stage_step_set over the active slots,
+ *   llamahip_stage_step for a single active slot -- with one host wait for the picks per step (stop tokens and streaming need it).
+ *   Handles without the one pass or without a set step (f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_UNFUSED and _FAST_PREFILL handles, head sizes
+ *   the table kernels do not take, n_threads for which llamahip_stage_set_applies is 0) run the contract's own per-slot calls for every
+ *   step (FALL-BACK steps): the same events, the same bits.  (A LLAMAHIP_FLAG_FAST_PREFILL handle makes no parity claim for evals long enough
+ *   to take its mat-mul: there a prompt evaluated in the scheduler's pieces need not equal the prompt evaluated whole.)
+ * Contract, for every request, whatever else is in flight, in whatever order the requests were submitted, for every row_budget: the tokens,
+ *   the KV rows [0, n_prompt + n - 1) of its slot in every layer (n = the tokens produced; read after its DONE and before the slot is
+ *   reused) and the sampler's window and rng state are bit for bit those of the request running ALONE on that slot:
+ *   llamahip_set_seq(slot) + llamahip_eval_chunks(prompt, 0, chunk_tokens) (llamahip_eval when chunk_tokens == 0), the greedy pick or the
+ *   draw from that logits row, then single-token steps (llamahip_decode_greedy, or llamahip_eval_topk -> draw -> accept), the stream cut
+ *   behind stop_token or at n_predict.  (Norm statistics: one pass in the fused single step, two in a multi-row pass.  The equality is
+ *   therefore BY TEST -- tests/test_gpu_sched.py -- not structural, as for set steps, verify steps and llamahip_eval_multi.)  `exact` of a
+ *   TOKEN event is reported as the sampled loops report it (1 for a greedy pick) and is not part of the equality.
+ * Refused before any device work, the message naming the limit.  llamahip_sched_new: max_active outside 1 .. 16 or > llamahip_opts.n_seq,
+ *   chunk_tokens < 0, row_budget < 0 or > LLAMAHIP_EVAL_MULTI_MAX_ROWS - 16, sampler parameters llamahip_verify_sample refuses, HOST_ONLY and
+ *   stage handles, a handle that already has a scheduler.  llamahip_sched_submit: n_prompt < 1, n_predict < 1, a token id (or a stop token other than -1) out of range, n_prompt +
+ *   n_predict - 1 > n_ctx, with chunk_tokens == 0 a prompt longer than LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active, a sampler held by another
+ *   live request.  llamahip_sched_step: cap < 2 * max_active + 1 (the call consumes nothing).
+ * llamahip_sched_cancel: a queued or active request ends with a DONE event of reason CANCELLED in the next step's events (an active one
+ *   takes no row in that step; its slot is free from that step on); -1 for an id that is not live.  llamahip_sched_pending: queued + active
+ *   + cancelled requests whose DONE has not been delivered.  A step that fails (LLAMAHIP_ERR_PREDICT) delivers no event and loses none: the
+ *   waiting DONE events and the requests it admitted are there for the next step.  One scheduler per handle at a time: llamahip_sched_new
+ *   refuses a handle that has one until it is freed; a handle freed first leaves a scheduler whose steps fail and whose llamahip_sched_free
+ *   is still safe.  Between steps the caller may use the slots at and above max_active with any other entry point.
+ * llamahip_op_sched_pick -- the pick half of k_sched_pick on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16;
+ *   picks[r] = the greedy pick of row r where emit[r] != 0, -1 where emit[r] == 0.
+ * Measured on the 7B (profiles/sched_probe_7b.json, tools/sched_probe.py): 64 requests, prompts of 9 .. 288 tokens, 8 .. 224
+ *   tokens each, 16 slots, chunks of 9: 2321 tokens/s aggregate at row_budget 256 (1523 / 1807 / 1941 / 2116 at 16 / 32 / 64 / 128) against
+ *   1124 for static waves of llamahip_eval_multi + llamahip_decode_greedy_multi, which keep stepping finished sequences; the longest step --
+ *   the stall a decoding conversation sees while prompts are admitted -- is 24.3 ms at 256 and 7.5 ms at 32.  A set-step capture costs 1.2 ..
+ *   1.35 ms and a run makes 8 .. 13 of them.
+ * Not built: drafts inside the scheduler; prefix copy between slots; the scheduler behind llama_runner; more than 16 active sequences;
+ *   generating past n_ctx (llamahip_decode_greedy_window's overflow plan); the mixed pass on the fused few-row launches. */
+#define LLAMAHIP_SCHED_ROW_BUDGET 256     /* the candidate of 16 .. 256 with the highest median tokens/s on the probe workload: profiles/sched_probe_7b.json, DESIGN.md 12.19 */
+#define LLAMAHIP_EV_TOKEN 1
+#define LLAMAHIP_EV_DONE  2
+#define LLAMAHIP_DONE_LENGTH    1
+#define LLAMAHIP_DONE_STOP      2
+#define LLAMAHIP_DONE_CANCELLED 3
+typedef struct llamahip_sched llamahip_sched;
+typedef struct llamahip_sched_opts {
+    int32_t struct_size;
+    int32_t n_threads;
+    int32_t max_active;      /* KV slots [0, max_active) belong to the scheduler; 1 .. 16 and <= llamahip_opts.n_seq */
+    int32_t chunk_tokens;    /* the contract's prompt chunking, as llamahip_eval_chunks; 0 = a prompt is one eval and is never split */
+    int32_t row_budget;      /* rows a step aims at; 0 = LLAMAHIP_SCHED_ROW_BUDGET */
+    double  repeat_penalty, top_p, temp;      /* for requests that carry a sampler; all three 0 with top_k 0: 1.3, 0.95f, 0.8f and top_k 40 */
+    int32_t top_k;
+} llamahip_sched_opts;
+typedef struct llamahip_request {
+    int32_t struct_size;
+    const int32_t *prompt; int32_t n_prompt;   /* >= 1; copied at submit */
+    int32_t n_predict;                         /* >= 1 tokens to produce */
+    int32_t stop_token;                        /* -1 = none; the request ends after producing it */
+    llamahip_sampler *sampler;                 /* NULL = greedy; else drawn from and accepted into, as llamahip_decode_sample_multi */
+} llamahip_request;
+typedef struct llamahip_sched_event {
+    int64_t id; int32_t kind;                  /* LLAMAHIP_EV_TOKEN / LLAMAHIP_EV_DONE */
+    int32_t token, exact, slot, position, reason;   /* TOKEN: the token, its exact flag, the position it will be evaluated at; DONE: reason
+                                                       LLAMAHIP_DONE_*, position = the context the slot holds (KV rows [0, position)); slot -1: never admitted */
+} llamahip_sched_event;
+typedef struct llamahip_sched_stats {
+    int32_t struct_size;
+    int32_t n_graph_captures;                  /* set-step graphs captured while the scheduler stepped */
+    int64_t n_steps, n_mixed_steps, n_set_steps, n_single_steps, n_fallback_steps;   /* steps that made a pass, by kind */
+    int64_t n_rows, n_prompt_rows, n_tokens;   /* rows evaluated, of those prompt rows, tokens produced */
+    int64_t n_submitted, n_done;
+} llamahip_sched_stats;
+int     llamahip_sched_new   (llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap);
+int     llamahip_sched_submit(llamahip_sched *s, const llamahip_request *r, int64_t *id, char *err, size_t err_cap);
+int     llamahip_sched_step  (llamahip_sched *s, llamahip_sched_event *ev, int32_t cap, int32_t *n_ev, char *err, size_t err_cap);
+int     llamahip_sched_cancel(llamahip_sched *s, int64_t id);
+int32_t llamahip_sched_pending(const llamahip_sched *s);
+int     llamahip_sched_get_stats(const llamahip_sched *s, llamahip_sched_stats *out);
+void    llamahip_sched_free  (llamahip_sched *s);
+int32_t llamahip_sched_plan(int32_t n_active, const int32_t *prompt_left /* admission order, 0 = decoding */,
+                            int32_t chunk_tokens, int32_t row_budget, int32_t *rows_out);
+int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, int32_t *picks, char *err, size_t err_cap);
+
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
 int llamahip_eval_debug(llamahip_model *m, int32_t n_threads, int32_t n_past,

@@ -19,6 +19,7 @@ from .binding import (  # noqa: F401
     LlamaHipError,
     Model,
     Sampler,
+    Scheduler,
     bench_gemv_names,
     build,
     ctx_overflow_plan,
@@ -43,6 +44,7 @@ from .binding import (  # noqa: F401
     op_prep,
     op_prompt_gemm_q4_0,
     op_quantize_row_q4_0,
+    op_sched_pick,
     op_topk,
     op_topk_rows,
     op_topk_slide,
@@ -51,6 +53,7 @@ from .binding import (  # noqa: F401
     op_verify_rows_set,
     qa_to_blocks,
     quantize_file,
+    sched_plan,
     gemv_plan,
     set_plan,
     version,

@@ -66,6 +66,27 @@ class _LookupStats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_verify_steps", C.c_int32), ("n_single_steps", C.c_int32), ("n_drafted", C.c_int64), ("n_accepted", C.c_int64)]
 
 
+class _SchedOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_threads", C.c_int32), ("max_active", C.c_int32), ("chunk_tokens", C.c_int32),
+                ("row_budget", C.c_int32), ("repeat_penalty", C.c_double), ("top_p", C.c_double), ("temp", C.c_double), ("top_k", C.c_int32)]
+
+
+class _Request(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("prompt", C.c_void_p), ("n_prompt", C.c_int32), ("n_predict", C.c_int32),
+                ("stop_token", C.c_int32), ("sampler", C.c_void_p)]
+
+
+class _SchedEvent(C.Structure):
+    _fields_ = [("id", C.c_int64), ("kind", C.c_int32), ("token", C.c_int32), ("exact", C.c_int32), ("slot", C.c_int32),
+                ("position", C.c_int32), ("reason", C.c_int32)]
+
+
+class _SchedStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_graph_captures", C.c_int32), ("n_steps", C.c_int64), ("n_mixed_steps", C.c_int64),
+                ("n_set_steps", C.c_int64), ("n_single_steps", C.c_int64), ("n_fallback_steps", C.c_int64), ("n_rows", C.c_int64),
+                ("n_prompt_rows", C.c_int64), ("n_tokens", C.c_int64), ("n_submitted", C.c_int64), ("n_done", C.c_int64)]
+
+
 class _Stats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("weight_bytes_device", C.c_int64), ("kv_bytes_device", C.c_int64),
                 ("n_evals", C.c_int64), ("t_load_ms", C.c_double), ("t_eval_ms_total", C.c_double), ("n_stages", C.c_int32), ("hand_off", C.c_int32)]
@@ -166,6 +187,18 @@ def lib() -> C.CDLL:
     L.llamahip_eval_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
     L.llamahip_eval_multi_rows.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
     L.llamahip_eval_multi_rows.restype = i32
+    L.llamahip_sched_new.argtypes = [vp, C.POINTER(_SchedOpts), C.POINTER(vp), cp, sz]
+    L.llamahip_sched_submit.argtypes = [vp, C.POINTER(_Request), C.POINTER(C.c_int64), cp, sz]
+    L.llamahip_sched_step.argtypes = [vp, vp, i32, C.POINTER(i32), cp, sz]
+    L.llamahip_sched_cancel.argtypes = [vp, C.c_int64]
+    L.llamahip_sched_pending.argtypes = [vp]
+    L.llamahip_sched_pending.restype = i32
+    L.llamahip_sched_get_stats.argtypes = [vp, C.POINTER(_SchedStats)]
+    L.llamahip_sched_free.argtypes = [vp]
+    L.llamahip_sched_free.restype = None
+    L.llamahip_sched_plan.argtypes = [i32, vp, i32, i32, vp]
+    L.llamahip_sched_plan.restype = i32
+    L.llamahip_op_sched_pick.argtypes = [vp, i32, i32, vp, vp, cp, sz]
     L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
     L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
@@ -732,6 +765,11 @@ class Model:
         _check(rc, err)
         return (out, np_out.value, logits) if want_logits else (out, np_out.value)
 
+    def scheduler(self, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8, repeat_penalty: float = 1.3,
+                  top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8))) -> "Scheduler":
+        """llamahip_sched_new: a request scheduler over KV slots [0, max_active) of this handle (include/llamahip.h "request scheduler")."""
+        return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp)
+
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
         v = np.empty((n_pos, self.n_embd), np.float32)
@@ -816,6 +854,116 @@ class Sampler:
                 self._s = None
         except Exception:
             pass
+
+
+EV_TOKEN, EV_DONE = 1, 2
+DONE_REASONS = {1: "length", 2: "stop", 3: "cancelled"}
+
+
+class Scheduler:
+    """llamahip_sched_*: requests wait in a queue, take a free KV slot, have their prompt evaluated inside the running decode's weight
+    passes, decode, and leave at their stop token or their length.  A context manager; one step() = one weight pass."""
+
+    def __init__(self, model: Model, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8,
+                 repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8))):
+        self._s = None
+        self.model, self.max_active = model, int(max_active)
+        self._samplers = {}          # id -> Sampler: kept alive while the request may draw
+        o = _SchedOpts(C.sizeof(_SchedOpts), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k)
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_sched_new(model._h, C.byref(o), C.byref(h), err, len(err)), err)
+        self._s = h
+        self._ev = (_SchedEvent * (2 * self.max_active + 64))()
+
+    def close(self) -> None:
+        if self._s:
+            lib().llamahip_sched_free(self._s)
+            self._s = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def submit(self, prompt, n_predict: int, stop_token: int = -1, sampler: "Sampler | None" = None) -> int:
+        """llamahip_sched_submit: returns the request's id (sampler None = greedy)."""
+        p = np.ascontiguousarray(prompt, np.int32).ravel()
+        r = _Request(C.sizeof(_Request), p.ctypes.data if p.size else None, p.size, int(n_predict), int(stop_token), None if sampler is None else sampler._s.value)
+        rid = C.c_int64(0)
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_sched_submit(self._s, C.byref(r), C.byref(rid), err, len(err)), err)
+        if sampler is not None:
+            self._samplers[rid.value] = sampler
+        return int(rid.value)
+
+    def step(self, cap: int | None = None) -> list[dict]:
+        """llamahip_sched_step: one weight pass; the step's events as dicts {id, kind ("token" / "done"), token, exact, slot, position, reason}."""
+        n = C.c_int32(0)
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_sched_step(self._s, C.cast(self._ev, C.c_void_p), len(self._ev) if cap is None else int(cap), C.byref(n), err, len(err)), err)
+        out = []
+        for e in self._ev[:n.value]:
+            done = e.kind == EV_DONE
+            out.append({"id": int(e.id), "kind": "done" if done else "token", "token": int(e.token), "exact": int(e.exact), "slot": int(e.slot),
+                        "position": int(e.position), "reason": DONE_REASONS.get(e.reason) if done else None})
+            if done:
+                self._samplers.pop(int(e.id), None)
+        return out
+
+    def cancel(self, rid: int) -> bool:
+        return lib().llamahip_sched_cancel(self._s, int(rid)) == 0
+
+    def pending(self) -> int:
+        return int(lib().llamahip_sched_pending(self._s))
+
+    def stats(self) -> dict:
+        st = _SchedStats(C.sizeof(_SchedStats))
+        lib().llamahip_sched_get_stats(self._s, C.byref(st))
+        return {k: int(getattr(st, k)) for k, _ in _SchedStats._fields_ if k != "struct_size"}
+
+    def run(self, on_done=None) -> dict:
+        """step until nothing is pending; returns {id: tokens}.  on_done(event), if given, is called at each DONE event -- while the
+        request's KV rows are still in its slot (the slot is reused from the next step)."""
+        out: dict = {}
+        while self.pending():
+            for e in self.step():
+                if e["kind"] == "token":
+                    out.setdefault(e["id"], []).append(e["token"])
+                else:
+                    out.setdefault(e["id"], [])
+                    if on_done is not None:
+                        on_done(e)
+        return out
+
+
+def sched_plan(prompt_left, chunk_tokens: int, row_budget: int):
+    """llamahip_sched_plan (host only): (total rows, rows per sequence) of the next step for sequences in admission order with prompt_left[i]
+    prompt tokens still to evaluate (0 = decoding); total -1 = bad arguments."""
+    left = np.ascontiguousarray(prompt_left, np.int32).ravel()
+    rows = np.full(max(left.size, 1), -1, np.int32)
+    total = lib().llamahip_sched_plan(left.size, _ptr(left) if left.size else None, int(chunk_tokens), int(row_budget), _ptr(rows))
+    return int(total), rows[:left.size]
+
+
+def op_sched_pick(logits2d, emit) -> np.ndarray:
+    """k_sched_pick's pick half on host rows: picks[r] = the greedy pick of row r where emit[r], -1 elsewhere (llamahip_op_sched_pick)."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    R, V = logits2d.shape
+    emit = np.ascontiguousarray(emit, np.int32).ravel()
+    if emit.size != R:
+        raise ValueError(f"op_sched_pick: {R} rows, {emit.size} emit flags")
+    picks = np.full(max(R, 1), -7, np.int32)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_sched_pick(_ptr(logits2d), R, V, _ptr(emit), _ptr(picks), err, len(err)), err)
+    return picks[:R]
 
 
 def ctx_overflow_plan(n_ctx: int, n_past: int, n_keep: int):

@@ -24,6 +24,7 @@
 #include "host_util.h"
 #include "llamahip_internal.h"
 #include "model_file.h"
+#include "sched.h"
 
 using namespace lh;
 
@@ -144,6 +145,7 @@ struct VsetBlock {
 // ------------------------------------------------------------------------------------------------
 // the model handle
 // ------------------------------------------------------------------------------------------------
+namespace lh { void sched_dev_orphan(SchedDev *d); }
 struct llamahip_model {
     ModelFile file;
     HParams hp;
@@ -242,6 +244,7 @@ struct llamahip_model {
     struct SetGraph { SeqSet *d_set = nullptr; hipGraphExec_t exec = nullptr; uint64_t last_use = 0; };
     std::map<std::vector<int>, SetGraph> set_graphs;      // key: {n_threads, slot ids in ascending order}: at most SET_GRAPHS_MAX, least recently used evicted
     uint64_t set_graph_clock = 0;
+    int64_t n_set_captures = 0;          // set steps captured (or, with LLAMAHIP_FLAG_NO_GRAPH, set descriptors built) since the load: llamahip_sched_stats
     std::vector<int> last_rows;          // llamahip_stage_logits: row of the caller's i-th slot in the most recent set step (empty: identity)
     float *set_sc = nullptr;             // attention scores of a set step: [SET_MAX][H][n_ctx]
     int32_t *d_slot_state = nullptr;     // [n_seq][2]: {position, step index}, advanced on the device
@@ -277,6 +280,10 @@ struct llamahip_model {
     char *d_rows = nullptr;
     int rows_cap = 0;
     std::vector<char> h_rows;
+    // llamahip_sched_*: the one scheduler that owns KV slots of this handle (the front of a pipeline handle), and on the last stage its
+    // k_sched_pick table {emit, slot, position, cursor} [SET_MAX] | res [SET_MAX]
+    lh::SchedDev *sched = nullptr;
+    int32_t *d_sched_tab = nullptr;
 
     ~llamahip_model();
 };
@@ -296,10 +303,12 @@ static hipError_t malloc_mailbox(void **p, size_t bytes) {
 }
 
 llamahip_model::~llamahip_model() {
+    if (sched) lh::sched_dev_orphan(sched);          // (a scheduler that outlives its handle: every later call on it fails, none touches the handle)
     for (llamahip_model *st : stages) delete st;
     if (host_only) return;
     (void) hipSetDevice(device);
     (void) hipDeviceSynchronize();      // captured steps may still run on a caller's stream: nothing is freed or destroyed under them
+    free_dev(d_sched_tab);
     free_dev(tok_emb); free_dev(norm_w); free_dev(output.tiles); free_dev(doutput.w); free_dev(doutput.w2);
     for (auto &l : layers) {
         free_dev(l.attention_norm); free_dev(l.ffn_norm);
@@ -1859,6 +1868,7 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
             (void) hipGraphDestroy(graph);
         }
         it = m->set_graphs.emplace(key, sg).first;
+        m->n_set_captures++;
     }
     it->second.last_use = ++m->set_graph_clock;
     m->last_rows.assign(n_seqs, 0);
@@ -2445,6 +2455,37 @@ static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass 
     return forward_rows(st, n_threads, rp, hidden_in, err, err_cap);
 }
 
+// the handle takes the one pass at all: not f16 / f32 / Q4_1 files, not fast-prefill handles (their GEMM choice depends on the row count), a
+// head size the table kernels take (llamahip_eval_multi and the scheduler's mixed pass share the rule)
+static bool rows_pass_applies(llamahip_model *m) {
+    const int dh = m->hp.n_embd / std::max(m->hp.n_head, 1);
+    return !first_of(m)->dense && !(m->flags & LLAMAHIP_FLAG_FAST_PREFILL) && dh % 32 == 0 && dh <= 256;
+}
+// the pass's row table and its short / long segment counts, from rp's segments (slots, n_past, n_tokens, chunk, R set by the caller)
+static int rows_pass_build(RowsPass &rp, int n_ctx) {
+    rp.pos.resize((size_t) rp.R); rp.keys.resize((size_t) rp.R); rp.seg.resize((size_t) rp.R);
+    if (llamahip_eval_multi_rows(n_ctx, rp.n_seqs, rp.n_past, rp.n_tokens, rp.chunk, rp.seg.data(), rp.pos.data(), rp.keys.data()) != rp.R) return -1;
+    for (int i = 0; i < rp.n_seqs; i++) {
+        if (rp.n_tokens[i] > rp.short_max) { rp.n_long_segs++; continue; }
+        rp.n_short_segs++; rp.n_short_rows += rp.n_tokens[i];
+        rp.max_keys = std::max(rp.max_keys, rp.n_past[i] + rp.n_tokens[i]);
+    }
+    return 0;
+}
+// the pass enqueued on every stage, the residual rows handed from stage to stage; not waited for
+static int rows_pass_enqueue(const std::vector<llamahip_model *> &stages, int n_threads, const RowsPass &rp, const int32_t *tokens, char *err, size_t err_cap) {
+    const int S = (int) stages.size();
+    const size_t d = stages[0]->hp.n_embd;
+    int rc = 0;
+    for (int s = 1; s < S; s++) if ((rc = pipe_ensure_in(stages[s], rp.R, err, err_cap)) != 0) return rc;
+    for (int s = 0; s < S && rc == 0; s++) {
+        llamahip_model *st = stages[s];
+        rc = rows_stage_enqueue(st, n_threads, rp, tokens, s ? st->pipe_in : nullptr, err, err_cap);
+        if (rc == 0 && s + 1 < S) rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) rp.R * d * 4, err, err_cap);
+    }
+    return rc;
+}
+
 int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
                         const int32_t *n_tokens, int32_t chunk_tokens, float *logits_out, llamahip_eval_multi_stats *stats, char *err, size_t err_cap) {
     static const char *fn = "llamahip_eval_multi";
@@ -2455,8 +2496,7 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
     const std::vector<llamahip_model *> stages = stages_of(m);
     const int S = (int) stages.size();
     llamahip_model *last = stages[S - 1];
-    const size_t d = m->hp.n_embd, V = m->hp.n_vocab;
-    const int dh = m->hp.n_embd / m->hp.n_head;
+    const size_t V = m->hp.n_vocab;
     RowsPass rp;
     rp.n_seqs = n_seqs; rp.chunk = chunk_tokens; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens;
     for (int i = 0; i < n_seqs; i++) rp.R += n_tokens[i];
@@ -2471,7 +2511,7 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
     // 4 x 512 rows 0.98 x, 2 x 512 rows 1.02 x): more than 1024 rows in segments of 512 rows or more each -- evals that long no longer wait for weights.
     bool all_huge = rp.R > EVAL_MULTI_LOOP_ROWS;
     for (int i = 0; i < n_seqs; i++) all_huge = all_huge && n_tokens[i] >= EVAL_MULTI_LOOP_SEG_ROWS;
-    if (dense || (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) || n_seqs == 1 || dh % 32 != 0 || dh > 256 || all_huge) {
+    if (!rows_pass_applies(m) || n_seqs == 1 || all_huge) {
         for (int i = 0; i < n_seqs; i++)
             out.n_passes += (dense && chunk_tokens > 0 && n_tokens[i] > chunk_tokens) ? (n_tokens[i] + chunk_tokens - 1) / chunk_tokens : 1;      // (llamahip_eval_chunks on such a file: one eval per chunk)
         std::vector<size_t> at((size_t) n_seqs, 0);
@@ -2487,23 +2527,10 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
     static const int env_short_max = getenv("LLAMAHIP_EVAL_MULTI_SHORT_MAX") ? atoi(getenv("LLAMAHIP_EVAL_MULTI_SHORT_MAX")) : 0;
     if (env_short_max > 0) rp.short_max = env_short_max;
     const double t0 = now_ms();
-    rp.pos.resize((size_t) rp.R); rp.keys.resize((size_t) rp.R); rp.seg.resize((size_t) rp.R);
-    if (llamahip_eval_multi_rows(m->hp.n_ctx, n_seqs, n_past, n_tokens, chunk_tokens, rp.seg.data(), rp.pos.data(), rp.keys.data()) != rp.R) {
-        set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT;
-    }
-    for (int i = 0; i < n_seqs; i++) {
-        if (n_tokens[i] > rp.short_max) { rp.n_long_segs++; continue; }
-        rp.n_short_segs++; rp.n_short_rows += n_tokens[i];
-        rp.max_keys = std::max(rp.max_keys, n_past[i] + n_tokens[i]);
-    }
+    if (rows_pass_build(rp, m->hp.n_ctx) != 0) { set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT; }
     out.n_passes = 1; out.n_short_segs = rp.n_short_segs; out.n_long_segs = rp.n_long_segs;
     out.attn_groups = (rp.n_short_segs > 0 ? 1 : 0) + rp.n_long_segs;
-    for (int s = 1; s < S; s++) if ((rc = pipe_ensure_in(stages[s], rp.R, err, err_cap)) != 0) return rc;
-    for (int s = 0; s < S && rc == 0; s++) {
-        llamahip_model *st = stages[s];
-        rc = rows_stage_enqueue(st, n_threads, rp, tokens, s ? st->pipe_in : nullptr, err, err_cap);
-        if (rc == 0 && s + 1 < S) rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) rp.R * d * 4, err, err_cap);
-    }
+    rc = rows_pass_enqueue(stages, n_threads, rp, tokens, err, err_cap);
     // (the bounded wait first, the copy of the logits rows behind it: pipe_eval)
     if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
@@ -2871,13 +2898,17 @@ int llamahip_decode_greedy_lookup(llamahip_model *m, int32_t n_threads, int32_t 
 // in place of k_verify_rows / k_accept_drafts) and the host walks the rows with the real sampler: row 0, then row j + 1 only if row j's
 // draw was draft[j].  Exactly the rng draws and accepts of the token-by-token loop; only the number of weight passes changes.
 // ------------------------------------------------------------------------------------------------
-static int check_sampler_params(const char *fn, const llamahip_sampler *sampler, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
-    if (!sampler) { set_err(err, err_cap, "%s: null sampler", fn); return LLAMAHIP_ERR_PREDICT; }
+// the sampling parameters' own rule (llamahip_sched_new checks them before any request brings a sampler)
+static int check_sampling_rule(const char *fn, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
     if (top_k < 1) { set_err(err, err_cap, "%s: top_k must be >= 1 (got %d)", fn, top_k); return LLAMAHIP_ERR_PREDICT; }
     if (!(temp > 0.0)) { set_err(err, err_cap, "%s: temp must be > 0 (got %g)", fn, temp); return LLAMAHIP_ERR_PREDICT; }
     if (!(repeat_penalty > 0.0)) { set_err(err, err_cap, "%s: repeat_penalty must be > 0 (got %g)", fn, repeat_penalty); return LLAMAHIP_ERR_PREDICT; }
     if (top_p != top_p) { set_err(err, err_cap, "%s: top_p is NaN", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
+}
+static int check_sampler_params(const char *fn, const llamahip_sampler *sampler, double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
+    if (!sampler) { set_err(err, err_cap, "%s: null sampler", fn); return LLAMAHIP_ERR_PREDICT; }
+    return check_sampling_rule(fn, repeat_penalty, top_k, top_p, temp, err, err_cap);
 }
 // the sampling parameters of a call and what every sampled entry point derives from them.  dev_sel: the device can make a row's candidates
 // (not with top_k > 64 or n_vocab > 32768; a window of more than 1024 ids rules it out for that sampler's rows only, checked where the window is known)
@@ -3028,6 +3059,9 @@ static std::vector<int> group_cut(int n_seqs, int n_stages) {
     return g0;
 }
 
+// the multi-sequence loops have a stage step to batch: not Q4_1 files, f16 / f32 pipeline stages or LLAMAHIP_FLAG_UNFUSED handles
+static bool multi_stage_steps(const llamahip_model *first) { return !(first->dense && !dense_stage_steps(first)) && !(first->flags & LLAMAHIP_FLAG_UNFUSED); }
+
 static int multi_prepare(llamahip_model *st, int n_groups, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     const size_t d = st->hp.n_embd;
@@ -3151,7 +3185,7 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
         if ((rc = check_eval_args(first, n_past[i], first_tokens + i, 1, true, err, err_cap)) != 0) return rc;
         if (n_past[i] + n_steps > m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", n_past[i], n_steps, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
     }
-    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED))
+    if (!multi_stage_steps(first))
         // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): llamahip_decode_greedy on each slot in turn
         return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
             return llamahip_decode_greedy(m, n_threads, n_past[i], first_tokens[i], n_steps, out_tokens + (size_t) i * n_steps, nullptr, err, err_cap); });
@@ -3516,7 +3550,7 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
     }
     // (the device half runs unless top_k > 64 or n_vocab > 32768 -- then every row is spilled; a window of more than 1024 ids spills its row only)
     const SampleParams sp = sample_params(m, repeat_penalty, top_k, top_p, temp);
-    if ((first->dense && !dense_stage_steps(first)) || (first->flags & LLAMAHIP_FLAG_UNFUSED)) {
+    if (!multi_stage_steps(first)) {
         // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): the single-sequence loop on each slot in turn
         std::vector<float> logits;
         std::vector<int32_t> win;
@@ -3758,6 +3792,257 @@ int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, in
     if (!m->stages.empty()) m->pipe_hand_off = 1;
     return LLAMAHIP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// The request scheduler's device half (sched.h; the queue, the slots and the step rule are sched.cpp's): what ONE planned step runs.
+// MIXED PASS, some segment a prompt piece: llamahip_eval_multi's pass (RowsPass: a decode row is a one-token segment of it) on every stage,
+// then on the last stage's stream the candidate selection over the sampled segments that emit (they are ordered first, so their logits
+// rows are rows [0, ns): sample_select) and k_sched_pick over all segments -- greedy picks into the result block, the slots' {position,
+// cursor} / next-token words / traces set on the device.  DECODE-ONLY STEP: step_group over the active slots, llamahip_decode_*_multi's step
+// (the captured set step; one active slot: the single step), one wait, the picks read from the slots' token words.
+// The slots [0, max_active) stay bound the greedy loops' way (multi_begin: token word = mq_tok[slot], fed by the last stage's pick); a
+// sampled request's token word is written by the host before every decode-only step.  The host mirrors every slot's {position, cursor,
+// token} and pushes them to every stage where the device cannot know them: after a (re)bind, and on a pipeline handle after a mixed pass
+// (k_sched_pick runs on the last stage only -- llamahip_decode_sample_lookup_multi keeps its stages in step the same way).
+// FALL-BACK, handles without the pass or without a set step: the contract's own per-slot calls, segment by segment.
+// ------------------------------------------------------------------------------------------------
+extern "C++" {
+namespace lh {
+struct SchedDev {
+    llamahip_model *m = nullptr;
+    int n_threads = 1, max_active = 1, chunk = 0;
+    double repeat_penalty = 0, top_p = 0, temp = 0;
+    int32_t top_k = 0;
+    bool decided = false, fallback = false, stale = true;
+    int32_t pos[SET_MAX] = { 0 }, cur[SET_MAX] = { 0 }, tok[SET_MAX] = { 0 };      // host mirrors of the slots' words
+    std::vector<float> logits;
+    std::vector<int32_t> win;
+};
+
+int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap) {
+    const int rc = decode_handle_check(m, "llamahip_sched_new", err, err_cap);
+    if (rc) return rc;
+    const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
+    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq };
+    return 0;
+}
+int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
+    return check_sampling_rule("llamahip_sched_new", repeat_penalty, top_k, top_p, temp, err, err_cap);
+}
+// one scheduler per handle at a time: a second one would rebind and overwrite the first one's slots
+int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *o, SchedDev **out, char *err, size_t err_cap) {
+    *out = nullptr;
+    if (m->sched) { set_err(err, err_cap, "llamahip_sched_new: the handle already has a scheduler (one per handle at a time: llamahip_sched_free the other first)"); return LLAMAHIP_ERR_PREDICT; }
+    SchedDev *d = new SchedDev();
+    d->m = m; d->n_threads = o->n_threads; d->max_active = o->max_active; d->chunk = o->chunk_tokens;
+    d->repeat_penalty = o->repeat_penalty; d->top_p = o->top_p; d->temp = o->temp; d->top_k = o->top_k;
+    m->sched = d;
+    *out = d;
+    return 0;
+}
+// the handle is being freed under a live scheduler: the scheduler forgets it (no device memory is the scheduler's own)
+void sched_dev_orphan(SchedDev *d) { d->m = nullptr; }
+void sched_dev_free(SchedDev *d) {
+    if (!d) return;
+    if (d->m) d->m->sched = nullptr;
+    delete d;
+}
+
+// the slots bound the greedy loops' way on every stage, the table on the last stage; after a (re)bind every word is the host's to push
+static int sched_bind(SchedDev *d, const std::vector<llamahip_model *> &stages, char *err, size_t err_cap) {
+    llamahip_model *first = stages[0], *last = stages.back();
+    bool bound = first->mq_tok != nullptr && last->mq_tok != nullptr;
+    for (llamahip_model *st : stages)
+        for (int i = 0; i < d->max_active && bound; i++)
+            bound = i < (int) st->slots.size() && st->slots[i].bound && (st != first || st->slots[i].token_in == first->mq_tok + i) &&
+                    (st != last || st->slots[i].token_out == last->mq_tok + i);
+    if (!bound) {
+        const std::vector<int32_t> zero((size_t) d->max_active, 0);
+        const int rc = multi_begin(stages, 1, d->max_active, zero.data(), zero.data(), err, err_cap);
+        if (rc) return rc;
+        d->stale = true;
+    }
+    if (!last->d_sched_tab) {
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMalloc((void **) &last->d_sched_tab, (size_t) 5 * SET_MAX * 4), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+// every scheduler slot's {position, cursor} to every stage, its token to the first and the last stage's token words; the hosts' position mirrors
+static int sched_push_words(SchedDev *d, const std::vector<llamahip_model *> &stages, char *err, size_t err_cap) {
+    int32_t w[2 * SET_MAX];
+    for (int i = 0; i < d->max_active; i++) { w[2 * i] = d->pos[i]; w[2 * i + 1] = d->cur[i]; }
+    for (llamahip_model *st : stages) {
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpy(st->d_slot_state, w, (size_t) d->max_active * 8, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+        if (st == stages[0] || st == stages.back()) HIP_TRY(hipMemcpy(st->mq_tok, d->tok, (size_t) d->max_active * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+        for (int i = 0; i < d->max_active; i++) st->slots[i].next_pos = d->pos[i];
+    }
+    d->stale = false;
+    return 0;
+}
+
+static int sched_fallback_step(SchedDev *d, SchedSeg *segs, int n_segs, const SampleParams &sp, char *err, size_t err_cap) {
+    llamahip_model *m = d->m;
+    const int V = m->hp.n_vocab;
+    d->logits.resize((size_t) V);
+    for (int j = 0; j < n_segs; j++) {
+        SchedSeg &g = segs[j];
+        const int rc = each_slot(m, 1, &g.slot, err, err_cap, [&](int) {
+            int r = 0;
+            if (g.n_rows == 1 && g.emit && g.pos > 0 && g.n_out > 0) {          // a decode row: the contract's single-token step
+                if (!g.sampler) { g.exact = 1; return llamahip_decode_greedy(m, d->n_threads, g.pos, g.tokens[0], 1, &g.token, nullptr, err, err_cap); }
+                return sample_single_step(m, d->n_threads, g.pos, g.tokens[0], g.sampler, sp, d->win, d->logits, &g.token, &g.exact, err, err_cap);
+            }
+            float *lo = g.emit ? d->logits.data() : nullptr;
+            r = d->chunk > 0 ? llamahip_eval_chunks(m, d->n_threads, g.pos, g.tokens, g.n_rows, d->chunk, lo, err, err_cap)
+                             : llamahip_eval(m, d->n_threads, g.pos, g.tokens, g.n_rows, lo, err, err_cap);
+            if (r || !g.emit) return r;
+            if (g.sampler) { g.token = sample_draw(m, g.sampler, sp, false, nullptr, nullptr, lo, &g.exact); return 0; }
+            const int32_t one = 1;
+            g.exact = 1;
+            return llamahip_op_sched_pick(lo, 1, V, &one, &g.token, err, err_cap);          // (the device's pick rule, not restated here)
+        });
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_sched_step";
+    llamahip_model *m = d->m;
+    *captures = 0;
+    if (!m) { set_err(err, err_cap, "%s: the scheduler's model handle has been freed", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (n_segs < 1 || n_segs > SET_MAX) { set_err(err, err_cap, "%s: %d segments in a step (1 .. %d)", fn, n_segs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    const int C = m->hp.n_ctx, V = m->hp.n_vocab;
+    int64_t R = 0;
+    for (int j = 0; j < n_segs; j++) {
+        const SchedSeg &g = segs[j];
+        if (g.slot < 0 || g.slot >= d->max_active || g.n_rows < 1 || g.pos < 0 || g.pos + g.n_rows > C || !g.tokens || (!mixed && (g.n_rows != 1 || !g.emit))) {
+            set_err(err, err_cap, "%s: segment %d (slot %d, %d rows at %d) is outside the scheduler's slots or the context (n_ctx %d)", fn, j, g.slot, g.n_rows, g.pos, C);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        for (int i = 0; i < j; i++) if (segs[i].slot == g.slot) { set_err(err, err_cap, "%s: slot %d has two segments in one step", fn, g.slot); return LLAMAHIP_ERR_PREDICT; }
+        R += g.n_rows;
+    }
+    if (R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { set_err(err, err_cap, "%s: %lld rows in one step, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const SampleParams sp = sample_params(m, d->repeat_penalty, d->top_k, d->top_p, d->temp);
+    if (!d->decided) {
+        // llamahip_eval_multi's and the multi-sequence decoders' own conditions: the pass, a stage step to batch, set steps of every size
+        d->fallback = !rows_pass_applies(m) || !multi_stage_steps(first) || !vset_applies(stages, d->n_threads);
+        d->decided = true;
+    }
+    const double t0 = now_ms();
+    if (d->fallback) {
+        *kind = SCHED_STEP_FALLBACK;
+        return sched_fallback_step(d, segs, n_segs, sp, err, err_cap);
+    }
+    int rc = sched_bind(d, stages, err, err_cap);
+    if (rc) return rc;
+    int64_t cap0 = 0;
+    for (llamahip_model *st : stages) cap0 += st->n_set_captures;
+    bool any_sampled = false;
+    for (int j = 0; j < n_segs; j++) any_sampled = any_sampled || (segs[j].sampler && segs[j].emit);
+    if (any_sampled) {
+        if ((rc = sample_prepare(last, true, err, err_cap)) != 0) return rc;
+        if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
+    }
+    const llamahip_model::SampleIo &hl = last->smp_h;
+    int order[SET_MAX], n_ord = 0;          // the step's rows: segment order[a] is row a of the logits
+    if (mixed) {
+        *kind = SCHED_STEP_MIXED;
+        // the sampled segments that emit first: their logits rows are rows [0, ns), their windows and candidates index a of the pinned block
+        for (int j = 0; j < n_segs; j++) if (segs[j].sampler && segs[j].emit) order[n_ord++] = j;
+        const int ns = n_ord;
+        for (int j = 0; j < n_segs; j++) if (!(segs[j].sampler && segs[j].emit)) order[n_ord++] = j;
+        int32_t slots[SET_MAX], n_past[SET_MAX], n_tokens[SET_MAX], tab[4 * SET_MAX];
+        std::vector<int32_t> tokens;
+        tokens.reserve((size_t) R);
+        for (int a = 0; a < n_segs; a++) {
+            const SchedSeg &g = segs[order[a]];
+            slots[a] = g.slot; n_past[a] = g.pos; n_tokens[a] = g.n_rows;
+            tokens.insert(tokens.end(), g.tokens, g.tokens + g.n_rows);
+            tab[4 * a] = g.emit && !g.sampler; tab[4 * a + 1] = g.slot; tab[4 * a + 2] = g.pos + g.n_rows; tab[4 * a + 3] = g.n_out + (g.emit ? 1 : 0);
+            if (a < ns) hl.n_last[a] = llamahip_sampler_window(g.sampler, hl.win + (size_t) a * 1024, 1024);          // (the streams are idle: every step is waited for)
+        }
+        RowsPass rp;
+        rp.n_seqs = n_segs; rp.chunk = d->chunk; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens; rp.R = (int) R;
+        if (rows_pass_build(rp, C) != 0) { set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT; }
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(last->d_sched_tab, tab, (size_t) n_segs * 16, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);      // (pageable: it has left `tab` when the call returns)
+        int32_t *d_res = last->h_io ? last->d_io->vset.res : last->d_sched_tab + 4 * SET_MAX;
+        rc = rows_pass_enqueue(stages, d->n_threads, rp, tokens.data(), err, err_cap);
+        if (rc == 0 && hipSetDevice(last->device) != hipSuccess) { set_err(err, err_cap, "%s: hipSetDevice failed", fn); rc = LLAMAHIP_ERR_PREDICT; }
+        if (rc == 0 && ns > 0) rc = sample_select(last, sp, 0, ns, err, err_cap);
+        if (rc == 0 && launch_sched_pick(last->logits, n_segs, V, last->d_sched_tab, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess) {
+            set_err(err, err_cap, "%s: HIP error launching k_sched_pick", fn); rc = LLAMAHIP_ERR_PREDICT;
+        }
+        if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        int32_t res[SET_MAX];
+        if (last->h_io) memcpy(res, last->h_io->vset.res, (size_t) n_segs * 4);
+        else HIP_TRY(hipMemcpy(res, d_res, (size_t) n_segs * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        for (int a = 0; a < n_segs; a++) {
+            SchedSeg &g = segs[order[a]];
+            if (g.emit && !g.sampler) { g.token = res[a]; g.exact = 1; }
+            else if (g.emit) {
+                const TopkOut &c = hl.out[a];
+                g.token = sample_draw(m, g.sampler, sp, sp.dev_sel && c.fl[0] == 1, c.sc, c.id, hl.spill + (size_t) a * V, &g.exact);
+            }
+            d->pos[g.slot] = g.pos + g.n_rows; d->cur[g.slot] = g.n_out + (g.emit ? 1 : 0);
+            if (g.emit) d->tok[g.slot] = g.token;
+            for (llamahip_model *st : stages) st->slots[g.slot].next_pos = d->pos[g.slot];
+        }
+        if (S > 1) d->stale = true;          // (k_sched_pick set the last stage's words only)
+        last->last_rows.clear();
+        m->last_rows.clear();
+        m->n_evals++;
+    } else {
+        // a set orders its rows by slot id: row a of the step = the a-th slot in ascending order
+        for (int j = 0; j < n_segs; j++) order[n_ord++] = j;
+        std::sort(order, order + n_segs, [&](int x, int y) { return segs[x].slot < segs[y].slot; });
+        int32_t act[SET_MAX];
+        for (int a = 0; a < n_segs; a++) {
+            const SchedSeg &g = segs[order[a]];
+            act[a] = g.slot;
+            if (d->pos[g.slot] != g.pos || d->tok[g.slot] != g.tokens[0]) { d->pos[g.slot] = g.pos; d->cur[g.slot] = g.n_out; d->tok[g.slot] = g.tokens[0]; d->stale = true; }
+            if (any_sampled) hl.n_last[a] = g.sampler ? llamahip_sampler_window(g.sampler, hl.win + (size_t) a * 1024, 1024) : 0;
+        }
+        if (d->stale) { if ((rc = sched_push_words(d, stages, err, err_cap)) != 0) return rc; }
+        else if (any_sampled) {
+            // a sampled request's token word holds the step's greedy pick: the host writes the draws over them -- the mirror holds every
+            // slot's token (a greedy slot's is what the device put there), so the whole array goes up in one copy
+            HIP_TRY(hipSetDevice(first->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpy(first->mq_tok, d->tok, (size_t) d->max_active * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+        }
+        *kind = n_segs >= 2 ? SCHED_STEP_SET : SCHED_STEP_SINGLE;
+        const std::function<int(int, int)> select = [&](int j, int rows) { return sample_select(last, sp, j, rows, err, err_cap); };
+        rc = step_group(stages, { act, n_segs, 0, d->max_active, 0 }, d->n_threads, false, true, any_sampled ? select : nullptr, err, err_cap);
+        if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        int32_t words[SET_MAX];
+        HIP_TRY(hipMemcpy(words, last->mq_tok, (size_t) d->max_active * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        for (int a = 0; a < n_segs; a++) {
+            SchedSeg &g = segs[order[a]];
+            if (!g.sampler) { g.token = words[g.slot]; g.exact = 1; }
+            else {
+                const TopkOut &c = hl.out[a];
+                g.token = sample_draw(m, g.sampler, sp, sp.dev_sel && c.fl[0] == 1, c.sc, c.id, hl.spill + (size_t) a * V, &g.exact);
+            }
+            d->pos[g.slot] = g.pos + 1; d->cur[g.slot] = g.n_out + 1; d->tok[g.slot] = g.token;
+        }
+        if (!m->stages.empty()) m->pipe_hand_off = 1;
+    }
+    for (llamahip_model *st : stages) cap0 -= st->n_set_captures;
+    *captures = (int32_t) -cap0;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+}  // namespace lh
+}  // extern "C++"
 
 int llamahip_set_seq(llamahip_model *m, int32_t seq, char *err, size_t err_cap) {
     if (!m || seq < 0 || seq >= m->n_seq) { set_err(err, err_cap, "sequence slot %d out of range [0, %d)", seq, m ? m->n_seq : 0); return LLAMAHIP_ERR_PREDICT; }

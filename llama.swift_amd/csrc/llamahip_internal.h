@@ -323,6 +323,11 @@ hipError_t launch_argmax(const float *logits, int V, int32_t *out, int out_idx, 
 // res = {n_accept, pick[0 .. n_rows)}.  pick == null: one row whose pick is pick_imm; restart_pos >= 0: state = {restart_pos, 0} first.
 constexpr int VERIFY_ROWS_MAX = 16;
 hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st);
+// a scheduler's mixed pass (k_sched_pick, one wave per segment): logits row s = segment s's last row, tab[s] = {emit, slot, position, cursor};
+// res[s] = the greedy pick of an emitting segment (k_verify_rows' rule), -1 otherwise; state / log / next_tok (all or none): the slot's
+// {position, cursor} words are set, an emitting segment's pick goes to the slot's next-token word and to log[slot][cursor - 1]
+hipError_t launch_sched_pick(const float *logits, int n_segs, int V, const int32_t *tab, int32_t *state, int32_t *log, int log_cap, int32_t *next_tok,
+                             int32_t *res, hipStream_t st);
 hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int pick_imm, int n_rows, int restart_pos, int32_t *log, int log_cap,
                                 int32_t *state, int32_t *res, hipStream_t st);
 // ... for the rows of several sequences in one step: segment s = rows [seg_begin[s], seg_begin[s + 1]) of slot seg_slot[s] (seg_begin ascending from 0

@@ -472,6 +472,25 @@ int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab
     return LLAMAHIP_OK;
 }
 
+// the pick half of k_sched_pick on caller-supplied rows, one segment per row, no slot words (parity tests): see llamahip_sched_step
+int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, int32_t *picks, char *err, size_t err_cap) {
+    if (!logits || !emit || !picks || n_rows < 1 || n_rows > SET_MAX || n_vocab < 1) {
+        set_err(err, err_cap, "llamahip_op_sched_pick: bad arguments (n_rows %d of 1 .. %d, n_vocab %d)", n_rows, SET_MAX, n_vocab);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows;
+    int32_t tab[4 * SET_MAX] = { 0 };
+    for (size_t r = 0; r < N; r++) tab[4 * r] = emit[r] != 0;
+    Scratch s;
+    int32_t *d_tab = s.alloc<int32_t>(4 * N, tab), *d_res = s.alloc<int32_t>(N);
+    float *d_l = s.alloc(N * (size_t) n_vocab, logits);
+    if (s.ok()) s.check(launch_sched_pick(d_l, n_rows, n_vocab, d_tab, nullptr, nullptr, 0, nullptr, d_res, nullptr));
+    if (s.ok()) s.download(picks, d_res, N * 4);
+    if (!s.ok()) return s.fail("llamahip_op_sched_pick", err, err_cap);
+    return LLAMAHIP_OK;
+}
+
 // k_verify_rows + k_accept_drafts_set on caller-supplied rows cut into segments (parity tests): see llamahip_verify_greedy_multi
 int llamahip_op_verify_rows_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens, const int32_t *seg_begin, int32_t n_segs,
                                 int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {

@@ -1,0 +1,40 @@
+// sched.h -- the seam between the request scheduler's host half (sched.cpp: queue, slots, the step rule, events) and its device half
+// (llamahip.cpp: what a planned step runs on the handle).  Plain C++ types only, no HIP header: sched.cpp is compiled as it is into
+// tools/host_sanitize, where the four functions below are stubs.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include "../../include/llamahip.h"
+
+namespace lh {
+
+struct SchedDev;          // the device half's state for one scheduler (llamahip.cpp)
+
+// what the host half needs to know of the handle; refuses (message in err, the handle named last) null, HOST_ONLY and stage handles
+struct SchedHandleInfo { int32_t n_ctx, n_vocab, n_seq; };
+int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap);
+// the sampler parameters of llamahip_sched_opts, by llamahip_verify_sample's rule
+int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap);
+
+// One segment of a planned step: n_rows tokens of KV slot `slot` at position pos.  A prefilling sequence's piece, or a decoding sequence's
+// one row [its last token].  emit: the segment's last row produces a token (a decode row, a piece that ends its prompt) -- the device half
+// fills token / exact: the greedy pick (sampler == null) or the sampler's draw, already accepted into it.
+// n_out: the tokens the request has produced before this step (the slot's trace cursor).
+struct SchedSeg {
+    int32_t slot, pos, n_rows, emit, n_out;
+    const int32_t *tokens;
+    llamahip_sampler *sampler;
+    int32_t token, exact;
+};
+enum { SCHED_STEP_MIXED = 0, SCHED_STEP_SET = 1, SCHED_STEP_SINGLE = 2, SCHED_STEP_FALLBACK = 3 };
+
+// no device work (everything is set up by the first step); refuses a handle that already has a scheduler.  A handle freed under its
+// scheduler orphans it: every later step fails, sched_dev_free never touches the handle
+int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *o, SchedDev **out, char *err, size_t err_cap);
+void sched_dev_free(SchedDev *d);
+// one weight pass over the segments (mixed: some segment is a prompt piece; else every segment is one decode row).  *kind: SCHED_STEP_*;
+// *captures: set-step graphs captured by this step.  Nothing of the host half's state is read: the segments say everything.
+int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap);
+
+}  // namespace lh

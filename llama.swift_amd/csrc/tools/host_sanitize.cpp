@@ -18,8 +18,9 @@
 #include "../../../include/llama_runner.h"
 #include "../../../include/llamahip.h"
 #include "../model_file.h"
+#include "../sched.h"
 
-struct llamahip_model { lh::ModelFile file; };
+struct llamahip_model { lh::ModelFile file; lh::SchedDev *sched = nullptr; };
 
 extern "C" {
 int llamahip_model_load(const char *path, int32_t n_ctx, const llamahip_opts *opts, llamahip_model **out, char *err, size_t err_cap) {
@@ -88,6 +89,49 @@ int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_
 int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+}
+
+// the request scheduler's device half (sched.h), stubbed: every planned step is logged segment by segment, exactly sized copies of what the host
+// half handed over (so that a read past a request's tokens is the sanitizer's to see), and answered with made-up tokens
+struct SchedCall { bool mixed; std::vector<lh::SchedSeg> segs; std::vector<std::vector<int32_t>> toks; };
+static std::vector<SchedCall> g_sched_calls;
+static bool g_sched_fail = false;          // the next steps fail like a device error: nothing of the host half's state may be lost
+namespace lh {
+struct SchedDev { int V; llamahip_model *m; };
+int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap) {
+    if (!m) { snprintf(err, err_cap, "llamahip_sched_new: null model"); return LLAMAHIP_ERR_PREDICT; }
+    *out = { m->file.hp.n_ctx, m->file.hp.n_vocab, 4 };
+    return 0;
+}
+int sched_sampler_check(double repeat_penalty, int32_t top_k, double, double temp, char *err, size_t err_cap) {
+    if (top_k < 1 || !(temp > 0.0) || !(repeat_penalty > 0.0)) { snprintf(err, err_cap, "llamahip_sched_new: sampler parameters"); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *, SchedDev **out, char *err, size_t err_cap) {
+    *out = nullptr;
+    if (m->sched) { snprintf(err, err_cap, "llamahip_sched_new: the handle already has a scheduler"); return LLAMAHIP_ERR_PREDICT; }
+    *out = m->sched = new SchedDev{ m->file.hp.n_vocab, m };
+    return 0;
+}
+void sched_dev_free(SchedDev *d) { if (d) d->m->sched = nullptr; delete d; }
+int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap) {
+    if (g_sched_fail) { snprintf(err, err_cap, "llamahip_sched_step: made-up device error"); return LLAMAHIP_ERR_PREDICT; }
+    SchedCall c;
+    c.mixed = mixed;
+    for (int j = 0; j < n_segs; j++) {
+        c.toks.emplace_back(segs[j].tokens, segs[j].tokens + segs[j].n_rows);
+        if (segs[j].emit) {
+            segs[j].token = (int32_t) (((uint32_t) c.toks.back().back() * 31u + (uint32_t) (segs[j].pos + segs[j].n_rows) * 7u + 3u) % (uint32_t) d->V);
+            segs[j].exact = 1;
+            if (segs[j].sampler) llamahip_sampler_accept(segs[j].sampler, segs[j].token);
+        }
+        c.segs.push_back(segs[j]);
+    }
+    g_sched_calls.push_back(std::move(c));
+    *kind = mixed ? SCHED_STEP_MIXED : n_segs >= 2 ? SCHED_STEP_SET : SCHED_STEP_SINGLE;
+    *captures = 0;
     return 0;
 }
 }
@@ -366,6 +410,253 @@ int main(int argc, char **argv) {
         EXPECT(llamahip_eval_multi_rows(4096, 1, np1, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, zero, 0, nullptr, nullptr, nullptr) == -1);
         EXPECT(llamahip_eval_multi_rows(64, 1, neg, np1, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 0, np1, np1, 0, nullptr, nullptr, nullptr) == -1);
         EXPECT(llamahip_eval_multi_rows(64, 1, nullptr, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, big, -1, nullptr, nullptr, nullptr) == -1);
+    }
+    // the request scheduler's host half against the stubbed device half: the step rule over a grid on exactly sized arrays against its
+    // restatement; then whole runs -- every step's segments replayed against the rule and the requests' own state (positions, offsets, tokens,
+    // emit flags), the events against the made-up tokens; the refusals of new / submit / step; cancelling queued and active requests
+    auto plan_ref = [](const std::vector<int32_t> &left, int c, int budget, std::vector<int32_t> &rows) {
+        long rest = budget, total = 0;
+        for (int32_t l : left) if (l == 0) rest--;
+        bool given = false, stop = false;
+        rows.assign(left.size(), 0);
+        for (size_t i = 0; i < left.size(); i++) {
+            long r = 0;
+            if (left[i] == 0) r = 1;
+            else if (!stop) {
+                const long room = rest > 0 ? rest : 0;
+                r = c > 0 ? std::min<long>(left[i], room / c * c) : (left[i] <= rest ? left[i] : 0);
+                if (r < 1 && !given) r = c > 0 ? std::min<long>(left[i], c) : left[i];
+                else if (r < 1) stop = true;
+                if (r > 0) { given = true; rest -= r; }
+            }
+            rows[i] = (int32_t) r; total += r;
+        }
+        return (int32_t) total;
+    };
+    for (int c : { 0, 1, 4, 9 })
+        for (int budget : { 1, 8, 16, 17, 64 })
+            for (int n = 0; n <= 16; n++)
+                for (int it = 0; it < 6; it++) {
+                    static const int lens[8] = { 0, 1, 3, 9, 10, 27, 61, 100 };
+                    std::vector<int32_t> left((size_t) n), rows((size_t) n, -7), want;
+                    for (int i = 0; i < n; i++) left[(size_t) i] = lens[rng() % 8];
+                    const int32_t total = llamahip_sched_plan(n, n ? left.data() : nullptr, c, budget, n ? rows.data() : nullptr);
+                    EXPECT(total == plan_ref(left, c, budget, want) && rows == want);
+                }
+    {
+        int32_t l1[1] = { 3 }, r1[1] = { 0 }, neg[1] = { -1 };
+        EXPECT(llamahip_sched_plan(1, l1, 0, 0, r1) == -1 && llamahip_sched_plan(1, l1, -1, 8, r1) == -1 && llamahip_sched_plan(17, l1, 0, 8, r1) == -1);
+        EXPECT(llamahip_sched_plan(1, nullptr, 0, 8, r1) == -1 && llamahip_sched_plan(1, l1, 0, 8, nullptr) == -1 && llamahip_sched_plan(1, neg, 0, 8, r1) == -1);
+        EXPECT(llamahip_sched_plan(-1, l1, 0, 8, r1) == -1 && llamahip_sched_plan(0, nullptr, 0, 8, nullptr) == 0);
+    }
+    if (parts <= 1) {
+        llamahip_model *ms = nullptr;
+        EXPECT(llamahip_model_load(path.c_str(), 48, &o, &ms, err, sizeof(err)) == 0);
+        for (int c : { 0, 1, 4, 9 })
+            for (int budget : { 1, 8, 17 })
+                for (int max_active : { 1, 3, 4 }) {
+                    if (!ms) break;
+                    llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                    so.struct_size = sizeof(so); so.n_threads = 2; so.max_active = max_active; so.chunk_tokens = c; so.row_budget = budget;
+                    llamahip_sched *sc = nullptr;
+                    EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                    if (!sc) continue;
+                    struct Want { std::vector<int32_t> prompt; int n_predict, stop; llamahip_sampler *smp; std::vector<int32_t> got; int done = 0, reason = 0, slot = -1, off = 0; };
+                    std::vector<Want> reqs;
+                    static const int plens[7] = { 1, 3, 9, 10, 20, 31, 40 }, npred[7] = { 1, 2, 5, 8, 3, 1, 4 };
+                    for (int i = 0; i < 7; i++) {
+                        Want w;
+                        w.prompt.resize((size_t) plens[i]);          // exactly sized: submit copies n_prompt ids and no more
+                        for (int32_t &t : w.prompt) t = (int32_t) (rng() % (uint32_t) V);
+                        w.n_predict = npred[i]; w.stop = -1; w.smp = i % 3 == 1 ? llamahip_sampler_new(i, 8) : nullptr;
+                        reqs.push_back(w);
+                    }
+                    std::vector<int64_t> ids(reqs.size());
+                    for (size_t i = 0; i < reqs.size(); i++) {
+                        llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                        rq.struct_size = sizeof(rq); rq.prompt = reqs[i].prompt.data(); rq.n_prompt = (int32_t) reqs[i].prompt.size();
+                        rq.n_predict = reqs[i].n_predict; rq.stop_token = reqs[i].stop; rq.sampler = reqs[i].smp;
+                        EXPECT(llamahip_sched_submit(sc, &rq, &ids[i], err, sizeof(err)) == 0 && ids[i] == (int64_t) i + 1);
+                        if (reqs[i].smp) EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // the sampler is held
+                    }
+                    EXPECT(llamahip_sched_cancel(sc, ids[6]) == 0 && llamahip_sched_cancel(sc, ids[6]) == -1 && llamahip_sched_cancel(sc, 99) == -1);      // a queued request
+                    // refusals of submit (exactly sized prompts) and of step: nothing is consumed
+                    {
+                        std::vector<int32_t> p1(1, V), p2(2, 1);
+                        llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                        rq.struct_size = sizeof(rq); rq.prompt = p1.data(); rq.n_prompt = 1; rq.n_predict = 1; rq.stop_token = -1;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);          // token id
+                        rq.prompt = p2.data(); rq.n_prompt = 2; rq.n_predict = 48;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);          // n_prompt + n_predict - 1 > n_ctx
+                        rq.n_predict = 0;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                        rq.n_predict = 1; rq.n_prompt = 0;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                        rq.n_prompt = 2; rq.stop_token = V;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+                        rq.stop_token = -1; rq.struct_size = 4;
+                        EXPECT(llamahip_sched_submit(sc, &rq, nullptr, nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+                        std::vector<llamahip_sched_event> small((size_t) 2 * max_active);
+                        int32_t ne = -1;
+                        const int32_t before = llamahip_sched_pending(sc);
+                        EXPECT(llamahip_sched_step(sc, small.data(), (int32_t) small.size(), &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0);
+                        EXPECT(llamahip_sched_pending(sc) == before && before == 7);
+                    }
+                    g_sched_calls.clear();
+                    std::vector<llamahip_sched_event> evs((size_t) 2 * max_active + 1);          // exactly the smallest cap
+                    std::vector<int> slot_req((size_t) max_active, -1), admit;          // admit: the active requests in admission order
+                    size_t next_q = 0, call = 0;
+                    int steps = 0, cancelled_seen = 0;
+                    bool cancel_active_done = false;
+                    while (llamahip_sched_pending(sc) > 0 && steps < 400) {
+                        int32_t ne = 0;
+                        EXPECT(llamahip_sched_step(sc, evs.data(), (int32_t) evs.size(), &ne, err, sizeof(err)) == 0);
+                        steps++;
+                        // the model of the step: cancelled actives leave, admissions (lowest slot, submission order; request 6 was cancelled while queued), the rule
+                        for (size_t k = 0; k < admit.size();) { if (reqs[(size_t) admit[k]].reason == -3) { slot_req[(size_t) reqs[(size_t) admit[k]].slot] = -1; admit.erase(admit.begin() + (long) k); } else k++; }
+                        for (int sl = 0; sl < max_active && next_q < 6; sl++)
+                            if (slot_req[(size_t) sl] < 0) { slot_req[(size_t) sl] = (int) next_q; reqs[next_q].slot = sl; admit.push_back((int) next_q); next_q++; }
+                        std::vector<int32_t> left, rows;
+                        for (int r : admit) left.push_back((int32_t) reqs[(size_t) r].prompt.size() - reqs[(size_t) r].off);
+                        plan_ref(left, c, budget, rows);
+                        if (!admit.empty()) {
+                            EXPECT(call < g_sched_calls.size());
+                            if (call >= g_sched_calls.size()) break;
+                            const SchedCall &sc_call = g_sched_calls[call++];
+                            size_t j = 0;
+                            bool any_prompt = false;
+                            for (size_t k = 0; k < admit.size(); k++) {
+                                if (rows[k] < 1) continue;
+                                Want &w = reqs[(size_t) admit[k]];
+                                EXPECT(j < sc_call.segs.size());
+                                if (j >= sc_call.segs.size()) break;
+                                const lh::SchedSeg &g = sc_call.segs[j];
+                                EXPECT(g.slot == w.slot && g.n_rows == rows[k] && g.sampler == w.smp && g.n_out == (int32_t) w.got.size());
+                                if (left[k] > 0) {
+                                    any_prompt = true;
+                                    EXPECT(g.pos == w.off && g.emit == (rows[k] == left[k]) && (c == 0 || w.off % c == 0));
+                                    EXPECT(std::equal(sc_call.toks[j].begin(), sc_call.toks[j].end(), w.prompt.begin() + w.off));
+                                    w.off += rows[k];
+                                } else {
+                                    EXPECT(g.emit == 1 && g.pos == (int32_t) (w.prompt.size() + w.got.size()) - 1 && sc_call.toks[j][0] == w.got.back());
+                                }
+                                if (g.emit) w.got.push_back(g.token);
+                                j++;
+                            }
+                            EXPECT(j == sc_call.segs.size() && sc_call.mixed == any_prompt);
+                        }
+                        // the events: a TOKEN per emitted token, DONE behind a request's last one; the model frees those slots
+                        for (int32_t e = 0; e < ne; e++) {
+                            const llamahip_sched_event &x = evs[(size_t) e];
+                            EXPECT(x.id >= 1 && x.id <= 7);
+                            Want &w = reqs[(size_t) (x.id - 1)];
+                            if (x.kind == LLAMAHIP_EV_TOKEN) { EXPECT(!w.got.empty() && x.token == w.got.back() && x.slot == w.slot && x.position == (int32_t) (w.prompt.size() + w.got.size()) - 1); }
+                            else {
+                                EXPECT(x.kind == LLAMAHIP_EV_DONE && !w.done);
+                                w.done = 1;
+                                if (x.reason == LLAMAHIP_DONE_CANCELLED) { cancelled_seen++; continue; }
+                                EXPECT(x.reason == LLAMAHIP_DONE_LENGTH && (int) w.got.size() == w.n_predict);
+                                w.reason = x.reason;
+                                slot_req[(size_t) w.slot] = -1;
+                                admit.erase(std::find(admit.begin(), admit.end(), (int) (x.id - 1)));
+                            }
+                        }
+                        // cancel an active request once it has produced a token (request 3: 10 prompt tokens, 8 to produce)
+                        if (!cancel_active_done && reqs[3].got.size() >= 1 && !reqs[3].done) {
+                            EXPECT(llamahip_sched_cancel(sc, ids[3]) == 0);
+                            reqs[3].reason = -3;
+                            cancel_active_done = true;
+                        }
+                    }
+                    EXPECT(llamahip_sched_pending(sc) == 0 && cancelled_seen == 2 && cancel_active_done);
+                    for (size_t i = 0; i < reqs.size(); i++) EXPECT(reqs[i].done == 1);
+                    llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                    EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_submitted == 7 && ss.n_done == 7 && ss.n_steps == (int64_t) g_sched_calls.size());
+                    EXPECT(ss.n_mixed_steps + ss.n_set_steps + ss.n_single_steps == ss.n_steps && ss.n_fallback_steps == 0);
+                    llamahip_sched_free(sc);
+                    for (Want &w : reqs) if (w.smp) llamahip_sampler_free(w.smp);
+                }
+        if (ms) {
+            // one scheduler per handle at a time; a step that fails delivers nothing and loses nothing (the waiting CANCELLED events, the
+            // admitted requests and the stats are all there for the step that succeeds)
+            llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+            so.struct_size = sizeof(so); so.max_active = 2; so.chunk_tokens = 9; so.row_budget = 16;
+            llamahip_sched *sa = nullptr, *sb = nullptr;
+            EXPECT(llamahip_sched_new(ms, &so, &sa, err, sizeof(err)) == 0 && sa);
+            EXPECT(llamahip_sched_new(ms, &so, &sb, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sb && strstr(err, "already"));
+            if (sa) {
+                std::vector<int32_t> p3(3, 1);
+                llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                rq.struct_size = sizeof(rq); rq.prompt = p3.data(); rq.n_prompt = 3; rq.n_predict = 2; rq.stop_token = -1;
+                int64_t id[3] = { 0, 0, 0 };
+                for (int i = 0; i < 3; i++) EXPECT(llamahip_sched_submit(sa, &rq, &id[i], err, sizeof(err)) == 0);
+                EXPECT(llamahip_sched_cancel(sa, id[2]) == 0);          // queued: its DONE waits for a step
+                std::vector<llamahip_sched_event> evs(5);
+                int32_t ne = -1;
+                g_sched_fail = true;
+                EXPECT(llamahip_sched_step(sa, evs.data(), 5, &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0 && llamahip_sched_pending(sa) == 3);
+                EXPECT(llamahip_sched_step(sa, evs.data(), 5, &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0 && llamahip_sched_pending(sa) == 3);
+                llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                EXPECT(llamahip_sched_get_stats(sa, &ss) == 0 && ss.n_done == 0 && ss.n_steps == 0 && ss.n_tokens == 0);
+                g_sched_fail = false;
+                g_sched_calls.clear();
+                EXPECT(llamahip_sched_step(sa, evs.data(), 5, &ne, err, sizeof(err)) == 0 && ne == 3);          // the CANCELLED DONE first, then a token per request
+                EXPECT(evs[0].id == id[2] && evs[0].kind == LLAMAHIP_EV_DONE && evs[0].reason == LLAMAHIP_DONE_CANCELLED && evs[1].kind == LLAMAHIP_EV_TOKEN && evs[2].kind == LLAMAHIP_EV_TOKEN);
+                EXPECT(g_sched_calls.size() == 1 && g_sched_calls[0].segs.size() == 2 && g_sched_calls[0].segs[0].pos == 0 && g_sched_calls[0].segs[0].n_rows == 3);
+                EXPECT(llamahip_sched_get_stats(sa, &ss) == 0 && ss.n_done == 1 && ss.n_steps == 1 && ss.n_tokens == 2);
+                llamahip_sched_free(sa);
+                EXPECT(llamahip_sched_new(ms, &so, &sb, err, sizeof(err)) == 0 && sb);          // free again after the first one is gone
+                llamahip_sched_free(sb);
+            }
+        }
+        // llamahip_sched_submit's row limit, on a handle whose context is long enough to reach it: with chunk_tokens 0 a prompt is one piece of
+        // at most LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active rows; in chunks the piece is the chunk -- and a chunk that long is refused the same way
+        {
+            llamahip_model *ml = nullptr;
+            EXPECT(llamahip_model_load(path.c_str(), 4096, &o, &ml, err, sizeof(err)) == 0);
+            for (int max_active : { 1, 3, 4 }) {
+                if (!ml) break;
+                const int lim = LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active;
+                std::vector<int32_t> fits((size_t) lim, 1), over((size_t) lim + 1, 1);          // exactly sized
+                for (int c : { 0, 9, 4000 }) {
+                    llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                    so.struct_size = sizeof(so); so.max_active = max_active; so.chunk_tokens = c;
+                    llamahip_sched *sc = nullptr;
+                    EXPECT(llamahip_sched_new(ml, &so, &sc, err, sizeof(err)) == 0 && sc);
+                    if (!sc) continue;
+                    llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                    rq.struct_size = sizeof(rq); rq.n_predict = 1; rq.stop_token = -1;
+                    rq.prompt = fits.data(); rq.n_prompt = lim;
+                    EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == 0);
+                    rq.prompt = over.data(); rq.n_prompt = lim + 1;
+                    err[0] = 0;
+                    const int rc = llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err));
+                    char want[32];
+                    snprintf(want, sizeof(want), "(%d)", lim);
+                    if (c == 9) EXPECT(rc == 0);          // pieces of 9 rows: accepted
+                    else EXPECT(rc == LLAMAHIP_ERR_PREDICT && strstr(err, "LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active") && strstr(err, want) && strstr(err, c ? "chunk_tokens" : "chunk_tokens 0"));
+                    EXPECT(llamahip_sched_pending(sc) == (c == 9 ? 2 : 1));
+                    llamahip_sched_free(sc);
+                }
+            }
+            if (ml) llamahip_model_free(ml);
+        }
+        if (ms) {
+            llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+            so.struct_size = sizeof(so); so.max_active = 2;
+            llamahip_sched *sc = nullptr;
+            so.max_active = 0;  EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.max_active = 17; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.max_active = 5;  EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);      // the stub handle has 4 slots
+            so.max_active = 2; so.chunk_tokens = -1; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.chunk_tokens = 0; so.row_budget = -1; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.row_budget = LLAMAHIP_EVAL_MULTI_MAX_ROWS - 15; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.row_budget = 0; so.temp = -1.0; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc);
+            so.temp = 0.0; EXPECT(llamahip_sched_new(nullptr, &so, &sc, nullptr, 0) == LLAMAHIP_ERR_PREDICT && !sc);
+            EXPECT(llamahip_sched_new(ms, nullptr, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+            llamahip_model_free(ms);
+        }
+        printf("host_sanitize: scheduler host half: %zu steps logged in the last run\n", g_sched_calls.size());
     }
     printf("host_sanitize: %zu tensor bytes merged, tokenizer + sampler + bridge failure path exercised: %s\n", total, failures ? "FAILED" : "clean");
     return failures ? 1 : 0;

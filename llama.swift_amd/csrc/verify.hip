@@ -23,6 +23,9 @@
 //   pick[0 .. n_accept] at the slot's cursor, the slot's {position, cursor} advance by n_accept + 1 and the slot's next-token word
 //   receives pick[n_accept] -- an ordinary set step or single step continues the slot from there.
 //   res = {n_accept[0 .. n_segs), pick[0 .. n_rows)}: 4 (n_rows + n_segs) bytes for the host.
+// k_sched_pick: the device half of a request scheduler's mixed pass (llamahip_sched_step), one wave per segment behind the lm head -- the
+//   greedy pick of every segment that emits, by the device function k_verify_rows picks with (vr_row_pick), into the result block, the
+//   slot's next-token word and its trace; every segment's slot {position, cursor} set behind its rows.  4 bytes per segment come back.
 #include <cmath>
 
 #include "kcommon.hip.h"
@@ -39,12 +42,9 @@ __device__ __forceinline__ void vr_take_dpp(float &v, int &i) {
     vr_take(v, i, ov, oi);
 }
 
-__global__ void __launch_bounds__(1024)
-k_verify_rows(const float *__restrict__ logits, int V, int32_t *__restrict__ pick) {
-    __shared__ float bv[16];
-    __shared__ int bi[16];
-    const int r = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
-    const float *__restrict__ row = logits + (size_t) r * V;
+// the greedy pick of one row by the whole workgroup (any whole number of waves up to 16; bv / bi: 16 LDS entries each): valid in thread 0
+__device__ __forceinline__ int vr_row_pick(const float *__restrict__ row, int V, float *bv, int *bi) {
+    const int tid = threadIdx.x, nt = blockDim.x;
     float best = -INFINITY;
     int idx = 0x7fffffff;
     for (int i0 = tid; i0 < V; i0 += 32 * nt) {
@@ -71,11 +71,43 @@ k_verify_rows(const float *__restrict__ logits, int V, int32_t *__restrict__ pic
         if ((tid & 63) == 0) { bv[tid >> 6] = wv; bi[tid >> 6] = wi; }
     }
     __syncthreads();
-    if (tid == 0) {
-        float v = bv[0];
-        int i = bi[0];
-        for (int w = 1; w < (nt >> 6); w++) vr_take(v, i, bv[w], bi[w]);
-        pick[r] = i == 0x7fffffff ? 0 : i;                    // (nothing taken: every entry a NaN)
+    float v = bv[0];
+    int i = bi[0];
+    for (int w = 1; w < (nt >> 6); w++) vr_take(v, i, bv[w], bi[w]);
+    return i == 0x7fffffff ? 0 : i;                           // (nothing taken: every entry a NaN)
+}
+
+__global__ void __launch_bounds__(1024)
+k_verify_rows(const float *__restrict__ logits, int V, int32_t *__restrict__ pick) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int p = vr_row_pick(logits + (size_t) blockIdx.x * V, V, bv, bi);
+    if (threadIdx.x == 0) pick[blockIdx.x] = p;
+}
+
+// The device half of a scheduler's mixed pass (llamahip_sched_step), one wave per segment (blockIdx.x), behind the lm head: row s of the
+// logits is segment s's last row.  tab[s] = {emit, slot, position, cursor}: a segment that emits takes its row's greedy pick by
+// vr_row_pick -- k_verify_rows' rule, not restated -- and res[s] receives it (-1 where it does not emit: four bytes per segment for the
+// host).  With slot words (state != null; all three or none): the slot's {position, cursor} become the segment's -- the position behind
+// its rows, the tokens its request has produced with this step -- and an emitting segment's pick goes to the slot's next-token word and
+// to its trace at cursor - 1, so that the next captured step continues the slot on the device.
+__global__ void __launch_bounds__(64)
+k_sched_pick(const float *__restrict__ logits, int V, const int32_t *__restrict__ tab, int32_t *__restrict__ state, int32_t *__restrict__ log,
+             int log_cap, int32_t *__restrict__ next_tok, int32_t *__restrict__ res) {
+    __shared__ float bv[16];
+    __shared__ int bi[16];
+    const int s = blockIdx.x;
+    const int emit = tab[4 * s], slot = tab[4 * s + 1], pos = tab[4 * s + 2], cur = tab[4 * s + 3];
+    int p = -1;
+    if (emit) p = vr_row_pick(logits + (size_t) s * V, V, bv, bi);          // (emit is uniform over the workgroup)
+    if (threadIdx.x != 0) return;
+    res[s] = p;
+    if (!state) return;
+    state[2 * (size_t) slot] = pos;
+    state[2 * (size_t) slot + 1] = cur;
+    if (emit) {
+        next_tok[slot] = p;
+        if (cur >= 1 && cur <= log_cap) log[(size_t) slot * log_cap + cur - 1] = p;
     }
 }
 
@@ -130,6 +162,16 @@ k_accept_drafts_set(const int32_t *__restrict__ tokens, const int32_t *__restric
 hipError_t launch_verify_rows(const float *logits, int n_rows, int V, int32_t *pick, hipStream_t st) {
     if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || V < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_verify_rows, dim3((unsigned) n_rows), dim3(1024), 0, st, logits, V, pick);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// tab: n_segs x {emit, slot, position, cursor} on the device; the slots are checked by the caller (< the rows of state / log / next_tok)
+hipError_t launch_sched_pick(const float *logits, int n_segs, int V, const int32_t *tab, int32_t *state, int32_t *log, int log_cap, int32_t *next_tok,
+                             int32_t *res, hipStream_t st) {
+    if (n_segs < 1 || n_segs > SET_MAX || V < 1 || !logits || !tab || !res) return hipErrorInvalidValue;
+    if (state && (!log || !next_tok || log_cap < 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sched_pick, dim3((unsigned) n_segs), dim3(64), 0, st, logits, V, tab, state, log, log_cap, next_tok, res);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -1,0 +1,136 @@
+#!/usr/bin/env python3
+"""The request scheduler (llamahip_sched_*) against what the library offers without it, on the synthetic 7B file.
+usage: sched_probe.py [--json OUT] [--budgets 16,32,64,128,256] [--repeats 3] [--requests 64]
+
+Workload: n_ctx 512, 16 KV slots, chunks of 9, 8 threads, greedy.  64 requests from a fixed seed: prompt lengths cycle through 9, 18, 36, 72, 144
+and 288 tokens; n_predict is a seeded permutation of 8, 16, 32, 64, 128 and 256 per cycle, capped at 224 = n_ctx - the longest prompt, so
+that a static wave (below) fits the context whatever it holds.
+Scheduler: all requests submitted at once, max_active 16, stepped until nothing is pending; every step is timed on its own.
+Baseline, in the same process, on the same handle: waves of 16 requests in submission order -- llamahip_eval_multi over the wave's prompts,
+then llamahip_decode_greedy_multi with n_steps = the wave's largest n_predict - 1 (every sequence is stepped to the end of the wave; only the
+tokens a request asked for are counted).
+The runs are interleaved (baseline, then every budget, `repeats` times over) after one untimed run of each.  Reported per configuration:
+median and min .. max of the aggregate tokens/s, the longest single step (what a decoding conversation waits while a prompt is admitted), the
+steps by kind, rows, graph captures; and what a capture costs: a set step that captured graphs against the next replayed set step of the same
+row count in the same run.
+LLAMAHIP_SCHED_ROW_BUDGET is the candidate with the highest median tokens/s; of candidates within the runs' spread of it, the smallest."""
+import json, os, statistics, subprocess, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+args = sys.argv[1:]
+opt = lambda k, d: args[args.index(k) + 1] if k in args else d
+BUDGETS = [int(x) for x in opt("--budgets", "16,32,64,128,256").split(",")]
+REPEATS, N_REQ = int(opt("--repeats", "3")), int(opt("--requests", "64"))
+MODEL = os.path.join(os.environ.get("LLAMAHIP_MODEL_DIR", "/tmp/llamahip_models"), "7B-seed20230312", "ggml-model-q4_0.bin")
+N_CTX, SLOTS, CHUNK, NTH = 512, 16, 9, 8
+LENS, PREDICTS = (9, 18, 36, 72, 144, 288), (8, 16, 32, 64, 128, 256)
+
+
+def main():
+    import numpy as np
+    import llama_swift_amd as L
+    subprocess.run(["bash", os.path.join(ROOT, "tools", "ensure_7b.sh")], cwd=ROOT, check=True)
+    rng = np.random.default_rng(20240611)
+    m = L.Model(MODEL, n_ctx=N_CTX, n_seq=SLOTS)
+    reqs = []
+    for i in range(N_REQ):
+        if i % len(PREDICTS) == 0:
+            perm = rng.permutation(PREDICTS)
+        n = LENS[i % len(LENS)]
+        prompt = np.concatenate([[1], rng.integers(3, m.n_vocab, n - 1)]).astype(np.int32)
+        reqs.append((prompt, int(min(perm[i % len(PREDICTS)], N_CTX - max(LENS)))))
+    asked = sum(k for _, k in reqs)
+
+    def run_sched(budget):
+        steps, out = [], {}
+        with m.scheduler(max_active=SLOTS, chunk_tokens=CHUNK, row_budget=budget, n_threads=NTH) as sc:
+            ids = [sc.submit(p, k) for p, k in reqs]
+            before = sc.stats()
+            t_all = time.perf_counter()
+            while sc.pending():
+                t0 = time.perf_counter()
+                ev = sc.step()
+                dt = (time.perf_counter() - t0) * 1e3
+                st = sc.stats()
+                kind = next(k for k in ("mixed", "set", "single", "fallback") if st[f"n_{k}_steps"] != before[f"n_{k}_steps"])
+                steps.append((kind, dt, st["n_graph_captures"] - before["n_graph_captures"], st["n_rows"] - before["n_rows"]))
+                before = st
+                for e in ev:
+                    if e["kind"] == "token":
+                        out.setdefault(e["id"], []).append(e["token"])
+            wall = time.perf_counter() - t_all
+        toks = [out[i] for i in ids]
+        assert [len(t) for t in toks] == [k for _, k in reqs]
+        return wall, steps, st, toks
+
+    def run_waves():
+        toks, t_eval, t_dec, n_steps_all = [], 0.0, 0.0, 0
+        t_all = time.perf_counter()
+        for w0 in range(0, N_REQ, SLOTS):
+            wave = reqs[w0:w0 + SLOTS]
+            t0 = time.perf_counter()
+            lg = m.eval_multi(list(range(len(wave))), [0] * len(wave), [p for p, _ in wave], chunk_tokens=CHUNK, n_threads=NTH)
+            t1 = time.perf_counter()
+            first = [int(np.argmax(lg[i])) for i in range(len(wave))]
+            n_steps = max(k for _, k in wave) - 1
+            rest = m.decode_greedy_multi(first, [len(p) for p, _ in wave], n_steps, n_threads=NTH) if n_steps > 0 else np.zeros((len(wave), 0), np.int32)
+            t_dec += time.perf_counter() - t1
+            t_eval += t1 - t0
+            n_steps_all += n_steps
+            toks += [[first[i]] + rest[i, :k - 1].tolist() for i, (_, k) in enumerate(wave)]
+        return time.perf_counter() - t_all, t_eval, t_dec, n_steps_all, toks
+
+    # one untimed run of each (graphs captured, workspaces grown), and the two ways must produce the same tokens
+    _, _, _, _, want = run_waves()
+    for b in BUDGETS:
+        _, _, _, got = run_sched(b)
+        assert got == want, f"row_budget {b}: the scheduler's tokens are not the static waves'"
+    base, runs = [], {b: [] for b in BUDGETS}
+    for _ in range(REPEATS):
+        base.append(run_waves()[:4])
+        for b in BUDGETS:
+            runs[b].append(run_sched(b)[:3])
+    spread = lambda xs: {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+    res = {"model": "7B synthetic (seed 20230312), Q4_0", "n_ctx": N_CTX, "max_active": SLOTS, "chunk_tokens": CHUNK, "n_threads": NTH,
+           "requests": N_REQ, "prompt_tokens": int(sum(len(p) for p, _ in reqs)), "tokens_asked": int(asked), "repeats": REPEATS,
+           "library": os.path.basename(L.LIB_PATH),
+           "method": "one process, one handle; static waves and every budget interleaved, `repeats` times, after one untimed run of each; wall time around the whole run and around every scheduler step",
+           "static_waves": {"tokens_per_s": spread([asked / w for w, _, _, _ in base]), "eval_multi_s": spread([e for _, e, _, _ in base]),
+                            "decode_multi_s": spread([d for _, _, d, _ in base]), "set_steps": base[0][3]},
+           "scheduler": []}
+    print(f"static waves: {res['static_waves']['tokens_per_s']} tokens/s, {base[0][3]} set steps", flush=True)
+    for b in BUDGETS:
+        tps = [asked / w for w, _, _ in runs[b]]
+        steps, st = runs[b][-1][1], runs[b][-1][2]
+        by = {k: [dt for kk, dt, _, _ in steps if kk == k] for k in ("mixed", "set", "single")}
+        # what a capture costs: a set step that captured graphs against the next replayed (already captured) set step of the same row count in the same run
+        capt = []
+        for r in runs[b]:
+            ss = [x for x in r[1] if x[0] == "set"]
+            for i, (_, dt, c, rows) in enumerate(ss):
+                nxt = [x for x in ss[i + 1:i + 4] if x[2] == 0 and x[3] == rows]
+                if c > 0 and nxt:
+                    capt.append((dt - nxt[0][1]) / c)
+        row = {"row_budget": b, "tokens_per_s": spread(tps), "longest_step_ms": spread([max(dt for _, dt, _, _ in r[1]) for r in runs[b]]),
+               "steps": {k: len(v) for k, v in by.items()}, "step_ms_median": {k: round(statistics.median(v), 3) for k, v in by.items() if v},
+               "mixed_step_rows_max": max([r for k, _, _, r in steps if k == "mixed"] or [0]),
+               "rows": st["n_rows"], "prompt_rows": st["n_prompt_rows"], "graph_captures_per_run": [r[2]["n_graph_captures"] for r in runs[b]],
+               "capture_ms": spread(capt) if capt else None, "captures_timed": len(capt),
+               "capture_share_of_wall": round(sum(capt) / 1e3 / sum(w for w, _, _ in runs[b]), 4) if capt else 0.0}
+        res["scheduler"].append(row)
+        print(f"budget {b:3d}: {row['tokens_per_s']} tokens/s | longest step {row['longest_step_ms']['median']} ms | steps {row['steps']} "
+              f"| captures {row['graph_captures_per_run']} at {row['capture_ms']} ms", flush=True)
+    best = max(res["scheduler"], key=lambda r: r["tokens_per_s"]["median"])
+    near = [r for r in res["scheduler"] if r["tokens_per_s"]["median"] >= best["tokens_per_s"]["median"] - (best["tokens_per_s"]["max"] - best["tokens_per_s"]["min"])]
+    res["choice"] = {"row_budget": min(r["row_budget"] for r in near), "best_median": best["row_budget"],
+                     "rule": "highest median tokens/s; of the candidates within the best one's min .. max spread of it, the smallest (shorter stalls)"}
+    print("choice:", res["choice"], flush=True)
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+    m.close()
+
+
+if __name__ == "__main__":
+    main()
