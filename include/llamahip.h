@@ -926,6 +926,12 @@ int64_t llamahip_debug_set_probe(uint64_t *records, int64_t cap, int32_t reset);
  * gathering them -- enabled only after a load-time check that all 65 536 entries are reproduced.  0 before any load. */
 int32_t llamahip_debug_lut_math(void);
 
+/* Host-only (no device needed): the device and pinned-host allocations this library holds at this moment, process-wide -- every model
+ * handle's (weights, KV cache, workspaces, slots, set descriptors) and the scratch of a single-op call while it runs -- and their bytes.
+ * Either pointer may be null.  The library's own exact count: a handle that is freed brings both back to what they were before its load,
+ * which free device memory as the runtime reports it cannot show on a card that other processes use.  Tests. */
+void llamahip_debug_live_allocs(int64_t *n, int64_t *bytes);
+
 typedef struct llamahip_stats {
     int32_t struct_size;
     int64_t weight_bytes_device;   /* repacked Q4_0 bytes resident in HBM */

@@ -33,6 +33,7 @@ from .binding import (  # noqa: F401
     eval_multi_rows,
     gemm_paths,
     lib,
+    live_allocs,
     lookup_deal_rows,
     lookup_draft,
     op_attention,

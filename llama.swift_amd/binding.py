@@ -223,6 +223,8 @@ def lib() -> C.CDLL:
     L.llamahip_debug_dense_mfma_launches.restype = C.c_int64
     L.llamahip_debug_dense_force.argtypes = [i32]
     L.llamahip_debug_dense_force.restype = i32
+    L.llamahip_debug_live_allocs.argtypes = [vp, vp]
+    L.llamahip_debug_live_allocs.restype = None
     _lib = L
     return L
 
@@ -299,6 +301,14 @@ def dense_force(path=0) -> str:
     if prev < 0:
         raise ValueError(f"dense_force({path!r}): 0 / 'auto', 'mm' or 'mfma'")
     return DENSE_PATHS[prev]
+
+
+def live_allocs() -> tuple:
+    """(allocations, bytes) of device / pinned memory the library holds right now, process-wide (llamahip_debug_live_allocs): its own exact
+    count, so a leak check compares it before a handle's load and after its free."""
+    n, b = C.c_int64(0), C.c_int64(0)
+    lib().llamahip_debug_live_allocs(C.byref(n), C.byref(b))
+    return int(n.value), int(b.value)
 
 
 def version() -> str:

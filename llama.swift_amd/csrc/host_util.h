@@ -6,9 +6,11 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <map>
 #include <vector>
 
 #include "../../include/llamahip.h"
+#include "dev_owner.h"
 
 namespace lh {
 
@@ -16,14 +18,12 @@ void set_err(char *err, size_t cap, const char *fmt, ...) __attribute__((format(
 
 #define HIP_TRY(expr, code)                                                                          \
     do {                                                                                             \
-        hipError_t e_ = (expr);                                                                      \
+        hipError_t e_ = (hipError_t) (expr);      /* (DevOwner reports the runtime's codes as int) */ \
         if (e_ != hipSuccess) {                                                                      \
             lh::set_err(err, err_cap, "HIP error: %s (%s) at %s:%d", hipGetErrorString(e_), #expr, __FILE__, __LINE__); \
             return (code);                                                                           \
         }                                                                                            \
     } while (0)
-
-inline void free_dev(void *p) { if (p) (void) hipFree(p); }
 
 // there is no CPU fallback: 0 with a device, else LLAMAHIP_ERR_PREDICT and the message
 inline int need_device(char *err, size_t err_cap) {
@@ -58,36 +58,78 @@ inline void qa_to_q4_0_blocks(const uint32_t *qa_A, const float *qa_d, int N, in
         }
 }
 
+// The owning holders of what is not memory.  Events: created through it, destroyed with it.
+struct Events {
+    std::vector<hipEvent_t> evs;
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() { for (hipEvent_t ev : evs) (void) hipEventDestroy(ev); }
+    hipError_t create(hipEvent_t *out, unsigned flags = hipEventDefault) {
+        *out = nullptr;
+        const hipError_t e = hipEventCreateWithFlags(out, flags);
+        if (e == hipSuccess) evs.push_back(*out);
+        return e;
+    }
+    size_t size() const { return evs.size(); }
+    hipEvent_t operator[](size_t i) const { return evs[i]; }
+};
+// Captured steps by key: the cache owns its hipGraphExec_t values (an entry without one, exec == nullptr, is a step that runs un-captured).
+// Whoever erases or clears waits for the device first where a caller's stream may still run an exec.  Payload: what travels with an entry.
+struct NoPayload {};
+template <class Key, class Payload = NoPayload> struct GraphCache {
+    struct Entry : Payload { hipGraphExec_t exec = nullptr; };
+    std::map<Key, Entry> map;
+    GraphCache() = default;
+    GraphCache(const GraphCache &) = delete;
+    GraphCache &operator=(const GraphCache &) = delete;
+    GraphCache(GraphCache &&o) noexcept : map(std::move(o.map)) { o.map.clear(); }      // (std::vector<StageSlot>::resize)
+    ~GraphCache() { clear(); }
+    Entry *find(const Key &k) { auto it = map.find(k); return it == map.end() ? nullptr : &it->second; }
+    Entry *put(const Key &k, hipGraphExec_t exec, const Payload &p = Payload()) {
+        erase(k);
+        Entry &e = map[k];
+        (Payload &) e = p; e.exec = exec;
+        return &e;
+    }
+    void erase(const Key &k) {
+        auto it = map.find(k);
+        if (it == map.end()) return;
+        if (it->second.exec) (void) hipGraphExecDestroy(it->second.exec);
+        map.erase(it);
+    }
+    void clear() {
+        for (auto &kv : map) if (kv.second.exec) (void) hipGraphExecDestroy(kv.second.exec);
+        map.clear();
+    }
+    size_t size() const { return map.size(); }
+};
+
 // Device memory, a stream and events that live for ONE call.  The first HIP error sticks: after it alloc returns null and upload /
 // download / fill / sync do nothing, so a body reads top to bottom, guards its launches with `if (s.ok()) s.check(launch_...)` and
 // asks once at the end.  The destructor releases everything on every return path.
 struct Scratch {
-    std::vector<void *> bufs;
-    std::vector<hipEvent_t> events;
+    DevOwner bufs;
+    Events events;
     hipStream_t st = nullptr;
     hipError_t e = hipSuccess;
     Scratch() = default;
     Scratch(const Scratch &) = delete;
     Scratch &operator=(const Scratch &) = delete;
-    ~Scratch() {
-        for (void *p : bufs) (void) hipFree(p);
-        for (hipEvent_t ev : events) (void) hipEventDestroy(ev);
-        if (st) (void) hipStreamDestroy(st);
-    }
+    ~Scratch() { if (st) (void) hipStreamDestroy(st); }
     bool ok() const { return e == hipSuccess; }
     hipError_t error() const { return e; }
     void check(hipError_t r) { if (ok()) e = r; }
     template <class T> T *alloc(size_t count, const T *init = nullptr) {      // init: uploaded at once
-        void *p = nullptr;
-        if (ok()) check(hipMalloc(&p, count * sizeof(T)));
+        T *p = nullptr;
+        if (ok()) check((hipError_t) bufs.alloc(&p, count));
         if (!ok()) return nullptr;
-        bufs.push_back(p);
         if (init) upload(p, init, count * sizeof(T));
-        return (T *) p;
+        return p;
     }
     // without a stream the copies and fills below are the synchronous ones on the null stream
     hipStream_t stream() { if (ok() && !st) check(hipStreamCreate(&st)); return st; }
-    hipEvent_t event() { hipEvent_t ev = nullptr; if (ok()) check(hipEventCreate(&ev)); if (ev) events.push_back(ev); return ev; }
+    hipEvent_t event() { hipEvent_t ev = nullptr; if (ok()) check(events.create(&ev)); return ev; }
     void upload(void *dst, const void *src, size_t bytes) { if (ok()) check(st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) : hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); }
     void download(void *dst, const void *src, size_t bytes) { if (ok()) check(st ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st) : hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost)); }
     void fill(void *dst, int byte, size_t bytes) { if (ok()) check(st ? hipMemsetAsync(dst, byte, bytes, st) : hipMemset(dst, byte, bytes)); }

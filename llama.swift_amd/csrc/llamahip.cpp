@@ -155,6 +155,10 @@ struct llamahip_model {
     int flags = 0;
     bool host_only = false;
     hipStream_t stream = nullptr;
+    // Every device / pinned allocation of this handle, of its slots and of its set descriptors is registered here; the members below are
+    // views.  Declared before the graph caches and the events: members go in reverse order, so the memory is released after them -- and
+    // after the destructor's device-wide wait.
+    DevOwner own;
 
     // weights
     uint8_t *tok_emb = nullptr;          // file-layout rows (gathered, never streamed)
@@ -225,7 +229,7 @@ struct llamahip_model {
                                                      // a: of the row in x (attention / final norm), b: of the row in x1 (ffn norm)
     int n_seq = 1, cur_seq = 0;          // KV caches: [seq][layer][n_ctx][d]
     AttnWs attn_ws;                      // many-row prompt attention workspace (allocated with the first eval of >= 2 tokens: ensure_attn_ws)
-    std::map<int, hipGraphExec_t> decode_graphs;   // keyed by nth * 4096 + seq + (attention schedule << 24)
+    GraphCache<int> decode_graphs;                 // keyed by nth * 4096 + seq + (attention schedule << 24)
     int attn_sched = 0;                            // decode attention schedule of the single-row pass being launched / captured (attn_sched_at): 0 fused, 1 two launches, 2 long-context
     // asynchronous pipeline-stage steps (llamahip_stage_bind / llamahip_stage_step)
     struct StageSlot {
@@ -237,12 +241,12 @@ struct llamahip_model {
         bool peer_hidden_ipc = false, peer_token_ipc = false;         // opened with hipIpcOpenMemHandle (closed with the handle)
         bool bound = false;
         int next_pos = 0;                                       // host mirror of the device position (bounds check)
-        std::map<int, hipGraphExec_t> graphs;                   // keyed by nth + (attention schedule << 16)
+        GraphCache<int> graphs;                                 // keyed by nth + (attention schedule << 16)
     };
     std::vector<StageSlot> slots;        // one per sequence slot
     // batched decode steps over a SET of slots (llamahip_stage_step_set): one captured graph + device-resident row descriptor per set
-    struct SetGraph { SeqSet *d_set = nullptr; hipGraphExec_t exec = nullptr; uint64_t last_use = 0; };
-    std::map<std::vector<int>, SetGraph> set_graphs;      // key: {n_threads, slot ids in ascending order}: at most SET_GRAPHS_MAX, least recently used evicted
+    struct SetGraph { SeqSet *d_set = nullptr; uint64_t last_use = 0; };      // (d_set: through `own`, released on eviction and on clear)
+    GraphCache<std::vector<int>, SetGraph> set_graphs;    // key: {n_threads, slot ids in ascending order}: at most SET_GRAPHS_MAX, least recently used evicted
     uint64_t set_graph_clock = 0;
     int64_t n_set_captures = 0;          // set steps captured (or, with LLAMAHIP_FLAG_NO_GRAPH, set descriptors built) since the load: llamahip_sched_stats
     std::vector<int> last_rows;          // llamahip_stage_logits: row of the caller's i-th slot in the most recent set step (empty: identity)
@@ -263,11 +267,12 @@ struct llamahip_model {
     int pipe_in_cap = 0;
     float *pipe_hout = nullptr;          // decode steps: the row this stage hands on, [n_embd]
     int32_t *pipe_tok = nullptr;         // decode steps: first stage token_in / last stage token_out
-    hipEvent_t pipe_ev = nullptr;        // recorded on this stage's stream behind its hand-off
+    hipEvent_t pipe_ev = nullptr;        // recorded on this stage's stream behind its hand-off (owned by `events`)
+    Events events;
     // llamahip_decode_greedy_multi (any handle; on the stages of a pipeline handle): per-slot rows in / out and token words, one event per group of slots
     float *mq_in = nullptr, *mq_out = nullptr;     // [n_seq][n_embd]
     int32_t *mq_tok = nullptr;                     // [n_seq]
-    std::vector<hipEvent_t> mq_ev;
+    Events mq_ev;
     // llamahip_decode_sample_multi: one pinned, device-mapped block per stage -- the first stage's token words, the last stage's sampler windows,
     // candidates and spilled rows -- and (last stage) the selection workspace of SET_MAX rows
     struct SampleIo { int32_t *tok = nullptr, *n_last = nullptr, *win = nullptr; TopkOut *out = nullptr; float *spill = nullptr; };
@@ -301,6 +306,20 @@ static hipError_t malloc_mailbox(void **p, size_t bytes) {
     // gets an error, reports "mailboxes unavailable" and the pipeline keeps its RCCL hand-off
     return hipErrorNotSupported;
 }
+// DevOwner's allocator in the library, by kind; the zero fill is the synchronous one
+int lh::dev_alloc_default(void **p, size_t bytes, int kind, bool zero) {
+    *p = nullptr;
+    hipError_t e = kind == MEM_PINNED ? hipHostMalloc(p, bytes, hipHostMallocMapped) : kind == MEM_MAILBOX ? malloc_mailbox(p, bytes) : hipMalloc(p, bytes);
+    if (e == hipSuccess && zero) {
+        if (kind == MEM_PINNED) memset(*p, 0, bytes);
+        else if ((e = hipMemset(*p, 0, bytes)) != hipSuccess) { dev_release_default(*p, kind); *p = nullptr; }
+    }
+    return (int) e;
+}
+void lh::dev_release_default(void *p, int kind) {
+    if (kind == MEM_PINNED) (void) hipHostFree(p);
+    else (void) hipFree(p);
+}
 
 llamahip_model::~llamahip_model() {
     if (sched) lh::sched_dev_orphan(sched);          // (a scheduler that outlives its handle: every later call on it fails, none touches the handle)
@@ -308,46 +327,10 @@ llamahip_model::~llamahip_model() {
     if (host_only) return;
     (void) hipSetDevice(device);
     (void) hipDeviceSynchronize();      // captured steps may still run on a caller's stream: nothing is freed or destroyed under them
-    free_dev(d_sched_tab);
-    free_dev(tok_emb); free_dev(norm_w); free_dev(output.tiles); free_dev(doutput.w); free_dev(doutput.w2);
-    for (auto &l : layers) {
-        free_dev(l.attention_norm); free_dev(l.ffn_norm);
-        free_dev(l.qkv.tiles); free_dev(l.wo.tiles); free_dev(l.w13.tiles); free_dev(l.w2.tiles);
-        free_dev(l.qkv.rows); free_dev(l.wo.rows); free_dev(l.w13.rows); free_dev(l.w2.rows);
-        free_dev(l.qkv.mt); free_dev(l.wo.mt); free_dev(l.w13.mt); free_dev(l.w2.mt);
-        free_dev(l.qkv.mt4); free_dev(l.wo.mt4); free_dev(l.w13.mt4); free_dev(l.w2.mt4);
-        free_dev(l.dqkv.w); free_dev(l.dwo.w); free_dev(l.dw13.w); free_dev(l.dw2.w);
-        free_dev(l.dqkv.w2); free_dev(l.dwo.w2); free_dev(l.dw13.w2); free_dev(l.dw2.w2);
-    }
-    free_dev(Kc); free_dev(Vc); free_dev(T_silu); free_dev(T_exp); free_dev(sincos);
-    free_dev(d_tokens); free_dev(x); free_dev(x1); free_dev(qkv); free_dev(qr); free_dev(merged); free_dev(gu);
-    free_dev(tmp); free_dev(logits); free_dev(qa_A); free_dev(qa_d); free_dev(qb_ws); free_dev(dbg_y); free_dev(dbg_p); free_dev(dbg_kqv);
-    free_dev(qaF_A); free_dev(qaF_d);
-    free_dev(d_out_tokens); free_dev(d_topk); free_dev(d_score); free_dev(d_verify); free_dev(d_vset); free_dev(d_slide); free_dev(d_slide_set);
-    free_dev(output.rows); free_dev(output.mt); free_dev(output.mt4);
-    free_dev(d_pick); free_dev(d_w13_amax); free_dev(d_set_amax);
-    free_dev(npart_a); free_dev(npart_b); free_dev(d_attn_sync); free_dev(d_qkv2); free_dev(d_sc2); free_dev(d_epoch); free_dev(d_pvx);
-    if (h_fault) { (void) hipHostFree(h_fault); h_fault = nullptr; }
-    if (h_io) { (void) hipHostFree(h_io); h_io = nullptr; }
-    free_dev(d_state); free_dev(sc); free_dev(part); free_dev(qa1_A); free_dev(qa2_A); free_dev(qa1_d); free_dev(qa2_d);
-    for (auto &kv : decode_graphs) (void) hipGraphExecDestroy(kv.second);
     for (auto &sl : slots) {
-        for (auto &kv : sl.graphs) (void) hipGraphExecDestroy(kv.second);
         if (sl.peer_hidden && sl.peer_hidden_ipc) (void) hipIpcCloseMemHandle(sl.peer_hidden);
         if (sl.peer_token && sl.peer_token_ipc) (void) hipIpcCloseMemHandle(sl.peer_token);
-        free_dev(sl.inbox_hidden); free_dev(sl.inbox_token);
     }
-    for (auto &kv : set_graphs) { if (kv.second.exec) (void) hipGraphExecDestroy(kv.second.exec); free_dev(kv.second.d_set); }
-    free_dev(set_sc);
-    free_dev(d_slot_state); free_dev(d_slot_trace);
-    free_dev(attn_ws.S); free_dev(attn_ws.pmax); free_dev(attn_ws.inv); free_dev(attn_ws.part);
-    free_dev(pipe_in); free_dev(pipe_hout); free_dev(pipe_tok);
-    free_dev(mq_in); free_dev(mq_out); free_dev(mq_tok);
-    for (hipEvent_t e : mq_ev) (void) hipEventDestroy(e);
-    if (smp_blk) { (void) hipHostFree(smp_blk); smp_blk = nullptr; }
-    free_dev(smp_ws);
-    free_dev(d_rows);
-    if (pipe_ev) (void) hipEventDestroy(pipe_ev);
     if (stream) (void) hipStreamDestroy(stream);
 }
 
@@ -373,45 +356,39 @@ int upload_dense(llamahip_model *m, const std::string &name, DMat &dst, int row0
     h_stage.resize((size_t) t.nbytes());
     std::string e;
     if (!m->file.read_tensor(name, h_stage.data(), e)) { set_err(err, err_cap, "%s", e.c_str()); return LLAMAHIP_ERR_LOAD; }
+    // the raw rows on the device for the length of this call (released on every return path)
+    DevOwner staging;
+    uint8_t *d_raw = nullptr;
+    HIP_TRY(staging.alloc(&d_raw, h_stage.size()), LLAMAHIP_ERR_LOAD);
+    HIP_TRY(hipMemcpy(d_raw, h_stage.data(), h_stage.size(), hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
+    hipError_t e1;
     if (dst.wtype == 3) {
         // Q4_1: regroup the rows into [row-block of 64][block][lane] (dense.hip); row0 is a multiple of 64
-        uint8_t *d_raw = nullptr;
-        HIP_TRY(hipMalloc((void **) &d_raw, h_stage.size()), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemcpy(d_raw, h_stage.data(), h_stage.size(), hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         DMat view = dst;
         const size_t at = (size_t) (row0 / 64) * (dst.K / 32) * 64;
         view.w = (uint8_t *) dst.w + at * 8; view.w2 = (uint8_t *) dst.w2 + at * 16; view.M = (int) t.ne1;
-        hipError_t e1 = launch_q41_repack(d_raw, view, m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        (void) hipFree(d_raw);
-        HIP_TRY(e1, LLAMAHIP_ERR_LOAD);
-        HIP_TRY(e2, LLAMAHIP_ERR_LOAD);
-        return 0;
+        e1 = launch_q41_repack(d_raw, view, m->stream);
+    } else {
+        // f16 / f32: rows into the chain-major order the dense mat-mul reads (dense.hip perm_index)
+        e1 = launch_dense_perm_rows(d_raw, dst, row0, (int) t.ne1, m->stream);
     }
-    {   // f16 / f32: rows into the chain-major order the dense mat-mul reads (dense.hip perm_index)
-        uint8_t *d_raw = nullptr;
-        HIP_TRY(hipMalloc((void **) &d_raw, h_stage.size()), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemcpy(d_raw, h_stage.data(), h_stage.size(), hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
-        hipError_t e1 = launch_dense_perm_rows(d_raw, dst, row0, (int) t.ne1, m->stream);
-        hipError_t e2 = hipStreamSynchronize(m->stream);
-        (void) hipFree(d_raw);
-        HIP_TRY(e1, LLAMAHIP_ERR_LOAD);
-        HIP_TRY(e2, LLAMAHIP_ERR_LOAD);
-    }
+    const hipError_t e2 = hipStreamSynchronize(m->stream);      // (also after a failed launch: d_raw goes with this call)
+    HIP_TRY(e1, LLAMAHIP_ERR_LOAD);
+    HIP_TRY(e2, LLAMAHIP_ERR_LOAD);
     return 0;
 }
 
 int alloc_dmat(DMat &q, int M, int K, llamahip_model *m, char *err, size_t err_cap) {
     q.M = M; q.K = K; q.wtype = m->hp.f16;
-    HIP_TRY(hipMalloc(&q.w, q.bytes()), LLAMAHIP_ERR_LOAD);
-    if (q.bytes2()) HIP_TRY(hipMalloc(&q.w2, q.bytes2()), LLAMAHIP_ERR_LOAD);
+    HIP_TRY(m->own.alloc(&q.w, q.bytes()), LLAMAHIP_ERR_LOAD);
+    if (q.bytes2()) HIP_TRY(m->own.alloc(&q.w2, q.bytes2()), LLAMAHIP_ERR_LOAD);
     m->weight_bytes += (int64_t) (q.bytes() + q.bytes2());
     return 0;
 }
 
 int alloc_qmat(QMat &q, int M, int K, llamahip_model *m, char *err, size_t err_cap) {
     q.set_shape(M, K);
-    HIP_TRY(hipMalloc((void **) &q.tiles, q.bytes()), LLAMAHIP_ERR_LOAD);
+    HIP_TRY(m->own.alloc(&q.tiles, q.bytes()), LLAMAHIP_ERR_LOAD);
     m->weight_bytes += (int64_t) q.bytes();
     return 0;
 }
@@ -430,10 +407,8 @@ int make_rows(QMat &q, llamahip_model *m) {
     if (m->flags & LLAMAHIP_FLAG_NO_PREFILL_COPY) return 0;
     auto build = [&](uint8_t **slot, size_t bytes, auto convert) -> bool {
         if (*slot) return true;
-        uint8_t *p = nullptr;
-        if (hipMalloc((void **) &p, bytes) != hipSuccess) { (void) hipGetLastError(); return false; }
-        *slot = p;                                   // (the conversion launchers read the destination from the QMat)
-        if (convert() != hipSuccess) { (void) hipGetLastError(); (void) hipFree(p); *slot = nullptr; return false; }
+        if (m->own.alloc(slot, bytes) != 0) { (void) hipGetLastError(); return false; }      // (the conversion launchers read the destination from the QMat)
+        if (convert() != hipSuccess) { (void) hipGetLastError(); m->own.release(slot); return false; }
         m->weight_bytes += (int64_t) bytes;
         return true;
     };
@@ -477,14 +452,45 @@ int upload_f32(llamahip_model *m, const std::string &name, float **dst, char *er
     std::vector<uint8_t> h((size_t) t.nbytes());
     std::string e;
     if (!m->file.read_tensor(name, h.data(), e)) { set_err(err, err_cap, "%s", e.c_str()); return LLAMAHIP_ERR_LOAD; }
-    HIP_TRY(hipMalloc((void **) dst, h.size()), LLAMAHIP_ERR_LOAD);
+    HIP_TRY(m->own.alloc((void **) dst, h.size()), LLAMAHIP_ERR_LOAD);
     HIP_TRY(hipMemcpy(*dst, h.data(), h.size(), hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
     return 0;
 }
 
 void drop_set_graphs(llamahip_model *m) {
-    for (auto &kv : m->set_graphs) { if (kv.second.exec) (void) hipGraphExecDestroy(kv.second.exec); free_dev(kv.second.d_set); }
+    for (auto &kv : m->set_graphs.map) m->own.release(&kv.second.d_set);
     m->set_graphs.clear();
+}
+// the slot tables: {position, step} and the picks of every KV slot, with the host's slot records behind them
+int ensure_slots(llamahip_model *m, char *err, size_t err_cap) {
+    if (m->d_slot_state) return 0;
+    HIP_TRY(m->own.alloc_all({ { &m->d_slot_state, (size_t) m->n_seq * 2 * sizeof(int32_t) },
+                               { &m->d_slot_trace, (size_t) m->n_seq * m->hp.n_ctx * sizeof(int32_t) } }), LLAMAHIP_ERR_PREDICT);
+    m->slots.resize(m->n_seq);
+    return 0;
+}
+// the attention scores of a set step: [SET_MAX][H][n_ctx]
+int ensure_set_sc(llamahip_model *m, char *err, size_t err_cap) {
+    if (!m->set_sc) HIP_TRY(m->own.alloc(&m->set_sc, (size_t) SET_MAX * m->hp.n_head * m->hp.n_ctx), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// The one capture path: the launches of a step (`body` issues them on m->stream and returns the project's code) recorded into an executable
+// graph.  The capture is always ended and the hipGraph_t destroyed on every path.  Returns the body's code if that is non-zero, else
+// LLAMAHIP_ERR_PREDICT with the HIP text on a runtime error; *exec is set on success only.
+template <class Body> int capture_step(llamahip_model *m, Body body, hipGraphExec_t *exec, char *err, size_t err_cap) {
+    *exec = nullptr;
+    HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal), LLAMAHIP_ERR_PREDICT);
+    const int rc = body();
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t made = nullptr;
+    hipError_t e = hipStreamEndCapture(m->stream, &graph);
+    if (!rc && e == hipSuccess) e = hipGraphInstantiate(&made, graph, nullptr, nullptr, 0);
+    if (graph) (void) hipGraphDestroy(graph);
+    if (rc) return rc;
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
+    *exec = made;
+    return 0;
 }
 int ensure_workspace(llamahip_model *m, int N, char *err, size_t err_cap) {
     if (N <= m->ws_cap) return 0;
@@ -492,44 +498,27 @@ int ensure_workspace(llamahip_model *m, int N, char *err, size_t err_cap) {
     // _step_set), so the handle's own stream says nothing about them: wait for the device before an exec or a buffer goes
     HIP_TRY(hipDeviceSynchronize(), LLAMAHIP_ERR_PREDICT);
     drop_set_graphs(m);
-    for (auto &kv : m->decode_graphs) (void) hipGraphExecDestroy(kv.second);
     m->decode_graphs.clear();
-    for (auto &sl : m->slots) {
-        for (auto &kv : sl.graphs) (void) hipGraphExecDestroy(kv.second);
-        sl.graphs.clear();
-    }
+    for (auto &sl : m->slots) sl.graphs.clear();
     const HParams &hp = m->hp;
     const size_t d = hp.n_embd, F = hp.n_ff, V = hp.n_vocab, C = hp.n_ctx, H = hp.n_head;
     const size_t KpMax = ((std::max(d, F) + 255) / 256) * 256;
     float **bufs[] = { &m->x, &m->x1, &m->qkv, &m->qr, &m->merged, &m->gu, &m->tmp, &m->logits, &m->qa_d, &m->dbg_y, &m->dbg_p, &m->dbg_kqv };
-    for (auto b : bufs) { free_dev(*b); *b = nullptr; }
-    free_dev(m->qa_A); m->qa_A = nullptr;
-    free_dev(m->qb_ws); m->qb_ws = nullptr;
-    free_dev(m->d_tokens); m->d_tokens = nullptr;
+    for (auto b : bufs) m->own.release(b);
+    m->own.release(&m->qa_A);
+    m->own.release(&m->qb_ws);
+    m->own.release(&m->d_tokens);
     m->ws_cap = 0;
     const size_t n = (size_t) N;
-    HIP_TRY(hipMalloc((void **) &m->d_tokens, n * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->x, n * d * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->x1, n * d * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->qkv, n * 3 * d * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->qr, n * d * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->merged, n * d * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->gu, n * 2 * F * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->tmp, n * std::max(d, F) * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->logits, n * V * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->qa_A, n * KpMax), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->qa_d, n * (KpMax / 32) * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->qb_ws, n * KpMax * 2), LLAMAHIP_ERR_PREDICT);  // fp16 (or int8) operand of the matrix-core GEMM
+    HIP_TRY(m->own.alloc_all({ { &m->d_tokens, n * 4 }, { &m->x, n * d * 4 }, { &m->x1, n * d * 4 }, { &m->qkv, n * 3 * d * 4 }, { &m->qr, n * d * 4 },
+                               { &m->merged, n * d * 4 }, { &m->gu, n * 2 * F * 4 }, { &m->tmp, n * std::max(d, F) * 4 }, { &m->logits, n * V * 4 },
+                               { &m->qa_A, n * KpMax }, { &m->qa_d, n * (KpMax / 32) * 4 },
+                               { &m->qb_ws, n * KpMax * 2 },      // fp16 (or int8) operand of the matrix-core GEMM
+                               { &m->dbg_y, n * std::max(d, F) * 4 }, { &m->dbg_p, H * n * C * 4 }, { &m->dbg_kqv, n * d * 4 } }), LLAMAHIP_ERR_PREDICT);
     if (!m->qaF_A) {
         const size_t KpF = ((F + 255) / 256) * 256;
-        HIP_TRY(hipMalloc((void **) &m->qaF_A, 64 * KpF), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &m->qaF_d, 64 * (KpF / 32) * 4), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(m->qaF_A, 0, 64 * KpF), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(m->qaF_d, 0, 64 * (KpF / 32) * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc_all({ { &m->qaF_A, 64 * KpF, true }, { &m->qaF_d, 64 * (KpF / 32) * 4, true } }), LLAMAHIP_ERR_PREDICT);
     }
-    HIP_TRY(hipMalloc((void **) &m->dbg_y, n * std::max(d, F) * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->dbg_p, H * n * C * 4), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &m->dbg_kqv, n * d * 4), LLAMAHIP_ERR_PREDICT);
     m->ws_cap = N;
     return 0;
 }
@@ -543,11 +532,16 @@ int ensure_attn_ws(llamahip_model *m, int N, char *err, size_t err_cap) {
     AttnWs &w = m->attn_ws;
     attn_ws_shape(w, m->hp.n_ctx);
     const AttnWsBytes b = attn_ws_bytes(w, m->hp.n_head);
-    HIP_TRY(hipMalloc((void **) &w.S, b.S), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.pmax, b.pmax), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.inv, b.inv), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMalloc((void **) &w.part, b.part), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(m->own.alloc_all({ { &w.S, b.S }, { &w.pmax, b.pmax }, { &w.inv, b.inv }, { &w.part, b.part } }), LLAMAHIP_ERR_PREDICT);
     return 0;
+}
+
+// a pinned, device-mapped host block and its device alias: both or neither
+template <class T> hipError_t alloc_pinned(llamahip_model *m, T **host, T **dev, size_t bytes) {
+    *dev = nullptr;
+    hipError_t e = (hipError_t) m->own.alloc_all({ { host, bytes, true, MEM_PINNED } });
+    if (e == hipSuccess && (e = hipHostGetDevicePointer((void **) dev, *host, 0)) != hipSuccess) { m->own.release(host); *dev = nullptr; }
+    return e;
 }
 
 struct DumpSink {
@@ -1001,22 +995,22 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
     {
         std::vector<uint16_t> ts(1 << 16), te(1 << 16);
         lut_tables(ts, te);
-        HIP_TRY(hipMalloc((void **) &m->T_silu, ts.size() * 2), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->T_exp, te.size() * 2), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->T_silu, ts.size()), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->T_exp, te.size()), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->T_silu, ts.data(), ts.size() * 2, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->T_exp, te.data(), te.size() * 2, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         HIP_TRY(launch_check_lut_math(m->T_silu, m->T_exp, m->stream), LLAMAHIP_ERR_LOAD);
         const std::vector<double> sc = rope_table(n_ctx, d / H);
-        HIP_TRY(hipMalloc((void **) &m->sincos, sc.size() * 8), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->sincos, sc.size()), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->sincos, sc.data(), sc.size() * 8, hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
     }
 
     // ---- weights
     size_t max_bytes = 0;
     for (const auto &kv : m->file.tensors) if (kv.second.q4) max_bytes = std::max(max_bytes, (size_t) kv.second.nbytes());
+    DevOwner staging;                    // the file-layout tensor on its way into the tiles: released on every return path
     uint8_t *d_stage = nullptr;
-    HIP_TRY(hipMalloc((void **) &d_stage, std::max<size_t>(max_bytes, 256)), LLAMAHIP_ERR_LOAD);
-    struct StageGuard { uint8_t *&p; ~StageGuard() { if (p) { (void) hipFree(p); p = nullptr; } } } stage_guard{ d_stage };   // freed on every return path
+    HIP_TRY(staging.alloc(&d_stage, std::max<size_t>(max_bytes, 256)), LLAMAHIP_ERR_LOAD);
     std::vector<uint8_t> h_stage;
     int rc = 0;
 #define LOAD_TRY(x) do { rc = (x); if (rc != 0) return rc; } while (0)
@@ -1025,7 +1019,7 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
         const TensorInfo &t = m->file.tensors.at("tok_embeddings.weight");
         h_stage.resize((size_t) t.nbytes());
         if (!m->file.read_tensor(t.name, h_stage.data(), e)) { set_err(err, err_cap, "%s", e.c_str()); return LLAMAHIP_ERR_LOAD; }
-        HIP_TRY(hipMalloc((void **) &m->tok_emb, h_stage.size()), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->tok_emb, h_stage.size()), LLAMAHIP_ERR_LOAD);
         HIP_TRY(hipMemcpy(m->tok_emb, h_stage.data(), h_stage.size(), hipMemcpyHostToDevice), LLAMAHIP_ERR_LOAD);
         m->weight_bytes += (int64_t) h_stage.size();
     }
@@ -1088,66 +1082,33 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
     }
     }
 #undef LOAD_TRY
-    (void) hipFree(d_stage);
-    d_stage = nullptr;
+    staging.release(&d_stage);
 
     // ---- KV cache (.mm:290-304); zero-initialised (the reference leaves malloc garbage)
     const size_t kv_elems = (size_t) m->n_seq * (m->l1 - m->l0) * n_ctx * d;
-    HIP_TRY(hipMalloc((void **) &m->Kc, kv_elems * 4), LLAMAHIP_ERR_LOAD);
-    HIP_TRY(hipMalloc((void **) &m->Vc, kv_elems * 4), LLAMAHIP_ERR_LOAD);
-    HIP_TRY(hipMemset(m->Kc, 0, kv_elems * 4), LLAMAHIP_ERR_LOAD);
-    HIP_TRY(hipMemset(m->Vc, 0, kv_elems * 4), LLAMAHIP_ERR_LOAD);
+    HIP_TRY(m->own.alloc_all({ { &m->Kc, kv_elems * 4, true }, { &m->Vc, kv_elems * 4, true } }), LLAMAHIP_ERR_LOAD);
     m->kv_bytes = (int64_t) kv_elems * 8;
     {
         const size_t Kp_d = ((size_t) d + 255) / 256 * 256, Kp_F = ((size_t) F + 255) / 256 * 256, dh = d / H;
-        HIP_TRY(hipMalloc((void **) &m->d_state, 2 * sizeof(int32_t)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->d_state, 0, 2 * sizeof(int32_t)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->sc, (size_t) H * n_ctx * 4), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->part, (size_t) H * 64 * dh * 4), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipHostMalloc((void **) &m->h_fault, 64, hipHostMallocMapped), LLAMAHIP_ERR_LOAD);
-        *m->h_fault = 0;
-        HIP_TRY(hipHostGetDevicePointer((void **) &m->d_fault, m->h_fault, 0), LLAMAHIP_ERR_LOAD);
-        if (!getenv("LLAMAHIP_NO_HOST_IO")) {
-            HIP_TRY(hipHostMalloc((void **) &m->h_io, sizeof(llamahip_model::HostIo), hipHostMallocMapped), LLAMAHIP_ERR_LOAD);
-            memset(m->h_io, 0, sizeof(llamahip_model::HostIo));
-            HIP_TRY(hipHostGetDevicePointer((void **) &m->d_io, m->h_io, 0), LLAMAHIP_ERR_LOAD);
-        }
+        HIP_TRY(m->own.alloc(&m->d_state, 2, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->sc, (size_t) H * n_ctx), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->part, (size_t) H * 64 * dh), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(alloc_pinned(m.get(), &m->h_fault, &m->d_fault, 64), LLAMAHIP_ERR_LOAD);
+        if (!getenv("LLAMAHIP_NO_HOST_IO")) HIP_TRY(alloc_pinned(m.get(), &m->h_io, &m->d_io, sizeof(llamahip_model::HostIo)), LLAMAHIP_ERR_LOAD);
         // decode attention as one launch needs every workgroup of a head behind one L2: check the placement on this
         // device before relying on it (LLAMAHIP_NO_ATTN_X: keep the two launches)
-        if (!getenv("LLAMAHIP_NO_ATTN_X") && H % 8 == 0 && xcd_selftest(H, (int) (d / H / 32) + (n_ctx + 31) / 32, m->stream)) {
-            HIP_TRY(hipMalloc((void **) &m->d_attn_sync, (size_t) H * 32 * 4), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMemset(m->d_attn_sync, 0, (size_t) H * 32 * 4), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMalloc((void **) &m->d_qkv2, (size_t) 3 * d * 8), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMemset(m->d_qkv2, 0, (size_t) 3 * d * 8), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMalloc((void **) &m->d_sc2, (size_t) H * n_ctx * 8), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMemset(m->d_sc2, 0, (size_t) H * n_ctx * 8), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMalloc((void **) &m->d_pvx, (size_t) d * 32 * 8), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMemset(m->d_pvx, 0, (size_t) d * 32 * 8), LLAMAHIP_ERR_LOAD);
-        }
-        HIP_TRY(hipMalloc((void **) &m->d_epoch, 64), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->d_epoch, 0, 64), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->d_w13_amax, ((size_t) F / 16 + 16) * 8), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->d_w13_amax, 0, ((size_t) F / 16 + 16) * 8), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->d_set_amax, (size_t) SET_MAX * set_amax_granules(F) * 8), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->d_set_amax, 0, (size_t) SET_MAX * set_amax_granules(F) * 8), LLAMAHIP_ERR_LOAD);
-        {   // lm-head pick epilogue: [0, 1024) bytes tickets, then one 8-byte key per workgroup of the lm head's launch (<= n_vocab / 8 + 8)
-            const size_t pb = 1024 + ((size_t) V / 8 + 8) * 8;
-            HIP_TRY(hipMalloc((void **) &m->d_pick, pb), LLAMAHIP_ERR_LOAD);
-            HIP_TRY(hipMemset(m->d_pick, 0, pb), LLAMAHIP_ERR_LOAD);
-        }
-        HIP_TRY(hipMalloc((void **) &m->npart_a, NORM_PART_MAX * 2 * sizeof(double)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->npart_b, NORM_PART_MAX * 2 * sizeof(double)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->npart_a, 0, NORM_PART_MAX * 2 * sizeof(double)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->npart_b, 0, NORM_PART_MAX * 2 * sizeof(double)), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->qa1_A, Kp_d), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->qa1_d, Kp_d / 32 * 4), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->qa2_A, Kp_F), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &m->qa2_d, Kp_F / 32 * 4), LLAMAHIP_ERR_LOAD);
+        if (!getenv("LLAMAHIP_NO_ATTN_X") && H % 8 == 0 && xcd_selftest(H, (int) (d / H / 32) + (n_ctx + 31) / 32, m->stream))
+            HIP_TRY(m->own.alloc_all({ { &m->d_attn_sync, (size_t) H * 32 * 4, true }, { &m->d_qkv2, (size_t) 3 * d * 8, true },
+                                       { &m->d_sc2, (size_t) H * n_ctx * 8, true }, { &m->d_pvx, (size_t) d * 32 * 8, true } }), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->d_epoch, 16, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->d_w13_amax, (size_t) F / 16 + 16, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->d_set_amax, (size_t) SET_MAX * set_amax_granules(F), true), LLAMAHIP_ERR_LOAD);
+        // lm-head pick epilogue: [0, 1024) bytes tickets, then one 8-byte key per workgroup of the lm head's launch (<= n_vocab / 8 + 8)
+        HIP_TRY(m->own.alloc(&m->d_pick, 128 + (size_t) V / 8 + 8, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->npart_a, NORM_PART_MAX * 2, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc(&m->npart_b, NORM_PART_MAX * 2, true), LLAMAHIP_ERR_LOAD);
         // blocks past K/32 (padding up to a multiple of 256 columns) are never written again: keep them zero
-        HIP_TRY(hipMemset(m->qa1_A, 0, Kp_d), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->qa1_d, 0, Kp_d / 32 * 4), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->qa2_A, 0, Kp_F), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(m->qa2_d, 0, Kp_F / 32 * 4), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(m->own.alloc_all({ { &m->qa1_A, Kp_d, true }, { &m->qa1_d, Kp_d / 32 * 4, true }, { &m->qa2_A, Kp_F, true }, { &m->qa2_d, Kp_F / 32 * 4, true } }), LLAMAHIP_ERR_LOAD);
     }
 
     rc = ensure_workspace(m.get(), 16, err, err_cap);
@@ -1316,10 +1277,7 @@ int llamahip_eval_topk(llamahip_model *m, int32_t n_threads, int32_t n_past, con
     const double t0 = now_ms();
     int rc = eval_impl(m, n_threads, n_past, tokens, n_tokens, nullptr, nullptr, -1, nullptr, 0, nullptr, false, err, err_cap);   // logits stay on the device, no wait
     if (rc) return rc;
-    if (!m->d_topk) {
-        HIP_TRY(hipMalloc(&m->d_topk, 8192 + TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(m->d_topk, 0, 8192 + TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-    }
+    if (!m->d_topk) HIP_TRY(m->own.alloc(&m->d_topk, 8192 + TOPK_WS_BYTES, true), LLAMAHIP_ERR_PREDICT);
     int32_t *d_win = (int32_t *) m->d_topk;
     double *d_sc = (double *) ((char *) m->d_topk + 4096);
     int32_t *d_id = (int32_t *) ((char *) m->d_topk + 4096 + 512), *d_fl = d_id + 64;
@@ -1403,7 +1361,7 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
     rc = ensure_workspace(m, 1, err, err_cap);
     if (rc) return rc;
     if (!m->d_out_tokens) {      // sized once for the whole context: captured graphs hold this pointer
-        HIP_TRY(hipMalloc((void **) &m->d_out_tokens, (size_t) m->hp.n_ctx * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&m->d_out_tokens, (size_t) m->hp.n_ctx), LLAMAHIP_ERR_PREDICT);
         m->out_tokens_cap = m->hp.n_ctx;
     }
     HIP_TRY(hipMemcpyAsync(m->d_tokens, &first_token, 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
@@ -1433,23 +1391,19 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
         for (int i = 0; i < n_steps; i++) {
             m->attn_sched = attn_sched_at(m, n_past + i);
             const int gkey = nth * 4096 + m->cur_seq + (m->attn_sched << 24) + (fold ? 1 << 27 : 0);
-            auto it = m->decode_graphs.find(gkey);
-            if (it == m->decode_graphs.end()) {
-                hipGraph_t graph = nullptr;
+            auto *g = m->decode_graphs.find(gkey);
+            if (!g) {
                 hipGraphExec_t exec = nullptr;
-                HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal), LLAMAHIP_ERR_PREDICT);
-                rc = forward(m, nth, 0, 1, nullptr, true, false, -1, nullptr, err, err_cap, fold ? &pio : nullptr);
-                hipError_t e1 = (rc || fold) ? (rc ? hipErrorUnknown : hipSuccess) : launch_argmax(m->logits, m->hp.n_vocab, m->d_out_tokens, 0, m->d_tokens, m->d_state, m->stream);
-                hipError_t e2 = hipStreamEndCapture(m->stream, &graph);
+                rc = capture_step(m, [&]() -> int {
+                    const int r = forward(m, nth, 0, 1, nullptr, true, false, -1, nullptr, err, err_cap, fold ? &pio : nullptr);
+                    if (r || fold) return r;
+                    HIP_TRY(launch_argmax(m->logits, m->hp.n_vocab, m->d_out_tokens, 0, m->d_tokens, m->d_state, m->stream), LLAMAHIP_ERR_PREDICT);
+                    return 0;
+                }, &exec, err, err_cap);
                 if (rc) return rc;
-                HIP_TRY(e1, LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(e2, LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-                (void) hipGraphDestroy(graph);
-                it = m->decode_graphs.emplace(gkey, exec).first;
+                g = m->decode_graphs.put(gkey, exec);
             }
-            HIP_TRY(hipGraphLaunch(it->second, m->stream), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipGraphLaunch(g->exec, m->stream), LLAMAHIP_ERR_PREDICT);
         }
     } else {
         for (int i = 0; i < n_steps; i++) {
@@ -1502,16 +1456,11 @@ int llamahip_stage_bind(llamahip_model *m, int32_t seq, int32_t n_past,
     }
     int rc = ensure_workspace(m, 1, err, err_cap);
     if (rc) return rc;
-    if (!m->d_slot_state) {
-        HIP_TRY(hipMalloc((void **) &m->d_slot_state, (size_t) m->n_seq * 2 * sizeof(int32_t)), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &m->d_slot_trace, (size_t) m->n_seq * m->hp.n_ctx * sizeof(int32_t)), LLAMAHIP_ERR_PREDICT);
-        m->slots.resize(m->n_seq);
-    }
+    if ((rc = ensure_slots(m, err, err_cap)) != 0) return rc;
     auto &sl = m->slots[seq];
     const bool same = sl.bound && sl.token_in == token_in && sl.token_out == token_out && sl.hidden_in == hidden_in && sl.hidden_out == hidden_out;
     if (!same) {                 // captured graphs hold the old pointers (and may still run on a caller stream: device-wide wait)
         HIP_TRY(hipDeviceSynchronize(), LLAMAHIP_ERR_PREDICT);
-        for (auto &kv : sl.graphs) (void) hipGraphExecDestroy(kv.second);
         sl.graphs.clear();
         drop_set_graphs(m);
     }
@@ -1534,19 +1483,9 @@ int llamahip_stage_bind(llamahip_model *m, int32_t seq, int32_t n_past,
 }
 
 namespace {
-static int ensure_slots(llamahip_model *m, char *err, size_t err_cap) {
-    if (!m->d_slot_state) {
-        HIP_TRY(hipMalloc((void **) &m->d_slot_state, (size_t) m->n_seq * 2 * sizeof(int32_t)), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &m->d_slot_trace, (size_t) m->n_seq * m->hp.n_ctx * sizeof(int32_t)), LLAMAHIP_ERR_PREDICT);
-        m->slots.resize(m->n_seq);
-    }
-    return 0;
-}
 static int drop_slot_graphs(llamahip_model *m, int seq, char *err, size_t err_cap) {
-    auto &sl = m->slots[seq];
     HIP_TRY(hipDeviceSynchronize(), LLAMAHIP_ERR_PREDICT);
-    for (auto &kv : sl.graphs) (void) hipGraphExecDestroy(kv.second);
-    sl.graphs.clear();
+    m->slots[seq].graphs.clear();
     return 0;
 }
 }  // namespace
@@ -1565,13 +1504,11 @@ int llamahip_stage_mailbox(llamahip_model *m, int32_t seq, void **hidden_inbox, 
     auto &sl = m->slots[seq];
     if (!m->first_stage && !sl.inbox_hidden) {
         if ((rc = drop_slot_graphs(m, seq, err, err_cap)) != 0) return rc;
-        HIP_TRY(malloc_mailbox((void **) &sl.inbox_hidden, (size_t) m->hp.n_embd * 8), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(sl.inbox_hidden, 0, (size_t) m->hp.n_embd * 8), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&sl.inbox_hidden, (size_t) m->hp.n_embd, true, MEM_MAILBOX), LLAMAHIP_ERR_PREDICT);
     }
     if (m->first_stage && !m->last_stage && !sl.inbox_token) {
         if ((rc = drop_slot_graphs(m, seq, err, err_cap)) != 0) return rc;
-        HIP_TRY(malloc_mailbox((void **) &sl.inbox_token, 64), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(sl.inbox_token, 0, 64), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&sl.inbox_token, 8, true, MEM_MAILBOX), LLAMAHIP_ERR_PREDICT);
     }
     if (hidden_inbox) *hidden_inbox = sl.inbox_hidden;
     if (token_inbox) *token_inbox = sl.inbox_token;
@@ -1673,24 +1610,17 @@ int llamahip_stage_step(llamahip_model *m, int32_t seq, int32_t n_threads, void 
     } else {
         m->attn_sched = attn_sched_at(m, sl.next_pos);
         const int gkey = nth + (m->attn_sched << 16);
-        auto it = sl.graphs.find(gkey);
-        if (it == sl.graphs.end()) {
+        auto *g = sl.graphs.find(gkey);
+        if (!g) {
             // One step of this stage (embed | stream in -> layers -> stream out | lm head + argmax)
             // captured once per (slot, n_threads); the position lives in device memory and the last
             // node advances it, so the same executable graph is replayed for every token.
-            hipGraph_t graph = nullptr;
             hipGraphExec_t exec = nullptr;
-            HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal), LLAMAHIP_ERR_PREDICT);
-            int rc = stage_step_launches(m, seq, nth, err, err_cap);
-            hipError_t e2 = hipStreamEndCapture(m->stream, &graph);
-            if (rc) { if (graph) (void) hipGraphDestroy(graph); return rc; }
-            HIP_TRY(e2, LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-            (void) hipGraphDestroy(graph);
-            it = sl.graphs.emplace(gkey, exec).first;
+            const int rc = capture_step(m, [&]() { return stage_step_launches(m, seq, nth, err, err_cap); }, &exec, err, err_cap);
+            if (rc) return rc;
+            g = sl.graphs.put(gkey, exec);
         }
-        HIP_TRY(hipGraphLaunch(it->second, run_on), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipGraphLaunch(g->exec, run_on), LLAMAHIP_ERR_PREDICT);
     }
     sl.next_pos++;
     m->n_evals++;
@@ -1809,7 +1739,7 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
     HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
     int rc = ensure_workspace(m, SET_MAX, err, err_cap);
     if (rc) return rc;
-    if (!m->set_sc) HIP_TRY(hipMalloc((void **) &m->set_sc, (size_t) SET_MAX * H * C * 4), LLAMAHIP_ERR_PREDICT);
+    if ((rc = ensure_set_sc(m, err, err_cap)) != 0) return rc;
     hipStream_t run_on = (hipStream_t) stream;
     // The rows of a step are independent (every sequence's results are those of stepping it alone), so a set is its slots in ascending
     // order: [0, 1] and [1, 0] share one captured graph and one device descriptor.  A server whose active set keeps changing would
@@ -1828,15 +1758,14 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
     key.push_back(nth);
     key.push_back(set_keys);
     for (int i = 0; i < n_seqs; i++) key.push_back(order[i]);
-    auto it = m->set_graphs.find(key);
-    if (it == m->set_graphs.end()) {
+    auto *g = m->set_graphs.find(key);
+    if (!g) {
         if (m->set_graphs.size() >= SET_GRAPHS_MAX) {
-            auto victim = m->set_graphs.begin();
-            for (auto jt = m->set_graphs.begin(); jt != m->set_graphs.end(); ++jt) if (jt->second.last_use < victim->second.last_use) victim = jt;
+            auto victim = m->set_graphs.map.begin();
+            for (auto jt = m->set_graphs.map.begin(); jt != m->set_graphs.map.end(); ++jt) if (jt->second.last_use < victim->second.last_use) victim = jt;
             HIP_TRY(hipDeviceSynchronize(), LLAMAHIP_ERR_PREDICT);          // its graph may still run on a caller's stream
-            if (victim->second.exec) (void) hipGraphExecDestroy(victim->second.exec);
-            free_dev(victim->second.d_set);
-            m->set_graphs.erase(victim);
+            m->own.release(&victim->second.d_set);
+            m->set_graphs.erase(victim->first);
         }
         SeqSet hs;
         memset(&hs, 0, sizeof(hs));
@@ -1851,33 +1780,25 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
             hs.kv_off[i] = (long) ((size_t) sq * (m->l1 - m->l0) * C * d);
         }
         llamahip_model::SetGraph sg;
-        HIP_TRY(hipMalloc((void **) &sg.d_set, sizeof(SeqSet)), LLAMAHIP_ERR_PREDICT);
-        if (hipMemcpy(sg.d_set, &hs, sizeof(SeqSet), hipMemcpyHostToDevice) != hipSuccess) { free_dev(sg.d_set); set_err(err, err_cap, "HIP error copying the set descriptor"); return LLAMAHIP_ERR_PREDICT; }
-        if (!(m->flags & LLAMAHIP_FLAG_NO_GRAPH)) {
-            hipGraph_t graph = nullptr;
-            HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
-            if (hipStreamBeginCapture(m->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { free_dev(sg.d_set); set_err(err, err_cap, "HIP error: stream capture"); return LLAMAHIP_ERR_PREDICT; }
-            rc = forward_set(m, nth, sg.d_set, n_seqs, err, err_cap, set_keys);
-            hipError_t e2 = hipStreamEndCapture(m->stream, &graph);
-            if (rc || e2 != hipSuccess || hipGraphInstantiate(&sg.exec, graph, nullptr, nullptr, 0) != hipSuccess) {
-                if (graph) (void) hipGraphDestroy(graph);
-                free_dev(sg.d_set);
-                if (!rc) set_err(err, err_cap, "HIP error capturing the set step");
-                return rc ? rc : LLAMAHIP_ERR_PREDICT;
-            }
-            (void) hipGraphDestroy(graph);
+        hipGraphExec_t exec = nullptr;
+        HIP_TRY(m->own.alloc(&sg.d_set, 1), LLAMAHIP_ERR_PREDICT);
+        if (hipMemcpy(sg.d_set, &hs, sizeof(SeqSet), hipMemcpyHostToDevice) != hipSuccess) { m->own.release(&sg.d_set); set_err(err, err_cap, "HIP error copying the set descriptor"); return LLAMAHIP_ERR_PREDICT; }
+        if (!(m->flags & LLAMAHIP_FLAG_NO_GRAPH) &&
+            (rc = capture_step(m, [&]() { return forward_set(m, nth, sg.d_set, n_seqs, err, err_cap, set_keys); }, &exec, err, err_cap)) != 0) {
+            m->own.release(&sg.d_set);
+            return rc;
         }
-        it = m->set_graphs.emplace(key, sg).first;
+        g = m->set_graphs.put(key, exec, sg);
         m->n_set_captures++;
     }
-    it->second.last_use = ++m->set_graph_clock;
+    g->last_use = ++m->set_graph_clock;
     m->last_rows.assign(n_seqs, 0);
     for (int i = 0; i < n_seqs; i++) m->last_rows[i] = (int) (std::lower_bound(order.begin(), order.end(), seqs[i]) - order.begin());
-    if (it->second.exec) HIP_TRY(hipGraphLaunch(it->second.exec, run_on), LLAMAHIP_ERR_PREDICT);
+    if (g->exec) HIP_TRY(hipGraphLaunch(g->exec, run_on), LLAMAHIP_ERR_PREDICT);
     else {
         hipStream_t own = m->stream;
         m->stream = run_on;
-        rc = forward_set(m, nth, it->second.d_set, n_seqs, err, err_cap, set_keys);
+        rc = forward_set(m, nth, g->d_set, n_seqs, err, err_cap, set_keys);
         m->stream = own;
         if (rc) return rc;
     }
@@ -2000,10 +1921,9 @@ static int pipe_load(const char *path, int32_t n_ctx, const llamahip_opts *opts,
     for (int s = 0; s < S; s++) {
         llamahip_model *st = stages[s];
         HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipEventCreateWithFlags(&st->pipe_ev, hipEventDisableTiming), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &st->pipe_tok, 64), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMemset(st->pipe_tok, 0, 64), LLAMAHIP_ERR_LOAD);
-        HIP_TRY(hipMalloc((void **) &st->pipe_hout, (size_t) front->hp.n_embd * 4), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(st->events.create(&st->pipe_ev, hipEventDisableTiming), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(st->own.alloc(&st->pipe_tok, 16, true), LLAMAHIP_ERR_LOAD);
+        HIP_TRY(st->own.alloc(&st->pipe_hout, (size_t) front->hp.n_embd), LLAMAHIP_ERR_LOAD);
         // direct peer copies to the next stage's device and (last stage) back to the first; without peer access the copy is staged by the runtime
         // peer access lets the runtime copy device to device over xGMI (without it hipMemcpyPeerAsync stages through host memory)
         const int peers[2] = { stages[(s + 1) % S]->device, stages[0]->device };
@@ -2027,9 +1947,9 @@ static int pipe_ensure_in(llamahip_model *st, int N, char *err, size_t err_cap) 
     if (N <= st->pipe_in_cap) return 0;
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     HIP_TRY(hipStreamSynchronize(st->stream), LLAMAHIP_ERR_PREDICT);
-    free_dev(st->pipe_in); st->pipe_in = nullptr; st->pipe_in_cap = 0;
+    st->own.release(&st->pipe_in); st->pipe_in_cap = 0;
     const int cap = std::max(N, 16);
-    HIP_TRY(hipMalloc((void **) &st->pipe_in, (size_t) cap * st->hp.n_embd * 4), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(st->own.alloc(&st->pipe_in, (size_t) cap * st->hp.n_embd), LLAMAHIP_ERR_PREDICT);
     st->pipe_in_cap = cap;
     return 0;
 }
@@ -2119,8 +2039,8 @@ static ScoreIo score_io(llamahip_model *m, int N) {
 static int score_enqueue(llamahip_model *m, int N, const int32_t *targets, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
     if (N > m->score_cap) {
-        free_dev(m->d_score); m->d_score = nullptr; m->score_cap = 0;
-        HIP_TRY(hipMalloc(&m->d_score, (size_t) N * 20), LLAMAHIP_ERR_PREDICT);
+        m->own.release(&m->d_score); m->score_cap = 0;
+        HIP_TRY(m->own.alloc(&m->d_score, (size_t) N * 20), LLAMAHIP_ERR_PREDICT);
         m->score_cap = N;
     }
     const ScoreIo io = score_io(m, N);
@@ -2371,9 +2291,9 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
     const size_t C = m->hp.n_ctx, d = m->hp.n_embd;
     if (rp.R > m->rows_cap) {
         HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
-        free_dev(m->d_rows); m->d_rows = nullptr; m->rows_cap = 0;
+        m->own.release(&m->d_rows); m->rows_cap = 0;
         const int cap = std::max(rp.R, 64);
-        HIP_TRY(hipMalloc((void **) &m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4), LLAMAHIP_ERR_PREDICT);
         m->rows_cap = cap;
     }
     const size_t cap = (size_t) m->rows_cap, bytes = cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4;
@@ -2554,9 +2474,7 @@ static VerifyIo verify_io(llamahip_model *m) { return { m->d_verify, m->d_verify
 static int verify_ensure(llamahip_model *last, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     if (last->d_verify) return 0;
-    const size_t bytes = (64 + (size_t) last->hp.n_ctx) * 4;
-    HIP_TRY(hipMalloc((void **) &last->d_verify, bytes), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMemset(last->d_verify, 0, bytes), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(last->own.alloc(&last->d_verify, 64 + (size_t) last->hp.n_ctx, true), LLAMAHIP_ERR_PREDICT);
     return 0;
 }
 // the two kernels over the N rows of last->logits, ordered behind the eval on last->stream (restart_pos >= 0: the log starts over there)
@@ -2593,8 +2511,7 @@ static int slide_ensure(llamahip_model *last, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     if (last->d_slide) return 0;
     const size_t bytes = SLIDE_WS_BYTES + SLIDE_IDS_BYTES + VERIFY_ROWS_MAX * sizeof(TopkOut);
-    HIP_TRY(hipMalloc((void **) &last->d_slide, bytes), LLAMAHIP_ERR_PREDICT);
-    HIP_TRY(hipMemset(last->d_slide, 0, bytes), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(last->own.alloc(&last->d_slide, bytes, true), LLAMAHIP_ERR_PREDICT);
     return 0;
 }
 static int slide_enqueue(llamahip_model *last, const SlideReq &sl, int N, char *err, size_t err_cap) {
@@ -3065,16 +2982,12 @@ static bool multi_stage_steps(const llamahip_model *first) { return !(first->den
 static int multi_prepare(llamahip_model *st, int n_groups, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     const size_t d = st->hp.n_embd;
-    if (!st->mq_tok) {
-        HIP_TRY(hipMalloc((void **) &st->mq_tok, (size_t) st->n_seq * 4 + 64), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(st->mq_tok, 0, (size_t) st->n_seq * 4 + 64), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &st->mq_in, (size_t) st->n_seq * d * 4), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &st->mq_out, (size_t) st->n_seq * d * 4), LLAMAHIP_ERR_PREDICT);
-    }
+    if (!st->mq_tok)
+        HIP_TRY(st->own.alloc_all({ { &st->mq_tok, (size_t) st->n_seq * 4 + 64, true }, { &st->mq_in, (size_t) st->n_seq * d * 4 },
+                                    { &st->mq_out, (size_t) st->n_seq * d * 4 } }), LLAMAHIP_ERR_PREDICT);
     while ((int) st->mq_ev.size() < n_groups) {
         hipEvent_t e = nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), LLAMAHIP_ERR_PREDICT);
-        st->mq_ev.push_back(e);
+        HIP_TRY(st->mq_ev.create(&e, hipEventDisableTiming), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -3086,19 +2999,18 @@ static int sample_prepare(llamahip_model *st, bool last, char *err, size_t err_c
     const size_t n = st->n_seq, V = last ? st->hp.n_vocab : 0;
     const size_t o_last = (n * 4 + 63) / 64 * 64, o_win = o_last + (n * 4 + 63) / 64 * 64, o_out = o_win + n * 1024 * 4;
     const size_t o_spill = o_out + (last ? n * sizeof(TopkOut) : 0), bytes = o_spill + n * V * 4;
-    HIP_TRY(hipHostMalloc((void **) &st->smp_blk, bytes, hipHostMallocMapped), LLAMAHIP_ERR_PREDICT);
-    memset(st->smp_blk, 0, bytes);
+    // the block, (last stage) the selection workspace and the block's device alias: all or none
+    const size_t ws_bytes = (size_t) SET_MAX * TOPK_WS_BYTES;
+    hipError_t e = (hipError_t) (last ? st->own.alloc_all({ { &st->smp_blk, bytes, true, MEM_PINNED }, { &st->smp_ws, ws_bytes, true } })
+                                      : st->own.alloc_all({ { &st->smp_blk, bytes, true, MEM_PINNED } }));
     char *d = nullptr;
-    HIP_TRY(hipHostGetDevicePointer((void **) &d, st->smp_blk, 0), LLAMAHIP_ERR_PREDICT);
+    if (e == hipSuccess && (e = hipHostGetDevicePointer((void **) &d, st->smp_blk, 0)) != hipSuccess) { st->own.release(&st->smp_blk); st->own.release(&st->smp_ws); }
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
     for (int v = 0; v < 2; v++) {
         char *b = v ? d : st->smp_blk;
         llamahip_model::SampleIo &io = v ? st->smp_d : st->smp_h;
         io.tok = (int32_t *) b; io.n_last = (int32_t *) (b + o_last); io.win = (int32_t *) (b + o_win);
         io.out = last ? (TopkOut *) (b + o_out) : nullptr; io.spill = last ? (float *) (b + o_spill) : nullptr;
-    }
-    if (last) {
-        HIP_TRY(hipMalloc(&st->smp_ws, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(st->smp_ws, 0, (size_t) SET_MAX * TOPK_WS_BYTES), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -3235,12 +3147,8 @@ static int vset_ensure(llamahip_model *st, bool first, char *err, size_t err_cap
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
     int rc = ensure_workspace(st, SET_MAX, err, err_cap);
     if (rc) return rc;
-    const size_t H = st->hp.n_head, C = st->hp.n_ctx;
-    if (!st->set_sc) HIP_TRY(hipMalloc((void **) &st->set_sc, (size_t) SET_MAX * H * C * 4), LLAMAHIP_ERR_PREDICT);
-    if (!st->d_vset) {
-        HIP_TRY(hipMalloc((void **) &st->d_vset, sizeof(VsetBlock)), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemset(st->d_vset, 0, sizeof(VsetBlock)), LLAMAHIP_ERR_PREDICT);
-    }
+    if ((rc = ensure_set_sc(st, err, err_cap)) != 0) return rc;
+    if (!st->d_vset) HIP_TRY(st->own.alloc(&st->d_vset, 1, true), LLAMAHIP_ERR_PREDICT);
     if (!first && (rc = pipe_ensure_in(st, SET_MAX, err, err_cap)) != 0) return rc;
     return 0;
 }
@@ -3267,7 +3175,7 @@ static int slide_set_enqueue(llamahip_model *last, const SlideSetReq &ss, int R,
         memcpy(last->h_io->row_tab + VERIFY_ROWS_MAX, ss.row_n_last, sizeof(ss.row_n_last));
         ids = last->d_io->pool; tab = last->d_io->row_tab; out = last->d_io->rows;
     } else {
-        if (!last->d_slide_set) HIP_TRY(hipMalloc((void **) &last->d_slide_set, (SLIDE_SET_IDS + 2 * VERIFY_ROWS_MAX) * 4), LLAMAHIP_ERR_PREDICT);
+        if (!last->d_slide_set) HIP_TRY(last->own.alloc(&last->d_slide_set, SLIDE_SET_IDS + 2 * VERIFY_ROWS_MAX), LLAMAHIP_ERR_PREDICT);
         int32_t *d_tab = last->d_slide_set + SLIDE_SET_IDS;
         // (pageable sources: each copy has left the host buffer when the call returns)
         if (ss.n_ids > 0) HIP_TRY(hipMemcpyAsync(last->d_slide_set, ss.ids, (size_t) ss.n_ids * 4, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
@@ -3864,7 +3772,7 @@ static int sched_bind(SchedDev *d, const std::vector<llamahip_model *> &stages, 
     }
     if (!last->d_sched_tab) {
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMalloc((void **) &last->d_sched_tab, (size_t) 5 * SET_MAX * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(last->own.alloc(&last->d_sched_tab, (size_t) 5 * SET_MAX), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -4081,10 +3989,10 @@ int64_t llamahip_debug_decode_phases(llamahip_model *m, int32_t n_past, int32_t 
                                      uint64_t *records, int64_t cap, char *err, size_t err_cap) {
     if (!m || m->host_only || cap < 1) { set_err(err, err_cap, "bad arguments"); return -1; }
     if (hipSetDevice(m->device) != hipSuccess) return -1;
+    DevOwner probe;                      // the records' buffer, for the length of this call
     unsigned long long *d_buf = nullptr;
     const size_t bytes = (size_t) (cap + 1) * 8 * sizeof(unsigned long long);
-    if (hipMalloc((void **) &d_buf, bytes) != hipSuccess) return -1;
-    (void) hipMemset(d_buf, 0, bytes);
+    if (probe.alloc(&d_buf, (size_t) (cap + 1) * 8, true) != 0) return -1;
     const unsigned long long hdr[2] = { 0, (unsigned long long) cap };
     (void) hipMemcpy(d_buf, hdr, sizeof(hdr), hipMemcpyHostToDevice);
     // warm the graph / caches first, unprobed
@@ -4103,8 +4011,14 @@ int64_t llamahip_debug_decode_phases(llamahip_model *m, int32_t n_past, int32_t 
             for (int64_t i = 0; i < n * 8; i++) records[i] = h[8 + i];
         }
     }
-    (void) hipFree(d_buf);
     return n;
+}
+
+// live registrations of every DevOwner of the process (handles, their slots and set descriptors, the single-op calls' scratch) and their
+// bytes: what a leak check compares before and after (free device memory as the runtime reports it says nothing on a shared card)
+void llamahip_debug_live_allocs(int64_t *n, int64_t *bytes) {
+    if (n) *n = DevOwner::live_n.load();
+    if (bytes) *bytes = DevOwner::live_bytes.load();
 }
 
 int32_t llamahip_debug_lut_math(void) { return g_lut_math; }

@@ -17,6 +17,7 @@
 
 #include "../../../include/llama_runner.h"
 #include "../../../include/llamahip.h"
+#include "../dev_owner.h"
 #include "../model_file.h"
 #include "../sched.h"
 
@@ -135,6 +136,17 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
     return 0;
 }
 }
+
+// DevOwner's allocator over malloc / free: counts the calls by kind and fails the k-th allocation like a device that ran out of memory
+static int g_own_calls = 0, g_own_fail_at = 0, g_own_allocs[3], g_own_releases[3];
+static int own_stub_alloc(void **p, size_t bytes, int kind, bool zero) {
+    *p = nullptr;
+    if (++g_own_calls == g_own_fail_at) return 2;
+    *p = zero ? calloc(1, bytes ? bytes : 1) : malloc(bytes ? bytes : 1);
+    g_own_allocs[kind]++;
+    return *p ? 0 : 2;
+}
+static void own_stub_release(void *p, int kind) { g_own_releases[kind]++; free(p); }
 
 static int failures = 0;
 #define EXPECT(c) do { if (!(c)) { fprintf(stderr, "host_sanitize: FAILED %s (line %d)\n", #c, __LINE__); failures++; } } while (0)
@@ -657,6 +669,66 @@ int main(int argc, char **argv) {
             llamahip_model_free(ms);
         }
         printf("host_sanitize: scheduler host half: %zu steps logged in the last run\n", g_sched_calls.size());
+    }
+    {   // the owner of device memory (dev_owner.h) on the stub allocator: groups are all-or-nothing at every failing call, release, destruction by kind
+        using lh::DevOwner;
+        const int64_t n_before = DevOwner::live_n.load(), b_before = DevOwner::live_bytes.load();
+        for (int n : { 1, 2, 12 }) {
+            for (int k = 1; k <= n + 1; k++) {          // k = n + 1: no call fails
+                DevOwner own(own_stub_alloc, own_stub_release);
+                char *keep = nullptr;
+                g_own_fail_at = 0;
+                EXPECT(own.alloc(&keep, 24) == 0 && keep);
+                const int64_t n0 = DevOwner::live_n.load(), b0 = DevOwner::live_bytes.load();
+                EXPECT(n0 == n_before + 1 && b0 == b_before + 24);
+                char *slot[12];
+                for (char *&q : slot) q = (char *) 1;          // (stale values: a failed group nulls them)
+                auto group = [&]() -> int {
+                    if (n == 1) return own.alloc_all({ { &slot[0], 16, true } });
+                    if (n == 2) return own.alloc_all({ { &slot[0], 16, true }, { &slot[1], 40, false, lh::MEM_PINNED } });
+                    return own.alloc_all({ { &slot[0], 16, true }, { &slot[1], 40 }, { &slot[2], 8, true }, { &slot[3], 1 }, { &slot[4], 100, true }, { &slot[5], 64 },
+                                           { &slot[6], 3, false, lh::MEM_MAILBOX }, { &slot[7], 5 }, { &slot[8], 7, true }, { &slot[9], 9 }, { &slot[10], 11 }, { &slot[11], 4096, true } });
+                };
+                g_own_calls = 0; g_own_fail_at = k;
+                int rc = group();
+                if (k <= n) {
+                    EXPECT(rc == 2);
+                    for (int i = 0; i < n; i++) EXPECT(slot[i] == nullptr);
+                    EXPECT(DevOwner::live_n.load() == n0 && DevOwner::live_bytes.load() == b0 && own.entries.size() == 1);
+                    g_own_fail_at = 0;                  // the allocator recovers: the same group now succeeds
+                    rc = group();
+                }
+                EXPECT(rc == 0 && DevOwner::live_n.load() == n0 + n && own.entries.size() == (size_t) n + 1);
+                for (int i = 0; i < n; i++) {
+                    EXPECT(slot[i] != nullptr && slot[i] != keep);
+                    for (int j = 0; j < i; j++) EXPECT(slot[i] != slot[j]);
+                }
+                EXPECT(slot[0][0] == 0 && slot[0][15] == 0);          // the zero fill
+                slot[n - 1][0] = 1;                                   // (writable to its last block)
+                const int64_t b1 = DevOwner::live_bytes.load();
+                own.release(&slot[0]);
+                EXPECT(slot[0] == nullptr && DevOwner::live_n.load() == n0 + n - 1 && DevOwner::live_bytes.load() == b1 - 16);
+                own.release(&slot[0]);                                // a null slot: nothing happens
+                EXPECT(DevOwner::live_n.load() == n0 + n - 1 && own.entries.size() == (size_t) n);
+            }
+            EXPECT(DevOwner::live_n.load() == n_before && DevOwner::live_bytes.load() == b_before);      // every owner gave everything back
+        }
+        {   // destruction releases every entry once, through the release function, with the entry's kind
+            memset(g_own_allocs, 0, sizeof(g_own_allocs)); memset(g_own_releases, 0, sizeof(g_own_releases));
+            g_own_calls = 0; g_own_fail_at = 0;
+            {
+                DevOwner own(own_stub_alloc, own_stub_release);
+                int32_t *a = nullptr; uint64_t *b = nullptr; char *c = nullptr; float *d = nullptr;
+                EXPECT(own.alloc(&a, 4) == 0 && own.alloc(&b, 2, true, lh::MEM_MAILBOX) == 0 && own.alloc(&c, 100, true, lh::MEM_PINNED) == 0 && own.alloc(&d, 3) == 0);
+                EXPECT(DevOwner::live_n.load() == n_before + 4 && DevOwner::live_bytes.load() == b_before + 16 + 16 + 100 + 12);
+                own.release(&d);
+                EXPECT(g_own_releases[lh::MEM_DEVICE] == 1);
+            }
+            EXPECT(g_own_allocs[lh::MEM_DEVICE] == 2 && g_own_allocs[lh::MEM_MAILBOX] == 1 && g_own_allocs[lh::MEM_PINNED] == 1);
+            for (int kind = 0; kind < 3; kind++) EXPECT(g_own_releases[kind] == g_own_allocs[kind]);
+            EXPECT(DevOwner::live_n.load() == n_before && DevOwner::live_bytes.load() == b_before);
+        }
+        printf("host_sanitize: device-memory owner: groups of 1, 2 and 12 at every failing allocation, release, destruction by kind\n");
     }
     printf("host_sanitize: %zu tensor bytes merged, tokenizer + sampler + bridge failure path exercised: %s\n", total, failures ? "FAILED" : "clean");
     return failures ? 1 : 0;

@@ -385,6 +385,36 @@ def test_host_half_is_clean_under_asan_and_ubsan(built, tmp_path):
             assert "driver with a 9-token prompt: 7 evals (0 tokens in one chunk-exact pass, 9 in the last chunk)" in r.stdout, r.stdout
 
 
+def test_device_memory_owner_is_all_or_nothing_under_asan_and_ubsan(built, tmp_path):
+    """`make asan`: csrc/dev_owner.h as it is, on counting stub allocators over malloc / free that fail at the k-th call, in the stand-alone
+    tools/host_sanitize -- alloc_all over groups of 1, 2 and 12 at every failing call (every slot null, the live count unchanged, the same
+    group succeeds afterwards), release, destruction through the release function of each entry's kind; LeakSanitizer clean at exit --
+    never loaded into python"""
+    import subprocess
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "llama.swift_amd", "csrc")
+    subprocess.run(["make", "-s", "-C", csrc, "asan"], check=True)
+    src = open(os.path.join(csrc, "tools", "host_sanitize.cpp")).read()
+    assert '#include "../dev_owner.h"' in src and "own.alloc_all(" in src and "own.release(" in src and "g_own_fail_at = k" in src and "{ 1, 2, 12 }" in src
+    assert "hip/hip_runtime.h" not in open(os.path.join(csrc, "dev_owner.h")).read()          # the owner compiles without the runtime
+    hp = synth.HParams(n_vocab=96, n_embd=256, n_mult=256, n_head=2, n_layer=2)
+    path = str(tmp_path / "m.bin")
+    synth.write_model(path, hp, synth.random_tensors(hp, seed=3))
+    r = subprocess.run([os.path.join(csrc, "tools", "host_sanitize"), path, "1"], capture_output=True, text=True)
+    assert r.returncode == 0 and "clean" in r.stdout and "device-memory owner: groups of 1, 2 and 12" in r.stdout, r.stdout + r.stderr
+    assert "FAILED" not in r.stderr and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stdout + r.stderr
+
+
+def test_live_allocs_is_exported_and_counts_no_device_memory_for_a_host_only_handle(L, tmp_path):
+    hp = synth.HParams(n_vocab=96, n_embd=128, n_mult=64, n_head=1, n_layer=1)
+    path = str(tmp_path / "m.bin")
+    synth.write_model(path, hp, synth.random_tensors(hp, seed=3))
+    assert "llamahip_debug_live_allocs" in L.declared_symbols()
+    before = L.live_allocs()
+    with L.Model(path, n_ctx=8, flags=4):
+        assert L.live_allocs() == before
+    assert L.live_allocs() == before and before[0] >= 0 and before[1] >= 0
+
+
 def test_runner_reports_load_failure_like_the_bridge(L, tmp_path):
     states, tokens = [], []
     r = L.LlamaRunner(str(tmp_path / "missing.bin"))
