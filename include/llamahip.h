@@ -850,6 +850,29 @@ int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, co
 int llamahip_op_prep(int32_t mode, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
                      int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, uint32_t *qa_A, float *qa_d, int32_t qa_rows,
                      float *y, int32_t *kernel_taken, char *err, size_t err_cap);
+/* ONE launch of the single-row decode mat-vec (k_gemv) on caller-supplied operands: y = W * prologue(in0, in1), through the epilogue.
+ * w_q4_0 [M][K / 32] blocks in file layout, K a positive multiple of 64; interleaved: w is w1's F rows then w3's (M = 2F, F % 32 == 0),
+ * repacked into the w1|w3 tile order as a model load does it.  pre: _QA the op quantizes in0 [K] first (the activation launch of
+ * llamahip_op_mul_mat_q4_0) and the kernel copies the operand; _PLAIN in0 [K] is quantized in the kernel; _NORM in0 [K] is normalised with
+ * the weights in1 [K] (with part_in: n_part_in {sum x, sum x^2} pairs of doubles replace the row's reduction -- the PREP_NORMP instance,
+ * selected as in a model's step, LLAMAHIP_NORM_MODE included); _SILU_MUL silu_table(in0 = gate [K]) * (in1 = up [K]).
+ * epi: _STORE y [M]; _RESID y = acc + resid [M], and with part_out one {sum y, sum y^2} pair per workgroup (n_part_out must be the
+ * launch's grid, plan[4], at most 512; the buffer holds part_out_cap >= n_part_out pairs); _SILU_QA (interleaved only) y [F] (may be
+ * NULL) = silu_table(gate) * up and its Q4_0 operand in row 0 of out_A [out_rows][Fp / 4] / out_d [out_rows][Fp / 32], Fp = F rounded up
+ * to 256.  y [y_floats], out_A, out_d and part_out are copied to the device before the launch and back after it: whatever the launch
+ * does not write keeps the caller's bits.  plan[6] (may be NULL): the plan launched {waves, granules, depth, ring, grid, LDS bytes}, set
+ * before the device is looked for.  Refused before any device is touched: the pairs whose kernels wait on other launches or workgroups
+ * (tagged operands, the lm head's pick, half-block w1|w3), pairs and shapes without a kernel instance, bad counts, null operands. */
+#define LLAMAHIP_GEMV_PRE_QA       0
+#define LLAMAHIP_GEMV_PRE_PLAIN    1
+#define LLAMAHIP_GEMV_PRE_NORM     2
+#define LLAMAHIP_GEMV_PRE_SILU_MUL 3
+#define LLAMAHIP_GEMV_EPI_STORE    0
+#define LLAMAHIP_GEMV_EPI_RESID    1
+#define LLAMAHIP_GEMV_EPI_SILU_QA  2
+int llamahip_op_gemv_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t interleaved, int32_t pre, int32_t epi, const float *in0, const float *in1,
+                          const double *part_in, int32_t n_part_in, const float *resid, float *y, int64_t y_floats, uint32_t *out_A, float *out_d,
+                          int32_t out_rows, double *part_out, int32_t n_part_out, int32_t part_out_cap, int64_t *plan, char *err, size_t err_cap);
 /* Host-only: N rows of the raw operand above -> [N][K / 32] Q4_0 blocks in file layout (what llamahip_op_attention's wo_operand holds). */
 int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t N, int32_t K, void *blocks);
 /* The embedding gather (ggml_get_rows on a Q4_0 matrix): tokens [N] in [0, V) (checked on the host), emb [V][d / 32] blocks in file layout,

@@ -207,6 +207,7 @@ def lib() -> C.CDLL:
     L.llamahip_op_prep.argtypes = [i32, i32, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, i32, vp, vp, i32, vp, vp, cp, sz]
     L.llamahip_debug_qa_to_blocks.argtypes = [vp, vp, i32, i32, vp]
     L.llamahip_op_embed.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, cp, sz]
+    L.llamahip_op_gemv_q4_0.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_int64, vp, vp, i32, vp, i32, i32, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
     L.llamahip_get_stats.argtypes = [vp, C.POINTER(_Stats)]
     L.llamahip_debug_lut_math.restype = i32
@@ -1293,6 +1294,53 @@ def op_prep(mode: str, buf: np.ndarray, K: int, N: int, in_stride: int | None = 
                                 int(in1_stride), int(K), int(N), _ptr(qa_A), _ptr(qa_d), rows, _ptr(y), C.byref(taken), err, len(err))
     _check(rc, err)
     return qa_A, qa_d, y, PREP_KERNELS[taken.value]
+
+
+GEMV_PRE = {"qa": 0, "plain": 1, "norm": 2, "silu_mul": 3}      # LLAMAHIP_GEMV_PRE_* of llamahip.h
+GEMV_EPI = {"store": 0, "resid": 1, "silu_qa": 2}                # LLAMAHIP_GEMV_EPI_*
+
+
+def op_gemv_q4_0(wq: np.ndarray, pre, epi, in0, in1=None, resid=None, interleaved: bool = False, part_in=None, n_part_in: int | None = None,
+                 y_init=None, want_y: bool = True, out_rows: int = 2, out_fill: int = 0xFF, part_out=None, n_part_out: int | None = None):
+    """One launch of the single-row decode mat-vec (llamahip_op_gemv_q4_0).  wq uint8 [M, K/32, 20] in file layout (interleaved: w1's F rows
+    then w3's); pre / epi: a name of GEMV_PRE / GEMV_EPI or the library's own code; in0 / in1 / resid float32 as the pair takes them;
+    part_in float64 [n, 2]; y_init: the y buffer before the launch (default: NaN, one float per output); part_out: the buffer of pairs
+    before the launch (float64 [cap, 2]), n_part_out of which the launch is told about (default: all).  Returns dict(y, out_A, out_d,
+    part_out, plan): the buffers as the device left them (out_A / out_d [out_rows, Fp/4] / [out_rows, Fp/32] start as `out_fill` bytes with
+    the padded blocks of row 0 zero, as a model's workspace has them), plan = (nw, pg, depth, ring, grid, lds)."""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    M, nb, _ = wq.shape
+    K = nb * 32
+    pcode = GEMV_PRE[pre] if pre in GEMV_PRE else int(pre)
+    ecode = GEMV_EPI[epi] if epi in GEMV_EPI else int(epi)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32).ravel()
+    in0, in1, resid = f32(in0), f32(in1), f32(resid)
+    silu_qa = ecode == GEMV_EPI["silu_qa"]
+    F = M // 2
+    y = None
+    if want_y or y_init is not None:
+        y = np.full(F if silu_qa else M, np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").ravel()
+    out_A = out_d = None
+    if silu_qa:
+        Fp = (F + 255) // 256 * 256
+        out_A = np.full((out_rows, Fp // 4), out_fill * 0x01010101, np.uint32)
+        out_d = np.full((out_rows, Fp // 32), out_fill * 0x01010101, np.uint32)
+        for b in range(F // 32, Fp // 32 if out_rows > 0 else 0):      # (dword (c * 8 + k) * 8 + j holds chain k of block c * 8 + j)
+            out_d[0, b] = 0
+            out_A[0].reshape(Fp // 256, 8, 8)[b >> 3, :, b & 7] = 0
+        out_d = out_d.view(np.float32)
+    pin = None if part_in is None else np.ascontiguousarray(part_in, np.float64).reshape(-1, 2)
+    npin = (0 if pin is None else pin.shape[0]) if n_part_in is None else int(n_part_in)
+    pout = None if part_out is None else np.array(part_out, np.float64, order="C").reshape(-1, 2)
+    cap = 0 if pout is None else pout.shape[0]
+    npout = cap if n_part_out is None else int(n_part_out)
+    plan = np.zeros(6, np.int64)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_gemv_q4_0(_ptr(wq), M, K, int(interleaved), pcode, ecode, _ptr(in0), _ptr(in1), _ptr(pin), npin, _ptr(resid),
+                                     _ptr(y), 0 if y is None else y.size, _ptr(out_A), _ptr(out_d), int(out_rows), _ptr(pout), npout, cap,
+                                     _ptr(plan), err, len(err))
+    _check(rc, err)
+    return dict(y=y, out_A=out_A, out_d=out_d, part_out=pout, plan=tuple(int(v) for v in plan))
 
 
 def qa_to_blocks(qa_A: np.ndarray, qa_d: np.ndarray, N: int, K: int) -> np.ndarray:

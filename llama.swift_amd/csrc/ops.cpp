@@ -46,6 +46,89 @@ int llamahip_op_mul_mat_q4_0(const void *w_q4_0, int32_t M, int32_t K, const flo
     return s.ok() ? LLAMAHIP_OK : s.fail("llamahip_op_mul_mat_q4_0", err, err_cap);
 }
 
+static_assert(LLAMAHIP_GEMV_PRE_QA == PRE_QA && LLAMAHIP_GEMV_PRE_PLAIN == PREP_PLAIN && LLAMAHIP_GEMV_PRE_NORM == PREP_NORM && LLAMAHIP_GEMV_PRE_SILU_MUL == PREP_SILU_MUL, "llamahip.h mirrors the mat-vec prologues");
+static_assert(LLAMAHIP_GEMV_EPI_STORE == EPI_STORE && LLAMAHIP_GEMV_EPI_RESID == EPI_RESID && LLAMAHIP_GEMV_EPI_SILU_QA == EPI_SILU_QA, "... and epilogues");
+constexpr size_t GEMV_LDS_CAP = 160 * 1024;      // init_attrs_decode's dynamic-LDS attribute
+
+// one launch of the single-row decode mat-vec (k_gemv) on caller-supplied operands (per-op tests of every instance gemv_plan can pick): see llamahip.h
+int llamahip_op_gemv_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t interleaved, int32_t pre, int32_t epi, const float *in0, const float *in1,
+                          const double *part_in, int32_t n_part_in, const float *resid, float *y, int64_t y_floats, uint32_t *out_A, float *out_d,
+                          int32_t out_rows, double *part_out, int32_t n_part_out, int32_t part_out_cap, int64_t *plan, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_gemv_q4_0";
+    // the pairs that wait on other launches or other workgroups (tagged operands, the lm head's pick, half-block exchange): not an op's to launch
+    const char *waits = pre == PREP_NORM_TAG ? "PREP_NORM_TAG" : epi == EPI_STORE_TAG ? "EPI_STORE_TAG" : epi == EPI_RESID_TAG ? "EPI_RESID_TAG"
+                      : epi == EPI_STORE_PICK ? "EPI_STORE_PICK" : epi == EPI_SILU_QAH ? "EPI_SILU_QAH" : nullptr;
+    if (waits) { set_err(err, err_cap, "%s: %s waits on other launches or workgroups: the op launches the untagged pairs only", fn, waits); return LLAMAHIP_ERR_PREDICT; }
+    if (pre == PREP_NORMP) { set_err(err, err_cap, "%s: PREP_NORMP is pre NORM with part_in / n_part_in", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (pre < PRE_QA || pre > PREP_SILU_MUL) { set_err(err, err_cap, "%s: unknown prologue %d", fn, pre); return LLAMAHIP_ERR_PREDICT; }
+    if (epi < EPI_STORE || epi > EPI_SILU_QA) { set_err(err, err_cap, "%s: unknown epilogue %d", fn, epi); return LLAMAHIP_ERR_PREDICT; }
+    if (M < 1 || K < 64 || K % 64 != 0) { set_err(err, err_cap, "%s: bad shape (M %d >= 1; K %d must be a positive multiple of 64)", fn, M, K); return LLAMAHIP_ERR_PREDICT; }
+    if (interleaved && M % 64 != 0) { set_err(err, err_cap, "%s: interleaved takes w1's F rows then w3's with F %% 32 == 0: M = 2F = %d is not a multiple of 64", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    const bool has1 = pre == PREP_NORM || pre == PREP_SILU_MUL, silu_qa = epi == EPI_SILU_QA;
+    if (!w_q4_0 || !in0 || (has1 && !in1)) { set_err(err, err_cap, "%s: null operand (w, in0%s)", fn, has1 ? ", in1" : ""); return LLAMAHIP_ERR_PREDICT; }
+    if (epi == EPI_RESID && !resid) { set_err(err, err_cap, "%s: EPI_RESID needs resid", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int64_t n_out = silu_qa ? M / 2 : M;      // floats the launch writes to y
+    if (!silu_qa && !y) { set_err(err, err_cap, "%s: y is NULL (only EPI_SILU_QA may leave it out)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (y && y_floats < n_out) { set_err(err, err_cap, "%s: y_floats %lld < the %lld outputs", fn, (long long) y_floats, (long long) n_out); return LLAMAHIP_ERR_PREDICT; }
+    if (silu_qa && (!out_A || !out_d || out_rows < 1)) { set_err(err, err_cap, "%s: EPI_SILU_QA needs out_A, out_d and out_rows %d >= 1", fn, out_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (part_in && pre != PREP_NORM) { set_err(err, err_cap, "%s: part_in is the NORM prologue's", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (part_in && (n_part_in < 1 || n_part_in > NORM_PART_MAX)) { set_err(err, err_cap, "%s: n_part_in %d outside 1 .. %d (NORM_PART_MAX)", fn, n_part_in, NORM_PART_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (part_out && epi != EPI_RESID) { set_err(err, err_cap, "%s: part_out is the RESID epilogue's", fn); return LLAMAHIP_ERR_PREDICT; }
+    QMat q;
+    q.set_shape(M, K);
+    if (interleaved) q.gmapF8 = M / 16;
+    NormPart np;
+    np.in = part_in; np.n_in = part_in ? n_part_in : 0;
+    int pre_run = pre;
+    norm_mode_resolve(&pre_run, &np);      // (the plan of what launch_gemv will launch: PREP_NORMP where the parts are taken)
+    const GemvPlan p = gemv_plan(q, pre_run, epi);
+    if (!gemv_plan_has_kernel(pre_run, epi, p)) {
+        set_err(err, err_cap, "%s: k_gemv has no instance for prologue %d, epilogue %d on M %d, K %d%s (plan: %d waves, %d granules, depth %d, ring %d)", fn, pre_run, epi, M, K,
+                interleaved ? " interleaved" : "", p.nw, p.pg, p.depth, (int) p.ring);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (p.lds > GEMV_LDS_CAP) { set_err(err, err_cap, "%s: K %d needs %zu bytes of LDS, the kernels' cap is %zu", fn, K, p.lds, GEMV_LDS_CAP); return LLAMAHIP_ERR_PREDICT; }
+    if (part_out && (p.grid > NORM_PART_MAX || n_part_out != p.grid || part_out_cap < n_part_out)) {
+        set_err(err, err_cap, "%s: part_out takes %d pairs (one per workgroup: gemv_resid_parts), at most %d (NORM_PART_MAX); got %d in a buffer of %d", fn, p.grid, NORM_PART_MAX, n_part_out, part_out_cap);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (plan) { const int64_t o[6] = { p.nw, p.pg, p.depth, p.ring, p.grid, (int64_t) p.lds }; for (int i = 0; i < 6; i++) plan[i] = o[i]; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t nb = (size_t) K / 32, Kp = (size_t) q.Kp(), F = (size_t) M / 2, Fp = (F + 255) / 256 * 256;
+    const size_t oA = silu_qa ? (size_t) out_rows * Fp / 4 : 0, od = silu_qa ? (size_t) out_rows * (Fp / 32) : 0;
+    const bool tables = pre == PREP_SILU_MUL || silu_qa;
+    std::vector<uint16_t> ts, te;
+    if (tables) { ts.resize(1 << 16); te.resize(1 << 16); lut_tables(ts, te); }
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_w = s.alloc((size_t) M * nb * 20, (const uint8_t *) w_q4_0);
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    float *d_in0 = s.alloc((size_t) K, in0), *d_in1 = has1 ? s.alloc((size_t) K, in1) : nullptr;
+    float *d_r = epi == EPI_RESID ? s.alloc((size_t) M, resid) : nullptr;
+    float *d_y = y ? s.alloc((size_t) y_floats, y) : nullptr;      // (the floats past the outputs keep the caller's bits; so do the buffers below)
+    uint32_t *d_oA = silu_qa ? s.alloc(oA, out_A) : nullptr;
+    float *d_od = silu_qa ? s.alloc(od, out_d) : nullptr;
+    double *d_pi = part_in ? s.alloc((size_t) 2 * n_part_in, part_in) : nullptr;
+    double *d_po = part_out ? s.alloc((size_t) 2 * part_out_cap, part_out) : nullptr;
+    uint32_t *d_qA = pre == PRE_QA ? s.alloc<uint32_t>(Kp / 4) : nullptr;
+    float *d_qd = pre == PRE_QA ? s.alloc<float>(Kp / 32) : nullptr;
+    uint16_t *d_ts = tables ? s.alloc(ts.size(), ts.data()) : nullptr, *d_te = tables ? s.alloc(te.size(), te.data()) : nullptr;
+    if (s.ok() && tables) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    if (s.ok() && !interleaved) s.check(launch_repack(d_w, q.tiles, M, K, 0, 0, st));
+    if (s.ok() && interleaved) s.check(launch_repack(d_w, q.tiles, (int) F, K, 1, 0, st));                      // as the loader: w1's rows ...
+    if (s.ok() && interleaved) s.check(launch_repack(d_w + F * nb * 20, q.tiles, (int) F, K, 1, 4, st));        // ... then w3's
+    if (s.ok() && pre == PRE_QA) s.check(launch_prep(PREP_PLAIN, d_in0, nullptr, K, 0, K, 1, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+    np = NormPart();
+    np.in = d_pi; np.n_in = d_pi ? n_part_in : 0; np.out = d_po;
+    if (s.ok()) s.check(launch_gemv(q, pre, epi, d_qA, d_qd, pre == PRE_QA ? nullptr : d_in0, d_in1, d_y, d_r, d_ts, d_oA, d_od, st, &np));
+    if (y) s.download(y, d_y, (size_t) y_floats * 4);
+    if (silu_qa) { s.download(out_A, d_oA, oA * 4); s.download(out_d, d_od, od * 4); }
+    if (part_out) s.download(part_out, d_po, (size_t) part_out_cap * 16);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
+}
+
 // one prompt GEMM kernel on caller-supplied operands (per-op tests of every kernel launch_gemm can pick): see llamahip.h
 int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {

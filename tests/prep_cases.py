@@ -113,11 +113,52 @@ def norm_stats(x):
                 v_ok=v_ok, scale_ok=bool(sc_lo == sc_hi), proof=bool(v_ok and sc_lo == sc_hi), scale=float(1 / np.sqrt(t_star)))
 
 
-def find_attempts(make_row, N, seed, limit=2000):
+def one_pass_stats(x):
+    """The ONE-PASS second moment of one fp32 row, sum2 = fma(-mean, S1, S2) with S1 = sum x, S2 = sum x^2 and mean = S1 / K in double (the
+    fused norm prologue of the decode mat-vec; S1 / S2 reduced by the kernel in its own order or handed over as per-slice partial sums),
+    and the interval every order can reach.  With u = 2^-53, A = sum|x|, exact S1, S2 and Q* = S2 - S1^2 / K = sum (x - m*)^2:
+      S1^: K - 1 additions of exact terms in any tree (rounded partial sums of slices that are then added are such a tree):
+           |S1^ - S1| <= e1 = gamma_K A   (0 where every partial sum is exact, sums_are_exact)
+      S2^: x^2 is exact in double (48 bits), so again only the additions round:   |S2^ - S2| <= e2 = gamma_K S2
+      mean^ = fl(S1^ / K):   |mean^ - m*| <= em = e1 / K + 2^-52 |m*|
+      mean^ S1^ - m* S1 = mean^ (S1^ - S1) + S1 (mean^ - m*):   |.| <= (|m*| + em) e1 + |S1| em
+      the fma rounds once:   |sum2^ - Q*| <= E + 2^-52 (|Q*| + E),   E = e2 + (|m*| + em) e1 + |S1| em
+    (each bound carries a factor 1 + 2^-40 for the roundings of this evaluation itself).  1 / sqrt(sum2 / K + eps) is monotone, so if
+    (float) scale agrees at both ends -- widened by 2^-50 as in norm_stats -- it is the same float for every order, and since Q* lies in
+    this interval and in norm_stats' two-pass one, it is the two-pass float too.  The kernel takes this form only where mean^ S1^ <= 0.25
+    S2^; `fast_possible` says whether ANY order can satisfy that (lower bound of the left side against the upper bound of the right),
+    `fast_certain` whether every order does.  A row on which no order can take the one-pass form is proved by norm_stats alone; every
+    other row needs scale_ok.  dict(fast_possible, fast_certain, lo, hi, scale_ok, proof)."""
+    xd = x.astype(np.float64)
+    K = x.size
+    sl = 1 + 2.0 ** -40
+    S1, A, S2 = math.fsum(xd), math.fsum(np.abs(xd)), math.fsum(xd * xd)
+    m = abs(S1) / K
+    e1 = 0.0 if sums_are_exact(x) else gamma(K) * A * sl
+    e2 = gamma(K) * S2 * sl
+    em = (e1 / K + 2.0 ** -52 * m) * sl
+    E = (e2 + (m + em) * e1 + abs(S1) * em) * sl
+    q = norm_stats(x)["q"]
+    w = 2.0 ** -50
+    lo, hi = q - E - w * (abs(q) + E), q + E + w * (abs(q) + E)
+    lhs_lo, lhs_hi = max(m - em, 0.0) * max(abs(S1) - e1, 0.0) * (1 - w), (m + em) * (abs(S1) + e1) * (1 + w)
+    rhs_lo, rhs_hi = 0.25 * (S2 - e2) * (1 - w), 0.25 * (S2 + e2) * (1 + w)
+    fast_possible, fast_certain = bool(lhs_lo <= rhs_hi), bool(lhs_hi <= rhs_lo)
+    t_lo, t_hi = (LD(lo) / K + LD(EPS_NORM)) * (1 - LD(w)), (LD(hi) / K + LD(EPS_NORM)) * (1 + LD(w))
+    scale_ok = bool(t_lo > 0 and np.float32(1 / np.sqrt(t_lo) * (1 + LD(w))) == np.float32(1 / np.sqrt(t_hi) * (1 - LD(w))))
+    return dict(fast_possible=fast_possible, fast_certain=fast_certain, lo=lo, hi=hi, scale_ok=scale_ok, proof=bool(scale_ok or not fast_possible))
+
+
+def norm_proof_both(x):
+    """order-proof under the two-pass form (norm_stats) AND under the one-pass form wherever an order can take it (one_pass_stats)"""
+    return norm_stats(x)["proof"] and one_pass_stats(x)["proof"]
+
+
+def find_attempts(make_row, N, seed, limit=2000, proof=lambda x: norm_stats(x)["proof"]):
     """per row n the first attempt a whose row make_row(default_rng([seed, n, a]), n) is order-proof -- how NORM_ATTEMPTS was made"""
     out = []
     for n in range(N):
-        a = next((a for a in range(limit) if norm_stats(make_row(np.random.default_rng([seed, n, a]), n))["proof"]), None)
+        a = next((a for a in range(limit) if proof(make_row(np.random.default_rng([seed, n, a]), n))), None)
         assert a is not None, f"no order-proof row in {limit} draws (row {n}, seed {seed})"
         out.append(a)
     return tuple(out)

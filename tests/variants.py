@@ -16,6 +16,7 @@ ROOT = os.path.dirname(HERE)
 
 PARITY = os.path.join(HERE, "test_gpu_parity.py")
 PIPELINE = os.path.join(HERE, "test_pipeline.py")
+GEMV_OP = os.path.join(HERE, "test_gpu_gemv_op.py")
 
 # (environment, pytest id) of test_few_row_kernel_selectable_epilogues_and_plans
 SET_PLAN_VARIANTS = [
@@ -51,6 +52,8 @@ NESTED = {"matrix_core_prompt_gemm_forced": ({"LLAMAHIP_MFMA_MIN": "32"}, "promp
 NESTED.update({"attn:" + tag: (env, sel, [PARITY]) for env, sel, tag in ATTN_FALLBACKS})
 NESTED.update({"plan:" + tag: (env, "short_chunks or batched_set_steps_equal or prompt_continuation", [PARITY, PIPELINE]) for env, tag in SET_PLAN_VARIANTS})
 NESTED.update({"prod:" + tag: (env, _PROD_SELECT, [PARITY]) for env, tag in PRODUCTION_FALLBACKS})
+# ... and with the tables gathered also the SiLU cases of the decode mat-vec's per-op file (the SILU_MUL prologue, the SILU_QA epilogue)
+NESTED["prod:tables_gathered"] = (NESTED["prod:tables_gathered"][0], _PROD_SELECT + " or (test_gpu_gemv_op and silu)", [PARITY, GEMV_OP])
 EPI_STORE, EPI_RESID, EPI_SILU_QA, EPI_ROPE_KV, EPI_SILU_QAH = 0, 1, 2, 3, 7
 SET_PAIRS = {(1, 2), (1, 3), (1, 4), (2, 1), (2, 2), (2, 3), (2, 4), (3, 1), (3, 3), (3, 4), (4, 1), (4, 2), (4, 4), (5, 1)}
 
