@@ -571,7 +571,7 @@ int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n
  *   chunk_tokens < 0, row_budget < 0 or > LLAMAHIP_EVAL_MULTI_MAX_ROWS - 16, sampler parameters llamahip_verify_sample refuses, HOST_ONLY and
  *   stage handles, a handle that already has a scheduler.  llamahip_sched_submit: n_prompt < 1, n_predict < 1, a token id (or a stop token other than -1) out of range, n_prompt +
  *   n_predict - 1 > n_ctx, with chunk_tokens == 0 a prompt longer than LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active, a sampler held by another
- *   live request.  llamahip_sched_step: cap < 2 * max_active + 1 (the call consumes nothing).
+ *   live request.  llamahip_sched_step: cap < LLAMAHIP_SCHED_EVENT_CAP (2 * max_active + 1 without drafts; the call consumes nothing).
  * llamahip_sched_cancel: a queued or active request ends with a DONE event of reason CANCELLED in the next step's events (an active one
  *   takes no row in that step; its slot is free from that step on); -1 for an id that is not live.  llamahip_sched_pending: queued + active
  *   + cancelled requests whose DONE has not been delivered.  A step that fails (LLAMAHIP_ERR_PREDICT) delivers no event and loses none: the
@@ -585,7 +585,52 @@ int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n
  *   1124 for static waves of llamahip_eval_multi + llamahip_decode_greedy_multi, which keep stepping finished sequences; the longest step --
  *   the stall a decoding conversation sees while prompts are admitted -- is 24.3 ms at 256 and 7.5 ms at 32.  A set-step capture costs 1.2 ..
  *   1.35 ms and a run makes 8 .. 13 of them.
- * Not built: drafts inside the scheduler; prefix copy between slots; the scheduler behind llama_runner; more than 16 active sequences;
+ * Drafted tokens in the rows a step leaves spare (llamahip_sched_opts.draft_len > 0; off by default).  A step has 16 logits
+ *   rows (VERIFY_ROWS_MAX); whenever fewer than 16 segments emit, the rest carry prompt-lookup drafts of the decoding requests.  What a request
+ *   WANTS: llamahip_lookup_draft over its prompt + everything it has produced, then the scheduler's corpus, cut to draft_len and to n_predict -
+ *   n_out - 1 (a verify step never passes n_predict, hence never n_ctx); 0 for a sampled request whose window exceeds 1024 ids, and for every
+ *   sampled request when top_k > 64 or n_vocab > 32768.  What it GETS: llamahip_sched_plan_drafts (host only, pure -- the one place the draft
+ *   policy lives).  Sequences in admission order, rows = llamahip_sched_plan's; want[i] must be 0 unless prompt_left[i] == 0.  A segment
+ *   emits if it is a decode row or a prompt piece with rows[i] == prompt_left[i]; spare = 16 - (emitting segments), further capped so that
+ *   sum(rows) + sum(give) <= LLAMAHIP_EVAL_MULTI_MAX_ROWS; the spare rows go to the decoding sequences by llamahip_lookup_deal_rows' rule (one
+ *   draft token at a time, round-robin in admission order).  Returns sum(give), -1 for bad arguments (n_active outside 0 .. 16, a null array,
+ *   a negative entry, want outside 0 .. 15 or non-zero on a prefilling sequence, rows[i] != 1 on a decoding one).  Draft rows do not count
+ *   against row_budget (it bounds the prompt rows and so the stall; at most 15 draft rows ride on any step).
+ *   A step that carries at least one draft row is a MIXED PASS whether or not anybody prefills: a decoding segment is [last token, draft ...]
+ *   at the slot's position, every row keyed as its own single-token eval (keys = position + 1, whatever chunk_tokens); the lm head runs over
+ *   every row of a draft segment and the last row of every other emitting segment.  Greedy segments: k_verify_rows picks every logits row,
+ *   k_sched_accept (one wave per segment) counts n_accept = the largest a <= n_draft with pick[j] == draft[j] for all j < a, publishes the
+ *   slot's words and returns 4 (rows + segments) bytes.  Sampled segments (ordered first): the sliding-window candidate selection over their
+ *   rows and the host walk of llamahip_verify_sample_multi (draw, accept, continue only while the draw is the draft's next token); after such
+ *   a step the host pushes the slots' words.  The request then produces n_accept + 1 TOKEN events in that step, in order, at consecutive
+ *   positions, ending at its stop token (accepted tokens behind a stop token are dropped and never reported; the slot's KV rows behind the
+ *   reported context are stale and never read) or at n_predict; its DONE follows its last TOKEN.  A step in which nothing is dealt is exactly
+ *   the step of a scheduler without drafts and is counted as such.  Fall-back handles draft nothing and report zero drafts.
+ *   The contract above holds unchanged: tokens, KV rows [0, n_prompt + n - 1), sampler window and rng state of the request ALONE
+ *   (BY TEST: tests/test_gpu_sched_draft.py).
+ *   Event capacity: LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len) -- with draft_len > 0 max_active + 17 (at most 16 logits rows = TOKEN
+ *   events per step, one DONE per request, one waiting DONE); 2 * max_active + 1 otherwise, as before.
+ *   Stats identity: n_tokens == n_emit_segs + n_accepted - n_dropped (n_emit_segs: emitting segments over all steps; n_accepted: draft tokens
+ *   the model reproduced; n_dropped: accepted tokens behind a stop token); n_accepted <= n_drafted.
+ *   Refused by llamahip_sched_new before any device work: draft_len outside 0 .. 15, ngram bounds llamahip_lookup_draft refuses (negative,
+ *   ngram_max < ngram_min after the defaults), n_corpus < 0 or without a corpus, a corpus token id out of range.
+ *   llamahip_op_sched_accept -- k_verify_rows + k_sched_accept on caller-supplied rows (parity tests): logits[n_rows][n_vocab], n_rows 1 .. 16;
+ *   seg_tab[n_segs][6] = {emit, slot, base position, base cursor, first logits row, row count}, n_segs 1 .. 16.  emit 0: no logits row (a
+ *   prompt piece that does not end its prompt); 1: one logits row, the segment's last of `row count` rows (a piece that ends its prompt, a
+ *   plain decode row); 2: every one of its `row count` rows has a logits row ([last token, draft ...]; tokens[r] = the token of logits row r).
+ *   The logits rows of the emitting segments tile [0, n_rows) in segment order.  n_accept[s] as above (0 unless emit == 2), picks[r] = the
+ *   greedy pick of logits row r.  With slot words (state[n_slots][2], log[n_slots][log_cap], next_tok[n_slots]: all three or none; copied
+ *   both ways, what the launch does not write keeps the caller's bits): position = base + rows consumed (n_accept + 1 for emit 2, the row
+ *   count otherwise), cursor = base cursor + tokens produced (n_accept + 1, 1, or 0 without a logits row), next-token word = pick[n_accept],
+ *   log[slot][base cursor + j] = pick[j] for j <= n_accept (entries at or past log_cap are dropped).
+ *   Measured on the 7B (profiles/sched_draft_probe_7b.json, tools/sched_probe.py --draft), the workload above at row_budget 256,
+ *   draft_len 15: 2321 tokens/s without drafts; 2508 with a corpus from which every draft is accepted (311 steps for 437: the 16 slots are
+ *   busy for most of the run, spare rows exist in its tail only); 2358 with 0.49 of the drafted tokens accepted; 2021 with none of 1578 accepted -- a
+ *   decode-only step that carries a draft is a mixed pass, not the captured set step.  Drafting pays from an acceptance rate of 0.44 on this
+ *   workload (interpolated); below it, leave draft_len at 0, the default.  draft_len == 0 against the parent commit's library, fresh processes,
+ *   interleaved, five each: 2321 against 2324 tokens/s, inside the parent's own spread of 19.
+ * Not built: prefix copy between slots; the scheduler behind llama_runner; more than 16 active sequences; a set-step-descriptor form for
+ *   decode-only drafted steps; drafts counted against row_budget;
  *   generating past n_ctx (llamahip_decode_greedy_window's overflow plan); the mixed pass on the fused few-row launches. */
 #define LLAMAHIP_SCHED_ROW_BUDGET 256     /* the candidate of 16 .. 256 with the highest median tokens/s on the probe workload: profiles/sched_probe_7b.json, DESIGN.md 12.19 */
 #define LLAMAHIP_EV_TOKEN 1
@@ -602,7 +647,12 @@ typedef struct llamahip_sched_opts {
     int32_t row_budget;      /* rows a step aims at; 0 = LLAMAHIP_SCHED_ROW_BUDGET */
     double  repeat_penalty, top_p, temp;      /* for requests that carry a sampler; all three 0 with top_k 0: 1.3, 0.95f, 0.8f and top_k 40 */
     int32_t top_k;
+    /* drafted tokens (read only where struct_size covers them; a shorter struct means no drafting) */
+    int32_t draft_len;       /* 0 = off; 1 .. 15 draft tokens per request and step at the most */
+    int32_t ngram_min, ngram_max;              /* llamahip_lookup_draft's; 0 = LLAMAHIP_LOOKUP_NGRAM_MIN / _MAX */
+    const int32_t *corpus; int32_t n_corpus;   /* optional, searched behind a request's own history; copied at llamahip_sched_new */
 } llamahip_sched_opts;
+#define LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len) ((draft_len) > 0 ? (max_active) + 17 : 2 * (max_active) + 1)   /* the smallest cap llamahip_sched_step takes */
 typedef struct llamahip_request {
     int32_t struct_size;
     const int32_t *prompt; int32_t n_prompt;   /* >= 1; copied at submit */
@@ -621,6 +671,9 @@ typedef struct llamahip_sched_stats {
     int64_t n_steps, n_mixed_steps, n_set_steps, n_single_steps, n_fallback_steps;   /* steps that made a pass, by kind */
     int64_t n_rows, n_prompt_rows, n_tokens;   /* rows evaluated, of those prompt rows, tokens produced */
     int64_t n_submitted, n_done;
+    int64_t n_draft_steps;                     /* steps that carried at least one draft row */
+    int64_t n_drafted, n_accepted;             /* draft tokens evaluated; of those, reproduced by the model */
+    int64_t n_emit_segs, n_dropped;            /* emitting segments over all steps; accepted tokens dropped behind a stop token */
 } llamahip_sched_stats;
 int     llamahip_sched_new   (llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap);
 int     llamahip_sched_submit(llamahip_sched *s, const llamahip_request *r, int64_t *id, char *err, size_t err_cap);
@@ -632,6 +685,11 @@ void    llamahip_sched_free  (llamahip_sched *s);
 int32_t llamahip_sched_plan(int32_t n_active, const int32_t *prompt_left /* admission order, 0 = decoding */,
                             int32_t chunk_tokens, int32_t row_budget, int32_t *rows_out);
 int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, int32_t *picks, char *err, size_t err_cap);
+int32_t llamahip_sched_plan_drafts(int32_t n_active, const int32_t *prompt_left, const int32_t *rows /* llamahip_sched_plan's */,
+                                   const int32_t *want, int32_t *give);
+int llamahip_op_sched_accept(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *seg_tab, int32_t n_segs, const int32_t *tokens,
+                             int32_t n_slots, int32_t log_cap, int32_t *state, int32_t *log, int32_t *next_tok,
+                             int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */

@@ -46,6 +46,7 @@ from .binding import (  # noqa: F401
     op_prep,
     op_prompt_gemm_q4_0,
     op_quantize_row_q4_0,
+    op_sched_accept,
     op_sched_pick,
     op_topk,
     op_topk_rows,
@@ -55,7 +56,9 @@ from .binding import (  # noqa: F401
     op_verify_rows_set,
     qa_to_blocks,
     quantize_file,
+    sched_event_cap,
     sched_plan,
+    sched_plan_drafts,
     gemv_plan,
     set_plan,
     version,

@@ -68,7 +68,8 @@ class _LookupStats(C.Structure):
 
 class _SchedOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_threads", C.c_int32), ("max_active", C.c_int32), ("chunk_tokens", C.c_int32),
-                ("row_budget", C.c_int32), ("repeat_penalty", C.c_double), ("top_p", C.c_double), ("temp", C.c_double), ("top_k", C.c_int32)]
+                ("row_budget", C.c_int32), ("repeat_penalty", C.c_double), ("top_p", C.c_double), ("temp", C.c_double), ("top_k", C.c_int32),
+                ("draft_len", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32), ("corpus", C.c_void_p), ("n_corpus", C.c_int32)]
 
 
 class _Request(C.Structure):
@@ -84,7 +85,8 @@ class _SchedEvent(C.Structure):
 class _SchedStats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_graph_captures", C.c_int32), ("n_steps", C.c_int64), ("n_mixed_steps", C.c_int64),
                 ("n_set_steps", C.c_int64), ("n_single_steps", C.c_int64), ("n_fallback_steps", C.c_int64), ("n_rows", C.c_int64),
-                ("n_prompt_rows", C.c_int64), ("n_tokens", C.c_int64), ("n_submitted", C.c_int64), ("n_done", C.c_int64)]
+                ("n_prompt_rows", C.c_int64), ("n_tokens", C.c_int64), ("n_submitted", C.c_int64), ("n_done", C.c_int64),
+                ("n_draft_steps", C.c_int64), ("n_drafted", C.c_int64), ("n_accepted", C.c_int64), ("n_emit_segs", C.c_int64), ("n_dropped", C.c_int64)]
 
 
 class _Stats(C.Structure):
@@ -199,6 +201,9 @@ def lib() -> C.CDLL:
     L.llamahip_sched_plan.argtypes = [i32, vp, i32, i32, vp]
     L.llamahip_sched_plan.restype = i32
     L.llamahip_op_sched_pick.argtypes = [vp, i32, i32, vp, vp, cp, sz]
+    L.llamahip_sched_plan_drafts.argtypes = [i32, vp, vp, vp, vp]
+    L.llamahip_sched_plan_drafts.restype = i32
+    L.llamahip_op_sched_accept.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
     L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
     L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
@@ -777,9 +782,11 @@ class Model:
         return (out, np_out.value, logits) if want_logits else (out, np_out.value)
 
     def scheduler(self, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8, repeat_penalty: float = 1.3,
-                  top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8))) -> "Scheduler":
-        """llamahip_sched_new: a request scheduler over KV slots [0, max_active) of this handle (include/llamahip.h "request scheduler")."""
-        return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp)
+                  top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), draft_len: int = 0,
+                  ngram_min: int = 0, ngram_max: int = 0, corpus=None) -> "Scheduler":
+        """llamahip_sched_new: a request scheduler over KV slots [0, max_active) of this handle (include/llamahip.h "request scheduler").
+        draft_len > 0: drafted tokens ride in the rows a step leaves spare (prompt lookup in each request's history, then `corpus`)."""
+        return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp, draft_len, ngram_min, ngram_max, corpus)
 
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
@@ -876,16 +883,19 @@ class Scheduler:
     passes, decode, and leave at their stop token or their length.  A context manager; one step() = one weight pass."""
 
     def __init__(self, model: Model, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8,
-                 repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8))):
+                 repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)),
+                 draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0, corpus=None):
         self._s = None
-        self.model, self.max_active = model, int(max_active)
+        self.model, self.max_active, self.draft_len = model, int(max_active), int(draft_len)
         self._samplers = {}          # id -> Sampler: kept alive while the request may draw
-        o = _SchedOpts(C.sizeof(_SchedOpts), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k)
+        c = np.ascontiguousarray(corpus if corpus is not None else [], np.int32).ravel()          # (copied by llamahip_sched_new)
+        o = _SchedOpts(C.sizeof(_SchedOpts), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k,
+                       int(draft_len), int(ngram_min), int(ngram_max), c.ctypes.data if c.size else None, c.size)
         h = C.c_void_p()
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_sched_new(model._h, C.byref(o), C.byref(h), err, len(err)), err)
         self._s = h
-        self._ev = (_SchedEvent * (2 * self.max_active + 64))()
+        self._ev = (_SchedEvent * (sched_event_cap(self.max_active, self.draft_len) + 63))()          # (room for waiting DONE events)
 
     def close(self) -> None:
         if self._s:
@@ -919,6 +929,7 @@ class Scheduler:
         """llamahip_sched_step: one weight pass; the step's events as dicts {id, kind ("token" / "done"), token, exact, slot, position, reason}."""
         n = C.c_int32(0)
         err = C.create_string_buffer(1024)
+        assert len(self._ev) >= sched_event_cap(self.max_active, self.draft_len)
         _check(lib().llamahip_sched_step(self._s, C.cast(self._ev, C.c_void_p), len(self._ev) if cap is None else int(cap), C.byref(n), err, len(err)), err)
         out = []
         for e in self._ev[:n.value]:
@@ -953,6 +964,48 @@ class Scheduler:
                     if on_done is not None:
                         on_done(e)
         return out
+
+
+def sched_event_cap(max_active: int, draft_len: int = 0) -> int:
+    """LLAMAHIP_SCHED_EVENT_CAP: the smallest event capacity llamahip_sched_step takes."""
+    return max_active + 17 if draft_len > 0 else 2 * max_active + 1
+
+
+def sched_plan_drafts(prompt_left, rows, want):
+    """llamahip_sched_plan_drafts (host only): (draft rows dealt, draft tokens per sequence) for sequences in admission order -- prompt_left and
+    rows as llamahip_sched_plan takes and gives them, want[i] the draft tokens sequence i could use; -1 = bad arguments."""
+    left, rows, want = (np.ascontiguousarray(a, np.int32).ravel() for a in (prompt_left, rows, want))
+    if not left.size == rows.size == want.size:
+        raise ValueError(f"sched_plan_drafts: {left.size} / {rows.size} / {want.size} entries")
+    give = np.full(max(left.size, 1), -1, np.int32)
+    n = lib().llamahip_sched_plan_drafts(left.size, *((_ptr(left), _ptr(rows), _ptr(want)) if left.size else (None, None, None)), _ptr(give))
+    return int(n), give[:left.size]
+
+
+def op_sched_accept(logits2d, seg_tab, tokens, state=None, log=None, next_tok=None):
+    """k_verify_rows + k_sched_accept on host rows (llamahip_op_sched_accept): seg_tab [n_segs][6] = {emit, slot, base position, base cursor,
+    first logits row, row count}, tokens [n_rows]; the slot words state [n_slots][2], log [n_slots][log_cap], next_tok [n_slots] -- all three
+    or none -- are updated in place (int32, C-contiguous).  Returns (n_accept [n_segs], picks [n_rows])."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    R, V = logits2d.shape
+    tab = np.ascontiguousarray(seg_tab, np.int32).reshape(-1, 6)
+    tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+    if tokens.size != R:
+        raise ValueError(f"op_sched_accept: {R} rows, {tokens.size} tokens")
+    words = [a for a in (state, log, next_tok) if a is not None]
+    for a in words:
+        if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+            raise ValueError("op_sched_accept: the slot words are int32 C-contiguous arrays, updated in place")
+    n_slots = int(next_tok.size) if next_tok is not None else 0
+    log_cap = int(log.size // max(n_slots, 1)) if log is not None else 0
+    if len(words) == 3 and (state.size != 2 * n_slots or log.size != n_slots * log_cap):
+        raise ValueError("op_sched_accept: state [n_slots][2], log [n_slots][log_cap], next_tok [n_slots]")
+    n_acc = np.full(max(len(tab), 1), -7, np.int32)
+    picks = np.full(max(R, 1), -7, np.int32)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_sched_accept(_ptr(logits2d), R, V, _ptr(tab), len(tab), _ptr(tokens), n_slots, log_cap,
+                                          *(None if a is None else _ptr(a) for a in (state, log, next_tok)), _ptr(n_acc), _ptr(picks), err, len(err)), err)
+    return n_acc[:len(tab)], picks[:R]
 
 
 def sched_plan(prompt_left, chunk_tokens: int, row_budget: int):

@@ -2280,7 +2280,15 @@ struct RowsPass {
     const int32_t *slots = nullptr, *n_past = nullptr, *n_tokens = nullptr;
     std::vector<int32_t> pos, keys, seg;          // llamahip_eval_multi_rows
     int n_short_segs = 0, n_long_segs = 0, n_short_rows = 0, max_keys = 1;      // max_keys: the largest position + 1 among the short segments' rows
+    // a scheduler step with drafted tokens (empty otherwise: llamahip_eval_multi's pass as it is).  seg_single[i]: every row of segment i is keyed
+    // as its own single-token eval, keys = position + 1, whatever `chunk` -- the per-segment override of the key rule.  logit_rows: the rows the
+    // lm head runs over, in logits-row order (empty: every segment's last row), at most ROWS_LOGITS_MAX
+    std::vector<char> seg_single;
+    std::vector<int32_t> logit_rows;
+    int n_logits() const { return logit_rows.empty() ? n_seqs : (int) logit_rows.size(); }
 };
+constexpr int ROWS_LOGITS_MAX = VERIFY_ROWS_MAX;
+static size_t rows_idx_entries(const llamahip_model *m) { return (size_t) std::max(m->n_seq, ROWS_LOGITS_MAX); }      // the lm head's row list
 struct RowsDev { RowTab *tab; int32_t *short_idx, *last_idx; };
 static RowsDev rows_dev(llamahip_model *m) {
     char *b = m->d_rows;
@@ -2293,10 +2301,14 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
         HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
         m->own.release(&m->d_rows); m->rows_cap = 0;
         const int cap = std::max(rp.R, 64);
-        HIP_TRY(m->own.alloc(&m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + rows_idx_entries(m) * 4), LLAMAHIP_ERR_PREDICT);
         m->rows_cap = cap;
     }
-    const size_t cap = (size_t) m->rows_cap, bytes = cap * (sizeof(RowTab) + 4) + (size_t) m->n_seq * 4;
+    const size_t cap = (size_t) m->rows_cap, bytes = cap * (sizeof(RowTab) + 4) + rows_idx_entries(m) * 4;
+    if (rp.logit_rows.size() > (size_t) ROWS_LOGITS_MAX || (rp.logit_rows.empty() && (size_t) rp.n_seqs > rows_idx_entries(m))) {
+        set_err(err, err_cap, "llamahip_eval_multi: %d logits rows in one pass (at most %d)", rp.n_logits(), (int) rows_idx_entries(m));
+        return LLAMAHIP_ERR_PREDICT;
+    }
     m->h_rows.assign(bytes, 0);
     RowTab *tab = (RowTab *) m->h_rows.data();
     int32_t *short_idx = (int32_t *) (m->h_rows.data() + cap * sizeof(RowTab)), *last_idx = short_idx + cap;
@@ -2310,7 +2322,11 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
         }
         tab[r] = { rp.pos[r], rp.keys[r], (long) slot * slot_stride };
         if (rp.n_tokens[i] <= rp.short_max) short_idx[ns++] = r;
-        if (r + 1 == rp.R || rp.seg[r + 1] != i) last_idx[i] = r;
+        if (rp.logit_rows.empty() && (r + 1 == rp.R || rp.seg[r + 1] != i)) last_idx[i] = r;
+    }
+    for (size_t k = 0; k < rp.logit_rows.size(); k++) {
+        if (rp.logit_rows[k] < 0 || rp.logit_rows[k] >= rp.R) { set_err(err, err_cap, "llamahip_eval_multi: logits row %d names row %d of %d", (int) k, rp.logit_rows[k], rp.R); return LLAMAHIP_ERR_PREDICT; }
+        last_idx[k] = rp.logit_rows[k];
     }
     HIP_TRY(hipMemcpyAsync(m->d_rows, m->h_rows.data(), bytes, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
     return 0;
@@ -2353,12 +2369,14 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
         HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, R, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
     }
     if (m->last_stage) {
-        // the segments' last rows side by side (x1 is free here), the final norm and the lm head over those n_seqs rows: logits rows 0 .. n_seqs - 1
-        HIP_TRY(launch_gather_rows(m->x, rd.last_idx, rp.n_seqs, d, m->x1, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, rp.n_seqs, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+        // the segments' last rows (a drafted scheduler step: its list of rows) side by side (x1 is free here), the final norm and the lm head over
+        // those nl rows: logits rows 0 .. nl - 1
+        const int nl = rp.n_logits();
+        HIP_TRY(launch_gather_rows(m->x, rd.last_idx, nl, d, m->x1, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, nl, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
         QMat out = m->output;
         out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr;          // (the decode tiles, as llamahip_eval's lm head)
-        HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, rp.n_seqs, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, nl, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
     }
     m->last_rows.clear();          // (m->logits rewritten)
     return 0;
@@ -2385,6 +2403,8 @@ static bool rows_pass_applies(llamahip_model *m) {
 static int rows_pass_build(RowsPass &rp, int n_ctx) {
     rp.pos.resize((size_t) rp.R); rp.keys.resize((size_t) rp.R); rp.seg.resize((size_t) rp.R);
     if (llamahip_eval_multi_rows(n_ctx, rp.n_seqs, rp.n_past, rp.n_tokens, rp.chunk, rp.seg.data(), rp.pos.data(), rp.keys.data()) != rp.R) return -1;
+    if (!rp.seg_single.empty())
+        for (int r = 0; r < rp.R; r++) if (rp.seg_single[(size_t) rp.seg[r]]) rp.keys[r] = rp.pos[r] + 1;
     for (int i = 0; i < rp.n_seqs; i++) {
         if (rp.n_tokens[i] > rp.short_max) { rp.n_long_segs++; continue; }
         rp.n_short_segs++; rp.n_short_rows += rp.n_tokens[i];
@@ -3713,9 +3733,18 @@ int llamahip_decode_sample_lookup_multi(llamahip_model *m, int32_t n_threads, in
 // token} and pushes them to every stage where the device cannot know them: after a (re)bind, and on a pipeline handle after a mixed pass
 // (k_sched_pick runs on the last stage only -- llamahip_decode_sample_lookup_multi keeps its stages in step the same way).
 // FALL-BACK, handles without the pass or without a set step: the contract's own per-slot calls, segment by segment.
+// A STEP WITH DRAFTED TOKENS (some decoding segment carries a draft; include/llamahip.h) is the mixed pass whether or not
+// anybody prefills: such a segment is [last token, draft ...], every row keyed as its own single-token eval, the lm head over every row of it
+// and the last row of every other emitting segment -- at most 16 logits rows.  Behind it k_verify_rows + k_sched_accept for the greedy
+// segments; for the sampled ones (still ordered first) the sliding-window candidate selection over their rows (slide_set_enqueue) and
+// llamahip_verify_sample_multi's host walk, after which the slots' words are the host's to push (stale).
 // ------------------------------------------------------------------------------------------------
 extern "C++" {
 namespace lh {
+// the last stage's d_sched_tab: k_sched_pick's table and result as before, behind them a drafted step's k_sched_accept table | the logits
+// rows' tokens | k_verify_rows' picks | the result {n_accept[16], pick[16]}
+constexpr int SCHED_ACC_TAB = 5 * SET_MAX, SCHED_ACC_TOK = SCHED_ACC_TAB + SCHED_TAB_W * SET_MAX, SCHED_ACC_PICK = SCHED_ACC_TOK + VERIFY_ROWS_MAX,
+              SCHED_ACC_RES = SCHED_ACC_PICK + VERIFY_ROWS_MAX, SCHED_TAB_WORDS = SCHED_ACC_RES + SET_MAX + VERIFY_ROWS_MAX;
 struct SchedDev {
     llamahip_model *m = nullptr;
     int n_threads = 1, max_active = 1, chunk = 0;
@@ -3724,7 +3753,7 @@ struct SchedDev {
     bool decided = false, fallback = false, stale = true;
     int32_t pos[SET_MAX] = { 0 }, cur[SET_MAX] = { 0 }, tok[SET_MAX] = { 0 };      // host mirrors of the slots' words
     std::vector<float> logits;
-    std::vector<int32_t> win;
+    std::vector<int32_t> win, pool;          // pool: the id streams of a drafted step's sampled segments
 };
 
 int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap) {
@@ -3747,6 +3776,18 @@ int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *o, SchedDev **ou
     m->sched = d;
     *out = d;
     return 0;
+}
+// llamahip_eval_multi's and the multi-sequence decoders' own conditions: the pass, a stage step to batch, set steps of every size
+static void sched_decide(SchedDev *d) {
+    if (d->decided) return;
+    const std::vector<llamahip_model *> stages = stages_of(d->m);
+    d->fallback = !rows_pass_applies(d->m) || !multi_stage_steps(stages[0]) || !vset_applies(stages, d->n_threads);
+    d->decided = true;
+}
+int sched_dev_drafts(SchedDev *d) {
+    if (!d || !d->m) return 0;
+    sched_decide(d);
+    return d->fallback ? 0 : 1;
 }
 // the handle is being freed under a live scheduler: the scheduler forgets it (no device memory is the scheduler's own)
 void sched_dev_orphan(SchedDev *d) { d->m = nullptr; }
@@ -3772,7 +3813,7 @@ static int sched_bind(SchedDev *d, const std::vector<llamahip_model *> &stages, 
     }
     if (!last->d_sched_tab) {
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(last->own.alloc(&last->d_sched_tab, (size_t) 5 * SET_MAX), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(last->own.alloc(&last->d_sched_tab, (size_t) SCHED_TAB_WORDS), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -3824,25 +3865,33 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
     if (n_segs < 1 || n_segs > SET_MAX) { set_err(err, err_cap, "%s: %d segments in a step (1 .. %d)", fn, n_segs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
     const int C = m->hp.n_ctx, V = m->hp.n_vocab;
     int64_t R = 0;
+    int n_logit_rows = 0;
+    bool drafted = false;
     for (int j = 0; j < n_segs; j++) {
         const SchedSeg &g = segs[j];
         if (g.slot < 0 || g.slot >= d->max_active || g.n_rows < 1 || g.pos < 0 || g.pos + g.n_rows > C || !g.tokens || (!mixed && (g.n_rows != 1 || !g.emit))) {
             set_err(err, err_cap, "%s: segment %d (slot %d, %d rows at %d) is outside the scheduler's slots or the context (n_ctx %d)", fn, j, g.slot, g.n_rows, g.pos, C);
             return LLAMAHIP_ERR_PREDICT;
         }
+        if (g.n_draft < 0 || g.n_draft > VERIFY_ROWS_MAX - 1 || (g.n_draft > 0 && (!g.draft || g.n_rows != 1 || !g.emit || g.pos + 1 + g.n_draft > C))) {
+            set_err(err, err_cap, "%s: segment %d (slot %d at %d) carries a draft of %d tokens (0 .. %d behind one decode row, inside n_ctx %d)", fn, j, g.slot, g.pos, g.n_draft, VERIFY_ROWS_MAX - 1, C);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        for (int i = 0; i < g.n_draft; i++)
+            if (g.draft[i] < 0 || g.draft[i] >= V) { set_err(err, err_cap, "%s: draft token id %d out of range [0, %d)", fn, g.draft[i], V); return LLAMAHIP_ERR_PREDICT; }
         for (int i = 0; i < j; i++) if (segs[i].slot == g.slot) { set_err(err, err_cap, "%s: slot %d has two segments in one step", fn, g.slot); return LLAMAHIP_ERR_PREDICT; }
-        R += g.n_rows;
+        R += g.n_rows + g.n_draft;
+        drafted = drafted || g.n_draft > 0;
+        n_logit_rows += g.emit ? 1 + g.n_draft : 0;
     }
+    if (drafted && n_logit_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: %d logits rows in a step with drafted tokens (at most %d)", fn, n_logit_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
     if (R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { set_err(err, err_cap, "%s: %lld rows in one step, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
     const std::vector<llamahip_model *> stages = stages_of(m);
     const int S = (int) stages.size();
     llamahip_model *first = stages[0], *last = stages[S - 1];
     const SampleParams sp = sample_params(m, d->repeat_penalty, d->top_k, d->top_p, d->temp);
-    if (!d->decided) {
-        // llamahip_eval_multi's and the multi-sequence decoders' own conditions: the pass, a stage step to batch, set steps of every size
-        d->fallback = !rows_pass_applies(m) || !multi_stage_steps(first) || !vset_applies(stages, d->n_threads);
-        d->decided = true;
-    }
+    sched_decide(d);
+    if (drafted && (d->fallback || !mixed)) { set_err(err, err_cap, "%s: a draft on a step or a handle that takes none", fn); return LLAMAHIP_ERR_PREDICT; }
     const double t0 = now_ms();
     if (d->fallback) {
         *kind = SCHED_STEP_FALLBACK;
@@ -3867,44 +3916,95 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
         const int ns = n_ord;
         for (int j = 0; j < n_segs; j++) if (!(segs[j].sampler && segs[j].emit)) order[n_ord++] = j;
         int32_t slots[SET_MAX], n_past[SET_MAX], n_tokens[SET_MAX], tab[4 * SET_MAX];
+        // a drafted step: k_sched_accept's table and the logits rows' tokens (one upload), each segment's first logits row, the sampled rows' id pool
+        int32_t acc[SCHED_TAB_W * SET_MAX + VERIFY_ROWS_MAX] = { 0 }, lrow0[SET_MAX] = { 0 }, *ltok = acc + SCHED_TAB_W * SET_MAX;
+        int nl = 0, ns_rows = 0;
         std::vector<int32_t> tokens;
         tokens.reserve((size_t) R);
+        RowsPass rp;
         for (int a = 0; a < n_segs; a++) {
             const SchedSeg &g = segs[order[a]];
-            slots[a] = g.slot; n_past[a] = g.pos; n_tokens[a] = g.n_rows;
+            slots[a] = g.slot; n_past[a] = g.pos; n_tokens[a] = g.n_rows + g.n_draft;
+            const int r0 = (int) tokens.size();
             tokens.insert(tokens.end(), g.tokens, g.tokens + g.n_rows);
+            tokens.insert(tokens.end(), g.draft, g.draft + g.n_draft);
             tab[4 * a] = g.emit && !g.sampler; tab[4 * a + 1] = g.slot; tab[4 * a + 2] = g.pos + g.n_rows; tab[4 * a + 3] = g.n_out + (g.emit ? 1 : 0);
-            if (a < ns) hl.n_last[a] = llamahip_sampler_window(g.sampler, hl.win + (size_t) a * 1024, 1024);          // (the streams are idle: every step is waited for)
+            if (!drafted) {
+                if (a < ns) hl.n_last[a] = llamahip_sampler_window(g.sampler, hl.win + (size_t) a * 1024, 1024);          // (the streams are idle: every step is waited for)
+                continue;
+            }
+            // every row of a segment with a draft has a logits row, the last row of every other emitting segment, none of the rest.  A sampled
+            // segment's words cannot be set by the device (the host draws): emit 0 with the words of a segment without a draft, the host's push follows
+            rp.seg_single.push_back(g.n_draft > 0);
+            lrow0[a] = nl;
+            int32_t *t = acc + SCHED_TAB_W * a;
+            t[0] = !g.emit || g.sampler ? 0 : g.n_draft > 0 ? 2 : 1; t[1] = g.slot; t[2] = g.pos; t[3] = g.n_out + (g.emit && g.sampler ? 1 : 0);
+            t[4] = nl; t[5] = n_tokens[a];
+            for (int r = g.n_draft > 0 ? r0 : r0 + g.n_rows - 1; g.emit && r < r0 + n_tokens[a]; r++) { ltok[nl++] = tokens[(size_t) r]; rp.logit_rows.push_back(r); }
+            if (a < ns) ns_rows = nl;
         }
-        RowsPass rp;
         rp.n_seqs = n_segs; rp.chunk = d->chunk; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens; rp.R = (int) R;
         if (rows_pass_build(rp, C) != 0) { set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT; }
+        // the sampled segments' id streams (drafted step): each segment slides inside its own -- its sampler's window, then its draft
+        TopkOut cand[VERIFY_ROWS_MAX];
+        bool seg_sel[SET_MAX] = { false };
+        SlideSetReq ss;
+        if (drafted && ns > 0) {
+            VsetReq rq;
+            llamahip_sampler *smp[SET_MAX];
+            rq.n_segs = ns; rq.n_rows = ns_rows;
+            for (int a = 0; a < ns; a++) { rq.seg_begin[a] = lrow0[a]; rq.slot[a] = slots[a]; rq.pos[a] = n_past[a]; smp[a] = segs[order[a]].sampler; }
+            rq.seg_begin[ns] = ns_rows;
+            memcpy(rq.rows, ltok, (size_t) ns_rows * 4);
+            d->pool.resize(SLIDE_SET_IDS);
+            slide_set_build(rq, smp, sp, d->pool.data(), cand, ss, seg_sel);
+        }
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(hipMemcpyAsync(last->d_sched_tab, tab, (size_t) n_segs * 16, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);      // (pageable: it has left `tab` when the call returns)
-        int32_t *d_res = last->h_io ? last->d_io->vset.res : last->d_sched_tab + 4 * SET_MAX;
+        // (pageable: the table has left the host array when the call returns)
+        if (!drafted) HIP_TRY(hipMemcpyAsync(last->d_sched_tab, tab, (size_t) n_segs * 16, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+        else HIP_TRY(hipMemcpyAsync(last->d_sched_tab + SCHED_ACC_TAB, acc, sizeof(acc), hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);
+        int32_t *d_res = last->h_io ? last->d_io->vset.res : last->d_sched_tab + (drafted ? SCHED_ACC_RES : 4 * SET_MAX);
         rc = rows_pass_enqueue(stages, d->n_threads, rp, tokens.data(), err, err_cap);
         if (rc == 0 && hipSetDevice(last->device) != hipSuccess) { set_err(err, err_cap, "%s: hipSetDevice failed", fn); rc = LLAMAHIP_ERR_PREDICT; }
-        if (rc == 0 && ns > 0) rc = sample_select(last, sp, 0, ns, err, err_cap);
-        if (rc == 0 && launch_sched_pick(last->logits, n_segs, V, last->d_sched_tab, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess) {
+        if (rc == 0 && ns > 0) rc = drafted ? slide_set_enqueue(last, ss, ns_rows, err, err_cap) : sample_select(last, sp, 0, ns, err, err_cap);
+        if (rc == 0 && !drafted && launch_sched_pick(last->logits, n_segs, V, last->d_sched_tab, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess) {
             set_err(err, err_cap, "%s: HIP error launching k_sched_pick", fn); rc = LLAMAHIP_ERR_PREDICT;
+        }
+        if (rc == 0 && drafted && (launch_verify_rows(last->logits, nl, V, last->d_sched_tab + SCHED_ACC_PICK, last->stream) != hipSuccess ||
+                                   launch_sched_accept(last->d_sched_tab + SCHED_ACC_PICK, last->d_sched_tab + SCHED_ACC_TOK, last->d_sched_tab + SCHED_ACC_TAB, n_segs, nl,
+                                                       last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess)) {
+            set_err(err, err_cap, "%s: HIP error launching k_verify_rows / k_sched_accept", fn); rc = LLAMAHIP_ERR_PREDICT;
         }
         if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        int32_t res[SET_MAX];
-        if (last->h_io) memcpy(res, last->h_io->vset.res, (size_t) n_segs * 4);
-        else HIP_TRY(hipMemcpy(res, d_res, (size_t) n_segs * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        int32_t res[SET_MAX + VERIFY_ROWS_MAX];
+        const size_t n_res = (size_t) n_segs + (drafted ? (size_t) nl : 0);
+        if (last->h_io) memcpy(res, last->h_io->vset.res, n_res * 4);
+        else HIP_TRY(hipMemcpy(res, d_res, n_res * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        if (drafted && ns > 0 && ss.k > 0 && (rc = slide_fetch(last, cand, ns_rows, err, err_cap)) != 0) return rc;
         for (int a = 0; a < n_segs; a++) {
             SchedSeg &g = segs[order[a]];
-            if (g.emit && !g.sampler) { g.token = res[a]; g.exact = 1; }
+            g.n_accept = 0;
+            if (drafted && g.emit && !g.sampler) {
+                g.n_accept = res[a];
+                if (g.n_accept < 0 || g.n_accept > g.n_draft) { set_err(err, err_cap, "%s: the device reported %d accepted of %d drafted tokens for slot %d", fn, g.n_accept, g.n_draft, g.slot); return LLAMAHIP_ERR_PREDICT; }
+                for (int i = 0; i <= g.n_accept; i++) { g.toks[i] = res[n_segs + lrow0[a] + i]; g.exacts[i] = 1; }
+                g.token = g.toks[0]; g.exact = 1;
+            } else if (drafted && g.emit) {
+                // llamahip_verify_sample_multi's walk: draw, accept, go on only while the draw is the draft's next token
+                if ((rc = sample_walk(m, last, lrow0[a], g.draft, g.n_draft, g.sampler, seg_sel[a], cand, sp, &g.n_accept, g.toks, g.exacts, d->logits, err, err_cap)) != 0) return rc;
+                g.token = g.toks[0]; g.exact = g.exacts[0];
+                if (g.n_draft > 0) d->stale = true;          // (the device could not know the draws: the words are the host's to push)
+            } else if (g.emit && !g.sampler) { g.token = res[a]; g.exact = 1; }
             else if (g.emit) {
                 const TopkOut &c = hl.out[a];
                 g.token = sample_draw(m, g.sampler, sp, sp.dev_sel && c.fl[0] == 1, c.sc, c.id, hl.spill + (size_t) a * V, &g.exact);
             }
-            d->pos[g.slot] = g.pos + g.n_rows; d->cur[g.slot] = g.n_out + (g.emit ? 1 : 0);
-            if (g.emit) d->tok[g.slot] = g.token;
+            d->pos[g.slot] = g.pos + (g.n_draft > 0 ? g.n_accept + 1 : g.n_rows); d->cur[g.slot] = g.n_out + (g.emit ? g.n_accept + 1 : 0);
+            if (g.emit) d->tok[g.slot] = g.n_draft > 0 ? g.toks[g.n_accept] : g.token;
             for (llamahip_model *st : stages) st->slots[g.slot].next_pos = d->pos[g.slot];
         }
-        if (S > 1) d->stale = true;          // (k_sched_pick set the last stage's words only)
+        if (S > 1) d->stale = true;          // (k_sched_pick / k_sched_accept set the last stage's words only)
         last->last_rows.clear();
         m->last_rows.clear();
         m->n_evals++;

@@ -335,5 +335,12 @@ hipError_t launch_accept_drafts(const int32_t *tokens, const int32_t *pick, int 
 // cursor} [slot][2], token logs [slot][log_cap] and next-token words [slot], advanced / appended / set per segment.
 hipError_t launch_accept_drafts_set(const int32_t *tokens, const int32_t *pick, const int32_t *seg_begin, const int32_t *seg_slot, int n_segs, int n_rows,
                                     int32_t *state, int32_t *log, int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st);
+// a scheduler's step with drafted tokens (k_sched_accept, one wave per segment, behind launch_verify_rows over the step's n_rows logits rows):
+// tab[s] = {emit, slot, base position, base cursor, first logits row, row count} (SCHED_TAB_W words; emit 0 / 1 / 2: llamahip_op_sched_accept),
+// tokens[r] = the token logits row r evaluated; res = {n_accept[n_segs], pick[n_rows]}.  state / log / next_tok (all or none): the slot's words.
+// The caller has checked that every emitting segment's logits rows lie in [0, n_rows) and every slot inside state / log / next_tok.
+constexpr int SCHED_TAB_W = 6;
+hipError_t launch_sched_accept(const int32_t *pick, const int32_t *tokens, const int32_t *tab, int n_segs, int n_rows, int32_t *state, int32_t *log,
+                               int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st);
 
 }  // namespace lh

@@ -574,6 +574,54 @@ int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab,
     return LLAMAHIP_OK;
 }
 
+// k_verify_rows + k_sched_accept on caller-supplied rows and a caller's segment table, with or without slot words (parity tests): see the
+// request scheduler's "drafted tokens" in llamahip.h
+int llamahip_op_sched_accept(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *seg_tab, int32_t n_segs, const int32_t *tokens,
+                             int32_t n_slots, int32_t log_cap, int32_t *state, int32_t *log, int32_t *next_tok,
+                             int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_sched_accept";
+    if (!logits || !seg_tab || !tokens || !n_accept || !picks || n_vocab < 1) { set_err(err, err_cap, "%s: bad arguments (null pointer or n_vocab %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: n_rows must be 1 .. %d (got %d): a step has at most %d logits rows", fn, VERIFY_ROWS_MAX, n_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_segs < 1 || n_segs > SET_MAX) { set_err(err, err_cap, "%s: n_segs must be 1 .. %d (got %d)", fn, SET_MAX, n_segs); return LLAMAHIP_ERR_PREDICT; }
+    const bool words = state || log || next_tok;
+    if (words && (!state || !log || !next_tok)) { set_err(err, err_cap, "%s: the slot words state, log and next_tok come all three or not at all", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (words && (n_slots < 1 || n_slots > 4096 || log_cap < 1 || log_cap > 1 << 20)) { set_err(err, err_cap, "%s: n_slots (%d) outside 1 .. 4096 or log_cap (%d) outside 1 .. 2^20", fn, n_slots, log_cap); return LLAMAHIP_ERR_PREDICT; }
+    int next_row = 0;
+    for (int s = 0; s < n_segs; s++) {
+        const int32_t *t = seg_tab + SCHED_TAB_W * s;
+        const int emit = t[0], slot = t[1], rows = t[5], N = emit == 2 ? rows : emit == 1 ? 1 : 0;
+        if (emit < 0 || emit > 2) { set_err(err, err_cap, "%s: segment %d: emit %d outside 0 .. 2", fn, s, emit); return LLAMAHIP_ERR_PREDICT; }
+        if (rows < 1 || (emit == 2 && rows > VERIFY_ROWS_MAX)) { set_err(err, err_cap, "%s: segment %d: row count %d (>= 1; at most %d where every row has a logits row)", fn, s, rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+        if (t[2] < 0 || t[3] < 0 || t[2] > INT32_MAX - rows || t[3] > INT32_MAX - VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: segment %d: base position %d / base cursor %d out of range", fn, s, t[2], t[3]); return LLAMAHIP_ERR_PREDICT; }
+        if (N > 0 && (t[4] != next_row || next_row + N > n_rows)) {
+            set_err(err, err_cap, "%s: segment %d: logits rows [%d, %d + %d) -- the emitting segments' rows must tile [0, n_rows = %d) in segment order", fn, s, t[4], t[4], N, n_rows);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        next_row += N;
+        if (!words) continue;
+        if (slot < 0 || slot >= n_slots) { set_err(err, err_cap, "%s: segment %d: slot %d out of range [0, n_slots = %d)", fn, s, slot, n_slots); return LLAMAHIP_ERR_PREDICT; }
+        for (int q = 0; q < s; q++) if (seg_tab[SCHED_TAB_W * q + 1] == slot) { set_err(err, err_cap, "%s: slot %d has two segments (%d and %d): one segment per slot", fn, slot, q, s); return LLAMAHIP_ERR_PREDICT; }
+    }
+    if (next_row != n_rows) { set_err(err, err_cap, "%s: the segments name %d logits rows, n_rows is %d", fn, next_row, n_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, S = (size_t) n_segs, NS = words ? (size_t) n_slots : 0;
+    int32_t h[SET_MAX + VERIFY_ROWS_MAX] = { 0 };
+    Scratch s;
+    float *d_l = s.alloc(N * (size_t) n_vocab, logits);
+    int32_t *d_tab = s.alloc<int32_t>(SCHED_TAB_W * S, seg_tab), *d_tok = s.alloc<int32_t>(N, tokens), *d_pick = s.alloc<int32_t>(N), *d_res = s.alloc<int32_t>(N + S);
+    // (the slot words go up and come back whole: what the launch does not write keeps the caller's bits)
+    int32_t *d_state = words ? s.alloc<int32_t>(2 * NS, state) : nullptr, *d_log = words ? s.alloc<int32_t>(NS * (size_t) log_cap, log) : nullptr;
+    int32_t *d_next = words ? s.alloc<int32_t>(NS, next_tok) : nullptr;
+    if (s.ok()) s.check(launch_verify_rows(d_l, n_rows, n_vocab, d_pick, nullptr));
+    if (s.ok()) s.check(launch_sched_accept(d_pick, d_tok, d_tab, n_segs, n_rows, d_state, d_log, log_cap, d_next, d_res, nullptr));
+    if (s.ok()) s.download(h, d_res, (N + S) * 4);
+    if (s.ok() && words) { s.download(state, d_state, 2 * NS * 4); s.download(log, d_log, NS * (size_t) log_cap * 4); s.download(next_tok, d_next, NS * 4); }
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    memcpy(n_accept, h, S * 4);
+    memcpy(picks, h + S, N * 4);
+    return LLAMAHIP_OK;
+}
+
 // k_verify_rows + k_accept_drafts_set on caller-supplied rows cut into segments (parity tests): see llamahip_verify_greedy_multi
 int llamahip_op_verify_rows_set(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *tokens, const int32_t *seg_begin, int32_t n_segs,
                                 int32_t *n_accept, int32_t *picks, char *err, size_t err_cap) {

@@ -1,5 +1,6 @@
 // sched.cpp -- the host half of the request scheduler (include/llamahip.h "request scheduler"): the step rule
-// (llamahip_sched_plan), the queue, the slots, what llamahip_sched_new / _submit / _step refuse, and the events of a step.  What a planned
+// (llamahip_sched_plan), the draft policy (llamahip_sched_plan_drafts: what rides in the rows a step leaves spare), the queue, the slots, what
+// llamahip_sched_new / _submit / _step refuse, and the events of a step.  What a planned
 // step runs on the handle is the device half's business (sched.h, llamahip.cpp).  Pure host code, no device, no HIP header:
 // tools/host_sanitize compiles this file as it is and runs it under ASan + UBSan against a stubbed device half.
 #include <stdint.h>
@@ -17,6 +18,7 @@ namespace {
 struct Req {
     int64_t id = 0;
     std::vector<int32_t> prompt;
+    std::vector<int32_t> hist;    // a drafting scheduler only: the prompt, then everything produced (the drafter's history)
     int32_t n_predict = 0, stop_token = -1;
     llamahip_sampler *sampler = nullptr;
     int32_t off = 0;              // prompt tokens evaluated
@@ -32,6 +34,7 @@ struct llamahip_sched {
     llamahip_model *m = nullptr;
     lh::SchedDev *dev = nullptr;
     llamahip_sched_opts o = {};
+    std::vector<int32_t> corpus;          // the caller's, copied (o.corpus points here)
     lh::SchedHandleInfo hi = {};
     int64_t next_id = 1;
     std::deque<Req> queue;
@@ -72,6 +75,28 @@ extern "C" int32_t llamahip_sched_plan(int32_t n_active, const int32_t *prompt_l
     return (int32_t) std::min<int64_t>(total, INT32_MAX);
 }
 
+extern "C" int32_t llamahip_sched_plan_drafts(int32_t n_active, const int32_t *prompt_left, const int32_t *rows, const int32_t *want, int32_t *give) {
+    if (n_active < 0 || n_active > 16 || (n_active > 0 && (!prompt_left || !rows || !want || !give))) return -1;
+    int32_t dec_want[16], dec_give[16], dec_at[16], n_dec = 0, emitting = 0;
+    int64_t total = 0;
+    for (int32_t i = 0; i < n_active; i++) {
+        if (prompt_left[i] < 0 || rows[i] < 0 || want[i] < 0 || want[i] > 15 || (prompt_left[i] > 0 && (want[i] != 0 || rows[i] > prompt_left[i])) ||
+            (prompt_left[i] == 0 && rows[i] != 1))
+            return -1;
+        give[i] = 0;
+        total += rows[i];
+        if (prompt_left[i] == 0) { dec_want[n_dec] = want[i]; dec_at[n_dec++] = i; emitting++; }
+        else if (rows[i] == prompt_left[i]) emitting++;
+    }
+    const int64_t spare = std::min<int64_t>(16 - emitting, LLAMAHIP_EVAL_MULTI_MAX_ROWS - total);
+    if (n_dec == 0 || spare < 1) return 0;
+    // (the dealing rule, not restated: every decoding sequence has its base row, the spare rows go round-robin in admission order)
+    const int32_t dealt = llamahip_lookup_deal_rows(dec_want, n_dec, n_dec + (int32_t) spare, dec_give);
+    if (dealt < 0) return -1;
+    for (int32_t k = 0; k < n_dec; k++) give[dec_at[k]] = dec_give[k];
+    return dealt;
+}
+
 extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap) {
     static const char *fn = "llamahip_sched_new";
     if (out) *out = nullptr;
@@ -84,6 +109,16 @@ extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *
     if (op.row_budget < 0 || op.row_budget > LLAMAHIP_EVAL_MULTI_MAX_ROWS - 16)
         return refuse(err, err_cap, "llamahip_sched_new: row_budget (%ld) outside 0 .. LLAMAHIP_EVAL_MULTI_MAX_ROWS - 16 (%ld)", op.row_budget, LLAMAHIP_EVAL_MULTI_MAX_ROWS - 16);
     if (op.row_budget == 0) op.row_budget = LLAMAHIP_SCHED_ROW_BUDGET;
+    if (op.draft_len < 0 || op.draft_len > 15) return refuse(err, err_cap, "llamahip_sched_new: draft_len (%ld) outside 0 .. 15 (0 = no drafting)", op.draft_len);
+    {
+        const int32_t mn = op.ngram_min ? op.ngram_min : LLAMAHIP_LOOKUP_NGRAM_MIN, mx = op.ngram_max ? op.ngram_max : LLAMAHIP_LOOKUP_NGRAM_MAX;
+        if (op.ngram_min < 0 || op.ngram_max < 0 || mx < mn)          // (what llamahip_lookup_draft refuses)
+            return refuse(err, err_cap, "llamahip_sched_new: ngram_min (%ld) / ngram_max (%ld) must be >= 0 (0 = LLAMAHIP_LOOKUP_NGRAM_MIN / _MAX) with ngram_max >= ngram_min", op.ngram_min, op.ngram_max);
+    }
+    if (op.n_corpus < 0 || (op.n_corpus > 0 && !op.corpus)) return refuse(err, err_cap, "llamahip_sched_new: n_corpus (%ld) must be >= 0, with a corpus where it is > 0", op.n_corpus);
+    if (const int32_t V = llamahip_n_vocab(m))          // (a null handle is refused below)
+        for (int32_t i = 0; i < op.n_corpus; i++)
+            if (op.corpus[i] < 0 || op.corpus[i] >= V) return refuse(err, err_cap, "llamahip_sched_new: corpus token id %ld at %ld out of range [0, %ld)", op.corpus[i], i, V);
     if (op.top_k == 0 && op.repeat_penalty == 0.0 && op.top_p == 0.0 && op.temp == 0.0) { op.repeat_penalty = 1.3; op.top_p = (double) 0.95f; op.temp = (double) 0.8f; op.top_k = 40; }      // (the reference's float defaults)
     int rc = lh::sched_sampler_check(op.repeat_penalty, op.top_k, op.top_p, op.temp, err, err_cap);
     if (rc) return rc;
@@ -94,6 +129,8 @@ extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *
     if ((rc = lh::sched_dev_new(m, &op, &dev, err, err_cap)) != 0) return rc;          // (the handle already has a scheduler)
     llamahip_sched *s = new llamahip_sched();
     s->m = m; s->o = op; s->hi = hi; s->dev = dev;
+    if (op.n_corpus > 0) s->corpus.assign(op.corpus, op.corpus + op.n_corpus);
+    s->o.corpus = s->corpus.data();
     s->slot.resize((size_t) op.max_active);
     s->st.struct_size = (int32_t) sizeof(s->st);
     *out = s;
@@ -131,6 +168,7 @@ extern "C" int llamahip_sched_submit(llamahip_sched *s, const llamahip_request *
     Req q;
     q.id = s->next_id++;
     q.prompt.assign(r->prompt, r->prompt + r->n_prompt);
+    if (s->o.draft_len > 0) q.hist = q.prompt;
     q.n_predict = r->n_predict; q.stop_token = r->stop_token; q.sampler = r->sampler;
     s->queue.push_back(std::move(q));
     s->st.n_submitted++;
@@ -169,7 +207,10 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     if (n_ev) *n_ev = 0;
     if (!s || !ev || !n_ev) { if (err && err_cap) snprintf(err, err_cap, "%s: null scheduler, events or n_ev", fn); return LLAMAHIP_ERR_PREDICT; }
     const int32_t A = s->o.max_active;
-    if (cap < 2 * A + 1) return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least 2 * max_active + 1 (%ld) events", cap, 2 * A + 1);
+    if (s->o.draft_len == 0 && cap < 2 * A + 1) return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least 2 * max_active + 1 (%ld) events", cap, 2 * A + 1);
+    if (cap < LLAMAHIP_SCHED_EVENT_CAP(A, s->o.draft_len))
+        return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least max_active + 17 (%ld) events with draft_len > 0 (LLAMAHIP_SCHED_EVENT_CAP)", cap, A + 17);
+    const int32_t own_events = LLAMAHIP_SCHED_EVENT_CAP(A, s->o.draft_len) - 1;          // what the step's own TOKEN and DONE events may take
     // 1. cancelled active requests leave their slots; then as many waiting DONE events as the step's own events leave room for
     for (size_t k = 0; k < s->order.size();) {
         Req &q = s->slot[(size_t) s->order[k]];
@@ -181,7 +222,7 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     // (the waiting DONE events are handed over only by a step that succeeds: a step that fails delivers nothing and loses nothing)
     int32_t n = 0;
     auto deliver_pending = [&]() {
-        const size_t room = (size_t) (cap - 2 * A), take = std::min(room, s->pend.size());
+        const size_t room = (size_t) (cap - own_events), take = std::min(room, s->pend.size());
         for (size_t k = 0; k < take; k++) { ev[n++] = s->pend[k]; s->st.n_done++; }
         s->pend.erase(s->pend.begin(), s->pend.begin() + (long) take);
     };
@@ -200,6 +241,27 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     for (int32_t k = 0; k < na; k++) left[k] = s->slot[(size_t) s->order[(size_t) k]].left();
     const int32_t total = llamahip_sched_plan(na, left, s->o.chunk_tokens, s->o.row_budget, rows);
     if (total < 1) return refuse(err, err_cap, "llamahip_sched_step: the step rule gave %ld rows for %ld active requests", total, na);
+    // 3b. drafted tokens in the rows the step leaves spare: what every decoding request could use, then the one policy
+    int32_t want[16] = { 0 }, give[16] = { 0 }, draft_rows = 0;
+    int32_t drafts[16][15];
+    if (s->o.draft_len > 0 && lh::sched_dev_drafts(s->dev)) {
+        bool any = false;
+        for (int32_t k = 0; k < na; k++) {
+            Req &q = s->slot[(size_t) s->order[(size_t) k]];
+            if (left[k] > 0 || q.n_out < 1) continue;
+            int32_t room = std::min(s->o.draft_len, q.n_predict - q.n_out - 1);          // a verify step never passes n_predict (and so never n_ctx)
+            if (room < 1) continue;
+            if (q.sampler && (s->o.top_k > 64 || s->hi.n_vocab > 32768 || llamahip_sampler_window(q.sampler, nullptr, 0) > 1024)) continue;      // (no candidates on the device)
+            int32_t n = llamahip_lookup_draft(q.hist.data(), (int32_t) q.hist.size(), s->corpus.data(), (int32_t) s->corpus.size(), room, s->o.ngram_min, s->o.ngram_max, drafts[k]);
+            // a sampled request draws nothing behind its stop token (the draws are accepted into its sampler as they are made): its draft
+            // ends before one.  A greedy request's accepted tokens behind a stop token are dropped below
+            for (int32_t j = 0; q.sampler && j < n; j++) if (q.stop_token >= 0 && drafts[k][j] == q.stop_token) n = j;
+            want[k] = std::max(n, 0);
+            any = any || want[k] > 0;
+        }
+        if (any && (draft_rows = llamahip_sched_plan_drafts(na, left, rows, want, give)) < 0)
+            return refuse(err, err_cap, "llamahip_sched_step: the draft policy refused the step of %ld active requests", na);
+    }
     lh::SchedSeg segs[16];
     int32_t seg_k[16], n_segs = 0, prompt_rows = 0;
     for (int32_t k = 0; k < na; k++) {
@@ -212,19 +274,29 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         if (left[k] > 0) {
             g.pos = q.off; g.tokens = q.prompt.data() + q.off; g.emit = rows[k] == left[k] ? 1 : 0;
             mixed = true; prompt_rows += rows[k];
-        } else { g.pos = (int32_t) q.prompt.size() + q.n_out - 1; g.tokens = &q.last; g.emit = 1; }
+        } else {
+            g.pos = (int32_t) q.prompt.size() + q.n_out - 1; g.tokens = &q.last; g.emit = 1;
+            if (give[k] > 0) { g.draft = drafts[k]; g.n_draft = give[k]; mixed = true; }
+        }
         seg_k[n_segs++] = k;
     }
     int32_t kind = -1, captures = 0;
     const int rc = lh::sched_dev_step(s->dev, segs, n_segs, mixed, &kind, &captures, err, err_cap);
     if (rc) return rc;          // (requests admitted by this step keep their slots: the next step plans the same rows again)
-    for (int32_t j = 0; j < n_segs; j++)
-        if (segs[j].emit && (segs[j].token < 0 || segs[j].token >= s->hi.n_vocab))
-            return refuse(err, err_cap, "llamahip_sched_step: the device half reported token %ld for slot %ld", segs[j].token, segs[j].slot);
+    for (int32_t j = 0; j < n_segs; j++) {
+        lh::SchedSeg &g = segs[j];
+        if (!g.emit) continue;
+        if (g.n_draft == 0) { g.n_accept = 0; g.toks[0] = g.token; g.exacts[0] = g.exact; }
+        if (g.n_accept < 0 || g.n_accept > g.n_draft) return refuse(err, err_cap, "llamahip_sched_step: the device half reported %ld accepted of %ld drafted tokens for slot %ld", g.n_accept, g.n_draft, g.slot);
+        for (int32_t a = 0; a <= g.n_accept; a++)
+            if (g.toks[a] < 0 || g.toks[a] >= s->hi.n_vocab || (a < g.n_accept && g.toks[a] != g.draft[a]))
+                return refuse(err, err_cap, "llamahip_sched_step: the device half reported token %ld for slot %ld", g.toks[a], g.slot);
+    }
     deliver_pending();
     s->st.n_steps++;
     (kind == lh::SCHED_STEP_MIXED ? s->st.n_mixed_steps : kind == lh::SCHED_STEP_SET ? s->st.n_set_steps : kind == lh::SCHED_STEP_SINGLE ? s->st.n_single_steps : s->st.n_fallback_steps)++;
-    s->st.n_rows += total; s->st.n_prompt_rows += prompt_rows; s->st.n_graph_captures += captures;
+    s->st.n_rows += total + draft_rows; s->st.n_prompt_rows += prompt_rows; s->st.n_graph_captures += captures;
+    if (draft_rows > 0) { s->st.n_draft_steps++; s->st.n_drafted += draft_rows; }
     // 4. the step's events; a request that produced its last token frees its slot (reused from the next step)
     bool freed[16] = { false };
     for (int32_t j = 0; j < n_segs; j++) {
@@ -232,15 +304,23 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         Req &q = s->slot[(size_t) g.slot];
         if (left[seg_k[j]] > 0) q.off += g.n_rows;
         if (!g.emit) continue;
-        q.last = g.token; q.n_out++;
-        s->st.n_tokens++;
-        const int32_t ctx = (int32_t) q.prompt.size() + q.n_out - 1;          // the KV rows the slot holds; the position g.token would be evaluated at
-        ev[n++] = { q.id, LLAMAHIP_EV_TOKEN, g.token, g.exact, g.slot, ctx, 0 };
-        const bool stop = q.stop_token >= 0 && g.token == q.stop_token;
-        if (stop || q.n_out >= q.n_predict) {
-            ev[n++] = { q.id, LLAMAHIP_EV_DONE, -1, 0, g.slot, ctx, stop ? LLAMAHIP_DONE_STOP : LLAMAHIP_DONE_LENGTH };
-            s->st.n_done++;
-            freed[seg_k[j]] = true;
+        s->st.n_emit_segs++;
+        s->st.n_accepted += g.n_accept;
+        // the segment's n_accept + 1 tokens in order, cut at the stop token (what was accepted behind it is dropped) or at n_predict
+        for (int32_t a = 0; a <= g.n_accept; a++) {
+            q.last = g.toks[a]; q.n_out++;
+            if (s->o.draft_len > 0) q.hist.push_back(q.last);
+            s->st.n_tokens++;
+            const int32_t ctx = (int32_t) q.prompt.size() + q.n_out - 1;          // the KV rows the slot holds; the position the token would be evaluated at
+            ev[n++] = { q.id, LLAMAHIP_EV_TOKEN, q.last, g.exacts[a], g.slot, ctx, 0 };
+            const bool stop = q.stop_token >= 0 && q.last == q.stop_token;
+            if (stop || q.n_out >= q.n_predict) {
+                ev[n++] = { q.id, LLAMAHIP_EV_DONE, -1, 0, g.slot, ctx, stop ? LLAMAHIP_DONE_STOP : LLAMAHIP_DONE_LENGTH };
+                s->st.n_done++;
+                s->st.n_dropped += g.n_accept - a;
+                freed[seg_k[j]] = true;
+                break;
+            }
         }
     }
     for (int32_t k = na - 1; k >= 0; k--)

@@ -1,6 +1,6 @@
 // sched.h -- the seam between the request scheduler's host half (sched.cpp: queue, slots, the step rule, events) and its device half
 // (llamahip.cpp: what a planned step runs on the handle).  Plain C++ types only, no HIP header: sched.cpp is compiled as it is into
-// tools/host_sanitize, where the four functions below are stubs.
+// tools/host_sanitize, where the functions below are stubs.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -21,11 +21,19 @@ int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, doub
 // one row [its last token].  emit: the segment's last row produces a token (a decode row, a piece that ends its prompt) -- the device half
 // fills token / exact: the greedy pick (sampler == null) or the sampler's draw, already accepted into it.
 // n_out: the tokens the request has produced before this step (the slot's trace cursor).
+// draft / n_draft (a decoding sequence's segment only: n_rows == 1, emit): the drafted tokens that ride behind its one row -- the pass
+// evaluates [tokens[0], draft ...] at pos, 1 + n_draft rows.  The device half fills n_accept (how many leading draft tokens the model
+// reproduced, 0 .. n_draft) and toks / exacts [0 .. n_accept]: the tokens the segment produced -- picks, or draws already accepted into the
+// sampler; token / exact = the first of them.  A segment without a draft gets token / exact only, as before.
+constexpr int SCHED_SEG_TOKS = 16;
 struct SchedSeg {
     int32_t slot, pos, n_rows, emit, n_out;
     const int32_t *tokens;
     llamahip_sampler *sampler;
     int32_t token, exact;
+    const int32_t *draft;
+    int32_t n_draft, n_accept;
+    int32_t toks[SCHED_SEG_TOKS], exacts[SCHED_SEG_TOKS];
 };
 enum { SCHED_STEP_MIXED = 0, SCHED_STEP_SET = 1, SCHED_STEP_SINGLE = 2, SCHED_STEP_FALLBACK = 3 };
 
@@ -33,7 +41,9 @@ enum { SCHED_STEP_MIXED = 0, SCHED_STEP_SET = 1, SCHED_STEP_SINGLE = 2, SCHED_ST
 // scheduler orphans it: every later step fails, sched_dev_free never touches the handle
 int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *o, SchedDev **out, char *err, size_t err_cap);
 void sched_dev_free(SchedDev *d);
-// one weight pass over the segments (mixed: some segment is a prompt piece; else every segment is one decode row).  *kind: SCHED_STEP_*;
+// the handle takes drafted tokens in a step (it has the one pass and set steps: not a fall-back handle); 0 for a freed handle.  No device work
+int sched_dev_drafts(SchedDev *d);
+// one weight pass over the segments (mixed: some segment is a prompt piece or carries a draft; else every segment is one decode row).  *kind: SCHED_STEP_*;
 // *captures: set-step graphs captured by this step.  Nothing of the host half's state is read: the segments say everything.
 int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap);
 

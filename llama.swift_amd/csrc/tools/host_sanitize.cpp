@@ -96,9 +96,11 @@ int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size
 
 // the request scheduler's device half (sched.h), stubbed: every planned step is logged segment by segment, exactly sized copies of what the host
 // half handed over (so that a read past a request's tokens is the sanitizer's to see), and answered with made-up tokens
-struct SchedCall { bool mixed; std::vector<lh::SchedSeg> segs; std::vector<std::vector<int32_t>> toks; };
+struct SchedCall { bool mixed; std::vector<lh::SchedSeg> segs; std::vector<std::vector<int32_t>> toks, drafts; };
 static std::vector<SchedCall> g_sched_calls;
 static bool g_sched_fail = false;          // the next steps fail like a device error: nothing of the host half's state may be lost
+static bool g_sched_drafts = true;         // the stubbed handle takes drafted tokens (false: a fall-back handle)
+static int g_sched_accept = -1;            // the script: draft tokens a segment accepts (cut to its draft); -1: (position + slot) % (n_draft + 1)
 namespace lh {
 struct SchedDev { int V; llamahip_model *m; };
 int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap) {
@@ -117,14 +119,28 @@ int sched_dev_new(llamahip_model *m, const llamahip_sched_opts *, SchedDev **out
     return 0;
 }
 void sched_dev_free(SchedDev *d) { if (d) d->m->sched = nullptr; delete d; }
+int sched_dev_drafts(SchedDev *d) { return d && g_sched_drafts ? 1 : 0; }
+static int32_t sched_made_up(const SchedDev *d, int32_t tok, int32_t pos) { return (int32_t) (((uint32_t) tok * 31u + (uint32_t) pos * 7u + 3u) % (uint32_t) d->V); }
 int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap) {
     if (g_sched_fail) { snprintf(err, err_cap, "llamahip_sched_step: made-up device error"); return LLAMAHIP_ERR_PREDICT; }
     SchedCall c;
     c.mixed = mixed;
     for (int j = 0; j < n_segs; j++) {
         c.toks.emplace_back(segs[j].tokens, segs[j].tokens + segs[j].n_rows);
-        if (segs[j].emit) {
-            segs[j].token = (int32_t) (((uint32_t) c.toks.back().back() * 31u + (uint32_t) (segs[j].pos + segs[j].n_rows) * 7u + 3u) % (uint32_t) d->V);
+        c.drafts.emplace_back(segs[j].draft, segs[j].draft + segs[j].n_draft);          // (exactly sized, as the rows' tokens)
+        if (segs[j].n_draft > 0) {
+            // the scripted number of draft tokens accepted, then a made-up token that is not the draft's next one
+            SchedSeg &g = segs[j];
+            if (!mixed || !g.emit || g.n_rows != 1 || g.n_draft > 15) { snprintf(err, err_cap, "llamahip_sched_step: a draft where none belongs"); return LLAMAHIP_ERR_PREDICT; }
+            g.n_accept = std::min(g.n_draft, g_sched_accept >= 0 ? g_sched_accept : (g.pos + g.slot) % (g.n_draft + 1));
+            for (int a = 0; a < g.n_accept; a++) g.toks[a] = c.drafts.back()[(size_t) a];
+            int32_t t = sched_made_up(d, g.n_accept ? g.toks[g.n_accept - 1] : c.toks.back()[0], g.pos + g.n_accept + 1);
+            if (g.n_accept < g.n_draft && t == c.drafts.back()[(size_t) g.n_accept]) t = (t + 1) % d->V;
+            g.toks[g.n_accept] = t;
+            for (int a = 0; a <= g.n_accept; a++) { g.exacts[a] = 1; if (g.sampler) llamahip_sampler_accept(g.sampler, g.toks[a]); }
+            g.token = g.toks[0]; g.exact = 1;
+        } else if (segs[j].emit) {
+            segs[j].token = sched_made_up(d, c.toks.back().back(), segs[j].pos + segs[j].n_rows);
             segs[j].exact = 1;
             if (segs[j].sampler) llamahip_sampler_accept(segs[j].sampler, segs[j].token);
         }
@@ -588,6 +604,156 @@ int main(int argc, char **argv) {
                     llamahip_sched_free(sc);
                     for (Want &w : reqs) if (w.smp) llamahip_sampler_free(w.smp);
                 }
+        // drafted tokens (draft_len > 0) against the stub's scripted accepts: every step's segments against the policy (llamahip_sched_plan_drafts
+        // on the requests' own state), the drafts against llamahip_lookup_draft on the model's history, the events against what the stub
+        // reported -- in order, at consecutive positions, cut at the stop token and at n_predict -- on an event array of exactly the smallest cap
+        int64_t dropped_in_all = 0;
+        for (int script : { -1, 0, 15 })
+            for (int draft_len : { 1, 4, 15 })
+                for (int max_active : { 1, 3, 4 }) {
+                    if (!ms) break;
+                    g_sched_accept = script;
+                    std::vector<int32_t> corpus(40);          // exactly sized: copied at llamahip_sched_new
+                    for (size_t i = 0; i < corpus.size(); i++) corpus[i] = (int32_t) ((i * 5 + 1) % (size_t) V);
+                    llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                    so.struct_size = sizeof(so); so.n_threads = 2; so.max_active = max_active; so.chunk_tokens = 4; so.row_budget = 8;
+                    so.draft_len = draft_len; so.corpus = corpus.data(); so.n_corpus = (int32_t) corpus.size();
+                    llamahip_sched *sc = nullptr;
+                    EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                    if (!sc) continue;
+                    std::fill(corpus.begin(), corpus.end(), -5);          // (the scheduler has its own copy)
+                    struct DReq { std::vector<int32_t> hist; size_t n_prompt; int n_predict, stop; llamahip_sampler *smp; int n_out = 0, done = 0; };
+                    std::vector<DReq> reqs;
+                    static const int plens[6] = { 2, 5, 9, 12, 3, 7 }, npred[6] = { 30, 12, 1, 20, 36, 2 };
+                    for (int i = 0; i < 6; i++) {
+                        DReq w;
+                        w.hist.resize((size_t) plens[i]);
+                        for (size_t k = 0; k < w.hist.size(); k++) w.hist[k] = (int32_t) ((k % 3 * 5 + 1 + (size_t) i) % (size_t) V);      // a repeated 3-gram: the history drafter fires
+                        w.n_prompt = w.hist.size(); w.n_predict = npred[i]; w.stop = i == 4 ? 6 : i == 0 ? 7 : i == 3 ? 11 : -1; w.smp = i % 3 == 1 ? llamahip_sampler_new(i, 8) : nullptr;
+                        reqs.push_back(w);
+                        llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                        rq.struct_size = sizeof(rq); rq.prompt = reqs.back().hist.data(); rq.n_prompt = plens[i]; rq.n_predict = npred[i]; rq.stop_token = w.stop; rq.sampler = w.smp;
+                        int64_t id = 0;
+                        EXPECT(llamahip_sched_submit(sc, &rq, &id, err, sizeof(err)) == 0 && id == (int64_t) i + 1);
+                    }
+                    {
+                        std::vector<llamahip_sched_event> small((size_t) max_active + 16);
+                        int32_t ne = -1;
+                        EXPECT(llamahip_sched_step(sc, small.data(), (int32_t) small.size(), &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0 && strstr(err, "max_active + 17"));
+                        EXPECT(llamahip_sched_pending(sc) == 6);
+                    }
+                    std::vector<llamahip_sched_event> evs((size_t) LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len));          // exactly the smallest cap
+                    EXPECT(evs.size() == (size_t) max_active + 17);
+                    g_sched_calls.clear();
+                    int steps = 0;
+                    int64_t emit_segs = 0, accepted = 0, drafted = 0, dropped = 0, tokens = 0, draft_steps = 0;
+                    while (llamahip_sched_pending(sc) > 0 && steps < 600) {
+                        int32_t ne = 0;
+                        const size_t call0 = g_sched_calls.size();
+                        EXPECT(llamahip_sched_step(sc, evs.data(), (int32_t) evs.size(), &ne, err, sizeof(err)) == 0 && ne <= (int32_t) evs.size());
+                        steps++;
+                        EXPECT(g_sched_calls.size() == call0 + 1);
+                        if (g_sched_calls.size() != call0 + 1) break;
+                        const SchedCall &cl = g_sched_calls.back();
+                        int logit_rows = 0, step_drafted = 0;
+                        int32_t e = 0;
+                        for (size_t j = 0; j < cl.segs.size(); j++) {
+                            const lh::SchedSeg &g = cl.segs[j];
+                            EXPECT(g.n_draft >= 0 && g.n_draft <= draft_len && (g.n_draft == 0 || (g.emit && g.n_rows == 1)));
+                            logit_rows += g.emit ? 1 + g.n_draft : 0;
+                            step_drafted += g.n_draft;
+                            if (!g.emit) continue;
+                            // whose segment: the request in that slot is the one the segment's events name
+                            EXPECT(e < ne && evs[(size_t) e].kind == LLAMAHIP_EV_TOKEN && evs[(size_t) e].slot == g.slot);
+                            if (e >= ne) break;
+                            DReq &w = reqs[(size_t) (evs[(size_t) e].id - 1)];
+                            if (g.n_draft > 0) {
+                                // the draft is the drafter's hit on the request's own history (then the corpus), cut to what is left to predict
+                                int32_t want[15];
+                                const int32_t room = std::min(draft_len, w.n_predict - w.n_out - 1);
+                                EXPECT(room >= g.n_draft);
+                                std::vector<int32_t> cp(40);
+                                for (size_t i = 0; i < cp.size(); i++) cp[i] = (int32_t) ((i * 5 + 1) % (size_t) V);
+                                const int32_t nw = llamahip_lookup_draft(w.hist.data(), (int32_t) w.hist.size(), cp.data(), 40, std::max(room, 1), 0, 0, want);
+                                EXPECT(nw >= g.n_draft && std::equal(cl.drafts[j].begin(), cl.drafts[j].end(), want));
+                                EXPECT(g.pos == (int32_t) w.hist.size() - 1 && cl.toks[j][0] == w.hist.back());
+                                if (w.smp && w.stop >= 0) EXPECT(std::find(cl.drafts[j].begin(), cl.drafts[j].end(), w.stop) == cl.drafts[j].end());
+                            }
+                            emit_segs++; accepted += g.n_accept;
+                            const int n_tok = g.n_draft > 0 ? g.n_accept + 1 : 1;
+                            bool ended = false;
+                            for (int a = 0; a < n_tok && !ended; a++) {
+                                const int32_t tok = g.n_draft > 0 ? g.toks[a] : g.token;
+                                EXPECT(e < ne);
+                                if (e >= ne) break;
+                                const llamahip_sched_event &x = evs[(size_t) e++];
+                                w.hist.push_back(tok); w.n_out++; tokens++;
+                                EXPECT(x.kind == LLAMAHIP_EV_TOKEN && x.token == tok && x.slot == g.slot && x.position == (int32_t) w.hist.size() - 1);
+                                if (tok == w.stop || w.n_out == w.n_predict) {
+                                    EXPECT(e < ne && evs[(size_t) e].kind == LLAMAHIP_EV_DONE && evs[(size_t) e].id == x.id && evs[(size_t) e].position == x.position);
+                                    EXPECT(evs[(size_t) e].reason == (tok == w.stop ? LLAMAHIP_DONE_STOP : LLAMAHIP_DONE_LENGTH) && !w.done);
+                                    e++; w.done = 1; ended = true;
+                                    dropped += n_tok - 1 - a;
+                                }
+                            }
+                        }
+                        EXPECT(e == ne && logit_rows <= 16);
+                        drafted += step_drafted;
+                        draft_steps += step_drafted > 0;
+                        EXPECT(step_drafted == 0 || cl.mixed);
+                    }
+                    EXPECT(llamahip_sched_pending(sc) == 0);
+                    for (const DReq &w : reqs) EXPECT(w.done == 1 && w.n_out <= w.n_predict && (w.stop >= 0 || w.n_out == w.n_predict));
+                    llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                    EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_tokens == tokens && ss.n_emit_segs == emit_segs && ss.n_accepted == accepted && ss.n_drafted == drafted);
+                    EXPECT(ss.n_dropped == dropped && ss.n_draft_steps == draft_steps && ss.n_tokens == ss.n_emit_segs + ss.n_accepted - ss.n_dropped && ss.n_accepted <= ss.n_drafted);
+                    EXPECT(drafted > 0 && (script == 0 ? accepted == 0 : accepted > 0));
+                    if (script == 15) EXPECT(accepted == drafted);
+                    dropped_in_all += dropped;
+                    llamahip_sched_free(sc);
+                    for (DReq &w : reqs) if (w.smp) llamahip_sampler_free(w.smp);
+                }
+        g_sched_accept = -1;
+        EXPECT(!ms || dropped_in_all > 0);          // (some greedy request met its stop token inside an accepted run)
+        printf("host_sanitize: scheduler with drafted tokens: scripted accepts at draft_len 1 / 4 / 15, %lld tokens dropped behind stop tokens\n", (long long) dropped_in_all);
+        if (ms) {
+            // a handle that takes no drafts (the fall-back handles): the drafting scheduler plans none; what llamahip_sched_new refuses of the draft options
+            g_sched_drafts = false;
+            llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+            so.struct_size = sizeof(so); so.max_active = 2; so.draft_len = 4;
+            llamahip_sched *sc = nullptr;
+            EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+            if (sc) {
+                std::vector<int32_t> p(6, 1);
+                llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                rq.struct_size = sizeof(rq); rq.prompt = p.data(); rq.n_prompt = 6; rq.n_predict = 9; rq.stop_token = -1;
+                EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == 0);
+                std::vector<llamahip_sched_event> evs(19);
+                g_sched_calls.clear();
+                int32_t ne = 0;
+                while (llamahip_sched_pending(sc) > 0 && g_sched_calls.size() < 50) EXPECT(llamahip_sched_step(sc, evs.data(), 19, &ne, err, sizeof(err)) == 0);
+                for (const SchedCall &cl : g_sched_calls) for (const lh::SchedSeg &g : cl.segs) EXPECT(g.n_draft == 0);
+                llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_drafted == 0 && ss.n_draft_steps == 0 && ss.n_tokens == 9 && g_sched_calls.size() == 9);
+                llamahip_sched_free(sc);
+            }
+            g_sched_drafts = true;
+            std::vector<int32_t> bad(3, 1);
+            bad[2] = V;
+            so.draft_len = 16; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "draft_len"));
+            so.draft_len = -1; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "draft_len"));
+            so.draft_len = 4; so.ngram_min = 3; so.ngram_max = 2; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "ngram"));
+            so.ngram_min = -1; so.ngram_max = 0; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "ngram"));
+            so.ngram_min = 0; so.corpus = bad.data(); so.n_corpus = 3; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "corpus token id"));
+            so.n_corpus = 2; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);          // (the id out of range lies behind n_corpus)
+            llamahip_sched_free(sc); sc = nullptr;
+            so.corpus = nullptr; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "n_corpus"));
+            so.n_corpus = -1; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "n_corpus"));
+            // a struct that ends before draft_len: no drafting, whatever lies behind it
+            so.n_corpus = 0; so.draft_len = 99; so.struct_size = (int32_t) offsetof(llamahip_sched_opts, draft_len);
+            EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+            llamahip_sched_free(sc);
+        }
         if (ms) {
             // one scheduler per handle at a time; a step that fails delivers nothing and loses nothing (the waiting CANCELLED events, the
             // admitted requests and the stats are all there for the step that succeeds)

@@ -26,6 +26,9 @@
 // k_sched_pick: the device half of a request scheduler's mixed pass (llamahip_sched_step), one wave per segment behind the lm head -- the
 //   greedy pick of every segment that emits, by the device function k_verify_rows picks with (vr_row_pick), into the result block, the
 //   slot's next-token word and its trace; every segment's slot {position, cursor} set behind its rows.  4 bytes per segment come back.
+// k_sched_accept: the same for a scheduler step that carries drafted tokens, behind k_verify_rows over all logits rows of the step -- per
+//   segment n_accept by the rule above (one device function, vr_n_accept, for the three kernels), the slot's words advanced by what was
+//   accepted.  4 (rows + segments) bytes come back.
 #include <cmath>
 
 #include "kcommon.hip.h"
@@ -77,6 +80,15 @@ __device__ __forceinline__ int vr_row_pick(const float *__restrict__ row, int V,
     return i == 0x7fffffff ? 0 : i;                           // (nothing taken: every entry a NaN)
 }
 
+// the accept rule of one segment of N rows by one wave: lane j < N holds row j's pick p, tokens = the tokens of the segment's rows (tokens[0]
+// the last accepted token, tokens[j + 1] the draft token behind row j).  Lane j < N - 1 agrees if row j's pick is the draft's next token;
+// the first lane where that fails (or N - 1) is n_accept.  N >= 1; every lane of the wave calls it.
+__device__ __forceinline__ int vr_n_accept(int lane, int N, int p, const int32_t *__restrict__ tokens) {
+    const bool agree = lane < N - 1 && p == tokens[lane + 1];
+    const unsigned long long miss = ~__ballot(agree);
+    return min((int) __builtin_ctzll(miss), N - 1);
+}
+
 __global__ void __launch_bounds__(1024)
 k_verify_rows(const float *__restrict__ logits, int V, int32_t *__restrict__ pick) {
     __shared__ float bv[16];
@@ -119,10 +131,7 @@ k_accept_drafts(const int32_t *__restrict__ tokens, const int32_t *__restrict__ 
                 int32_t *__restrict__ log, int log_cap, int32_t *__restrict__ state, int32_t *__restrict__ res) {
     const int lane = threadIdx.x;
     const int p = !pick ? pick_imm : lane < N ? pick[lane] : 0;
-    // lane j < N - 1: row j's pick is the draft's next token; the first lane where that fails (or N - 1) is n_accept
-    const bool agree = lane < N - 1 && p == tokens[lane + 1];
-    const unsigned long long miss = ~__ballot(agree);
-    const int n_accept = min((int) __builtin_ctzll(miss), N - 1);
+    const int n_accept = vr_n_accept(lane, N, p, tokens);
     const int pos = restart_pos >= 0 ? restart_pos : state[0], cur = restart_pos >= 0 ? 0 : state[1];
     if (lane <= n_accept && cur >= 0 && cur + lane < log_cap) log[cur + lane] = p;
     if (lane < N) res[1 + lane] = p;
@@ -142,9 +151,7 @@ k_accept_drafts_set(const int32_t *__restrict__ tokens, const int32_t *__restric
     const int b = seg_begin[s], N = seg_begin[s + 1] - b;
     if (b < 0 || N < 1 || b + N > n_rows) return;                 // (the host refuses such segments before the launch)
     const int p = lane < N ? pick[b + lane] : 0;
-    const bool agree = lane < N - 1 && p == tokens[b + lane + 1];
-    const unsigned long long miss = ~__ballot(agree);
-    const int n_accept = min((int) __builtin_ctzll(miss), N - 1);
+    const int n_accept = vr_n_accept(lane, N, p, tokens + b);
     if (lane < N) res[n_segs + b + lane] = p;
     if (lane == 0) res[s] = n_accept;
     if (!state) return;
@@ -156,6 +163,37 @@ k_accept_drafts_set(const int32_t *__restrict__ tokens, const int32_t *__restric
     if (lane == 0) {
         st[0] = pos + n_accept + 1;
         st[1] = cur + n_accept + 1;
+    }
+}
+
+// A scheduler's step with drafted tokens (llamahip_sched_step with draft_len > 0; llamahip_op_sched_accept), one wave per segment
+// (blockIdx.x) behind k_verify_rows, which has picked every logits row of the step: k_sched_pick generalised to segments with several
+// logits rows.  tab[s] = {emit, slot, base position, base cursor, first logits row b, row count}.  The segment's logits rows are
+// [b, b + N): N = the row count where emit == 2 (a decode segment [last token, draft ...]: tokens[b ..] are its rows' tokens), 1 where
+// emit == 1 (the last row of a prompt piece, a plain decode row), none where emit == 0.  n_accept by vr_n_accept -- the rule of
+// k_accept_drafts_set, not restated -- where N > 1, else 0.  res = {n_accept[n_segs], pick[n_rows]}.  With slot words (state != null; all
+// three or none): position = base + rows consumed (n_accept + 1 for emit 2, the row count otherwise), cursor = base cursor + tokens
+// produced, the slot's next-token word = pick[n_accept], its trace receives pick[0 .. n_accept] at the base cursor.
+// Plain loads and stores, program order inside the one wave, no hand-offs between workgroups.
+__global__ void __launch_bounds__(64)
+k_sched_accept(const int32_t *__restrict__ pick, const int32_t *__restrict__ tokens, const int32_t *__restrict__ tab, int n_segs, int n_rows,
+               int32_t *__restrict__ state, int32_t *__restrict__ log, int log_cap, int32_t *__restrict__ next_tok, int32_t *__restrict__ res) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int32_t *t = tab + SCHED_TAB_W * s;
+    const int emit = t[0], slot = t[1], pos = t[2], cur = t[3], b = t[4], rows = t[5];
+    const int N = emit == 2 ? rows : emit == 1 ? 1 : 0;          // (uniform over the wave)
+    if (N > 0 && (b < 0 || b + N > n_rows || N > 64)) return;    // (the host refuses such segments before the launch)
+    const int p = lane < N ? pick[b + lane] : 0;
+    const int n_accept = N > 1 ? vr_n_accept(lane, N, p, tokens + b) : 0;
+    if (lane < N) res[n_segs + b + lane] = p;
+    if (lane == 0) res[s] = n_accept;
+    if (!state) return;
+    const int made = N > 0 ? n_accept + 1 : 0;                   // the tokens the segment produced
+    if (lane < made && cur >= 0 && cur + lane < log_cap) log[(size_t) slot * log_cap + cur + lane] = p;
+    if (N > 0 && lane == n_accept) next_tok[slot] = p;
+    if (lane == 0) {
+        state[2 * (size_t) slot] = pos + (emit == 2 ? n_accept + 1 : rows);
+        state[2 * (size_t) slot + 1] = cur + made;
     }
 }
 
@@ -172,6 +210,15 @@ hipError_t launch_sched_pick(const float *logits, int n_segs, int V, const int32
     if (n_segs < 1 || n_segs > SET_MAX || V < 1 || !logits || !tab || !res) return hipErrorInvalidValue;
     if (state && (!log || !next_tok || log_cap < 1)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sched_pick, dim3((unsigned) n_segs), dim3(64), 0, st, logits, V, tab, state, log, log_cap, next_tok, res);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+hipError_t launch_sched_accept(const int32_t *pick, const int32_t *tokens, const int32_t *tab, int n_segs, int n_rows, int32_t *state, int32_t *log,
+                               int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st) {
+    if (n_segs < 1 || n_segs > SET_MAX || n_rows < 1 || n_rows > VERIFY_ROWS_MAX || !pick || !tokens || !tab || !res) return hipErrorInvalidValue;
+    if (state && (!log || !next_tok || log_cap < 1)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sched_accept, dim3((unsigned) n_segs), dim3(64), 0, st, pick, tokens, tab, n_segs, n_rows, state, log, log_cap, next_tok, res);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -13,9 +13,21 @@ The runs are interleaved (baseline, then every budget, `repeats` times over) aft
 median and min .. max of the aggregate tokens/s, the longest single step (what a decoding conversation waits while a prompt is admitted), the
 steps by kind, rows, graph captures; and what a capture costs: a set step that captured graphs against the next replayed set step of the same
 row count in the same run.
-LLAMAHIP_SCHED_ROW_BUDGET is the candidate with the highest median tokens/s; of candidates within the runs' spread of it, the smallest."""
+LLAMAHIP_SCHED_ROW_BUDGET is the candidate with the highest median tokens/s; of candidates within the runs' spread of it, the smallest.
+
+sched_probe.py --draft [--json OUT] [--repeats 3] [--alter 2,5] [--parent-root DIR] [--parent-runs 5]
+Drafted tokens inside the scheduler (llamahip_sched_opts.draft_len) on the same workload at LLAMAHIP_SCHED_ROW_BUDGET: draft_len 0 against
+LLAMAHIP_LOOKUP_DRAFT_LEN with three kinds of corpus -- none (the requests' own histories only); every request's own plain-run output (every
+draft from it is accepted); that output with every k-th token altered, for each k of --alter.  One process, one handle, the configurations
+interleaved `repeats` times after one untimed run of each; every run's tokens must be the plain run's.  Reported per configuration: aggregate
+tokens/s, the longest step, steps, drafted / accepted, and the acceptance rate from which drafting pays (the plain run's tokens/s, interpolated
+in acceptance rate between the configurations that draft from a corpus).
+--parent-root DIR: a tree of the parent commit with its library built (python package and libllamahip.so).  The draft_len == 0 scheduler of
+this tree against that tree's, each run in a fresh process (--one-plain-run, one untimed run, then the timed one), interleaved, --parent-runs
+each: both medians, both min .. max spreads, and whether the medians differ by less than the parent's own spread."""
 import json, os, statistics, subprocess, sys, time
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = os.environ.get("LLAMAHIP_PROBE_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # (--one-plain-run on the parent's tree)
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 args = sys.argv[1:]
@@ -27,19 +39,127 @@ N_CTX, SLOTS, CHUNK, NTH = 512, 16, 9, 8
 LENS, PREDICTS = (9, 18, 36, 72, 144, 288), (8, 16, 32, 64, 128, 256)
 
 
-def main():
-    import numpy as np
-    import llama_swift_amd as L
-    subprocess.run(["bash", os.path.join(ROOT, "tools", "ensure_7b.sh")], cwd=ROOT, check=True)
+def workload(np, n_vocab):
     rng = np.random.default_rng(20240611)
-    m = L.Model(MODEL, n_ctx=N_CTX, n_seq=SLOTS)
     reqs = []
     for i in range(N_REQ):
         if i % len(PREDICTS) == 0:
             perm = rng.permutation(PREDICTS)
         n = LENS[i % len(LENS)]
-        prompt = np.concatenate([[1], rng.integers(3, m.n_vocab, n - 1)]).astype(np.int32)
+        prompt = np.concatenate([[1], rng.integers(3, n_vocab, n - 1)]).astype(np.int32)
         reqs.append((prompt, int(min(perm[i % len(PREDICTS)], N_CTX - max(LENS)))))
+    return reqs
+
+
+def timed_run(m, reqs, budget, **kw):
+    """one scheduler run over the workload: (wall seconds, longest step in ms, stats, tokens per request)"""
+    out, longest = {}, 0.0
+    with m.scheduler(max_active=SLOTS, chunk_tokens=CHUNK, row_budget=budget, n_threads=NTH, **kw) as sc:
+        ids = [sc.submit(p, k) for p, k in reqs]
+        t_all = time.perf_counter()
+        while sc.pending():
+            t0 = time.perf_counter()
+            ev = sc.step()
+            longest = max(longest, (time.perf_counter() - t0) * 1e3)
+            for e in ev:
+                if e["kind"] == "token":
+                    out.setdefault(e["id"], []).append(e["token"])
+        wall = time.perf_counter() - t_all
+        st = sc.stats()
+    return wall, longest, st, [out[i] for i in ids]
+
+
+def one_plain_run():
+    """--one-plain-run: the draft_len == 0 scheduler of the tree at ROOT in this fresh process; one JSON line"""
+    import numpy as np
+    import llama_swift_amd as L
+    m = L.Model(MODEL, n_ctx=N_CTX, n_seq=SLOTS)
+    reqs = workload(np, m.n_vocab)
+    timed_run(m, reqs, 256)
+    wall, longest, st, toks = timed_run(m, reqs, 256)
+    print(json.dumps({"tokens_per_s": sum(k for _, k in reqs) / wall, "longest_step_ms": longest, "n_steps": st["n_steps"], "library": L.LIB_PATH,
+                      "tokens_crc": int(np.bitwise_xor.reduce(np.concatenate([np.asarray(t, np.int64) * (i + 1) for i, t in enumerate(toks)])))}), flush=True)
+    m.close()
+
+
+def main_draft():
+    import numpy as np
+    import llama_swift_amd as L
+    subprocess.run(["bash", os.path.join(HERE, "tools", "ensure_7b.sh")], cwd=HERE, check=True)
+    m = L.Model(MODEL, n_ctx=N_CTX, n_seq=SLOTS)
+    reqs = workload(np, m.n_vocab)
+    asked = sum(k for _, k in reqs)
+    budget, draft_len = 256, 15          # LLAMAHIP_SCHED_ROW_BUDGET, LLAMAHIP_LOOKUP_DRAFT_LEN
+    _, _, _, want = timed_run(m, reqs, budget)
+    own = np.concatenate([np.concatenate([p[-1:], np.asarray(t, np.int32)]) for (p, _), t in zip(reqs, want)]).astype(np.int32)
+    configs = [("draft_len 0", {}), ("no corpus", dict(draft_len=draft_len)), ("own output", dict(draft_len=draft_len, corpus=own))]
+    for k in [int(x) for x in opt("--alter", "2,5").split(",")]:
+        c = own.copy()
+        c[k - 1::k] = (c[k - 1::k] + 1) % m.n_vocab
+        configs.append((f"own output, every {k}th token altered", dict(draft_len=draft_len, corpus=c)))
+    for name, kw in configs:          # one untimed run of each; the tokens are the plain run's whatever is drafted
+        assert timed_run(m, reqs, budget, **kw)[3] == want, f"{name}: the tokens are not the plain run's"
+    runs = {name: [] for name, _ in configs}
+    for _ in range(REPEATS):
+        for name, kw in configs:
+            runs[name].append(timed_run(m, reqs, budget, **kw)[:3])
+    spread = lambda xs: {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+    res = {"model": "7B synthetic (seed 20230312), Q4_0", "n_ctx": N_CTX, "max_active": SLOTS, "chunk_tokens": CHUNK, "n_threads": NTH, "row_budget": budget,
+           "draft_len": draft_len, "requests": N_REQ, "tokens_asked": int(asked), "repeats": REPEATS, "library": os.path.basename(L.LIB_PATH),
+           "method": "one process, one handle; the configurations interleaved, `repeats` times, after one untimed run of each; wall time around the whole run and around every step",
+           "configs": []}
+    for name, _ in configs:
+        st = runs[name][-1][2]
+        row = {"corpus": name, "tokens_per_s": spread([asked / w for w, _, _ in runs[name]]), "longest_step_ms": spread([l for _, l, _ in runs[name]]),
+               "steps": st["n_steps"], "draft_steps": st.get("n_draft_steps", 0), "drafted": st.get("n_drafted", 0), "accepted": st.get("n_accepted", 0),
+               "acceptance": round(st.get("n_accepted", 0) / max(st.get("n_drafted", 0), 1), 4), "rows": st["n_rows"]}
+        res["configs"].append(row)
+        print(f"{name:40s} {row['tokens_per_s']} tokens/s | longest step {row['longest_step_ms']['median']} ms | {row['steps']} steps | "
+              f"{row['accepted']} / {row['drafted']} accepted ({row['acceptance']})", flush=True)
+    # from which acceptance rate drafting pays: the plain median, interpolated between the drafting configurations in acceptance rate
+    plain = res["configs"][0]["tokens_per_s"]["median"]
+    # (the corpus configurations only: they draft at every opportunity, so their cost per step is the same and the acceptance rate is what differs)
+    pts = sorted((r["acceptance"], r["tokens_per_s"]["median"]) for r in res["configs"][2:] if r["drafted"] > 0)
+    be = None
+    for (a0, t0), (a1, t1) in zip(pts, pts[1:]):
+        if (t0 - plain) * (t1 - plain) <= 0 and t1 != t0:
+            be = round(a0 + (plain - t0) * (a1 - a0) / (t1 - t0), 3)
+    res["break_even"] = {"plain_tokens_per_s": plain, "points": pts, "acceptance": be,
+                         "note": "acceptance rate at which the interpolated tokens/s equals the plain run's; null: not bracketed by the measured points "
+                                 + ("(drafting paid at every one)" if pts and min(t for _, t in pts) > plain else "(drafting paid at none)" if pts and max(t for _, t in pts) < plain else "")}
+    print("break-even:", res["break_even"], flush=True)
+    m.close()
+    parent = opt("--parent-root", "")
+    res["draft_len_0_against_parent"] = None
+    if parent:
+        n_runs = int(opt("--parent-runs", "5"))
+        got = {"this": [], "parent": []}
+        for _ in range(n_runs):
+            for who, root in (("parent", os.path.abspath(parent)), ("this", HERE)):
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-plain-run"], env={**os.environ, "LLAMAHIP_PROBE_ROOT": root},
+                                   capture_output=True, text=True, timeout=600)
+                assert r.returncode == 0, r.stderr[-2000:]
+                got[who].append(json.loads(r.stdout.strip().splitlines()[-1]))
+        assert len({x["tokens_crc"] for v in got.values() for x in v}) == 1, "the two libraries produced different tokens"
+        assert got["parent"][0]["library"] != got["this"][0]["library"]
+        tp, tt = spread([x["tokens_per_s"] for x in got["parent"]]), spread([x["tokens_per_s"] for x in got["this"]])
+        res["draft_len_0_against_parent"] = {
+            "method": f"fresh processes, interleaved, {n_runs} each; in each one untimed run, then the timed one", "parent_tokens_per_s": tp, "this_tokens_per_s": tt,
+            "parent_longest_step_ms": spread([x["longest_step_ms"] for x in got["parent"]]), "this_longest_step_ms": spread([x["longest_step_ms"] for x in got["this"]]),
+            "median_difference": round(tt["median"] - tp["median"], 3), "parent_spread": round(tp["max"] - tp["min"], 3),
+            "unchanged_within_the_parents_spread": abs(tt["median"] - tp["median"]) <= tp["max"] - tp["min"]}
+        print("draft_len 0 against the parent:", res["draft_len_0_against_parent"], flush=True)
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def main():
+    import numpy as np
+    import llama_swift_amd as L
+    subprocess.run(["bash", os.path.join(ROOT, "tools", "ensure_7b.sh")], cwd=ROOT, check=True)
+    m = L.Model(MODEL, n_ctx=N_CTX, n_seq=SLOTS)
+    reqs = workload(np, m.n_vocab)
     asked = sum(k for _, k in reqs)
 
     def run_sched(budget):
@@ -133,4 +253,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    one_plain_run() if "--one-plain-run" in args else main_draft() if "--draft" in args else main()
