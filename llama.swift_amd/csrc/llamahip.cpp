@@ -44,6 +44,8 @@ namespace {
 double now_ms() {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+// the n_threads of a call as the kernels take it (the key split of the attention follows it)
+inline int clamp_threads(int n_threads) { return std::max(1, std::min(n_threads, 64)); }
 
 struct Layer {
     float *attention_norm = nullptr, *ffn_norm = nullptr;   // fp32 [d]
@@ -186,7 +188,6 @@ struct llamahip_model {
                     int32_t pool[SLIDE_SET_IDS]; int32_t row_tab[2 * VERIFY_ROWS_MAX];          // (a sampled verify step over a set: its id pool and {row_off, row_n_last} in; `rows` back)
                     int32_t slot_words[2 * SET_MAX]; };                                         // (the drafted sampled loop: the slots' {position, cursor} on their way to d_slot_state)
     HostIo *h_io = nullptr, *d_io = nullptr;       // host pointer / its device alias
-    const int32_t *tok_src = nullptr;              // set by eval_impl around forward(): where the embedding kernel finds the token
     float *x = nullptr, *x1 = nullptr, *qkv = nullptr, *qr = nullptr, *merged = nullptr, *gu = nullptr;
     float *tmp = nullptr;                // debug: un-fused residual operand
     float *logits = nullptr;             // [ws_cap][V] (all rows only in debug evals)
@@ -209,7 +210,6 @@ struct llamahip_model {
     bool w13_interleaved = false;
     bool prompt_copies = false;          // the row-lane / matrix-core copies of the layer matrices exist (ensure_prompt_copies)
     bool output_copies_tried = false;    // ... and of `output`, for the scoring entry points' all-rows lm head (ensure_output_copies)
-    bool score_rows = false;             // set around forward() by the scoring entry points: the all-rows lm head takes those copies
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
     char *d_slide = nullptr;             // sampled verify step (last stage): 16 x TOPK_WS_BYTES of selection workspace | the id stream (SLIDE_IDS_BYTES) | 16 TopkOut (slide_ensure)
@@ -230,7 +230,6 @@ struct llamahip_model {
     int n_seq = 1, cur_seq = 0;          // KV caches: [seq][layer][n_ctx][d]
     AttnWs attn_ws;                      // many-row prompt attention workspace (allocated with the first eval of >= 2 tokens: ensure_attn_ws)
     GraphCache<int> decode_graphs;                 // keyed by nth * 4096 + seq + (attention schedule << 24)
-    int attn_sched = 0;                            // decode attention schedule of the single-row pass being launched / captured (attn_sched_at): 0 fused, 1 two launches, 2 long-context
     // asynchronous pipeline-stage steps (llamahip_stage_bind / llamahip_stage_step)
     struct StageSlot {
         int32_t *token_in = nullptr, *token_out = nullptr;     // caller-owned device buffers
@@ -439,7 +438,7 @@ int ensure_prompt_copies(llamahip_model *m, int N, char *err, size_t err_cap) {
 }
 // The lm head over EVERY row (llamahip_eval_logprobs / llamahip_perplexity) is a long-prompt GEMM of its own (7B: 32 000 x 4 096): from
 // 64 rows it gets `output`'s copies too, built once, by the same code, so that it can take k_gemm_mfma4.  Out of device memory: it keeps
-// the decode-tile kernels (bit-identical).  llamahip_eval / _chunks / _debug never build or read them (forward: score_rows).
+// the decode-tile kernels (bit-identical).  llamahip_eval / _chunks / _debug never build or read them (Pass::score_rows).
 constexpr int OUTPUT_COPY_MIN_ROWS = 64;
 void ensure_output_copies(llamahip_model *m, int N) {
     if (N < OUTPUT_COPY_MIN_ROWS || m->dense || m->output_copies_tried || (m->flags & LLAMAHIP_FLAG_NO_PREFILL_COPY)) return;
@@ -560,21 +559,29 @@ struct DumpSink {
     }
 };
 
-// The forward pass for N tokens at n_past on this handle's layers (.mm:510-735).
-//   hidden_in  : device fp32 [N][d] residual stream from the previous stage (nullptr on the first stage)
-//   want_all   : compute logits for every token (debug) instead of only the last (.mm:724-725)
-//   io         : (fused single-token path only) device-side endpoints of a captured step: token slot,
-//                position state, and the residual-stream buffers read by the first / written by the
-//                last layer of this stage in place of m->x (no staging copies)
-struct StepIO {
-    const int32_t *token = nullptr;
-    int32_t *state = nullptr;
-    const float *x_first = nullptr;
-    float *x_last = nullptr;
-    // device-side mailboxes instead of x_first / x_last / token (tagged granules, see MailboxIO)
-    const uint64_t *mb_in = nullptr;
+// What a forward pass for N tokens at n_past on this handle's layers (.mm:510-735) is told.  The caller fills the fields by name; the ones it
+// leaves alone mean this handle's own token buffer, position words, current KV slot and stream.  Nothing of a pass is kept on the handle.
+struct Pass {
+    explicit Pass(const llamahip_model *m) : tokens(m->d_tokens), seq(m->cur_seq), stream(m->stream), state(m->d_state) {}
+    int n_threads = 1, n_past = 0, N = 1;
+    const float *hidden_in = nullptr;   // device fp32 [N][d] residual stream from the previous stage (nullptr on the first stage)
+    bool want_all = false;              // logits for every token (debug, scoring) instead of only the last (.mm:724-725)
+    bool score_rows = false;            // ... by the scoring entry points: the all-rows lm head takes `output`'s prompt copies
+    int chunk = 0;                      // > 0: the rows are the evals of `chunk` tokens of llamahip_eval_chunks in one pass
+    int dump_layer = -1; DumpSink *sink = nullptr;      // per-layer dumps (llamahip_eval_debug): both or neither
+    const int32_t *tokens;              // device: where the embedding kernel finds the N tokens
+    int seq;                            // KV slot
+    hipStream_t stream;
+    // ---- single-token steps only
+    bool state_on_device = false;       // the position words are current (a captured / device-driven step); else n_past is published first
+    int attn_sched = 0;                 // decode attention schedule (attn_sched_at): 0 fused, 1 two launches, 2 long-context
+    // device-side endpoints of a stage step: the position words, and the residual-stream buffers read by the first / written by the
+    // last layer of this stage in place of m->x (no staging copies)
+    int32_t *state;
+    const float *x_first = nullptr; float *x_last = nullptr;
+    // device-side mailboxes instead of x_first / x_last / tokens (tagged granules, see MailboxIO)
+    const uint64_t *mb_in = nullptr, *mb_token = nullptr;
     uint64_t *mb_out = nullptr;
-    const uint64_t *mb_token = nullptr;
     // the device-resident greedy loop: the lm head's launch also picks the token, advances the position and embeds the pick for the
     // next step (EPI_STORE_PICK); the step then starts from the row the previous step (or the caller) left in x / npart_a
     bool fold_pick = false;
@@ -602,53 +609,41 @@ static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int m
 
 // f16 / f32 model files: the same graph with dense mat-muls (dense.hip).  Un-fused:
 // norm -> fp32 activations -> dense mat-mul; RoPE, KV cache and attention are the Q4_0 path's kernels.
-// (io, single-row steps: the token word and the {position, step} words of a stage step -- llamahip_stage_step on a whole-model handle)
-// chunk > 0: the rows are the evals of `chunk` tokens of llamahip_eval_chunks in one pass -- norm, RoPE and the mat-muls work row by row, the
-// attention splits every row's keys as its own eval would (launch_attn)
-int forward_dense(llamahip_model *m, int n_threads, int n_past, int N, const float *hidden_in, bool want_all,
-                  bool state_on_device, char *err, size_t err_cap, const StepIO *io = nullptr, int chunk = 0) {
+// (single-row steps: the token word and the {position, step} words of a stage step -- llamahip_stage_step on a whole-model handle)
+// chunk > 0: norm, RoPE and the mat-muls work row by row, the attention splits every row's keys as its own eval would (launch_attn)
+int forward_dense(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
-    const int nth = std::max(1, std::min(n_threads, 64));
-    hipStream_t st = m->stream;
-    if (N == 1 && !state_on_device) {
-        // the decode attention kernels read the position from device memory; only st[0] is written here
-        // (st[1], the step counter of the greedy loop, belongs to k_argmax)
-        const int32_t pos = n_past;
-        HIP_TRY(hipMemcpyAsync(m->d_state, &pos, sizeof(pos), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
-    }
-    if (m->first_stage) {
-        HIP_TRY(launch_embed_dense((io && io->token) ? io->token : m->tok_src ? m->tok_src : m->d_tokens, m->tok_emb, hp.f16, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);     // .mm:558-561
-    } else {
-        HIP_TRY(hipMemcpyAsync(m->x, hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
-    }
-    int32_t *state = (io && io->state) ? io->state : m->d_state;
+    const int nth = clamp_threads(p.n_threads), n_past = p.n_past, N = p.N;
+    hipStream_t st = p.stream;
+    // the decode attention kernels read the position from device memory; only state[0] is written here (state[1], the step counter of the
+    // greedy loop, belongs to k_argmax)
+    if (N == 1 && !p.state_on_device) HIP_TRY(hipMemcpyAsync(m->d_state, &p.n_past, sizeof(int32_t), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
+    if (m->first_stage) HIP_TRY(launch_embed_dense(p.tokens, m->tok_emb, hp.f16, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);     // .mm:558-561
+    else HIP_TRY(hipMemcpyAsync(m->x, p.hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
     auto prep_mm = [&](const DMat &w, int epi, int mode, const float *in0, const float *in1, long in_stride, long in1_stride,
                        int K, int rows, float *out, long out_stride, const float *resid, long resid_stride) -> hipError_t {
         return dense_prep_mm(m, w, epi, mode, in0, in1, in_stride, in1_stride, K, rows, out, out_stride, resid, resid_stride, st);
     };
     for (int il = m->l0; il < m->l1; il++) {
         const Layer &L = m->layers[il - m->l0];
-        const size_t kv_at = ((size_t) m->cur_seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
+        const size_t kv_at = ((size_t) p.seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
         float *Kl = m->Kc + kv_at, *Vl = m->Vc + kv_at;
         HIP_TRY(prep_mm(L.dqkv, EPI_STORE, PREP_NORM, m->x, L.attention_norm, d, 0, d, N, m->qkv, 3L * d, nullptr, 0), LLAMAHIP_ERR_PREDICT);             // .mm:570-582
         if (N == 1) {
             // one row: the decode attention kernels of the Q4_0 path (position from device memory, fp32 output)
-            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, p.state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);                             // .mm:586-611
-            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, chunk), LLAMAHIP_ERR_PREDICT); // .mm:614-646
+            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, p.chunk), LLAMAHIP_ERR_PREDICT); // .mm:614-646
         }
         HIP_TRY(prep_mm(L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->x1, d, m->x, d), LLAMAHIP_ERR_PREDICT);                          // .mm:649-654
         HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
         HIP_TRY(prep_mm(L.dw2, EPI_RESID, PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, N, m->x, d, m->x1, d), LLAMAHIP_ERR_PREDICT);               // .mm:678-687
     }
     if (m->last_stage) {
-        if (want_all) {
-            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x, m->norm_w, d, 0, d, N, m->logits, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-        } else {
-            HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
-        }
+        const size_t r0 = p.want_all ? 0 : N - 1;      // every row, or only the last
+        HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x + r0 * d, m->norm_w, d, 0, d, N - (int) r0, m->logits + r0 * V, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -670,27 +665,117 @@ static int attn_sched_at(const llamahip_model *m, int pos) {
     if (two_from >= 0 && pos >= two_from) return 1;
     return 0;
 }
-int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hidden_in, bool state_on_device,
-            bool want_all, int dump_layer, DumpSink *sink, char *err, size_t err_cap, const StepIO *io = nullptr, int chunk = 0) {
+// The fused single-token step of a Q4_0 handle: activation preparation lives in GEMV prologues / producer epilogues (four launches per
+// layer), the context position is read from p.state by the attention kernels.
+int forward_decode(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
     const HParams &hp = m->hp;
-    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx;
-    const int nth = std::max(1, std::min(n_threads, 64));
-    hipStream_t st = m->stream;
-    const bool debug = dump_layer >= 0 && sink;
-    if (m->dense) {
-        if (debug) { set_err(err, err_cap, "per-layer dumps are available for Q4_0 models only"); return LLAMAHIP_ERR_PREDICT; }
-        return forward_dense(m, n_threads, n_past, N, hidden_in, want_all, state_on_device && N == 1, err, err_cap, N == 1 ? io : nullptr, chunk);
+    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, C = hp.n_ctx, V = hp.n_vocab;
+    const int nth = clamp_threads(p.n_threads);
+    hipStream_t st = p.stream;
+    int32_t *state = p.state;
+    const bool has_layers = m->l1 > m->l0, tagged = has_layers && m->l1 - m->l0 <= TAG_MAX_LAYERS;      // (tags are (epoch, layer))
+    const int32_t hs[2] = { p.n_past, 0 };      // host-driven single-token eval: publish the position to the device-resident state
+    if (!p.state_on_device) HIP_TRY(hipMemcpyAsync(m->d_state, hs, sizeof(hs), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
+    const float *x_first = has_layers ? p.x_first : nullptr;
+    float *x_last = has_layers ? p.x_last : nullptr;
+    // the producer of every residual-stream row (embedding, wo and w2 mat-vecs) hands {sum, sum of squares} of the row to the norm-fused mat-vec
+    // that consumes it, which then needs no reduction of its own (k_gemv PREP_NORMP).  LLAMAHIP_NORM_MODE=0 / 1: self-contained prologues (measurement only).
+    const bool use_part = m->w13_interleaved && norm_mode_resolve();
+    int n_part_x = 0;                                       // pairs in npart_a valid for the row currently in x (0: none)
+    // wq|wk|wv + attention as one launch with tagged hand-offs (k_qkv_attn); one forward pass = one epoch
+    // (long contexts: soft_max . V is a bandwidth problem of its own there -- separate mat-vec, k_dec_scores, k_dec_pv_stream)
+    const bool long_attn = p.attn_sched == 2 && pv_stream_applies((int) (d / H), (int) C, nth);
+    const bool two_attn = p.attn_sched == 1 || (p.attn_sched == 2 && !long_attn);
+    const bool use_qkvx = !long_attn && !two_attn && m->d_attn_sync && tagged && qkv_attn_applies(m->layers[0].qkv, d, H, nth);
+    const bool pv_split = long_attn && m->d_pvx && m->l1 - m->l0 <= TAG_MAX_LAYERS;
+    // w1|w3 in half-block workgroups (balanced over the CUs; the halves of a block exchange their amax inside one XCD): needs the XCD
+    // placement the load-time self-test confirmed (d_attn_sync) and the epoch for its tags
+    const bool use_w13h = m->w13_interleaved && m->d_attn_sync && m->d_w13_amax && tagged && gemv_silu_half_applies(m->layers[0].w13);
+    const bool use_epoch = use_qkvx || pv_split || use_w13h;
+    if (use_epoch && !(m->first_stage && use_part)) HIP_TRY(launch_bump_epoch(m->d_epoch, st), LLAMAHIP_ERR_PREDICT);
+    if (p.mb_token && m->first_stage && !use_part) { set_err(err, err_cap, "pipeline mailboxes need the default norm-statistics mode (LLAMAHIP_NORM_MODE unset)"); return LLAMAHIP_ERR_PREDICT; }
+    const bool fold = p.fold_pick && use_part && m->first_stage && m->last_stage;
+    if (m->first_stage && fold) {
+        n_part_x = 1;               // x, npart_a and the epoch were left by the previous step's lm head (or by decode_greedy's first embedding launch)
+    } else if (m->first_stage) {
+        if (use_part) {
+            HIP_TRY(launch_embed_part(p.tokens, m->tok_emb, m->x, d, m->npart_a, st, use_epoch ? m->d_epoch : nullptr, nullptr, p.mb_token, state, m->d_fault, V), LLAMAHIP_ERR_PREDICT);
+            n_part_x = 1;
+        } else
+        HIP_TRY(launch_embed(p.tokens, m->tok_emb, m->x, d, 1, st), LLAMAHIP_ERR_PREDICT);      // .mm:558-561
+    } else if (!x_first && !p.mb_in) {
+        HIP_TRY(hipMemcpyAsync(m->x, p.hidden_in, (size_t) d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
     }
-    const bool fused = (N == 1) && !debug && !(m->flags & LLAMAHIP_FLAG_UNFUSED);
-    const bool fast_prefill = (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) != 0 && !debug;      // opt-in re-associated prompt GEMM (llamahip.h)
-    if (fused && !state_on_device) {
-        // host-driven single-token eval: publish the position to the device-resident state
-        const int32_t hs[2] = { n_past, 0 };
-        HIP_TRY(hipMemcpyAsync(m->d_state, hs, sizeof(hs), hipMemcpyHostToDevice, st), LLAMAHIP_ERR_PREDICT);
+    // pipeline mailboxes: the first layer's row arrives / the last layer's row leaves as tagged granules
+    static const int mb_test = getenv("LLAMAHIP_HANDOFF_FAULT_TEST") ? atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) : 0;      // 3: the last layer publishes a tag nobody waits for (test only)
+    MailboxIO mb_first, mb_last;
+    const bool has_mb_in = p.mb_in && has_layers, has_mb_out = p.mb_out && has_layers;
+    if (has_mb_in) { mb_first.in_t = p.mb_in; mb_first.resid_t = p.mb_in; mb_first.pos_w = state; mb_first.epoch = m->d_epoch; mb_first.fault = m->d_fault; mb_first.test_bits = mb_test ? 0x1000 : 0; }
+    if (has_mb_out) { mb_last.out_t = p.mb_out; mb_last.pos_w = state; mb_last.epoch = m->d_epoch; mb_last.fault = m->d_fault; mb_last.test_bits = mb_test == 3 ? 0x2000 : 0; }
+
+    for (int il = m->l0; il < m->l1; il++) {
+        const Layer &L = m->layers[il - m->l0];
+        const size_t kv_at = ((size_t) p.seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
+        float *Kl = m->Kc + kv_at, *Vl = m->Vc + kv_at;
+        const float *xa = (il == m->l0 && x_first) ? x_first : m->x;      // residual stream into this layer
+        float *xo = (il == m->l1 - 1 && x_last) ? x_last : m->x;           // ... and out of it
+        NormPart np_qkv, np_wo, np_w13, np_w2;
+        if (use_part) {
+            const int pw = gemv_resid_parts(L.wo), p2 = gemv_resid_parts(L.w2);
+            if (n_part_x > 0) { np_qkv.in = m->npart_a; np_qkv.n_in = n_part_x; }
+            if (pw > 0 && pw <= NORM_PART_MAX) { np_wo.out = m->npart_b; np_w13.in = m->npart_b; np_w13.n_in = pw; }
+            n_part_x = 0;
+            if (p2 > 0 && p2 <= NORM_PART_MAX) { np_w2.out = m->npart_a; n_part_x = p2; }
+        }
+        // (mailboxes: the first layer reads its row -- norm input and residual operand -- from the tagged inbox, the last layer's w2
+        //  stores its row into the next stage's inbox; everything in between is the usual schedule)
+        const MailboxIO *mbi = (has_mb_in && il == m->l0) ? &mb_first : nullptr, *mbo = (has_mb_out && il == m->l1 - 1) ? &mb_last : nullptr;
+        if (use_qkvx) {
+            HIP_TRY(launch_qkv_attn(L.qkv, xa, L.attention_norm, np_qkv, m->d_qkv2, m->d_sc2, m->d_epoch, il - m->l0, d, H, C, nth, m->sincos, Kl, Vl, nullptr,
+                                    m->qa1_A, m->qa1_d, m->T_silu, m->T_exp, state, m->d_fault, st, mbi), LLAMAHIP_ERR_PREDICT);
+        } else {
+            HIP_TRY(launch_gemv(L.qkv, PREP_NORM, EPI_STORE, nullptr, nullptr, xa, L.attention_norm, m->qkv, nullptr, m->T_silu, nullptr, nullptr, st, &np_qkv, mbi), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, nullptr, m->qa1_A, m->qa1_d, m->T_exp, state, st, two_attn ? nullptr : m->d_attn_sync, m->d_fault, long_attn,
+                                    pv_split ? m->d_pvx : nullptr, m->d_epoch, il - m->l0), LLAMAHIP_ERR_PREDICT);
+        }
+        HIP_TRY(launch_gemv(L.wo, PRE_QA, EPI_RESID, m->qa1_A, m->qa1_d, nullptr, nullptr, m->x1, xa, m->T_silu, nullptr, nullptr, st, &np_wo, mbi), LLAMAHIP_ERR_PREDICT);
+        if (m->w13_interleaved) {
+            if (use_w13h) HIP_TRY(launch_gemv_silu_half(L.w13, m->x1, L.ffn_norm, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13, m->d_w13_amax, m->d_epoch, il - m->l0, m->d_fault), LLAMAHIP_ERR_PREDICT);
+            else
+            HIP_TRY(launch_gemv(L.w13, PREP_NORM, EPI_SILU_QA, nullptr, nullptr, m->x1, L.ffn_norm, nullptr, nullptr, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemv(L.w2, PRE_QA, EPI_RESID, m->qa2_A, m->qa2_d, nullptr, nullptr, mbo ? nullptr : xo, m->x1, m->T_silu, nullptr, nullptr, st, &np_w2, mbo), LLAMAHIP_ERR_PREDICT);
+        } else {
+            if (mbo) { set_err(err, err_cap, "pipeline mailboxes need the interleaved w1|w3 layout"); return LLAMAHIP_ERR_PREDICT; }
+            HIP_TRY(launch_gemv(L.w13, PREP_NORM, EPI_STORE, nullptr, nullptr, m->x1, L.ffn_norm, m->gu, nullptr, m->T_silu, nullptr, nullptr, st), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemv(L.w2, PREP_SILU_MUL, EPI_RESID, nullptr, nullptr, m->gu, m->gu + F, xo, m->x1, m->T_silu, nullptr, nullptr, st), LLAMAHIP_ERR_PREDICT);
+        }
     }
 
-    // short prompt chunks (the reference evaluates prompts 8 tokens at a time, .mm / LlamaRunner n_batch) take
-    // the decode-shaped attention
+    if (m->last_stage) {
+        // final norm + lm head (.mm:695-705)
+        NormPart np_out;
+        if (n_part_x > 0 && has_layers) { np_out.in = m->npart_a; np_out.n_in = n_part_x; }      // (x_last is null on the last stage: the row is in m->x)
+        if (fold) {
+            const PickIO pk = { m->d_pick + 128, (uint32_t *) m->d_pick, p.pick_out, p.pick_next, state, m->tok_emb, m->x, m->npart_a,
+                                (m->d_attn_sync || m->d_pvx || m->d_w13_amax) ? m->d_epoch : nullptr, V };      // (the NEXT step's epoch: its schedule may use the tags even if this one does not)
+            HIP_TRY(launch_gemv_pick(m->output, m->x, m->norm_w, m->logits, m->T_silu, st, &np_out, pk), LLAMAHIP_ERR_PREDICT);
+        } else
+        HIP_TRY(launch_gemv(m->output, PREP_NORM, EPI_STORE, nullptr, nullptr, m->x, m->norm_w, m->logits, nullptr, m->T_silu, nullptr, nullptr, st, &np_out), LLAMAHIP_ERR_PREDICT);
+    }
+    return 0;
+}
+
+// The un-fused pass of a Q4_0 handle for N rows (prompt evals; one row on LLAMAHIP_FLAG_UNFUSED handles and in debug evals): prepare -> GEMM
+// per mat-mul, the position comes from the host.
+int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
+    const HParams &hp = m->hp;
+    const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
+    const int nth = clamp_threads(p.n_threads), n_past = p.n_past, N = p.N, chunk = p.chunk;
+    hipStream_t st = p.stream;
+    DumpSink *sink = p.sink;
+    const bool debug = p.dump_layer >= 0 && sink;
+    const bool fast_prefill = (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) != 0 && !debug;      // opt-in re-associated prompt GEMM (llamahip.h)
+    // short prompt chunks (the reference evaluates prompts 8 tokens at a time, .mm / LlamaRunner n_batch) take the decode-shaped attention
     const bool short_chunk = attn_path_pick(&m->attn_ws, N, dh, n_past + N, nth) == ATTN_PATH_SHORT;
     // short evals (2 .. 16 rows): the w1|w3 launch of k_gemv_set runs half-block workgroups whose halves exchange their amax as tagged
     // granules -- needs the XCD placement the load-time self-test confirmed and one epoch per pass
@@ -699,97 +784,19 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
         set_hx.amax_t = m->d_set_amax; set_hx.epoch = m->d_epoch; set_hx.fault = m->d_fault;
         HIP_TRY(launch_bump_epoch(m->d_epoch, st), LLAMAHIP_ERR_PREDICT);
     }
-    int32_t *state = (io && io->state) ? io->state : m->d_state;
-    const float *x_first = (io && fused && m->l1 > m->l0) ? io->x_first : nullptr;
-    float *x_last = (io && fused && m->l1 > m->l0) ? io->x_last : nullptr;
-    // decode: the producer of every residual-stream row (embedding, wo and w2 mat-vecs) hands {sum, sum of
-    // squares} of the row to the norm-fused mat-vec that consumes it, which then needs no reduction of its own
-    // (k_gemv PREP_NORMP).  LLAMAHIP_NORM_MODE=0 / 1 restore the self-contained prologues (measurement only).
-    const bool no_norm_part = !norm_mode_resolve();
-    const bool use_part = fused && m->w13_interleaved && !no_norm_part;
-    int n_part_x = 0;                                       // pairs in npart_a valid for the row currently in x (0: none)
-    // decode: wq|wk|wv + attention as one launch with tagged hand-offs (k_qkv_attn); one forward pass = one epoch
-    // (long contexts: soft_max . V is a bandwidth problem of its own there -- separate mat-vec, k_dec_scores, k_dec_pv_stream)
-    const bool long_attn = fused && m->attn_sched == 2 && pv_stream_applies((int) (d / H), (int) C, nth);
-    const bool two_attn = fused && (m->attn_sched == 1 || (m->attn_sched == 2 && !long_attn));
-    const bool use_qkvx = !long_attn && !two_attn && fused && m->d_attn_sync && m->l1 > m->l0 && m->l1 - m->l0 <= TAG_MAX_LAYERS && qkv_attn_applies(m->layers[0].qkv, d, H, nth);
-    const bool pv_split = long_attn && m->d_pvx && m->l1 - m->l0 <= TAG_MAX_LAYERS;          // (its tags are (epoch, layer) too)
-    // w1|w3 in half-block workgroups (balanced over the CUs; the halves of a block exchange their amax inside one XCD): needs the XCD
-    // placement the load-time self-test confirmed (d_attn_sync) and the epoch for its tags
-    const bool use_w13h = fused && m->w13_interleaved && m->d_attn_sync && m->d_w13_amax && m->l1 > m->l0 && m->l1 - m->l0 <= TAG_MAX_LAYERS && gemv_silu_half_applies(m->layers[0].w13);
-    const bool use_epoch = use_qkvx || pv_split || use_w13h;
-    if (use_epoch && !(m->first_stage && use_part)) HIP_TRY(launch_bump_epoch(m->d_epoch, st), LLAMAHIP_ERR_PREDICT);
-    if (io && fused && io->mb_token && m->first_stage && !use_part) { set_err(err, err_cap, "pipeline mailboxes need the default norm-statistics mode (LLAMAHIP_NORM_MODE unset)"); return LLAMAHIP_ERR_PREDICT; }
-    const bool fold = io && io->fold_pick && fused && use_part && m->first_stage && m->last_stage;
-    if (m->first_stage && fold) {
-        n_part_x = 1;               // x, npart_a and the epoch were left by the previous step's lm head (or by decode_greedy's first embedding launch)
-    } else
-    if (m->first_stage) {
-        if (use_part) {
-            HIP_TRY(launch_embed_part((io && io->token) ? io->token : m->tok_src ? m->tok_src : m->d_tokens, m->tok_emb, m->x, d, m->npart_a, st, use_epoch ? m->d_epoch : nullptr, nullptr,
-                                      (io && fused) ? io->mb_token : nullptr, state, m->d_fault, hp.n_vocab), LLAMAHIP_ERR_PREDICT);
-            n_part_x = 1;
-        } else
-        HIP_TRY(launch_embed((io && io->token) ? io->token : m->tok_src ? m->tok_src : m->d_tokens, m->tok_emb, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);      // .mm:558-561
-    } else if (!x_first && !(io && fused && io->mb_in)) {
-        HIP_TRY(hipMemcpyAsync(m->x, hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
-    }
-    // pipeline mailboxes (fused single-token steps only): the first layer's row arrives / the last layer's row leaves as tagged granules
-    static const int mb_test = getenv("LLAMAHIP_HANDOFF_FAULT_TEST") ? atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) : 0;      // 3: the last layer publishes a tag nobody waits for (test only)
-    MailboxIO mb_first, mb_last;
-    const bool has_mb_in = io && fused && io->mb_in && m->l1 > m->l0, has_mb_out = io && fused && io->mb_out && m->l1 > m->l0;
-    if (has_mb_in) { mb_first.in_t = io->mb_in; mb_first.resid_t = io->mb_in; mb_first.pos_w = state; mb_first.epoch = m->d_epoch; mb_first.fault = m->d_fault; mb_first.test_bits = mb_test ? 0x1000 : 0; }
-    if (has_mb_out) { mb_last.out_t = io->mb_out; mb_last.pos_w = state; mb_last.epoch = m->d_epoch; mb_last.fault = m->d_fault; mb_last.test_bits = mb_test == 3 ? 0x2000 : 0; }
+    if (m->first_stage) HIP_TRY(launch_embed(p.tokens, m->tok_emb, m->x, d, N, st), LLAMAHIP_ERR_PREDICT);      // .mm:558-561
+    else HIP_TRY(hipMemcpyAsync(m->x, p.hidden_in, (size_t) N * d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
 
     for (int il = m->l0; il < m->l1; il++) {
         const Layer &L = m->layers[il - m->l0];
-        const size_t kv_at = ((size_t) m->cur_seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
+        const size_t kv_at = ((size_t) p.seq * (m->l1 - m->l0) + (il - m->l0)) * C * d;
         float *Kl = m->Kc + kv_at, *Vl = m->Vc + kv_at;
-        const bool dmp = debug && il == dump_layer;
-
-        if (fused) {
-            // ---- decode: activation preparation lives in GEMV prologues / producer epilogues;
-            // the context position is read from m->d_state by the attention kernels
-            const float *xa = (il == m->l0 && x_first) ? x_first : m->x;      // residual stream into this layer
-            float *xo = (il == m->l1 - 1 && x_last) ? x_last : m->x;           // ... and out of it
-            NormPart np_qkv, np_wo, np_w13, np_w2;
-            if (use_part) {
-                const int pw = gemv_resid_parts(L.wo), p2 = gemv_resid_parts(L.w2);
-                if (n_part_x > 0) { np_qkv.in = m->npart_a; np_qkv.n_in = n_part_x; }
-                if (pw > 0 && pw <= NORM_PART_MAX) { np_wo.out = m->npart_b; np_w13.in = m->npart_b; np_w13.n_in = pw; }
-                n_part_x = 0;
-                if (p2 > 0 && p2 <= NORM_PART_MAX) { np_w2.out = m->npart_a; n_part_x = p2; }
-            }
-            // (mailboxes: the first layer reads its row -- norm input and residual operand -- from the tagged inbox, the last layer's w2
-            //  stores its row into the next stage's inbox; everything in between is the usual schedule)
-            const MailboxIO *mbi = (has_mb_in && il == m->l0) ? &mb_first : nullptr, *mbo = (has_mb_out && il == m->l1 - 1) ? &mb_last : nullptr;
-            if (use_qkvx) {
-                HIP_TRY(launch_qkv_attn(L.qkv, xa, L.attention_norm, np_qkv, m->d_qkv2, m->d_sc2, m->d_epoch, il - m->l0, d, H, C, nth, m->sincos, Kl, Vl, nullptr,
-                                        m->qa1_A, m->qa1_d, m->T_silu, m->T_exp, state, m->d_fault, st, mbi), LLAMAHIP_ERR_PREDICT);
-            } else {
-            HIP_TRY(launch_gemv(L.qkv, PREP_NORM, EPI_STORE, nullptr, nullptr, xa, L.attention_norm, m->qkv, nullptr, m->T_silu, nullptr, nullptr, st, &np_qkv, mbi), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, nullptr, m->qa1_A, m->qa1_d, m->T_exp, state, st, two_attn ? nullptr : m->d_attn_sync, m->d_fault, long_attn,
-                                    pv_split ? m->d_pvx : nullptr, m->d_epoch, il - m->l0), LLAMAHIP_ERR_PREDICT);
-            }
-            HIP_TRY(launch_gemv(L.wo, PRE_QA, EPI_RESID, m->qa1_A, m->qa1_d, nullptr, nullptr, m->x1, xa, m->T_silu, nullptr, nullptr, st, &np_wo, mbi), LLAMAHIP_ERR_PREDICT);
-            if (m->w13_interleaved) {
-                if (use_w13h) HIP_TRY(launch_gemv_silu_half(L.w13, m->x1, L.ffn_norm, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13, m->d_w13_amax, m->d_epoch, il - m->l0, m->d_fault), LLAMAHIP_ERR_PREDICT);
-                else
-                HIP_TRY(launch_gemv(L.w13, PREP_NORM, EPI_SILU_QA, nullptr, nullptr, m->x1, L.ffn_norm, nullptr, nullptr, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13), LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(launch_gemv(L.w2, PRE_QA, EPI_RESID, m->qa2_A, m->qa2_d, nullptr, nullptr, mbo ? nullptr : xo, m->x1, m->T_silu, nullptr, nullptr, st, &np_w2, mbo), LLAMAHIP_ERR_PREDICT);
-            } else {
-                if (mbo) { set_err(err, err_cap, "pipeline mailboxes need the interleaved w1|w3 layout"); return LLAMAHIP_ERR_PREDICT; }
-                HIP_TRY(launch_gemv(L.w13, PREP_NORM, EPI_STORE, nullptr, nullptr, m->x1, L.ffn_norm, m->gu, nullptr, m->T_silu, nullptr, nullptr, st), LLAMAHIP_ERR_PREDICT);
-                HIP_TRY(launch_gemv(L.w2, PREP_SILU_MUL, EPI_RESID, nullptr, nullptr, m->gu, m->gu + F, xo, m->x1, m->T_silu, nullptr, nullptr, st), LLAMAHIP_ERR_PREDICT);
-            }
-            continue;
-        }
-
-        // ---- general path (prompt chunks, debug dumps): prepare -> GEMM per mat-mul
+        const bool dmp = debug && il == p.dump_layer;
+        const bool short_layer = short_chunk && !dmp;        // (a dumped layer runs every operator on its own)
         if (dmp && !sink->put(0, m->x, (int64_t) N * d)) goto dump_fail;
         HIP_TRY(launch_prep(PREP_NORM, m->x, L.attention_norm, d, 0, d, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);   // .mm:570-575
         if (dmp && !sink->put(1, m->dbg_y, (int64_t) N * d)) goto dump_fail;
-        const bool rope_fused = short_chunk && !dmp && gemm_rope_kv_applies(L.qkv, N, d);
+        const bool rope_fused = short_layer && gemm_rope_kv_applies(L.qkv, N, d);
         if (rope_fused) {
             // short evals: q / k / v mat-mul, RoPE and the KV append in one launch (.mm:580-611)
             const RopeKvArgs ra = { m->sincos, m->qr, Kl, Vl, n_past, d, dh };
@@ -804,7 +811,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
         }
         if (!rope_fused) HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);        // .mm:586-611
         if (dmp && !sink->put(5, m->qr, (int64_t) N * d)) goto dump_fail;
-        if (short_chunk && !dmp) {
+        if (short_layer) {
             // the reference's n_batch = 8 prompt flow: per-row decode-style attention that also quantizes
             // the merged rows for wo (scores scratch: the many-row path's score matrix)
             HIP_TRY(launch_attn_short(m->qr, Kl, Vl, m->attn_ws.S, nullptr, m->qa_A, m->qa_d, n_past, N, d, H, C, nth, m->T_exp, st, chunk), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
@@ -827,7 +834,7 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
         }
         HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);        // .mm:660-665
         if (dmp && !sink->put(11, m->dbg_y, (int64_t) N * d)) goto dump_fail;
-        if (short_chunk && !dmp && m->w13_interleaved && N <= 64 && gemm_silu_qa_applies(L.w13, N)) {
+        if (short_layer && m->w13_interleaved && N <= 64 && gemm_silu_qa_applies(L.w13, N)) {
             // short evals: w1 | w3, SiLU * up and the quantization for w2 in one launch (.mm:668-680)
             const long KpF = ((long) F + 255) / 256 * 256;
             set_hx.layer = il - m->l0;
@@ -857,22 +864,12 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
     if (m->last_stage) {
         // final norm + lm head (.mm:695-705).  The reference multiplies all N rows and keeps the
         // last (.mm:724-725); only the last row is computed here unless every row is requested.
-        const int V = hp.n_vocab;
-        if (fused) {
-            NormPart np_out;
-            if (n_part_x > 0 && m->l1 > m->l0) { np_out.in = m->npart_a; np_out.n_in = n_part_x; }      // (x_last is null on the last stage: the row is in m->x)
-            if (fold) {
-                const PickIO pk = { m->d_pick + 128, (uint32_t *) m->d_pick, io->pick_out, io->pick_next, state, m->tok_emb, m->x, m->npart_a,
-                                    (m->d_attn_sync || m->d_pvx || m->d_w13_amax) ? m->d_epoch : nullptr, V };      // (the NEXT step's epoch: its schedule may use the tags even if this one does not)
-                HIP_TRY(launch_gemv_pick(m->output, m->x, m->norm_w, m->logits, m->T_silu, st, &np_out, pk), LLAMAHIP_ERR_PREDICT);
-            } else
-            HIP_TRY(launch_gemv(m->output, PREP_NORM, EPI_STORE, nullptr, nullptr, m->x, m->norm_w, m->logits, nullptr, m->T_silu, nullptr, nullptr, st, &np_out), LLAMAHIP_ERR_PREDICT);
-        } else if (want_all) {
+        if (p.want_all) {
             HIP_TRY(launch_prep(PREP_NORM, m->x, m->norm_w, d, 0, d, N, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
             // (the scoring entry points: with `output`'s prompt copies and the operand workspace; llamahip_eval_debug: the decode tiles only)
             QMat out = m->output;
-            if (!m->score_rows) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }
-            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st, m->score_rows ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
+            if (!p.score_rows) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }
+            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st, p.score_rows ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_prep(PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
             HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
@@ -883,6 +880,15 @@ int forward(llamahip_model *m, int n_threads, int n_past, int N, const float *hi
 dump_fail:
     set_err(err, err_cap, "HIP error while copying debug dump");
     return LLAMAHIP_ERR_PREDICT;
+}
+
+// which of the three schedules a pass takes: fixed by the handle and the pass before anything is launched
+int forward(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
+    const bool debug = p.dump_layer >= 0 && p.sink;
+    if (m->dense && debug) { set_err(err, err_cap, "per-layer dumps are available for Q4_0 models only"); return LLAMAHIP_ERR_PREDICT; }
+    if (m->dense) return forward_dense(m, p, err, err_cap);
+    if (p.N == 1 && !debug && !(m->flags & LLAMAHIP_FLAG_UNFUSED)) return forward_decode(m, p, err, err_cap);
+    return forward_eval(m, p, err, err_cap);
 }
 
 // Every tagged hand-off is a bounded poll; one that runs out raises the sticky fault word (results are invalid then).
@@ -1194,16 +1200,18 @@ static int eval_impl(llamahip_model *m, int32_t n_threads, int32_t n_past,
     const bool tok_mapped = N == 1 && m->h_io != nullptr;          // (the stream is idle here: every entry point synchronises before it returns)
     if (tok_mapped) m->h_io->tok[0] = tokens[0];
     else HIP_TRY(hipMemcpyAsync(m->d_tokens, tokens, (size_t) N * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+    Pass pass(m);
+    pass.n_threads = n_threads; pass.n_past = n_past; pass.N = N; pass.chunk = chunk;
+    pass.want_all = logits_all != nullptr;
     DumpSink sink;
     if (dump_layer >= 0 && dump && dump_sizes) {
         sink.dump = dump; sink.cap = dump_cap; sink.sizes = dump_sizes; sink.st = m->stream;
         for (int i = 0; i < 17; i++) dump_sizes[i] = 0;
+        pass.dump_layer = dump_layer; pass.sink = &sink;
     }
-    const bool want_all = logits_all != nullptr;
-    m->tok_src = tok_mapped ? m->d_io->tok : nullptr;
-    m->attn_sched = N == 1 ? attn_sched_at(m, n_past) : 0;
-    rc = forward(m, n_threads, n_past, N, nullptr, false, want_all, sink.dump ? dump_layer : -1, sink.dump ? &sink : nullptr, err, err_cap, nullptr, chunk);
-    m->tok_src = nullptr;
+    if (tok_mapped) pass.tokens = m->d_io->tok;
+    if (N == 1) pass.attn_sched = attn_sched_at(m, n_past);
+    rc = forward(m, pass, err, err_cap);
     m->last_rows.clear();
     if (rc) return rc;
     const size_t V = m->hp.n_vocab;
@@ -1320,11 +1328,12 @@ static int eval_stage_enqueue(llamahip_model *m, int32_t n_threads, int32_t n_pa
     const bool all = want_all && m->last_stage;
     if (all) ensure_output_copies(m, N);
     if (m->first_stage) HIP_TRY(hipMemcpyAsync(m->d_tokens, tokens, (size_t) N * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
-    m->attn_sched = N == 1 ? attn_sched_at(m, n_past) : 0;
-    m->score_rows = all;
-    rc = forward(m, n_threads, n_past, N, (const float *) hidden_in, false, all, -1, nullptr, err, err_cap, nullptr, chunk);
-    m->score_rows = false;
-    m->last_rows.clear();                                                 // (m->logits rewritten: llamahip_stage_logits rows are this eval's rows again)
+    Pass pass(m);
+    pass.n_threads = n_threads; pass.n_past = n_past; pass.N = N; pass.chunk = chunk; pass.hidden_in = (const float *) hidden_in;
+    pass.want_all = pass.score_rows = all;
+    if (N == 1) pass.attn_sched = attn_sched_at(m, n_past);
+    rc = forward(m, pass, err, err_cap);
+    m->last_rows.clear();                                                // (m->logits rewritten: llamahip_stage_logits rows are this eval's rows again)
     return rc;
 }
 
@@ -1369,9 +1378,12 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
         const int32_t hs[2] = { n_past, 0 };
         HIP_TRY(hipMemcpyAsync(m->d_state, hs, sizeof(hs), hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
     }
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     // (f16 / f32 / Q4_1 models: the un-fused single-row schedule is position-free as well, so it is captured too)
     const bool fusable = !(m->flags & LLAMAHIP_FLAG_UNFUSED) || m->dense;
+    Pass pass(m);
+    pass.n_threads = n_threads;
+    pass.state_on_device = fusable;       // (published above, advanced by the pick; the un-fused Q4_0 pass takes n_past from the host)
     if (fusable && !(m->flags & LLAMAHIP_FLAG_NO_GRAPH)) {
         // One decode step (embed -> layers -> lm head -> argmax) captured once per n_threads value.
         // Nothing in it depends on the step: position and token slots live in device memory and
@@ -1381,21 +1393,20 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
         static const bool no_fold = getenv("LLAMAHIP_NO_PICK_FOLD") != nullptr;
         const bool norm_default = norm_mode_resolve();
         const bool fold = !no_fold && norm_default && !m->dense && !(m->flags & LLAMAHIP_FLAG_UNFUSED) && m->w13_interleaved && m->l1 > m->l0 && gemv_pick_applies(m->output);
-        StepIO pio;
-        pio.fold_pick = true; pio.pick_out = m->d_out_tokens; pio.pick_next = m->d_tokens;
+        pass.fold_pick = fold; pass.pick_out = m->d_out_tokens; pass.pick_next = m->d_tokens;
         if (fold) {
             // the first token's row, statistics and epoch (what k_embed_part does at the head of an un-folded step)
             const bool ep = m->d_attn_sync || m->d_pvx || m->d_w13_amax;
             HIP_TRY(launch_embed_part(m->d_tokens, m->tok_emb, m->x, m->hp.n_embd, m->npart_a, m->stream, ep ? m->d_epoch : nullptr), LLAMAHIP_ERR_PREDICT);
         }
         for (int i = 0; i < n_steps; i++) {
-            m->attn_sched = attn_sched_at(m, n_past + i);
-            const int gkey = nth * 4096 + m->cur_seq + (m->attn_sched << 24) + (fold ? 1 << 27 : 0);
+            pass.attn_sched = attn_sched_at(m, n_past + i);
+            const int gkey = nth * 4096 + m->cur_seq + (pass.attn_sched << 24) + (fold ? 1 << 27 : 0);
             auto *g = m->decode_graphs.find(gkey);
             if (!g) {
                 hipGraphExec_t exec = nullptr;
                 rc = capture_step(m, [&]() -> int {
-                    const int r = forward(m, nth, 0, 1, nullptr, true, false, -1, nullptr, err, err_cap, fold ? &pio : nullptr);
+                    const int r = forward(m, pass, err, err_cap);
                     if (r || fold) return r;
                     HIP_TRY(launch_argmax(m->logits, m->hp.n_vocab, m->d_out_tokens, 0, m->d_tokens, m->d_state, m->stream), LLAMAHIP_ERR_PREDICT);
                     return 0;
@@ -1407,8 +1418,9 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
         }
     } else {
         for (int i = 0; i < n_steps; i++) {
-            m->attn_sched = attn_sched_at(m, n_past + i);
-            rc = forward(m, n_threads, n_past + i, 1, nullptr, fusable, false, -1, nullptr, err, err_cap);
+            pass.n_past = n_past + i;
+            pass.attn_sched = attn_sched_at(m, n_past + i);
+            rc = forward(m, pass, err, err_cap);
             if (rc) return rc;
             // argmax feeds the next step's token slot (and advances the position) on the device
             HIP_TRY(launch_argmax(m->logits, m->hp.n_vocab, m->d_out_tokens, i, m->d_tokens, m->d_state, m->stream), LLAMAHIP_ERR_PREDICT);
@@ -1558,34 +1570,33 @@ int llamahip_stage_mailbox_connect(llamahip_model *m, int32_t seq, const void *n
 }
 
 namespace {
-// the launches of one stage step, issued on m->stream (directly or under capture)
-static int stage_step_launches(llamahip_model *m, int seq, int nth, char *err, size_t err_cap) {
+// the launches of one stage step, issued on `st` (the caller's stream, or the handle's under capture)
+static int stage_step_launches(llamahip_model *m, int seq, int nth, int attn_sched, hipStream_t st, char *err, size_t err_cap) {
     auto &sl = m->slots[seq];
     int32_t *state = m->d_slot_state + 2 * seq;
-    StepIO io;
-    io.token = sl.token_in; io.state = state;
-    io.x_first = m->first_stage ? nullptr : sl.hidden_in;
-    io.x_last = m->last_stage ? nullptr : sl.hidden_out;
+    Pass pass(m);
+    pass.n_threads = nth; pass.hidden_in = sl.hidden_in; pass.seq = seq; pass.stream = st;
+    pass.state_on_device = true; pass.state = state; pass.attn_sched = attn_sched;
+    if (sl.token_in) pass.tokens = sl.token_in;
+    pass.x_first = m->first_stage ? nullptr : sl.hidden_in;
+    pass.x_last = m->last_stage ? nullptr : sl.hidden_out;
     // a slot bound WITHOUT hidden buffers runs on its mailboxes; one bound with them keeps the caller-ordered buffers (RCCL schedule)
     // even if mailboxes exist -- the way back when the mailbox handshake of a multi-GPU run fails
     const bool mb_mode = (m->first_stage || !sl.hidden_in) && (m->last_stage || !sl.hidden_out) && !(m->first_stage && m->last_stage);
-    io.mb_in = (mb_mode && !m->first_stage) ? sl.inbox_hidden : nullptr;
-    io.mb_out = (mb_mode && !m->last_stage) ? sl.peer_hidden : nullptr;
-    io.mb_token = (mb_mode && m->first_stage) ? sl.inbox_token : nullptr;
+    pass.mb_in = (mb_mode && !m->first_stage) ? sl.inbox_hidden : nullptr;
+    pass.mb_out = (mb_mode && !m->last_stage) ? sl.peer_hidden : nullptr;
+    pass.mb_token = (mb_mode && m->first_stage) ? sl.inbox_token : nullptr;
     uint64_t *mb_token_out = (mb_mode && m->last_stage) ? sl.peer_token : nullptr;
-    const int save_seq = m->cur_seq;
-    m->cur_seq = seq;
-    int rc = forward(m, nth, 0, 1, sl.hidden_in, true, false, -1, nullptr, err, err_cap, &io);
-    m->cur_seq = save_seq;
+    int rc = forward(m, pass, err, err_cap);
     if (rc) return rc;
     const size_t d = m->hp.n_embd;
     if (!m->last_stage && m->l1 == m->l0)           // a stage without layers only forwards the stream
-        HIP_TRY(hipMemcpyAsync(sl.hidden_out, m->x, d * 4, hipMemcpyDeviceToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(sl.hidden_out, m->x, d * 4, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
     if (m->last_stage) {
         // greedy pick on the device: trace[step] = token; token_out (if any) = token; position advances
-        HIP_TRY(launch_argmax(m->logits, m->hp.n_vocab, m->d_slot_trace + (size_t) seq * m->hp.n_ctx, 0, sl.token_out, state, m->stream, mb_token_out), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_argmax(m->logits, m->hp.n_vocab, m->d_slot_trace + (size_t) seq * m->hp.n_ctx, 0, sl.token_out, state, st, mb_token_out), LLAMAHIP_ERR_PREDICT);
     } else {
-        HIP_TRY(launch_advance(state, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_advance(state, st), LLAMAHIP_ERR_PREDICT);
     }
     return 0;
 }
@@ -1596,27 +1607,23 @@ int llamahip_stage_step(llamahip_model *m, int32_t seq, int32_t n_threads, void 
     if (!m) { set_err(err, err_cap, "null model"); return LLAMAHIP_ERR_PREDICT; }
     if (seq < 0 || seq >= (int32_t) m->slots.size() || !m->slots[seq].bound) { set_err(err, err_cap, "sequence slot %d is not bound (llamahip_stage_bind)", seq); return LLAMAHIP_ERR_PREDICT; }
     HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     hipStream_t run_on = (hipStream_t) stream;          // NULL = the null stream, as everywhere in HIP
     auto &sl = m->slots[seq];
     if (sl.next_pos >= m->hp.n_ctx) { set_err(err, err_cap, "context overflow: n_past (%d) + n_tokens (1) > n_ctx (%d)", sl.next_pos, m->hp.n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    const int attn_sched = attn_sched_at(m, sl.next_pos);
     if (m->flags & LLAMAHIP_FLAG_NO_GRAPH) {
-        m->attn_sched = attn_sched_at(m, sl.next_pos);
-        hipStream_t own = m->stream;
-        m->stream = run_on;
-        int rc = stage_step_launches(m, seq, nth, err, err_cap);
-        m->stream = own;
+        const int rc = stage_step_launches(m, seq, nth, attn_sched, run_on, err, err_cap);
         if (rc) return rc;
     } else {
-        m->attn_sched = attn_sched_at(m, sl.next_pos);
-        const int gkey = nth + (m->attn_sched << 16);
+        const int gkey = nth + (attn_sched << 16);
         auto *g = sl.graphs.find(gkey);
         if (!g) {
             // One step of this stage (embed | stream in -> layers -> stream out | lm head + argmax)
             // captured once per (slot, n_threads); the position lives in device memory and the last
             // node advances it, so the same executable graph is replayed for every token.
             hipGraphExec_t exec = nullptr;
-            const int rc = capture_step(m, [&]() { return stage_step_launches(m, seq, nth, err, err_cap); }, &exec, err, err_cap);
+            const int rc = capture_step(m, [&]() { return stage_step_launches(m, seq, nth, attn_sched, m->stream, err, err_cap); }, &exec, err, err_cap);
             if (rc) return rc;
             g = sl.graphs.put(gkey, exec);
         }
@@ -1629,17 +1636,16 @@ int llamahip_stage_step(llamahip_model *m, int32_t seq, int32_t n_threads, void 
 }
 
 namespace {
-// One decode step for B rows = B sequences (device-resident descriptor `d_set`): the 2..60-row schedule of forward() -- every operator of
+// One decode step for B rows = B sequences (device-resident descriptor `d_set`): the 2..60-row schedule of forward_eval -- every operator of
 // llama_eval's graph works row by row (.mm:563-705), so row b is bit for bit a single-token llama_eval of its sequence: its own
 // position in RoPE / the KV append / the causal range, its own cache, and the V*P key split of ITS eval, n_past_b + 1 keys over
 // n_threads (ggml.c:5459-5480).  The weights are streamed once per step for all rows.
 // (tail = false, a verify step over a set: the rows stay where they are -- logits on the last stage, m->x on the others -- and no slot advances)
 // f16 / f32 files: the same step on the dense schedule of forward_dense -- per mat-mul k_dense_prep + the few-row dense mat-mul (one pass over
 // the weights for all rows: launch_dense_mm), RoPE and the KV append per row of the set (k_rope_kv_set), launch_attn_short with fp32 merged rows
-static int forward_dense_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys, bool tail) {
+static int forward_dense_set(llamahip_model *m, int nth, SeqSet *d_set, int B, hipStream_t st, char *err, size_t err_cap, int set_keys, bool tail) {
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
-    hipStream_t st = m->stream;
     if (m->first_stage) HIP_TRY(launch_embed_dense_set(d_set, B, m->tok_emb, hp.f16, m->x, d, st), LLAMAHIP_ERR_PREDICT);                          // .mm:558-561
     else HIP_TRY(launch_rows_set(d_set, B, m->x, d, true, st), LLAMAHIP_ERR_PREDICT);
     for (int il = m->l0; il < m->l1; il++) {
@@ -1661,13 +1667,12 @@ static int forward_dense_set(llamahip_model *m, int nth, SeqSet *d_set, int B, c
     }
     return 0;
 }
-static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, char *err, size_t err_cap, int set_keys = 0, bool tail = true) {
-    if (m->dense) return forward_dense_set(m, nth, d_set, B, err, err_cap, set_keys, tail);
+static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, hipStream_t st, char *err, size_t err_cap, int set_keys = 0, bool tail = true) {
+    if (m->dense) return forward_dense_set(m, nth, d_set, B, st, err, err_cap, set_keys, tail);
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
-    hipStream_t st = m->stream;
     const long KpF = ((long) F + 255) / 256 * 256;
-    SiluHalfIO set_hx;          // (see forward(): the half-block w1|w3 launch of k_gemv_set; the step's first launch opens the epoch)
+    SiluHalfIO set_hx;          // (see forward_eval: the half-block w1|w3 launch of k_gemv_set; the step's first launch opens the epoch)
     if (m->d_attn_sync && m->d_set_amax && m->l1 - m->l0 <= TAG_MAX_LAYERS) { set_hx.amax_t = m->d_set_amax; set_hx.epoch = m->d_epoch; set_hx.fault = m->d_fault; }
     if (m->first_stage) HIP_TRY(launch_embed_set(d_set, B, m->tok_emb, m->x, d, st, set_hx.amax_t ? m->d_epoch : nullptr), LLAMAHIP_ERR_PREDICT);                // .mm:558-561
     else HIP_TRY(launch_rows_set(d_set, B, m->x, d, true, st, set_hx.amax_t ? m->d_epoch : nullptr), LLAMAHIP_ERR_PREDICT);
@@ -1709,7 +1714,7 @@ int32_t llamahip_stage_set_applies(const llamahip_model *m, int32_t n_seqs, int3
     if (!m || m->host_only || n_seqs < 1 || n_seqs > SET_MAX) return 0;
     if (n_seqs == 1) return 1;
     const int d = m->hp.n_embd, H = m->hp.n_head, dh = H > 0 ? d / H : 0;
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     if ((m->flags & LLAMAHIP_FLAG_UNFUSED) || m->l1 <= m->l0 || dh <= 0 || dh % 32 != 0 || dh > 256 || nth > 32) return 0;
     if (m->dense) return dense_stage_steps(m) ? 1 : 0;      // (f16 / f32 whole-model handles: the few-row dense mat-mul takes every width the loader takes)
     return gemm_rope_kv_applies(m->layers[0].qkv, n_seqs, d) ? 1 : 0;
@@ -1722,7 +1727,7 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
     if (n_seqs == 1) return llamahip_stage_step(m, seqs[0], n_threads, stream, err, err_cap);
     const HParams &hp = m->hp;
     const int d = hp.n_embd, H = hp.n_head, dh = d / H, C = hp.n_ctx;
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     for (int i = 0; i < n_seqs; i++) {
         const int sq = seqs[i];
         if (sq < 0 || sq >= (int32_t) m->slots.size() || !m->slots[sq].bound) { set_err(err, err_cap, "sequence slot %d is not bound (llamahip_stage_bind)", sq); return LLAMAHIP_ERR_PREDICT; }
@@ -1784,7 +1789,7 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
         HIP_TRY(m->own.alloc(&sg.d_set, 1), LLAMAHIP_ERR_PREDICT);
         if (hipMemcpy(sg.d_set, &hs, sizeof(SeqSet), hipMemcpyHostToDevice) != hipSuccess) { m->own.release(&sg.d_set); set_err(err, err_cap, "HIP error copying the set descriptor"); return LLAMAHIP_ERR_PREDICT; }
         if (!(m->flags & LLAMAHIP_FLAG_NO_GRAPH) &&
-            (rc = capture_step(m, [&]() { return forward_set(m, nth, sg.d_set, n_seqs, err, err_cap, set_keys); }, &exec, err, err_cap)) != 0) {
+            (rc = capture_step(m, [&]() { return forward_set(m, nth, sg.d_set, n_seqs, m->stream, err, err_cap, set_keys); }, &exec, err, err_cap)) != 0) {
             m->own.release(&sg.d_set);
             return rc;
         }
@@ -1795,13 +1800,7 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
     m->last_rows.assign(n_seqs, 0);
     for (int i = 0; i < n_seqs; i++) m->last_rows[i] = (int) (std::lower_bound(order.begin(), order.end(), seqs[i]) - order.begin());
     if (g->exec) HIP_TRY(hipGraphLaunch(g->exec, run_on), LLAMAHIP_ERR_PREDICT);
-    else {
-        hipStream_t own = m->stream;
-        m->stream = run_on;
-        rc = forward_set(m, nth, g->d_set, n_seqs, err, err_cap, set_keys);
-        m->stream = own;
-        if (rc) return rc;
-    }
+    else if ((rc = forward_set(m, nth, g->d_set, n_seqs, run_on, err, err_cap, set_keys)) != 0) return rc;
     for (int i = 0; i < n_seqs; i++) m->slots[seqs[i]].next_pos++;
     m->n_evals += n_seqs;
     return LLAMAHIP_OK;
@@ -2336,7 +2335,7 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
 static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, const float *hidden_in, char *err, size_t err_cap) {
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab, R = rp.R;
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     hipStream_t st = m->stream;
     int rc = rows_upload(m, rp, err, err_cap);
     if (rc) return rc;
@@ -3216,7 +3215,7 @@ static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &sta
     llamahip_model *first = stages[0], *last = stages[S - 1];
     const int C = m->hp.n_ctx, V = m->hp.n_vocab;
     const size_t d = m->hp.n_embd;
-    const int nth = std::max(1, std::min(n_threads, 64));
+    const int nth = clamp_threads(n_threads);
     int rc, max_pos = 0;
     for (int g = 0; g < G; g++) max_pos = std::max(max_pos, rq.pos[g] + rq.seg_begin[g + 1] - rq.seg_begin[g] - 1);
     if (R < 2 || R > SET_MAX || G < 1 || G > R || max_pos >= C) { set_err(err, err_cap, "verify step over a set: %d rows in %d segments up to position %d", R, G, max_pos); return LLAMAHIP_ERR_PREDICT; }
@@ -3248,7 +3247,7 @@ static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &sta
         // (pinned: stream-ordered; else the synchronous copy, done before the launches below are enqueued)
         if ((st->h_io ? hipMemcpyAsync(dv, hb, offsetof(VsetBlock, pick), hipMemcpyHostToDevice, st->stream)
                       : hipMemcpy(dv, hb, offsetof(VsetBlock, pick), hipMemcpyHostToDevice)) != hipSuccess) { set_err(err, err_cap, "HIP error copying the step descriptor"); return bail(LLAMAHIP_ERR_PREDICT); }
-        if ((rc = forward_set(st, nth, &dv->set, R, err, err_cap, set_keys, false)) != 0) return bail(rc);
+        if ((rc = forward_set(st, nth, &dv->set, R, st->stream, err, err_cap, set_keys, false)) != 0) return bail(rc);
         if (s + 1 < S && (rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) R * d * 4, err, err_cap)) != 0) return bail(rc);
     }
     HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
