@@ -629,8 +629,49 @@ int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n
  *   decode-only step that carries a draft is a mixed pass, not the captured set step.  Drafting pays from an acceptance rate of 0.44 on this
  *   workload (interpolated); below it, leave draft_len at 0, the default.  draft_len == 0 against the parent commit's library, fresh processes,
  *   interleaved, five each: 2321 against 2324 tokens/s, inside the parent's own spread of 19.
- * Not built: prefix copy between slots; the scheduler behind llama_runner; more than 16 active sequences; a set-step-descriptor form for
- *   decode-only drafted steps; drafts counted against row_budget;
+ * Evaluated prompt prefixes shared between KV slots (llamahip_sched_opts.prefix_share = 1; off by default).  Every operator of
+ *   an eval works row by row except the V.P key split, which depends on the eval a row belongs to: in a prompt evaluated by
+ *   llamahip_eval_chunks with chunk_tokens = c > 0, row j has min(N, (j / c + 1) * c) keys (llamahip_eval_multi_rows).  For two prompts and a
+ *   multiple P of c that is no larger than their common prefix and smaller than both lengths, every row j < P has the same tokens [0 .. j],
+ *   the same position and the same key count (j / c + 1) * c <= P in both: the K and V rows [0, P) of every layer are the same bits, and a
+ *   request that takes them over and evaluates the rest in pieces from offset P (what the step rule does for every later piece anyway) ends
+ *   with exactly the rows its own llamahip_eval_chunks from 0 would have written.  A K row carries its position's rotation: a copy keeps the
+ *   row index, only the slot changes.  NOT shareable, and never shared: rows written by decode or verify steps (keyed as single-token evals),
+ *   anything at chunk_tokens == 0 (every row's key count is its prompt's length), rows of a LLAMAHIP_FLAG_FAST_PREFILL handle (no parity
+ *   claim), the new prompt's last token (one row must be evaluated for the first logits).
+ *   Held records.  With the option on the scheduler remembers per slot the occupant's prompt and how many of its rows are evaluated prompt
+ *   rows (the request's offset; the whole prompt once it decodes).  The record outlives the request's DONE or cancel until the slot's next
+ *   occupant replaces it; decode and draft rows lie at and above the prompt's end and never enter it.
+ *   The policy (llamahip_sched_plan_prefix; host only, pure -- the one place it lives).  held / n_held[s]: the records, concatenated.
+ *   share(s) = floor(min(lcp(prompt, held_s), n_held[s], n_prompt - 1) / c) * c, 0 for c == 0.  The slot: among the free ones the largest
+ *   share(s) -- those rows are in place, nothing moves -- ties to the smallest n_held[s] (an empty slot loses nothing), then to the lowest
+ *   index (with nothing held anywhere: lowest slot first, as without the option).  The donor: over all OTHER slots, free or active, the largest
+ *   share(t), ties to the lowest index; if it exceeds the in-place share, *donor_out = t, rows [*n_inplace_out, share(t)) are to be copied
+ *   and share(t) is returned; else *donor_out = -1 and the in-place share is returned.  -1 for bad arguments (n_slots outside 1 .. 16, no
+ *   free slot, a null array, a negative entry, n_prompt < 1, chunk_tokens < 0).
+ *   Admission, one request at a time in submission order: the plan over the records as they stand; where rows are to be copied, ONE
+ *   k_kv_copy_rows launch per stage on the stage's stream; only then the request takes the slot, starts at offset P, and the record is
+ *   replaced.  Launches are stream-ordered: a later admission of the same step may share what an earlier one copied, and the step's pass
+ *   runs behind them.  A step that fails after admissions keeps them, their slots and their shared rows.  Fall-back handles share too
+ *   (their per-slot llamahip_eval_chunks at n_past = offset is what later pieces run anyway); LLAMAHIP_FLAG_FAST_PREFILL handles and
+ *   chunk_tokens == 0 share nothing, keep no records, choose slots lowest first and report zeros.  The contract above holds unchanged,
+ *   whatever was shared from whatever donor (BY TEST: tests/test_gpu_sched_prefix.py).  Stats: n_shared_rows (prompt rows taken over, in
+ *   place or copied), n_copied_rows (of those, moved), n_copy_launches; where every request reaches DONE uncancelled,
+ *   n_prompt_rows + n_shared_rows == the sum of the prompts' lengths.  llamahip_sched_new refuses prefix_share other than 0 or 1.
+ * llamahip_kv_copy_rows -- the copy for callers who manage slots themselves (evaluate a system prompt once, broadcast it, llamahip_eval_multi
+ *   with n_past = P): for each i < n_copies the rows [row_begin[i], row_begin[i] + n_rows[i]) of EVERY layer, K and V, from slot src_slot[i]
+ *   to the same rows of slot dst_slot[i]; one source may feed many destinations; n_rows[i] == 0 is a no-op entry.  One k_kv_copy_rows launch
+ *   per stage (every stage of a pipeline handle on its own device and stream), waited for; every file type (the cache is the same fp32
+ *   array for all).  No row outside the named ranges is touched, nor the handle's current slot.  Refused before any device work, the message
+ *   naming the limit, the handle last: a null handle, n_copies outside 1 .. 16, a null array, a slot outside [0, n_seq), src == dst, a
+ *   negative count or a range outside [0, n_ctx], a slot that is the destination of one copy and the source or destination of another,
+ *   HOST_ONLY and stage handles, and while a scheduler lives on the handle a destination below its max_active.
+ *   Measured on the 7B (tools/sched_probe.py --shared-prefix 256; the figures are in profiles/sched_prefix_probe_7b.json and DESIGN.md 12.23): 64 requests
+ *   behind one 256-token system prompt run about a third faster with the option on; k_kv_copy_rows is faster than a loop of hipMemcpyAsync calls over
+ *   the same ranges for 9 rows, for 256 rows and for a 15-way broadcast; prefix_share 0 is unchanged against the parent commit's library.
+ * Not built: the scheduler behind llama_runner; more than 16 active sequences; a set-step-descriptor form for
+ *   decode-only drafted steps; drafts counted against row_budget; sharing decode rows or rows at chunk_tokens == 0; a prefix store beyond
+ *   the slots' own records;
  *   generating past n_ctx (llamahip_decode_greedy_window's overflow plan); the mixed pass on the fused few-row launches. */
 #define LLAMAHIP_SCHED_ROW_BUDGET 256     /* the candidate of 16 .. 256 with the highest median tokens/s on the probe workload: profiles/sched_probe_7b.json, DESIGN.md 12.19 */
 #define LLAMAHIP_EV_TOKEN 1
@@ -651,6 +692,8 @@ typedef struct llamahip_sched_opts {
     int32_t draft_len;       /* 0 = off; 1 .. 15 draft tokens per request and step at the most */
     int32_t ngram_min, ngram_max;              /* llamahip_lookup_draft's; 0 = LLAMAHIP_LOOKUP_NGRAM_MIN / _MAX */
     const int32_t *corpus; int32_t n_corpus;   /* optional, searched behind a request's own history; copied at llamahip_sched_new */
+    /* shared prompt prefixes (read only where struct_size covers it; a shorter struct means off) */
+    int32_t prefix_share;    /* 0 = off; 1 = a request takes over the evaluated prompt rows it has in common with a slot's record */
 } llamahip_sched_opts;
 #define LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len) ((draft_len) > 0 ? (max_active) + 17 : 2 * (max_active) + 1)   /* the smallest cap llamahip_sched_step takes */
 typedef struct llamahip_request {
@@ -674,6 +717,8 @@ typedef struct llamahip_sched_stats {
     int64_t n_draft_steps;                     /* steps that carried at least one draft row */
     int64_t n_drafted, n_accepted;             /* draft tokens evaluated; of those, reproduced by the model */
     int64_t n_emit_segs, n_dropped;            /* emitting segments over all steps; accepted tokens dropped behind a stop token */
+    int64_t n_shared_rows, n_copied_rows;      /* prompt rows taken over instead of evaluated (in place or copied); of those, moved */
+    int64_t n_copy_launches;                   /* k_kv_copy_rows launches (one per stage and copy) */
 } llamahip_sched_stats;
 int     llamahip_sched_new   (llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap);
 int     llamahip_sched_submit(llamahip_sched *s, const llamahip_request *r, int64_t *id, char *err, size_t err_cap);
@@ -690,6 +735,12 @@ int32_t llamahip_sched_plan_drafts(int32_t n_active, const int32_t *prompt_left,
 int llamahip_op_sched_accept(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *seg_tab, int32_t n_segs, const int32_t *tokens,
                              int32_t n_slots, int32_t log_cap, int32_t *state, int32_t *log, int32_t *next_tok,
                              int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
+int32_t llamahip_sched_plan_prefix(int32_t n_slots, const int32_t *slot_free, const int32_t *held /* concatenated */,
+                                   const int32_t *n_held, const int32_t *prompt, int32_t n_prompt, int32_t chunk_tokens,
+                                   int32_t *slot_out, int32_t *donor_out, int32_t *n_inplace_out);
+#define LLAMAHIP_KV_COPY_MAX 16           /* copies in one llamahip_kv_copy_rows call */
+int llamahip_kv_copy_rows(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot,
+                          const int32_t *row_begin, const int32_t *n_rows, char *err, size_t err_cap);
 
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
@@ -954,6 +1005,13 @@ typedef struct llamahip_gemv_bench {
  * timed launches).  For `output` the matrix is evicted from the Infinity Cache between launches. */
 int llamahip_bench_gemv(llamahip_model *m, int32_t which, int32_t layer, int32_t warmup, int32_t iters,
                         llamahip_gemv_bench *out, char *err, size_t err_cap);
+
+/* Times llamahip_kv_copy_rows' launch against the obvious alternative on a plain handle: `iters` times over, the copies enqueued on the
+ * handle's stream and the stream waited for -- how = 0: one k_kv_copy_rows launch; how = 1: a loop of hipMemcpyAsync device-to-device calls, one
+ * per copy, layer and array (the same ranges, the same stream).  *ms_per_call: host wall time per enqueue + wait, the mean over `iters` after
+ * one untimed call.  The arguments are llamahip_kv_copy_rows' and are refused the same way.  Measurement tooling only. */
+int llamahip_bench_kv_copy(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot, const int32_t *row_begin,
+                           const int32_t *n_rows, int32_t how, int32_t iters, double *ms_per_call, char *err, size_t err_cap);
 
 /* In-kernel phase probe of the decode GEMVs: runs n_steps greedy decode steps with the probe armed;
  * one record of 8 uint64 per GEMV launch {s_memtime at entry, loads issued, prologue done, weights

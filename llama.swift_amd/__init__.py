@@ -59,6 +59,7 @@ from .binding import (  # noqa: F401
     sched_event_cap,
     sched_plan,
     sched_plan_drafts,
+    sched_plan_prefix,
     gemv_plan,
     set_plan,
     version,

@@ -69,7 +69,8 @@ class _LookupStats(C.Structure):
 class _SchedOpts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_threads", C.c_int32), ("max_active", C.c_int32), ("chunk_tokens", C.c_int32),
                 ("row_budget", C.c_int32), ("repeat_penalty", C.c_double), ("top_p", C.c_double), ("temp", C.c_double), ("top_k", C.c_int32),
-                ("draft_len", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32), ("corpus", C.c_void_p), ("n_corpus", C.c_int32)]
+                ("draft_len", C.c_int32), ("ngram_min", C.c_int32), ("ngram_max", C.c_int32), ("corpus", C.c_void_p), ("n_corpus", C.c_int32),
+                ("prefix_share", C.c_int32)]
 
 
 class _Request(C.Structure):
@@ -87,6 +88,11 @@ class _SchedStats(C.Structure):
                 ("n_set_steps", C.c_int64), ("n_single_steps", C.c_int64), ("n_fallback_steps", C.c_int64), ("n_rows", C.c_int64),
                 ("n_prompt_rows", C.c_int64), ("n_tokens", C.c_int64), ("n_submitted", C.c_int64), ("n_done", C.c_int64),
                 ("n_draft_steps", C.c_int64), ("n_drafted", C.c_int64), ("n_accepted", C.c_int64), ("n_emit_segs", C.c_int64), ("n_dropped", C.c_int64)]
+
+
+class _SchedStatsPrefix(_SchedStats):
+    """llamahip_sched_stats as it is now: the counters of shared prompt prefixes appended behind _SchedStats' (the struct is size-versioned)"""
+    _fields_ = [("n_shared_rows", C.c_int64), ("n_copied_rows", C.c_int64), ("n_copy_launches", C.c_int64)]
 
 
 class _Stats(C.Structure):
@@ -195,7 +201,7 @@ def lib() -> C.CDLL:
     L.llamahip_sched_cancel.argtypes = [vp, C.c_int64]
     L.llamahip_sched_pending.argtypes = [vp]
     L.llamahip_sched_pending.restype = i32
-    L.llamahip_sched_get_stats.argtypes = [vp, C.POINTER(_SchedStats)]
+    L.llamahip_sched_get_stats.argtypes = [vp, vp]          # (size-versioned: _SchedStats or _SchedStatsPrefix)
     L.llamahip_sched_free.argtypes = [vp]
     L.llamahip_sched_free.restype = None
     L.llamahip_sched_plan.argtypes = [i32, vp, i32, i32, vp]
@@ -204,6 +210,10 @@ def lib() -> C.CDLL:
     L.llamahip_sched_plan_drafts.argtypes = [i32, vp, vp, vp, vp]
     L.llamahip_sched_plan_drafts.restype = i32
     L.llamahip_op_sched_accept.argtypes = [vp, i32, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_sched_plan_prefix.argtypes = [i32, vp, vp, vp, vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.llamahip_sched_plan_prefix.restype = i32
+    L.llamahip_kv_copy_rows.argtypes = [vp, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_bench_kv_copy.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, C.POINTER(C.c_double), cp, sz]
     L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
     L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
@@ -783,10 +793,20 @@ class Model:
 
     def scheduler(self, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8, repeat_penalty: float = 1.3,
                   top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), draft_len: int = 0,
-                  ngram_min: int = 0, ngram_max: int = 0, corpus=None) -> "Scheduler":
+                  ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False) -> "Scheduler":
         """llamahip_sched_new: a request scheduler over KV slots [0, max_active) of this handle (include/llamahip.h "request scheduler").
-        draft_len > 0: drafted tokens ride in the rows a step leaves spare (prompt lookup in each request's history, then `corpus`)."""
-        return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp, draft_len, ngram_min, ngram_max, corpus)
+        draft_len > 0: drafted tokens ride in the rows a step leaves spare (prompt lookup in each request's history, then `corpus`).
+        prefix_share: a request takes over the evaluated prompt rows it has in common with a slot's record instead of evaluating them."""
+        return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp, draft_len, ngram_min, ngram_max, corpus,
+                         prefix_share)
+
+    def kv_copy_rows(self, copies) -> None:
+        """llamahip_kv_copy_rows: copies = [(src slot, dst slot, first row, row count), ...], 1 .. 16 of them -- those KV rows of every layer, K
+        and V, from the source slot to the same rows of the destination slot, in one launch per stage."""
+        c = np.ascontiguousarray(copies, np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_kv_copy_rows(self._h, len(c), *(_ptr(a) for a in cols), err, len(err)), err)
 
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
@@ -829,6 +849,16 @@ class Model:
         us = b.ms_total * 1e3 / b.iters
         return {"name": bench_gemv_names[which], "M": b.M, "K": b.K, "iters": b.iters, "us_per_launch": us,
                 "algo_bytes": b.algo_bytes, "GBps": b.algo_bytes / (us * 1e-6) / 1e9}
+
+    def bench_kv_copy(self, copies, how: int, iters: int = 20) -> float:
+        """llamahip_bench_kv_copy: milliseconds per enqueue + wait of `copies` (as kv_copy_rows takes them) -- how 0: one k_kv_copy_rows launch,
+        1: a loop of hipMemcpyAsync calls over the same ranges on the same stream."""
+        c = np.ascontiguousarray(copies, np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
+        ms = C.c_double(0)
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_bench_kv_copy(self._h, len(c), *(_ptr(a) for a in cols), int(how), int(iters), C.byref(ms), err, len(err)), err)
+        return float(ms.value)
 
     def stats(self) -> dict:
         s = _Stats()
@@ -884,13 +914,13 @@ class Scheduler:
 
     def __init__(self, model: Model, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8,
                  repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)),
-                 draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0, corpus=None):
+                 draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False):
         self._s = None
         self.model, self.max_active, self.draft_len = model, int(max_active), int(draft_len)
         self._samplers = {}          # id -> Sampler: kept alive while the request may draw
         c = np.ascontiguousarray(corpus if corpus is not None else [], np.int32).ravel()          # (copied by llamahip_sched_new)
         o = _SchedOpts(C.sizeof(_SchedOpts), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k,
-                       int(draft_len), int(ngram_min), int(ngram_max), c.ctypes.data if c.size else None, c.size)
+                       int(draft_len), int(ngram_min), int(ngram_max), c.ctypes.data if c.size else None, c.size, int(prefix_share))
         h = C.c_void_p()
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_sched_new(model._h, C.byref(o), C.byref(h), err, len(err)), err)
@@ -947,9 +977,9 @@ class Scheduler:
         return int(lib().llamahip_sched_pending(self._s))
 
     def stats(self) -> dict:
-        st = _SchedStats(C.sizeof(_SchedStats))
+        st = _SchedStatsPrefix(C.sizeof(_SchedStatsPrefix))
         lib().llamahip_sched_get_stats(self._s, C.byref(st))
-        return {k: int(getattr(st, k)) for k, _ in _SchedStats._fields_ if k != "struct_size"}
+        return {k: int(getattr(st, k)) for k, _ in _SchedStats._fields_ + _SchedStatsPrefix._fields_ if k != "struct_size"}
 
     def run(self, on_done=None) -> dict:
         """step until nothing is pending; returns {id: tokens}.  on_done(event), if given, is called at each DONE event -- while the
@@ -1006,6 +1036,22 @@ def op_sched_accept(logits2d, seg_tab, tokens, state=None, log=None, next_tok=No
     _check(lib().llamahip_op_sched_accept(_ptr(logits2d), R, V, _ptr(tab), len(tab), _ptr(tokens), n_slots, log_cap,
                                           *(None if a is None else _ptr(a) for a in (state, log, next_tok)), _ptr(n_acc), _ptr(picks), err, len(err)), err)
     return n_acc[:len(tab)], picks[:R]
+
+
+def sched_plan_prefix(slot_free, held, prompt, chunk_tokens: int):
+    """llamahip_sched_plan_prefix (host only): held[s] = the prompt tokens whose KV rows slot s holds as prompt rows, slot_free[s] whether the
+    slot is free.  Returns (shared rows P, slot, donor or -1, rows already in place in that slot); P == -1 = bad arguments."""
+    free = np.ascontiguousarray(slot_free, np.int32).ravel()
+    recs = [np.ascontiguousarray(h, np.int32).ravel() for h in held]
+    if len(recs) != free.size:
+        raise ValueError(f"sched_plan_prefix: {free.size} slots, {len(recs)} records")
+    n_held = np.array([h.size for h in recs], np.int32)
+    cat = np.concatenate(recs + [np.zeros(1, np.int32)]).astype(np.int32)          # (the last entry is never read: a non-null array where nothing is held)
+    prompt = np.ascontiguousarray(prompt, np.int32).ravel()
+    slot, donor, inplace = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    P = lib().llamahip_sched_plan_prefix(free.size, _ptr(free) if free.size else None, _ptr(cat), _ptr(n_held) if free.size else None,
+                                         _ptr(prompt) if prompt.size else None, prompt.size, int(chunk_tokens), C.byref(slot), C.byref(donor), C.byref(inplace))
+    return int(P), int(slot.value), int(donor.value), int(inplace.value)
 
 
 def sched_plan(prompt_left, chunk_tokens: int, row_budget: int):

@@ -147,7 +147,11 @@ struct VsetBlock {
 // ------------------------------------------------------------------------------------------------
 // the model handle
 // ------------------------------------------------------------------------------------------------
-namespace lh { void sched_dev_orphan(SchedDev *d); }
+namespace lh {
+void sched_dev_orphan(SchedDev *d);
+int sched_dev_max_active(const SchedDev *d);          // the slots [0, max_active) a live scheduler owns (llamahip_kv_copy_rows writes none of them)
+int kv_copy_enqueue(const std::vector<llamahip_model *> &stages, const KvCopyTab &tab, const char *fn, char *err, size_t err_cap);
+}
 struct llamahip_model {
     ModelFile file;
     HParams hp;
@@ -3759,7 +3763,7 @@ int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, 
     const int rc = decode_handle_check(m, "llamahip_sched_new", err, err_cap);
     if (rc) return rc;
     const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
-    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq };
+    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq, (first->flags & LLAMAHIP_FLAG_FAST_PREFILL) ? 1 : 0 };
     return 0;
 }
 int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
@@ -3787,6 +3791,35 @@ int sched_dev_drafts(SchedDev *d) {
     if (!d || !d->m) return 0;
     sched_decide(d);
     return d->fallback ? 0 : 1;
+}
+// one k_kv_copy_rows launch per stage, each on its own device and stream; nothing is waited for
+int sched_dev_max_active(const SchedDev *d) { return d->max_active; }
+int kv_copy_enqueue(const std::vector<llamahip_model *> &stages, const KvCopyTab &tab, const char *fn, char *err, size_t err_cap) {
+    for (llamahip_model *st : stages) {
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        if (launch_kv_copy_rows(st->Kc, st->Vc, tab, st->n_seq, st->l1 - st->l0, st->hp.n_ctx, st->hp.n_embd, st->stream) != hipSuccess) {
+            set_err(err, err_cap, "%s: HIP error launching k_kv_copy_rows on device %d", fn, st->device);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    return 0;
+}
+int sched_dev_copy_prefix(SchedDev *d, int32_t src, int32_t dst, int32_t row_begin, int32_t n_rows, int32_t *launches, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_sched_step";
+    *launches = 0;
+    llamahip_model *m = d->m;
+    if (!m) { set_err(err, err_cap, "%s: the scheduler's model handle has been freed", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (src < 0 || src >= d->max_active || dst < 0 || dst >= d->max_active || src == dst || row_begin < 0 || n_rows < 1 || (int64_t) row_begin + n_rows > m->hp.n_ctx) {
+        set_err(err, err_cap, "%s: a prefix copy of %d rows at %d from slot %d to slot %d is outside the scheduler's slots or the context (n_ctx %d)", fn, n_rows, row_begin, src, dst, m->hp.n_ctx);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    KvCopyTab tab = {};
+    tab.n = 1; tab.src[0] = src; tab.dst[0] = dst; tab.row_begin[0] = row_begin; tab.n_rows[0] = n_rows;
+    const int rc = kv_copy_enqueue(stages, tab, fn, err, err_cap);
+    if (rc) return drain_stages(stages, rc, err, err_cap);
+    *launches = (int32_t) stages.size();
+    return 0;
 }
 // the handle is being freed under a live scheduler: the scheduler forgets it (no device memory is the scheduler's own)
 void sched_dev_orphan(SchedDev *d) { d->m = nullptr; }
@@ -4055,6 +4088,86 @@ int llamahip_set_seq(llamahip_model *m, int32_t seq, char *err, size_t err_cap) 
     if (!m || seq < 0 || seq >= m->n_seq) { set_err(err, err_cap, "sequence slot %d out of range [0, %d)", seq, m ? m->n_seq : 0); return LLAMAHIP_ERR_PREDICT; }
     m->cur_seq = seq;
     for (llamahip_model *st : m->stages) st->cur_seq = seq;
+    return LLAMAHIP_OK;
+}
+
+// the arguments first (a HOST_ONLY handle knows n_ctx and n_seq: the checks are the same without a device), then the handle, then its scheduler
+static int kv_copy_check(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot, const int32_t *row_begin, const int32_t *n_rows,
+                         lh::KvCopyTab &tab, const char *fn, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int C = m->hp.n_ctx, n_seq = first_of(m)->n_seq;
+    if (n_copies < 1 || n_copies > LLAMAHIP_KV_COPY_MAX) { set_err(err, err_cap, "%s: n_copies (%d) outside 1 .. %d", fn, n_copies, LLAMAHIP_KV_COPY_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (!src_slot || !dst_slot || !row_begin || !n_rows) { set_err(err, err_cap, "%s: null array", fn); return LLAMAHIP_ERR_PREDICT; }
+    tab = {};
+    tab.n = n_copies;
+    for (int i = 0; i < n_copies; i++) {
+        if (src_slot[i] < 0 || src_slot[i] >= n_seq || dst_slot[i] < 0 || dst_slot[i] >= n_seq) {
+            set_err(err, err_cap, "%s: copy %d from slot %d to slot %d: slot out of range [0, %d) (llamahip_opts.n_seq)", fn, i, src_slot[i], dst_slot[i], n_seq);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        if (src_slot[i] == dst_slot[i]) { set_err(err, err_cap, "%s: copy %d: source and destination are the same slot (%d)", fn, i, src_slot[i]); return LLAMAHIP_ERR_PREDICT; }
+        if (n_rows[i] < 0 || row_begin[i] < 0 || (int64_t) row_begin[i] + n_rows[i] > C) {
+            set_err(err, err_cap, "%s: copy %d: rows [%d, %d + %d) outside [0, n_ctx (%d)]", fn, i, row_begin[i], row_begin[i], n_rows[i], C);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        tab.src[i] = src_slot[i]; tab.dst[i] = dst_slot[i]; tab.row_begin[i] = row_begin[i]; tab.n_rows[i] = n_rows[i];
+    }
+    for (int i = 0; i < n_copies; i++)
+        for (int o = 0; o < n_copies; o++)
+            if (o != i && (dst_slot[i] == src_slot[o] || dst_slot[i] == dst_slot[o])) {
+                set_err(err, err_cap, "%s: slot %d is the destination of copy %d and the %s of copy %d: a destination takes part in one copy of a call", fn, dst_slot[i], i,
+                        dst_slot[i] == src_slot[o] ? "source" : "destination", o);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    const int rc = lh::decode_handle_check(m, fn, err, err_cap);
+    if (rc) return rc;
+    if (m->sched)
+        for (int i = 0; i < n_copies; i++)
+            if (dst_slot[i] < lh::sched_dev_max_active(m->sched)) {
+                set_err(err, err_cap, "%s: copy %d writes slot %d, which belongs to the handle's live scheduler (slots below its max_active, %d)", fn, i, dst_slot[i], lh::sched_dev_max_active(m->sched));
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    return 0;
+}
+
+int llamahip_kv_copy_rows(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot, const int32_t *row_begin,
+                          const int32_t *n_rows, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_kv_copy_rows";
+    lh::KvCopyTab tab;
+    int rc = kv_copy_check(m, n_copies, src_slot, dst_slot, row_begin, n_rows, tab, fn, err, err_cap);
+    if (rc) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const double t0 = now_ms();
+    rc = lh::kv_copy_enqueue(stages, tab, fn, err, err_cap);
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_bench_kv_copy(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot, const int32_t *row_begin,
+                           const int32_t *n_rows, int32_t how, int32_t iters, double *ms_per_call, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_bench_kv_copy";
+    lh::KvCopyTab tab;
+    int rc = kv_copy_check(m, n_copies, src_slot, dst_slot, row_begin, n_rows, tab, fn, err, err_cap);
+    if (rc) return rc;
+    if (!m->stages.empty() || iters < 1 || (how != 0 && how != 1) || !ms_per_call) { set_err(err, err_cap, "%s: a plain handle, iters >= 1, how 0 or 1", fn); return LLAMAHIP_ERR_PREDICT; }
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    const size_t d = m->hp.n_embd, layer = (size_t) m->hp.n_ctx * d, L = (size_t) (m->l1 - m->l0);
+    double t0 = 0;
+    for (int it = -1; it < iters; it++) {          // (it == -1: untimed)
+        if (it == 0) t0 = now_ms();
+        if (how == 0) rc = lh::kv_copy_enqueue({ m }, tab, fn, err, err_cap);
+        else
+            for (int c = 0; c < tab.n && rc == 0; c++)
+                for (size_t il = 0; il < L && rc == 0 && tab.n_rows[c] > 0; il++)
+                    for (float *base : { m->Kc, m->Vc }) {
+                        const size_t in_slot = il * layer + (size_t) tab.row_begin[c] * d;
+                        if (hipMemcpyAsync(base + (size_t) tab.dst[c] * L * layer + in_slot, base + (size_t) tab.src[c] * L * layer + in_slot, (size_t) tab.n_rows[c] * d * 4,
+                                           hipMemcpyDeviceToDevice, m->stream) != hipSuccess) { set_err(err, err_cap, "%s: hipMemcpyAsync failed", fn); rc = LLAMAHIP_ERR_PREDICT; break; }
+                    }
+        if ((rc = drain_stages({ m }, rc, err, err_cap)) != 0) return rc;
+    }
+    *ms_per_call = (now_ms() - t0) / iters;
     return LLAMAHIP_OK;
 }
 

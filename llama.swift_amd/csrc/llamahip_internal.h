@@ -342,5 +342,12 @@ hipError_t launch_accept_drafts_set(const int32_t *tokens, const int32_t *pick, 
 constexpr int SCHED_TAB_W = 6;
 hipError_t launch_sched_accept(const int32_t *pick, const int32_t *tokens, const int32_t *tab, int n_segs, int n_rows, int32_t *state, int32_t *log,
                                int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st);
+// KV rows from slot to slot (kv_copy.hip, k_kv_copy_rows): for every copy c < n the rows [row_begin[c], row_begin[c] + n_rows[c]) of every one of
+// the n_layers layers of Kc and Vc ([n_slots][n_layers][n_ctx][d] fp32 each) go from slot src[c] to the same rows of slot dst[c].  The table
+// travels by value in the kernel arguments.  ONE launch (none where every copy is empty).  Refused (hipErrorInvalidValue, nothing launched):
+// a slot or a range outside the arrays, src == dst, a destination that is another copy's source or destination, d % 4 != 0.
+constexpr int KV_COPY_MAX = 16;
+struct KvCopyTab { int32_t n; int32_t src[KV_COPY_MAX], dst[KV_COPY_MAX], row_begin[KV_COPY_MAX], n_rows[KV_COPY_MAX]; };
+hipError_t launch_kv_copy_rows(float *Kc, float *Vc, const KvCopyTab &tab, int n_slots, int n_layers, int n_ctx, int d, hipStream_t st);
 
 }  // namespace lh

@@ -1,5 +1,6 @@
 // sched.cpp -- the host half of the request scheduler (include/llamahip.h "request scheduler"): the step rule
-// (llamahip_sched_plan), the draft policy (llamahip_sched_plan_drafts: what rides in the rows a step leaves spare), the queue, the slots, what
+// (llamahip_sched_plan), the draft policy (llamahip_sched_plan_drafts: what rides in the rows a step leaves spare), the prefix policy
+// (llamahip_sched_plan_prefix: which slot a request takes and whose evaluated prompt rows it takes over), the queue, the slots, what
 // llamahip_sched_new / _submit / _step refuse, and the events of a step.  What a planned
 // step runs on the handle is the device half's business (sched.h, llamahip.cpp).  Pure host code, no device, no HIP header:
 // tools/host_sanitize compiles this file as it is and runs it under ASan + UBSan against a stubbed device half.
@@ -28,6 +29,13 @@ struct Req {
     int32_t left() const { return (int32_t) prompt.size() - off; }
 };
 
+// a slot's held record (prefix_share): its latest occupant's prompt and how many of its KV rows [0, n) are evaluated prompt rows; it outlives
+// the occupant until the next one replaces it
+struct Held {
+    std::vector<int32_t> prompt;
+    int32_t n = 0;
+};
+
 }  // namespace
 
 struct llamahip_sched {
@@ -40,6 +48,8 @@ struct llamahip_sched {
     std::deque<Req> queue;
     std::vector<Req> slot;                // [max_active]; id 0 = free
     std::vector<int32_t> order;           // the active slots in admission order, oldest first
+    bool sharing = false;                 // prefix_share on a handle and at a chunking that can share (not FAST_PREFILL, chunk_tokens > 0)
+    std::vector<Held> held;               // [max_active], kept only while sharing
     std::vector<llamahip_sched_event> pend;      // DONE events of cancelled requests, delivered by the next step
     llamahip_sched_stats st = {};
 };
@@ -97,6 +107,40 @@ extern "C" int32_t llamahip_sched_plan_drafts(int32_t n_active, const int32_t *p
     return dealt;
 }
 
+extern "C" int32_t llamahip_sched_plan_prefix(int32_t n_slots, const int32_t *slot_free, const int32_t *held, const int32_t *n_held, const int32_t *prompt,
+                                              int32_t n_prompt, int32_t chunk_tokens, int32_t *slot_out, int32_t *donor_out, int32_t *n_inplace_out) {
+    if (n_slots < 1 || n_slots > 16 || !slot_free || !n_held || !prompt || n_prompt < 1 || chunk_tokens < 0 || !slot_out || !donor_out || !n_inplace_out) return -1;
+    int64_t n_all = 0;
+    bool any_free = false;
+    for (int32_t s = 0; s < n_slots; s++) {
+        if (slot_free[s] < 0 || n_held[s] < 0) return -1;
+        any_free = any_free || slot_free[s] != 0;
+        n_all += n_held[s];
+    }
+    if (!any_free || (n_all > 0 && !held)) return -1;
+    for (int32_t j = 0; j < n_prompt; j++) if (prompt[j] < 0) return -1;
+    for (int64_t j = 0; j < n_all; j++) if (held[j] < 0) return -1;
+    // share(s): the whole chunks of the common prefix that the record holds as prompt rows, the prompt's last token never among them
+    int32_t share[16];
+    const int32_t *h = held;
+    for (int32_t s = 0; s < n_slots; h += n_held[s], s++) {
+        const int32_t lim = std::min(n_held[s], n_prompt - 1);
+        int32_t l = 0;
+        while (l < lim && h[l] == prompt[l]) l++;
+        share[s] = chunk_tokens > 0 ? l / chunk_tokens * chunk_tokens : 0;
+    }
+    int32_t slot = -1, donor = -1;
+    for (int32_t s = 0; s < n_slots; s++)
+        if (slot_free[s] && (slot < 0 || share[s] > share[slot] || (share[s] == share[slot] && n_held[s] < n_held[slot]))) slot = s;
+    for (int32_t t = 0; t < n_slots; t++)
+        if (t != slot && (donor < 0 || share[t] > share[donor])) donor = t;
+    *slot_out = slot;
+    *n_inplace_out = share[slot];
+    if (donor >= 0 && share[donor] > share[slot]) { *donor_out = donor; return share[donor]; }
+    *donor_out = -1;
+    return share[slot];
+}
+
 extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap) {
     static const char *fn = "llamahip_sched_new";
     if (out) *out = nullptr;
@@ -115,6 +159,8 @@ extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *
         if (op.ngram_min < 0 || op.ngram_max < 0 || mx < mn)          // (what llamahip_lookup_draft refuses)
             return refuse(err, err_cap, "llamahip_sched_new: ngram_min (%ld) / ngram_max (%ld) must be >= 0 (0 = LLAMAHIP_LOOKUP_NGRAM_MIN / _MAX) with ngram_max >= ngram_min", op.ngram_min, op.ngram_max);
     }
+    if (o->struct_size < (int32_t) (offsetof(llamahip_sched_opts, prefix_share) + sizeof(op.prefix_share))) op.prefix_share = 0;          // (a shorter struct: off)
+    if (op.prefix_share != 0 && op.prefix_share != 1) return refuse(err, err_cap, "llamahip_sched_new: prefix_share (%ld) must be 0 (off) or 1", op.prefix_share);
     if (op.n_corpus < 0 || (op.n_corpus > 0 && !op.corpus)) return refuse(err, err_cap, "llamahip_sched_new: n_corpus (%ld) must be >= 0, with a corpus where it is > 0", op.n_corpus);
     if (const int32_t V = llamahip_n_vocab(m))          // (a null handle is refused below)
         for (int32_t i = 0; i < op.n_corpus; i++)
@@ -132,6 +178,10 @@ extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *
     if (op.n_corpus > 0) s->corpus.assign(op.corpus, op.corpus + op.n_corpus);
     s->o.corpus = s->corpus.data();
     s->slot.resize((size_t) op.max_active);
+    // a FAST_PREFILL handle makes no parity claim for its prompt rows and at chunk_tokens 0 a row's key count is its own prompt's length:
+    // nothing is shareable there, no record is kept and the slots are chosen as without the option
+    s->sharing = op.prefix_share == 1 && op.chunk_tokens > 0 && !hi.fast_prefill;
+    if (s->sharing) s->held.resize((size_t) op.max_active);
     s->st.struct_size = (int32_t) sizeof(s->st);
     *out = s;
     return LLAMAHIP_OK;
@@ -227,12 +277,42 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         s->pend.erase(s->pend.begin(), s->pend.begin() + (long) take);
     };
     // 2. queued requests take the free slots, lowest slot first, in submission order
-    for (int32_t i = 0; i < A && !s->queue.empty(); i++)
+    for (int32_t i = 0; !s->sharing && i < A && !s->queue.empty(); i++)
         if (s->slot[(size_t) i].id == 0) {
             s->slot[(size_t) i] = std::move(s->queue.front());
             s->queue.pop_front();
             s->order.push_back(i);
         }
+    // ... with shared prefixes: one at a time, the prefix policy over the held records as they stand; the copy is enqueued before the
+    // admission is committed (a copy that cannot be enqueued leaves the request queued; what was admitted before it stays admitted)
+    while (s->sharing && !s->queue.empty() && (int32_t) s->order.size() < A) {
+        int32_t is_free[16], n_held[16], sl = -1, donor = -1, inplace = 0, launches = 0;
+        std::vector<int32_t> held;
+        for (int32_t i = 0; i < A; i++) {
+            const Held &h = s->held[(size_t) i];
+            is_free[i] = s->slot[(size_t) i].id == 0;
+            n_held[i] = h.n;
+            held.insert(held.end(), h.prompt.begin(), h.prompt.begin() + h.n);
+        }
+        held.push_back(0);          // (never read: a non-null array where nothing is held)
+        const Req &front = s->queue.front();
+        const int32_t P = llamahip_sched_plan_prefix(A, is_free, held.data(), n_held, front.prompt.data(), (int32_t) front.prompt.size(), s->o.chunk_tokens, &sl, &donor, &inplace);
+        if (P < 0 || P >= (int32_t) front.prompt.size() || sl < 0 || sl >= A || s->slot[(size_t) sl].id != 0 || inplace < 0 || inplace > P || (donor >= 0 && (donor >= A || donor == sl)))
+            return refuse(err, err_cap, "llamahip_sched_step: the prefix policy gave %ld shared rows in slot %ld for a prompt of %ld tokens", P, sl, (long) front.prompt.size());
+        if (donor >= 0) {
+            const int rc = lh::sched_dev_copy_prefix(s->dev, donor, sl, inplace, P - inplace, &launches, err, err_cap);
+            if (rc) return rc;
+            s->st.n_copied_rows += P - inplace; s->st.n_copy_launches += launches;
+        }
+        s->st.n_shared_rows += P;
+        Req &q = s->slot[(size_t) sl];
+        q = std::move(s->queue.front());
+        s->queue.pop_front();
+        q.off = P;
+        s->held[(size_t) sl].prompt = q.prompt;
+        s->held[(size_t) sl].n = P;
+        s->order.push_back(sl);
+    }
     const int32_t na = (int32_t) s->order.size();
     if (na == 0) { deliver_pending(); *n_ev = n; return LLAMAHIP_OK; }
     // 3. the rows of this step
@@ -302,7 +382,10 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     for (int32_t j = 0; j < n_segs; j++) {
         const lh::SchedSeg &g = segs[j];
         Req &q = s->slot[(size_t) g.slot];
-        if (left[seg_k[j]] > 0) q.off += g.n_rows;
+        if (left[seg_k[j]] > 0) {
+            q.off += g.n_rows;
+            if (s->sharing) s->held[(size_t) g.slot].n = q.off;          // (evaluated prompt rows only: decode and draft rows lie above the prompt's end)
+        }
         if (!g.emit) continue;
         s->st.n_emit_segs++;
         s->st.n_accepted += g.n_accept;

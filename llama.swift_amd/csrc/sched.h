@@ -12,7 +12,8 @@ namespace lh {
 struct SchedDev;          // the device half's state for one scheduler (llamahip.cpp)
 
 // what the host half needs to know of the handle; refuses (message in err, the handle named last) null, HOST_ONLY and stage handles
-struct SchedHandleInfo { int32_t n_ctx, n_vocab, n_seq; };
+// fast_prefill: a LLAMAHIP_FLAG_FAST_PREFILL handle (no parity claim for its prompt rows: nothing of them is shared between slots)
+struct SchedHandleInfo { int32_t n_ctx, n_vocab, n_seq, fast_prefill; };
 int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap);
 // the sampler parameters of llamahip_sched_opts, by llamahip_verify_sample's rule
 int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap);
@@ -46,5 +47,9 @@ int sched_dev_drafts(SchedDev *d);
 // one weight pass over the segments (mixed: some segment is a prompt piece or carries a draft; else every segment is one decode row).  *kind: SCHED_STEP_*;
 // *captures: set-step graphs captured by this step.  Nothing of the host half's state is read: the segments say everything.
 int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int32_t *kind, int32_t *captures, char *err, size_t err_cap);
+// a shared prompt prefix: the KV rows [row_begin, row_begin + n_rows) of every layer, K and V, from slot src to the same rows of slot dst (both the
+// scheduler's) -- one k_kv_copy_rows launch enqueued on every stage's stream and NOT waited for: the step's pass runs behind it, and so does a
+// later copy of the same step that reads what this one wrote.  *launches: the launches made.  On an error the streams are drained.
+int sched_dev_copy_prefix(SchedDev *d, int32_t src, int32_t dst, int32_t row_begin, int32_t n_rows, int32_t *launches, char *err, size_t err_cap);
 
 }  // namespace lh

@@ -101,6 +101,14 @@ static std::vector<SchedCall> g_sched_calls;
 static bool g_sched_fail = false;          // the next steps fail like a device error: nothing of the host half's state may be lost
 static bool g_sched_drafts = true;         // the stubbed handle takes drafted tokens (false: a fall-back handle)
 static int g_sched_accept = -1;            // the script: draft tokens a segment accepts (cut to its draft); -1: (position + slot) % (n_draft + 1)
+// shared prefixes: the copies the host half asked for, and a shadow cache [slot][row] (kept while non-empty) in which every row a step evaluates
+// becomes a hash chained on the row below it in its slot -- a row shared or copied wrongly, or not at all, shows in every row above it
+struct CopyCall { int32_t src, dst, row_begin, n_rows; size_t n_steps_before; };
+static std::vector<CopyCall> g_sched_copies;
+static bool g_sched_copy_fail = false;
+static std::vector<std::vector<uint64_t>> g_vkv;
+static uint64_t vkv_mix(uint64_t below, int32_t tok) { return (below ^ (uint64_t) (uint32_t) tok) * 0x9e3779b97f4a7c15ull + 0x7f4a7c15ull; }
+static const uint64_t VKV_SEED = 0x1234567ull;
 namespace lh {
 struct SchedDev { int V; llamahip_model *m; };
 int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap) {
@@ -126,6 +134,11 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
     SchedCall c;
     c.mixed = mixed;
     for (int j = 0; j < n_segs; j++) {
+        for (int r = 0; !g_vkv.empty() && r < segs[j].n_rows + segs[j].n_draft; r++) {
+            std::vector<uint64_t> &rows = g_vkv[(size_t) segs[j].slot];
+            const size_t row = (size_t) (segs[j].pos + r);
+            rows.at(row) = vkv_mix(row ? rows[row - 1] : VKV_SEED, r < segs[j].n_rows ? segs[j].tokens[r] : segs[j].draft[r - segs[j].n_rows]);
+        }
         c.toks.emplace_back(segs[j].tokens, segs[j].tokens + segs[j].n_rows);
         c.drafts.emplace_back(segs[j].draft, segs[j].draft + segs[j].n_draft);          // (exactly sized, as the rows' tokens)
         if (segs[j].n_draft > 0) {
@@ -149,6 +162,14 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
     g_sched_calls.push_back(std::move(c));
     *kind = mixed ? SCHED_STEP_MIXED : n_segs >= 2 ? SCHED_STEP_SET : SCHED_STEP_SINGLE;
     *captures = 0;
+    return 0;
+}
+int sched_dev_copy_prefix(SchedDev *, int32_t src, int32_t dst, int32_t row_begin, int32_t n_rows, int32_t *launches, char *err, size_t err_cap) {
+    *launches = 0;
+    if (g_sched_copy_fail) { snprintf(err, err_cap, "llamahip_sched_step: made-up device error in a prefix copy"); return LLAMAHIP_ERR_PREDICT; }
+    g_sched_copies.push_back({ src, dst, row_begin, n_rows, g_sched_calls.size() });
+    for (int r = 0; !g_vkv.empty() && r < n_rows; r++) g_vkv.at((size_t) dst).at((size_t) (row_begin + r)) = g_vkv.at((size_t) src).at((size_t) (row_begin + r));
+    *launches = 1;
     return 0;
 }
 }
@@ -786,6 +807,184 @@ int main(int argc, char **argv) {
                 EXPECT(llamahip_sched_new(ms, &so, &sb, err, sizeof(err)) == 0 && sb);          // free again after the first one is gone
                 llamahip_sched_free(sb);
             }
+        }
+        // shared prompt prefixes (prefix_share): the policy over a grid on exactly sized arrays against its restatement, and its refusals; then
+        // whole runs against the stub's shadow cache -- at every request's first token its slot's prompt rows must be the chain over ITS prompt,
+        // whatever was shared in place or copied from whichever donor; the stats against the copies the stub saw; a copy and a step that fail
+        {
+            auto share_ref = [](const std::vector<int32_t> &h, const std::vector<int32_t> &p, int c) {
+                size_t l = 0;
+                while (l < h.size() && l + 1 < p.size() && h[l] == p[l]) l++;
+                return c > 0 ? (int32_t) (l / (size_t) c * (size_t) c) : 0;
+            };
+            long n_plans = 0, n_donors = 0;
+            for (int c : { 0, 1, 4, 9 })
+                for (int n_slots : { 1, 3, 16 })
+                    for (int it = 0; it < 80; it++) {
+                        std::vector<int32_t> prompt((size_t) (1 + rng() % 40));          // exactly sized, a small alphabet: long common prefixes
+                        for (int32_t &t : prompt) t = (int32_t) (rng() % 2);
+                        std::vector<std::vector<int32_t>> recs((size_t) n_slots);
+                        std::vector<int32_t> is_free((size_t) n_slots), n_held((size_t) n_slots), cat;
+                        for (int sl = 0; sl < n_slots; sl++) {
+                            std::vector<int32_t> &h = recs[(size_t) sl];
+                            const int kind = (int) (rng() % 4);
+                            if (kind == 1) h.assign(prompt.begin(), prompt.begin() + (long) (rng() % (prompt.size() + 1)));          // a prefix of the prompt
+                            if (kind == 2) { h = prompt; for (int k = (int) (rng() % 9); k > 0; k--) h.push_back((int32_t) (rng() % 2)); }      // the prompt and more
+                            if (kind == 3) { h.resize((size_t) (rng() % 45)); for (int32_t &t : h) t = (int32_t) (rng() % 2); }
+                            is_free[(size_t) sl] = it % 3 == 0 ? 1 : (int32_t) (rng() % 2);
+                            n_held[(size_t) sl] = (int32_t) h.size();
+                            cat.insert(cat.end(), h.begin(), h.end());
+                        }
+                        is_free[rng() % (size_t) n_slots] = 1;
+                        int32_t sl = -7, donor = -7, inplace = -7, want_slot = -1, want_donor = -1;
+                        const int32_t P = llamahip_sched_plan_prefix(n_slots, is_free.data(), cat.data(), n_held.data(), prompt.data(), (int32_t) prompt.size(), c, &sl, &donor, &inplace);
+                        for (int k = 0; k < n_slots; k++) {
+                            if (!is_free[(size_t) k]) continue;
+                            const int32_t a = share_ref(recs[(size_t) k], prompt, c), b = want_slot < 0 ? -1 : share_ref(recs[(size_t) want_slot], prompt, c);
+                            if (want_slot < 0 || a > b || (a == b && n_held[(size_t) k] < n_held[(size_t) want_slot])) want_slot = k;
+                        }
+                        for (int k = 0; k < n_slots; k++)
+                            if (k != want_slot && (want_donor < 0 || share_ref(recs[(size_t) k], prompt, c) > share_ref(recs[(size_t) want_donor], prompt, c))) want_donor = k;
+                        const int32_t in_place = share_ref(recs[(size_t) want_slot], prompt, c), given = want_donor < 0 ? -1 : share_ref(recs[(size_t) want_donor], prompt, c);
+                        EXPECT(sl == want_slot && inplace == in_place);
+                        if (given > in_place) { EXPECT(donor == want_donor && P == given); n_donors++; }
+                        else EXPECT(donor == -1 && P == in_place);
+                        EXPECT(P >= 0 && P <= (int32_t) prompt.size() - 1 && (c == 0 ? P == 0 : P % c == 0));
+                        n_plans++;
+                    }
+            EXPECT(n_plans == 4 * 3 * 80 && n_donors > 0);
+            {
+                int32_t f1[1] = { 1 }, f0[1] = { 0 }, h0[1] = { 0 }, h2[1] = { 2 }, neg[1] = { -1 }, p[2] = { 1, 2 }, hp2[2] = { 1, 2 }, a = 0, b = 0, cc = 0;
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 2, 1, &a, &b, &cc) == 1 && a == 0 && b == -1 && cc == 1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, nullptr, h0, p, 2, 1, &a, &b, &cc) == 0);          // nothing held: no array needed
+                EXPECT(llamahip_sched_plan_prefix(0, f1, hp2, h2, p, 2, 1, &a, &b, &cc) == -1 && llamahip_sched_plan_prefix(17, f1, hp2, h2, p, 2, 1, &a, &b, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f0, hp2, h2, p, 2, 1, &a, &b, &cc) == -1);             // no free slot
+                EXPECT(llamahip_sched_plan_prefix(1, nullptr, hp2, h2, p, 2, 1, &a, &b, &cc) == -1 && llamahip_sched_plan_prefix(1, f1, nullptr, h2, p, 2, 1, &a, &b, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, nullptr, p, 2, 1, &a, &b, &cc) == -1 && llamahip_sched_plan_prefix(1, f1, hp2, h2, nullptr, 2, 1, &a, &b, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 2, 1, nullptr, &b, &cc) == -1 && llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 2, 1, &a, nullptr, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 2, 1, &a, &b, nullptr) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, neg, p, 2, 1, &a, &b, &cc) == -1 && llamahip_sched_plan_prefix(1, neg, hp2, h2, p, 2, 1, &a, &b, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 0, 1, &a, &b, &cc) == -1 && llamahip_sched_plan_prefix(1, f1, hp2, h2, p, 2, -1, &a, &b, &cc) == -1);
+                EXPECT(llamahip_sched_plan_prefix(1, f1, hp2, h2, neg, 1, 1, &a, &b, &cc) == -1);
+            }
+            int64_t shared_in_all = 0, copied_in_all = 0;
+            for (int share : { 1, 0 })
+                for (int c : { 0, 1, 4, 9 })
+                    for (int max_active : { 1, 3, 4 })
+                        for (int draft_len : { 0, 4 }) {
+                            if (!ms) break;
+                            std::vector<int32_t> corpus(40);
+                            for (size_t i = 0; i < corpus.size(); i++) corpus[i] = (int32_t) ((i * 5 + 1) % (size_t) V);
+                            llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                            so.struct_size = sizeof(so); so.n_threads = 2; so.max_active = max_active; so.chunk_tokens = c; so.row_budget = 8;
+                            so.draft_len = draft_len; so.corpus = corpus.data(); so.n_corpus = (int32_t) corpus.size(); so.prefix_share = share;
+                            llamahip_sched *sc = nullptr;
+                            EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                            if (!sc) continue;
+                            // a 20-token system prompt in front of distinct tails; an exact resubmission; a prompt that IS the system prompt; a short
+                            // one; one with nothing in common
+                            std::vector<int32_t> sys(20);
+                            for (size_t i = 0; i < sys.size(); i++) sys[i] = (int32_t) ((i * 7 + 3) % (size_t) V);
+                            static const int tails[8] = { 5, 11, 0, 5, -17, -1, 2, 9 }, npred[8] = { 3, 5, 2, 1, 4, 2, 6, 3 };          // (negative: -n tokens of something else)
+                            std::vector<std::vector<int32_t>> prompts;
+                            for (int i = 0; i < 8; i++) {
+                                std::vector<int32_t> pr;
+                                if (tails[i] >= 0) { pr = sys; for (int k = 0; k < tails[i]; k++) pr.push_back((int32_t) ((k * 3 + (i == 3 ? 0 : i) * 11 + 40) % V)); }
+                                else for (int k = 0; k < -tails[i]; k++) pr.push_back((int32_t) ((k * 5 + 50 + i) % V));
+                                prompts.push_back(pr);          // exactly sized
+                            }
+                            EXPECT(prompts[0] == prompts[3]);
+                            for (int i = 0; i < 8; i++) {
+                                llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                                rq.struct_size = sizeof(rq); rq.prompt = prompts[(size_t) i].data(); rq.n_prompt = (int32_t) prompts[(size_t) i].size(); rq.n_predict = npred[i]; rq.stop_token = -1;
+                                int64_t id = 0;
+                                EXPECT(llamahip_sched_submit(sc, &rq, &id, err, sizeof(err)) == 0 && id == (int64_t) i + 1);
+                            }
+                            g_sched_calls.clear(); g_sched_copies.clear();
+                            g_vkv.assign(4, std::vector<uint64_t>(48));
+                            for (size_t a = 0; a < 4; a++) for (size_t r = 0; r < 48; r++) g_vkv[a][r] = 0xdead0000ull + a * 100 + r;
+                            std::vector<llamahip_sched_event> evs((size_t) LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len));
+                            int steps = 0, firsts = 0;
+                            std::vector<int> n_out(8, 0), slot_of(8, -1);
+                            while (llamahip_sched_pending(sc) > 0 && steps < 400) {
+                                int32_t ne = 0;
+                                EXPECT(llamahip_sched_step(sc, evs.data(), (int32_t) evs.size(), &ne, err, sizeof(err)) == 0);
+                                steps++;
+                                for (int32_t e = 0; e < ne; e++) {
+                                    const llamahip_sched_event &x = evs[(size_t) e];
+                                    if (x.kind != LLAMAHIP_EV_TOKEN) continue;
+                                    const size_t i = (size_t) (x.id - 1);
+                                    if (n_out[i]++ > 0) { EXPECT(x.slot == slot_of[i]); continue; }
+                                    // the request's first token: the prompt rows of its slot are the chain over its own prompt
+                                    slot_of[i] = x.slot;
+                                    EXPECT(x.position == (int32_t) prompts[i].size());
+                                    uint64_t h = VKV_SEED;
+                                    for (size_t r = 0; r < prompts[i].size(); r++) { h = vkv_mix(h, prompts[i][r]); EXPECT(g_vkv[(size_t) x.slot][r] == h); }
+                                    firsts++;
+                                }
+                            }
+                            EXPECT(llamahip_sched_pending(sc) == 0 && firsts == 8);
+                            // no piece starts off a chunk boundary; every copy lies below its recipient's first piece
+                            for (const SchedCall &cl : g_sched_calls) for (const lh::SchedSeg &g : cl.segs) if (g.n_out == 0 && c > 0) EXPECT(g.pos % c == 0);
+                            llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                            int64_t sum_prompt = 0, copied = 0;
+                            for (const auto &pr : prompts) sum_prompt += (int64_t) pr.size();
+                            for (const CopyCall &cp : g_sched_copies) { copied += cp.n_rows; EXPECT(cp.src != cp.dst && cp.src < max_active && cp.dst < max_active && cp.n_rows > 0 && cp.row_begin % std::max(c, 1) == 0 && cp.n_rows % std::max(c, 1) == 0); }
+                            EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_done == 8 && ss.n_prompt_rows + ss.n_shared_rows == sum_prompt);
+                            EXPECT(ss.n_copied_rows == copied && ss.n_copy_launches == (int64_t) g_sched_copies.size() && ss.n_copied_rows <= ss.n_shared_rows);
+                            if (share && c > 0) EXPECT(ss.n_shared_rows > 0 && (max_active > 1 || copied == 0));          // (one slot: in place only; whether several slots copy depends on who has evaluated what at each admission)
+                            else EXPECT(ss.n_shared_rows == 0 && g_sched_copies.empty());
+                            shared_in_all += ss.n_shared_rows; copied_in_all += copied;
+                            llamahip_sched_free(sc);
+                        }
+            g_vkv.clear();
+            if (ms) {
+                // a copy that cannot be enqueued leaves the request queued; a step that fails behind a committed admission keeps it, its slot and its rows
+                llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                so.struct_size = sizeof(so); so.max_active = 2; so.chunk_tokens = 4; so.row_budget = 16; so.prefix_share = 1;
+                llamahip_sched *sc = nullptr;
+                EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                if (sc) {
+                    std::vector<int32_t> pa(13), pb(15);
+                    for (size_t i = 0; i < pa.size(); i++) pa[i] = (int32_t) (i + 1);
+                    for (size_t i = 0; i < pb.size(); i++) pb[i] = (int32_t) (i < 12 ? i + 1 : 60 + i);
+                    llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                    rq.struct_size = sizeof(rq); rq.prompt = pa.data(); rq.n_prompt = 13; rq.n_predict = 9; rq.stop_token = -1;
+                    EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == 0);
+                    std::vector<llamahip_sched_event> evs(5);
+                    int32_t ne = 0;
+                    g_sched_calls.clear(); g_sched_copies.clear();
+                    EXPECT(llamahip_sched_step(sc, evs.data(), 5, &ne, err, sizeof(err)) == 0 && ne == 1);
+                    rq.prompt = pb.data(); rq.n_prompt = 15; rq.n_predict = 2;
+                    EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == 0);
+                    llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                    g_sched_copy_fail = true;
+                    EXPECT(llamahip_sched_step(sc, evs.data(), 5, &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0 && strstr(err, "prefix copy") && llamahip_sched_pending(sc) == 2);
+                    EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_shared_rows == 0 && ss.n_copy_launches == 0 && ss.n_steps == 1 && g_sched_copies.empty());
+                    g_sched_copy_fail = false; g_sched_fail = true;
+                    EXPECT(llamahip_sched_step(sc, evs.data(), 5, &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && ne == 0 && llamahip_sched_pending(sc) == 2);
+                    EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_shared_rows == 12 && ss.n_copied_rows == 12 && ss.n_copy_launches == 1 && ss.n_steps == 1);
+                    EXPECT(g_sched_copies.size() == 1 && g_sched_copies[0].src == 0 && g_sched_copies[0].dst == 1 && g_sched_copies[0].row_begin == 0 && g_sched_copies[0].n_rows == 12);
+                    g_sched_fail = false;
+                    const size_t call0 = g_sched_calls.size();
+                    EXPECT(llamahip_sched_step(sc, evs.data(), 5, &ne, err, sizeof(err)) == 0 && g_sched_calls.size() == call0 + 1 && g_sched_copies.size() == 1);
+                    if (g_sched_calls.size() == call0 + 1) {
+                        const SchedCall &cl = g_sched_calls.back();
+                        EXPECT(cl.segs.size() == 2 && cl.segs[1].slot == 1 && cl.segs[1].pos == 12 && cl.segs[1].n_rows == 3 && cl.segs[1].emit == 1 && cl.toks[1][0] == pb[12]);
+                    }
+                    while (llamahip_sched_pending(sc) > 0 && g_sched_calls.size() < 60) EXPECT(llamahip_sched_step(sc, evs.data(), 5, &ne, err, sizeof(err)) == 0);
+                    EXPECT(llamahip_sched_get_stats(sc, &ss) == 0 && ss.n_done == 2 && ss.n_prompt_rows + ss.n_shared_rows == 28);
+                    llamahip_sched_free(sc);
+                }
+                // prefix_share other than 0 or 1; a struct that ends before it: off, whatever lies behind it
+                so.prefix_share = 2; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "prefix_share"));
+                so.prefix_share = -1; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "prefix_share"));
+                so.prefix_share = 2; so.struct_size = (int32_t) offsetof(llamahip_sched_opts, prefix_share);
+                EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                llamahip_sched_free(sc);
+            }
+            EXPECT(!ms || (shared_in_all > 0 && copied_in_all > 0));
+            printf("host_sanitize: scheduler with shared prefixes: %ld plans against the restatement, %lld rows shared and %lld of them copied over all runs\n", n_plans, (long long) shared_in_all, (long long) copied_in_all);
         }
         // llamahip_sched_submit's row limit, on a handle whose context is long enough to reach it: with chunk_tokens 0 a prompt is one piece of
         // at most LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active rows; in chunks the piece is the chunk -- and a chunk that long is refused the same way

@@ -24,7 +24,19 @@ tokens/s, the longest step, steps, drafted / accepted, and the acceptance rate f
 in acceptance rate between the configurations that draft from a corpus).
 --parent-root DIR: a tree of the parent commit with its library built (python package and libllamahip.so).  The draft_len == 0 scheduler of
 this tree against that tree's, each run in a fresh process (--one-plain-run, one untimed run, then the timed one), interleaved, --parent-runs
-each: both medians, both min .. max spreads, and whether the medians differ by less than the parent's own spread."""
+each: both medians, both min .. max spreads, and whether the medians differ by less than the parent's own spread.
+
+sched_probe.py --shared-prefix N [--json OUT] [--repeats 5] [--parent-root DIR] [--parent-runs 5]
+Shared prompt prefixes (llamahip_sched_opts.prefix_share): the same 64 requests with one common N-token system prompt in front of every
+prompt, n_ctx raised by N to fit, row_budget LLAMAHIP_SCHED_ROW_BUDGET.  prefix_share off and on in one process on one handle, interleaved
+`repeats` times after one untimed run of each, for two arrival patterns -- all 64 at once (the first 16 find nothing held; everybody later finds
+the system prompt in the slot it takes) and the first request alone until its first token, then the other 63 (the next 15 copy its rows);
+the tokens of every run must be the first run's.  Reported per configuration: aggregate
+tokens/s, steps, the longest step, n_prompt_rows / n_shared_rows / n_copied_rows / n_copy_launches and the mean number of steps from
+submit to a request's first token.  Before that, the copy itself against the obvious alternative (llamahip_bench_kv_copy): one
+k_kv_copy_rows launch against a loop of hipMemcpyAsync calls over the same ranges of every layer, K and V, on the same stream -- one copy of 9
+rows (launch-bound), one of 256 rows (bandwidth-bound), 256 rows broadcast to 15 destinations; interleaved, `repeats` runs of 20 calls each.
+--parent-root DIR: as for --draft -- the standard workload (no shared prefix, prefix_share 0) of this tree against the parent's, fresh processes."""
 import json, os, statistics, subprocess, sys, time
 ROOT = os.environ.get("LLAMAHIP_PROBE_ROOT") or os.path.dirname(os.path.dirname(os.path.abspath(__file__)))      # (--one-plain-run on the parent's tree)
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -154,6 +166,120 @@ def main_draft():
             json.dump(res, f, indent=1)
 
 
+def parent_comparison(spread):
+    """the plain scheduler of this tree against the tree at --parent-root: fresh processes, interleaved (None without --parent-root)"""
+    parent = opt("--parent-root", "")
+    if not parent:
+        return None
+    n_runs = int(opt("--parent-runs", "5"))
+    got = {"this": [], "parent": []}
+    for _ in range(n_runs):
+        for who, root in (("parent", os.path.abspath(parent)), ("this", HERE)):
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--one-plain-run"], env={**os.environ, "LLAMAHIP_PROBE_ROOT": root},
+                               capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            got[who].append(json.loads(r.stdout.strip().splitlines()[-1]))
+    assert len({x["tokens_crc"] for v in got.values() for x in v}) == 1, "the two libraries produced different tokens"
+    assert got["parent"][0]["library"] != got["this"][0]["library"]
+    tp, tt = spread([x["tokens_per_s"] for x in got["parent"]]), spread([x["tokens_per_s"] for x in got["this"]])
+    return {"method": f"fresh processes, interleaved, {n_runs} each; in each one untimed run, then the timed one", "parent_tokens_per_s": tp, "this_tokens_per_s": tt,
+            "parent_longest_step_ms": spread([x["longest_step_ms"] for x in got["parent"]]), "this_longest_step_ms": spread([x["longest_step_ms"] for x in got["this"]]),
+            "median_difference": round(tt["median"] - tp["median"], 3), "parent_spread": round(tp["max"] - tp["min"], 3),
+            "unchanged_within_the_parents_spread": abs(tt["median"] - tp["median"]) <= tp["max"] - tp["min"]}
+
+
+def main_prefix():
+    import numpy as np
+    import llama_swift_amd as L
+    subprocess.run(["bash", os.path.join(HERE, "tools", "ensure_7b.sh")], cwd=HERE, check=True)
+    n_sys, repeats, budget = int(opt("--shared-prefix", "256")), int(opt("--repeats", "5")), 256
+    m = L.Model(MODEL, n_ctx=N_CTX + n_sys, n_seq=SLOTS)
+    rng = np.random.default_rng(20250131)
+    system = np.concatenate([[1], rng.integers(3, m.n_vocab, n_sys - 1)]).astype(np.int32)
+    reqs = [(np.concatenate([system, p[1:] if len(p) > 1 else p]).astype(np.int32), k) for p, k in workload(np, m.n_vocab)]
+    asked = sum(k for _, k in reqs)
+    spread = lambda xs: {"median": round(statistics.median(xs), 3), "min": round(min(xs), 3), "max": round(max(xs), 3)}
+    res = {"model": "7B synthetic (seed 20230312), Q4_0", "n_ctx": N_CTX + n_sys, "max_active": SLOTS, "chunk_tokens": CHUNK, "n_threads": NTH, "row_budget": budget,
+           "shared_prefix_tokens": n_sys, "requests": N_REQ, "prompt_tokens": int(sum(len(p) for p, _ in reqs)), "tokens_asked": int(asked), "repeats": repeats,
+           "library": os.path.basename(L.LIB_PATH)}
+    # the copy alone: rows that hold something (one eval of the system prompt in slot 0), then each case both ways, interleaved
+    m.set_seq(0)
+    m.eval_chunks(system, 0, CHUNK, NTH)
+    cases = [("one copy of 9 rows", [(0, 1, 0, 9)]), (f"one copy of {n_sys} rows", [(0, 1, 0, n_sys)]),
+             (f"{n_sys} rows broadcast to 15 destinations", [(0, d, 0, n_sys) for d in range(1, SLOTS)])]
+    res["copy"] = {"method": f"llamahip_bench_kv_copy: host wall time per enqueue + stream wait, the mean of 20 calls after one untimed call; kernel and loop interleaved, {repeats} runs each",
+                   "cases": []}
+    for name, copies in cases:
+        t = {0: [], 1: []}
+        for _ in range(repeats):
+            for how in (0, 1):
+                t[how].append(m.bench_kv_copy(copies, how, 20) * 1e3)
+        rows = sum(c[3] for c in copies)
+        nbytes = rows * m.n_embd * 4 * 2 * m.n_layer
+        k, l = spread(t[0]), spread(t[1])
+        row = {"case": name, "ranges": len(copies) * 2 * m.n_layer, "bytes_moved": int(nbytes), "k_kv_copy_rows_us": k, "hipMemcpyAsync_loop_us": l,
+               "kernel_GBps_read_plus_write": round(2 * nbytes / (k["median"] * 1e-6) / 1e9, 1), "loop_spread_us": round(l["max"] - l["min"], 3),
+               "kernel_not_slower_by_more_than_the_loops_spread": k["median"] <= l["median"] + (l["max"] - l["min"])}
+        res["copy"]["cases"].append(row)
+        print(f"{name:45s} kernel {k} us | memcpy loop {l} us | {row['kernel_GBps_read_plus_write']} GB/s", flush=True)
+
+    def run(share, warm):
+        """warm: the first request alone until its first token, then the other 63 at once (they find its rows and copy them); else all at once"""
+        out, first, sub_at, longest, n_step = {}, {}, {}, 0.0, 0
+        with m.scheduler(max_active=SLOTS, chunk_tokens=CHUNK, row_budget=budget, n_threads=NTH, prefix_share=share) as sc:
+            ids = []
+            todo = list(reqs)
+            t_all = time.perf_counter()
+            while todo or sc.pending():
+                if todo and (not warm or not ids or ids[0] in first):
+                    for p, k in (todo if ids or not warm else todo[:1]):
+                        ids.append(sc.submit(p, k))
+                        sub_at[ids[-1]] = n_step
+                    todo = reqs[len(ids):]
+                t0 = time.perf_counter()
+                ev = sc.step()
+                longest = max(longest, (time.perf_counter() - t0) * 1e3)
+                n_step += 1
+                for e in ev:
+                    if e["kind"] == "token":
+                        out.setdefault(e["id"], []).append(e["token"])
+                        first.setdefault(e["id"], n_step - sub_at[e["id"]])
+            wall = time.perf_counter() - t_all
+            st = sc.stats()
+        return wall, longest, st, [out[i] for i in ids], statistics.mean(first[i] for i in ids)
+
+    configs = [(False, False), (True, False), (False, True), (True, True)]
+    want = run(False, False)[3]
+    for share, warm in configs[1:]:
+        assert run(share, warm)[3] == want, "prefix_share or the arrival order changed a request's tokens"
+    runs = {c: [] for c in configs}
+    for _ in range(repeats):
+        for c in configs:
+            r = run(*c)
+            assert r[3] == want, "a run's tokens are not the first run's"
+            runs[c].append(r)
+    res["scheduler"] = {"method": "one process, one handle; the configurations interleaved, `repeats` times, after one untimed run of each; wall time around the whole run "
+                                  "(submissions included) and around every step",
+                        "configs": []}
+    for c in configs:
+        st = runs[c][-1][2]
+        row = {"prefix_share": int(c[0]), "arrival": "the first request alone until its first token, then the other 63" if c[1] else "all 64 at once",
+               "tokens_per_s": spread([asked / r[0] for r in runs[c]]), "longest_step_ms": spread([r[1] for r in runs[c]]),
+               "steps": st["n_steps"], "mixed_steps": st["n_mixed_steps"], "rows": st["n_rows"], "prompt_rows": st["n_prompt_rows"],
+               "shared_rows": st["n_shared_rows"], "copied_rows": st["n_copied_rows"], "copy_launches": st["n_copy_launches"],
+               "mean_steps_to_first_token": round(runs[c][-1][4], 2)}
+        res["scheduler"]["configs"].append(row)
+        print(f"prefix_share {row['prefix_share']}, {row['arrival']}: {row['tokens_per_s']} tokens/s | {row['steps']} steps | longest step {row['longest_step_ms']['median']} ms | "
+              f"prompt rows {row['prompt_rows']} shared {row['shared_rows']} copied {row['copied_rows']} in {row['copy_launches']} launches | "
+              f"{row['mean_steps_to_first_token']} steps to the first token", flush=True)
+    m.close()
+    res["prefix_share_0_against_parent"] = parent_comparison(spread)
+    print("prefix_share 0, standard workload, against the parent:", res["prefix_share_0_against_parent"], flush=True)
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     import numpy as np
     import llama_swift_amd as L
@@ -253,4 +379,4 @@ def main():
 
 
 if __name__ == "__main__":
-    one_plain_run() if "--one-plain-run" in args else main_draft() if "--draft" in args else main()
+    one_plain_run() if "--one-plain-run" in args else main_prefix() if "--shared-prefix" in args else main_draft() if "--draft" in args else main()
