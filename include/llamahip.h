@@ -893,6 +893,22 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
 #define LLAMAHIP_DENSE_MFMA 4
 int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                               float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
+/* The Q4_1 mat-mul with its kernel chosen by the caller: y[n][m] = ggml_vec_dot_q4_1(W[m], quantize_row_q4_1(x[n])) (+ resid[n][m]), bit for
+ * bit: one fp32 accumulator per output over all K/2 byte pairs in order, every product and sum rounded on its own.  w_q4_1: M rows in FILE
+ * layout, [K/32 floats min][K/32 floats d][K/32 * 16 nibble bytes] per row, K a positive multiple of 32; x [N][K]; resid [N][M] or NULL;
+ * y [N][y_stride], y_stride >= M: the WHOLE buffer is copied to the device before the launch and back after it, so columns M .. y_stride - 1
+ * keep what the caller put there unless a kernel writes out of place.  path: LLAMAHIP_Q41_AUTO -- what a model handle runs (_CHAIN);
+ * _CHAIN k_q41_chain: row tiles of at most 16, the weights streamed and dequantised once per tile, the pair terms formed by product waves
+ * and added in pair order by one chain lane per output; _LANE k_q41_mm: a lane per weight row does all of it, once per activation row.
+ * Both read the same load-time copy of the weights.  LLaMA-7B matrices of an 8-layer Q4_1 file, us per launch, _LANE -> _CHAIN (wq|wk|wv,
+ * wo, w1|w3, w2; profiles/q41_probe.json): 1 row 90 / 89 / 94 / 242 -> 29 / 24 / 54 / 61; 16 rows 130 / 90 / 225 / 249 -> 104 / 48 / 185 / 133
+ * (whole evals of 1 .. 512 rows: DESIGN.md 12.24).  Refusals name their limit and happen before any device is
+ * touched.  *path_taken (may be NULL): the path that ran. */
+#define LLAMAHIP_Q41_AUTO  0
+#define LLAMAHIP_Q41_CHAIN 1
+#define LLAMAHIP_Q41_LANE  2
+int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                             float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -1037,6 +1053,15 @@ int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32
  * 1 where LLAMAHIP_DENSE_AUTO picks the kernel for this shape else 0 }.  Returns 1, 0 where the kernel does not take the shape (n_rows <= 16,
  * K not a multiple of 128, another wtype, n_rows * k >= 2^31), -1 where the plan names an instance that was never compiled. */
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]);
+/* Q4_1 mat-muls per kernel since process start: out[0 .. 1] = { k_q41_chain, k_q41_mm } (at most `cap` entries are written); returns 2.
+ * One count per mat-mul, however many row tiles it launched.  Tests and measurement tooling. */
+int32_t llamahip_debug_q41_paths(int64_t *out, int32_t cap);
+/* Host only: the launch plan of k_q41_chain for an M x K Q4_1 matrix and n_rows activation rows -- out = { activation rows of the compiled
+ * instance, weight rows per workgroup, threads per workgroup, grid x, grid y (row tiles of at most 16), slab length in byte pairs
+ * (2 elements each), dynamic LDS bytes, chain lanes per workgroup }.  For n_rows > 16 this is the plan of the full tiles; a last tile of
+ * n_rows % 16 rows is a launch of its own on the plan of that row count.  Returns 1, 0 where the kernel does not take the shape (K not a
+ * positive multiple of 32, m or n_rows < 1), -1 where the plan names an instance that was never compiled. */
+int32_t llamahip_debug_q41_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[8]);
 /* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_mfma_launches(void);
 /* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more

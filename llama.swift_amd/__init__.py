@@ -42,6 +42,7 @@ from .binding import (  # noqa: F401
     op_gemv_q4_0,
     op_logprob,
     op_mul_mat_dense,
+    op_mul_mat_q4_1,
     op_mul_mat_q4_0,
     op_prep,
     op_prompt_gemm_q4_0,
@@ -54,6 +55,8 @@ from .binding import (  # noqa: F401
     op_topk_slide_set,
     op_verify_rows,
     op_verify_rows_set,
+    q41_paths,
+    q41_plan,
     qa_to_blocks,
     quantize_file,
     sched_event_cap,

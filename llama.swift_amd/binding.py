@@ -238,6 +238,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_dense_mfma_launches.argtypes = []
     L.llamahip_debug_dense_mfma_launches.restype = C.c_int64
     L.llamahip_debug_dense_force.argtypes = [i32]
+    L.llamahip_op_mul_mat_q4_1.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
+    L.llamahip_debug_q41_paths.argtypes = [vp, i32]
+    L.llamahip_debug_q41_paths.restype = i32
+    L.llamahip_debug_q41_plan.argtypes = [i32, i32, i32, vp]
+    L.llamahip_debug_q41_plan.restype = i32
     L.llamahip_debug_dense_force.restype = i32
     L.llamahip_debug_live_allocs.argtypes = [vp, vp]
     L.llamahip_debug_live_allocs.restype = None
@@ -291,6 +296,25 @@ def dense_set_plan(m: int, k: int, wtype: int, n_rows: int):
     if rc < 0:
         raise LlamaHipError(rc, f"dense_set_plan({m}, {k}, wtype={wtype}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
     return dict(zip(("grid", "threads", "rows_per_half_wave", "rows", "slab_groups", "lds_bytes"), (int(x) for x in a))) if rc else None
+
+
+def q41_paths() -> dict:
+    """Q4_1 mat-muls per kernel since process start (llamahip_debug_q41_paths): chain = k_q41_chain, lane = k_q41_mm."""
+    a = np.zeros(4, np.int64)
+    n = lib().llamahip_debug_q41_paths(a.ctypes.data_as(C.c_void_p), 4)
+    return dict(zip(("chain", "lane"), a[:n].tolist()))
+
+
+def q41_plan(m: int, k: int, n_rows: int):
+    """Host-only: the launch plan of the Q4_1 mat-mul k_q41_chain (llamahip_debug_q41_plan) for n_rows rows against an m x k matrix: a dict,
+    or None where the kernel does not take the shape; a plan that names an instance that does not exist is an error.  For n_rows > 16 the
+    plan is that of the full tiles of 16; a last tile of n_rows % 16 rows runs on q41_plan(m, k, n_rows % 16)."""
+    a = np.zeros(8, np.int64)
+    rc = lib().llamahip_debug_q41_plan(m, k, n_rows, a.ctypes.data_as(C.c_void_p))
+    if rc < 0:
+        raise LlamaHipError(rc, f"q41_plan({m}, {k}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
+    names = ("rows", "rows_per_workgroup", "threads", "grid_x", "grid_y", "slab_pairs", "lds_bytes", "chain_lanes")
+    return dict(zip(names, (int(x) for x in a))) if rc else None
 
 
 def dense_mfma_plan(m: int, k: int, wtype: int, n_rows: int):
@@ -1298,6 +1322,33 @@ def op_mul_mat_dense(w: np.ndarray, x: np.ndarray, resid=None, path: str = "auto
     rc = lib().llamahip_op_mul_mat_dense(_ptr(w), wt, M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
     _check(rc, err)
     return y, DENSE_PATHS[taken.value]
+
+
+Q41_PATHS = ("auto", "chain", "lane")      # LLAMAHIP_Q41_* of llamahip.h, in order
+
+
+def op_mul_mat_q4_1(w: np.ndarray, x: np.ndarray, resid=None, path: str = "auto", y_stride: int | None = None, y_init=None, K: int | None = None):
+    """One Q4_1 mat-mul kernel (llamahip_op_mul_mat_q4_1): w uint8 [M, K/32 * 24], the rows in file layout ([K/32 f32 min][K/32 f32 d][K/32 * 16
+    nibble bytes]); x f32 [N, K], resid f32 [N, M] or None.  path: one of Q41_PATHS.  Returns (y f32 [N, y_stride], the path taken): the
+    whole buffer as the device left it -- y_init (default: NaN everywhere) is what columns M .. y_stride - 1 keep.  K overrides the row
+    length the shape of w implies (refusal tests)."""
+    w = np.ascontiguousarray(w, np.uint8)
+    M, rb = w.shape
+    x = np.ascontiguousarray(x, np.float32)
+    if K is None:
+        K = rb // 24 * 32
+        x = x.reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    code = Q41_PATHS.index(path) if path in Q41_PATHS else int(path)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_mul_mat_q4_1(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
+    _check(rc, err)
+    return y, Q41_PATHS[taken.value]
 
 
 ATTN_PATHS = ("auto", "mfma", "row", "short", "dec", "dec_stream")      # LLAMAHIP_ATTN_* of llamahip.h, in order

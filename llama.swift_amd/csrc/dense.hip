@@ -778,10 +778,16 @@ hipError_t go(const DMat &w, int epi, const float *x, long x_stride, int N, floa
 //   dot product   ggml_vec_dot_q4_1 (ggml.c:1584-1626): ONE float accumulator per output, walked over all
 //                 blocks and byte pairs in order:  sumf += (d0*q0 + m0) * (d1*p0 + m1) + (d0*q1 + m0) * (d1*p1 + m1)
 //                 with every product and sum rounded separately (-std=c11: no contraction).
-// There is no parallelism inside an output, so a lane owns a whole weight row; the activation side
-// (d1*p + m1, the same for every row) is expanded once per mat-mul by k_q41_act and reaches the lanes
-// as SGPR operands.  Weights are regrouped at load into [row-block of 64][block][lane] so that a wave's
-// loads are coalesced.  Correct first, not fast: K/2 dependent additions per output.
+// The activation side (d1*p + m1, the same for every weight row) is expanded once per mat-mul by k_q41_act.
+// Weights are regrouped at load into [row-block of 64][block][lane] so that a wave's loads are coalesced.
+// Two kernels read that one copy:
+//   k_q41_mm     a lane owns a whole weight row and does everything for it, one activation row per workgroup:
+//                K/2 dependent additions behind a dozen instructions each.  Kept as the plain statement of the
+//                arithmetic (llamahip_op_mul_mat_q4_1, path LANE); model handles no longer launch it.
+//   k_q41_chain  the pair term p = f0*a0 + f1*a1 does not depend on the accumulator, so any lane may form it;
+//                only sum = sum + p has to run in pair order.  Product waves form the terms of a slab for up to
+//                16 activation rows from ONE dequantisation of the weights and park them in LDS; one chain lane
+//                per output adds them up in order while the product waves fill the other buffer (q41_plan).
 // ------------------------------------------------------------------------------------------------
 typedef uint32_t du32x4 __attribute__((ext_vector_type(4)));
 typedef float df32x2 __attribute__((ext_vector_type(2)));
@@ -855,6 +861,177 @@ k_q41_mm(const df32x2 *__restrict__ md, const du32x4 *__restrict__ nbv, int M, i
     if (m < M) {
         if (EPI == EPI_RESID) sum = sum + resid[(size_t) n * resid_stride + m];
         y[(size_t) n * y_stride + m] = sum;
+    }
+}
+
+// k_q41_chain<NR, EPI>: Q41_R weight rows x up to NR activation rows (n_base ..) per workgroup, C = Q41_R * NR outputs, slabs of
+// S = q41_slab_pairs(NR) byte pairs.
+//   threads 0 .. 255 (waves 0 .. 3), product role: thread = (row r = t & 15, word slot (t >> 4) & 15).  A word is 4 nibble bytes = 4 byte pairs
+//     of one row; the thread dequantises its 8 weights once and forms the 4 pair terms of each activation row, every product and sum
+//     rounded on its own as k_q41_mm rounds them, then parks them as one 16-byte store at terms[word][n * Q41_R + r].  The 16 rows of
+//     a word share their activations: the product threads stage the slab's NR x 2S floats in LDS with coalesced loads and read them
+//     back as broadcasts.  Nothing a slab needs from global memory is waited for inside it: the words and the activation slab of
+//     slab s + 1 are requested before slab s is computed, and land in registers / the other activation buffer behind it.
+//     From 12 rows on the slab is 32 pairs = 8 words, so that two workgroups share a CU (72 KiB of LDS at 16 rows) and one's barriers
+//     and LDS traffic overlap the other's arithmetic; the two halves of the product threads then split the activation rows of the
+//     same words (the dequantisation is done twice).
+//   the threads behind them, chain role: thread c < C owns output (n = c >> 4, r = c & 15) and adds its terms in pair order, 16-byte
+//     reads issued three blocks of 16 pairs ahead of their use; sum lives in a register from slab to slab.
+// A chain lane's 16 bytes sit next to its neighbours' (a wave reads 1 KiB contiguous: no bank conflict in any 16-lane group), and so
+// do the 16 rows of a product store.  The roles meet at ONE __syncthreads() per slab on two buffers: at step s the product waves fill
+// buffer s & 1 while the chain waves drain the other; nslab is a kernel argument, so every thread runs 1 + nslab barriers.  Row
+// tails are predicated: weight rows past M are the repack's zero rows, activation rows past N re-read row N - 1, neither is stored.
+// LDS: terms[2][S/4][C] float4, then act[2][NR][S/2] float4 (q41_plan's lds).
+// (Q41_R = 16 weight rows, the product threads, the compiled NR and their slab: q41_plan.h)
+template <int NR, int EPI>
+__global__ void __launch_bounds__(q41_prod_threads(NR) + (Q41_R * NR + 63) / 64 * 64)
+k_q41_chain(const df32x2 *__restrict__ md, const uint32_t *__restrict__ nbw, int M, int nb, const float *__restrict__ a, int K, int N, int n_base,
+            int nslab, float *__restrict__ y, long y_stride, const float *__restrict__ resid, long resid_stride) {
+    extern __shared__ __attribute__((aligned(16))) float q41_lds[];
+    constexpr int C = Q41_R * NR, S = q41_slab_pairs(NR);
+    constexpr int G = S / 4;                                 // words (16-byte term groups) per row and slab
+    constexpr int PROD = q41_prod_threads(NR);               // product threads
+    constexpr int WSLOTS = G < PROD / Q41_R ? G : PROD / Q41_R;      // word slots: 16, or the 8 words of a 32-pair slab ...
+    constexpr int NSPLIT = PROD / (Q41_R * WSLOTS);          // ... whose product threads then split the activation rows in two halves
+    constexpr int NH = NR / NSPLIT;                          // activation rows per product thread
+    constexpr int WPT = G / WSLOTS;                          // words per product thread and slab
+    constexpr int AROW = S / 2, AF4 = NR * AROW;             // float4 per activation row and slab, per slab
+    constexpr int APT = (AF4 + PROD - 1) / PROD;             // ... per product thread
+    static_assert(G % WSLOTS == 0 && WPT >= 1 && NR % NSPLIT == 0 && Q41_R * WSLOTS * NSPLIT == PROD, "a slab is whole rounds of the product threads");
+    const int tid = threadIdx.x;
+    const int P = nb * 16;                                   // byte pairs per row
+    const int n0 = n_base + blockIdx.y * NR;
+    float4 *terms = (float4 *) q41_lds, *act = (float4 *) q41_lds + 2 * G * C;
+    if (tid < PROD) {
+        const int r = tid & (Q41_R - 1), ws = (tid >> 4) & (WSLOTS - 1), nlo = tid / (Q41_R * WSLOTS) * NH;
+        const size_t rowbase = (size_t) (blockIdx.x >> 2) * nb * 64 + (blockIdx.x & 3) * Q41_R + r;
+        df32x2 wm[WPT], wm_next[WPT];
+        uint32_t bits[WPT], bits_next[WPT];
+        float4 areg[APT];
+        // the words and the activations of slab s, guarded by what the slab holds (the last one may be short)
+        auto fetch = [&](int s, df32x2 *m_, uint32_t *b_) {
+            const int pairs = min(S, P - s * S);
+#pragma unroll
+            for (int k = 0; k < WPT; k++) {
+                const int w = ws + k * WSLOTS;
+                m_[k] = df32x2{ 0.0f, 0.0f }; b_[k] = 0u;
+                if (4 * w < pairs) {
+                    const int gw = s * G + w, i = gw >> 2, q = gw & 3;
+                    m_[k] = md[rowbase + (size_t) i * 64];
+                    b_[k] = nbw[(rowbase + (size_t) i * 64) * 4 + q];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < APT; k++) {
+                const int e = tid + k * PROD, n = e / AROW, e4 = e % AROW;
+                areg[k] = float4{ 0.0f, 0.0f, 0.0f, 0.0f };
+                if (e < AF4 && 2 * e4 < pairs) areg[k] = *(const float4 *) (a + (size_t) min(n0 + n, N - 1) * K + (size_t) s * 2 * S + 4 * e4);
+            }
+        };
+        auto park = [&](int s) {
+#pragma unroll
+            for (int k = 0; k < APT; k++) {
+                const int e = tid + k * PROD;
+                if (e < AF4) act[(s & 1) * AF4 + e] = areg[k];
+            }
+        };
+        fetch(0, wm, bits);
+        park(0);
+        __syncthreads();
+        for (int s = 0; s < nslab; s++) {
+            if (s + 1 < nslab) fetch(s + 1, wm_next, bits_next);
+            float4 *buf = terms + (s & 1) * G * C;
+            const float4 *as = act + (s & 1) * AF4;
+            const int pairs = min(S, P - s * S);
+#pragma unroll
+            for (int k = 0; k < WPT; k++) {
+                const int w = ws + k * WSLOTS;
+                if (4 * w < pairs) {
+                    float f[8];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const uint32_t b = (bits[k] >> (8 * j)) & 0xFF;
+                        f[2 * j] = wm[k].y * (float) (b & 0xF) + wm[k].x;
+                        f[2 * j + 1] = wm[k].y * (float) (b >> 4) + wm[k].x;
+                    }
+#pragma unroll
+                    for (int n = nlo; n < nlo + NH; n++) {
+                        const float4 a0 = as[n * AROW + 2 * w], a1 = as[n * AROW + 2 * w + 1];
+                        float4 p;
+                        { const float t = f[0] * a0.x, u = f[1] * a0.y; p.x = t + u; }
+                        { const float t = f[2] * a0.z, u = f[3] * a0.w; p.y = t + u; }
+                        { const float t = f[4] * a1.x, u = f[5] * a1.y; p.z = t + u; }
+                        { const float t = f[6] * a1.z, u = f[7] * a1.w; p.w = t + u; }
+                        buf[w * C + n * Q41_R + r] = p;
+                    }
+                }
+            }
+            if (s + 1 < nslab) {
+                park(s + 1);
+#pragma unroll
+                for (int k = 0; k < WPT; k++) { wm[k] = wm_next[k]; bits[k] = bits_next[k]; }
+            }
+            __syncthreads();
+        }
+    } else {
+        const int c = tid - PROD;
+        const bool live = c < C;
+        float sum = 0.0f;
+        __syncthreads();                                     // (the product role's first activation slab)
+        for (int s = 0; s < nslab; s++) {
+            __syncthreads();
+            if (live) {
+                const float4 *bp = terms + (s & 1) * G * C + c;
+                const int nblk = (min(S, P - s * S)) >> 4;      // blocks of 16 pairs = 4 reads
+                // Whole groups of 4 blocks (every slab but a short last one is made of them) run through a ring of 4 blocks in
+                // registers, straight-line: block b + 3 is requested before block b is added up; the last three requests of a slab
+                // re-read its last block and are dropped.
+                const int nq4 = nblk & ~3;
+                if (nq4) {
+                    float4 ring[4][4];
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+#pragma unroll
+                        for (int j = 0; j < 4; j++) ring[k][j] = bp[(size_t) (4 * k + j) * C];
+                    for (int b = 0; b < nq4; b += 4) {
+#pragma unroll
+                        for (int k = 0; k < 4; k++) {
+                            const int nx = min(b + k + 3, nq4 - 1);
+#pragma unroll
+                            for (int j = 0; j < 4; j++) ring[(k + 3) & 3][j] = bp[(size_t) (4 * nx + j) * C];
+#pragma unroll
+                            for (int j = 0; j < 4; j++) {
+                                const float4 v = ring[k][j];
+                                sum = sum + v.x; sum = sum + v.y; sum = sum + v.z; sum = sum + v.w;
+                            }
+                        }
+                    }
+                }
+                if (S < 64) {                               // a slab of two blocks: both requested, then added (the second where it exists)
+                    float4 v[8];
+#pragma unroll
+                    for (int j = 0; j < 8; j++) v[j] = bp[j * C];
+#pragma unroll
+                    for (int j = 0; j < 4; j++) { sum = sum + v[j].x; sum = sum + v[j].y; sum = sum + v[j].z; sum = sum + v[j].w; }
+                    if (nblk > 1) {
+#pragma unroll
+                        for (int j = 4; j < 8; j++) { sum = sum + v[j].x; sum = sum + v[j].y; sum = sum + v[j].z; sum = sum + v[j].w; }
+                    }
+                } else
+                for (int b = nq4; b < nblk; b++) {          // a last slab's odd blocks
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const float4 v = bp[(size_t) (4 * b + j) * C];
+                        sum = sum + v.x; sum = sum + v.y; sum = sum + v.z; sum = sum + v.w;
+                    }
+                }
+            }
+        }
+        const int n = n0 + (c >> 4), m = blockIdx.x * Q41_R + (c & (Q41_R - 1));
+        if (live && n < N && m < M) {
+            if (EPI == EPI_RESID) sum = sum + resid[(size_t) n * resid_stride + m];
+            y[(size_t) n * y_stride + m] = sum;
+        }
     }
 }
 
@@ -991,15 +1168,37 @@ hipError_t init_attrs_dense() {
 #define LH_ATTR(KERNEL) do { hipError_t e_ = hipFuncSetAttribute((const void *) KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, cap); if (e_ != hipSuccess) return e_; } while (0)
     LH_ATTR((k_dense_mfma<0, EPI_STORE, 1>)); LH_ATTR((k_dense_mfma<0, EPI_RESID, 1>)); LH_ATTR((k_dense_mfma<0, EPI_STORE, 2>)); LH_ATTR((k_dense_mfma<0, EPI_RESID, 2>));
     LH_ATTR((k_dense_mfma<1, EPI_STORE, 1>)); LH_ATTR((k_dense_mfma<1, EPI_RESID, 1>)); LH_ATTR((k_dense_mfma<1, EPI_STORE, 2>)); LH_ATTR((k_dense_mfma<1, EPI_RESID, 2>));
+#define LH_Q41_ATTR(NR) LH_ATTR((k_q41_chain<NR, EPI_STORE>)); LH_ATTR((k_q41_chain<NR, EPI_RESID>));
+    LH_Q41_INSTANCES(LH_Q41_ATTR)          // k_q41_chain's two slab buffers: up to 128 KB
+#undef LH_Q41_ATTR
 #undef LH_ATTR
     return hipSuccess;
 }
 
-hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
-                           const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken) {
-    if (w.wtype == 3) {
-        if (w.K % 32 != 0 || !scratch) return hipErrorInvalidValue;
-        hipLaunchKernelGGL(k_q41_act, dim3(N), dim3(64), 0, st, x, x_stride, w.K, scratch);
+static hipError_t go_q41_chain(const Q41Plan &p, int grid_y, int n_base, const DMat &w, int epi, int N, float *y, long y_stride,
+                               const float *resid, long resid_stride, hipStream_t st, const float *scratch) {
+    if (!q41_plan_has_kernel(p)) return hipErrorInvalidValue;
+    const dim3 grid(p.grid_x, grid_y);
+    const int nb = w.K / 32, nslab = (nb * 16 + p.slab - 1) / p.slab;
+#define LH_GO(NR) if (p.nr == NR) { \
+        if (epi == EPI_RESID) hipLaunchKernelGGL((k_q41_chain<NR, EPI_RESID>), grid, dim3(p.threads), p.lds, st, (const df32x2 *) w.w, (const uint32_t *) w.w2, w.M, nb, scratch, w.K, N, n_base, nslab, y, y_stride, resid, resid_stride); \
+        else hipLaunchKernelGGL((k_q41_chain<NR, EPI_STORE>), grid, dim3(p.threads), p.lds, st, (const df32x2 *) w.w, (const uint32_t *) w.w2, w.M, nb, scratch, w.K, N, n_base, nslab, y, y_stride, resid, resid_stride); \
+    }
+    LH_Q41_INSTANCES(LH_GO)
+#undef LH_GO
+    return hipGetLastError();
+}
+
+// Q4_1 mat-mul: k_q41_act, then k_q41_chain in row tiles of at most 16 (AUTO, CHAIN) or k_q41_mm (LANE: llamahip_op_mul_mat_q4_1 only)
+hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
+                         const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken) {
+    if (w.wtype != 3 || w.K < 32 || w.K % 32 != 0 || !scratch || N < 1 || path < Q41_PATH_AUTO || path > Q41_PATH_LANE) return hipErrorInvalidValue;
+    const int run = path == Q41_PATH_AUTO ? Q41_PATH_CHAIN : path;
+    if (run == Q41_PATH_CHAIN && !q41_plan(w.M, w.K, N).nr) return hipErrorInvalidValue;
+    if (path_taken) *path_taken = run;
+    hipLaunchKernelGGL(k_q41_act, dim3(N), dim3(64), 0, st, x, x_stride, w.K, scratch);
+    if (run == Q41_PATH_LANE) {
+        g_q41_path_counts[Q41_COUNT_LANE]++;
         const dim3 grid((w.M + 63) / 64, N);
         if (epi == EPI_RESID)
             hipLaunchKernelGGL((k_q41_mm<EPI_RESID>), grid, dim3(64), 0, st, (const df32x2 *) w.w, (const du32x4 *) w.w2, w.M, w.K / 32, scratch, w.K, N, y, y_stride, resid, resid_stride);
@@ -1007,6 +1206,19 @@ hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride
             hipLaunchKernelGGL((k_q41_mm<EPI_STORE>), grid, dim3(64), 0, st, (const df32x2 *) w.w, (const du32x4 *) w.w2, w.M, w.K / 32, scratch, w.K, N, y, y_stride, resid, resid_stride);
         return hipGetLastError();
     }
+    g_q41_path_counts[Q41_COUNT_CHAIN]++;
+    const int full = N / Q41_TILE, rem = N % Q41_TILE;
+    if (full) {
+        const hipError_t e = go_q41_chain(q41_plan(w.M, w.K, Q41_TILE), full, 0, w, epi, N, y, y_stride, resid, resid_stride, st, scratch);
+        if (e != hipSuccess) return e;
+    }
+    if (rem) return go_q41_chain(q41_plan(w.M, w.K, rem), 1, full * Q41_TILE, w, epi, N, y, y_stride, resid, resid_stride, st, scratch);
+    return hipSuccess;
+}
+
+hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
+                           const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken) {
+    if (w.wtype == 3) return launch_q41_mm(w, epi, x, x_stride, N, y, y_stride, resid, resid_stride, st, scratch, Q41_PATH_AUTO, nullptr);
     if (w.K % 32 != 0 || (w.wtype != 0 && w.wtype != 1) || !scratch) return hipErrorInvalidValue;
     if (N < 1 || path < DENSE_PATH_AUTO || path > DENSE_PATH_MFMA || (path == DENSE_PATH_SET && N > DENSE_SET_MAX_ROWS)) return hipErrorInvalidValue;
     if (path == DENSE_PATH_MFMA && !dense_mfma_plan(w.M, w.K, w.wtype, N).ok) return hipErrorInvalidValue;

@@ -1245,7 +1245,7 @@ int llamahip_eval(llamahip_model *m, int32_t n_threads, int32_t n_past,
 // same bits -- every operator of the graph works row by row except the V*P key split, which depends on the eval a row belongs to
 // (prompt_attn.hip split_keys) and is applied per row here -- at the speed of a long eval (matrix-core GEMMs) instead of 9-row ones.
 // f16 / f32 files take the one pass from DENSE_ONE_PASS_MIN_ROWS rows (below it the chunk loop on k_dense_set measured no slower: DESIGN.md
-// 12.18); Q4_1 files (one slow kernel, correct first) keep the loop.  A pipeline handle's front is loaded HOST_ONLY and never learns the file
+// 12.18); Q4_1 files (no one-pass chunked eval: DESIGN.md 12.24) keep the loop.  A pipeline handle's front is loaded HOST_ONLY and never learns the file
 // type: its stages know it.
 static bool chunks_in_one_pass(const llamahip_model *m, int n_tokens) {
     if (m->host_only && m->stages.empty()) return false;
@@ -4277,6 +4277,20 @@ int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32
     const int64_t o[6] = { p.grid, p.hw * 32, p.rg, p.nr, p.slab, p.lds };
     for (int i = 0; i < 6; i++) out[i] = o[i];
     return dense_set_plan_has_kernel(p) ? 1 : -1;
+}
+
+int32_t llamahip_debug_q41_paths(int64_t *out, int32_t cap) {
+    for (int i = 0; out && i < cap && i < Q41_COUNT_N; i++) out[i] = g_q41_path_counts[i];
+    return Q41_COUNT_N;
+}
+
+int32_t llamahip_debug_q41_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[8]) {
+    if (!out) return 0;
+    const Q41Plan p = q41_plan(m, k, n_rows);
+    if (!p.nr) return 0;
+    const int64_t o[8] = { p.nr, p.rows, p.threads, p.grid_x, p.grid_y, p.slab, p.lds, p.chain };
+    for (int i = 0; i < 8; i++) out[i] = o[i];
+    return q41_plan_has_kernel(p) ? 1 : -1;
 }
 
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "q41_plan.h"
+
 namespace lh {
 
 constexpr int MT4_TILE_BYTES = 4608;   // k_gemm_mfma4's weight tile: 32 rows x 4 Q4_0 blocks, one byte per weight + 128 fp32 scales
@@ -63,8 +65,8 @@ struct QMat {
 
 // an f16 / f32 weight matrix (file layout: row-major [M][K]) of a dense model file (dense.hip)
 struct DMat {
-    void *w = nullptr;          // fp32 / fp16: the rows; Q4_1: {min, d} pairs [row-block of 64][block][lane]
-    void *w2 = nullptr;         // Q4_1: the 16 nibble bytes in the same order
+    void *w = nullptr;          // fp32 / fp16: the rows; Q4_1: {min, d} pairs [row-block of 64][block][lane] -- the one resident copy,
+    void *w2 = nullptr;         // Q4_1: the 16 nibble bytes in the same order             read by k_q41_chain and k_q41_mm alike
     int M = 0, K = 0;
     int wtype = 0;              // 0 fp32, 1 fp16, 3 Q4_1
     size_t bytes() const { return wtype == 3 ? (size_t) ((M + 63) / 64) * 64 * (K / 32) * 8 : (size_t) M * K * (wtype == 1 ? 2 : 4); }
@@ -73,7 +75,7 @@ struct DMat {
 // The f16 / f32 mat-mul kernels (dense.hip), = LLAMAHIP_DENSE_* of llamahip.h: k_dense_mv (one row; forced with more rows: one launch per row),
 // k_dense_mm (any row count, the rows on gridDim.y: the weights are streamed once per 8 rows), k_dense_set (1 .. 16 rows, the weights streamed
 // once), k_dense_mfma (more than 16 rows, K a multiple of 128: the chains on the fp32 matrix cores, the weights streamed once per 64 rows).
-// AUTO: one row MV, more by dense_auto_path (dense.hip).  Q4_1 has one kernel and ignores the path.
+// AUTO: one row MV, more by dense_auto_path (dense.hip).  Q4_1 ignores this path: launch_q41_mm and Q41_PATH_* below.
 enum { DENSE_PATH_AUTO = 0, DENSE_PATH_MV = 1, DENSE_PATH_MM = 2, DENSE_PATH_SET = 3, DENSE_PATH_MFMA = 4 };
 enum { DENSE_COUNT_MV = 0, DENSE_COUNT_MM = 1, DENSE_COUNT_SET = 2, DENSE_COUNT_N = 3 };
 extern long g_dense_path_counts[DENSE_COUNT_N];      // launches per kernel (process-wide; tests)
@@ -99,6 +101,9 @@ hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride
                            const float *resid, long resid_stride, hipStream_t st, float *scratch = nullptr,
                            int path = DENSE_PATH_AUTO, int *path_taken = nullptr);
 hipError_t launch_q41_repack(const uint8_t *raw_rows, DMat &w, hipStream_t st);
+// Q4_1 mat-mul: the paths, counters and k_q41_chain's launch plan are q41_plan.h's (host-only); scratch: N * K floats, the expanded operand
+hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
+                         const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken);
 bool dense_prep_applies(int wtype, int mode, int K);
 hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride,
                              int K, int N, float *scratch, const uint16_t *T_silu, hipStream_t st);

@@ -226,6 +226,34 @@ int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K
     return LLAMAHIP_OK;
 }
 
+// one Q4_1 mat-mul kernel on caller-supplied operands (per-op tests of both kernels launch_q41_mm can run): see llamahip.h
+int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                             float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_mul_mat_q4_1";
+    if (q41_op_check(w_q4_1, M, K, x, N, y, y_stride, path, err, err_cap)) return LLAMAHIP_ERR_PREDICT;          // (q41_plan.cpp: host-only)
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    DMat dm;
+    dm.M = M; dm.K = K; dm.wtype = 3;
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_raw = s.alloc((size_t) M * (K / 32) * 24, (const uint8_t *) w_q4_1);
+    dm.w = s.alloc<uint8_t>(dm.bytes());
+    dm.w2 = s.alloc<uint8_t>(dm.bytes2());
+    float *d_x = s.alloc((size_t) N * K, x);
+    float *d_y = s.alloc((size_t) N * y_stride, y);      // (the floats between M and y_stride keep the caller's bits)
+    float *d_r = resid ? s.alloc((size_t) N * M, resid) : nullptr;
+    float *d_ws = s.alloc<float>((size_t) N * K);
+    if (s.ok()) s.check(launch_q41_repack(d_raw, dm, st));
+    int taken = 0;
+    if (s.ok()) s.check(launch_q41_mm(dm, resid ? EPI_RESID : EPI_STORE, d_x, K, N, d_y, y_stride, d_r, M, st, d_ws, path, &taken));
+    s.download(y, d_y, (size_t) N * y_stride * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (path_taken) *path_taken = taken;
+    return LLAMAHIP_OK;
+}
+
 // one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
 int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
                           int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,

@@ -13,12 +13,14 @@
 #include <cstring>
 #include <random>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/llama_runner.h"
 #include "../../../include/llamahip.h"
 #include "../dev_owner.h"
 #include "../model_file.h"
+#include "../q41_plan.h"
 #include "../sched.h"
 
 struct llamahip_model { lh::ModelFile file; lh::SchedDev *sched = nullptr; };
@@ -1034,6 +1036,39 @@ int main(int argc, char **argv) {
             llamahip_model_free(ms);
         }
         printf("host_sanitize: scheduler host half: %zu steps logged in the last run\n", g_sched_calls.size());
+    }
+    {   // the Q4_1 mat-mul's host half (q41_plan.cpp): the plan over the model and test shapes, and every refusal of llamahip_op_mul_mat_q4_1 on
+        // exactly sized message buffers (a one-byte one included)
+        using namespace lh;
+        const int widths[4][2] = { { 4096, 11008 }, { 5120, 13824 }, { 6656, 17920 }, { 8192, 22016 } };
+        std::vector<std::pair<int, int>> shapes;
+        for (auto &w : widths) for (auto mk : { std::pair<int, int>{ 3 * w[0], w[0] }, { w[0], w[0] }, { 2 * w[1], w[0] }, { w[0], w[1] }, { 32000, w[0] } }) shapes.push_back(mk);
+        for (int K : { 32, 64, 224, 256, 288, 320, 544, 896, 1376, 4096, 11008 }) for (int M : { 1, 15, 16, 17, 64, 65, 200 }) shapes.push_back({ M, K });
+        int plans = 0;
+        for (auto &mk : shapes)
+            for (int N : { 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 100, 1048560 }) {
+                const Q41Plan p = q41_plan(mk.first, mk.second, N);
+                EXPECT(p.nr >= std::min(N, 16) && p.nr <= 16 && q41_plan_has_kernel(p));
+                EXPECT(p.lds <= 160 * 1024 && (int64_t) p.grid_x * p.rows >= mk.first && (int64_t) (p.grid_x - 1) * p.rows < mk.first && p.grid_y == (N + 15) / 16);
+                plans++;
+            }
+        EXPECT(!q41_plan(0, 64, 1).nr && !q41_plan(8, 48, 1).nr && !q41_plan(8, 0, 1).nr && !q41_plan(8, 64, 0).nr && !q41_plan(8, 64, 1048561).nr);
+        EXPECT(!q41_plan_has_kernel(Q41Plan{ 3, 16, 320, 1, 1, 64, 2 * 64 * 48 * 4, 48 }));            // (3 rows is no compiled instance)
+        const float xy = 0.0f;
+        const uint8_t wq = 0;
+        struct { int32_t M, K, N, ys, path; const void *w; const char *says; } bad[] = {
+            { 8, 48, 2, 8, 0, &wq, "K 48 must be a positive multiple of 32" }, { 8, 0, 2, 8, 0, &wq, "K 0 must be" }, { 8, 64, 0, 8, 0, &wq, "N 0 must be >= 1" },
+            { 0, 64, 2, 8, 0, &wq, "M 0 must be >= 1" }, { 8, 64, 2, 7, 0, &wq, "y_stride 7 < M 8" }, { 8, 64, 2, 8, 3, &wq, "unknown path 3" },
+            { 8, 64, 2, 8, -1, &wq, "unknown path -1" }, { 8, 64, 2, 8, 1, nullptr, "not NULL" }, { 8, 64, 1048561, 8, 1, &wq, "row tiles" },
+        };
+        for (auto &b : bad) {
+            std::vector<char> e(256, 0), e1(1, 'x');
+            EXPECT(q41_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, b.path, e.data(), e.size()) == -1 && strstr(e.data(), b.says));
+            EXPECT(q41_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, b.path, e1.data(), e1.size()) == -1 && e1[0] == 0);
+            EXPECT(q41_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, b.path, nullptr, 0) == -1);
+        }
+        EXPECT(q41_op_check(&wq, 8, 64, &xy, 17, &xy, 8, 2, err, sizeof(err)) == 0);
+        printf("host_sanitize: Q4_1 mat-mul host half: %d plans, %zu refusals\n", plans, sizeof(bad) / sizeof(bad[0]));
     }
     {   // the owner of device memory (dev_owner.h) on the stub allocator: groups are all-or-nothing at every failing call, release, destruction by kind
         using lh::DevOwner;

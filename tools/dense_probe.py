@@ -5,6 +5,7 @@ usage: dense_probe.py [n_layer]
        dense_probe.py [n_layer] --multi [--json OUT] [--repeats R] [--seqs 1,2,4,8,16] [--only-multi]
        dense_probe.py [n_layer] --prompt [--json OUT] [--repeats R] [--ftype f16|f32] [--force mm|mfma] [--evals 64,128,512]
                       [--chunks 18,36,72,144,504] [--trace-rows 17,32,64,128,512]
+       dense_probe.py [n_layer] --q41 [--json OUT] [--repeats R] [--evals 9,16,17,64,512] [--trace-rows 1,16]
 --multi (default 8 layers: 3.2 GB, larger than the Infinity Cache): ms per step and aggregate tokens/s of decode_greedy_multi for S sequences
 from position 256 for 64 steps, the 9-token eval, and the single-stream greedy loop; every figure is the wall time of a call that
 synchronises before it returns, after one untimed run of the same call (graph captures, first-touch allocations), R repeats each.
@@ -12,6 +13,10 @@ synchronises before it returns, after one untimed run of the same call (graph ca
 the 16-sequence set step, timed the same way; --force sends every mat-mul of more than 16 rows to one kernel (dense_force).  --trace-rows:
 nothing is timed -- per row count one untimed and R further eval_logprobs calls (the lm head over every row too) and exit, for a
 rocprofv3 --kernel-trace run that tools/dense_trace_summary.py reads.
+--q41 (default 8 layers): the f16 file of --prompt quantized with type 3 (Q4_1, kept next to it); ms per token of the single-stream greedy loop
+from position 256 for 64 steps and ms per eval of --evals rows, timed the same way; q41_paths where the library has it.  --trace-rows: nothing
+is timed -- per row count one untimed and R further evals (one row: a greedy loop of 1 + R steps, launched eagerly) and exit, for a rocprofv3
+--kernel-trace run.  Run it once per library (LLAMAHIP_LIB), fresh processes, alternating.
 LLAMAHIP_LIB / LLAMAHIP_DENSE_MM select the library / the mat-mul of 2 .. 16 rows as usual; the model file is kept for the next run."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,7 +27,8 @@ import llama_swift_amd as L
 
 args = sys.argv[1:]
 multi = "--multi" in args
-prompt_mode = "--prompt" in args
+q41_mode = "--q41" in args
+prompt_mode = "--prompt" in args or q41_mode
 opt = lambda k, d: args[args.index(k) + 1] if k in args else d
 nl = int(args[0]) if args and args[0].isdigit() else (8 if multi or prompt_mode else 4)
 ftype = opt("--ftype", "f16")
@@ -36,6 +42,45 @@ if not ((multi or prompt_mode) and os.path.exists(path)):
     synth.write_model_unquantized(path, hp, t, 0 if ftype == "f32" else 1)
     del t
 prompt = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 255)]).astype(np.int32)
+
+if q41_mode:
+    R = int(opt("--repeats", "3"))
+    ints = lambda k, d: [int(x) for x in opt(k, d).split(",") if x]
+    qpath = f"/tmp/dense7b_q41_{nl}.bin"
+    if not os.path.exists(qpath):
+        L.quantize_file(path, qpath, 3)
+    stream = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 511)]).astype(np.int32)
+    tracing = "--trace-rows" in args
+    m = L.Model(qpath, n_ctx=512, flags=1 if tracing else 0)          # (1 = LLAMAHIP_FLAG_NO_GRAPH: a kernel trace names the launches of a step)
+
+    def timed(fn):
+        fn()
+        out = []
+        for _ in range(R):
+            t0 = time.perf_counter(); fn(); out.append(round((time.perf_counter() - t0) * 1e3, 4))
+        return out
+    res = {"library": L.LIB_PATH, "ftype": "q41", "n_layer": nl, "file_gb": round(os.path.getsize(qpath) / 1e9, 2)}
+    if tracing:
+        for n in ints("--trace-rows", ""):
+            if n == 1:
+                m.eval(stream[:8], 0)
+                m.decode_greedy(int(stream[8]), 8, 1 + R)
+            else:
+                for _ in range(1 + R):
+                    m.eval(stream[:n], 0)
+        res["trace_rows"], res["repeats"] = ints("--trace-rows", ""), R
+    else:
+        first = int(np.argmax(m.eval(prompt, 0)))
+        res["decode_greedy_ms_per_token"] = [round(x / 64, 4) for x in timed(lambda: m.decode_greedy(first, 256, 64))]
+        res["eval_ms"] = {str(n): timed(lambda: m.eval(stream[:n], 0)) for n in ints("--evals", "9,16,17,64,512")}
+    if hasattr(L, "q41_paths"):
+        res["q41_paths"] = L.q41_paths()
+    print(json.dumps(res))
+    if "--json" in args:
+        with open(opt("--json", ""), "w") as f:
+            json.dump(res, f, indent=1)
+    m.close()
+    sys.exit(0)
 
 if prompt_mode:
     R = int(opt("--repeats", "3"))
