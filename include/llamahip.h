@@ -525,6 +525,67 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
 int32_t llamahip_eval_multi_rows(int32_t n_ctx, int32_t n_seqs, const int32_t *n_past, const int32_t *n_tokens,
                                  int32_t chunk_tokens, int32_t *row_seg, int32_t *row_pos, int32_t *row_keys);
 
+/* ---- scoring several texts in one weight pass ------------------------------------------------------------------------------------------
+ * llamahip_eval_logprobs streams every weight matrix once per text; a multiple-choice item -- one context, a few short endings -- pays that
+ * per ending for about ten useful rows.  llamahip_eval_logprobs_multi scores the segments of several KV slots in llamahip_eval_multi's ONE
+ * pass: the final norm and the lm head run over the SCORED rows only (gathered side by side in ascending row order, the lm head with the
+ * kernel a scoring eval of that many rows takes), k_row_logprob reduces those rows on the last stage's stream and 16 bytes per scored row
+ * come back, scattered to row order on the host.  No scored row: no lm head at all.
+ *
+ * Contract: for every i the call leaves, bit for bit, what llamahip_set_seq(slots[i]) + llamahip_eval_logprobs(n_past[i], tokens_i,
+ * n_tokens[i], chunk_tokens, targets_i, ...) leave on that slot alone -- logprob / argmax / rank of the scored rows, and KV rows
+ * [n_past[i], n_past[i] + n_tokens[i]) of every layer.  No other KV row is touched, the handle's current slot is left alone, the logits row
+ * map of llamahip_stage_logits is reset.  targets: R = sum n_tokens[i] ids in row order, -1 = not scored; NULL = the next token inside the
+ * row's segment, each segment's last row unscored.
+ * ONE DEVIATION: an unscored row takes no lm head, so it reports logprob 0.0, rank -1 and ARGMAX -1 (llamahip_eval_logprobs still computes
+ * that row's argmax).  Skipping the row is the point: the context rows of a whole-text scoring job never reach the lm head.  The per-slot
+ * loop below reports -1 there too, so the outputs do not depend on the path taken.
+ * (A one-token segment is a single-token eval on the yardstick side -- the fused decode step with one-pass norm statistics, two-pass here:
+ * equality there is BY TEST -- tests/test_gpu_score_multi.py -- not structural, as for llamahip_eval_multi.)
+ * Refused before any device work, the message naming the limit and this function, the handle last: what llamahip_eval_multi refuses of the
+ * same arguments, and a target outside [-1, n_vocab).
+ * Handles and fall-backs: llamahip_eval_multi's -- f16 / f32 / Q4_1 files, LLAMAHIP_FLAG_FAST_PREFILL handles, n_seqs == 1, and more than
+ * 1024 rows in segments of 512 rows or more each run llamahip_eval_logprobs slot by slot and report its eval count in stats->n_passes.
+ * Numbers (7B, one MI355X, n_past 64, every row scored, ms per call, median of five fresh processes; tools/score_probe.py,
+ * profiles/score_multi_probe_7b.json):
+ *   segments x rows    4 x 10   8 x 10   16 x 10   16 x 32   4 x 128
+ *   one pass             7.99    14.17     20.68     43.67     38.03
+ *   per-slot loop       12.70    25.39     50.42    111.36     59.04
+ *   No measured shape is slower than the loop, so the loop rule stays llamahip_eval_multi's.  llamahip_score_choices with four endings of 10
+ *   tokens behind a context of 64 / 256 tokens: 19.87 / 28.83 ms, against 59.89 / 93.24 for the per-choice sequence of its contract and
+ *   53.98 / 104.36 for four llamahip_eval_logprobs calls of the whole text.  DESIGN.md 12.25.
+ *
+ * llamahip_score_choices -- the multiple-choice call on KV slots 0 .. n_choices - 1, which it overwrites: the context is evaluated once on
+ * slot 0, rows [0, n_context - 1) are copied to the other slots in one stream-ordered launch (llamahip_kv_copy_rows' kernel, no host wait),
+ * and one pass of llamahip_eval_logprobs_multi scores segment i = [context[n_context - 1], ending_i[0 .. n_i - 1)] at n_context - 1 against
+ * the targets ending_i, every row scored.
+ * Contract: for every choice i, bit for bit, (1) if n_context > 1 llamahip_eval_chunks(0, context[0 .. n_context - 1), chunk_tokens)
+ * (chunk_tokens 0: llamahip_eval), then (2) llamahip_eval_logprobs at n_context - 1 of that segment in one eval, on slot i alone: the
+ * per-row logprobs, n_greedy[i] = the rows whose target had rank 0, KV rows [0, n_context - 1 + n_i) of slot i.  logprob_sum[i] =
+ * 0.0 + lp[0] + lp[1] + ..., summed in double in ascending row order on the host.  n_choices == 1 is that sequence itself.
+ * Refused before any device work: n_context < 1, n_choices outside 1 .. min(16, n_seq), n_ending[i] < 1, n_context - 1 + max(n_ending) >
+ * n_ctx, a token id out of range, chunk_tokens < 0, a handle with a live scheduler (its low slots are the scheduler's), HOST_ONLY and stage
+ * handles.  Picking the best choice is the caller's: n_choices doubles, and byte-length normalisation needs text the library does not have. */
+typedef struct llamahip_score_multi_stats {
+    int32_t struct_size;
+    int32_t n_rows;            /* sum of n_tokens */
+    int32_t n_scored_rows;     /* rows with a target: the rows the lm head ran over */
+    int32_t n_passes;          /* 1 = one pass over all rows; the per-slot loop reports its eval count */
+    int32_t n_short_segs, n_long_segs;   /* as llamahip_eval_multi_stats (0 on the per-slot loop) */
+} llamahip_score_multi_stats;
+int llamahip_eval_logprobs_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots,
+                                 const int32_t *n_past, const int32_t *tokens /* concatenated, n_tokens[i] each */,
+                                 const int32_t *n_tokens, int32_t chunk_tokens /* 0 = one eval per segment */,
+                                 const int32_t *targets /* [R], -1 = not scored; NULL = the next token inside the segment */,
+                                 double *logprob_out /* [R] */, int32_t *argmax_out /* [R] */, int32_t *rank_out /* [R]; any may be NULL */,
+                                 llamahip_score_multi_stats *stats /* may be NULL */, char *err, size_t err_cap);
+#define LLAMAHIP_SCORE_CHOICES_MAX 16
+int llamahip_score_choices(llamahip_model *m, int32_t n_threads, const int32_t *context, int32_t n_context /* >= 1 */,
+                           int32_t n_choices /* 1 .. 16, <= n_seq */, const int32_t *endings /* concatenated, n_ending[i] each */,
+                           const int32_t *n_ending /* each >= 1 */, int32_t chunk_tokens /* of the context eval; 0 = one eval */,
+                           double *logprob_sum /* [n_choices] */, int32_t *n_greedy /* [n_choices], may be NULL */,
+                           double *logprob_rows /* concatenated, n_ending[i] each; may be NULL */, char *err, size_t err_cap);
+
 /* ---- request scheduler: prompts admitted into a running multi-sequence decode --------------------------------------------------------
  * The *_multi loops above take their slots' contexts as given and run every sequence for the same n_steps; llamahip_eval_multi evaluates
  * several prompts in one pass.  The scheduler is the loop that joins them: requests wait in a queue, take a free KV slot, have their prompt

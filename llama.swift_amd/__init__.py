@@ -18,6 +18,7 @@ from .binding import (  # noqa: F401
     LIB_PATH,
     LlamaHipError,
     Model,
+    SCORE_CHOICES_MAX,
     Sampler,
     Scheduler,
     bench_gemv_names,

@@ -17,6 +17,7 @@ INCLUDE = os.path.join(ROOT, "include")
 
 ERR_LOAD, ERR_PREDICT = -1000, -1001
 CTX_REEVAL = 1          # LLAMAHIP_CTX_REEVAL: what to do when the KV cache is full
+SCORE_CHOICES_MAX = 16  # LLAMAHIP_SCORE_CHOICES_MAX: the endings of one Model.score_choices call
 DUMP_NAMES = [
     "layer_in", "attn_normed", "q", "k", "v", "q_roped", "kq_softmax", "kqv", "kqv_merged",
     "wo_out", "ffn_in", "ffn_normed", "w3_out", "w1_out", "silu_mul", "w2_out", "layer_out",
@@ -60,6 +61,11 @@ class _GemvBench(C.Structure):
 class _EvalMultiStats(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("n_rows", C.c_int32), ("n_passes", C.c_int32), ("n_short_segs", C.c_int32),
                 ("n_long_segs", C.c_int32), ("attn_groups", C.c_int32)]
+
+
+class _ScoreMultiStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("n_rows", C.c_int32), ("n_scored_rows", C.c_int32), ("n_passes", C.c_int32),
+                ("n_short_segs", C.c_int32), ("n_long_segs", C.c_int32)]
 
 
 class _LookupStats(C.Structure):
@@ -195,6 +201,8 @@ def lib() -> C.CDLL:
     L.llamahip_eval_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
     L.llamahip_eval_multi_rows.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
     L.llamahip_eval_multi_rows.restype = i32
+    L.llamahip_eval_logprobs_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, C.POINTER(_ScoreMultiStats), cp, sz]
+    L.llamahip_score_choices.argtypes = [vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, cp, sz]
     L.llamahip_sched_new.argtypes = [vp, C.POINTER(_SchedOpts), C.POINTER(vp), cp, sz]
     L.llamahip_sched_submit.argtypes = [vp, C.POINTER(_Request), C.POINTER(C.c_int64), cp, sz]
     L.llamahip_sched_step.argtypes = [vp, vp, i32, C.POINTER(i32), cp, sz]
@@ -679,6 +687,56 @@ class Model:
         _check(rc, err)
         logits = logits[:slots.size]
         return (logits, {k: getattr(st, k) for k, _ in _EvalMultiStats._fields_ if k != "struct_size"}) if want_stats else logits
+
+    def eval_logprobs_multi(self, slots, n_past, token_lists, targets=None, chunk_tokens: int = 0, n_threads: int = 8, want_stats: bool = False) -> dict:
+        """llamahip_eval_logprobs_multi: token_lists[i] evaluated at n_past[i] on KV slot slots[i] and scored, all in one weight pass.  targets:
+        one id per row over all segments (a flat array or one list per segment), -1 = not scored; None = the next token inside the row's
+        segment.  Returns logprob / argmax / rank [R] in row order (an unscored row: 0.0 / -1 / -1) and seg_begin, the segments' first rows
+        (with want_stats: + stats, the llamahip_score_multi_stats fields)."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        toks = [np.ascontiguousarray(t, np.int32).ravel() for t in token_lists]
+        if not (slots.size == npast.size == len(toks)):
+            raise ValueError(f"eval_logprobs_multi: {slots.size} slots, {npast.size} n_past, {len(toks)} token lists")
+        nt = np.array([t.size for t in toks], np.int32)
+        R = int(nt.sum())
+        flat = np.ascontiguousarray(np.concatenate(toks), np.int32) if R else np.zeros(1, np.int32)
+        if targets is not None:
+            if len(targets) and not np.isscalar(targets[0]):
+                targets = np.concatenate([np.ascontiguousarray(t, np.int32).ravel() for t in targets])
+            targets = np.ascontiguousarray(targets, np.int32).ravel()
+            if targets.size != R:
+                raise ValueError(f"eval_logprobs_multi: {targets.size} targets for {R} rows")
+            if not R:
+                targets = np.zeros(1, np.int32)
+        lp, am, rk = np.empty(max(R, 1), np.float64), np.empty(max(R, 1), np.int32), np.empty(max(R, 1), np.int32)
+        st = _ScoreMultiStats(C.sizeof(_ScoreMultiStats))
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_eval_logprobs_multi(self._h, n_threads, slots.size, _ptr(slots), _ptr(npast), _ptr(flat), _ptr(nt), int(chunk_tokens),
+                                                _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk), C.byref(st), err, len(err))
+        _check(rc, err)
+        out = {"logprob": lp[:R], "argmax": am[:R], "rank": rk[:R], "seg_begin": [int(b) for b in np.cumsum(nt) - nt]}
+        if want_stats:
+            out["stats"] = {k: getattr(st, k) for k, _ in _ScoreMultiStats._fields_ if k != "struct_size"}
+        return out
+
+    def score_choices(self, context, endings, chunk_tokens: int = 0, n_threads: int = 8) -> dict:
+        """llamahip_score_choices: one context, len(endings) endings on KV slots 0 .. len(endings) - 1 (overwritten) -- the context evaluated
+        once, its rows copied to the other slots, the endings scored in one weight pass.  Returns logprob_sum [n] (float64), n_greedy [n]
+        (rows whose target was the greedy pick) and rows, the per-ending arrays of log-probabilities."""
+        ctx = np.ascontiguousarray(context, np.int32).ravel()
+        ends = [np.ascontiguousarray(e, np.int32).ravel() for e in endings]
+        ne = np.array([e.size for e in ends], np.int32) if ends else np.zeros(1, np.int32)
+        E = int(ne.sum()) if ends else 0
+        flat = np.ascontiguousarray(np.concatenate(ends), np.int32) if E else np.zeros(1, np.int32)
+        sums, greedy = np.zeros(max(len(ends), 1), np.float64), np.zeros(max(len(ends), 1), np.int32)
+        rows = np.zeros(max(E, 1), np.float64)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_score_choices(self._h, n_threads, _ptr(ctx) if ctx.size else None, ctx.size, len(ends), _ptr(flat), _ptr(ne), int(chunk_tokens),
+                                          _ptr(sums), _ptr(greedy), _ptr(rows), err, len(err))
+        _check(rc, err)
+        at = np.cumsum(ne) - ne
+        return {"logprob_sum": sums[:len(ends)], "n_greedy": greedy[:len(ends)], "rows": [rows[int(a):int(a) + int(n)].copy() for a, n in zip(at, ne)]}
 
     def decode_greedy_multi(self, first_tokens, n_past, n_steps: int, n_threads: int = 8) -> np.ndarray:
         """llamahip_decode_greedy_multi: sequences in KV slots 0 .. len(first_tokens) - 1 decoded together; returns [n_seqs][n_steps]."""

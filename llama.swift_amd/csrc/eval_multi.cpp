@@ -1,8 +1,11 @@
 // eval_multi.cpp -- the host half of llamahip_eval_multi (include/llamahip.h): the row table of a pass over several KV slots
 // (llamahip_eval_multi_rows), what the entry point refuses of its arguments (eval_multi_check) and what llamahip_op_attention_rows refuses of a
-// caller's table (rows_table_check).  Pure host code, no device, no handle: tools/host_sanitize runs it under ASan + UBSan.
+// caller's table (rows_table_check); and of llamahip_eval_logprobs_multi / llamahip_score_choices: their argument checks (score_multi_check,
+// score_choices_check), the scored rows of a pass (score_multi_rows) and the way their results go back to row order (score_scatter).
+// Pure host code, no device, no handle: tools/host_sanitize runs it under ASan + UBSan.
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -18,9 +21,9 @@ static inline int32_t split_keys_host(int32_t n_past, int32_t N, int32_t j, int3
 }
 
 // what llamahip_eval_multi refuses of its ARGUMENTS (the handle is the caller's business): 0, or LLAMAHIP_ERR_PREDICT with the limit in err
-int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
-                     const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap) {
-    static const char *fn = "llamahip_eval_multi";
+// (fn: the entry point the messages name)
+static int segments_check(const char *fn, int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                          const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap) {
     if (!err) err_cap = 0;
     if (n_seqs < 1 || n_seqs > n_slots) { snprintf(err, err_cap, "%s: n_seqs (%d) outside 1 .. %d, the handle's KV slots (llamahip_opts.n_seq)", fn, n_seqs, n_slots); return LLAMAHIP_ERR_PREDICT; }
     if (!slots || !n_past || !tokens || !n_tokens) { snprintf(err, err_cap, "%s: null slots, n_past, tokens or n_tokens", fn); return LLAMAHIP_ERR_PREDICT; }
@@ -41,6 +44,82 @@ int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_
     for (int64_t r = 0; r < R; r++)
         if (tokens[r] < 0 || tokens[r] >= n_vocab) { snprintf(err, err_cap, "%s: token id %d at %lld out of range [0, %d)", fn, tokens[r], (long long) r, n_vocab); return LLAMAHIP_ERR_PREDICT; }
     if (R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: %lld rows in all, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                     const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap) {
+    return segments_check("llamahip_eval_multi", n_ctx, n_vocab, n_slots, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, err, err_cap);
+}
+
+// what llamahip_eval_logprobs_multi refuses of its arguments: eval_multi_check's rules, and a target (targets may be null) outside [-1, n_vocab)
+int score_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                      const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, const int32_t *targets, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_logprobs_multi";
+    const int rc = segments_check(fn, n_ctx, n_vocab, n_slots, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, err, err_cap);
+    if (rc || !targets) return rc;
+    if (!err) err_cap = 0;
+    int64_t r = 0;
+    for (int32_t i = 0; i < n_seqs; i++)
+        for (int32_t j = 0; j < n_tokens[i]; j++, r++)
+            if (targets[r] < -1 || targets[r] >= n_vocab) {
+                snprintf(err, err_cap, "%s: target %d of row %lld (row %d of segment %d) out of range [-1, %d)", fn, targets[r], (long long) r, j, i, n_vocab);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    return 0;
+}
+
+// the targets of the R rows of checked segments resolved (targets null: the next token inside the row's segment, the segment's last row -1)
+// into tgt [R], and the scored rows in ascending row order into scored (at most R entries): returns their count
+int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n_tokens, const int32_t *targets, int32_t *tgt, int32_t *scored) {
+    int32_t r = 0, nl = 0;
+    for (int32_t i = 0; i < n_seqs; i++)
+        for (int32_t j = 0; j < n_tokens[i]; j++, r++) {
+            tgt[r] = targets ? targets[r] : j + 1 < n_tokens[i] ? tokens[r + 1] : -1;
+            if (tgt[r] >= 0) scored[nl++] = r;
+        }
+    return nl;
+}
+
+// k_row_logprob's results of the nl scored rows -- packed: [nl] logprob (double) | [nl] argmax | [nl] rank, 16 nl bytes -- back to row order;
+// an unscored row reports 0.0 / -1 / -1.  Any output may be null.
+void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk) {
+    for (int32_t r = 0; r < R; r++) { if (lp) lp[r] = 0.0; if (am) am[r] = -1; if (rk) rk[r] = -1; }
+    const char *p = (const char *) packed;
+    for (int32_t k = 0; k < nl; k++) {
+        const int32_t r = scored[k];
+        if (lp) memcpy(&lp[r], p + (size_t) k * 8, 8);
+        if (am) memcpy(&am[r], p + (size_t) nl * 8 + (size_t) k * 4, 4);
+        if (rk) memcpy(&rk[r], p + (size_t) nl * 12 + (size_t) k * 4, 4);
+    }
+}
+
+// what llamahip_score_choices refuses of its arguments
+int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
+                        const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_score_choices";
+    if (!err) err_cap = 0;
+    const int32_t max_choices = std::min(LLAMAHIP_SCORE_CHOICES_MAX, n_slots);
+    if (n_context < 1) { snprintf(err, err_cap, "%s: n_context (%d) must be >= 1: the last context token predicts an ending's first", fn, n_context); return LLAMAHIP_ERR_PREDICT; }
+    if (n_choices < 1 || n_choices > max_choices) {
+        snprintf(err, err_cap, "%s: n_choices (%d) outside 1 .. %d (LLAMAHIP_SCORE_CHOICES_MAX %d, the handle's KV slots %d: llamahip_opts.n_seq)", fn, n_choices, max_choices, LLAMAHIP_SCORE_CHOICES_MAX, n_slots);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (!context || !endings || !n_ending) { snprintf(err, err_cap, "%s: null context, endings or n_ending", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (chunk_tokens < 0) { snprintf(err, err_cap, "%s: chunk_tokens (%d) must be >= 0 (0 = one eval of the context)", fn, chunk_tokens); return LLAMAHIP_ERR_PREDICT; }
+    int64_t E = 0;
+    for (int32_t i = 0; i < n_choices; i++) {
+        if (n_ending[i] < 1) { snprintf(err, err_cap, "%s: n_ending[%d] must be >= 1 (got %d)", fn, i, n_ending[i]); return LLAMAHIP_ERR_PREDICT; }
+        if ((int64_t) n_context - 1 + n_ending[i] > n_ctx) {
+            snprintf(err, err_cap, "%s: context overflow in choice %d: n_context - 1 (%d) + n_ending (%d) > n_ctx (%d)", fn, i, n_context - 1, n_ending[i], n_ctx);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        E += n_ending[i];
+    }
+    for (int32_t i = 0; i < n_context; i++)
+        if (context[i] < 0 || context[i] >= n_vocab) { snprintf(err, err_cap, "%s: context token id %d at %d out of range [0, %d)", fn, context[i], i, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    for (int64_t r = 0; r < E; r++)
+        if (endings[r] < 0 || endings[r] >= n_vocab) { snprintf(err, err_cap, "%s: ending token id %d at %lld out of range [0, %d)", fn, endings[r], (long long) r, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (E > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: %lld ending rows in all, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) E, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
     return 0;
 }
 

@@ -934,6 +934,13 @@ namespace lh {
 // eval_multi.cpp: what llamahip_eval_multi refuses of its arguments
 int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
                      const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap);
+// ... what llamahip_eval_logprobs_multi / llamahip_score_choices refuse of theirs, the scored rows of a pass and their results back in row order
+int score_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                      const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, const int32_t *targets, char *err, size_t err_cap);
+int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n_tokens, const int32_t *targets, int32_t *tgt, int32_t *scored);
+void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk);
+int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
+                        const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     if (!m->stages.empty()) return 0;
@@ -2288,10 +2295,15 @@ struct RowsPass {
     // lm head runs over, in logits-row order (empty: every segment's last row), at most ROWS_LOGITS_MAX
     std::vector<char> seg_single;
     std::vector<int32_t> logit_rows;
-    int n_logits() const { return logit_rows.empty() ? n_seqs : (int) logit_rows.size(); }
+    // scoring (llamahip_eval_logprobs_multi): logit_rows = the scored rows, up to logits_cap = R of them and possibly none (then no lm head at all);
+    // the lm head over them is a scoring eval's (Pass::score_rows), k_row_logprob follows it on the last stage
+    bool score = false;
+    int logits_cap = VERIFY_ROWS_MAX;             // (= ROWS_LOGITS_MAX: a scheduler's step)
+    int n_logits() const { return logit_rows.empty() && !score ? n_seqs : (int) logit_rows.size(); }
 };
 constexpr int ROWS_LOGITS_MAX = VERIFY_ROWS_MAX;
-static size_t rows_idx_entries(const llamahip_model *m) { return (size_t) std::max(m->n_seq, ROWS_LOGITS_MAX); }      // the lm head's row list
+// the lm head's row list: a row per KV slot or ROWS_LOGITS_MAX rows, and as many as the table has rows (a scoring pass may score every row)
+static size_t rows_idx_entries(const llamahip_model *m, int cap) { return (size_t) std::max(std::max(m->n_seq, ROWS_LOGITS_MAX), cap); }
 struct RowsDev { RowTab *tab; int32_t *short_idx, *last_idx; };
 static RowsDev rows_dev(llamahip_model *m) {
     char *b = m->d_rows;
@@ -2304,12 +2316,13 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
         HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
         m->own.release(&m->d_rows); m->rows_cap = 0;
         const int cap = std::max(rp.R, 64);
-        HIP_TRY(m->own.alloc(&m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + rows_idx_entries(m) * 4), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(m->own.alloc(&m->d_rows, (size_t) cap * (sizeof(RowTab) + 4) + rows_idx_entries(m, cap) * 4), LLAMAHIP_ERR_PREDICT);
         m->rows_cap = cap;
     }
-    const size_t cap = (size_t) m->rows_cap, bytes = cap * (sizeof(RowTab) + 4) + rows_idx_entries(m) * 4;
-    if (rp.logit_rows.size() > (size_t) ROWS_LOGITS_MAX || (rp.logit_rows.empty() && (size_t) rp.n_seqs > rows_idx_entries(m))) {
-        set_err(err, err_cap, "llamahip_eval_multi: %d logits rows in one pass (at most %d)", rp.n_logits(), (int) rows_idx_entries(m));
+    const size_t cap = (size_t) m->rows_cap, n_idx = rows_idx_entries(m, m->rows_cap), bytes = cap * (sizeof(RowTab) + 4) + n_idx * 4;
+    const int logits_max = std::max(m->n_seq, rp.logits_cap);
+    if (rp.logit_rows.size() > (size_t) rp.logits_cap || (size_t) rp.n_logits() > n_idx || (rp.logit_rows.empty() && !rp.score && rp.n_seqs > logits_max)) {
+        set_err(err, err_cap, "llamahip_eval_multi: %d logits rows in one pass (at most %d)", rp.n_logits(), logits_max);
         return LLAMAHIP_ERR_PREDICT;
     }
     m->h_rows.assign(bytes, 0);
@@ -2325,7 +2338,7 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
         }
         tab[r] = { rp.pos[r], rp.keys[r], (long) slot * slot_stride };
         if (rp.n_tokens[i] <= rp.short_max) short_idx[ns++] = r;
-        if (rp.logit_rows.empty() && (r + 1 == rp.R || rp.seg[r + 1] != i)) last_idx[i] = r;
+        if (rp.logit_rows.empty() && !rp.score && (r + 1 == rp.R || rp.seg[r + 1] != i)) last_idx[i] = r;
     }
     for (size_t k = 0; k < rp.logit_rows.size(); k++) {
         if (rp.logit_rows[k] < 0 || rp.logit_rows[k] >= rp.R) { set_err(err, err_cap, "llamahip_eval_multi: logits row %d names row %d of %d", (int) k, rp.logit_rows[k], rp.R); return LLAMAHIP_ERR_PREDICT; }
@@ -2374,12 +2387,16 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
     if (m->last_stage) {
         // the segments' last rows (a drafted scheduler step: its list of rows) side by side (x1 is free here), the final norm and the lm head over
         // those nl rows: logits rows 0 .. nl - 1
+        // (a scoring pass: the scored rows, none at all: no lm head; and the lm head a scoring eval of nl rows takes -- `output`'s prompt copies
+        //  and the operand workspace at row counts that use them, as forward_eval's under Pass::score_rows)
         const int nl = rp.n_logits();
-        HIP_TRY(launch_gather_rows(m->x, rd.last_idx, nl, d, m->x1, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, nl, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-        QMat out = m->output;
-        out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr;          // (the decode tiles, as llamahip_eval's lm head)
-        HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, nl, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
+        if (nl > 0) {
+            HIP_TRY(launch_gather_rows(m->x, rd.last_idx, nl, d, m->x1, st), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, nl, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
+            QMat out = m->output;
+            if (!rp.score) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }          // (the decode tiles, as llamahip_eval's lm head)
+            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, nl, m->logits, V, nullptr, 0, st, rp.score ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
+        }
     }
     m->last_rows.clear();          // (m->logits rewritten)
     return 0;
@@ -2392,6 +2409,7 @@ static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass 
     if ((rc = ensure_workspace(st, rp.R, err, err_cap)) != 0) return rc;
     if ((rc = ensure_attn_ws(st, 2, err, err_cap)) != 0) return rc;
     if ((rc = ensure_prompt_copies(st, rp.R, err, err_cap)) != 0) return rc;
+    if (rp.score && st->last_stage) ensure_output_copies(st, rp.n_logits());
     if (st->first_stage) HIP_TRY(hipMemcpyAsync(st->d_tokens, tokens, (size_t) rp.R * 4, hipMemcpyHostToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
     return forward_rows(st, n_threads, rp, hidden_in, err, err_cap);
 }
@@ -2482,6 +2500,131 @@ int llamahip_eval_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, co
     m->n_evals++;
     m->t_eval_ms += now_ms() - t0;
     report();
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Scoring over several KV slots: llamahip_eval_logprobs_multi / llamahip_score_choices (llamahip.h).  llamahip_eval_multi's
+// pass with RowsPass::logit_rows = the scored rows in ascending row order: the lm head runs over those nl rows alone, score_enqueue reduces
+// them behind it on the last stage's stream with the targets compacted in the same order, nl x 16 bytes come back and score_scatter
+// (eval_multi.cpp) puts them back into row order.
+// ------------------------------------------------------------------------------------------------
+static int logprobs_multi_impl(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                               const int32_t *n_tokens, int32_t chunk_tokens, const int32_t *targets, double *lp, int32_t *am, int32_t *rk,
+                               llamahip_score_multi_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_logprobs_multi";
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    llamahip_model *last = stages.back();
+    RowsPass rp;
+    rp.n_seqs = n_seqs; rp.chunk = chunk_tokens; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens;
+    for (int i = 0; i < n_seqs; i++) rp.R += n_tokens[i];
+    const int R = rp.R;
+    std::vector<int32_t> tgt((size_t) R), scored((size_t) R);
+    const int nl = score_multi_rows(n_seqs, tokens, n_tokens, targets, tgt.data(), scored.data());
+    llamahip_score_multi_stats out = {};
+    out.struct_size = (int32_t) sizeof(out);
+    out.n_rows = R; out.n_scored_rows = nl;
+    auto report = [&]() { if (stats) { const int32_t n = std::min((size_t) std::max(stats->struct_size, 0), sizeof(out)); if (n >= 4) { out.struct_size = n; memcpy(stats, &out, (size_t) n); } } };
+    // llamahip_eval_multi's rule for the per-slot loop of the contract itself (see there); the argmax of an unscored row is dropped, so that
+    // the outputs do not depend on the path
+    bool all_huge = R > EVAL_MULTI_LOOP_ROWS;
+    for (int i = 0; i < n_seqs; i++) all_huge = all_huge && n_tokens[i] >= EVAL_MULTI_LOOP_SEG_ROWS;
+    if (!rows_pass_applies(m) || n_seqs == 1 || all_huge) {
+        std::vector<size_t> at((size_t) n_seqs, 0);
+        for (int i = 1; i < n_seqs; i++) at[i] = at[i - 1] + (size_t) n_tokens[i - 1];
+        const int64_t evals0 = m->n_evals;
+        const int rc = each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
+            return logprobs_impl(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], chunk_tokens, tgt.data() + at[i], lp ? lp + at[i] : nullptr,
+                                 am ? am + at[i] : nullptr, rk ? rk + at[i] : nullptr, nullptr, err, err_cap); });
+        if (rc) return rc;
+        for (int r = 0; am && r < R; r++) if (tgt[r] < 0) am[r] = -1;
+        out.n_passes = (int32_t) (m->n_evals - evals0);
+        report();
+        return LLAMAHIP_OK;
+    }
+    const double t0 = now_ms();
+    rp.score = true; rp.logits_cap = R;
+    rp.logit_rows.assign(scored.begin(), scored.begin() + nl);
+    if (rows_pass_build(rp, m->hp.n_ctx) != 0) { set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT; }
+    out.n_passes = 1; out.n_short_segs = rp.n_short_segs; out.n_long_segs = rp.n_long_segs;
+    int rc = rows_pass_enqueue(stages, n_threads, rp, tokens, err, err_cap);
+    std::vector<int32_t> ctgt((size_t) nl);          // (alive until the stages have drained)
+    for (int k = 0; k < nl; k++) ctgt[k] = tgt[(size_t) scored[k]];
+    if (rc == 0 && nl > 0) rc = score_enqueue(last, nl, ctgt.data(), err, err_cap);
+    // (the bounded wait first, the copy of the results behind it: pipe_eval)
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    std::vector<char> packed((size_t) nl * 16);
+    if (nl > 0) {
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpy(packed.data(), last->d_score, packed.size(), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    }
+    score_scatter(R, nl, scored.data(), packed.data(), lp, am, rk);
+    m->last_rows.clear();
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    report();
+    return LLAMAHIP_OK;
+}
+
+int llamahip_eval_logprobs_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                                 const int32_t *n_tokens, int32_t chunk_tokens, const int32_t *targets, double *logprob_out, int32_t *argmax_out,
+                                 int32_t *rank_out, llamahip_score_multi_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_logprobs_multi";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = score_multi_check(m->hp.n_ctx, m->hp.n_vocab, m->n_seq, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, targets, err, err_cap);
+    if (rc) return rc;
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    return logprobs_multi_impl(m, n_threads, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, targets, logprob_out, argmax_out, rank_out, stats, err, err_cap);
+}
+
+int llamahip_score_choices(llamahip_model *m, int32_t n_threads, const int32_t *context, int32_t n_context, int32_t n_choices, const int32_t *endings,
+                           const int32_t *n_ending, int32_t chunk_tokens, double *logprob_sum, int32_t *n_greedy, double *logprob_rows,
+                           char *err, size_t err_cap) {
+    static const char *fn = "llamahip_score_choices";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = score_choices_check(m->hp.n_ctx, m->hp.n_vocab, m->n_seq, context, n_context, n_choices, endings, n_ending, chunk_tokens, err, err_cap);
+    if (rc) return rc;
+    if (!logprob_sum) { set_err(err, err_cap, "%s: null logprob_sum", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (m->sched) { set_err(err, err_cap, "%s: the handle has a live scheduler, which owns KV slots 0 .. %d: free it first", fn, sched_dev_max_active(m->sched) - 1); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    const int n = n_choices, P = n_context - 1;
+    // the segments: choice i = [the context's last token, ending_i without its last token] at P on slot i, every row scored against ending_i
+    std::vector<int32_t> slots((size_t) n), past((size_t) n, P), toks, tgt;
+    for (int i = 0, e = 0; i < n; e += n_ending[i], i++) {
+        slots[i] = i;
+        toks.push_back(context[P]);
+        toks.insert(toks.end(), endings + e, endings + e + n_ending[i] - 1);
+        tgt.insert(tgt.end(), endings + e, endings + e + n_ending[i]);
+    }
+    const int R = (int) toks.size();
+    if (P > 0) {
+        // the context once, on slot 0 (enqueued and waited for as the entry point it is), then its rows to the other slots: one launch per stage,
+        // stream-ordered ahead of the pass, no host wait
+        const int32_t zero = 0;
+        rc = each_slot(m, 1, &zero, err, err_cap, [&](int) {
+            return chunk_tokens > 0 ? eval_chunks_impl(m, n_threads, 0, context, P, chunk_tokens, nullptr, true, err, err_cap)
+                                    : llamahip_eval(m, n_threads, 0, context, P, nullptr, err, err_cap); });
+        if (rc) return rc;
+        if (n > 1) {
+            KvCopyTab tab = {};
+            tab.n = n - 1;
+            for (int i = 1; i < n; i++) { tab.src[i - 1] = 0; tab.dst[i - 1] = i; tab.row_begin[i - 1] = 0; tab.n_rows[i - 1] = P; }
+            const std::vector<llamahip_model *> stages = stages_of(m);
+            if ((rc = kv_copy_enqueue(stages, tab, fn, err, err_cap)) != 0) return drain_stages(stages, rc, err, err_cap);
+        }
+    }
+    std::vector<double> lp((size_t) R);
+    std::vector<int32_t> rk((size_t) R);
+    rc = logprobs_multi_impl(m, n_threads, n, slots.data(), past.data(), toks.data(), n_ending, 0, tgt.data(), lp.data(), nullptr, rk.data(), nullptr, err, err_cap);
+    if (rc) return rc;
+    for (int i = 0, r = 0; i < n; i++) {
+        double sum = 0.0;
+        int32_t greedy = 0;
+        for (int j = 0; j < n_ending[i]; j++, r++) { sum += lp[(size_t) r]; greedy += rk[(size_t) r] == 0; }
+        logprob_sum[i] = sum;
+        if (n_greedy) n_greedy[i] = greedy;
+    }
+    if (logprob_rows) std::copy(lp.begin(), lp.end(), logprob_rows);
     return LLAMAHIP_OK;
 }
 

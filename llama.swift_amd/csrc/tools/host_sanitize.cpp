@@ -90,6 +90,13 @@ namespace lh {
 int eval_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
                      const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, char *err, size_t err_cap);
 int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, char *err, size_t err_cap);
+// ... the host half of llamahip_eval_logprobs_multi / llamahip_score_choices: argument checks, the scored rows, the results back in row order
+int score_multi_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                      const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, const int32_t *targets, char *err, size_t err_cap);
+int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n_tokens, const int32_t *targets, int32_t *tgt, int32_t *scored);
+void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk);
+int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
+                        const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
@@ -189,6 +196,113 @@ static void own_stub_release(void *p, int kind) { g_own_releases[kind]++; free(p
 
 static int failures = 0;
 #define EXPECT(c) do { if (!(c)) { fprintf(stderr, "host_sanitize: FAILED %s (line %d)\n", #c, __LINE__); failures++; } } while (0)
+
+// scoring over several KV slots (llamahip_eval_logprobs_multi / llamahip_score_choices): the argument checks on exactly sized arrays and
+// exactly sized message buffers (every refusal, at buffers too short for its message and with none), the scored rows against the rule
+// restated, and the compacted results scattered back to row order from a buffer of exactly 16 bytes per scored row
+__attribute__((noinline)) static void scoring_host_half(int V) {          // (its own frame: main is as large as the compiler's variable tracking takes)
+    char err[512] = { 0 };
+    long n_checks = 0, n_scatter = 0;
+    auto refused = [&](auto call) {          // call(err, cap): refused with a message that fits a buffer of 1, 24 and 400 bytes, and with no buffer
+        for (size_t cap : { (size_t) 1, (size_t) 24, (size_t) 400 }) {
+            std::vector<char> e(cap, 'x');
+            EXPECT(call(e.data(), cap) == LLAMAHIP_ERR_PREDICT);
+            EXPECT(memchr(e.data(), 0, cap) != nullptr);
+            if (cap == 400) EXPECT(strstr(e.data(), "llamahip_eval_logprobs_multi") || strstr(e.data(), "llamahip_score_choices"));
+            n_checks++;
+        }
+        EXPECT(call(nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+    };
+    for (int C : { 64, 128 })
+        for (int n = 1; n <= 5; n++)
+            for (int mode = 0; mode < 5; mode++) {          // targets: null | every row | scattered -1 rows | one segment unscored | none at all
+                static const int lens[6] = { 1, 2, 9, 10, 18, 61 }, pasts[3] = { 0, 3, 37 };
+                std::vector<int32_t> np((size_t) n), nt((size_t) n), slots((size_t) n);
+                int R = 0;
+                bool fits = true;
+                for (int i = 0; i < n; i++) { np[i] = pasts[(mode + i) % 3]; nt[i] = lens[(mode * 5 + i) % 6]; slots[i] = n - 1 - i; R += nt[i]; fits = fits && np[i] + nt[i] <= C; }
+                std::vector<int32_t> toks((size_t) R), tg((size_t) R);
+                for (int r = 0; r < R; r++) toks[r] = (r * 7 + 3) % V;
+                for (int r = 0, i = 0, j = 0; r < R; r++) {
+                    tg[r] = mode == 1 ? (r * 5 + 1) % V : mode == 2 ? (r % 3 == 1 ? -1 : (r * 5 + 1) % V) : mode == 3 ? (i == n / 2 ? -1 : V - 1) : -1;
+                    if (++j == nt[i]) { j = 0; i++; }
+                }
+                const int32_t *targets = mode == 0 ? nullptr : tg.data();
+                EXPECT((lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), 0, targets, err, sizeof(err)) == 0) == fits);
+                if (!fits) { refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), 0, targets, e, cap); }); continue; }
+                std::vector<int32_t> tgt((size_t) R), scored((size_t) R);
+                const int32_t nl = lh::score_multi_rows(n, toks.data(), nt.data(), targets, tgt.data(), scored.data());
+                int want_nl = 0;
+                for (int r = 0, i = 0, j = 0; r < R; r++) {
+                    const int32_t want = targets ? targets[r] : (j + 1 < nt[i] ? toks[r + 1] : -1);
+                    EXPECT(tgt[r] == want);
+                    if (want >= 0) { EXPECT(want_nl < nl && scored[want_nl] == r); want_nl++; }
+                    if (++j == nt[i]) { j = 0; i++; }
+                }
+                EXPECT(nl == want_nl && (mode != 4 || nl == 0) && (mode != 1 || nl == R));
+                // made-up results of the nl scored rows, exactly 16 nl bytes, back to row order
+                std::vector<char> packed((size_t) nl * 16);
+                for (int k = 0; k < nl; k++) {
+                    const double l = -0.5 * (k + 1); const int32_t a = 1000 + k, q = k % 4;
+                    memcpy(packed.data() + (size_t) k * 8, &l, 8);
+                    memcpy(packed.data() + (size_t) nl * 8 + (size_t) k * 4, &a, 4);
+                    memcpy(packed.data() + (size_t) nl * 12 + (size_t) k * 4, &q, 4);
+                }
+                std::vector<double> lp((size_t) R, 7.0);
+                std::vector<int32_t> am((size_t) R, 7), rk((size_t) R, 7);
+                lh::score_scatter(R, nl, scored.data(), packed.data(), lp.data(), am.data(), rk.data());
+                for (int r = 0, k = 0; r < R; r++) {
+                    if (tgt[r] >= 0) { EXPECT(lp[r] == -0.5 * (k + 1) && am[r] == 1000 + k && rk[r] == k % 4); k++; }
+                    else EXPECT(lp[r] == 0.0 && am[r] == -1 && rk[r] == -1);
+                }
+                lh::score_scatter(R, nl, scored.data(), packed.data(), nullptr, nullptr, nullptr);
+                lh::score_scatter(R, nl, scored.data(), packed.data(), lp.data(), nullptr, rk.data());
+                n_scatter++;
+                // the refusals: a target of n_vocab and of -2, then eval_multi_check's rules under this function's name
+                if (mode == 0) continue;
+                const int32_t keep = tg[R - 1];
+                for (int32_t bad : { V, -2 }) {
+                    tg[R - 1] = bad;
+                    refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), 0, tg.data(), e, cap); });
+                }
+                tg[R - 1] = keep;
+                refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), -1, tg.data(), e, cap); });
+                refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n - 1, n, slots.data(), np.data(), toks.data(), nt.data(), 0, tg.data(), e, cap); });
+                refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, 0, slots.data(), np.data(), toks.data(), nt.data(), 0, tg.data(), e, cap); });
+                if (n > 1) { slots[n - 1] = slots[0]; refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), 0, tg.data(), e, cap); }); slots[n - 1] = 0; }
+                nt[0] = 0;
+                refused([&](char *e, size_t cap) { return lh::score_multi_check(C, V, n, n, slots.data(), np.data(), toks.data(), nt.data(), 0, tg.data(), e, cap); });
+            }
+    {   // one row more than a pass takes
+        const int32_t slot0[1] = { 0 }, np0[1] = { 0 }, big[1] = { LLAMAHIP_EVAL_MULTI_MAX_ROWS + 1 };
+        std::vector<int32_t> toks((size_t) big[0], 1);
+        refused([&](char *e, size_t cap) { return lh::score_multi_check(4096, V, 1, 1, slot0, np0, toks.data(), big, 0, nullptr, e, cap); });
+    }
+    // llamahip_score_choices: contexts of 1, 10 and 40 tokens, 1 .. 16 endings, accepted; then every refusal
+    for (int nc : { 1, 10, 40 })
+        for (int n : { 1, 4, 16 }) {
+            std::vector<int32_t> ctx((size_t) nc, 2), ne((size_t) n);
+            int E = 0;
+            for (int i = 0; i < n; i++) { ne[i] = 1 + (i * 3) % 7; E += ne[i]; }
+            std::vector<int32_t> ends((size_t) E, 3);
+            EXPECT(lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 9, err, sizeof(err)) == 0);
+            EXPECT(lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, nullptr, 0) == 0);
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), 0, n, ends.data(), ne.data(), 0, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, 0, ends.data(), ne.data(), 0, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 32, ctx.data(), nc, 17, ends.data(), ne.data(), 0, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, n - 1, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), -1, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(nc - 1 + ne[n - 1] - 1, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, nullptr, nc, n, ends.data(), ne.data(), 0, e, cap); });
+            ctx[(size_t) nc - 1] = V;
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
+            ctx[(size_t) nc - 1] = 2; ends[(size_t) E - 1] = -1;
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
+            ends[(size_t) E - 1] = 3; ne[n - 1] = 0;          // an empty ending (the last one: no array is read past its end)
+            refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
+        }
+    printf("host_sanitize: scoring over KV slots: %ld refusals at short and missing message buffers, %ld scatters of compacted results against the rule restated\n", n_checks, n_scatter);
+}
 
 int main(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "usage: host_sanitize <model file> [n_parts]\n"); return 2; }
@@ -462,6 +576,7 @@ int main(int argc, char **argv) {
         EXPECT(llamahip_eval_multi_rows(64, 1, neg, np1, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 0, np1, np1, 0, nullptr, nullptr, nullptr) == -1);
         EXPECT(llamahip_eval_multi_rows(64, 1, nullptr, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, big, -1, nullptr, nullptr, nullptr) == -1);
     }
+    scoring_host_half(V);
     // the request scheduler's host half against the stubbed device half: the step rule over a grid on exactly sized arrays against its
     // restatement; then whole runs -- every step's segments replayed against the rule and the requests' own state (positions, offsets, tokens,
     // emit flags), the events against the made-up tokens; the refusals of new / submit / step; cancelling queued and active requests
