@@ -1059,6 +1059,35 @@ int llamahip_op_prep(int32_t mode, int32_t kernel, const float *buf, int64_t buf
 int llamahip_op_gemv_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t interleaved, int32_t pre, int32_t epi, const float *in0, const float *in1,
                           const double *part_in, int32_t n_part_in, const float *resid, float *y, int64_t y_floats, uint32_t *out_A, float *out_d,
                           int32_t out_rows, double *part_out, int32_t n_part_out, int32_t part_out_cap, int64_t *plan, char *err, size_t err_cap);
+/* ONE launch of the few-row mat-mul (k_gemv_set, 2 .. 60 rows) on caller-supplied operands: the kernel behind every batched decode step,
+ * drafted / verify step, scheduler step and short eval.  w_q4_0 and interleaved as llamahip_op_gemv_q4_0; x [N][K] fp32, K a positive
+ * multiple of 64, quantized by the plain activation launch as a model does it.  epi:
+ *   _STORE / _RESID   y [N][y_stride] (y_stride >= M) = acc (+ resid [N][M]); copied to the device and back whole: the floats outside the
+ *                     N x M block keep the caller's bits.
+ *   _ROPE_KV          M == 3 d, d a multiple of 8 and of the head size dh (K need not be d): q rotated into qr [N][d], k rotated and v
+ *                     copied into Kc / Vc [n_slots][n_ctx][d], modified in place.  Row r sits at position n_past + r of slot 0, or -- with
+ *                     row_pos [N] / row_slot [N] (both or neither; N <= 16) -- at row_pos[r] of slot row_slot[r]: the op builds the SeqSet
+ *                     of a batched decode step with pos[] and kv_off[] filled and every other member null.  Positions inside n_ctx and no
+ *                     two rows on one (slot, position) are checked on the host.
+ *   _SILU_QA / _SILU_QAH (interleaved only)  the Q4_0 operand of silu_table(gate) * up in rows 0 .. N-1 of out_A [out_rows][Fp / 4] /
+ *                     out_d [out_rows][Fp / 32] (out_rows >= N, Fp = F rounded up to 256), uploaded and downloaded whole: the launch never
+ *                     writes the blocks that pad F.  _SILU_QAH (half-block workgroups, N <= 16): the op owns a zeroed exchange buffer,
+ *                     epoch word and fault word; layer in 0 .. 249 enters the tags; the epoch is bumped before each launch; *fault
+ *                     receives the fault word.  x_prev [N][K] (may be NULL): the same launch runs first on x_prev into scratch operand
+ *                     rows under its own epoch, then the epoch is bumped again and the launch on x runs on the SAME, uncleared exchange
+ *                     buffer -- what a model's second step sees.  The fault-injection path is never taken.
+ * force: NULL launches what the library's rule picks; else {nc, cw, rgw} (rgw 0: derived) is launched exactly or refused with the reason:
+ * the pair must be instantiated, rgw x cw <= 8, the SiLU epilogues take cw == 1 and their own rgw, and the LDS must fit.  plan[7] (may be
+ * NULL): the launch {nc, cw, ncg, rgw, LDS bytes, grid, threads}, set before the device is looked for.  Everything is refused before any
+ * device is touched: N outside 2 .. 60, shapes the kernel does not take, SILU_QAH with N > 16, null operands, y_stride < M. */
+#define LLAMAHIP_GEMV_EPI_ROPE_KV  3
+#define LLAMAHIP_GEMV_EPI_SILU_QAH 7
+int llamahip_op_gemv_set_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t interleaved, int32_t epi, const float *x, int32_t N, const int32_t *force,
+                              const float *resid, float *y, int32_t y_stride,
+                              int32_t d, int32_t dh, int32_t n_ctx, int32_t n_slots, int32_t n_past, const int32_t *row_pos, const int32_t *row_slot,
+                              float *qr, float *Kc, float *Vc,
+                              uint32_t *out_A, float *out_d, int32_t out_rows, int32_t layer, const float *x_prev, uint32_t *fault,
+                              int64_t *plan, char *err, size_t err_cap);
 /* Host-only: N rows of the raw operand above -> [N][K / 32] Q4_0 blocks in file layout (what llamahip_op_attention's wo_operand holds). */
 int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t N, int32_t K, void *blocks);
 /* The embedding gather (ggml_get_rows on a Q4_0 matrix): tokens [N] in [0, V) (checked on the host), emb [V][d / 32] blocks in file layout,

@@ -41,6 +41,7 @@ from .binding import (  # noqa: F401
     op_attention_rows,
     op_embed,
     op_gemv_q4_0,
+    op_gemv_set_q4_0,
     op_logprob,
     op_mul_mat_dense,
     op_mul_mat_q4_1,

@@ -231,6 +231,7 @@ def lib() -> C.CDLL:
     L.llamahip_debug_qa_to_blocks.argtypes = [vp, vp, i32, i32, vp]
     L.llamahip_op_embed.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, cp, sz]
     L.llamahip_op_gemv_q4_0.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_int64, vp, vp, i32, vp, i32, i32, vp, cp, sz]
+    L.llamahip_op_gemv_set_q4_0.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
     L.llamahip_get_stats.argtypes = [vp, C.POINTER(_Stats)]
     L.llamahip_debug_lut_math.restype = i32
@@ -1549,6 +1550,59 @@ def op_gemv_q4_0(wq: np.ndarray, pre, epi, in0, in1=None, resid=None, interleave
                                      _ptr(plan), err, len(err))
     _check(rc, err)
     return dict(y=y, out_A=out_A, out_d=out_d, part_out=pout, plan=tuple(int(v) for v in plan))
+
+
+GEMV_SET_EPI = {"store": 0, "resid": 1, "silu_qa": 2, "rope_kv": 3, "silu_qah": 7}      # LLAMAHIP_GEMV_EPI_*
+
+
+def op_gemv_set_q4_0(wq: np.ndarray, epi, x, force=None, interleaved: bool = False, resid=None, y_init=None, y_stride: int | None = None,
+                     d: int = 0, dh: int = 0, n_ctx: int = 0, n_slots: int = 1, n_past: int = 0, row_pos=None, row_slot=None,
+                     qr_init=None, Kc=None, Vc=None, out_A=None, out_d=None, layer: int = 0, x_prev=None):
+    """One launch of the few-row mat-mul k_gemv_set (llamahip_op_gemv_set_q4_0).  wq uint8 [M, K/32, 20] in file layout (interleaved: w1's F
+    rows then w3's); epi: a name of GEMV_SET_EPI or the library's own code; x float32 [N, K]; force None (the library's rule) or
+    (nc, cw[, rgw]).  store / resid: resid [N, M], y_init [N, y_stride] (default NaN).  rope_kv: d, dh, n_ctx, n_slots, n_past or
+    row_pos / row_slot [N], qr_init [N, d] (default NaN), Kc / Vc [n_slots, n_ctx, d] (copied, not modified).  silu_qa / silu_qah: out_A
+    uint32 [rows, Fp/4] / out_d float32 or uint32 [rows, Fp/32] as the buffers are before the launch (copied); layer; x_prev [N, K].
+    Returns dict(y, qr, Kc, Vc, out_A, out_d (uint32 view kept as float32), fault, plan): the buffers as the device left them,
+    plan = (nc, cw, ncg, rgw, lds, grid, threads)."""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    M, nb, _ = wq.shape
+    K = nb * 32
+    ecode = GEMV_SET_EPI[epi] if epi in GEMV_SET_EPI else int(epi)
+    x = None if x is None else np.ascontiguousarray(x, np.float32)
+    N = 0 if x is None else (x.shape[0] if x.ndim == 2 else 1)
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, np.float32)
+    i32a = lambda a: None if a is None else np.ascontiguousarray(a, np.int32).ravel()
+    resid, x_prev, row_pos, row_slot = f32(resid), f32(x_prev), i32a(row_pos), i32a(row_slot)
+    fc = None
+    if force is not None:
+        fc = np.zeros(3, np.int32)
+        fc[:len(force)] = force
+    y = qr = None
+    ys = M if y_stride is None else int(y_stride)
+    if ecode in (0, 1):
+        y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C")
+    if ecode == 3:
+        qr = np.full((N, max(d, 0)), np.nan, np.float32) if qr_init is None else np.array(qr_init, np.float32, order="C")
+        Kc = None if Kc is None else np.array(Kc, np.float32, order="C")
+        Vc = None if Vc is None else np.array(Vc, np.float32, order="C")
+    else:
+        Kc = Vc = None
+    out_rows = 0
+    if ecode in (2, 7):
+        out_A = None if out_A is None else np.array(out_A, np.uint32, order="C")
+        out_d = None if out_d is None else np.array(np.asarray(out_d).view(np.float32), np.float32, order="C")
+        out_rows = 0 if out_A is None else out_A.shape[0]
+    else:
+        out_A = out_d = None
+    fault = np.full(1, 0xFFFFFFFF, np.uint32)
+    plan = np.zeros(7, np.int64)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_gemv_set_q4_0(_ptr(wq), M, K, int(interleaved), ecode, _ptr(x), N, _ptr(fc), _ptr(resid), _ptr(y), ys,
+                                         int(d), int(dh), int(n_ctx), int(n_slots), int(n_past), _ptr(row_pos), _ptr(row_slot), _ptr(qr), _ptr(Kc), _ptr(Vc),
+                                         _ptr(out_A), _ptr(out_d), out_rows, int(layer), _ptr(x_prev), _ptr(fault), _ptr(plan), err, len(err))
+    _check(rc, err)
+    return dict(y=y, qr=qr, Kc=Kc, Vc=Vc, out_A=out_A, out_d=out_d, fault=int(fault[0]) if ecode == 7 else None, plan=tuple(int(v) for v in plan))
 
 
 def qa_to_blocks(qa_A: np.ndarray, qa_d: np.ndarray, N: int, K: int) -> np.ndarray:

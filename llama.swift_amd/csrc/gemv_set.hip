@@ -83,9 +83,7 @@ struct GemvSetArgs {
 // LH_SET_PROBE (measurement build, tools/set_timeline.py): wave 0 of every workgroup stamps s_memtime at the phase boundaries and inside its
 // first steps into a record of 32 words: [0] wall clock at entry | [1] entry | [2] loads issued | [3] operands staged | [4 + 3 s + {0, 1, 2}] step s
 // (s < 4): start, its chunk has landed, behind the barrier (the items end where the next step starts) | [24] loop done | [25] exit | [26] wall clock at exit | [27] id
-#ifndef LH_SET_PROBE
-#define LH_SET_PROBE 0
-#endif
+// (default 0: set_plan.h)
 #if LH_SET_PROBE
 #define LH_PSTAMP(IDX) do { if (probe_on) probe_t[IDX] = __builtin_readcyclecounter(); } while (0)      /* probe_t: LDS, behind the ring */
 #else
@@ -96,16 +94,10 @@ struct GemvSetArgs {
 // every chunk with a ds_write.  Its in-kernel timeline, profiles/r05_t_timeline_register_ring.txt: 3.0 - 6.5 us between "ring issued" and the first
 // step -- the operand rows were requested BEHIND the ring and vmcnt retires in order, and the register copies the compiler places in
 // front of a loop that carries a ring made every wave wait for ALL of its prefill, i.e. for the far end of its rows, before step 0.)
-#ifndef LH_SET_DR
-#define LH_SET_DR 4
-#endif
-constexpr int SET_DR = LH_SET_DR;
+// (LH_SET_DR, default 4, and SET_DR: set_plan.h -- the plan's LDS arithmetic needs them too)
 // LDS operands of an item (chunk, column) are requested SET_PF items ahead into a ring of SET_PF + 1 register buffers.  Three items ahead
 // measured the same as one (profiles/r05_c_pf.txt: the loop is not LDS-latency bound) and costs 20 VGPRs: one.
-#ifndef LH_SET_PF
-#define LH_SET_PF 1
-#endif
-constexpr int SET_PF = LH_SET_PF, SET_NB = SET_PF + 1;
+// (LH_SET_PF, default 1, SET_PF and SET_NB: set_plan.h)
 static_assert((SET_DR % SET_NB) == 0 || SET_NB == 2, "the operand-buffer index is the item's position in the unrolled block of SET_DR steps");
 
 // one wave instruction of LDS-DMA: lane l's 16 (4) bytes at `base + voff` land in LDS at `lds_dst + 16 l` (`+ 4 l`); lds_dst, base wave-uniform
@@ -498,125 +490,18 @@ k_gemv_set(const GemvSetArgs a) {
 // ------------------------------------------------------------------------------------------------
 // host side: the (NC, CW) plan per row count, launchers
 // ------------------------------------------------------------------------------------------------
-struct SetPlan { int nc = 0, cw = 0, rgw = 0, ncg = 1; size_t lds = 0; };
-
-static size_t set_lds_bytes(const QMat &w, int ncols_group, int nc, int cw, int rgw) {
-    const int steps = (w.nchunks + cw - 1) / cw, npad = steps * cw + SET_PF;
-    size_t lds = (size_t) ncols_group * npad * 288 + (cw > 1 ? (size_t) rgw * SET_DR * cw * TILE_BYTES : 0) + (LH_SET_PROBE ? 256 : 0);
-    return std::max(lds, (size_t) nc * cw * 64 * 4);
+// (the plan itself, its overrides and a launch's grid / threads: set_plan.cpp, host-only)
+static_assert(SET_TILE_BYTES == TILE_BYTES && SET_EPI_STORE == EPI_STORE && SET_EPI_RESID == EPI_RESID && SET_EPI_SILU_QA == EPI_SILU_QA &&
+              SET_EPI_ROPE_KV == EPI_ROPE_KV && SET_EPI_SILU_QAH == EPI_SILU_QAH, "set_plan.h mirrors llamahip_internal.h");
+static SetShape set_shape_of(const QMat &w) {
+    SetShape s;
+    s.M = w.M; s.K = w.K; s.ngroups = w.ngroups; s.nchunks = w.nchunks; s.gmapF8 = w.gmapF8; s.tiles = w.tiles != nullptr;
+    return s;
 }
-
-// Columns per wave (nc), waves per row-group (cw) and column groups (ncg) for N rows.  What the in-kernel timelines say (profiles/r05_*):
-// a wave spends ~0.07 - 0.09 us per (chunk, column) item whatever shares its SIMD, a step of a shared ring costs a barrier (~0.3 us in a
-// 16-wave workgroup), and a launch ends when its longest wave does.  So: matrices with few row-groups (wo, w2: 512 at 7B) take cw waves per
-// row-group with one or two columns each (items per wave = chunks x nc); matrices with >= 1 024 row-groups (wq|wk|wv, w1|w3, the lm head)
-// have waves enough: up to four columns per wave, no sharing, and for more than four rows column GROUPS at grid level (the groups of a
-// row block run side by side on one XCD; the second read of a tile is an L2 hit hidden behind arithmetic -- at 8 rows these launches
-// are VALU bound: sharing the ring there AND streaming the operand rows through a second ring, k_gemv_set_ar of round 5, read the weights once
-// and measured the same -- profiles/r05_o_operand_ring_ab.txt; removed).  LLAMAHIP_SET_PLAN[_BIG|_SMALL]="nc,cw[,ncg[,rgw]]" overrides (measurement; _BIG: the unshared class).
-// the short evals: up to 60 rows (measured crossover against the row-per-lane kernel at 7B shapes, round 1: +25 % at 33 rows, +7 % at 56, -1 % at
-// 63; k_gemv_set against k_gemm_skinny at 20 / 24 / 32 / 48 / 60 rows: -5.5 / -5.5 / -0.7 / -5.2 / -6.3 % per eval, profiles/r05_y_rows_max.txt)
-constexpr int SET_ROWS_MAX = 60;
-constexpr size_t SET_LDS_CAP = 160 * 1024;
-// the (NC, CW) pairs k_gemv_set is instantiated for (launch_set_any's dispatch list)
-static bool set_plan_instantiated(int nc, int cw) {
-    static const int pairs[][2] = { {1, 2}, {1, 3}, {1, 4}, {2, 1}, {2, 2}, {2, 3}, {2, 4}, {3, 1}, {3, 3}, {3, 4}, {4, 1}, {4, 2}, {4, 4}, {5, 1} };
-    for (const auto &pr : pairs) if (pr[0] == nc && pr[1] == cw) return true;
-    return false;
-}
-
-// LLAMAHIP_SET_PLAN[_BIG|_SMALL] are parsed once per process (the switches of this library are read once; set_plan runs several times per launch)
-struct SetPlanEnv { int got = 0, nc = 0, cw = 0, ncg = 0, rgw = 0; };
-static SetPlanEnv set_plan_env_parse(const char *name) {
-    SetPlanEnv e;
-    const char *env = getenv(name);
-    if (!env) return e;
-    e.got = sscanf(env, "%d,%d,%d,%d", &e.nc, &e.cw, &e.ncg, &e.rgw);
-    if (e.got < 2 || e.nc < 1 || e.nc > 5 || e.cw < 1 || e.cw > 4 || (e.nc == 5 && e.cw != 1)) e.got = 0;
-    return e;
-}
-static bool set_plan_env(int which, int N, int epi, int &nc, int &cw, int &ncg, int &rgw) {
-    static const SetPlanEnv envs[3] = { set_plan_env_parse("LLAMAHIP_SET_PLAN_BIG"), set_plan_env_parse("LLAMAHIP_SET_PLAN_SMALL"), set_plan_env_parse("LLAMAHIP_SET_PLAN") };
-    const SetPlanEnv &e = envs[which];
-    if (e.got < 2) return false;
-    int e_ncg = e.ncg;
-    if (e.got < 3 || e_ncg < 1) e_ncg = (N + e.nc * e.cw - 1) / (e.nc * e.cw);
-    if (e.nc * e.cw * e_ncg < N || (e_ncg - 1) * e.nc * e.cw >= N) return false;
-    nc = e.nc; cw = e.cw; ncg = e_ncg;
-    if (e.got >= 4 && e.rgw >= 1 && e.rgw <= 8 && epi != EPI_SILU_QAH && epi != EPI_SILU_QA) rgw = e.rgw;
-    return true;
-}
-static SetPlan set_plan(const QMat &w, int N, int epi) {
-    SetPlan p;
-    // waves per row-group: enough to put about two waves on every SIMD of the chip (ngroups x cw >= ~2 000), w1|w3 always unshared (its
-    // half-block workgroups are many); then <= 4 columns per wave, column groups at grid level beyond 4 cw columns
-    const bool big = w.ngroups >= 1536 || epi == EPI_SILU_QAH || epi == EPI_SILU_QA;
-    int cw = big ? 1 : w.ngroups >= 768 ? 2 : 4;
-    if (cw > N) cw = N;
-    const int ncmax = cw == 1 ? 5 : 4;                                // (five columns per wave are instantiated for unshared rings only: 9 rows = 5 + 4)
-    int ncg = (N + ncmax * cw - 1) / (ncmax * cw);
-    const int ng = (N + ncg - 1) / ncg;                               // columns per group, balanced (9 rows, unshared: 3 + 3 + 3)
-    int nc = (ng + cw - 1) / cw, rgw = 0;
-    cw = (ng + nc - 1) / nc;
-    // the small class by row count, measured (7B wo / w2, fresh processes, profiles/r05_u_fresh_ab.txt, r05_v_small_plans.txt): three
-    // column-waves leave 16 chunks a ragged last step (5 - 6 rows: <2,4> -1.5 %); from 9 rows on the launches are VALU bound and a step's
-    // barrier is pure loss: unshared rings in column groups of 3 (9 - 12 rows: -4 ... -6 % per eval) or 4 (13 - 16: -2 %)
-    // (the 768 .. 1 535 row-group class -- wo of the 30B / 65B -- takes the same rule from 9 rows on: the argument does not depend on the size)
-    if (!big && N >= 5) {
-        if (N <= 8) { if (w.ngroups < 768) { nc = 2; cw = 4; ncg = 1; } }
-        else if (N <= 12) { nc = 3; cw = 1; ncg = (N + 2) / 3; }
-        else { nc = 4; cw = 1; ncg = (N + 3) / 4; }
-    }
-    (void) (set_plan_env(big ? 0 : 1, N, epi, nc, cw, ncg, rgw) || set_plan_env(2, N, epi, nc, cw, ncg, rgw));
-    auto finish = [&]() {
-        // (instantiated: <1,2> <1,3> <1,4> <2,1> <2,2> <2,3> <2,4> <3,1> <3,3> <3,4> <4,1> <4,2> <4,4> <5,1>)
-        if (nc == 1 && cw == 1) nc = 2;
-        if (nc == 3 && cw == 2) nc = 4;
-        if (nc == 4 && cw == 3) cw = 4;
-        ncg = (N + nc * cw - 1) / (nc * cw);                          // (the promotions above widen a group: no column group may start past row N)
-        if (!rgw) rgw = epi == EPI_SILU_QAH ? 4 : (cw >= 3 ? 2 : 4);
-        if (epi == EPI_SILU_QAH) rgw = 4;
-        else if (epi == EPI_SILU_QA) rgw = 8;
-        else if (rgw * cw > 8) rgw = 8 / cw;                          // (set_max_threads)
-        p.nc = nc; p.cw = cw; p.rgw = rgw; p.ncg = ncg;
-        p.lds = set_lds_bytes(w, std::min(N, nc * cw), nc, cw, rgw);
-    };
-    finish();
-    if (p.lds > SET_LDS_CAP) {
-        // (a forced plan that cannot fit degrades to this rule for that shape too: a measurement variant never sends a shape to the generic kernel)
-        // wide rows (w2 of the 13B / 65B: 54 / 86 chunks): the operand rows of a whole group do not fit next to a shared ring.  Unshared
-        // column groups of as many columns (<= 4) as leave two workgroups' worth of LDS per CU where possible
-        const size_t per_col = set_lds_bytes(w, 1, 1, 1, 4);
-        int fit = (int) std::min<size_t>(4, (SET_LDS_CAP / 2) / per_col);
-        if (fit < 2) fit = (int) std::min<size_t>(4, SET_LDS_CAP / per_col);
-        if (fit >= 1) {
-            cw = 1; rgw = 0;
-            ncg = (N + fit - 1) / fit;
-            nc = (N + ncg - 1) / ncg;
-            finish();
-        }
-    }
-    return p;
-}
-
-bool gemv_set_applies(const QMat &w, int N, int epi) {
-    if (N < 2 || N > SET_ROWS_MAX || !w.tiles) return false;
-    if (epi == EPI_ROPE_KV && w.gmapF8 != 0) return false;
-    if ((epi == EPI_SILU_QAH || epi == EPI_SILU_QA) && (w.gmapF8 == 0 || w.ngroups % 8 != 0)) return false;
-    if (epi != EPI_STORE && epi != EPI_RESID && epi != EPI_ROPE_KV && epi != EPI_SILU_QAH && epi != EPI_SILU_QA) return false;
-    const SetPlan p = set_plan(w, N, epi);
-    if (epi == EPI_SILU_QA && p.cw != 1) return false;                // (whole-block workgroups are instantiated for unshared rings)
-    return p.lds <= SET_LDS_CAP && set_plan_instantiated(p.nc, p.cw);
-}
-// host-only query (tests, no device needed): the plan for N rows against an M x K matrix -- out = { nc, cw, ncg, rgw, LDS bytes }
-bool gemv_set_plan_query(int M, int K, bool interleaved, int N, int epi, long out[5]) {
-    QMat w;
-    w.tiles = (uint8_t *) (uintptr_t) 16; w.M = M; w.K = K; w.ngroups = (M + 7) / 8; w.nchunks = (K + 255) / 256; w.gmapF8 = interleaved ? w.ngroups / 2 : 0;
-    if (!gemv_set_applies(w, N, epi)) return false;
-    const SetPlan p = set_plan(w, N, epi);
-    out[0] = p.nc; out[1] = p.cw; out[2] = p.ncg; out[3] = p.rgw; out[4] = (long) p.lds;
-    return true;
-}
+static SetPlan set_plan(const QMat &w, int N, int epi, const SetForce *force = nullptr) { return set_plan(set_shape_of(w), N, epi, force); }
+bool gemv_set_applies(const QMat &w, int N, int epi) { return set_applies(set_shape_of(w), N, epi); }
+bool gemv_set_force_check(const QMat &w, int N, int epi, const SetForce &f, char *why, size_t why_cap) { return set_force_check(set_shape_of(w), N, epi, f, why, why_cap); }
+bool gemv_set_launch_query(const QMat &w, int N, int epi, const SetForce *force, long out[7]) { return set_launch_query(set_shape_of(w), N, epi, force, out); }
 
 template <int NC, int CW>
 static hipError_t launch_set_t(const GemvSetArgs &a, int epi, int grid, int nthreads, size_t lds, hipStream_t st) {
@@ -646,7 +531,7 @@ long set_probe_dump(unsigned long long *out, long cap_records, bool reset) {
     if (reset) { hdr[0] = 0; hdr[1] = (unsigned long long) g_set_probe_cap; (void) hipMemcpy(g_set_probe, hdr, sizeof(hdr), hipMemcpyHostToDevice); }
     return n;
 }
-static hipError_t launch_set_any(const QMat &w, GemvSetArgs a, int epi, hipStream_t st) {
+static hipError_t launch_set_any(const QMat &w, GemvSetArgs a, int epi, hipStream_t st, const SetForce *force = nullptr) {
 #if LH_SET_PROBE
     if (!g_set_probe && getenv("LLAMAHIP_SET_PROBE")) {
         g_set_probe_cap = std::max(1L, atol(getenv("LLAMAHIP_SET_PROBE")));
@@ -655,12 +540,11 @@ static hipError_t launch_set_any(const QMat &w, GemvSetArgs a, int epi, hipStrea
     }
     a.probe = g_set_probe;
 #endif
-    const SetPlan p = set_plan(w, a.ncols, epi);
+    const SetPlan p = set_plan(w, a.ncols, epi, force);
     if (p.lds > SET_LDS_CAP || !set_plan_instantiated(p.nc, p.cw)) return hipErrorInvalidValue;
     a.rgw = p.rgw; a.ncg = p.ncg;
-    const int nwg = epi == EPI_SILU_QAH ? (w.ngroups / 8 + 7) / 8 * 16 : (w.ngroups + p.rgw - 1) / p.rgw;      // (EPI_SILU_QA: rgw = 8, a workgroup per block)
-    const int grid = p.ncg == 1 ? nwg : (nwg + 7) / 8 * 8 * p.ncg;
-    const int nthreads = p.rgw * p.cw * 64;
+    int grid = 0, nthreads = 0;
+    set_launch_shape(set_shape_of(w), p, epi, grid, nthreads);
 #define LH_SP(NCV, CWV) if (p.nc == NCV && p.cw == CWV) return launch_set_t<NCV, CWV>(a, epi, grid, nthreads, p.lds, st)
     LH_SP(1, 2); LH_SP(1, 3); LH_SP(1, 4);
     LH_SP(2, 1); LH_SP(2, 2); LH_SP(2, 3); LH_SP(2, 4);
@@ -688,15 +572,15 @@ bool gemv_set_silu_whole_blocks(const QMat &w13, int N, bool have_exchange) {
     return set_plan(w13, N, EPI_SILU_QA).ncg >= 2;
 }
 hipError_t launch_gemv_set(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
-                           float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st) {
+                           float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, const SetForce *force) {
     GemvSetArgs a = set_args(w, qa_A, qa_d, N);
     a.y = y; a.y_stride = y_stride; a.resid = resid; a.resid_stride = resid_stride;
-    return launch_set_any(w, a, epi, st);
+    return launch_set_any(w, a, epi, st, force);
 }
-hipError_t launch_gemv_set_rope_kv(const QMat &wqkv, const uint32_t *qa_A, const float *qa_d, int N, const RopeKvArgs &ra, hipStream_t st) {
+hipError_t launch_gemv_set_rope_kv(const QMat &wqkv, const uint32_t *qa_A, const float *qa_d, int N, const RopeKvArgs &ra, hipStream_t st, const SetForce *force) {
     GemvSetArgs a = set_args(wqkv, qa_A, qa_d, N);
     a.ra = ra;
-    return launch_set_any(wqkv, a, EPI_ROPE_KV, st);
+    return launch_set_any(wqkv, a, EPI_ROPE_KV, st, force);
 }
 hipError_t launch_gemv_set_silu(const QMat &w13, const uint32_t *qa_A, const float *qa_d, int N, const uint16_t *T_silu,
                                 uint32_t *out_A, float *out_d, long out_strideA, long out_strideD, const SiluHalfIO &hx, hipStream_t st) {
@@ -705,6 +589,17 @@ hipError_t launch_gemv_set_silu(const QMat &w13, const uint32_t *qa_A, const flo
     a.T_silu = T_silu; a.out_A = out_A; a.out_d = out_d; a.out_strideA = out_strideA; a.out_strideD = out_strideD;
     a.amax_t = hx.amax_t; a.epoch = hx.epoch; a.layer = hx.layer; a.fault = hx.fault; a.lut_math = g_lut_math | fault_test;
     return launch_set_any(w13, a, gemv_set_silu_whole_blocks(w13, N, hx.amax_t && hx.epoch) ? EPI_SILU_QA : EPI_SILU_QAH, st);
+}
+
+// one SiLU epilogue named by the caller (llamahip_op_gemv_set_q4_0): no rule between halves and whole blocks, never the fault-injection bit
+hipError_t launch_gemv_set_silu_epi(const QMat &w13, int epi, const uint32_t *qa_A, const float *qa_d, int N, const uint16_t *T_silu,
+                                    uint32_t *out_A, float *out_d, long out_strideA, long out_strideD, const SiluHalfIO &hx, hipStream_t st, const SetForce *force) {
+    if (epi != EPI_SILU_QA && epi != EPI_SILU_QAH) return hipErrorInvalidValue;
+    if (epi == EPI_SILU_QAH && !(hx.amax_t && hx.epoch && hx.fault)) return hipErrorInvalidValue;
+    GemvSetArgs a = set_args(w13, qa_A, qa_d, N);
+    a.T_silu = T_silu; a.out_A = out_A; a.out_d = out_d; a.out_strideA = out_strideA; a.out_strideD = out_strideD;
+    a.amax_t = hx.amax_t; a.epoch = hx.epoch; a.layer = hx.layer; a.fault = hx.fault; a.lut_math = g_lut_math;
+    return launch_set_any(w13, a, epi, st, force);
 }
 
 hipError_t init_attrs_gemv_set() {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "q41_plan.h"
+#include "set_plan.h"
 
 namespace lh {
 
@@ -248,11 +249,15 @@ hipError_t launch_gemm_silu_qa(const QMat &w13, const uint32_t *qa_A, const floa
 //   placement xcd_selftest confirmed, the epoch word and SET_AMAX_GRANULES(F) * 16 zeroed granules)
 inline size_t set_amax_granules(int F) { return (size_t) F / 16 + 16; }      // per column
 bool gemv_set_applies(const QMat &w, int N, int epi);
-bool gemv_set_plan_query(int M, int K, bool interleaved, int N, int epi, long out[5]);      // host-only: the (nc, cw, ncg, rgw, LDS) plan, false = the kernel does not take the shape
+// (SetForce, an override of the plan's rule; the plan itself: set_plan.h)
+bool gemv_set_force_check(const QMat &w, int N, int epi, const SetForce &f, char *why, size_t why_cap);      // host-only; false: the reason in why
+bool gemv_set_launch_query(const QMat &w, int N, int epi, const SetForce *force, long out[7]);      // host-only: { nc, cw, ncg, rgw, LDS, grid, threads } of the launch
 bool gemv_set_silu_whole_blocks(const QMat &w13, int N, bool have_exchange);      // EPI_SILU_QA (whole-block workgroups, no exchange) instead of EPI_SILU_QAH
 hipError_t launch_gemv_set(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
-                           float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st);
-hipError_t launch_gemv_set_rope_kv(const QMat &wqkv, const uint32_t *qa_A, const float *qa_d, int N, const RopeKvArgs &ra, hipStream_t st);
+                           float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, const SetForce *force = nullptr);
+hipError_t launch_gemv_set_rope_kv(const QMat &wqkv, const uint32_t *qa_A, const float *qa_d, int N, const RopeKvArgs &ra, hipStream_t st, const SetForce *force = nullptr);
+hipError_t launch_gemv_set_silu_epi(const QMat &w13, int epi, const uint32_t *qa_A, const float *qa_d, int N, const uint16_t *T_silu,
+                                    uint32_t *out_A, float *out_d, long out_strideA, long out_strideD, const SiluHalfIO &hx, hipStream_t st, const SetForce *force = nullptr);
 hipError_t launch_gemv_set_silu(const QMat &w13, const uint32_t *qa_A, const float *qa_d, int N, const uint16_t *T_silu,
                                 uint32_t *out_A, float *out_d, long out_strideA, long out_strideD, const SiluHalfIO &hx, hipStream_t st);
 hipError_t init_attrs_gemv_set();

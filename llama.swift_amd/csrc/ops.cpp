@@ -129,6 +129,150 @@ int llamahip_op_gemv_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t inte
     return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
 }
 
+static_assert(LLAMAHIP_GEMV_EPI_ROPE_KV == EPI_ROPE_KV && LLAMAHIP_GEMV_EPI_SILU_QAH == EPI_SILU_QAH, "llamahip.h mirrors the few-row epilogues");
+
+// one launch of the few-row mat-mul (k_gemv_set) on caller-supplied operands (per-op tests of every (NC, CW) instance under every epilogue): see llamahip.h
+int llamahip_op_gemv_set_q4_0(const void *w_q4_0, int32_t M, int32_t K, int32_t interleaved, int32_t epi, const float *x, int32_t N, const int32_t *force,
+                              const float *resid, float *y, int32_t y_stride,
+                              int32_t d, int32_t dh, int32_t n_ctx, int32_t n_slots, int32_t n_past, const int32_t *row_pos, const int32_t *row_slot,
+                              float *qr, float *Kc, float *Vc,
+                              uint32_t *out_A, float *out_d, int32_t out_rows, int32_t layer, const float *x_prev, uint32_t *fault,
+                              int64_t *plan, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_gemv_set_q4_0";
+    const bool plain = epi == EPI_STORE || epi == EPI_RESID, rope = epi == EPI_ROPE_KV, qah = epi == EPI_SILU_QAH, silu = qah || epi == EPI_SILU_QA;
+    if (!plain && !rope && !silu) { set_err(err, err_cap, "%s: unknown epilogue %d (STORE, RESID, ROPE_KV, SILU_QA, SILU_QAH)", fn, epi); return LLAMAHIP_ERR_PREDICT; }
+    if (N < 2 || N > 60) { set_err(err, err_cap, "%s: N %d outside 2 .. 60 rows", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    if (M < 1 || K < 64 || K % 64 != 0) { set_err(err, err_cap, "%s: bad shape (M %d >= 1; K %d must be a positive multiple of 64)", fn, M, K); return LLAMAHIP_ERR_PREDICT; }
+    if (interleaved && M % 64 != 0) { set_err(err, err_cap, "%s: interleaved takes w1's F rows then w3's with F %% 32 == 0: M = 2F = %d is not a multiple of 64", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    if (silu != (interleaved != 0)) { set_err(err, err_cap, "%s: the SiLU epilogues take the interleaved w1|w3 matrix, the others a plain one (epilogue %d, interleaved %d)", fn, epi, interleaved); return LLAMAHIP_ERR_PREDICT; }
+    if (!w_q4_0 || !x) { set_err(err, err_cap, "%s: null operand (w, x)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (plain && !y) { set_err(err, err_cap, "%s: null operand (STORE / RESID need y)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (epi == EPI_RESID && !resid) { set_err(err, err_cap, "%s: null operand (RESID needs resid)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (plain && y_stride < M) { set_err(err, err_cap, "%s: y_stride %d < M %d", fn, y_stride, M); return LLAMAHIP_ERR_PREDICT; }
+    if (rope && (!qr || !Kc || !Vc)) { set_err(err, err_cap, "%s: null operand (ROPE_KV needs qr, Kc, Vc)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (silu && (!out_A || !out_d)) { set_err(err, err_cap, "%s: null operand (the SiLU epilogues need out_A, out_d)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (silu && out_rows < N) { set_err(err, err_cap, "%s: out_rows %d < N %d", fn, out_rows, N); return LLAMAHIP_ERR_PREDICT; }
+    if (qah && N > SET_MAX) { set_err(err, err_cap, "%s: SILU_QAH takes N <= %d rows (its exchange buffer), got %d", fn, SET_MAX, N); return LLAMAHIP_ERR_PREDICT; }
+    if (qah && !fault) { set_err(err, err_cap, "%s: null operand (SILU_QAH returns its fault word)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (qah && (layer < 0 || layer >= TAG_MAX_LAYERS)) { set_err(err, err_cap, "%s: layer %d outside 0 .. %d", fn, layer, TAG_MAX_LAYERS - 1); return LLAMAHIP_ERR_PREDICT; }
+    if (x_prev && !qah) { set_err(err, err_cap, "%s: x_prev is SILU_QAH's (the launch before this one on the same exchange buffer)", fn); return LLAMAHIP_ERR_PREDICT; }
+    const bool tables = rope && (row_pos || row_slot);
+    if (rope) {
+        if (d < 8 || d % 8 != 0 || M != 3 * d || dh < 2 || dh % 2 != 0 || d % dh != 0) {
+            set_err(err, err_cap, "%s: ROPE_KV takes M = 3 d (M %d, d %d), d a multiple of 8 and of the even head size dh %d", fn, M, d, dh); return LLAMAHIP_ERR_PREDICT;
+        }
+        if (n_ctx < 1 || n_slots < 1) { set_err(err, err_cap, "%s: n_ctx (%d) and n_slots (%d) must be >= 1", fn, n_ctx, n_slots); return LLAMAHIP_ERR_PREDICT; }
+        if (tables) {
+            if (!row_pos || !row_slot) { set_err(err, err_cap, "%s: row_pos and row_slot come together", fn); return LLAMAHIP_ERR_PREDICT; }
+            if (N > SET_MAX) { set_err(err, err_cap, "%s: a row table takes N <= %d rows (SeqSet), got %d", fn, SET_MAX, N); return LLAMAHIP_ERR_PREDICT; }
+            for (int r = 0; r < N; r++) {
+                if (row_slot[r] < 0 || row_slot[r] >= n_slots) { set_err(err, err_cap, "%s: row_slot[%d] = %d out of range [0, %d)", fn, r, row_slot[r], n_slots); return LLAMAHIP_ERR_PREDICT; }
+                if (row_pos[r] < 0 || row_pos[r] >= n_ctx) { set_err(err, err_cap, "%s: row_pos[%d] = %d out of range [0, n_ctx = %d)", fn, r, row_pos[r], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+                for (int q = 0; q < r; q++)
+                    if (row_slot[q] == row_slot[r] && row_pos[q] == row_pos[r]) {
+                        set_err(err, err_cap, "%s: rows %d and %d both write position %d of slot %d", fn, q, r, row_pos[r], row_slot[r]); return LLAMAHIP_ERR_PREDICT;
+                    }
+            }
+        } else if (n_past < 0 || n_past + N > n_ctx) {
+            set_err(err, err_cap, "%s: n_past %d + N %d rows outside n_ctx %d", fn, n_past, N, n_ctx); return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    QMat q;
+    q.set_shape(M, K);
+    if (interleaved) q.gmapF8 = M / 16;
+    q.tiles = (uint8_t *) (uintptr_t) 16;      // (the plan's predicates ask for a tile copy; the real one follows below)
+    SetForce sf;
+    if (force) {
+        sf.nc = force[0]; sf.cw = force[1]; sf.rgw = force[2]; sf.strict = true;
+        char why[200] = "";
+        if (!gemv_set_force_check(q, N, epi, sf, why, sizeof(why))) {
+            set_err(err, err_cap, "%s: forced plan {nc %d, cw %d, rgw %d} refused for M %d, K %d, N %d, epilogue %d: %s", fn, sf.nc, sf.cw, sf.rgw, M, K, N, epi, why);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    } else if (!gemv_set_applies(q, N, epi)) {
+        set_err(err, err_cap, "%s: k_gemv_set does not take M %d, K %d, N %d under epilogue %d (a plan that is instantiated and fits its LDS: llamahip_debug_set_plan)", fn, M, K, N, epi);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const SetForce *fp = force ? &sf : nullptr;
+    long lp[7];
+    if (!gemv_set_launch_query(q, N, epi, fp, lp)) { set_err(err, err_cap, "%s: no launch for M %d, K %d, N %d under epilogue %d", fn, M, K, N, epi); return LLAMAHIP_ERR_PREDICT; }
+    if (force && (lp[0] != sf.nc || lp[1] != sf.cw || (sf.rgw && lp[3] != sf.rgw))) {
+        set_err(err, err_cap, "%s: forced plan {nc %d, cw %d, rgw %d} would launch as <%ld,%ld> rgw %ld", fn, sf.nc, sf.cw, sf.rgw, lp[0], lp[1], lp[3]); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (plan) for (int i = 0; i < 7; i++) plan[i] = lp[i];
+    q.tiles = nullptr;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t nb = (size_t) K / 32, Kp = (size_t) q.Kp(), F = (size_t) M / 2, Fp = (F + 255) / 256 * 256;
+    const size_t oA = silu ? (size_t) out_rows * Fp / 4 : 0, od = silu ? (size_t) out_rows * (Fp / 32) : 0;
+    const size_t cache_f = rope ? (size_t) n_slots * n_ctx * d : 0;
+    std::vector<uint16_t> ts, te;
+    if (silu) { ts.resize(1 << 16); te.resize(1 << 16); lut_tables(ts, te); }
+    std::vector<double> tab;
+    if (rope) tab = rope_table(n_ctx, dh);
+    Scratch s;
+    hipStream_t st = s.stream();
+    if (qah && s.ok() && !xcd_selftest(8, 4, st)) {
+        set_err(err, err_cap, "%s: SILU_QAH needs workgroups 8 apart in the grid on one XCD; this device does not place them so", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    uint8_t *d_w = s.alloc((size_t) M * nb * 20, (const uint8_t *) w_q4_0);
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    float *d_x = s.alloc((size_t) N * K, x), *d_xp = x_prev ? s.alloc((size_t) N * K, x_prev) : nullptr;
+    uint32_t *d_qA = s.alloc<uint32_t>((size_t) N * Kp / 4);
+    float *d_qd = s.alloc<float>((size_t) N * (Kp / 32));
+    float *d_y = plain ? s.alloc((size_t) N * y_stride, y) : nullptr;      // (the floats outside the N x M block keep the caller's bits; so do the buffers below)
+    float *d_r = epi == EPI_RESID ? s.alloc((size_t) N * M, resid) : nullptr;
+    float *d_qr = rope ? s.alloc((size_t) N * d, qr) : nullptr, *d_K = rope ? s.alloc(cache_f, Kc) : nullptr, *d_V = rope ? s.alloc(cache_f, Vc) : nullptr;
+    double *d_tab = rope ? s.alloc(tab.size(), tab.data()) : nullptr;
+    SeqSet *d_set = nullptr;
+    if (tables) {
+        // pos[] and kv_off[] filled, every other member null: as the step's first launch (k_embed_set) leaves the descriptor for this kernel
+        SeqSet hs;
+        memset(&hs, 0, sizeof(hs));
+        hs.n = N;
+        for (int r = 0; r < N; r++) { hs.pos[r] = row_pos[r]; hs.kv_off[r] = (long) row_slot[r] * n_ctx * d; }
+        d_set = s.alloc(1, &hs);
+        s.sync();                              // (hs leaves scope)
+    }
+    uint32_t *d_oA = silu ? s.alloc(oA, out_A) : nullptr;
+    float *d_od = silu ? s.alloc(od, out_d) : nullptr;
+    uint16_t *d_ts = silu ? s.alloc(ts.size(), ts.data()) : nullptr, *d_te = silu ? s.alloc(te.size(), te.data()) : nullptr;
+    // SILU_QAH: the exchange granules, the epoch word and the fault word, zeroed ONCE (a model handle's: never cleared between launches)
+    const size_t ng = (size_t) SET_MAX * set_amax_granules((int) F);
+    uint64_t *d_am = qah ? s.alloc<uint64_t>(ng) : nullptr;
+    uint32_t *d_words = qah ? s.alloc<uint32_t>(8) : nullptr;              // [0] epoch, [4] fault
+    uint32_t *d_pA = x_prev ? s.alloc<uint32_t>((size_t) N * Fp / 4) : nullptr;      // the scratch operand rows of the launch on x_prev
+    float *d_pd = x_prev ? s.alloc<float>((size_t) N * (Fp / 32)) : nullptr;
+    if (qah) { s.fill(d_am, 0, ng * 8); s.fill(d_words, 0, 32); }
+    if (x_prev) { s.fill(d_pA, 0, (size_t) N * Fp); s.fill(d_pd, 0, (size_t) N * (Fp / 32) * 4); }
+    if (s.ok() && silu) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    if (s.ok() && !interleaved) s.check(launch_repack(d_w, q.tiles, M, K, 0, 0, st));
+    if (s.ok() && interleaved) s.check(launch_repack(d_w, q.tiles, (int) F, K, 1, 0, st));                      // as the loader: w1's rows ...
+    if (s.ok() && interleaved) s.check(launch_repack(d_w + F * nb * 20, q.tiles, (int) F, K, 1, 4, st));        // ... then w3's
+    SiluHalfIO hx;
+    if (qah) { hx.amax_t = d_am; hx.epoch = d_words; hx.layer = layer; hx.fault = d_words + 4; }
+    if (x_prev) {
+        if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_xp, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+        if (s.ok()) s.check(launch_bump_epoch(d_words, st));
+        if (s.ok()) s.check(launch_gemv_set_silu_epi(q, epi, d_qA, d_qd, N, d_ts, d_pA, d_pd, (long) (Fp / 4), (long) (Fp / 32), hx, st, fp));
+    }
+    if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, N, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+    if (s.ok() && qah) s.check(launch_bump_epoch(d_words, st));
+    if (s.ok() && plain) s.check(launch_gemv_set(q, epi, d_qA, d_qd, N, d_y, y_stride, d_r, M, st, fp));
+    if (s.ok() && rope) {
+        RopeKvArgs ra = { d_tab, d_qr, d_K, d_V, tables ? 0 : n_past, d, dh };
+        ra.set = d_set;
+        s.check(launch_gemv_set_rope_kv(q, d_qA, d_qd, N, ra, st, fp));
+    }
+    if (s.ok() && silu) s.check(launch_gemv_set_silu_epi(q, epi, d_qA, d_qd, N, d_ts, d_oA, d_od, (long) (Fp / 4), (long) (Fp / 32), hx, st, fp));
+    if (plain) s.download(y, d_y, (size_t) N * y_stride * 4);
+    if (rope) { s.download(qr, d_qr, (size_t) N * d * 4); s.download(Kc, d_K, cache_f * 4); s.download(Vc, d_V, cache_f * 4); }
+    if (silu) { s.download(out_A, d_oA, oA * 4); s.download(out_d, d_od, od * 4); }
+    if (qah) s.download(fault, d_words + 4, 4);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
+}
+
 // one prompt GEMM kernel on caller-supplied operands (per-op tests of every kernel launch_gemm can pick): see llamahip.h
 int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {

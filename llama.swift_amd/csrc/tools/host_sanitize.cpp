@@ -21,6 +21,7 @@
 #include "../dev_owner.h"
 #include "../model_file.h"
 #include "../q41_plan.h"
+#include "../set_plan.h"
 #include "../sched.h"
 
 struct llamahip_model { lh::ModelFile file; lh::SchedDev *sched = nullptr; };
@@ -1184,6 +1185,62 @@ int main(int argc, char **argv) {
         }
         EXPECT(q41_op_check(&wq, 8, 64, &xy, 17, &xy, 8, 2, err, sizeof(err)) == 0);
         printf("host_sanitize: Q4_1 mat-mul host half: %d plans, %zu refusals\n", plans, sizeof(bad) / sizeof(bad[0]));
+    }
+    {   // the few-row Q4_0 mat-mul's host half (set_plan.cpp): the plan of every LLaMA matrix at every row count 2 .. 60 and its launch shape,
+        // every (nc, cw) pair forced -- admitted or refused with a reason, on exactly sized message buffers -- and what the rule refuses
+        using namespace lh;
+        auto shape = [](int M, int K, bool inter) {
+            SetShape s;
+            s.M = M; s.K = K; s.ngroups = (M + 7) / 8; s.nchunks = (K + 255) / 256; s.gmapF8 = inter ? s.ngroups / 2 : 0; s.tiles = true;
+            return s;
+        };
+        const int widths[4][2] = { { 4096, 11008 }, { 5120, 13824 }, { 6656, 17920 }, { 8192, 22016 } };
+        struct Mat { int M, K; bool inter; int epi; };
+        std::vector<Mat> mats;
+        for (auto &w : widths) {
+            mats.push_back({ 3 * w[0], w[0], false, SET_EPI_ROPE_KV }); mats.push_back({ w[0], w[0], false, SET_EPI_RESID });
+            mats.push_back({ 2 * w[1], w[0], true, SET_EPI_SILU_QA });   mats.push_back({ 2 * w[1], w[0], true, SET_EPI_SILU_QAH });
+            mats.push_back({ w[0], w[1], false, SET_EPI_RESID });        mats.push_back({ 32000, w[0], false, SET_EPI_STORE });
+        }
+        for (int M : { 1, 24, 75, 6136, 6144, 12280, 12288 }) for (int K : { 64, 320, 4352 }) mats.push_back({ M, K, false, SET_EPI_STORE });
+        int plans = 0, admitted = 0, refused = 0;
+        for (auto &m : mats) {
+            const SetShape s = shape(m.M, m.K, m.inter);
+            for (int N = 2; N <= SET_ROWS_MAX; N++) {
+                const bool takes = set_applies(s, N, m.epi);
+                long q[7] = { 0 }, q5[5] = { 0 };
+                EXPECT(set_launch_query(s, N, m.epi, nullptr, q) == takes);
+                EXPECT(gemv_set_plan_query(m.M, m.K, m.inter, N, m.epi, q5) == takes);
+                if (takes) {
+                    EXPECT(set_plan_instantiated((int) q[0], (int) q[1]) && q[0] * q[1] * q[2] >= N && q[0] * q[1] * (q[2] - 1) < N);
+                    EXPECT(q[4] > 0 && (size_t) q[4] <= SET_LDS_CAP && q[6] == q[3] * q[1] * 64 && q[6] <= 512 && q[5] >= 1);
+                    EXPECT(q[2] == 1 || q[5] % (8 * q[2]) == 0);
+                    for (int i = 0; i < 5; i++) EXPECT(q[i] == q5[i]);
+                    plans++;
+                }
+                for (int nc = 0; nc <= 6; nc++)
+                    for (int cw = 0; cw <= 5; cw++)
+                        for (int rgw : { 0, 2, 4, 8, 9 }) {
+                            SetForce f;
+                            f.nc = nc; f.cw = cw; f.rgw = rgw; f.strict = true;
+                            std::vector<char> why(200, 0), why1(1, 'x');
+                            const bool ok = set_force_check(s, N, m.epi, f, why.data(), why.size());
+                            EXPECT(set_force_check(s, N, m.epi, f, why1.data(), why1.size()) == ok && (ok || why1[0] == 0));
+                            if (!ok) { EXPECT(why[0] != 0); refused++; continue; }
+                            EXPECT(set_plan_instantiated(nc, cw) && set_launch_query(s, N, m.epi, &f, q));
+                            EXPECT(q[0] == nc && q[1] == cw && q[2] == (N + nc * cw - 1) / (nc * cw) && (rgw == 0 || q[3] == rgw) && (size_t) q[4] <= SET_LDS_CAP && q[6] <= 512);
+                            admitted++;
+                        }
+            }
+            EXPECT(!set_applies(s, 1, m.epi) && !set_applies(s, SET_ROWS_MAX + 1, m.epi));
+        }
+        SetShape bare = shape(4096, 4096, false);
+        bare.tiles = false;
+        EXPECT(!set_applies(bare, 4, SET_EPI_RESID));                                                 // no tile copy
+        EXPECT(!set_applies(shape(4096, 4096, false), 4, SET_EPI_SILU_QA) && !set_applies(shape(4096, 4096, false), 4, SET_EPI_SILU_QAH));      // not the interleaved layout
+        EXPECT(!set_applies(shape(22016, 4096, true), 4, SET_EPI_ROPE_KV) && !set_applies(shape(4096, 4096, false), 4, 4) && !set_applies(shape(64, 147456, false), 4, SET_EPI_STORE));
+        EXPECT(plans > 0 && admitted > 0 && refused > 0);
+        printf("host_sanitize: few-row mat-mul host half: %d plans, %d forced plans admitted, %d refused\n", plans, admitted, refused);
     }
     {   // the owner of device memory (dev_owner.h) on the stub allocator: groups are all-or-nothing at every failing call, release, destruction by kind
         using lh::DevOwner;
