@@ -88,9 +88,11 @@ int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, struct ll
 
 /* Extension: generating past the context window (llamahip.h "generating past the context window").
  * mode 0 = stop at the wall (the default and the reference's behaviour: n_predict = min(numberOfTokens, n_ctx - n_inp), .mm:812),
- * 1 = re-evaluate (LLAMAHIP_CTX_REEVAL: exact); other values are 0.
+ * 1 = re-evaluate (LLAMAHIP_CTX_REEVAL: exact), 4 = shift the cache in place (LLAMAHIP_CTX_SHIFT: NOT the reference's arithmetic, opt-in:
+ * at the wall llamahip_kv_shift_rows moves the surviving rows down instead of the evals below; token bookkeeping, events and the lookup
+ * room are the same); other values are 0.
  * n_keep: the tokens at the start of the context that are never dropped; -1 = the prompt's length; either way at most n_ctx / 2.
- * A bridge that never calls the setter -- a caller that cannot be changed -- takes LLAMAHIP_RUNNER_OVERFLOW=reeval from the
+ * A bridge that never calls the setter -- a caller that cannot be changed -- takes LLAMAHIP_RUNNER_OVERFLOW=reeval (or =shift) from the
  * environment at each run (n_keep -1).  llama_runner_config keeps its layout.
  * With a mode set and a prompt that fits (n_inp <= n_ctx), n_predict is numberOfTokens, uncapped.  When the prompt is used up and the
  * pending token has no room (n_past == n_ctx) the loop applies llamahip_ctx_overflow_plan and feeds

@@ -452,7 +452,7 @@ int llamahip_op_topk_slide_set(const float *logits, int32_t n_rows, int32_t n_vo
 /* ---- generating past the context window ----------------------------------------------------------------------------------------------
  * The reference stops when the KV cache is full (n_predict = min(n_predict, n_ctx - n_inp), .mm:812) and every entry point above refuses
  * to pass n_ctx.  What every LLaMA runtime offers instead: keep the first n_keep tokens, drop the older half of the rest, go on.
- * Here by RE-EVALUATION:
+ * Two modes carry the plan out; the exact one is the default everywhere:
  *   LLAMAHIP_CTX_REEVAL  rows [0, n_keep) stay; the surviving tail is evaluated again at its new positions (llamahip_eval /
  *                        llamahip_eval_chunks at n_past = n_keep).  Defined purely by llama_eval calls, so it is EXACT: the reference making
  *                        the same calls leaves the same bits.  Costs one eval of the tail.
@@ -466,15 +466,48 @@ int llamahip_op_topk_slide_set(const float *logits, int32_t n_rows, int32_t n_vo
  *   llamahip_eval -- the loop's own token list drops the discarded tokens, and the pending token is evaluated as an ordinary single step.
  *   n_steps may exceed n_ctx many times over; n_past == n_ctx on entry is allowed.  out_tokens [n_steps]; logits_last (may be NULL): the
  *   last step's logits; *n_past_out (may be NULL): the context the cache holds afterwards.  Refused before any device work: what
- *   llamahip_decode_greedy refuses (HOST_ONLY and stage handles, token ids out of range), a mode other than LLAMAHIP_CTX_REEVAL, n_context != n_past,
+ *   llamahip_decode_greedy refuses (HOST_ONLY and stage handles, token ids out of range), a mode other than LLAMAHIP_CTX_REEVAL or LLAMAHIP_CTX_SHIFT, n_context != n_past,
  *   n_past > n_ctx, chunk_tokens < 0, and n_keep outside [0, n_ctx - 2] (nothing could be discarded at the wall).
- * An in-place shift of the cache (move the surviving K / V rows down, re-rotate the keys) is a second way to carry out the same plan; it is
- * not the reference's arithmetic and is not part of this library. */
+ *
+ *   LLAMAHIP_CTX_SHIFT   NOT the reference's arithmetic -- opt-in, never a default, never used for a parity claim (as LLAMAHIP_FLAG_FAST_PREFILL).
+ *                        The same plan carried out IN PLACE: the surviving K / V rows of every layer move down by n_discard positions on the
+ *                        device and every key is re-rotated by -n_discard positions (llamahip_kv_shift_rows, one launch per stage); nothing is
+ *                        evaluated again.  Two differences from re-evaluation: every moved key is narrowed to fp32 a second time, and the moved
+ *                        rows of every layer but the first keep the influence of the dropped tokens (they were computed attending to them).
+ *                        What IS claimed, and tested bit for bit: the kernel's arithmetic below, that no other row is written, and that the loop
+ *                        equals llamahip_decode_greedy legs with llamahip_kv_shift_rows calls between them.  Its value is 4: modes 0, 2 and 3 stay
+ *                        refused, as they always were.  Measured on the 7B (profiles/overflow_shift_probe_7b.json), per
+ *                        crossing, median (min .. max) of five fresh processes, n_keep 0 and 1 (disjoint ranges / one row of overlap):
+ *                        the shift 0.102 ms (0.096 .. 0.108) at n_ctx 512 and 0.37 ms (0.367 .. 0.380) at 2048 against 19.8 ms (19.8 .. 20.0)
+ *                        and 70.8 ms (70.7 .. 71.0) for one eval of the same tail --
+ *                        the shift's max lies below the re-eval's min at both sizes, the rule that justifies the mode.
+ *   llamahip_decode_greedy_window with mode LLAMAHIP_CTX_SHIFT calls, at the wall, llamahip_kv_shift_rows on the current slot with row_begin =
+ *   n_keep + n_discard, n_rows = position - n_keep - n_discard and the plan's n_discard in place of the eval; chunk_tokens is ignored (still
+ *   checked); every other argument check is the same.
+ *
+ * llamahip_kv_shift_rows -- n_shifts (1 .. LLAMAHIP_KV_SHIFT_MAX) shifts {slot[i], row_begin[i], n_rows[i], n_discard[i]} in one
+ *   k_kv_shift_rows launch per stage, each on its own device and stream, waited for; every file type.  Afterwards rows [row_begin - n_discard,
+ *   row_begin - n_discard + n_rows) of every layer of the slot hold the rows [row_begin, row_begin + n_rows): V bytewise; a K pair (x0, x1) at
+ *   elements (e, e + 1), e even, with pr = (e % head size) / 2 and (c, s) = (cos, sin) of entry [n_discard][pr] of the handle's own double
+ *   table (llamahip_debug_rope_table gives the same values), as
+ *       y0 = (float) (rn(rn((double) x0 * c) + rn((double) x1 * s)))        y1 = (float) (rn(rn((double) x1 * c) - rn((double) x0 * s)))
+ *   every operation rounded on its own in double, nothing contracted.  The two ranges may overlap in any way (n_discard >= 1).  NO other row
+ *   of any slot or layer is written; the current slot is left alone; n_rows[i] == 0 is a no-op entry.  Results that are subnormal in fp32
+ *   are outside the contract.  Refused before any device work, the message naming the limit: a null handle, n_shifts outside 1 .. 16, null
+ *   arrays, a slot outside [0, n_seq), a slot twice, n_discard < 1, rows outside [0, n_ctx] before or after the move, HOST_ONLY and stage
+ *   handles, a slot below a live scheduler's max_active.
+ * llamahip_cur_seq -- the handle's current slot (llamahip_set_seq), -1 for a null handle. */
 #define LLAMAHIP_CTX_REEVAL 1
+#define LLAMAHIP_CTX_SHIFT 4             /* (4: existing callers and tests know 0, 2 and 3 as refused) */
+#define LLAMAHIP_KV_SHIFT_MAX 16         /* shifts in one llamahip_kv_shift_rows call */
+#define LLAMAHIP_KV_SHIFT_ROWS_IN_FLIGHT 8   /* rows a thread of k_kv_shift_rows loads before it stores them (its batch edge, for tests) */
 int32_t llamahip_ctx_overflow_plan(int32_t n_ctx, int32_t n_past, int32_t n_keep, int32_t *n_discard);
 int llamahip_decode_greedy_window(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps,
                                   const int32_t *context, int32_t n_context, int32_t n_keep, int32_t mode, int32_t chunk_tokens,
                                   int32_t *out_tokens, float *logits_last, int32_t *n_past_out, char *err, size_t err_cap);
+int llamahip_kv_shift_rows(llamahip_model *m, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                           const int32_t *n_discard, char *err, size_t err_cap);
+int32_t llamahip_cur_seq(const llamahip_model *m);
 
 /* ---- the prompts of several sequences in one weight pass ------------------------------------------------------------------------------
  * The *_multi decode loops above step up to 16 conversations per weight stream, but every slot's context still had to be evaluated with
@@ -1118,6 +1151,22 @@ int llamahip_bench_gemv(llamahip_model *m, int32_t which, int32_t layer, int32_t
  * one untimed call.  The arguments are llamahip_kv_copy_rows' and are refused the same way.  Measurement tooling only. */
 int llamahip_bench_kv_copy(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot, const int32_t *row_begin,
                            const int32_t *n_rows, int32_t how, int32_t iters, double *ms_per_call, char *err, size_t err_cap);
+
+/* Times llamahip_kv_shift_rows' launch on a plain handle: one untimed launch, then `iters` launches between two events on the handle's stream;
+ * *ms_per_launch: the events' time / iters.  The arguments are llamahip_kv_shift_rows' and are refused the same way; the rows it moves are
+ * moved iters + 1 times, so the slot's contents are spent afterwards.  Measurement tooling only. */
+int llamahip_bench_kv_shift(llamahip_model *m, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                            const int32_t *n_discard, int32_t iters, double *ms_per_launch, char *err, size_t err_cap);
+
+/* One k_kv_shift_rows launch (llamahip_kv_shift_rows' kernel and arithmetic; NOT the reference's) on caller-supplied host caches Kc, Vc
+ * [n_slots][n_layers][n_ctx][d] fp32, copied up and back, with the library's angle table for (n_ctx, dh).  Refused with the limit named, before
+ * any device work: null caches, counts < 1, d not a multiple of 4, dh odd or not dividing d, and what llamahip_kv_shift_rows refuses of its table. */
+int llamahip_op_kv_shift(float *Kc, float *Vc, int32_t n_slots, int32_t n_layers, int32_t n_ctx, int32_t d, int32_t dh, int32_t n_shifts,
+                         const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows, const int32_t *n_discard, char *err, size_t err_cap);
+/* Host only: the library's RoPE angle table, out[n_ctx][dh / 2][2] = {cos, sin} of position * 10000^(-2 pair / dh) from the host libm's
+ * sincos -- what a model load and the ops upload.  Other libms differ in the last bit of some entries, so a restatement of a kernel that
+ * reads the table reads this.  Returns 0, or -1 for n_ctx < 1, dh odd or < 2, or a null out. */
+int32_t llamahip_debug_rope_table(int32_t n_ctx, int32_t dh, double *out);
 
 /* In-kernel phase probe of the decode GEMVs: runs n_steps greedy decode steps with the probe armed;
  * one record of 8 uint64 per GEMV launch {s_memtime at entry, loads issued, prologue done, weights

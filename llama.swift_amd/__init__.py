@@ -15,6 +15,9 @@ shim module at the repository root.
 """
 from .binding import (  # noqa: F401
     CTX_REEVAL,
+    CTX_SHIFT,
+    KV_SHIFT_MAX,
+    KV_SHIFT_ROWS_IN_FLIGHT,
     LIB_PATH,
     LlamaHipError,
     Model,
@@ -42,6 +45,7 @@ from .binding import (  # noqa: F401
     op_embed,
     op_gemv_q4_0,
     op_gemv_set_q4_0,
+    op_kv_shift,
     op_logprob,
     op_mul_mat_dense,
     op_mul_mat_q4_1,
@@ -61,6 +65,7 @@ from .binding import (  # noqa: F401
     q41_plan,
     qa_to_blocks,
     quantize_file,
+    rope_table,
     sched_event_cap,
     sched_plan,
     sched_plan_drafts,

@@ -17,6 +17,9 @@ INCLUDE = os.path.join(ROOT, "include")
 
 ERR_LOAD, ERR_PREDICT = -1000, -1001
 CTX_REEVAL = 1          # LLAMAHIP_CTX_REEVAL: what to do when the KV cache is full
+CTX_SHIFT = 4           # LLAMAHIP_CTX_SHIFT: ... the in-place shift (NOT the reference's arithmetic: opt-in)
+KV_SHIFT_MAX = 16       # LLAMAHIP_KV_SHIFT_MAX: the shifts of one Model.kv_shift_rows / op_kv_shift call
+KV_SHIFT_ROWS_IN_FLIGHT = 8   # LLAMAHIP_KV_SHIFT_ROWS_IN_FLIGHT: rows a thread of k_kv_shift_rows loads before it stores them
 SCORE_CHOICES_MAX = 16  # LLAMAHIP_SCORE_CHOICES_MAX: the endings of one Model.score_choices call
 DUMP_NAMES = [
     "layer_in", "attn_normed", "q", "k", "v", "q_roped", "kq_softmax", "kqv", "kqv_merged",
@@ -222,6 +225,13 @@ def lib() -> C.CDLL:
     L.llamahip_sched_plan_prefix.restype = i32
     L.llamahip_kv_copy_rows.argtypes = [vp, i32, vp, vp, vp, vp, cp, sz]
     L.llamahip_bench_kv_copy.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, C.POINTER(C.c_double), cp, sz]
+    L.llamahip_kv_shift_rows.argtypes = [vp, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_bench_kv_shift.argtypes = [vp, i32, vp, vp, vp, vp, i32, C.POINTER(C.c_double), cp, sz]
+    L.llamahip_op_kv_shift.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_debug_rope_table.argtypes = [i32, i32, vp]
+    L.llamahip_debug_rope_table.restype = i32
+    L.llamahip_cur_seq.argtypes = [vp]
+    L.llamahip_cur_seq.restype = i32
     L.llamahip_debug_attn_path.argtypes = [i32, i32, i32, i32, i32]
     L.llamahip_debug_attn_path.restype = i32
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
@@ -861,7 +871,8 @@ class Model:
     def decode_greedy_window(self, first_token: int, n_steps: int, n_past: int, context, n_keep: int = 0, mode: int = CTX_REEVAL,
                              chunk_tokens: int = 0, n_threads: int = 8, want_logits: bool = False):
         """llamahip_decode_greedy_window: decode_greedy in legs that never stop at n_ctx -- at the wall the first n_keep tokens stay, the older
-        half of the rest is dropped (ctx_overflow_plan) and the tail is re-evaluated (CTX_REEVAL, exact; chunk_tokens 0 = one eval).
+        half of the rest is dropped (ctx_overflow_plan) and the tail is re-evaluated (CTX_REEVAL, exact; chunk_tokens 0 = one eval) or, with
+        mode CTX_SHIFT, the surviving rows are moved down in place by kv_shift_rows (NOT the reference's arithmetic; chunk_tokens ignored).
         context: the n_past tokens already evaluated.  Returns (tokens[n_steps], n_past afterwards) and with
         want_logits the last step's logits too."""
         context = np.ascontiguousarray(context, np.int32).ravel()
@@ -890,6 +901,19 @@ class Model:
         cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_kv_copy_rows(self._h, len(c), *(_ptr(a) for a in cols), err, len(err)), err)
+
+    def kv_shift_rows(self, shifts) -> None:
+        """llamahip_kv_shift_rows (NOT the reference's arithmetic): shifts = [(slot, first row, row count, n_discard), ...], 1 .. 16 of them --
+        those KV rows of every layer move down by n_discard rows in place, the keys re-rotated by -n_discard positions, one launch per stage."""
+        c = np.ascontiguousarray(shifts, np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_kv_shift_rows(self._h, len(c), *(_ptr(a) for a in cols), err, len(err)), err)
+
+    @property
+    def cur_seq(self) -> int:
+        """llamahip_cur_seq: the handle's current KV slot"""
+        return int(lib().llamahip_cur_seq(self._h))
 
     def kv(self, il: int, n_pos: int):
         k = np.empty((n_pos, self.n_embd), np.float32)
@@ -941,6 +965,16 @@ class Model:
         ms = C.c_double(0)
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_bench_kv_copy(self._h, len(c), *(_ptr(a) for a in cols), int(how), int(iters), C.byref(ms), err, len(err)), err)
+        return float(ms.value)
+
+    def bench_kv_shift(self, shifts, iters: int = 20) -> float:
+        """llamahip_bench_kv_shift: milliseconds per k_kv_shift_rows launch of `shifts` (as kv_shift_rows takes them), event-timed over `iters`
+        launches after one untimed launch."""
+        c = np.ascontiguousarray(shifts, np.int32).reshape(-1, 4)
+        cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
+        ms = C.c_double(0)
+        err = C.create_string_buffer(1024)
+        _check(lib().llamahip_bench_kv_shift(self._h, len(c), *(_ptr(a) for a in cols), int(iters), C.byref(ms), err, len(err)), err)
         return float(ms.value)
 
     def stats(self) -> dict:
@@ -1471,6 +1505,29 @@ def op_attention_rows(qkv: np.ndarray, H: int, Kc: np.ndarray, Vc: np.ndarray, r
                                           _ptr(tab[2]), int(n_threads), _ptr(merged), ms, _ptr(wo), err, len(err))
     _check(rc, err)
     return merged, wo
+
+
+def op_kv_shift(Kc: np.ndarray, Vc: np.ndarray, dh: int, shifts) -> None:
+    """One k_kv_shift_rows launch (llamahip_op_kv_shift; NOT the reference's arithmetic) on Kc / Vc f32 [n_slots, n_layers, n_ctx, d], updated
+    in place: shifts = [(slot, first row, row count, n_discard), ...] as Model.kv_shift_rows takes them; the angle table is rope_table(n_ctx, dh)."""
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 4 or a.shape != Kc.shape:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_slots, n_layers, n_ctx, d]")
+    c = np.ascontiguousarray(shifts, np.int32).reshape(-1, 4)
+    cols = [np.ascontiguousarray(c[:, k]) for k in range(4)]
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_kv_shift(_ptr(Kc), _ptr(Vc), Kc.shape[0], Kc.shape[1], Kc.shape[2], Kc.shape[3], int(dh), len(c), *(_ptr(a) for a in cols), err, len(err))
+    _check(rc, err)
+
+
+def rope_table(n_ctx: int, dh: int) -> np.ndarray:
+    """Host-only: the library's RoPE angle table float64 [n_ctx, dh // 2, 2] = (cos, sin) (llamahip_debug_rope_table)."""
+    if n_ctx < 1 or dh < 2 or dh % 2:
+        raise ValueError(f"rope_table: n_ctx {n_ctx} >= 1 and an even head size {dh} >= 2")
+    out = np.empty((n_ctx, dh // 2, 2), np.float64)
+    if lib().llamahip_debug_rope_table(int(n_ctx), int(dh), _ptr(out)) != 0:
+        raise ValueError("llamahip_debug_rope_table refused its arguments")
+    return out
 
 
 def debug_attn_path(N: int, head_size: int, n_past: int, n_threads: int, n_ctx: int) -> str | None:

@@ -1,7 +1,7 @@
 // ctx_overflow.cpp -- generating past the context window (include/llamahip.h): the one rule for what to drop when the KV cache is full
 // (llamahip_ctx_overflow_plan) and the device-resident greedy loop run in legs around it (llamahip_decode_greedy_window).  Pure host
 // code above the C ABI: the legs are llamahip_decode_greedy calls, the wall is crossed by llamahip_eval / llamahip_eval_chunks of the
-// surviving tail.
+// surviving tail (LLAMAHIP_CTX_REEVAL) or by llamahip_kv_shift_rows of the surviving rows (LLAMAHIP_CTX_SHIFT, not the reference's arithmetic).
 #include <stdint.h>
 #include <stdio.h>
 
@@ -31,7 +31,7 @@ extern "C" int llamahip_decode_greedy_window(llamahip_model *m, int32_t n_thread
     if (!err) err_cap = 0;
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     const int32_t C = llamahip_n_ctx(m), V = llamahip_n_vocab(m);
-    if (mode != LLAMAHIP_CTX_REEVAL) { snprintf(err, err_cap, "%s: mode %d is not LLAMAHIP_CTX_REEVAL (1)", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    if (mode != LLAMAHIP_CTX_REEVAL && mode != LLAMAHIP_CTX_SHIFT) { snprintf(err, err_cap, "%s: mode %d is not LLAMAHIP_CTX_REEVAL (1) or LLAMAHIP_CTX_SHIFT (4)", fn, mode); return LLAMAHIP_ERR_PREDICT; }
     if (n_steps < 1 || !out_tokens) { snprintf(err, err_cap, "%s: n_steps (%d) must be >= 1 and out_tokens non-null", fn, n_steps); return LLAMAHIP_ERR_PREDICT; }
     if (n_past < 0 || n_past > C) { snprintf(err, err_cap, "%s: n_past (%d) outside [0, n_ctx = %d]", fn, n_past, C); return LLAMAHIP_ERR_PREDICT; }
     if (n_context != n_past || (n_context > 0 && !context)) { snprintf(err, err_cap, "%s: n_context (%d) must equal n_past (%d): context holds the tokens at positions [0, n_past)", fn, n_context, n_past); return LLAMAHIP_ERR_PREDICT; }
@@ -53,8 +53,13 @@ extern "C" int llamahip_decode_greedy_window(llamahip_model *m, int32_t n_thread
             const int32_t np = llamahip_ctx_overflow_plan(C, pos, n_keep, &nd);
             if (np < 0) { snprintf(err, err_cap, "%s: nothing to discard at position %d with n_keep %d", fn, pos, n_keep); return LLAMAHIP_ERR_PREDICT; }
             const int32_t *tail = toks.data() + n_keep + nd, M = pos - n_keep - nd;
-            rc = chunk_tokens > 0 ? llamahip_eval_chunks(m, n_threads, n_keep, tail, M, chunk_tokens, nullptr, err, err_cap)
-                                  : llamahip_eval(m, n_threads, n_keep, tail, M, nullptr, err, err_cap);
+            if (mode == LLAMAHIP_CTX_SHIFT) {
+                // in place: the surviving rows move down by nd positions, the keys re-rotated; nothing is evaluated
+                const int32_t slot = llamahip_cur_seq(m), row_begin = n_keep + nd;
+                rc = llamahip_kv_shift_rows(m, 1, &slot, &row_begin, &M, &nd, err, err_cap);
+            } else
+                rc = chunk_tokens > 0 ? llamahip_eval_chunks(m, n_threads, n_keep, tail, M, chunk_tokens, nullptr, err, err_cap)
+                                      : llamahip_eval(m, n_threads, n_keep, tail, M, nullptr, err, err_cap);
             if (rc) return rc;
             toks.erase(toks.begin() + n_keep, toks.begin() + n_keep + nd);
             pos = np;

@@ -37,6 +37,11 @@ inline int need_device(char *err, size_t err_cap) {
 // (llamahip.cpp: a model load and llamahip_op_attention upload the same ones)
 void lut_tables(std::vector<uint16_t> &ts, std::vector<uint16_t> &te);
 std::vector<double> rope_table(int n_ctx, int dh);
+// what llamahip_kv_shift_rows and llamahip_op_kv_shift refuse of a table of shifts (llamahip.cpp): 0 and `tab` filled, or LLAMAHIP_ERR_PREDICT and
+// the message naming the limit; slots_of is appended to the slot-range message (what bounds the slots, or "")
+struct KvShiftTab;
+int kv_shift_table_check(int32_t n_slots, const char *slots_of, int32_t n_ctx, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                         const int32_t *n_discard, KvShiftTab &tab, const char *fn, char *err, size_t err_cap);
 
 // QA operand (kcommon.hip.h quantize_y: rows Kp / 4 dwords and Kp / 32 scales apart, Kp = K rounded up to 256; dword (c * 8 + k) * 8 + j
 // of a row holds chain k of block c * 8 + j as signed nibbles, shifted 4 bits in odd blocks) -> N rows of K / 32 Q4_0 blocks in file

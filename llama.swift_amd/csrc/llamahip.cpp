@@ -4314,6 +4314,110 @@ int llamahip_bench_kv_copy(llamahip_model *m, int32_t n_copies, const int32_t *s
     return LLAMAHIP_OK;
 }
 
+static_assert(LLAMAHIP_KV_SHIFT_MAX == lh::KV_SHIFT_MAX && LLAMAHIP_KV_SHIFT_ROWS_IN_FLIGHT == lh::KV_SHIFT_U, "llamahip.h mirrors k_kv_shift_rows' limits");
+
+// what llamahip_kv_shift_rows and llamahip_op_kv_shift refuse of a table of shifts, one set of messages (host_util.h); slots_of: what bounds the slots
+extern "C++" int lh::kv_shift_table_check(int32_t n_slots, const char *slots_of, int32_t n_ctx, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                             const int32_t *n_discard, KvShiftTab &tab, const char *fn, char *err, size_t err_cap) {
+    if (n_shifts < 1 || n_shifts > LLAMAHIP_KV_SHIFT_MAX) { set_err(err, err_cap, "%s: n_shifts (%d) outside 1 .. %d", fn, n_shifts, LLAMAHIP_KV_SHIFT_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (!slot || !row_begin || !n_rows || !n_discard) { set_err(err, err_cap, "%s: null array", fn); return LLAMAHIP_ERR_PREDICT; }
+    tab = {};
+    tab.n = n_shifts;
+    for (int i = 0; i < n_shifts; i++) {
+        if (slot[i] < 0 || slot[i] >= n_slots) { set_err(err, err_cap, "%s: shift %d: slot %d out of range [0, %d)%s", fn, i, slot[i], n_slots, slots_of); return LLAMAHIP_ERR_PREDICT; }
+        for (int o = 0; o < i; o++)
+            if (slot[o] == slot[i]) { set_err(err, err_cap, "%s: slot %d is shifted by shift %d and by shift %d: a slot takes part in one shift of a call", fn, slot[i], o, i); return LLAMAHIP_ERR_PREDICT; }
+        if (n_discard[i] < 1) { set_err(err, err_cap, "%s: shift %d: n_discard (%d) must be >= 1", fn, i, n_discard[i]); return LLAMAHIP_ERR_PREDICT; }
+        if (n_rows[i] < 0 || row_begin[i] < 0 || (int64_t) row_begin[i] + n_rows[i] > n_ctx) {
+            set_err(err, err_cap, "%s: shift %d: rows [%d, %d + %d) outside [0, n_ctx (%d)]", fn, i, row_begin[i], row_begin[i], n_rows[i], n_ctx);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        if (row_begin[i] < n_discard[i]) {
+            set_err(err, err_cap, "%s: shift %d: rows moved down from %d by n_discard %d would begin below row 0, outside [0, n_ctx (%d)]", fn, i, row_begin[i], n_discard[i], n_ctx);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+        tab.slot[i] = slot[i]; tab.row_begin[i] = row_begin[i]; tab.n_rows[i] = n_rows[i]; tab.n_discard[i] = n_discard[i];
+    }
+    return 0;
+}
+
+// llamahip_kv_copy_rows' order: the arguments, then the handle, then its scheduler
+static int kv_shift_check(llamahip_model *m, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows, const int32_t *n_discard,
+                          lh::KvShiftTab &tab, const char *fn, char *err, size_t err_cap) {
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = lh::kv_shift_table_check(first_of(m)->n_seq, " (llamahip_opts.n_seq)", m->hp.n_ctx, n_shifts, slot, row_begin, n_rows, n_discard, tab, fn, err, err_cap);
+    if (rc) return rc;
+    if ((rc = lh::decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    if (m->sched)
+        for (int i = 0; i < n_shifts; i++)
+            if (slot[i] < lh::sched_dev_max_active(m->sched)) {
+                set_err(err, err_cap, "%s: shift %d writes slot %d, which belongs to the handle's live scheduler (slots below its max_active, %d)", fn, i, slot[i], lh::sched_dev_max_active(m->sched));
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    return 0;
+}
+// one k_kv_shift_rows launch per stage, each on its own device and stream, with the stage's own angle table; nothing is waited for
+static int kv_shift_enqueue(const std::vector<llamahip_model *> &stages, const lh::KvShiftTab &tab, const char *fn, char *err, size_t err_cap) {
+    for (llamahip_model *st : stages) {
+        HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
+        if (lh::launch_kv_shift_rows(st->Kc, st->Vc, st->sincos, tab, st->n_seq, st->l1 - st->l0, st->hp.n_ctx, st->hp.n_embd, st->hp.n_embd / st->hp.n_head, st->stream) != hipSuccess) {
+            set_err(err, err_cap, "%s: HIP error launching k_kv_shift_rows on device %d", fn, st->device);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    return 0;
+}
+
+int32_t llamahip_cur_seq(const llamahip_model *m) { return m ? m->cur_seq : -1; }
+
+int llamahip_kv_shift_rows(llamahip_model *m, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                           const int32_t *n_discard, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_kv_shift_rows";
+    lh::KvShiftTab tab;
+    int rc = kv_shift_check(m, n_shifts, slot, row_begin, n_rows, n_discard, tab, fn, err, err_cap);
+    if (rc) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const double t0 = now_ms();
+    rc = kv_shift_enqueue(stages, tab, fn, err, err_cap);
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_bench_kv_shift(llamahip_model *m, int32_t n_shifts, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows,
+                            const int32_t *n_discard, int32_t iters, double *ms_per_launch, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_bench_kv_shift";
+    lh::KvShiftTab tab;
+    int rc = kv_shift_check(m, n_shifts, slot, row_begin, n_rows, n_discard, tab, fn, err, err_cap);
+    if (rc) return rc;
+    if (!m->stages.empty() || iters < 1 || !ms_per_launch) {
+        set_err(err, err_cap, "%s: a plain handle, iters >= 1", fn);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    Events evs;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    HIP_TRY(evs.create(&e0), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(evs.create(&e1), LLAMAHIP_ERR_PREDICT);
+    // whatever fails once a launch is enqueued, the stream is drained before the call returns
+    auto record = [&](hipEvent_t ev) {
+        if (hipEventRecord(ev, m->stream) == hipSuccess) return 0;
+        (void) hipGetLastError();
+        set_err(err, err_cap, "%s: hipEventRecord failed", fn);
+        return (int) LLAMAHIP_ERR_PREDICT;
+    };
+    for (int it = -1; it < iters && rc == 0; it++) {          // (it == -1: untimed)
+        if (it == 0) rc = record(e0);
+        if (rc == 0) rc = kv_shift_enqueue({ m }, tab, fn, err, err_cap);
+    }
+    if (rc == 0) rc = record(e1);
+    if ((rc = drain_stages({ m }, rc, err, err_cap)) != 0) return rc;
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1), LLAMAHIP_ERR_PREDICT);
+    *ms_per_launch = (double) ms / iters;
+    return LLAMAHIP_OK;
+}
+
 int llamahip_kv_read(llamahip_model *m, int32_t il, int32_t n_pos, float *out_k, float *out_v, char *err, size_t err_cap) {
     if (m) for (llamahip_model *st : m->stages) if (il >= st->l0 && il < st->l1) return llamahip_kv_read(st, il, n_pos, out_k, out_v, err, err_cap);
     if (!m || m->host_only || il < m->l0 || il >= m->l1 || n_pos < 0 || n_pos > m->hp.n_ctx) { set_err(err, err_cap, "bad kv_read arguments"); return LLAMAHIP_ERR_PREDICT; }

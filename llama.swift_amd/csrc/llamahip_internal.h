@@ -359,5 +359,14 @@ hipError_t launch_sched_accept(const int32_t *pick, const int32_t *tokens, const
 constexpr int KV_COPY_MAX = 16;
 struct KvCopyTab { int32_t n; int32_t src[KV_COPY_MAX], dst[KV_COPY_MAX], row_begin[KV_COPY_MAX], n_rows[KV_COPY_MAX]; };
 hipError_t launch_kv_copy_rows(float *Kc, float *Vc, const KvCopyTab &tab, int n_slots, int n_layers, int n_ctx, int d, hipStream_t st);
+// KV rows of a slot moved down in place, keys re-rotated (kv_shift.hip, k_kv_shift_rows; NOT the reference's arithmetic): for every shift c < n
+// the rows [row_begin[c], row_begin[c] + n_rows[c]) of every one of the n_layers layers of Kc and Vc go to the rows n_discard[c] below, every K
+// pair rotated by -n_discard[c] positions with (cos, sin) = sincos_tab[n_discard[c]][pair] ([n_ctx][dh / 2][2] doubles, device memory).  Any
+// overlap of the two ranges is safe.  ONE launch (none where every shift is empty).  Refused (hipErrorInvalidValue, nothing launched): what
+// launch_kv_copy_rows refuses of slots, ranges and d, a slot twice, n_discard < 1, row_begin - n_discard < 0, dh odd or not dividing d.
+constexpr int KV_SHIFT_MAX = 16, KV_SHIFT_U = 8;
+struct KvShiftTab { int32_t n; int32_t slot[KV_SHIFT_MAX], row_begin[KV_SHIFT_MAX], n_rows[KV_SHIFT_MAX], n_discard[KV_SHIFT_MAX]; };
+hipError_t launch_kv_shift_rows(float *Kc, float *Vc, const double *sincos_tab, const KvShiftTab &tab, int n_slots, int n_layers, int n_ctx, int d, int dh,
+                                hipStream_t st);
 
 }  // namespace lh

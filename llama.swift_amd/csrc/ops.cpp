@@ -542,6 +542,37 @@ int llamahip_op_attention_rows(const float *qkv, int32_t R, int32_t d, int32_t H
     return LLAMAHIP_OK;
 }
 
+// one k_kv_shift_rows launch on caller-supplied caches [n_slots][n_layers][n_ctx][d] with rope_table(n_ctx, dh) (per-op tests of kv_shift.hip): see llamahip.h
+int llamahip_op_kv_shift(float *Kc, float *Vc, int32_t n_slots, int32_t n_layers, int32_t n_ctx, int32_t d, int32_t dh, int32_t n_shifts,
+                         const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows, const int32_t *n_discard, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_kv_shift";
+    if (!Kc || !Vc || n_slots < 1 || n_layers < 1 || n_ctx < 1) { set_err(err, err_cap, "%s: bad arguments (Kc, Vc not NULL; n_slots %d, n_layers %d, n_ctx %d all >= 1)", fn, n_slots, n_layers, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (d < 4 || d % 4 != 0) { set_err(err, err_cap, "%s: d (%d) must be a positive multiple of 4 (rows move in 16-byte granules)", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    if (dh < 2 || dh % 2 != 0 || d % dh != 0) { set_err(err, err_cap, "%s: head size %d must be even and divide d (%d)", fn, dh, d); return LLAMAHIP_ERR_PREDICT; }
+    KvShiftTab tab;
+    if (kv_shift_table_check(n_slots, "", n_ctx, n_shifts, slot, row_begin, n_rows, n_discard, tab, fn, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t cache = (size_t) n_slots * n_layers * n_ctx * d;
+    const std::vector<double> rt = rope_table(n_ctx, dh);
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_K = s.alloc(cache, Kc), *d_V = s.alloc(cache, Vc);
+    double *d_tab = s.alloc(rt.size(), rt.data());
+    if (s.ok()) s.check(launch_kv_shift_rows(d_K, d_V, d_tab, tab, n_slots, n_layers, n_ctx, d, dh, st));
+    s.download(Kc, d_K, cache * 4);
+    s.download(Vc, d_V, cache * 4);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
+}
+
+// host-only: the library's RoPE angle table [n_ctx][dh / 2][cos, sin] (rope_table: what a model load and the ops upload)
+int32_t llamahip_debug_rope_table(int32_t n_ctx, int32_t dh, double *out) {
+    if (n_ctx < 1 || dh < 2 || dh % 2 != 0 || !out) return -1;
+    const std::vector<double> rt = rope_table(n_ctx, dh);
+    memcpy(out, rt.data(), rt.size() * sizeof(double));
+    return 0;
+}
+
 // host-only: the attention path a model's multi-row eval of N rows after n_past takes once its workspace exists (ensure_attn_ws)
 int32_t llamahip_debug_attn_path(int32_t N, int32_t head_size, int32_t n_past, int32_t n_threads, int32_t n_ctx) {
     AttnWs ws;

@@ -41,7 +41,7 @@ struct llama_runner_bridge {
     int64_t loads = 0;                   // model loads performed by this bridge (tests)
     int32_t lookup = -1;                 // drafted sampled decoding: -1 never set (LLAMAHIP_RUNNER_LOOKUP decides), 0 off, 1 .. 15 the draft length
     llamahip_lookup_stats lookup_stats = { (int32_t) sizeof(llamahip_lookup_stats), 0, 0, 0, 0 };   // of the last run
-    int32_t overflow = -1;               // past the context window: -1 never set (LLAMAHIP_RUNNER_OVERFLOW decides), 0 stop at the wall, 1 re-evaluate
+    int32_t overflow = -1;               // past the context window: -1 never set (LLAMAHIP_RUNNER_OVERFLOW decides), 0 stop at the wall, 1 re-evaluate, 4 shift in place
     int32_t overflow_keep = -1;          // ... tokens never dropped; -1 = the prompt's length
 };
 
@@ -222,7 +222,7 @@ void llama_runner_bridge_set_lookup(llama_runner_bridge *b, int32_t draft_len) {
 }
 void llama_runner_bridge_set_overflow(llama_runner_bridge *b, int32_t mode, int32_t n_keep) {
     if (!b) return;
-    b->overflow = mode == LLAMAHIP_CTX_REEVAL ? mode : 0;
+    b->overflow = mode == LLAMAHIP_CTX_REEVAL || mode == LLAMAHIP_CTX_SHIFT ? mode : 0;
     b->overflow_keep = n_keep < 0 ? -1 : n_keep;
 }
 int32_t llama_runner_bridge_lookup_stats(const llama_runner_bridge *b, llamahip_lookup_stats *out) {
@@ -254,11 +254,11 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
         const char *e = getenv("LLAMAHIP_RUNNER_LOOKUP");
         lookup = e ? std::min(std::max(atoi(e), 0), 15) : 0;
     }
-    // past the context window: the setter's values, else LLAMAHIP_RUNNER_OVERFLOW=reeval (0: the reference's stop at the wall)
+    // past the context window: the setter's values, else LLAMAHIP_RUNNER_OVERFLOW=reeval or =shift (0: the reference's stop at the wall)
     int32_t overflow = b->overflow, keep_req = b->overflow_keep;
     if (overflow < 0) {
         const char *e = getenv("LLAMAHIP_RUNNER_OVERFLOW");
-        overflow = e && !strcmp(e, "reeval") ? LLAMAHIP_CTX_REEVAL : 0;
+        overflow = e && !strcmp(e, "reeval") ? LLAMAHIP_CTX_REEVAL : e && !strcmp(e, "shift") ? LLAMAHIP_CTX_SHIFT : 0;
         keep_req = -1;
     }
     llamahip_lookup_stats &ls = b->lookup_stats;
@@ -332,8 +332,12 @@ int32_t llama_runner_bridge_run(llama_runner_bridge *b, const char *prompt_c, co
             int32_t n_discard = 0;
             const int32_t n_new = llamahip_ctx_overflow_plan(n_ctx, n_past, n_keep, &n_discard);
             if (n_new < 0) { snprintf(err, sizeof(err), "context overflow: nothing to discard at n_ctx %d with n_keep %d", n_ctx, n_keep); return fail(); }
-            if (llamahip_eval_chunks(model, n_threads, n_keep, ctx_toks.data() + n_keep + n_discard, n_past - n_keep - n_discard, n_batch + 1,
-                                     nullptr, err, sizeof(err)) != 0) return fail();
+            if (overflow == LLAMAHIP_CTX_SHIFT) {
+                // ... the shift moves the surviving rows down in place instead (not the reference's arithmetic: opt-in)
+                const int32_t slot = llamahip_cur_seq(model), row_begin = n_keep + n_discard, n_rows = n_past - n_keep - n_discard;
+                if (llamahip_kv_shift_rows(model, 1, &slot, &row_begin, &n_rows, &n_discard, err, sizeof(err)) != 0) return fail();
+            } else if (llamahip_eval_chunks(model, n_threads, n_keep, ctx_toks.data() + n_keep + n_discard, n_past - n_keep - n_discard, n_batch + 1,
+                                            nullptr, err, sizeof(err)) != 0) return fail();
             ctx_toks.erase(ctx_toks.begin() + n_keep, ctx_toks.begin() + n_keep + n_discard);
             n_past = n_new;
         }

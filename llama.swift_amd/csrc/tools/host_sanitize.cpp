@@ -85,6 +85,15 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t, int32_t np, int32_t first
     for (int i = 0; lg && i < V; i++) lg[i] = (float) i;
     return 0;
 }
+// the in-place shift (LLAMAHIP_CTX_SHIFT): one shift of slot 0 per call, inside the cache on both sides; logged as kind 5 {first row, rows, n_discard}
+int32_t llamahip_cur_seq(const llamahip_model *m) { return m ? 0 : -1; }
+int llamahip_kv_shift_rows(llamahip_model *m, int32_t n, const int32_t *slot, const int32_t *row_begin, const int32_t *n_rows, const int32_t *n_discard, char *err, size_t err_cap) {
+    if (!g_drive) { snprintf(err, err_cap, "no HIP device available: libllamahip has no CPU fallback"); return LLAMAHIP_ERR_PREDICT; }
+    if (!m || n != 1 || !slot || !row_begin || !n_rows || !n_discard || slot[0] != 0 || n_discard[0] < 1 || n_rows[0] < 0 || row_begin[0] < n_discard[0] ||
+        row_begin[0] + n_rows[0] > m->file.hp.n_ctx) { snprintf(err, err_cap, "llamahip_kv_shift_rows: shift outside [0, n_ctx (%d)]", m ? m->file.hp.n_ctx : 0); return LLAMAHIP_ERR_PREDICT; }
+    g_calls.push_back({ 5, row_begin[0], n_rows[0], n_discard[0] });
+    return 0;
+}
 }
 namespace lh {
 // eval_multi.cpp (compiled in as it is): what llamahip_eval_multi refuses of its arguments / llamahip_op_attention_rows of a caller's table
@@ -511,6 +520,83 @@ int main(int argc, char **argv) {
                     if (mode == 1) EXPECT(reevals >= 2 && e3.tokens > 60);
                 }
         g_drive = false;
+    }
+    // the same in shift mode (LLAMAHIP_CTX_SHIFT): the greedy loop in legs on exactly sized arrays, every wall crossed by ONE shift of the plan's
+    // rows and no eval; the driver in mode 4, greedy, sampled and with lookup steps -- the stub's call sequence replayed against the plan
+    if (parts <= 1) {
+        g_drive = true;
+        llamahip_model *ms = nullptr;
+        EXPECT(llamahip_model_load(path.c_str(), 16, &o, &ms, err, sizeof(err)) == 0);
+        int shifts_window = 0, shifts_driver = 0;
+        if (ms)
+            for (int keep = 0; keep <= 14; keep++)
+                for (int np0 : { 0, 5, 16 })
+                    for (int chunk : { 0, 3 }) {          // (ignored by the mode)
+                        const int n_steps = 70;
+                        std::vector<int32_t> ctx((size_t) np0), out((size_t) n_steps, -1);
+                        for (int i = 0; i < np0; i++) ctx[i] = (int32_t) (rng() % (uint32_t) V);
+                        int32_t np_out = -1;
+                        g_calls.clear();
+                        EXPECT(llamahip_decode_greedy_window(ms, 1, np0, 1, n_steps, ctx.data(), np0, keep, LLAMAHIP_CTX_SHIFT, chunk, out.data(), nullptr, &np_out, err, sizeof(err)) == 0);
+                        int pos = np0, steps = 0;
+                        for (const EvalCall &c : g_calls) {
+                            if (c.kind == 3) { EXPECT(c.n_past == pos && pos + c.n <= 16); pos += c.n; steps += c.n; continue; }
+                            int32_t nd = 0;
+                            const int32_t nn = llamahip_ctx_overflow_plan(16, pos, keep, &nd);
+                            EXPECT(pos == 16 && nn > 0);
+                            EXPECT(c.kind == 5 && c.n_past == keep + nd && c.n == pos - keep - nd && c.chunk == nd);
+                            pos = nn;
+                            shifts_window++;
+                        }
+                        EXPECT(steps == n_steps && np_out == pos);
+                        for (int32_t t : out) EXPECT(t >= 0 && t < V);
+                    }
+        if (ms) {
+            int32_t out1[4], one = 1, npo = 0;
+            EXPECT(llamahip_decode_greedy_window(ms, 1, 1, 1, 4, &one, 1, 15, LLAMAHIP_CTX_SHIFT, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // n_keep
+            EXPECT(llamahip_decode_greedy_window(ms, 1, 1, 1, 4, &one, 1, 0, LLAMAHIP_CTX_SHIFT, -1, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);      // chunk_tokens
+            EXPECT(llamahip_decode_greedy_window(ms, 1, 1, 1, 4, &one, 1, 0, 5, 0, out1, nullptr, &npo, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);                        // mode
+            llamahip_model_free(ms);
+        }
+        for (int greedy = 0; greedy <= 2; greedy++)          // (2: sampled with lookup steps of up to 4 draft tokens)
+            for (int keep : { -1, 0, 3, 100 }) {
+                struct Ev4 { int tokens = 0, failed = 0, completed = 0; } e4;
+                g_calls.clear();
+                llama_runner_bridge *b4 = llama_runner_bridge_new(path.c_str());
+                llama_runner_bridge_set_overflow(b4, LLAMAHIP_CTX_SHIFT, keep);
+                if (greedy == 2) llama_runner_bridge_set_lookup(b4, 4);
+                llama_runner_config c4; llama_runner_config_default(&c4); c4.numberOfTokens = 60; c4.n_ctx = 24; c4.greedy = greedy == 1; c4.seed = 7;
+                const int32_t rc4 = llama_runner_bridge_run(b4, "", &c4, [](void *u, llama_event_type t, const char *, uint32_t, int32_t) {
+                    Ev4 *e = (Ev4 *) u; if (t == LLAMA_EVENT_OUTPUT_TOKEN) e->tokens++; if (t == LLAMA_EVENT_FAILED) e->failed++; if (t == LLAMA_EVENT_COMPLETED) e->completed++; }, &e4);
+                llama_runner_bridge_free(b4);
+                EXPECT(rc4 == 0 && e4.failed == 0 && e4.completed == 1 && e4.tokens > 60);
+                // replay: the evaluated rows add up to the position; a shift comes at the wall only and is the plan's; no eval of the tail follows it
+                int pos = 0, shifts = 0, verifies = 0, n_keep = -1;
+                for (size_t k = 1; k < g_calls.size(); k++) {          // (k = 0: the warm-up)
+                    const EvalCall &c = g_calls[k];
+                    if (c.kind == 5) {
+                        // (n_keep as the driver clamps it: c.n_past - c.chunk; the same at every crossing of a run)
+                        const int kp = c.n_past - c.chunk;
+                        int32_t nd = 0;
+                        const int32_t nn = llamahip_ctx_overflow_plan(24, pos, kp, &nd);
+                        EXPECT(pos == 24 && nn > 0 && c.chunk == nd && c.n == pos - kp - nd && kp >= 0 && kp <= 12 && (n_keep < 0 || n_keep == kp));
+                        if (keep >= 0) EXPECT(kp == std::min(keep, 12));
+                        n_keep = kp;
+                        pos = nn;
+                        shifts++;
+                        continue;
+                    }
+                    EXPECT(c.n_past == pos && pos + c.n <= 24);
+                    if (c.kind == 4) { verifies++; pos = k + 1 < g_calls.size() && g_calls[k + 1].kind != 5 ? g_calls[k + 1].n_past : pos + c.n; continue; }      // (a verify step keeps n_accept + 1 of its rows)
+                    EXPECT(shifts == 0 || c.n == 1);          // after the first crossing nothing but single steps
+                    pos += c.n;
+                }
+                EXPECT(shifts >= 2);
+                EXPECT(greedy == 2 ? verifies > 0 : verifies == 0);
+                shifts_driver += shifts;
+            }
+        g_drive = false;
+        printf("host_sanitize: shift mode: %d shifts in the greedy loop's legs and %d in the driver's runs, each the plan's, no tail evaluated again\n", shifts_window, shifts_driver);
     }
     // the dealing of a multi-sequence verify step's rows: exactly sized arrays, every n_seqs and budget, and the refusals
     for (int n = 1; n <= 16; n++)

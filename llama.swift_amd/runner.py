@@ -72,7 +72,8 @@ class LlamaRunner:
 
     def set_overflow(self, mode: int, n_keep: int = -1) -> None:
         """Generating past the context window (llama_runner_bridge_set_overflow): mode 0 = stop at the wall (the reference), 1 = re-evaluate
-        the surviving tail (exact); n_keep -1 = the prompt's length."""
+        the surviving tail (exact), 4 = shift the cache in place (binding.CTX_SHIFT: NOT the reference's arithmetic); n_keep -1 = the
+        prompt's length."""
         L, bridge = self._get_bridge()
         L.llama_runner_bridge_set_overflow.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         L.llama_runner_bridge_set_overflow.restype = None
