@@ -1016,8 +1016,8 @@ int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const flo
  * _SHORT k_rope_kv, k_decn_scores + k_dec_pv_blk<true> (2 .. 60 rows); _DEC k_dec_scores (RoPE and append inside, position from a device
  * state word) + k_dec_pv_blk<false> (N = 1); _DEC_STREAM k_dec_scores + k_dec_pv_stream with one workgroup per column block (N = 1).
  * A path that cannot take the shape is refused with a message naming the limit, before anything is launched.  *path_taken (may be NULL):
- * the path that ran.  Not covered (model-level tests only): the kernels with cross-workgroup hand-offs (k_dec_attn_x, k_qkv_attn,
- * k_dec_pv_dma, k_dec_pv_stream split over workgroups) and the batched decode step's form of the short path. */
+ * the path that ran.  Not covered here: the kernels with cross-workgroup hand-offs (k_dec_attn_x, k_dec_pv_dma, k_dec_pv_stream split
+ * over workgroups: llamahip_op_dec_attention; k_qkv_attn: llamahip_op_qkv_attn) and the batched decode step's form of the short path. */
 #define LLAMAHIP_ATTN_AUTO       0
 #define LLAMAHIP_ATTN_MFMA       1
 #define LLAMAHIP_ATTN_ROW        2
@@ -1037,6 +1037,61 @@ int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int
 int llamahip_op_attention_rows(const float *qkv, int32_t R, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
                                const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, int32_t n_threads,
                                float *merged, int32_t merged_stride, void *wo_operand, char *err, size_t err_cap);
+/* The one-row decode attention through ONE of the kernels that hand data between workgroups inside a launch, for n_steps (1 .. 64) steps on
+ * hand-off buffers that live across the steps: _X k_dec_attn_x (per-head counters; H % 8 == 0, n_threads <= 8, n_ctx <= 1024), _STREAM
+ * k_dec_scores + k_dec_pv_stream and _DMA k_dec_scores + k_dec_pv_dma (tagged partial sums when the key chains are split over workgroups;
+ * n_threads <= 32, n_ctx <= 4096; _DMA: head size 128, H % 8 == 0).  Step i: qkv row i of [n_steps][3d] (un-rotated, as the wq|wk|wv
+ * product) at position n_past[i], tagged with layer[i] (0 .. 249); bump_epoch[i] != 0 advances the epoch word (first epoch0) before the
+ * launch, as the first launch of a forward pass does.  Kc, Vc [n_ctx][d] go to the device once, every step appends its row, and the whole
+ * caches come back.  The op allocates the counters [H][32], the partial sums [32 d], the epoch word and the fault word, zeroes them ONCE and
+ * never clears them between steps (what a model handle's later steps see); its score and operand buffers start as 0xFF bytes.  First it
+ * asks the placement self-test as a model load does (H x (d / H / 32 + ceil(n_ctx / 32)) workgroups; H % 8 != 0: the 1-D rule over as
+ * many); a device that places workgroups otherwise is an error, not a fallback.  The fault-injection bit is never set.
+ * force: NULL = the library's rule, else {split, stage_rows, ns, dma} with 0 (dma: -1) = the rule: taken exactly as asked or refused with
+ * the reason (a split n_threads cannot take, a stage beyond 512 rows, more than 3 chains per workgroup of k_dec_pv_dma, ns < 2, LDS above
+ * 160 KB, dma contradicting the path); the LLAMAHIP_PV_* switches are not read.  plan[8] (may be NULL), set before the device is looked
+ * for: what llamahip_debug_dec_attn_plan reports.  Per step: merged [n_steps][d] (0xFF where the launch wrote nothing), wo_operand
+ * [n_steps][d / 32] Q4_0 blocks (may be NULL), fault [n_steps] the fault word after the step.  A fault word that is not zero ends the
+ * call with an error (later steps are not launched).  A layer used twice under one epoch with split chains is refused: a forward pass
+ * spends each tag once.  Everything is refused before any device is touched. */
+#define LLAMAHIP_DEC_ATTN_X      0
+#define LLAMAHIP_DEC_ATTN_STREAM 1
+#define LLAMAHIP_DEC_ATTN_DMA    2
+int llamahip_op_dec_attention(const float *qkv, int32_t n_steps, const int32_t *n_past, const int32_t *layer, const int32_t *bump_epoch, uint32_t epoch0,
+                              int32_t d, int32_t H, int32_t n_ctx, float *Kc, float *Vc, int32_t n_threads, int32_t path, const int32_t *force,
+                              float *merged, void *wo_operand, uint32_t *fault, int64_t *plan, char *err, size_t err_cap);
+/* The fused wq|wk|wv mat-vec + decode attention launch (k_qkv_attn: tagged q|k|v granules, tagged scores) for n_steps (1 .. 64) steps on
+ * hand-off buffers that live across the steps.  w_q4_0 [3d][d] Q4_0 blocks in file layout (repacked as llamahip_op_gemv_q4_0 does), norm_w
+ * [d], Kc / Vc [n_ctx][d] (n_ctx <= 4096; uploaded once, every step appends its row, the whole caches come back).  Step i: the residual-stream
+ * row x[i] of [n_steps][d]; n_part[i] pairs {sum, sum of squares} at part_in + 2 i part_stride (0: none -- the pairs are what makes the
+ * PREP_NORMP prologue apply); position n_past[i]; layer[i] (0 .. 249) enters the tags; bump_epoch[i] != 0 advances the epoch word (first
+ * epoch0) before the launch.  The op allocates the granules of the q|k|v row [3d] and of the scores [H][n_ctx], the epoch word and the
+ * fault word, zeroes them ONCE and never clears them between steps; it asks the placement self-test first, as a model load does.  Refused
+ * on the host with the reason: everything the model's own predicate refuses (H % 8, head sizes, n_threads > 8, a d whose mat-vec role is
+ * none of the three instances), tagged_in != 0 (the mailbox prologue PREP_NORM_TAG waits on another stage), a layer used twice under one
+ * epoch, positions outside the cache.  plans [n_steps][5] (may be NULL): per step what llamahip_debug_qkv_attn_plan reports.  Per step:
+ * merged [n_steps][d] (the op passes a buffer; the model passes none), wo_operand [n_steps][d / 32] Q4_0 blocks (may be NULL), fault
+ * [n_steps].  A fault word that is not zero ends the call with an error.  The fault-injection bit is never set. */
+int llamahip_op_qkv_attn(const void *w_q4_0, const float *norm_w, int32_t d, int32_t H, int32_t n_ctx, float *Kc, float *Vc, int32_t n_threads,
+                         int32_t n_steps, const float *x, const double *part_in, const int32_t *n_part, int32_t part_stride,
+                         const int32_t *n_past, const int32_t *layer, const int32_t *bump_epoch, uint32_t epoch0, int32_t tagged_in,
+                         float *merged, void *wo_operand, uint32_t *fault, int64_t *plans, char *err, size_t err_cap);
+/* Host-only (no device needed): the launch plan of the one-row decode attention (csrc/dec_attn_plan.cpp) for head layout (d, H), n_ctx and
+ * n_threads.  long_ctx: the long-context schedule; have_sync / have_xpart: the handle owns the counters of k_dec_attn_x / the partial-sum
+ * buffer of the split soft_max . V (both exist where the load-time placement self-test passed).  force NULL: the rule under the
+ * LLAMAHIP_PV_* switches, what a model handle launches; else {split, stage_rows, ns, dma} as llamahip_op_dec_attention takes it (strict).
+ * out = { kernel (LLAMAHIP_DEC_KERNEL_*), split, chains per workgroup, rows per stage (PV_STREAM), ring slots (PV_DMA), LDS bytes,
+ * workgroups, threads } of the soft_max . V launch (_X: of the one launch).  Returns 1, or 0 with the reason in why (may be NULL). */
+#define LLAMAHIP_DEC_KERNEL_PV_BLK    0
+#define LLAMAHIP_DEC_KERNEL_X         1
+#define LLAMAHIP_DEC_KERNEL_PV_STREAM 2
+#define LLAMAHIP_DEC_KERNEL_PV_DMA    3
+int32_t llamahip_debug_dec_attn_plan(int32_t d, int32_t H, int32_t n_ctx, int32_t n_threads, int32_t long_ctx, int32_t have_sync, int32_t have_xpart,
+                                     const int32_t *force, int64_t out[8], char *why, size_t why_cap);
+/* Host-only: the fused wq|wk|wv + attention launch (k_qkv_attn) a model handle of head layout (d, H) runs at n_ctx and n_threads, with
+ * n_part_in norm statistics offered by the row's producer (0: none) -- out = { prologue (2 NORM, 4 NORMP), ring depth, granules per thread,
+ * workgroups, LDS bytes }.  Returns 1, or 0 where the launch does not take the shape, the reason in why (may be NULL). */
+int32_t llamahip_debug_qkv_attn_plan(int32_t d, int32_t H, int32_t n_ctx, int32_t n_threads, int32_t n_part_in, int64_t out[5], char *why, size_t why_cap);
 /* the device half of llamahip_eval_topk on caller-supplied logits (n_vocab <= 32768, top_k <= 64) */
 int llamahip_op_topk(const float *logits, int32_t n_vocab, const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty,
                      int32_t top_k, double temp, double *cand_scores, int32_t *cand_ids, int32_t *exact, char *err, size_t err_cap);

@@ -15,6 +15,9 @@ shim module at the repository root.
 """
 from .binding import (  # noqa: F401
     CTX_REEVAL,
+    DEC_ATTN_KERNELS,
+    DEC_ATTN_PATHS,
+    DecAttnPlan,
     CTX_SHIFT,
     KV_SHIFT_MAX,
     KV_SHIFT_ROWS_IN_FLIGHT,
@@ -28,6 +31,7 @@ from .binding import (  # noqa: F401
     build,
     ctx_overflow_plan,
     debug_attn_path,
+    dec_attn_plan,
     declared_symbols,
     dense_paths,
     dense_set_plan,
@@ -42,6 +46,7 @@ from .binding import (  # noqa: F401
     lookup_draft,
     op_attention,
     op_attention_rows,
+    op_dec_attention,
     op_embed,
     op_gemv_q4_0,
     op_gemv_set_q4_0,
@@ -52,6 +57,7 @@ from .binding import (  # noqa: F401
     op_mul_mat_q4_0,
     op_prep,
     op_prompt_gemm_q4_0,
+    op_qkv_attn,
     op_quantize_row_q4_0,
     op_sched_accept,
     op_sched_pick,
@@ -64,6 +70,7 @@ from .binding import (  # noqa: F401
     q41_paths,
     q41_plan,
     qa_to_blocks,
+    qkv_attn_plan,
     quantize_file,
     rope_table,
     sched_event_cap,

@@ -1,6 +1,7 @@
 """ctypes binding of include/llamahip.h (no torch types cross the boundary)."""
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 import os
@@ -201,6 +202,12 @@ def lib() -> C.CDLL:
     L.llamahip_op_prompt_gemm_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
     L.llamahip_op_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, cp, sz]
     L.llamahip_op_attention_rows.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, cp, sz]
+    L.llamahip_op_dec_attention.argtypes = [vp, i32, vp, vp, vp, C.c_uint32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_debug_dec_attn_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, cp, sz]
+    L.llamahip_debug_dec_attn_plan.restype = i32
+    L.llamahip_debug_qkv_attn_plan.argtypes = [i32, i32, i32, i32, i32, vp, cp, sz]
+    L.llamahip_debug_qkv_attn_plan.restype = i32
+    L.llamahip_op_qkv_attn.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, C.c_uint32, i32, vp, vp, vp, vp, cp, sz]
     L.llamahip_eval_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
     L.llamahip_eval_multi_rows.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp]
     L.llamahip_eval_multi_rows.restype = i32
@@ -1469,6 +1476,102 @@ def op_attention(qkv: np.ndarray, H: int, n_past: int, Kc: np.ndarray, Vc: np.nd
     _check(rc, err)
     name = ATTN_PATHS[taken.value]
     return merged, (wo if name in ("short", "dec", "dec_stream") else None), name
+
+
+DEC_ATTN_PATHS = ("x", "stream", "dma")                                # LLAMAHIP_DEC_ATTN_* of llamahip.h, in order
+DEC_ATTN_KERNELS = ("pv_blk", "attn_x", "pv_stream", "pv_dma")         # LLAMAHIP_DEC_KERNEL_*, in order
+DecAttnPlan = collections.namedtuple("DecAttnPlan", "kernel split cpw SR NS lds grid threads")
+
+
+def _dec_force(force):
+    """None, or int32 [4] = (split, stage_rows, ns, dma) from a tuple or a dict of some of them (0, dma -1: the library's rule)"""
+    if force is None:
+        return None
+    if isinstance(force, dict):
+        force = (force.get("split", 0), force.get("stage_rows", 0), force.get("ns", 0), force.get("dma", -1))
+    return np.ascontiguousarray(force, np.int32).reshape(4)
+
+
+def _dec_plan(a) -> DecAttnPlan:
+    return DecAttnPlan(DEC_ATTN_KERNELS[int(a[0])], *(int(v) for v in a[1:]))
+
+
+def dec_attn_plan(d: int, H: int, n_ctx: int, n_threads: int, long_ctx: bool = False, have_sync: bool = True, have_xpart: bool = True, force=None):
+    """Host-only: the launch plan of the one-row decode attention (llamahip_debug_dec_attn_plan) as DecAttnPlan(kernel, split, cpw, SR, NS, lds,
+    grid, threads).  force None: what a model handle launches (the rule under the LLAMAHIP_PV_* switches); else (split, stage_rows, ns, dma) or
+    a dict of some of them, taken exactly or refused: LlamaHipError with the reason."""
+    a = np.zeros(8, np.int64)
+    why = C.create_string_buffer(256)
+    if not lib().llamahip_debug_dec_attn_plan(int(d), int(H), int(n_ctx), int(n_threads), int(long_ctx), int(have_sync), int(have_xpart),
+                                              _ptr(_dec_force(force)), _ptr(a), why, len(why)):
+        raise LlamaHipError(-1, why.value.decode(errors="replace"))
+    return _dec_plan(a)
+
+
+def qkv_attn_plan(d: int, H: int, n_ctx: int, n_threads: int, n_part_in: int = 0):
+    """Host-only: (prologue, depth, pg, grid, lds) of the fused wq|wk|wv + attention launch of a model of head layout (d, H), or None where
+    k_qkv_attn does not take it (llamahip_debug_qkv_attn_plan)."""
+    a = np.zeros(5, np.int64)
+    return tuple(int(v) for v in a) if lib().llamahip_debug_qkv_attn_plan(int(d), int(H), int(n_ctx), int(n_threads), int(n_part_in), _ptr(a), None, 0) else None
+
+
+def op_dec_attention(path: str, steps, H: int, Kc: np.ndarray, Vc: np.ndarray, n_threads: int = 8, force=None, epoch0: int = 0, want_wo: bool = True):
+    """Decode steps of one layer's attention through a hand-off kernel (llamahip_op_dec_attention), on hand-off buffers the op zeroes once and
+    keeps across the steps.  path "x" | "stream" | "dma"; steps: [(qkv f32 [3d] un-rotated, n_past, layer, bump_epoch), ...]; Kc / Vc f32
+    [n_ctx, d] (updated in place: the device's whole copy comes back); force as dec_attn_plan's.  Returns (merged f32 [n_steps, d], the wo
+    operand uint8 [n_steps, d/32, 20] or None, fault uint32 [n_steps], the DecAttnPlan that ran)."""
+    n = len(steps)
+    qkv = np.ascontiguousarray(np.stack([np.asarray(s[0], np.float32).ravel() for s in steps]), np.float32) if n else np.zeros((0, 3), np.float32)
+    d = qkv.shape[1] // 3
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 2 or a.shape[1] != d or a.shape[0] != Kc.shape[0]:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_ctx, d]")
+    cols = [np.ascontiguousarray([int(s[k]) for s in steps], np.int32) for k in (1, 2, 3)]
+    merged = np.full((n, d), np.nan, np.float32)
+    wo = np.full((n, max(d // 32, 1), 20), 0xEE, np.uint8) if want_wo else None
+    fault = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+    plan = np.full(8, -1, np.int64)
+    code = DEC_ATTN_PATHS.index(path) if path in DEC_ATTN_PATHS else int(path)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_dec_attention(_ptr(qkv), n, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), int(epoch0) & 0xFFFFFFFF, d, int(H), Kc.shape[0],
+                                         _ptr(Kc), _ptr(Vc), int(n_threads), code, _ptr(_dec_force(force)), _ptr(merged), _ptr(wo), _ptr(fault),
+                                         _ptr(plan), err, len(err))
+    _check(rc, err)
+    return merged, wo, fault[:n], _dec_plan(plan)
+
+
+def op_qkv_attn(wq: np.ndarray, norm_w, steps, H: int, Kc: np.ndarray, Vc: np.ndarray, n_threads: int = 8, epoch0: int = 0, tagged_in: bool = False,
+                want_wo: bool = True):
+    """Decode steps of the fused wq|wk|wv + attention launch (llamahip_op_qkv_attn).  wq uint8 [3d, d/32, 20] in file layout; norm_w f32 [d];
+    steps: [(x f32 [d], part_in float64 [n, 2] or None, n_past, layer, bump_epoch), ...]; Kc / Vc f32 [n_ctx, d] (updated in place).  Returns
+    (merged f32 [n_steps, d], the wo operand uint8 [n_steps, d/32, 20] or None, fault uint32 [n_steps], plans [(pre, depth, pg, grid, lds)])."""
+    wq = np.ascontiguousarray(wq, np.uint8)
+    d = wq.shape[1] * 32
+    n = len(steps)
+    x = np.ascontiguousarray(np.stack([np.asarray(s[0], np.float32).ravel() for s in steps]), np.float32)
+    parts = [None if s[1] is None else np.ascontiguousarray(s[1], np.float64).reshape(-1, 2) for s in steps]
+    n_part = np.ascontiguousarray([0 if p is None else p.shape[0] for p in parts], np.int32)
+    stride = int(n_part.max()) if n else 0
+    pin = None
+    if stride:
+        pin = np.zeros((n, stride, 2), np.float64)
+        for i, p in enumerate(parts):
+            if p is not None:
+                pin[i, :p.shape[0]] = p
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 2 or a.shape[1] != d or a.shape[0] != Kc.shape[0]:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_ctx, d]")
+    cols = [np.ascontiguousarray([int(s[k]) for s in steps], np.int32) for k in (2, 3, 4)]
+    merged = np.full((n, d), np.nan, np.float32)
+    wo = np.full((n, max(d // 32, 1), 20), 0xEE, np.uint8) if want_wo else None
+    fault = np.full(max(n, 1), 0xFFFFFFFF, np.uint32)
+    plans = np.full((max(n, 1), 5), -1, np.int64)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_qkv_attn(_ptr(wq), _ptr(np.ascontiguousarray(norm_w, np.float32)), d, int(H), Kc.shape[0], _ptr(Kc), _ptr(Vc), int(n_threads),
+                                    n, _ptr(x), _ptr(pin), _ptr(n_part), stride, _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), int(epoch0) & 0xFFFFFFFF,
+                                    int(tagged_in), _ptr(merged), _ptr(wo), _ptr(fault), _ptr(plans), err, len(err))
+    _check(rc, err)
+    return merged, wo, fault[:n], [tuple(int(v) for v in p) for p in plans[:n]]
 
 
 def eval_multi_rows(n_ctx: int, n_past, n_tokens, chunk_tokens: int = 0):

@@ -2094,68 +2094,26 @@ bool xcd_selftest(int H, int Y, hipStream_t st) {
 // (LLAMAHIP_HANDOFF_FAULT_TEST=4: the polls of k_dec_pv_stream give up after 256 looks and its publishers use a tag nobody waits for)
 static const int g_pv_fault_test = (getenv("LLAMAHIP_HANDOFF_FAULT_TEST") && atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) == 4) ? 0x1000 : 0;
 static bool th_split_ok(int nth, int split, int cpw) { return split >= 1 && cpw >= 1 && (split - 1) * cpw < nth; }
-bool pv_stream_applies(int dh, int n_ctx, int nth) { return nth >= 1 && nth <= 32 && n_ctx <= 4096 && dh % 32 == 0; }
+static_assert(DEC_ATTN_TS == DEC_TS, "dec_attn_plan.h mirrors the keys per score workgroup");
 
+// What runs -- kernel, split, rows per stage, ring slots, LDS, grid -- is dec_attn_plan's answer (dec_attn_plan.cpp, host-only); this
+// launches exactly that.  force (may be null: the LLAMAHIP_PV_* switches): a caller's plan (llamahip_op_dec_attention)
 hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, const double *tab, float *Kc, float *Vc,
                            float *sc, float *part, float *merged, uint32_t *qa_A, float *qa_d,
                            const uint16_t *T_exp, const int32_t *state, hipStream_t st, uint32_t *xsync, uint32_t *fault, bool long_ctx,
-                           uint64_t *xpart, const uint32_t *epoch, int layer) {
+                           uint64_t *xpart, const uint32_t *epoch, int layer, const DecAttnForce *force) {
     const int dh = d / H;
     const float kq_scale = 1.0f / sqrtf((float) d / (float) H);          // .mm:620
     (void) part;
-    // long contexts (the caller knows the position): scores, then the streaming soft_max . V
-    if (long_ctx && pv_stream_applies(dh, n_ctx, nth)) {
-        const int nsl = (n_ctx + DEC_TS - 1) / DEC_TS;
-        hipLaunchKernelGGL(k_dec_scores, dim3(H, nsl), dim3(256), 2 * dh * sizeof(float), st, qkv, d, dh, tab, Kc, Vc, sc, n_ctx, kq_scale, state);
-        LH_LAUNCH_CHECK();
-        // chains of a (head, column block) over `split` workgroups until the chip is full (needs the XCD placement: xpart is only
-        // passed when the load-time self-test confirmed it); every workgroup must own at least one chain
-        static const int split_env = getenv("LLAMAHIP_PV_SPLIT") ? atoi(getenv("LLAMAHIP_PV_SPLIT")) : 0;
-        const int W = H * (dh / 32);
-        auto valid = [&](int s) { const int cpw = (nth + s - 1) / s; return s >= 1 && s <= nth && (s - 1) * cpw < nth; };
-        int split = 1;
-        if (xpart && epoch && fault && W % 8 == 0) {
-            if (split_env > 0) { if (valid(split_env)) split = split_env; }
-            else while (W * split * 2 <= 256 && valid(split * 2)) split *= 2;       // (13B: 160 workgroups stay unsplit -- 320 would need two rounds: 322 against 298 tokens/s at 2 048 keys)
-        }
-        const int cpw = (nth + split - 1) / split;
-        constexpr int nl = 4;                   // 16-byte loads per thread and stage: 64 KB stages, 128 KB of LDS, one workgroup per CU
-        // (LLAMAHIP_PV_STAGE_ROWS shortens the stages so that small test contexts run many of them; tests only)
-        static const int sr_cap = getenv("LLAMAHIP_PV_STAGE_ROWS") ? std::max(1, atoi(getenv("LLAMAHIP_PV_STAGE_ROWS"))) : 1 << 20;
-        const int SR = std::min(nl * 128 / cpw, sr_cap);
-        const size_t lds = 32 * sizeof(double) + ((size_t) ((n_ctx + 3) & ~3) + (size_t) nth * 32) * sizeof(float) + (size_t) 2 * cpw * SR * 128;
-        // the LDS-DMA variant (k_dec_pv_dma): head size 128, a workgroup = (head, up to 3 chunks of the key split) over all 128 columns,
-        // the heads' chunks split over as many workgroups as fill the chip once; LLAMAHIP_PV_DMA=0 keeps k_dec_pv_stream
-        static const bool no_dma = getenv("LLAMAHIP_PV_DMA") && atoi(getenv("LLAMAHIP_PV_DMA")) == 0;
-        if (!no_dma && dh == 128 && xpart && epoch && fault && H % 8 == 0 && !getenv("LLAMAHIP_PV_STAGE_ROWS")) {
-            int sp = 1;
-            if (split_env > 0 && valid(split_env)) sp = split_env;
-            else while (H * sp * 2 <= 256 && valid(sp * 2)) sp *= 2;
-            const int cpwd = (nth + sp - 1) / sp;
-            if (cpwd <= 3) {
-                const size_t fixed = 32 * sizeof(double) + ((size_t) ((n_ctx + 3) & ~3) + (size_t) nth * 128) * sizeof(float) + 64;
-                int NS = (int) (((size_t) 156 * 1024 - fixed) / ((size_t) cpwd * 4096));
-                NS = std::max(2, std::min(NS, 256));
-                const size_t ldsd = fixed + (size_t) NS * cpwd * 4096;
-                hipLaunchKernelGGL(k_dec_pv_dma, dim3(H * sp), dim3(512), ldsd, st, sc, Vc, d, n_ctx, nth, NS, merged, qa_A, qa_d, T_exp, state, g_lut_math | g_pv_fault_test, H, sp, xpart, epoch, layer, fault);
-                LH_LAUNCH_CHECK();
-                return hipSuccess;
-            }
-        }
-        hipLaunchKernelGGL(k_dec_pv_stream<4>, dim3(W * split), dim3(1024), lds, st, sc, Vc, d, dh, n_ctx, nth, SR, merged, qa_A, qa_d, T_exp, state, g_lut_math | g_pv_fault_test, H, split, xpart, epoch, layer, fault);
-        LH_LAUNCH_CHECK();
-        return hipSuccess;
-    }
+    const DecAttnPlan p = dec_attn_plan(d, H, n_ctx, nth, long_ctx, xsync && fault, xpart && epoch && fault, force);
+    if (p.kernel < 0) return hipErrorInvalidValue;
     // scores and soft_max . V in one launch with an XCD-local hand-off (k_dec_attn_x); the caller passes xsync only
     // after xcd_selftest() confirmed the placement it relies on
     // (contexts beyond 1 024: the score slices no longer fit the chip next to the waiting workgroups at this kernel's 4 waves per
     //  SIMD -- 525 against 570 tokens/s at context 1 024, 429 against 481 at 2 048 on the 7B -- the two launches below take over)
-    if (xsync && fault && nth <= 8 && dh % 32 == 0 && dh <= 256 && H % 8 == 0 && n_ctx <= 1024) {
-        const int nsl = (n_ctx + DEC_TS - 1) / DEC_TS;
-        const size_t lds_pv = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
-        const size_t lds = std::max(lds_pv, (size_t) 2 * dh * sizeof(float));
+    if (p.kernel == DEC_ATTN_X) {
         const AttnXArgs aa = { qkv, d, dh, tab, Kc, Vc, sc, n_ctx, nth, kq_scale, merged, qa_A, qa_d, T_exp, state, xsync, fault, g_lut_math, nullptr, nullptr, nullptr, 0 };
-        hipLaunchKernelGGL(k_dec_attn_x, dim3(H, dh / 32 + nsl), dim3(256), lds, st, aa);
+        hipLaunchKernelGGL(k_dec_attn_x, dim3(p.gx, p.gy), dim3(p.threads), p.lds, st, aa);
         LH_LAUNCH_CHECK();
         return hipSuccess;
     }
@@ -2164,9 +2122,12 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
     const int nsl = (n_ctx + DEC_TS - 1) / DEC_TS;
     hipLaunchKernelGGL(k_dec_scores, dim3(H, nsl), dim3(256), 2 * dh * sizeof(float), st, qkv, d, dh, tab, Kc, Vc, sc, n_ctx, kq_scale, state);
     LH_LAUNCH_CHECK();
-    const int nt = (32 * (nth < 32 ? nth : 32) + 63) / 64 * 64;      // whole waves: the DPP reductions need every lane live
-    const size_t lds = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
-    hipLaunchKernelGGL(k_dec_pv_blk<false>, dim3(H, dh / 32), dim3(nt), lds, st, sc, Vc, d, dh, n_ctx, nth, merged, qa_A, qa_d, T_exp, state, 0, 0L, 0L, g_lut_math, 0, (const SeqSet *) nullptr, 0L);
+    if (p.kernel == DEC_ATTN_PV_DMA)
+        hipLaunchKernelGGL(k_dec_pv_dma, dim3(p.gx), dim3(p.threads), p.lds, st, sc, Vc, d, n_ctx, nth, p.NS, merged, qa_A, qa_d, T_exp, state, g_lut_math | g_pv_fault_test, H, p.split, xpart, epoch, layer, fault);
+    else if (p.kernel == DEC_ATTN_PV_STREAM)
+        hipLaunchKernelGGL(k_dec_pv_stream<4>, dim3(p.gx), dim3(p.threads), p.lds, st, sc, Vc, d, dh, n_ctx, nth, p.SR, merged, qa_A, qa_d, T_exp, state, g_lut_math | g_pv_fault_test, H, p.split, xpart, epoch, layer, fault);
+    else
+        hipLaunchKernelGGL(k_dec_pv_blk<false>, dim3(p.gx, p.gy), dim3(p.threads), p.lds, st, sc, Vc, d, dh, n_ctx, nth, merged, qa_A, qa_d, T_exp, state, 0, 0L, 0L, g_lut_math, 0, (const SeqSet *) nullptr, 0L);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -2188,15 +2149,24 @@ static QkvAttnKernel qkv_attn_kernel(int pre, int depth, int pg) {
 }
 static GemvPlan qkv_attn_plan(const QMat &w) {
     GemvPlan p = gemv_plan(w, PREP_NORM, EPI_STORE);
-    if (p.nw != 4 || !p.ring || !qkv_attn_kernel(PREP_NORM, p.depth, p.pg)) p.nw = 0;
+    if (!qkv_attn_instance(p.nw, p.ring, p.depth, p.pg) || !qkv_attn_kernel(PREP_NORM, p.depth, p.pg)) p.nw = 0;
     return p;
 }
 bool qkv_attn_applies(const QMat &w, int d, int H, int nth) {
     static const bool off = getenv("LLAMAHIP_NO_QKV_ATTN") != nullptr;
-    if (off || H % 8 != 0 || d % H != 0) return false;
-    const int dh = d / H;
-    if (dh % 32 != 0 || dh > 256 || nth > 8 || w.gmapF8 || w.M != 3 * d || w.K != d || w.ngroups != 3 * d / 8) return false;        // head layouts whose workgroups line up with heads
+    if (off || !qkv_attn_shape_ok(d, H, nth, w.M, w.K, w.ngroups, w.gmapF8)) return false;        // head layouts whose workgroups line up with heads
     return qkv_attn_plan(w).nw != 0;
+}
+// host-only: what launch_qkv_attn launches for (w, the norm statistics offered) -- out = { prologue, ring depth, granules per thread, grid, LDS bytes }
+bool qkv_attn_launch_query(const QMat &w, const NormPart &npp, int d, int H, int n_ctx, int nth, long out[5]) {
+    const GemvPlan p = qkv_attn_plan(w);
+    NormPart np = npp;
+    int pre = PREP_NORM;
+    norm_mode_resolve(&pre, &np);
+    if (!p.nw || !qkv_attn_kernel(pre, p.depth, p.pg)) return false;
+    const QkvAttnGeom g = qkv_attn_geom(p.grid, p.lds, d, H, n_ctx, nth);
+    out[0] = pre; out[1] = p.depth; out[2] = p.pg; out[3] = g.grid; out[4] = (long) g.lds;
+    return true;
 }
 hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, const NormPart &npp, uint64_t *qkv2, uint64_t *sc2, uint32_t *epoch, int layer,
                            int d, int H, int n_ctx, int nth, const double *tab, float *Kc, float *Vc, float *merged, uint32_t *qa_A, float *qa_d,
@@ -2210,10 +2180,9 @@ hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, c
     norm_mode_resolve(&pre, &np);
     const QkvAttnKernel k = qkv_attn_kernel(pre, p.depth, p.pg);
     if (!p.nw || !k) return hipErrorInvalidValue;
-    const int dh = d / H, nsl = (n_ctx + DEC_TS - 1) / DEC_TS, gridA = p.grid;
+    const int dh = d / H, gridA = p.grid;
     const float kq_scale = 1.0f / sqrtf((float) d / (float) H);          // .mm:620
-    const size_t lds_pv = 32 * sizeof(double) + ((size_t) n_ctx + (size_t) nth * 32 + 16) * sizeof(float);
-    const size_t lds = std::max(std::max(p.lds, lds_pv), (size_t) 2 * dh * sizeof(float));
+    const QkvAttnGeom g = qkv_attn_geom(p.grid, p.lds, d, H, n_ctx, nth);
     // the mat-vec role writes tagged granules: y -> qkv2, sync -> the epoch word, sync_epoch = layer
     // test only (tests/test_gpu_parity.py): the mat-vec role publishes a wrong tag and every poll gives up after 256 looks -> the
     // sticky fault word must come back as an error
@@ -2223,7 +2192,7 @@ hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, c
     if (x_t) { ga.in_t = x_t; ga.slot_in = 0; ga.pos_w = mb->pos_w; ga.patience = 3; ga.lut_math |= mb->test_bits; }
     const AttnXArgs aa = { nullptr, d, dh, tab, Kc, Vc, nullptr, n_ctx, nth, kq_scale, merged, qa_A, qa_d, T_exp, state, nullptr, fault, g_lut_math | fault_test,
                            qkv2, sc2, epoch, layer };
-    hipLaunchKernelGGL(k, dim3(gridA + H * (nsl + dh / 32)), dim3(256), lds, st, ga, aa, gridA, H);
+    hipLaunchKernelGGL(k, dim3(g.grid), dim3(256), g.lds, st, ga, aa, gridA, H);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

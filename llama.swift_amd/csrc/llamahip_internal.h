@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "dec_attn_plan.h"
 #include "q41_plan.h"
 #include "set_plan.h"
 
@@ -288,12 +289,13 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
                            const uint16_t *T_exp, const int32_t *state, hipStream_t st,
                            uint32_t *xsync = nullptr, uint32_t *fault = nullptr,      // xsync: H * 32 zeroed dwords -> single-launch k_dec_attn_x
                            bool long_ctx = false,                                     // long_ctx: k_dec_scores + k_dec_pv_stream (pv_stream_applies) ...
-                           uint64_t *xpart = nullptr, const uint32_t *epoch = nullptr, int layer = 0);      // ... its chains split over workgroups: [H dh/32][nth][32] granules, tag = (epoch, layer + 1)
-bool pv_stream_applies(int dh, int n_ctx, int nth);
+                           uint64_t *xpart = nullptr, const uint32_t *epoch = nullptr, int layer = 0,       // ... its chains split over workgroups: [H dh/32][nth][32] granules, tag = (epoch, layer + 1)
+                           const DecAttnForce *force = nullptr);                      // what runs is dec_attn_plan's answer (dec_attn_plan.h; pv_stream_applies lives there)
 bool xcd_selftest(int H, int Y, hipStream_t st);
 // wq|wk|wv mat-vec + decode attention as one launch (k_qkv_attn); xsync / fault as launch_dec_attn
 constexpr int TAG_MAX_LAYERS = 250;                                 // hand-off tags carry the layer index in 8 bits (kernels.hip make_tag)
 bool qkv_attn_applies(const QMat &w, int d, int H, int nth);
+bool qkv_attn_launch_query(const QMat &w, const NormPart &np, int d, int H, int n_ctx, int nth, long out[5]);      // host-only: { prologue, depth, pg, grid, LDS } of the launch
 hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, const NormPart &np, uint64_t *qkv2, uint64_t *sc2, uint32_t *epoch, int layer,
                            int d, int H, int n_ctx, int nth, const double *tab, float *Kc, float *Vc, float *merged, uint32_t *qa_A, float *qa_d,
                            const uint16_t *T_silu, const uint16_t *T_exp, const int32_t *state, uint32_t *fault, hipStream_t st,

@@ -487,6 +487,250 @@ int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int
     return LLAMAHIP_OK;
 }
 
+static_assert(LLAMAHIP_DEC_ATTN_X == 0 && LLAMAHIP_DEC_ATTN_STREAM == 1 && LLAMAHIP_DEC_ATTN_DMA == 2, "llamahip.h names the one-row hand-off paths");
+static_assert(LLAMAHIP_DEC_KERNEL_PV_BLK == DEC_ATTN_PV_BLK && LLAMAHIP_DEC_KERNEL_X == DEC_ATTN_X && LLAMAHIP_DEC_KERNEL_PV_STREAM == DEC_ATTN_PV_STREAM &&
+              LLAMAHIP_DEC_KERNEL_PV_DMA == DEC_ATTN_PV_DMA, "... and mirrors dec_attn_plan.h's kernels");
+
+static void dec_attn_plan_out(const DecAttnPlan &p, int64_t out[8]) {
+    const int64_t o[8] = { p.kernel, p.split, p.cpw, p.SR, p.NS, (int64_t) p.lds, (int64_t) p.gx * p.gy, p.threads };
+    for (int i = 0; i < 8; i++) out[i] = o[i];
+}
+// the plan llamahip_op_dec_attention runs for (path, force): strict, the path decides long_ctx / which buffers exist / dma; the switches are not read
+static DecAttnPlan dec_attn_op_plan(int d, int H, int n_ctx, int nth, int path, const int32_t *force, DecAttnForce &f) {
+    if (force) { f.split = force[0]; f.stage_rows = force[1]; f.ns = force[2]; f.dma = force[3]; }
+    f.strict = true;
+    DecAttnPlan bad;
+    const int want = path == LLAMAHIP_DEC_ATTN_X ? DEC_ATTN_X : path == LLAMAHIP_DEC_ATTN_STREAM ? DEC_ATTN_PV_STREAM : DEC_ATTN_PV_DMA;
+    if (path != LLAMAHIP_DEC_ATTN_X) {
+        const int dma = path == LLAMAHIP_DEC_ATTN_DMA ? 1 : 0;
+        if (f.dma != -1 && f.dma != dma) { snprintf(bad.why, sizeof(bad.why), "force dma %d contradicts path %s", f.dma, dma ? "DMA" : "STREAM"); return bad; }
+        f.dma = dma;
+    }
+    const bool lng = path != LLAMAHIP_DEC_ATTN_X;
+    const DecAttnPlan p = dec_attn_plan(d, H, n_ctx, nth, lng, !lng, lng, &f);
+    if (p.kernel >= 0 && p.kernel != want) {
+        snprintf(bad.why, sizeof(bad.why), "%s", want == DEC_ATTN_X ? "path X takes H % 8 == 0, n_threads <= 8 and n_ctx <= 1024 (k_dec_attn_x)"
+                                                                     : "paths STREAM / DMA take n_threads <= 32 and n_ctx <= 4096 (pv_stream_applies)");
+        return bad;
+    }
+    return p;
+}
+
+int32_t llamahip_debug_dec_attn_plan(int32_t d, int32_t H, int32_t n_ctx, int32_t n_threads, int32_t long_ctx, int32_t have_sync, int32_t have_xpart,
+                                     const int32_t *force, int64_t out[8], char *why, size_t why_cap) {
+    DecAttnForce f;
+    if (force) { f.split = force[0]; f.stage_rows = force[1]; f.ns = force[2]; f.dma = force[3]; f.strict = true; }
+    const DecAttnPlan p = dec_attn_plan(d, H, n_ctx, n_threads, long_ctx != 0, have_sync != 0, have_xpart != 0, force ? &f : nullptr);
+    if (why && why_cap) snprintf(why, why_cap, "%s", p.why);
+    if (p.kernel < 0 || !out) return 0;
+    dec_attn_plan_out(p, out);
+    return 1;
+}
+
+int32_t llamahip_debug_qkv_attn_plan(int32_t d, int32_t H, int32_t n_ctx, int32_t n_threads, int32_t n_part_in, int64_t out[5], char *why, size_t why_cap) {
+    char none[1];
+    if (!why || !why_cap) { why = none; why_cap = sizeof(none); }
+    why[0] = 0;
+    if (d < 1 || H < 1 || n_ctx < 1 || n_threads < 1) { snprintf(why, why_cap, "d %d, H %d, n_ctx %d and n_threads %d must be >= 1", d, H, n_ctx, n_threads); return 0; }
+    QMat w;
+    w.set_shape(3 * d, d);
+    if (!qkv_attn_shape_ok(d, H, n_threads, w.M, w.K, w.ngroups, w.gmapF8, why, why_cap)) return 0;
+    NormPart np;
+    // (a non-null marker: the query resolves the prologue, nothing is read)
+    if (n_part_in > 0) { np.in = (const double *) (uintptr_t) 16; np.n_in = n_part_in; }
+    long o[5];
+    if (!qkv_attn_applies(w, d, H, n_threads) || !qkv_attn_launch_query(w, np, d, H, n_ctx, n_threads, o)) {
+        snprintf(why, why_cap, "the wq|wk|wv mat-vec of d %d is not a 4-wave ring of depth 8 / 10 / 4 (or LLAMAHIP_NO_QKV_ATTN is set): no instance of k_qkv_attn", d);
+        return 0;
+    }
+    for (int i = 0; out && i < 5; i++) out[i] = o[i];
+    return 1;
+}
+
+// n_steps decode steps of one layer's attention through ONE of the hand-off kernels, on hand-off buffers that live across the steps: see llamahip.h
+int llamahip_op_dec_attention(const float *qkv, int32_t n_steps, const int32_t *n_past, const int32_t *layer, const int32_t *bump_epoch, uint32_t epoch0,
+                              int32_t d, int32_t H, int32_t n_ctx, float *Kc, float *Vc, int32_t n_threads, int32_t path, const int32_t *force,
+                              float *merged, void *wo_operand, uint32_t *fault, int64_t *plan, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_dec_attention";
+    if (!qkv || !n_past || !layer || !bump_epoch || !Kc || !Vc || !merged || !fault) { set_err(err, err_cap, "%s: null operand (qkv, n_past, layer, bump_epoch, Kc, Vc, merged, fault)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (n_steps < 1 || n_steps > 64) { set_err(err, err_cap, "%s: n_steps %d outside 1 .. 64", fn, n_steps); return LLAMAHIP_ERR_PREDICT; }
+    if (path < LLAMAHIP_DEC_ATTN_X || path > LLAMAHIP_DEC_ATTN_DMA) { set_err(err, err_cap, "%s: unknown path %d (X, STREAM, DMA)", fn, path); return LLAMAHIP_ERR_PREDICT; }
+    if (d < 1 || H < 1 || d % H != 0 || d % 32 != 0) { set_err(err, err_cap, "%s: d %d must be a multiple of H %d and of 32", fn, d, H); return LLAMAHIP_ERR_PREDICT; }
+    const int dh = d / H, nth = n_threads;
+    DecAttnForce f;
+    const DecAttnPlan p = dec_attn_op_plan(d, H, n_ctx, nth, path, force, f);
+    if (p.kernel < 0) { set_err(err, err_cap, "%s: path %d refused for d %d, H %d, n_ctx %d, n_threads %d: %s", fn, path, d, H, n_ctx, nth, p.why); return LLAMAHIP_ERR_PREDICT; }
+    const bool tags = path != LLAMAHIP_DEC_ATTN_X;
+    bool used[TAG_MAX_LAYERS] = { false };      // layers whose tag (epoch, layer + 1) this epoch has spent
+    for (int i = 0; i < n_steps; i++) {
+        if (n_past[i] < 0 || n_past[i] >= n_ctx) { set_err(err, err_cap, "%s: step %d: n_past %d outside [0, n_ctx = %d)", fn, i, n_past[i], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        if (layer[i] < 0 || layer[i] >= TAG_MAX_LAYERS) { set_err(err, err_cap, "%s: step %d: layer %d outside 0 .. %d", fn, i, layer[i], TAG_MAX_LAYERS - 1); return LLAMAHIP_ERR_PREDICT; }
+        if (bump_epoch[i]) std::fill(used, used + TAG_MAX_LAYERS, false);
+        if (tags && p.split > 1 && used[layer[i]]) {
+            set_err(err, err_cap, "%s: step %d: layer %d again under one epoch: a forward pass spends each tag once (bump_epoch)", fn, i, layer[i]); return LLAMAHIP_ERR_PREDICT;
+        }
+        used[layer[i]] = true;
+    }
+    if (plan) dec_attn_plan_out(p, plan);
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const int Kp = (d + 255) / 256 * 256;
+    const size_t cache_b = (size_t) n_ctx * d * 4, qaA_b = (size_t) Kp, qad_b = (size_t) (Kp / 32) * 4, sc_b = (size_t) H * n_ctx * 4;
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    std::vector<int32_t> hs((size_t) n_steps * 2, 0);
+    for (int i = 0; i < n_steps; i++) hs[2 * i] = n_past[i];
+    Scratch s;
+    hipStream_t st = s.stream();
+    // the placement every hand-off here relies on, asked as a model load asks (H x (column blocks + score slices) workgroups; head counts
+    // that are no multiple of 8 -- no model handle splits those -- ask for the 1-D rule over as many workgroups)
+    const int Y = dh / 32 + (n_ctx + 31) / 32;
+    if (s.ok() && !(H % 8 == 0 ? xcd_selftest(H, Y, st) : xcd_selftest(8, (H * Y + 7) / 8, st))) {
+        set_err(err, err_cap, "%s: the hand-off kernels need the workgroups of a head on one XCD; this device does not place them so", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    float *d_m = s.alloc<float>((size_t) d), *d_qad = s.alloc<float>(qad_b / 4), *d_sc = s.alloc<float>(sc_b / 4);
+    uint32_t *d_qaA = s.alloc<uint32_t>(qaA_b / 4);
+    // the op's own workspace, every byte NaN (0xFF): a read of something the launch did not write shows in the result
+    s.fill(d_sc, 0xFF, sc_b); s.fill(d_qaA, 0xFF, qaA_b); s.fill(d_qad, 0xFF, qad_b);
+    float *d_qkv = s.alloc((size_t) n_steps * 3 * d, qkv), *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    uint16_t *d_ts = s.alloc(ts.size(), ts.data()), *d_te = s.alloc(te.size(), te.data());
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    int32_t *d_state = s.alloc(hs.size(), hs.data());
+    // the hand-off state, sized and zeroed ONCE as a model load does and never cleared between the steps: the heads' counters, the tagged
+    // partial sums, the epoch word ([0]) and the fault word ([4])
+    uint32_t *d_sync = s.alloc<uint32_t>((size_t) H * 32), *d_words = s.alloc<uint32_t>(8);
+    uint64_t *d_xpart = s.alloc<uint64_t>((size_t) d * 32);
+    s.fill(d_sync, 0, (size_t) H * 32 * 4); s.fill(d_xpart, 0, (size_t) d * 32 * 8); s.fill(d_words, 0, 32);
+    s.upload(d_words, &epoch0, 4);
+    if (s.ok()) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    std::vector<uint32_t> qa(qaA_b / 4);
+    std::vector<float> qd(qad_b / 4);
+    for (int i = 0; i < n_steps && s.ok(); i++) {
+        fault[i] = 0xFFFFFFFFu;
+        s.fill(d_m, 0xFF, (size_t) d * 4);
+        if (bump_epoch[i]) s.check(launch_bump_epoch(d_words, st));
+        if (s.ok()) s.check(launch_dec_attn(d_qkv + (size_t) i * 3 * d, d, H, n_ctx, nth, d_tab, d_K, d_V, d_sc, nullptr, d_m, d_qaA, d_qad, d_te, d_state + 2 * i, st,
+                                            tags ? nullptr : d_sync, d_words + 4, tags, tags ? d_xpart : nullptr, d_words, layer[i], &f));
+        s.download(merged + (size_t) i * d, d_m, (size_t) d * 4);
+        s.download(fault + i, d_words + 4, 4);
+        if (wo_operand) { s.download(qa.data(), d_qaA, qaA_b); s.download(qd.data(), d_qad, qad_b); }
+        s.sync();
+        if (!s.ok()) break;
+        if (wo_operand) qa_to_q4_0_blocks(qa.data(), qd.data(), 1, d, (uint8_t *) wo_operand + (size_t) i * (d / 32) * 20);
+        if (fault[i] != 0u) {      // a hand-off timed out: the results of that launch are invalid and nothing more is launched
+            set_err(err, err_cap, "%s: step %d (n_past %d, layer %d): the fault word is %#x: a hand-off between workgroups timed out", fn, i, n_past[i], layer[i], fault[i]);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
+}
+
+// n_steps decode steps of the fused wq|wk|wv + attention launch (k_qkv_attn) on hand-off buffers that live across the steps: see llamahip.h
+int llamahip_op_qkv_attn(const void *w_q4_0, const float *norm_w, int32_t d, int32_t H, int32_t n_ctx, float *Kc, float *Vc, int32_t n_threads,
+                         int32_t n_steps, const float *x, const double *part_in, const int32_t *n_part, int32_t part_stride,
+                         const int32_t *n_past, const int32_t *layer, const int32_t *bump_epoch, uint32_t epoch0, int32_t tagged_in,
+                         float *merged, void *wo_operand, uint32_t *fault, int64_t *plans, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_qkv_attn";
+    if (tagged_in) { set_err(err, err_cap, "%s: PREP_NORM_TAG waits on another pipeline stage's mailbox: the op launches the NORM / NORMP prologues only", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!w_q4_0 || !norm_w || !Kc || !Vc || !x || !n_part || !n_past || !layer || !bump_epoch || !merged || !fault) {
+        set_err(err, err_cap, "%s: null operand (w, norm_w, Kc, Vc, x, n_part, n_past, layer, bump_epoch, merged, fault)", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (n_steps < 1 || n_steps > 64) { set_err(err, err_cap, "%s: n_steps %d outside 1 .. 64", fn, n_steps); return LLAMAHIP_ERR_PREDICT; }
+    if (n_ctx < 1 || n_ctx > 4096) { set_err(err, err_cap, "%s: n_ctx %d outside 1 .. 4096", fn, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (d < 1 || d % 256 != 0) { set_err(err, err_cap, "%s: d %d must be a positive multiple of 256", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    const int nth = n_threads;
+    if (nth < 1) { set_err(err, err_cap, "%s: n_threads %d must be >= 1", fn, nth); return LLAMAHIP_ERR_PREDICT; }
+    QMat q;
+    q.set_shape(3 * d, d);
+    char why[200] = "";
+    if (!qkv_attn_shape_ok(d, H, nth, q.M, q.K, q.ngroups, q.gmapF8, why, sizeof(why))) { set_err(err, err_cap, "%s: k_qkv_attn does not take d %d, H %d, n_threads %d: %s", fn, d, H, nth, why); return LLAMAHIP_ERR_PREDICT; }
+    if (!qkv_attn_applies(q, d, H, nth)) {
+        set_err(err, err_cap, "%s: k_qkv_attn has no instance for d %d: its mat-vec role must be a 4-wave ring of (depth, granules) (8, 1), (10, 2) or (4, 2) (llamahip_debug_qkv_attn_plan)", fn, d);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    bool used[TAG_MAX_LAYERS] = { false };      // layers whose tag (epoch, layer + 1) this epoch has spent
+    int max_part = 0;
+    for (int i = 0; i < n_steps; i++) {
+        if (n_past[i] < 0 || n_past[i] >= n_ctx) { set_err(err, err_cap, "%s: step %d: n_past %d outside [0, n_ctx = %d)", fn, i, n_past[i], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        if (layer[i] < 0 || layer[i] >= TAG_MAX_LAYERS) { set_err(err, err_cap, "%s: step %d: layer %d outside 0 .. %d", fn, i, layer[i], TAG_MAX_LAYERS - 1); return LLAMAHIP_ERR_PREDICT; }
+        if (n_part[i] < 0 || n_part[i] > NORM_PART_MAX || (n_part[i] > 0 && (!part_in || part_stride < n_part[i]))) {
+            set_err(err, err_cap, "%s: step %d: n_part %d outside 0 .. %d (NORM_PART_MAX), or part_in missing / part_stride %d too small", fn, i, n_part[i], NORM_PART_MAX, part_stride); return LLAMAHIP_ERR_PREDICT;
+        }
+        if (bump_epoch[i]) std::fill(used, used + TAG_MAX_LAYERS, false);
+        if (used[layer[i]]) { set_err(err, err_cap, "%s: step %d: layer %d again under one epoch: a forward pass spends each tag once (bump_epoch)", fn, i, layer[i]); return LLAMAHIP_ERR_PREDICT; }
+        used[layer[i]] = true;
+        max_part = std::max(max_part, n_part[i]);
+        long lp[5];
+        NormPart np;
+        if (n_part[i] > 0) { np.in = part_in + (size_t) i * part_stride * 2; np.n_in = n_part[i]; }
+        if (!qkv_attn_launch_query(q, np, d, H, n_ctx, nth, lp)) { set_err(err, err_cap, "%s: step %d: no launch", fn, i); return LLAMAHIP_ERR_PREDICT; }
+        if ((size_t) lp[4] > GEMV_LDS_CAP) { set_err(err, err_cap, "%s: %ld bytes of LDS, the kernels' cap is %zu", fn, lp[4], GEMV_LDS_CAP); return LLAMAHIP_ERR_PREDICT; }
+        if (plans) for (int k = 0; k < 5; k++) plans[(size_t) i * 5 + k] = lp[k];
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const int dh = d / H, Kp = q.Kp();
+    const size_t nb = (size_t) d / 32, cache_b = (size_t) n_ctx * d * 4, qaA_b = (size_t) Kp, qad_b = (size_t) (Kp / 32) * 4;
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    std::vector<int32_t> hs((size_t) n_steps * 2, 0);
+    for (int i = 0; i < n_steps; i++) hs[2 * i] = n_past[i];
+    Scratch s;
+    hipStream_t st = s.stream();
+    if (s.ok() && !xcd_selftest(H, dh / 32 + (n_ctx + 31) / 32, st)) {
+        set_err(err, err_cap, "%s: k_qkv_attn needs the workgroups of a head on one XCD; this device does not place them so", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    uint8_t *d_w = s.alloc((size_t) q.M * nb * 20, (const uint8_t *) w_q4_0);
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    float *d_nw = s.alloc((size_t) d, norm_w), *d_x = s.alloc((size_t) n_steps * d, x);
+    double *d_pi = max_part > 0 ? s.alloc((size_t) n_steps * part_stride * 2, part_in) : nullptr;
+    float *d_m = s.alloc<float>((size_t) d), *d_qad = s.alloc<float>(qad_b / 4);
+    uint32_t *d_qaA = s.alloc<uint32_t>(qaA_b / 4);
+    s.fill(d_qaA, 0xFF, qaA_b); s.fill(d_qad, 0xFF, qad_b);
+    float *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    uint16_t *d_ts = s.alloc(ts.size(), ts.data()), *d_te = s.alloc(te.size(), te.data());
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    int32_t *d_state = s.alloc(hs.size(), hs.data());
+    // the hand-off state, sized and zeroed ONCE as a model load does and never cleared between the steps: the tagged q|k|v row, the tagged
+    // scores, the epoch word ([0]) and the fault word ([4])
+    uint64_t *d_qkv2 = s.alloc<uint64_t>((size_t) 3 * d), *d_sc2 = s.alloc<uint64_t>((size_t) H * n_ctx);
+    uint32_t *d_words = s.alloc<uint32_t>(8);
+    s.fill(d_qkv2, 0, (size_t) 3 * d * 8); s.fill(d_sc2, 0, (size_t) H * n_ctx * 8); s.fill(d_words, 0, 32);
+    s.upload(d_words, &epoch0, 4);
+    if (s.ok()) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    if (s.ok()) s.check(launch_repack(d_w, q.tiles, q.M, q.K, 0, 0, st));
+    std::vector<uint32_t> qa(qaA_b / 4);
+    std::vector<float> qd(qad_b / 4);
+    for (int i = 0; i < n_steps && s.ok(); i++) {
+        fault[i] = 0xFFFFFFFFu;
+        s.fill(d_m, 0xFF, (size_t) d * 4);
+        if (bump_epoch[i]) s.check(launch_bump_epoch(d_words, st));
+        NormPart np;
+        if (n_part[i] > 0) { np.in = d_pi + (size_t) i * part_stride * 2; np.n_in = n_part[i]; }
+        if (s.ok()) s.check(launch_qkv_attn(q, d_x + (size_t) i * d, d_nw, np, d_qkv2, d_sc2, d_words, layer[i], d, H, n_ctx, nth, d_tab, d_K, d_V, d_m, d_qaA, d_qad,
+                                            d_ts, d_te, d_state + 2 * i, d_words + 4, st, nullptr));
+        s.download(merged + (size_t) i * d, d_m, (size_t) d * 4);
+        s.download(fault + i, d_words + 4, 4);
+        if (wo_operand) { s.download(qa.data(), d_qaA, qaA_b); s.download(qd.data(), d_qad, qad_b); }
+        s.sync();
+        if (!s.ok()) break;
+        if (wo_operand) qa_to_q4_0_blocks(qa.data(), qd.data(), 1, d, (uint8_t *) wo_operand + (size_t) i * (d / 32) * 20);
+        if (fault[i] != 0u) {      // a hand-off timed out: the results of that launch are invalid and nothing more is launched
+            set_err(err, err_cap, "%s: step %d (n_past %d, layer %d): the fault word is %#x: a hand-off between workgroups timed out", fn, i, n_past[i], layer[i], fault[i]);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    s.sync();
+    return s.ok() ? LLAMAHIP_OK : s.fail(fn, err, err_cap);
+}
+
 // the attention of llamahip_eval_multi's pass on caller-supplied rows, caches and row table (per-op tests of rows_attn.hip): see llamahip.h
 int llamahip_op_attention_rows(const float *qkv, int32_t R, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
                                const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, int32_t n_threads,

@@ -22,6 +22,7 @@
 #include "../model_file.h"
 #include "../q41_plan.h"
 #include "../set_plan.h"
+#include "../dec_attn_plan.h"
 #include "../sched.h"
 
 struct llamahip_model { lh::ModelFile file; lh::SchedDev *sched = nullptr; };
@@ -1327,6 +1328,57 @@ int main(int argc, char **argv) {
         EXPECT(!set_applies(shape(22016, 4096, true), 4, SET_EPI_ROPE_KV) && !set_applies(shape(4096, 4096, false), 4, 4) && !set_applies(shape(64, 147456, false), 4, SET_EPI_STORE));
         EXPECT(plans > 0 && admitted > 0 && refused > 0);
         printf("host_sanitize: few-row mat-mul host half: %d plans, %d forced plans admitted, %d refused\n", plans, admitted, refused);
+    }
+    {   // the decode attention's host half (dec_attn_plan.cpp): the plan of every LLaMA head layout and of small ones at every thread count,
+        // context and set of buffers; every forced {split, stage_rows, ns, dma} admitted as asked or refused with a reason; the fused launch's geometry
+        using namespace lh;
+        const int shapes[][2] = { { 4096, 32 }, { 5120, 40 }, { 6656, 52 }, { 8192, 64 }, { 256, 8 }, { 1024, 8 }, { 2048, 8 }, { 256, 2 }, { 96, 3 } };
+        int plans = 0, admitted = 0, refused = 0;
+        for (auto &sh : shapes) {
+            const int d = sh[0], H = sh[1], dh = d / H;
+            for (int n_ctx : { 1, 64, 100, 1001, 1024, 1025, 2048, 4096, 4097 })
+                for (int nth = 1; nth <= 64; nth++)
+                    for (int mode = 0; mode < 8; mode++) {
+                        const bool long_ctx = mode & 1, sync = mode & 2, xpart = mode & 4;
+                        const DecAttnPlan p = dec_attn_plan(d, H, n_ctx, nth, long_ctx, sync, xpart);
+                        EXPECT(p.kernel >= DEC_ATTN_PV_BLK && p.kernel <= DEC_ATTN_PV_DMA && p.why[0] == 0 && p.gx >= 1 && p.gy >= 1 && p.lds > 0);
+                        EXPECT(p.threads >= 64 && p.threads <= 1024 && p.threads % 64 == 0 && p.split >= 1 && p.cpw >= 1 && (p.split - 1) * p.cpw < nth && p.split * p.cpw >= nth);
+                        if (p.kernel == DEC_ATTN_PV_STREAM) EXPECT(p.SR >= 1 && p.cpw * p.SR * 8 <= PV_STREAM_QUADS && p.lds <= DEC_ATTN_LDS_CAP && p.gx == H * (dh / 32) * p.split);
+                        if (p.kernel == DEC_ATTN_PV_DMA) EXPECT(xpart && dh == 128 && p.cpw <= PV_DMA_CPW_MAX && p.NS >= 2 && p.lds <= DEC_ATTN_LDS_CAP && p.gx == H * p.split);
+                        if (p.kernel == DEC_ATTN_X) EXPECT(sync && n_ctx <= DEC_ATTN_X_CTX_MAX && nth <= 8 && p.lds <= DEC_ATTN_LDS_CAP);
+                        EXPECT((p.kernel >= DEC_ATTN_PV_STREAM) == (long_ctx && pv_stream_applies(dh, n_ctx, nth)));
+                        plans++;
+                        if ((nth > 9 && nth != 24 && nth != 32 && nth != 33) || n_ctx == 1 || n_ctx == 64 || n_ctx == 1001) continue;
+                        for (int split : { -1, 0, 1, 2, 3, 4, 8, 16, 32, 33 })
+                            for (int sr : { -1, 0, 1, 3, 171, 512, 513 })
+                                for (int ns : { -1, 0, 1, 2, 3, 37, 256, 257 })
+                                    for (int dma = -2; dma <= 2; dma++) {
+                                        DecAttnForce f;
+                                        f.split = split; f.stage_rows = sr; f.ns = ns; f.dma = dma; f.strict = true;
+                                        const DecAttnPlan q = dec_attn_plan(d, H, n_ctx, nth, long_ctx, sync, xpart, &f);
+                                        if (q.kernel < 0) { EXPECT(q.why[0] != 0 && strlen(q.why) < sizeof(q.why)); refused++; continue; }
+                                        EXPECT(q.why[0] == 0 && q.lds <= DEC_ATTN_LDS_CAP && (split == 0 || q.split == split) && (sr == 0 || q.SR == sr) && (ns == 0 || q.NS == ns));
+                                        EXPECT((dma != 1 || q.kernel == DEC_ATTN_PV_DMA) && (dma != 0 || q.kernel != DEC_ATTN_PV_DMA) && pv_split_valid(nth, q.split));
+                                        EXPECT(q.kernel != DEC_ATTN_PV_DMA || q.cpw <= PV_DMA_CPW_MAX);
+                                        admitted++;
+                                    }
+                    }
+            char why[120] = "", why1[1] = { 'x' };
+            for (int nth : { 1, 8, 9 }) {
+                const bool ok = qkv_attn_shape_ok(d, H, nth, 3 * d, d, 3 * d / 8, 0, why, sizeof(why));
+                EXPECT(ok == (H % 8 == 0 && dh % 32 == 0 && dh <= 256 && nth <= 8) && (ok || why[0] != 0));
+                EXPECT(qkv_attn_shape_ok(d, H, nth, 3 * d, d, 3 * d / 8, 0, why1, sizeof(why1)) == ok && qkv_attn_shape_ok(d, H, nth, 3 * d, d, 3 * d / 8, 0) == ok);
+                EXPECT(!qkv_attn_shape_ok(d, H, nth, 3 * d, d, 3 * d / 8, d / 8) && !qkv_attn_shape_ok(d, H, nth, d, d, d / 8, 0));
+            }
+            const QkvAttnGeom g = qkv_attn_geom(3 * d / 32, 1000, d, H, 2048, 8);
+            EXPECT(g.grid == 3 * d / 32 + H * (64 + dh / 32) && g.lds == 32 * 8 + (2048 + 8 * 32 + 16) * 4);
+        }
+        EXPECT(qkv_attn_instance(4, true, 8, 1) && qkv_attn_instance(4, true, 10, 2) && qkv_attn_instance(4, true, 4, 2) && !qkv_attn_instance(4, false, 8, 1) &&
+               !qkv_attn_instance(2, true, 8, 1) && !qkv_attn_instance(4, true, 8, 2) && !qkv_attn_instance(4, true, 16, 1));
+        EXPECT(dec_attn_plan(0, 1, 64, 1, false, false, false).kernel < 0 && dec_attn_plan(64, 0, 64, 1, false, false, false).kernel < 0 &&
+               dec_attn_plan(64, 1, 0, 1, false, false, false).kernel < 0 && dec_attn_plan(64, 1, 64, 0, false, false, false).kernel < 0);
+        EXPECT(plans > 0 && admitted > 0 && refused > 0);
+        printf("host_sanitize: decode attention host half: %d plans, %d forced plans admitted, %d refused\n", plans, admitted, refused);
     }
     {   // the owner of device memory (dev_owner.h) on the stub allocator: groups are all-or-nothing at every failing call, release, destruction by kind
         using lh::DevOwner;
