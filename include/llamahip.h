@@ -619,6 +619,57 @@ int llamahip_score_choices(llamahip_model *m, int32_t n_threads, const int32_t *
                            double *logprob_sum /* [n_choices] */, int32_t *n_greedy /* [n_choices], may be NULL */,
                            double *logprob_rows /* concatenated, n_ending[i] each; may be NULL */, char *err, size_t err_cap);
 
+/* ---- text embeddings: pooled final-norm rows, several texts per weight pass --------------------------------------------------------------
+ * A text's embedding is the final-norm hidden state the lm head would have read (.mm:695-700: inpL after ggml_norm x model.norm), of the text's
+ * last row (LLAMAHIP_POOL_LAST: what llama.cpp's --embedding of the reference's era returns) or the mean over the text's rows
+ * (LLAMAHIP_POOL_MEAN).  An embedding pass is the eval of the same arguments with the lm head replaced by three small launches on the last
+ * stage's stream (csrc/pool.hip): the final norm stored as plain fp32 rows (k_norm_rows_f32: the norm's arithmetic of every path here, mean and
+ * second moment in double in the two-pass form, no fp16 rounding, no permutation), the pooling (k_pool_rows: LAST copies the segment's last
+ * row -- only the last rows are gathered and normed; MEAN adds (double) y[j][c] over the segment's rows j in ascending order from 0.0 and
+ * stores (float) (acc / (double) n_rows)), and with normalize = 1 the L2 normalisation (k_l2_rows: lane l of 64 sums (double) o[c] * (double) o[c]
+ * over c = l, l + 64, ... ascending, the 64 partials are folded by the xor butterfly 32, 16, 8, 4, 2, 1, out[c] = (float) ((double) o[c] /
+ * sqrt(ss)); ss == 0.0 leaves the zero vector).  No lm head runs (262 MB of the 7B's 4.1 GB), n_embd floats per text come back instead of
+ * n_vocab, and no logits are written: the logits buffer and the row map of llamahip_stage_logits stay as the last eval left them.
+ *
+ * llamahip_text_embedding -- one text on the current KV slot.  Contract: the call leaves the KV rows [n_past, n_past + n_tokens) of every layer
+ * that llamahip_eval_chunks(n_past, tokens, n_tokens, chunk_tokens) (chunk_tokens 0: llamahip_eval) leaves, bit for bit, and touches no other
+ * KV row; out = the n_embd floats.  MEAN pools the rows of this call only: rows below n_past are context, not text.  A one-token text is legal
+ * (it is evaluated as a one-row multi-row eval, not as a decode step: the decode step's final norm lives inside the lm head's launch).  The
+ * norm's sums are folded in the kernel's own order; equality with the reference's sequential sums is BY TEST (tests/test_gpu_pool_op.py,
+ * tests/test_gpu_text_embedding.py), on rows whose result no order can change.
+ * llamahip_text_embedding_multi -- text i at n_past[i] on KV slot slots[i], all texts in llamahip_eval_multi's ONE pass; out [n_seqs][n_embd].
+ * Contract: per text what llamahip_set_seq(slots[i]) + llamahip_text_embedding of its arguments returns, the KV rows llamahip_eval_multi of
+ * the same arguments leaves, bit for bit; no other KV row is touched and the current slot is left alone.
+ * Handles and fall-backs: llamahip_eval_multi's -- plain and in-process pipeline handles take the one pass under its loop rule; f16 / f32 /
+ * Q4_1 files, LLAMAHIP_FLAG_FAST_PREFILL handles, n_seqs == 1 and head sizes the table kernels refuse run llamahip_text_embedding slot by
+ * slot, restore the current slot and report the eval count in stats->n_passes (the one pass: 1).
+ * Refused before any device work, the message naming the limit and the function, the handle last: what llamahip_eval_multi refuses of the same
+ * arguments, pool outside {0, 1}, normalize outside {0, 1}, a null out, HOST_ONLY and stage handles, and a handle with a live scheduler when
+ * a named slot (llamahip_text_embedding: the current slot) is below its max_active.
+ * llamahip_op_pool_rows -- the three launches on caller-supplied rows x[R][d] (parity tests): also refuses R outside 1 ..
+ * LLAMAHIP_EVAL_MULTI_MAX_ROWS, d < 32 or d % 32 != 0, n_segs outside 1 .. 16 and a seg_begin that does not rise strictly from 0 to R.
+ * (llamahip_op_embed is the token-embedding GATHER at the bottom of the graph; these are the TEXT's embedding at its top.)
+ * Numbers (7B, one MI355X, n_past 64, normalize on, ms per call, median of five fresh processes; tools/embed_probe.py,
+ * profiles/embed_probe_7b.json):
+ *   segments x rows (MEAN)        4 x 10   16 x 10   16 x 32   4 x 128
+ *   one pass                        7.90     20.53     42.92     37.28
+ *   llamahip_eval_multi + logits    7.88     20.52     42.96     37.43
+ *   per-slot loop                  12.41     49.83    111.80     58.81
+ *   LAST measured the same to within the spread.  Against llamahip_eval_multi with logits the difference is inside the spread: its lm head
+ *   already runs over the segments' last rows only.  No measured shape is slower than the loop, so the loop rule stays llamahip_eval_multi's.
+ *   DESIGN.md 12.28. */
+#define LLAMAHIP_POOL_LAST 0
+#define LLAMAHIP_POOL_MEAN 1
+#define LLAMAHIP_POOL_MAX_SEGS 16
+int llamahip_text_embedding(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                            int32_t chunk_tokens /* 0 = one eval */, int32_t pool, int32_t normalize, float *out /* n_embd */, char *err, size_t err_cap);
+int llamahip_text_embedding_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past,
+                                  const int32_t *tokens /* concatenated, n_tokens[i] each */, const int32_t *n_tokens, int32_t chunk_tokens,
+                                  int32_t pool, int32_t normalize, float *out /* [n_seqs][n_embd] */,
+                                  llamahip_eval_multi_stats *stats /* may be NULL */, char *err, size_t err_cap);
+int llamahip_op_pool_rows(const float *x /* [R][d] */, int32_t R, int32_t d, const float *norm_w /* [d] */, const int32_t *seg_begin /* n_segs + 1 */,
+                          int32_t n_segs, int32_t pool, int32_t normalize, float *out /* [n_segs][d] */, char *err, size_t err_cap);
+
 /* ---- request scheduler: prompts admitted into a running multi-sequence decode --------------------------------------------------------
  * The *_multi loops above take their slots' contexts as given and run every sequence for the same n_steps; llamahip_eval_multi evaluates
  * several prompts in one pass.  The scheduler is the loop that joins them: requests wait in a queue, take a free KV slot, have their prompt

@@ -24,6 +24,8 @@ from .binding import (  # noqa: F401
     LIB_PATH,
     LlamaHipError,
     Model,
+    POOL_LAST,
+    POOL_MEAN,
     SCORE_CHOICES_MAX,
     Sampler,
     Scheduler,
@@ -53,6 +55,7 @@ from .binding import (  # noqa: F401
     op_kv_shift,
     op_logprob,
     op_mul_mat_dense,
+    op_pool_rows,
     op_mul_mat_q4_1,
     op_mul_mat_q4_0,
     op_prep,

@@ -22,6 +22,8 @@ CTX_SHIFT = 4           # LLAMAHIP_CTX_SHIFT: ... the in-place shift (NOT the re
 KV_SHIFT_MAX = 16       # LLAMAHIP_KV_SHIFT_MAX: the shifts of one Model.kv_shift_rows / op_kv_shift call
 KV_SHIFT_ROWS_IN_FLIGHT = 8   # LLAMAHIP_KV_SHIFT_ROWS_IN_FLIGHT: rows a thread of k_kv_shift_rows loads before it stores them
 SCORE_CHOICES_MAX = 16  # LLAMAHIP_SCORE_CHOICES_MAX: the endings of one Model.score_choices call
+POOL_LAST, POOL_MEAN = 0, 1  # LLAMAHIP_POOL_*: how Model.text_embedding pools a text's final-norm rows
+_POOLS = {"last": POOL_LAST, "mean": POOL_MEAN}
 DUMP_NAMES = [
     "layer_in", "attn_normed", "q", "k", "v", "q_roped", "kq_softmax", "kqv", "kqv_merged",
     "wo_out", "ffn_in", "ffn_normed", "w3_out", "w1_out", "silu_mul", "w2_out", "layer_out",
@@ -244,6 +246,9 @@ def lib() -> C.CDLL:
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_text_embedding.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, cp, sz]
+    L.llamahip_text_embedding_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
+    L.llamahip_op_pool_rows.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, cp, sz]
     L.llamahip_op_prep.argtypes = [i32, i32, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, i32, vp, vp, i32, vp, vp, cp, sz]
     L.llamahip_debug_qa_to_blocks.argtypes = [vp, vp, i32, i32, vp]
     L.llamahip_op_embed.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, cp, sz]
@@ -705,6 +710,37 @@ class Model:
         _check(rc, err)
         logits = logits[:slots.size]
         return (logits, {k: getattr(st, k) for k, _ in _EvalMultiStats._fields_ if k != "struct_size"}) if want_stats else logits
+
+    def text_embedding(self, tokens, n_past: int = 0, n_threads: int = 8, chunk_tokens: int = 0, pool="last", normalize: bool = False) -> np.ndarray:
+        """llamahip_text_embedding: the text's embedding [n_embd] -- the final-norm hidden state of its last row (pool "last") or the mean over its
+        rows (pool "mean"), optionally divided by its L2 length; the eval of llamahip_eval_chunks without the lm head, no logits written."""
+        toks = np.ascontiguousarray(tokens, np.int32).ravel()
+        out = np.empty(self.n_embd, np.float32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_text_embedding(self._h, n_threads, int(n_past), _ptr(toks if toks.size else np.zeros(1, np.int32)), toks.size, int(chunk_tokens),
+                                           _pool_id(pool), int(normalize), _ptr(out), err, len(err))
+        _check(rc, err)
+        return out
+
+    def text_embedding_multi(self, slots, n_past, token_lists, chunk_tokens: int = 0, n_threads: int = 8, pool="last", normalize: bool = False,
+                             want_stats: bool = False):
+        """llamahip_text_embedding_multi: token_lists[i] evaluated at n_past[i] on KV slot slots[i], all in one weight pass; returns the texts'
+        embeddings [n_seqs][n_embd] (with want_stats: (embeddings, the llamahip_eval_multi_stats fields as a dict))."""
+        slots = np.ascontiguousarray(slots, np.int32).ravel()
+        npast = np.ascontiguousarray(n_past, np.int32).ravel()
+        toks = [np.ascontiguousarray(t, np.int32).ravel() for t in token_lists]
+        if not (slots.size == npast.size == len(toks)):
+            raise ValueError(f"text_embedding_multi: {slots.size} slots, {npast.size} n_past, {len(toks)} token lists")
+        nt = np.array([t.size for t in toks], np.int32) if toks else np.zeros(1, np.int32)
+        flat = np.ascontiguousarray(np.concatenate(toks), np.int32) if toks and int(nt.sum()) else np.zeros(1, np.int32)
+        out = np.empty((max(slots.size, 1), self.n_embd), np.float32)
+        st = _EvalMultiStats(C.sizeof(_EvalMultiStats))
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_text_embedding_multi(self._h, n_threads, slots.size, _ptr(slots), _ptr(npast), _ptr(flat), _ptr(nt), int(chunk_tokens),
+                                                 _pool_id(pool), int(normalize), _ptr(out), C.byref(st), err, len(err))
+        _check(rc, err)
+        out = out[:slots.size]
+        return (out, {k: getattr(st, k) for k, _ in _EvalMultiStats._fields_ if k != "struct_size"}) if want_stats else out
 
     def eval_logprobs_multi(self, slots, n_past, token_lists, targets=None, chunk_tokens: int = 0, n_threads: int = 8, want_stats: bool = False) -> dict:
         """llamahip_eval_logprobs_multi: token_lists[i] evaluated at n_past[i] on KV slot slots[i] and scored, all in one weight pass.  targets:
@@ -1297,6 +1333,27 @@ def op_logprob(logits2d, targets=None):
     rc = lib().llamahip_op_logprob(_ptr(logits2d), R, V, _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk), err, len(err))
     _check(rc, err)
     return lp, am, rk
+
+
+def _pool_id(pool) -> int:
+    return _POOLS[pool] if isinstance(pool, str) else int(pool)
+
+
+def op_pool_rows(x, norm_w, seg_begin, pool="last", normalize: bool = False, out=None) -> np.ndarray:
+    """The tail of an embedding pass (k_norm_rows_f32, k_pool_rows, the L2 normalisation) on host rows x f32 [R, d]: the final norm with norm_w,
+    rows [seg_begin[s], seg_begin[s + 1]) pooled per segment; returns [n_segs, d].  out: a caller's float32 buffer of at least n_segs * d
+    floats, written in place (what lies behind the result keeps its bits)."""
+    x = np.ascontiguousarray(x, np.float32)
+    norm_w = np.ascontiguousarray(norm_w, np.float32)
+    seg = np.ascontiguousarray(seg_begin, np.int32).ravel()
+    R, d = x.shape
+    n_segs = seg.size - 1
+    if out is None:
+        out = np.empty(max(n_segs, 1) * d, np.float32)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_pool_rows(_ptr(x), R, d, _ptr(norm_w), _ptr(seg), n_segs, _pool_id(pool), int(normalize), _ptr(out), err, len(err))
+    _check(rc, err)
+    return out.ravel()[:max(n_segs, 0) * d].reshape(max(n_segs, 0), d)
 
 
 def lookup_draft(history, corpus=None, draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0) -> np.ndarray:

@@ -1,7 +1,8 @@
 // eval_multi.cpp -- the host half of llamahip_eval_multi (include/llamahip.h): the row table of a pass over several KV slots
 // (llamahip_eval_multi_rows), what the entry point refuses of its arguments (eval_multi_check) and what llamahip_op_attention_rows refuses of a
 // caller's table (rows_table_check); and of llamahip_eval_logprobs_multi / llamahip_score_choices: their argument checks (score_multi_check,
-// score_choices_check), the scored rows of a pass (score_multi_rows) and the way their results go back to row order (score_scatter).
+// score_choices_check), the scored rows of a pass (score_multi_rows) and the way their results go back to row order (score_scatter); and what
+// llamahip_text_embedding[_multi] and llamahip_op_pool_rows refuse of theirs (embed_check, pool_rows_check).
 // Pure host code, no device, no handle: tools/host_sanitize runs it under ASan + UBSan.
 #include <stdint.h>
 #include <stdio.h>
@@ -120,6 +121,43 @@ int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const i
     for (int64_t r = 0; r < E; r++)
         if (endings[r] < 0 || endings[r] >= n_vocab) { snprintf(err, err_cap, "%s: ending token id %d at %lld out of range [0, %d)", fn, endings[r], (long long) r, n_vocab); return LLAMAHIP_ERR_PREDICT; }
     if (E > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: %lld ending rows in all, more than LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, (long long) E, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    return 0;
+}
+
+// what llamahip_text_embedding_multi (fn names it; llamahip_text_embedding: its one segment on the current slot) refuses of its arguments:
+// eval_multi_check's rules, pool / normalize outside {0, 1}, a null out, and a named slot that a live scheduler owns (sched_max_active: the
+// slots [0, max_active) of the handle's scheduler, 0 = none)
+int embed_check(const char *fn, int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t sched_max_active, int32_t n_seqs, const int32_t *slots,
+                const int32_t *n_past, const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, int32_t pool, int32_t normalize,
+                const float *out, char *err, size_t err_cap) {
+    const int rc = segments_check(fn, n_ctx, n_vocab, n_slots, n_seqs, slots, n_past, tokens, n_tokens, chunk_tokens, err, err_cap);
+    if (rc) return rc;
+    if (!err) err_cap = 0;
+    if (pool != LLAMAHIP_POOL_LAST && pool != LLAMAHIP_POOL_MEAN) { snprintf(err, err_cap, "%s: pool (%d) must be LLAMAHIP_POOL_LAST (0) or LLAMAHIP_POOL_MEAN (1)", fn, pool); return LLAMAHIP_ERR_PREDICT; }
+    if (normalize != 0 && normalize != 1) { snprintf(err, err_cap, "%s: normalize (%d) must be 0 or 1", fn, normalize); return LLAMAHIP_ERR_PREDICT; }
+    if (!out) { snprintf(err, err_cap, "%s: null out", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int32_t i = 0; i < n_seqs; i++)
+        if (slots[i] < sched_max_active) {
+            snprintf(err, err_cap, "%s: slot %d (slots[%d]) belongs to the handle's live scheduler, which owns KV slots 0 .. %d: name a slot from %d, or free it first", fn, slots[i], i, sched_max_active - 1, sched_max_active);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    return 0;
+}
+
+// what llamahip_op_pool_rows refuses of its arguments
+int pool_rows_check(const float *x, int32_t R, int32_t d, const float *norm_w, const int32_t *seg_begin, int32_t n_segs, int32_t pool, int32_t normalize,
+                    const float *out, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_pool_rows";
+    if (!err) err_cap = 0;
+    if (!x || !norm_w || !seg_begin || !out) { snprintf(err, err_cap, "%s: null x, norm_w, seg_begin or out", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (R < 1 || R > LLAMAHIP_EVAL_MULTI_MAX_ROWS) { snprintf(err, err_cap, "%s: R (%d) outside 1 .. LLAMAHIP_EVAL_MULTI_MAX_ROWS (%d)", fn, R, LLAMAHIP_EVAL_MULTI_MAX_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    if (d < 32 || d % 32 != 0) { snprintf(err, err_cap, "%s: d (%d) must be a multiple of 32, at least 32", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    if (n_segs < 1 || n_segs > LLAMAHIP_POOL_MAX_SEGS) { snprintf(err, err_cap, "%s: n_segs (%d) outside 1 .. LLAMAHIP_POOL_MAX_SEGS (%d)", fn, n_segs, LLAMAHIP_POOL_MAX_SEGS); return LLAMAHIP_ERR_PREDICT; }
+    if (pool != LLAMAHIP_POOL_LAST && pool != LLAMAHIP_POOL_MEAN) { snprintf(err, err_cap, "%s: pool (%d) must be LLAMAHIP_POOL_LAST (0) or LLAMAHIP_POOL_MEAN (1)", fn, pool); return LLAMAHIP_ERR_PREDICT; }
+    if (normalize != 0 && normalize != 1) { snprintf(err, err_cap, "%s: normalize (%d) must be 0 or 1", fn, normalize); return LLAMAHIP_ERR_PREDICT; }
+    if (seg_begin[0] != 0 || seg_begin[n_segs] != R) { snprintf(err, err_cap, "%s: seg_begin must run from 0 to R (%d): seg_begin[0] = %d, seg_begin[%d] = %d", fn, R, seg_begin[0], n_segs, seg_begin[n_segs]); return LLAMAHIP_ERR_PREDICT; }
+    for (int32_t s = 0; s < n_segs; s++)
+        if (seg_begin[s + 1] <= seg_begin[s]) { snprintf(err, err_cap, "%s: seg_begin must rise strictly: seg_begin[%d] = %d, seg_begin[%d] = %d", fn, s, seg_begin[s], s + 1, seg_begin[s + 1]); return LLAMAHIP_ERR_PREDICT; }
     return 0;
 }
 

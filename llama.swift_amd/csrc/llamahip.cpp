@@ -216,6 +216,11 @@ struct llamahip_model {
     bool output_copies_tried = false;    // ... and of `output`, for the scoring entry points' all-rows lm head (ensure_output_copies)
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
+    // a text's embedding (last stage; embed_ensure): out [embed_segs_cap][d] | seg_begin [embed_segs_cap + 1] | the fp32 norm rows y [embed_rows_cap][d],
+    // and the host copy seg_begin is uploaded from
+    char *d_embed = nullptr;
+    int embed_segs_cap = 0, embed_rows_cap = 0;
+    std::vector<int32_t> h_embed_seg;
     char *d_slide = nullptr;             // sampled verify step (last stage): 16 x TOPK_WS_BYTES of selection workspace | the id stream (SLIDE_IDS_BYTES) | 16 TopkOut (slide_ensure)
     VsetBlock *d_vset = nullptr;         // a verify step over a set: the step's descriptor (vset_step)
     int32_t *d_slide_set = nullptr;      // sampled verify step over a set (last stage, no pinned block): the id pool (SLIDE_SET_IDS) | row_off[16] | row_n_last[16]
@@ -572,6 +577,11 @@ struct Pass {
     bool want_all = false;              // logits for every token (debug, scoring) instead of only the last (.mm:724-725)
     bool score_rows = false;            // ... by the scoring entry points: the all-rows lm head takes `output`'s prompt copies
     int chunk = 0;                      // > 0: the rows are the evals of `chunk` tokens of llamahip_eval_chunks in one pass
+    // an embedding pass (llamahip_text_embedding): no lm head, no logits; in its place the final norm of rows embed_first .. N - 1 as fp32 rows
+    // into embed_y (null: nothing at all -- a chunk of a LAST-pooled text that is not its last)
+    bool embed = false;
+    float *embed_y = nullptr;
+    int embed_first = 0;
     int dump_layer = -1; DumpSink *sink = nullptr;      // per-layer dumps (llamahip_eval_debug): both or neither
     const int32_t *tokens;              // device: where the embedding kernel finds the N tokens
     int seq;                            // KV slot
@@ -645,7 +655,9 @@ int forward_dense(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
         HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
         HIP_TRY(prep_mm(L.dw2, EPI_RESID, PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, N, m->x, d, m->x1, d), LLAMAHIP_ERR_PREDICT);               // .mm:678-687
     }
-    if (m->last_stage) {
+    if (m->last_stage && p.embed) {
+        if (p.embed_y) HIP_TRY(launch_norm_rows_f32(m->x + (size_t) p.embed_first * d, m->norm_w, d, N - p.embed_first, p.embed_y, st), LLAMAHIP_ERR_PREDICT);
+    } else if (m->last_stage) {
         const size_t r0 = p.want_all ? 0 : N - 1;      // every row, or only the last
         HIP_TRY(prep_mm(m->doutput, EPI_STORE, PREP_NORM, m->x + r0 * d, m->norm_w, d, 0, d, N - (int) r0, m->logits + r0 * V, V, nullptr, 0), LLAMAHIP_ERR_PREDICT);
     }
@@ -865,7 +877,10 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
         }
     }
 
-    if (m->last_stage) {
+    if (m->last_stage && p.embed) {
+        // an embedding pass: the final norm as fp32 rows in place of the lm head (m->x is fp32 on every path)
+        if (p.embed_y) HIP_TRY(launch_norm_rows_f32(m->x + (size_t) p.embed_first * d, m->norm_w, d, N - p.embed_first, p.embed_y, st), LLAMAHIP_ERR_PREDICT);
+    } else if (m->last_stage) {
         // final norm + lm head (.mm:695-705).  The reference multiplies all N rows and keeps the
         // last (.mm:724-725); only the last row is computed here unless every row is requested.
         if (p.want_all) {
@@ -891,7 +906,7 @@ int forward(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
     const bool debug = p.dump_layer >= 0 && p.sink;
     if (m->dense && debug) { set_err(err, err_cap, "per-layer dumps are available for Q4_0 models only"); return LLAMAHIP_ERR_PREDICT; }
     if (m->dense) return forward_dense(m, p, err, err_cap);
-    if (p.N == 1 && !debug && !(m->flags & LLAMAHIP_FLAG_UNFUSED)) return forward_decode(m, p, err, err_cap);
+    if (p.N == 1 && !debug && !p.embed && !(m->flags & LLAMAHIP_FLAG_UNFUSED)) return forward_decode(m, p, err, err_cap);      // (the decode step's final norm lives inside its lm head)
     return forward_eval(m, p, err, err_cap);
 }
 
@@ -941,6 +956,10 @@ int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n
 void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk);
 int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
                         const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap);
+// ... and llamahip_text_embedding[_multi] of theirs
+int embed_check(const char *fn, int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t sched_max_active, int32_t n_seqs, const int32_t *slots,
+                const int32_t *n_past, const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, int32_t pool, int32_t normalize,
+                const float *out, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     if (!m->stages.empty()) return 0;
@@ -1324,8 +1343,10 @@ int llamahip_eval_topk(llamahip_model *m, int32_t n_threads, int32_t n_past, con
 
 // the launches of a stage eval, enqueued on m->stream without waiting (llamahip_eval_stage; the in-process pipeline walks its stages with it)
 // (want_all: the last stage computes the logits of every row, for k_row_logprob -- the scoring entry points)
+// (embed: an embedding pass -- Pass::embed with {embed_y, embed_first} = *embed on the last stage; the logits and their row map stay as they are)
+struct EmbedReq { float *y; int first; };
 static int eval_stage_enqueue(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, const void *hidden_in,
-                              int chunk, bool want_all, char *err, size_t err_cap) {
+                              int chunk, bool want_all, char *err, size_t err_cap, const EmbedReq *embed = nullptr) {
     int rc = check_eval_args(m, n_past, tokens, N, m && m->first_stage, err, err_cap);
     if (rc) return rc;
     if (!m->first_stage && !hidden_in) { set_err(err, err_cap, "stage [%d,%d) needs hidden_in", m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
@@ -1342,9 +1363,10 @@ static int eval_stage_enqueue(llamahip_model *m, int32_t n_threads, int32_t n_pa
     Pass pass(m);
     pass.n_threads = n_threads; pass.n_past = n_past; pass.N = N; pass.chunk = chunk; pass.hidden_in = (const float *) hidden_in;
     pass.want_all = pass.score_rows = all;
+    if (embed) { pass.embed = true; pass.embed_y = embed->y; pass.embed_first = embed->first; }
     if (N == 1) pass.attn_sched = attn_sched_at(m, n_past);
     rc = forward(m, pass, err, err_cap);
-    m->last_rows.clear();                                                // (m->logits rewritten: llamahip_stage_logits rows are this eval's rows again)
+    if (!(embed && m->last_stage)) m->last_rows.clear();                 // (m->logits rewritten: llamahip_stage_logits rows are this eval's rows again)
     return rc;
 }
 
@@ -2300,6 +2322,10 @@ struct RowsPass {
     bool score = false;
     int logits_cap = VERIFY_ROWS_MAX;             // (= ROWS_LOGITS_MAX: a scheduler's step)
     int n_logits() const { return logit_rows.empty() && !score ? n_seqs : (int) logit_rows.size(); }
+    // an embedding pass (llamahip_text_embedding_multi): in place of the lm head the fp32 final norm, the pooling per segment and the optional L2
+    // normalisation into the last stage's d_embed (embed_tail_rows); the logits and their row map stay as they are
+    bool embed = false;
+    int embed_pool = 0, embed_normalize = 0;
 };
 constexpr int ROWS_LOGITS_MAX = VERIFY_ROWS_MAX;
 // the lm head's row list: a row per KV slot or ROWS_LOGITS_MAX rows, and as many as the table has rows (a scoring pass may score every row)
@@ -2348,6 +2374,37 @@ static int rows_upload(llamahip_model *m, const RowsPass &rp, char *err, size_t 
     return 0;
 }
 
+// ---- a text's embedding: the device buffer of the last stage and the tail of a pass (pool.hip; llamahip_text_embedding[_multi] below)
+struct EmbedDev { float *out; int32_t *seg; float *y; };
+static EmbedDev embed_dev(llamahip_model *m) {
+    const size_t d = m->hp.n_embd, out_b = (size_t) m->embed_segs_cap * d * 4, seg_b = ((size_t) m->embed_segs_cap + 1 + 3) / 4 * 16;
+    return { (float *) m->d_embed, (int32_t *) (m->d_embed + out_b), (float *) (m->d_embed + out_b + seg_b) };
+}
+// room for n_segs pooled rows and n_rows norm rows (grown outside any enqueued work: the stage is idle between entry points)
+static int embed_ensure(llamahip_model *m, int n_segs, int n_rows, char *err, size_t err_cap) {
+    if (m->d_embed && n_segs <= m->embed_segs_cap && n_rows <= m->embed_rows_cap) return 0;
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+    m->own.release(&m->d_embed);
+    const int segs = std::max(std::max(n_segs, m->embed_segs_cap), LLAMAHIP_POOL_MAX_SEGS), rows = std::max(std::max(n_rows, m->embed_rows_cap), 64);
+    m->embed_segs_cap = m->embed_rows_cap = 0;
+    const size_t d = m->hp.n_embd;
+    HIP_TRY(m->own.alloc(&m->d_embed, (size_t) segs * d * 4 + ((size_t) segs + 1 + 3) / 4 * 16 + (size_t) rows * d * 4), LLAMAHIP_ERR_PREDICT);
+    m->embed_segs_cap = segs; m->embed_rows_cap = rows;
+    return 0;
+}
+// seg_begin (n_segs + 1 entries over the rows of y) up, the pooling and the optional L2 normalisation behind whatever wrote y on m->stream
+static int embed_pool_enqueue(llamahip_model *m, const std::vector<int32_t> &seg_begin, int pool, int normalize, char *err, size_t err_cap) {
+    const EmbedDev ed = embed_dev(m);
+    const int n_segs = (int) seg_begin.size() - 1;
+    m->h_embed_seg = seg_begin;          // (alive until the stream has drained)
+    HIP_TRY(hipMemcpyAsync(ed.seg, m->h_embed_seg.data(), m->h_embed_seg.size() * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_pool_rows(ed.y, ed.seg, n_segs, m->hp.n_embd, pool, normalize, ed.out, m->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+struct RowsPass;
+static int embed_tail_rows(llamahip_model *m, const RowsPass &rp, const int32_t *last_idx, char *err, size_t err_cap);
+
 // the pass on one handle's layers, enqueued on its stream (the multi-row branch of forward, with the table kernels where the rows' segments matter)
 static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, const float *hidden_in, char *err, size_t err_cap) {
     const HParams &hp = m->hp;
@@ -2384,6 +2441,7 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
         HIP_TRY(launch_prep(PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
         HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, R, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
     }
+    if (m->last_stage && rp.embed) return embed_tail_rows(m, rp, rd.last_idx, err, err_cap);
     if (m->last_stage) {
         // the segments' last rows (a drafted scheduler step: its list of rows) side by side (x1 is free here), the final norm and the lm head over
         // those nl rows: logits rows 0 .. nl - 1
@@ -2402,6 +2460,23 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
     return 0;
 }
 
+// the tail of an embedding pass over the R rows of m->x.  LAST: the segments' last rows side by side (x1 is free here, as for the lm head), the
+// norm over those n_seqs rows alone, each a segment of one row; MEAN: the norm over all R rows, the segments as the pass has them
+static int embed_tail_rows(llamahip_model *m, const RowsPass &rp, const int32_t *last_idx, char *err, size_t err_cap) {
+    const int d = m->hp.n_embd, n = rp.n_seqs;
+    const EmbedDev ed = embed_dev(m);
+    std::vector<int32_t> seg((size_t) n + 1, 0);
+    if (rp.embed_pool == LLAMAHIP_POOL_LAST) {
+        HIP_TRY(launch_gather_rows(m->x, last_idx, n, d, m->x1, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_norm_rows_f32(m->x1, m->norm_w, d, n, ed.y, m->stream), LLAMAHIP_ERR_PREDICT);
+        for (int i = 0; i <= n; i++) seg[(size_t) i] = i;
+    } else {
+        HIP_TRY(launch_norm_rows_f32(m->x, m->norm_w, d, rp.R, ed.y, m->stream), LLAMAHIP_ERR_PREDICT);
+        for (int i = 0; i < n; i++) seg[(size_t) i + 1] = seg[(size_t) i] + rp.n_tokens[i];
+    }
+    return embed_pool_enqueue(m, seg, rp.embed_pool, rp.embed_normalize, err, err_cap);
+}
+
 // one stage of the pass: its workspaces, the tokens (first stage), the launches -- enqueued, not waited for
 static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass &rp, const int32_t *tokens, const float *hidden_in, char *err, size_t err_cap) {
     HIP_TRY(hipSetDevice(st->device), LLAMAHIP_ERR_PREDICT);
@@ -2410,6 +2485,7 @@ static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass 
     if ((rc = ensure_attn_ws(st, 2, err, err_cap)) != 0) return rc;
     if ((rc = ensure_prompt_copies(st, rp.R, err, err_cap)) != 0) return rc;
     if (rp.score && st->last_stage) ensure_output_copies(st, rp.n_logits());
+    if (rp.embed && st->last_stage && (rc = embed_ensure(st, rp.n_seqs, rp.embed_pool == LLAMAHIP_POOL_LAST ? rp.n_seqs : rp.R, err, err_cap)) != 0) return rc;
     if (st->first_stage) HIP_TRY(hipMemcpyAsync(st->d_tokens, tokens, (size_t) rp.R * 4, hipMemcpyHostToDevice, st->stream), LLAMAHIP_ERR_PREDICT);
     return forward_rows(st, n_threads, rp, hidden_in, err, err_cap);
 }
@@ -2625,6 +2701,114 @@ int llamahip_score_choices(llamahip_model *m, int32_t n_threads, const int32_t *
         if (n_greedy) n_greedy[i] = greedy;
     }
     if (logprob_rows) std::copy(lp.begin(), lp.end(), logprob_rows);
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// A text's embedding: llamahip_text_embedding / llamahip_text_embedding_multi (llamahip.h).  The eval of the same arguments --
+// llamahip_eval_chunks' split for one text, llamahip_eval_multi's pass for several -- with the lm head replaced by pool.hip's launches on the last
+// stage's stream; n_embd floats per text come back from the last stage's d_embed.
+// ------------------------------------------------------------------------------------------------
+// one text on the current slot (checked by the caller), on a plain or a pipeline handle, every file type
+static int embed_text_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int32_t chunk_tokens, int32_t pool,
+                           int32_t normalize, float *out, char *err, size_t err_cap) {
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *last = stages[S - 1];
+    const size_t d = m->hp.n_embd;
+    const bool mean = pool == LLAMAHIP_POOL_MEAN;
+    int rc;
+    if ((rc = embed_ensure(last, 1, mean ? N : 1, err, err_cap)) != 0) return rc;
+    const EmbedDev ed = embed_dev(last);
+    // llamahip_eval_chunks' split: one pass with the chunks' key splits where the file type has one, else eval by eval
+    const bool chunked = chunk_tokens > 0 && N > chunk_tokens, one_pass = !chunked || chunks_in_one_pass(m, N);
+    const int step = one_pass ? N : chunk_tokens;
+    for (int32_t c0 = 0; c0 < N; c0 += step) {
+        const double t0 = now_ms();
+        const int32_t n = std::min(step, N - c0);
+        const bool final = c0 + n == N;
+        const EmbedReq rq = mean ? EmbedReq{ ed.y + (size_t) c0 * d, 0 } : final ? EmbedReq{ ed.y, n - 1 } : EmbedReq{ nullptr, 0 };
+        rc = 0;
+        for (int s = 1; s < S && rc == 0; s++) rc = pipe_ensure_in(stages[s], n, err, err_cap);
+        if (rc) return rc;
+        for (int s = 0; s < S && rc == 0; s++) {
+            llamahip_model *st = stages[s];
+            st->cur_seq = m->cur_seq;
+            rc = eval_stage_enqueue(st, n_threads, n_past + c0, tokens + c0, n, s ? st->pipe_in : nullptr, one_pass && chunked ? chunk_tokens : 0, false, err, err_cap, &rq);
+            if (rc == 0 && s + 1 < S) rc = pipe_hand_off(st, stages[s + 1], stages[s + 1]->pipe_in, st->x, (size_t) n * d * 4, err, err_cap);
+        }
+        if (rc == 0 && final) {
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            rc = embed_pool_enqueue(last, { 0, mean ? N : 1 }, pool, normalize, err, err_cap);
+        }
+        // (the bounded wait first, the copy of the result behind it: pipe_eval)
+        if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+        m->n_evals++;
+        m->t_eval_ms += now_ms() - t0;
+    }
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(out, ed.out, d * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    return LLAMAHIP_OK;
+}
+
+int llamahip_text_embedding(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens, int32_t chunk_tokens,
+                            int32_t pool, int32_t normalize, float *out, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_text_embedding";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    const int32_t slot = m->cur_seq;
+    int rc = embed_check(fn, m->hp.n_ctx, m->hp.n_vocab, m->n_seq, m->sched ? sched_dev_max_active(m->sched) : 0, 1, &slot, &n_past, tokens, &n_tokens,
+                         chunk_tokens, pool, normalize, out, err, err_cap);
+    if (rc) return rc;
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    return embed_text_impl(m, n_threads, n_past, tokens, n_tokens, chunk_tokens, pool, normalize, out, err, err_cap);
+}
+
+int llamahip_text_embedding_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *slots, const int32_t *n_past, const int32_t *tokens,
+                                  const int32_t *n_tokens, int32_t chunk_tokens, int32_t pool, int32_t normalize, float *out,
+                                  llamahip_eval_multi_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_text_embedding_multi";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = embed_check(fn, m->hp.n_ctx, m->hp.n_vocab, m->n_seq, m->sched ? sched_dev_max_active(m->sched) : 0, n_seqs, slots, n_past, tokens, n_tokens,
+                         chunk_tokens, pool, normalize, out, err, err_cap);
+    if (rc) return rc;
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    llamahip_model *last = stages.back();
+    const size_t d = m->hp.n_embd;
+    RowsPass rp;
+    rp.n_seqs = n_seqs; rp.chunk = chunk_tokens; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens;
+    for (int i = 0; i < n_seqs; i++) rp.R += n_tokens[i];
+    llamahip_eval_multi_stats st_out = {};
+    st_out.struct_size = (int32_t) sizeof(st_out);
+    st_out.n_rows = rp.R;
+    auto report = [&]() { if (stats) { const int32_t n = std::min((size_t) std::max(stats->struct_size, 0), sizeof(st_out)); if (n >= 4) { st_out.struct_size = n; memcpy(stats, &st_out, (size_t) n); } } };
+    // llamahip_eval_multi's rule for the per-slot loop (see there)
+    bool all_huge = rp.R > EVAL_MULTI_LOOP_ROWS;
+    for (int i = 0; i < n_seqs; i++) all_huge = all_huge && n_tokens[i] >= EVAL_MULTI_LOOP_SEG_ROWS;
+    if (!rows_pass_applies(m) || n_seqs == 1 || all_huge) {
+        std::vector<size_t> at((size_t) n_seqs, 0);
+        for (int i = 1; i < n_seqs; i++) at[i] = at[i - 1] + (size_t) n_tokens[i - 1];
+        const int64_t evals0 = m->n_evals;
+        rc = each_slot(m, n_seqs, slots, err, err_cap, [&](int i) {
+            return embed_text_impl(m, n_threads, n_past[i], tokens + at[i], n_tokens[i], chunk_tokens, pool, normalize, out + (size_t) i * d, err, err_cap); });
+        if (rc) return rc;
+        st_out.n_passes = (int32_t) (m->n_evals - evals0);
+        report();
+        return LLAMAHIP_OK;
+    }
+    const double t0 = now_ms();
+    rp.embed = true; rp.embed_pool = pool; rp.embed_normalize = normalize;
+    if (rows_pass_build(rp, m->hp.n_ctx) != 0) { set_err(err, err_cap, "%s: the row table could not be built", fn); return LLAMAHIP_ERR_PREDICT; }
+    st_out.n_passes = 1; st_out.n_short_segs = rp.n_short_segs; st_out.n_long_segs = rp.n_long_segs;
+    st_out.attn_groups = (rp.n_short_segs > 0 ? 1 : 0) + rp.n_long_segs;
+    rc = rows_pass_enqueue(stages, n_threads, rp, tokens, err, err_cap);
+    // (the bounded wait first, the copy of the vectors behind it: pipe_eval)
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(out, embed_dev(last).out, (size_t) n_seqs * d * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    m->n_evals++;
+    m->t_eval_ms += now_ms() - t0;
+    report();
     return LLAMAHIP_OK;
 }
 

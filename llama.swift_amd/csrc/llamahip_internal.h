@@ -328,6 +328,11 @@ constexpr size_t SLIDE_SET_IDS = 16 * 1024 + 16;
 // on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,
                               hipStream_t st);
+// a text's embedding (pool.hip): the final norm of n_rows rows x[n_rows][d] as plain fp32 rows y (k_dense_prep<PREP_NORM>'s arithmetic, no fp16
+// rounding, no permutation); then out[s] = the last row (pool 0) or the mean in double over rows [seg_begin[s], seg_begin[s + 1]) of y in ascending
+// row order (pool 1), and with normalize the row divided by its L2 length (64 lane sums folded by the xor butterfly; a zero row stays zero)
+hipError_t launch_norm_rows_f32(const float *x, const float *w, int d, int n_rows, float *y, hipStream_t st);
+hipError_t launch_pool_rows(const float *y, const int32_t *seg_begin /* device, n_segs + 1 */, int n_segs, int d, int pool, int normalize, float *out, hipStream_t st);
 hipError_t launch_argmax(const float *logits, int V, int32_t *out, int out_idx, int32_t *next_token, int32_t *state, hipStream_t st, uint64_t *token_mb = nullptr);
 // drafted greedy decoding (verify.hip): pick[r] = the greedy pick of row r (k_argmax's rule), 1 .. VERIFY_ROWS_MAX rows; then, for
 // tokens = [last accepted token, draft ...] of those rows: n_accept = the number of leading draft tokens the picks reproduce,

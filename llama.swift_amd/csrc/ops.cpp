@@ -15,6 +15,8 @@ static_assert(LLAMAHIP_PREP_KERNEL_AUTO == PREP_FORCE_AUTO && LLAMAHIP_PREP_KERN
 
 namespace lh {      // eval_multi.cpp
 int rows_table_check(int32_t R, int32_t n_ctx, int32_t n_slots, const int32_t *row_slot, const int32_t *row_pos, const int32_t *row_keys, char *err, size_t err_cap);
+int pool_rows_check(const float *x, int32_t R, int32_t d, const float *norm_w, const int32_t *seg_begin, int32_t n_segs, int32_t pool, int32_t normalize,
+                    const float *out, char *err, size_t err_cap);
 }
 
 extern "C" {
@@ -975,6 +977,31 @@ int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, co
     if (logprob_out) memcpy(logprob_out, h.data(), N * 8);
     if (argmax_out) memcpy(argmax_out, h.data() + N * 8, N * 4);
     if (rank_out) memcpy(rank_out, h.data() + N * 12, N * 4);
+    return LLAMAHIP_OK;
+}
+
+// the tail of an embedding pass on caller-supplied rows (parity tests): see llamahip_text_embedding.  LAST: the segments' last rows gathered first,
+// the norm over those rows alone -- forward_rows' launches
+int llamahip_op_pool_rows(const float *x, int32_t R, int32_t d, const float *norm_w, const int32_t *seg_begin, int32_t n_segs, int32_t pool, int32_t normalize,
+                          float *out, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_pool_rows";
+    if (pool_rows_check(x, R, d, norm_w, seg_begin, n_segs, pool, normalize, out, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const bool last = pool == LLAMAHIP_POOL_LAST;
+    const size_t D = (size_t) d, ny = last ? (size_t) n_segs : (size_t) R;
+    // LAST: idx = the segments' last rows, seg = 0 .. n_segs over the gathered rows
+    std::vector<int32_t> idx((size_t) n_segs), seg(seg_begin, seg_begin + n_segs + 1);
+    for (int s = 0; s < n_segs; s++) idx[(size_t) s] = seg_begin[s + 1] - 1;
+    if (last) for (int s = 0; s <= n_segs; s++) seg[(size_t) s] = s;
+    Scratch s;
+    float *d_x = s.alloc((size_t) R * D, x), *d_w = s.alloc(D, norm_w);
+    float *d_g = last ? s.alloc<float>(ny * D) : nullptr, *d_y = s.alloc<float>(ny * D), *d_o = s.alloc<float>((size_t) n_segs * D);
+    int32_t *d_seg = s.alloc(seg.size(), seg.data()), *d_idx = s.alloc(idx.size(), idx.data());
+    if (s.ok() && last) s.check(launch_gather_rows(d_x, d_idx, n_segs, d, d_g, nullptr));
+    if (s.ok()) s.check(launch_norm_rows_f32(last ? d_g : d_x, d_w, d, (int) ny, d_y, nullptr));
+    if (s.ok()) s.check(launch_pool_rows(d_y, d_seg, n_segs, d, pool, normalize, d_o, nullptr));
+    s.download(out, d_o, (size_t) n_segs * D * 4);
+    if (!s.ok()) return s.fail(fn, err, err_cap);
     return LLAMAHIP_OK;
 }
 

@@ -108,6 +108,12 @@ int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n
 void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk);
 int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
                         const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap);
+// ... and of llamahip_text_embedding[_multi] / llamahip_op_pool_rows
+int embed_check(const char *fn, int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t sched_max_active, int32_t n_seqs, const int32_t *slots,
+                const int32_t *n_past, const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, int32_t pool, int32_t normalize,
+                const float *out, char *err, size_t err_cap);
+int pool_rows_check(const float *x, int32_t R, int32_t d, const float *norm_w, const int32_t *seg_begin, int32_t n_segs, int32_t pool, int32_t normalize,
+                    const float *out, char *err, size_t err_cap);
 int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size_t err_cap) {
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
@@ -313,6 +319,103 @@ __attribute__((noinline)) static void scoring_host_half(int V) {          // (it
             refused([&](char *e, size_t cap) { return lh::score_choices_check(64, V, 16, ctx.data(), nc, n, ends.data(), ne.data(), 0, e, cap); });
         }
     printf("host_sanitize: scoring over KV slots: %ld refusals at short and missing message buffers, %ld scatters of compacted results against the rule restated\n", n_checks, n_scatter);
+}
+
+// text embeddings (llamahip_text_embedding[_multi] / llamahip_op_pool_rows): the argument checks on exactly sized arrays, every refusal at
+// message buffers too short for its message and with none
+__attribute__((noinline)) static void embedding_host_half(int V) {
+    long n_checks = 0;
+    auto refused = [&](const char *fn, auto call) {
+        for (size_t cap : { (size_t) 1, (size_t) 24, (size_t) 400 }) {
+            std::vector<char> e(cap, 'x');
+            EXPECT(call(e.data(), cap) == LLAMAHIP_ERR_PREDICT);
+            EXPECT(memchr(e.data(), 0, cap) != nullptr);
+            if (cap == 400) EXPECT(strstr(e.data(), fn) != nullptr);
+            n_checks++;
+        }
+        EXPECT(call(nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+        n_checks++;
+    };
+    static const char *fm = "llamahip_text_embedding_multi", *f1 = "llamahip_text_embedding", *fo = "llamahip_op_pool_rows";
+    const int C = 64;
+    float out1[1] = { 0.f };
+    for (int n : { 1, 3, 16 }) {
+        std::vector<int32_t> slots((size_t) n), np((size_t) n), nt((size_t) n);
+        int R = 0;
+        for (int i = 0; i < n; i++) { slots[i] = n - 1 - i; np[i] = i % 5; nt[i] = 1 + (i * 7) % 11; R += nt[i]; }
+        std::vector<int32_t> toks((size_t) R, V - 1);
+        char err[256];
+        for (int pool : { 0, 1 })
+            for (int nrm : { 0, 1 }) {
+                EXPECT(lh::embed_check(fm, C, V, n, 0, n, slots.data(), np.data(), toks.data(), nt.data(), 9, pool, nrm, out1, err, sizeof(err)) == 0);
+                EXPECT(lh::embed_check(fm, C, V, n, 0, n, slots.data(), np.data(), toks.data(), nt.data(), 0, pool, nrm, out1, nullptr, 0) == 0);
+            }
+        auto chk = [&](int n_slots, int sched, int n_seqs, int chunk, int pool, int nrm, const float *out) {
+            return [=, &slots, &np, &toks, &nt](char *e, size_t cap) { return lh::embed_check(fm, C, V, n_slots, sched, n_seqs, slots.data(), np.data(), toks.data(), nt.data(), chunk, pool, nrm, out, e, cap); };
+        };
+        refused(fm, chk(n, 0, n, 0, 2, 0, out1));
+        refused(fm, chk(n, 0, n, 0, -1, 0, out1));
+        refused(fm, chk(n, 0, n, 0, 0, 2, out1));
+        refused(fm, chk(n, 0, n, 0, 1, -1, out1));
+        refused(fm, chk(n, 0, n, 0, 1, 1, nullptr));
+        refused(fm, chk(n, 1, n, 0, 1, 1, out1));          // (slot 0 is named and is the scheduler's)
+        refused(fm, chk(n, 0, n, -1, 0, 0, out1));
+        refused(fm, chk(n - 1, 0, n, 0, 0, 0, out1));
+        refused(fm, chk(n, 0, 0, 0, 0, 0, out1));
+        toks[(size_t) R - 1] = V;
+        refused(fm, chk(n, 0, n, 0, 0, 0, out1));
+        toks[(size_t) R - 1] = 0; np[n - 1] = C;
+        refused(fm, chk(n, 0, n, 0, 0, 0, out1));
+        np[n - 1] = 0;
+        if (n > 1) { slots[n - 1] = slots[0]; refused(fm, chk(n, 0, n, 0, 0, 0, out1)); slots[n - 1] = 0; }
+        nt[n - 1] = 0;          // (the last segment: no array is read past its end)
+        refused(fm, chk(n, 0, n, 0, 0, 0, out1));
+    }
+    {   // the single text: one segment on the current slot
+        const int32_t slot = 2, past = 3, N = 5, toks[5] = { 1, 2, 3, 4, 5 };
+        char err[256];
+        EXPECT(lh::embed_check(f1, C, V, 4, 2, 1, &slot, &past, toks, &N, 0, 1, 1, out1, err, sizeof(err)) == 0);
+        refused(f1, [&](char *e, size_t cap) { return lh::embed_check(f1, C, V, 4, 3, 1, &slot, &past, toks, &N, 0, 1, 1, out1, e, cap); });
+        refused(f1, [&](char *e, size_t cap) { return lh::embed_check(f1, C, V, 4, 0, 1, &slot, &past, toks, &N, 0, 3, 0, out1, e, cap); });
+        refused(f1, [&](char *e, size_t cap) { return lh::embed_check(f1, C, V, 4, 0, 1, &slot, &past, nullptr, &N, 0, 0, 0, out1, e, cap); });
+        const int32_t far = C - 4;
+        refused(f1, [&](char *e, size_t cap) { return lh::embed_check(f1, C, V, 4, 0, 1, &slot, &far, toks, &N, 0, 0, 0, out1, e, cap); });
+    }
+    {   // llamahip_op_pool_rows: x, norm_w and out are not read by the check
+        const float x[1] = { 0.f }, w[1] = { 0.f };
+        char err[256];
+        for (int n : { 1, 5, 16 }) {
+            std::vector<int32_t> seg((size_t) n + 1);
+            for (int i = 0; i <= n; i++) seg[i] = i * 3;
+            const int R = 3 * n;
+            EXPECT(lh::pool_rows_check(x, R, 96, w, seg.data(), n, 1, 1, out1, err, sizeof(err)) == 0);
+            EXPECT(lh::pool_rows_check(x, R, 32, w, seg.data(), n, 0, 0, out1, nullptr, 0) == 0);
+            auto chk = [&](const float *xx, int RR, int d, const float *ww, int ns, int pool, int nrm, const float *out) {
+                return [=, &seg](char *e, size_t cap) { return lh::pool_rows_check(xx, RR, d, ww, seg.data(), ns, pool, nrm, out, e, cap); };
+            };
+            refused(fo, chk(nullptr, R, 32, w, n, 0, 0, out1));
+            refused(fo, chk(x, R, 32, nullptr, n, 0, 0, out1));
+            refused(fo, chk(x, R, 32, w, n, 0, 0, nullptr));
+            refused(fo, [&](char *e, size_t cap) { return lh::pool_rows_check(x, R, 32, w, nullptr, n, 0, 0, out1, e, cap); });
+            refused(fo, chk(x, 0, 32, w, n, 0, 0, out1));
+            refused(fo, chk(x, LLAMAHIP_EVAL_MULTI_MAX_ROWS + 1, 32, w, n, 0, 0, out1));
+            refused(fo, chk(x, R, 0, w, n, 0, 0, out1));
+            refused(fo, chk(x, R, 16, w, n, 0, 0, out1));
+            refused(fo, chk(x, R, 48, w, n, 0, 0, out1));
+            refused(fo, chk(x, R, 32, w, 0, 0, 0, out1));
+            refused(fo, chk(x, R, 32, w, n, 2, 0, out1));
+            refused(fo, chk(x, R, 32, w, n, 0, 2, out1));
+            refused(fo, chk(x, R + 1, 32, w, n, 0, 0, out1));          // (seg_begin ends below R)
+            seg[0] = 1;
+            refused(fo, chk(x, R, 32, w, n, 0, 0, out1));
+            seg[0] = 0;
+            if (n > 1) { const int32_t keep = seg[1]; seg[1] = seg[2]; refused(fo, chk(x, R, 32, w, n, 0, 0, out1)); seg[1] = 0; refused(fo, chk(x, R, 32, w, n, 0, 0, out1)); seg[1] = keep; }
+        }
+        std::vector<int32_t> seg17(18);
+        for (int i = 0; i <= 17; i++) seg17[i] = i;
+        refused(fo, [&](char *e, size_t cap) { return lh::pool_rows_check(x, 17, 32, w, seg17.data(), 17, 0, 0, out1, e, cap); });
+    }
+    printf("host_sanitize: text embeddings: %ld refusals at short and missing message buffers\n", n_checks);
 }
 
 int main(int argc, char **argv) {
@@ -665,6 +768,7 @@ int main(int argc, char **argv) {
         EXPECT(llamahip_eval_multi_rows(64, 1, nullptr, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, big, -1, nullptr, nullptr, nullptr) == -1);
     }
     scoring_host_half(V);
+    embedding_host_half(V);
     // the request scheduler's host half against the stubbed device half: the step rule over a grid on exactly sized arrays against its
     // restatement; then whole runs -- every step's segments replayed against the rule and the requests' own state (positions, offsets, tokens,
     // emit flags), the events against the made-up tokens; the refusals of new / submit / step; cancelling queued and active requests
