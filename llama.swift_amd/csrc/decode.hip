@@ -24,7 +24,7 @@
 //       da : float  [block b]
 //
 // Contents of this file, in order:
-//   tagged hand-off helpers (poll_tagged, store_tagged), GemvArgs
+//   tagged hand-off helpers (poll_tagged, store_tagged), GemvHot / GemvCold
 //   gemv_body / k_gemv          the decode mat-vec: fused prologues (QA copy | norm | plain | SiLU*up | norm on a tagged row) and
 //                               epilogues (store | +residual | SiLU*up -> Q4_0 | tagged rows), register ring of weight chunks
 //   k_dec_scores, k_decn_scores, k_dec_pv_blk   attention of one row (decode fallback) / of a short eval (2..60 rows)
@@ -87,44 +87,70 @@ __device__ __forceinline__ void store_tagged(uint64_t *p, float v, uint32_t tag)
 }
 
 
-struct GemvArgs {
-    const uint8_t *wt; int ngroups, nchunks, M, gmapF8;
-    const uint32_t *qa_A; const float *qa_d;
-    const float *in0, *in1; int K;
+// The arguments of a decode mat-vec launch, split by who reads them (DESIGN.md "Kernel entry").  A wave cannot request a weight
+// byte before its kernel arguments are in SGPRs, and every 64-byte line of the kernarg segment it touches for the first time is a
+// scalar-cache miss: GemvHot is everything a launch of the default schedule reads, two lines, fetched in ONE batch at entry
+// (gemv_entry below); GemvCold is a further kernel parameter of the instances that need it and of no other.
+struct alignas(64) GemvHot {
+    const uint8_t *wt;                                // chain-major tiles of the matrix
+    const void *op0, *op1;                            // PRE_QA: qa_A (uint32), qa_d (float); fp32 prologues: in0 (the row), in1 (the norm weight)
     float *y; const float *resid;
     const uint16_t *T_silu;
     uint32_t *out_A; float *out_d;
-    const f64x2 *part_in; int npart; f64x2 *part_out;
-    uint32_t *sync; int sync_blocks, sync_epoch;      // hand-off words, blocks of the producer role, 1-based epoch
-    int lut_math;                                     // bit 0: evaluate SiLU instead of gathering it (verified at load time)
+    const f64x2 *part_in; f64x2 *part_out;
+    const uint32_t *epoch;                            // tagged hand-offs: the epoch word the tags are made from
+    uint64_t *amax_t;                                 // EPI_SILU_QAH: the granules the two halves of a block exchange their amax through
+    int ngroups, nchunks, M, gmapF8, K, npart;
+    int lut_math;                                     // bit 0: evaluate SiLU instead of gathering it (verified at load time); 0x1000 / 0x2000: fault-injection tests
+    uint16_t layer, nw;                               // tags of layer `layer` are make_tag(epoch, layer + 1); waves per workgroup (blockDim.x / 64, known to the host)
+};
+static_assert(sizeof(GemvHot) <= 128 && alignof(GemvHot) == 64, "the hot block of a decode mat-vec is two scalar-cache lines");
+struct GemvCold {
     uint32_t *fault;                                  // tagged operands: sticky fault word (a bounded poll that ran out)
-    // residual-stream rows handed between pipeline stages through a device-side mailbox: tagged granules; `sync` -> the epoch word
+    // residual-stream rows handed between pipeline stages through a device-side mailbox: tagged granules
     const uint64_t *in_t;   int slot_in;              // PREP_NORM_TAG: the fp32 row [K] arrives tagged
     const uint64_t *resid_t; int slot_resid;          // EPI_RESID_TAG: the residual row [M] arrives tagged (null: plain `resid`)
     uint64_t *out_t;        int slot_out;             // EPI_RESID_TAG: y [M] also leaves tagged (null: plain `y` only)
     const int32_t *pos_w;                             // mailbox tags are made from the sequence position, *pos_w + 1, not from the epoch (null: epoch)
     PickIO pick;                                      // EPI_STORE_PICK (llamahip_internal.h)
+    int nwg;                                          // EPI_STORE_PICK: workgroups of the launch
     int patience;                                     // mailbox polls wait for ANOTHER process / device: their bounds are shifted left by this (3: ~20 s of
                                                       // looks at an uncached / remote granule -- legitimate waits are milliseconds, and a mapping that does not carry
                                                       // the stores must cost the bench's one-token handshake seconds, not minutes, before it falls back to RCCL)
 };
+// the instances that take a GemvCold: the mailbox prologue / epilogue, the pick, the half-block w1|w3 (its fault word)
+constexpr bool gemv_needs_cold(int pre, int epi) { return pre == PREP_NORM_TAG || epi == EPI_RESID_TAG || epi == EPI_STORE_PICK || epi == EPI_SILU_QAH; }
+
+// Kernel entry: every field of the hot block is requested at once and held in SGPRs from here on -- the epilogue's pointers too, so
+// that nothing is fetched from the kernarg segment behind the weight stream.  (Left alone the compiler sinks each s_load to its
+// first use: four dependent round trips before the first weight load of the w1|w3 kernel.)  The empty asm only names the values
+// as scalar inputs; it emits nothing.
+__device__ __forceinline__ void gemv_entry(const GemvHot &gh) {
+    asm volatile("" :: "s"(gh.wt), "s"(gh.op0), "s"(gh.op1), "s"(gh.y), "s"(gh.resid), "s"(gh.T_silu), "s"(gh.out_A), "s"(gh.out_d),
+                       "s"(gh.part_in), "s"(gh.part_out), "s"(gh.epoch), "s"(gh.amax_t),
+                       "s"(gh.ngroups), "s"(gh.nchunks), "s"(gh.M), "s"(gh.gmapF8), "s"(gh.K), "s"(gh.npart), "s"(gh.lut_math),
+                       "s"((uint32_t) gh.layer | ((uint32_t) gh.nw << 16)));
+}
+
 template <int PRE, int EPI, int D, bool RING, int PG>
-__device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, const int nw, double *smem_d) {
-    const uint8_t *__restrict__ wt = ga.wt;
-    const int ngroups = ga.ngroups, nchunks = ga.nchunks, M = ga.M, gmapF8 = ga.gmapF8, K = ga.K, npart = ga.npart;
-    const uint32_t *__restrict__ qa_A = ga.qa_A; const float *__restrict__ qa_d = ga.qa_d;
-    const float *__restrict__ in0 = ga.in0; const float *__restrict__ in1 = ga.in1;
-    float *__restrict__ y = ga.y; const float *__restrict__ resid = ga.resid;
-    const uint16_t *__restrict__ T_silu = ga.T_silu;
-    uint32_t *__restrict__ out_A = ga.out_A; float *__restrict__ out_d = ga.out_d;
-    const f64x2 *__restrict__ part_in = ga.part_in; f64x2 *__restrict__ part_out = ga.part_out;
-    // (EPI_STORE_TAG: the tag of this launch's output granules, read up front -- not a dependent load at the tail)
+__device__ __forceinline__ void gemv_body(const GemvHot &gh, const GemvCold &gc, const int blk, const int nw, double *smem_d) {
+    const uint8_t *__restrict__ wt = gh.wt;
+    const int ngroups = gh.ngroups, nchunks = gh.nchunks, M = gh.M, gmapF8 = gh.gmapF8, K = gh.K, npart = gh.npart, lut_math = gh.lut_math;
+    const uint32_t *__restrict__ qa_A = (const uint32_t *) gh.op0; const float *__restrict__ qa_d = (const float *) gh.op1;
+    const float *__restrict__ in0 = (const float *) gh.op0; const float *__restrict__ in1 = (const float *) gh.op1;
+    float *__restrict__ y = gh.y; const float *__restrict__ resid = gh.resid;
+    const uint16_t *__restrict__ T_silu = gh.T_silu;
+    uint32_t *__restrict__ out_A = gh.out_A; float *__restrict__ out_d = gh.out_d;
+    const f64x2 *__restrict__ part_in = gh.part_in; f64x2 *__restrict__ part_out = gh.part_out;
+    uint64_t *amax_t = gh.amax_t;
+    // (EPI_STORE_TAG: the tag of this launch's output granules, read up front -- not a dependent load at the tail; it is waited for
+    //  where the tag is first used)
     constexpr bool TAGGED = (EPI == EPI_STORE_TAG || PRE == PREP_NORM_TAG || EPI == EPI_RESID_TAG || EPI == EPI_SILU_QAH);
-    const uint32_t epoch_ = TAGGED ? __builtin_nontemporal_load(ga.sync) : 0u;
-    const uint32_t store_tag = make_tag(epoch_, ga.sync_epoch + 1);        // EPI_STORE_TAG output of layer ga.sync_epoch
+    const uint32_t epoch_ = TAGGED ? __builtin_nontemporal_load(gh.epoch) : 0u;
+    const uint32_t store_tag = make_tag(epoch_, (int) gh.layer + 1);        // EPI_STORE_TAG output of layer gh.layer
     // (mailbox rows between pipeline stages: the tag is the sequence position both sides know, st[0] + 1 -- the stages' epochs differ)
-    const uint32_t mb_epoch_ = ((PRE == PREP_NORM_TAG || EPI == EPI_RESID_TAG) && ga.pos_w) ? (uint32_t) __builtin_nontemporal_load(ga.pos_w) + 1u : epoch_;
-    const uint32_t tag_in = make_tag(mb_epoch_, ga.slot_in), tag_resid = make_tag(mb_epoch_, ga.slot_resid), tag_out = make_tag(mb_epoch_, ga.slot_out);
+    const uint32_t mb_epoch_ = ((PRE == PREP_NORM_TAG || EPI == EPI_RESID_TAG) && gc.pos_w) ? (uint32_t) __builtin_nontemporal_load(gc.pos_w) + 1u : epoch_;
+    const uint32_t tag_in = make_tag(mb_epoch_, gc.slot_in), tag_resid = make_tag(mb_epoch_, gc.slot_resid), tag_out = make_tag(mb_epoch_, gc.slot_out);
     // RING kernels: LDS holds D chunks more than the row has.  The ring's tail and its one-chunk-ahead
     // operand fetch run past the end (against the zero tile), and with zeroed padding those reads need no
     // index clamp -- their addresses are `loop base + immediate` instead of three VALU per chunk.
@@ -190,7 +216,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
     u32x4 qg[MAXQA], qh[MAXQD];
     const int nt = nw * 64;
     const int nh = K >> 4;                                   // half-blocks in the row
-    // (trip counts are wave-uniform; a skipped load only makes the compiler's vmcnt for these
+    // (which passes a thread takes part in is a per-lane compare against the row's granule count -- no trip count, i.e. no
+    //  integer division, stands between entry and the first load; a skipped load only makes the compiler's vmcnt for these
     //  prologue loads stricter -- they are all older than the weight loads, which stay in flight)
     // PREP_NORMP: the producer of the row (an EPI_RESID mat-vec, or k_embed_part) left per-workgroup
     // {sum x, sum x^2} in double; wave 0 folds them (same data, same order in every workgroup -> identical
@@ -198,16 +225,14 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
     // producer workgroups.
     constexpr int PNP = (PRE == PREP_NORMP) ? 8 : 1;
     f64x2 pp[PNP];
-    const int npl = (npart + 63) >> 6;
     float resid_v = 0.0f;
     uint64_t resid_g = 0;
     auto phase1 = [&]() {
     if ((NORMLIKE || PRE == PREP_PLAIN) && active) {
-        const int ng = (nh + nt - 1) / nt;
 #pragma unroll
         for (int u = 0; u < MAXH; u++) {
             // (waves whose granules all lie past the row issue nothing: w1|w3 runs 8 waves on a 4-wave row)
-            if (u < ng && (tid & ~63) + u * nt < nh) {
+            if ((tid & ~63) + u * nt < nh) {
                 const int hi = min(tid + u * nt, nh - 1);
 #pragma unroll
                 for (int v = 0; v < 4; v++) {
@@ -221,29 +246,28 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
         }
         if (PRE == PREP_NORMP && wave == 0) {          // one wave folds the pairs for the workgroup
 #pragma unroll
-            for (int u = 0; u < PNP; u++) if (u < npl) pp[u] = part_in[min(lane + u * 64, npart - 1)];
+            for (int u = 0; u < PNP; u++) if (lane + u * 64 < npart) pp[u] = part_in[lane + u * 64];
         }
     }
     // the residual operand of the epilogue is fetched here too, not at the end of the kernel where it
     // would add a memory round trip to every wave's critical path
-    if ((EPI == EPI_RESID || (EPI == EPI_RESID_TAG && !ga.resid_t)) && active) {
+    if ((EPI == EPI_RESID || (EPI == EPI_RESID_TAG && !gc.resid_t)) && active) {
         int lg0 = g;
         if (gmapF8) { const int b8 = g >> 3, w8 = g & 7; lg0 = w8 < 4 ? b8 * 4 + w8 : gmapF8 + b8 * 4 + (w8 - 4); }
         resid_v = resid[min(lg0 * 8 + (lane >> 3), M - 1)];
     }
     // (EPI_RESID_TAG with a mailbox residual: the granule is requested here as well -- the launch before this one gathered the same
     //  row, so it is there; the epilogue re-polls only if the tag says otherwise)
-    if (EPI == EPI_RESID_TAG && ga.resid_t && active && (lane & 7) == 0) {
+    if (EPI == EPI_RESID_TAG && gc.resid_t && active && (lane & 7) == 0) {
         int lg0 = g;
         if (gmapF8) { const int b8 = g >> 3, w8 = g & 7; lg0 = w8 < 4 ? b8 * 4 + w8 : gmapF8 + b8 * 4 + (w8 - 4); }
-        resid_g = load_granule_sys(ga.resid_t + min(lg0 * 8 + (lane >> 3), M - 1));
+        resid_g = load_granule_sys(gc.resid_t + min(lg0 * 8 + (lane >> 3), M - 1));
     }
     if (PRE == PRE_QA && active) {
-        const int nqa = (nchunks * 16 + nt - 1) / nt, nqd = (nchunks * 2 + nt - 1) / nt;
 #pragma unroll
-        for (int u = 0; u < MAXQA; u++) if (u < nqa) qg[u] = ((const u32x4 *) qa_A)[min(tid + u * nt, nchunks * 16 - 1)];
+        for (int u = 0; u < MAXQA; u++) if (tid + u * nt < nchunks * 16) qg[u] = ((const u32x4 *) qa_A)[tid + u * nt];
 #pragma unroll
-        for (int u = 0; u < MAXQD; u++) if (u < nqd) qh[u] = ((const u32x4 *) qa_d)[min(tid + u * nt, nchunks * 2 - 1)];
+        for (int u = 0; u < MAXQD; u++) if (tid + u * nt < nchunks * 2) qh[u] = ((const u32x4 *) qa_d)[tid + u * nt];
     }
     };
     // ---- phase 2: put the first D weight chunks in flight (they do not depend on the activations).
@@ -262,8 +286,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
         // over the row, sleeping between looks -- the producer's workgroups finish together, and pollers compete with its
         // weight stream -- then every thread runs the tag-checked copy of its own half-blocks, which passes on its first or second
         // round.  Correctness rests on the copy alone; the watch only keeps the polling traffic small.
-        const uint64_t *__restrict__ xt = ga.in_t;
-        const int give_up = (ga.lut_math & 0x1000) ? (1 << 8) : ((1 << 20) << ga.patience);      // (0x1000: fault-injection test)
+        const uint64_t *__restrict__ xt = gc.in_t;
+        const int give_up = (lut_math & 0x1000) ? (1 << 8) : ((1 << 20) << gc.patience);      // (0x1000: fault-injection test)
         if (wave == 0) {
             int spins = 0;
             for (;;) {
@@ -271,7 +295,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                 if (lane < LH_WATCH) ok = (uint32_t) (load_granule_sys(xt + ((2 * lane + 1) * K / (2 * LH_WATCH))) >> 32) == tag_in;
                 if (__all(ok)) break;
                 __builtin_amdgcn_s_sleep(8);
-                if (++spins > (give_up >> 2) || ((spins & 255) == 0 && __hip_atomic_load(ga.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) break;   // (the copy below raises the fault word if the row never comes)
+                if (++spins > (give_up >> 2) || ((spins & 255) == 0 && __hip_atomic_load(gc.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u)) break;   // (the copy below raises the fault word if the row never comes)
             }
         }
         __syncthreads();
@@ -290,7 +314,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                     }
                     if (ok) break;
                     __builtin_amdgcn_s_sleep(1);
-                    if (poll_give_up(spins, give_up, ga.fault)) break;
+                    if (poll_give_up(spins, give_up, gc.fault)) break;
                 }
 #pragma unroll
                 for (int v = 0; v < 4; v++)
@@ -332,7 +356,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                 if (wave == 0) {
 #pragma unroll
                     for (int u = 0; u < PNP; u++)
-                        if (u < npl && lane + u * 64 < npart) { S1 += pp[u].x; S2 += pp[u].y; }
+                        if (lane + u * 64 < npart) { S1 += pp[u].x; S2 += pp[u].y; }
                     S1 = wave_sum_d(S1);
                     S2 = wave_sum_d(S2);
                     if (lane == 0) { red[0] = S1; red[1] = S2; }
@@ -350,7 +374,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                             S2 = __builtin_fma(x0, x0, S2); S2 = __builtin_fma(x1, x1, S2); S2 = __builtin_fma(x2, x2, S2); S2 = __builtin_fma(x3, x3, S2);
                         }
                     }
-                block_sum_d2(S1, S2, red, 0);
+                block_sum_d2(S1, S2, red, 0, nw);
             }
             const double mean = S1 / (double) K;
             double sum2 = __builtin_fma(-mean, S1, S2);
@@ -368,7 +392,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                         if (!fast) { s2 += v0 * v0; s2 += v1 * v1; s2 += v2 * v2; s2 += v3 * v3; }
                     }
                 }
-            if (!fast) sum2 = block_sum_d(s2, red, 1);
+            if (!fast) sum2 = block_sum_d(s2, red, 1, nw);
             const float scale = (float) (1.0 / sqrt(sum2 / (double) K + (double) 1e-5f));
             LH_STAMP2(3);
 #pragma unroll
@@ -512,15 +536,15 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
         if (wave == 0 && valid) {
             const int i = lane & 15;
             const uint16_t gh = f2h_bits(gu[i]);
-            const float act = h2f_bits((ga.lut_math & 1) ? silu_math_bits(gh) : T_silu[gh]) * gu[16 + i];
+            const float act = h2f_bits((lut_math & 1) ? silu_math_bits(gh) : T_silu[gh]) * gu[16 + i];
             float amax = wave_max_f(lane < 16 ? fabsf(act) : 0.0f);
             // the other half's partial amax: one tagged granule each way inside this XCD's L2
-            uint64_t *at = (uint64_t *) ga.out_t;
+            uint64_t *at = amax_t;
             const int hb = qah_block * 2 + qah_half;
             float other = 0.0f;
             if (lane == 0) {
-                store_tagged(at + hb, amax, store_tag ^ ((ga.lut_math & 0x1000) ? 1u : 0u));      // (0x1000: fault-injection test)
-                other = poll_tagged(at + (hb ^ 1), store_tag, ga.fault, (ga.lut_math & 0x1000) != 0);
+                store_tagged(at + hb, amax, store_tag ^ ((lut_math & 0x1000) ? 1u : 0u));      // (0x1000: fault-injection test)
+                other = poll_tagged(at + (hb ^ 1), store_tag, gc.fault, (lut_math & 0x1000) != 0);
             }
             other = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, other)));
             amax = fmaxf(amax, other);
@@ -543,7 +567,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
         if (wave == 0) {
             const int i = lane & 31;
             const uint16_t gh = f2h_bits(gu[i]);
-            const float act = h2f_bits((ga.lut_math & 1) ? silu_math_bits(gh) : T_silu[gh]) * gu[32 + i];
+            const float act = h2f_bits((lut_math & 1) ? silu_math_bits(gh) : T_silu[gh]) * gu[32 + i];
             float amax = fabsf(act);
             amax = max_lanes_0_31(amax);
             const float dd = amax / 7.0f;
@@ -565,16 +589,16 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
         if (EPI == EPI_RESID) acc = acc + resid_v;
         if (EPI == EPI_RESID_TAG) {
             float rv = resid_v;
-            if (ga.resid_t) {
+            if (gc.resid_t) {
                 rv = __builtin_bit_cast(float, (uint32_t) resid_g);
                 if (live && (uint32_t) (resid_g >> 32) != tag_resid) {
                     int spins = 0;
                     uint64_t gq;
                     for (;;) {
-                        gq = load_granule_sys(ga.resid_t + m);
+                        gq = load_granule_sys(gc.resid_t + m);
                         if ((uint32_t) (gq >> 32) == tag_resid) break;
                         __builtin_amdgcn_s_sleep(4);
-                        if (poll_give_up(spins, (ga.lut_math & 0x1000) ? (1 << 8) : ((1 << 20) << ga.patience), ga.fault)) break;
+                        if (poll_give_up(spins, (lut_math & 0x1000) ? (1 << 8) : ((1 << 20) << gc.patience), gc.fault)) break;
                     }
                     rv = __builtin_bit_cast(float, (uint32_t) gq);
                 }
@@ -606,20 +630,20 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
             if (tid == 0) {
                 unsigned long long k2 = wk[0];
                 for (int w2_ = 1; w2_ < nw; w2_++) k2 = wk[w2_] > k2 ? wk[w2_] : k2;
-                __hip_atomic_store(ga.pick.key + blk, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(gc.pick.key + blk, k2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const int nwg = (int) gridDim.x, shard = blk & 7, nsh = (nwg + 7 - shard) / 8, ntop = nwg < 8 ? nwg : 8;
+                const int nwg = gc.nwg, shard = blk & 7, nsh = (nwg + 7 - shard) / 8, ntop = nwg < 8 ? nwg : 8;
                 int lastwg = 0;
-                if (atomicAdd(ga.pick.count + shard * 16, 1u) == (uint32_t) (nsh - 1))
-                    lastwg = atomicAdd(ga.pick.count + 128, 1u) == (uint32_t) (ntop - 1);
+                if (atomicAdd(gc.pick.count + shard * 16, 1u) == (uint32_t) (nsh - 1))
+                    lastwg = atomicAdd(gc.pick.count + 128, 1u) == (uint32_t) (ntop - 1);
                 wk[15] = (unsigned long long) lastwg;
             }
             __syncthreads();
             if (wk[15] != 0ull) {
                 // the last workgroup: every key is visible (each was acknowledged before its ticket); fold them in index order
                 unsigned long long best = 0ull;
-                for (int i = tid; i < (int) gridDim.x; i += nw * 64) {
-                    const unsigned long long kv = __hip_atomic_load(ga.pick.key + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int i = tid; i < gc.nwg; i += nw * 64) {
+                    const unsigned long long kv = __hip_atomic_load(gc.pick.key + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     best = kv > best ? kv : best;
                 }
 #pragma unroll
@@ -635,22 +659,22 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                     unsigned long long fin = wk[0];
                     for (int w2_ = 1; w2_ < nw; w2_++) fin = wk[w2_] > fin ? wk[w2_] : fin;
                     const int r = (fin >> 32) == 0ull ? 0 : (int) (0xFFFFFFFFu - (uint32_t) fin);
-                    int32_t *st = ga.pick.state;
-                    ga.pick.out[st[1]] = r;
-                    if (ga.pick.next_token) *ga.pick.next_token = r;
+                    int32_t *st = gc.pick.state;
+                    gc.pick.out[st[1]] = r;
+                    if (gc.pick.next_token) *gc.pick.next_token = r;
                     st[0] += 1; st[1] += 1;
-                    for (int sh = 0; sh < 8; sh++) __hip_atomic_store(ga.pick.count + sh * 16, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(ga.pick.count + 128, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    wk[14] = (unsigned long long) (r < ga.pick.n_vocab ? r : 0);
+                    for (int sh = 0; sh < 8; sh++) __hip_atomic_store(gc.pick.count + sh * 16, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(gc.pick.count + 128, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    wk[14] = (unsigned long long) (r < gc.pick.n_vocab ? r : 0);
                 }
                 __syncthreads();
             }
-            if (wk[15] != 0ull && ga.pick.emb) {
+            if (wk[15] != 0ull && gc.pick.emb) {
                 // the picked token's embedding row for the next step: k_embed_part's arithmetic, thread for thread (nw * 64 = 256 threads)
                 const int tok = (int) wk[14];
                 const int dE = K;
                 __syncthreads();
-                const uint8_t *row = ga.pick.emb + (size_t) tok * (dE / 32) * 20;
+                const uint8_t *row = gc.pick.emb + (size_t) tok * (dE / 32) * 20;
                 double s1 = 0.0, s2 = 0.0;
                 for (int i = tid; i < dE / 2; i += nw * 64) {
                     const int b = i >> 4, j = i & 15;
@@ -659,24 +683,24 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
                     const float dd = __builtin_bit_cast(float, bits);
                     const uint32_t q = blk_[4 + j];
                     const float v0 = (float) ((int) (q & 0xF) - 8) * dd, v1 = (float) ((int) (q >> 4) - 8) * dd;
-                    ga.pick.x_next[2 * i + 0] = v0;
-                    ga.pick.x_next[2 * i + 1] = v1;
+                    gc.pick.x_next[2 * i + 0] = v0;
+                    gc.pick.x_next[2 * i + 1] = v1;
                     s1 += (double) v0; s1 += (double) v1;
                     s2 += (double) v0 * (double) v0; s2 += (double) v1 * (double) v1;
                 }
-                s1 = block_sum_d(s1, red, 0);
-                s2 = block_sum_d(s2, red, 1);
+                s1 = block_sum_d(s1, red, 0, nw);
+                s2 = block_sum_d(s2, red, 1, nw);
                 if (tid == 0) {
-                    ((f64x2 *) ga.pick.part_next)[0] = f64x2{ s1, s2 };
-                    if (ga.pick.epoch) ga.pick.epoch[0] = next_epoch(ga.pick.epoch[0]);
+                    ((f64x2 *) gc.pick.part_next)[0] = f64x2{ s1, s2 };
+                    if (gc.pick.epoch) gc.pick.epoch[0] = next_epoch(gc.pick.epoch[0]);
                 }
             }
         } else
-        if (EPI == EPI_STORE_TAG) {                     // ga.sync -> the epoch word, ga.sync_epoch = layer (k_qkv_attn)
-            if (live) store_tagged((uint64_t *) y + m, acc, store_tag ^ ((ga.lut_math & 0x1000) ? 1u : 0u));      // (0x1000: fault-injection test -- a tag nobody waits for)
+        if (EPI == EPI_STORE_TAG) {                     // gh.epoch -> the epoch word, gh.layer = layer (k_qkv_attn)
+            if (live) store_tagged((uint64_t *) y + m, acc, store_tag ^ ((lut_math & 0x1000) ? 1u : 0u));      // (0x1000: fault-injection test -- a tag nobody waits for)
         } else if (EPI == EPI_RESID_TAG) {              // the row leaves for the next pipeline stage's mailbox (and / or plain)
             if (live) {
-                if (ga.out_t) store_tagged_sys(ga.out_t + m, __builtin_bit_cast(uint32_t, acc), tag_out ^ ((ga.lut_math & 0x2000) ? 1u : 0u));      // (0x2000: fault-injection test)
+                if (gc.out_t) store_tagged_sys(gc.out_t + m, __builtin_bit_cast(uint32_t, acc), tag_out ^ ((lut_math & 0x2000) ? 1u : 0u));      // (0x2000: fault-injection test)
                 if (y) y[m] = acc;
             }
         } else
@@ -718,9 +742,19 @@ __device__ __forceinline__ void gemv_body(const GemvArgs &ga, const int blk, con
 
 template <int PRE, int EPI, int D, bool RING, int PG>
 __global__ void __launch_bounds__(EPI == EPI_SILU_QA ? 512 : 256, EPI == EPI_SILU_QA ? 4 : 1)
-k_gemv(const GemvArgs ga) {
+k_gemv(const GemvHot gh) {
     extern __shared__ double smem_d[];
-    gemv_body<PRE, EPI, D, RING, PG>(ga, blockIdx.x, blockDim.x >> 6, smem_d);
+    gemv_entry(gh);
+    const GemvCold none = {};          // (no instance launched through this overload reads it: gemv_needs_cold)
+    gemv_body<PRE, EPI, D, RING, PG>(gh, none, blockIdx.x, gh.nw, smem_d);
+}
+// ... and the instances that take the cold block (gemv_needs_cold): the same name, one more parameter
+template <int PRE, int EPI, int D, bool RING, int PG>
+__global__ void __launch_bounds__(EPI == EPI_SILU_QA ? 512 : 256, EPI == EPI_SILU_QA ? 4 : 1)
+k_gemv(const GemvHot gh, const GemvCold gc) {
+    extern __shared__ double smem_d[];
+    gemv_entry(gh);
+    gemv_body<PRE, EPI, D, RING, PG>(gh, gc, blockIdx.x, gh.nw, smem_d);
 }
 
 
@@ -1335,24 +1369,38 @@ __device__ __forceinline__ float load_f32_sc1(const float *p) {
 #ifndef LH_ATTN_ABLATE
 #define LH_ATTN_ABLATE 0
 #endif
-struct AttnXArgs {
-    const float *qkv; int d, dh; const double *sincos_tab; float *Kc, *Vc, *sc; int n_ctx, nth; float kq_scale;
-    float *merged; uint32_t *qa_A; float *qa_d; const uint16_t *T_exp; const int32_t *st; uint32_t *sync, *fault; int lut_math;
-    // k_qkv_attn only: data-tagged hand-offs.  qkv2[3 d] / sc2[H][n_ctx] hold {fp32 bits, tag} 8-byte granules,
-    // tag = make_tag(epoch[0], layer + 1): a reader polls the granule itself until the tag is this launch's
-    const uint64_t *qkv2; uint64_t *sc2; const uint32_t *epoch; int layer;
+// Hot block of the attention launches, as GemvHot: one batch of scalar loads at entry (attn_entry).  What the score and the
+// soft_max . V roles read first -- the position word, the epoch word, the caches and tables -- sits at the front.
+struct alignas(64) AttnHot {
+    const int32_t *st;                                // st[0] = n_past
+    uint32_t *word;                                   // k_qkv_attn: the epoch word (tag = make_tag(word[0], layer + 1)); k_dec_attn_x: sync, [H][32] arrival counters
+    float *Kc, *Vc; const double *sincos_tab;
+    // k_dec_attn_x: qkv[3 d] / sc[H][n_ctx] fp32.  k_qkv_attn: data-tagged hand-offs, {fp32 bits, tag} 8-byte granules in the
+    // same shapes -- a reader polls the granule itself until the tag is this launch's
+    const void *qkv; void *sc;
+    const uint16_t *T_exp; float *merged; uint32_t *qa_A; float *qa_d; uint32_t *fault;
+    int n_ctx; float kq_scale; int lut_math;
+    int gridA;                                        // k_qkv_attn: workgroups of the mat-vec role (the first gridA blocks)
+    uint16_t d, dh, H, nth, layer;
 };
+static_assert(sizeof(AttnHot) <= 128 && alignof(AttnHot) == 64, "the hot block of a decode attention launch is two scalar-cache lines");
+__device__ __forceinline__ void attn_entry(const AttnHot &aa) {
+    asm volatile("" :: "s"(aa.st), "s"(aa.word), "s"(aa.Kc), "s"(aa.Vc), "s"(aa.sincos_tab), "s"(aa.qkv), "s"(aa.sc), "s"(aa.T_exp),
+                       "s"(aa.merged), "s"(aa.qa_A), "s"(aa.qa_d), "s"(aa.fault), "s"(aa.n_ctx), "s"(aa.kq_scale), "s"(aa.lut_math), "s"(aa.gridA),
+                       "s"((uint32_t) aa.d | ((uint32_t) aa.dh << 16)), "s"((uint32_t) aa.H | ((uint32_t) aa.nth << 16)), "s"((uint32_t) aa.layer));
+}
 // role of workgroup (h, yy): yy < ncb: soft_max . V for column block yy; else scores for key slice yy - ncb.
 // QKV_WAIT (k_qkv_attn): the head's q / k / v rows come from mat-vec workgroups of the SAME launch as tagged granules
 // (qkv2); the K rows of the slice are requested first, then the rotating threads poll their own q / k / v granules.  The
 // scores go to the soft_max . V workgroups as tagged granules too (sc2): no counters, no store-acknowledge wait, no
 // separate poll -- a hand-off is one store and one load that sees it.
 template <bool QKV_WAIT>
-__device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, const int yy, double *smem_d) {
-    const float *__restrict__ qkv = aa.qkv; const int d = aa.d, dh = aa.dh; const double *__restrict__ sincos_tab = aa.sincos_tab;
-    float *__restrict__ Kc = aa.Kc, *__restrict__ Vc = aa.Vc; float *sc = aa.sc; const int n_ctx = aa.n_ctx, nth = aa.nth; const float kq_scale = aa.kq_scale;
+__device__ __forceinline__ void attn_x_body(const AttnHot &aa, const int h, const int yy, double *smem_d) {
+    const float *__restrict__ qkv = (const float *) aa.qkv; const int d = aa.d, dh = aa.dh; const double *__restrict__ sincos_tab = aa.sincos_tab;
+    float *__restrict__ Kc = aa.Kc, *__restrict__ Vc = aa.Vc; float *sc = (float *) aa.sc; const int n_ctx = aa.n_ctx, nth = aa.nth; const float kq_scale = aa.kq_scale;
     float *__restrict__ merged = aa.merged; uint32_t *__restrict__ qa_A = aa.qa_A; float *__restrict__ qa_d = aa.qa_d;
-    const uint16_t *__restrict__ T_exp = aa.T_exp; const int32_t *__restrict__ st = aa.st; uint32_t *sync = aa.sync, *fault = aa.fault; const int lut_math = aa.lut_math;
+    const uint16_t *__restrict__ T_exp = aa.T_exp; const int32_t *__restrict__ st = aa.st; uint32_t *sync = aa.word, *fault = aa.fault; const int lut_math = aa.lut_math;
+    const uint64_t *qkv2 = (const uint64_t *) aa.qkv; uint64_t *sc2 = (uint64_t *) aa.sc;
     const int ncb = dh / 32, tid = threadIdx.x;
 #if LH_PHASE_PROBE == 3        /* timeline probe (tools/attn_timeline.py): kind 0xA0 = score workgroup, 0xA1 = soft_max . V workgroup */
     unsigned long long probe_t[5] = { 0, 0, 0, 0, 0 };
@@ -1366,7 +1414,9 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
 #define LH_AFLUSH(KIND) do { } while (0)
 #endif
     LH_ASTAMP(0);
+    // the two dependent scalar loads of the launch go out together, right behind the kernel arguments
     const int n_past = st[0];
+    const uint32_t epoch_ = QKV_WAIT ? __builtin_nontemporal_load(aa.word) : 0u;
     uint32_t *cnt = sync + h * 32;
     if (yy >= ncb) {
         // ---- score workgroup: keys [t0, t0 + 32)
@@ -1390,12 +1440,12 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
             }
         };
         const bool nowait = (lut_math & 0x1000) != 0;     // (fault-injection test: short poll bound)
-        const uint32_t tag = QKV_WAIT ? (make_tag(aa.epoch[0], aa.layer + 1)) : 0u;
+        const uint32_t tag = make_tag(epoch_, (int) aa.layer + 1);
         if (QKV_WAIT) load_keys();                              // in flight while the mat-vec workgroups finish
         if (tid < dh / 2) {
             const int e = 2 * tid;
             const double cs = tab[e], sn = tab[e + 1];
-            const uint64_t *q2 = aa.qkv2 + h * dh, *k2 = q2 + d, *v2 = q2 + 2 * d;
+            const uint64_t *q2 = qkv2 + h * dh, *k2 = q2 + d, *v2 = q2 + 2 * d;
             // the granules this thread needs -- 2 (q) or, in the workgroup whose slice holds the new key, 6 (q, k, v) -- are polled TOGETHER:
             // one look = all loads in flight at once, one L2 round trip (they used to be polled one after the other: six dependent
             // round trips in the one workgroup every soft_max . V workgroup of the head waits for)
@@ -1457,7 +1507,7 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
             }
             s = tree32_to_lane0(s);
             if (l == 0 && t <= n_past) {
-                if (QKV_WAIT) store_tagged(aa.sc2 + (size_t) h * n_ctx + t, s * kq_scale, tag);
+                if (QKV_WAIT) store_tagged(sc2 + (size_t) h * n_ctx + t, s * kq_scale, tag);
                 else sc[(size_t) h * n_ctx + t] = s * kq_scale;
             }
         }
@@ -1516,7 +1566,7 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
     const float *row = sc + (size_t) h * n_ctx;
     float mx = -INFINITY;
     if (QKV_WAIT) {
-        const uint32_t tag = make_tag(aa.epoch[0], aa.layer + 1);
+        const uint32_t tag = make_tag(epoch_, (int) aa.layer + 1);
         const bool nowait = (lut_math & 0x1000) != 0;
         // (a thread's granules, up to four at a time, are polled together: one round trip per look instead of one per granule)
 #if LH_ATTN_ABLATE == 2        /* measurement build, results wrong: the soft_max . V workgroups do not wait for the scores (bound of the hop + soft_max) */
@@ -1532,7 +1582,7 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
 #pragma unroll
                 for (int i = 0; i < 4; i++) {
                     const int t = t0 + i * nt;
-                    if (t < T) { g_[i] = __hip_atomic_load(aa.sc2 + (size_t) h * n_ctx + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && (uint32_t) (g_[i] >> 32) == tag; }
+                    if (t < T) { g_[i] = __hip_atomic_load(sc2 + (size_t) h * n_ctx + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = ok && (uint32_t) (g_[i] >> 32) == tag; }
                 }
                 if (ok) break;
                 __builtin_amdgcn_s_sleep(1);
@@ -1549,7 +1599,7 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
 #if LH_ATTN_ABLATE == 1 || LH_ATTN_ABLATE == 2      /* measurement build, results wrong: no soft_max arithmetic between the scores and the V*P chains (bound of every soft_max restructuring) */
     if (!QKV_WAIT) {
 #endif
-    mx = block_max_f(mx, red, 0);
+    mx = block_max_f(mx, red, 0, nt / 64);
     double sum = 0.0;
     for (int t = tid; t < T; t += nt) {
         const uint16_t xh = f2h_bits(p[t] - mx);
@@ -1557,7 +1607,7 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
         p[t] = e;
         sum += (double) e;
     }
-    sum = block_sum_d(sum, red, 1);
+    sum = block_sum_d(sum, red, 1, nt / 64);
     const float inv = (float) (1.0 / sum);
     for (int t = tid; t < T; t += nt) p[t] *= inv;
 #if LH_ATTN_ABLATE == 1 || LH_ATTN_ABLATE == 2
@@ -1627,8 +1677,9 @@ __device__ __forceinline__ void attn_x_body(const AttnXArgs &aa, const int h, co
 #undef LH_AFLUSH
 
 __global__ void __launch_bounds__(256)
-k_dec_attn_x(const AttnXArgs aa) {
+k_dec_attn_x(const AttnHot aa) {
     extern __shared__ double smem_d[];
+    attn_entry(aa);
     attn_x_body<false>(aa, blockIdx.x, blockIdx.y, smem_d);
 }
 
@@ -1643,24 +1694,42 @@ k_dec_attn_x(const AttnXArgs aa) {
 //  from a plain buffer, one launch per stage step -- needs ~20 registers more and gets one wave less instead of spilling them
 //  (tools/kernel_scratch_report.py).  The mailbox prologue PREP_NORM_TAG keeps 4 / 3 and its few spilled registers: its workgroups WAIT for
 //  another stage's row, and when stages share one GPU (tests, one-GPU smoke runs) the fewer slots they hold while waiting the better.)
+#define LH_QKV_ATTN_OCC __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE == PREP_NORM ? (PG == 1 ? 3 : 2) : (PG == 1 ? 4 : 3))))
 template <int PRE, int D, int PG>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRE == PREP_NORM ? (PG == 1 ? 3 : 2) : (PG == 1 ? 4 : 3))))
-k_qkv_attn(const GemvArgs ga, const AttnXArgs aa, const int gridA, const int H) {
-    extern __shared__ double smem_d[];
+__device__ __forceinline__ void qkv_attn_body(const AttnHot &aa, const GemvHot &gh, const GemvCold &gc, double *smem_d) {
+    // both hot blocks in one batch, before the role is known: the role needs gridA, and a second batch behind that branch would be
+    // a second round trip
+    attn_entry(aa);
+    gemv_entry(gh);
     const int b = blockIdx.x;
-    if (b < gridA) {
+    if (b < aa.gridA) {
         const int ncb = aa.dh / 32, wph = 3 * ncb;
         // (round 5 measured the other dispatch order -- the q and k row-groups of every head of an XCD before any v row-group: a head's score
         //  chain needs q and k, only its last V*P chain needs v -- and found no difference, 14.97 against 14.99 us per launch:
         //  profiles/r05_m_qkv_order_ab.txt; the switch is gone)
         const int xcd = b & 7, slot = b >> 3, j = slot / wph, part = slot % wph, mat = part / ncb, sub = part % ncb;
         const int h = xcd + 8 * j;
-        gemv_body<PRE, EPI_STORE_TAG, D, true, PG>(ga, mat * (aa.d / 32) + h * ncb + sub, 4, smem_d);    // y = tagged granules
+        gemv_body<PRE, EPI_STORE_TAG, D, true, PG>(gh, gc, mat * (aa.d / 32) + h * ncb + sub, 4, smem_d);    // y = tagged granules
         return;
     }
-    const int a = b - gridA, h = a % H, y = a / H;            // y < dh / 32: soft_max . V (their V prefetch starts with the mat-vec), then the score slices
+    const int H = aa.H, a = b - aa.gridA, h = a % H, y = a / H;            // y < dh / 32: soft_max . V (their V prefetch starts with the mat-vec), then the score slices
     attn_x_body<true>(aa, h, y, smem_d);
 }
+template <int PRE, int D, int PG>
+__global__ void LH_QKV_ATTN_OCC
+k_qkv_attn(const AttnHot aa, const GemvHot gh) {
+    extern __shared__ double smem_d[];
+    const GemvCold none = {};
+    qkv_attn_body<PRE, D, PG>(aa, gh, none, smem_d);
+}
+// ... the mailbox prologue (PREP_NORM_TAG) takes the cold block as well
+template <int PRE, int D, int PG>
+__global__ void LH_QKV_ATTN_OCC
+k_qkv_attn(const AttnHot aa, const GemvHot gh, const GemvCold gc) {
+    extern __shared__ double smem_d[];
+    qkv_attn_body<PRE, D, PG>(aa, gh, gc, smem_d);
+}
+#undef LH_QKV_ATTN_OCC
 
 // load-time self-test of the assumption above: out[b] = XCC_ID of workgroup b of a (H, Y) grid
 __global__ void k_xcd_selftest(uint32_t *out) {
@@ -1903,23 +1972,29 @@ GemvPlan gemv_plan(const QMat &w, int pre, int epi) {
 }
 
 // The instances of k_gemv<PRE, EPI, ., ., PG>: run-time (ring depth, ring or whole row in flight) -> the kernel, null where there is none
-using GemvKernel = void (*)(const GemvArgs);
+// (a kernel's address; which of the two overloads it is -- with or without the cold block -- is gemv_needs_cold(pre, epi))
+using GemvKernel = const void *;
+template <int PRE, int EPI, int D, bool RING, int PG>
+static GemvKernel gemv_instance() {
+    if constexpr (gemv_needs_cold(PRE, EPI)) return (const void *) (void (*)(const GemvHot, const GemvCold)) k_gemv<PRE, EPI, D, RING, PG>;
+    else return (const void *) (void (*)(const GemvHot)) k_gemv<PRE, EPI, D, RING, PG>;
+}
 template <int PRE, int EPI, int PG>
 static GemvKernel gemv_kernel_at(int depth, bool ring) {
     constexpr bool ALL = EPI != EPI_STORE_PICK && EPI != EPI_SILU_QAH;      // (those two: rings only, the shallow ones)
     if (!ring) {
-        if constexpr (ALL) if (depth == 16) return k_gemv<PRE, EPI, 16, false, PG>;
+        if constexpr (ALL) if (depth == 16) return gemv_instance<PRE, EPI, 16, false, PG>();
         return nullptr;
     }
-    if (depth == 4) return k_gemv<PRE, EPI, 4, true, PG>;
+    if (depth == 4) return gemv_instance<PRE, EPI, 4, true, PG>();
     if constexpr (EPI != EPI_SILU_QAH) {
-        if (depth == 8) return k_gemv<PRE, EPI, 8, true, PG>;
-        if (depth == 10) return k_gemv<PRE, EPI, 10, true, PG>;
+        if (depth == 8) return gemv_instance<PRE, EPI, 8, true, PG>();
+        if (depth == 10) return gemv_instance<PRE, EPI, 10, true, PG>();
         if constexpr (ALL) {
-            if (depth == 14) return k_gemv<PRE, EPI, 14, true, PG>;
-            if (depth == 16) return k_gemv<PRE, EPI, 16, true, PG>;
-            if (depth == 18) return k_gemv<PRE, EPI, 18, true, PG>;
-            if (depth == 22) return k_gemv<PRE, EPI, 22, true, PG>;
+            if (depth == 14) return gemv_instance<PRE, EPI, 14, true, PG>();
+            if (depth == 16) return gemv_instance<PRE, EPI, 16, true, PG>();
+            if (depth == 18) return gemv_instance<PRE, EPI, 18, true, PG>();
+            if (depth == 22) return gemv_instance<PRE, EPI, 22, true, PG>();
         }
     }
     return nullptr;
@@ -1966,8 +2041,8 @@ bool norm_mode_resolve(int *pre, NormPart *np) {
     return norm_mode >= 2;
 }
 
-// Every launcher of k_gemv: `ga` arrives with the operands; the statistics, the mailbox, the matrix and the plan are filled in here
-static hipError_t launch_gemv_plan(const QMat &w, int pre, int epi, const NormPart *npp, const MailboxIO *mb, GemvArgs ga, hipStream_t st) {
+// Every launcher of k_gemv: `gh` / `gc` arrive with the operands; the statistics, the mailbox, the matrix and the plan are filled in here
+static hipError_t launch_gemv_plan(const QMat &w, int pre, int epi, const NormPart *npp, const MailboxIO *mb, GemvHot gh, GemvCold gc, hipStream_t st) {
     NormPart np = npp ? *npp : NormPart();
     norm_mode_resolve(&pre, &np);
     if (mb) {
@@ -1976,16 +2051,20 @@ static hipError_t launch_gemv_plan(const QMat &w, int pre, int epi, const NormPa
         if (mb->in_t && (pre == PREP_NORM || pre == PREP_NORMP) && epi == EPI_STORE) pre = PREP_NORM_TAG;
         else if ((mb->resid_t || mb->out_t) && pre == PRE_QA && epi == EPI_RESID) epi = EPI_RESID_TAG;
         else return hipErrorInvalidValue;
-        ga.in_t = mb->in_t; ga.resid_t = mb->resid_t; ga.out_t = mb->out_t;
-        ga.pos_w = mb->pos_w; ga.patience = 3; ga.fault = mb->fault; ga.sync = mb->epoch; ga.lut_math = mb->test_bits;
+        gc.in_t = mb->in_t; gc.resid_t = mb->resid_t; gc.out_t = mb->out_t;
+        gc.pos_w = mb->pos_w; gc.patience = 3; gc.fault = mb->fault; gh.epoch = mb->epoch; gh.lut_math = mb->test_bits;
     }
     const GemvPlan p = gemv_plan(w, pre, epi);
     const GemvKernel k = gemv_kernel(pre, epi, p);
     if (!p.nw || !k || (np.out && p.grid > NORM_PART_MAX)) return hipErrorInvalidValue;
-    ga.wt = w.tiles; ga.ngroups = w.ngroups; ga.nchunks = w.nchunks; ga.M = w.M; ga.gmapF8 = w.gmapF8; ga.K = w.K;
-    ga.part_in = (const f64x2 *) np.in; ga.npart = np.n_in; ga.part_out = (f64x2 *) np.out;
-    ga.lut_math |= g_lut_math;
-    hipLaunchKernelGGL(k, dim3(p.grid), dim3(p.nw * 64), p.lds, st, ga);
+    gh.wt = w.tiles; gh.ngroups = w.ngroups; gh.nchunks = w.nchunks; gh.M = w.M; gh.gmapF8 = w.gmapF8; gh.K = w.K;
+    gh.part_in = (const f64x2 *) np.in; gh.npart = np.n_in; gh.part_out = (f64x2 *) np.out;
+    gh.lut_math |= g_lut_math;
+    gh.nw = (uint16_t) p.nw;
+    gc.nwg = p.grid;
+    void *args[] = { &gh, &gc };          // (the overload without the cold block has one parameter and takes the first alone)
+    const hipError_t le = hipLaunchKernel(k, dim3(p.grid), dim3(p.nw * 64), args, p.lds, st);
+    if (le != hipSuccess) return le;
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
@@ -1995,18 +2074,20 @@ hipError_t launch_gemv(const QMat &w, int pre, int epi, const uint32_t *qa_A, co
                        const uint16_t *T_silu,
                        uint32_t *out_A, float *out_d, hipStream_t st, const NormPart *np, const MailboxIO *mb) {
     if (pre == PREP_NORM_TAG || epi >= EPI_STORE_TAG) return hipErrorInvalidValue;      // (selected by a mailbox / launchers of their own)
-    GemvArgs ga = {};
-    ga.qa_A = qa_A; ga.qa_d = qa_d; ga.in0 = in0; ga.in1 = in1; ga.y = y; ga.resid = resid; ga.T_silu = T_silu; ga.out_A = out_A; ga.out_d = out_d;
-    return launch_gemv_plan(w, pre, epi, np, mb, ga, st);
+    GemvHot gh = {};
+    if (pre == PRE_QA) { gh.op0 = qa_A; gh.op1 = qa_d; } else { gh.op0 = in0; gh.op1 = in1; }
+    gh.y = y; gh.resid = resid; gh.T_silu = T_silu; gh.out_A = out_A; gh.out_d = out_d;
+    return launch_gemv_plan(w, pre, epi, np, mb, gh, GemvCold{}, st);
 }
 
 // the lm head with the pick epilogue (EPI_STORE_PICK, llamahip_internal.h)
 bool gemv_pick_applies(const QMat &w) { return gemv_plan(w, PREP_NORM, EPI_STORE_PICK).nw != 0; }
 hipError_t launch_gemv_pick(const QMat &w, const float *in0, const float *in1, float *y, const uint16_t *T_silu, hipStream_t st,
                             const NormPart *np, const PickIO &pick) {
-    GemvArgs ga = {};
-    ga.in0 = in0; ga.in1 = in1; ga.y = y; ga.T_silu = T_silu; ga.pick = pick;
-    return launch_gemv_plan(w, PREP_NORM, EPI_STORE_PICK, np, nullptr, ga, st);      // (the caller checks gemv_pick_applies)
+    GemvHot gh = {};
+    GemvCold gc = {};
+    gh.op0 = in0; gh.op1 = in1; gh.y = y; gh.T_silu = T_silu; gc.pick = pick;
+    return launch_gemv_plan(w, PREP_NORM, EPI_STORE_PICK, np, nullptr, gh, gc, st);      // (the caller checks gemv_pick_applies)
 }
 // w1|w3 in half-block workgroups (EPI_SILU_QAH, llamahip_internal.h)
 // (QUARTER-block workgroups of two waves -- VERDICT r04 item 4c: 13B's 432 blocks would go from max / mean 1.19 to 1.04 workgroups per CU --
@@ -2028,10 +2109,11 @@ bool gemv_silu_half_applies(const QMat &w) {
 hipError_t launch_gemv_silu_half(const QMat &w, const float *in0, const float *in1, const uint16_t *T_silu, uint32_t *out_A, float *out_d, hipStream_t st,
                                  const NormPart *np, uint64_t *amax_t, uint32_t *epoch, int layer, uint32_t *fault) {
     static const int fault_test = (getenv("LLAMAHIP_HANDOFF_FAULT_TEST") && atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) == 6) ? 0x1000 : 0;
-    GemvArgs ga = {};
-    ga.in0 = in0; ga.in1 = in1; ga.T_silu = T_silu; ga.out_A = out_A; ga.out_d = out_d;
-    ga.sync = epoch; ga.sync_epoch = layer; ga.lut_math = fault_test; ga.fault = fault; ga.out_t = amax_t;
-    return launch_gemv_plan(w, PREP_NORM, EPI_SILU_QAH, np, nullptr, ga, st);      // (the caller checks gemv_silu_half_applies)
+    GemvHot gh = {};
+    GemvCold gc = {};
+    gh.op0 = in0; gh.op1 = in1; gh.T_silu = T_silu; gh.out_A = out_A; gh.out_d = out_d;
+    gh.epoch = epoch; gh.layer = (uint16_t) layer; gh.lut_math = fault_test; gc.fault = fault; gh.amax_t = amax_t;
+    return launch_gemv_plan(w, PREP_NORM, EPI_SILU_QAH, np, nullptr, gh, gc, st);      // (the caller checks gemv_silu_half_applies)
 }
 
 // Short prompt chunk (see k_decn_scores): scores -> soft_max + V*P + ordered combine + Q4_0 quantization of the
@@ -2112,7 +2194,10 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
     // (contexts beyond 1 024: the score slices no longer fit the chip next to the waiting workgroups at this kernel's 4 waves per
     //  SIMD -- 525 against 570 tokens/s at context 1 024, 429 against 481 at 2 048 on the 7B -- the two launches below take over)
     if (p.kernel == DEC_ATTN_X) {
-        const AttnXArgs aa = { qkv, d, dh, tab, Kc, Vc, sc, n_ctx, nth, kq_scale, merged, qa_A, qa_d, T_exp, state, xsync, fault, g_lut_math, nullptr, nullptr, nullptr, 0 };
+        AttnHot aa = {};
+        aa.st = state; aa.word = xsync; aa.Kc = Kc; aa.Vc = Vc; aa.sincos_tab = tab; aa.qkv = qkv; aa.sc = sc; aa.T_exp = T_exp;
+        aa.merged = merged; aa.qa_A = qa_A; aa.qa_d = qa_d; aa.fault = fault; aa.n_ctx = n_ctx; aa.kq_scale = kq_scale; aa.lut_math = g_lut_math;
+        aa.d = (uint16_t) d; aa.dh = (uint16_t) dh; aa.H = (uint16_t) H; aa.nth = (uint16_t) nth;
         hipLaunchKernelGGL(k_dec_attn_x, dim3(p.gx, p.gy), dim3(p.threads), p.lds, st, aa);
         LH_LAUNCH_CHECK();
         return hipSuccess;
@@ -2135,12 +2220,17 @@ hipError_t launch_dec_attn(const float *qkv, int d, int H, int n_ctx, int nth, c
 // wq|wk|wv mat-vec + decode attention in ONE launch (k_qkv_attn).  Its mat-vec role is gemv_plan's answer for (PREP_NORM, EPI_STORE) where
 // that is a 4-wave ring of (ring depth, granules per thread) = (8, 1) [7B], (10, 2) [13B], (4, 2) [30B, 65B] -- the instances below; other
 // shapes (the whole-row-in-flight variant of small models among them) keep the separate launches.
-using QkvAttnKernel = void (*)(const GemvArgs, const AttnXArgs, const int, const int);
+using QkvAttnKernel = const void *;      // (as GemvKernel: the overload with the cold block where gemv_needs_cold(pre, EPI_STORE_TAG))
+template <int PRE, int D, int PG>
+static QkvAttnKernel qkv_attn_instance_at() {
+    if constexpr (gemv_needs_cold(PRE, EPI_STORE_TAG)) return (const void *) (void (*)(const AttnHot, const GemvHot, const GemvCold)) k_qkv_attn<PRE, D, PG>;
+    else return (const void *) (void (*)(const AttnHot, const GemvHot)) k_qkv_attn<PRE, D, PG>;
+}
 template <int PRE>
 static QkvAttnKernel qkv_attn_kernel_at(int depth, int pg) {
-    if (depth == 8 && pg == 1) return k_qkv_attn<PRE, 8, 1>;
-    if (depth == 10 && pg == 2) return k_qkv_attn<PRE, 10, 2>;
-    if (depth == 4 && pg == 2) return k_qkv_attn<PRE, 4, 2>;
+    if (depth == 8 && pg == 1) return qkv_attn_instance_at<PRE, 8, 1>();
+    if (depth == 10 && pg == 2) return qkv_attn_instance_at<PRE, 10, 2>();
+    if (depth == 4 && pg == 2) return qkv_attn_instance_at<PRE, 4, 2>();
     return nullptr;
 }
 static QkvAttnKernel qkv_attn_kernel(int pre, int depth, int pg) {
@@ -2183,16 +2273,24 @@ hipError_t launch_qkv_attn(const QMat &w, const float *x, const float *norm_w, c
     const int dh = d / H, gridA = p.grid;
     const float kq_scale = 1.0f / sqrtf((float) d / (float) H);          // .mm:620
     const QkvAttnGeom g = qkv_attn_geom(p.grid, p.lds, d, H, n_ctx, nth);
-    // the mat-vec role writes tagged granules: y -> qkv2, sync -> the epoch word, sync_epoch = layer
+    // the mat-vec role writes tagged granules: y -> qkv2, tags of (the epoch word, layer)
     // test only (tests/test_gpu_parity.py): the mat-vec role publishes a wrong tag and every poll gives up after 256 looks -> the
     // sticky fault word must come back as an error
     static const int fault_test = (getenv("LLAMAHIP_HANDOFF_FAULT_TEST") && atoi(getenv("LLAMAHIP_HANDOFF_FAULT_TEST")) < 2) ? 0x1000 : 0;     // (2: the wo launch of the overlapped schedule misbehaves instead)
-    GemvArgs ga = { w.tiles, w.ngroups, w.nchunks, w.M, w.gmapF8, nullptr, nullptr, x, norm_w, w.K, (float *) qkv2, nullptr, T_silu, nullptr, nullptr,
-                    (const f64x2 *) np.in, np.n_in, nullptr, epoch, 0, layer, g_lut_math | fault_test, fault };
-    if (x_t) { ga.in_t = x_t; ga.slot_in = 0; ga.pos_w = mb->pos_w; ga.patience = 3; ga.lut_math |= mb->test_bits; }
-    const AttnXArgs aa = { nullptr, d, dh, tab, Kc, Vc, nullptr, n_ctx, nth, kq_scale, merged, qa_A, qa_d, T_exp, state, nullptr, fault, g_lut_math | fault_test,
-                           qkv2, sc2, epoch, layer };
-    hipLaunchKernelGGL(k, dim3(g.grid), dim3(256), g.lds, st, ga, aa, gridA, H);
+    GemvHot gh = {};
+    GemvCold gc = {};
+    gh.wt = w.tiles; gh.ngroups = w.ngroups; gh.nchunks = w.nchunks; gh.M = w.M; gh.gmapF8 = w.gmapF8; gh.K = w.K;
+    gh.op0 = x; gh.op1 = norm_w; gh.y = (float *) qkv2; gh.T_silu = T_silu;
+    gh.part_in = (const f64x2 *) np.in; gh.npart = np.n_in; gh.epoch = epoch; gh.layer = (uint16_t) layer; gh.nw = 4;
+    gh.lut_math = g_lut_math | fault_test; gc.fault = fault;
+    if (x_t) { gc.in_t = x_t; gc.slot_in = 0; gc.pos_w = mb->pos_w; gc.patience = 3; gh.lut_math |= mb->test_bits; }
+    AttnHot aa = {};
+    aa.st = state; aa.word = epoch; aa.Kc = Kc; aa.Vc = Vc; aa.sincos_tab = tab; aa.qkv = qkv2; aa.sc = sc2; aa.T_exp = T_exp;
+    aa.merged = merged; aa.qa_A = qa_A; aa.qa_d = qa_d; aa.fault = fault; aa.n_ctx = n_ctx; aa.kq_scale = kq_scale; aa.lut_math = g_lut_math | fault_test;
+    aa.gridA = gridA; aa.d = (uint16_t) d; aa.dh = (uint16_t) dh; aa.H = (uint16_t) H; aa.nth = (uint16_t) nth; aa.layer = (uint16_t) layer;
+    void *args[] = { &aa, &gh, &gc };          // (the overload without the cold block takes the first two)
+    const hipError_t le = hipLaunchKernel(k, dim3(g.grid), dim3(256), args, g.lds, st);
+    if (le != hipSuccess) return le;
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }

@@ -154,9 +154,10 @@ __device__ __forceinline__ float max_lanes_0_31(float v) {
 // block-wide sums / max; `red` is LDS scratch of >= 32 doubles.  All threads get the result.
 // Successive calls alternate between the two halves of `red`, so one barrier per call suffices
 // (a slot is rewritten only two calls later, after every wave passed the barrier in between).
-static __device__ double block_sum_d(double v, double *red, int phase = 0) {
+// (the overloads with `nw`: the caller knows its waves per workgroup, and blockDim.x, a hidden kernel argument, is not fetched)
+static __device__ double block_sum_d(double v, double *red, int phase, int nw) {
     v = wave_sum_d(v);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const int w = threadIdx.x >> 6;
     double *r = red + (phase & 1) * 16;
     if ((threadIdx.x & 63) == 0) r[w] = v;
     __syncthreads();
@@ -164,11 +165,12 @@ static __device__ double block_sum_d(double v, double *red, int phase = 0) {
     for (int i = 0; i < nw; i++) s += r[i];
     return s;
 }
+static __device__ double block_sum_d(double v, double *red, int phase = 0) { return block_sum_d(v, red, phase, (int) (blockDim.x + 63) >> 6); }
 // two sums with one barrier (at most 8 waves: 16 doubles per phase)
-static __device__ void block_sum_d2(double &a, double &b, double *red, int phase = 0) {
+static __device__ void block_sum_d2(double &a, double &b, double *red, int phase, int nw) {
     a = wave_sum_d(a);
     b = wave_sum_d(b);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const int w = threadIdx.x >> 6;
     double *r = red + (phase & 1) * 16;
     if ((threadIdx.x & 63) == 0) { r[2 * w] = a; r[2 * w + 1] = b; }
     __syncthreads();
@@ -176,9 +178,10 @@ static __device__ void block_sum_d2(double &a, double &b, double *red, int phase
     for (int i = 0; i < nw; i++) { sa += r[2 * i]; sb += r[2 * i + 1]; }
     a = sa; b = sb;
 }
-static __device__ float block_max_f(float v, double *red, int phase = 0) {
+static __device__ void block_sum_d2(double &a, double &b, double *red, int phase = 0) { block_sum_d2(a, b, red, phase, (int) (blockDim.x + 63) >> 6); }
+static __device__ float block_max_f(float v, double *red, int phase, int nw) {
     v = wave_max_f(v);
-    const int w = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+    const int w = threadIdx.x >> 6;
     float *r = (float *) (red + (phase & 1) * 16);
     if ((threadIdx.x & 63) == 0) r[w] = v;
     __syncthreads();
@@ -186,6 +189,7 @@ static __device__ float block_max_f(float v, double *red, int phase = 0) {
     for (int i = 1; i < nw; i++) s = fmaxf(s, r[i]);
     return s;
 }
+static __device__ float block_max_f(float v, double *red, int phase = 0) { return block_max_f(v, red, phase, (int) (blockDim.x + 63) >> 6); }
 
 // ------------------------------------------------------------------------------------------------
 // activation preparation: [norm * weight | silu(gate) * up | plain]  ->  Q4_0 activation operands
