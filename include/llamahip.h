@@ -1068,7 +1068,8 @@ int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const flo
  * state word) + k_dec_pv_blk<false> (N = 1); _DEC_STREAM k_dec_scores + k_dec_pv_stream with one workgroup per column block (N = 1).
  * A path that cannot take the shape is refused with a message naming the limit, before anything is launched.  *path_taken (may be NULL):
  * the path that ran.  Not covered here: the kernels with cross-workgroup hand-offs (k_dec_attn_x, k_dec_pv_dma, k_dec_pv_stream split
- * over workgroups: llamahip_op_dec_attention; k_qkv_attn: llamahip_op_qkv_attn) and the batched decode step's form of the short path. */
+ * over workgroups: llamahip_op_dec_attention; k_qkv_attn: llamahip_op_qkv_attn).  The batched decode step's form of the short path (a
+ * SeqSet: positions on the device, one cache per row) is llamahip_op_set_attention's. */
 #define LLAMAHIP_ATTN_AUTO       0
 #define LLAMAHIP_ATTN_MFMA       1
 #define LLAMAHIP_ATTN_ROW        2
@@ -1235,6 +1236,55 @@ int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t
  * the decode step's k_embed_part, which also leaves {sum x, sum x^2} of the row in stats[0 .. 1]. */
 int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, int32_t V, int32_t d, float *x, int32_t x_stride,
                       double *stats, char *err, size_t err_cap);
+/* The attention of a BATCHED decode step (forward_set / forward_dense_set: llamahip_stage_step_set, the multi-sequence decoders, the verify
+ * steps over a set, the request scheduler) on caller-supplied operands: B rows (2 .. 16), each the next token of its own sequence.
+ * qkv [B][3d] un-rotated; Kc, Vc [n_slots][n_ctx][d], copied whole both ways; row r appends at position row_pos[r] of slot row_slot[r] and
+ * sees keys 0 .. row_pos[r] of that slot, split over n_threads (1 .. 32) as its own one-row eval splits them.  The op builds a device
+ * SeqSet: state[r] points at the row's {position, step} pair inside a pool (the pairs are NOT in row order), kv_off[r] = row_slot[r] n_ctx d,
+ * pos[r] starts wrong; then, as a step: k_rows_set (gather, on dummy rows) fills pos[], k_rope_kv_set rotates and appends, and
+ * launch_attn_short runs k_decn_scores + k_dec_pv_blk<true> with the set and set_keys (0: n_ctx; else the score grid is cut there and
+ * every row_pos must lie below it).  The score scratch [16][H][n_ctx] starts filled with the word score_fill, the operand buffers as 0xFF.
+ * merged [B][merged_stride] (copied whole both ways) or NULL -- the launch then gets a null merged, as on Q4_0 handles --; wo_operand
+ * [B][d/32] Q4_0 blocks or NULL.  After the launch the op fails, naming the row, if the operand blocks that pad d up to a multiple of
+ * 256 are not all zero or a state word changed.  Refused on the host with the limit named, before any device is looked for: head sizes
+ * that are no multiple of 32 or above 256, n_threads outside 1 .. 32, B outside 2 .. 16, set_keys outside 0 .. n_ctx, slots and positions
+ * outside their range, a row at or beyond set_keys, two rows on one (slot, position), rows of one slot that are not ONE run of
+ * consecutive ascending positions in adjacent rows (a drafted segment: each row sees the key its neighbour appended in the same step). */
+int llamahip_op_set_attention(const float *qkv, int32_t B, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
+                              const int32_t *row_slot, const int32_t *row_pos, int32_t n_threads, int32_t set_keys,
+                              float *merged, int32_t merged_stride, void *wo_operand, uint32_t score_fill, char *err, size_t err_cap);
+/* The FIRST launch of a batched decode step on caller-supplied rows.  mode: _EMBED_Q4_0 k_embed_set, _EMBED_F16 / _EMBED_F32
+ * k_embed_dense_set (emb [V][d] in file layout: Q4_0 blocks, fp16 or fp32), _ROWS k_rows_set gathering hid_in [B][d].  tokens [B] in
+ * [0, V) (embed modes), row_pos [B] >= 0.  Every row's token word, {position, step} pair (step 7 + 3 r) and hid_in row lives at its own
+ * scattered address inside ONE device pool whose other words are 0xFF; the descriptor's pos[] starts wrong.  epoch_in: the epoch word
+ * before the launch; pass_epoch != 0 hands the word to the launch (_EMBED_Q4_0 and _ROWS only: the dense kernels take none).
+ * x [B][x_stride] copied whole both ways (columns >= d keep the caller's bits; the kernels write dense [B][d] rows followed by a guard the
+ * op checks).  Out: pos_out [16] the descriptor's pos[] after the launch (entries >= B must keep their 0x7F7F7F7F), *epoch_out the epoch
+ * word, state_out [B][2] the rows' state words, *pool_changed whether any other word of the pool, of the descriptor or around the epoch
+ * word changed.  B 2 .. 16, d a multiple of 32; refused on the host before any device is looked for. */
+#define LLAMAHIP_SET_ENTRY_EMBED_Q4_0 0
+#define LLAMAHIP_SET_ENTRY_EMBED_F16  1
+#define LLAMAHIP_SET_ENTRY_EMBED_F32  2
+#define LLAMAHIP_SET_ENTRY_ROWS       3
+int llamahip_op_set_entry(int32_t mode, const void *emb, int32_t V, int32_t d, const int32_t *tokens, const float *hid_in, int32_t B,
+                          const int32_t *row_pos, uint32_t epoch_in, int32_t pass_epoch, float *x, int32_t x_stride,
+                          int32_t *pos_out, uint32_t *epoch_out, int32_t *state_out, int32_t *pool_changed, char *err, size_t err_cap);
+/* The LAST launches of a batched decode step on caller-supplied rows.  mode: _ARGMAX k_argmax_set on logits [B][V]; _ROWS_OUT k_rows_set
+ * scattering x [B][d] to the rows' hid_out, then k_advance_set; _ARGMAX_ONE k_argmax with a state pointer and no mailbox (B = 1: the
+ * kernel k_argmax_set is a copy of).  Row r's state pair starts as {row_pos[r], row_step[r]} (row_step in [0, n_ctx)); its tok_out
+ * pointer is null where tok_out_null[r] != 0.  State pairs, pick words, trace rows and hid_out rows are scattered inside one device pool
+ * whose other words (the guards between the hid_out rows among them) are 0xFF: the op fails if any of those changed.
+ * trace [B][n_ctx] copied whole both ways (the picks go to trace[r][row_step[r]]); tok_out [B] the pick words (-1 where nothing was
+ * written), hid_out [B][d], state_out [B][2] after the launch.  Refused on the host before any device is looked for. */
+#define LLAMAHIP_SET_EXIT_ARGMAX     0
+#define LLAMAHIP_SET_EXIT_ROWS_OUT   1
+#define LLAMAHIP_SET_EXIT_ARGMAX_ONE 2
+int llamahip_op_set_exit(int32_t mode, const float *logits, int32_t V, const float *x, int32_t d, int32_t B, int32_t n_ctx,
+                         const int32_t *row_pos, const int32_t *row_step, const int32_t *tok_out_null,
+                         int32_t *trace, int32_t *tok_out, float *hid_out, int32_t *state_out, char *err, size_t err_cap);
+/* Host only: the key bucket of a batched decode step whose highest row position is max_pos -- the set_keys its score launch is cut at:
+ * min(n_ctx, (max_pos / 128 + 1) * 128), so max_pos < set_keys <= n_ctx.  -1 for n_ctx < 1 or max_pos outside [0, n_ctx). */
+int32_t llamahip_debug_set_keys(int32_t n_ctx, int32_t max_pos);
 /* runtime activation quantizer (ggml.c:456-523): x[k] -> k/32 blocks of 20 bytes */
 int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap);
 

@@ -204,6 +204,11 @@ def lib() -> C.CDLL:
     L.llamahip_op_prompt_gemm_q4_0.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
     L.llamahip_op_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, i32, i32, vp, i32, vp, vp, cp, sz]
     L.llamahip_op_attention_rows.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, vp, cp, sz]
+    L.llamahip_op_set_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, vp, i32, vp, C.c_uint32, cp, sz]
+    L.llamahip_op_set_entry.argtypes = [i32, vp, i32, i32, vp, vp, i32, vp, C.c_uint32, i32, vp, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_op_set_exit.argtypes = [i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_debug_set_keys.argtypes = [i32, i32]
+    L.llamahip_debug_set_keys.restype = i32
     L.llamahip_op_dec_attention.argtypes = [vp, i32, vp, vp, vp, C.c_uint32, i32, i32, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
     L.llamahip_debug_dec_attn_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, vp, cp, sz]
     L.llamahip_debug_dec_attn_plan.restype = i32
@@ -1665,6 +1670,108 @@ def op_attention_rows(qkv: np.ndarray, H: int, Kc: np.ndarray, Vc: np.ndarray, r
                                           _ptr(tab[2]), int(n_threads), _ptr(merged), ms, _ptr(wo), err, len(err))
     _check(rc, err)
     return merged, wo
+
+
+def debug_set_keys(n_ctx: int, max_pos: int) -> int | None:
+    """Host-only: the key bucket (set_keys) of a batched decode step whose highest row position is max_pos (llamahip_debug_set_keys);
+    None where the arguments are refused."""
+    r = lib().llamahip_debug_set_keys(int(n_ctx), int(max_pos))
+    return None if r < 0 else r
+
+
+def op_set_attention(qkv: np.ndarray, H: int, Kc: np.ndarray, Vc: np.ndarray, row_slot, row_pos, n_threads: int = 8, set_keys: int = 0,
+                     merged_stride: int | None = None, merged_init=None, want_merged: bool = True, want_wo: bool = True, score_fill: int = 0xFFFFFFFF):
+    """The attention of a batched decode step (llamahip_op_set_attention): qkv f32 [B, 3d] un-rotated, Kc / Vc f32 [n_slots, n_ctx, d]
+    (updated in place).  want_merged False: the launch gets a null merged (Q4_0 handles).  Returns (merged f32 [B, merged_stride] or None,
+    the wo operand uint8 [B, d/32, 20] or None)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    B, d3 = qkv.shape
+    d = d3 // 3
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 3 or a.shape[2] != d or a.shape != Kc.shape:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_slots, n_ctx, d]")
+    tab = [np.ascontiguousarray(a, np.int32).ravel() for a in (row_slot, row_pos)]
+    if any(a.size != B for a in tab):
+        raise ValueError(f"op_set_attention: the table must have B = {B} entries")
+    ms = d if merged_stride is None else int(merged_stride)
+    merged = None
+    if want_merged:
+        merged = np.full((B, ms), np.nan, np.float32) if merged_init is None else np.array(merged_init, np.float32, order="C").reshape(B, ms)
+    wo = np.full((B, max(d // 32, 1), 20), 0xEE, np.uint8) if want_wo else None
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_set_attention(_ptr(qkv), B, d, int(H), Kc.shape[1], Kc.shape[0], _ptr(Kc), _ptr(Vc), _ptr(tab[0]), _ptr(tab[1]),
+                                         int(n_threads), int(set_keys), _ptr(merged), ms, _ptr(wo), int(score_fill) & 0xFFFFFFFF, err, len(err))
+    _check(rc, err)
+    return merged, wo
+
+
+SET_ENTRY_MODES = ("embed_q4_0", "embed_f16", "embed_f32", "rows")      # LLAMAHIP_SET_ENTRY_* of llamahip.h, in order
+SET_EXIT_MODES = ("argmax", "rows_out", "argmax_one")                  # LLAMAHIP_SET_EXIT_*, in order
+
+
+def op_set_entry(mode, row_pos, emb=None, tokens=None, hid_in=None, epoch_in: int = 0, pass_epoch: bool = False, x_stride: int | None = None, x_init=None):
+    """The first launch of a batched decode step (llamahip_op_set_entry).  mode "embed_q4_0" (emb uint8 [V, d/32, 20]), "embed_f16" /
+    "embed_f32" (emb [V, d]) with tokens int32 [B]; "rows" with hid_in f32 [B, d].  Returns dict(x f32 [B, x_stride], pos int32 [16] -- the
+    descriptor's pos[] --, epoch, state int32 [B, 2], changed: whether anything else moved)."""
+    code = SET_ENTRY_MODES.index(mode) if mode in SET_ENTRY_MODES else int(mode)
+    row_pos = np.ascontiguousarray(row_pos, np.int32).ravel()
+    B = row_pos.size
+    V = 0
+    if code == 3:
+        hid_in = None if hid_in is None else np.ascontiguousarray(hid_in, np.float32)
+        d = 0 if hid_in is None else hid_in.shape[1]
+        if hid_in is not None and hid_in.shape[0] != B:
+            raise ValueError(f"op_set_entry: {hid_in.shape[0]} hid_in rows for {B} positions")
+    else:
+        if emb is not None:
+            emb = np.ascontiguousarray(emb, (np.uint8, np.float16, np.float32)[code] if code in (0, 1, 2) else None)
+            V, d = emb.shape[0], emb.shape[1] * (32 if code == 0 else 1)
+        else:
+            d = 32
+        tokens = None if tokens is None else np.ascontiguousarray(tokens, np.int32).ravel()
+        if tokens is not None and tokens.size != B:
+            raise ValueError(f"op_set_entry: {tokens.size} tokens for {B} positions")
+    xs = d if x_stride is None else int(x_stride)
+    x = np.full((B, max(xs, 0)), np.nan, np.float32) if x_init is None else np.array(x_init, np.float32, order="C").reshape(B, xs)
+    pos, state = np.full(16, -2, np.int32), np.full((max(B, 1), 2), -2, np.int32)
+    epoch, changed = C.c_uint32(0), C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_set_entry(code, _ptr(emb) if code != 3 else None, V, d, _ptr(tokens) if code != 3 else None, _ptr(hid_in) if code == 3 else None, B,
+                                     _ptr(row_pos), int(epoch_in) & 0xFFFFFFFF, int(bool(pass_epoch)), _ptr(x), xs, _ptr(pos), C.byref(epoch), _ptr(state),
+                                     C.byref(changed), err, len(err))
+    _check(rc, err)
+    return dict(x=x, pos=pos, epoch=epoch.value, state=state, changed=bool(changed.value))
+
+
+def op_set_exit(mode, row_pos, row_step, n_ctx: int, logits=None, x=None, tok_out_null=None):
+    """The last launches of a batched decode step (llamahip_op_set_exit).  mode "argmax" / "argmax_one" on logits f32 [B, V]; "rows_out" on
+    x f32 [B, d].  Returns dict(trace int32 [B, n_ctx] (started as -1), tok_out int32 [B] (-1: not written), hid_out f32 [B, d] or None,
+    state int32 [B, 2])."""
+    code = SET_EXIT_MODES.index(mode) if mode in SET_EXIT_MODES else int(mode)
+    row_pos = np.ascontiguousarray(row_pos, np.int32).ravel()
+    row_step = np.ascontiguousarray(row_step, np.int32).ravel()
+    B = row_pos.size
+    if row_step.size != B:
+        raise ValueError(f"op_set_exit: {row_step.size} steps for {B} positions")
+    null = np.zeros(B, np.int32) if tok_out_null is None else np.ascontiguousarray(tok_out_null, np.int32).ravel()
+    if null.size != B:
+        raise ValueError(f"op_set_exit: {null.size} tok_out flags for {B} rows")
+    V = d = 0
+    hid = None
+    if logits is not None:
+        logits = np.ascontiguousarray(logits, np.float32).reshape(B, -1)
+        V = logits.shape[1]
+    if x is not None:
+        x = np.ascontiguousarray(x, np.float32).reshape(B, -1)
+        d = x.shape[1]
+        hid = np.full((B, d), np.nan, np.float32)
+    trace = np.full((B, max(int(n_ctx), 1)), -1, np.int32)
+    tok, state = np.full(B, -2, np.int32), np.full((B, 2), -2, np.int32)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_set_exit(code, _ptr(logits), V, _ptr(x), d, B, int(n_ctx), _ptr(row_pos), _ptr(row_step), _ptr(null), _ptr(trace), _ptr(tok),
+                                    _ptr(hid), _ptr(state), err, len(err))
+    _check(rc, err)
+    return dict(trace=trace, tok_out=tok, hid_out=hid, state=state)
 
 
 def op_kv_shift(Kc: np.ndarray, Vc: np.ndarray, dh: int, shifts) -> None:

@@ -1788,10 +1788,9 @@ int llamahip_stage_step_set(llamahip_model *m, const int32_t *seqs, int32_t n_se
     // The score launch of a step covers the key slices up to the set's highest position, in buckets of SET_KEY_BUCKET positions: the host
     // tracks every slot's position (next_pos), a captured step is keyed by its bucket and replayed until a row crosses into the next one
     // (n_ctx / 128 captures per set at most; the launch used to cover every slice of n_ctx whatever the positions -- ADVICE r04).
-    constexpr int SET_KEY_BUCKET = 128;
     int max_pos = 0;
     for (int i = 0; i < n_seqs; i++) max_pos = std::max(max_pos, m->slots[seqs[i]].next_pos);
-    const int set_keys = std::min(C, (max_pos / SET_KEY_BUCKET + 1) * SET_KEY_BUCKET);
+    const int set_keys = set_key_bucket(C, max_pos);
     std::vector<int> key;
     key.push_back(nth);
     key.push_back(set_keys);
@@ -3550,7 +3549,7 @@ static int vset_step(llamahip_model *m, const std::vector<llamahip_model *> &sta
     int rc, max_pos = 0;
     for (int g = 0; g < G; g++) max_pos = std::max(max_pos, rq.pos[g] + rq.seg_begin[g + 1] - rq.seg_begin[g] - 1);
     if (R < 2 || R > SET_MAX || G < 1 || G > R || max_pos >= C) { set_err(err, err_cap, "verify step over a set: %d rows in %d segments up to position %d", R, G, max_pos); return LLAMAHIP_ERR_PREDICT; }
-    const int set_keys = std::min(C, (max_pos / 128 + 1) * 128);            // (llamahip_stage_step_set's key bucket, exact for this step)
+    const int set_keys = set_key_bucket(C, max_pos);            // (llamahip_stage_step_set's key bucket, exact for this step)
     for (int s = 0; s < S; s++) if ((rc = vset_ensure(stages[s], s == 0, err, err_cap)) != 0) return rc;
     auto bail = [&](int r) { (void) pipe_sync_stages(stages, nullptr, 0); return r; };
     for (int s = 0; s < S; s++) {

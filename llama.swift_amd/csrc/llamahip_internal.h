@@ -35,6 +35,10 @@ struct SeqSet {
                                         // load instead of a pointer chase at the tail of the wq|wk|wv launch (written by the device, every step)
     int n;
 };
+// The score launch of a set step covers the key slices up to the set's highest position, in buckets of SET_KEY_BUCKET positions: what
+// launch_attn_short takes as set_keys (max_pos < set_keys <= n_ctx).  Host only; llamahip_debug_set_keys reports it.
+constexpr int SET_KEY_BUCKET = 128;
+inline int set_key_bucket(int n_ctx, int max_pos) { const int k = (max_pos / SET_KEY_BUCKET + 1) * SET_KEY_BUCKET; return k < n_ctx ? k : n_ctx; }
 // operands of the EPI_ROPE_KV epilogue (short evals, wq|wk|wv): rotate q / k, append k / v to the cache
 // (set: row n is at position set->state[n][0] of the cache at Kc / Vc + set->kv_off[n] instead of n_past + n)
 struct RopeKvArgs { const double *tab; float *qr, *Kc, *Vc; int n_past, d, dh; const SeqSet *set = nullptr; };

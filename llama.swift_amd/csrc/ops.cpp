@@ -1210,6 +1210,270 @@ int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, in
     return LLAMAHIP_OK;
 }
 
+// ---- the batched decode step (SeqSet) op by op: llamahip_op_set_attention, llamahip_op_set_entry, llamahip_op_set_exit (see llamahip.h) ----
+// Row r's scattered words live in cell set_cell(r) of a pool (SET_CELL_W words: [1] token in, [2] pick out, [4] position, [5] step) and its
+// row buffers (hid_in / hid_out / trace) in place set_place(r) of SET_MAX places: neither is the row order.  Every other word is 0xFF.
+constexpr int SET_CELL_W = 8, SET_ROW_GUARD = 8;
+constexpr uint32_t SET_POS_UNSET = 0x7F7F7F7Fu;
+static inline int set_cell(int r) { return (5 * r + 3) % SET_MAX; }
+static inline int set_place(int r) { return (7 * r + 2) % SET_MAX; }
+
+int32_t llamahip_debug_set_keys(int32_t n_ctx, int32_t max_pos) {
+    if (n_ctx < 1 || max_pos < 0 || max_pos >= n_ctx) return -1;
+    return set_key_bucket(n_ctx, max_pos);
+}
+
+// what llamahip_op_set_attention refuses of its row table
+static int set_rows_check(const char *fn, int B, int n_ctx, int n_slots, int set_keys, const int32_t *row_slot, const int32_t *row_pos, char *err, size_t err_cap) {
+    for (int r = 0; r < B; r++) {
+        if (row_slot[r] < 0 || row_slot[r] >= n_slots) { set_err(err, err_cap, "%s: row_slot[%d] = %d out of range [0, %d)", fn, r, row_slot[r], n_slots); return LLAMAHIP_ERR_PREDICT; }
+        if (row_pos[r] < 0 || row_pos[r] >= n_ctx) { set_err(err, err_cap, "%s: row_pos[%d] = %d out of range [0, n_ctx = %d)", fn, r, row_pos[r], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        if (set_keys > 0 && row_pos[r] >= set_keys) { set_err(err, err_cap, "%s: row_pos[%d] = %d is not below set_keys %d", fn, r, row_pos[r], set_keys); return LLAMAHIP_ERR_PREDICT; }
+    }
+    for (int r = 0; r < B; r++)
+        for (int q = 0; q < r; q++)
+            if (row_slot[q] == row_slot[r] && row_pos[q] == row_pos[r]) {
+                set_err(err, err_cap, "%s: rows %d and %d are both at position %d of slot %d", fn, q, r, row_pos[r], row_slot[r]); return LLAMAHIP_ERR_PREDICT;
+            }
+    for (int r = 1; r < B; r++)
+        for (int q = 0; q < r; q++)
+            if (row_slot[q] == row_slot[r] && (row_slot[r - 1] != row_slot[r] || row_pos[r] != row_pos[r - 1] + 1)) {
+                set_err(err, err_cap, "%s: the rows of slot %d are not one run of consecutive ascending positions in adjacent rows (row %d at %d, row %d of slot %d at %d)",
+                        fn, row_slot[r], r, row_pos[r], r - 1, row_slot[r - 1], row_pos[r - 1]);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    return 0;
+}
+
+int llamahip_op_set_attention(const float *qkv, int32_t B, int32_t d, int32_t H, int32_t n_ctx, int32_t n_slots, float *Kc, float *Vc,
+                              const int32_t *row_slot, const int32_t *row_pos, int32_t n_threads, int32_t set_keys,
+                              float *merged, int32_t merged_stride, void *wo_operand, uint32_t score_fill, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_set_attention";
+    if (!qkv || !Kc || !Vc || !row_slot || !row_pos || d < 1 || H < 1 || d % H != 0 || n_ctx < 1 || n_slots < 1) {
+        set_err(err, err_cap, "%s: bad arguments (qkv, Kc, Vc, row_slot, row_pos not NULL; d %d a multiple of H %d; n_ctx %d, n_slots %d >= 1)", fn, d, H, n_ctx, n_slots);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const int dh = d / H, nth = n_threads;
+    if (dh % 32 != 0 || dh > 256) { set_err(err, err_cap, "%s: head size %d: multiples of 32 up to 256", fn, dh); return LLAMAHIP_ERR_PREDICT; }
+    if (nth < 1 || nth > 32) { set_err(err, err_cap, "%s: n_threads %d outside 1 .. 32", fn, nth); return LLAMAHIP_ERR_PREDICT; }
+    if (B < 2 || B > SET_MAX) { set_err(err, err_cap, "%s: B %d outside 2 .. %d rows (SeqSet)", fn, B, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (set_keys < 0 || set_keys > n_ctx) { set_err(err, err_cap, "%s: set_keys %d outside 0 .. n_ctx = %d", fn, set_keys, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (merged && merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (set_rows_check(fn, B, n_ctx, n_slots, set_keys, row_slot, row_pos, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const int Kp = (d + 255) / 256 * 256;
+    const size_t cache_b = (size_t) n_slots * n_ctx * d * 4, ms = merged ? (size_t) merged_stride : (size_t) d, mbytes = (size_t) B * ms * 4;
+    const size_t qaA_b = (size_t) B * Kp, qad_b = (size_t) B * (Kp / 32) * 4, sc_w = (size_t) SET_MAX * H * n_ctx;
+    std::vector<uint16_t> ts(1 << 16), te(1 << 16);
+    lut_tables(ts, te);
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    std::vector<int32_t> pool((size_t) SET_MAX * SET_CELL_W, -1);
+    for (int r = 0; r < B; r++) { pool[set_cell(r) * SET_CELL_W + 4] = row_pos[r]; pool[set_cell(r) * SET_CELL_W + 5] = 1000 + r; }
+    SeqSet hs;
+    memset(&hs, 0, sizeof(hs));
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_qr = s.alloc<float>((size_t) B * d), *d_m = s.alloc<float>(mbytes / 4), *d_qad = s.alloc<float>(qad_b / 4), *d_sc = s.alloc<float>(sc_w);
+    float *d_hid = s.alloc<float>((size_t) B * d), *d_x = s.alloc<float>((size_t) B * d);      // the dummy rows the step's first launch gathers
+    uint32_t *d_qaA = s.alloc<uint32_t>(qaA_b / 4);
+    if (s.ok()) s.check(hipMemsetD32Async((hipDeviceptr_t) d_sc, (int) score_fill, sc_w, st));
+    s.fill(d_qr, 0xFF, (size_t) B * d * 4); s.fill(d_qaA, 0xFF, qaA_b); s.fill(d_qad, 0xFF, qad_b);
+    s.fill(d_hid, 0, (size_t) B * d * 4); s.fill(d_x, 0xFF, (size_t) B * d * 4);
+    if (!merged) s.fill(d_m, 0xFF, mbytes);
+    float *d_qkv = s.alloc((size_t) B * 3 * d, qkv), *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    if (merged) s.upload(d_m, merged, mbytes);
+    uint16_t *d_ts = s.alloc(ts.size(), ts.data()), *d_te = s.alloc(te.size(), te.data());
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    int32_t *d_pool = s.alloc(pool.size(), pool.data());
+    hs.n = B;
+    for (int r = 0; r < B; r++) {
+        hs.state[r] = d_pool + set_cell(r) * SET_CELL_W + 4;
+        hs.hid_in[r] = d_hid + (size_t) r * d;
+        hs.kv_off[r] = (long) row_slot[r] * n_ctx * d;
+        // pos[] before the step's first launch: inside the cache (nothing is written out of place if it were used) and NOT the row's position
+        hs.pos[r] = n_ctx < 2 ? 0 : (row_pos[r] + 1 + r % (n_ctx - 1)) % n_ctx;
+    }
+    SeqSet *d_set = s.alloc(1, &hs);
+    if (s.ok()) s.check(launch_check_lut_math(d_ts, d_te, st));          // g_lut_math, as a model load leaves it
+    if (s.ok()) s.check(launch_rows_set(d_set, B, d_x, d, true, st));      // fills SeqSet::pos, as the step's first launch
+    if (s.ok()) s.check(launch_rope_kv_set(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, d_set, B, st));
+    if (s.ok()) s.check(launch_attn_short(d_qr, d_K, d_V, d_sc, merged ? d_m : nullptr, d_qaA, d_qad, 0, B, d, H, n_ctx, nth, d_te, st, 0, d_set, set_keys, (long) ms));
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    if (merged) s.download(merged, d_m, mbytes);
+    std::vector<uint32_t> qa(qaA_b / 4), qd(qad_b / 4);
+    std::vector<int32_t> pool_after(pool.size());
+    s.download(qa.data(), d_qaA, qaA_b);
+    s.download(qd.data(), d_qad, qad_b);
+    s.download(pool_after.data(), d_pool, pool.size() * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (int r = 0; r < B; r++) {
+        for (int pb = d / 32; pb < Kp / 32; pb++) {
+            bool zero = qd[(size_t) r * (Kp / 32) + pb] == 0;
+            for (int kk = 0; kk < 8; kk++) zero = zero && qa[(size_t) r * (Kp / 4) + ((pb >> 3) * 8 + kk) * 8 + (pb & 7)] == 0;
+            if (!zero) { set_err(err, err_cap, "%s: row %d: operand block %d (padding d %d up to %d) is not all zero", fn, r, pb, d, Kp); return LLAMAHIP_ERR_PREDICT; }
+        }
+        for (int w = 4; w < 6; w++)
+            if (pool_after[set_cell(r) * SET_CELL_W + w] != pool[set_cell(r) * SET_CELL_W + w]) {
+                set_err(err, err_cap, "%s: row %d: state word %d changed (%d -> %d)", fn, r, w - 4, pool[set_cell(r) * SET_CELL_W + w], pool_after[set_cell(r) * SET_CELL_W + w]);
+                return LLAMAHIP_ERR_PREDICT;
+            }
+    }
+    if (pool_after != pool) { set_err(err, err_cap, "%s: a word of the state pool outside the rows' pairs changed", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (wo_operand) qa_to_q4_0_blocks(qa.data(), (const float *) qd.data(), B, d, (uint8_t *) wo_operand);
+    return LLAMAHIP_OK;
+}
+
+int llamahip_op_set_entry(int32_t mode, const void *emb, int32_t V, int32_t d, const int32_t *tokens, const float *hid_in, int32_t B,
+                          const int32_t *row_pos, uint32_t epoch_in, int32_t pass_epoch, float *x, int32_t x_stride,
+                          int32_t *pos_out, uint32_t *epoch_out, int32_t *state_out, int32_t *pool_changed, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_set_entry";
+    if (mode < LLAMAHIP_SET_ENTRY_EMBED_Q4_0 || mode > LLAMAHIP_SET_ENTRY_ROWS) { set_err(err, err_cap, "%s: unknown mode %d", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    const bool embed = mode != LLAMAHIP_SET_ENTRY_ROWS, dense = mode == LLAMAHIP_SET_ENTRY_EMBED_F16 || mode == LLAMAHIP_SET_ENTRY_EMBED_F32;
+    if (B < 2 || B > SET_MAX) { set_err(err, err_cap, "%s: B %d outside 2 .. %d rows (SeqSet)", fn, B, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (d < 32 || d % 32 != 0) { set_err(err, err_cap, "%s: d %d must be a positive multiple of 32", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    if (!row_pos || !x || !pos_out || !epoch_out || !state_out || !pool_changed) { set_err(err, err_cap, "%s: null operand (row_pos, x, pos_out, epoch_out, state_out, pool_changed)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (x_stride < d) { set_err(err, err_cap, "%s: x_stride %d < d %d", fn, x_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (embed && (!emb || !tokens || V < 1)) { set_err(err, err_cap, "%s: the embed modes need emb, tokens and V %d >= 1", fn, V); return LLAMAHIP_ERR_PREDICT; }
+    if (!embed && !hid_in) { set_err(err, err_cap, "%s: mode ROWS needs hid_in", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (dense && pass_epoch) { set_err(err, err_cap, "%s: k_embed_dense_set takes no epoch word (pass_epoch with mode %d)", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    for (int r = 0; r < B; r++) {
+        if (embed && (tokens[r] < 0 || tokens[r] >= V)) { set_err(err, err_cap, "%s: token %d of row %d outside [0, %d)", fn, tokens[r], r, V); return LLAMAHIP_ERR_PREDICT; }
+        if (row_pos[r] < 0) { set_err(err, err_cap, "%s: row_pos[%d] = %d is negative", fn, r, row_pos[r]); return LLAMAHIP_ERR_PREDICT; }
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t cells_w = (size_t) SET_MAX * SET_CELL_W, row_w = (size_t) d + SET_ROW_GUARD, pool_w = cells_w + (embed ? 0 : SET_MAX * row_w);
+    std::vector<uint32_t> pool(pool_w, 0xFFFFFFFFu), after(pool_w);
+    for (int r = 0; r < B; r++) {
+        uint32_t *c = pool.data() + set_cell(r) * SET_CELL_W;
+        if (embed) c[1] = (uint32_t) tokens[r];
+        c[4] = (uint32_t) row_pos[r]; c[5] = (uint32_t) (7 + 3 * r);
+        if (!embed) memcpy(pool.data() + cells_w + set_place(r) * row_w, hid_in + (size_t) r * d, (size_t) d * 4);
+    }
+    uint32_t ep[8], ep_after[8];
+    for (uint32_t &w : ep) w = 0xFFFFFFFFu;
+    ep[3] = epoch_in;
+    const size_t emb_b = !embed ? 0 : mode == LLAMAHIP_SET_ENTRY_EMBED_Q4_0 ? (size_t) V * (d / 32) * 20 : (size_t) V * d * (mode == LLAMAHIP_SET_ENTRY_EMBED_F16 ? 2 : 4);
+    const size_t xfloats = (size_t) B * x_stride;
+    SeqSet hs, hs_after;
+    memset(&hs, 0, sizeof(hs));
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint32_t *d_pool = s.alloc(pool_w, pool.data()), *d_ep = s.alloc(8, ep);
+    uint8_t *d_emb = embed ? s.alloc(emb_b, (const uint8_t *) emb) : nullptr;
+    float *d_x = s.alloc(xfloats, x);      // (the floats between d and x_stride keep the caller's bits)
+    float *d_rows = s.alloc<float>((size_t) B * d + 64);      // the kernels' dense [B][d] output, then 64 floats that must stay NaN
+    s.fill(d_rows, 0xFF, ((size_t) B * d + 64) * 4);
+    hs.n = B;
+    for (int r = 0; r < SET_MAX; r++) hs.pos[r] = (int32_t) SET_POS_UNSET;
+    for (int r = 0; r < B; r++) {
+        int32_t *c = (int32_t *) d_pool + set_cell(r) * SET_CELL_W;
+        hs.state[r] = c + 4;
+        if (embed) hs.tok_in[r] = c + 1;
+        else hs.hid_in[r] = (const float *) (d_pool + cells_w + set_place(r) * row_w);
+    }
+    SeqSet *d_set = s.alloc(1, &hs);
+    uint32_t *epw = pass_epoch ? d_ep + 3 : nullptr;
+    if (s.ok() && mode == LLAMAHIP_SET_ENTRY_EMBED_Q4_0) s.check(launch_embed_set(d_set, B, d_emb, d_rows, d, st, epw));
+    if (s.ok() && dense) s.check(launch_embed_dense_set(d_set, B, d_emb, mode == LLAMAHIP_SET_ENTRY_EMBED_F16 ? 1 : 0, d_rows, d, st));
+    if (s.ok() && !embed) s.check(launch_rows_set(d_set, B, d_rows, d, true, st, epw));
+    if (s.ok()) s.check(hipMemcpy2DAsync(d_x, (size_t) x_stride * 4, d_rows, (size_t) d * 4, (size_t) d * 4, B, hipMemcpyDeviceToDevice, st));
+    uint32_t tail[64];
+    s.download(tail, d_rows + (size_t) B * d, sizeof(tail));
+    s.download(x, d_x, xfloats * 4);
+    s.download(after.data(), d_pool, pool_w * 4);
+    s.download(ep_after, d_ep, sizeof(ep_after));
+    s.download(&hs_after, d_set, sizeof(SeqSet));
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (uint32_t t : tail)
+        if (t != 0xFFFFFFFFu) { set_err(err, err_cap, "%s: the kernel wrote past row B - 1 of its [B][d] output", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int r = 0; r < SET_MAX; r++) pos_out[r] = hs_after.pos[r];
+    *epoch_out = ep_after[3];
+    bool changed = false;
+    for (int r = 0; r < B; r++) {
+        const size_t c = (size_t) set_cell(r) * SET_CELL_W;
+        state_out[2 * r] = (int32_t) after[c + 4]; state_out[2 * r + 1] = (int32_t) after[c + 5];
+        after[c + 4] = pool[c + 4]; after[c + 5] = pool[c + 5];
+        hs_after.pos[r] = hs.pos[r];
+    }
+    for (int r = B; r < SET_MAX; r++) changed = changed || hs_after.pos[r] != (int32_t) SET_POS_UNSET;
+    ep_after[3] = ep[3];
+    changed = changed || after != pool || memcmp(ep_after, ep, sizeof(ep)) != 0 || memcmp(&hs_after, &hs, sizeof(SeqSet)) != 0;
+    *pool_changed = changed ? 1 : 0;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_op_set_exit(int32_t mode, const float *logits, int32_t V, const float *x, int32_t d, int32_t B, int32_t n_ctx,
+                         const int32_t *row_pos, const int32_t *row_step, const int32_t *tok_out_null,
+                         int32_t *trace, int32_t *tok_out, float *hid_out, int32_t *state_out, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_set_exit";
+    if (mode < LLAMAHIP_SET_EXIT_ARGMAX || mode > LLAMAHIP_SET_EXIT_ARGMAX_ONE) { set_err(err, err_cap, "%s: unknown mode %d", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    const bool one = mode == LLAMAHIP_SET_EXIT_ARGMAX_ONE, rows = mode == LLAMAHIP_SET_EXIT_ROWS_OUT;
+    if (one && B != 1) { set_err(err, err_cap, "%s: mode ARGMAX_ONE takes B = 1 row (k_argmax), got %d", fn, B); return LLAMAHIP_ERR_PREDICT; }
+    if (!one && (B < 2 || B > SET_MAX)) { set_err(err, err_cap, "%s: B %d outside 2 .. %d rows (SeqSet)", fn, B, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (!row_pos || !row_step || !tok_out_null || !trace || !tok_out || !state_out) { set_err(err, err_cap, "%s: null operand (row_pos, row_step, tok_out_null, trace, tok_out, state_out)", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!rows && (!logits || V < 1)) { set_err(err, err_cap, "%s: the argmax modes need logits and V %d >= 1", fn, V); return LLAMAHIP_ERR_PREDICT; }
+    if (rows && (!x || !hid_out || d < 1)) { set_err(err, err_cap, "%s: mode ROWS_OUT needs x, hid_out and d %d >= 1", fn, d); return LLAMAHIP_ERR_PREDICT; }
+    if (n_ctx < 1) { set_err(err, err_cap, "%s: n_ctx %d must be >= 1", fn, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    for (int r = 0; r < B; r++) {
+        if (row_pos[r] < 0 || row_pos[r] >= n_ctx) { set_err(err, err_cap, "%s: row_pos[%d] = %d out of range [0, n_ctx = %d)", fn, r, row_pos[r], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+        if (row_step[r] < 0 || row_step[r] >= n_ctx) { set_err(err, err_cap, "%s: row_step[%d] = %d out of range [0, n_ctx = %d) (the trace row)", fn, r, row_step[r], n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t cells_w = (size_t) SET_MAX * SET_CELL_W, trace_w = (size_t) SET_MAX * n_ctx, row_w = rows ? (size_t) d + SET_ROW_GUARD : 0;
+    const size_t pool_w = cells_w + trace_w + SET_MAX * row_w;
+    std::vector<uint32_t> pool(pool_w, 0xFFFFFFFFu), after(pool_w);
+    for (int r = 0; r < B; r++) {
+        uint32_t *c = pool.data() + set_cell(r) * SET_CELL_W;
+        c[4] = (uint32_t) row_pos[r]; c[5] = (uint32_t) row_step[r];
+        memcpy(pool.data() + cells_w + (size_t) set_place(r) * n_ctx, trace + (size_t) r * n_ctx, (size_t) n_ctx * 4);
+    }
+    SeqSet hs;
+    memset(&hs, 0, sizeof(hs));
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint32_t *d_pool = s.alloc(pool_w, pool.data());
+    float *d_l = rows ? nullptr : s.alloc((size_t) B * V, logits), *d_x = rows ? s.alloc((size_t) B * d, x) : nullptr;
+    hs.n = B;
+    for (int r = 0; r < B; r++) {
+        int32_t *c = (int32_t *) d_pool + set_cell(r) * SET_CELL_W;
+        hs.state[r] = c + 4;
+        hs.tok_out[r] = tok_out_null[r] ? nullptr : c + 2;
+        hs.trace[r] = (int32_t *) d_pool + cells_w + (size_t) set_place(r) * n_ctx;
+        if (rows) hs.hid_out[r] = (float *) (d_pool + cells_w + trace_w + set_place(r) * row_w);
+        hs.pos[r] = row_pos[r];
+    }
+    SeqSet *d_set = s.alloc(1, &hs);
+    if (s.ok() && mode == LLAMAHIP_SET_EXIT_ARGMAX) s.check(launch_argmax_set(d_l, V, d_set, B, st));
+    if (s.ok() && one) s.check(launch_argmax(d_l, V, hs.trace[0], 0, hs.tok_out[0], hs.state[0], st));
+    if (s.ok() && rows) s.check(launch_rows_set(d_set, B, d_x, d, false, st));
+    if (s.ok() && rows) s.check(launch_advance_set(d_set, B, st));
+    s.download(after.data(), d_pool, pool_w * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    // the named words go to the caller and are put back as they were; everything else must be what it was
+    for (int r = 0; r < B; r++) {
+        const size_t c = (size_t) set_cell(r) * SET_CELL_W, t = cells_w + (size_t) set_place(r) * n_ctx, h = cells_w + trace_w + set_place(r) * row_w;
+        state_out[2 * r] = (int32_t) after[c + 4]; state_out[2 * r + 1] = (int32_t) after[c + 5];
+        after[c + 4] = pool[c + 4]; after[c + 5] = pool[c + 5];
+        tok_out[r] = (int32_t) after[c + 2];
+        if (!tok_out_null[r]) after[c + 2] = pool[c + 2];
+        memcpy(trace + (size_t) r * n_ctx, after.data() + t, (size_t) n_ctx * 4);
+        memcpy(after.data() + t, pool.data() + t, (size_t) n_ctx * 4);
+        if (rows) { memcpy(hid_out + (size_t) r * d, after.data() + h, (size_t) d * 4); memcpy(after.data() + h, pool.data() + h, (size_t) d * 4); }
+    }
+    for (size_t i = 0; i < pool_w; i++)
+        if (after[i] != pool[i]) {
+            set_err(err, err_cap, "%s: word %zu of the pool (%s) changed: %#x -> %#x", fn, i, i < cells_w ? "the cells: a null tok_out's word or padding" : i < cells_w + trace_w ? "a trace row no row names" : "a guard around the hid_out rows",
+                    pool[i], after[i]);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    return LLAMAHIP_OK;
+}
+
 int llamahip_op_quantize_row_q4_0(const float *x, int32_t k, void *y, char *err, size_t err_cap) {
     if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
     if (!x || !y || k < 32 || k % 32 != 0) { set_err(err, err_cap, "bad quantize arguments"); return LLAMAHIP_ERR_PREDICT; }
