@@ -1236,6 +1236,25 @@ int llamahip_debug_qa_to_blocks(const uint32_t *qa_A, const float *qa_d, int32_t
  * the decode step's k_embed_part, which also leaves {sum x, sum x^2} of the row in stats[0 .. 1]. */
 int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, int32_t V, int32_t d, float *x, int32_t x_stride,
                       double *stats, char *err, size_t err_cap);
+/* The producers of an f16 / f32 mat-mul's activation operand on caller-supplied rows.  mode, buf, buf_floats, the offsets and the strides
+ * are llamahip_op_prep's; wtype 1 (fp16 weights: every value is rounded to fp16 once, RNE, and widened again) or 0 (fp32: unchanged).
+ * kernel: _AUTO what a model's mat-mul launches (_FUSED unless a NORM row has K / 16 > 1024), _FUSED k_dense_prep (one launch; refused for
+ * such NORM rows), _SPLIT launch_prep's fp32 rows (PLAIN: in0 as it lies) + k_dense_perm_act.  xp [N][K] floats + 64 guard floats, copied
+ * to the device before the launch and back after it: the operand as the kernels wrote it, in the chain-major order of the mat-mul kernels
+ * (element g * 256 + 32 s + l of a row at g * 256 + l * st + s, st = the steps of its group of 256: 8, fewer in a tail group); whatever
+ * the launch does not write keeps the caller's bits.  *kernel_taken (may be NULL): _FUSED or _SPLIT.  Refusals happen before any device
+ * is touched. */
+#define LLAMAHIP_DENSE_PREP_AUTO  0
+#define LLAMAHIP_DENSE_PREP_FUSED 1
+#define LLAMAHIP_DENSE_PREP_SPLIT 2
+int llamahip_op_dense_prep(int32_t mode, int32_t wtype, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
+                           int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, float *xp, int32_t *kernel_taken, char *err, size_t err_cap);
+/* The embedding gather of an f16 / f32 / Q4_1 model file (ggml_get_rows): tokens [N] in [0, V) (checked on the host); emb [V] rows in file
+ * layout, wtype 0 fp32 [d], 1 fp16 [d], 3 Q4_1 ([d / 32 floats min][d / 32 floats d][d / 32 * 16 nibble bytes]); x [N][x_stride] (x_stride >= d)
+ * copied whole both ways: the kernels write dense [N][d] rows on the device (followed by a guard the op checks), which the op places
+ * x_stride apart. */
+int llamahip_op_embed_dense(const int32_t *tokens, int32_t N, const void *emb, int32_t wtype, int32_t V, int32_t d, float *x, int32_t x_stride,
+                            char *err, size_t err_cap);
 /* The attention of a BATCHED decode step (forward_set / forward_dense_set: llamahip_stage_step_set, the multi-sequence decoders, the verify
  * steps over a set, the request scheduler) on caller-supplied operands: B rows (2 .. 16), each the next token of its own sequence.
  * qkv [B][3d] un-rotated; Kc, Vc [n_slots][n_ctx][d], copied whole both ways; row r appends at position row_pos[r] of slot row_slot[r] and

@@ -257,6 +257,8 @@ def lib() -> C.CDLL:
     L.llamahip_op_prep.argtypes = [i32, i32, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, i32, vp, vp, i32, vp, vp, cp, sz]
     L.llamahip_debug_qa_to_blocks.argtypes = [vp, vp, i32, i32, vp]
     L.llamahip_op_embed.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, cp, sz]
+    L.llamahip_op_dense_prep.argtypes = [i32, i32, i32, vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64, i32, i32, vp, vp, cp, sz]
+    L.llamahip_op_embed_dense.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, cp, sz]
     L.llamahip_op_gemv_q4_0.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, i32, vp, vp, C.c_int64, vp, vp, i32, vp, i32, i32, vp, cp, sz]
     L.llamahip_op_gemv_set_q4_0.argtypes = [vp, i32, i32, i32, i32, vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, cp, sz]
     L.llamahip_bench_gemv.argtypes = [vp, i32, i32, i32, i32, C.POINTER(_GemvBench), cp, sz]
@@ -1955,6 +1957,48 @@ def op_embed(tokens, emb: np.ndarray, x_stride: int | None = None, x_init=None, 
     rc = lib().llamahip_op_embed(_ptr(tokens), N, _ptr(emb), V, d, _ptr(x), xs, _ptr(stats), err, len(err))
     _check(rc, err)
     return (x, stats) if want_stats else x
+
+
+DENSE_PREP_KERNELS = ("auto", "fused", "split")          # LLAMAHIP_DENSE_PREP_*, in order
+DENSE_XP_GUARD = 64                                       # floats behind row N - 1 of op_dense_prep's operand
+
+
+def op_dense_prep(mode: str, wtype: int, buf: np.ndarray, K: int, N: int, in_stride: int | None = None, in0_offset: int = 0, in1_offset: int = 0,
+                  in1_stride: int = 0, kernel: str = "auto", xp_init=None):
+    """The activation operand of an f16 / f32 mat-mul (llamahip_op_dense_prep).  buf and the offsets / strides as op_prep takes them; wtype 1
+    (fp16 weights) or 0 (fp32).  Returns (xp float32 [N * K + DENSE_XP_GUARD], the kernel taken): the operand rows in the kernels' permuted
+    order followed by the guard floats, as the device left them -- xp_init (default: 0xFF in every byte) wherever nothing was written."""
+    buf = np.ascontiguousarray(buf, np.float32).ravel()
+    n = max(int(N), 0) * max(int(K), 0) + DENSE_XP_GUARD
+    xp = np.full(n, 0xFFFFFFFF, np.uint32).view(np.float32) if xp_init is None else np.array(xp_init, np.float32, order="C").reshape(n)
+    mcode = PREP_MODES[mode] if mode in PREP_MODES else int(mode)
+    kcode = DENSE_PREP_KERNELS.index(kernel) if kernel in DENSE_PREP_KERNELS else int(kernel)
+    taken = C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_dense_prep(mcode, int(wtype), kcode, _ptr(buf), buf.size, int(in0_offset), int(K if in_stride is None else in_stride),
+                                      int(in1_offset), int(in1_stride), int(K), int(N), _ptr(xp), C.byref(taken), err, len(err))
+    _check(rc, err)
+    return xp, DENSE_PREP_KERNELS[taken.value]
+
+
+def op_embed_dense(tokens, emb: np.ndarray, x_stride: int | None = None, x_init=None, wtype: int | None = None):
+    """The embedding gather of an f16 / f32 / Q4_1 file (llamahip_op_embed_dense): tokens int32 [N]; emb float32 / float16 [V, d] (wtype 0 / 1)
+    or uint8 [V, d/32 * 24] Q4_1 rows in file layout (wtype 3); wtype overrides what the dtype implies.  Returns x float32 [N, x_stride] as
+    the device left it (x_init, default NaN, where nothing was written)."""
+    tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+    emb = np.ascontiguousarray(emb)
+    if emb.dtype not in (np.float16, np.float32, np.uint8):
+        emb = emb.astype(np.float32)
+    wt = {np.dtype(np.float32): 0, np.dtype(np.float16): 1, np.dtype(np.uint8): 3}[emb.dtype] if wtype is None else int(wtype)
+    V = emb.shape[0]
+    d = emb.shape[1] // 24 * 32 if emb.dtype == np.uint8 else emb.shape[1]
+    N = tokens.size
+    xs = d if x_stride is None else int(x_stride)
+    x = np.full((N, max(xs, 0)), np.nan, np.float32) if x_init is None else np.array(x_init, np.float32, order="C").reshape(N, xs)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_embed_dense(_ptr(tokens), N, _ptr(emb), wt, V, d, _ptr(x), xs, err, len(err))
+    _check(rc, err)
+    return x
 
 
 def op_quantize_row_q4_0(x: np.ndarray) -> np.ndarray:

@@ -168,7 +168,8 @@ k_dense_prep(const float *__restrict__ in0, const float *__restrict__ in1, long 
     // The fp32 products above must exist as fp32 values before they are rounded to fp16: left alone, hipcc
     // folds `(_Float16) (a * b)` into v_fma_mixlo_f16 -- ONE rounding of the exact product -- while the
     // reference rounds the product to fp32 (ggml_mul) and that to fp16 (the mat-mul's INIT phase).  Rare
-    // (a few elements per thousand rows), and enough to flip logits in the 4th digit.
+    // (a few elements per thousand rows), and enough to flip logits in the 4th digit.  tests/test_gpu_dense_prep_op.py holds this fence
+    // in place: its f16_double_rounding rows are made of such products (64 and more per row), so the kernel without it fails them.
 #pragma unroll
     for (int v = 0; v < 4; v++) asm volatile("" : "+v"(xa[v].x), "+v"(xa[v].y), "+v"(xa[v].z), "+v"(xa[v].w));
     // element e = hi*16 + i  ->  g*256 + l*st + sidx  (perm_index): the 16 elements share g and sidx
@@ -726,7 +727,10 @@ hipError_t go_set_rows(const DenseSetPlan &p, const DMat &w, int N, float *y, lo
 template <int WT, int NC>
 hipError_t go(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
               const float *resid, long resid_stride, hipStream_t st, float *scratch, int path) {
-    if (x) hipLaunchKernelGGL(k_dense_perm_act<WT>, dim3(N), dim3(256), 0, st, x, x_stride, w.K, scratch);     // x == nullptr: scratch already holds the prepared rows
+    if (x) {                                               // x == nullptr: scratch already holds the prepared rows
+        const hipError_t e = launch_dense_perm_act(WT, x, x_stride, w.K, N, scratch, st);
+        if (e != hipSuccess) return e;
+    }
     if (path == DENSE_PATH_MV) {
         // small matrices: 4 half-waves per workgroup so that every CU gets one (a 4096-row matrix is 256 workgroups)
         const int nhw = (w.M + 8 * RG - 1) / (8 * RG) >= 512 ? 8 : 4;
@@ -1259,6 +1263,39 @@ hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float 
     }
 #undef LD_PREP
     return hipGetLastError();
+}
+
+// fp32 rows -> the rounded (f16 weights), permuted operand rows: the second half of the split preparation, and what launch_dense_mm does
+// with rows it is handed un-prepared
+hipError_t launch_dense_perm_act(int wtype, const float *x, long x_stride, int K, int N, float *xp, hipStream_t st) {
+    if (wtype == 1) hipLaunchKernelGGL(k_dense_perm_act<1>, dim3(N), dim3(256), 0, st, x, x_stride, K, xp);
+    else if (wtype == 0) hipLaunchKernelGGL(k_dense_perm_act<0>, dim3(N), dim3(256), 0, st, x, x_stride, K, xp);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// The activation operand of an f16 / f32 mat-mul, the one place that picks its producer (a model's dense_prep_mm and
+// llamahip_op_dense_prep both come here).  AUTO: FUSED -- k_dense_prep, one launch -- where dense_prep_applies, else SPLIT: launch_prep
+// leaves the fp32 rows y in `rows` [N][K] (PLAIN has nothing to compute: in0 is read as it lies) and k_dense_perm_act rounds and permutes
+// them.  FUSED asked for where it does not apply is refused with hipErrorInvalidValue, nothing launched.  qa_A / qa_d: the Q4_0 operand
+// launch_prep always writes next to y (N rows of K rounded up to 256); *taken (may be null): DENSE_PREP_FUSED or DENSE_PREP_SPLIT.
+int dense_prep_kernel(int kernel, int wtype, int mode, int K) {
+    if (kernel < DENSE_PREP_AUTO || kernel > DENSE_PREP_SPLIT || (wtype != 0 && wtype != 1) || mode < PREP_PLAIN || mode > PREP_SILU_MUL || K < 32 || K % 32 != 0) return -1;
+    const bool fused_ok = dense_prep_applies(wtype, mode, K);
+    if (kernel == DENSE_PREP_FUSED && !fused_ok) return -1;
+    return kernel == DENSE_PREP_AUTO ? (fused_ok ? DENSE_PREP_FUSED : DENSE_PREP_SPLIT) : kernel;
+}
+hipError_t launch_dense_act(int kernel, int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride, int K, int N,
+                            float *xp, float *rows, uint32_t *qa_A, float *qa_d, const uint16_t *T_silu, hipStream_t st, int *taken) {
+    const int run = dense_prep_kernel(kernel, wtype, mode, K);
+    if (run < 0 || !xp) return hipErrorInvalidValue;
+    if (taken) *taken = run;
+    if (run == DENSE_PREP_FUSED) return launch_dense_prep(mode, wtype, in0, in1, in_stride, in1_stride, K, N, xp, T_silu, st);
+    if (mode == PREP_PLAIN) return launch_dense_perm_act(wtype, in0, in_stride, K, N, xp, st);
+    if (!rows || !qa_A || !qa_d) return hipErrorInvalidValue;
+    const hipError_t e = launch_prep(mode, in0, in1, in_stride, in1_stride, K, N, qa_A, qa_d, rows, nullptr, T_silu, st);
+    if (e != hipSuccess) return e;
+    return launch_dense_perm_act(wtype, rows, K, K, N, xp, st);
 }
 
 hipError_t launch_embed_dense(const int32_t *tokens, const void *emb, int wtype, float *x, int d, int N, hipStream_t st) {

@@ -602,12 +602,13 @@ struct Pass {
     int32_t *pick_out = nullptr, *pick_next = nullptr;
 };
 
-// dense model files: activation preparation + mat-mul of `rows` rows.  f16 / f32 weights: one fused launch writes the rounded, permuted rows
-// straight into the mat-mul's operand buffer; Q4_1: fp32 rows, expanded by the mat-mul itself.
+// dense model files: activation preparation + mat-mul of `rows` rows.  f16 / f32 weights: launch_dense_act writes the rounded, permuted rows
+// straight into the mat-mul's operand buffer (one fused launch, or launch_prep's fp32 rows + k_dense_perm_act where a NORM row is too wide for
+// it); Q4_1: fp32 rows, expanded by the mat-mul itself.
 static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int mode, const float *in0, const float *in1, long in_stride, long in1_stride,
                                 int K, int rows, float *out, long out_stride, const float *resid, long resid_stride, hipStream_t st) {
-    if (dense_prep_applies(w.wtype, mode, K)) {
-        hipError_t e = launch_dense_prep(mode, w.wtype, in0, in1, in_stride, in1_stride, K, rows, m->tmp, m->T_silu, st);
+    if (w.wtype != 3) {                                    // fused where it applies, else split: launch_dense_act's rule (dense.hip)
+        hipError_t e = launch_dense_act(DENSE_PREP_AUTO, mode, w.wtype, in0, in1, in_stride, in1_stride, K, rows, m->tmp, m->dbg_y, m->qa_A, m->qa_d, m->T_silu, st);
         if (e != hipSuccess) return e;
         return launch_dense_mm(w, epi, nullptr, K, rows, out, out_stride, resid, resid_stride, st, m->tmp);
     }

@@ -113,6 +113,12 @@ hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, 
 bool dense_prep_applies(int wtype, int mode, int K);
 hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride,
                              int K, int N, float *scratch, const uint16_t *T_silu, hipStream_t st);
+hipError_t launch_dense_perm_act(int wtype, const float *x, long x_stride, int K, int N, float *xp, hipStream_t st);
+// which producer writes an f16 / f32 mat-mul's operand rows (dense.hip launch_dense_act), = LLAMAHIP_DENSE_PREP_* of llamahip.h
+enum { DENSE_PREP_AUTO = 0, DENSE_PREP_FUSED = 1, DENSE_PREP_SPLIT = 2 };
+int dense_prep_kernel(int kernel, int wtype, int mode, int K);      // the producer that runs, -1: refused
+hipError_t launch_dense_act(int kernel, int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride, int K, int N,
+                            float *xp, float *rows, uint32_t *qa_A, float *qa_d, const uint16_t *T_silu, hipStream_t st, int *taken = nullptr);
 hipError_t launch_dense_perm_rows(const void *raw_rows, DMat &w, int row0, int rows, hipStream_t st);
 hipError_t launch_quantize_q41_offline(const void *src, int f16, uint8_t *dst, long nrows, int nb, hipStream_t st);
 hipError_t launch_embed_dense(const int32_t *tokens, const void *emb, int wtype, float *x, int d, int N, hipStream_t st);

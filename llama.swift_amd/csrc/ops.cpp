@@ -1210,6 +1210,87 @@ int llamahip_op_embed(const int32_t *tokens, int32_t N, const void *emb_q4_0, in
     return LLAMAHIP_OK;
 }
 
+static_assert(LLAMAHIP_DENSE_PREP_AUTO == DENSE_PREP_AUTO && LLAMAHIP_DENSE_PREP_FUSED == DENSE_PREP_FUSED && LLAMAHIP_DENSE_PREP_SPLIT == DENSE_PREP_SPLIT, "llamahip.h mirrors launch_dense_act's kernels");
+
+// the producers of an f16 / f32 mat-mul's activation operand on caller-supplied rows (launch_dense_act: k_dense_prep, or launch_prep +
+// k_dense_perm_act), the producer chosen by the caller: see llamahip.h
+int llamahip_op_dense_prep(int32_t mode, int32_t wtype, int32_t kernel, const float *buf, int64_t buf_floats, int64_t in0_offset, int64_t in_stride,
+                           int64_t in1_offset, int64_t in1_stride, int32_t K, int32_t N, float *xp, int32_t *kernel_taken, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_dense_prep";
+    if (mode != LLAMAHIP_PREP_PLAIN && mode != LLAMAHIP_PREP_NORM && mode != LLAMAHIP_PREP_SILU_MUL) { set_err(err, err_cap, "%s: unknown mode %d", fn, mode); return LLAMAHIP_ERR_PREDICT; }
+    if (wtype != 0 && wtype != 1) { set_err(err, err_cap, "%s: wtype %d: 0 (fp32) or 1 (fp16) weights", fn, wtype); return LLAMAHIP_ERR_PREDICT; }
+    if (kernel < LLAMAHIP_DENSE_PREP_AUTO || kernel > LLAMAHIP_DENSE_PREP_SPLIT) { set_err(err, err_cap, "%s: unknown kernel %d", fn, kernel); return LLAMAHIP_ERR_PREDICT; }
+    if (!buf || !xp || N < 1) { set_err(err, err_cap, "%s: bad arguments (buf, xp not NULL; N %d >= 1)", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    if (K < 32 || K % 32 != 0 || K > 32768) { set_err(err, err_cap, "%s: K %d must be a multiple of 32 in 32 .. 32768", fn, K); return LLAMAHIP_ERR_PREDICT; }
+    const bool rows1 = mode == LLAMAHIP_PREP_SILU_MUL, has1 = mode != LLAMAHIP_PREP_PLAIN;
+    if (in_stride < K || (rows1 && in1_stride < K)) {
+        set_err(err, err_cap, "%s: row stride %lld / %lld < K %d", fn, (long long) in_stride, (long long) in1_stride, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (in_stride % 4 != 0 || in0_offset % 4 != 0 || (has1 && in1_offset % 4 != 0) || (rows1 && in1_stride % 4 != 0)) {
+        set_err(err, err_cap, "%s: strides and offsets must be multiples of 4 floats (the kernels load 16 bytes at a time)", fn); return LLAMAHIP_ERR_PREDICT;
+    }
+    const int64_t end0 = in0_offset + (int64_t) (N - 1) * in_stride + K, end1 = !has1 ? 0 : in1_offset + (rows1 ? (int64_t) (N - 1) * in1_stride : 0) + K;
+    if (in0_offset < 0 || (has1 && in1_offset < 0) || end0 > buf_floats || end1 > buf_floats) {
+        set_err(err, err_cap, "%s: the operands end at float %lld / %lld of a buffer of %lld", fn, (long long) end0, (long long) end1, (long long) buf_floats); return LLAMAHIP_ERR_PREDICT;
+    }
+    const int run = dense_prep_kernel(kernel, wtype, mode, K);
+    if (run < 0) {
+        set_err(err, err_cap, "%s: kernel FUSED (k_dense_prep) refused for NORM with K %d: a row is one workgroup of K / 16 <= 1024 threads", fn, K); return LLAMAHIP_ERR_PREDICT;
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t Kp = ((size_t) K + 255) / 256 * 256, xfloats = (size_t) N * K + 64;      // (64 guard floats behind row N - 1)
+    const bool staged = run == DENSE_PREP_SPLIT && has1;      // launch_prep's fp32 rows and the Q4_0 operand it writes next to them
+    int launched = -1;
+    std::vector<uint16_t> ts, te;
+    if (rows1) { ts.resize(1 << 16); te.resize(1 << 16); lut_tables(ts, te); }
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_buf = s.alloc((size_t) buf_floats, buf);
+    float *d_xp = s.alloc(xfloats, xp);      // (whatever the launch does not write keeps the caller's bits)
+    float *d_rows = staged ? s.alloc<float>((size_t) N * K) : nullptr, *d_qd = staged ? s.alloc<float>((size_t) N * (Kp / 32)) : nullptr;
+    uint32_t *d_qA = staged ? s.alloc<uint32_t>((size_t) N * (Kp / 4)) : nullptr;
+    uint16_t *d_ts = rows1 ? s.alloc(ts.size(), ts.data()) : nullptr;
+    if (s.ok()) s.check(launch_dense_act(kernel, mode, wtype, d_buf + in0_offset, has1 ? d_buf + in1_offset : nullptr, (long) in_stride, (long) in1_stride, K, N,
+                                         d_xp, d_rows, d_qA, d_qd, d_ts, st, &launched));
+    s.download(xp, d_xp, xfloats * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (kernel_taken) *kernel_taken = launched;
+    return LLAMAHIP_OK;
+}
+
+// the embedding gather of an f16 / f32 / Q4_1 model file on a caller-supplied matrix (launch_embed_dense): see llamahip.h
+int llamahip_op_embed_dense(const int32_t *tokens, int32_t N, const void *emb, int32_t wtype, int32_t V, int32_t d, float *x, int32_t x_stride,
+                            char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_embed_dense";
+    if (wtype != 0 && wtype != 1 && wtype != 3) { set_err(err, err_cap, "%s: wtype %d: 0 (fp32), 1 (fp16) or 3 (Q4_1) rows", fn, wtype); return LLAMAHIP_ERR_PREDICT; }
+    if (!tokens || !emb || !x || N < 1 || V < 1 || d < 32 || d % 32 != 0) { set_err(err, err_cap, "%s: bad arguments (N %d, V %d >= 1; d %d a multiple of 32)", fn, N, V, d); return LLAMAHIP_ERR_PREDICT; }
+    if (x_stride < d) { set_err(err, err_cap, "%s: x_stride %d < d %d", fn, x_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    for (int n = 0; n < N; n++)
+        if (tokens[n] < 0 || tokens[n] >= V) { set_err(err, err_cap, "%s: token %d of row %d outside [0, %d)", fn, tokens[n], n, V); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t xfloats = (size_t) N * x_stride;
+    const size_t emb_bytes = wtype == 3 ? (size_t) V * (d / 32) * 24 : (size_t) V * d * (wtype == 1 ? 2 : 4);
+    Scratch s;
+    hipStream_t st = s.stream();
+    int32_t *d_tok = s.alloc((size_t) N, tokens);
+    uint8_t *d_emb = s.alloc(emb_bytes, (const uint8_t *) emb);
+    float *d_x = s.alloc(xfloats, x);      // (the floats between d and x_stride keep the caller's bits)
+    float *d_rows = s.alloc<float>((size_t) N * d + 64);      // the kernels' dense [N][d] output, then 64 floats that must stay NaN
+    s.fill(d_rows, 0xFF, ((size_t) N * d + 64) * 4);
+    if (s.ok()) s.check(launch_embed_dense(d_tok, d_emb, wtype, d_rows, d, N, st));
+    if (s.ok()) s.check(hipMemcpy2DAsync(d_x, (size_t) x_stride * 4, d_rows, (size_t) d * 4, (size_t) d * 4, N, hipMemcpyDeviceToDevice, st));
+    uint32_t tail[64];
+    s.download(tail, d_rows + (size_t) N * d, sizeof(tail));
+    s.download(x, d_x, xfloats * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (uint32_t t : tail)
+        if (t != 0xFFFFFFFFu) { set_err(err, err_cap, "%s: the kernel wrote past row N - 1 of its [N][d] output", fn); return LLAMAHIP_ERR_PREDICT; }
+    return LLAMAHIP_OK;
+}
+
 // ---- the batched decode step (SeqSet) op by op: llamahip_op_set_attention, llamahip_op_set_entry, llamahip_op_set_exit (see llamahip.h) ----
 // Row r's scattered words live in cell set_cell(r) of a pool (SET_CELL_W words: [1] token in, [2] pick out, [4] position, [5] step) and its
 // row buffers (hid_in / hid_out / trace) in place set_place(r) of SET_MAX places: neither is the row order.  Every other word is 0xFF.

@@ -207,6 +207,38 @@ float orc_vec_dot_f32(int n, const float *x, const float *y) {
     return (float) sumf;
 }
 
+/* y[n][m] = orc_vec_dot_f32(W[m,:], x[n,:]): the f32 mat-mul (ggml.c:5430-5680), and the f16 one (ggml.c:5681-5985) on operands the
+ * caller has widened (weights) and rounded through fp16 (activations).  Row-parallel in the reference: no thread count enters a result. */
+void orc_mul_mat_dense(const float *w, const float *x, float *y, int M, int K, int N) {
+#pragma omp parallel for schedule(static)
+    for (int m = 0; m < M; m++)
+        for (int n = 0; n < N; n++)
+            y[(size_t) n * M + m] = orc_vec_dot_f32(K, w + (size_t) m * K, x + (size_t) n * K);
+}
+
+/* orc_vec_dot_f32 with the knobs tests/dense_cases.py turns to show that its inputs tell the reference's arithmetic from its neighbours:
+ * chains (a power of two from 8 to 64: chain c = elements c, c + chains, ...), fused (fmaf, or product and sum rounded separately),
+ * lane_order (the fold pairs c with c ^ 1, 2, 4, ... instead of the reference's c ^ 8, 16, .., 4, 1, 2: whole vectors first, then
+ * GGML_F32x8_REDUCE's lanes).  (32, 1, 0) is orc_vec_dot_f32 on n % 32 == 0. */
+float orc_vec_dot_f32_variant(int n, const float *x, const float *y, int chains, int fused, int lane_order) {
+    float s[64], t[64];
+    if (chains < 8 || chains > 64 || (chains & (chains - 1))) return NAN;
+    memset(s, 0, sizeof(s));
+    for (int i = 0; i < n; i++) {
+        float *a = &s[i % chains];
+        if (fused) *a = fmaf(x[i], y[i], *a);
+        else { const float p = x[i] * y[i]; *a = *a + p; }
+    }
+    int masks[6], nm = 0;
+    if (lane_order) for (int k = 1; k < chains; k <<= 1) masks[nm++] = k;
+    else { for (int k = 8; k < chains; k <<= 1) masks[nm++] = k; masks[nm++] = 4; masks[nm++] = 1; masks[nm++] = 2; }
+    for (int i = 0; i < nm; i++) {
+        for (int c = 0; c < chains; c++) t[c] = s[c] + s[c ^ masks[i]];
+        memcpy(s, t, sizeof(float) * (size_t) chains);
+    }
+    return s[0];
+}
+
 /* y[n][m] = W[m,:] . quantize(x[n,:])   (ggml.c:5987-6285: INIT quantizes every src1 row
  * :6134-6152, COMPUTE is row-parallel :6182-6222; results do not depend on the thread count)    */
 void orc_mul_mat_q4_0(const uint8_t *w, const float *x, float *y, int M, int K, int N, int n_threads) {

@@ -28,6 +28,8 @@ void     orc_quantize_q4_0_offline(const float *src, uint8_t *dst, long n, int k
 float    orc_vec_dot_q4_0(int n, const uint8_t *x, const uint8_t *y);            /* ggml.c:1415-1466 */
 float    orc_vec_dot_q4_0_scalar(int n, const uint8_t *x, const uint8_t *y);     /* same, lane-emulating scalar C */
 float    orc_vec_dot_f32(int n, const float *x, const float *y);                 /* ggml.c:1223-1258, :872-887 */
+void     orc_mul_mat_dense(const float *w, const float *x, float *y, int M, int K, int N);   /* ggml.c:5430-5680 / 5681-5985 on widened operands */
+float    orc_vec_dot_f32_variant(int n, const float *x, const float *y, int chains, int fused, int lane_order);   /* tests: what the inputs can tell apart */
 void     orc_mul_mat_q4_0(const uint8_t *w, const float *x, float *y, int M, int K, int N, int n_threads); /* ggml.c:5987-6285 */
 void     orc_norm_rows(const float *x, float *y, int ncols, int nrows);          /* ggml.c:5327-5385 */
 void     orc_silu_rows(const float *x, float *y, int ncols, int nrows);          /* ggml.c:1956-1963 */

@@ -453,6 +453,45 @@ void ref_mul_mat_q4_0(const void * w, const float * x, float * y, int M, int K, 
     ggml_free(c);
 }
 
+// y[N][M] = W(F32: wtype 0, F16: wtype 1; M rows of K) x X(f32, N rows of K)   -- ggml.c:5430-5680 / 5681-5985
+void ref_mul_mat_dense(const void * w, int wtype, const float * x, float * y, int M, int K, int N, int n_threads) {
+    const size_t wbytes = (size_t) M*K*(wtype == 1 ? 2 : 4);
+    auto & buf = op_arena(wbytes + (size_t) N*K*4 + (size_t) N*M*4 + (size_t) N*K*2 + (1u << 20));
+    ggml_init_params ip = { buf.size(), buf.data() };
+    ggml_context * c = ggml_init(ip);
+    ggml_tensor * tw = ggml_new_tensor_2d(c, wtype == 1 ? GGML_TYPE_F16 : GGML_TYPE_F32, K, M);
+    ggml_tensor * tx = ggml_new_tensor_2d(c, GGML_TYPE_F32, K, N);
+    memcpy(tw->data, w, wbytes);
+    memcpy(tx->data, x, sizeof(float)*(size_t) N*K);
+    ggml_tensor * ty = ggml_mul_mat(c, tw, tx);
+    ggml_cgraph gf = {};
+    gf.n_threads = n_threads;
+    ggml_build_forward_expand(&gf, ty);
+    ggml_graph_compute(c, &gf);
+    memcpy(y, ty->data, sizeof(float)*(size_t) N*M);
+    ggml_free(c);
+}
+
+// x[N][d] = rows tokens[0 .. N) of emb (V rows of d; wtype 0 F32, 1 F16, 2 Q4_0, 3 Q4_1 in file layout)   -- ggml.c:6758-6900
+void ref_get_rows(const void * emb, int wtype, const int32_t * tokens, float * x, int V, int d, int N) {
+    const ggml_type t = wtype == 0 ? GGML_TYPE_F32 : wtype == 1 ? GGML_TYPE_F16 : wtype == 2 ? GGML_TYPE_Q4_0 : GGML_TYPE_Q4_1;
+    const size_t ebytes = (size_t) V*(d/ggml_blck_size(t))*ggml_type_size(t);
+    auto & buf = op_arena(ebytes + (size_t) N*4 + (size_t) N*d*4 + (1u << 20));
+    ggml_init_params ip = { buf.size(), buf.data() };
+    ggml_context * c = ggml_init(ip);
+    ggml_tensor * te = ggml_new_tensor_2d(c, t, d, V);
+    ggml_tensor * tt = ggml_new_tensor_1d(c, GGML_TYPE_I32, N);
+    memcpy(te->data, emb, ebytes);
+    memcpy(tt->data, tokens, sizeof(int32_t)*(size_t) N);
+    ggml_tensor * tx = ggml_get_rows(c, te, tt);
+    ggml_cgraph gf = {};
+    gf.n_threads = 1;
+    ggml_build_forward_expand(&gf, tx);
+    ggml_graph_compute(c, &gf);
+    memcpy(x, tx->data, sizeof(float)*(size_t) N*d);
+    ggml_free(c);
+}
+
 // op: 0 = norm (ggml.c:5327), 1 = silu (ggml.c:5261), 2 = soft_max over rows of length ncols (ggml.c:6982)
 void ref_unary_rows(int op, const float * x, float * y, int ncols, int nrows, int n_threads) {
     auto & buf = op_arena((size_t) ncols*nrows*8 + (1u << 20));

@@ -64,6 +64,11 @@ class RefLib:
         self.has_attention = hasattr(L, "ref_attention")
         if self.has_attention:
             L.ref_attention.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32p]
+        # (likewise the dense mat-mul and the gather: tests/test_dense_op_host.py)
+        self.has_dense_ops = hasattr(L, "ref_mul_mat_dense") and hasattr(L, "ref_get_rows")
+        if self.has_dense_ops:
+            L.ref_mul_mat_dense.argtypes = [C.c_void_p, C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int]
+            L.ref_get_rows.argtypes = [C.c_void_p, C.c_int, i32p, f32p, C.c_int, C.c_int, C.c_int]
         L.refllama_tokenize.argtypes = [C.c_void_p, C.c_char_p, C.c_int, i32p, C.c_int]
         L.refllama_sampler_new.restype = C.c_void_p
         L.refllama_sampler_new.argtypes = [C.c_int32, C.c_int]
@@ -106,6 +111,28 @@ class RefLib:
         y = np.empty((N, M), np.float32)
         self.L.ref_mul_mat_q4_0(np.ascontiguousarray(wq).reshape(-1), x, y, M, K, N, n_threads)
         return y
+
+    def mul_mat_dense(self, w: np.ndarray, x: np.ndarray, n_threads: int = 1) -> np.ndarray:
+        """w float16 / float32 [M, K], x f32 [N, K] -> f32 [N, M] (ggml_mul_mat with an F16 / F32 src0)."""
+        w = np.ascontiguousarray(w)
+        assert w.dtype in (np.float16, np.float32)
+        M, K = w.shape
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        N = x.shape[0]
+        y = np.empty((N, M), np.float32)
+        self.L.ref_mul_mat_dense(w.ctypes.data_as(C.c_void_p), 1 if w.dtype == np.float16 else 0, x, y, M, K, N, n_threads)
+        return y
+
+    def get_rows(self, emb: np.ndarray, tokens, wtype: int | None = None) -> np.ndarray:
+        """emb float32 / float16 [V, d] or uint8 [V, row bytes] (wtype 2 Q4_0, 3 Q4_1: required) -> f32 [N, d] (ggml_get_rows)."""
+        emb = np.ascontiguousarray(emb)
+        wt = {np.dtype(np.float32): 0, np.dtype(np.float16): 1}[emb.dtype] if wtype is None else int(wtype)
+        V = emb.shape[0]
+        d = emb.shape[1] if wt in (0, 1) else emb.reshape(V, -1).shape[1] // (20 if wt == 2 else 24) * 32
+        tokens = np.ascontiguousarray(tokens, np.int32).ravel()
+        x = np.empty((tokens.size, d), np.float32)
+        self.L.ref_get_rows(emb.ctypes.data_as(C.c_void_p), wt, tokens, x, V, d, tokens.size)
+        return x
 
     def unary_rows(self, op: str, x: np.ndarray, n_threads: int = 1) -> np.ndarray:
         code = {"norm": 0, "silu": 1, "soft_max": 2}[op]
@@ -239,6 +266,9 @@ class OracleLib:
         L.orc_vec_dot_f32.restype = C.c_float
         L.orc_vec_dot_f32.argtypes = [C.c_int, f32p, f32p]
         L.orc_mul_mat_q4_0.argtypes = [u8p, f32p, f32p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.orc_mul_mat_dense.argtypes = [f32p, f32p, f32p, C.c_int, C.c_int, C.c_int]
+        L.orc_vec_dot_f32_variant.restype = C.c_float
+        L.orc_vec_dot_f32_variant.argtypes = [C.c_int, f32p, f32p, C.c_int, C.c_int, C.c_int]
         for fn in (L.orc_norm_rows, L.orc_silu_rows, L.orc_softmax_rows):
             fn.argtypes = [f32p, f32p, C.c_int, C.c_int]
         L.orc_rope.argtypes = [f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
@@ -292,6 +322,21 @@ class OracleLib:
         a = np.ascontiguousarray(a, np.float32).ravel()
         b = np.ascontiguousarray(b, np.float32).ravel()
         return np.float32(self.L.orc_vec_dot_f32(a.size, a, b))
+
+    def vec_dot_f32_variant(self, a, b, chains=32, fused=True, lane_order=False):
+        """orc_vec_dot_f32 with another chain count, un-fused multiply-add or the fold in lane order (tests/dense_cases.py)"""
+        a = np.ascontiguousarray(a, np.float32).ravel()
+        b = np.ascontiguousarray(b, np.float32).ravel()
+        return np.float32(self.L.orc_vec_dot_f32_variant(a.size, a, b, int(chains), int(fused), int(lane_order)))
+
+    def mul_mat_dense(self, w, x):
+        """y [N, M] = vec_dot_f32(w[m], x[n]) on float32 operands as the caller prepared them (orc_mul_mat_dense)"""
+        w = np.ascontiguousarray(w, np.float32)
+        M, K = w.shape
+        x = np.ascontiguousarray(x, np.float32).reshape(-1, K)
+        y = np.empty((x.shape[0], M), np.float32)
+        self.L.orc_mul_mat_dense(w, x, y, M, K, x.shape[0])
+        return y
 
     def mul_mat_q4_0(self, wq, x, n_threads=1):
         M, nb, _ = wq.shape

@@ -1,5 +1,5 @@
 """GPU (-m gpu): the matrix-core f16 / f32 mat-mul k_dense_mfma alone (llamahip_op_mul_mat_dense, path MFMA), bit for bit against the one-row
-kernel k_dense_mv run on each row (path MV: the kernel the dense goldens of tests/test_gpu_dense.py pin to the reference's ggml_vec_dot_f16 /
+kernel k_dense_mv run on each row (path MV: the kernel tests/test_gpu_dense_mv_op.py pins op by op to the reference's ggml_vec_dot_f16 /
 _f32).
 
 K walks the structures of the kernel's loop:  128 the 4-step tail group alone | 256 one group | 384 a group + the tail | 1280 five groups |

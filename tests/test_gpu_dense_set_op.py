@@ -1,5 +1,5 @@
 """GPU (-m gpu): the few-row f16 / f32 mat-mul k_dense_set alone (llamahip_op_mul_mat_dense, path SET), bit for bit against the one-row kernel
-k_dense_mv run on each row (path MV: the kernel the dense goldens of tests/test_gpu_dense.py pin to the reference's ggml_vec_dot_f16 / _f32);
+k_dense_mv run on each row (path MV: the kernel tests/test_gpu_dense_mv_op.py pins op by op to the reference's ggml_vec_dot_f16 / _f32);
 k_dense_mm (path MM) must equal it too.
 
 K walks the structures of the kernel's loop:  256 one group | 320 a group + a 2-step tail | 896 three groups + a 4-step tail | 1344 five groups

@@ -21,6 +21,7 @@ def test_library_exports_every_declared_symbol(L):
     missing = [s for s in L.declared_symbols() if not hasattr(lib, s)]
     assert not missing
     assert len(L.declared_symbols()) >= 25
+    assert {"llamahip_op_dense_prep", "llamahip_op_embed_dense"} <= set(L.declared_symbols())
     assert L.version().startswith("llamahip")
 
 
