@@ -887,6 +887,98 @@ int32_t llamahip_sched_plan_prefix(int32_t n_slots, const int32_t *slot_free, co
 int llamahip_kv_copy_rows(llamahip_model *m, int32_t n_copies, const int32_t *src_slot, const int32_t *dst_slot,
                           const int32_t *row_begin, const int32_t *n_rows, char *err, size_t err_cap);
 
+/* ---- the n most probable next tokens of a row; beam search over KV slots ------ */
+/* llamahip_eval_top_logprobs: llamahip_eval_logprobs' pass (its all-rows lm head, its handles and file types, its refusals) with k_row_topn
+ * (topn.hip) behind it: per row i, ids_out[i][0 .. n_top) = the row's entries by value descending, the LOWER index first on equal values
+ * (+0.0 == -0.0; ids_out[i][0] is the greedy pick), and logprob_out[i][j] = log softmax(logits_i)[ids_out[i][j]] in double -- bit for bit what
+ * llamahip_eval_logprobs reports for that target.  A row holding a NaN or a +inf: every id -1, every logprob NaN; -inf entries are ordinary
+ * and come last, in index order.  n_tokens * n_top * 12 bytes come back.  1 <= n_top <= 64 (LLAMAHIP_TOPN_MAX) and <= n_vocab.  KV cache and
+ * logits_last (may be NULL) are bit for bit llamahip_eval / llamahip_eval_chunks' (chunk_tokens 0 = one eval). */
+#define LLAMAHIP_TOPN_MAX 64
+int llamahip_eval_top_logprobs(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens, int32_t chunk_tokens,
+                               int32_t n_top, int32_t *ids_out, double *logprob_out, float *logits_last, char *err, size_t err_cap);
+/* ... its device half on caller-supplied rows logits[n_rows][n_vocab] (parity tests): ids_out / logprob_out [n_rows][n_top].  A row's result
+ * depends on its bits, n_vocab and n_top only.  Refused before any launch: a NULL array, n_rows < 1, n_vocab < 1, n_top outside 1 .. 64, n_top > n_vocab. */
+int llamahip_op_top_logprobs(const float *logits, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t *ids_out, double *logprob_out,
+                             char *err, size_t err_cap);
+
+/* llamahip_beam_search: the n_beams best continuations of one prompt, searched over KV slots [0, n_beams).
+ * SETUP.  The prompt is evaluated at position 0 on slot 0 by llamahip_eval (chunk_tokens 0) / llamahip_eval_chunks(chunk_tokens).  A live
+ *   beam is (tokens, S, slot, row): the tokens produced so far, their summed score, the KV slot that holds their rows, and the logits row its
+ *   next token is chosen from.  S is a double, S_L = S_{L-1} + lp_L, added in generation order.  The initial live list is one empty beam with
+ *   S = 0 on the prompt's last row.
+ * ONE STEP (llamahip_beam_select).  Beam i of the live list, in list order, offers the 2 * n_beams entries (id v, logprob) of k_row_topn on
+ *   its row (llamahip_op_top_logprobs with n_top = 2 * n_beams): candidates (i, v, c = S_i + logprob).  A beam whose row is non-finite (ids -1)
+ *   offers nothing -- it dies.  A candidate with a NaN c is dropped.  The candidates are ordered by c descending, then i ascending, then v
+ *   ascending, and walked in that order until n_beams live successors are collected or the candidates run out: a candidate with
+ *   v == stop_token (stop_token >= 0) goes to the finished list -- tokens = beam i's + v, score c, reason LLAMAHIP_DONE_STOP, in walk order --
+ *   every other candidate becomes the next live beam of that rank: tokens = beam i's + v, S = c.
+ * ENDING.  The step that gives the beams their n_predict-th token ends the search: its live beams join the finished list in rank order
+ *   (reason LLAMAHIP_DONE_LENGTH) and their last token is not evaluated.  Otherwise: the search ends when no live beam is left; and, only
+ *   with length_norm == 0 and stop_token >= 0, when behind a step's walk the finished list holds at least n_return entries and the
+ *   n_return-th best finished score is >= the best live S (scores only fall: logprob <= 0 by construction) -- the live beams are dropped.
+ *   Else every new live beam's last token is evaluated as a single-token step of its slot at position n_prompt + length - 1.
+ * SLOTS (llamahip_beam_slots).  In rank order the first child of a parent keeps the parent's slot; every further child takes the lowest slot
+ *   of [0, n_beams) that no beam kept and not yet taken, and receives the rows [0, rows the parent holds) of the parent's slot (k_kv_copy_rows:
+ *   one launch per stage and step, stream-ordered in front of the step, not waited for; sources are never destinations).
+ * RESULT.  The finished hypotheses ranked by S (length_norm 0) or S / length as one IEEE double division (length_norm 1), descending, ties
+ *   to the earlier entry of the finished list; the first n_return (0 = n_beams) are returned, fewer if fewer finished: *n_hyps_out of them,
+ *   hyps_out[k] = {length (a stop token counts), reason, slot, score = S}, tokens_out[k][0 .. length) of rows n_predict apart, -1 behind.
+ *   slot: for a LENGTH hypothesis the slot whose KV rows [0, n_prompt + length - 1) are that hypothesis' rows (no copy is made for the last
+ *   step, so several hypotheses may name one slot); -1 for a STOP hypothesis.  The other rows of slots [0, n_beams) are unspecified, and so
+ *   is every slot's content after an early end; slots from n_beams on and the handle's current slot are untouched.
+ * BITS.  Every live beam's logits row is bit for bit the row of llamahip_eval_chunks(prompt) followed by single-token llamahip_evals of the
+ *   beam's tokens on a slot of its own -- BY TEST (tests/test_gpu_beam_search.py), as for every set step: the norm's one-pass against
+ *   two-pass statistics.  So the result is what tests/beam_ref.py, this contract in plain Python, computes from such rows.
+ * DEVICE LOOP.  llamahip_decode_sample_multi's: the slots bound with host-written token words, one set step over the live slots
+ *   (llamahip_stage_step_set: the weights streamed once for all beams) with k_row_topn over the step's rows behind it, writing 2 * n_beams x
+ *   12 bytes per beam into pinned memory; one wait per step; select, slots, the copies, the token words.  Positions advance on the device (a
+ *   slot that sat out a step is re-bound at its position).  Plain and in-process pipeline handles; Q4_0 and f16 / f32 whole-model handles.
+ *   Handles without set steps (Q4_1 files, LLAMAHIP_FLAG_UNFUSED, f16 / f32 pipeline stages) run one llamahip_eval per live beam on its slot
+ *   with the same kernel over its device row -- the same bits -- counted in stats->n_fallback_steps.
+ * Refused before any device work, the message naming the limit, the handle last: NULL arguments, n_beams outside 1 .. 16, above
+ *   llamahip_opts.n_seq or with 2 * n_beams > n_vocab, n_prompt < 1, n_predict < 1, n_prompt + n_predict > n_ctx, a token id or a stop token
+ *   out of range, n_return outside 0 .. n_beams, chunk_tokens < 0, length_norm other than 0 or 1; HOST_ONLY and stage handles, a live
+ *   scheduler on the handle.
+ * llamahip_beam_select -- live_score[n_live], cand_ids / cand_logprob [n_live][n_cand] (n_cand <= 32; the search passes 2 * n_beams);
+ *   out: new_parent / new_token / new_score [n_beams] and *n_new, fin_parent / fin_score [n_live] and *n_fin (the finished entries of the
+ *   walk: beam fin_parent's tokens + stop_token), *n_dead (may be NULL) = live beams on a non-finite row.  0, or LLAMAHIP_ERR_PREDICT for
+ *   counts out of range or NULL arrays.
+ * llamahip_beam_slots -- prev_slot[n_prev] (distinct, in [0, n_beams)), parent[n_new] (indices into prev); out: new_slot[n_new], copy_src /
+ *   copy_dst [n_new].  Returns the number of copies, -1 for arguments it refuses.
+ * Not built: more than 16 beams; diverse or sampled beams; beams inside the scheduler; sharing the prompt rows between beams instead of
+ *   copying them. */
+#define LLAMAHIP_BEAM_MAX 16
+typedef struct llamahip_beam_opts {
+    int32_t struct_size;
+    int32_t n_threads;
+    int32_t n_beams;         /* 1 .. 16, <= llamahip_opts.n_seq, 2 * n_beams <= n_vocab */
+    int32_t n_predict;       /* >= 1 tokens per hypothesis at the most */
+    int32_t stop_token;      /* -1 = none */
+    int32_t n_return;        /* 1 .. n_beams; 0 = n_beams */
+    int32_t length_norm;     /* 0 / 1 */
+    int32_t chunk_tokens;    /* the prompt's chunking, as llamahip_eval_chunks; 0 = one eval */
+} llamahip_beam_opts;
+typedef struct llamahip_beam_hyp { int32_t length, reason /* LLAMAHIP_DONE_STOP / _LENGTH */, slot, reserved; double score; } llamahip_beam_hyp;
+typedef struct llamahip_beam_stats {
+    int32_t struct_size, reserved;
+    int64_t n_steps;             /* steps that evaluated the live beams' tokens */
+    int64_t n_rows;              /* rows those steps evaluated: the sum of their live beams */
+    int64_t n_set_steps;         /* of the steps, those on the slots' stage steps (one set step, or one stage step for a single beam) */
+    int64_t n_fallback_steps;    /* single llamahip_evals on handles without set steps */
+    int64_t n_copy_launches;     /* k_kv_copy_rows launches (one per stage and step that forked a beam) */
+    int64_t n_copied_rows;       /* KV rows (per layer, K and V counted once) those copies moved */
+    int64_t n_stop;              /* hypotheses finished by the stop token */
+    int64_t n_dead;              /* beams that died on a non-finite row */
+} llamahip_beam_stats;
+int llamahip_beam_search(llamahip_model *m, const llamahip_beam_opts *opts, const int32_t *prompt, int32_t n_prompt, llamahip_beam_hyp *hyps_out,
+                         int32_t *tokens_out, int32_t *n_hyps_out, llamahip_beam_stats *stats /* may be NULL */, char *err, size_t err_cap);
+int32_t llamahip_beam_select(int32_t n_live, const double *live_score, int32_t n_cand, const int32_t *cand_ids, const double *cand_logprob,
+                             int32_t n_beams, int32_t stop_token, int32_t *new_parent, int32_t *new_token, double *new_score, int32_t *n_new,
+                             int32_t *fin_parent, double *fin_score, int32_t *n_fin, int32_t *n_dead);
+int32_t llamahip_beam_slots(int32_t n_prev, const int32_t *prev_slot, int32_t n_new, const int32_t *parent, int32_t n_beams,
+                            int32_t *new_slot, int32_t *copy_src, int32_t *copy_dst);
+
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
 int llamahip_eval_debug(llamahip_model *m, int32_t n_threads, int32_t n_past,

@@ -31,6 +31,9 @@ DUMP_NAMES = [
 bench_gemv_names = {0: "wq|wk|wv", 1: "wo", 2: "w1|w3", 3: "w2", 4: "output"}
 
 
+DONE_LENGTH, DONE_STOP = 1, 2      # LLAMAHIP_DONE_*
+
+
 class LlamaHipError(RuntimeError):
     """Mirrors NSError(domain LlamaErrorDomain, code) (Sources/llamaObjCxx/headers/LlamaError.h:12-19)."""
 
@@ -51,6 +54,19 @@ def build(verbose: bool = False) -> str:
 
 
 _lib = None
+
+
+class _BeamOpts(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "n_threads", "n_beams", "n_predict", "stop_token", "n_return", "length_norm", "chunk_tokens")]
+
+
+class _BeamHyp(C.Structure):
+    _fields_ = [("length", C.c_int32), ("reason", C.c_int32), ("slot", C.c_int32), ("reserved", C.c_int32), ("score", C.c_double)]
+
+
+class _BeamStats(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_int64) for n in (
+        "n_steps", "n_rows", "n_set_steps", "n_fallback_steps", "n_copy_launches", "n_copied_rows", "n_stop", "n_dead")]
 
 
 class _Opts(C.Structure):
@@ -251,6 +267,13 @@ def lib() -> C.CDLL:
     L.llamahip_op_topk.argtypes = [vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, vp, vp, cp, sz]
     L.llamahip_op_topk_rows.argtypes = [vp, i32, i32, vp, vp, C.c_double, i32, C.c_double, vp, vp, vp, vp, cp, sz]
     L.llamahip_op_logprob.argtypes = [vp, i32, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_op_top_logprobs.argtypes = [vp, i32, i32, i32, vp, vp, cp, sz]
+    L.llamahip_eval_top_logprobs.argtypes = [vp, i32, i32, vp, i32, i32, i32, vp, vp, vp, cp, sz]
+    L.llamahip_beam_search.argtypes = [vp, C.POINTER(_BeamOpts), vp, i32, vp, vp, C.POINTER(i32), C.POINTER(_BeamStats), cp, sz]
+    L.llamahip_beam_select.argtypes = [i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, C.POINTER(i32), vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.llamahip_beam_select.restype = i32
+    L.llamahip_beam_slots.argtypes = [i32, vp, i32, vp, i32, vp, vp, vp]
+    L.llamahip_beam_slots.restype = i32
     L.llamahip_text_embedding.argtypes = [vp, i32, i32, vp, i32, i32, i32, i32, vp, cp, sz]
     L.llamahip_text_embedding_multi.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, vp, C.POINTER(_EvalMultiStats), cp, sz]
     L.llamahip_op_pool_rows.argtypes = [vp, i32, i32, vp, vp, i32, i32, i32, vp, cp, sz]
@@ -504,6 +527,40 @@ class Model:
                                           _ptr(last), err, len(err))
         _check(rc, err)
         return {"logprob": lp, "argmax": am, "rank": rk, "logits": last}
+
+    def eval_top_logprobs(self, tokens, n_past: int, n_top: int, n_threads: int = 8, chunk_tokens: int = 0) -> dict:
+        """llamahip_eval_top_logprobs: eval / eval_chunks (chunk_tokens 0 = one eval) + every row's n_top most probable tokens, reduced on the
+        device: ids int32 [N, n_top] (value descending, the lower index first on ties), logprob float64 [N, n_top], logits (the last row's)."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        N, n = tokens.size, max(int(n_top), 0)
+        ids, lp = np.empty((N, n), np.int32), np.empty((N, n), np.float64)
+        last = np.empty(self.n_vocab, np.float32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_eval_top_logprobs(self._h, n_threads, n_past, _ptr(tokens), N, chunk_tokens, n_top, _ptr(ids), _ptr(lp), _ptr(last), err, len(err))
+        _check(rc, err)
+        return {"ids": ids, "logprob": lp, "logits": last}
+
+    def beam_search(self, prompt, n_beams: int, n_predict: int, stop_token: int = -1, n_return: int = 0, length_norm: bool = False,
+                    chunk_tokens: int = 0, n_threads: int = 8, with_stats: bool = False):
+        """llamahip_beam_search: the best continuations of `prompt` searched over KV slots [0, n_beams) (include/llamahip.h states the contract).
+        Returns a list of dicts, best first: tokens (int32 array), length, reason ("stop" / "length"), slot (-1 for a stop hypothesis),
+        score (the summed log-probability, float64); with_stats: (that list, the llamahip_beam_stats counters as a dict)."""
+        prompt = np.ascontiguousarray(prompt, np.int32)
+        o = _BeamOpts(C.sizeof(_BeamOpts), n_threads, n_beams, n_predict, stop_token, n_return, int(length_norm), chunk_tokens)
+        cap = max(n_return or n_beams, 1)
+        hyps = (_BeamHyp * cap)()
+        toks = np.full((cap, max(n_predict, 1)), -1, np.int32)
+        n = C.c_int32(0)
+        st = _BeamStats()
+        st.struct_size = C.sizeof(_BeamStats)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_beam_search(self._h, C.byref(o), _ptr(prompt), prompt.size, C.cast(hyps, C.c_void_p), _ptr(toks), C.byref(n), C.byref(st), err, len(err))
+        _check(rc, err)
+        out = [{"tokens": toks[k, : hyps[k].length].copy(), "length": int(hyps[k].length), "reason": "stop" if hyps[k].reason == DONE_STOP else "length",
+                "slot": int(hyps[k].slot), "score": float(hyps[k].score)} for k in range(n.value)]
+        if not with_stats:
+            return out
+        return out, {f: int(getattr(st, f)) for f, _ in _BeamStats._fields_ if f.startswith("n_")}
 
     def perplexity(self, tokens, window: int = 0, score_from: int = -1, n_threads: int = 8, chunk_tokens: int = 0) -> dict:
         """Perplexity of a token stream over windows of `window` tokens (0 = n_ctx; the partial tail is unused), rows from score_from
@@ -1340,6 +1397,53 @@ def op_logprob(logits2d, targets=None):
     rc = lib().llamahip_op_logprob(_ptr(logits2d), R, V, _ptr(targets), _ptr(lp), _ptr(am), _ptr(rk), err, len(err))
     _check(rc, err)
     return lp, am, rk
+
+
+def op_top_logprobs(logits2d, n_top: int):
+    """k_row_topn on host rows f32 [n_rows, n_vocab]: returns (ids int32 [n_rows, n_top], logprob float64 [n_rows, n_top]) -- per row the n_top
+    entries by value descending (the lower index first on ties) with their log-probabilities; a row with a NaN or a +inf: ids -1, logprobs NaN."""
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    n = min(max(int(n_top), 0), 1024)
+    ids, lp = np.empty((R, n), np.int32), np.empty((R, n), np.float64)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_top_logprobs(_ptr(logits2d), R, V, n_top, _ptr(ids), _ptr(lp), err, len(err))
+    _check(rc, err)
+    return ids, lp
+
+
+def beam_select(live_score, cand_ids, cand_logprob, n_beams: int, stop_token: int = -1) -> dict:
+    """llamahip_beam_select, the step rule of llamahip_beam_search (host only): live_score [n_live], cand_ids / cand_logprob [n_live, n_cand].
+    Returns parent / token / score of the new live beams in rank order, fin_parent / fin_score of the walk's finished entries, n_dead."""
+    sc = np.ascontiguousarray(live_score, np.float64).reshape(-1)
+    ids = np.ascontiguousarray(cand_ids, np.int32).reshape(sc.size, -1)
+    lp = np.ascontiguousarray(cand_logprob, np.float64).reshape(sc.size, -1)
+    if ids.shape != lp.shape:
+        raise ValueError("cand_ids and cand_logprob differ in shape")
+    cap = max(n_beams, 1)
+    par, tok, nsc = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+    fpar, fsc = np.zeros(max(sc.size, 1), np.int32), np.zeros(max(sc.size, 1), np.float64)
+    nn, nf, nd = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = lib().llamahip_beam_select(sc.size, _ptr(sc), ids.shape[1], _ptr(ids), _ptr(lp), n_beams, stop_token, _ptr(par), _ptr(tok), _ptr(nsc), C.byref(nn),
+                                    _ptr(fpar), _ptr(fsc), C.byref(nf), C.byref(nd))
+    if rc != 0:
+        raise LlamaHipError(-1, f"llamahip_beam_select refused its arguments (n_live {sc.size}, n_cand {ids.shape[1]}, n_beams {n_beams})")
+    return {"parent": par[: nn.value].copy(), "token": tok[: nn.value].copy(), "score": nsc[: nn.value].copy(),
+            "fin_parent": fpar[: nf.value].copy(), "fin_score": fsc[: nf.value].copy(), "n_dead": nd.value}
+
+
+def beam_slots(prev_slot, parent, n_beams: int):
+    """llamahip_beam_slots (host only): the slots of a step's new beams and the KV copies [(src slot, dst slot), ...] they need."""
+    prev = np.ascontiguousarray(prev_slot, np.int32).reshape(-1)
+    par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+    cap = max(par.size, 1)
+    ns, cs, cd = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+    n = lib().llamahip_beam_slots(prev.size, _ptr(prev), par.size, _ptr(par), n_beams, _ptr(ns), _ptr(cs), _ptr(cd))
+    if n < 0:
+        raise LlamaHipError(-1, f"llamahip_beam_slots refused its arguments (n_prev {prev.size}, n_new {par.size}, n_beams {n_beams})")
+    return ns[: par.size].copy(), [(int(cs[k]), int(cd[k])) for k in range(n)]
 
 
 def _pool_id(pool) -> int:

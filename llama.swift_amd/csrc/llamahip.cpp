@@ -216,6 +216,10 @@ struct llamahip_model {
     bool output_copies_tried = false;    // ... and of `output`, for the scoring entry points' all-rows lm head (ensure_output_copies)
     void *d_score = nullptr;             // scoring of N rows: [N] logprob (double) | [N] argmax | [N] rank | [N] targets (score_io)
     int score_cap = 0;
+    char *beam_blk = nullptr;            // llamahip_beam_search (last stage): pinned, mapped -- [16][32] logprob (double) | [16][32] ids; beam_dev: its device alias
+    char *beam_dev = nullptr;
+    char *d_topn = nullptr;              // the top-n places of N rows (last stage; topn_enqueue): [N][n] logprob (double) | [N][n] ids
+    size_t topn_cap = 0;                 // ... its bytes
     // a text's embedding (last stage; embed_ensure): out [embed_segs_cap][d] | seg_begin [embed_segs_cap + 1] | the fp32 norm rows y [embed_rows_cap][d],
     // and the host copy seg_begin is uploaded from
     char *d_embed = nullptr;
@@ -957,6 +961,10 @@ int32_t score_multi_rows(int32_t n_seqs, const int32_t *tokens, const int32_t *n
 void score_scatter(int32_t R, int32_t nl, const int32_t *scored, const void *packed, double *lp, int32_t *am, int32_t *rk);
 int score_choices_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const int32_t *context, int32_t n_context, int32_t n_choices,
                         const int32_t *endings, const int32_t *n_ending, int32_t chunk_tokens, char *err, size_t err_cap);
+// beam.cpp: what llamahip_beam_search refuses of its arguments, and the ranking of its finished hypotheses
+int beam_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const llamahip_beam_opts *o, const int32_t *prompt, int32_t n_prompt,
+               const void *hyps_out, const void *tokens_out, const void *n_hyps_out, char *err, size_t err_cap);
+void beam_rank(int32_t n, const double *score, const int32_t *length, int32_t length_norm, int32_t *order);
 // ... and llamahip_text_embedding[_multi] of theirs
 int embed_check(const char *fn, int32_t n_ctx, int32_t n_vocab, int32_t n_slots, int32_t sched_max_active, int32_t n_seqs, const int32_t *slots,
                 const int32_t *n_past, const int32_t *tokens, const int32_t *n_tokens, int32_t chunk_tokens, int32_t pool, int32_t normalize,
@@ -2090,15 +2098,35 @@ static int score_fetch(llamahip_model *m, int N, double *lp, int32_t *am, int32_
     return 0;
 }
 
+// llamahip_eval_top_logprobs: k_row_topn over the N rows of m->logits in k_row_logprob's place, ordered behind the eval on m->stream
+static int topn_enqueue(llamahip_model *m, int N, int n_top, char *err, size_t err_cap) {
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    const size_t cells = (size_t) N * n_top, bytes = cells * 12;
+    if (bytes > m->topn_cap) {
+        m->own.release(&m->d_topn); m->topn_cap = 0;
+        HIP_TRY(m->own.alloc(&m->d_topn, bytes), LLAMAHIP_ERR_PREDICT);
+        m->topn_cap = bytes;
+    }
+    HIP_TRY(launch_row_topn(m->logits, N, m->hp.n_vocab, n_top, (int32_t *) (m->d_topn + cells * 8), (double *) m->d_topn, m->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+static int topn_fetch(llamahip_model *m, int N, int n_top, double *lp, int32_t *ids, char *err, size_t err_cap) {
+    const size_t cells = (size_t) N * n_top;
+    HIP_TRY(hipMemcpy(lp, m->d_topn, cells * 8, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipMemcpy(ids, m->d_topn + cells * 8, cells * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
 // one eval of N rows at n_past (chunk: the key split of llamahip_eval_chunks, 0 = none) + the scores of its rows, on a plain or a pipeline handle
+// (n_top > 0: the rows' top-n places instead -- lp [N][n_top], am = the ids [N][n_top], targets and rk unused)
 static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int chunk, const int32_t *targets,
-                      double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap) {
+                      double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap, int n_top = 0) {
     const double t0 = now_ms();
     llamahip_model *last = m;
     int rc;
     if (m->stages.empty()) {
         if ((rc = eval_stage_enqueue(m, n_threads, n_past, tokens, N, nullptr, chunk, true, err, err_cap)) != 0) return rc;
-        if ((rc = score_enqueue(m, N, targets, err, err_cap)) != 0) return rc;
+        if ((rc = n_top ? topn_enqueue(m, N, n_top, err, err_cap) : score_enqueue(m, N, targets, err, err_cap)) != 0) return rc;
         HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
         if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
     } else {
@@ -2113,11 +2141,11 @@ static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, cons
             if (s + 1 < S && (rc = pipe_hand_off(st, m->stages[s + 1], m->stages[s + 1]->pipe_in, st->x, (size_t) N * d * 4, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         }
         last = m->stages[S - 1];
-        if ((rc = score_enqueue(last, N, targets, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
+        if ((rc = n_top ? topn_enqueue(last, N, n_top, err, err_cap) : score_enqueue(last, N, targets, err, err_cap)) != 0) { (void) pipe_sync(m, nullptr, 0); return rc; }
         if ((rc = pipe_sync(m, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
     }
-    if ((rc = score_fetch(last, N, lp, am, rk, err, err_cap)) != 0) return rc;
+    if ((rc = n_top ? topn_fetch(last, N, n_top, lp, am, err, err_cap) : score_fetch(last, N, lp, am, rk, err, err_cap)) != 0) return rc;
     const size_t V = m->hp.n_vocab;
     if (logits_last) HIP_TRY(hipMemcpy(logits_last, last->logits + (size_t) (N - 1) * V, V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
     m->n_evals++;
@@ -2128,13 +2156,14 @@ static int eval_score(llamahip_model *m, int32_t n_threads, int32_t n_past, cons
 // llamahip_eval_chunks' split: Q4_0 files in one pass, f16 / f32 files too from DENSE_ONE_PASS_MIN_ROWS rows, else (and Q4_1 files) chunk by
 // chunk, each chunk's rows scored
 static int logprobs_impl(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t N, int32_t chunk_tokens,
-                         const int32_t *targets, double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap) {
+                         const int32_t *targets, double *lp, int32_t *am, int32_t *rk, float *logits_last, char *err, size_t err_cap, int n_top = 0) {
     const bool chunked = chunk_tokens > 0 && N > chunk_tokens;
-    if (!chunked || chunks_in_one_pass(m, N)) return eval_score(m, n_threads, n_past, tokens, N, chunked ? chunk_tokens : 0, targets, lp, am, rk, logits_last, err, err_cap);
+    if (!chunked || chunks_in_one_pass(m, N)) return eval_score(m, n_threads, n_past, tokens, N, chunked ? chunk_tokens : 0, targets, lp, am, rk, logits_last, err, err_cap, n_top);
+    const size_t w = n_top ? n_top : 1;      // (cells per row of lp / am)
     for (int32_t c0 = 0; c0 < N; c0 += chunk_tokens) {
         const int32_t n = std::min(chunk_tokens, N - c0);
-        const int rc = eval_score(m, n_threads, n_past + c0, tokens + c0, n, 0, targets + c0, lp ? lp + c0 : nullptr, am ? am + c0 : nullptr,
-                                  rk ? rk + c0 : nullptr, c0 + n == N ? logits_last : nullptr, err, err_cap);
+        const int rc = eval_score(m, n_threads, n_past + c0, tokens + c0, n, 0, targets ? targets + c0 : nullptr, lp ? lp + c0 * w : nullptr, am ? am + c0 * w : nullptr,
+                                  rk ? rk + c0 : nullptr, c0 + n == N ? logits_last : nullptr, err, err_cap, n_top);
         if (rc) return rc;
     }
     return LLAMAHIP_OK;
@@ -2167,6 +2196,18 @@ int llamahip_eval_logprobs(llamahip_model *m, int32_t n_threads, int32_t n_past,
     if (targets) std::copy(targets, targets + n_tokens, tgt.begin());
     else for (int i = 0; i + 1 < n_tokens; i++) tgt[i] = tokens[i + 1];
     return logprobs_impl(m, n_threads, n_past, tokens, n_tokens, chunk_tokens, tgt.data(), logprob_out, argmax_out, rank_out, logits_last, err, err_cap);
+}
+
+int llamahip_eval_top_logprobs(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens, int32_t chunk_tokens,
+                               int32_t n_top, int32_t *ids_out, double *logprob_out, float *logits_last, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_top_logprobs";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (n_top < 1 || n_top > TOPN_MAX) { set_err(err, err_cap, "%s: n_top %d outside 1 .. %d", fn, n_top, TOPN_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_top > m->hp.n_vocab) { set_err(err, err_cap, "%s: n_top %d > n_vocab %d", fn, n_top, m->hp.n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (!ids_out || !logprob_out) { set_err(err, err_cap, "%s: %s is NULL", fn, !ids_out ? "ids_out" : "logprob_out"); return LLAMAHIP_ERR_PREDICT; }
+    const int rc = check_score_args(m, n_past, tokens, n_tokens, chunk_tokens, nullptr, fn, err, err_cap);
+    if (rc) return rc;
+    return logprobs_impl(m, n_threads, n_past, tokens, n_tokens, chunk_tokens, nullptr, logprob_out, ids_out, nullptr, logits_last, err, err_cap, n_top);
 }
 
 int llamahip_perplexity(llamahip_model *m, int32_t n_threads, const int32_t *tokens, int32_t n_tokens, int32_t window,
@@ -3859,6 +3900,192 @@ int llamahip_decode_sample_multi(llamahip_model *m, int32_t n_threads, int32_t n
         if (state[2 * i] != n_past[i] + n_steps) { set_err(err, err_cap, "%s: sequence %d ended at position %d, not %d", F, i, state[2 * i], n_past[i] + n_steps); return LLAMAHIP_ERR_PREDICT; }
     m->n_evals += (int64_t) n_seqs * n_steps;
     m->t_eval_ms += now_ms() - t0;
+    if (!m->stages.empty()) m->pipe_hand_off = 1;
+    return LLAMAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// llamahip_beam_search (llamahip.h): llamahip_decode_sample_multi's loop -- slots bound with host-written token words, one
+// set step over the live slots, a device reduction behind it (step_group's hook: k_row_topn over the step's rows into pinned memory), one
+// wait per step -- with the beams' bookkeeping between the steps: the step rule (llamahip_beam_select), the slots and the KV copies
+// (llamahip_beam_slots; one k_kv_copy_rows launch per stage, stream-ordered in front of the step) and the token words.  One group whatever
+// the stage count: the live set changes from step to step and every step waits for its candidates anyway.
+// ------------------------------------------------------------------------------------------------
+constexpr int BEAM_CAND_MAX = 2 * LLAMAHIP_BEAM_MAX;
+static int beam_prepare(llamahip_model *last, char *err, size_t err_cap) {
+    if (last->beam_blk) return 0;
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(last->own.alloc(&last->beam_blk, (size_t) LLAMAHIP_BEAM_MAX * BEAM_CAND_MAX * 12, true, MEM_PINNED), LLAMAHIP_ERR_PREDICT);
+    const hipError_t e = hipHostGetDevicePointer((void **) &last->beam_dev, last->beam_blk, 0);
+    if (e != hipSuccess) last->own.release(&last->beam_blk);
+    HIP_TRY(e, LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// k_row_topn over R rows of the last stage's logits from `row` on, nc places each, results at index i0 .. of the pinned block
+static int beam_topn(llamahip_model *last, const float *row, int R, int nc, int i0, char *err, size_t err_cap) {
+    double *lp = (double *) last->beam_dev;
+    int32_t *ids = (int32_t *) (last->beam_dev + (size_t) LLAMAHIP_BEAM_MAX * BEAM_CAND_MAX * 8);
+    HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(launch_row_topn(row, R, last->hp.n_vocab, nc, ids + (size_t) i0 * nc, lp + (size_t) i0 * nc, last->stream), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+
+int llamahip_beam_search(llamahip_model *m, const llamahip_beam_opts *o, const int32_t *prompt, int32_t n_prompt, llamahip_beam_hyp *hyps_out,
+                         int32_t *tokens_out, int32_t *n_hyps_out, llamahip_beam_stats *stats, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_beam_search";
+    if (!m) { set_err(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
+    int rc = beam_check(m->hp.n_ctx, m->hp.n_vocab, m->n_seq, o, prompt, n_prompt, hyps_out, tokens_out, n_hyps_out, err, err_cap);
+    if (rc) return rc;
+    if (m->sched) { set_err(err, err_cap, "%s: the handle has a live scheduler, which owns KV slots 0 .. %d: free it first", fn, sched_dev_max_active(m->sched) - 1); return LLAMAHIP_ERR_PREDICT; }
+    if ((rc = decode_handle_check(m, fn, err, err_cap)) != 0) return rc;
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    const int S = (int) stages.size();
+    llamahip_model *first = stages[0], *last = stages[S - 1];
+    const int B = o->n_beams, nc = 2 * B, P0 = n_prompt, T = o->n_predict, V = m->hp.n_vocab, nth = o->n_threads;
+    const int n_return = o->n_return ? o->n_return : B;
+    const size_t d = first->hp.n_embd;
+    const bool set_path = multi_stage_steps(first);
+    llamahip_beam_stats bs;
+    memset(&bs, 0, sizeof(bs));
+    bs.struct_size = (int32_t) sizeof(bs);
+    *n_hyps_out = 0;
+    if ((rc = beam_prepare(last, err, err_cap)) != 0) return rc;
+    const double *h_lp = (const double *) last->beam_blk;
+    const int32_t *h_ids = (const int32_t *) (last->beam_blk + (size_t) LLAMAHIP_BEAM_MAX * BEAM_CAND_MAX * 8);
+
+    // the prompt on slot 0 (enqueued and waited for as the entry point it is); its last row stays where the last pass left it
+    const int32_t zero = 0;
+    const int chunk = o->chunk_tokens;
+    rc = each_slot(m, 1, &zero, err, err_cap, [&](int) {
+        return chunk > 0 ? eval_chunks_impl(m, nth, 0, prompt, P0, chunk, nullptr, true, err, err_cap) : llamahip_eval(m, nth, 0, prompt, P0, nullptr, err, err_cap); });
+    if (rc) return rc;
+    const int n_last_pass = (chunk > 0 && P0 > chunk && !chunks_in_one_pass(m, P0)) ? P0 - (P0 - 1) / chunk * chunk : P0;
+    if ((rc = beam_topn(last, last->logits + (size_t) (n_last_pass - 1) * V, 1, nc, 0, err, err_cap)) != 0) return drain_stages(stages, rc, err, err_cap);
+    if ((rc = drain_stages(stages, 0, err, err_cap)) != 0) return rc;
+
+    struct Beam { std::vector<int32_t> tokens; double S; int32_t slot, row; };
+    struct Fin { std::vector<int32_t> tokens; double S; int32_t reason, slot; };
+    std::vector<Beam> live(1), next;
+    live[0].S = 0.0; live[0].slot = 0; live[0].row = 0;
+    std::vector<Fin> fin;
+    bool bound = false;
+    std::vector<int32_t> dev_pos((size_t) B, P0);      // the slots' device positions (set steps)
+    // slot `slot` of every stage at position `pos`, multi_begin's pointers (the same ones: no graph is dropped)
+    auto rebind = [&](int slot, int pos) {
+        for (int s = 0; s < S; s++) {
+            llamahip_model *st = stages[s];
+            const int r = llamahip_stage_bind(st, slot, pos, s == 0 ? first->smp_d.tok + slot : nullptr, s ? st->mq_in + (size_t) slot * d : nullptr,
+                                              s + 1 < S ? st->mq_out + (size_t) slot * d : nullptr, nullptr, err, err_cap);
+            if (r) return r;
+        }
+        return 0;
+    };
+    const int save_seq = m->cur_seq;
+    for (int t = 1; rc == 0; t++) {
+        // ---- the step rule over the live beams' candidates
+        const int L = (int) live.size();
+        double sc[LLAMAHIP_BEAM_MAX], c_lp[LLAMAHIP_BEAM_MAX * BEAM_CAND_MAX], new_S[LLAMAHIP_BEAM_MAX], fin_S[LLAMAHIP_BEAM_MAX];
+        int32_t c_id[LLAMAHIP_BEAM_MAX * BEAM_CAND_MAX], new_par[LLAMAHIP_BEAM_MAX], new_tok[LLAMAHIP_BEAM_MAX], fin_par[LLAMAHIP_BEAM_MAX], n_new = 0, n_fin = 0, n_dead = 0;
+        for (int i = 0; i < L; i++) {
+            sc[i] = live[i].S;
+            memcpy(c_lp + (size_t) i * nc, h_lp + (size_t) live[i].row * nc, (size_t) nc * 8);
+            memcpy(c_id + (size_t) i * nc, h_ids + (size_t) live[i].row * nc, (size_t) nc * 4);
+        }
+        if (llamahip_beam_select(L, sc, nc, c_id, c_lp, B, o->stop_token, new_par, new_tok, new_S, &n_new, fin_par, fin_S, &n_fin, &n_dead) != 0) {
+            set_err(err, err_cap, "%s: llamahip_beam_select refused a step of %d beams", fn, L); rc = LLAMAHIP_ERR_PREDICT; break; }
+        bs.n_dead += n_dead; bs.n_stop += n_fin;
+        for (int k = 0; k < n_fin; k++) {
+            Fin f = { live[fin_par[k]].tokens, fin_S[k], LLAMAHIP_DONE_STOP, -1 };
+            f.tokens.push_back(o->stop_token);
+            fin.push_back(std::move(f));
+        }
+        next.assign((size_t) n_new, Beam());
+        for (int k = 0; k < n_new; k++) {
+            next[k].tokens = live[new_par[k]].tokens;
+            next[k].tokens.push_back(new_tok[k]);
+            next[k].S = new_S[k];
+        }
+        if (t == T) {      // the last token is not evaluated: the hypothesis' rows are its parent's
+            for (int k = 0; k < n_new; k++) fin.push_back({ std::move(next[k].tokens), next[k].S, LLAMAHIP_DONE_LENGTH, live[new_par[k]].slot });
+            break;
+        }
+        if (n_new == 0) break;
+        if (!o->length_norm && o->stop_token >= 0 && (int) fin.size() >= n_return) {
+            std::vector<double> fs;
+            for (const Fin &f : fin) fs.push_back(f.S);
+            std::sort(fs.begin(), fs.end(), [](double a, double b) { return a > b; });
+            if (fs[(size_t) n_return - 1] >= next[0].S) break;
+        }
+        // ---- the slots, and the forked beams' rows: rows [0, P) of the parent's slot
+        const int P = P0 + t - 1;      // the position the new tokens are evaluated at = the rows a parent holds
+        int32_t prev_slot[LLAMAHIP_BEAM_MAX], new_slot[LLAMAHIP_BEAM_MAX], c_src[LLAMAHIP_BEAM_MAX], c_dst[LLAMAHIP_BEAM_MAX];
+        for (int i = 0; i < L; i++) prev_slot[i] = live[i].slot;
+        const int n_copies = llamahip_beam_slots(L, prev_slot, n_new, new_par, B, new_slot, c_src, c_dst);
+        if (n_copies < 0) { set_err(err, err_cap, "%s: llamahip_beam_slots refused a step of %d beams", fn, n_new); rc = LLAMAHIP_ERR_PREDICT; break; }
+        if (n_copies > 0) {
+            KvCopyTab tab = {};
+            tab.n = n_copies;
+            for (int c = 0; c < n_copies; c++) { tab.src[c] = c_src[c]; tab.dst[c] = c_dst[c]; tab.row_begin[c] = 0; tab.n_rows[c] = P; }
+            if ((rc = kv_copy_enqueue(stages, tab, fn, err, err_cap)) != 0) break;
+            bs.n_copy_launches += S; bs.n_copied_rows += (int64_t) n_copies * P;
+        }
+        // ---- the step: the live slots in ascending order (a set orders its rows by slot id), beam k's candidates at index next[k].row
+        std::vector<int32_t> act((size_t) n_new);
+        for (int k = 0; k < n_new; k++) { next[k].slot = new_slot[k]; act[k] = new_slot[k]; }
+        std::sort(act.begin(), act.end());
+        for (int k = 0; k < n_new; k++) next[k].row = (int32_t) (std::lower_bound(act.begin(), act.end(), next[k].slot) - act.begin());
+        if (set_path) {
+            if (!bound) {
+                std::vector<int32_t> past((size_t) B, P0);
+                if ((rc = multi_begin(stages, 1, B, past.data(), nullptr, err, err_cap)) != 0) break;
+                bound = true;
+            }
+            for (int k = 0; k < n_new && rc == 0; k++) {
+                const int sl = next[k].slot;
+                if (dev_pos[sl] != P) rc = rebind(sl, P);      // (a slot that sat out a step)
+                dev_pos[sl] = P + 1;
+                first->smp_h.tok[sl] = next[k].tokens.back();
+            }
+            if (rc) break;
+            rc = step_group(stages, { act.data(), n_new, 0, B, 0 }, nth, false, false,
+                            [&](int j, int R) { return beam_topn(last, last->logits, R, nc, j, err, err_cap); }, err, err_cap);
+            if (rc == 0) rc = pipe_wait_stage(last, S - 1, err, err_cap, last->mq_ev[0]);
+            bs.n_set_steps++;
+        } else {
+            // no stage step to batch (Q4_1 files, f16 / f32 pipeline stages, LLAMAHIP_FLAG_UNFUSED): llamahip_eval on each live slot in turn, the
+            // same kernel over its row (the copies above are on the stages' streams, ahead of the evals)
+            for (int j = 0; j < n_new && rc == 0; j++) {
+                int k = 0;
+                while (next[k].row != j) k++;
+                const int32_t tok = next[k].tokens.back();
+                if ((rc = llamahip_set_seq(m, act[j], err, err_cap)) != 0) break;
+                if ((rc = llamahip_eval(m, nth, P, &tok, 1, nullptr, err, err_cap)) != 0) break;
+                rc = beam_topn(last, last->logits, 1, nc, j, err, err_cap);
+                if (rc == 0 && hipStreamSynchronize(last->stream) != hipSuccess) { set_err(err, err_cap, "%s: HIP error waiting for k_row_topn", fn); rc = LLAMAHIP_ERR_PREDICT; }
+                bs.n_fallback_steps++;
+            }
+        }
+        bs.n_steps++; bs.n_rows += n_new;
+        live.swap(next);
+    }
+    (void) llamahip_set_seq(m, save_seq, nullptr, 0);
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+
+    // ---- the result: the finished list ranked
+    const int nf = (int) fin.size();
+    std::vector<double> fS((size_t) nf);
+    std::vector<int32_t> fL((size_t) nf), order((size_t) nf);
+    for (int k = 0; k < nf; k++) { fS[k] = fin[k].S; fL[k] = (int32_t) fin[k].tokens.size(); }
+    beam_rank(nf, fS.data(), fL.data(), o->length_norm, order.data());
+    const int n_out = std::min(nf, n_return);
+    for (int k = 0; k < n_out; k++) {
+        const Fin &f = fin[order[k]];
+        hyps_out[k].length = (int32_t) f.tokens.size(); hyps_out[k].reason = f.reason; hyps_out[k].slot = f.slot; hyps_out[k].reserved = 0; hyps_out[k].score = f.S;
+        int32_t *row = tokens_out + (size_t) k * T;
+        for (int j = 0; j < T; j++) row[j] = j < (int) f.tokens.size() ? f.tokens[j] : -1;
+    }
+    *n_hyps_out = n_out;
+    if (stats) { const int32_t n = std::min((size_t) std::max(stats->struct_size, 0), sizeof(bs)); if (n >= 4) { bs.struct_size = n; memcpy(stats, &bs, (size_t) n); } }
     if (!m->stages.empty()) m->pipe_hand_off = 1;
     return LLAMAHIP_OK;
 }

@@ -338,6 +338,11 @@ constexpr size_t SLIDE_SET_IDS = 16 * 1024 + 16;
 // on ties) and the target's rank (entries strictly greater); target -1: not scored.  A row's result depends on its bits and V only.
 hipError_t launch_row_logprob(const float *logits, int n_rows, int V, const int32_t *targets, double *lp_out, int32_t *am_out, int32_t *rk_out,
                               hipStream_t st);
+// the n <= TOPN_MAX most probable entries of n_rows rows of logits (topn.hip): per row ids[n] (value descending, the lower index first on equal
+// values) and logprob[n], bit for bit launch_row_logprob's for those targets; a row with a NaN or a +inf: ids -1, logprobs NaN.  A row's result
+// depends on its bits, V and n only.  Refused (hipErrorInvalidValue, nothing launched): n_rows < 1, V < 1, n outside 1 .. TOPN_MAX, n > V.
+constexpr int TOPN_MAX = 64;
+hipError_t launch_row_topn(const float *logits, int n_rows, int V, int n, int32_t *ids_out, double *lp_out, hipStream_t st);
 // a text's embedding (pool.hip): the final norm of n_rows rows x[n_rows][d] as plain fp32 rows y (k_dense_prep<PREP_NORM>'s arithmetic, no fp16
 // rounding, no permutation); then out[s] = the last row (pool 0) or the mean in double over rows [seg_begin[s], seg_begin[s + 1]) of y in ascending
 // row order (pool 1), and with normalize the row divided by its L2 length (64 lane sums folded by the xor butterfly; a zero row stays zero)

@@ -980,6 +980,32 @@ int llamahip_op_logprob(const float *logits, int32_t n_rows, int32_t n_vocab, co
     return LLAMAHIP_OK;
 }
 
+// k_row_topn on caller-supplied rows (parity tests): see llamahip_eval_top_logprobs
+int llamahip_op_top_logprobs(const float *logits, int32_t n_rows, int32_t n_vocab, int32_t n_top, int32_t *ids_out, double *logprob_out,
+                             char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_top_logprobs";
+    if (!logits || !ids_out || !logprob_out) { set_err(err, err_cap, "%s: %s is NULL", fn, !logits ? "logits" : !ids_out ? "ids_out" : "logprob_out"); return LLAMAHIP_ERR_PREDICT; }
+    if (n_rows < 1) { set_err(err, err_cap, "%s: n_rows must be >= 1 (got %d)", fn, n_rows); return LLAMAHIP_ERR_PREDICT; }
+    if (n_vocab < 1) { set_err(err, err_cap, "%s: n_vocab must be >= 1 (got %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_top < 1 || n_top > TOPN_MAX) { set_err(err, err_cap, "%s: n_top %d outside 1 .. %d", fn, n_top, TOPN_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_top > n_vocab) { set_err(err, err_cap, "%s: n_top %d > n_vocab %d", fn, n_top, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows * (size_t) n_top;
+    Scratch s;
+    float *d_l = s.alloc((size_t) n_rows * (size_t) n_vocab, logits);
+    double *d_lp = s.alloc<double>(N);
+    int32_t *d_id = s.alloc<int32_t>(N);
+    if (s.ok()) s.check(launch_row_topn(d_l, n_rows, n_vocab, n_top, d_id, d_lp, nullptr));
+    std::vector<double> hl(N);
+    std::vector<int32_t> hi(N);
+    s.download(hl.data(), d_lp, N * 8);
+    s.download(hi.data(), d_id, N * 4);
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    std::copy(hl.begin(), hl.end(), logprob_out);
+    std::copy(hi.begin(), hi.end(), ids_out);
+    return LLAMAHIP_OK;
+}
+
 // the tail of an embedding pass on caller-supplied rows (parity tests): see llamahip_text_embedding.  LAST: the segments' last rows gathered first,
 // the norm over those rows alone -- forward_rows' launches
 int llamahip_op_pool_rows(const float *x, int32_t R, int32_t d, const float *norm_w, const int32_t *seg_begin, int32_t n_segs, int32_t pool, int32_t normalize,

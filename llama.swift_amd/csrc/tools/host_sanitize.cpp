@@ -118,6 +118,10 @@ int decode_handle_check(const llamahip_model *m, const char *fn, char *err, size
     if (!m) { snprintf(err, err_cap, "%s: null model", fn); return LLAMAHIP_ERR_PREDICT; }
     return 0;
 }
+// beam.cpp (compiled in as it is): what llamahip_beam_search refuses of its arguments, the ranking of its finished hypotheses
+int beam_check(int32_t n_ctx, int32_t n_vocab, int32_t n_slots, const llamahip_beam_opts *o, const int32_t *prompt, int32_t n_prompt,
+               const void *hyps_out, const void *tokens_out, const void *n_hyps_out, char *err, size_t err_cap);
+void beam_rank(int32_t n, const double *score, const int32_t *length, int32_t length_norm, int32_t *order);
 }
 
 // the request scheduler's device half (sched.h), stubbed: every planned step is logged segment by segment, exactly sized copies of what the host
@@ -416,6 +420,121 @@ __attribute__((noinline)) static void embedding_host_half(int V) {
         refused(fo, [&](char *e, size_t cap) { return lh::pool_rows_check(x, 17, 32, w, seg17.data(), 17, 0, 0, out1, e, cap); });
     }
     printf("host_sanitize: text embeddings: %ld refusals at short and missing message buffers\n", n_checks);
+}
+
+// beam search (llamahip_beam_search): the step rule and the slots on exactly sized arrays over a grid of beam counts, candidate tables with
+// ties, stop candidates, NaN candidates and dead beams, against the rules restated; the argument check at short and missing message buffers;
+// the ranking with ties
+__attribute__((noinline)) static void beam_host_half(int V) {
+    long n_sel = 0, n_slots = 0, n_checks = 0;
+    uint32_t rng = 12345u;
+    auto next = [&]() { rng = rng * 1664525u + 1013904223u; return rng >> 8; };
+    for (int B = 1; B <= LLAMAHIP_BEAM_MAX; B++)
+        for (int L = 0; L <= B; L++)
+            for (int rep = 0; rep < 6; rep++) {
+                const int nc = 2 * B, stop = rep % 3 == 0 ? -1 : (int) (next() % 7);
+                std::vector<double> sc((size_t) L), lp((size_t) L * nc);
+                std::vector<int32_t> ids((size_t) L * nc);
+                int want_dead = 0;
+                for (int i = 0; i < L; i++) {
+                    sc[i] = -0.25 * (double) (next() % 5);
+                    const bool dead = rep == 4 && next() % 3 == 0;
+                    want_dead += dead;
+                    for (int j = 0; j < nc; j++) {
+                        ids[(size_t) i * nc + j] = dead ? -1 : (int32_t) ((j * 3 + next() % 3) % 97);      // (ascending-ish, a stop id among them)
+                        lp[(size_t) i * nc + j] = dead || (rep == 5 && next() % 4 == 0) ? NAN : -0.25 * (double) (j / 2) - (rep == 2 && j >= nc - 2 ? INFINITY : 0.0);
+                    }
+                    if (!dead) for (int j = 1; j < nc; j++) if (ids[(size_t) i * nc + j] <= ids[(size_t) i * nc + j - 1]) ids[(size_t) i * nc + j] = ids[(size_t) i * nc + j - 1] + 1;
+                }
+                std::vector<int32_t> par((size_t) B, -7), tok((size_t) B, -7), fpar((size_t) std::max(L, 1), -7);
+                std::vector<double> nsc((size_t) B, 7.0), fsc((size_t) std::max(L, 1), 7.0);
+                int32_t nn = -1, nf = -1, nd = -1;
+                EXPECT(llamahip_beam_select(L, sc.data(), nc, ids.data(), lp.data(), B, stop, par.data(), tok.data(), nsc.data(), &nn, fpar.data(), fsc.data(), &nf, &nd) == 0);
+                EXPECT(nd == want_dead && nn >= 0 && nn <= B && nf >= 0 && nf <= L);
+                // the rule restated: every taken entry is a candidate, the walk's order is (c desc, i asc, v asc), nothing better was left out
+                double prev_c = INFINITY;
+                for (int k = 0; k < nn; k++) {
+                    EXPECT(par[k] >= 0 && par[k] < L && tok[k] != stop && nsc[k] == nsc[k] && nsc[k] <= prev_c);
+                    prev_c = nsc[k];
+                    bool found = false;
+                    for (int j = 0; j < nc && par[k] >= 0 && par[k] < L; j++)
+                        found = found || (ids[(size_t) par[k] * nc + j] == tok[k] && sc[par[k]] + lp[(size_t) par[k] * nc + j] == nsc[k]);
+                    EXPECT(found);
+                }
+                int n_valid = 0;
+                for (int i = 0; i < L; i++)
+                    for (int j = 0; j < nc; j++) {
+                        const double c = sc[i] + lp[(size_t) i * nc + j];
+                        const int32_t v = ids[(size_t) i * nc + j];
+                        if (ids[(size_t) i * nc] < 0 || v < 0 || c != c) continue;
+                        if (stop >= 0 && v == stop) { if (nn < B || c > nsc[nn - 1]) { bool in = false; for (int k = 0; k < nf; k++) in = in || (fpar[k] == i && fsc[k] == c); EXPECT(in); } continue; }
+                        n_valid++;
+                        if (nn == B) EXPECT(c <= nsc[nn - 1] || [&]() { for (int k = 0; k < nn; k++) if (par[k] == i && tok[k] == v) return true; return false; }());
+                    }
+                EXPECT(nn == std::min(B, n_valid));
+                n_sel++;
+                // the slots of those beams: the previous beams on a made-up permutation of distinct slots
+                std::vector<int32_t> prev((size_t) L), ns((size_t) std::max(nn, 1), -7), cs((size_t) std::max(nn, 1), -7), cd((size_t) std::max(nn, 1), -7);
+                for (int i = 0; i < L; i++) prev[i] = (i * 5 + rep) % B;
+                bool distinct = true;
+                for (int i = 0; i < L; i++) for (int j = 0; j < i; j++) distinct = distinct && prev[i] != prev[j];
+                const int32_t ncp = llamahip_beam_slots(L, prev.data(), nn, par.data(), B, ns.data(), cs.data(), cd.data());
+                if (!distinct) { EXPECT(ncp == -1); continue; }
+                EXPECT(ncp >= 0 && ncp <= nn);
+                for (int k = 0; k < nn; k++) for (int j = 0; j < k; j++) EXPECT(ns[k] != ns[j]);
+                for (int c = 0; c < ncp; c++) {
+                    for (int e = 0; e < ncp; e++) EXPECT(cs[c] != cd[e]);      // sources are never destinations
+                    for (int e = 0; e < c; e++) EXPECT(cd[c] != cd[e]);
+                }
+                int firsts = 0;
+                for (int k = 0; k < nn; k++) { bool first = true; for (int j = 0; j < k; j++) first = first && par[j] != par[k]; if (first) { EXPECT(ns[k] == prev[par[k]]); firsts++; } }
+                EXPECT(ncp == nn - firsts);
+                n_slots++;
+            }
+    {   // what the two refuse: counts out of range, null arrays
+        double d1[2] = { 0, 0 }; int32_t i1[2] = { 1, 2 }, n = 0;
+        EXPECT(llamahip_beam_select(17, d1, 2, i1, d1, 1, -1, i1, i1, d1, &n, i1, d1, &n, nullptr) != 0);
+        EXPECT(llamahip_beam_select(1, d1, 33, i1, d1, 1, -1, i1, i1, d1, &n, i1, d1, &n, nullptr) != 0);
+        EXPECT(llamahip_beam_select(1, d1, 2, i1, d1, 0, -1, i1, i1, d1, &n, i1, d1, &n, nullptr) != 0);
+        EXPECT(llamahip_beam_select(1, nullptr, 2, i1, d1, 1, -1, i1, i1, d1, &n, i1, d1, &n, nullptr) != 0);
+        EXPECT(llamahip_beam_slots(1, i1, 1, i1, 17, i1, i1, i1) == -1 && llamahip_beam_slots(2, i1, 1, i1, 1, i1, i1, i1) == -1);
+        int32_t bad_par[1] = { 3 }, prev1[1] = { 0 }, o1[1], o2[1], o3[1];
+        EXPECT(llamahip_beam_slots(1, prev1, 1, bad_par, 4, o1, o2, o3) == -1);
+    }
+    // the argument check: every refusal with a message that fits a buffer of 1, 24 and 400 bytes, and with no buffer
+    llamahip_beam_opts ok = { (int32_t) sizeof(llamahip_beam_opts), 8, 4, 12, -1, 0, 0, 9 };
+    std::vector<int32_t> prompt(20);
+    for (int i = 0; i < 20; i++) prompt[i] = (i * 7 + 3) % V;
+    int32_t out_i[4]; char out_h[4];
+    EXPECT(lh::beam_check(64, V, 4, &ok, prompt.data(), 20, out_h, out_i, out_i, nullptr, 0) == 0);
+    auto refused = [&](llamahip_beam_opts o, int n_prompt, int n_slots_, const int32_t *p) {
+        for (size_t cap : { (size_t) 1, (size_t) 24, (size_t) 400 }) {
+            std::vector<char> e(cap, 'x');
+            EXPECT(lh::beam_check(64, V, n_slots_, &o, p, n_prompt, out_h, out_i, out_i, e.data(), cap) == LLAMAHIP_ERR_PREDICT);
+            EXPECT(memchr(e.data(), 0, cap) != nullptr);
+            if (cap == 400) EXPECT(strstr(e.data(), "llamahip_beam_search") != nullptr);
+            n_checks++;
+        }
+        EXPECT(lh::beam_check(64, V, n_slots_, &o, p, n_prompt, out_h, out_i, out_i, nullptr, 0) == LLAMAHIP_ERR_PREDICT);
+    };
+    { auto o = ok; o.n_beams = 0; refused(o, 20, 4, prompt.data()); o.n_beams = 17; refused(o, 20, 32, prompt.data()); o.n_beams = 5; refused(o, 20, 4, prompt.data()); }
+    { auto o = ok; o.struct_size = 8; refused(o, 20, 4, prompt.data()); }
+    { auto o = ok; o.n_predict = 0; refused(o, 20, 4, prompt.data()); o.n_predict = 45; refused(o, 20, 4, prompt.data()); }
+    { auto o = ok; o.n_return = 5; refused(o, 20, 4, prompt.data()); o.n_return = -1; refused(o, 20, 4, prompt.data()); }
+    { auto o = ok; o.chunk_tokens = -1; refused(o, 20, 4, prompt.data()); o = ok; o.length_norm = 2; refused(o, 20, 4, prompt.data()); o = ok; o.stop_token = V; refused(o, 20, 4, prompt.data()); }
+    refused(ok, 0, 4, prompt.data());
+    refused(ok, 20, 4, nullptr);
+    { std::vector<int32_t> p2(prompt); p2[19] = V; refused(ok, 20, 4, p2.data()); }
+    EXPECT(lh::beam_check(64, 7, 4, &ok, prompt.data(), 20, out_h, out_i, out_i, nullptr, 0) == LLAMAHIP_ERR_PREDICT);      // 2 * 4 candidates > 7
+    {   // the ranking: ties to the earlier entry, one division for the normalised key
+        const double S[5] = { -2.0, -1.0, -2.0, -1.0, -3.0 }; const int32_t len[5] = { 4, 2, 2, 1, 3 }; int32_t order[5];
+        lh::beam_rank(5, S, len, 0, order);
+        EXPECT(order[0] == 1 && order[1] == 3 && order[2] == 0 && order[3] == 2 && order[4] == 4);
+        lh::beam_rank(5, S, len, 1, order);      // keys -0.5 -0.5 -1 -1 -1
+        EXPECT(order[0] == 0 && order[1] == 1 && order[2] == 2 && order[3] == 3 && order[4] == 4);
+        lh::beam_rank(0, S, len, 1, order);
+    }
+    printf("host_sanitize: beam search: %ld walks and %ld slot assignments against the rules restated, %ld refusals at short and missing message buffers\n", n_sel, n_slots, n_checks);
 }
 
 int main(int argc, char **argv) {
@@ -768,6 +887,7 @@ int main(int argc, char **argv) {
         EXPECT(llamahip_eval_multi_rows(64, 1, nullptr, big, 0, nullptr, nullptr, nullptr) == -1 && llamahip_eval_multi_rows(64, 1, np1, big, -1, nullptr, nullptr, nullptr) == -1);
     }
     scoring_host_half(V);
+    beam_host_half(V);
     embedding_host_half(V);
     // the request scheduler's host half against the stubbed device half: the step rule over a grid on exactly sized arrays against its
     // restatement; then whole runs -- every step's segments replayed against the rule and the requests' own state (positions, offsets, tokens,
