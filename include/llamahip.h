@@ -979,6 +979,113 @@ int32_t llamahip_beam_select(int32_t n_live, const double *live_score, int32_t n
 int32_t llamahip_beam_slots(int32_t n_prev, const int32_t *prev_slot, int32_t n_new, const int32_t *parent, int32_t n_beams,
                             int32_t *new_slot, int32_t *copy_src, int32_t *copy_dst);
 
+/* ---- constrained decoding: token-level DFA masks applied on the device ------ */
+/* A constraint is a deterministic automaton over BYTES, lifted once on the host to an automaton over the model's tokens: the table
+ * uint16 next[n_states + 1][n_vocab], LLAMAHIP_CONSTRAINT_BANNED = the token is not allowed in that state.  A static allow-list is the
+ * one-state case.
+ * llamahip_constraint_new -- trans[n_states][256] (the next byte-state, -1 = dead), accept[n_states] (0 / 1), start, stop_token (required).
+ *   THE LIFT.  Token t with text bytes b0 .. bk leads from state s to the state the walk of trans over those bytes reaches, and is BANNED
+ *   where the walk dies.  A token with an empty text is BANNED in every state (it adds no bytes: a pick could loop in place).  stop_token is
+ *   allowed exactly in accepting states, whatever its text, and leads to the extra sink state DONE (index n_states), in which only
+ *   stop_token is allowed, looping on itself.
+ *   THE PRUNE.  A state is live if it is accepting or some token leads from it to a live state (the least fixed point over the token graph);
+ *   a transition into a state that is not live becomes BANNED; a start state that is not live is refused.  CONSEQUENCE: every state
+ *   reachable from start has at least one allowed token -- an accepting state has stop_token, every other live state a token towards a
+ *   live state -- so a row with nothing allowed cannot occur with a state this constraint handed out.  A byte-state that only bytes no
+ *   token supplies would reach is never entered.  Any segmentation of an accepted string into tokens is admitted.
+ *   Works on any handle, LLAMAHIP_FLAG_HOST_ONLY included: only the vocabulary is read.  The device copy of the table is made by the first
+ *   device call that uses the constraint on its handle and belongs to the handle's owner (llamahip_debug_live_allocs counts it);
+ *   llamahip_constraint_free releases it.  Free a constraint before its handle; one that outlives its handle may only be freed.
+ *   Refused before any work, the message naming the limit: NULL arguments, n_states outside 1 .. 4096, a table over 256 MiB, a trans entry
+ *   outside [-1, n_states), start or stop_token out of range, no accepting state; then a start state that is not live.
+ * llamahip_constraint_new_choices -- "answer with one of these strings": the trie of n >= 1 non-empty byte strings as the byte automaton,
+ *   accepting at each string's end, start = the root, through the same path (duplicates are fine; so is a string that is a prefix of another).
+ * llamahip_constraint_n_states (DONE included), _start, _done (the sink's index); _table(c, out, cap): the whole table, n_states * n_vocab
+ *   entries -- returns that count, copies where cap holds it; _advance(c, state, token): the next state, -1 if banned or out of range.
+ * llamahip_constraint_pick(c, state, logits) -- THE PICK RULE, the host statement of k_pick_dfa (constrain.hip): k_argmax's rule over the
+ *   allowed entries of next[state] -- the largest value, the lowest index on ties (+0.0 == -0.0), a NaN never wins; where every allowed entry
+ *   is a NaN, the lowest allowed index.  -1 for a row with nothing allowed or a state out of range.
+ * llamahip_constraint_mask_row(c, state, in, out) -- the host statement of k_mask_rows_dfa: banned entries become -INFINITY, all others are
+ *   copied bit for bit (in == out is fine).
+ * EXACT BY CONSTRUCTION: the lift and the prune (integers), the mask, the pick rule against its host statement (a total order on the
+ *   non-NaN entries: every reduction tree gives the same pick) -- tests/test_constrain_host.py, tests/test_gpu_constrain_op.py.
+ * EXACT BY TEST: the equality of the device loop below with one-token evals (tests/test_gpu_constrain.py) -- the norm's one-pass against
+ *   two-pass statistics, as for every captured step.
+ *
+ * llamahip_decode_greedy_constrained -- llamahip_decode_greedy's un-folded step (forward + a pick kernel behind the lm head) with k_pick_dfa
+ *   in k_argmax's place: the automaton's state is one more device-resident word, read and advanced by the pick like the position, so the
+ *   step stays captured (a graph-key bit and cache of its own: llamahip_decode_greedy's graphs are neither shared nor disturbed); eager on
+ *   LLAMAHIP_FLAG_NO_GRAPH / unfused handles.  *state_io comes in as the state before the first pick (llamahip_constraint_start for a fresh
+ *   answer) and goes out as the state behind the last reported token, so a caller resumes with it.  The loop runs in legs of
+ *   LLAMAHIP_CONSTRAIN_LEG steps; after each leg it reads {state, dead} (8 bytes) and stops once the state is DONE.  *n_out counts the
+ *   tokens up to and including the stop token, *finished is 1 if the stop token was produced.
+ *   CONTRACT, bit for bit -- out_tokens[0 .. *n_out), logits_last (the logits the last reported token was picked from; may be NULL), KV rows
+ *   [0, n_past + *n_out) of the current slot: the loop "one-token llamahip_eval -> llamahip_constraint_pick -> llamahip_constraint_advance"
+ *   on that slot.  Rows at and above n_past + *n_out are unspecified (a leg may run past the stop token).  BY TEST, see above.  With a
+ *   constraint that allows everything the tokens are llamahip_decode_greedy's.
+ *   SAFETY.  A pick becomes an embedding read on the next step: where the state word is out of range or its row allows nothing, the kernel
+ *   indexes nothing, picks stop_token, leaves the state and sets a `dead` word; the loop then fails with LLAMAHIP_ERR_PREDICT.
+ *   Handles: plain handles, every file type and flag.  In-process pipeline handles run the reference loop itself (llamahip_eval, the host
+ *   pick).  Stage and HOST_ONLY handles are refused.  The arguments are checked first, without a device: NULL arguments, a constraint of
+ *   another handle, a state out of range, first_token out of range, n_steps < 1, n_past + n_steps > n_ctx.
+ * llamahip_op_pick_dfa / llamahip_op_mask_rows_dfa -- the two kernels on caller-supplied operands (parity tests): logits[n_rows][n_vocab],
+ *   n_rows 1 .. 16, ONE table[n_table_states][n_vocab] with per-row states.  pick: states_io / picks / dead [n_rows] go up as they are and come
+ *   back -- a row whose state is out of range or allows nothing gets fallback_token, dead = 1 and keeps its state; every other row its pick,
+ *   its next state and its dead word untouched.  mask: out[n_rows][n_vocab]; states out of range are refused.  Refused before any launch: NULL
+ *   arrays, n_rows outside 1 .. 16, n_vocab < 1, n_table_states outside 1 .. 65535, a table entry that is neither a state nor BANNED, a
+ *   fallback_token out of range.
+ * llamahip_decode_greedy_constrained_multi -- sequence i lives in KV slot i, as in llamahip_decode_greedy_multi; 1 .. 16 sequences, one weight
+ *   pass per step for all of them, each under its own constraint (constraints[n_seqs]), start state (states_io[n_seqs], in / out) and position.
+ *   The captured set step stays exactly as it is; ONE k_pick_dfa launch over the set's rows stands behind it and re-picks from the step's logits:
+ *   it overwrites what the step's own tail wrote for that step -- the trace entry and the slot's next-token word -- and leaves the position as
+ *   advanced.  llamahip_decode_greedy_multi and llamahip_stage_step_set are untouched.  A finished sequence stays in the set in DONE; the loop
+ *   ends when all are finished or after n_steps, checked once per leg.  out_tokens[n_seqs][n_steps], n_out / finished [n_seqs] as above.
+ *   CONTRACT: per sequence, bit for bit the single-sequence call on that slot alone, KV rows [0, n_past[i] + n_out[i]) included -- BY TEST.
+ *   Pipeline handles and handles without a set step to batch (Q4_1 files, LLAMAHIP_FLAG_UNFUSED) run the single-sequence call per slot.
+ *   Refused before any device work: NULL arguments, n_seqs outside 1 .. 16 or above llamahip_opts.n_seq, and per sequence what the
+ *   single-sequence call refuses.
+ * llamahip_eval_topk_constrained -- llamahip_eval_topk's arguments and results plus (c, state): the eval, then k_mask_rows_dfa from the logits
+ *   row into a scratch row, then the existing candidate selection on that row.  Everything llamahip_eval_topk promises holds for the MASKED
+ *   row: exact == 1 candidates are the reference sampler's on the masked row (llamahip_constraint_mask_row, then
+ *   llamahip_sample_top_p_top_k); with exact == 0 logits_out holds the masked row and the caller samples on the host.  Ties among -inf at the
+ *   k-th place report exact = 0: that is EVERY step on which fewer than top_k + 1 tokens are allowed.  Pipeline handles (and what else
+ *   llamahip_eval_topk hands to the host) mask on the host.  There is no C loop: Model.decode_sample_constrained (binding.py) runs
+ *   "eval_topk_constrained -> draw -> accept -> advance".
+ * LLAMAHIP_CONSTRAIN_LEG in the ENVIRONMENT (1 .. 64, read once per process, like LLAMAHIP_NO_PICK_FOLD) overrides the macro below: a
+ *   measurement switch for tools/constrain_probe.py's leg sweep, not an interface; results do not depend on it.
+ * HAZARD: a constraint keeps a pointer to its handle.  After llamahip_model_free the constraint may only be passed to llamahip_constraint_free;
+ *   the "made on another handle" check compares that pointer and cannot tell a freed handle from a new one at the same address.
+ * Not built: constraints in the scheduler, the runner, beam search and the drafted loops; context-free grammars; canonical tokenisation. */
+#define LLAMAHIP_CONSTRAINT_BANNED 0xFFFF
+#define LLAMAHIP_CONSTRAIN_LEG 4          /* steps between two looks at the state word (measured: DESIGN.md 12.33, profiles/constrain_probe_7b.json) */
+typedef struct llamahip_constraint llamahip_constraint;
+int llamahip_constraint_new(const llamahip_model *m, int32_t n_states, const int32_t *trans, const uint8_t *accept, int32_t start, int32_t stop_token,
+                            llamahip_constraint **out, char *err, size_t err_cap);
+int llamahip_constraint_new_choices(const llamahip_model *m, const uint8_t *const *strings, const int32_t *lens, int32_t n, int32_t stop_token,
+                                    llamahip_constraint **out, char *err, size_t err_cap);
+void llamahip_constraint_free(llamahip_constraint *c);
+int32_t llamahip_constraint_n_states(const llamahip_constraint *c);
+int32_t llamahip_constraint_start(const llamahip_constraint *c);
+int32_t llamahip_constraint_done(const llamahip_constraint *c);
+int64_t llamahip_constraint_table(const llamahip_constraint *c, uint16_t *out, int64_t cap);
+int32_t llamahip_constraint_advance(const llamahip_constraint *c, int32_t state, int32_t token);
+int32_t llamahip_constraint_pick(const llamahip_constraint *c, int32_t state, const float *logits);
+int llamahip_constraint_mask_row(const llamahip_constraint *c, int32_t state, const float *logits_in, float *logits_out);
+int llamahip_decode_greedy_constrained(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps, llamahip_constraint *c,
+                                       int32_t *state_io, int32_t *out_tokens, int32_t *n_out, int32_t *finished, float *logits_last,
+                                       char *err, size_t err_cap);
+int llamahip_decode_greedy_constrained_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                             int32_t n_steps, llamahip_constraint *const *constraints, int32_t *states_io, int32_t *out_tokens,
+                                             int32_t *n_out, int32_t *finished, char *err, size_t err_cap);
+int llamahip_eval_topk_constrained(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                                   const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty, int32_t top_k, double temp,
+                                   llamahip_constraint *c, int32_t state, double *cand_scores, int32_t *cand_ids, int32_t *exact, float *logits_out,
+                                   char *err, size_t err_cap);
+int llamahip_op_pick_dfa(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, int32_t *states_io,
+                         int32_t fallback_token, int32_t *picks, int32_t *dead, char *err, size_t err_cap);
+int llamahip_op_mask_rows_dfa(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, const int32_t *states,
+                              float *out, char *err, size_t err_cap);
+
 /* llamahip_eval + every token's logits (n_tokens * n_vocab) and, for dump_layer >= 0, that layer's
  * 17 intermediates in the order documented in DESIGN.md ("debug dump order").  Parity tooling. */
 int llamahip_eval_debug(llamahip_model *m, int32_t n_threads, int32_t n_past,

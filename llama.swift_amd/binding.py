@@ -305,6 +305,25 @@ def lib() -> C.CDLL:
     L.llamahip_debug_q41_plan.argtypes = [i32, i32, i32, vp]
     L.llamahip_debug_q41_plan.restype = i32
     L.llamahip_debug_dense_force.restype = i32
+    L.llamahip_constraint_new.argtypes = [vp, i32, vp, vp, i32, i32, C.POINTER(vp), cp, sz]
+    L.llamahip_constraint_new_choices.argtypes = [vp, vp, vp, i32, i32, C.POINTER(vp), cp, sz]
+    L.llamahip_constraint_free.argtypes = [vp]
+    L.llamahip_constraint_free.restype = None
+    for name in ("n_states", "start", "done"):
+        getattr(L, "llamahip_constraint_" + name).argtypes = [vp]
+        getattr(L, "llamahip_constraint_" + name).restype = i32
+    L.llamahip_constraint_table.argtypes = [vp, vp, C.c_int64]
+    L.llamahip_constraint_table.restype = C.c_int64
+    L.llamahip_constraint_advance.argtypes = [vp, i32, i32]
+    L.llamahip_constraint_advance.restype = i32
+    L.llamahip_constraint_pick.argtypes = [vp, i32, vp]
+    L.llamahip_constraint_pick.restype = i32
+    L.llamahip_constraint_mask_row.argtypes = [vp, i32, vp, vp]
+    L.llamahip_decode_greedy_constrained.argtypes = [vp, i32, i32, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32), vp, cp, sz]
+    L.llamahip_decode_greedy_constrained_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, cp, sz]
+    L.llamahip_eval_topk_constrained.argtypes = [vp, i32, i32, vp, i32, vp, i32, C.c_double, i32, C.c_double, vp, i32, vp, vp, C.POINTER(i32), vp, cp, sz]
+    L.llamahip_op_pick_dfa.argtypes = [vp, i32, i32, vp, i32, vp, i32, vp, vp, cp, sz]
+    L.llamahip_op_mask_rows_dfa.argtypes = [vp, i32, i32, vp, i32, vp, vp, cp, sz]
     L.llamahip_debug_live_allocs.argtypes = [vp, vp]
     L.llamahip_debug_live_allocs.restype = None
     _lib = L
@@ -697,6 +716,88 @@ class Model:
         _check(rc, err)
         return (out, logits) if want_logits else out
 
+    # --- constrained decoding (include/llamahip.h) ---------------------------------
+    def constraint(self, dfa=None, choices=None, regex=None, stop_token: int = 2) -> "Constraint":
+        """One of: dfa = (trans int32[n_states, 256] with -1 = dead, accept[n_states], start) -- a byte automaton; choices = byte strings (or
+        str, taken as UTF-8) -- "answer with one of these"; regex = a pattern for regex_dfa.compile (full-match semantics).  stop_token ends
+        an answer: it is allowed exactly where the text so far is accepted."""
+        if (dfa is not None) + (choices is not None) + (regex is not None) != 1:
+            raise ValueError("constraint: exactly one of dfa=, choices=, regex=")
+        if regex is not None:
+            from . import regex_dfa
+            dfa = regex_dfa.compile(regex)
+        return Constraint(self, dfa=dfa, choices=choices, stop_token=stop_token)
+
+    def decode_greedy_constrained(self, first_token: int, n_past: int, n_steps: int, constraint: "Constraint", state: int | None = None,
+                                  n_threads: int = 8, want_logits: bool = False) -> dict:
+        """llamahip_decode_greedy_constrained: tokens (up to and including the stop token), finished, state (behind the last reported token:
+        pass it back to resume) and with want_logits the logits the last reported token was picked from."""
+        out = np.full(max(n_steps, 1), -1, np.int32)
+        logits = np.empty(self.n_vocab, np.float32) if want_logits else None
+        st = C.c_int32(constraint.start if state is None else int(state))
+        n_out, fin = C.c_int32(0), C.c_int32(0)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_greedy_constrained(self._h, n_threads, n_past, int(first_token), n_steps, constraint._c, C.byref(st), _ptr(out),
+                                                      C.byref(n_out), C.byref(fin), _ptr(logits), err, len(err))
+        _check(rc, err)
+        return {"tokens": out[:n_out.value].copy(), "finished": bool(fin.value), "state": st.value, "logits": logits}
+
+    def decode_greedy_constrained_multi(self, first_tokens, n_past, n_steps: int, constraints, states=None, n_threads: int = 8) -> list:
+        """llamahip_decode_greedy_constrained_multi: sequence i in KV slot i under constraints[i] from states[i] (default: each start state).
+        Returns one dict per sequence: tokens (up to and including the stop token), finished, state."""
+        first_tokens = np.ascontiguousarray(first_tokens, np.int32).ravel()
+        n_past = np.ascontiguousarray(n_past, np.int32).ravel()
+        n = first_tokens.size
+        if n_past.size != n or len(constraints) != n:
+            raise ValueError(f"{n} first tokens, {n_past.size} positions, {len(constraints)} constraints")
+        st = np.array([c.start for c in constraints] if states is None else states, np.int32).ravel()
+        if st.size != n:
+            raise ValueError(f"states: {st.size} for {n} sequences")
+        cs = (C.c_void_p * max(n, 1))(*[c._c.value for c in constraints])
+        out = np.full((max(n, 1), max(n_steps, 1)), -1, np.int32)
+        n_out, fin = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_decode_greedy_constrained_multi(self._h, n_threads, n, _ptr(n_past), _ptr(first_tokens), n_steps, cs, _ptr(st), _ptr(out),
+                                                            _ptr(n_out), _ptr(fin), err, len(err))
+        _check(rc, err)
+        return [{"tokens": out[i, :n_out[i]].copy(), "finished": bool(fin[i]), "state": int(st[i])} for i in range(n)]
+
+    def eval_topk_constrained(self, tokens, n_past: int, sampler: "Sampler", constraint: "Constraint", state: int, repeat_penalty: float = 1.3,
+                              top_k: int = 40, temp: float = float(np.float32(0.8)), n_threads: int = 8):
+        """llamahip_eval_topk_constrained: (exact, scores[k], ids[k], masked logits or None) -- eval_topk's results for the row masked by
+        the constraint's state."""
+        tokens = np.ascontiguousarray(tokens, np.int32)
+        win = np.zeros(1024, np.int32)
+        nw = lib().llamahip_sampler_window(sampler._s, _ptr(win), 1024)
+        sc, ids = np.zeros(64, np.float64), np.zeros(64, np.int32)
+        exact = C.c_int32(0)
+        logits = np.empty(self.n_vocab, np.float32)
+        err = C.create_string_buffer(1024)
+        rc = lib().llamahip_eval_topk_constrained(self._h, n_threads, n_past, _ptr(tokens), tokens.size, _ptr(win), nw, repeat_penalty, top_k, temp,
+                                                  constraint._c, int(state), _ptr(sc), _ptr(ids), C.byref(exact), _ptr(logits), err, len(err))
+        _check(rc, err)
+        k = min(top_k, self.n_vocab)
+        return bool(exact.value), sc[:k], ids[:k], (None if exact.value else logits)
+
+    def decode_sample_constrained(self, first_token: int, n_past: int, n_steps: int, constraint: "Constraint", sampler: "Sampler", state: int | None = None,
+                                  repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)),
+                                  temp: float = float(np.float32(0.8)), n_threads: int = 8) -> dict:
+        """Sampled decoding under a constraint: eval_topk_constrained -> draw -> accept -> advance, until the stop token or n_steps.  Token
+        for token, and in the sampler's window and rng state, the loop eval -> Constraint.mask_row -> Sampler.sample -> accept.  Returns
+        tokens, finished, state and n_exact (the steps whose candidates came from the device)."""
+        state = constraint.start if state is None else int(state)
+        tok, out, n_exact = int(first_token), [], 0
+        while len(out) < n_steps and state != constraint.done:
+            exact, sc, ids, masked = self.eval_topk_constrained([tok], n_past + len(out), sampler, constraint, state, repeat_penalty, top_k, temp, n_threads)
+            tok = sampler.sample_from_candidates(sc, ids, top_p) if exact else sampler.sample(self, masked, repeat_penalty, top_k, top_p, temp)
+            n_exact += int(exact)
+            sampler.accept(tok)
+            state = constraint.advance(state, tok)
+            if state < 0:
+                raise LlamaHipError(ERR_PREDICT, f"decode_sample_constrained: the sampler drew token {tok}, which the constraint bans")
+            out.append(tok)
+        return {"tokens": np.array(out, np.int32), "finished": state == constraint.done, "state": state, "n_exact": n_exact}
+
     def verify_greedy(self, token: int, draft, n_past: int, n_threads: int = 8, want_logits: bool = False):
         """llamahip_verify_greedy: the rows [token, draft ...] at n_past as one eval.  Returns (n_accept, picks[len(draft) + 1]) -- the new
         context is n_past + n_accept + 1, the next token picks[n_accept] -- and with want_logits the logits that token was picked from."""
@@ -1088,6 +1189,79 @@ class Model:
         s = _Stats()
         lib().llamahip_get_stats(self._h, C.byref(s))
         return {k: getattr(s, k) for k, _ in _Stats._fields_ if k != "struct_size"}
+
+
+class Constraint:
+    """A token-level constraint of one Model (llamahip_constraint_*): owns the handle's constraint -- close it (or leave the `with` block)
+    before the model is closed."""
+
+    def __init__(self, model: Model, dfa=None, choices=None, stop_token: int = 2):
+        L = lib()
+        err = C.create_string_buffer(1024)
+        c = C.c_void_p()
+        self._c = None
+        self.model, self.stop_token = model, int(stop_token)
+        if choices is not None:
+            bs = [x.encode() if isinstance(x, str) else bytes(x) for x in choices]
+            bufs = [C.create_string_buffer(b, max(len(b), 1)) for b in bs]
+            ptrs = (C.c_void_p * max(len(bs), 1))(*[C.cast(b, C.c_void_p).value for b in bufs])
+            lens = np.array([len(b) for b in bs], np.int32)
+            rc = L.llamahip_constraint_new_choices(model._h, ptrs, _ptr(lens), len(bs), self.stop_token, C.byref(c), err, len(err))
+        else:
+            trans, accept, start = dfa
+            trans = np.ascontiguousarray(trans, np.int32)
+            if trans.ndim != 2 or trans.shape[1] != 256:
+                raise ValueError("constraint: trans is int32 [n_states, 256]")
+            accept = np.ascontiguousarray(accept, np.uint8).ravel()
+            if accept.size != trans.shape[0]:
+                raise ValueError(f"constraint: accept has {accept.size} entries for {trans.shape[0]} states")
+            rc = L.llamahip_constraint_new(model._h, trans.shape[0], _ptr(trans), _ptr(accept), int(start), self.stop_token, C.byref(c), err, len(err))
+        _check(rc, err)
+        self._c = c
+        self.n_states, self.start, self.done = L.llamahip_constraint_n_states(c), L.llamahip_constraint_start(c), L.llamahip_constraint_done(c)
+        self.n_vocab = model.n_vocab
+
+    def close(self) -> None:
+        if getattr(self, "_c", None):
+            lib().llamahip_constraint_free(self._c)
+            self._c = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def table(self) -> np.ndarray:
+        """uint16 [n_states, n_vocab]; 0xFFFF = banned"""
+        out = np.empty((self.n_states, self.n_vocab), np.uint16)
+        n = lib().llamahip_constraint_table(self._c, _ptr(out), out.size)
+        assert n == out.size
+        return out
+
+    def advance(self, state: int, token: int) -> int:
+        return lib().llamahip_constraint_advance(self._c, int(state), int(token))
+
+    def pick(self, state: int, logits) -> int:
+        logits = np.ascontiguousarray(logits, np.float32)
+        if logits.size != self.n_vocab:
+            raise ValueError(f"pick: {logits.size} logits for n_vocab {self.n_vocab}")
+        return lib().llamahip_constraint_pick(self._c, int(state), _ptr(logits))
+
+    def mask_row(self, state: int, logits) -> np.ndarray:
+        logits = np.ascontiguousarray(logits, np.float32)
+        if logits.size != self.n_vocab:
+            raise ValueError(f"mask_row: {logits.size} logits for n_vocab {self.n_vocab}")
+        out = np.empty_like(logits)
+        if lib().llamahip_constraint_mask_row(self._c, int(state), _ptr(logits), _ptr(out)) != 0:
+            raise LlamaHipError(ERR_PREDICT, f"llamahip_constraint_mask_row: state {state} out of range [0, {self.n_states})")
+        return out
 
 
 class Sampler:
@@ -1509,6 +1683,43 @@ def op_verify_rows_set(logits2d, tokens, seg_begin):
     rc = lib().llamahip_op_verify_rows_set(_ptr(logits2d), R, V, _ptr(tokens), _ptr(seg_begin), n_segs, _ptr(n_acc), _ptr(picks), err, len(err))
     _check(rc, err)
     return n_acc, picks
+
+
+def _dfa_operands(logits2d, table, states):
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    if logits2d.ndim == 1:
+        logits2d = logits2d.reshape(1, -1)
+    R, V = logits2d.shape
+    table = np.ascontiguousarray(table, np.uint16)
+    if table.ndim != 2 or table.shape[1] != V:
+        raise ValueError(f"table: uint16 [n_states, {V}]")
+    states = np.array(states, np.int32).ravel()
+    if states.size != R:
+        raise ValueError(f"states: {states.size} for {R} rows")
+    return logits2d, R, V, table, states
+
+
+def op_pick_dfa(logits2d, table, states, fallback_token: int, picks=None, dead=None):
+    """k_pick_dfa on host rows f32 [n_rows, n_vocab] (1 .. 16 rows) under ONE table uint16 [n_states, n_vocab] (0xFFFF = banned) with per-row
+    states.  picks / dead: what the words hold before the launch (default -1 / 0).  Returns (picks, next states, dead), int32[n_rows] each."""
+    logits2d, R, V, table, states = _dfa_operands(logits2d, table, states)
+    picks = np.full(R, -1, np.int32) if picks is None else np.array(picks, np.int32).ravel()
+    dead = np.zeros(R, np.int32) if dead is None else np.array(dead, np.int32).ravel()
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_pick_dfa(_ptr(logits2d), R, V, _ptr(table), table.shape[0], _ptr(states), int(fallback_token), _ptr(picks), _ptr(dead), err, len(err))
+    _check(rc, err)
+    return picks, states, dead
+
+
+def op_mask_rows_dfa(logits2d, table, states, out=None):
+    """k_mask_rows_dfa on host rows: f32 [n_rows, n_vocab] with the banned entries of each row's state at -inf, the others bit for bit.
+    out: what the result buffer holds before the launch."""
+    logits2d, R, V, table, states = _dfa_operands(logits2d, table, states)
+    out = np.zeros((R, V), np.float32) if out is None else np.array(out, np.float32).reshape(R, V)
+    err = C.create_string_buffer(512)
+    rc = lib().llamahip_op_mask_rows_dfa(_ptr(logits2d), R, V, _ptr(table), table.shape[0], _ptr(states), _ptr(out), err, len(err))
+    _check(rc, err)
+    return out
 
 
 def op_verify_rows(logits2d, tokens):

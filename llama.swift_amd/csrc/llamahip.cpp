@@ -25,6 +25,7 @@
 #include "llamahip_internal.h"
 #include "model_file.h"
 #include "sched.h"
+#include "constrain.h"
 
 using namespace lh;
 
@@ -243,6 +244,12 @@ struct llamahip_model {
     int n_seq = 1, cur_seq = 0;          // KV caches: [seq][layer][n_ctx][d]
     AttnWs attn_ws;                      // many-row prompt attention workspace (allocated with the first eval of >= 2 tokens: ensure_attn_ws)
     GraphCache<int> decode_graphs;                 // keyed by nth * 4096 + seq + (attention schedule << 24)
+    // constrained greedy decoding: the sequence's {automaton state, dead} words, the constraints whose tables this handle's owner holds, and the
+    // captured steps -- decode_graphs' key with bit 28, per constraint (the step holds the table's address)
+    int32_t *d_cst = nullptr;
+    float *d_cst_row = nullptr;          // llamahip_eval_topk_constrained: the masked logits row, [n_vocab]
+    std::vector<llamahip_constraint *> constraints;
+    GraphCache<std::pair<int, const void *>> cst_graphs;
     // asynchronous pipeline-stage steps (llamahip_stage_bind / llamahip_stage_step)
     struct StageSlot {
         int32_t *token_in = nullptr, *token_out = nullptr;     // caller-owned device buffers
@@ -335,6 +342,7 @@ void lh::dev_release_default(void *p, int kind) {
 
 llamahip_model::~llamahip_model() {
     if (sched) lh::sched_dev_orphan(sched);          // (a scheduler that outlives its handle: every later call on it fails, none touches the handle)
+    for (llamahip_constraint *c : constraints) { c->dev = nullptr; c->dev_release = nullptr; }      // (the tables go with `own`)
     for (llamahip_model *st : stages) delete st;
     if (host_only) return;
     (void) hipSetDevice(device);
@@ -511,6 +519,7 @@ int ensure_workspace(llamahip_model *m, int N, char *err, size_t err_cap) {
     HIP_TRY(hipDeviceSynchronize(), LLAMAHIP_ERR_PREDICT);
     drop_set_graphs(m);
     m->decode_graphs.clear();
+    m->cst_graphs.clear();
     for (auto &sl : m->slots) sl.graphs.clear();
     const HParams &hp = m->hp;
     const size_t d = hp.n_embd, F = hp.n_ff, V = hp.n_vocab, C = hp.n_ctx, H = hp.n_head;
@@ -1473,6 +1482,164 @@ int llamahip_decode_greedy(llamahip_model *m, int32_t n_threads, int32_t n_past,
     HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
     if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
     m->n_evals += n_steps;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+// ---- constrained greedy decoding (llamahip.h) ---------------------------------
+// the device copy of a constraint's table: made by the first device call that uses it on its handle, registered with the handle's owner
+static void cst_dev_release(llamahip_constraint *c) {
+    llamahip_model *m = const_cast<llamahip_model *>(c->m);
+    (void) hipSetDevice(m->device);
+    (void) hipDeviceSynchronize();      // a captured step that reads the table may still run
+    for (auto it = m->cst_graphs.map.begin(); it != m->cst_graphs.map.end();) {
+        if (it->first.second != (const void *) c) { ++it; continue; }
+        if (it->second.exec) (void) hipGraphExecDestroy(it->second.exec);
+        it = m->cst_graphs.map.erase(it);
+    }
+    m->own.release(&c->dev);
+    m->constraints.erase(std::remove(m->constraints.begin(), m->constraints.end(), c), m->constraints.end());
+    c->dev_release = nullptr;
+}
+static int cst_ensure_dev(llamahip_model *m, llamahip_constraint *c, char *err, size_t err_cap) {
+    if (!m->d_cst) HIP_TRY(m->own.alloc(&m->d_cst, (size_t) 2 * SET_MAX), LLAMAHIP_ERR_PREDICT);      // {state, dead} per sequence of a multi call
+    if (c->dev) return 0;
+    HIP_TRY(m->own.alloc(&c->dev, c->next.size()), LLAMAHIP_ERR_PREDICT);
+    c->dev_release = cst_dev_release;
+    m->constraints.push_back(c);
+    HIP_TRY(hipMemcpy(c->dev, c->next.data(), c->next.size() * 2, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+    return 0;
+}
+// the contract itself: one-token llamahip_eval -> llamahip_constraint_pick -> llamahip_constraint_advance (pipeline handles run this)
+static int cst_reference_loop(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps, const llamahip_constraint *c,
+                              int32_t *state_io, int32_t *out_tokens, int32_t *n_out, int32_t *finished, float *logits_last, char *err, size_t err_cap) {
+    std::vector<float> row((size_t) m->hp.n_vocab);
+    const int32_t done = c->n_states - 1;
+    int32_t tok = first_token, state = *state_io, n = 0, fin = 0;
+    while (n < n_steps && !fin) {
+        const int rc = llamahip_eval(m, n_threads, n_past + n, &tok, 1, row.data(), err, err_cap);
+        if (rc) return rc;
+        tok = llamahip_constraint_pick(c, state, row.data());
+        const int32_t q = tok < 0 ? -1 : llamahip_constraint_advance(c, state, tok);
+        if (q < 0) { set_err(err, err_cap, "llamahip_decode_greedy_constrained: state %d allows no token (the state does not come from this constraint)", state); return LLAMAHIP_ERR_PREDICT; }
+        out_tokens[n++] = tok;
+        state = q;
+        fin = state == done;
+    }
+    if (logits_last) memcpy(logits_last, row.data(), row.size() * 4);
+    *state_io = state; *n_out = n; *finished = fin;
+    return LLAMAHIP_OK;
+}
+
+int llamahip_decode_greedy_constrained(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps, llamahip_constraint *c,
+                                       int32_t *state_io, int32_t *out_tokens, int32_t *n_out, int32_t *finished, float *logits_last,
+                                       char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_greedy_constrained";
+    // the arguments first, without a device; the handle last
+    if (!m || !c || !state_io || !out_tokens || !n_out || !finished) {
+        set_err(err, err_cap, "%s: %s is NULL", fn, !m ? "model" : !c ? "constraint" : !state_io ? "state_io" : !out_tokens ? "out_tokens" : !n_out ? "n_out" : "finished");
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (c->m != m) { set_err(err, err_cap, "%s: the constraint was made on another handle", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (*state_io < 0 || *state_io >= c->n_states) { set_err(err, err_cap, "%s: state %d out of range [0, %d)", fn, *state_io, c->n_states); return LLAMAHIP_ERR_PREDICT; }
+    if (first_token < 0 || first_token >= m->hp.n_vocab) { set_err(err, err_cap, "%s: token id %d out of range [0, %d)", fn, first_token, m->hp.n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_steps < 1) { set_err(err, err_cap, "%s: n_steps must be >= 1 (got %d)", fn, n_steps); return LLAMAHIP_ERR_PREDICT; }
+    if (n_past < 0 || (int64_t) n_past + n_steps > m->hp.n_ctx) {
+        set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past, n_steps, m->hp.n_ctx);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    // (the front of a pipeline handle holds no device state of its own: its stages do)
+    if (!m->stages.empty()) return cst_reference_loop(m, n_threads, n_past, first_token, n_steps, c, state_io, out_tokens, n_out, finished, logits_last, err, err_cap);
+    if (m->host_only) { set_err(err, err_cap, "%s: model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!m->first_stage || !m->last_stage) { set_err(err, err_cap, "%s: needs a whole-model handle (this one holds layers [%d, %d))", fn, m->l0, m->l1); return LLAMAHIP_ERR_PREDICT; }
+    m->last_rows.clear();
+    const double t0 = now_ms();
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    int rc = ensure_workspace(m, 1, err, err_cap);
+    if (rc) return rc;
+    if ((rc = cst_ensure_dev(m, c, err, err_cap)) != 0) return rc;
+    if (!m->d_out_tokens) {      // sized once for the whole context: captured graphs hold this pointer
+        HIP_TRY(m->own.alloc(&m->d_out_tokens, (size_t) m->hp.n_ctx), LLAMAHIP_ERR_PREDICT);
+        m->out_tokens_cap = m->hp.n_ctx;
+    }
+    const int V = m->hp.n_vocab, nth = clamp_threads(n_threads), done = c->n_states - 1;
+    const bool fusable = !(m->flags & LLAMAHIP_FLAG_UNFUSED) || m->dense;
+    const bool graphs = fusable && !(m->flags & LLAMAHIP_FLAG_NO_GRAPH);
+    Pass pass(m);
+    pass.n_threads = n_threads;
+    pass.state_on_device = fusable;
+    DfaRows rows = {};
+    rows.r[0] = { m->logits, c->dev, m->d_cst, m->d_out_tokens, m->d_tokens, m->d_state, c->n_states, c->stop_token, 0, 0 };
+    // one step at position pos: llamahip_decode_greedy's un-folded step with k_pick_dfa in k_argmax's place
+    auto step = [&](int pos) -> int {
+        pass.attn_sched = attn_sched_at(m, pos);
+        if (!graphs) {
+            pass.n_past = pos;
+            const int r = forward(m, pass, err, err_cap);
+            if (r) return r;
+            HIP_TRY(launch_pick_dfa(rows, 1, V, m->stream), LLAMAHIP_ERR_PREDICT);
+            return 0;
+        }
+        const std::pair<int, const void *> gkey(nth * 4096 + m->cur_seq + (pass.attn_sched << 24) + (1 << 28), (const void *) c);
+        auto *g = m->cst_graphs.find(gkey);
+        if (!g) {
+            hipGraphExec_t exec = nullptr;
+            const int r = capture_step(m, [&]() -> int {
+                const int rf = forward(m, pass, err, err_cap);
+                if (rf) return rf;
+                HIP_TRY(launch_pick_dfa(rows, 1, V, m->stream), LLAMAHIP_ERR_PREDICT);
+                return 0;
+            }, &exec, err, err_cap);
+            if (r) return r;
+            g = m->cst_graphs.put(gkey, exec);
+        }
+        HIP_TRY(hipGraphLaunch(g->exec, m->stream), LLAMAHIP_ERR_PREDICT);
+        return 0;
+    };
+    // the device-resident words of step k: the token, {position, step index}, {state, dead}
+    auto publish = [&](int32_t token, int32_t k, int32_t state) -> int {
+        const int32_t hs[2] = { n_past + k, k }, hc[2] = { state, 0 };
+        HIP_TRY(hipMemcpyAsync(m->d_tokens, &token, 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(m->d_state, hs, sizeof(hs), hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipMemcpyAsync(m->d_cst, hc, sizeof(hc), hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);      // (the words above are the caller's and this frame's)
+        return 0;
+    };
+    // (measurement switch, read once per process: tools/constrain_probe.py sweeps the leg with it)
+    static const int leg_env = getenv("LLAMAHIP_CONSTRAIN_LEG") ? atoi(getenv("LLAMAHIP_CONSTRAIN_LEG")) : 0;
+    const int32_t leg_steps = leg_env >= 1 && leg_env <= 64 ? leg_env : LLAMAHIP_CONSTRAIN_LEG;
+    if ((rc = publish(first_token, 0, *state_io)) != 0) return rc;
+    int32_t ran = 0, hc[2] = { *state_io, 0 };
+    do {      // (a state that comes in as DONE still takes a step: the stop token, as the reference loop)
+        const int32_t leg = std::min<int32_t>(leg_steps, n_steps - ran);
+        for (int32_t i = 0; i < leg; i++) if ((rc = step(n_past + ran + i)) != 0) return rc;
+        ran += leg;
+        HIP_TRY(hipMemcpyAsync(hc, m->d_cst, sizeof(hc), hipMemcpyDeviceToHost, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+        if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
+        if (hc[1] != 0 || hc[0] < 0 || hc[0] >= c->n_states) {
+            set_err(err, err_cap, "%s: a pick found no allowed token (state word %d, dead %d): the state does not come from this constraint", fn, hc[0], hc[1]);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    } while (ran < n_steps && hc[0] != done);
+    HIP_TRY(hipMemcpy(out_tokens, m->d_out_tokens, (size_t) ran * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+    const int32_t fin = hc[0] == done;
+    int32_t n = ran;
+    if (fin) for (n = 0; n < ran && out_tokens[n] != c->stop_token; n++) {}
+    if (fin) n = std::min(n + 1, ran);      // the stop token counts; what a leg produced behind it (stop tokens in DONE) is not reported
+    if (logits_last && n < ran) {
+        // the leg ran past the stop token: m->logits holds a later step's row.  The step that picked the stop token once more, from the words it
+        // had then -- the same launches on the same operands, so the same bits, and KV row n_past + n - 1 is rewritten with what it holds
+        int32_t state = *state_io;
+        for (int32_t k = 0; k + 1 < n; k++) state = llamahip_constraint_advance(c, state, out_tokens[k]);
+        if ((rc = publish(n >= 2 ? out_tokens[n - 2] : first_token, n - 1, state)) != 0) return rc;
+        if ((rc = step(n_past + n - 1)) != 0) return rc;
+    }
+    if (logits_last) HIP_TRY(hipMemcpyAsync(logits_last, m->logits, (size_t) V * 4, hipMemcpyDeviceToHost, m->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+    if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
+    *state_io = hc[0]; *n_out = n; *finished = fin;
+    m->n_evals += ran;
     m->t_eval_ms += now_ms() - t0;
     return LLAMAHIP_OK;
 }
@@ -3512,6 +3679,159 @@ int llamahip_decode_greedy_multi(llamahip_model *m, int32_t n_threads, int32_t n
     m->n_evals += (int64_t) n_seqs * n_steps;
     m->t_eval_ms += now_ms() - t0;
     if (!m->stages.empty()) m->pipe_hand_off = 1;
+    return LLAMAHIP_OK;
+}
+
+// Constrained greedy decoding for several sequences at once (llamahip.h): llamahip_decode_greedy_multi's loop -- sequence i
+// bound to slot i, one set step per token for all of them, the captured set step exactly as it is -- with ONE k_pick_dfa launch over the
+// step's rows behind it (step_group's hook).  That launch re-picks from the step's logits under each row's own table and state word and
+// overwrites what the step's tail wrote: the trace entry at step - 1 and the slot's next-token word; the position stays as the tail advanced
+// it.  A finished sequence stays in the set in DONE (its picks are stop tokens).  The host reads the {state, dead} words once per leg.
+int llamahip_decode_greedy_constrained_multi(llamahip_model *m, int32_t n_threads, int32_t n_seqs, const int32_t *n_past, const int32_t *first_tokens,
+                                             int32_t n_steps, llamahip_constraint *const *constraints, int32_t *states_io, int32_t *out_tokens,
+                                             int32_t *n_out, int32_t *finished, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_decode_greedy_constrained_multi";
+    if (!m || !n_past || !first_tokens || !constraints || !states_io || !out_tokens || !n_out || !finished) {
+        set_err(err, err_cap, "%s: %s is NULL", fn, !m ? "model" : !n_past ? "n_past" : !first_tokens ? "first_tokens" : !constraints ? "constraints" : !states_io ? "states_io"
+                : !out_tokens ? "out_tokens" : !n_out ? "n_out" : "finished");
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    if (n_seqs < 1 || n_seqs > SET_MAX) { set_err(err, err_cap, "%s: n_seqs %d outside 1 .. %d", fn, n_seqs, SET_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_steps < 1) { set_err(err, err_cap, "%s: n_steps must be >= 1 (got %d)", fn, n_steps); return LLAMAHIP_ERR_PREDICT; }
+    const int V = m->hp.n_vocab;
+    for (int i = 0; i < n_seqs; i++) {
+        const llamahip_constraint *c = constraints[i];
+        if (!c) { set_err(err, err_cap, "%s: constraints[%d] is NULL", fn, i); return LLAMAHIP_ERR_PREDICT; }
+        if (c->m != m) { set_err(err, err_cap, "%s: constraints[%d] was made on another handle", fn, i); return LLAMAHIP_ERR_PREDICT; }
+        if (states_io[i] < 0 || states_io[i] >= c->n_states) { set_err(err, err_cap, "%s: states_io[%d] = %d out of range [0, %d)", fn, i, states_io[i], c->n_states); return LLAMAHIP_ERR_PREDICT; }
+        if (first_tokens[i] < 0 || first_tokens[i] >= V) { set_err(err, err_cap, "%s: token id %d out of range [0, %d)", fn, first_tokens[i], V); return LLAMAHIP_ERR_PREDICT; }
+        if (n_past[i] < 0 || (int64_t) n_past[i] + n_steps > m->hp.n_ctx) {
+            set_err(err, err_cap, "%s: context overflow: n_past (%d) + n_steps (%d) > n_ctx (%d)", fn, n_past[i], n_steps, m->hp.n_ctx);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    }
+    const std::vector<llamahip_model *> stages = stages_of(m);
+    llamahip_model *first = stages[0], *last = stages.back();
+    if (n_seqs > first->n_seq) { set_err(err, err_cap, "%s: %d sequences on a handle with %d KV slots (llamahip_opts.n_seq)", fn, n_seqs, first->n_seq); return LLAMAHIP_ERR_PREDICT; }
+    if (first->host_only) { set_err(err, err_cap, "%s: model was loaded with LLAMAHIP_FLAG_HOST_ONLY: no device state, cannot evaluate", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (!first->first_stage || !last->last_stage) { set_err(err, err_cap, "%s: needs a whole-model or a pipeline handle", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (stages.size() > 1 || !multi_stage_steps(first))
+        // pipeline handles, and handles with no stage step to batch (Q4_1 files, LLAMAHIP_FLAG_UNFUSED): the single-sequence call on each slot in turn
+        return each_slot(m, n_seqs, nullptr, err, err_cap, [&](int i) {
+            return llamahip_decode_greedy_constrained(m, n_threads, n_past[i], first_tokens[i], n_steps, constraints[i], states_io + i,
+                                                      out_tokens + (size_t) i * n_steps, n_out + i, finished + i, nullptr, err, err_cap); });
+    const double t0 = now_ms();
+    int rc = 0;
+    HIP_TRY(hipSetDevice(m->device), LLAMAHIP_ERR_PREDICT);
+    for (int i = 0; i < n_seqs; i++) if ((rc = cst_ensure_dev(m, constraints[i], err, err_cap)) != 0) return rc;
+    if ((rc = multi_begin(stages, 1, n_seqs, n_past, first_tokens, err, err_cap)) != 0) return rc;
+    int32_t hc[2 * SET_MAX];
+    for (int i = 0; i < n_seqs; i++) { hc[2 * i] = states_io[i]; hc[2 * i + 1] = 0; }
+    HIP_TRY(hipMemcpy(m->d_cst, hc, (size_t) n_seqs * 8, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
+    std::vector<int32_t> slots(n_seqs);
+    for (int i = 0; i < n_seqs; i++) slots[i] = i;
+    // rows [0, R) of the step's logits are slots j .. j + R - 1 (a set orders its rows by slot id; a single step leaves row 0)
+    const std::function<int(int, int)> repick = [&](int j, int R) -> int {
+        DfaRows rows = {};
+        for (int r = 0; r < R; r++) {
+            const int i = j + r;
+            const llamahip_constraint *c = constraints[i];
+            rows.r[r] = { m->logits + (size_t) r * V, c->dev, m->d_cst + 2 * i, m->d_slot_trace + (size_t) i * m->hp.n_ctx, m->mq_tok + i, m->d_slot_state + 2 * i,
+                          c->n_states, c->stop_token, 0, 1 };
+        }
+        HIP_TRY(launch_pick_dfa(rows, R, V, m->stream), LLAMAHIP_ERR_PREDICT);
+        return 0;
+    };
+    static const int leg_env = getenv("LLAMAHIP_CONSTRAIN_LEG") ? atoi(getenv("LLAMAHIP_CONSTRAIN_LEG")) : 0;
+    const int32_t leg_steps = leg_env >= 1 && leg_env <= 64 ? leg_env : LLAMAHIP_CONSTRAIN_LEG;
+    int32_t ran = 0;
+    bool all_done = false;
+    while (ran < n_steps && !all_done && rc == 0) {
+        const int32_t leg = std::min<int32_t>(leg_steps, n_steps - ran);
+        for (int32_t t = 0; t < leg && rc == 0; t++) rc = step_group(stages, { slots.data(), n_seqs, 0, n_seqs, 0 }, n_threads, false, false, repick, err, err_cap);
+        if (rc) break;
+        ran += leg;
+        HIP_TRY(hipMemcpyAsync(hc, m->d_cst, (size_t) n_seqs * 8, hipMemcpyDeviceToHost, m->stream), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+        if ((rc = check_sync_timeout(m, err, err_cap)) != 0) break;
+        all_done = true;
+        for (int i = 0; i < n_seqs; i++) {
+            if (hc[2 * i + 1] != 0 || hc[2 * i] < 0 || hc[2 * i] >= constraints[i]->n_states) {
+                set_err(err, err_cap, "%s: a pick of sequence %d found no allowed token (state word %d, dead %d): the state does not come from its constraint", fn, i, hc[2 * i], hc[2 * i + 1]);
+                rc = LLAMAHIP_ERR_PREDICT;
+                break;
+            }
+            all_done = all_done && hc[2 * i] == constraints[i]->n_states - 1;
+        }
+    }
+    if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
+    for (int i = 0; i < n_seqs; i++) {
+        int32_t pos = 0, *out = out_tokens + (size_t) i * n_steps;
+        const int n = llamahip_stage_trace(last, i, &pos, out, ran, err, err_cap);
+        if (n < 0) return n;
+        if (n != ran || pos != n_past[i] + ran) { set_err(err, err_cap, "%s: sequence %d recorded %d of %d steps, position %d", fn, i, n, ran, pos); return LLAMAHIP_ERR_PREDICT; }
+        const llamahip_constraint *c = constraints[i];
+        const int32_t fin = hc[2 * i] == c->n_states - 1;
+        int32_t k = ran;
+        if (fin) { for (k = 0; k < ran && out[k] != c->stop_token; k++) {} k = std::min(k + 1, ran); }
+        states_io[i] = hc[2 * i]; n_out[i] = k; finished[i] = fin;
+    }
+    m->n_evals += (int64_t) n_seqs * ran;
+    m->t_eval_ms += now_ms() - t0;
+    return LLAMAHIP_OK;
+}
+
+// llamahip_eval_topk under a constraint (llamahip.h): the eval, k_mask_rows_dfa from the logits row into a scratch row, the candidate
+// selection of llamahip_eval_topk on that row.  Where llamahip_eval_topk falls back to the logits row (pipeline handles, sizes the selection
+// does not take) the row is masked on the host: *exact = 0, logits_out = the masked row.
+int llamahip_eval_topk_constrained(llamahip_model *m, int32_t n_threads, int32_t n_past, const int32_t *tokens, int32_t n_tokens,
+                                   const int32_t *last_n_tokens, int32_t n_last, double repeat_penalty, int32_t top_k, double temp,
+                                   llamahip_constraint *c, int32_t state, double *cand_scores, int32_t *cand_ids, int32_t *exact, float *logits_out,
+                                   char *err, size_t err_cap) {
+    static const char *fn = "llamahip_eval_topk_constrained";
+    if (!m || !c || !cand_scores || !cand_ids || !exact || !logits_out) { set_err(err, err_cap, "%s: null argument", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (c->m != m) { set_err(err, err_cap, "%s: the constraint was made on another handle", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (state < 0 || state >= c->n_states) { set_err(err, err_cap, "%s: state %d out of range [0, %d)", fn, state, c->n_states); return LLAMAHIP_ERR_PREDICT; }
+    *exact = 0;
+    const int V = m->hp.n_vocab;
+    const int k = std::min(std::max(top_k, 1), V);
+    const bool device_ok = m->stages.empty() && !m->host_only && V <= 32768 && k <= 64 && n_last >= 0 && n_last <= 1024 && (n_last == 0 || last_n_tokens);
+    if (!device_ok) {
+        const int rc = llamahip_eval(m, n_threads, n_past, tokens, n_tokens, logits_out, err, err_cap);
+        if (rc) return rc;
+        return llamahip_constraint_mask_row(c, state, logits_out, logits_out);
+    }
+    const double t0 = now_ms();
+    int rc = eval_impl(m, n_threads, n_past, tokens, n_tokens, nullptr, nullptr, -1, nullptr, 0, nullptr, false, err, err_cap);   // logits stay on the device, no wait
+    if (rc) return rc;
+    if ((rc = cst_ensure_dev(m, c, err, err_cap)) != 0) return rc;
+    if (!m->d_cst_row) HIP_TRY(m->own.alloc(&m->d_cst_row, (size_t) V), LLAMAHIP_ERR_PREDICT);
+    if (!m->d_topk) HIP_TRY(m->own.alloc(&m->d_topk, 8192 + TOPK_WS_BYTES, true), LLAMAHIP_ERR_PREDICT);
+    int32_t *d_win = (int32_t *) m->d_topk;
+    double *d_sc = (double *) ((char *) m->d_topk + 4096);
+    int32_t *d_id = (int32_t *) ((char *) m->d_topk + 4096 + 512), *d_fl = d_id + 64;
+    const bool mapped = m->h_io != nullptr;
+    if (mapped) {
+        if (n_last > 0) memcpy(m->h_io->window, last_n_tokens, (size_t) n_last * 4);
+        d_win = m->d_io->window; d_sc = m->d_io->sc; d_id = m->d_io->id; d_fl = m->d_io->fl;
+    } else if (n_last > 0) HIP_TRY(hipMemcpyAsync(d_win, last_n_tokens, (size_t) n_last * 4, hipMemcpyHostToDevice, m->stream), LLAMAHIP_ERR_PREDICT);
+    DfaMaskRows mr = {};
+    mr.row[0] = c->dev + (size_t) state * V;
+    HIP_TRY(launch_mask_rows_dfa(m->logits + (size_t) (n_tokens - 1) * V, m->d_cst_row, 1, V, mr, m->stream), LLAMAHIP_ERR_PREDICT);
+    const float *row = m->d_cst_row;
+    HIP_TRY(launch_topk_candidates(row, V, d_win, n_last, 1.0 / temp, repeat_penalty, k, d_sc, d_id, d_fl, m->stream, (char *) m->d_topk + 8192), LLAMAHIP_ERR_PREDICT);
+    struct { double sc[64]; int32_t id[64]; int32_t fl[2]; } h;
+    if (!mapped) HIP_TRY(hipMemcpyAsync(&h, d_sc, sizeof(h), hipMemcpyDeviceToHost, m->stream), LLAMAHIP_ERR_PREDICT);
+    HIP_TRY(hipStreamSynchronize(m->stream), LLAMAHIP_ERR_PREDICT);
+    if (mapped) { memcpy(h.sc, m->h_io->sc, sizeof(h.sc)); memcpy(h.id, m->h_io->id, sizeof(h.id)); memcpy(h.fl, m->h_io->fl, sizeof(h.fl)); }
+    if ((rc = check_sync_timeout(m, err, err_cap)) != 0) return rc;
+    m->t_eval_ms += now_ms() - t0;
+    if (h.fl[0] == 1) {
+        for (int i = 0; i < k; i++) { cand_scores[i] = h.sc[i]; cand_ids[i] = h.id[i]; }
+        *exact = 1;
+        return LLAMAHIP_OK;
+    }
+    HIP_TRY(hipMemcpy(logits_out, row, (size_t) V * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
     return LLAMAHIP_OK;
 }
 

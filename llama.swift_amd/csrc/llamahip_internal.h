@@ -390,5 +390,20 @@ constexpr int KV_SHIFT_MAX = 16, KV_SHIFT_U = 8;
 struct KvShiftTab { int32_t n; int32_t slot[KV_SHIFT_MAX], row_begin[KV_SHIFT_MAX], n_rows[KV_SHIFT_MAX], n_discard[KV_SHIFT_MAX]; };
 hipError_t launch_kv_shift_rows(float *Kc, float *Vc, const double *sincos_tab, const KvShiftTab &tab, int n_slots, int n_layers, int n_ctx, int d, int dh,
                                 hipStream_t st);
+// constrained decoding (constrain.hip): the pick of 1 .. DFA_ROWS_MAX rows under their constraints' token tables, and the masked rows for the
+// sampler front end.  A row of k_pick_dfa: its logits row, its table next[n_states][V] (DFA_BANNED_U16 = not allowed), its words
+// cst = {state, dead}, the token picked where the state is out of range or nothing is allowed (dead := 1, state kept), and k_argmax's
+// operands: out[st ? st[1] : out_idx] = pick (out may be null), *next_token = pick (may be null), st = {position, step} advanced (may be null).
+// The rows travel by value in the kernel arguments, so a captured step replays them.
+constexpr int DFA_ROWS_MAX = 16;
+constexpr uint16_t DFA_BANNED_U16 = 0xFFFF;
+struct DfaRow {
+    const float *logits; const uint16_t *table; int32_t *cst; int32_t *out; int32_t *next_token; int32_t *st;
+    int32_t n_states, fallback, out_idx, repick;      // repick: out[st[1] - 1] = pick, st stays (behind a step that has advanced it)
+};
+struct DfaRows { DfaRow r[DFA_ROWS_MAX]; };
+struct DfaMaskRows { const uint16_t *row[DFA_ROWS_MAX]; };
+hipError_t launch_pick_dfa(const DfaRows &rows, int n_rows, int V, hipStream_t st);
+hipError_t launch_mask_rows_dfa(const float *logits, float *out, int n_rows, int V, const DfaMaskRows &rows, hipStream_t st);
 
 }  // namespace lh

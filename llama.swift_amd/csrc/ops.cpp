@@ -1055,6 +1055,67 @@ int llamahip_op_verify_rows(const float *logits, int32_t n_rows, int32_t n_vocab
     return LLAMAHIP_OK;
 }
 
+// what the two constrained-decoding ops refuse of their operands: 0, or LLAMAHIP_ERR_PREDICT with the limit in err
+static int dfa_op_check(const char *fn, const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, const int32_t *states,
+                        char *err, size_t err_cap) {
+    if (!logits || !table || !states) { set_err(err, err_cap, "%s: %s is NULL", fn, !logits ? "logits" : !table ? "table" : "states"); return LLAMAHIP_ERR_PREDICT; }
+    if (n_rows < 1 || n_rows > DFA_ROWS_MAX) { set_err(err, err_cap, "%s: n_rows %d outside 1 .. %d", fn, n_rows, DFA_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
+    if (n_vocab < 1) { set_err(err, err_cap, "%s: n_vocab must be >= 1 (got %d)", fn, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (n_table_states < 1 || n_table_states > 0xFFFF) { set_err(err, err_cap, "%s: n_table_states %d outside 1 .. %d", fn, n_table_states, 0xFFFF); return LLAMAHIP_ERR_PREDICT; }
+    const size_t n = (size_t) n_table_states * (size_t) n_vocab;
+    for (size_t i = 0; i < n; i++)
+        if (table[i] != DFA_BANNED_U16 && table[i] >= n_table_states) {
+            set_err(err, err_cap, "%s: table[%zu][%zu] = %d is neither a state below %d nor BANNED (65535)", fn, i / (size_t) n_vocab, i % (size_t) n_vocab, (int) table[i], n_table_states);
+            return LLAMAHIP_ERR_PREDICT;
+        }
+    return 0;
+}
+
+// k_pick_dfa on caller-supplied rows (parity tests): see llamahip_decode_greedy_constrained
+int llamahip_op_pick_dfa(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, int32_t *states_io,
+                         int32_t fallback_token, int32_t *picks, int32_t *dead, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_pick_dfa";
+    if (dfa_op_check(fn, logits, n_rows, n_vocab, table, n_table_states, states_io, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!picks || !dead) { set_err(err, err_cap, "%s: %s is NULL", fn, !picks ? "picks" : "dead"); return LLAMAHIP_ERR_PREDICT; }
+    if (fallback_token < 0 || fallback_token >= n_vocab) { set_err(err, err_cap, "%s: fallback_token %d out of range [0, %d)", fn, fallback_token, n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, V = (size_t) n_vocab;
+    int32_t h[3 * DFA_ROWS_MAX];      // picks | {state, dead} per row: the caller's words go up and come back, so what the kernel leaves alone shows
+    for (size_t r = 0; r < N; r++) { h[r] = picks[r]; h[DFA_ROWS_MAX + 2 * r] = states_io[r]; h[DFA_ROWS_MAX + 2 * r + 1] = dead[r]; }
+    Scratch s;
+    float *d_l = s.alloc(N * V, logits);
+    uint16_t *d_t = s.alloc((size_t) n_table_states * V, table);
+    int32_t *d_w = s.alloc(3 * (size_t) DFA_ROWS_MAX, h);
+    DfaRows rows = {};
+    for (size_t r = 0; r < N; r++) rows.r[r] = { d_l + r * V, d_t, d_w + DFA_ROWS_MAX + 2 * r, d_w, nullptr, nullptr, n_table_states, fallback_token, (int32_t) r, 0 };
+    if (s.ok()) s.check(launch_pick_dfa(rows, n_rows, n_vocab, nullptr));
+    s.download(h, d_w, sizeof(h));
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (size_t r = 0; r < N; r++) { picks[r] = h[r]; states_io[r] = h[DFA_ROWS_MAX + 2 * r]; dead[r] = h[DFA_ROWS_MAX + 2 * r + 1]; }
+    return LLAMAHIP_OK;
+}
+
+// k_mask_rows_dfa on caller-supplied rows (parity tests): see llamahip_eval_topk_constrained
+int llamahip_op_mask_rows_dfa(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, const int32_t *states,
+                              float *out, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_mask_rows_dfa";
+    if (dfa_op_check(fn, logits, n_rows, n_vocab, table, n_table_states, states, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!out) { set_err(err, err_cap, "%s: out is NULL", fn); return LLAMAHIP_ERR_PREDICT; }
+    for (int32_t r = 0; r < n_rows; r++)
+        if (states[r] < 0 || states[r] >= n_table_states) { set_err(err, err_cap, "%s: states[%d] = %d out of range [0, %d)", fn, r, states[r], n_table_states); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, V = (size_t) n_vocab;
+    Scratch s;
+    float *d_l = s.alloc(N * V, logits), *d_o = s.alloc(N * V, out);      // (the caller's bits go up: an entry the kernel skipped would show)
+    uint16_t *d_t = s.alloc((size_t) n_table_states * V, table);
+    DfaMaskRows rows = {};
+    for (size_t r = 0; r < N; r++) rows.row[r] = d_t + (size_t) states[r] * V;
+    if (s.ok()) s.check(launch_mask_rows_dfa(d_l, d_o, n_rows, n_vocab, rows, nullptr));
+    s.download(out, d_o, N * V * 4);
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    return LLAMAHIP_OK;
+}
+
 // the pick half of k_sched_pick on caller-supplied rows, one segment per row, no slot words (parity tests): see llamahip_sched_step
 int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, int32_t *picks, char *err, size_t err_cap) {
     if (!logits || !emit || !picks || n_rows < 1 || n_rows > SET_MAX || n_vocab < 1) {

@@ -7,6 +7,7 @@
 // bridge's failure path, and -- with evals that succeed on made-up logits -- the driver's whole control flow (prompt taken at once,
 // chunk-exact pass + last chunk, one eval per generated token, event counts).  usage: host_sanitize <model file> [n_parts]   (exit code 0 = clean)
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -537,6 +538,146 @@ __attribute__((noinline)) static void beam_host_half(int V) {
     printf("host_sanitize: beam search: %ld walks and %ld slot assignments against the rules restated, %ld refusals at short and missing message buffers\n", n_sel, n_slots, n_checks);
 }
 
+// constrained decoding (constrain.cpp, compiled in as it is): the lift on the model file's vocabulary against the rule restated entry by entry,
+// on exactly sized arrays; a prune case (a state no token leads out of: its row and every way into it banned, as a start refused); every
+// refusal at message buffers too short for its text and with none; the choices builder against the walk of its strings; pick / mask_row /
+// advance at their edges (ties, signed zeros, NaN, all allowed entries NaN, states and tokens out of range)
+__attribute__((noinline)) static void constrain_host_half(const llamahip_model *m, int V) {
+    long n_entries = 0, n_checks = 0, n_picks = 0;
+    const int32_t stop = 2;
+    // bytes of the vocabulary's words: a .. z, the space, "tok" and digits.  0: start; 1: behind letters (accepting); 2: behind a space; 3: trap
+    const int S = 4;
+    std::vector<int32_t> trans((size_t) S * 256, -1);
+    std::vector<uint8_t> accept = { 0, 1, 0, 0 };
+    for (int b = 'a'; b <= 'z'; b++) { trans[0 * 256 + b] = 1; trans[1 * 256 + b] = 1; trans[2 * 256 + b] = 1; }
+    trans[1 * 256 + ' '] = 2;
+    for (int b = '0'; b <= '9'; b++) trans[1 * 256 + b] = 1;
+    trans[0 * 256 + ' '] = 3; trans[3 * 256 + ' '] = 3;      // the trap: enterable, never left towards an accepting state
+    llamahip_constraint *c = nullptr;
+    char err[256];
+    EXPECT(llamahip_constraint_new(m, S, trans.data(), accept.data(), 0, stop, &c, err, sizeof(err)) == 0 && c);
+    if (c) {
+        EXPECT(llamahip_constraint_n_states(c) == S + 1 && llamahip_constraint_start(c) == 0 && llamahip_constraint_done(c) == S);
+        const int64_t n = llamahip_constraint_table(c, nullptr, 0);
+        EXPECT(n == (int64_t) (S + 1) * V);
+        std::vector<uint16_t> tab((size_t) n), small((size_t) n - 1, 7);
+        EXPECT(llamahip_constraint_table(c, small.data(), n - 1) == n && small[0] == 7);      // too small: the count, nothing copied
+        EXPECT(llamahip_constraint_table(c, tab.data(), n) == n);
+        for (int s = 0; s <= S; s++)
+            for (int t = 0; t < V; t++) {
+                uint32_t len = 0;
+                const uint8_t *text = (const uint8_t *) llamahip_token_text(m, t, &len);
+                int want = -1;
+                if (s == S) want = t == stop ? S : -1;
+                else if (t == stop) want = accept[(size_t) s] ? S : -1;
+                else if (len > 0) {
+                    int q = s;
+                    for (uint32_t k = 0; k < len && q >= 0; k++) q = trans[(size_t) q * 256 + text[k]];
+                    want = q == 3 ? -1 : q;      // the prune: the trap is not live
+                }
+                if (s == 3) want = -1;           // ... and nothing leaves it
+                EXPECT(tab[(size_t) s * V + t] == (want < 0 ? LLAMAHIP_CONSTRAINT_BANNED : want));
+                EXPECT(llamahip_constraint_advance(c, s, t) == want);
+                n_entries++;
+            }
+        EXPECT(llamahip_constraint_advance(c, -1, 3) == -1 && llamahip_constraint_advance(c, S + 1, 3) == -1 && llamahip_constraint_advance(c, 0, V) == -1 && llamahip_constraint_advance(c, 0, -1) == -1);
+        // pick and mask_row on exactly sized rows
+        std::vector<float> row((size_t) V), out((size_t) V);
+        std::mt19937 rng(9);
+        for (int it = 0; it < 64; it++) {
+            const int s = it % (S + 1), mode = it / (S + 1) % 5;
+            for (int t = 0; t < V; t++) row[(size_t) t] = (float) ((int) (rng() % 17) - 8) * (mode == 1 ? 0.0f : 0.5f);      // coarse values: ties; mode 1: +0.0 / -0.0
+            if (mode == 2) for (int t = 0; t < V; t += 3) row[(size_t) t] = NAN;
+            if (mode == 3) for (int t = 0; t < V; t++) if (tab[(size_t) s * V + t] != LLAMAHIP_CONSTRAINT_BANNED) row[(size_t) t] = NAN;
+            if (mode == 4) for (int t = 0; t < V; t++) row[(size_t) t] = tab[(size_t) s * V + t] != LLAMAHIP_CONSTRAINT_BANNED ? -INFINITY : INFINITY;
+            int want = -1, lowest = -1;
+            for (int t = 0; t < V; t++) {
+                if (tab[(size_t) s * V + t] == LLAMAHIP_CONSTRAINT_BANNED) continue;
+                if (lowest < 0) lowest = t;
+                if (row[(size_t) t] == row[(size_t) t] && (want < 0 || row[(size_t) t] > row[(size_t) want])) want = t;
+            }
+            EXPECT(llamahip_constraint_pick(c, s, row.data()) == (want >= 0 ? want : lowest));
+            EXPECT(llamahip_constraint_mask_row(c, s, row.data(), out.data()) == 0);
+            for (int t = 0; t < V; t++) {
+                const float w = tab[(size_t) s * V + t] == LLAMAHIP_CONSTRAINT_BANNED ? -INFINITY : row[(size_t) t];
+                EXPECT(memcmp(&w, &out[(size_t) t], 4) == 0);
+            }
+            n_picks++;
+        }
+        EXPECT(llamahip_constraint_pick(c, S + 1, row.data()) == -1 && llamahip_constraint_pick(c, -1, row.data()) == -1 && llamahip_constraint_pick(c, 0, nullptr) == -1);
+        EXPECT(llamahip_constraint_mask_row(c, S + 1, row.data(), out.data()) != 0 && llamahip_constraint_mask_row(c, 0, nullptr, out.data()) != 0);
+        llamahip_constraint_free(c);
+    }
+    llamahip_constraint_free(nullptr);
+    EXPECT(llamahip_constraint_n_states(nullptr) == 0 && llamahip_constraint_start(nullptr) == -1 && llamahip_constraint_done(nullptr) == -1 && llamahip_constraint_table(nullptr, nullptr, 0) == -1);
+    // the refusals
+    auto refused = [&](auto call, const char *fn) {
+        for (size_t cap : { (size_t) 1, (size_t) 24, (size_t) 400 }) {
+            std::vector<char> e(cap, 'x');
+            llamahip_constraint *o = (llamahip_constraint *) 1;
+            EXPECT(call(&o, e.data(), cap) == LLAMAHIP_ERR_PREDICT && o == nullptr);
+            EXPECT(memchr(e.data(), 0, cap) != nullptr);
+            if (cap == 400) EXPECT(strstr(e.data(), fn) == e.data());
+            n_checks++;
+        }
+        llamahip_constraint *o = (llamahip_constraint *) 1;
+        EXPECT(call(&o, nullptr, 0) == LLAMAHIP_ERR_PREDICT && o == nullptr);
+    };
+    const char *fn1 = "llamahip_constraint_new", *fn2 = "llamahip_constraint_new_choices";
+    const int32_t *T = trans.data();
+    const uint8_t *A = accept.data();
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(nullptr, S, T, A, 0, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, nullptr, A, 0, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, nullptr, 0, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, 0, T, A, 0, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, 4097, T, A, 0, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, A, S, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, A, -1, stop, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, A, 0, V, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, A, 0, -1, o, e, cap); }, fn1);
+    refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, A, 3, stop, o, e, cap); }, fn1);      // the trap as the start: not live
+    { const std::vector<uint8_t> none((size_t) S, 0);
+      refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, T, none.data(), 0, stop, o, e, cap); }, fn1); }
+    { std::vector<int32_t> bad = trans; bad.back() = S;
+      refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, bad.data(), A, 0, stop, o, e, cap); }, fn1);
+      bad.back() = -2;
+      refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new(m, S, bad.data(), A, 0, stop, o, e, cap); }, fn1); }
+    EXPECT(llamahip_constraint_new(m, S, T, A, 0, stop, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT);
+    // the choices builder: exactly sized strings; the table against the walk of the strings
+    {
+        const std::vector<std::vector<uint8_t>> strs = { { 'a', 'b' }, { 'a', 'b', 'c' }, { 'b' }, { 'a', 'b' }, { 't', 'o', 'k', '0', '0', '0', '4', '0' } };
+        std::vector<const uint8_t *> ptr;
+        std::vector<int32_t> len;
+        for (const auto &s : strs) { ptr.push_back(s.data()); len.push_back((int32_t) s.size()); }
+        llamahip_constraint *cc = nullptr;
+        EXPECT(llamahip_constraint_new_choices(m, ptr.data(), len.data(), (int32_t) strs.size(), stop, &cc, err, sizeof(err)) == 0 && cc);
+        if (cc) {
+            EXPECT(llamahip_constraint_n_states(cc) == 1 + 2 + 1 + 1 + 8 + 1);      // root, a ab, abc, b, tok00040's eight, DONE
+            const int done = llamahip_constraint_done(cc);
+            // every token that is a prefix-walk of a choice advances; the stop token is allowed exactly at a string's end
+            int q = 0;
+            for (uint8_t b : strs[1]) { int t = -1; for (int v = 3; v < V && t < 0; v++) { uint32_t l = 0; const char *x = llamahip_token_text(m, v, &l); if (l == 1 && (uint8_t) x[0] == b) t = v; }
+                                        EXPECT(llamahip_constraint_advance(cc, q, stop) == ((q == 0 || q == 1) ? -1 : done)); q = t < 0 ? -1 : llamahip_constraint_advance(cc, q, t); EXPECT(q > 0); if (q < 0) break; }
+            if (q > 0) EXPECT(llamahip_constraint_advance(cc, q, stop) == done);
+            EXPECT(llamahip_constraint_advance(cc, done, stop) == done);
+            llamahip_constraint_free(cc);
+        }
+        refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, ptr.data(), len.data(), 0, stop, o, e, cap); }, fn2);
+        refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, nullptr, len.data(), 2, stop, o, e, cap); }, fn2);
+        refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, ptr.data(), nullptr, 2, stop, o, e, cap); }, fn2);
+        refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, ptr.data(), len.data(), 2, V, o, e, cap); }, fn2);
+        { std::vector<int32_t> l0 = len; l0[1] = 0;
+          refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, ptr.data(), l0.data(), 3, stop, o, e, cap); }, fn2); }
+        { std::vector<const uint8_t *> p0 = ptr; p0[2] = nullptr;
+          refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, p0.data(), len.data(), 3, stop, o, e, cap); }, fn2); }
+        { const std::vector<uint8_t> longs(5000, 'a'); const uint8_t *lp[1] = { longs.data() }; const int32_t ll[1] = { 5000 };
+          refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, lp, ll, 1, stop, o, e, cap); }, fn2); }
+        { const uint8_t hi[2] = { 0xff, 0xfe }; const uint8_t *lp[1] = { hi }; const int32_t ll[1] = { 2 };      // bytes no token supplies: the start is not live
+          refused([&](llamahip_constraint **o, char *e, size_t cap) { return llamahip_constraint_new_choices(m, lp, ll, 1, stop, o, e, cap); }, fn2); }
+    }
+    printf("host_sanitize: constraints: %ld table entries against the lift restated, %ld picks and masked rows, %ld refusals at short and missing message buffers\n", n_entries, n_picks, n_checks);
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "usage: host_sanitize <model file> [n_parts]\n"); return 2; }
     const std::string path = argv[1];
@@ -586,6 +727,7 @@ int main(int argc, char **argv) {
     EXPECT(llamahip_sampler_window(s, win, 64) == 64);
     EXPECT(llamahip_sampler_random_prompt(s) != nullptr);
     llamahip_sampler_free(s);
+    constrain_host_half(m, V);      // (the lift reads the handle's vocabulary)
     llamahip_model_free(m);
     // corrupted copies of the file: every header field and a sweep of truncations must be load errors, never crashes
     std::vector<uint8_t> raw;
