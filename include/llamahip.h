@@ -814,7 +814,53 @@ int llamahip_op_pool_rows(const float *x /* [R][d] */, int32_t R, int32_t d, con
  *   Measured on the 7B (tools/sched_probe.py --shared-prefix 256; the figures are in profiles/sched_prefix_probe_7b.json and DESIGN.md 12.23): 64 requests
  *   behind one 256-token system prompt run about a third faster with the option on; k_kv_copy_rows is faster than a loop of hipMemcpyAsync calls over
  *   the same ranges for 9 rows, for 256 rows and for a 15-way broadcast; prefix_share 0 is unchanged against the parent commit's library.
- * Not built: the scheduler behind llama_runner; more than 16 active sequences; a set-step-descriptor form for
+ * Constrained requests (llamahip_request.constraint; forced tokens as drafts: llamahip_sched_opts.forced_drafts, off by default; DESIGN.md
+ *   12.34).  A greedy request may carry a constraint (llamahip_constraint_*, below) and the automaton state before its first pick
+ *   (constraint_state; -1 = the constraint's start): every one of its picks is then k_pick_dfa's rule over the entries its state allows, the
+ *   host half advances the state over every token it reports, and the constraint's stop token ends the request (stop_token is -1 or that
+ *   token).  The caller keeps the constraint alive until the request's DONE.  The scheduler waits for every step's picks, so the host knows
+ *   each request's state before it builds the next step: the kernels take, per logits row and BY VALUE in their arguments, a pointer to the
+ *   table row next[state] (null = the row is unconstrained) and a range-checked fallback token -- no device-resident state word.
+ *   CONTRACT, the sentence above extended: the tokens of a constrained request, its DONE reason and the KV rows [0, n_prompt + n - 1) of its
+ *   slot in every layer are bit for bit those of the request ALONE on that slot -- llamahip_set_seq(slot), llamahip_eval_chunks(prompt, 0,
+ *   chunk_tokens), then the loop llamahip_constraint_pick(c, state, logits) -> llamahip_constraint_advance -> one-token llamahip_eval, cut
+ *   behind the stop token (reason STOP) or at n_predict (LENGTH) -- whatever else is in flight, for every submission order, row_budget,
+ *   draft_len and forced_drafts.  BY TEST (tests/test_gpu_sched_constrain.py), as for every multi-row step.
+ *   What a step launches.  No emitting greedy segment constrained: exactly what it launched before.  A mixed pass without drafts:
+ *   k_sched_pick_dfa in k_sched_pick's place (same geometry, same stores, dead flags behind the picks in the result block).  A step with
+ *   drafts: k_verify_rows_dfa in k_verify_rows' place -- each logits row picked under the state reached by advancing over the draft tokens
+ *   in front of it -- and k_sched_accept unchanged behind it.  A decode-only step: the captured set step (the single step for one active
+ *   slot) exactly as it is, then ONE k_sched_pick_dfa launch over the step's logits rows with the advanced {position, cursor} in its table; it
+ *   overwrites the trace entry and the next-token word the step's own tail wrote, as llamahip_decode_greedy_constrained_multi does with
+ *   k_pick_dfa.  (The stage step's tail only stores its pick; nothing reads the token word before the next step's embedding gather, which
+ *   runs behind the re-pick on the same stream.  A single active constrained slot therefore keeps the single step.)  A row that allows
+ *   nothing -- impossible with a state the constraint handed out -- picks the constraint's stop token and sets its dead word: the step fails
+ *   with LLAMAHIP_ERR_PREDICT.  Fall-back handles run the contract's own loop per slot (one-token evals, the host pick) and draft nothing.
+ *   Drafts of a constrained request.  With forced_drafts = 1 it wants its FORCED RUN (llamahip_forced_run) from the state behind the
+ *   token it is about to evaluate, cut to 15 tokens and to n_predict - n_out - 1: a draft that is accepted by construction, because a forced
+ *   token is the only allowed entry of its row and the rule picks it whatever the logits hold -- an answer of ten forced tokens costs one
+ *   weight pass instead of ten, and the stream stays the single-token loop's.  Where the forced run is empty and draft_len > 0 it wants its
+ *   lookup draft, cut at the first token banned in the running state and behind a drafted stop token.  The spare rows are dealt by
+ *   llamahip_sched_plan_drafts, unchanged.  forced_drafts works with draft_len == 0; the event capacity a step then requires is
+ *   LLAMAHIP_SCHED_EVENT_CAP(max_active, 1) = max_active + 17, and a smaller cap is refused.
+ *   Stats: n_dfa_rows (logits rows picked under a constraint), n_forced_drafted / n_forced_accepted (counted in n_drafted / n_accepted too).
+ *   n_forced_accepted == n_forced_drafted always, and n_tokens == n_emit_segs + n_accepted - n_dropped still holds.
+ *   Struct sizes: llamahip_sched_submit takes a llamahip_request of the size before these fields (offsetof constraint) or larger and reads
+ *   the new fields only where struct_size covers them; llamahip_sched_new reads forced_drafts only where struct_size covers it.
+ *   Refused before any device work, the message naming the limit.  llamahip_sched_new: forced_drafts other than 0 or 1.
+ *   llamahip_sched_submit: a constraint made on another handle; constraint_state outside [-1, n_states); a stop_token that is neither -1 nor
+ *   the constraint's stop token; a sampler together with a constraint; a constrained request on an in-process pipeline handle (the table's
+ *   device copy belongs to one device).
+ *   llamahip_op_verify_rows_allow / llamahip_op_sched_pick_allow -- the two kernels on caller-supplied rows (parity tests): logits[n_rows][n_vocab],
+ *   n_rows 1 .. 16, ONE table[n_table_states][n_vocab], states[n_rows] (-1 = unconstrained), fallback[n_rows]; picks / dead [n_rows] out.
+ *   sched_pick_dfa also takes emit[n_rows] as llamahip_op_sched_pick does (picks -1 and dead 0 where emit == 0) and, optionally, slot words:
+ *   seg_words[n_rows][3] = {slot, position, cursor} with state[n_slots][2], log[n_slots][log_cap], next_tok[n_slots] -- all four or none,
+ *   copied both ways.  Refused before any launch: a NULL array, n_rows outside 1 .. 16, n_vocab < 1, n_table_states outside 1 .. 65535, a
+ *   table entry that is neither a state nor BANNED, a state outside [-1, n_table_states), a fallback token out of range.
+ *   Measured: not measured yet (tools/sched_probe.py --constrained).
+ * Not built: sampled constrained requests; constrained requests on pipeline handles; forced rows without an lm head (a forced token's row
+ *   still runs the lm head and the pick: the verify step is what keeps the stream the single-token loop's); the scheduler behind
+ *   llama_runner; more than 16 active sequences; a set-step-descriptor form for
  *   decode-only drafted steps; drafts counted against row_budget; sharing decode rows or rows at chunk_tokens == 0; a prefix store beyond
  *   the slots' own records;
  *   generating past n_ctx (llamahip_decode_greedy_window's overflow plan); the mixed pass on the fused few-row launches. */
@@ -839,6 +885,8 @@ typedef struct llamahip_sched_opts {
     const int32_t *corpus; int32_t n_corpus;   /* optional, searched behind a request's own history; copied at llamahip_sched_new */
     /* shared prompt prefixes (read only where struct_size covers it; a shorter struct means off) */
     int32_t prefix_share;    /* 0 = off; 1 = a request takes over the evaluated prompt rows it has in common with a slot's record */
+    /* forced tokens as drafts (read only where struct_size covers it; a shorter struct means off) */
+    int32_t forced_drafts;   /* 0 = off; 1 = a constrained greedy request's forced run rides as its draft (works with draft_len == 0) */
 } llamahip_sched_opts;
 #define LLAMAHIP_SCHED_EVENT_CAP(max_active, draft_len) ((draft_len) > 0 ? (max_active) + 17 : 2 * (max_active) + 1)   /* the smallest cap llamahip_sched_step takes */
 typedef struct llamahip_request {
@@ -847,6 +895,9 @@ typedef struct llamahip_request {
     int32_t n_predict;                         /* >= 1 tokens to produce */
     int32_t stop_token;                        /* -1 = none; the request ends after producing it */
     llamahip_sampler *sampler;                 /* NULL = greedy; else drawn from and accepted into, as llamahip_decode_sample_multi */
+    /* constrained requests (read only where struct_size covers them; the struct up to `sampler` is still taken) */
+    struct llamahip_constraint *constraint;    /* NULL = none; the caller's, alive until the request's DONE; greedy requests only */
+    int32_t constraint_state;                  /* the automaton's state before the first pick; -1 = the constraint's start */
 } llamahip_request;
 typedef struct llamahip_sched_event {
     int64_t id; int32_t kind;                  /* LLAMAHIP_EV_TOKEN / LLAMAHIP_EV_DONE */
@@ -864,6 +915,8 @@ typedef struct llamahip_sched_stats {
     int64_t n_emit_segs, n_dropped;            /* emitting segments over all steps; accepted tokens dropped behind a stop token */
     int64_t n_shared_rows, n_copied_rows;      /* prompt rows taken over instead of evaluated (in place or copied); of those, moved */
     int64_t n_copy_launches;                   /* k_kv_copy_rows launches (one per stage and copy) */
+    int64_t n_dfa_rows;                        /* logits rows picked under a constraint */
+    int64_t n_forced_drafted, n_forced_accepted;   /* of n_drafted / n_accepted, the forced tokens of constrained requests: always equal */
 } llamahip_sched_stats;
 int     llamahip_sched_new   (llamahip_model *m, const llamahip_sched_opts *o, llamahip_sched **out, char *err, size_t err_cap);
 int     llamahip_sched_submit(llamahip_sched *s, const llamahip_request *r, int64_t *id, char *err, size_t err_cap);
@@ -877,6 +930,14 @@ int32_t llamahip_sched_plan(int32_t n_active, const int32_t *prompt_left /* admi
 int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, int32_t *picks, char *err, size_t err_cap);
 int32_t llamahip_sched_plan_drafts(int32_t n_active, const int32_t *prompt_left, const int32_t *rows /* llamahip_sched_plan's */,
                                    const int32_t *want, int32_t *give);
+int llamahip_op_verify_rows_allow(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states,
+                                const int32_t *states /* -1 = unconstrained */, const int32_t *fallback, int32_t *picks, int32_t *dead,
+                                char *err, size_t err_cap);
+int llamahip_op_sched_pick_allow(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, const uint16_t *table,
+                               int32_t n_table_states, const int32_t *states /* -1 = unconstrained */, const int32_t *fallback,
+                               const int32_t *seg_words /* [n_rows][3] = {slot, position, cursor}; with the slot words or NULL */,
+                               int32_t n_slots, int32_t log_cap, int32_t *state, int32_t *log, int32_t *next_tok,
+                               int32_t *picks, int32_t *dead, char *err, size_t err_cap);
 int llamahip_op_sched_accept(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *seg_tab, int32_t n_segs, const int32_t *tokens,
                              int32_t n_slots, int32_t log_cap, int32_t *state, int32_t *log, int32_t *next_tok,
                              int32_t *n_accept, int32_t *picks, char *err, size_t err_cap);
@@ -1055,7 +1116,14 @@ int32_t llamahip_beam_slots(int32_t n_prev, const int32_t *prev_slot, int32_t n_
  *   measurement switch for tools/constrain_probe.py's leg sweep, not an interface; results do not depend on it.
  * HAZARD: a constraint keeps a pointer to its handle.  After llamahip_model_free the constraint may only be passed to llamahip_constraint_free;
  *   the "made on another handle" check compares that pointer and cannot tell a freed handle from a new one at the same address.
- * Not built: constraints in the scheduler, the runner, beam search and the drafted loops; context-free grammars; canonical tokenisation. */
+ * llamahip_forced_run(c, state, out, cap) -- THE FORCED RUN of a state: while fewer than cap tokens are out, the state is not DONE and
+ *   allows exactly ONE token, that token, and on to next[state][token].  An accepting state whose only allowed token is the stop token yields
+ *   the stop token, enters DONE, and the run ends there; DONE itself yields nothing.  Returns the count; -1 for a null constraint, a state out
+ *   of range or cap < 0 (out may be NULL when cap == 0).  The per-state "single allowed token or none" is computed once at the lift, in the
+ *   prune's walk over the table: a call costs O(run).  What such a state's pick will be is known before the model runs -- the request
+ *   scheduler drafts these tokens (llamahip_sched_opts.forced_drafts, "constrained requests" in the scheduler's section above).
+ * Not built: constraints in the runner, beam search and the drafted loops (llamahip_decode_greedy_lookup*); sampled constrained requests in the
+ *   scheduler; context-free grammars; canonical tokenisation. */
 #define LLAMAHIP_CONSTRAINT_BANNED 0xFFFF
 #define LLAMAHIP_CONSTRAIN_LEG 4          /* steps between two looks at the state word (measured: DESIGN.md 12.33, profiles/constrain_probe_7b.json) */
 typedef struct llamahip_constraint llamahip_constraint;
@@ -1070,6 +1138,7 @@ int32_t llamahip_constraint_done(const llamahip_constraint *c);
 int64_t llamahip_constraint_table(const llamahip_constraint *c, uint16_t *out, int64_t cap);
 int32_t llamahip_constraint_advance(const llamahip_constraint *c, int32_t state, int32_t token);
 int32_t llamahip_constraint_pick(const llamahip_constraint *c, int32_t state, const float *logits);
+int32_t llamahip_forced_run(const llamahip_constraint *c, int32_t state, int32_t *out, int32_t cap);
 int llamahip_constraint_mask_row(const llamahip_constraint *c, int32_t state, const float *logits_in, float *logits_out);
 int llamahip_decode_greedy_constrained(llamahip_model *m, int32_t n_threads, int32_t n_past, int32_t first_token, int32_t n_steps, llamahip_constraint *c,
                                        int32_t *state_io, int32_t *out_tokens, int32_t *n_out, int32_t *finished, float *logits_last,

@@ -106,6 +106,16 @@ class _Request(C.Structure):
                 ("stop_token", C.c_int32), ("sampler", C.c_void_p)]
 
 
+class _RequestCst(_Request):
+    """llamahip_request as it is now: the constraint fields appended behind _Request's (the struct is size-versioned; the old size is still taken)"""
+    _fields_ = [("constraint", C.c_void_p), ("constraint_state", C.c_int32)]
+
+
+class _SchedOptsForced(_SchedOpts):
+    """llamahip_sched_opts as it is now: forced_drafts appended behind _SchedOpts' fields"""
+    _fields_ = [("forced_drafts", C.c_int32)]
+
+
 class _SchedEvent(C.Structure):
     _fields_ = [("id", C.c_int64), ("kind", C.c_int32), ("token", C.c_int32), ("exact", C.c_int32), ("slot", C.c_int32),
                 ("position", C.c_int32), ("reason", C.c_int32)]
@@ -121,6 +131,11 @@ class _SchedStats(C.Structure):
 class _SchedStatsPrefix(_SchedStats):
     """llamahip_sched_stats as it is now: the counters of shared prompt prefixes appended behind _SchedStats' (the struct is size-versioned)"""
     _fields_ = [("n_shared_rows", C.c_int64), ("n_copied_rows", C.c_int64), ("n_copy_launches", C.c_int64)]
+
+
+class _SchedStatsDfa(_SchedStatsPrefix):
+    """... and the counters of constrained requests behind those"""
+    _fields_ = [("n_dfa_rows", C.c_int64), ("n_forced_drafted", C.c_int64), ("n_forced_accepted", C.c_int64)]
 
 
 class _Stats(C.Structure):
@@ -318,6 +333,10 @@ def lib() -> C.CDLL:
     L.llamahip_constraint_advance.restype = i32
     L.llamahip_constraint_pick.argtypes = [vp, i32, vp]
     L.llamahip_constraint_pick.restype = i32
+    L.llamahip_forced_run.argtypes = [vp, i32, vp, i32]
+    L.llamahip_forced_run.restype = i32
+    L.llamahip_op_verify_rows_allow.argtypes = [vp, i32, i32, vp, i32, vp, vp, vp, vp, cp, sz]
+    L.llamahip_op_sched_pick_allow.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, cp, sz]
     L.llamahip_constraint_mask_row.argtypes = [vp, i32, vp, vp]
     L.llamahip_decode_greedy_constrained.argtypes = [vp, i32, i32, i32, i32, vp, C.POINTER(i32), vp, C.POINTER(i32), C.POINTER(i32), vp, cp, sz]
     L.llamahip_decode_greedy_constrained_multi.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, cp, sz]
@@ -1095,12 +1114,13 @@ class Model:
 
     def scheduler(self, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8, repeat_penalty: float = 1.3,
                   top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)), draft_len: int = 0,
-                  ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False) -> "Scheduler":
+                  ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False, forced_drafts: bool = False) -> "Scheduler":
         """llamahip_sched_new: a request scheduler over KV slots [0, max_active) of this handle (include/llamahip.h "request scheduler").
         draft_len > 0: drafted tokens ride in the rows a step leaves spare (prompt lookup in each request's history, then `corpus`).
-        prefix_share: a request takes over the evaluated prompt rows it has in common with a slot's record instead of evaluating them."""
+        prefix_share: a request takes over the evaluated prompt rows it has in common with a slot's record instead of evaluating them.
+        forced_drafts: a constrained greedy request's forced tokens ride as its draft (works with draft_len 0)."""
         return Scheduler(self, max_active, chunk_tokens, row_budget, n_threads, repeat_penalty, top_k, top_p, temp, draft_len, ngram_min, ngram_max, corpus,
-                         prefix_share)
+                         prefix_share, forced_drafts)
 
     def kv_copy_rows(self, copies) -> None:
         """llamahip_kv_copy_rows: copies = [(src slot, dst slot, first row, row count), ...], 1 .. 16 of them -- those KV rows of every layer, K
@@ -1254,6 +1274,14 @@ class Constraint:
             raise ValueError(f"pick: {logits.size} logits for n_vocab {self.n_vocab}")
         return lib().llamahip_constraint_pick(self._c, int(state), _ptr(logits))
 
+    def forced(self, state: int, cap: int = 15) -> np.ndarray:
+        """llamahip_forced_run: the tokens forced from `state` on (each the single allowed token of its state), at most cap"""
+        out = np.empty(max(int(cap), 1), np.int32)
+        n = lib().llamahip_forced_run(self._c, int(state), _ptr(out) if cap > 0 else None, int(cap))
+        if n < 0:
+            raise LlamaHipError(ERR_PREDICT, f"llamahip_forced_run: state {state} out of range [0, {self.n_states}) or cap {cap} < 0")
+        return out[:n].copy()
+
     def mask_row(self, state: int, logits) -> np.ndarray:
         logits = np.ascontiguousarray(logits, np.float32)
         if logits.size != self.n_vocab:
@@ -1312,18 +1340,21 @@ class Scheduler:
 
     def __init__(self, model: Model, max_active: int, chunk_tokens: int = 0, row_budget: int = 0, n_threads: int = 8,
                  repeat_penalty: float = 1.3, top_k: int = 40, top_p: float = float(np.float32(0.95)), temp: float = float(np.float32(0.8)),
-                 draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False):
+                 draft_len: int = 0, ngram_min: int = 0, ngram_max: int = 0, corpus=None, prefix_share: bool = False, forced_drafts: bool = False):
         self._s = None
         self.model, self.max_active, self.draft_len = model, int(max_active), int(draft_len)
+        self.forced_drafts = bool(forced_drafts)
+        self._cap_len = max(self.draft_len, int(self.forced_drafts))          # (forced drafts need a drafting scheduler's event capacity)
         self._samplers = {}          # id -> Sampler: kept alive while the request may draw
+        self._constraints = {}       # id -> Constraint: kept alive while the request lives
         c = np.ascontiguousarray(corpus if corpus is not None else [], np.int32).ravel()          # (copied by llamahip_sched_new)
-        o = _SchedOpts(C.sizeof(_SchedOpts), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k,
-                       int(draft_len), int(ngram_min), int(ngram_max), c.ctypes.data if c.size else None, c.size, int(prefix_share))
+        o = _SchedOptsForced(C.sizeof(_SchedOptsForced), n_threads, max_active, chunk_tokens, row_budget, repeat_penalty, top_p, temp, top_k,
+                             int(draft_len), int(ngram_min), int(ngram_max), c.ctypes.data if c.size else None, c.size, int(prefix_share), int(forced_drafts))
         h = C.c_void_p()
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_sched_new(model._h, C.byref(o), C.byref(h), err, len(err)), err)
         self._s = h
-        self._ev = (_SchedEvent * (sched_event_cap(self.max_active, self.draft_len) + 63))()          # (room for waiting DONE events)
+        self._ev = (_SchedEvent * (sched_event_cap(self.max_active, self._cap_len) + 63))()          # (room for waiting DONE events)
 
     def close(self) -> None:
         if self._s:
@@ -1342,22 +1373,27 @@ class Scheduler:
         except Exception:
             pass
 
-    def submit(self, prompt, n_predict: int, stop_token: int = -1, sampler: "Sampler | None" = None) -> int:
-        """llamahip_sched_submit: returns the request's id (sampler None = greedy)."""
+    def submit(self, prompt, n_predict: int, stop_token: int = -1, sampler: "Sampler | None" = None, constraint: "Constraint | None" = None,
+               constraint_state: int = -1) -> int:
+        """llamahip_sched_submit: returns the request's id (sampler None = greedy; constraint: every pick under it, from constraint_state,
+        -1 = its start; the scheduler keeps the Constraint alive while the request lives)."""
         p = np.ascontiguousarray(prompt, np.int32).ravel()
-        r = _Request(C.sizeof(_Request), p.ctypes.data if p.size else None, p.size, int(n_predict), int(stop_token), None if sampler is None else sampler._s.value)
+        r = _RequestCst(C.sizeof(_RequestCst), p.ctypes.data if p.size else None, p.size, int(n_predict), int(stop_token), None if sampler is None else sampler._s.value,
+                        None if constraint is None else constraint._c.value, int(constraint_state))
         rid = C.c_int64(0)
         err = C.create_string_buffer(1024)
         _check(lib().llamahip_sched_submit(self._s, C.byref(r), C.byref(rid), err, len(err)), err)
         if sampler is not None:
             self._samplers[rid.value] = sampler
+        if constraint is not None:
+            self._constraints[rid.value] = constraint
         return int(rid.value)
 
     def step(self, cap: int | None = None) -> list[dict]:
         """llamahip_sched_step: one weight pass; the step's events as dicts {id, kind ("token" / "done"), token, exact, slot, position, reason}."""
         n = C.c_int32(0)
         err = C.create_string_buffer(1024)
-        assert len(self._ev) >= sched_event_cap(self.max_active, self.draft_len)
+        assert len(self._ev) >= sched_event_cap(self.max_active, self._cap_len)
         _check(lib().llamahip_sched_step(self._s, C.cast(self._ev, C.c_void_p), len(self._ev) if cap is None else int(cap), C.byref(n), err, len(err)), err)
         out = []
         for e in self._ev[:n.value]:
@@ -1366,6 +1402,7 @@ class Scheduler:
                         "position": int(e.position), "reason": DONE_REASONS.get(e.reason) if done else None})
             if done:
                 self._samplers.pop(int(e.id), None)
+                self._constraints.pop(int(e.id), None)
         return out
 
     def cancel(self, rid: int) -> bool:
@@ -1375,9 +1412,9 @@ class Scheduler:
         return int(lib().llamahip_sched_pending(self._s))
 
     def stats(self) -> dict:
-        st = _SchedStatsPrefix(C.sizeof(_SchedStatsPrefix))
+        st = _SchedStatsDfa(C.sizeof(_SchedStatsDfa))
         lib().llamahip_sched_get_stats(self._s, C.byref(st))
-        return {k: int(getattr(st, k)) for k, _ in _SchedStats._fields_ + _SchedStatsPrefix._fields_ if k != "struct_size"}
+        return {k: int(getattr(st, k)) for k, _ in _SchedStats._fields_ + _SchedStatsPrefix._fields_ + _SchedStatsDfa._fields_ if k != "struct_size"}
 
     def run(self, on_done=None) -> dict:
         """step until nothing is pending; returns {id: tokens}.  on_done(event), if given, is called at each DONE event -- while the
@@ -1697,6 +1734,56 @@ def _dfa_operands(logits2d, table, states):
     if states.size != R:
         raise ValueError(f"states: {states.size} for {R} rows")
     return logits2d, R, V, table, states
+
+
+def _dfa_rows_args(logits2d, table, states, fallback):
+    logits2d = np.ascontiguousarray(logits2d, np.float32)
+    table = np.ascontiguousarray(table, np.uint16)
+    R, V = logits2d.shape
+    if table.ndim != 2 or table.shape[1] != V:
+        raise ValueError(f"table is uint16 [n_states, n_vocab = {V}]")
+    states = np.ascontiguousarray(states, np.int32).ravel()
+    fallback = np.ascontiguousarray(np.broadcast_to(np.asarray(fallback, np.int32), (R,)), np.int32)
+    if states.size != R:
+        raise ValueError(f"{states.size} states for {R} rows")
+    return logits2d, table, states, fallback, R, V
+
+
+def op_verify_rows_dfa(logits2d, table, states, fallback, picks=None, dead=None):
+    """k_verify_rows_dfa on host rows (llamahip_op_verify_rows_allow): states[r] = the table row of logits row r, -1 = unconstrained;
+    returns (picks, dead).  picks / dead, if given, go up first: what the kernel leaves alone keeps their values."""
+    logits2d, table, states, fallback, R, V = _dfa_rows_args(logits2d, table, states, fallback)
+    picks = np.full(R, -7, np.int32) if picks is None else np.ascontiguousarray(picks, np.int32).copy()
+    dead = np.full(R, -7, np.int32) if dead is None else np.ascontiguousarray(dead, np.int32).copy()
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_verify_rows_allow(_ptr(logits2d), R, V, _ptr(table), table.shape[0], _ptr(states), _ptr(fallback), _ptr(picks), _ptr(dead), err, len(err)), err)
+    return picks, dead
+
+
+def op_sched_pick_dfa(logits2d, emit, table, states, fallback, seg_words=None, state=None, log=None, next_tok=None):
+    """k_sched_pick_dfa on host rows, one segment per row (llamahip_op_sched_pick_allow): returns (picks, dead), picks[r] = -1 where emit[r] == 0.
+    With slot words -- seg_words [R, 3] = {slot, position, cursor}, state [n_slots, 2], log [n_slots, log_cap], next_tok [n_slots] -- the
+    three arrays are updated in place as the kernel leaves them."""
+    logits2d, table, states, fallback, R, V = _dfa_rows_args(logits2d, table, states, fallback)
+    emit = np.ascontiguousarray(emit, np.int32).ravel()
+    if emit.size != R:
+        raise ValueError(f"{emit.size} emit flags for {R} rows")
+    picks, dead = np.full(R, -7, np.int32), np.full(R, -7, np.int32)
+    n_slots = log_cap = 0
+    if seg_words is not None:
+        seg_words = np.ascontiguousarray(seg_words, np.int32)
+        for a in (state, log, next_tok):
+            if not (isinstance(a, np.ndarray) and a.dtype == np.int32 and a.flags.c_contiguous):
+                raise ValueError("state, log and next_tok are contiguous int32 arrays (updated in place)")
+        n_slots, log_cap = log.shape
+        if seg_words.shape != (R, 3) or state.shape != (n_slots, 2) or next_tok.shape != (n_slots,):
+            raise ValueError("seg_words [R, 3], state [n_slots, 2], log [n_slots, log_cap], next_tok [n_slots]")
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_sched_pick_allow(_ptr(logits2d), R, V, _ptr(emit), _ptr(table), table.shape[0], _ptr(states), _ptr(fallback),
+                                            None if seg_words is None else _ptr(seg_words), n_slots, log_cap,
+                                            None if seg_words is None else _ptr(state), None if seg_words is None else _ptr(log),
+                                            None if seg_words is None else _ptr(next_tok), _ptr(picks), _ptr(dead), err, len(err)), err)
+    return picks, dead
 
 
 def op_pick_dfa(logits2d, table, states, fallback_token: int, picks=None, dead=None):

@@ -96,7 +96,14 @@ int llamahip_constraint_new(const llamahip_model *m, int32_t n_states, const int
         for (int32_t s : preds[q]) if (!live[s]) { live[s] = 1; work.push_back(s); }
     }
     if (!live[start]) { delete c; REFUSE("%s: start state %d is not live: no sequence of tokens leads from it to an accepting state", fn, start); }
-    for (size_t i = 0; i < (size_t) S * V; i++) if (next[i] != DFA_BANNED && !live[next[i]]) next[i] = DFA_BANNED;
+    // ... and, in the same walk, every state's single allowed token (-1: none allowed, -2: more than one) for llamahip_forced_run
+    try { c->single.assign((size_t) S + 1, -1); } catch (const std::bad_alloc &) { delete c; REFUSE("%s: out of memory", fn); }
+    for (int32_t s = 0; s < S; s++)
+        for (int32_t t = 0; t < V; t++) {
+            uint16_t &q = next[(size_t) s * V + t];
+            if (q != DFA_BANNED && !live[q]) q = DFA_BANNED;
+            if (q != DFA_BANNED) c->single[(size_t) s] = c->single[(size_t) s] == -1 ? t : -2;
+        }
     *out = c;
     return LLAMAHIP_OK;
 }
@@ -163,6 +170,18 @@ int32_t llamahip_constraint_advance(const llamahip_constraint *c, int32_t state,
     if (!c || state < 0 || state >= c->n_states || token < 0 || token >= c->n_vocab) return -1;
     const uint16_t q = c->next[(size_t) state * c->n_vocab + token];
     return q == DFA_BANNED ? -1 : (int32_t) q;
+}
+
+int32_t llamahip_forced_run(const llamahip_constraint *c, int32_t state, int32_t *out, int32_t cap) {
+    if (!c || state < 0 || state >= c->n_states || cap < 0 || (cap > 0 && !out)) return -1;
+    const int32_t done = c->n_states - 1;
+    int32_t n = 0;
+    while (n < cap && state != done && c->single[(size_t) state] >= 0) {
+        const int32_t t = c->single[(size_t) state];
+        out[n++] = t;
+        state = (int32_t) c->next[(size_t) state * c->n_vocab + t];
+    }
+    return n;
 }
 
 int32_t llamahip_constraint_pick(const llamahip_constraint *c, int32_t state, const float *logits) {

@@ -16,6 +16,7 @@ struct llamahip_constraint {
     int32_t n_vocab = 0;
     int32_t start = 0, stop_token = 0;
     std::vector<uint16_t> next;             // [n_states][n_vocab], LLAMAHIP_CONSTRAINT_BANNED = not allowed
+    std::vector<int32_t> single;            // [n_states]: the state's single allowed token; -1 none allowed (DONE's entry: it yields nothing), -2 several
     // the device copy (null until a device call needs it) and how to release it
     uint16_t *dev = nullptr;
     void (*dev_release)(llamahip_constraint *) = nullptr;

@@ -3,7 +3,8 @@
 //
 // k_pick_dfa: one workgroup of 1024 threads per row, 1 .. 16 rows, each with its own logits row, state word and table.  The pick is
 //   k_argmax's rule (decode.hip argmax_take) over the ALLOWED entries of next[state]: the largest value, the LOWEST index on ties
-//   (+0.0 == -0.0), a NaN never taken; where every allowed entry is a NaN, the lowest allowed index.  The scan is k_argmax's -- 32 loads
+//   (+0.0 == -0.0), a NaN never taken; where every allowed entry is a NaN, the lowest allowed index.  The scan and the fold are the device
+//   function dfa_row_pick (dfa_pick.hip.h: the one statement of them, shared with the scheduler's kernels in verify.hip) -- k_argmax's, 32 loads
 //   in flight per thread, the DPP / readlane fold, one barrier -- with the table row read beside the logits at the same indices (plain
 //   16-bit loads: rows are 2 * n_vocab bytes apart, so with an odd n_vocab a row is not 4-byte aligned, and nothing here is packed).
 //   "Largest value, then lowest index" is a total order on the non-NaN entries, so the fold's shape does not matter.
@@ -18,72 +19,22 @@
 // Plain loads and stores, no hand-offs between workgroups.
 #include <cmath>
 
+#include "dfa_pick.hip.h"
 #include "kcommon.hip.h"
 
 namespace lh {
-
-__device__ __forceinline__ void dfa_take(float &v, int &i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-template <int CTRL>
-__device__ __forceinline__ void dfa_take_dpp(float &v, int &i, int &lo) {
-    const float ov = dpp_f<CTRL>(v);
-    const int oi = __builtin_amdgcn_mov_dpp(i, CTRL, 0xF, 0xF, true);
-    dfa_take(v, i, ov, oi);
-    lo = min(lo, __builtin_amdgcn_mov_dpp(lo, CTRL, 0xF, 0xF, true));
-}
-
-constexpr int DFA_NONE = 0x7fffffff;
 
 __global__ void __launch_bounds__(1024)
 k_pick_dfa(const DfaRows rows, int V) {
     __shared__ float bv[16];
     __shared__ int bi[16], bl[16];
     const DfaRow &R = rows.r[blockIdx.x];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    const float *__restrict__ logits = R.logits;
     const int state = R.cst[0];                                   // (every thread reads it in front of the barrier; thread 0 writes behind it)
     const bool in_range = state >= 0 && state < R.n_states;       // uniform over the workgroup
-    float best = -INFINITY;
-    int idx = DFA_NONE, lo = DFA_NONE;                            // lo: the thread's lowest allowed index (its indices ascend)
-    if (in_range) {
-        const uint16_t *__restrict__ tab = R.table + (size_t) state * (size_t) V;
-        for (int i0 = tid; i0 < V; i0 += 32 * nt) {
-            float v[32];
-            uint16_t t[32];
-#pragma unroll
-            for (int u = 0; u < 32; u++) { const int i = min(i0 + u * nt, V - 1); v[u] = logits[i]; t[u] = tab[i]; }
-#pragma unroll
-            for (int u = 0; u < 32; u++) {
-                const int i = i0 + u * nt;
-                if (i < V && t[u] != DFA_BANNED_U16) {
-                    dfa_take(best, idx, v[u], i);                 // ascending i: a tie keeps the lower index
-                    lo = min(lo, i);
-                }
-            }
-        }
-    }
-    dfa_take_dpp<DPP_QUAD_XOR1>(best, idx, lo);
-    dfa_take_dpp<DPP_QUAD_XOR2>(best, idx, lo);
-    dfa_take_dpp<DPP_ROW_HALF_MIRROR>(best, idx, lo);
-    dfa_take_dpp<DPP_ROW_MIRROR>(best, idx, lo);                  // every lane of a 16-lane row holds the row's pick
-    {
-        const int vb = __builtin_bit_cast(int, best);
-        float wv = __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 0));
-        int wi = __builtin_amdgcn_readlane(idx, 0), wl = __builtin_amdgcn_readlane(lo, 0);
-        dfa_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 16)), __builtin_amdgcn_readlane(idx, 16));
-        dfa_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 32)), __builtin_amdgcn_readlane(idx, 32));
-        dfa_take(wv, wi, __builtin_bit_cast(float, __builtin_amdgcn_readlane(vb, 48)), __builtin_amdgcn_readlane(idx, 48));
-        wl = min(min(wl, __builtin_amdgcn_readlane(lo, 16)), min(__builtin_amdgcn_readlane(lo, 32), __builtin_amdgcn_readlane(lo, 48)));
-        if ((tid & 63) == 0) { bv[tid >> 6] = wv; bi[tid >> 6] = wi; bl[tid >> 6] = wl; }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        float v = bv[0];
-        int i = bi[0], l = bl[0];
-        for (int w = 1; w < (nt >> 6); w++) { dfa_take(v, i, bv[w], bi[w]); l = min(l, bl[w]); }
-        const int p = i != DFA_NONE ? i : l;                      // (nothing taken: every allowed entry a NaN -> the lowest allowed index)
-        const bool dead = !in_range || p == DFA_NONE || p < 0 || p >= V;
+    // the scan and the fold: dfa_pick.hip.h, not restated
+    const int p = dfa_row_pick(R.logits, in_range ? R.table + (size_t) state * (size_t) V : nullptr, V, bv, bi, bl);
+    if (threadIdx.x == 0) {
+        const bool dead = !in_range || p == DFA_NONE;
         const int r = dead ? R.fallback : p;
         int32_t *st = R.st;
         // repick (behind a set step, whose own tail has picked and advanced): the entry that tail wrote, and no advance

@@ -4620,8 +4620,9 @@ extern "C++" {
 namespace lh {
 // the last stage's d_sched_tab: k_sched_pick's table and result as before, behind them a drafted step's k_sched_accept table | the logits
 // rows' tokens | k_verify_rows' picks | the result {n_accept[16], pick[16]}
-constexpr int SCHED_ACC_TAB = 5 * SET_MAX, SCHED_ACC_TOK = SCHED_ACC_TAB + SCHED_TAB_W * SET_MAX, SCHED_ACC_PICK = SCHED_ACC_TOK + VERIFY_ROWS_MAX,
-              SCHED_ACC_RES = SCHED_ACC_PICK + VERIFY_ROWS_MAX, SCHED_TAB_WORDS = SCHED_ACC_RES + SET_MAX + VERIFY_ROWS_MAX;
+// (k_sched_pick_dfa's result is {pick[16], dead[16]}: the table's 64 words, then 32; a constrained drafted step's dead words lie at the end)
+constexpr int SCHED_ACC_TAB = 6 * SET_MAX, SCHED_ACC_TOK = SCHED_ACC_TAB + SCHED_TAB_W * SET_MAX, SCHED_ACC_PICK = SCHED_ACC_TOK + VERIFY_ROWS_MAX,
+              SCHED_ACC_RES = SCHED_ACC_PICK + VERIFY_ROWS_MAX, SCHED_ACC_DEAD = SCHED_ACC_RES + SET_MAX + VERIFY_ROWS_MAX, SCHED_TAB_WORDS = SCHED_ACC_DEAD + VERIFY_ROWS_MAX;
 struct SchedDev {
     llamahip_model *m = nullptr;
     int n_threads = 1, max_active = 1, chunk = 0;
@@ -4637,7 +4638,7 @@ int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, 
     const int rc = decode_handle_check(m, "llamahip_sched_new", err, err_cap);
     if (rc) return rc;
     const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
-    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq, (first->flags & LLAMAHIP_FLAG_FAST_PREFILL) ? 1 : 0 };
+    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq, (first->flags & LLAMAHIP_FLAG_FAST_PREFILL) ? 1 : 0, m->stages.empty() ? 0 : 1 };
     return 0;
 }
 int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
@@ -4745,6 +4746,16 @@ static int sched_fallback_step(SchedDev *d, SchedSeg *segs, int n_segs, const Sa
         SchedSeg &g = segs[j];
         const int rc = each_slot(m, 1, &g.slot, err, err_cap, [&](int) {
             int r = 0;
+            if (g.cst && g.emit) {
+                // a constrained segment: the contract's own loop -- the eval (a decode row: the one-token llamahip_eval), the host pick
+                r = g.n_out == 0 && d->chunk > 0 ? llamahip_eval_chunks(m, d->n_threads, g.pos, g.tokens, g.n_rows, d->chunk, d->logits.data(), err, err_cap)
+                                                 : llamahip_eval(m, d->n_threads, g.pos, g.tokens, g.n_rows, d->logits.data(), err, err_cap);
+                if (r) return r;
+                g.exact = 1;
+                g.token = llamahip_constraint_pick(g.cst, g.cst_state, d->logits.data());
+                if (g.token < 0) { set_err(err, err_cap, "llamahip_sched_step: state %d of slot %d's constraint allows no token (the state does not come from this constraint)", g.cst_state, g.slot); return LLAMAHIP_ERR_PREDICT; }
+                return 0;
+            }
             if (g.n_rows == 1 && g.emit && g.pos > 0 && g.n_out > 0) {          // a decode row: the contract's single-token step
                 if (!g.sampler) { g.exact = 1; return llamahip_decode_greedy(m, d->n_threads, g.pos, g.tokens[0], 1, &g.token, nullptr, err, err_cap); }
                 return sample_single_step(m, d->n_threads, g.pos, g.tokens[0], g.sampler, sp, d->win, d->logits, &g.token, &g.exact, err, err_cap);
@@ -4772,7 +4783,7 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
     const int C = m->hp.n_ctx, V = m->hp.n_vocab;
     int64_t R = 0;
     int n_logit_rows = 0;
-    bool drafted = false;
+    bool drafted = false, constrained = false;
     for (int j = 0; j < n_segs; j++) {
         const SchedSeg &g = segs[j];
         if (g.slot < 0 || g.slot >= d->max_active || g.n_rows < 1 || g.pos < 0 || g.pos + g.n_rows > C || !g.tokens || (!mixed && (g.n_rows != 1 || !g.emit))) {
@@ -4786,8 +4797,13 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
         for (int i = 0; i < g.n_draft; i++)
             if (g.draft[i] < 0 || g.draft[i] >= V) { set_err(err, err_cap, "%s: draft token id %d out of range [0, %d)", fn, g.draft[i], V); return LLAMAHIP_ERR_PREDICT; }
         for (int i = 0; i < j; i++) if (segs[i].slot == g.slot) { set_err(err, err_cap, "%s: slot %d has two segments in one step", fn, g.slot); return LLAMAHIP_ERR_PREDICT; }
+        if (g.cst && (!g.emit || g.sampler || g.cst->m != m || !m->stages.empty() || g.cst_state < 0 || g.cst_state >= g.cst->n_states)) {
+            set_err(err, err_cap, "%s: segment %d (slot %d) carries a constraint it cannot take (state %d; a greedy emitting segment of the constraint's own whole-model handle)", fn, j, g.slot, g.cst_state);
+            return LLAMAHIP_ERR_PREDICT;
+        }
         R += g.n_rows + g.n_draft;
         drafted = drafted || g.n_draft > 0;
+        constrained = constrained || g.cst != nullptr;
         n_logit_rows += g.emit ? 1 + g.n_draft : 0;
     }
     if (drafted && n_logit_rows > VERIFY_ROWS_MAX) { set_err(err, err_cap, "%s: %d logits rows in a step with drafted tokens (at most %d)", fn, n_logit_rows, VERIFY_ROWS_MAX); return LLAMAHIP_ERR_PREDICT; }
@@ -4814,6 +4830,15 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
         if (first != last && (rc = sample_prepare(first, false, err, err_cap)) != 0) return rc;
     }
     const llamahip_model::SampleIo &hl = last->smp_h;
+    // a step with constrained segments: the tables on the device; the allow-list and the fallback token (the constraint's stop token) of every
+    // logits row, filled where the rows are laid out.  A step without one launches exactly what it launched before
+    DfaMaskRows allow = {};
+    DfaFallback fb = {};
+    int dead_at[SET_MAX], pick_at[SET_MAX];
+    if (constrained) {
+        HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+        for (int j = 0; j < n_segs; j++) if (segs[j].cst && (rc = cst_ensure_dev(m, segs[j].cst, err, err_cap)) != 0) return rc;
+    }
     int order[SET_MAX], n_ord = 0;          // the step's rows: segment order[a] is row a of the logits
     if (mixed) {
         *kind = SCHED_STEP_MIXED;
@@ -4836,6 +4861,7 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
             tokens.insert(tokens.end(), g.draft, g.draft + g.n_draft);
             tab[4 * a] = g.emit && !g.sampler; tab[4 * a + 1] = g.slot; tab[4 * a + 2] = g.pos + g.n_rows; tab[4 * a + 3] = g.n_out + (g.emit ? 1 : 0);
             if (!drafted) {
+                if (g.cst) { allow.row[a] = g.cst->dev + (size_t) g.cst_state * V; fb.t[a] = g.cst->stop_token; }
                 if (a < ns) hl.n_last[a] = llamahip_sampler_window(g.sampler, hl.win + (size_t) a * 1024, 1024);          // (the streams are idle: every step is waited for)
                 continue;
             }
@@ -4846,7 +4872,16 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
             int32_t *t = acc + SCHED_TAB_W * a;
             t[0] = !g.emit || g.sampler ? 0 : g.n_draft > 0 ? 2 : 1; t[1] = g.slot; t[2] = g.pos; t[3] = g.n_out + (g.emit && g.sampler ? 1 : 0);
             t[4] = nl; t[5] = n_tokens[a];
-            for (int r = g.n_draft > 0 ? r0 : r0 + g.n_rows - 1; g.emit && r < r0 + n_tokens[a]; r++) { ltok[nl++] = tokens[(size_t) r]; rp.logit_rows.push_back(r); }
+            // (a constrained segment's logits row i is picked under the state behind the draft tokens in front of it)
+            int32_t cs = g.cst ? g.cst_state : -1;
+            for (int r = g.n_draft > 0 ? r0 : r0 + g.n_rows - 1, i = 0; g.emit && r < r0 + n_tokens[a]; r++, i++) {
+                if (g.cst) {
+                    if (cs < 0) { set_err(err, err_cap, "%s: draft token %d of slot %d is banned in its constraint's state", fn, g.draft[i - 1], g.slot); return LLAMAHIP_ERR_PREDICT; }
+                    allow.row[nl] = g.cst->dev + (size_t) cs * V; fb.t[nl] = g.cst->stop_token;
+                    if (i < g.n_draft) cs = llamahip_constraint_advance(g.cst, cs, g.draft[i]);
+                }
+                ltok[nl++] = tokens[(size_t) r]; rp.logit_rows.push_back(r);
+            }
             if (a < ns) ns_rows = nl;
         }
         rp.n_seqs = n_segs; rp.chunk = d->chunk; rp.slots = slots; rp.n_past = n_past; rp.n_tokens = n_tokens; rp.R = (int) R;
@@ -4873,20 +4908,29 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
         rc = rows_pass_enqueue(stages, d->n_threads, rp, tokens.data(), err, err_cap);
         if (rc == 0 && hipSetDevice(last->device) != hipSuccess) { set_err(err, err_cap, "%s: hipSetDevice failed", fn); rc = LLAMAHIP_ERR_PREDICT; }
         if (rc == 0 && ns > 0) rc = drafted ? slide_set_enqueue(last, ss, ns_rows, err, err_cap) : sample_select(last, sp, 0, ns, err, err_cap);
-        if (rc == 0 && !drafted && launch_sched_pick(last->logits, n_segs, V, last->d_sched_tab, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess) {
+        int32_t *d_dead = last->h_io ? last->d_io->vset.pick : last->d_sched_tab + SCHED_ACC_DEAD;          // (a constrained drafted step's dead words)
+        if (rc == 0 && !drafted && (constrained ? launch_sched_pick_dfa(last->logits, n_segs, V, last->d_sched_tab, allow, fb, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream)
+                                                : launch_sched_pick(last->logits, n_segs, V, last->d_sched_tab, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream)) != hipSuccess) {
             set_err(err, err_cap, "%s: HIP error launching k_sched_pick", fn); rc = LLAMAHIP_ERR_PREDICT;
         }
-        if (rc == 0 && drafted && (launch_verify_rows(last->logits, nl, V, last->d_sched_tab + SCHED_ACC_PICK, last->stream) != hipSuccess ||
+        if (rc == 0 && drafted && ((constrained ? launch_verify_rows_dfa(last->logits, nl, V, allow, fb, last->d_sched_tab + SCHED_ACC_PICK, d_dead, last->stream)
+                                                : launch_verify_rows(last->logits, nl, V, last->d_sched_tab + SCHED_ACC_PICK, last->stream)) != hipSuccess ||
                                    launch_sched_accept(last->d_sched_tab + SCHED_ACC_PICK, last->d_sched_tab + SCHED_ACC_TOK, last->d_sched_tab + SCHED_ACC_TAB, n_segs, nl,
                                                        last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res, last->stream) != hipSuccess)) {
             set_err(err, err_cap, "%s: HIP error launching k_verify_rows / k_sched_accept", fn); rc = LLAMAHIP_ERR_PREDICT;
         }
         if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
-        int32_t res[SET_MAX + VERIFY_ROWS_MAX];
-        const size_t n_res = (size_t) n_segs + (drafted ? (size_t) nl : 0);
+        int32_t res[SET_MAX + VERIFY_ROWS_MAX], dead[VERIFY_ROWS_MAX] = { 0 };
+        const size_t n_res = (size_t) n_segs + (drafted ? (size_t) nl : constrained ? (size_t) n_segs : 0);
         if (last->h_io) memcpy(res, last->h_io->vset.res, n_res * 4);
         else HIP_TRY(hipMemcpy(res, d_res, n_res * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        if (constrained && drafted) {
+            if (last->h_io) memcpy(dead, last->h_io->vset.pick, (size_t) nl * 4);
+            else HIP_TRY(hipMemcpy(dead, d_dead, (size_t) nl * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        } else if (constrained) memcpy(dead, res + n_segs, (size_t) n_segs * 4);
+        for (int r = 0; constrained && r < (drafted ? nl : n_segs); r++)
+            if (dead[r] != 0) { set_err(err, err_cap, "%s: a pick found no allowed token (logits row %d): the state does not come from the request's constraint", fn, r); return LLAMAHIP_ERR_PREDICT; }
         if (drafted && ns > 0 && ss.k > 0 && (rc = slide_fetch(last, cand, ns_rows, err, err_cap)) != 0) return rc;
         for (int a = 0; a < n_segs; a++) {
             SchedSeg &g = segs[order[a]];
@@ -4933,12 +4977,50 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
             HIP_TRY(hipMemcpy(first->mq_tok, d->tok, (size_t) d->max_active * 4, hipMemcpyHostToDevice), LLAMAHIP_ERR_PREDICT);
         }
         *kind = n_segs >= 2 ? SCHED_STEP_SET : SCHED_STEP_SINGLE;
-        const std::function<int(int, int)> select = [&](int j, int rows) { return sample_select(last, sp, j, rows, err, err_cap); };
-        rc = step_group(stages, { act, n_segs, 0, d->max_active, 0 }, d->n_threads, false, true, any_sampled ? select : nullptr, err, err_cap);
+        // constrained slots: the step exactly as it is, then ONE k_sched_pick_dfa launch over the step's logits rows (one per row where the
+        // slots are stepped one by one) with the advanced {position, cursor} in its table -- it overwrites the trace entry and the next-token
+        // word the step's own tail wrote, as llamahip_decode_greedy_constrained_multi does with k_pick_dfa's repick.  The stage step's tail
+        // (k_argmax / k_argmax_set) only stores its pick: nothing has read the token word before the next step's embedding gather, which
+        // runs behind this launch on the same stream.  Unconstrained rows emit nothing here: what the tail wrote stands
+        int32_t *d_res = last->h_io ? last->d_io->vset.res : last->d_sched_tab + 4 * SET_MAX;
+        if (constrained) {
+            int32_t tab[4 * SET_MAX];
+            for (int a = 0; a < n_segs; a++) {
+                const SchedSeg &g = segs[order[a]];
+                tab[4 * a] = g.cst ? 1 : 0; tab[4 * a + 1] = g.slot; tab[4 * a + 2] = g.pos + 1; tab[4 * a + 3] = g.n_out + 1;
+                if (g.cst) { allow.row[a] = g.cst->dev + (size_t) g.cst_state * V; fb.t[a] = g.cst->stop_token; }
+            }
+            HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(hipMemcpyAsync(last->d_sched_tab, tab, (size_t) n_segs * 16, hipMemcpyHostToDevice, last->stream), LLAMAHIP_ERR_PREDICT);      // (pageable: gone when the call returns)
+        }
+        const std::function<int(int, int)> hook = [&](int j, int rows) -> int {
+            if (any_sampled) { const int r = sample_select(last, sp, j, rows, err, err_cap); if (r) return r; }
+            if (!constrained) return 0;
+            DfaMaskRows al = {};
+            DfaFallback f = {};
+            for (int r = 0; r < rows; r++) { al.row[r] = allow.row[j + r]; f.t[r] = fb.t[j + r]; pick_at[j + r] = 2 * j + r; dead_at[j + r] = 2 * j + rows + r; }
+            if (launch_sched_pick_dfa(last->logits, rows, V, last->d_sched_tab + 4 * j, al, f, last->d_slot_state, last->d_slot_trace, C, last->mq_tok, d_res + 2 * j, last->stream) != hipSuccess) {
+                set_err(err, err_cap, "%s: HIP error launching k_sched_pick_dfa", fn); return LLAMAHIP_ERR_PREDICT;
+            }
+            return 0;
+        };
+        rc = step_group(stages, { act, n_segs, 0, d->max_active, 0 }, d->n_threads, false, true, any_sampled || constrained ? hook : nullptr, err, err_cap);
         if ((rc = drain_stages(stages, rc, err, err_cap)) != 0) return rc;
         HIP_TRY(hipSetDevice(last->device), LLAMAHIP_ERR_PREDICT);
         int32_t words[SET_MAX];
         HIP_TRY(hipMemcpy(words, last->mq_tok, (size_t) d->max_active * 4, hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+        if (constrained) {
+            int32_t res[2 * SET_MAX];
+            if (last->h_io) memcpy(res, last->h_io->vset.res, sizeof(res));
+            else HIP_TRY(hipMemcpy(res, d_res, sizeof(res), hipMemcpyDeviceToHost), LLAMAHIP_ERR_PREDICT);
+            for (int a = 0; a < n_segs; a++) {
+                const SchedSeg &g = segs[order[a]];
+                if (g.cst && (res[dead_at[a]] != 0 || res[pick_at[a]] != words[g.slot])) {
+                    set_err(err, err_cap, "%s: a pick found no allowed token (slot %d, state %d): the state does not come from the request's constraint", fn, g.slot, g.cst_state);
+                    return LLAMAHIP_ERR_PREDICT;
+                }
+            }
+        }
         for (int a = 0; a < n_segs; a++) {
             SchedSeg &g = segs[order[a]];
             if (!g.sampler) { g.token = words[g.slot]; g.exact = 1; }

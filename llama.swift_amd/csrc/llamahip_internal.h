@@ -405,5 +405,12 @@ struct DfaRows { DfaRow r[DFA_ROWS_MAX]; };
 struct DfaMaskRows { const uint16_t *row[DFA_ROWS_MAX]; };
 hipError_t launch_pick_dfa(const DfaRows &rows, int n_rows, int V, hipStream_t st);
 hipError_t launch_mask_rows_dfa(const float *logits, float *out, int n_rows, int V, const DfaMaskRows &rows, hipStream_t st);
+// a scheduler step with constrained greedy segments (verify.hip): launch_verify_rows / launch_sched_pick with a per-row allow-list --
+// rows.row[r] = the table row next[state] of logits row r (the host resolves the state), null = unconstrained (vr_row_pick); fb.t[r] = the
+// range-checked token a row that allows nothing picks, its dead word then 1.  launch_sched_pick_dfa's res = {pick[n_segs], dead[n_segs]}.
+struct DfaFallback { int32_t t[DFA_ROWS_MAX]; };
+hipError_t launch_verify_rows_dfa(const float *logits, int n_rows, int V, const DfaMaskRows &rows, const DfaFallback &fb, int32_t *pick, int32_t *dead, hipStream_t st);
+hipError_t launch_sched_pick_dfa(const float *logits, int n_segs, int V, const int32_t *tab, const DfaMaskRows &rows, const DfaFallback &fb, int32_t *state,
+                                 int32_t *log, int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st);
 
 }  // namespace lh

@@ -1135,6 +1135,84 @@ int llamahip_op_sched_pick(const float *logits, int32_t n_rows, int32_t n_vocab,
     return LLAMAHIP_OK;
 }
 
+// what the two per-row allow-list ops refuse behind dfa_op_check: a state outside [-1, n_table_states), a fallback token out of range
+static int dfa_rows_check(const char *fn, int32_t n_rows, int32_t n_vocab, int32_t n_table_states, const int32_t *states, const int32_t *fallback, const int32_t *picks,
+                          const int32_t *dead, char *err, size_t err_cap) {
+    if (!fallback || !picks || !dead) { set_err(err, err_cap, "%s: %s is NULL", fn, !fallback ? "fallback" : !picks ? "picks" : "dead"); return LLAMAHIP_ERR_PREDICT; }
+    for (int32_t r = 0; r < n_rows; r++) {
+        if (states[r] < -1 || states[r] >= n_table_states) { set_err(err, err_cap, "%s: states[%d] = %d out of range [-1, %d) (-1 = unconstrained)", fn, r, states[r], n_table_states); return LLAMAHIP_ERR_PREDICT; }
+        if (fallback[r] < 0 || fallback[r] >= n_vocab) { set_err(err, err_cap, "%s: fallback[%d] = %d out of range [0, %d)", fn, r, fallback[r], n_vocab); return LLAMAHIP_ERR_PREDICT; }
+    }
+    return 0;
+}
+
+// k_verify_rows_dfa on caller-supplied rows (parity tests): see the request scheduler's "constrained requests" in llamahip.h
+int llamahip_op_verify_rows_allow(const float *logits, int32_t n_rows, int32_t n_vocab, const uint16_t *table, int32_t n_table_states, const int32_t *states,
+                                const int32_t *fallback, int32_t *picks, int32_t *dead, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_verify_rows_allow";
+    if (dfa_op_check(fn, logits, n_rows, n_vocab, table, n_table_states, states, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (dfa_rows_check(fn, n_rows, n_vocab, n_table_states, states, fallback, picks, dead, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, V = (size_t) n_vocab;
+    int32_t h[2 * DFA_ROWS_MAX];      // picks | dead: the caller's words go up and come back, so what the kernel leaves alone shows
+    for (size_t r = 0; r < N; r++) { h[r] = picks[r]; h[DFA_ROWS_MAX + r] = dead[r]; }
+    Scratch s;
+    float *d_l = s.alloc(N * V, logits);
+    uint16_t *d_t = s.alloc((size_t) n_table_states * V, table);
+    int32_t *d_w = s.alloc(2 * (size_t) DFA_ROWS_MAX, h);
+    DfaMaskRows rows = {};
+    DfaFallback fb = {};
+    for (size_t r = 0; r < N; r++) { rows.row[r] = states[r] < 0 ? nullptr : d_t + (size_t) states[r] * V; fb.t[r] = fallback[r]; }
+    if (s.ok()) s.check(launch_verify_rows_dfa(d_l, n_rows, n_vocab, rows, fb, d_w, d_w + DFA_ROWS_MAX, nullptr));
+    s.download(h, d_w, sizeof(h));
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    for (size_t r = 0; r < N; r++) { picks[r] = h[r]; dead[r] = h[DFA_ROWS_MAX + r]; }
+    return LLAMAHIP_OK;
+}
+
+// k_sched_pick_dfa on caller-supplied rows, one segment per row, with or without slot words (parity tests)
+int llamahip_op_sched_pick_allow(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *emit, const uint16_t *table, int32_t n_table_states,
+                               const int32_t *states, const int32_t *fallback, const int32_t *seg_words, int32_t n_slots, int32_t log_cap, int32_t *state,
+                               int32_t *log, int32_t *next_tok, int32_t *picks, int32_t *dead, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_sched_pick_allow";
+    if (dfa_op_check(fn, logits, n_rows, n_vocab, table, n_table_states, states, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    if (!emit) { set_err(err, err_cap, "%s: emit is NULL", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (dfa_rows_check(fn, n_rows, n_vocab, n_table_states, states, fallback, picks, dead, err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const bool words = state || log || next_tok || seg_words;
+    if (words && (!state || !log || !next_tok || !seg_words)) { set_err(err, err_cap, "%s: the slot words state, log, next_tok and seg_words come all four or not at all", fn); return LLAMAHIP_ERR_PREDICT; }
+    if (words && (n_slots < 1 || n_slots > 4096 || log_cap < 1 || log_cap > 1 << 20)) { set_err(err, err_cap, "%s: n_slots (%d) outside 1 .. 4096 or log_cap (%d) outside 1 .. 2^20", fn, n_slots, log_cap); return LLAMAHIP_ERR_PREDICT; }
+    int32_t tab[4 * SET_MAX] = { 0 };
+    for (int r = 0; r < n_rows; r++) {
+        tab[4 * r] = emit[r] != 0;
+        if (!words) continue;
+        const int32_t *w = seg_words + 3 * r;
+        if (w[0] < 0 || w[0] >= n_slots) { set_err(err, err_cap, "%s: segment %d: slot %d out of range [0, n_slots = %d)", fn, r, w[0], n_slots); return LLAMAHIP_ERR_PREDICT; }
+        for (int q = 0; q < r; q++) if (seg_words[3 * q] == w[0]) { set_err(err, err_cap, "%s: slot %d has two segments (%d and %d): one segment per slot", fn, w[0], q, r); return LLAMAHIP_ERR_PREDICT; }
+        if (w[1] < 0 || w[2] < 0) { set_err(err, err_cap, "%s: segment %d: position %d / cursor %d out of range", fn, r, w[1], w[2]); return LLAMAHIP_ERR_PREDICT; }
+        tab[4 * r + 1] = w[0]; tab[4 * r + 2] = w[1]; tab[4 * r + 3] = w[2];
+    }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    const size_t N = (size_t) n_rows, V = (size_t) n_vocab, NS = words ? (size_t) n_slots : 0;
+    int32_t h[2 * SET_MAX];
+    Scratch s;
+    float *d_l = s.alloc(N * V, logits);
+    uint16_t *d_t = s.alloc((size_t) n_table_states * V, table);
+    int32_t *d_tab = s.alloc<int32_t>(4 * N, tab), *d_res = s.alloc<int32_t>(2 * N);
+    // (the slot words go up and come back whole: what the launch does not write keeps the caller's bits)
+    int32_t *d_state = words ? s.alloc<int32_t>(2 * NS, state) : nullptr, *d_log = words ? s.alloc<int32_t>(NS * (size_t) log_cap, log) : nullptr;
+    int32_t *d_next = words ? s.alloc<int32_t>(NS, next_tok) : nullptr;
+    DfaMaskRows rows = {};
+    DfaFallback fb = {};
+    for (size_t r = 0; r < N; r++) { rows.row[r] = states[r] < 0 ? nullptr : d_t + (size_t) states[r] * V; fb.t[r] = fallback[r]; }
+    if (s.ok()) s.check(launch_sched_pick_dfa(d_l, n_rows, n_vocab, d_tab, rows, fb, d_state, d_log, log_cap, d_next, d_res, nullptr));
+    if (s.ok()) s.download(h, d_res, 2 * N * 4);
+    if (s.ok() && words) { s.download(state, d_state, 2 * NS * 4); s.download(log, d_log, NS * (size_t) log_cap * 4); s.download(next_tok, d_next, NS * 4); }
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    memcpy(picks, h, N * 4);
+    memcpy(dead, h + N, N * 4);
+    return LLAMAHIP_OK;
+}
+
 // k_verify_rows + k_sched_accept on caller-supplied rows and a caller's segment table, with or without slot words (parity tests): see the
 // request scheduler's "drafted tokens" in llamahip.h
 int llamahip_op_sched_accept(const float *logits, int32_t n_rows, int32_t n_vocab, const int32_t *seg_tab, int32_t n_segs, const int32_t *tokens,

@@ -12,6 +12,7 @@
 #include <deque>
 #include <vector>
 
+#include "constrain.h"
 #include "sched.h"
 
 namespace {
@@ -22,6 +23,8 @@ struct Req {
     std::vector<int32_t> hist;    // a drafting scheduler only: the prompt, then everything produced (the drafter's history)
     int32_t n_predict = 0, stop_token = -1;
     llamahip_sampler *sampler = nullptr;
+    llamahip_constraint *cst = nullptr;      // the caller's; lives until the request's DONE
+    int32_t cst_state = 0;        // the automaton's state behind everything produced: the state of the next pick
     int32_t off = 0;              // prompt tokens evaluated
     int32_t last = 0;             // the token the next decode row evaluates
     int32_t n_out = 0;            // tokens produced
@@ -161,6 +164,8 @@ extern "C" int llamahip_sched_new(llamahip_model *m, const llamahip_sched_opts *
     }
     if (o->struct_size < (int32_t) (offsetof(llamahip_sched_opts, prefix_share) + sizeof(op.prefix_share))) op.prefix_share = 0;          // (a shorter struct: off)
     if (op.prefix_share != 0 && op.prefix_share != 1) return refuse(err, err_cap, "llamahip_sched_new: prefix_share (%ld) must be 0 (off) or 1", op.prefix_share);
+    if (o->struct_size < (int32_t) (offsetof(llamahip_sched_opts, forced_drafts) + sizeof(op.forced_drafts))) op.forced_drafts = 0;          // (a shorter struct: off)
+    if (op.forced_drafts != 0 && op.forced_drafts != 1) return refuse(err, err_cap, "llamahip_sched_new: forced_drafts (%ld) must be 0 (off) or 1", op.forced_drafts);
     if (op.n_corpus < 0 || (op.n_corpus > 0 && !op.corpus)) return refuse(err, err_cap, "llamahip_sched_new: n_corpus (%ld) must be >= 0, with a corpus where it is > 0", op.n_corpus);
     if (const int32_t V = llamahip_n_vocab(m))          // (a null handle is refused below)
         for (int32_t i = 0; i < op.n_corpus; i++)
@@ -196,7 +201,11 @@ extern "C" void llamahip_sched_free(llamahip_sched *s) {
 extern "C" int llamahip_sched_submit(llamahip_sched *s, const llamahip_request *r, int64_t *id, char *err, size_t err_cap) {
     static const char *fn = "llamahip_sched_submit";
     if (!s || !r) { if (err && err_cap) snprintf(err, err_cap, "%s: null scheduler or request", fn); return LLAMAHIP_ERR_PREDICT; }
-    if (r->struct_size < (int32_t) sizeof(llamahip_request)) return refuse(err, err_cap, "llamahip_sched_submit: struct_size (%ld) is not sizeof(llamahip_request) (%ld)", r->struct_size, sizeof(llamahip_request));
+    // the request up to `sampler` (the struct before constraints) or the whole of it; the new fields are read only where struct_size covers them
+    if (r->struct_size < (int32_t) offsetof(llamahip_request, constraint))
+        return refuse(err, err_cap, "llamahip_sched_submit: struct_size (%ld) is smaller than the request up to sampler (%ld; sizeof(llamahip_request) is %ld)", r->struct_size, offsetof(llamahip_request, constraint), sizeof(llamahip_request));
+    llamahip_constraint *cst = r->struct_size >= (int32_t) (offsetof(llamahip_request, constraint) + sizeof(r->constraint)) ? r->constraint : nullptr;
+    int32_t cst_state = r->struct_size >= (int32_t) (offsetof(llamahip_request, constraint_state) + sizeof(r->constraint_state)) ? r->constraint_state : -1;
     if (!r->prompt || r->n_prompt < 1) return refuse(err, err_cap, "llamahip_sched_submit: n_prompt must be >= 1 (got %ld)", r->n_prompt);
     if (r->n_predict < 1) return refuse(err, err_cap, "llamahip_sched_submit: n_predict must be >= 1 (got %ld)", r->n_predict);
     if ((int64_t) r->n_prompt + r->n_predict - 1 > s->hi.n_ctx)
@@ -215,11 +224,21 @@ extern "C" int llamahip_sched_submit(llamahip_sched *s, const llamahip_request *
         for (const Req &q : s->slot) held = held || (q.id && q.sampler == r->sampler && !q.cancelled);
         if (held) return refuse(err, err_cap, "llamahip_sched_submit: the sampler is held by another live request: every request draws with its own");
     }
+    if (cst) {
+        if (cst->m != s->m) return refuse(err, err_cap, "llamahip_sched_submit: the constraint was made on another handle");
+        if (cst_state < -1 || cst_state >= cst->n_states) return refuse(err, err_cap, "llamahip_sched_submit: constraint_state %ld out of range [0, %ld) (-1 = the constraint's start)", cst_state, cst->n_states);
+        if (r->stop_token != -1 && r->stop_token != cst->stop_token)
+            return refuse(err, err_cap, "llamahip_sched_submit: stop_token %ld is neither -1 nor the constraint's stop token (%ld), which ends a constrained request", r->stop_token, cst->stop_token);
+        if (r->sampler) return refuse(err, err_cap, "llamahip_sched_submit: a sampler together with a constraint: sampled constrained requests are not built (greedy only)");
+        if (s->hi.pipeline) return refuse(err, err_cap, "llamahip_sched_submit: a constrained request on an in-process pipeline handle is not built (the table's device copy belongs to one device)");
+        if (cst_state < 0) cst_state = cst->start;
+    }
     Req q;
     q.id = s->next_id++;
     q.prompt.assign(r->prompt, r->prompt + r->n_prompt);
     if (s->o.draft_len > 0) q.hist = q.prompt;
-    q.n_predict = r->n_predict; q.stop_token = r->stop_token; q.sampler = r->sampler;
+    q.n_predict = r->n_predict; q.stop_token = cst ? cst->stop_token : r->stop_token; q.sampler = r->sampler;
+    q.cst = cst; q.cst_state = cst ? cst_state : 0;
     s->queue.push_back(std::move(q));
     s->st.n_submitted++;
     if (id) *id = s->queue.back().id;
@@ -257,10 +276,12 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     if (n_ev) *n_ev = 0;
     if (!s || !ev || !n_ev) { if (err && err_cap) snprintf(err, err_cap, "%s: null scheduler, events or n_ev", fn); return LLAMAHIP_ERR_PREDICT; }
     const int32_t A = s->o.max_active;
-    if (s->o.draft_len == 0 && cap < 2 * A + 1) return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least 2 * max_active + 1 (%ld) events", cap, 2 * A + 1);
-    if (cap < LLAMAHIP_SCHED_EVENT_CAP(A, s->o.draft_len))
-        return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least max_active + 17 (%ld) events with draft_len > 0 (LLAMAHIP_SCHED_EVENT_CAP)", cap, A + 17);
-    const int32_t own_events = LLAMAHIP_SCHED_EVENT_CAP(A, s->o.draft_len) - 1;          // what the step's own TOKEN and DONE events may take
+    // (forced drafts put several tokens of a request into one step whatever draft_len is: the capacity of a drafting scheduler)
+    const int32_t cap_len = std::max(s->o.draft_len, s->o.forced_drafts);
+    if (cap_len == 0 && cap < 2 * A + 1) return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least 2 * max_active + 1 (%ld) events", cap, 2 * A + 1);
+    if (cap < LLAMAHIP_SCHED_EVENT_CAP(A, cap_len))
+        return refuse(err, err_cap, "llamahip_sched_step: cap (%ld) must be at least max_active + 17 (%ld) events with draft_len > 0 or forced_drafts (LLAMAHIP_SCHED_EVENT_CAP(max_active, 1))", cap, A + 17);
+    const int32_t own_events = LLAMAHIP_SCHED_EVENT_CAP(A, cap_len) - 1;          // what the step's own TOKEN and DONE events may take
     // 1. cancelled active requests leave their slots; then as many waiting DONE events as the step's own events leave room for
     for (size_t k = 0; k < s->order.size();) {
         Req &q = s->slot[(size_t) s->order[k]];
@@ -324,11 +345,17 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
     // 3b. drafted tokens in the rows the step leaves spare: what every decoding request could use, then the one policy
     int32_t want[16] = { 0 }, give[16] = { 0 }, draft_rows = 0;
     int32_t drafts[16][15];
-    if (s->o.draft_len > 0 && lh::sched_dev_drafts(s->dev)) {
+    bool forced[16] = { false };
+    if ((s->o.draft_len > 0 || s->o.forced_drafts) && lh::sched_dev_drafts(s->dev)) {
         bool any = false;
         for (int32_t k = 0; k < na; k++) {
             Req &q = s->slot[(size_t) s->order[(size_t) k]];
             if (left[k] > 0 || q.n_out < 1) continue;
+            // a constrained request's forced run, from the state behind the token it is about to evaluate: a draft accepted by construction
+            if (q.cst && s->o.forced_drafts) {
+                const int32_t n = llamahip_forced_run(q.cst, q.cst_state, drafts[k], std::max(std::min(15, q.n_predict - q.n_out - 1), 0));
+                if (n > 0) { want[k] = n; forced[k] = true; any = true; continue; }
+            }
             int32_t room = std::min(s->o.draft_len, q.n_predict - q.n_out - 1);          // a verify step never passes n_predict (and so never n_ctx)
             if (room < 1) continue;
             if (q.sampler && (s->o.top_k > 64 || s->hi.n_vocab > 32768 || llamahip_sampler_window(q.sampler, nullptr, 0) > 1024)) continue;      // (no candidates on the device)
@@ -336,6 +363,12 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
             // a sampled request draws nothing behind its stop token (the draws are accepted into its sampler as they are made): its draft
             // ends before one.  A greedy request's accepted tokens behind a stop token are dropped below
             for (int32_t j = 0; q.sampler && j < n; j++) if (q.stop_token >= 0 && drafts[k][j] == q.stop_token) n = j;
+            // a constrained request's lookup draft ends at the first token banned in the running state, and behind a drafted stop token
+            for (int32_t j = 0, st = q.cst_state; q.cst && j < n; j++) {
+                st = llamahip_constraint_advance(q.cst, st, drafts[k][j]);
+                if (st < 0) n = j;
+                else if (drafts[k][j] == q.stop_token) n = j + 1;
+            }
             want[k] = std::max(n, 0);
             any = any || want[k] > 0;
         }
@@ -351,8 +384,10 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         lh::SchedSeg &g = segs[n_segs];
         g = lh::SchedSeg();
         g.slot = sl; g.n_rows = rows[k]; g.n_out = q.n_out; g.sampler = q.sampler; g.token = -1;
+        g.cst = q.cst; g.cst_state = q.cst_state;
         if (left[k] > 0) {
             g.pos = q.off; g.tokens = q.prompt.data() + q.off; g.emit = rows[k] == left[k] ? 1 : 0;
+            if (!g.emit) g.cst = nullptr;
             mixed = true; prompt_rows += rows[k];
         } else {
             g.pos = (int32_t) q.prompt.size() + q.n_out - 1; g.tokens = &q.last; g.emit = 1;
@@ -371,12 +406,17 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         for (int32_t a = 0; a <= g.n_accept; a++)
             if (g.toks[a] < 0 || g.toks[a] >= s->hi.n_vocab || (a < g.n_accept && g.toks[a] != g.draft[a]))
                 return refuse(err, err_cap, "llamahip_sched_step: the device half reported token %ld for slot %ld", g.toks[a], g.slot);
+        // a constrained segment: every token it produced is allowed in the state it was picked in
+        for (int32_t a = 0, st = g.cst_state; g.cst && a <= g.n_accept; a++)
+            if ((st = llamahip_constraint_advance(g.cst, st, g.toks[a])) < 0)
+                return refuse(err, err_cap, "llamahip_sched_step: the device half reported token %ld for slot %ld, which the request's constraint bans", g.toks[a], g.slot);
     }
     deliver_pending();
     s->st.n_steps++;
     (kind == lh::SCHED_STEP_MIXED ? s->st.n_mixed_steps : kind == lh::SCHED_STEP_SET ? s->st.n_set_steps : kind == lh::SCHED_STEP_SINGLE ? s->st.n_single_steps : s->st.n_fallback_steps)++;
     s->st.n_rows += total + draft_rows; s->st.n_prompt_rows += prompt_rows; s->st.n_graph_captures += captures;
     if (draft_rows > 0) { s->st.n_draft_steps++; s->st.n_drafted += draft_rows; }
+    for (int32_t k = 0; k < na; k++) if (forced[k]) s->st.n_forced_drafted += give[k];
     // 4. the step's events; a request that produced its last token frees its slot (reused from the next step)
     bool freed[16] = { false };
     for (int32_t j = 0; j < n_segs; j++) {
@@ -389,9 +429,12 @@ extern "C" int llamahip_sched_step(llamahip_sched *s, llamahip_sched_event *ev, 
         if (!g.emit) continue;
         s->st.n_emit_segs++;
         s->st.n_accepted += g.n_accept;
+        if (forced[seg_k[j]]) s->st.n_forced_accepted += g.n_accept;
+        if (g.cst) s->st.n_dfa_rows += 1 + g.n_draft;
         // the segment's n_accept + 1 tokens in order, cut at the stop token (what was accepted behind it is dropped) or at n_predict
         for (int32_t a = 0; a <= g.n_accept; a++) {
             q.last = g.toks[a]; q.n_out++;
+            if (q.cst) q.cst_state = llamahip_constraint_advance(q.cst, q.cst_state, q.last);          // (checked above: never banned)
             if (s->o.draft_len > 0) q.hist.push_back(q.last);
             s->st.n_tokens++;
             const int32_t ctx = (int32_t) q.prompt.size() + q.n_out - 1;          // the KV rows the slot holds; the position the token would be evaluated at

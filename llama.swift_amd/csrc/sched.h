@@ -13,7 +13,8 @@ struct SchedDev;          // the device half's state for one scheduler (llamahip
 
 // what the host half needs to know of the handle; refuses (message in err, the handle named last) null, HOST_ONLY and stage handles
 // fast_prefill: a LLAMAHIP_FLAG_FAST_PREFILL handle (no parity claim for its prompt rows: nothing of them is shared between slots)
-struct SchedHandleInfo { int32_t n_ctx, n_vocab, n_seq, fast_prefill; };
+// pipeline: an in-process pipeline handle (a constraint's device table belongs to one device: constrained requests are refused there)
+struct SchedHandleInfo { int32_t n_ctx, n_vocab, n_seq, fast_prefill, pipeline; };
 int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, size_t err_cap);
 // the sampler parameters of llamahip_sched_opts, by llamahip_verify_sample's rule
 int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap);
@@ -26,6 +27,10 @@ int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, doub
 // evaluates [tokens[0], draft ...] at pos, 1 + n_draft rows.  The device half fills n_accept (how many leading draft tokens the model
 // reproduced, 0 .. n_draft) and toks / exacts [0 .. n_accept]: the tokens the segment produced -- picks, or draws already accepted into the
 // sampler; token / exact = the first of them.  A segment without a draft gets token / exact only, as before.
+// cst / cst_state (a greedy segment that emits; null = unconstrained): the request's constraint and the automaton state BEFORE the segment's
+// first pick.  Every pick of the segment is then k_pick_dfa's rule under the state reached by advancing over the draft tokens in front of its
+// logits row (the device half resolves the states: it has the table); a draft token banned in its state, or a row that allows nothing (the
+// device's dead word), fails the step.  The host half advances the request's state over the tokens it reports.
 constexpr int SCHED_SEG_TOKS = 16;
 struct SchedSeg {
     int32_t slot, pos, n_rows, emit, n_out;
@@ -35,6 +40,8 @@ struct SchedSeg {
     const int32_t *draft;
     int32_t n_draft, n_accept;
     int32_t toks[SCHED_SEG_TOKS], exacts[SCHED_SEG_TOKS];
+    llamahip_constraint *cst;
+    int32_t cst_state;
 };
 enum { SCHED_STEP_MIXED = 0, SCHED_STEP_SET = 1, SCHED_STEP_SINGLE = 2, SCHED_STEP_FALLBACK = 3 };
 

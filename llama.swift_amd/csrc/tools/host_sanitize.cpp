@@ -172,7 +172,26 @@ int sched_dev_step(SchedDev *d, SchedSeg *segs, int32_t n_segs, bool mixed, int3
         }
         c.toks.emplace_back(segs[j].tokens, segs[j].tokens + segs[j].n_rows);
         c.drafts.emplace_back(segs[j].draft, segs[j].draft + segs[j].n_draft);          // (exactly sized, as the rows' tokens)
-        if (segs[j].n_draft > 0) {
+        if (segs[j].cst && segs[j].emit) {
+            // a constrained segment: the rule's pick (llamahip_constraint_pick) on a synthetic logits row per logits row of the segment -- made up
+            // from the row's token and position, with ties, a NaN and a -0.0 in it -- under the state behind the draft tokens in front of it
+            SchedSeg &g = segs[j];
+            if (g.sampler || g.n_draft > 15 || (g.n_draft > 0 && (!mixed || g.n_rows != 1))) { snprintf(err, err_cap, "llamahip_sched_step: a constraint where none belongs"); return LLAMAHIP_ERR_PREDICT; }
+            std::vector<float> row((size_t) d->V);
+            int32_t st = g.cst_state, tok = c.toks.back().back();
+            g.n_accept = 0;
+            for (int i = 0; i <= g.n_draft; i++) {
+                for (int v = 0; v < d->V; v++) row[(size_t) v] = (float) (sched_made_up(d, tok + v, g.pos + g.n_rows + i) % 17) - 8.0f;
+                row[(size_t) (tok % d->V)] = NAN; row[(size_t) ((tok + 1) % d->V)] = -0.0f;
+                const int32_t p = llamahip_constraint_pick(g.cst, st, row.data());
+                if (p < 0) { snprintf(err, err_cap, "llamahip_sched_step: a pick found no allowed token"); return LLAMAHIP_ERR_PREDICT; }
+                g.toks[i] = p; g.exacts[i] = 1; g.n_accept = i;
+                if (i == g.n_draft || p != g.draft[i]) break;
+                st = llamahip_constraint_advance(g.cst, st, p);
+                tok = p;
+            }
+            g.token = g.toks[0]; g.exact = 1;
+        } else if (segs[j].n_draft > 0) {
             // the scripted number of draft tokens accepted, then a made-up token that is not the draft's next one
             SchedSeg &g = segs[j];
             if (!mixed || !g.emit || g.n_rows != 1 || g.n_draft > 15) { snprintf(err, err_cap, "llamahip_sched_step: a draft where none belongs"); return LLAMAHIP_ERR_PREDICT; }
@@ -1556,6 +1575,134 @@ int main(int argc, char **argv) {
             }
             EXPECT(!ms || (shared_in_all > 0 && copied_in_all > 0));
             printf("host_sanitize: scheduler with shared prefixes: %ld plans against the restatement, %lld rows shared and %lld of them copied over all runs\n", n_plans, (long long) shared_in_all, (long long) copied_in_all);
+        }
+        // constrained requests (sched.cpp + constrain.cpp as they are): choices with long forced tails over the file's vocabulary, forced drafts off
+        // and on (with and without lookup drafts), a cancel in mid-answer, a stop token inside an accepted draft; every stream against the
+        // contract's loop restated on the stub's rows (forced drafts change the steps, never the tokens), the three stats identities
+        if (ms) {
+            const int32_t stop = 2;
+            // the vocabulary's words (constrain_host_half): letters, a space, tokNNNNN.  Every string below is spelt letter by letter
+            static const char *strs[] = { "yes please", "no thanks", "cab", "cabbage" };
+            const uint8_t *sp[4]; int32_t sl[4];
+            for (int i = 0; i < 4; i++) { sp[i] = (const uint8_t *) strs[i]; sl[i] = (int32_t) strlen(strs[i]); }
+            llamahip_constraint *cc = nullptr;
+            EXPECT(llamahip_constraint_new_choices(ms, sp, sl, 4, stop, &cc, err, sizeof(err)) == 0 && cc);
+            long n_forced_all = 0, n_streams = 0;
+            std::vector<std::vector<int32_t>> base;          // the streams with forced drafts off: every other configuration repeats them
+            for (int cfg = 0; cc && cfg < 4; cfg++) {          // 0: off; 1: forced; 2: forced + lookup drafts; 3: lookup drafts alone
+                llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                so.struct_size = sizeof(so); so.n_threads = 2; so.max_active = 3; so.chunk_tokens = 4; so.row_budget = 8;
+                so.forced_drafts = cfg == 1 || cfg == 2; so.draft_len = cfg >= 2 ? 6 : 0;
+                llamahip_sched *sc = nullptr;
+                EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                if (!sc) continue;
+                g_sched_calls.clear(); g_sched_accept = -1;
+                const int NR = 6;
+                std::vector<std::vector<int32_t>> prompts((size_t) NR), got((size_t) NR);
+                std::vector<int64_t> ids((size_t) NR);
+                std::vector<int> reason((size_t) NR, 0);
+                static const int plens[NR] = { 1, 5, 9, 3, 12, 2 }, npred[NR] = { 16, 16, 4, 16, 16, 16 };
+                for (int i = 0; i < NR; i++) {
+                    prompts[(size_t) i].resize((size_t) plens[i]);
+                    for (size_t k = 0; k < prompts[(size_t) i].size(); k++) prompts[(size_t) i][k] = (int32_t) ((i * 37 + k * 11 + 5) % (size_t) V);
+                    llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                    rq.struct_size = sizeof(rq); rq.prompt = prompts[(size_t) i].data(); rq.n_prompt = plens[i]; rq.n_predict = npred[i];
+                    rq.stop_token = i % 2 ? stop : -1; rq.constraint = i == 3 ? nullptr : cc; rq.constraint_state = -1;
+                    EXPECT(llamahip_sched_submit(sc, &rq, &ids[(size_t) i], err, sizeof(err)) == 0);
+                }
+                const int32_t cap = LLAMAHIP_SCHED_EVENT_CAP(3, so.draft_len > 0 || so.forced_drafts ? 1 : 0);
+                std::vector<llamahip_sched_event> evs((size_t) cap);          // exactly sized
+                int32_t ne = 0;
+                if (cfg != 0) { EXPECT(llamahip_sched_step(sc, evs.data(), cap - 1, &ne, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "cap")); }
+                int steps = 0;
+                bool cancelled = false;
+                while (llamahip_sched_pending(sc) > 0 && steps++ < 200) {
+                    EXPECT(llamahip_sched_step(sc, evs.data(), cap, &ne, err, sizeof(err)) == 0);
+                    for (int32_t e = 0; e < ne; e++) {
+                        size_t i = 0;
+                        while (i < ids.size() && ids[i] != evs[(size_t) e].id) i++;
+                        EXPECT(i < ids.size());
+                        if (i >= ids.size()) continue;
+                        if (evs[(size_t) e].kind == LLAMAHIP_EV_TOKEN) got[i].push_back(evs[(size_t) e].token);
+                        else reason[i] = evs[(size_t) e].reason;
+                    }
+                    // a cancel in mid-answer: request 4, once it has produced its first token (with forced drafts the next step would end it)
+                    if (!cancelled && got[4].size() >= 1 && reason[4] == 0) { EXPECT(llamahip_sched_cancel(sc, ids[4]) == 0); cancelled = true; }
+                }
+                EXPECT(llamahip_sched_pending(sc) == 0 && cancelled);
+                for (int i = 0; i < NR; i++) {
+                    const std::vector<int32_t> &t = got[(size_t) i];
+                    if (i == 4) { EXPECT(reason[4] == LLAMAHIP_DONE_CANCELLED); continue; }
+                    if (i == 3) { EXPECT(reason[3] == (t.size() == 16 ? LLAMAHIP_DONE_LENGTH : LLAMAHIP_DONE_STOP)); continue; }
+                    // a constrained stream: a walk of the automaton from its start that ends in DONE at the stop token, or at n_predict
+                    int32_t st = llamahip_constraint_start(cc);
+                    for (int32_t tok : t) { st = llamahip_constraint_advance(cc, st, tok); EXPECT(st >= 0); if (st < 0) break; }
+                    const bool stopped = !t.empty() && t.back() == stop;
+                    EXPECT(stopped ? (st == llamahip_constraint_done(cc) && reason[(size_t) i] == LLAMAHIP_DONE_STOP) : ((int) t.size() == npred[i] && reason[(size_t) i] == LLAMAHIP_DONE_LENGTH));
+                    for (size_t k = 0; k + 1 < t.size(); k++) EXPECT(t[k] != stop);
+                    n_streams++;
+                }
+                EXPECT(reason[2] == LLAMAHIP_DONE_LENGTH && got[2].size() == 4);          // n_predict shorter than every answer
+                // (the stub's constrained rows depend on a row's token and position alone, so every configuration produces the same constrained
+                // streams; the unconstrained request's made-up tokens follow the scripted accepts)
+                if (cfg == 0) base = got;
+                else for (int i = 0; i < NR; i++) if (i != 4 && i != 3) EXPECT(got[(size_t) i] == base[(size_t) i]);
+                llamahip_sched_stats ss; memset(&ss, 0, sizeof(ss)); ss.struct_size = sizeof(ss);
+                EXPECT(llamahip_sched_get_stats(sc, &ss) == 0);
+                EXPECT(ss.n_forced_accepted == ss.n_forced_drafted && ss.n_tokens == ss.n_emit_segs + ss.n_accepted - ss.n_dropped && ss.n_dfa_rows > 0);
+                EXPECT((so.forced_drafts != 0) == (ss.n_forced_drafted > 0) && ss.n_forced_drafted <= ss.n_drafted && ss.n_forced_accepted <= ss.n_accepted);
+                if (cfg == 1) EXPECT(ss.n_dropped > 0);          // a stop token inside an accepted draft: the row behind it is dropped
+                n_forced_all += (long) ss.n_forced_drafted;
+                // every draft handed to the device half for a constrained segment is allowed token by token from the segment's state
+                for (const SchedCall &call : g_sched_calls)
+                    for (size_t j = 0; j < call.segs.size(); j++) {
+                        const lh::SchedSeg &g = call.segs[j];
+                        int32_t st = g.cst_state;
+                        for (int32_t tok : call.drafts[j]) { if (!g.cst) break; st = llamahip_constraint_advance(g.cst, st, tok); EXPECT(st >= 0); if (st < 0) break; }
+                    }
+                llamahip_sched_free(sc);
+            }
+            // what llamahip_sched_submit refuses of a constrained request, and the two struct sizes it takes
+            if (cc) {
+                llamahip_sched_opts so; memset(&so, 0, sizeof(so));
+                so.struct_size = sizeof(so); so.max_active = 2;
+                llamahip_sched *sc = nullptr;
+                so.forced_drafts = 2; EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && !sc && strstr(err, "forced_drafts"));
+                so.struct_size = (int32_t) offsetof(llamahip_sched_opts, forced_drafts);          // a struct that ends before it: off, whatever lies behind
+                EXPECT(llamahip_sched_new(ms, &so, &sc, err, sizeof(err)) == 0 && sc);
+                if (sc) {
+                    const int32_t p1[1] = { 5 };
+                    llamahip_request rq; memset(&rq, 0, sizeof(rq));
+                    rq.struct_size = sizeof(rq); rq.prompt = p1; rq.n_prompt = 1; rq.n_predict = 2; rq.stop_token = -1; rq.constraint = cc; rq.constraint_state = -1;
+                    llamahip_sampler *smp = llamahip_sampler_new(1, 8);
+                    rq.constraint_state = llamahip_constraint_n_states(cc); EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "constraint_state"));
+                    rq.constraint_state = -2; EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "constraint_state"));
+                    rq.constraint_state = -1; rq.stop_token = 3; EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "stop token"));
+                    rq.stop_token = -1; rq.sampler = smp; EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "sampler"));
+                    rq.sampler = nullptr;
+                    llamahip_model *mo = nullptr;          // the same file on another handle
+                    llamahip_constraint *other = nullptr;
+                    EXPECT(llamahip_model_load(path.c_str(), 48, &o, &mo, err, sizeof(err)) == 0 && mo);
+                    EXPECT(mo && llamahip_constraint_new_choices(mo, sp, sl, 4, stop, &other, err, sizeof(err)) == 0 && other);
+                    rq.constraint = other; EXPECT(!other ||llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "another handle"));
+                    rq.constraint = cc;
+                    llamahip_constraint_free(other);
+                    if (mo) llamahip_model_free(mo);
+                    rq.struct_size = (int32_t) offsetof(llamahip_request, constraint);          // the request before constraints: taken, the fields behind it not read
+                    rq.constraint_state = 99999; EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == 0);
+                    rq.struct_size -= 1; EXPECT(llamahip_sched_submit(sc, &rq, nullptr, err, sizeof(err)) == LLAMAHIP_ERR_PREDICT && strstr(err, "struct_size"));
+                    EXPECT(llamahip_sched_pending(sc) == 1);
+                    llamahip_sampler_free(smp);
+                    llamahip_sched_free(sc);
+                }
+                int32_t run[16];
+                EXPECT(llamahip_forced_run(nullptr, 0, run, 4) == -1 && llamahip_forced_run(cc, -1, run, 4) == -1 && llamahip_forced_run(cc, 0, run, -1) == -1);
+                EXPECT(llamahip_forced_run(cc, llamahip_constraint_n_states(cc), run, 4) == -1 && llamahip_forced_run(cc, llamahip_constraint_done(cc), run, 4) == 0);
+                EXPECT(llamahip_forced_run(cc, 0, nullptr, 0) == 0);
+                llamahip_constraint_free(cc);
+            }
+            EXPECT(n_forced_all > 0 && n_streams > 0);
+            printf("host_sanitize: scheduler with constrained requests: %ld streams walk their automaton in 4 configurations, %ld forced tokens drafted and accepted\n", n_streams, n_forced_all);
         }
         // llamahip_sched_submit's row limit, on a handle whose context is long enough to reach it: with chunk_tokens 0 a prompt is one piece of
         // at most LLAMAHIP_EVAL_MULTI_MAX_ROWS - max_active rows; in chunks the piece is the chunk -- and a chunk that long is refused the same way

@@ -29,8 +29,14 @@
 // k_sched_accept: the same for a scheduler step that carries drafted tokens, behind k_verify_rows over all logits rows of the step -- per
 //   segment n_accept by the rule above (one device function, vr_n_accept, for the three kernels), the slot's words advanced by what was
 //   accepted.  4 (rows + segments) bytes come back.
+// k_verify_rows_dfa / k_sched_pick_dfa: the two kernels above for a scheduler step in which some greedy segment decodes under a constraint
+//   (include/llamahip.h "constrained requests").  Same geometry, same stores; every logits row carries a pointer to the table
+//   row next[state] of the state the host resolved for it (null: the row is unconstrained and takes vr_row_pick, not restated) and a
+//   range-checked fallback token.  A constrained row's pick is k_pick_dfa's rule (dfa_pick.hip.h, the one statement of that scan); a row that
+//   allows nothing picks its fallback and sets its dead word.  Plain 16-bit loads, no hand-offs between workgroups.
 #include <cmath>
 
+#include "dfa_pick.hip.h"
 #include "kcommon.hip.h"
 
 namespace lh {
@@ -114,6 +120,49 @@ k_sched_pick(const float *__restrict__ logits, int V, const int32_t *__restrict_
     if (emit) p = vr_row_pick(logits + (size_t) s * V, V, bv, bi);          // (emit is uniform over the workgroup)
     if (threadIdx.x != 0) return;
     res[s] = p;
+    if (!state) return;
+    state[2 * (size_t) slot] = pos;
+    state[2 * (size_t) slot + 1] = cur;
+    if (emit) {
+        next_tok[slot] = p;
+        if (cur >= 1 && cur <= log_cap) log[(size_t) slot * log_cap + cur - 1] = p;
+    }
+}
+
+// k_verify_rows under per-row allow-lists: rows.row[r] = the table row of logits row r's state (null = unconstrained), fb.t[r] = the token
+// a row that allows nothing picks (dead[r] = 1; 0 otherwise).  The pick is an embedding read on the next step: always a checked token id.
+__global__ void __launch_bounds__(1024)
+k_verify_rows_dfa(const float *__restrict__ logits, int V, const DfaMaskRows rows, const DfaFallback fb, int32_t *__restrict__ pick, int32_t *__restrict__ dead) {
+    __shared__ float bv[16];
+    __shared__ int bi[16], bl[16];
+    const int r = blockIdx.x;
+    const uint16_t *__restrict__ tab = rows.row[r];               // (uniform over the workgroup)
+    const float *__restrict__ row = logits + (size_t) r * V;
+    const int p = tab ? dfa_row_pick(row, tab, V, bv, bi, bl) : vr_row_pick(row, V, bv, bi);
+    if (threadIdx.x == 0) {
+        pick[r] = p == DFA_NONE ? fb.t[r] : p;
+        dead[r] = p == DFA_NONE ? 1 : 0;
+    }
+}
+
+// k_sched_pick under per-segment allow-lists: the stores are k_sched_pick's; res = {pick[n_segs], dead[n_segs]}
+__global__ void __launch_bounds__(64)
+k_sched_pick_dfa(const float *__restrict__ logits, int V, const int32_t *__restrict__ tab, const DfaMaskRows rows, const DfaFallback fb,
+                 int32_t *__restrict__ state, int32_t *__restrict__ log, int log_cap, int32_t *__restrict__ next_tok, int32_t *__restrict__ res) {
+    __shared__ float bv[16];
+    __shared__ int bi[16], bl[16];
+    const int s = blockIdx.x, n_segs = gridDim.x;
+    const int emit = tab[4 * s], slot = tab[4 * s + 1], pos = tab[4 * s + 2], cur = tab[4 * s + 3];
+    const uint16_t *__restrict__ allow = rows.row[s];
+    const float *__restrict__ row = logits + (size_t) s * V;
+    int p = -1, dead = 0;
+    if (emit) {                                                   // (emit and allow are uniform over the workgroup)
+        p = allow ? dfa_row_pick(row, allow, V, bv, bi, bl) : vr_row_pick(row, V, bv, bi);
+        if (p == DFA_NONE) { p = fb.t[s]; dead = 1; }
+    }
+    if (threadIdx.x != 0) return;
+    res[s] = p;
+    res[n_segs + s] = dead;
     if (!state) return;
     state[2 * (size_t) slot] = pos;
     state[2 * (size_t) slot + 1] = cur;
@@ -210,6 +259,26 @@ hipError_t launch_sched_pick(const float *logits, int n_segs, int V, const int32
     if (n_segs < 1 || n_segs > SET_MAX || V < 1 || !logits || !tab || !res) return hipErrorInvalidValue;
     if (state && (!log || !next_tok || log_cap < 1)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_sched_pick, dim3((unsigned) n_segs), dim3(64), 0, st, logits, V, tab, state, log, log_cap, next_tok, res);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// rows.row[r] null = unconstrained; every fallback token in [0, V) -- the callers' business, re-checked here because the pick is an index
+hipError_t launch_verify_rows_dfa(const float *logits, int n_rows, int V, const DfaMaskRows &rows, const DfaFallback &fb, int32_t *pick, int32_t *dead, hipStream_t st) {
+    if (n_rows < 1 || n_rows > VERIFY_ROWS_MAX || V < 1 || !logits || !pick || !dead) return hipErrorInvalidValue;
+    for (int r = 0; r < n_rows; r++) if (fb.t[r] < 0 || fb.t[r] >= V) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_verify_rows_dfa, dim3((unsigned) n_rows), dim3(1024), 0, st, logits, V, rows, fb, pick, dead);
+    LH_LAUNCH_CHECK();
+    return hipSuccess;
+}
+
+// launch_sched_pick's operands; res receives {pick[n_segs], dead[n_segs]}
+hipError_t launch_sched_pick_dfa(const float *logits, int n_segs, int V, const int32_t *tab, const DfaMaskRows &rows, const DfaFallback &fb, int32_t *state,
+                                 int32_t *log, int log_cap, int32_t *next_tok, int32_t *res, hipStream_t st) {
+    if (n_segs < 1 || n_segs > SET_MAX || V < 1 || !logits || !tab || !res) return hipErrorInvalidValue;
+    if (state && (!log || !next_tok || log_cap < 1)) return hipErrorInvalidValue;
+    for (int r = 0; r < n_segs; r++) if (fb.t[r] < 0 || fb.t[r] >= V) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sched_pick_dfa, dim3((unsigned) n_segs), dim3(64), 0, st, logits, V, tab, rows, fb, state, log, log_cap, next_tok, res);
     LH_LAUNCH_CHECK();
     return hipSuccess;
 }
