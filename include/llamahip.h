@@ -99,6 +99,17 @@ typedef struct llamahip_opts {
                                         average (cosine 0.986).  2.2x the exact path.  Decode and short evals are unaffected.
                                         Never the default, never used for a parity claim. */
 
+#define LLAMAHIP_FLAG_FAST_DENSE 32 /* OPT-IN, NOT the reference's arithmetic: on an f16 model file, multi-token evals of >= 64 rows
+                                        run wq|wk|wv, wo, w1|w3, w2 and the all-rows lm head on the fp16 matrix cores
+                                        (k_dense_f16_fast) instead of the exact k_dense_mfma.  Same weights, same fp16-rounded
+                                        activations, every product exact; ONE fp32 sum per output in the matrix core's order
+                                        instead of the reference's 32 chains, so a mat-mul agrees to rounding only
+                                        (|y - y64| <= gamma(K + 1) sum |w x|).  8-layer f16 file of 7B width, one MI355X: a 512-row eval
+                                        23.6 -> 5.45 ms, a 64-row eval 4.12 -> 2.21 ms.
+                                        Decode, set steps and evals below 64 rows are unaffected (the exact kernels, the same
+                                        bits); f32, Q4_0 and Q4_1 files accept the flag and ignore it.  llamahip_get_info-style
+                                        accessors do not report it.  Never the default, never used for a parity claim. */
+
 /* ---- the drop-in boundary ------------------------------------------------------------------ */
 
 /* Replaces llama_model_load(fname, model, vocab, n_ctx, &error)  (.mm:98).
@@ -1306,6 +1317,15 @@ int llamahip_op_prompt_gemm_q4_0(const void *w_q4_0, int32_t M, int32_t K, const
 #define LLAMAHIP_DENSE_MFMA 4
 int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                               float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
+/* The opt-in fp16 matrix-core mat-mul of f16 files (k_dense_f16_fast, what a LLAMAHIP_FLAG_FAST_DENSE handle runs for >= 64 rows) alone:
+ * y[n][m] = sum_k W[m][k] * fp16(x[n][k]) (+ resid[n][m], added last), every product exact, ONE fp32 sum per output in an order the kernel
+ * does not promise -- NOT bit for bit ggml_vec_dot_f16; held to |y - y64| <= gamma(K + 1) sum |w x| (+ |resid|) + one ulp instead.  Operand
+ * conventions are llamahip_op_mul_mat_dense's: w M rows of K fp16 values in file layout (the library permutes them as a model handle does at
+ * load, and rounds and permutes x as its activation preparation does), x [N][K], resid [N][M] or NULL, y [N][y_stride] copied to the device
+ * and back whole.  One launch.  Refused before any device is touched, the limit named: N < 64, K not a positive multiple of 32, w / x / y
+ * NULL or M < 1, y_stride < M. */
+int llamahip_op_mul_mat_f16_fast(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, char *err, size_t err_cap);
 /* The Q4_1 mat-mul with its kernel chosen by the caller: y[n][m] = ggml_vec_dot_q4_1(W[m], quantize_row_q4_1(x[n])) (+ resid[n][m]), bit for
  * bit: one fp32 accumulator per output over all K/2 byte pairs in order, every product and sum rounded on its own.  w_q4_1: M rows in FILE
  * layout, [K/32 floats min][K/32 floats d][K/32 * 16 nibble bytes] per row, K a positive multiple of 32; x [N][K]; resid [N][M] or NULL;
@@ -1635,6 +1655,13 @@ int32_t llamahip_debug_dense_set_plan(int32_t m, int32_t k, int32_t wtype, int32
  * 1 where LLAMAHIP_DENSE_AUTO picks the kernel for this shape else 0 }.  Returns 1, 0 where the kernel does not take the shape (n_rows <= 16,
  * K not a multiple of 128, another wtype, n_rows * k >= 2^31), -1 where the plan names an instance that was never compiled. */
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]);
+/* Host only: the launch plan of k_dense_f16_fast for an M x K f16 matrix and n_rows activation rows -- out = { grid x (row tiles), grid y
+ * (weight-row tiles), activation rows per workgroup tile, weight rows per workgroup tile, K elements per tile, dynamic LDS bytes }: the widest
+ * of 128 x 128, 64 x 64 and 64 x 16 that still makes 256 / 128 workgroups.  Returns 1, 0 where the kernel does not take the shape
+ * (n_rows < 64, K not a positive multiple of 32, m < 1 or more than 65535 weight-row tiles). */
+int32_t llamahip_debug_dense_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]);
+/* Launches of k_dense_f16_fast since process start.  Tests and measurement tooling. */
+int64_t llamahip_debug_dense_fast_launches(void);
 /* Q4_1 mat-muls per kernel since process start: out[0 .. 1] = { k_q41_chain, k_q41_mm } (at most `cap` entries are written); returns 2.
  * One count per mat-mul, however many row tiles it launched.  Tests and measurement tooling. */
 int32_t llamahip_debug_q41_paths(int64_t *out, int32_t cap);

@@ -623,6 +623,9 @@ static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int m
     if (w.wtype != 3) {                                    // fused where it applies, else split: launch_dense_act's rule (dense.hip)
         hipError_t e = launch_dense_act(DENSE_PREP_AUTO, mode, w.wtype, in0, in1, in_stride, in1_stride, K, rows, m->tmp, m->dbg_y, m->qa_A, m->qa_d, m->T_silu, st);
         if (e != hipSuccess) return e;
+        // opt-in (LLAMAHIP_FLAG_FAST_DENSE): long evals of an f16 file on the fp16 matrix cores, the same operands with re-associated sums
+        if ((m->flags & LLAMAHIP_FLAG_FAST_DENSE) && w.wtype == 1 && rows >= DENSE_FAST_MIN_ROWS && dense_fast_plan(w.M, K, rows).ok)
+            return launch_dense_f16_fast(w, epi, m->tmp, rows, out, out_stride, resid, resid_stride, st);
         return launch_dense_mm(w, epi, nullptr, K, rows, out, out_stride, resid, resid_stride, st, m->tmp);
     }
     const float *src = in0;
@@ -5363,6 +5366,17 @@ int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int3
 }
 
 int64_t llamahip_debug_dense_mfma_launches(void) { return g_dense_mfma_launches; }
+
+int32_t llamahip_debug_dense_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]) {
+    if (!out) return 0;
+    const DenseFastPlan p = dense_fast_plan(m, k, n_rows);
+    if (!p.ok) return 0;
+    const int64_t o[6] = { p.grid_x, p.grid_y, p.tile_rows, p.tile_cols, p.k_tile, p.lds };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_dense_fast_launches(void) { return g_dense_fast_launches; }
 
 int32_t llamahip_debug_dense_force(int32_t path) {
     if (path != 0 && path != LLAMAHIP_DENSE_MM && path != LLAMAHIP_DENSE_MFMA) return -1;

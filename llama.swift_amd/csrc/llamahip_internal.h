@@ -106,6 +106,17 @@ hipError_t init_attrs_dense();
 hipError_t launch_dense_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
                            const float *resid, long resid_stride, hipStream_t st, float *scratch = nullptr,
                            int path = DENSE_PATH_AUTO, int *path_taken = nullptr);
+// k_dense_f16_fast (dense_fast.hip): the opt-in fp16 matrix-core mat-mul of f16 files, LLAMAHIP_FLAG_FAST_DENSE handles' evals of >= 64 rows and
+// llamahip_op_mul_mat_f16_fast.  NOT the reference's arithmetic (sums re-associated).  The plan: ok = the kernel takes the shape; grid
+// (grid_x, grid_y) workgroups of 256 threads, each tile_rows activation rows x tile_cols weight rows, K in tiles of k_tile; lds = dynamic LDS bytes
+struct DenseFastPlan { int ok, grid_x, grid_y, tile_rows, tile_cols, k_tile, lds; };
+constexpr int DENSE_FAST_MIN_ROWS = 64;              // the flag's row threshold
+DenseFastPlan dense_fast_plan(int M, int K, int N);
+extern long g_dense_fast_launches;                   // launches of k_dense_f16_fast (process-wide; tests)
+hipError_t init_attrs_dense_fast();
+// xp: the N prepared rows launch_dense_act / launch_dense_perm_act leave for f16 weights
+hipError_t launch_dense_f16_fast(const DMat &w, int epi, const float *xp, int N, float *y, long y_stride,
+                                 const float *resid, long resid_stride, hipStream_t st);
 hipError_t launch_q41_repack(const uint8_t *raw_rows, DMat &w, hipStream_t st);
 // Q4_1 mat-mul: the paths, counters and k_q41_chain's launch plan are q41_plan.h's (host-only); scratch: N * K floats, the expanded operand
 hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,

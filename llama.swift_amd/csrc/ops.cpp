@@ -372,6 +372,36 @@ int llamahip_op_mul_mat_dense(const void *w, int32_t wtype, int32_t M, int32_t K
     return LLAMAHIP_OK;
 }
 
+// the opt-in fp16 matrix-core mat-mul of f16 files (k_dense_f16_fast) on caller-supplied operands, prepared as a model handle would: see llamahip.h
+int llamahip_op_mul_mat_f16_fast(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_mul_mat_f16_fast";
+    if (!w || !x || !y || M < 1) { set_err(err, err_cap, "%s: bad arguments (w, x, y not NULL; M %d >= 1)", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    if (K < 32 || K % 32 != 0) { set_err(err, err_cap, "%s: K %d must be a positive multiple of 32", fn, K); return LLAMAHIP_ERR_PREDICT; }
+    if (N < DENSE_FAST_MIN_ROWS) { set_err(err, err_cap, "%s: N %d: the kernel takes N >= %d rows", fn, N, DENSE_FAST_MIN_ROWS); return LLAMAHIP_ERR_PREDICT; }
+    if (y_stride < M) { set_err(err, err_cap, "%s: y_stride %d < M %d", fn, y_stride, M); return LLAMAHIP_ERR_PREDICT; }
+    if (!dense_fast_plan(M, K, N).ok) { set_err(err, err_cap, "%s: M %d makes more than 65535 rows of workgroups", fn, M); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    DMat dm;
+    dm.M = M; dm.K = K; dm.wtype = 1;
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_raw = s.alloc(dm.bytes(), (const uint8_t *) w);
+    dm.w = s.alloc<uint8_t>(dm.bytes());
+    float *d_x = s.alloc((size_t) N * K, x);
+    float *d_y = s.alloc((size_t) N * y_stride, y);      // (the floats between M and y_stride keep the caller's bits)
+    float *d_r = resid ? s.alloc((size_t) N * M, resid) : nullptr;
+    float *d_ws = s.alloc<float>((size_t) N * K);
+    if (s.ok()) s.check(launch_dense_perm_rows(d_raw, dm, 0, M, st));
+    if (s.ok()) s.check(launch_dense_perm_act(1, d_x, K, K, N, d_ws, st));
+    if (s.ok()) s.check(launch_dense_f16_fast(dm, resid ? EPI_RESID : EPI_STORE, d_ws, N, d_y, y_stride, d_r, M, st));
+    s.download(y, d_y, (size_t) N * y_stride * 4);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    return LLAMAHIP_OK;
+}
+
 // one Q4_1 mat-mul kernel on caller-supplied operands (per-op tests of both kernels launch_q41_mm can run): see llamahip.h
 int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                              float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap) {

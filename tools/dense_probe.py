@@ -3,14 +3,15 @@
 finishes in seconds): per-layer time extrapolates to the 32-layer model.
 usage: dense_probe.py [n_layer]
        dense_probe.py [n_layer] --multi [--json OUT] [--repeats R] [--seqs 1,2,4,8,16] [--only-multi]
-       dense_probe.py [n_layer] --prompt [--json OUT] [--repeats R] [--ftype f16|f32] [--force mm|mfma] [--evals 64,128,512]
+       dense_probe.py [n_layer] --prompt [--fast] [--json OUT] [--repeats R] [--ftype f16|f32] [--force mm|mfma] [--evals 64,128,512]
                       [--chunks 18,36,72,144,504] [--trace-rows 17,32,64,128,512]
        dense_probe.py [n_layer] --q41 [--json OUT] [--repeats R] [--evals 9,16,17,64,512] [--trace-rows 1,16]
 --multi (default 8 layers: 3.2 GB, larger than the Infinity Cache): ms per step and aggregate tokens/s of decode_greedy_multi for S sequences
 from position 256 for 64 steps, the 9-token eval, and the single-stream greedy loop; every figure is the wall time of a call that
 synchronises before it returns, after one untimed run of the same call (graph captures, first-touch allocations), R repeats each.
 --prompt (default 8 layers): ms per call of eval of --evals rows and of eval_chunks(chunk 9) of --chunks tokens, the single-stream greedy loop and
-the 16-sequence set step, timed the same way; --force sends every mat-mul of more than 16 rows to one kernel (dense_force).  --trace-rows:
+the 16-sequence set step, timed the same way; --force sends every mat-mul of more than 16 rows to one kernel (dense_force); --fast opens the
+handle with LLAMAHIP_FLAG_FAST_DENSE (f16 files: evals of >= 64 rows on k_dense_f16_fast -- not the reference's arithmetic).  --trace-rows:
 nothing is timed -- per row count one untimed and R further eval_logprobs calls (the lm head over every row too) and exit, for a
 rocprofv3 --kernel-trace run that tools/dense_trace_summary.py reads.
 --q41 (default 8 layers): the f16 file of --prompt quantized with type 3 (Q4_1, kept next to it); ms per token of the single-stream greedy loop
@@ -89,7 +90,8 @@ if prompt_mode:
     if force:
         L.dense_force(force)
     stream = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 511)]).astype(np.int32)
-    m = L.Model(path, n_ctx=512, n_seq=16)
+    fast = "--fast" in args
+    m = L.Model(path, n_ctx=512, n_seq=16, flags=L.FAST_DENSE if fast else 0)
 
     def timed(fn):
         fn()
@@ -97,7 +99,7 @@ if prompt_mode:
         for _ in range(R):
             t0 = time.perf_counter(); fn(); out.append(round((time.perf_counter() - t0) * 1e3, 4))
         return out
-    res = {"library": os.path.basename(L.LIB_PATH), "force": force, "ftype": ftype, "n_layer": nl, "file_gb": round(os.path.getsize(path) / 1e9, 2)}
+    res = {"library": os.path.basename(L.LIB_PATH), "force": force, "fast_dense": fast, "ftype": ftype, "n_layer": nl, "file_gb": round(os.path.getsize(path) / 1e9, 2)}
     if "--trace-rows" in args:
         for n in ints("--trace-rows", ""):
             for _ in range(1 + R):
@@ -117,6 +119,7 @@ if prompt_mode:
         res["dense_paths"] = L.dense_paths()
     if hasattr(L, "dense_mfma_launches"):
         res["dense_mfma_launches"] = L.dense_mfma_launches()
+    res["dense_fast_launches"] = L.dense_fast_launches()
     print(json.dumps(res))
     if "--json" in args:
         with open(opt("--json", ""), "w") as f:

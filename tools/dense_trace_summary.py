@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Per-launch time of the f16 / f32 mat-mul of more than 16 rows from a rocprofv3 --kernel-trace run of
-`tools/dense_probe.py N_LAYER --prompt --trace-rows A,B,.. --repeats R [--force mm|mfma]`.
+`tools/dense_probe.py N_LAYER --prompt --trace-rows A,B,.. --repeats R [--force mm|mfma] [--fast]`.
 usage: dense_trace_summary.py <dir-or-kernel_trace.csv> N_LAYER R A,B,..
-The dispatches of k_dense_mm / k_dense_mfma are taken in start order: per row count 1 + R eval_logprobs calls (the first one untimed), per call
+The dispatches of k_dense_mm / k_dense_mfma / k_dense_f16_fast are taken in start order: per row count 1 + R eval_logprobs calls (the first one untimed), per call
 N_LAYER x (wq|wk|wv, wo, w1|w3, w2) then the lm head.  Prints one JSON object: per row count and matrix the median / min / max us over the R
 calls x N_LAYER layers, and the FMA rate of the median in TF (2 M K N flop) for LLaMA-7B shapes."""
 import csv, glob, json, os, statistics, sys
@@ -14,13 +14,13 @@ for f in files:
     for r in csv.DictReader(open(f)):
         low = {k.lower(): v for k, v in r.items()}
         name = low.get("kernel_name", "")
-        if "k_dense_mm" in name or "k_dense_mfma" in name:
-            disp.append((int(low["start_timestamp"]), int(low["end_timestamp"]), "mfma" if "k_dense_mfma" in name else "mm"))
+        if "k_dense_mm" in name or "k_dense_mfma" in name or "k_dense_f16_fast" in name:
+            disp.append((int(low["start_timestamp"]), int(low["end_timestamp"]), "mfma" if "k_dense_mfma" in name else "fast" if "k_dense_f16_fast" in name else "mm"))
 disp.sort()
 per_call = nl * 4 + 1
 want = len(rows_list) * (1 + R) * per_call
 if len(disp) != want:
-    sys.exit(f"{len(disp)} dispatches of the two kernels, expected {want}")
+    sys.exit(f"{len(disp)} dispatches of the mat-mul kernels, expected {want}")
 MATS = ("wqkv", "wo", "w13", "w2", "lm_head")
 SHAPE = {"wqkv": (12288, 4096), "wo": (4096, 4096), "w13": (22016, 4096), "w2": (4096, 11008), "lm_head": (32000, 4096)}
 out, at = {}, 0
