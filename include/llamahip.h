@@ -110,6 +110,19 @@ typedef struct llamahip_opts {
                                         bits); f32, Q4_0 and Q4_1 files accept the flag and ignore it.  llamahip_get_info-style
                                         accessors do not report it.  Never the default, never used for a parity claim. */
 
+#define LLAMAHIP_FLAG_FAST_ATTN 64 /* OPT-IN, NOT the reference's arithmetic: multi-token evals of >= 64 rows whose attention would take
+                                        the exact matrix-core chain (head size 128) run ONE fused launch on the fp16 matrix cores
+                                        (k_flash_attn, csrc/flash_attn.hip) instead of scores / soft_max / V*P / merge: q, k and v
+                                        narrowed once to fp16 (saturating), fp32 scores, exp2 under a running maximum, the weights
+                                        narrowed to fp16, one division by the fp32 sum of the narrowed weights.  No score matrix in
+                                        memory, no fp16 exp table, no per-thread key split: chunk and n_threads do not enter.  The
+                                        KV cache is appended bit for bit as on the exact path, so decode, set steps, evals below 64
+                                        rows, debug-dump evals and other head sizes are unaffected (the exact kernels, the same
+                                        bits).  Accepted on every file type; independent of and combinable with FAST_PREFILL and
+                                        FAST_DENSE; stage handles of a pipeline inherit it.  Like a FAST_PREFILL handle, a flagged
+                                        handle takes llamahip_eval_multi's per-slot loops and shares no prefixes in the scheduler
+                                        (DESIGN.md 12.36).  Never the default, never used for a parity claim. */
+
 /* ---- the drop-in boundary ------------------------------------------------------------------ */
 
 /* Replaces llama_model_load(fname, model, vocab, n_ctx, &error)  (.mm:98).
@@ -1367,6 +1380,17 @@ int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const flo
 int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
                           int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,
                           void *wo_operand, int32_t *path_taken, char *err, size_t err_cap);
+/* The opt-in fused attention of long evals (what a LLAMAHIP_FLAG_FAST_ATTN handle runs for >= 64 rows) alone: k_rope_kv, then k_flash_attn
+ * (+ k_flash_combine where the keys are split).  NOT the reference's arithmetic (csrc/flash_attn.hip states it).  Operand conventions are
+ * llamahip_op_attention's: qkv [N][3 d]; Kc / Vc [n_ctx][d] copied to the device and back whole (rows n_past .. n_past + N - 1 come back
+ * appended, bit for bit as llamahip_op_attention appends them; the kernel never loads a row at or past n_past + N); merged [N][merged_stride]
+ * copied both ways whole (floats d .. merged_stride - 1 of a row keep the caller's bits).  tile: 64 or 128 queries per workgroup, key_splits
+ * 1 .. 8 workgroups per (head, query tile); 0 = the plan's choice (llamahip_debug_flash_attn_plan).  *tile_taken / *splits_taken (may be NULL)
+ * report the launch.  Refused before any device is touched, the limit named: head size d / H != 128, N < 2, n_past + N > n_ctx,
+ * merged_stride < d, a tile that is not an instance, key_splits beyond 8. */
+int llamahip_op_flash_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
+                                int32_t tile, int32_t key_splits, float *merged, int32_t merged_stride,
+                                int32_t *tile_taken, int32_t *splits_taken, char *err, size_t err_cap);
 /* The attention of llamahip_eval_multi's pass on caller-supplied operands: R rows of several KV slots through the row-table kernels
  * (rows_attn.hip: k_rope_kv_rows, then k_rows_scores + k_rows_pv over all R rows).  qkv [R][3d] un-rotated; Kc, Vc [n_slots][n_ctx][d],
  * copied whole both ways; row r belongs to slot row_slot[r], sits at position row_pos[r] and splits row_keys[r] keys over n_threads
@@ -1662,6 +1686,13 @@ int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int3
 int32_t llamahip_debug_dense_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]);
 /* Launches of k_dense_f16_fast since process start.  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_fast_launches(void);
+/* Host only: the launch plan of k_flash_attn for n_rows query rows that end at key n_keys - 1 (n_keys = n_past + n_rows) and n_head heads of
+ * 128 -- out = { queries per workgroup (128 or 64), key splits, query tiles, workgroups in all, dynamic LDS bytes, workspace bytes (0 without
+ * splits) }: the 128-query tile where it still makes 256 workgroups, else the 64-query tile; then the fewest key splits that make 256, at most
+ * the key tiles of 64 there are and at most 8.  Returns 1, 0 where there is no plan (n_rows < 2, n_keys < n_rows, n_head < 1). */
+int32_t llamahip_debug_flash_attn_plan(int32_t n_rows, int32_t n_keys, int32_t n_head, int64_t out[6]);
+/* Launches of k_flash_attn and k_flash_combine since process start.  Tests and measurement tooling. */
+int64_t llamahip_debug_flash_attn_launches(void);
 /* Q4_1 mat-muls per kernel since process start: out[0 .. 1] = { k_q41_chain, k_q41_mm } (at most `cap` entries are written); returns 2.
  * One count per mat-mul, however many row tiles it launched.  Tests and measurement tooling. */
 int32_t llamahip_debug_q41_paths(int64_t *out, int32_t cap);

@@ -318,6 +318,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_dense_fast_plan.restype = i32
     L.llamahip_debug_dense_fast_launches.argtypes = []
     L.llamahip_debug_dense_fast_launches.restype = C.c_int64
+    L.llamahip_op_flash_attention.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, cp, sz]
+    L.llamahip_debug_flash_attn_plan.argtypes = [i32, i32, i32, vp]
+    L.llamahip_debug_flash_attn_plan.restype = i32
+    L.llamahip_debug_flash_attn_launches.argtypes = []
+    L.llamahip_debug_flash_attn_launches.restype = C.c_int64
     L.llamahip_debug_dense_force.argtypes = [i32]
     L.llamahip_op_mul_mat_q4_1.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
     L.llamahip_debug_q41_paths.argtypes = [vp, i32]
@@ -443,6 +448,19 @@ def dense_fast_plan(m: int, k: int, n_rows: int):
 def dense_fast_launches() -> int:
     """Launches of k_dense_f16_fast since process start (llamahip_debug_dense_fast_launches)."""
     return int(lib().llamahip_debug_dense_fast_launches())
+
+
+def flash_attn_plan(n_rows: int, n_keys: int, n_head: int):
+    """Host-only: the launch plan of the opt-in fused attention k_flash_attn (llamahip_debug_flash_attn_plan) for n_rows query rows that end at
+    key n_keys - 1 (n_keys = n_past + n_rows) and n_head heads of 128: a dict, or None where there is no plan."""
+    a = np.zeros(6, np.int64)
+    rc = lib().llamahip_debug_flash_attn_plan(n_rows, n_keys, n_head, a.ctypes.data_as(C.c_void_p))
+    return dict(zip(("tile", "key_splits", "query_tiles", "workgroups", "lds_bytes", "ws_bytes"), (int(x) for x in a))) if rc else None
+
+
+def flash_attn_launches() -> int:
+    """Launches of k_flash_attn and k_flash_combine since process start (llamahip_debug_flash_attn_launches)."""
+    return int(lib().llamahip_debug_flash_attn_launches())
 
 
 def dense_mfma_launches() -> int:
@@ -1926,6 +1944,30 @@ def op_mul_mat_f16_fast(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int 
     err = C.create_string_buffer(1024)
     _check(lib().llamahip_op_mul_mat_f16_fast(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
     return y
+
+
+FAST_ATTN = 64       # LLAMAHIP_FLAG_FAST_ATTN: opt-in, the attention of evals of >= 64 rows (head size 128) in one fused fp16 matrix-core launch (not the reference's arithmetic)
+
+
+def op_flash_attention(qkv: np.ndarray, H: int, n_past: int, Kc: np.ndarray, Vc: np.ndarray, tile: int = 0, key_splits: int = 0,
+                       merged_stride: int | None = None, merged_init=None):
+    """The opt-in fused attention alone (llamahip_op_flash_attention): qkv f32 [N, 3d] un-rotated, Kc / Vc f32 [n_ctx, d] (updated in place: the
+    device's whole copy comes back).  tile 64 / 128 and key_splits 1 .. 8, 0: the plan's choice.  Returns (merged f32 [N, merged_stride] --
+    merged_init, default NaN, where nothing was written --, the tile taken, the key splits taken)."""
+    qkv = np.ascontiguousarray(qkv, np.float32)
+    N, d3 = qkv.shape
+    d = d3 // 3
+    for a in (Kc, Vc):
+        if a.dtype != np.float32 or not a.flags.c_contiguous or a.ndim != 2 or a.shape[1] != d or a.shape[0] != Kc.shape[0]:
+            raise ValueError("Kc / Vc must be C-contiguous float32 [n_ctx, d]")
+    ms = d if merged_stride is None else int(merged_stride)
+    merged = np.full((N, max(ms, 0)), np.nan, np.float32) if merged_init is None else np.array(merged_init, np.float32, order="C").reshape(N, ms)
+    tt, st = C.c_int32(-1), C.c_int32(-1)
+    err = C.create_string_buffer(1024)
+    rc = lib().llamahip_op_flash_attention(_ptr(qkv), N, d, int(H), int(n_past), Kc.shape[0], _ptr(Kc), _ptr(Vc), int(tile), int(key_splits),
+                                           _ptr(merged), ms, C.byref(tt), C.byref(st), err, len(err))
+    _check(rc, err)
+    return merged, tt.value, st.value
 
 
 Q41_PATHS = ("auto", "chain", "lane")      # LLAMAHIP_Q41_* of llamahip.h, in order

@@ -2589,6 +2589,7 @@ hipError_t init_kernel_attrs() {
     if ((e = init_attrs_gemv_set()) != hipSuccess) return e;
     if ((e = init_attrs_rows_attn()) != hipSuccess) return e;
     if ((e = init_attrs_dense()) != hipSuccess) return e;
+    if ((e = init_attrs_flash_attn()) != hipSuccess) return e;
     return init_attrs_prompt_attn();
 }
 

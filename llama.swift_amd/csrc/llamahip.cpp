@@ -554,7 +554,24 @@ int ensure_attn_ws(llamahip_model *m, int N, char *err, size_t err_cap) {
     attn_ws_shape(w, m->hp.n_ctx);
     const AttnWsBytes b = attn_ws_bytes(w, m->hp.n_head);
     HIP_TRY(m->own.alloc_all({ { &w.S, b.S }, { &w.pmax, b.pmax }, { &w.inv, b.inv }, { &w.part, b.part } }), LLAMAHIP_ERR_PREDICT);
+    // opt-in (LLAMAHIP_FLAG_FAST_ATTN): the key-split workspace of k_flash_attn, sized for every plan the rule can make
+    if (m->flags & LLAMAHIP_FLAG_FAST_ATTN) HIP_TRY(m->own.alloc_all({ { &w.flash, FLASH_WS_CAP_BYTES } }), LLAMAHIP_ERR_PREDICT);
     return 0;
+}
+
+// a handle whose long prompt rows make no parity claim (either opt-in fast prompt path): per-slot loops, no shared prefixes
+static bool fast_prompt_rows(const llamahip_model *m) { return (m->flags & (LLAMAHIP_FLAG_FAST_PREFILL | LLAMAHIP_FLAG_FAST_ATTN)) != 0; }
+
+// The attention of a multi-row eval that is not a debug dump: on a LLAMAHIP_FLAG_FAST_ATTN handle, evals of >= FLASH_MIN_ROWS rows that would take
+// the exact matrix-core chain (ATTN_PATH_MFMA) run k_flash_attn instead -- NOT the reference's arithmetic (flash_attn.hip); chunk and n_threads
+// only shape the exact chain's V*P key split and do not enter.  Everything else is launch_attn, launch for launch what an unflagged handle runs.
+static hipError_t launch_attn_or_flash(llamahip_model *m, const float *Kl, const float *Vl, int n_past, int N, int nth, int chunk, hipStream_t st) {
+    const int d = m->hp.n_embd, H = m->hp.n_head;
+    if ((m->flags & LLAMAHIP_FLAG_FAST_ATTN) && N >= FLASH_MIN_ROWS && m->attn_ws.flash && attn_path_pick(&m->attn_ws, N, d / H, n_past + N, nth) == ATTN_PATH_MFMA) {
+        const FlashAttnPlan p = flash_attn_plan(N, n_past + N, H);
+        if (p.ok && p.ws_bytes <= FLASH_WS_CAP_BYTES) return launch_flash_attn(p, m->qr, Kl, Vl, m->merged, d, n_past, N, d, H, m->attn_ws.flash, st);
+    }
+    return launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, chunk);
 }
 
 // a pinned, device-mapped host block and its device alias: both or neither
@@ -666,7 +683,7 @@ int forward_dense(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
             HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, m->merged, m->qa1_A, m->qa1_d, m->T_exp, p.state, st, m->d_attn_sync, m->d_fault), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_rope_kv(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, n_past, N, st), LLAMAHIP_ERR_PREDICT);                             // .mm:586-611
-            HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, nullptr, nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, p.chunk), LLAMAHIP_ERR_PREDICT); // .mm:614-646
+            HIP_TRY(launch_attn_or_flash(m, Kl, Vl, n_past, N, nth, p.chunk, st), LLAMAHIP_ERR_PREDICT);                                             // .mm:614-646
         }
         HIP_TRY(prep_mm(L.dwo, EPI_RESID, PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->x1, d, m->x, d), LLAMAHIP_ERR_PREDICT);                          // .mm:649-654
         HIP_TRY(prep_mm(L.dw13, EPI_STORE, PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->gu, 2L * F, nullptr, 0), LLAMAHIP_ERR_PREDICT);                  // .mm:660-675
@@ -849,7 +866,8 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
             // the merged rows for wo (scores scratch: the many-row path's score matrix)
             HIP_TRY(launch_attn_short(m->qr, Kl, Vl, m->attn_ws.S, nullptr, m->qa_A, m->qa_d, n_past, N, d, H, C, nth, m->T_exp, st, chunk), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
         } else {
-        HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, dmp ? m->dbg_p : nullptr, dmp ? m->dbg_kqv : nullptr, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, chunk), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
+        if (dmp) HIP_TRY(launch_attn(m->qr, Kl, Vl, m->merged, m->dbg_p, m->dbg_kqv, n_past, N, d, H, nth, m->T_exp, &m->attn_ws, st, chunk), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
+        else HIP_TRY(launch_attn_or_flash(m, Kl, Vl, n_past, N, nth, chunk, st), LLAMAHIP_ERR_PREDICT);
         if (dmp) {
             if (!sink->put(6, m->dbg_p, (int64_t) H * N * (n_past + N))) goto dump_fail;
             if (!sink->put(7, m->dbg_kqv, (int64_t) N * d)) goto dump_fail;
@@ -2705,7 +2723,7 @@ static int rows_stage_enqueue(llamahip_model *st, int n_threads, const RowsPass 
 // head size the table kernels take (llamahip_eval_multi and the scheduler's mixed pass share the rule)
 static bool rows_pass_applies(llamahip_model *m) {
     const int dh = m->hp.n_embd / std::max(m->hp.n_head, 1);
-    return !first_of(m)->dense && !(m->flags & LLAMAHIP_FLAG_FAST_PREFILL) && dh % 32 == 0 && dh <= 256;
+    return !first_of(m)->dense && !fast_prompt_rows(m) && dh % 32 == 0 && dh <= 256;
 }
 // the pass's row table and its short / long segment counts, from rp's segments (slots, n_past, n_tokens, chunk, R set by the caller)
 static int rows_pass_build(RowsPass &rp, int n_ctx) {
@@ -4641,7 +4659,7 @@ int sched_handle_info(const llamahip_model *m, SchedHandleInfo *out, char *err, 
     const int rc = decode_handle_check(m, "llamahip_sched_new", err, err_cap);
     if (rc) return rc;
     const llamahip_model *first = m->stages.empty() ? m : m->stages[0];
-    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq, (first->flags & LLAMAHIP_FLAG_FAST_PREFILL) ? 1 : 0, m->stages.empty() ? 0 : 1 };
+    *out = { m->hp.n_ctx, m->hp.n_vocab, first->n_seq, fast_prompt_rows(first) ? 1 : 0, m->stages.empty() ? 0 : 1 };
     return 0;
 }
 int sched_sampler_check(double repeat_penalty, int32_t top_k, double top_p, double temp, char *err, size_t err_cap) {
@@ -5377,6 +5395,17 @@ int32_t llamahip_debug_dense_fast_plan(int32_t m, int32_t k, int32_t n_rows, int
 }
 
 int64_t llamahip_debug_dense_fast_launches(void) { return g_dense_fast_launches; }
+
+int32_t llamahip_debug_flash_attn_plan(int32_t n_rows, int32_t n_keys, int32_t n_head, int64_t out[6]) {
+    if (!out) return 0;
+    const FlashAttnPlan p = flash_attn_plan(n_rows, n_keys, n_head);
+    if (!p.ok) return 0;
+    const int64_t o[6] = { p.tile, p.ks, p.grid_x, (int64_t) p.grid_x * p.grid_y * p.grid_z, p.lds, (int64_t) p.ws_bytes };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_flash_attn_launches(void) { return g_flash_attn_launches; }
 
 int32_t llamahip_debug_dense_force(int32_t path) {
     if (path != 0 && path != LLAMAHIP_DENSE_MM && path != LLAMAHIP_DENSE_MFMA) return -1;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "dec_attn_plan.h"
+#include "flash_attn_plan.h"
 #include "q41_plan.h"
 #include "set_plan.h"
 
@@ -117,6 +118,14 @@ hipError_t init_attrs_dense_fast();
 // xp: the N prepared rows launch_dense_act / launch_dense_perm_act leave for f16 weights
 hipError_t launch_dense_f16_fast(const DMat &w, int epi, const float *xp, int N, float *y, long y_stride,
                                  const float *resid, long resid_stride, hipStream_t st);
+// k_flash_attn (flash_attn.hip, plan: flash_attn_plan.h): the opt-in fused causal attention of long evals on the fp16 matrix cores,
+// LLAMAHIP_FLAG_FAST_ATTN handles' evals of >= FLASH_MIN_ROWS rows that would take ATTN_PATH_MFMA, and llamahip_op_flash_attention.  NOT the
+// reference's arithmetic.  One launch (+ k_flash_combine where the plan splits the keys); ws: p.ws_bytes of workspace (AttnWs::flash)
+constexpr int FLASH_MIN_ROWS = 64;                   // the flag's row threshold
+extern long g_flash_attn_launches;                   // launches of k_flash_attn and k_flash_combine (process-wide; tests)
+hipError_t init_attrs_flash_attn();
+hipError_t launch_flash_attn(const FlashAttnPlan &p, const float *qr, const float *Kc, const float *Vc, float *merged, long merged_stride,
+                             int n_past, int N, int d, int H, float *ws, hipStream_t st);
 hipError_t launch_q41_repack(const uint8_t *raw_rows, DMat &w, hipStream_t st);
 // Q4_1 mat-mul: the paths, counters and k_q41_chain's launch plan are q41_plan.h's (host-only); scratch: N * K floats, the expanded operand
 hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
@@ -233,6 +242,7 @@ hipError_t launch_rope_kv(const float *qkv, long qkv_stride, int d, int dh, cons
 // workspace of the many-row prompt attention (k_attnq_*): scores [H][T_cap][NB] fp32 + per-query max / 1/sum
 struct AttnWs {
     float *S = nullptr, *pmax = nullptr, *inv = nullptr, *part = nullptr;   // part: [nth_cap][H][NB][128]
+    float *flash = nullptr;                                                 // FLASH_WS_CAP_BYTES of k_flash_attn's key-split workspace (LLAMAHIP_FLAG_FAST_ATTN handles only)
     int NB = 0;        // query rows per batch (multiple of 64)
     int T_cap = 0;     // keys the workspace can hold
     int KS_cap = 0;    // key slices of the score pass

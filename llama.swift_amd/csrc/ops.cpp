@@ -519,6 +519,49 @@ int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int
     return LLAMAHIP_OK;
 }
 
+// the opt-in fused attention of long evals (k_rope_kv, then k_flash_attn [+ k_flash_combine]) on caller-supplied q|k|v rows and caches: see llamahip.h
+int llamahip_op_flash_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
+                                int32_t tile, int32_t key_splits, float *merged, int32_t merged_stride,
+                                int32_t *tile_taken, int32_t *splits_taken, char *err, size_t err_cap) {
+    const char *fn = "llamahip_op_flash_attention";
+    if (!qkv || !Kc || !Vc || !merged || d < 1 || H < 1 || d % H != 0 || n_past < 0) {
+        set_err(err, err_cap, "%s: bad arguments (qkv, Kc, Vc, merged not NULL; d %d a multiple of H %d, n_past %d >= 0)", fn, d, H, n_past);
+        return LLAMAHIP_ERR_PREDICT;
+    }
+    const int dh = d / H, T = n_past + N;
+    if (dh != FLASH_HEAD) { set_err(err, err_cap, "%s: head size %d: the kernel takes head size %d", fn, dh, FLASH_HEAD); return LLAMAHIP_ERR_PREDICT; }
+    if (N < 2) { set_err(err, err_cap, "%s: N %d: the kernel takes N >= 2 rows (one row is the decode step)", fn, N); return LLAMAHIP_ERR_PREDICT; }
+    if (T > n_ctx) { set_err(err, err_cap, "%s: T = n_past + N = %d > n_ctx %d", fn, T, n_ctx); return LLAMAHIP_ERR_PREDICT; }
+    if (merged_stride < d) { set_err(err, err_cap, "%s: merged_stride %d < d %d", fn, merged_stride, d); return LLAMAHIP_ERR_PREDICT; }
+    if (tile != 0 && tile != 64 && tile != 128) { set_err(err, err_cap, "%s: tile %d is not an instance (64 or 128 queries; 0: the plan's choice)", fn, tile); return LLAMAHIP_ERR_PREDICT; }
+    if (key_splits < 0 || key_splits > FLASH_KS_CAP) { set_err(err, err_cap, "%s: key_splits %d outside 0 .. %d (0: the plan's choice)", fn, key_splits, FLASH_KS_CAP); return LLAMAHIP_ERR_PREDICT; }
+    const FlashAttnPlan p = flash_attn_plan(N, T, H, tile, key_splits);
+    if (!p.ok) { set_err(err, err_cap, "%s: no plan for N %d, T %d, H %d", fn, N, T, H); return LLAMAHIP_ERR_PREDICT; }
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    const size_t cache_b = (size_t) n_ctx * d * 4, qr_b = (size_t) N * d * 4, mbytes = (size_t) N * merged_stride * 4;
+    const std::vector<double> tab = rope_table(n_ctx, dh);
+    Scratch s;
+    hipStream_t st = s.stream();
+    float *d_qr = s.alloc<float>(qr_b / 4), *d_m = s.alloc((size_t) N * merged_stride, merged);      // (the floats between d and merged_stride keep the caller's bits)
+    float *d_ws = p.ws_bytes ? s.alloc<float>(p.ws_bytes / 4) : nullptr;
+    // the op's own workspace, every byte NaN (0xFF): a read of something the launch did not write shows in the result
+    s.fill(d_qr, 0xFF, qr_b);
+    if (d_ws) s.fill(d_ws, 0xFF, p.ws_bytes);
+    float *d_qkv = s.alloc((size_t) N * 3 * d, qkv), *d_K = s.alloc(cache_b / 4, Kc), *d_V = s.alloc(cache_b / 4, Vc);
+    double *d_tab = s.alloc(tab.size(), tab.data());
+    if (s.ok()) s.check(launch_rope_kv(d_qkv, 3L * d, d, dh, d_tab, d_qr, d_K, d_V, n_past, N, st));
+    if (s.ok()) s.check(launch_flash_attn(p, d_qr, d_K, d_V, d_m, merged_stride, n_past, N, d, H, d_ws, st));
+    s.download(Kc, d_K, cache_b);
+    s.download(Vc, d_V, cache_b);
+    s.download(merged, d_m, mbytes);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    if (tile_taken) *tile_taken = p.tile;
+    if (splits_taken) *splits_taken = p.ks;
+    return LLAMAHIP_OK;
+}
+
 static_assert(LLAMAHIP_DEC_ATTN_X == 0 && LLAMAHIP_DEC_ATTN_STREAM == 1 && LLAMAHIP_DEC_ATTN_DMA == 2, "llamahip.h names the one-row hand-off paths");
 static_assert(LLAMAHIP_DEC_KERNEL_PV_BLK == DEC_ATTN_PV_BLK && LLAMAHIP_DEC_KERNEL_X == DEC_ATTN_X && LLAMAHIP_DEC_KERNEL_PV_STREAM == DEC_ATTN_PV_STREAM &&
               LLAMAHIP_DEC_KERNEL_PV_DMA == DEC_ATTN_PV_DMA, "... and mirrors dec_attn_plan.h's kernels");
