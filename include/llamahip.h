@@ -123,6 +123,21 @@ typedef struct llamahip_opts {
                                         handle takes llamahip_eval_multi's per-slot loops and shares no prefixes in the scheduler
                                         (DESIGN.md 12.36).  Never the default, never used for a parity claim. */
 
+#define LLAMAHIP_FLAG_FAST_Q41 128 /* OPT-IN, NOT the reference's arithmetic: on a Q4_1 model file, multi-token evals of >= 64 rows
+                                        run wq|wk|wv, wo, w1|w3, w2 and the all-rows lm head on the fp16 matrix cores
+                                        (k_q41_act_f16 + k_q41_fast, csrc/q41_fast.hip) instead of the exact k_q41_chain.  Same
+                                        weights, the same activation codes (quantize_row_q4_1, bit for bit); both operands
+                                        expanded in fp32 as on the exact path, then narrowed once to fp16 (round to nearest even,
+                                        saturating), every product exact; ONE fp32 sum per output in the matrix core's order
+                                        instead of the reference's ordered chain, so a mat-mul agrees to two 2^-11 narrowings
+                                        and rounding only (where the measurements are).
+                                        Decode and evals below 64 rows are unaffected (the exact kernels, the same bits); f16,
+                                        f32 and Q4_0 files accept the flag and ignore it, as FAST_DENSE ignores Q4_1 files.
+                                        Combinable with FAST_ATTN; stage handles of a pipeline inherit it.  Q4_1 handles already
+                                        take the per-slot loops of llamahip_eval_multi, scoring, embeddings and the scheduler:
+                                        those entry points need no code for the flag.  Never the default, never used for a
+                                        parity claim. */
+
 /* ---- the drop-in boundary ------------------------------------------------------------------ */
 
 /* Replaces llama_model_load(fname, model, vocab, n_ctx, &error)  (.mm:98).
@@ -1355,6 +1370,16 @@ int llamahip_op_mul_mat_f16_fast(const void *w, int32_t M, int32_t K, const floa
 #define LLAMAHIP_Q41_LANE  2
 int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                              float *y, int32_t y_stride, int32_t path, int32_t *path_taken, char *err, size_t err_cap);
+/* The opt-in fp16 matrix-core mat-mul of Q4_1 files (k_q41_act_f16 + k_q41_fast, what a LLAMAHIP_FLAG_FAST_Q41 handle runs for >= 64 rows)
+ * alone: y[n][m] = sum_k fp16(W[m][k]) * fp16(a[n][k]) (+ resid[n][m], added last), W[m][k] = fl(fl(d0 * q) + m0) and a = the expansion
+ * fl(fl(d1 * code) + m1) of quantize_row_q4_1(x[n]) as on the exact path, both narrowed once (round to nearest even, saturating at
+ * +-65504), every product exact, ONE fp32 sum per output in an order the kernel does not promise -- NOT bit for bit ggml_vec_dot_q4_1; held
+ * to |y - y64| <= gamma(K + 1) (sum |w a| + |resid|) + one ulp over the narrowed operands instead.  Operand conventions are
+ * llamahip_op_mul_mat_q4_1's: w_q4_1 M rows in file layout, x [N][K], resid [N][M] or NULL, y [N][y_stride] copied to the device and back
+ * whole.  Any N >= 1 (a model handle sends >= 64 rows).  Two launches.  Refused before any device is touched, the limit named: K not a
+ * positive multiple of 32, N < 1, M < 1, y_stride < M, w_q4_1 / x / y NULL, M past 65535 rows of workgroups. */
+int llamahip_op_mul_mat_q4_1_fast(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                  float *y, int32_t y_stride, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -1702,6 +1727,12 @@ int32_t llamahip_debug_q41_paths(int64_t *out, int32_t cap);
  * n_rows % 16 rows is a launch of its own on the plan of that row count.  Returns 1, 0 where the kernel does not take the shape (K not a
  * positive multiple of 32, m or n_rows < 1), -1 where the plan names an instance that was never compiled. */
 int32_t llamahip_debug_q41_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[8]);
+/* Host only: the launch plan of k_q41_fast for an M x K Q4_1 matrix and n_rows activation rows -- out = { grid x (row tiles), grid y
+ * (weight-row tiles), activation rows per tile, weight rows per tile, K tile, dynamic LDS bytes }.  Returns 1, or 0 where the kernel does
+ * not take the shape (K no positive multiple of 32, n_rows < 1, more than 65535 rows of workgroups). */
+int32_t llamahip_debug_q41_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]);
+/* Launches of k_q41_fast since process start.  Tests and measurement tooling. */
+int64_t llamahip_debug_q41_fast_launches(void);
 /* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_mfma_launches(void);
 /* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more

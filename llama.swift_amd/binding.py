@@ -325,6 +325,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_flash_attn_launches.restype = C.c_int64
     L.llamahip_debug_dense_force.argtypes = [i32]
     L.llamahip_op_mul_mat_q4_1.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, cp, sz]
+    L.llamahip_op_mul_mat_q4_1_fast.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, cp, sz]
+    L.llamahip_debug_q41_fast_plan.argtypes = [i32, i32, i32, vp]
+    L.llamahip_debug_q41_fast_plan.restype = i32
+    L.llamahip_debug_q41_fast_launches.argtypes = []
+    L.llamahip_debug_q41_fast_launches.restype = C.c_int64
     L.llamahip_debug_q41_paths.argtypes = [vp, i32]
     L.llamahip_debug_q41_paths.restype = i32
     L.llamahip_debug_q41_plan.argtypes = [i32, i32, i32, vp]
@@ -435,6 +440,19 @@ def dense_mfma_plan(m: int, k: int, wtype: int, n_rows: int):
     if rc < 0:
         raise LlamaHipError(rc, f"dense_mfma_plan({m}, {k}, wtype={wtype}, n_rows={n_rows}): the plan {a.tolist()} names a kernel instance that does not exist")
     return dict(zip(("grid", "threads", "tile_rows", "tile_cols", "lds_bytes", "auto"), (int(x) for x in a))) if rc else None
+
+
+def q41_fast_plan(m: int, k: int, n_rows: int):
+    """Host-only: the launch plan of the opt-in fp16 matrix-core Q4_1 mat-mul k_q41_fast (llamahip_debug_q41_fast_plan) for n_rows rows
+    against an m x k Q4_1 matrix: a dict, or None where the kernel does not take the shape."""
+    a = np.zeros(6, np.int64)
+    rc = lib().llamahip_debug_q41_fast_plan(m, k, n_rows, a.ctypes.data_as(C.c_void_p))
+    return dict(zip(("grid_x", "grid_y", "tile_rows", "tile_cols", "k_tile", "lds_bytes"), (int(x) for x in a))) if rc else None
+
+
+def q41_fast_launches() -> int:
+    """Launches of k_q41_fast since process start (llamahip_debug_q41_fast_launches)."""
+    return int(lib().llamahip_debug_q41_fast_launches())
 
 
 def dense_fast_plan(m: int, k: int, n_rows: int):
@@ -1995,6 +2013,30 @@ def op_mul_mat_q4_1(w: np.ndarray, x: np.ndarray, resid=None, path: str = "auto"
     rc = lib().llamahip_op_mul_mat_q4_1(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, code, C.byref(taken), err, len(err))
     _check(rc, err)
     return y, Q41_PATHS[taken.value]
+
+
+FAST_Q41 = 128       # LLAMAHIP_FLAG_FAST_Q41: opt-in, Q4_1 files' evals of >= 64 rows on the fp16 matrix cores (not the reference's arithmetic)
+
+
+def op_mul_mat_q4_1_fast(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int | None = None, y_init=None, K: int | None = None):
+    """The opt-in fp16 matrix-core mat-mul of Q4_1 files alone (llamahip_op_mul_mat_q4_1_fast): operands as op_mul_mat_q4_1's (w uint8
+    [M, K/32 * 24] in file layout, x f32 [N, K], resid f32 [N, M] or None).  Returns y f32 [N, y_stride], the whole buffer as the device
+    left it -- y_init (default: NaN everywhere) is what columns M .. y_stride - 1 keep.  K overrides the row length the shape of w implies
+    (refusal tests)."""
+    w = np.ascontiguousarray(w, np.uint8)
+    M, rb = w.shape
+    x = np.ascontiguousarray(x, np.float32)
+    if K is None:
+        K = rb // 24 * 32
+        x = x.reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_mul_mat_q4_1_fast(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
+    return y
 
 
 ATTN_PATHS = ("auto", "mfma", "row", "short", "dec", "dec_stream")      # LLAMAHIP_ATTN_* of llamahip.h, in order

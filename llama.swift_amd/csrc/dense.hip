@@ -1176,7 +1176,8 @@ hipError_t init_attrs_dense() {
     LH_Q41_INSTANCES(LH_Q41_ATTR)          // k_q41_chain's two slab buffers: up to 128 KB
 #undef LH_Q41_ATTR
 #undef LH_ATTR
-    return init_attrs_dense_fast();
+    const hipError_t e = init_attrs_dense_fast();
+    return e != hipSuccess ? e : init_attrs_q41_fast();
 }
 
 static hipError_t go_q41_chain(const Q41Plan &p, int grid_y, int n_base, const DMat &w, int epi, int N, float *y, long y_stride,

@@ -652,6 +652,9 @@ static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int m
         if (e != hipSuccess) return e;
         src = m->dbg_y; src_stride = K;
     }
+    // opt-in (LLAMAHIP_FLAG_FAST_Q41): long evals of a Q4_1 file on the fp16 matrix cores, the same activation codes, operands narrowed to fp16
+    if ((m->flags & LLAMAHIP_FLAG_FAST_Q41) && rows >= Q41_FAST_MIN_ROWS && q41_fast_plan(w.M, K, rows).ok)
+        return launch_q41_fast(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
     return launch_dense_mm(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
 }
 
@@ -5373,6 +5376,17 @@ int32_t llamahip_debug_q41_plan(int32_t m, int32_t k, int32_t n_rows, int64_t ou
     for (int i = 0; i < 8; i++) out[i] = o[i];
     return q41_plan_has_kernel(p) ? 1 : -1;
 }
+
+int32_t llamahip_debug_q41_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]) {
+    if (!out) return 0;
+    const Q41FastPlan p = q41_fast_plan(m, k, n_rows);
+    if (!p.ok) return 0;
+    const int64_t o[6] = { p.grid_x, p.grid_y, p.tile_rows, p.tile_cols, p.k_tile, p.lds };
+    for (int i = 0; i < 6; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_q41_fast_launches(void) { return g_q41_fast_launches; }
 
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
     if (!out) return 0;

@@ -130,6 +130,10 @@ hipError_t launch_q41_repack(const uint8_t *raw_rows, DMat &w, hipStream_t st);
 // Q4_1 mat-mul: the paths, counters and k_q41_chain's launch plan are q41_plan.h's (host-only); scratch: N * K floats, the expanded operand
 hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
                          const float *resid, long resid_stride, hipStream_t st, float *scratch, int path, int *path_taken);
+// k_q41_act_f16 + k_q41_fast (q41_fast.hip; plan, threshold and counter: q41_plan.h): x N fp32 rows (x_stride a multiple of 4), scratch N * K halves
+hipError_t init_attrs_q41_fast();
+hipError_t launch_q41_fast(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
+                           const float *resid, long resid_stride, hipStream_t st, float *scratch);
 bool dense_prep_applies(int wtype, int mode, int K);
 hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride,
                              int K, int N, float *scratch, const uint16_t *T_silu, hipStream_t st);

@@ -32,4 +32,15 @@ bool q41_plan_has_kernel(const Q41Plan &p);
 // llamahip_op_mul_mat_q4_1's refusals, before any device is touched: 0, or -1 with the limit named in err
 int q41_op_check(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *y, int32_t y_stride, int32_t path, char *err, size_t err_cap);
 
+// k_q41_fast (q41_fast.hip; plan: q41_fast_plan.cpp): the opt-in fp16 matrix-core mat-mul of Q4_1 files, LLAMAHIP_FLAG_FAST_Q41 handles' evals of
+// >= Q41_FAST_MIN_ROWS rows and llamahip_op_mul_mat_q4_1_fast.  NOT the reference's arithmetic.  The plan: ok = the kernel takes the shape;
+// grid (grid_x, grid_y) workgroups of 256 threads, each tile_rows activation rows x tile_cols weight rows, K in tiles of k_tile; lds = dynamic
+// LDS bytes
+struct Q41FastPlan { int ok, grid_x, grid_y, tile_rows, tile_cols, k_tile, lds; };
+constexpr int Q41_FAST_MIN_ROWS = 64;                // the flag's row threshold
+Q41FastPlan q41_fast_plan(int M, int K, int N);
+extern long g_q41_fast_launches;                     // launches of k_q41_fast (process-wide; tests)
+// llamahip_op_mul_mat_q4_1_fast's refusals, before any device is touched: 0, or -1 with the limit named in err
+int q41_fast_op_check(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *y, int32_t y_stride, char *err, size_t err_cap);
+
 }  // namespace lh

@@ -1785,6 +1785,34 @@ int main(int argc, char **argv) {
         }
         EXPECT(q41_op_check(&wq, 8, 64, &xy, 17, &xy, 8, 2, err, sizeof(err)) == 0);
         printf("host_sanitize: Q4_1 mat-mul host half: %d plans, %zu refusals\n", plans, sizeof(bad) / sizeof(bad[0]));
+        // the opt-in matrix-core mat-mul's host half (q41_fast_plan.cpp): a compiled instance, a covering grid and LDS bytes a CU has at
+        // every shape and row count, and llamahip_op_mul_mat_q4_1_fast's refusals the same way
+        int fast_plans = 0;
+        for (auto &mk : shapes)
+            for (int N : { 1, 16, 63, 64, 65, 70, 127, 128, 129, 512, 1048560 }) {
+                const Q41FastPlan p = q41_fast_plan(mk.first, mk.second, N);
+                const bool inst = (p.tile_rows == 128 && p.tile_cols == 128 && p.k_tile == 64) || (p.tile_rows == 64 && p.tile_cols == 64 && p.k_tile == 128)
+                               || (p.tile_rows == 64 && p.tile_cols == 16 && p.k_tile == 256);
+                EXPECT(p.ok && inst && p.lds == 2 * (p.tile_rows + p.tile_cols) * (p.k_tile + 8) * 2 && p.lds <= 160 * 1024);
+                EXPECT((int64_t) p.grid_x * p.tile_rows >= N && (int64_t) (p.grid_x - 1) * p.tile_rows < N && (int64_t) p.grid_y * p.tile_cols >= mk.first
+                       && (int64_t) (p.grid_y - 1) * p.tile_cols < mk.first && p.grid_y <= 65535);
+                fast_plans++;
+            }
+        EXPECT(!q41_fast_plan(0, 64, 64).ok && !q41_fast_plan(8, 48, 64).ok && !q41_fast_plan(8, 0, 64).ok && !q41_fast_plan(8, 64, 0).ok);
+        EXPECT(q41_fast_plan(128 * 65535, 32, 1).ok && !q41_fast_plan(128 * 65535 + 1, 32, 1).ok);
+        struct { int32_t M, K, N, ys; const void *w; const char *says; } fbad[] = {
+            { 8, 48, 64, 8, &wq, "K 48 must be a positive multiple of 32" }, { 8, 0, 64, 8, &wq, "K 0 must be" }, { 8, 64, 0, 8, &wq, "N 0 must be >= 1" },
+            { 0, 64, 64, 8, &wq, "M 0 must be >= 1" }, { 8, 64, 64, 7, &wq, "y_stride 7 < M 8" }, { 8, 64, 64, 8, nullptr, "not NULL" },
+            { 128 * 65535 + 1, 32, 1, 128 * 65535 + 1, &wq, "more than 65535 rows of workgroups" },
+        };
+        for (auto &b : fbad) {
+            std::vector<char> e(256, 0), e1(1, 'x');
+            EXPECT(q41_fast_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e.data(), e.size()) == -1 && strstr(e.data(), b.says));
+            EXPECT(q41_fast_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e1.data(), e1.size()) == -1 && e1[0] == 0);
+            EXPECT(q41_fast_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, nullptr, 0) == -1);
+        }
+        EXPECT(q41_fast_op_check(&wq, 8, 64, &xy, 70, &xy, 8, err, sizeof(err)) == 0);
+        printf("host_sanitize: Q4_1 fast mat-mul host half: %d plans, %zu refusals\n", fast_plans, sizeof(fbad) / sizeof(fbad[0]));
     }
     {   // the few-row Q4_0 mat-mul's host half (set_plan.cpp): the plan of every LLaMA matrix at every row count 2 .. 60 and its launch shape,
         // every (nc, cw) pair forced -- admitted or refused with a reason, on exactly sized message buffers -- and what the rule refuses
