@@ -138,6 +138,23 @@ typedef struct llamahip_opts {
                                         those entry points need no code for the flag.  Never the default, never used for a
                                         parity claim. */
 
+#define LLAMAHIP_FLAG_FAST_Q41_DECODE 256 /* OPT-IN, NOT the reference's arithmetic: on a Q4_1 model file, decode steps and evals of
+                                        fewer than 64 rows run wq|wk|wv, wo, w1|w3, w2 and the lm head on the 4-bit integer dot
+                                        instruction (k_q41_act_q + k_q41_dot, csrc/q41_dot.hip) instead of the exact k_q41_chain.
+                                        Same weights, the same activation codes (quantize_row_q4_1, bit for bit), kept as codes:
+                                        per block the exact integer sums of q c, q and c, combined with the four scales in five
+                                        rounded fp32 operations; the block terms are added in a fixed order that depends on K
+                                        alone.  The per-element roundings of the exact path's operands are gone and the order of
+                                        summation differs (where the measurements are).  Deterministic, and a
+                                        mat-mul row's bits do not depend on the rows it is evaluated with: decode_greedy equals
+                                        the loop of one-row evals bit for bit on such a handle, and a 9-row eval nine one-row
+                                        evals wherever the exact attention does (n_threads 1; with more threads the reference's
+                                        own key split follows the row count of an eval).
+                                        Evals of >= 64 rows are unaffected (k_q41_fast with FAST_Q41, else the exact kernel);
+                                        f16, f32 and Q4_0 files accept the flag and ignore it.  Independent of and combinable
+                                        with FAST_Q41 and FAST_ATTN; stage handles of a pipeline inherit it.  Attention, RoPE and
+                                        the KV append stay the exact kernels.  Never the default, never used for a parity claim. */
+
 /* ---- the drop-in boundary ------------------------------------------------------------------ */
 
 /* Replaces llama_model_load(fname, model, vocab, n_ctx, &error)  (.mm:98).
@@ -1380,6 +1397,18 @@ int llamahip_op_mul_mat_q4_1(const void *w_q4_1, int32_t M, int32_t K, const flo
  * positive multiple of 32, N < 1, M < 1, y_stride < M, w_q4_1 / x / y NULL, M past 65535 rows of workgroups. */
 int llamahip_op_mul_mat_q4_1_fast(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                   float *y, int32_t y_stride, char *err, size_t err_cap);
+/* The opt-in integer-dot mat-mul of Q4_1 files (k_q41_act_q + k_q41_dot, what a LLAMAHIP_FLAG_FAST_Q41_DECODE handle runs below 64 rows)
+ * alone: y[n][m] = sum over blocks of fma(d0, fma(d1, S_qc, m1 * S_q), m0 * E) (+ resid[n][m], added last), with q, d0, m0 the codes and
+ * scales of W[m]'s block, c, d1, m1 those of quantize_row_q4_1(x[n]), S_qc = sum q c, S_q = sum q, S_c = sum c exact integers and
+ * E = fma(d1, S_c, 32 m1): sum_k (d0 q + m0)(d1 c + m1) over the un-rounded operands in five roundings per block, the block terms added in
+ * a fixed order that depends on K alone -- NOT bit for bit ggml_vec_dot_q4_1; held to |y - y64| <= gamma(K/32 + 8) mass + one ulp instead
+ * (mass: the absolute values of a block's four parts, + |resid|).  Row n's bits are those of the one-row call on x[n].  Operand conventions
+ * are llamahip_op_mul_mat_q4_1_fast's: w_q4_1 M rows in file layout, x [N][K], resid [N][M] or NULL, y [N][y_stride] copied to the device
+ * and back whole.  Any N >= 1 (a model handle sends 1 .. 63 rows): tiles of 16 rows, a last tile of N % 16 a launch of its own.  Refused
+ * before any device is touched, the limit named: K not a positive multiple of 32, N < 1, M < 1, y_stride < M, w_q4_1 / x / y NULL, N past
+ * 65535 row tiles of 16. */
+int llamahip_op_mul_mat_q4_1_dot(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -1733,6 +1762,13 @@ int32_t llamahip_debug_q41_plan(int32_t m, int32_t k, int32_t n_rows, int64_t ou
 int32_t llamahip_debug_q41_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[6]);
 /* Launches of k_q41_fast since process start.  Tests and measurement tooling. */
 int64_t llamahip_debug_q41_fast_launches(void);
+/* Host only: the launch plan of k_q41_dot for an M x K Q4_1 matrix and n_rows activation rows -- out = { compiled row count of a tile,
+ * threads, grid x (groups of 16 weight rows), grid y (row tiles of 16), K-lanes, blocks per LDS slab, static LDS bytes }; a last tile of
+ * n_rows % 16 rows is a launch of its own on the plan of that row count.  Grid x and K-lanes do not depend on n_rows.  Returns 1, or
+ * 0 where the kernel does not take the shape (K no positive multiple of 32, m or n_rows < 1, more than 65535 row tiles). */
+int32_t llamahip_debug_q41_dot_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[7]);
+/* Mat-muls on k_q41_dot since process start (one per mat-mul, whatever its row tiles).  Tests and measurement tooling. */
+int64_t llamahip_debug_q41_dot_launches(void);
 /* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_mfma_launches(void);
 /* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more

@@ -330,6 +330,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_q41_fast_plan.restype = i32
     L.llamahip_debug_q41_fast_launches.argtypes = []
     L.llamahip_debug_q41_fast_launches.restype = C.c_int64
+    L.llamahip_op_mul_mat_q4_1_dot.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, cp, sz]
+    L.llamahip_debug_q41_dot_plan.argtypes = [i32, i32, i32, vp]
+    L.llamahip_debug_q41_dot_plan.restype = i32
+    L.llamahip_debug_q41_dot_launches.argtypes = []
+    L.llamahip_debug_q41_dot_launches.restype = C.c_int64
     L.llamahip_debug_q41_paths.argtypes = [vp, i32]
     L.llamahip_debug_q41_paths.restype = i32
     L.llamahip_debug_q41_plan.argtypes = [i32, i32, i32, vp]
@@ -453,6 +458,19 @@ def q41_fast_plan(m: int, k: int, n_rows: int):
 def q41_fast_launches() -> int:
     """Launches of k_q41_fast since process start (llamahip_debug_q41_fast_launches)."""
     return int(lib().llamahip_debug_q41_fast_launches())
+
+
+def q41_dot_plan(m: int, k: int, n_rows: int):
+    """Host-only: the launch plan of the opt-in integer-dot Q4_1 mat-mul k_q41_dot (llamahip_debug_q41_dot_plan) for n_rows rows against an
+    m x k Q4_1 matrix: a dict, or None where the kernel does not take the shape."""
+    a = np.zeros(7, np.int64)
+    rc = lib().llamahip_debug_q41_dot_plan(m, k, n_rows, a.ctypes.data_as(C.c_void_p))
+    return dict(zip(("nr", "threads", "grid_x", "grid_y", "klanes", "slab", "lds_bytes"), (int(x) for x in a))) if rc else None
+
+
+def q41_dot_launches() -> int:
+    """Mat-muls on k_q41_dot since process start (llamahip_debug_q41_dot_launches)."""
+    return int(lib().llamahip_debug_q41_dot_launches())
 
 
 def dense_fast_plan(m: int, k: int, n_rows: int):
@@ -2036,6 +2054,29 @@ def op_mul_mat_q4_1_fast(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int
         resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
     err = C.create_string_buffer(1024)
     _check(lib().llamahip_op_mul_mat_q4_1_fast(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
+    return y
+
+
+FAST_Q41_DECODE = 256       # LLAMAHIP_FLAG_FAST_Q41_DECODE: opt-in, Q4_1 files' decode steps and evals below 64 rows on the 4-bit integer dot (not the reference's arithmetic)
+
+
+def op_mul_mat_q4_1_dot(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int | None = None, y_init=None, K: int | None = None):
+    """The opt-in integer-dot mat-mul of Q4_1 files alone (llamahip_op_mul_mat_q4_1_dot): operands and result as op_mul_mat_q4_1_fast's (w
+    uint8 [M, K/32 * 24] in file layout, x f32 [N, K], resid f32 [N, M] or None; y f32 [N, y_stride], the whole buffer as the device left
+    it).  K overrides the row length the shape of w implies (refusal tests)."""
+    w = np.ascontiguousarray(w, np.uint8)
+    M, rb = w.shape
+    x = np.ascontiguousarray(x, np.float32)
+    if K is None:
+        K = rb // 24 * 32
+        x = x.reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_mul_mat_q4_1_dot(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
     return y
 
 

@@ -655,6 +655,9 @@ static hipError_t dense_prep_mm(llamahip_model *m, const DMat &w, int epi, int m
     // opt-in (LLAMAHIP_FLAG_FAST_Q41): long evals of a Q4_1 file on the fp16 matrix cores, the same activation codes, operands narrowed to fp16
     if ((m->flags & LLAMAHIP_FLAG_FAST_Q41) && rows >= Q41_FAST_MIN_ROWS && q41_fast_plan(w.M, K, rows).ok)
         return launch_q41_fast(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
+    // opt-in (LLAMAHIP_FLAG_FAST_Q41_DECODE): decode steps and short evals of a Q4_1 file on the 4-bit integer dot, the same activation codes
+    if ((m->flags & LLAMAHIP_FLAG_FAST_Q41_DECODE) && rows < Q41_FAST_MIN_ROWS && q41_dot_plan(w.M, K, rows).ok)
+        return launch_q41_dot(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
     return launch_dense_mm(w, epi, src, src_stride, rows, out, out_stride, resid, resid_stride, st, m->tmp);
 }
 
@@ -5387,6 +5390,17 @@ int32_t llamahip_debug_q41_fast_plan(int32_t m, int32_t k, int32_t n_rows, int64
 }
 
 int64_t llamahip_debug_q41_fast_launches(void) { return g_q41_fast_launches; }
+
+int32_t llamahip_debug_q41_dot_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[7]) {
+    if (!out) return 0;
+    const Q41DotPlan p = q41_dot_plan(m, k, n_rows);
+    if (!p.ok) return 0;
+    const int64_t o[7] = { p.nr, p.threads, p.grid_x, p.grid_y, p.klanes, p.slab, p.lds };
+    for (int i = 0; i < 7; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_q41_dot_launches(void) { return g_q41_dot_launches; }
 
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
     if (!out) return 0;

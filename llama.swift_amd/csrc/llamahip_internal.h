@@ -134,6 +134,9 @@ hipError_t launch_q41_mm(const DMat &w, int epi, const float *x, long x_stride, 
 hipError_t init_attrs_q41_fast();
 hipError_t launch_q41_fast(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
                            const float *resid, long resid_stride, hipStream_t st, float *scratch);
+// k_q41_act_q + k_q41_dot (q41_dot.hip; plan and counter: q41_plan.h): x N fp32 rows (x_stride a multiple of 4), scratch N * K bytes of records
+hipError_t launch_q41_dot(const DMat &w, int epi, const float *x, long x_stride, int N, float *y, long y_stride,
+                          const float *resid, long resid_stride, hipStream_t st, float *scratch);
 bool dense_prep_applies(int wtype, int mode, int K);
 hipError_t launch_dense_prep(int mode, int wtype, const float *in0, const float *in1, long in_stride, long in1_stride,
                              int K, int N, float *scratch, const uint16_t *T_silu, hipStream_t st);

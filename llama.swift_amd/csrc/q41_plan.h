@@ -43,4 +43,21 @@ extern long g_q41_fast_launches;                     // launches of k_q41_fast (
 // llamahip_op_mul_mat_q4_1_fast's refusals, before any device is touched: 0, or -1 with the limit named in err
 int q41_fast_op_check(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *y, int32_t y_stride, char *err, size_t err_cap);
 
+// k_q41_dot (q41_dot.hip; plan: q41_dot_plan.cpp): the opt-in integer-dot mat-mul of Q4_1 files, LLAMAHIP_FLAG_FAST_Q41_DECODE handles' decode
+// steps and evals below Q41_FAST_MIN_ROWS rows, and llamahip_op_mul_mat_q4_1_dot.  NOT the reference's arithmetic.  The plan: ok = the kernel
+// takes the shape; nr = the compiled row count of a tile (LH_Q41_INSTANCES); grid (grid_x, grid_y) workgroups of `threads` threads, each
+// Q41_DOT_ROWS weight rows x klanes K-lanes (K-lane l adds the terms of blocks l, l + klanes, ... in that order); grid_y row tiles of at
+// most Q41_DOT_TILE (a last tile of N % 16 rows is launched on the plan of that row count); slab = blocks whose activation records are
+// staged in LDS at a time (it follows nr and orders no sum); lds = static LDS bytes.  grid_x and klanes do not depend on N: the bits of a
+// row do not either.
+struct Q41DotPlan { int ok, nr, threads, grid_x, grid_y, klanes, slab, lds; };
+constexpr int Q41_DOT_ROWS = 16, Q41_DOT_KLANES = 16, Q41_DOT_TILE = 16;
+// blocks per LDS slab of the instance of nr rows (whole walks of the 16 K-lanes): how much of the next slab a thread holds in registers --
+// sized so that no instance parks registers in AGPRs or scratch and every one keeps two waves per SIMD or more
+constexpr int q41_dot_slab(int nr) { return nr <= 4 ? 64 : nr <= 8 ? 32 : 16; }
+Q41DotPlan q41_dot_plan(int M, int K, int N);
+extern long g_q41_dot_launches;                      // mat-muls on k_q41_dot (process-wide; tests)
+// llamahip_op_mul_mat_q4_1_dot's refusals, before any device is touched: 0, or -1 with the limit named in err
+int q41_dot_op_check(const void *w, int32_t M, int32_t K, const float *x, int32_t N, const float *y, int32_t y_stride, char *err, size_t err_cap);
+
 }  // namespace lh

@@ -1813,6 +1813,37 @@ int main(int argc, char **argv) {
         }
         EXPECT(q41_fast_op_check(&wq, 8, 64, &xy, 70, &xy, 8, err, sizeof(err)) == 0);
         printf("host_sanitize: Q4_1 fast mat-mul host half: %d plans, %zu refusals\n", fast_plans, sizeof(fbad) / sizeof(fbad[0]));
+        // the opt-in integer-dot mat-mul's host half (q41_dot_plan.cpp): the four LLaMA widths x 1 .. 63 rows -- a compiled instance, a
+        // covering grid that does not follow N, LDS bytes a workgroup may declare -- and llamahip_op_mul_mat_q4_1_dot's refusals the same way
+        int dot_plans = 0;
+        for (size_t i = 0; i < 20; i++)
+            for (int N = 1; N < 64; N++) {
+                const int M = shapes[i].first, K = shapes[i].second, rows = std::min(N, 16);
+                const Q41DotPlan p = q41_dot_plan(M, K, N), one = q41_dot_plan(M, K, 1);
+                bool inst = false;
+#define LH_IS(NR) inst = inst || p.nr == NR;
+                LH_Q41_INSTANCES(LH_IS)
+#undef LH_IS
+                EXPECT(p.ok && inst && p.nr >= rows && p.threads == 256 && p.klanes == 16 && p.slab == q41_dot_slab(p.nr) && p.slab % p.klanes == 0);
+                EXPECT(p.lds == 2 * p.nr * p.slab * 32 && p.lds <= 64 * 1024 && p.nr * p.threads * 4 <= p.lds);
+                EXPECT(p.grid_x == one.grid_x && p.klanes == one.klanes && (int64_t) p.grid_x * 16 >= M && (int64_t) (p.grid_x - 1) * 16 < M && p.grid_y == (N + 15) / 16);
+                dot_plans++;
+            }
+        EXPECT(!q41_dot_plan(0, 64, 1).ok && !q41_dot_plan(8, 48, 1).ok && !q41_dot_plan(8, 0, 1).ok && !q41_dot_plan(8, 64, 0).ok);
+        EXPECT(q41_dot_plan(8, 64, 1048560).ok && !q41_dot_plan(8, 64, 1048561).ok);
+        struct { int32_t M, K, N, ys; const void *w; const char *says; } dbad[] = {
+            { 8, 48, 2, 8, &wq, "K 48 must be a positive multiple of 32" }, { 8, 0, 2, 8, &wq, "K 0 must be" }, { 8, 64, 0, 8, &wq, "N 0 must be >= 1" },
+            { 0, 64, 2, 8, &wq, "M 0 must be >= 1" }, { 8, 64, 2, 7, &wq, "y_stride 7 < M 8" }, { 8, 64, 2, 8, nullptr, "not NULL" },
+            { 8, 64, 1048561, 8, &wq, "more than 65535 row tiles of 16" },
+        };
+        for (auto &b : dbad) {
+            std::vector<char> e(256, 0), e1(1, 'x');
+            EXPECT(q41_dot_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e.data(), e.size()) == -1 && strstr(e.data(), b.says));
+            EXPECT(q41_dot_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e1.data(), e1.size()) == -1 && e1[0] == 0);
+            EXPECT(q41_dot_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, nullptr, 0) == -1);
+        }
+        EXPECT(q41_dot_op_check(&wq, 8, 64, &xy, 63, &xy, 8, err, sizeof(err)) == 0);
+        printf("host_sanitize: Q4_1 dot mat-mul host half: %d plans, %zu refusals\n", dot_plans, sizeof(dbad) / sizeof(dbad[0]));
     }
     {   // the few-row Q4_0 mat-mul's host half (set_plan.cpp): the plan of every LLaMA matrix at every row count 2 .. 60 and its launch shape,
         // every (nc, cw) pair forced -- admitted or refused with a reason, on exactly sized message buffers -- and what the rule refuses

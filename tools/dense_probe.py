@@ -5,7 +5,7 @@ usage: dense_probe.py [n_layer]
        dense_probe.py [n_layer] --multi [--json OUT] [--repeats R] [--seqs 1,2,4,8,16] [--only-multi]
        dense_probe.py [n_layer] --prompt [--fast] [--json OUT] [--repeats R] [--ftype f16|f32] [--force mm|mfma] [--evals 64,128,512]
                       [--chunks 18,36,72,144,504] [--trace-rows 17,32,64,128,512]
-       dense_probe.py [n_layer] --q41 [--fast] [--json OUT] [--repeats R] [--evals 9,16,17,64,512] [--trace-rows 1,16]
+       dense_probe.py [n_layer] --q41 [--fast] [--dot] [--json OUT] [--repeats R] [--evals 9,16,17,64,512] [--trace-rows 1,16]
 --multi (default 8 layers: 3.2 GB, larger than the Infinity Cache): ms per step and aggregate tokens/s of decode_greedy_multi for S sequences
 from position 256 for 64 steps, the 9-token eval, and the single-stream greedy loop; every figure is the wall time of a call that
 synchronises before it returns, after one untimed run of the same call (graph captures, first-touch allocations), R repeats each.
@@ -18,7 +18,8 @@ rocprofv3 --kernel-trace run that tools/dense_trace_summary.py reads.
 from position 256 for 64 steps and ms per eval of --evals rows, timed the same way; q41_paths where the library has it.  --trace-rows: nothing
 is timed -- per row count one untimed and R further evals (one row: a greedy loop of 1 + R steps, launched eagerly) and exit, for a rocprofv3
 --kernel-trace run.  --fast opens the handle with LLAMAHIP_FLAG_FAST_Q41 (evals of >= 64 rows on k_q41_fast -- not the reference's arithmetic).
-Run it once per library (LLAMAHIP_LIB) or per side (--fast), fresh processes, alternating.
+--dot opens it with LLAMAHIP_FLAG_FAST_Q41_DECODE (decode and evals below 64 rows on k_q41_dot -- not the reference's arithmetic either); the two combine.
+Run it once per library (LLAMAHIP_LIB) or per side (--fast, --dot), fresh processes, alternating.
 LLAMAHIP_LIB / LLAMAHIP_DENSE_MM select the library / the mat-mul of 2 .. 16 rows as usual; the model file is kept for the next run."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -53,8 +54,8 @@ if q41_mode:
         L.quantize_file(path, qpath, 3)
     stream = np.concatenate([[1], np.random.default_rng(2).integers(3, 32000, 511)]).astype(np.int32)
     tracing = "--trace-rows" in args
-    fast = "--fast" in args
-    m = L.Model(qpath, n_ctx=512, flags=(1 if tracing else 0) | (L.FAST_Q41 if fast else 0))      # (1 = LLAMAHIP_FLAG_NO_GRAPH: a kernel trace names the launches of a step)
+    fast, dot = "--fast" in args, "--dot" in args
+    m = L.Model(qpath, n_ctx=512, flags=(1 if tracing else 0) | (L.FAST_Q41 if fast else 0) | (L.FAST_Q41_DECODE if dot else 0))      # (1 = LLAMAHIP_FLAG_NO_GRAPH: a kernel trace names the launches of a step)
 
     def timed(fn):
         fn()
@@ -62,7 +63,7 @@ if q41_mode:
         for _ in range(R):
             t0 = time.perf_counter(); fn(); out.append(round((time.perf_counter() - t0) * 1e3, 4))
         return out
-    res = {"library": L.LIB_PATH, "ftype": "q41", "fast_q41": fast, "n_layer": nl, "file_gb": round(os.path.getsize(qpath) / 1e9, 2)}
+    res = {"library": L.LIB_PATH, "ftype": "q41", "fast_q41": fast, "fast_q41_decode": dot, "n_layer": nl, "file_gb": round(os.path.getsize(qpath) / 1e9, 2)}
     if tracing:
         for n in ints("--trace-rows", ""):
             if n == 1:
@@ -80,6 +81,8 @@ if q41_mode:
         res["q41_paths"] = L.q41_paths()
     if hasattr(L, "q41_fast_launches"):
         res["q41_fast_launches"] = L.q41_fast_launches()
+    if hasattr(L, "q41_dot_launches"):
+        res["q41_dot_launches"] = L.q41_dot_launches()
     print(json.dumps(res))
     if "--json" in args:
         with open(opt("--json", ""), "w") as f:
