@@ -155,6 +155,25 @@ typedef struct llamahip_opts {
                                         with FAST_Q41 and FAST_ATTN; stage handles of a pipeline inherit it.  Attention, RoPE and
                                         the KV append stay the exact kernels.  Never the default, never used for a parity claim. */
 
+#define LLAMAHIP_FLAG_FAST_Q40_FEW 512 /* OPT-IN, NOT the reference's arithmetic: on a Q4_0 model file, every mat-mul of 16 .. 63 rows
+                                        (wide batched decode steps, verify steps over drafted tokens, the scheduler's steps, beam search,
+                                        score_choices; 2 .. 15 rows measured slower than the exact kernels and stay with them) runs wq|wk|wv, wo, w1|w3, w2 and the lm head
+                                        on the int8 matrix cores (k_q40_few, csrc/q40_few.hip) instead of the exact k_gemv_set /
+                                        k_gemm_rows / LDS GEMM.  Same load-time weights (the one tile copy), the same activation codes
+                                        (quantize_row_q4_0, bit for bit): per block the exact integer sum of q c, then
+                                        fma((float) isum, fl(d_w * d_a), acc); K in 8 slices (4 above 8192 weight rows) added in a fixed
+                                        order that depends on (M, K) alone -- the reference's eight per-lane fp32 chains are gone and
+                                        the order of summation differs (where the measurements are).  Deterministic,
+                                        and a mat-mul row's bits do not depend on the rows it is evaluated with.  Such evals and steps
+                                        take the un-fused schedule: mat-mul, then the EXACT RoPE / KV append, attention, SiLU * up and
+                                        quantizers.  Unchanged, same kernels and same bits: the captured single-token decode step, every
+                                        mat-mul below 16 rows (the last-row lm head of an eval), evals of >= 64 rows, debug-dump evals; f16, f32
+                                        and Q4_1 files accept the flag and ignore it.  The one-pass entry points (eval_multi, the
+                                        scheduler's mixed pass, scoring, embeddings) run whatever their pass's row count runs: on such a
+                                        handle a request's bits depend on whether its pass had 16 .. 63 rows, so the scheduler's
+                                        "bit for bit the request alone" is NOT claimed there.  Combinable with FAST_PREFILL and FAST_ATTN;
+                                        stage handles of a pipeline inherit it.  Never the default, never used for a parity claim. */
+
 /* ---- the drop-in boundary ------------------------------------------------------------------ */
 
 /* Replaces llama_model_load(fname, model, vocab, n_ctx, &error)  (.mm:98).
@@ -1409,6 +1428,18 @@ int llamahip_op_mul_mat_q4_1_fast(const void *w_q4_1, int32_t M, int32_t K, cons
  * 65535 row tiles of 16. */
 int llamahip_op_mul_mat_q4_1_dot(const void *w_q4_1, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, char *err, size_t err_cap);
+/* The opt-in int8 matrix-core few-row mat-mul of Q4_0 files (k_q40_few, what a LLAMAHIP_FLAG_FAST_Q40_FEW handle runs at 16 .. 63 rows)
+ * alone, through the real prep and launch code: y[n][m] = sum over blocks of fma((float) isum, fl(d_w * d_a), .) (+ resid[n][m], added
+ * last), with isum the exact integer sum of q c over the block, q, d_w the codes - 8 and the scale of W[m]'s block, c, d_a those of
+ * quantize_row_q4_0(x[n]); K-slice s of S = 8 (4 where M > 8192) adds the blocks of chunks s, s + S, ... of 256 elements in ascending
+ * order, the slices are added 0, 1, 2, ... -- NOT bit for bit ggml_vec_dot_q4_0; held to |y - y64| <= gamma(K/32 + 4) mass + one ulp
+ * instead (mass: sum over blocks of |d_w d_a| sum |q c|, + |resid|).  Row n's bits are those of the one-row call on x[n].
+ * w_q4_0 M rows in file layout (K/32 blocks of 20 bytes), x [N][K], resid [N][M] or NULL, y [N][y_stride] copied to the device and back
+ * whole (the floats between M and y_stride keep the caller's bits).  N 1 .. 63 (a model handle sends 16 .. 63): one launch, one pass over
+ * the weights.  Refused before any device is touched, the limit named: K not a positive multiple of 32, N outside 1 .. 63, M < 1,
+ * y_stride < M, w_q4_0 / x / y NULL. */
+int llamahip_op_mul_mat_q4_0_few(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
+                                 float *y, int32_t y_stride, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -1769,6 +1800,13 @@ int64_t llamahip_debug_q41_fast_launches(void);
 int32_t llamahip_debug_q41_dot_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[7]);
 /* Mat-muls on k_q41_dot since process start (one per mat-mul, whatever its row tiles).  Tests and measurement tooling. */
 int64_t llamahip_debug_q41_dot_launches(void);
+/* Host only: the launch plan of k_q40_few for an M x K Q4_0 matrix and n_rows activation rows -- out = { column tiles of 16 rows, K-slices
+ * (= waves of a workgroup), threads, grid (workgroups of 16 weight rows), static LDS bytes }.  The slices and the grid do not depend on
+ * n_rows.  Returns 1, or 0 where the kernel does not take the shape (K no positive multiple of 32, m < 1, n_rows outside 1 .. 63). */
+int32_t llamahip_debug_q40_few_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[5]);
+/* Launches of k_q40_few since process start (a counter of its own: llamahip_debug_gemm_paths keeps its six entries).  Tests and
+ * measurement tooling. */
+int64_t llamahip_debug_q40_few_launches(void);
 /* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_mfma_launches(void);
 /* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more

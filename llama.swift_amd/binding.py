@@ -335,6 +335,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_q41_dot_plan.restype = i32
     L.llamahip_debug_q41_dot_launches.argtypes = []
     L.llamahip_debug_q41_dot_launches.restype = C.c_int64
+    L.llamahip_op_mul_mat_q4_0_few.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, cp, sz]
+    L.llamahip_debug_q40_few_plan.argtypes = [i32, i32, i32, vp]
+    L.llamahip_debug_q40_few_plan.restype = i32
+    L.llamahip_debug_q40_few_launches.argtypes = []
+    L.llamahip_debug_q40_few_launches.restype = C.c_int64
     L.llamahip_debug_q41_paths.argtypes = [vp, i32]
     L.llamahip_debug_q41_paths.restype = i32
     L.llamahip_debug_q41_plan.argtypes = [i32, i32, i32, vp]
@@ -471,6 +476,19 @@ def q41_dot_plan(m: int, k: int, n_rows: int):
 def q41_dot_launches() -> int:
     """Mat-muls on k_q41_dot since process start (llamahip_debug_q41_dot_launches)."""
     return int(lib().llamahip_debug_q41_dot_launches())
+
+
+def q40_few_plan(m: int, k: int, n_rows: int):
+    """Host-only: the launch plan of the opt-in int8 matrix-core few-row Q4_0 mat-mul k_q40_few (llamahip_debug_q40_few_plan) for n_rows rows
+    against an m x k Q4_0 matrix: a dict, or None where the kernel does not take the shape."""
+    a = np.zeros(5, np.int64)
+    rc = lib().llamahip_debug_q40_few_plan(m, k, n_rows, a.ctypes.data_as(C.c_void_p))
+    return dict(zip(("nt", "slices", "threads", "grid", "lds_bytes"), (int(x) for x in a))) if rc else None
+
+
+def q40_few_launches() -> int:
+    """Launches of k_q40_few since process start (llamahip_debug_q40_few_launches)."""
+    return int(lib().llamahip_debug_q40_few_launches())
 
 
 def dense_fast_plan(m: int, k: int, n_rows: int):
@@ -2077,6 +2095,30 @@ def op_mul_mat_q4_1_dot(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int 
         resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
     err = C.create_string_buffer(1024)
     _check(lib().llamahip_op_mul_mat_q4_1_dot(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
+    return y
+
+
+FAST_Q40_FEW = 512          # LLAMAHIP_FLAG_FAST_Q40_FEW: opt-in, Q4_0 files' mat-muls of 16 .. 63 rows on the int8 matrix cores (not the reference's arithmetic)
+
+
+def op_mul_mat_q4_0_few(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int | None = None, y_init=None, K: int | None = None):
+    """The opt-in int8 matrix-core few-row mat-mul of Q4_0 files alone (llamahip_op_mul_mat_q4_0_few): w uint8 [M, K/32, 20] in file layout,
+    x f32 [N, K] (N 1 .. 63), resid f32 [N, M] or None; y f32 [N, y_stride], the whole buffer as the device left it.  K overrides the row
+    length the shape of w implies (refusal tests)."""
+    w = np.ascontiguousarray(w, np.uint8)
+    w = w.reshape(w.shape[0], -1)
+    M, rb = w.shape
+    x = np.ascontiguousarray(x, np.float32)
+    if K is None:
+        K = rb // 20 * 32
+        x = x.reshape(-1, K)
+    N = x.shape[0]
+    ys = M if y_stride is None else int(y_stride)
+    y = np.full((N, max(ys, 0)), np.nan, np.float32) if y_init is None else np.array(y_init, np.float32, order="C").reshape(N, ys)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(N, M)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_mul_mat_q4_0_few(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
     return y
 
 

@@ -831,6 +831,10 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
     DumpSink *sink = p.sink;
     const bool debug = p.dump_layer >= 0 && sink;
     const bool fast_prefill = (m->flags & LLAMAHIP_FLAG_FAST_PREFILL) != 0 && !debug;      // opt-in re-associated prompt GEMM (llamahip.h)
+    // opt-in int8 matrix-core mat-mul of 16 .. 63 rows (llamahip.h): launch_gemm is the gate; such an eval takes the un-fused branches below
+    // (mat-mul, then the exact RoPE / KV append, SiLU * up and quantizer), so that wq|wk|wv and w1|w3 reach launch_gemm too
+    const bool few = (m->flags & LLAMAHIP_FLAG_FAST_Q40_FEW) != 0 && !debug;
+    const bool few_rows = few && N >= Q40_FEW_MIN_ROWS && N <= Q40_FEW_MAX_ROWS;
     // short prompt chunks (the reference evaluates prompts 8 tokens at a time, .mm / LlamaRunner n_batch) take the decode-shaped attention
     const bool short_chunk = attn_path_pick(&m->attn_ws, N, dh, n_past + N, nth) == ATTN_PATH_SHORT;
     // short evals (2 .. 16 rows): the w1|w3 launch of k_gemv_set runs half-block workgroups whose halves exchange their amax as tagged
@@ -852,13 +856,13 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
         if (dmp && !sink->put(0, m->x, (int64_t) N * d)) goto dump_fail;
         HIP_TRY(launch_prep(PREP_NORM, m->x, L.attention_norm, d, 0, d, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);   // .mm:570-575
         if (dmp && !sink->put(1, m->dbg_y, (int64_t) N * d)) goto dump_fail;
-        const bool rope_fused = short_layer && gemm_rope_kv_applies(L.qkv, N, d);
+        const bool rope_fused = short_layer && !few_rows && gemm_rope_kv_applies(L.qkv, N, d);
         if (rope_fused) {
             // short evals: q / k / v mat-mul, RoPE and the KV append in one launch (.mm:580-611)
             const RopeKvArgs ra = { m->sincos, m->qr, Kl, Vl, n_past, d, dh };
             HIP_TRY(launch_gemm_rope_kv(L.qkv, m->qa_A, m->qa_d, N, ra, st), LLAMAHIP_ERR_PREDICT);
         } else
-        HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, N, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);   // .mm:580-582
+        HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, N, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);   // .mm:580-582
         if (dmp) {
             for (int which = 0; which < 3; which++) {           // q, k, v are column slices of qkv[N][3d]
                 HIP_TRY(hipMemcpy2DAsync(m->tmp, (size_t) d * 4, m->qkv + (size_t) which * d, (size_t) 3 * d * 4, (size_t) d * 4, N, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
@@ -882,24 +886,24 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
         HIP_TRY(launch_prep(PREP_PLAIN, m->merged, nullptr, d, 0, d, N, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
         }
         if (dmp) {
-            HIP_TRY(launch_gemm(L.wo, EPI_STORE, m->qa_A, m->qa_d, N, m->tmp, d, nullptr, 0, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);      // .mm:649-651
+            HIP_TRY(launch_gemm(L.wo, EPI_STORE, m->qa_A, m->qa_d, N, m->tmp, d, nullptr, 0, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);      // .mm:649-651
             if (!sink->put(9, m->tmp, (int64_t) N * d)) goto dump_fail;
             HIP_TRY(launch_add(m->tmp, m->x, m->x1, (long) N * d, st), LLAMAHIP_ERR_PREDICT);                                   // .mm:654
             if (!sink->put(10, m->x1, (int64_t) N * d)) goto dump_fail;
         } else {
-            HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, N, m->x1, d, m->x, d, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, N, m->x1, d, m->x, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
         }
         HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);        // .mm:660-665
         if (dmp && !sink->put(11, m->dbg_y, (int64_t) N * d)) goto dump_fail;
-        if (short_layer && m->w13_interleaved && N <= 64 && gemm_silu_qa_applies(L.w13, N)) {
+        if (short_layer && !few_rows && m->w13_interleaved && N <= 64 && gemm_silu_qa_applies(L.w13, N)) {
             // short evals: w1 | w3, SiLU * up and the quantization for w2 in one launch (.mm:668-680)
             const long KpF = ((long) F + 255) / 256 * 256;
             set_hx.layer = il - m->l0;
             HIP_TRY(launch_gemm_silu_qa(L.w13, m->qa_A, m->qa_d, N, m->T_silu, m->qaF_A, m->qaF_d, KpF / 4, KpF / 32, st, &set_hx), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qaF_A, m->qaF_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);      // .mm:682-687
+            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qaF_A, m->qaF_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);      // .mm:682-687
             continue;
         }
-        HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, N, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);     // .mm:668-675
+        HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, N, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);     // .mm:668-675
         if (dmp) {
             HIP_TRY(hipMemcpy2DAsync(m->tmp, (size_t) F * 4, m->gu + F, (size_t) 2 * F * 4, (size_t) F * 4, N, hipMemcpyDeviceToDevice, st), LLAMAHIP_ERR_PREDICT);
             if (!sink->put(12, m->tmp, (int64_t) N * F)) goto dump_fail;       // w3 output ("tmp" in the reference)
@@ -909,12 +913,12 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
         HIP_TRY(launch_prep(PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);   // .mm:678-680
         if (dmp && !sink->put(14, m->dbg_y, (int64_t) N * F)) goto dump_fail;
         if (dmp) {
-            HIP_TRY(launch_gemm(L.w2, EPI_STORE, m->qa_A, m->qa_d, N, m->tmp, d, nullptr, 0, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);      // .mm:682-684
+            HIP_TRY(launch_gemm(L.w2, EPI_STORE, m->qa_A, m->qa_d, N, m->tmp, d, nullptr, 0, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);      // .mm:682-684
             if (!sink->put(15, m->tmp, (int64_t) N * d)) goto dump_fail;
             HIP_TRY(launch_add(m->tmp, m->x1, m->x, (long) N * d, st), LLAMAHIP_ERR_PREDICT);                                   // .mm:687
             if (!sink->put(16, m->x, (int64_t) N * d)) goto dump_fail;
         } else {
-            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
         }
     }
 
@@ -929,7 +933,7 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
             // (the scoring entry points: with `output`'s prompt copies and the operand workspace; llamahip_eval_debug: the decode tiles only)
             QMat out = m->output;
             if (!p.score_rows) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }
-            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st, p.score_rows ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, N, m->logits, V, nullptr, 0, st, p.score_rows ? m->qb_ws : nullptr, false, few), LLAMAHIP_ERR_PREDICT);
         } else {
             HIP_TRY(launch_prep(PREP_NORM, m->x + (size_t) (N - 1) * d, m->norm_w, d, 0, d, 1, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
             HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, 1, m->logits + (size_t) (N - 1) * V, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
@@ -1908,6 +1912,7 @@ static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, hipStre
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab;
     const long KpF = ((long) F + 255) / 256 * 256;
+    const bool few = (m->flags & LLAMAHIP_FLAG_FAST_Q40_FEW) != 0 && B >= Q40_FEW_MIN_ROWS && B <= Q40_FEW_MAX_ROWS;      // (see forward_eval)
     SiluHalfIO set_hx;          // (see forward_eval: the half-block w1|w3 launch of k_gemv_set; the step's first launch opens the epoch)
     if (m->d_attn_sync && m->d_set_amax && m->l1 - m->l0 <= TAG_MAX_LAYERS) { set_hx.amax_t = m->d_set_amax; set_hx.epoch = m->d_epoch; set_hx.fault = m->d_fault; }
     if (m->first_stage) HIP_TRY(launch_embed_set(d_set, B, m->tok_emb, m->x, d, st, set_hx.amax_t ? m->d_epoch : nullptr), LLAMAHIP_ERR_PREDICT);                // .mm:558-561
@@ -1919,22 +1924,27 @@ static int forward_set(llamahip_model *m, int nth, SeqSet *d_set, int B, hipStre
         HIP_TRY(launch_prep(PREP_NORM, m->x, L.attention_norm, d, 0, d, B, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);   // .mm:570-575
         RopeKvArgs ra = { m->sincos, m->qr, Kl, Vl, 0, d, dh };
         ra.set = d_set;
+        if (few) {
+            // (LLAMAHIP_FLAG_FAST_Q40_FEW: the mat-mul through launch_gemm's gate, then the exact RoPE / KV append per row of the set)
+            HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, B, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_rope_kv_set(m->qkv, 3L * d, d, dh, m->sincos, m->qr, Kl, Vl, d_set, B, st), LLAMAHIP_ERR_PREDICT);
+        } else
         HIP_TRY(launch_gemm_rope_kv(L.qkv, m->qa_A, m->qa_d, B, ra, st), LLAMAHIP_ERR_PREDICT);                                // .mm:580-611
         HIP_TRY(launch_attn_short(m->qr, Kl, Vl, m->set_sc, nullptr, m->qa_A, m->qa_d, 0, B, d, H, C, nth, m->T_exp, st, 0, d_set, set_keys), LLAMAHIP_ERR_PREDICT);   // .mm:614-646
-        HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, B, m->x1, d, m->x, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);  // .mm:649-654
+        HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, B, m->x1, d, m->x, d, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);  // .mm:649-654
         HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, B, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);        // .mm:660-665
-        if (m->w13_interleaved && gemm_silu_qa_applies(L.w13, B)) {
+        if (!few && m->w13_interleaved && gemm_silu_qa_applies(L.w13, B)) {
             HIP_TRY(launch_gemm_silu_qa(L.w13, m->qa_A, m->qa_d, B, m->T_silu, m->qaF_A, m->qaF_d, KpF / 4, KpF / 32, st, &set_hx), LLAMAHIP_ERR_PREDICT);       // .mm:668-680
             HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qaF_A, m->qaF_d, B, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);                 // .mm:682-687
         } else {
-            HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, B, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, B, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
             HIP_TRY(launch_prep(PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, B, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, B, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, B, m->x, d, m->x1, d, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
         }
     }
     if (m->last_stage) {
         HIP_TRY(launch_prep(PREP_NORM, m->x, m->norm_w, d, 0, d, B, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);          // .mm:695-705
-        HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, B, m->logits, V, nullptr, 0, st), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(m->output, EPI_STORE, m->qa_A, m->qa_d, B, m->logits, V, nullptr, 0, st, nullptr, false, few), LLAMAHIP_ERR_PREDICT);
         if (tail) HIP_TRY(launch_argmax_set(m->logits, V, d_set, B, st), LLAMAHIP_ERR_PREDICT);
     } else if (tail) {
         HIP_TRY(launch_rows_set(d_set, B, m->x, d, false, st), LLAMAHIP_ERR_PREDICT);
@@ -2645,6 +2655,7 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
     const HParams &hp = m->hp;
     const int d = hp.n_embd, F = hp.n_ff, H = hp.n_head, dh = d / H, C = hp.n_ctx, V = hp.n_vocab, R = rp.R;
     const int nth = clamp_threads(n_threads);
+    const bool few = (m->flags & LLAMAHIP_FLAG_FAST_Q40_FEW) != 0;      // (a pass of 16 .. 63 rows runs what launch_gemm runs for its row count: llamahip.h)
     hipStream_t st = m->stream;
     int rc = rows_upload(m, rp, err, err_cap);
     if (rc) return rc;
@@ -2655,7 +2666,7 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
         const Layer &L = m->layers[il - m->l0];
         float *K0 = m->Kc + (size_t) (il - m->l0) * C * d, *V0 = m->Vc + (size_t) (il - m->l0) * C * d;      // slot 0's cache of this layer: the table's offsets start here
         HIP_TRY(launch_prep(PREP_NORM, m->x, L.attention_norm, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, R, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.qkv, EPI_STORE, m->qa_A, m->qa_d, R, m->qkv, 3L * d, nullptr, 0, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
         HIP_TRY(launch_rope_kv_rows(m->qkv, 3L * d, d, dh, m->sincos, m->qr, K0, V0, rd.tab, R, st), LLAMAHIP_ERR_PREDICT);
         if (rp.n_long_segs == 0) {
             // every segment short: one launch pair for all rows, quantizing the merged rows straight into wo's operand
@@ -2670,11 +2681,11 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
             }
             HIP_TRY(launch_prep(PREP_PLAIN, m->merged, nullptr, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
         }
-        HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, R, m->x1, d, m->x, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, R, m->x1, d, m->x, d, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
         HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, R, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.w13, EPI_STORE, m->qa_A, m->qa_d, R, m->gu, 2L * F, nullptr, 0, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
         HIP_TRY(launch_prep(PREP_SILU_MUL, m->gu, m->gu + F, 2L * F, 2L * F, F, R, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
-        HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, R, m->x, d, m->x1, d, st, m->qb_ws, false), LLAMAHIP_ERR_PREDICT);
+        HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, R, m->x, d, m->x1, d, st, m->qb_ws, false, few), LLAMAHIP_ERR_PREDICT);
     }
     if (m->last_stage && rp.embed) return embed_tail_rows(m, rp, rd.last_idx, err, err_cap);
     if (m->last_stage) {
@@ -2688,7 +2699,7 @@ static int forward_rows(llamahip_model *m, int n_threads, const RowsPass &rp, co
             HIP_TRY(launch_prep(PREP_NORM, m->x1, m->norm_w, d, 0, d, nl, m->qa_A, m->qa_d, nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);
             QMat out = m->output;
             if (!rp.score) { out.rows = nullptr; out.mt = nullptr; out.mt4 = nullptr; }          // (the decode tiles, as llamahip_eval's lm head)
-            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, nl, m->logits, V, nullptr, 0, st, rp.score ? m->qb_ws : nullptr), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(launch_gemm(out, EPI_STORE, m->qa_A, m->qa_d, nl, m->logits, V, nullptr, 0, st, rp.score ? m->qb_ws : nullptr, false, few), LLAMAHIP_ERR_PREDICT);
         }
     }
     m->last_rows.clear();          // (m->logits rewritten)
@@ -5401,6 +5412,17 @@ int32_t llamahip_debug_q41_dot_plan(int32_t m, int32_t k, int32_t n_rows, int64_
 }
 
 int64_t llamahip_debug_q41_dot_launches(void) { return g_q41_dot_launches; }
+
+int32_t llamahip_debug_q40_few_plan(int32_t m, int32_t k, int32_t n_rows, int64_t out[5]) {
+    if (!out) return 0;
+    const Q40FewPlan p = q40_few_plan(m, k, n_rows);
+    if (!p.ok) return 0;
+    const int64_t o[5] = { p.nt, p.slices, p.threads, p.grid, p.lds };
+    for (int i = 0; i < 5; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_q40_few_launches(void) { return g_q40_few_launches; }
 
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
     if (!out) return 0;

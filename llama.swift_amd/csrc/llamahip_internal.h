@@ -6,6 +6,7 @@
 
 #include "dec_attn_plan.h"
 #include "flash_attn_plan.h"
+#include "q40_few_plan.h"
 #include "q41_plan.h"
 #include "set_plan.h"
 
@@ -233,9 +234,14 @@ hipError_t launch_embed_part(const int32_t *token, const uint8_t *emb, float *x,
 enum { GEMM_PATH_MFMA = 0, GEMM_PATH_ROWS = 1, GEMM_PATH_LDS = 2, GEMM_PATH_GEMV = 3, GEMM_PATH_SET = 4, GEMM_PATH_FAST = 5, GEMM_PATH_COUNT = 6 };
 extern long g_gemm_path_counts[GEMM_PATH_COUNT];     // launches per kernel family of launch_gemm (process-wide; tests)
 // qb_ws: scratch for the int8 operand of the matrix-core path (N * nchunks * 256 B), or nullptr
+// few (LLAMAHIP_FLAG_FAST_Q40_FEW handles): Q40_FEW_MIN_ROWS .. Q40_FEW_MAX_ROWS rows that no matrix-core path takes run k_q40_few
 hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
                        float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st,
-                       uint8_t *qb_ws = nullptr, bool fast = false);
+                       uint8_t *qb_ws = nullptr, bool fast = false, bool few = false);
+// k_q40_few (q40_few.hip; plan and counter: q40_few_plan.h): 1 .. Q40_FEW_MAX_ROWS operand rows against the tile copy, EPI_STORE / EPI_RESID;
+// counts in g_q40_few_launches, NOT in g_gemm_path_counts
+hipError_t launch_q40_few(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                          float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st);
 // ONE kernel family of launch_gemm, forced whatever its selection rule would pick (llamahip_op_prompt_gemm_q4_0: per-op tests of every
 // prompt GEMM).  The path values are LLAMAHIP_GEMM_* of llamahip.h; EPI_STORE / EPI_RESID only.  A family that cannot take the matrix
 // (its copy is missing) or the shape is refused with hipErrorInvalidValue and the limit in *why; nothing is launched then.  Counts as

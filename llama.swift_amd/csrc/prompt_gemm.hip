@@ -941,7 +941,7 @@ static hipError_t launch_lds(const QMat &w, int epi, const uint32_t *qa_A, const
 }
 
 hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
-                       float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast) {
+                       float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast, bool few) {
     // Matrix-core path when its 64 x 64-output workgroups fill the chip twice over, or from 128 rows when the last 64-column tile is
     // not mostly padding (measured against the row-per-lane kernel, 7B, every matrix on one kernel, profiles/r04_y_midN_ab.txt: 64 rows
     // -3 %, 96 -7 %, 128 +19 %, 192 +10 %, 240 +32 %; 1.5x at 1 024).
@@ -958,6 +958,10 @@ hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float
         // matrix-core path on the int8 tiles (the opt-in fast path; LLAMAHIP_MFMA_I8: the round-1 exact kernel): needs the int8 operand (QB)
         return launch_mfma_i8(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st, qb_ws, fast);
     }
+    // opt-in (LLAMAHIP_FLAG_FAST_Q40_FEW): 16 .. 63 rows on the int8 matrix cores from the tile copy, whichever of the kernels below they
+    // would have taken -- not the reference's arithmetic, counted on its own (g_q40_few_launches)
+    if (few && N >= Q40_FEW_MIN_ROWS && N <= Q40_FEW_MAX_ROWS && (epi == EPI_STORE || epi == EPI_RESID) && q40_few_plan(w.M, w.K, N).ok)
+        return launch_q40_few(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st);
     // 2 .. 60 rows (a batched decode step, the reference's 9-token evals, short prompt chunks): k_gemv_set
     if ((epi == EPI_STORE || epi == EPI_RESID) && gemv_set_applies(w, N, epi)) {
         g_gemm_path_counts[GEMM_PATH_SET]++;

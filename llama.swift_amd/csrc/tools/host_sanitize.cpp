@@ -21,6 +21,7 @@
 #include "../../../include/llamahip.h"
 #include "../dev_owner.h"
 #include "../model_file.h"
+#include "../q40_few_plan.h"
 #include "../q41_plan.h"
 #include "../set_plan.h"
 #include "../dec_attn_plan.h"
@@ -1844,6 +1845,31 @@ int main(int argc, char **argv) {
         }
         EXPECT(q41_dot_op_check(&wq, 8, 64, &xy, 63, &xy, 8, err, sizeof(err)) == 0);
         printf("host_sanitize: Q4_1 dot mat-mul host half: %d plans, %zu refusals\n", dot_plans, sizeof(dbad) / sizeof(dbad[0]));
+        // the opt-in int8 matrix-core few-row mat-mul of Q4_0 files (q40_few_plan.cpp): every shape above x 1 .. 63 rows -- column tiles that
+        // cover N, a grid that covers M, slices and grid that do not follow N, the instance's LDS -- and llamahip_op_mul_mat_q4_0_few's refusals
+        int few_plans = 0;
+        for (auto &mk : shapes)
+            for (int N = 1; N <= Q40_FEW_MAX_ROWS; N++) {
+                const int M = mk.first, K = mk.second;
+                const Q40FewPlan p = q40_few_plan(M, K, N), one = q40_few_plan(M, K, 1);
+                EXPECT(p.ok && p.nt >= 1 && p.nt <= Q40_FEW_MAX_NT && p.nt * 16 >= N && (p.nt - 1) * 16 < N);
+                EXPECT(p.slices == one.slices && p.grid == one.grid && p.slices == (M <= 8192 ? 8 : 4) && p.slices <= Q40_FEW_MAX_SLICES && p.threads == 64 * p.slices);
+                EXPECT((int64_t) p.grid * 16 >= M && (int64_t) (p.grid - 1) * 16 < M && p.lds == 8 * (p.nt * 1024 + 512) && p.lds <= 64 * 1024);
+                few_plans++;
+            }
+        EXPECT(!q40_few_plan(0, 64, 2).ok && !q40_few_plan(8, 48, 2).ok && !q40_few_plan(8, 0, 2).ok && !q40_few_plan(8, 64, 0).ok && !q40_few_plan(8, 64, 64).ok);
+        struct { int32_t M, K, N, ys; const void *w; const char *says; } wbad[] = {
+            { 8, 48, 2, 8, &wq, "K 48 must be a positive multiple of 32" }, { 8, 0, 2, 8, &wq, "K 0 must be" }, { 8, 64, 0, 8, &wq, "N 0 outside 1 .. 63" },
+            { 8, 64, 64, 8, &wq, "N 64 outside 1 .. 63" }, { 0, 64, 2, 8, &wq, "M 0 must be >= 1" }, { 8, 64, 2, 7, &wq, "y_stride 7 < M 8" }, { 8, 64, 2, 8, nullptr, "not NULL" },
+        };
+        for (auto &b : wbad) {
+            std::vector<char> e(256, 0), e1(1, 'x');
+            EXPECT(q40_few_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e.data(), e.size()) == -1 && strstr(e.data(), b.says));
+            EXPECT(q40_few_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, e1.data(), e1.size()) == -1 && e1[0] == 0);
+            EXPECT(q40_few_op_check(b.w, b.M, b.K, &xy, b.N, &xy, b.ys, nullptr, 0) == -1);
+        }
+        EXPECT(q40_few_op_check(&wq, 8, 32, &xy, 63, &xy, 8, err, sizeof(err)) == 0);
+        printf("host_sanitize: Q4_0 few-row mat-mul host half: %d plans, %zu refusals\n", few_plans, sizeof(wbad) / sizeof(wbad[0]));
     }
     {   // the few-row Q4_0 mat-mul's host half (set_plan.cpp): the plan of every LLaMA matrix at every row count 2 .. 60 and its launch shape,
         // every (nc, cw) pair forced -- admitted or refused with a reason, on exactly sized message buffers -- and what the rule refuses

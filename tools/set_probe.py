@@ -3,7 +3,9 @@
 (llamahip_stage_step_set) on one handle -- ms per step, aggregate tokens/s, a CRC of every sequence's tokens (variants of the
 library / of its switches must agree), and with --evals the reference's 9-token evals next to it.  Run it under
 `rocprofv3 --kernel-trace --stats` for the per-kernel table of a set step (tools/set_ab.sh).
-usage: set_probe.py [--model 7B] [--seqs 4,8] [--steps 96] [--n_ctx 512] [--evals 9]"""
+--flags opens the handles with LLAMAHIP_FLAG_* bits (512 = FAST_Q40_FEW: the set steps and the evals of 16 .. 63 rows on k_q40_few -- not the
+reference's arithmetic, so its CRCs differ from the exact handle's).
+usage: set_probe.py [--model 7B] [--seqs 4,8] [--steps 96] [--n_ctx 512] [--evals 9] [--flags 0]"""
 import argparse
 import os
 import sys
@@ -26,13 +28,14 @@ ap.add_argument("--n_ctx", type=int, default=512)
 ap.add_argument("--threads", type=int, default=8)
 ap.add_argument("--layers", type=int, default=0, help="load only the first N layers (a pipeline stage's share)")
 ap.add_argument("--evals", default="", help="also time llama_eval calls of these row counts (e.g. 9: the reference's prompt flow)")
+ap.add_argument("--flags", type=int, default=0, help="LLAMAHIP_FLAG_* bits of the handles")
 args = ap.parse_args()
 cfg = bench.MODELS[args.model]
 path = bench.model_path(args.model, cfg, 20230312)
 rng = np.random.default_rng(5)
 kw = dict(layer_begin=0, layer_end=args.layers) if args.layers else {}
 for S in [int(x) for x in args.seqs.split(",") if x]:
-    m = L.Model(path, n_ctx=args.n_ctx, n_seq=S, **kw)
+    m = L.Model(path, n_ctx=args.n_ctx, n_seq=S, flags=args.flags, **kw)
     last = not args.layers or args.layers >= cfg["n_layer"]
     prompts = [np.concatenate([[1], rng.integers(3, cfg["n_vocab"], 7 + s)]).astype(np.int32) for s in range(S)]      # positions 8, 9, ...
     firsts = []
@@ -76,10 +79,10 @@ for S in [int(x) for x in args.seqs.split(",") if x]:
         for s in range(S):
             n, pos, got = m.stage_trace(s, steps)
             crc = zlib.crc32(np.asarray(got, np.int32).tobytes(), crc)
-    print(f"set of {S:2d}: {best / steps * 1e3:6.3f} ms per step = {S * steps / best:7.1f} tok/s aggregate, crc {crc:08x}, paths {L.gemm_paths()}", flush=True)
+    print(f"set of {S:2d}: {best / steps * 1e3:6.3f} ms per step = {S * steps / best:7.1f} tok/s aggregate, crc {crc:08x}, paths {L.gemm_paths()}, few {L.q40_few_launches()}", flush=True)
     m.close()
 if args.evals:
-    m = L.Model(path, n_ctx=args.n_ctx)
+    m = L.Model(path, n_ctx=args.n_ctx, flags=args.flags)
     toks = np.random.default_rng(0).integers(3, cfg["n_vocab"], args.n_ctx).astype(np.int32)
     toks[0] = 1
     for n in [int(x) for x in args.evals.split(",")]:
