@@ -64,6 +64,22 @@ typedef struct llamahip_opts {
     int32_t n_seq;         /* independent KV caches held by this handle (pipeline micro-batching); 0 = 1 */
     int32_t n_devices;     /* > 1: an in-process layer pipeline, stage s = an even share of the layers on devices[s] (below); 0 / 1 = `device` */
     int32_t devices[8];    /* HIP device ordinals of the stages, in layer order (an ordinal may repeat: several stages on one GPU) */
+    int32_t fast_decode;   /* OPT-IN, NOT the reference's arithmetic; read only where struct_size covers it (a shorter struct -- 24, 28, 64 bytes --
+                              means 0).  0 = off.  1 = on a Q4_0 model file the wo and w2 mat-vecs of every single-token step (the captured
+                              decode step, LLAMAHIP_FLAG_NO_GRAPH, LLAMAHIP_FLAG_UNFUSED, a one-token llamahip_eval) run the K-split
+                              integer-dot kernel k_q40_dot (csrc/q40_dot.hip) where its plan applies (llamahip_debug_q40_dot_plan) instead of
+                              the exact k_gemv.  Same load-time weights (the one tile copy), the same activation codes (quantize_row_q4_0,
+                              bit for bit): per block the exact integer sum of q c, then fma((float) isum, fl(d_w * d_a), acc); K in 8
+                              slices (4 above 8192 weight rows) of whole 256-element chunks, slice s taking chunks s, s + S, ..., added in
+                              slice order, the residual last -- k_q40_few's arithmetic at one row: the reference's eight per-lane fp32
+                              chains are gone and the order of summation differs (where the bound and the measurements
+                              are).  MEASURED SLOWER than k_gemv on both 7B matrices (1.401 against 1.296 ms per token), so by the project's
+                              give-back rule the plan applies below 4096 weight rows only: at every LLaMA width the field changes nothing,
+                              same kernels and same bits as 0.  Deterministic; a step's bits do not depend on graph capture or on the flags above.  Unchanged, same
+                              kernels and same bits: wq|wk|wv, attention, w1|w3, the lm head and its pick, set steps, evals of 2+ rows,
+                              debug-dump evals, pipeline mailbox launches; f16, f32 and Q4_1 files accept the field and ignore it.  Any
+                              other value is refused at load.  Stage handles of an in-process pipeline inherit it.  Never the default,
+                              never used for a parity claim. */
 } llamahip_opts;
 #define LLAMAHIP_MAX_DEVICES 8
 /* In-process layer pipeline (SURVEY.md section 8e behind the reference's own surface): the bridge makes ONE llama_model_load call from ONE
@@ -1440,6 +1456,20 @@ int llamahip_op_mul_mat_q4_1_dot(const void *w_q4_1, int32_t M, int32_t K, const
  * y_stride < M, w_q4_0 / x / y NULL. */
 int llamahip_op_mul_mat_q4_0_few(const void *w_q4_0, int32_t M, int32_t K, const float *x, int32_t N, const float *resid,
                                  float *y, int32_t y_stride, char *err, size_t err_cap);
+/* The opt-in K-split integer-dot mat-vec of Q4_0 files (k_q40_dot, what a llamahip_opts.fast_decode = 1 handle runs for wo and w2 of a
+ * single-token step) alone, through the real prep and launch code: y[m] = sum over blocks of fma((float) isum, fl(d_w * d_a), .) (+ resid[m],
+ * added last), with isum the exact integer sum of q c over the block, q, d_w the codes - 8 and the scale of W[m]'s block, c, d_a those of
+ * quantize_row_q4_0(x); K-slice s of S = 8 (4 where M > 8192) adds the blocks of chunks s, s + S, ... of 256 elements in ascending order
+ * from +0, the slices are added 0, 1, 2, ... -- NOT bit for bit ggml_vec_dot_q4_0; held to |y - y64| <= gamma(K/32 + 4) mass + one ulp
+ * (mass: sum over blocks of |d_w d_a| sum |q c|, + |resid|).  parts[g] = {sum y, sum y^2} in double over the stored outputs of rows
+ * 16 g .. 16 g + 15, summed as the pairwise tree ((y0 + y1) + (y2 + y3)) + ((y4 + y5) + (y6 + y7)), the same of rows 8 .. 15, the halves
+ * added; rows past M count as 0 -- what the next launch's norm prologue folds.
+ * w_q4_0 M rows in file layout (K/32 blocks of 20 bytes), x [K], resid [M] or NULL; y [y_cap] and parts [parts_cap][2] are copied to the
+ * device and back whole (the floats behind M and the pairs behind ceil(M / 16) keep the caller's bits).  Refused before any device is
+ * touched, the limit named: K not a positive multiple of 32 (or above what 48 KiB of LDS hold of the row), M < 1, y_cap < M, parts_cap
+ * < ceil(M / 16), w_q4_0 / x / y / parts NULL. */
+int llamahip_op_gemv_q4_0_dot(const void *w_q4_0, int32_t M, int32_t K, const float *x, const float *resid,
+                              float *y, int32_t y_cap, double *parts, int32_t parts_cap, char *err, size_t err_cap);
 /* One layer's attention (.mm:586-646) on caller-supplied operands with its kernels chosen by the caller.  qkv [N][3d]: the un-rotated q | k | v
  * rows of the eval (the wq | wk | wv product); Kc, Vc [n_ctx][d]: the caches, rows < n_past rotated keys / values, COPIED WHOLE to the device
  * and back, so rows >= n_past + N keep what the caller put there unless a kernel writes out of place.  The op appends rows n_past .. T - 1
@@ -1807,6 +1837,15 @@ int32_t llamahip_debug_q40_few_plan(int32_t m, int32_t k, int32_t n_rows, int64_
 /* Launches of k_q40_few since process start (a counter of its own: llamahip_debug_gemm_paths keeps its six entries).  Tests and
  * measurement tooling. */
 int64_t llamahip_debug_q40_few_launches(void);
+/* Host only: the launch plan of k_q40_dot for an M x K Q4_0 matrix -- out = { K-slices (= waves of a workgroup), threads, grid (workgroups
+ * of 16 weight rows = {sum, sum of squares} pairs it hands on), dynamic LDS bytes, applies (1: a fast_decode handle's single-token step
+ * takes the kernel for this matrix -- the grid fits the hand-off and the measured rule of DESIGN.md 12.40 keeps it: fewer than 4096 rows) }.  Returns 1, or 0
+ * where the kernel does not take the shape (K no positive multiple of 32 or too long for its LDS, m < 1). */
+int32_t llamahip_debug_q40_dot_plan(int32_t m, int32_t k, int64_t out[5]);
+/* Launches of k_q40_dot: of this handle since it was loaded, graph replays included (each launch adds one to a device word of the handle;
+ * the call waits for the device; the stages of a pipeline handle are summed; 0 on a handle without fast_decode) -- or, model NULL, the
+ * launcher's calls of the whole process.  Tests and measurement tooling. */
+int64_t llamahip_debug_q40_dot_launches(const llamahip_model *model);
 /* Launches of k_dense_mfma since process start (llamahip_debug_dense_paths keeps its three entries).  Tests and measurement tooling. */
 int64_t llamahip_debug_dense_mfma_launches(void);
 /* Process-wide, for tests and measurement: 0 -- the measured rule; LLAMAHIP_DENSE_MM / LLAMAHIP_DENSE_MFMA -- every f16 / f32 mat-mul of more

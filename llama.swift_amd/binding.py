@@ -72,7 +72,7 @@ class _BeamStats(C.Structure):
 class _Opts(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("layer_begin", C.c_int32),
                 ("layer_end", C.c_int32), ("n_parts", C.c_int32), ("flags", C.c_int32), ("n_seq", C.c_int32),
-                ("n_devices", C.c_int32), ("devices", C.c_int32 * 8)]
+                ("n_devices", C.c_int32), ("devices", C.c_int32 * 8), ("fast_decode", C.c_int32)]
 
 
 class _GemvBench(C.Structure):
@@ -336,6 +336,11 @@ def lib() -> C.CDLL:
     L.llamahip_debug_q41_dot_launches.argtypes = []
     L.llamahip_debug_q41_dot_launches.restype = C.c_int64
     L.llamahip_op_mul_mat_q4_0_few.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, cp, sz]
+    L.llamahip_op_gemv_q4_0_dot.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, i32, cp, sz]
+    L.llamahip_debug_q40_dot_plan.argtypes = [i32, i32, vp]
+    L.llamahip_debug_q40_dot_plan.restype = i32
+    L.llamahip_debug_q40_dot_launches.argtypes = [vp]
+    L.llamahip_debug_q40_dot_launches.restype = C.c_int64
     L.llamahip_debug_q40_few_plan.argtypes = [i32, i32, i32, vp]
     L.llamahip_debug_q40_few_plan.restype = i32
     L.llamahip_debug_q40_few_launches.argtypes = []
@@ -491,6 +496,20 @@ def q40_few_launches() -> int:
     return int(lib().llamahip_debug_q40_few_launches())
 
 
+def q40_dot_plan(m: int, k: int):
+    """Host-only: the launch plan of the opt-in K-split integer-dot Q4_0 mat-vec k_q40_dot (llamahip_debug_q40_dot_plan) for an m x k Q4_0
+    matrix: a dict, or None where the kernel does not take the shape."""
+    a = np.zeros(5, np.int64)
+    rc = lib().llamahip_debug_q40_dot_plan(m, k, a.ctypes.data_as(C.c_void_p))
+    return dict(zip(("slices", "threads", "grid", "lds_bytes", "applies"), (int(x) for x in a))) if rc else None
+
+
+def q40_dot_launches(model=None) -> int:
+    """Launches of k_q40_dot (llamahip_debug_q40_dot_launches): of a Model since it was loaded, graph replays included, or -- no model -- the
+    launcher's calls of the whole process."""
+    return int(lib().llamahip_debug_q40_dot_launches(model._h if model is not None else None))
+
+
 def dense_fast_plan(m: int, k: int, n_rows: int):
     """Host-only: the launch plan of the opt-in fp16 matrix-core mat-mul k_dense_f16_fast (llamahip_debug_dense_fast_plan) for n_rows rows
     against an m x k f16 matrix: a dict, or None where the kernel does not take the shape."""
@@ -580,16 +599,18 @@ class Model:
     """Opaque model handle (llama_model + gpt_vocab of the reference, .mm:71-88, utils.h:49-55)."""
 
     def __init__(self, path: str, n_ctx: int = 512, device: int = -1, layer_begin: int = 0,
-                 layer_end: int = -1, n_parts: int = 0, flags: int = 0, n_seq: int = 1, devices=None):
+                 layer_end: int = -1, n_parts: int = 0, flags: int = 0, n_seq: int = 1, devices=None, fast_decode: int = 0):
         """devices: a list of HIP device ordinals = an in-process layer pipeline, one stage per entry (include/llamahip.h);
-        the same entry points work on it (eval, eval_chunks, eval_topk, decode_greedy, kv, stats)."""
+        the same entry points work on it (eval, eval_chunks, eval_topk, decode_greedy, kv, stats).
+        fast_decode: llamahip_opts.fast_decode -- 1 = opt-in K-split integer-dot wo / w2 of single-token steps on Q4_0 files (not the
+        reference's arithmetic)."""
         L = lib()
         err = C.create_string_buffer(1024)
         h = C.c_void_p()
         devices = list(devices or [])
         if len(devices) > 8:
             raise ValueError("at most 8 pipeline stages")
-        opts = _Opts(C.sizeof(_Opts), device, layer_begin, layer_end, n_parts, flags, n_seq, len(devices), (C.c_int32 * 8)(*devices))
+        opts = _Opts(C.sizeof(_Opts), device, layer_begin, layer_end, n_parts, flags, n_seq, len(devices), (C.c_int32 * 8)(*devices), fast_decode)
         self.layer_begin, self.n_seq = layer_begin, n_seq
         rc = L.llamahip_model_load(path.encode(), n_ctx, C.byref(opts), C.byref(h), err, len(err))
         _check(rc, err)
@@ -2120,6 +2141,26 @@ def op_mul_mat_q4_0_few(w: np.ndarray, x: np.ndarray, resid=None, y_stride: int 
     err = C.create_string_buffer(1024)
     _check(lib().llamahip_op_mul_mat_q4_0_few(_ptr(w), M, K, _ptr(x), N, _ptr(resid), _ptr(y), ys, err, len(err)), err)
     return y
+
+
+def op_gemv_q4_0_dot(w: np.ndarray, x: np.ndarray, resid=None, y_cap: int | None = None, parts_cap: int | None = None, K: int | None = None):
+    """The opt-in K-split integer-dot mat-vec of Q4_0 files alone (llamahip_op_gemv_q4_0_dot): w uint8 [M, K/32, 20] in file layout, x f32
+    [K], resid f32 [M] or None -> (y f32 [y_cap], parts f64 [parts_cap, 2]), both whole buffers as the device left them (NaN where it wrote
+    nothing).  K overrides the row length the shape of w implies (refusal tests)."""
+    w = np.ascontiguousarray(w, np.uint8)
+    w = w.reshape(w.shape[0], -1)
+    M, rb = w.shape
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    if K is None:
+        K = rb // 20 * 32
+    y = np.full(M if y_cap is None else max(int(y_cap), 0), np.nan, np.float32)
+    parts = np.full((-(-M // 16) if parts_cap is None else max(int(parts_cap), 0), 2), np.nan, np.float64)
+    if resid is not None:
+        resid = np.ascontiguousarray(resid, np.float32).reshape(M)
+    err = C.create_string_buffer(1024)
+    _check(lib().llamahip_op_gemv_q4_0_dot(_ptr(w), M, K, _ptr(x), _ptr(resid), _ptr(y), y.shape[0] if y_cap is None else int(y_cap), _ptr(parts),
+                                           parts.shape[0] if parts_cap is None else int(parts_cap), err, len(err)), err)
+    return y, parts
 
 
 ATTN_PATHS = ("auto", "mfma", "row", "short", "dec", "dec_stream")      # LLAMAHIP_ATTN_* of llamahip.h, in order

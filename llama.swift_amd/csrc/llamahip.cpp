@@ -160,6 +160,8 @@ struct llamahip_model {
     int l0 = 0, l1 = 0;                  // layers [l0, l1) live on this handle
     bool first_stage = true, last_stage = true;
     int flags = 0;
+    int fast_decode = 0;                 // llamahip_opts.fast_decode: 1 = wo / w2 of a single-token step on k_q40_dot where its plan applies (Q4_0 files)
+    unsigned long long *d_dot_count = nullptr;      // ... and the device word its launches count themselves in (graph replays included)
     bool host_only = false;
     hipStream_t stream = nullptr;
     // Every device / pinned allocation of this handle, of its slots and of its set descriptors is registered here; the members below are
@@ -721,6 +723,14 @@ static int attn_sched_at(const llamahip_model *m, int pos) {
     if (two_from >= 0 && pos >= two_from) return 1;
     return 0;
 }
+// llamahip_opts.fast_decode = 1: does a one-row wo / w2 mat-vec of this handle take k_q40_dot?  (the plan's measured rule; no w1|w3 layout)
+static bool dot_takes(const llamahip_model *m, const QMat &w) { return m->fast_decode == 1 && !w.gmapF8 && q40_dot_plan(w.M, w.K).applies; }
+// ... as launch_gemm's caller for wo / w2 of an un-fused pass: one row goes to the kernel the fused step runs, more rows where they went
+static hipError_t gemm_or_dot(const llamahip_model *m, bool one_row, const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
+                              float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st, uint8_t *qb_ws, bool fast, bool few) {
+    if (one_row && N == 1 && dot_takes(m, w)) return launch_q40_dot(w, epi, qa_A, qa_d, y, resid, nullptr, 0, m->d_dot_count, st);
+    return launch_gemm(w, epi, qa_A, qa_d, N, y, y_stride, resid, resid_stride, st, qb_ws, fast, few);
+}
 // The fused single-token step of a Q4_0 handle: activation preparation lives in GEMV prologues / producer epilogues (four launches per
 // layer), the context position is read from p.state by the attention kernels.
 int forward_decode(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
@@ -776,16 +786,20 @@ int forward_decode(llamahip_model *m, const Pass &p, char *err, size_t err_cap) 
         const float *xa = (il == m->l0 && x_first) ? x_first : m->x;      // residual stream into this layer
         float *xo = (il == m->l1 - 1 && x_last) ? x_last : m->x;           // ... and out of it
         NormPart np_qkv, np_wo, np_w13, np_w2;
+        // (mailboxes: the first layer reads its row -- norm input and residual operand -- from the tagged inbox, the last layer's w2
+        //  stores its row into the next stage's inbox; everything in between is the usual schedule)
+        const MailboxIO *mbi = (has_mb_in && il == m->l0) ? &mb_first : nullptr, *mbo = (has_mb_out && il == m->l1 - 1) ? &mb_last : nullptr;
+        // llamahip_opts.fast_decode: wo / w2 on the K-split integer-dot kernel (mailbox launches stay on k_gemv's tagged variants)
+        const bool dot_wo = dot_takes(m, L.wo) && !mbi, dot_w2 = dot_takes(m, L.w2) && !mbo && m->w13_interleaved;
         if (use_part) {
-            const int pw = gemv_resid_parts(L.wo), p2 = gemv_resid_parts(L.w2);
+            // (the pairs the next prologue folds are those of the kernel that runs)
+            const int pw = dot_wo ? q40_dot_plan(L.wo.M, L.wo.K).grid : gemv_resid_parts(L.wo);
+            const int p2 = dot_w2 ? q40_dot_plan(L.w2.M, L.w2.K).grid : gemv_resid_parts(L.w2);
             if (n_part_x > 0) { np_qkv.in = m->npart_a; np_qkv.n_in = n_part_x; }
             if (pw > 0 && pw <= NORM_PART_MAX) { np_wo.out = m->npart_b; np_w13.in = m->npart_b; np_w13.n_in = pw; }
             n_part_x = 0;
             if (p2 > 0 && p2 <= NORM_PART_MAX) { np_w2.out = m->npart_a; n_part_x = p2; }
         }
-        // (mailboxes: the first layer reads its row -- norm input and residual operand -- from the tagged inbox, the last layer's w2
-        //  stores its row into the next stage's inbox; everything in between is the usual schedule)
-        const MailboxIO *mbi = (has_mb_in && il == m->l0) ? &mb_first : nullptr, *mbo = (has_mb_out && il == m->l1 - 1) ? &mb_last : nullptr;
         if (use_qkvx) {
             HIP_TRY(launch_qkv_attn(L.qkv, xa, L.attention_norm, np_qkv, m->d_qkv2, m->d_sc2, m->d_epoch, il - m->l0, d, H, C, nth, m->sincos, Kl, Vl, nullptr,
                                     m->qa1_A, m->qa1_d, m->T_silu, m->T_exp, state, m->d_fault, st, mbi), LLAMAHIP_ERR_PREDICT);
@@ -794,11 +808,15 @@ int forward_decode(llamahip_model *m, const Pass &p, char *err, size_t err_cap) 
             HIP_TRY(launch_dec_attn(m->qkv, d, H, C, nth, m->sincos, Kl, Vl, m->sc, m->part, nullptr, m->qa1_A, m->qa1_d, m->T_exp, state, st, two_attn ? nullptr : m->d_attn_sync, m->d_fault, long_attn,
                                     pv_split ? m->d_pvx : nullptr, m->d_epoch, il - m->l0), LLAMAHIP_ERR_PREDICT);
         }
+        if (dot_wo) HIP_TRY(launch_q40_dot(L.wo, EPI_RESID, m->qa1_A, m->qa1_d, m->x1, xa, np_wo.out, NORM_PART_MAX, m->d_dot_count, st), LLAMAHIP_ERR_PREDICT);
+        else
         HIP_TRY(launch_gemv(L.wo, PRE_QA, EPI_RESID, m->qa1_A, m->qa1_d, nullptr, nullptr, m->x1, xa, m->T_silu, nullptr, nullptr, st, &np_wo, mbi), LLAMAHIP_ERR_PREDICT);
         if (m->w13_interleaved) {
             if (use_w13h) HIP_TRY(launch_gemv_silu_half(L.w13, m->x1, L.ffn_norm, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13, m->d_w13_amax, m->d_epoch, il - m->l0, m->d_fault), LLAMAHIP_ERR_PREDICT);
             else
             HIP_TRY(launch_gemv(L.w13, PREP_NORM, EPI_SILU_QA, nullptr, nullptr, m->x1, L.ffn_norm, nullptr, nullptr, m->T_silu, m->qa2_A, m->qa2_d, st, &np_w13), LLAMAHIP_ERR_PREDICT);
+            if (dot_w2) HIP_TRY(launch_q40_dot(L.w2, EPI_RESID, m->qa2_A, m->qa2_d, xo, m->x1, np_w2.out, NORM_PART_MAX, m->d_dot_count, st), LLAMAHIP_ERR_PREDICT);
+            else
             HIP_TRY(launch_gemv(L.w2, PRE_QA, EPI_RESID, m->qa2_A, m->qa2_d, nullptr, nullptr, mbo ? nullptr : xo, m->x1, m->T_silu, nullptr, nullptr, st, &np_w2, mbo), LLAMAHIP_ERR_PREDICT);
         } else {
             if (mbo) { set_err(err, err_cap, "pipeline mailboxes need the interleaved w1|w3 layout"); return LLAMAHIP_ERR_PREDICT; }
@@ -891,7 +909,7 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
             HIP_TRY(launch_add(m->tmp, m->x, m->x1, (long) N * d, st), LLAMAHIP_ERR_PREDICT);                                   // .mm:654
             if (!sink->put(10, m->x1, (int64_t) N * d)) goto dump_fail;
         } else {
-            HIP_TRY(launch_gemm(L.wo, EPI_RESID, m->qa_A, m->qa_d, N, m->x1, d, m->x, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(gemm_or_dot(m, !debug, L.wo, EPI_RESID, m->qa_A, m->qa_d, N, m->x1, d, m->x, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
         }
         HIP_TRY(launch_prep(PREP_NORM, m->x1, L.ffn_norm, d, 0, d, N, m->qa_A, m->qa_d, dmp ? m->dbg_y : nullptr, nullptr, m->T_silu, st), LLAMAHIP_ERR_PREDICT);        // .mm:660-665
         if (dmp && !sink->put(11, m->dbg_y, (int64_t) N * d)) goto dump_fail;
@@ -918,7 +936,7 @@ int forward_eval(llamahip_model *m, const Pass &p, char *err, size_t err_cap) {
             HIP_TRY(launch_add(m->tmp, m->x1, m->x, (long) N * d, st), LLAMAHIP_ERR_PREDICT);                                   // .mm:687
             if (!sink->put(16, m->x, (int64_t) N * d)) goto dump_fail;
         } else {
-            HIP_TRY(launch_gemm(L.w2, EPI_RESID, m->qa_A, m->qa_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
+            HIP_TRY(gemm_or_dot(m, !debug, L.w2, EPI_RESID, m->qa_A, m->qa_d, N, m->x, d, m->x1, d, st, m->qb_ws, fast_prefill, few), LLAMAHIP_ERR_PREDICT);
         }
     }
 
@@ -1037,7 +1055,9 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
         force_parts = opts->n_parts; layer_begin = opts->layer_begin; layer_end = opts->layer_end;
         device = opts->device; m->flags = opts->flags;
         if (opts->struct_size >= 28 && opts->n_seq > 0) m->n_seq = opts->n_seq;      // (28: the struct up to n_seq, as older callers pass it)
+        if (opts->struct_size >= (int32_t) (offsetof(llamahip_opts, fast_decode) + sizeof(opts->fast_decode))) m->fast_decode = opts->fast_decode;      // (a shorter struct: off)
     }
+    if (m->fast_decode != 0 && m->fast_decode != 1) { set_err(err, err_cap, "llamahip_opts.fast_decode %d: 0 (off) or 1 (K-split integer-dot wo / w2 on Q4_0 files)", m->fast_decode); return LLAMAHIP_ERR_LOAD; }
     std::string e;
     if (!m->file.open(path, n_ctx, force_parts, e)) { set_err(err, err_cap, "%s", e.c_str()); return LLAMAHIP_ERR_LOAD; }
     m->hp = m->file.hp;
@@ -1192,6 +1212,7 @@ static int model_load_impl(const char *path, int32_t n_ctx, const llamahip_opts 
         HIP_TRY(m->own.alloc(&m->d_pick, 128 + (size_t) V / 8 + 8, true), LLAMAHIP_ERR_LOAD);
         HIP_TRY(m->own.alloc(&m->npart_a, NORM_PART_MAX * 2, true), LLAMAHIP_ERR_LOAD);
         HIP_TRY(m->own.alloc(&m->npart_b, NORM_PART_MAX * 2, true), LLAMAHIP_ERR_LOAD);
+        if (m->fast_decode == 1) HIP_TRY(m->own.alloc(&m->d_dot_count, 1, true), LLAMAHIP_ERR_LOAD);
         // blocks past K/32 (padding up to a multiple of 256 columns) are never written again: keep them zero
         HIP_TRY(m->own.alloc_all({ { &m->qa1_A, Kp_d, true }, { &m->qa1_d, Kp_d / 32 * 4, true }, { &m->qa2_A, Kp_F, true }, { &m->qa2_d, Kp_F / 32 * 4, true } }), LLAMAHIP_ERR_LOAD);
     }
@@ -2129,7 +2150,7 @@ static int pipe_load(const char *path, int32_t n_ctx, const llamahip_opts *opts,
     if (base.flags & LLAMAHIP_FLAG_HOST_ONLY) { set_err(err, err_cap, "a device list and LLAMAHIP_FLAG_HOST_ONLY exclude each other"); return LLAMAHIP_ERR_LOAD; }
     // the front: file, vocab, hparams (the reader's validation and error messages, .mm:98-498), no device state
     llamahip_opts fo = base;
-    fo.struct_size = 28; fo.device = -1; fo.layer_begin = 0; fo.layer_end = -1; fo.flags = base.flags | LLAMAHIP_FLAG_HOST_ONLY;
+    fo.struct_size = (int32_t) sizeof(fo); fo.n_devices = 0; fo.device = -1; fo.layer_begin = 0; fo.layer_end = -1; fo.flags = base.flags | LLAMAHIP_FLAG_HOST_ONLY;
     llamahip_model *front = nullptr;
     int rc = model_load_impl(path, n_ctx, &fo, &front, err, err_cap);
     if (rc) return rc;
@@ -2149,7 +2170,7 @@ static int pipe_load(const char *path, int32_t n_ctx, const llamahip_opts *opts,
         th.emplace_back([&, s]() {
             char e[512] = "";
             llamahip_opts so = base;
-            so.struct_size = 28; so.device = devices[s];
+            so.struct_size = (int32_t) sizeof(so); so.n_devices = 0; so.device = devices[s];      // (whole: the stage handles inherit fast_decode)
             const int bq = L / S, rem = L % S;
             so.layer_begin = s * bq + std::min(s, rem);
             so.layer_end = so.layer_begin + bq + (s < rem ? 1 : 0);
@@ -5423,6 +5444,25 @@ int32_t llamahip_debug_q40_few_plan(int32_t m, int32_t k, int32_t n_rows, int64_
 }
 
 int64_t llamahip_debug_q40_few_launches(void) { return g_q40_few_launches; }
+
+int32_t llamahip_debug_q40_dot_plan(int32_t m, int32_t k, int64_t out[5]) {
+    if (!out) return 0;
+    const Q40DotPlan p = q40_dot_plan(m, k);
+    if (!p.ok) return 0;
+    const int64_t o[5] = { p.slices, p.threads, p.grid, p.lds, p.applies };
+    for (int i = 0; i < 5; i++) out[i] = o[i];
+    return 1;
+}
+
+int64_t llamahip_debug_q40_dot_launches(const llamahip_model *model) {
+    if (!model) return g_q40_dot_launches;
+    int64_t n = 0;
+    for (const llamahip_model *h : model->stages) n += llamahip_debug_q40_dot_launches(h);
+    unsigned long long v = 0;
+    if (model->d_dot_count && hipSetDevice(model->device) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+        hipMemcpy(&v, model->d_dot_count, sizeof(v), hipMemcpyDeviceToHost) == hipSuccess) n += (int64_t) v;
+    return n;
+}
 
 int32_t llamahip_debug_dense_mfma_plan(int32_t m, int32_t k, int32_t wtype, int32_t n_rows, int64_t out[6]) {
     if (!out) return 0;

@@ -6,6 +6,7 @@
 
 #include "dec_attn_plan.h"
 #include "flash_attn_plan.h"
+#include "q40_dot_plan.h"
 #include "q40_few_plan.h"
 #include "q41_plan.h"
 #include "set_plan.h"
@@ -242,6 +243,12 @@ hipError_t launch_gemm(const QMat &w, int epi, const uint32_t *qa_A, const float
 // counts in g_q40_few_launches, NOT in g_gemm_path_counts
 hipError_t launch_q40_few(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, int N,
                           float *y, long y_stride, const float *resid, long resid_stride, hipStream_t st);
+// k_q40_dot (q40_dot.hip; plan and counter: q40_dot_plan.h): one operand row against the tile copy, EPI_STORE / EPI_RESID, and -- part_out
+// set -- the {sum y, sum y^2} pair of each workgroup's rows (q40_dot_plan(M, K).grid of them, refused above part_cap) for a PREP_NORMP
+// prologue.  count: a device word the launch adds one to (a handle's counter: graph replays count themselves), or null; every call counts
+// in g_q40_dot_launches.  What a llamahip_opts.fast_decode = 1 handle launches for wo and w2 of a single-token step where the plan `applies`.
+hipError_t launch_q40_dot(const QMat &w, int epi, const uint32_t *qa_A, const float *qa_d, float *y, const float *resid,
+                          double *part_out, int part_cap, unsigned long long *count, hipStream_t st);
 // ONE kernel family of launch_gemm, forced whatever its selection rule would pick (llamahip_op_prompt_gemm_q4_0: per-op tests of every
 // prompt GEMM).  The path values are LLAMAHIP_GEMM_* of llamahip.h; EPI_STORE / EPI_RESID only.  A family that cannot take the matrix
 // (its copy is missing) or the shape is refused with hipErrorInvalidValue and the limit in *why; nothing is launched then.  Counts as

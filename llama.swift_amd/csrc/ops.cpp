@@ -510,6 +510,36 @@ int llamahip_op_mul_mat_q4_0_few(const void *w_q4_0, int32_t M, int32_t K, const
     return LLAMAHIP_OK;
 }
 
+// the opt-in K-split integer-dot mat-vec of Q4_0 files (launch_prep + k_q40_dot) on caller-supplied operands: see llamahip.h
+int llamahip_op_gemv_q4_0_dot(const void *w_q4_0, int32_t M, int32_t K, const float *x, const float *resid,
+                              float *y, int32_t y_cap, double *parts, int32_t parts_cap, char *err, size_t err_cap) {
+    static const char *fn = "llamahip_op_gemv_q4_0_dot";
+    if (q40_dot_op_check(w_q4_0, M, K, x, y, y_cap, parts, parts_cap, err, err_cap)) return LLAMAHIP_ERR_PREDICT;            // (q40_dot_plan.cpp: host-only)
+    if (need_device(err, err_cap)) return LLAMAHIP_ERR_PREDICT;
+    HIP_TRY(init_kernel_attrs(), LLAMAHIP_ERR_PREDICT);
+    QMat q;
+    q.set_shape(M, K);
+    const size_t Kp = (size_t) q.Kp();
+    Scratch s;
+    hipStream_t st = s.stream();
+    uint8_t *d_w = s.alloc((size_t) M * (K / 32) * 20, (const uint8_t *) w_q4_0);
+    q.tiles = s.alloc<uint8_t>(q.bytes());
+    float *d_x = s.alloc((size_t) K, x);
+    float *d_y = s.alloc((size_t) y_cap, y);                        // (the floats behind M keep the caller's bits)
+    double *d_p = s.alloc((size_t) parts_cap * 2, parts);           // (... and the pairs behind the grid)
+    float *d_r = resid ? s.alloc((size_t) M, resid) : nullptr;
+    uint32_t *d_qA = s.alloc<uint32_t>(Kp / 4);
+    float *d_qd = s.alloc<float>(Kp / 32);
+    if (s.ok()) s.check(launch_repack(d_w, q.tiles, M, K, 0, 0, st));
+    if (s.ok()) s.check(launch_prep(PREP_PLAIN, d_x, nullptr, K, 0, K, 1, d_qA, d_qd, nullptr, nullptr, nullptr, st));
+    if (s.ok()) s.check(launch_q40_dot(q, resid ? EPI_RESID : EPI_STORE, d_qA, d_qd, d_y, d_r, d_p, parts_cap, nullptr, st));
+    s.download(y, d_y, (size_t) y_cap * 4);
+    s.download(parts, d_p, (size_t) parts_cap * 16);
+    s.sync();
+    if (!s.ok()) return s.fail(fn, err, err_cap);
+    return LLAMAHIP_OK;
+}
+
 // one layer's attention on caller-supplied q|k|v rows and K / V caches, kernels chosen by the caller (per-op tests): see llamahip.h
 int llamahip_op_attention(const float *qkv, int32_t N, int32_t d, int32_t H, int32_t n_past, int32_t n_ctx, float *Kc, float *Vc,
                           int32_t n_threads, int32_t chunk, int32_t path, int32_t ws_rows, float *merged, int32_t merged_stride,

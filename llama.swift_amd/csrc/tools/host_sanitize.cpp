@@ -21,6 +21,7 @@
 #include "../../../include/llamahip.h"
 #include "../dev_owner.h"
 #include "../model_file.h"
+#include "../q40_dot_plan.h"
 #include "../q40_few_plan.h"
 #include "../q41_plan.h"
 #include "../set_plan.h"
@@ -1870,6 +1871,30 @@ int main(int argc, char **argv) {
         }
         EXPECT(q40_few_op_check(&wq, 8, 32, &xy, 63, &xy, 8, err, sizeof(err)) == 0);
         printf("host_sanitize: Q4_0 few-row mat-mul host half: %d plans, %zu refusals\n", few_plans, sizeof(wbad) / sizeof(wbad[0]));
+        // the opt-in K-split integer-dot mat-vec of Q4_0 files (q40_dot_plan.cpp): every shape above -- a grid that covers M, the slices by M
+        // alone, the row's LDS, `applies` never above the hand-off's pairs -- and llamahip_op_gemv_q4_0_dot's refusals
+        int dot1_plans = 0;
+        for (auto &mk : shapes) {
+            const int M = mk.first, K = mk.second;
+            const Q40DotPlan p = q40_dot_plan(M, K);
+            EXPECT(p.ok && p.slices == (M <= 8192 ? 8 : 4) && p.threads == 64 * p.slices && (int64_t) p.grid * 16 >= M && (int64_t) (p.grid - 1) * 16 < M);
+            EXPECT(p.lds == (K + 255) / 256 * 288 + 512 && p.lds <= Q40_DOT_MAX_LDS && (!p.applies || p.grid <= Q40_DOT_MAX_PARTS));
+            dot1_plans++;
+        }
+        EXPECT(!q40_dot_plan(0, 64).ok && !q40_dot_plan(8, 48).ok && !q40_dot_plan(8, 0).ok && !q40_dot_plan(8, 256 * 200).ok);
+        const double pr[2] = { 0, 0 };
+        struct { int32_t M, K, yc, pc; const void *w; const char *says; } dbad1[] = {
+            { 8, 48, 8, 1, &wq, "K 48 must be a positive multiple of 32" }, { 0, 64, 8, 1, &wq, "M 0 must be >= 1" }, { 8, 64, 7, 1, &wq, "y_cap 7 < M 8" },
+            { 17, 64, 17, 1, &wq, "parts_cap 1 < 2 pairs" }, { 8, 256 * 200, 8, 1, &wq, "bytes of LDS" }, { 8, 64, 8, 1, nullptr, "not NULL" },
+        };
+        for (auto &b : dbad1) {
+            std::vector<char> e(256, 0), e1(1, 'x');
+            EXPECT(q40_dot_op_check(b.w, b.M, b.K, &xy, &xy, b.yc, pr, b.pc, e.data(), e.size()) == -1 && strstr(e.data(), b.says));
+            EXPECT(q40_dot_op_check(b.w, b.M, b.K, &xy, &xy, b.yc, pr, b.pc, e1.data(), e1.size()) == -1 && e1[0] == 0);
+            EXPECT(q40_dot_op_check(b.w, b.M, b.K, &xy, &xy, b.yc, pr, b.pc, nullptr, 0) == -1);
+        }
+        EXPECT(q40_dot_op_check(&wq, 8, 32, &xy, &xy, 8, pr, 1, err, sizeof(err)) == 0);
+        printf("host_sanitize: Q4_0 dot mat-vec host half: %d plans, %zu refusals\n", dot1_plans, sizeof(dbad1) / sizeof(dbad1[0]));
     }
     {   // the few-row Q4_0 mat-mul's host half (set_plan.cpp): the plan of every LLaMA matrix at every row count 2 .. 60 and its launch shape,
         // every (nc, cw) pair forced -- admitted or refused with a reason, on exactly sized message buffers -- and what the rule refuses
